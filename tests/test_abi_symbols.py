@@ -38,7 +38,7 @@ def test_library_exports_every_declared_symbol(P):
     assert lib.ppo_abi_version() == P.binding.ABI_VERSION == 5
 
 
-def test_struct_mirrors_match_header(P):
+def test_struct_mirrors_match_header(P, tmp_path):
     # compile a probe against the header and compare sizeof / offsetof with the ctypes mirrors
     probe = r'''
 #include <stdio.h>
@@ -50,7 +50,7 @@ int main(void) {
          sizeof(ppo_profile), offsetof(ppo_profile, allreduce_ms), offsetof(ppo_profile, vector_fallback_launches));
   return 0;
 }'''
-    exe = "/tmp/ppo_abi_probe"
+    exe = str(tmp_path / "ppo_abi_probe")
     subprocess.run(["gcc", "-x", "c", "-I", os.path.join(ROOT, "include"), "-o", exe, "-"], input=probe.encode(), check=True)
     got = [int(x) for x in subprocess.check_output([exe]).split()]
     Cfg, St, Pr = P.binding.Config, P.binding.Stats, P.binding.Profile

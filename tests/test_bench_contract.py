@@ -58,7 +58,7 @@ R06 = sorted(p for p in glob.glob(os.path.join(ROOT, "profiles", "r06_v*_bench.j
 
 @pytest.mark.parametrize("path", R06, ids=[os.path.basename(p) for p in R06])
 def test_round6_default_line_carries_the_other_workloads_and_the_repeats(path):
-    """The driver's default command (`python bench.py --gpus 1 --steps K --warmup W`) times configs[1] as `value` -- and, in the same run, repeats that K-step region
+    """The round-6 default command (`python bench.py --gpus 1 --steps K --warmup W`, what `--full` produces now) times configs[1] as `value` -- and, in the same run, repeats that K-step region
     (`value_runs`: median / min / max) and times BASELINE configs[3] and one GPU's share of configs[4] live for >= 0.5 s each (`other_workloads`), so that those numbers
     are driver-observed and not only builder-run lines under profiles/."""
     d = json.loads(open(path).read().strip().splitlines()[-1])

@@ -12,7 +12,7 @@ OUT=/tmp/collect_$TAG
 KEEP=$ROOT/gpurun_out/$TAG
 rm -rf "$OUT"
 mkdir -p "$OUT" "$KEEP" "$ROOT/profiles"
-BENCH="python3 $ROOT/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-other-workloads --repeats 0"   # the headline workload alone under the tracer / the counters
+BENCH="python3 $ROOT/bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-other-workloads --repeats 0"   # the headline workload alone under the tracer / the counters
 
 rocprofv3 --kernel-trace --stats -f csv -d "$OUT/trace" -o run -- $BENCH > "$OUT/trace.log" 2>&1
 cp "$(find "$OUT/trace" -name '*kernel_stats.csv' | head -n 1)" "$ROOT/profiles/${TAG}_kernel_stats.csv"
@@ -62,10 +62,10 @@ python3 $ROOT/tests/test_gpu_curves.py > "$ROOT/profiles/${TAG}_curves.json" 2> 
 # what ties this set to the binary: the fingerprint of the sources it was built from (bench.py quotes a set only while it matches)
 python3 $ROOT/tools/src_fingerprint.py --meta "$TAG" > "$OUT/meta.txt"
 # the judged bench lines LAST: they quote this set (traffic, in-trace durations, floor, curves), which exists and is tied only now
-python3 $ROOT/bench.py --steps 20 --warmup 3 > "$OUT/bench.json" 2> "$OUT/bench.err"
+python3 $ROOT/bench.py --steps 20 --warmup 3 --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 tail -n 1 "$OUT/bench.json" > "$ROOT/profiles/${TAG}_bench.json"
-python3 $ROOT/bench.py --workload config4 --no-cpu-baseline > "$OUT/bench_c4.json" 2> "$OUT/bench_c4.err" && tail -n 1 "$OUT/bench_c4.json" > "$ROOT/profiles/${TAG}_bench_default_config4.json" || echo "config4 bench FAILED"
-python3 $ROOT/bench.py --workload mountaincar --no-cpu-baseline > "$OUT/bench_mc.json" 2> "$OUT/bench_mc.err" && tail -n 1 "$OUT/bench_mc.json" > "$ROOT/profiles/${TAG}_bench_default_mountaincar.json" || echo "mountaincar bench FAILED"
+python3 $ROOT/bench.py --workload config4 --full --no-cpu-baseline > "$OUT/bench_c4.json" 2> "$OUT/bench_c4.err" && tail -n 1 "$OUT/bench_c4.json" > "$ROOT/profiles/${TAG}_bench_default_config4.json" || echo "config4 bench FAILED"
+python3 $ROOT/bench.py --workload mountaincar --full --no-cpu-baseline > "$OUT/bench_mc.json" 2> "$OUT/bench_mc.err" && tail -n 1 "$OUT/bench_mc.json" > "$ROOT/profiles/${TAG}_bench_default_mountaincar.json" || echo "mountaincar bench FAILED"
 cp "$ROOT"/profiles/${TAG}_* "$KEEP/"
 cp "$OUT"/*.log "$OUT"/*.txt "$OUT"/*.err "$OUT"/*.json "$KEEP/" 2>/dev/null || true
 echo done

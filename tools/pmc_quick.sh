@@ -8,7 +8,7 @@ OUT=$ROOT/gpurun_out/$TAG; mkdir -p "$OUT"
 i=0
 for set in "$@"; do
     i=$((i + 1))
-    rocprofv3 --pmc $set -f csv -d "$OUT/pmc$i" -o run -- python3 $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --profile 0 > "$OUT/pmc$i.log" 2>&1 || echo "pass $i failed"
+    rocprofv3 --pmc $set -f csv -d "$OUT/pmc$i" -o run -- python3 $ROOT/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --profile 0 > "$OUT/pmc$i.log" 2>&1 || echo "pass $i failed"
 done
 python3 $ROOT/tools/pmc_summary.py "$OUT/summary.json" "$OUT"/pmc* > "$OUT/summary.txt"
 python3 - "$OUT/summary.json" <<'PY'

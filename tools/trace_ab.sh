@@ -9,7 +9,7 @@ for i in $(seq 1 $R); do
         export PPO_HIP_LIBRARY="$(realpath "$src")"
         D=/tmp/trace_ab_${i}_$(basename $src)
         rm -rf $D
-        rocprofv3 --kernel-trace --stats -f csv -d $D -o run -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-other-workloads --repeats 0 > $D.out 2>&1
+        rocprofv3 --kernel-trace --stats -f csv -d $D -o run -- python3 bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-other-workloads --repeats 0 > $D.out 2>&1
         python3 - "$D" "$PAT" "$src" <<'PY'
 import csv, glob, re, sys
 d, pat, src = sys.argv[1:4]
