@@ -35,7 +35,12 @@ enum { PPO_OK = 0, PPO_ERR_INVALID = 1, PPO_ERR_HIP = 2, PPO_ERR_STATE = 3, PPO_
 
 /* PPO_ENV_SYNTHETIC: the synthetic env of BASELINE configs[4] (obs ~ N(0,1) of any width, reward ~ U(-1,1), done ~ Bernoulli(0.01), random
  * action masks); it is the env with which networks other than the reference's 2 x 64 (hidden / n_hidden) are accepted. */
-enum { PPO_ENV_CARTPOLE = 0, PPO_ENV_MOUNTAINCAR = 1, PPO_ENV_SYNTHETIC = 2 };
+/* PPO_ENV_HOST: the CALLER owns the environments and steps them on the host (the reference's custom-environment framework: any class with reset(),
+ * step(action), episode_length and episode_reward in PPO_Discrete::m_envs, PPO_Discrete.cpp:365-483); the context owns everything else.  Driven by the
+ * ppo_host_* calls ("Caller-stepped environments" below); ppo_rollout / ppo_train_iteration / ppo_env_reset / ppo_env_step return PPO_ERR_UNSUPPORTED.
+ * obs_size is not checked against any env.  The reference's network (2 x 64, f32) with obs_size 2, 4 or 8 runs on the reference-shape kernels, every
+ * other network (and compute_dtype) on the generic engine with PPO_ENV_SYNTHETIC's limits. */
+enum { PPO_ENV_CARTPOLE = 0, PPO_ENV_MOUNTAINCAR = 1, PPO_ENV_SYNTHETIC = 2, PPO_ENV_HOST = 3 };
 /* PPO_DIST_CATEGORICAL reproduces Distributions/Categorical.cpp including its entropy clamp (:112-119);
  * PPO_DIST_MASKED reproduces Distributions/CategoricalMasked.cpp (true entropy, -1e8 masking). */
 enum { PPO_DIST_CATEGORICAL = 0, PPO_DIST_MASKED = 1 };
@@ -48,7 +53,7 @@ enum { PPO_DTYPE_F32 = 0, PPO_DTYPE_BF16 = 1 };
 typedef struct ppo_config {
     int32_t struct_size;        /* = sizeof(ppo_config) */
     int32_t device;             /* HIP device ordinal (reference: use_cuda -> torch::kCUDA, PPO_Discrete.cpp:65) */
-    int32_t env_kind;           /* PPO_ENV_* : PPO_Discrete owns CartPole, PPO_MultiDiscrete owns MountainCar */
+    int32_t env_kind;           /* PPO_ENV_* : PPO_Discrete owns CartPole, PPO_MultiDiscrete owns MountainCar, PPO_ENV_HOST: the caller's envs */
     int32_t dist_kind;          /* PPO_DIST_* */
     int32_t obs_size;           /* [environment] obs_size */
     int32_t n_heads;            /* Agent::m_actionSpace.size() (Agent.cpp:21) */
@@ -322,6 +327,43 @@ PPO_API ppo_status ppo_stats_snapshot(ppo_ctx* ctx);
 PPO_API ppo_status ppo_stats_snapshot_read(ppo_ctx* ctx, ppo_stats* out);
 /* LR anneal (:514-518) is applied by ppo_train_iteration; direct control for tests. */
 PPO_API ppo_status ppo_set_learning_rate(ppo_ctx* ctx, double lr);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Caller-stepped environments (PPO_ENV_HOST contexts; PPO_Discrete::initEnvs / stepEnvs / train, PPO_Discrete.cpp:365-483, 511-548)
+ *
+ *   ppo_host_env_reset(ctx, obs0)                                    once: every env's reset observation
+ *   per iteration:  ppo_host_rollout_begin(ctx)
+ *                   T x { ppo_host_act(ctx, mask, actions); step the envs on the host; ppo_host_observe(ctx, obs, reward, done, fin_len, fin_rew) }
+ *                   ppo_host_rollout_end(ctx)                        enqueues the values, the scan and the update (ppo_stats_snapshot / ppo_read_stats as usual)
+ *
+ * Arithmetic: that of a device-env context of the same shape.  The sampler key is (seed, env_offset + row, rollout_steps + t, head); for the
+ * reference's shapes the actor runs rollout16_kernel's products (policy_act16_kernel) or, under PPO_KERNEL_ROLLOUT_VECTOR, the vector form, chosen
+ * ONCE per rollout at ppo_host_rollout_begin from the same weight-range snapshot as ppo_rollout (weights outside fp16 send the whole rollout to the
+ * vector form, counted in ppo_profile.vector_fallback_launches); values are one batched launch at ppo_host_rollout_end, as ppo_rollout's tail.  A
+ * host-stepped CartPole reproduces ppo_train_iteration bit for bit (tests/test_gpu_host_env.py).
+ * One launch per env step: ppo_host_act commits the step ppo_host_observe staged and acts on the next one in one kernel and waits for that kernel
+ * only; ppo_host_observe copies into pinned staging and launches nothing.
+ * Errors: the ppo_host_* calls return PPO_ERR_STATE on a context with a device env and out of sequence (act twice without observe, observe
+ * before act, end before T steps, begin while a rollout is open); such a call changes nothing.
+ * ------------------------------------------------------------------------------------------------------- */
+/* initEnvs (PPO_Discrete.cpp:365-402) for caller-stepped envs: obs_h f32 [N,O] (host) = every env's reset observation.
+ * NEXT_OBS = obs_h, NEXT_DONE = 0, per-env episode sums = 0.  Synchronous. */
+PPO_API ppo_status ppo_host_env_reset(ppo_ctx* ctx, const float* obs_h);
+/* Opens the rollout of one iteration: the LR anneal ppo_train_iteration applies (:514-518); t = 0. */
+PPO_API ppo_status ppo_host_rollout_begin(ppo_ctx* ctx);
+/* Step t of :524-548: m_obs[t] = next_obs, m_dones[t] = next_done, actor forward + sample, m_actions[t], m_logprobs[t] (and masks [t]);
+ * mask_h u8 [N,A] or NULL (masked policies; NULL = all valid); returns when action_h i64 [N,H] (host) holds the actions. */
+PPO_API ppo_status ppo_host_act(ppo_ctx* ctx, const uint8_t* mask_h, int64_t* action_h);
+/* stepEnvs' outputs for step t (:413-483): next_obs_h [N,O] (already the reset observation where done), reward_h f32 [N], done_h i32 [N]
+ * (truncation included).  fin_len_h i32 [N] / fin_rew_h f32 [N]: the length and reward of the episodes that finished, as the reference reads
+ * them from env->episode_length / episode_reward (:474-480), read where done only (a length of 0 is not counted as an episode).  NULL = the
+ * context keeps them as running sums (steps counted, rewards summed), which is what CartPole and MountainCar report.  The data is copied
+ * before the call returns. */
+PPO_API ppo_status ppo_host_observe(ppo_ctx* ctx, const float* next_obs_h, const float* reward_h, const int32_t* done_h, const int32_t* fin_len_h,
+                                    const float* fin_rew_h);
+/* After T act/observe pairs: values of every stored observation and the bootstrap value (:280), the scan, the update: the rest of
+ * ppo_train_iteration.  Enqueued; rollout_steps += T, global_step += T * global_num_envs, finished episodes pending, as after ppo_rollout. */
+PPO_API ppo_status ppo_host_rollout_end(ppo_ctx* ctx);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Measurement (new; the reference only has a wall clock around each update, PPO_Discrete.cpp:650-652)

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PPO_HIP_LIBRARY") or os.path.join(_HERE, "libppo_hip.so")
 
 MAX_HEADS = 8
-ENV_CARTPOLE, ENV_MOUNTAINCAR, ENV_SYNTHETIC = 0, 1, 2
+ENV_CARTPOLE, ENV_MOUNTAINCAR, ENV_SYNTHETIC, ENV_HOST = 0, 1, 2, 3
 MM_EPI_NONE, MM_EPI_BIAS, MM_EPI_BIAS_TANH, MM_EPI_DTANH = 0, 1, 2, 3
 MM_F32X3, MM_BF16 = 0, 1
 DIST_CATEGORICAL, DIST_MASKED = 0, 1
@@ -46,6 +46,7 @@ ABI_SYMBOLS = [
     "ppo_read_stats", "ppo_set_learning_rate", "ppo_profile_enable", "ppo_profile_read", "ppo_comm_unique_id", "ppo_comm_init",
     "ppo_comm_init_local", "ppo_comm_exchange_handle", "ppo_comm_init_exchange", "ppo_comm_exchange_timeouts",
     "ppo_comm_set_wait_limit", "ppo_stats_snapshot", "ppo_stats_snapshot_read",
+    "ppo_host_env_reset", "ppo_host_rollout_begin", "ppo_host_act", "ppo_host_observe", "ppo_host_rollout_end",
 ]
 
 
@@ -306,6 +307,35 @@ class Context:
         r, k = np.empty(self.N, np.float32), np.empty(self.N, np.int32)
         _check(lib().ppo_env_get_state_h(self.h, *(x.ctypes.data_as(C.c_void_p) for x in (s, l, r, k))), self.h)
         return s, l, r, k
+
+    # ---- caller-stepped environments (ENV_HOST contexts: include/ppo_hip.h ppo_host_*)
+    def host_env_reset(self, obs):
+        """initEnvs for the caller's envs: obs f32 [N,O] = every env's reset observation."""
+        obs = np.ascontiguousarray(obs, np.float32).reshape(self.N, self.O)
+        _check(lib().ppo_host_env_reset(self.h, obs.ctypes.data_as(C.c_void_p)), self.h)
+
+    def host_rollout_begin(self):
+        _check(lib().ppo_host_rollout_begin(self.h), self.h)
+
+    def host_act(self, mask=None):
+        """Step t of the rollout: returns the sampled actions i64 [N,H] (host)."""
+        out = np.empty((self.N, self.H), np.int64)
+        m = np.ascontiguousarray(mask, np.uint8).reshape(self.N, self.A) if mask is not None else None
+        _check(lib().ppo_host_act(self.h, m.ctypes.data_as(C.c_void_p) if m is not None else None, out.ctypes.data_as(C.c_void_p)), self.h)
+        return out
+
+    def host_observe(self, obs, reward, done, fin_len=None, fin_rew=None):
+        """The caller's envs' outputs for the step just acted on (obs already the reset observation where done; done includes truncation)."""
+        o = np.ascontiguousarray(obs, np.float32).reshape(self.N, self.O)
+        r = np.ascontiguousarray(reward, np.float32).reshape(self.N)
+        d = np.ascontiguousarray(done, np.int32).reshape(self.N)
+        fl = np.ascontiguousarray(fin_len, np.int32).reshape(self.N) if fin_len is not None else None
+        fr = np.ascontiguousarray(fin_rew, np.float32).reshape(self.N) if fin_rew is not None else None
+        _check(lib().ppo_host_observe(self.h, *(x.ctypes.data_as(C.c_void_p) if x is not None else None for x in (o, r, d, fl, fr))), self.h)
+
+    def host_rollout_end(self):
+        """Values, advantages and the update of the rollout (enqueued)."""
+        _check(lib().ppo_host_rollout_end(self.h), self.h)
 
     # ---- rollout / advantages / update
     def rollout(self, forced_actions=None):

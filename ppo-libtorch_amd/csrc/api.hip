@@ -182,6 +182,20 @@ struct ppo_ctx {
     bool wr_in_update = false;                 // rollout / update / stand-alone step, not per launch (an update moves a weight by less than 40 lr: the thresholds' margin)
     int64_t vector_fallback_launches = 0;   // launches that took a vector kernel because a weight did not fit fp16 (ppo_profile.vector_fallback_launches)
     unsigned long long* stamps = nullptr;  // [2][12] phase cycles of the diagnostic kernel variant
+    // caller-stepped envs (PPO_ENV_HOST: ppo_host_*).  The staging block is pinned host memory the GPU can read: ppo_host_observe copies the caller's step
+    // outputs into it (no launch), the next launch commits them reading the block in place (measured faster than one async copy of it ahead of every
+    // launch at N = 256 .. 16384: DESIGN.md section 6a).  Layout: [obs N*O f32 | reward N f32 | done N i32 | fin_len N i32 | fin_rew N f32 | mask N*A u8]
+    bool host_env = false;
+    int host_phase = 0;               // 0: no rollout open, 1: ppo_host_act is next, 2: ppo_host_observe is next
+    int host_t = 0;                   // steps acted on in the open rollout
+    bool host_staged = false;         // step host_t - 1 is staged and not committed yet
+    bool host_fin_given = false;
+    bool host_as16 = false;           // rollout16_kernel's arithmetic for the whole open rollout (decided by ppo_host_rollout_begin)
+    unsigned char* host_stage = nullptr;       // hipHostMalloc'ed, mapped
+    unsigned char* host_stage_dev = nullptr;   // the device's address of the same bytes
+    size_t host_stage_bytes = 0;
+    int64_t* host_act = nullptr;               // i64 [N,H] actions, pinned and mapped: the act kernel writes them with plain stores
+    int64_t* host_act_dev = nullptr;
     GenericCtx* gen = nullptr;       // non-null: synthetic env / network other than 2 x 64 (generic.hpp); every L-dependent entry point dispatches on it
     uint8_t* cur_mask = nullptr;     // generic path: action mask of the observation in NEXT_OBS, [N, A]
     bool force_collectives = false;  // PPO_COMM_SELFTEST: world == 1 but the multi-rank path (RCCL included) is taken
@@ -396,6 +410,8 @@ extern "C" void ppo_ctx_destroy(ppo_ctx* c) {
     if (c->gen) { delete c->gen; c->gen = nullptr; }
     for (void* p : c->allocs) (void)hipFree(p);
     if (c->adam_coefs_h) (void)hipHostFree(c->adam_coefs_h);
+    if (c->host_stage) (void)hipHostFree(c->host_stage);
+    if (c->host_act) (void)hipHostFree(c->host_act);
     if (c->wr_host) (void)hipHostFree(c->wr_host);
     if (c->snap) (void)hipHostFree(c->snap);
     for (hipEvent_t e : c->snap_ev) if (e) (void)hipEventDestroy(e);
@@ -413,14 +429,19 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
     if (!cfg || !out) return fail(nullptr, PPO_ERR_INVALID, "null argument");
     *out = nullptr;
     if (cfg->struct_size != (int32_t)sizeof(ppo_config)) return fail(nullptr, PPO_ERR_INVALID, "ppo_config.struct_size %d != %zu", cfg->struct_size, sizeof(ppo_config));
-    const bool generic = cfg->env_kind == PPO_ENV_SYNTHETIC;
+    // PPO_ENV_HOST: the caller's envs (ppo_host_*).  The reference's network (2 x 64, f32) at the observation widths the reference-shape kernels are built
+    // for runs on them; every other network on the generic engine, with PPO_ENV_SYNTHETIC's limits
+    const bool host_env = cfg->env_kind == PPO_ENV_HOST;
+    const bool host_ref = host_env && cfg->hidden == PPO_HIDDEN && cfg->n_hidden == 2 && cfg->compute_dtype == PPO_DTYPE_F32 &&
+                          (cfg->obs_size == 2 || cfg->obs_size == 4 || cfg->obs_size == 8);
+    const bool generic = cfg->env_kind == PPO_ENV_SYNTHETIC || (host_env && !host_ref);
     if (!generic && (cfg->hidden != PPO_HIDDEN || cfg->n_hidden != 2))
         return fail(nullptr, PPO_ERR_UNSUPPORTED, "only the reference architecture (2 hidden layers of 64, Agent.cpp:25-59) is built for the reference's "
                     "environments; got %d x %d (other shapes run with env_kind = PPO_ENV_SYNTHETIC)", cfg->n_hidden, cfg->hidden);
     if (generic && (cfg->hidden < 1 || cfg->hidden > 2048 || cfg->n_hidden < 1 || cfg->n_hidden > GEN_MAX_LAYERS - 1 || cfg->obs_size < 1 || cfg->obs_size > 8192))
         return fail(nullptr, PPO_ERR_UNSUPPORTED, "generic network out of range: hidden %d (1..2048), n_hidden %d (1..%d), obs %d (1..8192)", cfg->hidden,
                     cfg->n_hidden, GEN_MAX_LAYERS - 1, cfg->obs_size);
-    if (cfg->env_kind != PPO_ENV_CARTPOLE && cfg->env_kind != PPO_ENV_MOUNTAINCAR && cfg->env_kind != PPO_ENV_SYNTHETIC)
+    if (cfg->env_kind != PPO_ENV_CARTPOLE && cfg->env_kind != PPO_ENV_MOUNTAINCAR && cfg->env_kind != PPO_ENV_SYNTHETIC && cfg->env_kind != PPO_ENV_HOST)
         return fail(nullptr, PPO_ERR_INVALID, "unknown env_kind %d", cfg->env_kind);
     if (cfg->dist_kind != PPO_DIST_CATEGORICAL && cfg->dist_kind != PPO_DIST_MASKED) return fail(nullptr, PPO_ERR_INVALID, "unknown dist_kind %d", cfg->dist_kind);
     if (cfg->compute_dtype != PPO_DTYPE_F32 && cfg->compute_dtype != PPO_DTYPE_BF16) return fail(nullptr, PPO_ERR_INVALID, "unknown compute_dtype %d", cfg->compute_dtype);
@@ -428,7 +449,7 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
     if (cfg->compute_dtype == PPO_DTYPE_BF16 && !generic)
         return fail(nullptr, PPO_ERR_UNSUPPORTED, "compute_dtype = PPO_DTYPE_BF16 applies to networks whose layers are GEMMs (env_kind = PPO_ENV_SYNTHETIC); the reference's "
                     "2 x 64 networks always compute in f32");
-    const int env_obs = cfg->env_kind == PPO_ENV_CARTPOLE ? 4 : (cfg->env_kind == PPO_ENV_MOUNTAINCAR ? 2 : cfg->obs_size);
+    const int env_obs = cfg->env_kind == PPO_ENV_CARTPOLE ? 4 : (cfg->env_kind == PPO_ENV_MOUNTAINCAR ? 2 : cfg->obs_size);   // host / synthetic: no check
     if (cfg->obs_size != env_obs) {
         // the reference's runtime check in initEnvs (PPO_Discrete.cpp:370-375), same wording
         return fail(nullptr, PPO_ERR_INVALID,
@@ -519,6 +540,9 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
     c->use_mfma = A <= 4;   // the matrix-core update kernel folds heads of up to 4 logits; wider policies (2 x 64 nets) run the vector kernel
     // ppo_config.kernel_flags (include/ppo_hip.h): the only switch between kernels; nothing is read from the environment
     if (cfg->kernel_flags & PPO_KERNEL_UPDATE_VECTOR) c->use_mfma = false;
+    // the matrix-core update kernels (and their record packing) are built for the reference's observation widths 2 and 4; a caller-stepped env with 8
+    // observations trains on the vector update kernel (fwd_bwd_kernel), which serves 2, 4 and 8
+    if (!generic && c->O != 2 && c->O != 4) c->use_mfma = false;
     c->update_single_wave = (cfg->kernel_flags & PPO_KERNEL_UPDATE_ONE_WAVE) != 0;
     c->rollout_vector = (cfg->kernel_flags & PPO_KERNEL_ROLLOUT_VECTOR) != 0;
     c->max_blocks_per_net = 512;
@@ -554,6 +578,15 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
     CK(dalloc(c, &c->ring, 1));
     CK(dalloc(c, &c->scratch_obs, N * c->O));
     CK(dalloc(c, &c->stamps, 24));
+    if (host_env) {
+        c->host_env = true;
+        c->host_stage_bytes = ((size_t)N * c->O * 4 + 4 * N * 4 + N * (size_t)A + 15) / 16 * 16;
+        CK(hipHostMalloc(reinterpret_cast<void**>(&c->host_stage), c->host_stage_bytes, hipHostMallocMapped));
+        CK(hipHostGetDevicePointer(reinterpret_cast<void**>(&c->host_stage_dev), c->host_stage, 0));
+        std::memset(c->host_stage, 0, c->host_stage_bytes);
+        CK(hipHostMalloc(reinterpret_cast<void**>(&c->host_act), N * c->H * sizeof(int64_t), hipHostMallocMapped));
+        CK(hipHostGetDevicePointer(reinterpret_cast<void**>(&c->host_act_dev), c->host_act, 0));
+    }
     if (c->gen) {
         GenericCtx& g = *c->gen;
         const GenLayout& GL = g.L;
@@ -940,8 +973,15 @@ extern "C" ppo_status ppo_env_transition(int32_t env_kind, const float* state_in
     return launch_env_transition(env_kind, state_in, action, n, next_state, reward, terminated, (hipStream_t)stream) == hipSuccess ? PPO_OK : PPO_ERR_HIP;
 }
 
+// PPO_ENV_HOST: the entry points that step the context's own device env refuse, and say what to call instead
+static ppo_status host_env_refuses(ppo_ctx* c, const char* what) {
+    return fail(c, PPO_ERR_UNSUPPORTED, "%s steps the context's device environment, but this context's environments are the caller's (PPO_ENV_HOST): drive "
+                                        "them with ppo_host_env_reset, ppo_host_rollout_begin, ppo_host_act, ppo_host_observe and ppo_host_rollout_end", what);
+}
+
 extern "C" ppo_status ppo_env_reset(ppo_ctx* c) {
     NEED(c, c != nullptr, "null ctx");
+    if (c->host_env) return host_env_refuses(c, "ppo_env_reset");
     DeviceGuard dev_guard(c);
     if (c->gen) {   // synthetic env: memoryless, the observation of global step `rollout_steps` (0 after creation)
         HIPCHK(c, hipMemsetAsync(c->buf[PPO_BUF_EP_LEN], 0, (size_t)c->N * sizeof(int32_t), c->stream));
@@ -959,6 +999,7 @@ extern "C" ppo_status ppo_env_reset(ppo_ctx* c) {
 
 extern "C" ppo_status ppo_env_step(ppo_ctx* c, const int64_t* action, float* obs, float* reward, int32_t* done) {
     NEED(c, c && action && obs && reward && done, "null argument");
+    if (c->host_env) return host_env_refuses(c, "ppo_env_step");
     DeviceGuard dev_guard(c);
     if (c->gen) {   // synthetic env: one step at the context's global step counter (the action does not influence it)
         HIPCHK(c, gen_synthetic_step(c->gen->L, c->N, c->cfg.seed, c->cfg.env_offset, c->rollout_steps, c->cfg.max_episode_steps,
@@ -1060,6 +1101,7 @@ static inline OptGuard opt_guard(const ppo_ctx* c) {
 
 extern "C" ppo_status ppo_rollout(ppo_ctx* c, const int64_t* forced_actions) {
     NEED(c, c != nullptr, "null ctx");
+    if (c->host_env) return host_env_refuses(c, "ppo_rollout");
     DeviceGuard dev_guard(c);
     ppo_status s = consume_finished_episodes(c);
     if (s != PPO_OK) return s;
@@ -1642,17 +1684,211 @@ extern "C" ppo_status ppo_update(ppo_ctx* c) {
 }
 
 // One iteration of PPO_Discrete::train()'s loop (:511-659) without printing / checkpointing.
-extern "C" ppo_status ppo_train_iteration(ppo_ctx* c) {
-    NEED(c, c != nullptr, "null ctx");
-    DeviceGuard dev_guard(c);
+// frac = 1.0 - (update - 1.0) / num_updates; lr_now = frac * m_learning_rate  (:515-517), update is 1-based
+static void anneal_lr(ppo_ctx* c) {
     if (c->cfg.anneal_lr && c->num_updates_total > 0) {
-        // frac = 1.0 - (update - 1.0) / num_updates; lr_now = frac * m_learning_rate  (:515-517), update is 1-based
         const double frac = 1.0 - ((double)(c->updates + 1) - 1.0) / (double)c->num_updates_total;
         c->lr = frac * c->cfg.learning_rate;
     }
+}
+
+extern "C" ppo_status ppo_train_iteration(ppo_ctx* c) {
+    NEED(c, c != nullptr, "null ctx");
+    if (c->host_env) return host_env_refuses(c, "ppo_train_iteration");
+    DeviceGuard dev_guard(c);
+    anneal_lr(c);
     ppo_status s = ppo_rollout(c, nullptr);
     if (s != PPO_OK) return s;
     // NEXT_VALUE was produced by the rollout's epilogue with the same parameters: go straight to the scan
+    s = run_scan(c);
+    if (s != PPO_OK) return s;
+    return ppo_update(c);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Caller-stepped environments (PPO_ENV_HOST): the rollout of PPO_Discrete::train (:524-548) with the caller's envs stepped between the launches.
+// One launch per env step: ppo_host_act commits what ppo_host_observe staged for step t - 1 and acts on step t (launch_host_act); the host waits for
+// that launch only, to read the actions.  ppo_host_rollout_end commits step T - 1 and runs the rest of ppo_train_iteration.
+// ---------------------------------------------------------------------------------------------------------
+static ppo_status host_state(ppo_ctx* c, const char* what) {
+    if (!c->host_env)
+        return fail(c, PPO_ERR_STATE, "%s: this context steps its own device environment (env_kind %d); the ppo_host_* calls serve PPO_ENV_HOST contexts", what,
+                    c->cfg.env_kind);
+    return PPO_OK;
+}
+
+// the staged step and the rollout rows it lands in; t = the step about to be acted on (T at the end of the rollout)
+static HostStepArgs host_args(ppo_ctx* c, int t, bool act_stores) {
+    const size_t N = (size_t)c->N;
+    const unsigned char* st = c->host_stage_dev;
+    HostStepArgs h{};
+    h.st_obs = reinterpret_cast<const float*>(st);
+    h.st_rew = reinterpret_cast<const float*>(st + N * c->O * 4);
+    h.st_done = reinterpret_cast<const int32_t*>(st + N * c->O * 4 + N * 4);
+    h.st_fin_len = reinterpret_cast<const int32_t*>(st + N * c->O * 4 + 2 * N * 4);
+    h.st_fin_rew = reinterpret_cast<const float*>(st + N * c->O * 4 + 3 * N * 4);
+    h.commit = c->host_staged ? 1 : 0;
+    h.fin_given = c->host_fin_given ? 1 : 0;
+    const size_t prev = t > 0 ? (size_t)(t - 1) * N : 0;
+    h.rewards_prev = B_<float>(c, PPO_BUF_REWARDS) + prev;
+    h.fin_len_prev = B_<int32_t>(c, PPO_BUF_FIN_LEN) + prev;
+    h.fin_rew_prev = B_<float>(c, PPO_BUF_FIN_REW) + prev;
+    h.next_done = B_<int32_t>(c, PPO_BUF_NEXT_DONE);
+    h.next_obs = B_<float>(c, PPO_BUF_NEXT_OBS);
+    h.ep_len = B_<int32_t>(c, PPO_BUF_EP_LEN);
+    h.ep_rew = B_<float>(c, PPO_BUF_EP_REW);
+    if (act_stores) {
+        const size_t tn = (size_t)t * N;
+        h.obs_t = B_<float>(c, PPO_BUF_OBS) + tn * c->O;
+        h.dones_t = B_<float>(c, PPO_BUF_DONES) + tn;
+        h.masks_t = c->cfg.dist_kind == PPO_DIST_MASKED ? B_<uint8_t>(c, PPO_BUF_MASKS) + tn * c->A : nullptr;
+        h.actions_t = B_<int32_t>(c, PPO_BUF_ACTIONS) + tn * c->H;
+    }
+    return h;
+}
+static const uint8_t* host_stage_mask(ppo_ctx* c) {
+    const size_t N = (size_t)c->N;
+    return c->host_stage_dev + N * c->O * 4 + 4 * N * 4;
+}
+
+// initEnvs (PPO_Discrete.cpp:365-402) for caller-stepped envs: obs_h f32 [N,O] = every env's reset observation
+extern "C" ppo_status ppo_host_env_reset(ppo_ctx* c, const float* obs_h) {
+    NEED(c, c != nullptr, "null ctx");
+    ppo_status s = host_state(c, "ppo_host_env_reset");
+    if (s != PPO_OK) return s;
+    if (c->host_phase != 0) return fail(c, PPO_ERR_STATE, "ppo_host_env_reset: a rollout is open (ppo_host_rollout_end first)");
+    NEED(c, obs_h != nullptr, "null argument");
+    DeviceGuard dev_guard(c);
+    HIPCHK(c, hipMemsetAsync(c->buf[PPO_BUF_NEXT_DONE], 0, (size_t)c->N * sizeof(int32_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->buf[PPO_BUF_EP_LEN], 0, (size_t)c->N * sizeof(int32_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->buf[PPO_BUF_EP_REW], 0, (size_t)c->N * sizeof(float), c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->buf[PPO_BUF_NEXT_OBS], obs_h, (size_t)c->N * c->O * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // obs_h is the caller's: consumed before return
+    return PPO_OK;
+}
+
+// Opens the rollout of one iteration: the LR anneal of ppo_train_iteration (:514-518), the finished episodes of the last rollout into the ring, and the
+// choice of arithmetic for the whole rollout from the same weight-range snapshot ppo_rollout takes
+extern "C" ppo_status ppo_host_rollout_begin(ppo_ctx* c) {
+    NEED(c, c != nullptr, "null ctx");
+    ppo_status s = host_state(c, "ppo_host_rollout_begin");
+    if (s != PPO_OK) return s;
+    if (c->host_phase != 0) return fail(c, PPO_ERR_STATE, "ppo_host_rollout_begin: a rollout is already open (%d of %d steps acted on)", c->host_t, c->T);
+    DeviceGuard dev_guard(c);
+    s = consume_finished_episodes(c);
+    if (s != PPO_OK) return s;
+    bool as16 = false;
+    if (!c->gen) {
+        as16 = !c->rollout_vector && policy_act16_serves(c->L);
+        if (as16) {
+            s = refresh_weight_range(c);
+            if (s != PPO_OK) return s;
+            wr_snapshot(c);
+            if (!weights_fit_rollout16(c)) { as16 = false; c->vector_fallback_launches += 1; }
+        }
+    }
+    anneal_lr(c);
+    c->host_as16 = as16;
+    c->host_phase = 1;
+    c->host_t = 0;
+    c->host_staged = false;
+    c->host_fin_given = false;
+    return PPO_OK;
+}
+
+// Step t of :524-548: commit step t - 1, then m_obs[t], m_dones[t], the actor forward + sample, m_actions[t], m_logprobs[t] (and masks [t]); returns
+// when action_h holds the actions
+extern "C" ppo_status ppo_host_act(ppo_ctx* c, const uint8_t* mask_h, int64_t* action_h) {
+    NEED(c, c != nullptr, "null ctx");
+    ppo_status s = host_state(c, "ppo_host_act");
+    if (s != PPO_OK) return s;
+    if (c->host_phase == 0) return fail(c, PPO_ERR_STATE, "ppo_host_act: no rollout is open (ppo_host_rollout_begin)");
+    if (c->host_phase == 2) return fail(c, PPO_ERR_STATE, "ppo_host_act: step %d was acted on and not observed (ppo_host_observe)", c->host_t - 1);
+    if (c->host_t >= c->T) return fail(c, PPO_ERR_STATE, "ppo_host_act: all %d steps of the rollout are taken (ppo_host_rollout_end)", c->T);
+    NEED(c, action_h != nullptr, "null argument");
+    DeviceGuard dev_guard(c);
+    const int t = c->host_t, N = c->N;
+    const bool masked = c->cfg.dist_kind == PPO_DIST_MASKED && mask_h != nullptr;
+    if (masked) std::memcpy(c->host_stage + (size_t)N * c->O * 4 + 4 * (size_t)N * 4, mask_h, (size_t)N * c->A);
+    const HostStepArgs h = host_args(c, t, true);
+    const uint8_t* mask = masked ? host_stage_mask(c) : nullptr;
+    const int64_t step = c->rollout_steps + t;
+    float* params = B_<float>(c, PPO_BUF_PARAMS);
+    if (c->gen) {
+        // generic engine: the commit in place of gen_synthetic_step, then gen_rollout's per-step sequence on the committed observation
+        GenericCtx& g = *c->gen;
+        if (h.commit) HIPCHK(c, launch_host_commit(h, N, c->O, c->stream));
+        s = gen_policy(c, B_<float>(c, PPO_BUF_NEXT_OBS), mask, nullptr, N, step, g.act64, g.step_lp, g.step_en);
+        if (s != PPO_OK) return s;
+        HIPCHK(c, gen_store_step(g.L, N, B_<float>(c, PPO_BUF_NEXT_OBS), mask, g.act64, g.step_lp, B_<int32_t>(c, PPO_BUF_NEXT_DONE), h.obs_t,
+                                 B_<uint8_t>(c, PPO_BUF_MASKS) + (size_t)t * N * c->A, h.actions_t, B_<float>(c, PPO_BUF_LOGPROBS) + (size_t)t * N, h.dones_t,
+                                 c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->host_act, g.act64, (size_t)N * c->H * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    } else {
+        HIPCHK(c, launch_host_act(params, c->L, c->cfg.dist_kind, mask, N, c->cfg.seed, c->cfg.env_offset, step, h, c->host_act_dev,
+                                  B_<float>(c, PPO_BUF_LOGPROBS) + (size_t)t * N, c->host_as16, c->error_flag, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // the one wait of a step: the actions
+    std::memcpy(action_h, c->host_act, (size_t)N * c->H * sizeof(int64_t));
+    c->host_staged = false;
+    c->host_t = t + 1;
+    c->host_phase = 2;
+    return PPO_OK;
+}
+
+// stepEnvs' outputs for step t (:413-483), staged for the next launch (host memory only: no launch)
+extern "C" ppo_status ppo_host_observe(ppo_ctx* c, const float* next_obs_h, const float* reward_h, const int32_t* done_h, const int32_t* fin_len_h,
+                                       const float* fin_rew_h) {
+    NEED(c, c != nullptr, "null ctx");
+    ppo_status s = host_state(c, "ppo_host_observe");
+    if (s != PPO_OK) return s;
+    if (c->host_phase != 2) return fail(c, PPO_ERR_STATE, "ppo_host_observe: no step awaits its observation (ppo_host_act first)");
+    NEED(c, next_obs_h && reward_h && done_h, "null argument");
+    NEED(c, (fin_len_h == nullptr) == (fin_rew_h == nullptr), "fin_len_h and fin_rew_h: both or neither");
+    const size_t N = (size_t)c->N;
+    unsigned char* st = c->host_stage;
+    std::memcpy(st, next_obs_h, N * c->O * 4);
+    std::memcpy(st + N * c->O * 4, reward_h, N * 4);
+    std::memcpy(st + N * c->O * 4 + N * 4, done_h, N * 4);
+    if (fin_len_h) {
+        std::memcpy(st + N * c->O * 4 + 2 * N * 4, fin_len_h, N * 4);
+        std::memcpy(st + N * c->O * 4 + 3 * N * 4, fin_rew_h, N * 4);
+    }
+    c->host_fin_given = fin_len_h != nullptr;
+    c->host_staged = true;
+    c->host_phase = 1;
+    return PPO_OK;
+}
+
+// After T act / observe pairs: commit step T - 1, the values of every stored observation and the bootstrap value (:280) in one batched launch, the
+// scan and the update -- the rest of ppo_train_iteration
+extern "C" ppo_status ppo_host_rollout_end(ppo_ctx* c) {
+    NEED(c, c != nullptr, "null ctx");
+    ppo_status s = host_state(c, "ppo_host_rollout_end");
+    if (s != PPO_OK) return s;
+    if (c->host_phase == 0) return fail(c, PPO_ERR_STATE, "ppo_host_rollout_end: no rollout is open (ppo_host_rollout_begin)");
+    if (c->host_t != c->T || !c->host_staged)
+        return fail(c, PPO_ERR_STATE, "ppo_host_rollout_end: %d of %d steps acted on, %d observed", c->host_t, c->T, c->host_staged ? c->host_t : c->host_t - 1);
+    DeviceGuard dev_guard(c);
+    const int N = c->N, T = c->T;
+    HIPCHK(c, launch_host_commit(host_args(c, T, false), N, c->O, c->stream));
+    float* next_obs = B_<float>(c, PPO_BUF_NEXT_OBS);
+    if (c->gen) {
+        s = gen_values(c, B_<float>(c, PPO_BUF_OBS), (int64_t)T * N, B_<float>(c, PPO_BUF_VALUES));
+        if (s == PPO_OK) s = gen_values(c, next_obs, N, B_<float>(c, PPO_BUF_NEXT_VALUE));
+        if (s != PPO_OK) return s;
+    } else if (c->O == 4 || c->O == 2) {   // launch_rollout's tail
+        HIPCHK(c, launch_values_mfma(B_<float>(c, PPO_BUF_PARAMS), c->L, B_<float>(c, PPO_BUF_OBS), (int64_t)T * N, B_<float>(c, PPO_BUF_VALUES), next_obs, N,
+                                     B_<float>(c, PPO_BUF_NEXT_VALUE), c->stream));
+    } else {
+        HIPCHK(c, launch_values(B_<float>(c, PPO_BUF_PARAMS), c->L, B_<float>(c, PPO_BUF_OBS), (int64_t)T * N, B_<float>(c, PPO_BUF_VALUES), next_obs, N,
+                                B_<float>(c, PPO_BUF_NEXT_VALUE), c->stream));
+    }
+    c->host_phase = 0;
+    c->host_staged = false;
+    c->rollout_steps += T;
+    c->global_step += (int64_t)T * c->cfg.global_num_envs;   // :526
+    c->fin_pending = true;
     s = run_scan(c);
     if (s != PPO_OK) return s;
     return ppo_update(c);

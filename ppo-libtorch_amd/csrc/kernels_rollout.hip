@@ -801,6 +801,40 @@ __global__ __launch_bounds__(384, 1) void rollout16_kernel(RolloutArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// Caller-stepped envs (PPO_ENV_HOST): one lane per env commits what the caller's env returned for step t - 1 (stepEnvs' outputs,
+// PPO_Discrete.cpp:440-458, 474-480) -- exactly the bookkeeping the fused rollout does after its own env step: episode sums, the finished episode's
+// length and reward (the caller's own numbers when it passed them), the reward row, the done flag -- and stores m_dones[t] (:530).
+// ---------------------------------------------------------------------------------------------------------
+// the trailing argument of a HOST kernel (none in the stand-alone policy's instantiations)
+__device__ __forceinline__ const HostStepArgs* host_step_args() { return nullptr; }
+__device__ __forceinline__ const HostStepArgs* host_step_args(const HostStepArgs& h) { return &h; }
+
+__device__ __forceinline__ void host_commit_row(const HostStepArgs& hs, int64_t row) {
+    int d = hs.next_done[row];
+    if (hs.commit) {
+        const float r = hs.st_rew[row];
+        d = hs.st_done[row] != 0 ? 1 : 0;
+        int len = hs.ep_len[row] + 1;
+        float rew = hs.ep_rew[row] + r;
+        int fl = 0;
+        float fr = 0.0f;
+        if (d) {
+            fl = hs.fin_given ? hs.st_fin_len[row] : len;
+            fr = hs.fin_given ? hs.st_fin_rew[row] : rew;
+            len = 0;
+            rew = 0.0f;
+        }
+        hs.ep_len[row] = len;
+        hs.ep_rew[row] = rew;
+        hs.rewards_prev[row] = r;     // :544
+        hs.fin_len_prev[row] = fl;    // :455-456
+        hs.fin_rew_prev[row] = fr;
+        hs.next_done[row] = d;
+    }
+    if (hs.dones_t) hs.dones_t[row] = (float)d;
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // Stand-alone policy evaluation WITH rollout16_kernel's ARITHMETIC (Agent::getActionAndValueDiscrete / Masked, Agent.cpp:117-170): one wave per
 // 16-row tile doing the work of the four policy waves in turn.  A column of an MFMA result is a sum over k only, so which wave forms a block of
 // units -- and which tile a row sits in -- does not change a bit: layer 1 as one 16x16x4 fp32 product per block of 16 units, layer 2 as three
@@ -810,13 +844,16 @@ __global__ __launch_bounds__(384, 1) void rollout16_kernel(RolloutArgs a) {
 // observations, weights and Philox word agree in every log-prob bit and in every sampled action (round 5's VERDICT, weak 4: until round 6 the
 // stand-alone policy was always the vector-ALU form, ~1e-7 away, and <= 2 of 8 192 samples fell on the other side of a CDF edge).
 // ---------------------------------------------------------------------------------------------------------
-template <int DIST, int OBS, int EXACTA>
+// HOST (ppo_host_act, caller-stepped envs): the commit of step t - 1 and the rollout stores of step t around the same body (host_commit_row; the one
+// trailing HostStepArgs names the buffers).  HOST = false has no trailing argument: the stand-alone policy's kernel, signature and code as they were.
+template <int DIST, int OBS, int EXACTA, bool HOST = false, class... Host>
 __global__ __launch_bounds__(64) void policy_act16_kernel(const float* __restrict__ P, NetLayout L, const float* __restrict__ obs,
                                                           const uint8_t* __restrict__ mask, const int64_t* __restrict__ forced, int64_t n,
                                                           int64_t seed, int64_t env_offset, int64_t step_index, int64_t* action, float* logprob,
-                                                          float* entropy, int32_t* error_flag) {
+                                                          float* entropy, int32_t* error_flag, const Host... host) {
     const int lane = threadIdx.x, e = lane & 15, kg = lane >> 4;
     constexpr int A = EXACTA;
+    const HostStepArgs* hs = host_step_args(host...);
     // the four blocks' weights as MFMA A operands (rollout16_kernel's per-wave preamble, block mw = 0 .. 3)
     float a1[4], b1d[4][4], b2d[4][4], b3[A];
     r16_u32x4 w2a[4][2][2];   // [block][chunk c][term]
@@ -860,6 +897,14 @@ __global__ __launch_bounds__(64) void policy_act16_kernel(const float* __restric
         const bool live = row < n;      // a ragged last tile: its idle columns compute on row n - 1 and store nothing
         if (!live) row = n - 1;
         const float xk = kg < OBS ? obs[row * OBS + kg] : 0.0f;
+        if constexpr (HOST) {
+            if (live && kg == 0) host_commit_row(*hs, row);
+            if (live && kg < OBS) {
+                hs->obs_t[row * OBS + kg] = xk;                       // m_obs[step] = next_obs (PPO_Discrete.cpp:529)
+                if (hs->commit) hs->next_obs[row * OBS + kg] = xk;
+            }
+            if (live && kg < A && hs->masks_t) hs->masks_t[row * A + kg] = mask ? mask[row * A + kg] : (uint8_t)1;   // PPO_MultiDiscrete.cpp:555
+        }
         // layer 1 + tanh, block by block; the fp16 terms of block mw are one half of chunk (mw >> 1)'s B operand
         uint2 t1[4], t2[4];
 #pragma unroll
@@ -916,6 +961,7 @@ __global__ __launch_bounds__(64) void policy_act16_kernel(const float* __restric
             if (logprob) logprob[row] = lp;
             if (entropy) entropy[row] = en;
             if (action) action[row] = act[0];
+            if constexpr (HOST) hs->actions_t[row] = act[0];   // :537
         }
     }
 }
@@ -942,13 +988,16 @@ __global__ __launch_bounds__(64) void values_kernel(const float* __restrict__ pa
 // ---------------------------------------------------------------------------------------------------------
 // Stand-alone policy evaluation (Agent::getActionAndValueDiscrete / Masked): one wave per row, grid-stride.
 // ---------------------------------------------------------------------------------------------------------
-template <int DIST, int OBS, int AMAX>
+// HOST: as in policy_act16_kernel (ppo_host_act in the vector form: PPO_KERNEL_ROLLOUT_VECTOR, weights outside rollout16_kernel's range, the shapes it
+// does not serve)
+template <int DIST, int OBS, int AMAX, bool HOST = false, class... Host>
 __global__ __launch_bounds__(64) void policy_act_kernel(const float* __restrict__ params, NetLayout L, const float* __restrict__ obs,
                                                         const uint8_t* __restrict__ mask, const int64_t* __restrict__ forced, int64_t n,
                                                         int64_t seed, int64_t env_offset, int64_t step_index, int64_t* action,
-                                                        float* logprob, float* entropy, float* value) {
+                                                        float* logprob, float* entropy, float* value, const Host... host) {
     __shared__ __attribute__((aligned(16))) float lds[PPO_HIDDEN];
     const int lane = threadIdx.x;
+    const HostStepArgs* hs = host_step_args(host...);
     LaneNet<OBS> actor, critic;
     load_lane_net<OBS>(actor, params, L, 1, lane);
     load_lane_net<OBS>(critic, params, L, 0, lane);
@@ -957,6 +1006,14 @@ __global__ __launch_bounds__(64) void policy_act_kernel(const float* __restrict_
         float x[OBS];
 #pragma unroll
         for (int k = 0; k < OBS; k++) x[k] = obs[row * OBS + k];
+        if constexpr (HOST) {
+            if (lane == 0) host_commit_row(*hs, row);
+            if (lane < OBS) {
+                hs->obs_t[row * OBS + lane] = obs[row * OBS + lane];   // m_obs[step] = next_obs (PPO_Discrete.cpp:529)
+                if (hs->commit) hs->next_obs[row * OBS + lane] = obs[row * OBS + lane];
+            }
+            if (lane < A && hs->masks_t) hs->masks_t[row * A + lane] = mask ? mask[row * A + lane] : (uint8_t)1;   // PPO_MultiDiscrete.cpp:555
+        }
         if (value) {
             const float v = critic_head(params, L, trunk_forward<OBS>(critic, x, lds, lane), lane);
             if (lane == 0) value[row] = v;
@@ -972,7 +1029,15 @@ __global__ __launch_bounds__(64) void policy_act_kernel(const float* __restrict_
             if (entropy) entropy[row] = en;
         }
         if (action && lane < H) action[row * H + lane] = act[lane];
+        if constexpr (HOST) { if (lane < H) hs->actions_t[row * H + lane] = act[lane]; }   // :537
     }
+}
+
+// ppo_host_rollout_end (and the generic engine's per-step commit): step t - 1's staged outputs into the rollout, one thread per env
+__global__ __launch_bounds__(256) void host_commit_kernel(HostStepArgs hs, int N, int O) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    for (int64_t k = i; k < N; k += (int64_t)gridDim.x * 256) host_commit_row(hs, k);
+    for (int64_t k = i; k < (int64_t)N * O; k += (int64_t)gridDim.x * 256) hs.next_obs[k] = hs.st_obs[k];
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1307,10 +1372,10 @@ hipError_t launch_policy_act(const float* params, const NetLayout& L, int dist_k
     do {                                                                                                                              \
         if (L.act <= 4)                                                                                                               \
             hipLaunchKernelGGL((policy_act_kernel<DIST, OBS, 4>), dim3(grid), dim3(64), 0, s, params, L, obs, mask, forced_action, n, seed, \
-                               env_offset, step_index, action, logprob, entropy, value);                                              \
+                               env_offset, step_index, action, logprob, entropy, value);                                                            \
         else                                                                                                                          \
             hipLaunchKernelGGL((policy_act_kernel<DIST, OBS, PPO_MAX_ACT>), dim3(grid), dim3(64), 0, s, params, L, obs, mask, forced_action, n, \
-                               seed, env_offset, step_index, action, logprob, entropy, value);                                        \
+                               seed, env_offset, step_index, action, logprob, entropy, value);                                                      \
     } while (0)
     if (L.obs == 4) {
         if (dist_kind == PPO_DIST_CATEGORICAL) PPO_LAUNCH_ACT(PPO_DIST_CATEGORICAL, 4); else PPO_LAUNCH_ACT(PPO_DIST_MASKED, 4);
@@ -1322,6 +1387,58 @@ hipError_t launch_policy_act(const float* params, const NetLayout& L, int dist_k
         return hipErrorInvalidValue;
     }
 #undef PPO_LAUNCH_ACT
+    return hipGetLastError();
+}
+
+hipError_t launch_host_act(const float* params, const NetLayout& L, int dist_kind, const uint8_t* mask, int N, int64_t seed, int64_t env_offset,
+                           int64_t step_index, const HostStepArgs& hs, int64_t* action_h, float* logprob_t, bool as16, int32_t* error_flag, hipStream_t s) {
+    if (N <= 0) return hipSuccess;
+    const float* obs = hs.commit ? hs.st_obs : hs.next_obs;   // step t's observation: what the caller's envs returned for t - 1, or NEXT_OBS at t = 0
+    if (as16 && policy_act16_serves(L)) {
+        // policy_act16_kernel's grid (ppo_policy_act): a row's arithmetic does not depend on the grid
+        const int64_t tiles = (N + 15) / 16;
+        const dim3 grid16((unsigned)(tiles < 4096 ? tiles : 4096));
+#define PPO_LAUNCH_HACT16(DIST, OBS, AA) \
+    hipLaunchKernelGGL((policy_act16_kernel<DIST, OBS, AA, true>), grid16, dim3(64), 0, s, params, L, obs, mask, nullptr, (int64_t)N, seed, env_offset, step_index, action_h, \
+                       logprob_t, nullptr, error_flag, hs)
+#define PPO_LAUNCH_HACT16_D(OBS, AA) \
+    do { if (dist_kind == PPO_DIST_CATEGORICAL) PPO_LAUNCH_HACT16(PPO_DIST_CATEGORICAL, OBS, AA); else PPO_LAUNCH_HACT16(PPO_DIST_MASKED, OBS, AA); } while (0)
+        if (L.obs == 4 && L.act == 2) PPO_LAUNCH_HACT16_D(4, 2);
+        else if (L.obs == 4) PPO_LAUNCH_HACT16_D(4, 3);
+        else if (L.act == 2) PPO_LAUNCH_HACT16_D(2, 2);
+        else PPO_LAUNCH_HACT16_D(2, 3);
+#undef PPO_LAUNCH_HACT16_D
+#undef PPO_LAUNCH_HACT16
+        return hipGetLastError();
+    }
+    const unsigned grid = (unsigned)(N < 8192 ? N : 8192);
+#define PPO_LAUNCH_HACT(DIST, OBS)                                                                                                            \
+    do {                                                                                                                                      \
+        if (L.act <= 4)                                                                                                                       \
+            hipLaunchKernelGGL((policy_act_kernel<DIST, OBS, 4, true>), dim3(grid), dim3(64), 0, s, params, L, obs, mask, nullptr, (int64_t)N, seed, \
+                               env_offset, step_index, action_h, logprob_t, nullptr, nullptr, hs);                                            \
+        else                                                                                                                                  \
+            hipLaunchKernelGGL((policy_act_kernel<DIST, OBS, PPO_MAX_ACT, true>), dim3(grid), dim3(64), 0, s, params, L, obs, mask, nullptr, (int64_t)N, \
+                               seed, env_offset, step_index, action_h, logprob_t, nullptr, nullptr, hs);                                      \
+    } while (0)
+    if (L.obs == 4) {
+        if (dist_kind == PPO_DIST_CATEGORICAL) PPO_LAUNCH_HACT(PPO_DIST_CATEGORICAL, 4); else PPO_LAUNCH_HACT(PPO_DIST_MASKED, 4);
+    } else if (L.obs == 2) {
+        if (dist_kind == PPO_DIST_CATEGORICAL) PPO_LAUNCH_HACT(PPO_DIST_CATEGORICAL, 2); else PPO_LAUNCH_HACT(PPO_DIST_MASKED, 2);
+    } else if (L.obs == 8) {
+        if (dist_kind == PPO_DIST_CATEGORICAL) PPO_LAUNCH_HACT(PPO_DIST_CATEGORICAL, 8); else PPO_LAUNCH_HACT(PPO_DIST_MASKED, 8);
+    } else {
+        return hipErrorInvalidValue;
+    }
+#undef PPO_LAUNCH_HACT
+    return hipGetLastError();
+}
+
+hipError_t launch_host_commit(const HostStepArgs& hs, int N, int O, hipStream_t s) {
+    if (N <= 0) return hipSuccess;
+    const int64_t work = (int64_t)N * (O > 1 ? O : 1);
+    const unsigned grid = (unsigned)((work + 255) / 256 < 65535 ? (work + 255) / 256 : 65535);
+    hipLaunchKernelGGL(host_commit_kernel, dim3(grid), dim3(256), 0, s, hs, N, O);
     return hipGetLastError();
 }
 

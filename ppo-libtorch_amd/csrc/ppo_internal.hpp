@@ -562,6 +562,36 @@ hipError_t launch_policy_act(const float* params, const NetLayout& L, int dist_k
                              int64_t* action, float* logprob, float* entropy, float* value, bool value_only, hipStream_t s, bool as_rollout16 = false,
                              int32_t* error_flag = nullptr);   // as_rollout16: rollout16_kernel's arithmetic where that kernel serves the shape (policy_act16_serves)
 bool policy_act16_serves(const NetLayout& L);
+
+// Caller-stepped environments (PPO_ENV_HOST; api.hip: ppo_host_*).  ppo_host_observe stages step t - 1's outputs of the caller's envs; the next
+// launch COMMITS them (rewards / finished episodes of row t - 1, NEXT_DONE, NEXT_OBS, the per-env episode sums) and, in the act kernels, goes on to
+// step t: OBS[t], DONES[t], MASKS[t], the actor forward + sample, ACTIONS[t], LOGPROBS[t] and the i64 actions where the host reads them.
+struct HostStepArgs {
+    const float* st_obs;        // [N,O] staged next observation (already the reset observation where done)
+    const float* st_rew;        // [N]
+    const int32_t* st_done;     // [N] (truncation included)
+    const int32_t* st_fin_len;  // [N] length / reward of the episodes that finished (fin_given), else the context's running sums are used
+    const float* st_fin_rew;
+    int commit;                 // 1: step t - 1 is staged and not yet committed (0 at t = 0: the observation is NEXT_OBS)
+    int fin_given;
+    float* rewards_prev;        // REWARDS[t - 1], FIN_LEN[t - 1], FIN_REW[t - 1]
+    int32_t* fin_len_prev;
+    float* fin_rew_prev;
+    int32_t* next_done;         // [N]
+    float* next_obs;            // [N,O]
+    int32_t* ep_len;            // [N] episode sums of the running episodes
+    float* ep_rew;
+    float* obs_t;               // OBS[t], DONES[t], MASKS[t] (null: not a masked policy), ACTIONS[t]; all null in the commit-only launch
+    float* dones_t;
+    uint8_t* masks_t;
+    int32_t* actions_t;
+};
+// commit + act of one step in ONE launch: rollout16_kernel's arithmetic (policy_act16_kernel) when as16 and the shape is one of its, else the vector
+// form (policy_act_kernel).  mask: [N,A] of step t or null; action_h: i64 [N,H], device-visible host memory; logprob_t: LOGPROBS[t]
+hipError_t launch_host_act(const float* params, const NetLayout& L, int dist_kind, const uint8_t* mask, int N, int64_t seed, int64_t env_offset,
+                           int64_t step_index, const HostStepArgs& hs, int64_t* action_h, float* logprob_t, bool as16, int32_t* error_flag, hipStream_t s);
+// commit only (ppo_host_rollout_end; the generic engine's per-step commit ahead of gen_forward)
+hipError_t launch_host_commit(const HostStepArgs& hs, int N, int O, hipStream_t s);
 hipError_t launch_categorical(int dist_kind, const float* logits, const uint8_t* mask, const int64_t* value, int64_t n, int A,
                               float* m_logits, float* m_probs, float* log_prob, float* entropy, int64_t* mode, hipStream_t s);
 

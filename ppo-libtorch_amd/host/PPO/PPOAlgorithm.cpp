@@ -131,7 +131,10 @@ void PPOAlgorithm::construct() {
     c.num_minibatches = static_cast<int32_t>(m_num_minibatches);
     c.update_epochs = static_cast<int32_t>(m_update_epochs);
     c.max_episode_steps = static_cast<int32_t>(m_max_episode_steps);
-    c.use_gae = m_use_gae; c.norm_adv = m_norm_adv; c.clip_vloss = m_clip_vloss; c.anneal_lr = m_anneal_lr;
+    c.use_gae = m_use_gae; c.norm_adv = m_norm_adv; c.clip_vloss = m_clip_vloss;
+    // train() sets the annealed learning rate itself (ppo_set_learning_rate); a caller-stepped context (PPO_ENV_HOST) would anneal again in
+    // ppo_host_rollout_begin -- from the update count of THIS run, not from the steps left after a resume
+    c.anneal_lr = m_env_kind == PPO_ENV_HOST ? 0 : m_anneal_lr;
     c.seed = m_seed;
     c.total_timesteps = m_total_timesteps;
     c.learning_rate = m_learning_rate; c.gamma = m_gamma; c.gae_lambda = m_gae_lambda; c.clip_coef = m_clip_coef;
@@ -198,13 +201,20 @@ Tensor PPOAlgorithm::getApproxKLAndClippedObj(const Tensor& ratio, const Tensor&
     return Tensor::from_host<float>(m_device, { static_cast<float>(kl / static_cast<double>(r.size())) }, { 1 });
 }
 
+void PPOAlgorithm::trainInitEnvs() { ppo::check(ppo_env_reset(m_ctx), m_ctx, "initEnvs"); }
+void PPOAlgorithm::trainRollout() {
+    ppo::check(ppo_rollout(m_ctx, nullptr), m_ctx, "rollout");
+    ppo::check(ppo_calc_advantage(m_ctx), m_ctx, "calcAdvantage");
+    ppo::check(ppo_update(m_ctx), m_ctx, "update");
+}
+
 void PPOAlgorithm::train() {
     m_threadPool->start();
     uint64_t global_step = m_global_step;
     const auto start_time = std::chrono::steady_clock::now();
     auto update_time = start_time;
     const int64_t num_updates = (m_total_timesteps - static_cast<int64_t>(global_step)) / m_batch_size;   // :496
-    ppo::check(ppo_env_reset(m_ctx), m_ctx, "initEnvs");
+    trainInitEnvs();
 
     // One iteration = LR anneal (:514-518), rollout (:524-548), advantages (:554), all epochs x minibatches (:567-644), explained variance (:647-648),
     // and a statistics snapshot behind them.  Everything here is ENQUEUED: nothing waits for the GPU.
@@ -213,9 +223,7 @@ void PPOAlgorithm::train() {
             const double frac = 1.0 - (update - 1.0) / num_updates;
             ppo::check(ppo_set_learning_rate(m_ctx, frac * m_learning_rate), m_ctx, "lr");
         }
-        ppo::check(ppo_rollout(m_ctx, nullptr), m_ctx, "rollout");
-        ppo::check(ppo_calc_advantage(m_ctx), m_ctx, "calcAdvantage");
-        ppo::check(ppo_update(m_ctx), m_ctx, "update");
+        trainRollout();
         ppo::check(ppo_stats_snapshot(m_ctx), m_ctx, "stats");
     };
     if (num_updates >= 1) enqueue(1);
@@ -227,6 +235,7 @@ void PPOAlgorithm::train() {
         if (update < num_updates && !checkpoint_due) enqueue(update + 1);
         ppo::check(ppo_stats_snapshot_read(m_ctx, &m_last_stats), m_ctx, "stats");   // waits for iteration `update` only
         const ppo_stats& st = m_last_stats;
+        if (m_on_update) m_on_update(update, st);
         global_step += static_cast<uint64_t>(m_batch_size);
         m_episode_stats->assign(st.ep_len_mean, static_cast<float>(st.ep_rew_mean), static_cast<size_t>(st.ep_count));
         m_clipfracs.assign(1, static_cast<float>(st.clipfrac_mean));

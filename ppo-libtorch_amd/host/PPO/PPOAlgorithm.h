@@ -4,6 +4,7 @@
 #pragma once
 #include <array>
 #include <chrono>
+#include <functional>
 #include <iomanip>
 #include <iostream>
 #include <memory>
@@ -82,8 +83,13 @@ class PPOAlgorithm {
     std::unique_ptr<CircularBuffer> m_episode_stats;
     uint64_t m_global_step;
     std::shared_ptr<ThreadPool> m_threadPool;
+    // called by train() with every update's statistics as printPPOResults receives them (not in the reference: for logging and tests)
+    std::function<void(int64_t update, const ppo_stats&)> m_on_update;
 
   protected:
+    // train()'s env handling: the context's device envs here; PPO_HostEnv (PPO_HostEnv.h) steps the caller's envs instead
+    virtual void trainInitEnvs();         // initEnvs before the first update (:492-494)
+    virtual void trainRollout();          // rollout (:524-548), advantages (:554) and the update (:567-648) of one iteration, enqueued
     PPOAlgorithm(int env_kind, int dist_kind, int64_t default_obs, int64_t default_max_episode_steps);
     void construct();                     // second half of the reference's constructor: needs the final hyper-parameters
     ppo::Tensor initEnvsImpl();

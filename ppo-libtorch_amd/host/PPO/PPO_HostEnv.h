@@ -1,0 +1,134 @@
+// PPO on the caller's own environments: the reference's custom-environment framework (README: "easily implement your own training environments").
+// A reference user writes a class with reset() / step(action) / episode_length / episode_reward and puts it in place of CartPole in PPO_Discrete's
+// m_envs; stepEnvs steps them on the thread pool (PPO_Discrete.cpp:365-483).  Here the same class is the template argument:
+//
+//     PPO_HostEnv<MyEnv> algo;                       // ./PPOConfig.toml as for PPO_Discrete (obs_size / action_size = MyEnv's)
+//     algo.train();
+//
+// Env (duck type of the reference's CartPole): std::vector<float> reset(); std::tuple<std::vector<float>, float, bool, bool> step(const int64_t&);
+// episode_length; episode_reward; and, when Masked, getActionMask() (any container of A values convertible to bool, or a ppo::Tensor of u8).
+// The envs are made by a factory (default std::make_shared<Env>(m_seed), as the reference constructs its CartPoles).  Every env is stepped by one
+// pool job at a time; envs must not share mutable state with each other (the facade's CartPole owns its Device: no shared HIP stream or context).
+// The context (PPO_ENV_HOST) owns parameters, AdamW state, rollout buffers, sampler and episode statistics: include/ppo_hip.h ppo_host_*.
+#pragma once
+#include <atomic>
+#include <cstring>
+#include <functional>
+#include <memory>
+#include <stdexcept>
+#include <string>
+#include <tuple>
+#include <type_traits>
+#include <vector>
+
+#include "PPOAlgorithm.h"
+
+template <class Env, bool Masked = false>
+class PPO_HostEnv : public PPOAlgorithm {
+  public:
+    using EnvFactory = std::function<std::shared_ptr<Env>(int64_t env_index)>;
+
+    explicit PPO_HostEnv(EnvFactory factory = nullptr)
+        : PPOAlgorithm(PPO_ENV_HOST, Masked ? PPO_DIST_MASKED : PPO_DIST_CATEGORICAL, 4, 500) {
+        getArgs();
+        construct();
+        m_envs.reserve(static_cast<size_t>(m_num_envs));
+        for (int64_t i = 0; i < m_num_envs; i++) m_envs.push_back(factory ? factory(i) : std::make_shared<Env>(m_seed));
+        const size_t N = static_cast<size_t>(m_num_envs);
+        m_next_obs.assign(N * static_cast<size_t>(m_obs_size), 0.0f);
+        m_reward.assign(N, 0.0f);
+        m_done.assign(N, 0);
+        m_fin_len.assign(N, 0);
+        m_fin_rew.assign(N, 0.0f);
+        m_action.assign(N, 0);
+        if (Masked) m_mask.assign(N * static_cast<size_t>(m_action_size), 1);
+    }
+
+    std::vector<std::shared_ptr<Env>> m_envs;
+
+    // initEnvs (:365-402): env 0 once for the obs-size check, then every env (env 0 twice, as the reference); NEXT_OBS = the reset observations
+    ppo::Tensor initEnvs() {
+        const std::vector<float> test_obs = m_envs[0]->reset();
+        if (static_cast<int64_t>(test_obs.size()) != m_obs_size)
+            throw std::runtime_error("The environment returned an observation of size " + std::to_string(test_obs.size()) +
+                                     ", but your config defined the expected observation size to be " + std::to_string(m_obs_size) + ".\n" +
+                                     "Have you properly defined your PPOConfig.toml file for your environment?");
+        std::atomic<int64_t> bad_width{ -1 };
+        for (int64_t i = 0; i < m_num_envs; i++)
+            m_threadPool->queueJob([this, i, &bad_width]() {
+                const std::vector<float> o = m_envs[static_cast<size_t>(i)]->reset();
+                if (static_cast<int64_t>(o.size()) != m_obs_size) bad_width = static_cast<int64_t>(o.size());
+                else copyObs(i, o);
+            });
+        m_threadPool->waitForJobsToFinish();
+        if (bad_width >= 0) throw std::runtime_error("an environment returned an observation of size " + std::to_string(bad_width.load()) + " on reset");
+        ppo::check(ppo_host_env_reset(m_ctx, m_next_obs.data()), m_ctx, "initEnvs");
+        return bufferView(PPO_BUF_NEXT_OBS, { m_num_envs, m_obs_size }, ppo::DType::f32);
+    }
+
+    // stepEnvs (:413-483) on the pool: step, truncation at max_episode_steps, the finished episode's length / reward from the env itself, auto-reset.
+    // Fills the host arrays ppo_host_observe takes.
+    void stepEnvs(const std::vector<int64_t>& action) {
+        std::atomic<int64_t> bad_width{ -1 };
+        for (int64_t i = 0; i < m_num_envs; i++)
+            m_threadPool->queueJob([this, i, &action, &bad_width]() {
+                const size_t k = static_cast<size_t>(i);
+                Env& env = *m_envs[k];
+                auto [obs, reward, terminated, info] = env.step(action[k]);
+                (void)info;
+                if (static_cast<int64_t>(env.episode_length) == m_max_episode_steps) terminated = true;
+                m_fin_len[k] = 0;
+                m_fin_rew[k] = 0.0f;
+                if (terminated) {
+                    m_fin_len[k] = static_cast<int32_t>(env.episode_length);
+                    m_fin_rew[k] = static_cast<float>(env.episode_reward);
+                    obs = env.reset();
+                }
+                if (static_cast<int64_t>(obs.size()) != m_obs_size) bad_width = static_cast<int64_t>(obs.size());   // (pool jobs must not throw)
+                else copyObs(i, obs);
+                m_reward[k] = reward;
+                m_done[k] = terminated ? 1 : 0;
+            });
+        m_threadPool->waitForJobsToFinish();
+        if (bad_width >= 0)
+            throw std::runtime_error("The environment returned an observation of size " + std::to_string(bad_width.load()) +
+                                     ", but your config defined the expected observation size to be " + std::to_string(m_obs_size) + ".");
+    }
+
+  protected:
+    void trainInitEnvs() override { initEnvs(); }
+
+    // the rollout of :524-548 with the caller's envs: one ppo_host_act (one kernel, one wait) and one stepEnvs per step; then values, advantages
+    // and the update, enqueued by ppo_host_rollout_end
+    void trainRollout() override {
+        ppo::check(ppo_host_rollout_begin(m_ctx), m_ctx, "rollout");
+        for (int64_t t = 0; t < m_num_steps; t++) {
+            if constexpr (Masked) gatherMasks();
+            ppo::check(ppo_host_act(m_ctx, Masked ? m_mask.data() : nullptr, m_action.data()), m_ctx, "rollout");
+            stepEnvs(m_action);
+            ppo::check(ppo_host_observe(m_ctx, m_next_obs.data(), m_reward.data(), m_done.data(), m_fin_len.data(), m_fin_rew.data()), m_ctx, "rollout");
+        }
+        ppo::check(ppo_host_rollout_end(m_ctx), m_ctx, "update");
+    }
+
+  private:
+    void copyObs(int64_t i, const std::vector<float>& o) {
+        std::memcpy(m_next_obs.data() + static_cast<size_t>(i * m_obs_size), o.data(), sizeof(float) * static_cast<size_t>(m_obs_size));
+    }
+    template <class M> static bool maskAt(const M& m, size_t a) {
+        if constexpr (std::is_same<M, ppo::Tensor>::value) return m.template cpu<uint8_t>()[a] != 0;
+        else return static_cast<bool>(m[a]);
+    }
+    void gatherMasks() {
+        const size_t A = static_cast<size_t>(m_action_size);
+        for (size_t i = 0; i < m_envs.size(); i++) {
+            const auto m = m_envs[i]->getActionMask();
+            for (size_t a = 0; a < A; a++) m_mask[i * A + a] = maskAt(m, a) ? 1 : 0;
+        }
+    }
+
+    std::vector<float> m_next_obs, m_reward, m_fin_rew;
+    std::vector<int32_t> m_done, m_fin_len;
+    std::vector<int64_t> m_action;
+    std::vector<uint8_t> m_mask;
+};

@@ -1,0 +1,149 @@
+"""Where the time of a host-stepped env step goes (PPO_ENV_HOST, include/ppo_hip.h ppo_host_*).  Prints one JSON line:
+
+  (a) launch_wait_us      round trip of a trivial launch (a one-env ppo_env_transition) plus the wait for it
+  (b) act_us[N]           ppo_host_act + ppo_host_observe per step with a zero-cost env (fixed arrays), N in {256, 4096, 16384}
+  (c) end_ms              ppo_host_rollout_end (commit, values, scan, update) until the stream is idle, 4096 x 128
+  (d) host_sps            env-steps/s of full host-stepped iterations at 4096 x 128 (zero-cost env), next to device_sps: ppo_train_iteration's
+
+  --one-rollout           only one host-stepped rollout at 4096 x 128 (for a rocprofv3 --kernel-trace --memory-copy-trace --stats run around it)
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from __graft_entry__ import load_package  # noqa: E402
+
+P = load_package()
+
+
+def host_ctx(N, T, flags=0, iters=4):
+    c = P.Context(P.make_config(env_kind=P.ENV_HOST, num_envs=N, num_steps=T, num_minibatches=4, update_epochs=4, seed=1,
+                                total_timesteps=N * T * iters, kernel_flags=flags))
+    c.init_orthogonal(1)
+    return c
+
+
+class ZeroEnv:
+    """Fixed arrays: the cost of the env is nil, what is left is the library's."""
+
+    def __init__(self, N):
+        rng = np.random.default_rng(0)
+        self.obs = rng.uniform(-0.05, 0.05, (N, 4)).astype(np.float32)
+        self.rew = np.ones(N, np.float32)
+        self.done = (rng.random(N) < 0.02).astype(np.int32)
+        self.args = [np.ascontiguousarray(x).ctypes.data_as(C.c_void_p) for x in (self.obs, self.rew, self.done)]
+        self.act = np.empty((N, 1), np.int64)
+        self.act_p = self.act.ctypes.data_as(C.c_void_p)
+
+
+def rollout_steps(c, env, T):
+    L = P.binding.lib()
+    for _ in range(T):
+        P.binding._check(L.ppo_host_act(c.h, None, env.act_p), c.h)
+        P.binding._check(L.ppo_host_observe(c.h, env.args[0], env.args[1], env.args[2], None, None), c.h)
+
+
+def launch_wait_us(reps=2000):
+    c = P.Context(P.make_config(num_envs=8, num_steps=4, num_minibatches=1, update_epochs=1))
+    L = P.binding.lib()
+    st, a = c.dev(np.zeros((1, 4), np.float32)), c.dev(np.zeros(1, np.int64))
+    ns, r, d = c.empty((1, 4), np.float32), c.empty(1, np.float32), c.empty(1, np.int32)
+    stream = C.c_void_p(c.stream())
+
+    def once():
+        P.binding._check(L.ppo_env_transition(0, st.ptr, a.ptr, C.c_int64(1), ns.ptr, r.ptr, d.ptr, stream))
+        P.binding._check(L.ppo_sync(c.h), c.h)
+    for _ in range(200):
+        once()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        once()
+    us = (time.perf_counter() - t0) / reps * 1e6
+    c.close()
+    return us
+
+
+def act_us(N, flags=0, T=64, rounds=3):
+    c = host_ctx(N, T, flags)
+    env = ZeroEnv(N)
+    c.host_env_reset(env.obs)
+    best = None
+    for r in range(rounds + 1):
+        c.host_rollout_begin()
+        t0 = time.perf_counter()
+        rollout_steps(c, env, T)
+        dt = (time.perf_counter() - t0) / T * 1e6
+        c.host_rollout_end()
+        c.sync()
+        if r > 0:
+            best = dt if best is None else min(best, dt)
+    c.close()
+    return best
+
+
+def iteration_times(flags=0, N=4096, T=128, iters=4):
+    c = host_ctx(N, T, flags, iters + 1)
+    env = ZeroEnv(N)
+    c.host_env_reset(env.obs)
+    ends, its = [], []
+    for i in range(iters + 1):
+        t0 = time.perf_counter()
+        c.host_rollout_begin()
+        rollout_steps(c, env, T)
+        t1 = time.perf_counter()
+        c.host_rollout_end()
+        c.sync()
+        t2 = time.perf_counter()
+        if i > 0:
+            ends.append((t2 - t1) * 1e3)
+            its.append(t2 - t0)
+    c.close()
+    return min(ends), N * T / min(its)
+
+
+def device_sps(N=4096, T=128, iters=5):
+    c = P.Context(P.make_config(num_envs=N, num_steps=T, num_minibatches=4, update_epochs=4, seed=1, total_timesteps=N * T * (iters + 1)))
+    c.init_orthogonal(1)
+    c.env_reset()
+    c.train_iteration()
+    c.sync()
+    t0 = time.perf_counter()
+    for _ in range(iters):
+        c.train_iteration()
+    c.sync()
+    sps = N * T * iters / (time.perf_counter() - t0)
+    c.close()
+    return sps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--one-rollout", action="store_true")
+    args = ap.parse_args()
+    if args.one_rollout:
+        N, T = 4096, 128
+        c = host_ctx(N, T)
+        env = ZeroEnv(N)
+        c.host_env_reset(env.obs)
+        c.host_rollout_begin()
+        rollout_steps(c, env, T)
+        c.host_rollout_end()
+        c.sync()
+        c.close()
+        print(json.dumps({"one_rollout": True, "N": N, "T": T}))
+        return
+    out = {"launch_wait_us": launch_wait_us(), "act_us": {N: act_us(N) for N in (256, 4096, 16384)}}
+    out["end_ms"], out["host_sps"] = iteration_times()
+    out["device_sps"] = device_sps()
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
