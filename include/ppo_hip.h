@@ -168,7 +168,8 @@ enum {
  * ------------------------------------------------------------------------------------------------------- */
 PPO_API int32_t ppo_abi_version(void);
 /* PPO_Discrete::PPO_Discrete() (PPO_Discrete.cpp:4-100): allocates every device buffer once (rollout [T,N,*],
- * parameters, AdamW state, env SoA, reset-stream table); no allocation happens afterwards. */
+ * parameters, AdamW state, env SoA, reset-stream table); no allocation happens afterwards -- except ppo_evaluate's scratch (per-episode arrays, the
+ * evaluation reset table), allocated by its first call, kept, and grown only by a call that asks for more episodes than any before it. */
 PPO_API ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out);
 PPO_API void ppo_ctx_destroy(ppo_ctx* ctx);
 /* Error text of the last failing call on ctx (ctx == NULL: of the last failing ppo_ctx_create in this thread).
@@ -207,6 +208,19 @@ PPO_API ppo_status ppo_get_value(ppo_ctx* ctx, const float* obs, int64_t n, floa
  *   Arithmetic: that of the kernel ppo_rollout would run in this context now (PPO_KERNEL_ROLLOUT_VECTOR above): bit for bit the rollout's log-probs / actions. */
 PPO_API ppo_status ppo_policy_act(ppo_ctx* ctx, const float* obs, const uint8_t* mask, const int64_t* forced_action, int64_t n,
                           int64_t step_index, int64_t* action, float* logprob, float* entropy, float* value);
+
+/* Categorical::mode / CategoricalMasked::mode (Categorical.cpp:139-141, CategoricalMasked.cpp:160-162) through the Agent
+ * (Agent.cpp:117-170): action[n,H] = per head argmax of m_probs (masked logits set to -1e8 first), FIRST index on equal values;
+ * logprob / entropy summed over heads for that action; value as ppo_get_value.  Outputs may be NULL except action.
+ *   The deterministic policy of a trained or loaded agent (the reference's README: real-time inference, embedding into a game engine).  Draws no random
+ *   number, touches no rollout state, does not advance the sampler: valid on every context kind at any time, PPO_ENV_HOST contexts in the middle of a
+ *   rollout included.
+ *   Arithmetic: as ppo_policy_act -- the logits of the kernel the context's rollout would run now (policy_act16_kernel's products by default; the vector form
+ *   under PPO_KERNEL_ROLLOUT_VECTOR or when the weight-range snapshot says the output layer does not fit fp16, counted in vector_fallback_launches; generic
+ *   networks: the generic engine's forward in the context's compute_dtype).  logprob, entropy and value are, bit for bit, what ppo_policy_act returns when the
+ *   greedy action is passed back as forced_action. */
+PPO_API ppo_status ppo_policy_act_greedy(ppo_ctx* ctx, const float* obs, const uint8_t* mask, int64_t n,
+                                         int64_t* action, float* logprob, float* entropy, float* value);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Distributions (Distributions/Categorical.h:11-22, CategoricalMasked.h:12-23), stateless
@@ -364,6 +378,38 @@ PPO_API ppo_status ppo_host_observe(ppo_ctx* ctx, const float* next_obs_h, const
 /* After T act/observe pairs: values of every stored observation and the bootstrap value (:280), the scan, the update: the rest of
  * ppo_train_iteration.  Enqueued; rollout_steps += T, global_step += T * global_num_envs, finished episodes pending, as after ppo_rollout. */
 PPO_API ppo_status ppo_host_rollout_end(ppo_ctx* ctx);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Evaluation (new; the reference reports only the mean over the last 100 exploration episodes of its training envs, PPO_Discrete.cpp:474-480, Utils.h:72-78)
+ * ------------------------------------------------------------------------------------------------------- */
+typedef struct ppo_eval_stats {
+    int64_t episodes, env_steps;                 /* env_steps = sum of lengths */
+    double return_mean, return_std, return_min, return_max;   /* std: population (ddof 0) */
+    double length_mean; int64_t length_min, length_max;
+    int64_t truncated;                           /* episodes that reached max_episode_steps (PPO_Discrete.cpp:449-452) */
+} ppo_eval_stats;
+/* n_episodes whole episodes of the context's device env (PPO_ENV_CARTPOLE, PPO_ENV_MOUNTAINCAR) under the current policy, as ONE launch: no host round
+ * trip per step and no [T,N,*] stores, only an episode's return, length and truncated flag leave the chip.
+ *   Episode e (0 <= e < n_episodes) is a pure function of (parameters, seed, e, greedy, max_episode_steps).  Start state: CartPole = row e of
+ *   ppo_cartpole_reset_stream_h(seed, n_episodes) (CartPole.cpp:34-45); MountainCar = MountainCar::reset (MountainCar.cpp:59-66) with the build's key
+ *   (seed, env e, reset 0).  Steps as stepEnvs (PPO_Discrete.cpp:440-458): CartPole::step / MountainCar::step (CartPole.cpp:47-94, MountainCar.cpp:29-57),
+ *   reward summed in f32 in step order, the episode ends where the env terminates or its length reaches the context's max_episode_steps (:449-452).
+ *   greedy != 0: actions as ppo_policy_act_greedy.  greedy == 0: the sampler of ppo_policy_act (Categorical.cpp:73-79) keyed (seed, row e, step t within
+ *   the episode, head).  Logits: those of ppo_policy_act_greedy / ppo_policy_act on the same context (the kernel is chosen once per call from the same
+ *   weight-range snapshot as ppo_rollout's) -- stepping the same start states through those calls and ppo_env_transition gives the same bits.
+ *   Hence: results do not depend on how episodes are spread over workgroups, and ppo_evaluate(n = 16) equals the first 16 entries of ppo_evaluate(n = 64)
+ *   with the same seed.
+ *   ep_return f32 [n_episodes] / ep_length i32 [n_episodes]: device arrays or NULL.  out_h (host, required): the summary, formed on the host in f64 from the
+ *   per-episode arrays in index order.  Evaluates the parameters as they are behind everything already enqueued on the context's stream; SYNCHRONOUS (returns
+ *   when out_h is filled).
+ *   Leaves the training state exactly as it was: every PPO_BUF_*, reset counters, sampler position, episode ring, statistics, error word and ppo_profile
+ *   (a vector-kernel fallback of this launch is not counted).  Purely local: no collective on a sharded context (every rank that asks the same question
+ *   gets the same answer).
+ *   Errors: PPO_ENV_SYNTHETIC and PPO_ENV_HOST contexts -> PPO_ERR_UNSUPPORTED (step the episodes yourself around ppo_policy_act_greedy);
+ *   n_episodes <= 0, out_h == NULL, max_episode_steps <= 0 -> PPO_ERR_INVALID.  A failing call changes nothing. */
+PPO_API ppo_status ppo_evaluate(ppo_ctx* ctx, int64_t n_episodes, int64_t seed, int32_t greedy,
+                                float* ep_return /* dev f32[n] or NULL */, int32_t* ep_length /* dev i32[n] or NULL */,
+                                ppo_eval_stats* out_h);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Measurement (new; the reference only has a wall clock around each update, PPO_Discrete.cpp:650-652)

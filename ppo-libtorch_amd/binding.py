@@ -47,6 +47,7 @@ ABI_SYMBOLS = [
     "ppo_comm_init_local", "ppo_comm_exchange_handle", "ppo_comm_init_exchange", "ppo_comm_exchange_timeouts",
     "ppo_comm_set_wait_limit", "ppo_stats_snapshot", "ppo_stats_snapshot_read",
     "ppo_host_env_reset", "ppo_host_rollout_begin", "ppo_host_act", "ppo_host_observe", "ppo_host_rollout_end",
+    "ppo_policy_act_greedy", "ppo_evaluate",
 ]
 
 
@@ -83,6 +84,16 @@ class Profile(C.Structure):
         d = {n: getattr(self, n) for n, _ in self._fields_ if n != "phase_cycles"}
         d["phase_cycles"] = list(self.phase_cycles)
         return d
+
+
+class EvalStats(C.Structure):
+    """ppo_eval_stats: the summary of one ppo_evaluate run."""
+    _fields_ = [("episodes", C.c_int64), ("env_steps", C.c_int64), ("return_mean", C.c_double), ("return_std", C.c_double),
+                ("return_min", C.c_double), ("return_max", C.c_double), ("length_mean", C.c_double), ("length_min", C.c_int64),
+                ("length_max", C.c_int64), ("truncated", C.c_int64)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 def make_config(env_kind=ENV_CARTPOLE, dist_kind=DIST_CATEGORICAL, obs_size=4, head_dims=(2,), num_envs=8, num_steps=32,
@@ -282,6 +293,35 @@ class Context:
         _check(lib().ppo_policy_act(self.h, d_obs.ptr, d_mask.ptr if d_mask else None, d_forced.ptr if d_forced else None, C.c_int64(n),
                                     C.c_int64(step_index), d_a.ptr, d_lp.ptr, d_en.ptr, d_v.ptr), self.h)
         return d_a.download(), d_lp.download(), d_en.download(), d_v.download()
+
+    def policy_act_greedy(self, obs, mask=None):
+        """Categorical::mode through the Agent (reference Categorical.cpp:139-141, Agent.cpp:117-170): the deterministic action per head, with the
+        log-prob / entropy / value ppo_policy_act gives for it.  Returns (action i64 [n,H], logprob, entropy, value)."""
+        obs = np.ascontiguousarray(obs, np.float32).reshape(-1, self.O)
+        n = obs.shape[0]
+        d_obs = self.dev(obs)
+        d_mask = self.dev(np.asarray(mask).reshape(n, self.A), np.uint8) if mask is not None else None
+        d_a, d_lp, d_en, d_v = self.empty((n, self.H), np.int64), self.empty(n, np.float32), self.empty(n, np.float32), self.empty(n, np.float32)
+        _check(lib().ppo_policy_act_greedy(self.h, d_obs.ptr, d_mask.ptr if d_mask else None, C.c_int64(n), d_a.ptr, d_lp.ptr, d_en.ptr, d_v.ptr), self.h)
+        out = d_a.download(), d_lp.download(), d_en.download(), d_v.download()
+        for x in (d_obs, d_mask, d_a, d_lp, d_en, d_v):
+            if x is not None:
+                x.free()
+        return out
+
+    def evaluate(self, n_episodes, seed, greedy=True):
+        """ppo_evaluate: n_episodes whole episodes of the context's device env under the current policy in one launch.
+        Returns (stats dict, returns f32 [n], lengths i32 [n])."""
+        n = int(n_episodes)
+        d_r = self.empty(max(n, 1), np.float32)
+        d_l = self.empty(max(n, 1), np.int32)
+        st = EvalStats()
+        try:
+            _check(lib().ppo_evaluate(self.h, C.c_int64(n), C.c_int64(seed), C.c_int32(1 if greedy else 0), d_r.ptr, d_l.ptr, C.byref(st)), self.h)
+            return st.as_dict(), d_r.download()[:n], d_l.download()[:n]
+        finally:
+            d_r.free()
+            d_l.free()
 
     # ---- Environments
     def env_reset(self):

@@ -165,6 +165,14 @@ struct ppo_ctx {
     uint64_t* group_bits = nullptr;     // [T, ceil(N/64)] ballots of finished episodes
     EpisodeRing* ring = nullptr;
     float* scratch_obs = nullptr;       // [N,O] staging for AoS<->SoA conversions
+    // ppo_evaluate's scratch, allocated on first use and kept (grown when a call asks for more episodes): per-episode results and, for CartPole, the
+    // evaluation reset table (rows of ppo_cartpole_reset_stream_h(eval_table_seed, .); the host copy is kept so that a larger n extends, not redraws)
+    float* eval_ret = nullptr;
+    int32_t* eval_len = nullptr;        // [eval_cap] lengths, then [eval_cap] truncated flags
+    int64_t eval_cap = 0;
+    float* eval_table = nullptr;
+    int64_t eval_table_cap = 0, eval_table_rows = 0, eval_table_seed = 0;
+    std::vector<float> eval_table_h;
     int max_blocks_per_net = 0;
     bool use_mfma = true;
     bool update_single_wave = false;   // PPO_KERNEL_UPDATE_ONE_WAVE
@@ -901,7 +909,7 @@ static ppo_status gen_values(ppo_ctx* c, const float* obs, int64_t n, float* val
     return PPO_OK;
 }
 static ppo_status gen_policy(ppo_ctx* c, const float* obs, const uint8_t* mask, const int64_t* forced, int64_t n, int64_t step_index, int64_t* action,
-                             float* logprob, float* entropy) {
+                             float* logprob, float* entropy, bool greedy = false) {
     GenericCtx& g = *c->gen;
     for (int64_t off = 0; off < n; off += g.rows_max) {
         const int64_t rows = std::min<int64_t>(g.rows_max, n - off);
@@ -909,7 +917,7 @@ static ppo_status gen_policy(ppo_ctx* c, const float* obs, const uint8_t* mask, 
         else HIPCHK(c, gen_forward(g, B_<float>(c, PPO_BUF_PARAMS), 1, obs + off * g.L.obs, rows, nullptr, g.dz[0], g.dz[1], g.logits, c->stream));
         HIPCHK(c, gen_heads(g.L, c->cfg.dist_kind, g.logits, mask ? mask + off * g.L.act : nullptr, forced ? forced + off * g.L.n_heads : nullptr, rows,
                             c->cfg.seed, c->cfg.env_offset + off, step_index, action ? action + off * g.L.n_heads : nullptr,
-                            logprob ? logprob + off : nullptr, entropy ? entropy + off : nullptr, c->stream));
+                            logprob ? logprob + off : nullptr, entropy ? entropy + off : nullptr, c->stream, greedy));
     }
     return PPO_OK;
 }
@@ -927,13 +935,11 @@ static ppo_status refresh_weight_range(ppo_ctx* c);          // (the fp16 range 
 static inline void wr_snapshot(ppo_ctx* c);
 static inline bool weights_fit_rollout16(const ppo_ctx* c);
 
-extern "C" ppo_status ppo_policy_act(ppo_ctx* c, const float* obs, const uint8_t* mask, const int64_t* forced_action, int64_t n,
-                                     int64_t step_index, int64_t* action, float* logprob, float* entropy, float* value) {
-    NEED(c, c && obs, "null argument");
-    DeviceGuard dev_guard(c);
-    NEED(c, forced_action || action, "sampling needs an action output");
+// ppo_policy_act and ppo_policy_act_greedy: one body.  greedy: the heads' modes instead of draws (no random number, forced_action unused).
+static ppo_status policy_act_common(ppo_ctx* c, const float* obs, const uint8_t* mask, const int64_t* forced_action, int64_t n, int64_t step_index,
+                                    int64_t* action, float* logprob, float* entropy, float* value, bool greedy) {
     if (c->gen) {
-        ppo_status s = gen_policy(c, obs, mask, forced_action, n, step_index, action, logprob, entropy);
+        ppo_status s = gen_policy(c, obs, mask, forced_action, n, step_index, action, logprob, entropy, greedy);
         if (s == PPO_OK && value) s = gen_values(c, obs, n, value);
         return s;
     }
@@ -948,8 +954,25 @@ extern "C" ppo_status ppo_policy_act(ppo_ctx* c, const float* obs, const uint8_t
         if (!weights_fit_rollout16(c)) { as16 = false; c->vector_fallback_launches += 1; }
     }
     HIPCHK(c, launch_policy_act(B_<float>(c, PPO_BUF_PARAMS), c->L, c->cfg.dist_kind, obs, mask, forced_action, n, c->cfg.seed, c->cfg.env_offset,
-                                step_index, action, logprob, entropy, value, false, c->stream, as16, c->error_flag));
+                                step_index, action, logprob, entropy, value, false, c->stream, as16, c->error_flag, greedy));
     return PPO_OK;
+}
+
+extern "C" ppo_status ppo_policy_act(ppo_ctx* c, const float* obs, const uint8_t* mask, const int64_t* forced_action, int64_t n,
+                                     int64_t step_index, int64_t* action, float* logprob, float* entropy, float* value) {
+    NEED(c, c && obs, "null argument");
+    DeviceGuard dev_guard(c);
+    NEED(c, forced_action || action, "sampling needs an action output");
+    return policy_act_common(c, obs, mask, forced_action, n, step_index, action, logprob, entropy, value, false);
+}
+
+extern "C" ppo_status ppo_policy_act_greedy(ppo_ctx* c, const float* obs, const uint8_t* mask, int64_t n, int64_t* action, float* logprob, float* entropy,
+                                            float* value) {
+    NEED(c, c && obs, "null argument");
+    DeviceGuard dev_guard(c);
+    NEED(c, action != nullptr, "ppo_policy_act_greedy needs an action output");
+    NEED(c, n >= 0, "n < 0");
+    return policy_act_common(c, obs, mask, nullptr, n, 0, action, logprob, entropy, value, true);
 }
 
 extern "C" ppo_status ppo_categorical(int32_t dist_kind, const float* logits, const uint8_t* mask, const int64_t* value, int64_t n, int32_t A,
@@ -1147,6 +1170,120 @@ extern "C" ppo_status ppo_rollout(ppo_ctx* c, const int64_t* forced_actions) {
     c->rollout_steps += c->T;
     c->global_step += (int64_t)c->T * c->cfg.global_num_envs;  // global_step += num_envs per step (:526)
     c->fin_pending = true;
+    return PPO_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Evaluation (no reference counterpart; the reference's README offers trained policies for inference, its code has only train())
+// ---------------------------------------------------------------------------------------------------------
+static ppo_status eval_scratch(ppo_ctx* c, int64_t n, int64_t seed) {
+    if (n > c->eval_cap) {
+        int64_t cap = std::max<int64_t>(c->eval_cap, 1024);
+        while (cap < n) cap *= 2;
+        float* r = nullptr;
+        int32_t* l = nullptr;
+        HIPCHK(c, hipStreamSynchronize(c->stream));   // nothing enqueued may still be using the arrays that are replaced
+        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&r), (size_t)cap * sizeof(float)));
+        if (hipMalloc(reinterpret_cast<void**>(&l), (size_t)cap * 2 * sizeof(int32_t)) != hipSuccess) {
+            (void)hipFree(r);
+            return fail(c, PPO_ERR_HIP, "ppo_evaluate: no device memory for %lld episodes", (long long)cap);
+        }
+        for (void* old : { (void*)c->eval_ret, (void*)c->eval_len })
+            if (old) { c->allocs.erase(std::remove(c->allocs.begin(), c->allocs.end(), old), c->allocs.end()); (void)hipFree(old); }
+        c->allocs.push_back(r); c->allocs.push_back(l);
+        c->eval_ret = r; c->eval_len = l; c->eval_cap = cap;
+    }
+    if (c->cfg.env_kind != PPO_ENV_CARTPOLE) return PPO_OK;
+    if (n > c->eval_table_cap) {
+        int64_t cap = std::max<int64_t>(c->eval_table_cap, 1024);
+        while (cap < n) cap *= 2;
+        float* d = nullptr;
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&d), (size_t)cap * 4 * sizeof(float)));
+        if (c->eval_table) { c->allocs.erase(std::remove(c->allocs.begin(), c->allocs.end(), (void*)c->eval_table), c->allocs.end()); (void)hipFree(c->eval_table); }
+        c->allocs.push_back(d);
+        c->eval_table = d; c->eval_table_cap = cap; c->eval_table_rows = 0;
+    }
+    if (c->eval_table_rows < n || c->eval_table_seed != seed) {
+        // row e of the stream is the same whatever the stream's length (one generator, drawn in order): a table of cap rows serves every n <= cap
+        c->eval_table_h.resize((size_t)c->eval_table_cap * 4);
+        ppo_cartpole_reset_stream_h(seed, c->eval_table_cap, c->eval_table_h.data());
+        HIPCHK(c, hipStreamSynchronize(c->stream));   // a launch of an earlier call may still read the table
+        HIPCHK(c, hipMemcpy(c->eval_table, c->eval_table_h.data(), (size_t)c->eval_table_cap * 4 * sizeof(float), hipMemcpyHostToDevice));
+        c->eval_table_rows = c->eval_table_cap; c->eval_table_seed = seed;
+    }
+    return PPO_OK;
+}
+
+extern "C" ppo_status ppo_evaluate(ppo_ctx* c, int64_t n_episodes, int64_t seed, int32_t greedy, float* ep_return, int32_t* ep_length, ppo_eval_stats* out_h) {
+    NEED(c, c != nullptr, "null ctx");
+    if (c->host_env || c->gen || c->cfg.env_kind == PPO_ENV_SYNTHETIC)
+        return fail(c, PPO_ERR_UNSUPPORTED, "ppo_evaluate steps the context's device environment (CartPole, MountainCar); this context's environment is %s: "
+                                            "run the episodes on the host with one ppo_policy_act_greedy launch per step",
+                    c->host_env ? "the caller's (PPO_ENV_HOST)" : "synthetic (PPO_ENV_SYNTHETIC)");
+    NEED(c, out_h != nullptr, "ppo_evaluate: out_h is null");
+    NEED(c, n_episodes > 0, "ppo_evaluate: n_episodes <= 0");
+    NEED(c, n_episodes < (1ll << 28), "ppo_evaluate: more than 2^28 episodes");
+    NEED(c, c->cfg.max_episode_steps > 0, "ppo_evaluate: max_episode_steps <= 0 (an episode would never be truncated)");
+    NEED(c, c->O == (c->cfg.env_kind == PPO_ENV_CARTPOLE ? 4 : 2), "ppo_evaluate: obs_size does not match the environment");
+    DeviceGuard dev_guard(c);
+    ppo_status s = eval_scratch(c, n_episodes, seed);
+    if (s != PPO_OK) return s;
+    EvalArgs a{};
+    a.params = B_<float>(c, PPO_BUF_PARAMS);
+    a.L = c->L;
+    a.dist_kind = c->cfg.dist_kind;
+    a.env_kind = c->cfg.env_kind;
+    a.max_episode_steps = c->cfg.max_episode_steps;
+    a.greedy = greedy != 0;
+    a.n_episodes = n_episodes;
+    a.seed = seed;
+    a.reset_table = c->eval_table;
+    a.ep_return = c->eval_ret;
+    a.ep_length = c->eval_len;
+    a.ep_trunc = c->eval_len + c->eval_cap;
+    // the arithmetic ppo_rollout would choose now, from the same weight-range snapshot; the snapshot is read into locals and the fallback is not counted:
+    // the call leaves the training state, ppo_profile.vector_fallback_launches included, as it was
+    a.vector_kernel = (c->rollout_vector || !policy_act16_serves(c->L)) ? 1 : 0;
+    if (!a.vector_kernel) {
+        s = refresh_weight_range(c);
+        if (s != PPO_OK) return s;
+        const uint32_t bits = __atomic_load_n(c->wr_host + PPO_WR_W3, __ATOMIC_RELAXED);
+        float w3;
+        std::memcpy(&w3, &bits, 4);
+        if (!(w3 < WR_LIMIT_W3)) a.vector_kernel = 1;
+    }
+    HIPCHK(c, launch_evaluate(a, c->stream));
+    if (ep_return) HIPCHK(c, hipMemcpyAsync(ep_return, c->eval_ret, (size_t)n_episodes * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    if (ep_length) HIPCHK(c, hipMemcpyAsync(ep_length, c->eval_len, (size_t)n_episodes * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
+    std::vector<float> ret((size_t)n_episodes);
+    std::vector<int32_t> len((size_t)n_episodes), trunc((size_t)n_episodes);
+    HIPCHK(c, hipMemcpyAsync(ret.data(), c->eval_ret, ret.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(len.data(), c->eval_len, len.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(trunc.data(), c->eval_len + c->eval_cap, trunc.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    // the summary: f64, in index order
+    ppo_eval_stats o{};
+    o.episodes = n_episodes;
+    double rs = 0.0, ls = 0.0;
+    o.return_min = o.return_max = ret[0];
+    o.length_min = o.length_max = len[0];
+    for (int64_t i = 0; i < n_episodes; i++) {
+        rs += (double)ret[i];
+        ls += (double)len[i];
+        o.env_steps += len[i];
+        o.return_min = std::min(o.return_min, (double)ret[i]);
+        o.return_max = std::max(o.return_max, (double)ret[i]);
+        o.length_min = std::min<int64_t>(o.length_min, len[i]);
+        o.length_max = std::max<int64_t>(o.length_max, len[i]);
+        o.truncated += trunc[i] != 0;
+    }
+    o.return_mean = rs / (double)n_episodes;
+    o.length_mean = ls / (double)n_episodes;
+    double q = 0.0;
+    for (int64_t i = 0; i < n_episodes; i++) { const double d = (double)ret[i] - o.return_mean; q += d * d; }
+    o.return_std = std::sqrt(q / (double)n_episodes);
+    *out_h = o;
     return PPO_OK;
 }
 

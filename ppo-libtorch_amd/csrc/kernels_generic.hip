@@ -15,7 +15,8 @@ __global__ void fill_kernel(float* p, int64_t n, float v) {
 
 // One thread per row: per-head (masked) categorical over the row's logits; samples (Philox, same keying as the specialised path:
 // counter (row, step / 4, head, 0), word step % 4) unless an action is forced.  Agent.cpp:137-170.
-template <int DIST>
+// GREEDY: the head's mode (argmax of m_probs, first index on equal values; Categorical.cpp:139-141, CategoricalMasked.cpp:160-162), no random number.
+template <int DIST, bool GREEDY = false>
 __global__ __launch_bounds__(128) void heads_kernel(GenLayout L, const float* __restrict__ logits, const uint8_t* __restrict__ mask,
                                                     const int64_t* __restrict__ forced, int64_t n, int64_t seed, int64_t row_offset, int64_t step_index,
                                                     int64_t* action, float* logprob, float* entropy) {
@@ -30,7 +31,10 @@ __global__ __launch_bounds__(128) void heads_kernel(GenLayout L, const float* __
         const uint8_t* mrow = (DIST == PPO_DIST_MASKED && mask) ? mask + r * L.act + off : nullptr;
         const float en = categorical_head<DIST>(z, p, mrow, A);
         int a;
-        if (forced) {
+        if constexpr (GREEDY) {
+            a = 0;
+            for (int k = 1; k < A; k++) if (p[k] > p[a]) a = k;
+        } else if (forced) {
             a = (int)forced[r * L.n_heads + h];
         } else {
             const uint4 w = philox4x32_10((uint32_t)seed, (uint32_t)((uint64_t)seed >> 32), (uint32_t)(row_offset + r), (uint32_t)(step_index >> 2), (uint32_t)h, 0u);
@@ -1151,10 +1155,14 @@ hipError_t gen_forward(const GenericCtx& g, const float* params, int net, const 
 }
 
 hipError_t gen_heads(const GenLayout& L, int dist_kind, const float* logits, const uint8_t* mask, const int64_t* forced, int64_t n, int64_t seed,
-                     int64_t row_offset, int64_t step_index, int64_t* action, float* logprob, float* entropy, hipStream_t s) {
+                     int64_t row_offset, int64_t step_index, int64_t* action, float* logprob, float* entropy, hipStream_t s, bool greedy) {
     if (n <= 0) return hipSuccess;
     const dim3 grid((unsigned)((n + 127) / 128)), block(128);
-    if (dist_kind == PPO_DIST_MASKED)
+    if (greedy && dist_kind == PPO_DIST_MASKED)
+        hipLaunchKernelGGL((heads_kernel<PPO_DIST_MASKED, true>), grid, block, 0, s, L, logits, mask, nullptr, n, seed, row_offset, step_index, action, logprob, entropy);
+    else if (greedy)
+        hipLaunchKernelGGL((heads_kernel<PPO_DIST_CATEGORICAL, true>), grid, block, 0, s, L, logits, mask, nullptr, n, seed, row_offset, step_index, action, logprob, entropy);
+    else if (dist_kind == PPO_DIST_MASKED)
         hipLaunchKernelGGL(heads_kernel<PPO_DIST_MASKED>, grid, block, 0, s, L, logits, mask, forced, n, seed, row_offset, step_index, action, logprob, entropy);
     else
         hipLaunchKernelGGL(heads_kernel<PPO_DIST_CATEGORICAL>, grid, block, 0, s, L, logits, mask, forced, n, seed, row_offset, step_index, action, logprob, entropy);

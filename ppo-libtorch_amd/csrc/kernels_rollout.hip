@@ -66,7 +66,9 @@ __device__ __forceinline__ float critic_head(const float* __restrict__ p, const 
 // philox_cache (optional): the four 32-bit words of the Philox call that serves steps 4k .. 4k+3 of head 0, kept by the caller
 // across steps and refreshed here when step_index % 4 == 0 (or when *cache_valid is false).
 // heads_from_logits: everything after the actor's output layer (z[] = raw logits in, consumed).
-template <int DIST, int AMAX, int EXACTA = 0>
+// GREEDY: Categorical::mode / CategoricalMasked::mode (Categorical.cpp:139-141, CategoricalMasked.cpp:160-162) instead of a draw: argmax of m_probs, the
+// FIRST index on equal values; no random number is formed.
+template <int DIST, int AMAX, int EXACTA = 0, bool GREEDY = false>
 __device__ __forceinline__ void heads_from_logits(float* z, const NetLayout& L, const uint8_t* mask_row, bool all_valid, bool sample, int64_t seed,
                                                   int64_t row_global, int64_t step_index, int* act, float& logprob, float& entropy,
                                                   uint4* philox_cache = nullptr, bool* cache_valid = nullptr, bool cache_fresh = false) {
@@ -109,7 +111,15 @@ __device__ __forceinline__ void heads_from_logits(float* z, const NetLayout& L, 
             }
         }
         ent = -ent;
-        if (sample) {
+        if constexpr (GREEDY) {
+            int best = 0;
+            float pb = -1.0f;
+#pragma unroll
+            for (int a = 0; a < AMAX; a++) if (a >= off && a < off + Ah) {
+                if (pr[a] > pb) { pb = pr[a]; best = a - off; }
+            }
+            act[h] = best;
+        } else if (sample) {
             // one Philox call feeds four consecutive steps: counter (row, step / 4, head, 0), word step % 4
             uint4 w;
             if (philox_cache && h == 0) {
@@ -142,7 +152,7 @@ __device__ __forceinline__ void heads_from_logits(float* z, const NetLayout& L, 
     }
 }
 
-template <int DIST, int AMAX, int EXACTA = 0>
+template <int DIST, int AMAX, int EXACTA = 0, bool GREEDY = false>
 __device__ __forceinline__ void actor_heads(const float* __restrict__ p, const NetLayout& L, float h2a, int lane, const uint8_t* mask_row,
                                             bool all_valid, bool sample, int64_t seed, int64_t row_global, int64_t step_index, int* act,
                                             float& logprob, float& entropy, uint4* philox_cache = nullptr, bool* cache_valid = nullptr) {
@@ -153,7 +163,7 @@ __device__ __forceinline__ void actor_heads(const float* __restrict__ p, const N
         z[a] = 0.0f;
         if (a < A) z[a] = wave_sum(h2a * p[L.w3[1] + a * PPO_HIDDEN + lane]) + p[L.b3[1] + a];
     }
-    heads_from_logits<DIST, AMAX, EXACTA>(z, L, mask_row, all_valid, sample, seed, row_global, step_index, act, logprob, entropy, philox_cache, cache_valid);
+    heads_from_logits<DIST, AMAX, EXACTA, GREEDY>(z, L, mask_row, all_valid, sample, seed, row_global, step_index, act, logprob, entropy, philox_cache, cache_valid);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -846,65 +856,54 @@ __device__ __forceinline__ void host_commit_row(const HostStepArgs& hs, int64_t 
 // ---------------------------------------------------------------------------------------------------------
 // HOST (ppo_host_act, caller-stepped envs): the commit of step t - 1 and the rollout stores of step t around the same body (host_commit_row; the one
 // trailing HostStepArgs names the buffers).  HOST = false has no trailing argument: the stand-alone policy's kernel, signature and code as they were.
-template <int DIST, int OBS, int EXACTA, bool HOST = false, class... Host>
-__global__ __launch_bounds__(64) void policy_act16_kernel(const float* __restrict__ P, NetLayout L, const float* __restrict__ obs,
-                                                          const uint8_t* __restrict__ mask, const int64_t* __restrict__ forced, int64_t n,
-                                                          int64_t seed, int64_t env_offset, int64_t step_index, int64_t* action, float* logprob,
-                                                          float* entropy, int32_t* error_flag, const Host... host) {
-    const int lane = threadIdx.x, e = lane & 15, kg = lane >> 4;
-    constexpr int A = EXACTA;
-    const HostStepArgs* hs = host_step_args(host...);
-    // the four blocks' weights as MFMA A operands (rollout16_kernel's per-wave preamble, block mw = 0 .. 3)
+// The actor as one wave holds it for policy_act16_kernel's arithmetic -- the four blocks' weights as MFMA A operands (rollout16_kernel's per-wave
+// preamble, block mw = 0 .. 3) -- and the logits of a 16-row tile from them.  Shared by the stand-alone policy and the evaluation launch
+// (eval16_kernel): ONE definition, so the two agree in every bit.
+template <int OBS, int A>
+struct Act16Net {
     float a1[4], b1d[4][4], b2d[4][4], b3[A];
     r16_u32x4 w2a[4][2][2];   // [block][chunk c][term]
     uint2 w3a[4][2];          // [block][term]
+
+    __device__ __forceinline__ void load(const float* __restrict__ P, const NetLayout& L, int e, int kg, int32_t* error_flag) {
 #pragma unroll
-    for (int mw = 0; mw < 4; mw++) {
-        a1[mw] = kg < OBS ? P[L.w1[1] + (16 * mw + e) * OBS + kg] : 0.0f;
+        for (int mw = 0; mw < 4; mw++) {
+            a1[mw] = kg < OBS ? P[L.w1[1] + (16 * mw + e) * OBS + kg] : 0.0f;
 #pragma unroll
-        for (int c = 0; c < 2; c++) {
-            float w[8];
+            for (int c = 0; c < 2; c++) {
+                float w[8];
 #pragma unroll
-            for (int q = 0; q < 8; q++) w[q] = P[L.w2[1] + (16 * mw + e) * PPO_HIDDEN + 32 * c + 16 * (q >> 2) + 4 * kg + (q & 3)];
+                for (int q = 0; q < 8; q++) w[q] = P[L.w2[1] + (16 * mw + e) * PPO_HIDDEN + 32 * c + 16 * (q >> 2) + 4 * kg + (q & 3)];
 #pragma unroll
-            for (int q = 0; q < 4; q++) {
-                uint32_t p1, p2;
-                r16_split2(w[2 * q], w[2 * q + 1], p1, p2);
-                w2a[mw][c][0][q] = p1; w2a[mw][c][1][q] = p2;
+                for (int q = 0; q < 4; q++) {
+                    uint32_t p1, p2;
+                    r16_split2(w[2 * q], w[2 * q + 1], p1, p2);
+                    w2a[mw][c][0][q] = p1; w2a[mw][c][1][q] = p2;
+                }
             }
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int u = 16 * mw + 4 * kg + r;
+                b1d[mw][r] = P[L.b1[1] + u];
+                b2d[mw][r] = P[L.b2[1] + u];
+            }
+            float w[4];
+#pragma unroll
+            for (int r = 0; r < 4; r++) w[r] = e < A ? 256.0f * P[L.w3[1] + e * PPO_HIDDEN + 16 * mw + 4 * kg + r] : 0.0f;
+            const float w3max = fmaxf(fmaxf(fabsf(w[0]), fabsf(w[1])), fmaxf(fabsf(w[2]), fabsf(w[3])));
+            if (w3max >= 65280.0f && error_flag) atomicOr(error_flag, PPO_ERRFLAG_ROLLOUT_RANGE);   // (the host sends such weights to policy_act_kernel: see ppo_policy_act)
+            uint32_t p1a, p2a, p1b, p2b;
+            r16_split2(w[0], w[1], p1a, p2a);
+            r16_split2(w[2], w[3], p1b, p2b);
+            w3a[mw][0] = make_uint2(p1a, p1b); w3a[mw][1] = make_uint2(p2a, p2b);
         }
 #pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const int u = 16 * mw + 4 * kg + r;
-            b1d[mw][r] = P[L.b1[1] + u];
-            b2d[mw][r] = P[L.b2[1] + u];
-        }
-        float w[4];
-#pragma unroll
-        for (int r = 0; r < 4; r++) w[r] = e < A ? 256.0f * P[L.w3[1] + e * PPO_HIDDEN + 16 * mw + 4 * kg + r] : 0.0f;
-        const float w3max = fmaxf(fmaxf(fabsf(w[0]), fabsf(w[1])), fmaxf(fabsf(w[2]), fabsf(w[3])));
-        if (w3max >= 65280.0f && error_flag) atomicOr(error_flag, PPO_ERRFLAG_ROLLOUT_RANGE);   // (the host sends such weights to policy_act_kernel: see ppo_policy_act)
-        uint32_t p1a, p2a, p1b, p2b;
-        r16_split2(w[0], w[1], p1a, p2a);
-        r16_split2(w[2], w[3], p1b, p2b);
-        w3a[mw][0] = make_uint2(p1a, p1b); w3a[mw][1] = make_uint2(p2a, p2b);
+        for (int aa = 0; aa < A; aa++) b3[aa] = P[L.b3[1] + aa];
     }
-#pragma unroll
-    for (int aa = 0; aa < A; aa++) b3[aa] = P[L.b3[1] + aa];
-    const int64_t n_tiles = (n + 15) / 16;
-    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        int64_t row = 16 * tile + e;
-        const bool live = row < n;      // a ragged last tile: its idle columns compute on row n - 1 and store nothing
-        if (!live) row = n - 1;
-        const float xk = kg < OBS ? obs[row * OBS + kg] : 0.0f;
-        if constexpr (HOST) {
-            if (live && kg == 0) host_commit_row(*hs, row);
-            if (live && kg < OBS) {
-                hs->obs_t[row * OBS + kg] = xk;                       // m_obs[step] = next_obs (PPO_Discrete.cpp:529)
-                if (hs->commit) hs->next_obs[row * OBS + kg] = xk;
-            }
-            if (live && kg < A && hs->masks_t) hs->masks_t[row * A + kg] = mask ? mask[row * A + kg] : (uint8_t)1;   // PPO_MultiDiscrete.cpp:555
-        }
+
+    // xk: component kg of the observation of this lane's row (column e of the tile), 0 for kg >= OBS.  z[0 .. A): the row's logits, valid in lanes kg = 0
+    // (rows a = 0 .. 3 of a 16 x 16 result sit there; the other lanes compute on: their rows of W3 are zero, their z is the bias)
+    __device__ __forceinline__ void logits(float xk, float* z) const {
         // layer 1 + tanh, block by block; the fp16 terms of block mw are one half of chunk (mw >> 1)'s B operand
         uint2 t1[4], t2[4];
 #pragma unroll
@@ -949,14 +948,45 @@ __global__ __launch_bounds__(64) void policy_act16_kernel(const float* __restric
 #pragma unroll
             for (int aa = 0; aa < A; aa++) part[mw][aa] = zacc[aa];
         }
-        // rows a = 0 .. 3 of a 16 x 16 result sit in lanes kg = 0: those lanes carry the row's logits (the others compute on and store nothing)
-        float z[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
+#pragma unroll
+        for (int aa = 0; aa < 4; aa++) z[aa] = 0.0f;
 #pragma unroll
         for (int aa = 0; aa < A; aa++) z[aa] = __builtin_fmaf(((part[0][aa] + part[1][aa]) + part[2][aa]) + part[3][aa], 0x1p-8f, b3[aa]);
+    }
+};
+
+// GREEDY (ppo_policy_act_greedy): the head's mode instead of a draw (heads_from_logits)
+template <int DIST, int OBS, int EXACTA, bool HOST = false, bool GREEDY = false, class... Host>
+__global__ __launch_bounds__(64) void policy_act16_kernel(const float* __restrict__ P, NetLayout L, const float* __restrict__ obs,
+                                                          const uint8_t* __restrict__ mask, const int64_t* __restrict__ forced, int64_t n,
+                                                          int64_t seed, int64_t env_offset, int64_t step_index, int64_t* action, float* logprob,
+                                                          float* entropy, int32_t* error_flag, const Host... host) {
+    const int lane = threadIdx.x, e = lane & 15, kg = lane >> 4;
+    constexpr int A = EXACTA;
+    const HostStepArgs* hs = host_step_args(host...);
+    Act16Net<OBS, A> net;
+    net.load(P, L, e, kg, error_flag);
+    const int64_t n_tiles = (n + 15) / 16;
+    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        int64_t row = 16 * tile + e;
+        const bool live = row < n;      // a ragged last tile: its idle columns compute on row n - 1 and store nothing
+        if (!live) row = n - 1;
+        const float xk = kg < OBS ? obs[row * OBS + kg] : 0.0f;
+        if constexpr (HOST) {
+            if (live && kg == 0) host_commit_row(*hs, row);
+            if (live && kg < OBS) {
+                hs->obs_t[row * OBS + kg] = xk;                       // m_obs[step] = next_obs (PPO_Discrete.cpp:529)
+                if (hs->commit) hs->next_obs[row * OBS + kg] = xk;
+            }
+            if (live && kg < A && hs->masks_t) hs->masks_t[row * A + kg] = mask ? mask[row * A + kg] : (uint8_t)1;   // PPO_MultiDiscrete.cpp:555
+        }
+        // rows a = 0 .. 3 of a 16 x 16 result sit in lanes kg = 0: those lanes carry the row's logits (the others compute on and store nothing)
+        float z[4];
+        net.logits(xk, z);
         int act[PPO_MAX_HEADS];
         if (forced) act[0] = (int)forced[row];
         float lp, en;
-        heads_from_logits<DIST, 4, EXACTA>(z, L, mask ? mask + row * A : nullptr, mask == nullptr, forced == nullptr, seed, env_offset + row, step_index, act, lp, en);
+        heads_from_logits<DIST, 4, EXACTA, GREEDY>(z, L, mask ? mask + row * A : nullptr, mask == nullptr, forced == nullptr, seed, env_offset + row, step_index, act, lp, en);
         if (live && kg == 0) {
             if (logprob) logprob[row] = lp;
             if (entropy) entropy[row] = en;
@@ -990,7 +1020,7 @@ __global__ __launch_bounds__(64) void values_kernel(const float* __restrict__ pa
 // ---------------------------------------------------------------------------------------------------------
 // HOST: as in policy_act16_kernel (ppo_host_act in the vector form: PPO_KERNEL_ROLLOUT_VECTOR, weights outside rollout16_kernel's range, the shapes it
 // does not serve)
-template <int DIST, int OBS, int AMAX, bool HOST = false, class... Host>
+template <int DIST, int OBS, int AMAX, bool HOST = false, bool GREEDY = false, class... Host>
 __global__ __launch_bounds__(64) void policy_act_kernel(const float* __restrict__ params, NetLayout L, const float* __restrict__ obs,
                                                         const uint8_t* __restrict__ mask, const int64_t* __restrict__ forced, int64_t n,
                                                         int64_t seed, int64_t env_offset, int64_t step_index, int64_t* action,
@@ -1022,14 +1052,120 @@ __global__ __launch_bounds__(64) void policy_act_kernel(const float* __restrict_
         int act[PPO_MAX_HEADS];
         if (forced) for (int h = 0; h < H; h++) act[h] = (int)forced[row * H + h];
         float lp, en;
-        actor_heads<DIST, AMAX>(params, L, h2a, lane, mask ? mask + row * A : nullptr, mask == nullptr, forced == nullptr, seed,
-                                env_offset + row, step_index, act, lp, en);
+        actor_heads<DIST, AMAX, 0, GREEDY>(params, L, h2a, lane, mask ? mask + row * A : nullptr, mask == nullptr, forced == nullptr, seed,
+                                           env_offset + row, step_index, act, lp, en);
         if (lane == 0) {
             if (logprob) logprob[row] = lp;
             if (entropy) entropy[row] = en;
         }
         if (action && lane < H) action[row * H + lane] = act[lane];
         if constexpr (HOST) { if (lane < H) hs->actions_t[row * H + lane] = act[lane]; }   // :537
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Evaluation run (ppo_evaluate): n_episodes whole episodes of the context's device env under the current policy as ONE launch; only an episode's return,
+// length and truncated flag leave the chip.  Episode e is a pure function of (parameters, seed, e, greedy, max_episode_steps): it starts from row e of the
+// evaluation reset table (CartPole: ppo_cartpole_reset_stream_h(seed, n_episodes)) or from env_reset<MOUNTAINCAR> keyed (seed, e, reset 0), steps as
+// stepEnvs does (PPO_Discrete.cpp:440-458: reward summed in f32 in step order, truncation at max_episode_steps), and acts by the head's mode (GREEDY) or
+// by the sampler keyed (seed, row e, step t of the episode, head).  Episode lengths differ, so a SLOT (one column of a 16-row tile, or one wave of the
+// vector form) that finishes an episode takes a further one by a static rule -- slot s of S runs episodes s, s + S, s + 2 S, ... -- and nothing depends on
+// how many slots the launch has.  A slot that has run out of episodes keeps computing on its last start state and stores nothing; a wave leaves the loop
+// when all of its slots are done (a wave-uniform test: the MFMAs need every lane; no LDS barrier spans waves here, workgroups are one wave).
+// The physics are env_step<ENV>, the logits Act16Net's (= policy_act16_kernel's = rollout16_kernel's) or, in the vector form, policy_act_kernel's
+// trunk_forward + actor_heads: stepping the same start states through ppo_policy_act_greedy / ppo_policy_act + ppo_env_transition gives the same bits.
+// ---------------------------------------------------------------------------------------------------------
+template <int ENV, int OBS>
+__device__ __forceinline__ void eval_start_state(float* st, const EvalArgs& a, int64_t ep) {
+    const int64_t k = ep < a.n_episodes ? ep : a.n_episodes - 1;   // idle slots: the last episode's start state (in bounds, results not stored)
+    if constexpr (ENV == PPO_ENV_CARTPOLE) env_reset<ENV>(st, a.reset_table, (int)k, a.seed, k);
+    else env_reset<ENV>(st, nullptr, 0, a.seed, k);
+}
+
+template <int ENV, int DIST, int OBS, int EXACTA, bool GREEDY>
+__global__ __launch_bounds__(64) void eval16_kernel(EvalArgs a) {
+    const int lane = threadIdx.x, e = lane & 15, kg = lane >> 4;
+    const NetLayout& L = a.L;
+    Act16Net<OBS, EXACTA> net;
+    net.load(a.params, L, e, kg, nullptr);
+    const int64_t S = (int64_t)gridDim.x * 16;
+    int64_t ep = (int64_t)blockIdx.x * 16 + e;      // the four lanes kg of a column hold identical copies of the slot's state; lane kg = 0 stores
+    bool active = ep < a.n_episodes;
+    float st[OBS];
+    eval_start_state<ENV, OBS>(st, a, ep);
+    int ep_len = 0;
+    float ep_rew = 0.0f;
+    uint4 philox_words = make_uint4(0u, 0u, 0u, 0u);
+    bool philox_valid = false;
+    while (__any(active)) {
+        float xk = 0.0f;
+#pragma unroll
+        for (int k = 0; k < OBS; k++) xk = kg == k ? st[k] : xk;
+        float z[4];
+        net.logits(xk, z);
+        int act[PPO_MAX_HEADS];
+        act[0] = 0;
+        float lp, en;
+        // MountainCar::getActionMask is all-ones (MountainCar.cpp:69-77): every action valid, as in the rollout
+        heads_from_logits<DIST, 4, EXACTA, GREEDY>(z, L, nullptr, true, true, a.seed, ep < a.n_episodes ? ep : a.n_episodes - 1, (int64_t)ep_len, act, lp, en,
+                                                   &philox_words, &philox_valid);
+        const int action = __shfl(act[0], e, 64);   // the column's logits live in its lane kg = 0
+        int term;
+        const float reward = env_step<ENV>(st, action, term);
+        ep_len += 1;        // CartPole.cpp:90-91
+        ep_rew += reward;
+        const int trunc = ep_len == a.max_episode_steps ? 1 : 0;
+        if (trunc) term = 1;
+        if (term) {
+            if (active && kg == 0) {
+                a.ep_return[ep] = ep_rew;
+                a.ep_length[ep] = ep_len;
+                a.ep_trunc[ep] = trunc;
+            }
+            if (active) ep += S;
+            active = ep < a.n_episodes;
+            eval_start_state<ENV, OBS>(st, a, ep);
+            ep_len = 0;
+            ep_rew = 0.0f;
+            philox_valid = false;
+        }
+    }
+}
+
+// The vector form (PPO_KERNEL_ROLLOUT_VECTOR, weights outside rollout16_kernel's range, policies rollout16_kernel does not serve): one wave per slot,
+// policy_act_kernel's arithmetic; everything is wave-uniform.
+template <int ENV, int DIST, int OBS, int AMAX, bool GREEDY>
+__global__ __launch_bounds__(64) void evalv_kernel(EvalArgs a) {
+    __shared__ __attribute__((aligned(16))) float lds[PPO_HIDDEN];
+    const int lane = threadIdx.x;
+    const NetLayout& L = a.L;
+    LaneNet<OBS> actor;
+    load_lane_net<OBS>(actor, a.params, L, 1, lane);
+    for (int64_t ep = blockIdx.x; ep < a.n_episodes; ep += gridDim.x) {
+        float st[OBS];
+        eval_start_state<ENV, OBS>(st, a, ep);
+        int ep_len = 0, term = 0, trunc = 0;
+        float ep_rew = 0.0f;
+        uint4 philox_words = make_uint4(0u, 0u, 0u, 0u);
+        bool philox_valid = false;
+        while (!term) {
+            const float h2a = trunk_forward<OBS>(actor, st, lds, lane);
+            int act[PPO_MAX_HEADS];
+#pragma unroll
+            for (int h = 0; h < PPO_MAX_HEADS; h++) act[h] = 0;
+            float lp, en;
+            actor_heads<DIST, AMAX, 0, GREEDY>(a.params, L, h2a, lane, nullptr, true, true, a.seed, ep, (int64_t)ep_len, act, lp, en, &philox_words, &philox_valid);
+            const float reward = env_step<ENV>(st, act[0], term);
+            ep_len += 1;
+            ep_rew += reward;
+            trunc = ep_len == a.max_episode_steps ? 1 : 0;
+            if (trunc) term = 1;
+        }
+        if (lane == 0) {
+            a.ep_return[ep] = ep_rew;
+            a.ep_length[ep] = ep_len;
+            a.ep_trunc[ep] = trunc;
+        }
     }
 }
 
@@ -1340,7 +1476,7 @@ bool policy_act16_serves(const NetLayout& L) { return L.n_heads == 1 && (L.act =
 hipError_t launch_policy_act(const float* params, const NetLayout& L, int dist_kind, const float* obs, const uint8_t* mask,
                              const int64_t* forced_action, int64_t n, int64_t seed, int64_t env_offset, int64_t step_index,
                              int64_t* action, float* logprob, float* entropy, float* value, bool value_only, hipStream_t s, bool as_rollout16,
-                             int32_t* error_flag) {
+                             int32_t* error_flag, bool greedy) {
     if (n <= 0) return hipSuccess;
     // every critic evaluation of a context goes through ONE kernel (the matrix-core one for the reference's observation widths), so
     // stand-alone calls reproduce the fused rollout's values bit for bit
@@ -1355,8 +1491,15 @@ hipError_t launch_policy_act(const float* params, const NetLayout& L, int dist_k
         // the shapes launch_rollout gives to rollout16_kernel: the same arithmetic, bit for bit (policy_act16_kernel)
         const int64_t tiles = (n + 15) / 16;
         const dim3 grid16((unsigned)(tiles < 4096 ? tiles : 4096));
-#define PPO_LAUNCH_ACT16(DIST, OBS, AA) \
-    hipLaunchKernelGGL((policy_act16_kernel<DIST, OBS, AA>), grid16, dim3(64), 0, s, params, L, obs, mask, forced_action, n, seed, env_offset, step_index, action, logprob, entropy, error_flag)
+#define PPO_LAUNCH_ACT16(DIST, OBS, AA)                                                                                                                                        \
+    do {                                                                                                                                                                      \
+        if (greedy)                                                                                                                                                           \
+            hipLaunchKernelGGL((policy_act16_kernel<DIST, OBS, AA, false, true>), grid16, dim3(64), 0, s, params, L, obs, mask, nullptr, n, seed, env_offset, step_index,     \
+                               action, logprob, entropy, error_flag);                                                                                                         \
+        else                                                                                                                                                                  \
+            hipLaunchKernelGGL((policy_act16_kernel<DIST, OBS, AA>), grid16, dim3(64), 0, s, params, L, obs, mask, forced_action, n, seed, env_offset, step_index, action,    \
+                               logprob, entropy, error_flag);                                                                                                                 \
+    } while (0)
 #define PPO_LAUNCH_ACT16_D(OBS, AA) \
     do { if (dist_kind == PPO_DIST_CATEGORICAL) PPO_LAUNCH_ACT16(PPO_DIST_CATEGORICAL, OBS, AA); else PPO_LAUNCH_ACT16(PPO_DIST_MASKED, OBS, AA); } while (0)
         if (L.obs == 4 && L.act == 2) PPO_LAUNCH_ACT16_D(4, 2);
@@ -1368,14 +1511,19 @@ hipError_t launch_policy_act(const float* params, const NetLayout& L, int dist_k
         return hipGetLastError();
     }
     const unsigned grid = (unsigned)(n < 8192 ? n : 8192);
-#define PPO_LAUNCH_ACT(DIST, OBS)                                                                                                     \
-    do {                                                                                                                              \
-        if (L.act <= 4)                                                                                                               \
-            hipLaunchKernelGGL((policy_act_kernel<DIST, OBS, 4>), dim3(grid), dim3(64), 0, s, params, L, obs, mask, forced_action, n, seed, \
-                               env_offset, step_index, action, logprob, entropy, value);                                                            \
-        else                                                                                                                          \
-            hipLaunchKernelGGL((policy_act_kernel<DIST, OBS, PPO_MAX_ACT>), dim3(grid), dim3(64), 0, s, params, L, obs, mask, forced_action, n, \
-                               seed, env_offset, step_index, action, logprob, entropy, value);                                                      \
+#define PPO_LAUNCH_ACT_A(DIST, OBS, AMAX)                                                                                                        \
+    do {                                                                                                                                         \
+        if (greedy)                                                                                                                              \
+            hipLaunchKernelGGL((policy_act_kernel<DIST, OBS, AMAX, false, true>), dim3(grid), dim3(64), 0, s, params, L, obs, mask, nullptr, n, seed, \
+                               env_offset, step_index, action, logprob, entropy, value);                                                         \
+        else                                                                                                                                     \
+            hipLaunchKernelGGL((policy_act_kernel<DIST, OBS, AMAX>), dim3(grid), dim3(64), 0, s, params, L, obs, mask, forced_action, n, seed,   \
+                               env_offset, step_index, action, logprob, entropy, value);                                                         \
+    } while (0)
+#define PPO_LAUNCH_ACT(DIST, OBS)                               \
+    do {                                                        \
+        if (L.act <= 4) PPO_LAUNCH_ACT_A(DIST, OBS, 4);         \
+        else PPO_LAUNCH_ACT_A(DIST, OBS, PPO_MAX_ACT);          \
     } while (0)
     if (L.obs == 4) {
         if (dist_kind == PPO_DIST_CATEGORICAL) PPO_LAUNCH_ACT(PPO_DIST_CATEGORICAL, 4); else PPO_LAUNCH_ACT(PPO_DIST_MASKED, 4);
@@ -1387,6 +1535,46 @@ hipError_t launch_policy_act(const float* params, const NetLayout& L, int dist_k
         return hipErrorInvalidValue;
     }
 #undef PPO_LAUNCH_ACT
+#undef PPO_LAUNCH_ACT_A
+    return hipGetLastError();
+}
+
+int eval_slots(const EvalArgs& a) {
+    if (a.vector_kernel) return (int)(a.n_episodes < 16384 ? a.n_episodes : 16384);
+    const int64_t tiles = (a.n_episodes + 15) / 16;
+    return 16 * (int)(tiles < 4096 ? tiles : 4096);   // 4096 one-wave workgroups: 16 per CU of an MI355X
+}
+
+hipError_t launch_evaluate(const EvalArgs& a, hipStream_t s) {
+    if (a.n_episodes <= 0 || a.max_episode_steps <= 0) return hipErrorInvalidValue;
+    const int slots = eval_slots(a);
+    const bool cart = a.env_kind == PPO_ENV_CARTPOLE && a.L.obs == 4, car = a.env_kind == PPO_ENV_MOUNTAINCAR && a.L.obs == 2;
+    if (!cart && !car) return hipErrorInvalidValue;
+    if (cart && !a.reset_table) return hipErrorInvalidValue;
+    const bool masked = a.dist_kind != PPO_DIST_CATEGORICAL;
+#define PPO_EVAL16(ENV, DIST, OBS, AA)                                                                                                \
+    do {                                                                                                                              \
+        if (a.greedy) hipLaunchKernelGGL((eval16_kernel<ENV, DIST, OBS, AA, true>), dim3((unsigned)(slots / 16)), dim3(64), 0, s, a); \
+        else hipLaunchKernelGGL((eval16_kernel<ENV, DIST, OBS, AA, false>), dim3((unsigned)(slots / 16)), dim3(64), 0, s, a);         \
+    } while (0)
+#define PPO_EVALV(ENV, DIST, OBS, AMAX)                                                                                         \
+    do {                                                                                                                        \
+        if (a.greedy) hipLaunchKernelGGL((evalv_kernel<ENV, DIST, OBS, AMAX, true>), dim3((unsigned)slots), dim3(64), 0, s, a); \
+        else hipLaunchKernelGGL((evalv_kernel<ENV, DIST, OBS, AMAX, false>), dim3((unsigned)slots), dim3(64), 0, s, a);         \
+    } while (0)
+#define PPO_EVAL(ENV, DIST, OBS)                                                       \
+    do {                                                                               \
+        if (!a.vector_kernel && a.L.act == 2) PPO_EVAL16(ENV, DIST, OBS, 2);           \
+        else if (!a.vector_kernel) PPO_EVAL16(ENV, DIST, OBS, 3);                      \
+        else if (a.L.act <= 4) PPO_EVALV(ENV, DIST, OBS, 4);                           \
+        else PPO_EVALV(ENV, DIST, OBS, PPO_MAX_ACT);                                   \
+    } while (0)
+    if (!a.vector_kernel && !policy_act16_serves(a.L)) return hipErrorInvalidValue;
+    if (cart) { if (masked) PPO_EVAL(PPO_ENV_CARTPOLE, PPO_DIST_MASKED, 4); else PPO_EVAL(PPO_ENV_CARTPOLE, PPO_DIST_CATEGORICAL, 4); }
+    else { if (masked) PPO_EVAL(PPO_ENV_MOUNTAINCAR, PPO_DIST_MASKED, 2); else PPO_EVAL(PPO_ENV_MOUNTAINCAR, PPO_DIST_CATEGORICAL, 2); }
+#undef PPO_EVAL
+#undef PPO_EVALV
+#undef PPO_EVAL16
     return hipGetLastError();
 }
 

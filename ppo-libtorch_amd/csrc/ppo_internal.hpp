@@ -560,8 +560,25 @@ hipError_t launch_aos_to_soa(const float* aos, float* soa, int N, int O, bool to
 hipError_t launch_policy_act(const float* params, const NetLayout& L, int dist_kind, const float* obs, const uint8_t* mask,
                              const int64_t* forced_action, int64_t n, int64_t seed, int64_t env_offset, int64_t step_index,
                              int64_t* action, float* logprob, float* entropy, float* value, bool value_only, hipStream_t s, bool as_rollout16 = false,
-                             int32_t* error_flag = nullptr);   // as_rollout16: rollout16_kernel's arithmetic where that kernel serves the shape (policy_act16_serves)
+                             int32_t* error_flag = nullptr, bool greedy = false);   // as_rollout16: rollout16_kernel's arithmetic where that kernel serves the shape (policy_act16_serves); greedy: the heads' modes instead of draws (forced_action is ignored)
 bool policy_act16_serves(const NetLayout& L);
+
+// ppo_evaluate: whole episodes of the context's device env under the current policy as one launch (kernels_rollout.hip: eval16_kernel / evalv_kernel)
+struct EvalArgs {
+    const float* params;
+    NetLayout L;
+    int dist_kind, env_kind;
+    int max_episode_steps;
+    int greedy;                 // the heads' modes; 0: the sampler keyed (seed, episode, step of the episode, head)
+    int vector_kernel;          // policy_act_kernel's arithmetic instead of policy_act16_kernel's (the choice ppo_rollout would make now)
+    int64_t n_episodes, seed;
+    const float* reset_table;   // CartPole: [n_episodes][4] = ppo_cartpole_reset_stream_h(seed, n_episodes); MountainCar: unused
+    float* ep_return;           // [n_episodes]
+    int32_t* ep_length;         // [n_episodes]
+    int32_t* ep_trunc;          // [n_episodes] 1: the episode reached max_episode_steps
+};
+int eval_slots(const EvalArgs& a);   // episodes in flight (slot s runs episodes s, s + slots, ...)
+hipError_t launch_evaluate(const EvalArgs& a, hipStream_t s);
 
 // Caller-stepped environments (PPO_ENV_HOST; api.hip: ppo_host_*).  ppo_host_observe stages step t - 1's outputs of the caller's envs; the next
 // launch COMMITS them (rewards / finished episodes of row t - 1, NEXT_DONE, NEXT_OBS, the per-env episode sums) and, in the act kernels, goes on to

@@ -64,6 +64,24 @@ AgentOutput Agent::getActionAndValueDiscrete(const Tensor& x, Tensor action) { r
 
 AgentOutput Agent::getActionAndValueMasked(const Tensor& x, const Tensor& mask, Tensor action) { return act(x, &mask, action); }
 
+AgentOutput Agent::actGreedy(const Tensor& x, const Tensor* mask) {
+    const int64_t n = x.size(0), H = m_actionSpaceSize;
+    AgentOutput o;
+    o.action = Tensor(m_device, { n, H }, DType::i64);
+    o.logprob = Tensor(m_device, { n }, DType::f32);
+    o.entropy = Tensor(m_device, { n }, DType::f32);
+    o.value = Tensor(m_device, { n, 1 }, DType::f32);
+    ppo::check(ppo_policy_act_greedy(m_ctx, x.data<float>(), mask ? mask->data<uint8_t>() : nullptr, n, o.action.data<int64_t>(), o.logprob.data<float>(),
+                                     o.entropy.data<float>(), o.value.data<float>()),
+               m_ctx, "Agent::getActionGreedy");
+    ppo::check(ppo_sync(m_ctx), m_ctx, "sync");
+    return o;
+}
+
+AgentOutput Agent::getActionGreedy(const Tensor& x) { return actGreedy(x, nullptr); }
+
+AgentOutput Agent::getActionGreedyMasked(const Tensor& x, const Tensor& mask) { return actGreedy(x, &mask); }
+
 std::vector<float> Agent::parameters() const {
     std::vector<float> p(static_cast<size_t>(ppo_param_count(m_ctx)));
     ppo::check(ppo_params_get_h(m_ctx, p.data(), static_cast<int64_t>(p.size())), m_ctx, "Agent::parameters");

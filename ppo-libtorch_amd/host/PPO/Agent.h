@@ -32,6 +32,10 @@ class Agent {
     ppo::Tensor getValue(const ppo::Tensor& x);                                                       // Agent.cpp:107-109
     AgentOutput getActionAndValueDiscrete(const ppo::Tensor& x, ppo::Tensor action = ppo::Tensor());  // :117-128
     AgentOutput getActionAndValueMasked(const ppo::Tensor& x, const ppo::Tensor& mask, ppo::Tensor action = ppo::Tensor());  // :137-170
+    // Categorical::mode / CategoricalMasked::mode through the agent (Categorical.cpp:139-141, CategoricalMasked.cpp:160-162): the deterministic action
+    // per head (argmax of the probabilities, first index on equal values) with its log-prob, entropy and the value.  Draws nothing: m_sampleCalls stays.
+    AgentOutput getActionGreedy(const ppo::Tensor& x);
+    AgentOutput getActionGreedyMasked(const ppo::Tensor& x, const ppo::Tensor& mask);
     void printAgent();
 
     // flat parameter vector in Agent::parameters() order (critic first, Agent.cpp:65-66)
@@ -48,5 +52,6 @@ class Agent {
 
   private:
     AgentOutput act(const ppo::Tensor& x, const ppo::Tensor* mask, const ppo::Tensor& action);
+    AgentOutput actGreedy(const ppo::Tensor& x, const ppo::Tensor* mask);
     bool m_owns = false;
 };

@@ -1,5 +1,6 @@
 #include "PPOAlgorithm.h"
 
+#include <algorithm>
 #include <cmath>
 #include <filesystem>
 #include <fstream>
@@ -155,6 +156,42 @@ void PPOAlgorithm::construct() {
     m_values = bufferView(PPO_BUF_VALUES, { T, N }, DType::f32);
     if (m_dist_kind == PPO_DIST_MASKED) m_action_masks = bufferView(PPO_BUF_MASKS, { T, N, m_action_size }, DType::u8);
     m_episode_stats = std::make_unique<CircularBuffer>(static_cast<size_t>(100));
+}
+
+EvalResult PPOAlgorithm::evaluate(int64_t episodes, bool greedy, int64_t seed) {
+    EvalResult r;
+    const int64_t n = episodes > 0 ? episodes : 1;
+    Tensor ret(m_device, { n }, DType::f32), len(m_device, { n }, DType::i32);
+    ppo::check(ppo_evaluate(m_ctx, episodes, seed, greedy ? 1 : 0, ret.data<float>(), len.data<int32_t>(), &r.stats), m_ctx, "evaluate");
+    r.returns = ret.cpu<float>();
+    r.lengths = len.cpu<int32_t>();
+    return r;
+}
+
+ppo_eval_stats PPOAlgorithm::summarizeEpisodes(const std::vector<float>& returns, const std::vector<int32_t>& lengths, int64_t max_episode_steps) {
+    ppo_eval_stats o{};
+    const size_t n = returns.size();
+    if (n == 0 || lengths.size() != n) return o;
+    o.episodes = static_cast<int64_t>(n);
+    o.return_min = o.return_max = returns[0];
+    o.length_min = o.length_max = lengths[0];
+    double rs = 0.0, ls = 0.0;
+    for (size_t i = 0; i < n; i++) {
+        rs += returns[i];
+        ls += lengths[i];
+        o.env_steps += lengths[i];
+        o.return_min = std::min(o.return_min, static_cast<double>(returns[i]));
+        o.return_max = std::max(o.return_max, static_cast<double>(returns[i]));
+        o.length_min = std::min<int64_t>(o.length_min, lengths[i]);
+        o.length_max = std::max<int64_t>(o.length_max, lengths[i]);
+        o.truncated += lengths[i] == max_episode_steps;
+    }
+    o.return_mean = rs / static_cast<double>(n);
+    o.length_mean = ls / static_cast<double>(n);
+    double q = 0.0;
+    for (size_t i = 0; i < n; i++) { const double d = returns[i] - o.return_mean; q += d * d; }
+    o.return_std = std::sqrt(q / static_cast<double>(n));
+    return o;
 }
 
 AgentOutput PPOAlgorithm::actImpl(const Tensor& obs, const Tensor* mask, const Tensor& action) const {

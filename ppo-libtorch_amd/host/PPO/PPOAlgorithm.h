@@ -17,6 +17,13 @@
 #include "../Utils/Utils.h"
 #include "Agent.h"
 
+// What evaluate() returns: the summary ppo_evaluate forms (include/ppo_hip.h ppo_eval_stats) and the per-episode numbers it is formed from.
+struct EvalResult {
+    ppo_eval_stats stats{};
+    std::vector<float> returns;
+    std::vector<int32_t> lengths;
+};
+
 class PPOAlgorithm {
   public:
     virtual ~PPOAlgorithm();
@@ -29,6 +36,14 @@ class PPOAlgorithm {
     std::array<ppo::Tensor, 2> calcAdvantage(const ppo::Tensor& next_obs, const ppo::Tensor& next_done) const;  // {returns, advantages}, :274-331
     ppo::Tensor getApproxKLAndClippedObj(const ppo::Tensor& ratio, const ppo::Tensor& logratio);                 // :343-356
     void train();                                                                                              // :485-690
+
+    // Held-out evaluation of the current policy (not in the reference, whose only quality signal is the mean over the last 100 exploration episodes,
+    // :474-480): `episodes` whole episodes of the context's device env in one launch (ppo_evaluate), greedy (Categorical::mode) or sampled, episode e
+    // from start state e of `seed` (default m_seed).  Prints nothing and leaves the training state untouched.  PPO_HostEnv has its own evaluate().
+    EvalResult evaluate(int64_t episodes, bool greedy = true) { return evaluate(episodes, greedy, m_seed); }
+    EvalResult evaluate(int64_t episodes, bool greedy, int64_t seed);
+    // the summary of per-episode returns / lengths as ppo_evaluate forms it (f64, index order; truncated = episodes of max_episode_steps steps)
+    static ppo_eval_stats summarizeEpisodes(const std::vector<float>& returns, const std::vector<int32_t>& lengths, int64_t max_episode_steps);
 
     // Controlling Environments
     std::tuple<ppo::Tensor, ppo::Tensor, ppo::Tensor> stepEnvs(const ppo::Tensor& action);                      // :413-483

@@ -11,6 +11,7 @@
 // pool job at a time; envs must not share mutable state with each other (the facade's CartPole owns its Device: no shared HIP stream or context).
 // The context (PPO_ENV_HOST) owns parameters, AdamW state, rollout buffers, sampler and episode statistics: include/ppo_hip.h ppo_host_*.
 #pragma once
+#include <algorithm>
 #include <atomic>
 #include <cstring>
 #include <functional>
@@ -93,6 +94,90 @@ class PPO_HostEnv : public PPOAlgorithm {
         if (bad_width >= 0)
             throw std::runtime_error("The environment returned an observation of size " + std::to_string(bad_width.load()) +
                                      ", but your config defined the expected observation size to be " + std::to_string(m_obs_size) + ".");
+    }
+
+    // Held-out greedy evaluation on the caller's envs: episode e runs on a FRESH env factory(e) (never a training env: m_envs, their episode sums
+    // and the context's rollout state stay as they are), up to num_envs episodes in flight on a thread pool, one ppo_policy_act_greedy launch per
+    // step over the envs in flight, truncation at max_episode_steps as stepEnvs applies it.  An episode's return and length are the env's own
+    // episode_reward / episode_length (:474-480).  Prints nothing.
+    EvalResult evaluate(int64_t episodes, EnvFactory factory) {
+        if (episodes <= 0 || !factory) throw std::runtime_error("PPO_HostEnv::evaluate needs episodes > 0 and an env factory");
+        const size_t N = static_cast<size_t>(m_num_envs), O = static_cast<size_t>(m_obs_size), A = static_cast<size_t>(m_action_size);
+        EvalResult r;
+        r.returns.assign(static_cast<size_t>(episodes), 0.0f);
+        r.lengths.assign(static_cast<size_t>(episodes), 0);
+        std::vector<std::shared_ptr<Env>> envs;     // the episodes in flight, densely packed
+        std::vector<int64_t> episode;
+        std::vector<float> obs(N * O, 0.0f);
+        std::vector<uint8_t> mask(Masked ? N * A : 0, 1);
+        std::vector<char> finished(N, 0);
+        ppo::Tensor d_obs(m_device, { m_num_envs, m_obs_size }, ppo::DType::f32), d_act(m_device, { m_num_envs, 1 }, ppo::DType::i64);
+        ppo::Tensor d_mask;
+        if (Masked) d_mask = ppo::Tensor(m_device, { m_num_envs, m_action_size }, ppo::DType::u8);
+        // a pool of its own: m_threadPool runs only inside train() (which starts and stops it), and evaluate() may be called from train()'s m_on_update
+        const int64_t hw = static_cast<int64_t>(std::thread::hardware_concurrency());
+        ThreadPool pool(std::max<int64_t>(1, std::min<int64_t>(m_num_envs, hw)));
+        pool.start();
+        int64_t next = 0;
+        std::atomic<int64_t> bad_width{ -1 };
+        std::atomic<bool> failed{ false };
+        auto put = [&](size_t k, const std::vector<float>& o) {
+            if (o.size() != O) bad_width = static_cast<int64_t>(o.size());
+            else std::memcpy(obs.data() + k * O, o.data(), sizeof(float) * O);
+        };
+        while (next < episodes || !envs.empty()) {
+            while (envs.size() < N && next < episodes) {   // start further episodes, in index order
+                envs.push_back(factory(next));
+                episode.push_back(next++);
+                put(envs.size() - 1, envs.back()->reset());
+            }
+            if (bad_width >= 0) throw std::runtime_error("an environment returned an observation of size " + std::to_string(bad_width.load()) + " on reset");
+            const size_t k_live = envs.size();
+            if constexpr (Masked) {
+                for (size_t k = 0; k < k_live; k++) {
+                    const auto m = envs[k]->getActionMask();
+                    for (size_t a = 0; a < A; a++) mask[k * A + a] = maskAt(m, a) ? 1 : 0;
+                }
+                d_mask.copy_from_host(mask);
+            }
+            d_obs.copy_from_host(obs);
+            ppo::check(ppo_policy_act_greedy(m_ctx, d_obs.template data<float>(), Masked ? d_mask.template data<uint8_t>() : nullptr, static_cast<int64_t>(k_live),
+                                             d_act.template data<int64_t>(), nullptr, nullptr, nullptr),
+                       m_ctx, "evaluate");
+            ppo::check(ppo_sync(m_ctx), m_ctx, "sync");
+            const std::vector<int64_t> action = d_act.template cpu<int64_t>();
+            for (size_t k = 0; k < k_live; k++)
+                pool.queueJob([&, k]() { try {
+                    Env& env = *envs[k];
+                    auto [o, reward, terminated, info] = env.step(action[k]);
+                    (void)reward; (void)info;
+                    if (static_cast<int64_t>(env.episode_length) == m_max_episode_steps) terminated = true;
+                    finished[k] = terminated ? 1 : 0;
+                    if (terminated) {
+                        r.returns[static_cast<size_t>(episode[k])] = static_cast<float>(env.episode_reward);
+                        r.lengths[static_cast<size_t>(episode[k])] = static_cast<int32_t>(env.episode_length);
+                    } else {
+                        put(k, o);
+                    }
+                } catch (...) { failed = true; } });   // (the pool swallows a job's exception: an episode that cannot step must not be stepped for ever)
+            pool.waitForJobsToFinish();
+            if (failed) throw std::runtime_error("PPO_HostEnv::evaluate: an environment's step threw");
+            if (bad_width >= 0) throw std::runtime_error("an environment returned an observation of size " + std::to_string(bad_width.load()));
+            size_t w = 0;   // drop the finished episodes, keep the rest packed
+            for (size_t k = 0; k < k_live; k++) {
+                if (finished[k]) continue;
+                if (w != k) {
+                    envs[w] = envs[k];
+                    episode[w] = episode[k];
+                    std::memcpy(obs.data() + w * O, obs.data() + k * O, sizeof(float) * O);
+                }
+                w++;
+            }
+            envs.resize(w);
+            episode.resize(w);
+        }
+        r.stats = summarizeEpisodes(r.returns, r.lengths, m_max_episode_steps);
+        return r;
     }
 
   protected:
