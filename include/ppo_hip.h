@@ -349,6 +349,7 @@ PPO_API ppo_status ppo_set_learning_rate(ppo_ctx* ctx, double lr);
  *   per iteration:  ppo_host_rollout_begin(ctx)
  *                   T x { ppo_host_act(ctx, mask, actions); step the envs on the host; ppo_host_observe(ctx, obs, reward, done, fin_len, fin_rew) }
  *                   ppo_host_rollout_end(ctx)                        enqueues the values, the scan and the update (ppo_stats_snapshot / ppo_read_stats as usual)
+ *   (or group by group, the env stepping of one group overlapped with the policy call of the next: "Env groups" below)
  *
  * Arithmetic: that of a device-env context of the same shape.  The sampler key is (seed, env_offset + row, rollout_steps + t, head); for the
  * reference's shapes the actor runs rollout16_kernel's products (policy_act16_kernel) or, under PPO_KERNEL_ROLLOUT_VECTOR, the vector form, chosen
@@ -378,6 +379,37 @@ PPO_API ppo_status ppo_host_observe(ppo_ctx* ctx, const float* next_obs_h, const
 /* After T act/observe pairs: values of every stored observation and the bootstrap value (:280), the scan, the update: the rest of
  * ppo_train_iteration.  Enqueued; rollout_steps += T, global_step += T * global_num_envs, finished episodes pending, as after ppo_rollout. */
 PPO_API ppo_status ppo_host_rollout_end(ppo_ctx* ctx);
+
+/* Env groups: the same rollout taken group by group, so that the caller steps one group's envs while the GPU and the host link serve another's.
+ *
+ *   per iteration:  ppo_host_rollout_begin_groups(ctx, n_groups, bounds)
+ *                   per group g, T x { ppo_host_group_act(ctx, g, mask_g);              enqueues and returns
+ *                                      ppo_host_group_actions(ctx, g, actions_g);       waits for group g's launch only
+ *                                      step the group's envs on the host;
+ *                                      ppo_host_group_observe(ctx, g, obs_g, reward_g, done_g, fin_len_g, fin_rew_g) }
+ *                   ppo_host_rollout_end(ctx)                                           once every group has observed its step T - 1
+ *
+ * Group g owns env rows [bounds[g], bounds[g + 1]); every array of a group call holds that group's rows only ([n_g, ...]).  Groups advance
+ * independently: the calls of different groups interleave in any order, and one group may be any number of steps ahead of another.  A typical
+ * pipeline enqueues ppo_host_group_act(g + 1) before it reads ppo_host_group_actions(g), and steps group g on worker threads meanwhile.
+ * The rollout does not depend on the grouping or the interleaving in a single bit: the sampler is keyed by (seed, env_offset + row, rollout_steps + t,
+ * head), a row's arithmetic does not depend on the launch it sits in, and finished episodes reach the statistics from FIN_LEN / FIN_REW after the
+ * rollout (tests/test_gpu_host_env_groups.py).  Everything is enqueued on the context's one stream; only the host-side wait is per group.
+ * Errors: PPO_ERR_STATE (nothing changed; the message names group and step) for a group call on a rollout opened with ppo_host_rollout_begin,
+ * ppo_host_act / ppo_host_observe on a rollout opened here, a group's calls out of sequence, an act beyond step T - 1, ppo_host_rollout_end before
+ * every group is done, a begin while a rollout is open, and device-env contexts; PPO_ERR_INVALID for n_groups outside 1 .. PPO_HOST_MAX_GROUPS,
+ * bounds that are not 0 = b[0] < b[1] < ... < b[n_groups] = num_envs, g out of range, null pointers, and fin_len_h / fin_rew_h not both-or-neither. */
+#define PPO_HOST_MAX_GROUPS 8
+/* ppo_host_rollout_begin with the envs cut into n_groups row ranges: bounds_h i32 [n_groups + 1] (host; copied).  Every group starts at step 0. */
+PPO_API ppo_status ppo_host_rollout_begin_groups(ppo_ctx* ctx, int32_t n_groups, const int32_t* bounds_h);
+/* ppo_host_act for group g's rows at the group's step t_g, WITHOUT the wait: commit of the group's staged step t_g - 1, actor forward, sample, the
+ * rollout stores of step t_g, actions into pinned host memory, an event of the group's own.  mask_h u8 [n_g,A] or NULL; copied before return. */
+PPO_API ppo_status ppo_host_group_act(ppo_ctx* ctx, int32_t g, const uint8_t* mask_h);
+/* Waits for group g's act (its event, not the stream: launches enqueued behind it keep running) and copies its actions out: action_h i64 [n_g,H]. */
+PPO_API ppo_status ppo_host_group_actions(ppo_ctx* ctx, int32_t g, int64_t* action_h);
+/* ppo_host_observe for group g's rows (all arrays [n_g, ...]); host memory only, no launch. */
+PPO_API ppo_status ppo_host_group_observe(ppo_ctx* ctx, int32_t g, const float* next_obs_h, const float* reward_h, const int32_t* done_h,
+                                          const int32_t* fin_len_h, const float* fin_rew_h);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Evaluation (new; the reference reports only the mean over the last 100 exploration episodes of its training envs, PPO_Discrete.cpp:474-480, Utils.h:72-78)

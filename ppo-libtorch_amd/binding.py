@@ -34,6 +34,8 @@ _BUF_DTYPE = dict(OBS=np.float32, ACTIONS=np.int32, LOGPROBS=np.float32, REWARDS
                   EXP_AVG_SQ=np.float32, ENV_STATE=np.float32, EP_LEN=np.int32, EP_REW=np.float32, RESET_COUNT=np.int32,
                   PERM=np.int32, FIN_LEN=np.int32, FIN_REW=np.float32)
 
+MAX_HOST_GROUPS = 8   # PPO_HOST_MAX_GROUPS
+
 # every symbol include/ppo_hip.h declares (tests/test_abi_symbols.py checks the built library exports exactly these)
 ABI_SYMBOLS = [
     "ppo_abi_version", "ppo_ctx_create", "ppo_ctx_destroy", "ppo_last_error", "ppo_sync", "ppo_stream", "ppo_get_config",
@@ -47,6 +49,7 @@ ABI_SYMBOLS = [
     "ppo_comm_init_local", "ppo_comm_exchange_handle", "ppo_comm_init_exchange", "ppo_comm_exchange_timeouts",
     "ppo_comm_set_wait_limit", "ppo_stats_snapshot", "ppo_stats_snapshot_read",
     "ppo_host_env_reset", "ppo_host_rollout_begin", "ppo_host_act", "ppo_host_observe", "ppo_host_rollout_end",
+    "ppo_host_rollout_begin_groups", "ppo_host_group_act", "ppo_host_group_actions", "ppo_host_group_observe",
     "ppo_policy_act_greedy", "ppo_evaluate",
 ]
 
@@ -354,8 +357,52 @@ class Context:
         obs = np.ascontiguousarray(obs, np.float32).reshape(self.N, self.O)
         _check(lib().ppo_host_env_reset(self.h, obs.ctypes.data_as(C.c_void_p)), self.h)
 
-    def host_rollout_begin(self):
-        _check(lib().ppo_host_rollout_begin(self.h), self.h)
+    def host_rollout_begin(self, groups=None):
+        """Opens a rollout.  groups: None = the ungrouped calls (host_act / host_observe); an int G = G equal contiguous env groups (the remainder to the
+        last); a sequence = the row boundaries [0, ..., N].  Grouped rollouts are driven by host_group_act / host_group_actions / host_group_observe."""
+        if groups is None:
+            _check(lib().ppo_host_rollout_begin(self.h), self.h)
+            self.host_bounds = None
+            return
+        if isinstance(groups, (int, np.integer)):
+            G = int(groups)
+            if G < 1 or G > self.N:
+                raise ValueError("groups = %d for %d envs" % (G, self.N))
+            bounds = [g * (self.N // G) for g in range(G)] + [self.N]
+        else:
+            bounds = [int(b) for b in groups]
+        b = np.ascontiguousarray(bounds, np.int32)
+        _check(lib().ppo_host_rollout_begin_groups(self.h, C.c_int32(len(bounds) - 1), b.ctypes.data_as(C.c_void_p)), self.h)
+        self.host_bounds = bounds
+
+    def _group_rows(self, g):
+        b = getattr(self, "host_bounds", None)
+        if b is None or not 0 <= g < len(b) - 1:
+            return self.N   # the library refuses the call; any shape will do
+        return b[g + 1] - b[g]
+
+    def host_group_act(self, g, mask=None):
+        """Enqueues step t_g of group g (commit of its staged step, act, stores) and returns; mask u8 [n_g,A] or None."""
+        n = self._group_rows(g)
+        m = np.ascontiguousarray(mask, np.uint8).reshape(n, self.A) if mask is not None else None
+        _check(lib().ppo_host_group_act(self.h, C.c_int32(g), m.ctypes.data_as(C.c_void_p) if m is not None else None), self.h)
+
+    def host_group_actions(self, g):
+        """Waits for group g's act only and returns its actions i64 [n_g,H]."""
+        out = np.empty((self._group_rows(g), self.H), np.int64)
+        _check(lib().ppo_host_group_actions(self.h, C.c_int32(g), out.ctypes.data_as(C.c_void_p)), self.h)
+        return out
+
+    def host_group_observe(self, g, obs, reward, done, fin_len=None, fin_rew=None):
+        """host_observe for group g's rows (arrays [n_g, ...])."""
+        n = self._group_rows(g)
+        o = np.ascontiguousarray(obs, np.float32).reshape(n, self.O)
+        r = np.ascontiguousarray(reward, np.float32).reshape(n)
+        d = np.ascontiguousarray(done, np.int32).reshape(n)
+        fl = np.ascontiguousarray(fin_len, np.int32).reshape(n) if fin_len is not None else None
+        fr = np.ascontiguousarray(fin_rew, np.float32).reshape(n) if fin_rew is not None else None
+        _check(lib().ppo_host_group_observe(self.h, C.c_int32(g), *(x.ctypes.data_as(C.c_void_p) if x is not None else None for x in (o, r, d, fl, fr))),
+               self.h)
 
     def host_act(self, mask=None):
         """Step t of the rollout: returns the sampled actions i64 [N,H] (host)."""

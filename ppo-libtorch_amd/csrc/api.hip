@@ -204,6 +204,18 @@ struct ppo_ctx {
     size_t host_stage_bytes = 0;
     int64_t* host_act = nullptr;               // i64 [N,H] actions, pinned and mapped: the act kernel writes them with plain stores
     int64_t* host_act_dev = nullptr;
+    // env groups (ppo_host_rollout_begin_groups): host_n_groups > 0 while a grouped rollout is open (host_phase stays 1 then: "a rollout is open").  A group
+    // owns rows [row0, row0 + rows) of every per-env array, the staging block and the action block included, and its own place in the rollout.
+    struct HostGroup {
+        int row0 = 0, rows = 0;
+        int t = 0;                    // steps acted on
+        int phase = 1;                // 1: ppo_host_group_act is next, 2: ppo_host_group_actions, 3: ppo_host_group_observe
+        bool staged = false;          // step t - 1 is staged and not committed yet
+        bool fin_given = false;
+        hipEvent_t ev = nullptr;      // recorded behind the group's act; ppo_host_group_actions waits for it (created with the context, timing disabled)
+    };
+    int host_n_groups = 0;
+    HostGroup host_grp[PPO_HOST_MAX_GROUPS];
     GenericCtx* gen = nullptr;       // non-null: synthetic env / network other than 2 x 64 (generic.hpp); every L-dependent entry point dispatches on it
     uint8_t* cur_mask = nullptr;     // generic path: action mask of the observation in NEXT_OBS, [N, A]
     bool force_collectives = false;  // PPO_COMM_SELFTEST: world == 1 but the multi-rank path (RCCL included) is taken
@@ -420,6 +432,7 @@ extern "C" void ppo_ctx_destroy(ppo_ctx* c) {
     if (c->adam_coefs_h) (void)hipHostFree(c->adam_coefs_h);
     if (c->host_stage) (void)hipHostFree(c->host_stage);
     if (c->host_act) (void)hipHostFree(c->host_act);
+    for (auto& hg : c->host_grp) if (hg.ev) (void)hipEventDestroy(hg.ev);
     if (c->wr_host) (void)hipHostFree(c->wr_host);
     if (c->snap) (void)hipHostFree(c->snap);
     for (hipEvent_t e : c->snap_ev) if (e) (void)hipEventDestroy(e);
@@ -594,6 +607,7 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
         std::memset(c->host_stage, 0, c->host_stage_bytes);
         CK(hipHostMalloc(reinterpret_cast<void**>(&c->host_act), N * c->H * sizeof(int64_t), hipHostMallocMapped));
         CK(hipHostGetDevicePointer(reinterpret_cast<void**>(&c->host_act_dev), c->host_act, 0));
+        for (auto& hg : c->host_grp) CK(hipEventCreateWithFlags(&hg.ev, hipEventDisableTiming));
     }
     if (c->gen) {
         GenericCtx& g = *c->gen;
@@ -908,15 +922,22 @@ static ppo_status gen_values(ppo_ctx* c, const float* obs, int64_t n, float* val
     }
     return PPO_OK;
 }
+// row0 / key_rows (env groups: the n rows are rows row0 .. of a batch of key_rows): the sampler's row origin, and the row count that picks between the fused
+// forward and the per-layer products -- the one launch choice here that follows the row count and changes bits -- so that a group's rows get what the
+// whole batch would.  It only matters for N > GEN_FUSED_MAX_ROWS (rows_max >= N: the ungrouped call is one chunk of N rows), which no test reaches.
+// gen_forward's own choices by row count are left alone, on a reading of gemm_kernel, not on a test beyond the sizes the suite has: launch_prec takes the
+// double-buffered variant for M <= 8192 (three-term product), and both variants walk the k chunks in ascending order with the same MFMAs per chunk; its
+// 32 x 128 tile for M <= 32 is never taken here (gen_forward always passes weight planes).  tests/test_gpu_host_env_groups.py covers groups of 7 .. 32
+// rows in batches of 50 / 64; equality for N > 8192 cut into groups <= 8192 rests on that reading.
 static ppo_status gen_policy(ppo_ctx* c, const float* obs, const uint8_t* mask, const int64_t* forced, int64_t n, int64_t step_index, int64_t* action,
-                             float* logprob, float* entropy, bool greedy = false) {
+                             float* logprob, float* entropy, bool greedy = false, int64_t row0 = 0, int64_t key_rows = 0) {
     GenericCtx& g = *c->gen;
     for (int64_t off = 0; off < n; off += g.rows_max) {
         const int64_t rows = std::min<int64_t>(g.rows_max, n - off);
-        if (gen_fused_forward_ok(g) && rows <= GEN_FUSED_MAX_ROWS) HIPCHK(c, gen_fused_forward(g, B_<float>(c, PPO_BUF_PARAMS), 1, obs + off * g.L.obs, nullptr, 0, rows, false, g.logits, c->stream));
+        if (gen_fused_forward_ok(g) && (key_rows > 0 ? std::min<int64_t>(g.rows_max, key_rows) : rows) <= GEN_FUSED_MAX_ROWS) HIPCHK(c, gen_fused_forward(g, B_<float>(c, PPO_BUF_PARAMS), 1, obs + off * g.L.obs, nullptr, 0, rows, false, g.logits, c->stream));
         else HIPCHK(c, gen_forward(g, B_<float>(c, PPO_BUF_PARAMS), 1, obs + off * g.L.obs, rows, nullptr, g.dz[0], g.dz[1], g.logits, c->stream));
         HIPCHK(c, gen_heads(g.L, c->cfg.dist_kind, g.logits, mask ? mask + off * g.L.act : nullptr, forced ? forced + off * g.L.n_heads : nullptr, rows,
-                            c->cfg.seed, c->cfg.env_offset + off, step_index, action ? action + off * g.L.n_heads : nullptr,
+                            c->cfg.seed, c->cfg.env_offset + row0 + off, step_index, action ? action + off * g.L.n_heads : nullptr,
                             logprob ? logprob + off : nullptr, entropy ? entropy + off : nullptr, c->stream, greedy));
     }
     return PPO_OK;
@@ -1855,27 +1876,28 @@ static ppo_status host_state(ppo_ctx* c, const char* what) {
 }
 
 // the staged step and the rollout rows it lands in; t = the step about to be acted on (T at the end of the rollout)
-static HostStepArgs host_args(ppo_ctx* c, int t, bool act_stores) {
+// row0 (env groups): every pointer names row row0 of its array, so that a launch over the group's n_g rows indexes them 0 .. n_g - 1
+static HostStepArgs host_args_rows(ppo_ctx* c, int t, bool act_stores, size_t row0, bool staged, bool fin_given) {
     const size_t N = (size_t)c->N;
     const unsigned char* st = c->host_stage_dev;
     HostStepArgs h{};
-    h.st_obs = reinterpret_cast<const float*>(st);
-    h.st_rew = reinterpret_cast<const float*>(st + N * c->O * 4);
-    h.st_done = reinterpret_cast<const int32_t*>(st + N * c->O * 4 + N * 4);
-    h.st_fin_len = reinterpret_cast<const int32_t*>(st + N * c->O * 4 + 2 * N * 4);
-    h.st_fin_rew = reinterpret_cast<const float*>(st + N * c->O * 4 + 3 * N * 4);
-    h.commit = c->host_staged ? 1 : 0;
-    h.fin_given = c->host_fin_given ? 1 : 0;
-    const size_t prev = t > 0 ? (size_t)(t - 1) * N : 0;
+    h.st_obs = reinterpret_cast<const float*>(st) + row0 * c->O;
+    h.st_rew = reinterpret_cast<const float*>(st + N * c->O * 4) + row0;
+    h.st_done = reinterpret_cast<const int32_t*>(st + N * c->O * 4 + N * 4) + row0;
+    h.st_fin_len = reinterpret_cast<const int32_t*>(st + N * c->O * 4 + 2 * N * 4) + row0;
+    h.st_fin_rew = reinterpret_cast<const float*>(st + N * c->O * 4 + 3 * N * 4) + row0;
+    h.commit = staged ? 1 : 0;
+    h.fin_given = fin_given ? 1 : 0;
+    const size_t prev = (t > 0 ? (size_t)(t - 1) * N : 0) + row0;
     h.rewards_prev = B_<float>(c, PPO_BUF_REWARDS) + prev;
     h.fin_len_prev = B_<int32_t>(c, PPO_BUF_FIN_LEN) + prev;
     h.fin_rew_prev = B_<float>(c, PPO_BUF_FIN_REW) + prev;
-    h.next_done = B_<int32_t>(c, PPO_BUF_NEXT_DONE);
-    h.next_obs = B_<float>(c, PPO_BUF_NEXT_OBS);
-    h.ep_len = B_<int32_t>(c, PPO_BUF_EP_LEN);
-    h.ep_rew = B_<float>(c, PPO_BUF_EP_REW);
+    h.next_done = B_<int32_t>(c, PPO_BUF_NEXT_DONE) + row0;
+    h.next_obs = B_<float>(c, PPO_BUF_NEXT_OBS) + row0 * c->O;
+    h.ep_len = B_<int32_t>(c, PPO_BUF_EP_LEN) + row0;
+    h.ep_rew = B_<float>(c, PPO_BUF_EP_REW) + row0;
     if (act_stores) {
-        const size_t tn = (size_t)t * N;
+        const size_t tn = (size_t)t * N + row0;
         h.obs_t = B_<float>(c, PPO_BUF_OBS) + tn * c->O;
         h.dones_t = B_<float>(c, PPO_BUF_DONES) + tn;
         h.masks_t = c->cfg.dist_kind == PPO_DIST_MASKED ? B_<uint8_t>(c, PPO_BUF_MASKS) + tn * c->A : nullptr;
@@ -1883,6 +1905,7 @@ static HostStepArgs host_args(ppo_ctx* c, int t, bool act_stores) {
     }
     return h;
 }
+static HostStepArgs host_args(ppo_ctx* c, int t, bool act_stores) { return host_args_rows(c, t, act_stores, 0, c->host_staged, c->host_fin_given); }
 static const uint8_t* host_stage_mask(ppo_ctx* c) {
     const size_t N = (size_t)c->N;
     return c->host_stage_dev + N * c->O * 4 + 4 * N * 4;
@@ -1906,13 +1929,9 @@ extern "C" ppo_status ppo_host_env_reset(ppo_ctx* c, const float* obs_h) {
 
 // Opens the rollout of one iteration: the LR anneal of ppo_train_iteration (:514-518), the finished episodes of the last rollout into the ring, and the
 // choice of arithmetic for the whole rollout from the same weight-range snapshot ppo_rollout takes
-extern "C" ppo_status ppo_host_rollout_begin(ppo_ctx* c) {
-    NEED(c, c != nullptr, "null ctx");
-    ppo_status s = host_state(c, "ppo_host_rollout_begin");
-    if (s != PPO_OK) return s;
-    if (c->host_phase != 0) return fail(c, PPO_ERR_STATE, "ppo_host_rollout_begin: a rollout is already open (%d of %d steps acted on)", c->host_t, c->T);
+static ppo_status host_begin(ppo_ctx* c) {
     DeviceGuard dev_guard(c);
-    s = consume_finished_episodes(c);
+    ppo_status s = consume_finished_episodes(c);
     if (s != PPO_OK) return s;
     bool as16 = false;
     if (!c->gen) {
@@ -1930,7 +1949,16 @@ extern "C" ppo_status ppo_host_rollout_begin(ppo_ctx* c) {
     c->host_t = 0;
     c->host_staged = false;
     c->host_fin_given = false;
+    c->host_n_groups = 0;
     return PPO_OK;
+}
+extern "C" ppo_status ppo_host_rollout_begin(ppo_ctx* c) {
+    NEED(c, c != nullptr, "null ctx");
+    ppo_status s = host_state(c, "ppo_host_rollout_begin");
+    if (s != PPO_OK) return s;
+    if (c->host_n_groups > 0) return fail(c, PPO_ERR_STATE, "ppo_host_rollout_begin: a rollout of %d env groups is already open", c->host_n_groups);
+    if (c->host_phase != 0) return fail(c, PPO_ERR_STATE, "ppo_host_rollout_begin: a rollout is already open (%d of %d steps acted on)", c->host_t, c->T);
+    return host_begin(c);
 }
 
 // Step t of :524-548: commit step t - 1, then m_obs[t], m_dones[t], the actor forward + sample, m_actions[t], m_logprobs[t] (and masks [t]); returns
@@ -1939,6 +1967,7 @@ extern "C" ppo_status ppo_host_act(ppo_ctx* c, const uint8_t* mask_h, int64_t* a
     NEED(c, c != nullptr, "null ctx");
     ppo_status s = host_state(c, "ppo_host_act");
     if (s != PPO_OK) return s;
+    if (c->host_n_groups > 0) return fail(c, PPO_ERR_STATE, "ppo_host_act: the open rollout is taken by env groups (ppo_host_group_act)");
     if (c->host_phase == 0) return fail(c, PPO_ERR_STATE, "ppo_host_act: no rollout is open (ppo_host_rollout_begin)");
     if (c->host_phase == 2) return fail(c, PPO_ERR_STATE, "ppo_host_act: step %d was acted on and not observed (ppo_host_observe)", c->host_t - 1);
     if (c->host_t >= c->T) return fail(c, PPO_ERR_STATE, "ppo_host_act: all %d steps of the rollout are taken (ppo_host_rollout_end)", c->T);
@@ -1979,6 +2008,7 @@ extern "C" ppo_status ppo_host_observe(ppo_ctx* c, const float* next_obs_h, cons
     NEED(c, c != nullptr, "null ctx");
     ppo_status s = host_state(c, "ppo_host_observe");
     if (s != PPO_OK) return s;
+    if (c->host_n_groups > 0) return fail(c, PPO_ERR_STATE, "ppo_host_observe: the open rollout is taken by env groups (ppo_host_group_observe)");
     if (c->host_phase != 2) return fail(c, PPO_ERR_STATE, "ppo_host_observe: no step awaits its observation (ppo_host_act first)");
     NEED(c, next_obs_h && reward_h && done_h, "null argument");
     NEED(c, (fin_len_h == nullptr) == (fin_rew_h == nullptr), "fin_len_h and fin_rew_h: both or neither");
@@ -1997,6 +2027,124 @@ extern "C" ppo_status ppo_host_observe(ppo_ctx* c, const float* next_obs_h, cons
     return PPO_OK;
 }
 
+// ---- env groups: the same rollout, group by group.  One stream: launches run in the order they were enqueued, and the activation scratch of the generic
+// engine (per context) is never used by two groups at once; what is per group is the host's wait (an event behind the group's act) and the place in
+// the rollout.  A group's rows of the staging block and of the action block are written by the host / the device only between that group's own calls,
+// which its phase keeps in order, so no group waits for another.
+static ppo_status host_group_state(ppo_ctx* c, const char* what, int32_t g) {
+    ppo_status s = host_state(c, what);
+    if (s != PPO_OK) return s;
+    if (c->host_n_groups == 0)
+        return fail(c, PPO_ERR_STATE, c->host_phase == 0 ? "%s: no rollout is open (ppo_host_rollout_begin_groups)"
+                                                         : "%s: the open rollout was not opened with env groups (ppo_host_act / ppo_host_observe)", what);
+    if (g < 0 || g >= c->host_n_groups) return fail(c, PPO_ERR_INVALID, "%s: group %d of %d", what, (int)g, c->host_n_groups);
+    return PPO_OK;
+}
+
+extern "C" ppo_status ppo_host_rollout_begin_groups(ppo_ctx* c, int32_t n_groups, const int32_t* bounds_h) {
+    NEED(c, c != nullptr, "null ctx");
+    ppo_status s = host_state(c, "ppo_host_rollout_begin_groups");
+    if (s != PPO_OK) return s;
+    if (c->host_n_groups > 0) return fail(c, PPO_ERR_STATE, "ppo_host_rollout_begin_groups: a rollout of %d env groups is already open", c->host_n_groups);
+    if (c->host_phase != 0) return fail(c, PPO_ERR_STATE, "ppo_host_rollout_begin_groups: a rollout is already open (%d of %d steps acted on)", c->host_t, c->T);
+    NEED(c, bounds_h != nullptr, "null argument");
+    if (n_groups < 1 || n_groups > PPO_HOST_MAX_GROUPS)
+        return fail(c, PPO_ERR_INVALID, "ppo_host_rollout_begin_groups: n_groups %d outside 1 .. %d", (int)n_groups, PPO_HOST_MAX_GROUPS);
+    if (bounds_h[0] != 0 || bounds_h[n_groups] != c->N)
+        return fail(c, PPO_ERR_INVALID, "ppo_host_rollout_begin_groups: bounds run from %d to %d, not from 0 to num_envs = %d", (int)bounds_h[0], (int)bounds_h[n_groups], c->N);
+    for (int g = 0; g < n_groups; g++)
+        if (bounds_h[g + 1] <= bounds_h[g])
+            return fail(c, PPO_ERR_INVALID, "ppo_host_rollout_begin_groups: group %d is empty or reversed (rows %d .. %d)", g, (int)bounds_h[g], (int)bounds_h[g + 1]);
+    s = host_begin(c);
+    if (s != PPO_OK) return s;
+    for (int g = 0; g < n_groups; g++) {
+        ppo_ctx::HostGroup& G = c->host_grp[g];
+        G.row0 = bounds_h[g]; G.rows = bounds_h[g + 1] - bounds_h[g];
+        G.t = 0; G.phase = 1; G.staged = false; G.fin_given = false;
+    }
+    c->host_n_groups = n_groups;
+    return PPO_OK;
+}
+
+extern "C" ppo_status ppo_host_group_act(ppo_ctx* c, int32_t g, const uint8_t* mask_h) {
+    NEED(c, c != nullptr, "null ctx");
+    ppo_status s = host_group_state(c, "ppo_host_group_act", g);
+    if (s != PPO_OK) return s;
+    ppo_ctx::HostGroup& G = c->host_grp[g];
+    if (G.phase == 2) return fail(c, PPO_ERR_STATE, "ppo_host_group_act: group %d: the actions of step %d were not read (ppo_host_group_actions)", (int)g, G.t - 1);
+    if (G.phase == 3) return fail(c, PPO_ERR_STATE, "ppo_host_group_act: group %d: step %d was acted on and not observed (ppo_host_group_observe)", (int)g, G.t - 1);
+    if (G.t >= c->T) return fail(c, PPO_ERR_STATE, "ppo_host_group_act: group %d: all %d steps of the rollout are taken (ppo_host_rollout_end)", (int)g, c->T);
+    DeviceGuard dev_guard(c);
+    const int t = G.t, N = c->N, n = G.rows;
+    const size_t b = (size_t)G.row0;
+    const bool masked = c->cfg.dist_kind == PPO_DIST_MASKED && mask_h != nullptr;
+    if (masked) std::memcpy(c->host_stage + (size_t)N * c->O * 4 + 4 * (size_t)N * 4 + b * c->A, mask_h, (size_t)n * c->A);
+    const HostStepArgs h = host_args_rows(c, t, true, b, G.staged, G.fin_given);
+    const uint8_t* mask = masked ? host_stage_mask(c) + b * c->A : nullptr;
+    const int64_t step = c->rollout_steps + t;
+    float* logprob_t = B_<float>(c, PPO_BUF_LOGPROBS) + (size_t)t * N + b;
+    if (c->gen) {
+        GenericCtx& ge = *c->gen;
+        int64_t* act64 = ge.act64 + b * c->H;
+        if (h.commit) HIPCHK(c, launch_host_commit(h, n, c->O, c->stream));
+        s = gen_policy(c, h.next_obs, mask, nullptr, n, step, act64, ge.step_lp + b, ge.step_en + b, false, (int64_t)b, N);
+        if (s != PPO_OK) return s;
+        HIPCHK(c, gen_store_step(ge.L, n, h.next_obs, mask, act64, ge.step_lp + b, h.next_done, h.obs_t, B_<uint8_t>(c, PPO_BUF_MASKS) + ((size_t)t * N + b) * c->A,
+                                 h.actions_t, logprob_t, h.dones_t, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->host_act + b * c->H, act64, (size_t)n * c->H * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    } else {
+        HIPCHK(c, launch_host_act(B_<float>(c, PPO_BUF_PARAMS), c->L, c->cfg.dist_kind, mask, n, c->cfg.seed, c->cfg.env_offset + (int64_t)b, step, h,
+                                  c->host_act_dev + b * c->H, logprob_t, c->host_as16, c->error_flag, c->stream));
+    }
+    HIPCHK(c, hipEventRecord(G.ev, c->stream));
+    G.staged = false;
+    G.t = t + 1;
+    G.phase = 2;
+    return PPO_OK;
+}
+
+extern "C" ppo_status ppo_host_group_actions(ppo_ctx* c, int32_t g, int64_t* action_h) {
+    NEED(c, c != nullptr, "null ctx");
+    ppo_status s = host_group_state(c, "ppo_host_group_actions", g);
+    if (s != PPO_OK) return s;
+    ppo_ctx::HostGroup& G = c->host_grp[g];
+    if (G.phase != 2)
+        return fail(c, PPO_ERR_STATE, "ppo_host_group_actions: group %d: no act awaits its read at step %d (%s)", (int)g, G.t,
+                    G.phase == 1 ? "ppo_host_group_act first" : "the actions were read; ppo_host_group_observe is next");
+    NEED(c, action_h != nullptr, "null argument");
+    DeviceGuard dev_guard(c);
+    HIPCHK(c, hipEventSynchronize(G.ev));   // this group's act only: what other groups enqueued behind it keeps running
+    std::memcpy(action_h, c->host_act + (size_t)G.row0 * c->H, (size_t)G.rows * c->H * sizeof(int64_t));
+    G.phase = 3;
+    return PPO_OK;
+}
+
+extern "C" ppo_status ppo_host_group_observe(ppo_ctx* c, int32_t g, const float* next_obs_h, const float* reward_h, const int32_t* done_h,
+                                             const int32_t* fin_len_h, const float* fin_rew_h) {
+    NEED(c, c != nullptr, "null ctx");
+    ppo_status s = host_group_state(c, "ppo_host_group_observe", g);
+    if (s != PPO_OK) return s;
+    ppo_ctx::HostGroup& G = c->host_grp[g];
+    if (G.phase != 3)
+        return fail(c, PPO_ERR_STATE, "ppo_host_group_observe: group %d: no step awaits its observation at step %d (%s)", (int)g, G.t,
+                    G.phase == 1 ? "ppo_host_group_act first" : "ppo_host_group_actions first");
+    NEED(c, next_obs_h && reward_h && done_h, "null argument");
+    NEED(c, (fin_len_h == nullptr) == (fin_rew_h == nullptr), "fin_len_h and fin_rew_h: both or neither");
+    const size_t N = (size_t)c->N, b = (size_t)G.row0, n = (size_t)G.rows;
+    unsigned char* st = c->host_stage;
+    std::memcpy(st + b * c->O * 4, next_obs_h, n * c->O * 4);
+    std::memcpy(st + N * c->O * 4 + b * 4, reward_h, n * 4);
+    std::memcpy(st + N * c->O * 4 + N * 4 + b * 4, done_h, n * 4);
+    if (fin_len_h) {
+        std::memcpy(st + N * c->O * 4 + 2 * N * 4 + b * 4, fin_len_h, n * 4);
+        std::memcpy(st + N * c->O * 4 + 3 * N * 4 + b * 4, fin_rew_h, n * 4);
+    }
+    G.fin_given = fin_len_h != nullptr;
+    G.staged = true;
+    G.phase = 1;
+    return PPO_OK;
+}
+
 // After T act / observe pairs: commit step T - 1, the values of every stored observation and the bootstrap value (:280) in one batched launch, the
 // scan and the update -- the rest of ppo_train_iteration
 extern "C" ppo_status ppo_host_rollout_end(ppo_ctx* c) {
@@ -2004,11 +2152,24 @@ extern "C" ppo_status ppo_host_rollout_end(ppo_ctx* c) {
     ppo_status s = host_state(c, "ppo_host_rollout_end");
     if (s != PPO_OK) return s;
     if (c->host_phase == 0) return fail(c, PPO_ERR_STATE, "ppo_host_rollout_end: no rollout is open (ppo_host_rollout_begin)");
-    if (c->host_t != c->T || !c->host_staged)
+    for (int g = 0; g < c->host_n_groups; g++) {
+        const ppo_ctx::HostGroup& G = c->host_grp[g];
+        if (G.t != c->T || !G.staged)
+            return fail(c, PPO_ERR_STATE, "ppo_host_rollout_end: group %d: %d of %d steps acted on, %d observed", g, G.t, c->T, G.staged ? G.t : (G.t > 0 ? G.t - 1 : 0));
+    }
+    if (c->host_n_groups == 0 && (c->host_t != c->T || !c->host_staged))
         return fail(c, PPO_ERR_STATE, "ppo_host_rollout_end: %d of %d steps acted on, %d observed", c->host_t, c->T, c->host_staged ? c->host_t : c->host_t - 1);
     DeviceGuard dev_guard(c);
     const int N = c->N, T = c->T;
-    HIPCHK(c, launch_host_commit(host_args(c, T, false), N, c->O, c->stream));
+    if (c->host_n_groups > 0) {   // every group's step T - 1 in one launch
+        HostGroupTable tab{};
+        tab.n = c->host_n_groups;
+        for (int g = 0; g < tab.n; g++) { tab.row0[g] = c->host_grp[g].row0; tab.fin_given[g] = c->host_grp[g].fin_given ? 1 : 0; }
+        tab.row0[tab.n] = N;
+        HIPCHK(c, launch_host_commit_groups(host_args_rows(c, T, false, 0, true, false), tab, N, c->O, c->stream));
+    } else {
+        HIPCHK(c, launch_host_commit(host_args(c, T, false), N, c->O, c->stream));
+    }
     float* next_obs = B_<float>(c, PPO_BUF_NEXT_OBS);
     if (c->gen) {
         s = gen_values(c, B_<float>(c, PPO_BUF_OBS), (int64_t)T * N, B_<float>(c, PPO_BUF_VALUES));
@@ -2023,6 +2184,7 @@ extern "C" ppo_status ppo_host_rollout_end(ppo_ctx* c) {
     }
     c->host_phase = 0;
     c->host_staged = false;
+    c->host_n_groups = 0;
     c->rollout_steps += T;
     c->global_step += (int64_t)T * c->cfg.global_num_envs;   // :526
     c->fin_pending = true;

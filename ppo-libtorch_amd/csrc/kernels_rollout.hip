@@ -1176,6 +1176,21 @@ __global__ __launch_bounds__(256) void host_commit_kernel(HostStepArgs hs, int N
     for (int64_t k = i; k < (int64_t)N * O; k += (int64_t)gridDim.x * 256) hs.next_obs[k] = hs.st_obs[k];
 }
 
+// ppo_host_rollout_end of a grouped rollout: the last staged step of EVERY group in one launch.  The table travels by value (kernel arguments); a row's
+// group is found by comparing against the boundaries in a fixed-length unrolled loop, so no lane indexes the table dynamically.
+__global__ __launch_bounds__(256) void host_commit_groups_kernel(HostStepArgs hs, HostGroupTable tab, int N, int O) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    for (int64_t k = i; k < N; k += (int64_t)gridDim.x * 256) {
+        int fin = tab.fin_given[0];
+#pragma unroll
+        for (int q = 1; q < PPO_HOST_MAX_GROUPS; q++) fin = (q < tab.n && k >= tab.row0[q]) ? tab.fin_given[q] : fin;
+        HostStepArgs h = hs;
+        h.fin_given = fin;
+        host_commit_row(h, k);
+    }
+    for (int64_t k = i; k < (int64_t)N * O; k += (int64_t)gridDim.x * 256) hs.next_obs[k] = hs.st_obs[k];
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // Stand-alone env kernels: one thread per env (struct-of-arrays state).
 // ---------------------------------------------------------------------------------------------------------
@@ -1627,6 +1642,15 @@ hipError_t launch_host_commit(const HostStepArgs& hs, int N, int O, hipStream_t 
     const int64_t work = (int64_t)N * (O > 1 ? O : 1);
     const unsigned grid = (unsigned)((work + 255) / 256 < 65535 ? (work + 255) / 256 : 65535);
     hipLaunchKernelGGL(host_commit_kernel, dim3(grid), dim3(256), 0, s, hs, N, O);
+    return hipGetLastError();
+}
+
+hipError_t launch_host_commit_groups(const HostStepArgs& hs, const HostGroupTable& tab, int N, int O, hipStream_t s) {
+    if (N <= 0) return hipSuccess;
+    if (tab.n < 1 || tab.n > PPO_HOST_MAX_GROUPS || tab.row0[0] != 0 || tab.row0[tab.n] != N) return hipErrorInvalidValue;
+    const int64_t work = (int64_t)N * (O > 1 ? O : 1);
+    const unsigned grid = (unsigned)((work + 255) / 256 < 65535 ? (work + 255) / 256 : 65535);
+    hipLaunchKernelGGL(host_commit_groups_kernel, dim3(grid), dim3(256), 0, s, hs, tab, N, O);
     return hipGetLastError();
 }
 

@@ -609,6 +609,18 @@ hipError_t launch_host_act(const float* params, const NetLayout& L, int dist_kin
                            int64_t step_index, const HostStepArgs& hs, int64_t* action_h, float* logprob_t, bool as16, int32_t* error_flag, hipStream_t s);
 // commit only (ppo_host_rollout_end; the generic engine's per-step commit ahead of gen_forward)
 hipError_t launch_host_commit(const HostStepArgs& hs, int N, int O, hipStream_t s);
+// Env groups (ppo_host_rollout_begin_groups): group g owns rows [row0[g], row0[g + 1]) and steps through the rollout at its own pace.  A group's act launch
+// is launch_host_act on the group's rows: every HostStepArgs pointer, the mask, the action block and logprob_t are offset to row row0[g] (and to the
+// group's own step t_g), n = the group's row count and env_offset + row0[g] is the sampler's row origin -- the kernels index by row and a row's arithmetic
+// does not depend on the tile or grid it sits in, so they run unchanged.  At the end of the rollout every group's last staged step is committed by ONE
+// launch over all N rows; the only thing that differs between groups there is whether the caller passed the finished episodes' numbers (fin_given).
+struct HostGroupTable {
+    int n;                                       // groups, 1 .. PPO_HOST_MAX_GROUPS
+    int32_t row0[PPO_HOST_MAX_GROUPS + 1];       // row0[0] = 0 < ... < row0[n] = N
+    int32_t fin_given[PPO_HOST_MAX_GROUPS];
+};
+// hs: the whole context's rows at step T (commit = 1; fin_given is taken from the table)
+hipError_t launch_host_commit_groups(const HostStepArgs& hs, const HostGroupTable& tab, int N, int O, hipStream_t s);
 hipError_t launch_categorical(int dist_kind, const float* logits, const uint8_t* mask, const int64_t* value, int64_t n, int A,
                               float* m_logits, float* m_probs, float* log_prob, float* entropy, int64_t* mode, hipStream_t s);
 

@@ -81,6 +81,7 @@ class PPOAlgorithm {
     float m_max_grad_norm;
     int64_t m_checkpoint_updates;
     int64_t m_max_episode_steps;
+    int64_t m_env_groups = 1;            // extension ([environment] env_groups): PPO_HostEnv's env groups; the device-env algorithms have no use for it
 
     int64_t m_batch_size;
     int64_t m_minibatch_size;

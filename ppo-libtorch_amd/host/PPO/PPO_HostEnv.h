@@ -10,12 +10,19 @@
 // The envs are made by a factory (default std::make_shared<Env>(m_seed), as the reference constructs its CartPoles).  Every env is stepped by one
 // pool job at a time; envs must not share mutable state with each other (the facade's CartPole owns its Device: no shared HIP stream or context).
 // The context (PPO_ENV_HOST) owns parameters, AdamW state, rollout buffers, sampler and episode statistics: include/ppo_hip.h ppo_host_*.
+//
+// Env groups (setEnvGroups(g), or `env_groups = g` in [environment] of PPOConfig.toml; default 1): with g > 1 the envs are cut into g equal contiguous
+// groups (the remainder goes to the last) and the rollout is pipelined: while the pool steps group k, the main thread enqueues the policy call of the
+// next group and collects its actions (ppo_host_group_*).  The GPU and host-link round trip of one group then hides behind the env stepping of
+// another.  Training does not depend on g in a single bit.
 #pragma once
 #include <algorithm>
 #include <atomic>
+#include <condition_variable>
 #include <cstring>
 #include <functional>
 #include <memory>
+#include <mutex>
 #include <stdexcept>
 #include <string>
 #include <tuple>
@@ -31,8 +38,9 @@ class PPO_HostEnv : public PPOAlgorithm {
 
     explicit PPO_HostEnv(EnvFactory factory = nullptr)
         : PPOAlgorithm(PPO_ENV_HOST, Masked ? PPO_DIST_MASKED : PPO_DIST_CATEGORICAL, 4, 500) {
-        getArgs();
+        getArgs();   // (reads the extension key env_groups too)
         construct();
+        setEnvGroups(m_env_groups);
         m_envs.reserve(static_cast<size_t>(m_num_envs));
         for (int64_t i = 0; i < m_num_envs; i++) m_envs.push_back(factory ? factory(i) : std::make_shared<Env>(m_seed));
         const size_t N = static_cast<size_t>(m_num_envs);
@@ -46,6 +54,14 @@ class PPO_HostEnv : public PPOAlgorithm {
     }
 
     std::vector<std::shared_ptr<Env>> m_envs;
+
+    // g env groups for trainRollout's pipeline (1: the whole batch per call, as always)
+    void setEnvGroups(int64_t g) {
+        if (g < 1 || g > PPO_HOST_MAX_GROUPS || g > m_num_envs)
+            throw std::runtime_error("env_groups = " + std::to_string(g) + ": expected 1 .. " + std::to_string(std::min<int64_t>(PPO_HOST_MAX_GROUPS, m_num_envs)));
+        m_env_groups = g;
+    }
+    int64_t envGroups() const { return m_env_groups; }
 
     // initEnvs (:365-402): env 0 once for the obs-size check, then every env (env 0 twice, as the reference); NEXT_OBS = the reset observations
     ppo::Tensor initEnvs() {
@@ -72,28 +88,9 @@ class PPO_HostEnv : public PPOAlgorithm {
     void stepEnvs(const std::vector<int64_t>& action) {
         std::atomic<int64_t> bad_width{ -1 };
         for (int64_t i = 0; i < m_num_envs; i++)
-            m_threadPool->queueJob([this, i, &action, &bad_width]() {
-                const size_t k = static_cast<size_t>(i);
-                Env& env = *m_envs[k];
-                auto [obs, reward, terminated, info] = env.step(action[k]);
-                (void)info;
-                if (static_cast<int64_t>(env.episode_length) == m_max_episode_steps) terminated = true;
-                m_fin_len[k] = 0;
-                m_fin_rew[k] = 0.0f;
-                if (terminated) {
-                    m_fin_len[k] = static_cast<int32_t>(env.episode_length);
-                    m_fin_rew[k] = static_cast<float>(env.episode_reward);
-                    obs = env.reset();
-                }
-                if (static_cast<int64_t>(obs.size()) != m_obs_size) bad_width = static_cast<int64_t>(obs.size());   // (pool jobs must not throw)
-                else copyObs(i, obs);
-                m_reward[k] = reward;
-                m_done[k] = terminated ? 1 : 0;
-            });
+            m_threadPool->queueJob([this, i, &action, &bad_width]() { stepOne(i, action, bad_width); });
         m_threadPool->waitForJobsToFinish();
-        if (bad_width >= 0)
-            throw std::runtime_error("The environment returned an observation of size " + std::to_string(bad_width.load()) +
-                                     ", but your config defined the expected observation size to be " + std::to_string(m_obs_size) + ".");
+        throwBadWidth(bad_width);
     }
 
     // Held-out greedy evaluation on the caller's envs: episode e runs on a FRESH env factory(e) (never a training env: m_envs, their episode sums
@@ -186,6 +183,7 @@ class PPO_HostEnv : public PPOAlgorithm {
     // the rollout of :524-548 with the caller's envs: one ppo_host_act (one kernel, one wait) and one stepEnvs per step; then values, advantages
     // and the update, enqueued by ppo_host_rollout_end
     void trainRollout() override {
+        if (m_env_groups > 1) { trainRolloutGroups(); return; }
         ppo::check(ppo_host_rollout_begin(m_ctx), m_ctx, "rollout");
         for (int64_t t = 0; t < m_num_steps; t++) {
             if constexpr (Masked) gatherMasks();
@@ -197,6 +195,99 @@ class PPO_HostEnv : public PPOAlgorithm {
     }
 
   private:
+    // one env's share of stepEnvs (a pool job: must not throw)
+    void stepOne(int64_t i, const std::vector<int64_t>& action, std::atomic<int64_t>& bad_width) {
+        const size_t k = static_cast<size_t>(i);
+        Env& env = *m_envs[k];
+        auto [obs, reward, terminated, info] = env.step(action[k]);
+        (void)info;
+        if (static_cast<int64_t>(env.episode_length) == m_max_episode_steps) terminated = true;
+        m_fin_len[k] = 0;
+        m_fin_rew[k] = 0.0f;
+        if (terminated) {
+            m_fin_len[k] = static_cast<int32_t>(env.episode_length);
+            m_fin_rew[k] = static_cast<float>(env.episode_reward);
+            obs = env.reset();
+        }
+        if (static_cast<int64_t>(obs.size()) != m_obs_size) bad_width = static_cast<int64_t>(obs.size());   // (pool jobs must not throw)
+        else copyObs(i, obs);
+        m_reward[k] = reward;
+        m_done[k] = terminated ? 1 : 0;
+    }
+    void throwBadWidth(const std::atomic<int64_t>& bad_width) const {
+        if (bad_width >= 0)
+            throw std::runtime_error("The environment returned an observation of size " + std::to_string(bad_width.load()) +
+                                     ", but your config defined the expected observation size to be " + std::to_string(m_obs_size) + ".");
+    }
+
+    // Jobs of ONE group still running.  The pool's waitForJobsToFinish waits for every job of every group, which would put the groups back in series.
+    struct Latch {
+        std::mutex mu;
+        std::condition_variable cv;
+        int64_t left = 0;
+        void arm(int64_t n) { std::lock_guard<std::mutex> g(mu); left = n; }
+        // notified with the mutex held: the waiter cannot return (and the latch go out of scope) until this job has let go of mutex and condition variable
+        void done() { std::lock_guard<std::mutex> g(mu); --left; cv.notify_all(); }
+        void wait() { std::unique_lock<std::mutex> g(mu); cv.wait(g, [this] { return left == 0; }); }
+    };
+    struct LatchDone {   // counts the job down however it ends (the pool swallows a job's exception)
+        Latch& l;
+        ~LatchDone() { l.done(); }
+    };
+
+    // The rollout as a pipeline over env groups.  Main thread, per group g in turn: read g's actions (waits for g's launch only), hand g's envs to the
+    // pool, then finish the group whose envs were handed over before -- wait for ITS jobs, stage its observations, enqueue its next policy call.  So the
+    // GPU and the host link serve one group while the pool steps another.  Group by group the calls are those of the ungrouped rollout, and the rollout
+    // is the same in every bit (include/ppo_hip.h, "Env groups").
+    void trainRolloutGroups() {
+        const int64_t G = m_env_groups, N = m_num_envs, T = m_num_steps;
+        std::vector<int32_t> bounds(static_cast<size_t>(G) + 1);
+        for (int64_t g = 0; g < G; g++) bounds[static_cast<size_t>(g)] = static_cast<int32_t>(g * (N / G));
+        bounds[static_cast<size_t>(G)] = static_cast<int32_t>(N);
+        std::vector<Latch> latch(static_cast<size_t>(G));
+        std::vector<int64_t> t_of(static_cast<size_t>(G), 0);
+        std::atomic<int64_t> bad_width{ -1 };
+        const size_t O = static_cast<size_t>(m_obs_size), A = static_cast<size_t>(m_action_size);
+        auto act = [&](int64_t g) {
+            const size_t b = static_cast<size_t>(bounds[static_cast<size_t>(g)]);
+            if constexpr (Masked) gatherMasks(b, static_cast<size_t>(bounds[static_cast<size_t>(g) + 1]));
+            ppo::check(ppo_host_group_act(m_ctx, static_cast<int32_t>(g), Masked ? m_mask.data() + b * A : nullptr), m_ctx, "rollout");
+        };
+        auto finish = [&](int64_t g) {   // the group's envs have been handed to the pool: wait for them, stage, enqueue the group's next step
+            const size_t b = static_cast<size_t>(bounds[static_cast<size_t>(g)]);
+            latch[static_cast<size_t>(g)].wait();
+            if (bad_width >= 0) return;
+            ppo::check(ppo_host_group_observe(m_ctx, static_cast<int32_t>(g), m_next_obs.data() + b * O, m_reward.data() + b, m_done.data() + b,
+                                              m_fin_len.data() + b, m_fin_rew.data() + b),
+                       m_ctx, "rollout");
+            if (++t_of[static_cast<size_t>(g)] < T) act(g);
+        };
+        ppo::check(ppo_host_rollout_begin_groups(m_ctx, static_cast<int32_t>(G), bounds.data()), m_ctx, "rollout");
+        for (int64_t g = 0; g < G; g++) act(g);
+        int64_t stepping = -1;   // the group whose envs the pool is stepping
+        try {
+            for (int64_t t = 0; t < T; t++)
+                for (int64_t g = 0; g < G; g++) {
+                    const int64_t b0 = bounds[static_cast<size_t>(g)], b1 = bounds[static_cast<size_t>(g) + 1];
+                    ppo::check(ppo_host_group_actions(m_ctx, static_cast<int32_t>(g), m_action.data() + b0), m_ctx, "rollout");
+                    Latch& l = latch[static_cast<size_t>(g)];
+                    l.arm(b1 - b0);
+                    for (int64_t i = b0; i < b1; i++)
+                        m_threadPool->queueJob([this, i, &l, &bad_width]() { LatchDone d{ l }; stepOne(i, m_action, bad_width); });
+                    if (stepping >= 0) finish(stepping);
+                    stepping = g;
+                    throwBadWidth(bad_width);
+                }
+            finish(stepping);
+            stepping = -1;
+            throwBadWidth(bad_width);
+        } catch (...) {
+            m_threadPool->waitForJobsToFinish();   // no job may outlive the latches and bad_width it refers to
+            throw;
+        }
+        ppo::check(ppo_host_rollout_end(m_ctx), m_ctx, "update");
+    }
+
     void copyObs(int64_t i, const std::vector<float>& o) {
         std::memcpy(m_next_obs.data() + static_cast<size_t>(i * m_obs_size), o.data(), sizeof(float) * static_cast<size_t>(m_obs_size));
     }
@@ -204,9 +295,10 @@ class PPO_HostEnv : public PPOAlgorithm {
         if constexpr (std::is_same<M, ppo::Tensor>::value) return m.template cpu<uint8_t>()[a] != 0;
         else return static_cast<bool>(m[a]);
     }
-    void gatherMasks() {
+    void gatherMasks() { gatherMasks(0, m_envs.size()); }
+    void gatherMasks(size_t i0, size_t i1) {
         const size_t A = static_cast<size_t>(m_action_size);
-        for (size_t i = 0; i < m_envs.size(); i++) {
+        for (size_t i = i0; i < i1; i++) {
             const auto m = m_envs[i]->getActionMask();
             for (size_t a = 0; a < A; a++) m_mask[i * A + a] = maskAt(m, a) ? 1 : 0;
         }

@@ -6,8 +6,15 @@
   (d) host_sps            env-steps/s of full host-stepped iterations at 4096 x 128 (zero-cost env), next to device_sps: ppo_train_iteration's
 
   --one-rollout           only one host-stepped rollout at 4096 x 128 (for a rocprofv3 --kernel-trace --memory-copy-trace --stats run around it)
+
+  --groups G [G ...] --env-cost-us X   env groups (ppo_host_group_*) against the ungrouped calls in ONE process: a worker thread stands for the caller's
+                          envs -- stepping n of the N envs takes X n / N us there (a sleep that releases the interpreter; its real cost is measured and
+                          printed as env_us) -- while the main thread makes the policy call of the next group.  Prints, for --envs N and num_steps 128, the
+                          ungrouped round trip R (X = 0), and the time of one iteration (rollout + update, stream idle) ungrouped and with each G,
+                          at X = 0 and at X = --env-cost-us (default: R), next to the ideal gain (E + R) / max(E, R) with E the measured env_us.
 """
 import argparse
+import concurrent.futures
 import ctypes as C
 import json
 import os
@@ -123,10 +130,116 @@ def device_sps(N=4096, T=128, iters=5):
     return sps
 
 
+class WorkerEnv:
+    """The caller's envs on a thread of their own: step(n) occupies that thread for cost_us * n / N and returns a future."""
+
+    def __init__(self, N, cost_us):
+        self.N, self.cost_us = N, cost_us
+        self.libc = C.CDLL(None)
+        self.pool = concurrent.futures.ThreadPoolExecutor(1, initializer=self._init)
+
+    def _init(self):
+        self.libc.prctl(29, C.c_ulong(1), C.c_ulong(0), C.c_ulong(0), C.c_ulong(0))   # PR_SET_TIMERSLACK of THIS thread: 1 ns instead of 50 us
+
+    def _busy(self, us):
+        if us > 0:
+            self.libc.usleep(C.c_uint(int(round(us))))   # (ctypes releases the interpreter lock for the call: the main thread runs)
+
+    def step(self, n):
+        return self.pool.submit(self._busy, self.cost_us * n / self.N)
+
+    def measured_us(self, reps=200):
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            self.step(self.N).result()
+        return (time.perf_counter() - t0) / reps * 1e6
+
+    def close(self):
+        self.pool.shutdown()
+
+
+def grouped_iteration_ms(c, env, work, T, G, iters=3):
+    """min over iters of one full iteration; G = 0: the ungrouped calls (ppo_host_act waits, the worker steps all envs, ppo_host_observe)"""
+    L, chk, N = P.binding.lib(), P.binding._check, c.N
+    bounds = [g * (N // G) for g in range(G)] + [N] if G else None
+    ptr = lambda a, off: C.c_void_p(a.ctypes.data + off * a.strides[0])
+    best = None
+    for it in range(iters + 1):
+        t0 = time.perf_counter()
+        if not G:
+            c.host_rollout_begin()
+            for _ in range(T):
+                chk(L.ppo_host_act(c.h, None, env.act_p), c.h)
+                work.step(N).result()
+                chk(L.ppo_host_observe(c.h, env.args[0], env.args[1], env.args[2], None, None), c.h)
+        else:
+            c.host_rollout_begin(bounds)
+            for g in range(G):
+                chk(L.ppo_host_group_act(c.h, g, None), c.h)
+            t_of, stepping, fut = [0] * G, -1, [None] * G
+
+            def finish(g):
+                fut[g].result()
+                b0 = bounds[g]
+                chk(L.ppo_host_group_observe(c.h, g, ptr(env.obs, b0), ptr(env.rew, b0), ptr(env.done, b0), None, None), c.h)
+                t_of[g] += 1
+                if t_of[g] < T:
+                    chk(L.ppo_host_group_act(c.h, g, None), c.h)
+            for k in range(T * G):
+                g = k % G
+                chk(L.ppo_host_group_actions(c.h, g, ptr(env.act, bounds[g])), c.h)
+                fut[g] = work.step(bounds[g + 1] - bounds[g])
+                if stepping >= 0:
+                    finish(stepping)
+                stepping = g
+            finish(stepping)
+        c.host_rollout_end()
+        c.sync()
+        dt = (time.perf_counter() - t0) * 1e3
+        if it > 0:
+            best = dt if best is None else min(best, dt)
+    return best
+
+
+def groups_bench(N, groups, env_cost_us, T=128):
+    c = host_ctx(N, T, iters=64)
+    env = ZeroEnv(N)
+    c.host_env_reset(env.obs)
+    R = None   # the ungrouped round trip per step with a zero-cost env, as act_us measures it
+    for r in range(3):
+        c.host_rollout_begin()
+        t0 = time.perf_counter()
+        rollout_steps(c, env, T)
+        dt = (time.perf_counter() - t0) / T * 1e6
+        c.host_rollout_end()
+        c.sync()
+        if r > 0:
+            R = dt if R is None else min(R, dt)
+    out = {"N": N, "T": T, "round_trip_us": R, "runs": []}
+    for X in (0.0, R if env_cost_us is None else env_cost_us):
+        work = WorkerEnv(N, X)
+        E = work.measured_us()   # what one env batch step really costs the caller, hand-over to the worker thread included
+        run = {"env_cost_us": X, "env_us": E, "iteration_ms": {"ungrouped": grouped_iteration_ms(c, env, work, T, 0)},
+               "ideal_gain": (E + R) / max(E, R)}
+        for G in groups:
+            run["iteration_ms"]["G%d" % G] = grouped_iteration_ms(c, env, work, T, G)
+        run["gain"] = {k: run["iteration_ms"]["ungrouped"] / v for k, v in run["iteration_ms"].items() if k != "ungrouped"}
+        out["runs"].append(run)
+        work.close()
+    c.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--one-rollout", action="store_true")
+    ap.add_argument("--groups", type=int, nargs="+", default=None, help="env groups to compare with the ungrouped calls, e.g. --groups 2 4")
+    ap.add_argument("--env-cost-us", type=float, default=None, help="cost of one step of all N envs on the worker thread (default: the measured round trip)")
+    ap.add_argument("--envs", type=int, default=4096)
     args = ap.parse_args()
+    if args.groups:
+        print(json.dumps({"groups_bench": groups_bench(args.envs, args.groups, args.env_cost_us)}))
+        return
     if args.one_rollout:
         N, T = 4096, 128
         c = host_ctx(N, T)
