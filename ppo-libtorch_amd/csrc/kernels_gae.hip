@@ -61,12 +61,6 @@ __device__ __forceinline__ int strip_of_block(int b, int grid) {
     return (((k >> 1) << 3) + xcd) * 2 + (k & 1);
 }
 
-#ifndef GAE_KEEPV_ALL
-#define GAE_KEEPV_ALL false   /* -DGAE_KEEPV_ALL=true: v_t in registers in the 16- / 32-column kernels of the smaller sizes too (A/B) */
-#endif
-#ifndef GAE_NO_PIPELINE
-#define GAE_NO_PIPELINE 0   /* -DGAE_NO_PIPELINE=1: the walk without software-pipelined LDS reads (A/B) */
-#endif
 // MODE 0: GAE.  MODE 1: n-step returns (PPO_Discrete.cpp:309-329: ret_t = r_t + (gamma*nnt_t)*ret_{t+1}; adv = ret - v).
 // TC: time steps per LDS tile (GAE_TC; 64 / 32 for the wide strips of HBM-resident sizes, launch_scan).  KEEPV (VEC only): v_t stays in the
 // registers of the thread that loaded it until the same thread stores R_t = A_t + v_t -- no third LDS tile (EPB = 32, TC = 128: 32 KB instead of 48).
@@ -210,7 +204,7 @@ __global__ __launch_bounds__(GAE_THREADS) void gae_kernel(const float* __restric
             if (k == 0) sCarry[(tile_par ^ 1) * EPB + c] = x;   // A of the tile's first row: the carry of the next (earlier) tile
             tile_par ^= 1;
             (void)r_hi; (void)r_lo;
-        } else if (walker && rows == TC && !GAE_NO_PIPELINE) {
+        } else if (walker && rows == TC) {
             // full tile: the chunks' LDS reads are software-pipelined -- chunk k + 1's 32 reads are in flight while chunk k's 16-step chain runs, so
             // only the chain itself (2 dependent operations per row) and the first chunk's read latency are serial
             float last = carry;
@@ -313,12 +307,8 @@ __global__ __launch_bounds__(GAE_THREADS) void gae_kernel(const float* __restric
 // bounded anyway.  Arithmetic, association order and the -ffp-contract=off build are gae_kernel's: the results are the same bits (tests/test_gpu_parity.py).
 // ---------------------------------------------------------------------------------------------------------------------------------------
 constexpr int GP_THREADS = GAE_THREADS + 64;                 // four mover waves + the walker
-#ifndef GAE_PIPE_MIN_ENVS
-#define GAE_PIPE_MIN_ENVS 4096
-#endif
-#ifndef GAE_PIPE_MAX_BLOCKS
-#define GAE_PIPE_MAX_BLOCKS 256                               /* strips up to which the pipelined kernel is launched: one workgroup per CU (12 288 envs x 32 columns = 384: 9.0 - 9.3 us against 7.2) */
-#endif
+constexpr int GP_MIN_ENVS = 4096;                            // the pipelined kernel is launched above this many envs only (launch_scan)
+constexpr int GP_MAX_BLOCKS = 256;                           // ... and up to this many strips: one workgroup per CU (12 288 envs x 32 columns = 384: 9.0 - 9.3 us against 7.2)
 typedef __attribute__((address_space(3))) volatile uint32_t gp_flag_t;
 // Bounded wait.  false = the count never came (cannot happen by construction, above): the caller poisons what it would have produced with NaN and raises the
 // context's error word where there is one -- never a silently wrong advantage (mg_wait_ge of the update kernel does the same).
@@ -473,36 +463,22 @@ hipError_t launch_scan(const float* rewards, const float* values, const float* d
     // Strip width: wide strips coalesce better (EPB*4-byte rows), narrow strips give more workgroups.  Keep >= ~2 per CU.
     // Strip width, measured on MI355X (tools/gae_sweep.py): 32 columns (48 KB of LDS, three workgroups per CU overlapping their
     // load / walk / store phases) is best from 32 768 envs up (4.5 TB/s); below ~8 192 envs 16 columns give every CU a workgroup.
-#ifdef GAE_EPB64_FROM   /* exploration builds: 64-column strips (96 KB of LDS: one workgroup per CU) from this many envs -- measured at 131 072 / 2^20 envs: 2.88 / 2.88 TB/s against 4.34 / 4.06 */
-    const int epb = N >= GAE_EPB64_FROM ? 64 : (N >= 8192 ? 32 : 16);
-#else
+    // (64-column strips of 128 rows -- 96 KB of LDS, one workgroup per CU -- measured at 131 072 / 2^20 envs: 2.88 / 2.88 TB/s against 4.34 / 4.06.)
     const int epb = N >= 8192 ? 32 : 16;
-#endif
-#ifndef GAE_NO_TIME_PIPELINE   /* -DGAE_NO_TIME_PIPELINE: the three-phase kernel at every size (A/B) */
     // Whole tiles, whole strips, and a grid of about one workgroup per CU: the kernel pipelined in time (same bits).  Measured in trace, builds alternated in
     // one call, two rounds (three-phase | 16 columns x 2 groups | 16 x 4 | 32 x 2 | 32 x 4, us): 4096 envs 4.86 - 5.12 | 4.37 - 4.71 | 4.27 - 4.57 | 4.65 - 4.97 |
     // 5.2; 8192 envs 6.2 - 7.5 | 8.1 - 8.6 | 8.1 - 8.4 | 5.9 - 6.0 | 5.66 - 5.74; 16 384 envs 9.1 | 15.4 | 15.4 | 10.0 | 9.9; 32 768 envs 18.5 | 30 | 30 | 20.7 |
     // 20.4 -- with two and more workgroups per CU the three-phase kernel's workgroups overlap their phases among themselves and the hand-overs only cost.
-#ifdef GP_FORCE   /* exploration builds: -DGP_FORCE=<epb * 10 + groups>, e.g. 164 */
-    const int gp_epb = GP_FORCE / 10, gp_groups = GP_FORCE % 10;
-#else
-    const int gp_epb = 32, gp_groups = 4;
-#endif
+    constexpr int gp_epb = 32, gp_groups = 4;
     // ... and only above 4096 envs: at 4096 (16-column strips) the pipelined kernel is ahead in a trace of the scan alone (4.3 - 4.8 us against 4.9 - 5.1) but
     // not inside the training iteration (5.34 against 5.27 us in trace) and slower back to back (6.6 against 5.1 us: five waves per workgroup leave the next
     // launch's workgroups less room to start under the tail of this one).  8192 envs = BASELINE configs[3]'s size: 5.7 us, 0.46 of 8 TB/s in trace.
-    if (!FAST && vec_ok && T % GAE_TC == 0 && N % gp_epb == 0 && N / gp_epb <= (int64_t)GAE_PIPE_MAX_BLOCKS && N > GAE_PIPE_MIN_ENVS) {
+    if (!FAST && vec_ok && T % GAE_TC == 0 && N % gp_epb == 0 && N / gp_epb <= (int64_t)GP_MAX_BLOCKS && N > GP_MIN_ENVS) {
         const dim3 grid((unsigned)(N / gp_epb)), block(GP_THREADS);
-#define PPO_GP_LAUNCH(E, G) hipLaunchKernelGGL((gae_pipe_kernel<E, MODE, G>), grid, block, 0, s, rewards, values, dones, next_value, next_done, (int)T, (int)N, gamma, gae_lambda, adv, ret, error_flag)
-        if (gp_epb == 32 && gp_groups == 4) PPO_GP_LAUNCH(32, 4);
-        else if (gp_epb == 32) PPO_GP_LAUNCH(32, 2);
-        else if (gp_groups == 4) PPO_GP_LAUNCH(16, 4);
-        else PPO_GP_LAUNCH(16, 2);
-#undef PPO_GP_LAUNCH
+        hipLaunchKernelGGL((gae_pipe_kernel<gp_epb, MODE, gp_groups>), grid, block, 0, s, rewards, values, dones, next_value, next_done, (int)T, (int)N, gamma, gae_lambda, adv, ret, error_flag);
         return hipGetLastError();
     }
-#endif
-    // From GAE_WIDE_FROM envs (two and more workgroups per CU even with 64-column strips): strips of 64 columns x a time tile of 32 rows, v_t kept in registers.
+    // From wide_from envs (two and more workgroups per CU even with 64-column strips): strips of 64 columns x a time tile of 32 rows, v_t kept in registers.
     // The 64-column strip reads 256-byte row pieces (two memory lines per row and array instead of one) and fills all 64 lanes of the walking wave; the SHORT
     // time tile keeps its LDS at 16 KB so that eight workgroups share a CU and overlap each other's load / walk / store phases -- round 5's 64-column experiment
     // kept 128 rows (96 KB, ONE workgroup per CU) and lost for that reason.  Same chain, same operation order: same bits (the carry crosses tiles in a register
@@ -510,17 +486,10 @@ hipError_t launch_scan(const float* rewards, const float* values, const float* d
     // 131 072 / 2^20 envs): 32 x 128 (round 5) 0.58 / 0.57 / 0.61 / 0.53 - 0.55 / 0.51; 64 x 128 - / - / 0.50 / 0.36 / 0.37; 64 x 64 - / - / 0.69 / 0.57 - 0.59 /
     // 0.60 - 0.63; 64 x 32 - / - / 0.75 / 0.60 / 0.62 - 0.64; 64 x 16 and 128 x 16, 128 x 32: within 0.02 of 64 x 32; 64 x 32 with non-temporal stores
     // 0.66 / 0.68 / 0.76 / 0.75 - 0.79 / 0.63 - 0.69 (non-temporal loads as well: worse at 65 536 and 131 072, the same at 2^20).
-    // Non-temporal stores from GAE_NT_FROM envs only: below that the batch (20 B x T x N) fits the memory-side cache with room to spare and the kernels that read
+    // Non-temporal stores from nt_from envs only: below that the batch (20 B x T x N) fits the memory-side cache with room to spare and the kernels that read
     // the advantages next (pack_records, perm_adv_stats) find them there.
-#ifndef GAE_WIDE_FROM
-#define GAE_WIDE_FROM 16384
-#endif
-#ifndef GAE_NT_FROM
-#define GAE_NT_FROM 65536
-#endif
-#ifndef GAE_WIDE_CFG   /* exploration builds: -DGAE_WIDE_CFG=<epb * 1000 + tc>, e.g. 64064, 64016, 128016, 32128 */
-#define GAE_WIDE_CFG 64032
-#endif
+    constexpr int64_t wide_from = 16384, nt_from = 65536;
+    constexpr int wide_epb = 64, wide_tc = 32;
 #define PPO_GAE_LAUNCH(EPB, TC, KEEPV, NT)                                                                                    \
     do {                                                                                                                      \
         const dim3 grid((unsigned)((N + EPB - 1) / EPB)), block(GAE_THREADS);                                                  \
@@ -531,14 +500,12 @@ hipError_t launch_scan(const float* rewards, const float* values, const float* d
             hipLaunchKernelGGL((gae_kernel<EPB, MODE, false, FAST, TC, false, false>), grid, block, 0, s, rewards, values, dones, next_value, next_done, \
                                (int)T, (int)N, gamma, gae_lambda, adv, ret);                                                  \
     } while (0)
-    constexpr int wide_epb = GAE_WIDE_CFG / 1000, wide_tc = GAE_WIDE_CFG % 1000;
-    if (!FAST && vec_ok && N >= GAE_WIDE_FROM && N % wide_epb == 0) {
-        if (N >= GAE_NT_FROM) PPO_GAE_LAUNCH(wide_epb, wide_tc, true, true);
+    if (!FAST && vec_ok && N >= wide_from && N % wide_epb == 0) {
+        if (N >= nt_from) PPO_GAE_LAUNCH(wide_epb, wide_tc, true, true);
         else PPO_GAE_LAUNCH(wide_epb, wide_tc, true, false);
     }
-    else if (epb == 64) PPO_GAE_LAUNCH(64, GAE_TC, false, false);
-    else if (epb == 32) PPO_GAE_LAUNCH(32, GAE_TC, GAE_KEEPV_ALL, false);
-    else PPO_GAE_LAUNCH(16, GAE_TC, GAE_KEEPV_ALL, false);
+    else if (epb == 32) PPO_GAE_LAUNCH(32, GAE_TC, false, false);
+    else PPO_GAE_LAUNCH(16, GAE_TC, false, false);
 #undef PPO_GAE_LAUNCH
     return hipGetLastError();
 }

@@ -94,29 +94,20 @@ __device__ __forceinline__ void bw_barrier() {
 // is still 53; a CU's address path moves a tile's 40 KB in ~900 cycles (tools/probes/l2_stream: 45 - 59 B/clk per CU by LDS-DMA, ~30 by plain loads, whatever the number
 // of CUs) and the waves that issue the instructions are blocked meanwhile (in-kernel stamps: 800 - 2000 cycles per tile).  Plain loads into registers + ds_write (two
 // register sets, the tile loop unrolled by two) were built: 62.8 / 55.5 us against 51.8 / 53.0; so was issuing the pieces one at a time between the products
-// (BW_DMA_SPREAD: the stall moves into the products) and leaving the fetch to the P2 waves alone (BW_ALL_MOVERS = 0: below).
-#ifndef BW_NT   /* exploration builds: bit 0 = non-temporal DMA of the h tile (read by ONE workgroup), bit 1 = of the dZ tile (read by the CB workgroups of a row range), bit 2 = non-temporal stores of dZ_{l-1} */
-#define BW_NT 0
-#endif
+// (54.3 against 51.7 / 59.3 against 53.5 us: the stall moves into the products) and leaving the fetch to the P2 waves alone (below).  Also measured and not taken:
+// non-temporal DMA of the h tile / of the dZ tile and non-temporal stores of dZ_{l-1} (no change); __builtin_amdgcn_global_load_lds (the vmcnt(0) waits described
+// above); range z taking tiles z, z + S, ... so that a launch reads one contiguous band of rows at a time (57.0 against 56.6 us).
 __device__ __forceinline__ uint32_t bw_lds_addr(const void* p) { return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char*)p; }
-template <bool NT = false>
 __device__ __forceinline__ void bw_glds16(const uint16_t* src, uint32_t dst) {
-#ifdef BW_GLDS_BUILTIN
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src, (__attribute__((address_space(3))) void*)(uintptr_t)dst, 16, 0, 0);
-    return;
-#endif
     const uint32_t d = (uint32_t)__builtin_amdgcn_readfirstlane((int)dst);   // wave-uniform by construction (it depends on the wave's index): the compiler has to be told
     uint32_t keep;
-    if (NT) asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0" : "=&s"(keep) : "v"(src), "s"(d) : "memory");
-    else asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" : "=&s"(keep) : "v"(src), "s"(d) : "memory");
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" : "=&s"(keep) : "v"(src), "s"(d) : "memory");
 }
 // The same with the source as a wave-uniform base (SGPR pair) + a 32-bit byte offset per lane: no 64-bit address arithmetic on the vector ALU per instruction.
-template <bool NT = false>
 __device__ __forceinline__ void bw_glds16_s(const uint16_t* sbase, uint32_t voff_bytes, uint32_t dst) {
     const uint32_t d = (uint32_t)__builtin_amdgcn_readfirstlane((int)dst);
     uint32_t keep;
-    if (NT) asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 nt\n\ts_mov_b32 m0, %0" : "=&s"(keep) : "v"(voff_bytes), "s"(sbase), "s"(d) : "memory");
-    else asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0" : "=&s"(keep) : "v"(voff_bytes), "s"(sbase), "s"(d) : "memory");
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0" : "=&s"(keep) : "v"(voff_bytes), "s"(sbase), "s"(d) : "memory");
 }
 
 // 64 lanes x 4 bytes -> 256 bytes at lds_wave_base, lane-linear: the index list's entries of a tile's rows (layer 0, rows read in place).  A DMA, not a load into a
@@ -179,13 +170,10 @@ __global__ __launch_bounds__(BW_THREADS, 1) void bwd_layer_kernel(const BwdPair 
     constexpr int DSZ = BW_ROWS * (N < 64 ? 64 : N);      // elements of one dZ buffer (>= the weight block [N][64])
     constexpr int P2W = P1 ? 4 : 8;            // waves that run P2
     constexpr int NBW = (NB + P2W - 1) / P2W;  // n blocks of a P2 wave (each against both 32-column halves of the block)
-    // Movers: the waves that issue a tile's DMA.  Every wave fetches its eighth of the tile (BW_ALL_MOVERS = 1, shipped).  0: beside P1 only the four P2 waves do -- they
-    // have the slack (the P1 waves carry the epilogue and are the longer path of an iteration), and a wave is blocked while the CU's address path moves what it issued
-    // (~900 cycles for the tile's 40 KB: stamps, NOTES) -- measured in one call: 53.5 against 52.6 us for the hidden layers' launch: the blocked time only moves.
-#ifndef BW_ALL_MOVERS
-#define BW_ALL_MOVERS 1
-#endif
-    constexpr int MW = (P1 && !BW_ALL_MOVERS) ? 4 : BW_WAVES;      // movers
+    // Movers: the waves that issue a tile's DMA.  Every wave fetches its eighth of the tile.  Leaving it to the four P2 waves alone beside P1 -- they have the slack (the
+    // P1 waves carry the epilogue and are the longer path of an iteration), and a wave is blocked while the CU's address path moves what it issued (~900 cycles
+    // for the tile's 40 KB: stamps, NOTES) -- measured in one call 53.5 against 52.6 us for the hidden layers' launch: the blocked time only moves.
+    constexpr int MW = BW_WAVES;               // movers
     constexpr int DPW = (CPR + MW - 1) / MW;   // 1-KiB DMA pieces of the dZ tile per mover (the tile has CPR of them)
     constexpr int HPW = BW_WAVES / MW;         // 1-KiB pieces of an h image per mover (an image has eight)
     static_assert(NB == 1 || NB == 4 || NB == 8, "dZ widths of 32 (a head), 128 and 256");
@@ -200,12 +188,6 @@ __global__ __launch_bounds__(BW_THREADS, 1) void bwd_layer_kernel(const BwdPair 
     const int xcd = bid & 7, slot = bid >> 3;
     const int z = (slot / a.CB) * 8 + xcd, c = slot % a.CB;   // c counts blocks of 64 KCB columns
     if (z >= a.S) return;
-#ifdef BW_INTERLEAVE   /* exploration: range z takes tiles z, z + S, z + 2 S, ...: at any moment the workgroups of a launch read ONE contiguous band of rows */
-    const int64_t all_tiles = (a.rows + BW_ROWS - 1) / BW_ROWS;
-    int n_tiles = z < all_tiles ? (int)((all_tiles - z + a.S - 1) / a.S) : 0;
-    if (n_tiles > a.tiles_per_range) n_tiles = a.tiles_per_range;
-    auto tile_row = [&](int t) -> int64_t { return ((int64_t)t * a.S + z) * BW_ROWS; };
-#else
     const int64_t row_begin = (int64_t)z * a.tiles_per_range * BW_ROWS;
     int n_tiles = a.tiles_per_range;
     {
@@ -214,13 +196,11 @@ __global__ __launch_bounds__(BW_THREADS, 1) void bwd_layer_kernel(const BwdPair 
         if (have < n_tiles) n_tiles = (int)have;
     }
     auto tile_row = [&](int t) -> int64_t { return row_begin + (int64_t)t * BW_ROWS; };
-#endif
     const int li = lane & 31, kg = lane >> 5;
     const bool p1_wave = P1 && wave < 4;
     const int cb1 = wave & 1, rb1 = (wave >> 1) & 1;   // P1: the wave's 32 columns (of the block's 64) and 32 rows (of the tile's 64)
     const int pj = P1 ? wave - 4 : wave;               // P2: the wave's index among the P2 waves (< 0: not one)
-    const bool mover = MW == BW_WAVES || pj >= 0;      // (wave-uniform) this wave issues DMA
-    const int mv = MW == BW_WAVES ? wave : (pj >= 0 ? pj : 0);   // its index among the movers
+    const int mv = wave;                               // the wave's index among the movers
 
     // What a wave keeps for the whole launch lives in ONE register block `st`: a P1 wave's weight fragments (4 registers per k step) or a P2 wave's
     // accumulators (16 per n block and column half).  The two kinds of waves never need both, but two arrays would both be live through the tile loop for the
@@ -293,53 +273,44 @@ __global__ __launch_bounds__(BW_THREADS, 1) void bwd_layer_kernel(const BwdPair 
         bw_glds4(gathered ? a.idx + index_row(t) : reinterpret_cast<const int32_t*>(a.zeros), idx0 + (uint32_t)(t & 1) * (BW_WAVES * 256u));
     };
     // One of the VM_TILE = DPW + KCB LDS-DMA instructions a wave issues for tile t (into ring buffer b = t % BW_RING): p < DPW = a KiB of the dZ tile, else an h image's.
-    // They are issued ONE AT A TIME between the products of the tile loop (round 6): eight waves issuing their five at the top of the iteration queued on the CU's one
-    // address path -- 40 KB at 64 B/clk -- and every wave sat 800 - 930 cycles of a 3 400-cycle iteration in front of its first product (in-kernel stamps, NOTES).
+    // Eight waves issuing their five at the top of the iteration queue on the CU's one address path -- 40 KB at 64 B/clk -- and every wave sits 800 - 930 cycles of a
+    // 3 400-cycle iteration in front of its first product (in-kernel stamps, NOTES); issued one at a time between the products the stall only moves into the products.
     auto issue_piece = [&](int t, int b, int hsrc, int p) {
-#ifdef BW_ABL_NODMA   /* timing-only: no tile ever arrives */
-        return;
-#endif
         const int64_t r0 = tile_row(t);
         const bool whole = r0 + BW_ROWS <= a.rows;   // wave-uniform: every row of the tile exists (all tiles but the minibatch's last)
-#ifndef BW_ABL
-#define BW_ABL 0   /* timing-only ablations (wrong results): 1 = every tile's DMA reads the first rows (cache-resident), 2 = every result tile is stored over the first rows */
-#endif
-        const int64_t r0s = (BW_ABL & 1) ? (int64_t)(t & 1) * BW_ROWS : r0;
         if (p < DPW) {
             const int i = p < DPW ? p : 0;
             const uint32_t dD = lds0 + (uint32_t)(b * DSZ) * 2u;                          // byte addresses in LDS (wave-uniform)
-            const uint16_t* const dbase = a.d + r0s * a.ldd;   // wave-uniform base: SGPR pair + the lane's 32-bit offset
+            const uint16_t* const dbase = a.d + r0 * a.ldd;   // wave-uniform base: SGPR pair + the lane's 32-bit offset
             const int pc = mv + MW * i;
             const bool have = pc < CPR;
             const uint32_t dst = have ? dD + 1024u * pc : spare0 + 1024u * wave;
-            if (whole && have) bw_glds16_s<(BW_NT & 2) != 0>(dbase, d_off[i], dst);
-            else bw_glds16<(BW_NT & 2) != 0>(have && r0 + d_row[i] < a.rows ? reinterpret_cast<const uint16_t*>(reinterpret_cast<const char*>(dbase) + d_off[i]) : a.zeros, dst);
+            if (whole && have) bw_glds16_s(dbase, d_off[i], dst);
+            else bw_glds16(have && r0 + d_row[i] < a.rows ? reinterpret_cast<const uint16_t*>(reinterpret_cast<const char*>(dbase) + d_off[i]) : a.zeros, dst);
         } else {
             const int hp = p - DPW;
             const int k = hp / HPW < KCB ? hp / HPW : 0, j = hp % HPW;   // image k (columns 64 (KCB c + k) ..), its piece mv + MW j
             const uint32_t dH = lds0 + (uint32_t)(BW_RING * DSZ + b * HSZ) * 2u;
-            const uint16_t* const hbase = a.h + r0s * a.ldh;
+            const uint16_t* const hbase = a.h + r0 * a.ldh;
             const uint32_t dst = dH + (uint32_t)(k * BW_ROWS * BW_KC) * 2u + 1024u * (mv + MW * j);
-            if (whole && !gathered) bw_glds16_s<(BW_NT & 1) != 0>(hbase, h_off[k][j], dst);
+            if (whole && !gathered) bw_glds16_s(hbase, h_off[k][j], dst);
             else {
                 const uint16_t* src = gathered ? reinterpret_cast<const uint16_t*>(reinterpret_cast<const char*>(a.h + (int64_t)hsrc * a.ldh) + (h_off[k][j] - (uint32_t)(h_row[j] * (int)a.ldh) * 2u))
                                                : reinterpret_cast<const uint16_t*>(reinterpret_cast<const char*>(hbase) + h_off[k][j]);
-                bw_glds16<(BW_NT & 1) != 0>(r0 + h_row[j] < a.rows ? src : a.zeros, dst);
+                bw_glds16(r0 + h_row[j] < a.rows ? src : a.zeros, dst);
             }
         }
     };
-    auto issue = [&](int t, int b, int hsrc) {   // all of this mover's pieces of tile t
-        if (!mover) return;
+    auto issue = [&](int t, int b, int hsrc) {   // all of this wave's pieces of tile t
 #pragma unroll
         for (int p = 0; p < DPW + KCB * HPW; p++) issue_piece(t, b, hsrc, p);
     };
     // the result tile of tile t leaves in 16-byte row pieces (rows past the minibatch are zeros: they keep the destination's padding zero)
     auto store_out = [&](int t) {
-        const int64_t r0 = (BW_ABL & 2) ? (int64_t)(t & 1) * BW_ROWS : tile_row(t);
+        const int64_t r0 = tile_row(t);
         const int row = tid >> 3, ch = tid & 7;
         const u32x4 piece = *reinterpret_cast<const u32x4*>(sO + (t & 1) * BW_ROWS * BW_KC + row * BW_KC + ((ch ^ swz_h(row)) << 3));
-        if (BW_NT & 4) __builtin_nontemporal_store(piece, reinterpret_cast<u32x4*>(a.dz_out + (r0 + row) * a.ld_out + BW_KC * c + 8 * ch));
-        else *reinterpret_cast<u32x4*>(a.dz_out + (r0 + row) * a.ld_out + BW_KC * c + 8 * ch) = piece;
+        *reinterpret_cast<u32x4*>(a.dz_out + (r0 + row) * a.ld_out + BW_KC * c + 8 * ch) = piece;
     };
     // vector-memory operations a wave issues per iteration of the steady state: the DMA pieces of one tile, and (P1) one store of the result tile
     constexpr int VM_TILE = DPW + KCB * HPW;     // DMA instructions of one tile (per mover)
@@ -370,8 +341,7 @@ __global__ __launch_bounds__(BW_THREADS, 1) void bwd_layer_kernel(const BwdPair 
 #pragma unroll
         for (int h = 0; h < 2 * KCB; h++) { frag_off<BW_KC, false>(32 * (h & 1), lane, h_lo[h], h_hi[h]); h_lo[h] += (h >> 1) * BW_ROWS * BW_KC; h_hi[h] += (h >> 1) * BW_ROWS * BW_KC; }
     }
-    if (!mover) { }   // (a wave that fetches nothing waits for nothing: the movers' waits and the barrier cover the tile)
-    else if (n_tiles > 1) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(VM_TILE) : "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // tile 0 has landed
+    if (n_tiles > 1) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(VM_TILE) : "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // tile 0 has landed
     bw_barrier();
 #ifdef BW_STAMP   /* diagnostic build: cycle sums of the tile loop's phases for one P1 and one P2 wave of workgroup 0, printed by the device */
     unsigned long long st_sum[5] = { 0, 0, 0, 0, 0 }, st_t0 = 0, st_begin = __builtin_amdgcn_s_memtime();
@@ -395,22 +365,10 @@ __global__ __launch_bounds__(BW_THREADS, 1) void bwd_layer_kernel(const BwdPair 
                 if (t > 0) hs_next = gathered ? sIdx[((t + 2) & 1) * (BW_WAVES * 64) + 64 * wave + lane] : 0;
                 index_dma(t + 3);
             }
+            // tile t + 2's pieces: all at the top, every wave in front of its products (beside P1 the P2 waves issuing theirs BEHIND their products, so that a SIMD's
+            // two waves are blocked in the address path at different times, measured 55.9 against 53.1 us)
+            issue(t + 2, rb2, hs_next);
         }
-        const bool pf = t + 2 < n_tiles;   // (uniform) this iteration issues tile t + 2's pieces, between its products: `pieces(lo, hi)` below
-#ifndef BW_DMA_SPREAD
-#define BW_DMA_SPREAD 0   /* 1: a tile's DMA instructions one at a time between the products (measured: the stall moves into the products, layer 0 gets slower); 0: all at the top */
-#endif
-#ifndef BW_STAGGER
-#define BW_STAGGER 0   /* 1: beside P1 the P2 waves issue their pieces BEHIND their products, the P1 waves in front of theirs, so that a SIMD's two waves are blocked in the address path at different times -- measured 55.9 against 53.1 us: not taken */
-#endif
-        const bool late = BW_STAGGER && P1 && !p1_wave;   // (wave-uniform)
-        if (!BW_DMA_SPREAD && pf && !late) issue(t + 2, rb2, hs_next);
-        auto pieces = [&](int lo, int hi) {
-            if (BW_DMA_SPREAD && pf) {
-#pragma unroll
-                for (int p = 0; p < VM_TILE; p++) if (mover && p >= lo && p < hi) issue_piece(t + 2, rb2, hs_next, p);
-            }
-        };
         BW_ST(0);   // (index entries of tile t + 3 requested)
         if constexpr (P1) { if (t > 0) store_out(t - 1); }
         BW_ST(1);   // result tile of t - 1 stored
@@ -434,7 +392,6 @@ __global__ __launch_bounds__(BW_THREADS, 1) void bwd_layer_kernel(const BwdPair 
                 __builtin_amdgcn_sched_barrier(0);   // the next batch's reads are issued in front of this batch's products
 #pragma unroll
                 for (int j = 0; j < BT; j++) acc1 = bw_mfma(wfrag(b * BT + j), bq[b & 1][j], acc1);
-                pieces(b * VM_TILE / NBT, (b + 1) * VM_TILE / NBT);
             }
             // epilogue: register r <-> column 32 cb1 + (r & 3) + 8 (r >> 2) + 4 kg of the block; tanh' from the staged h, result to its own image
             uint16_t* const tO = sO + (t & 1) * BW_ROWS * BW_KC;
@@ -459,9 +416,7 @@ __global__ __launch_bounds__(BW_THREADS, 1) void bwd_layer_kernel(const BwdPair 
                 for (int h = 0; h < 2 * KCB; h++) bf[h] = frag_at(tH + 16 * ks * BW_KC, h_lo[h], h_hi[h]);
 #pragma unroll
                 for (int i = 0; i < NBW; i++) af[i] = frag_at(tD + 16 * ks * N, a_lo[i], a_hi[i]);   // (a block past NB reads inside the tile and is not used)
-#ifndef BW_P2_NOBARRIER
                 __builtin_amdgcn_sched_barrier(0);   // every transposing read of the k step in front of its products (hipcc sinks each read to its product otherwise)
-#endif
 #pragma unroll
                 for (int i = 0; i < NBW; i++) {
                     const int nb = pj * NBW + i;
@@ -471,25 +426,13 @@ __global__ __launch_bounds__(BW_THREADS, 1) void bwd_layer_kernel(const BwdPair 
                             st[2 * KCB * i + h] = __builtin_bit_cast(u32x16, bw_mfma(af[i], bf[h], __builtin_bit_cast(f32x16, st[2 * KCB * i + h])));
                     }
                 }
-                pieces(ks * VM_TILE / KS2, (ks + 1) * VM_TILE / KS2);
             }
-        } else {
-            pieces(0, VM_TILE);   // a wave without products (narrow layers) still issues its share of the DMA
-        }
-        if (!BW_DMA_SPREAD && pf && late) issue(t + 2, rb2, hs_next);
-        BW_ST(2);   // products (+ P1's epilogue; the P2 waves' share of tile t + 2's DMA behind them)
+        }   // (a wave without products -- narrow layers -- has still issued its share of the DMA)
+        BW_ST(2);   // products (+ P1's epilogue)
         // this wave's pieces of tile t + 1 have landed: everything it issued up to them is done, i.e. all but what this iteration issued (the pieces of
         // tile t + 2 and the store of tile t - 1) -- counted, so that tile t + 2 stays in flight across the barrier (a plain __syncthreads() would drain
         // it: the compiler's fence waits for vmcnt(0)).  The last iterations issue less: they wait for everything.
-        if (!mover) {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // a wave that fetches nothing: its result tile is in LDS; the movers' waits + the barrier cover the tiles
-        } else
-#ifdef BW_FULL_WAIT
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        if (false) {
-#else
         if (t + 2 < n_tiles) {
-#endif
             if (t > 0) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" :: "n"(VM_PER_ITER) : "memory");
             else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" :: "n"(VM_TILE) : "memory");   // the first iteration has no result tile to store yet
         } else {

@@ -393,9 +393,6 @@ struct FusedLossArgs {
     float* head_db_part;                  // [GEN_LOSS_BLOCKS][act + 1]
     double* loss_part;                    // [GEN_LOSS_BLOCKS][8]
 };
-#ifndef FL_ABL
-#define FL_ABL 0   /* timing-only ablation builds (wrong results): 1 no E1, 2 no E3, 4 no E4, 8 no E5, 16 no record prefetch */
-#endif
 constexpr int FL_NP = 16;                 // logits as staged: one k step of the matrix cores (the slot-wise loss serves <= 4 heads of <= 4 logits)
 constexpr int FL_DLT_PITCH = 72;          // [n][row] image: 64 rows + 8
 constexpr int FL_DW_ROWS = FL_NP + 4;     // LDS rows of the dW_head accumulator: the actor's 16, the critic's (1, padded to 4)
@@ -432,8 +429,9 @@ typedef float f32x4a4 __attribute__((ext_vector_type(4), aligned(4)));
 // dual: every workgroup runs BOTH passes on each of its tiles -- the input tile is fetched and staged from the same registers twice, read from memory once.
 struct FusedForwardPair { FusedForwardArgs a[2]; int split; int dual; FusedLossArgs loss; };
 // LOSS: 0 = forward only; PPO_DIST_CATEGORICAL + 1 / PPO_DIST_MASKED + 1 = the loss and the head layer's backward in the epilogue of every pass (dual launches only)
-// NW / FMT: waves per workgroup and 32-row blocks per tile.  8 / 2 = one workgroup of 64-row tiles per CU; 4 / 1 (LOSS == 0 only, exploration: -DFU_HALF) = TWO
-// workgroups of 32-row tiles per CU, whose phases (weights from L2, LDS + matrix cores, tanh epilogue) can overlap each other's instead of running in lockstep.
+// NW / FMT: waves per workgroup and 32-row blocks per tile.  8 / 2 = one workgroup of 64-row tiles per CU; 4 / 1 (LOSS == 0 only) = TWO
+// workgroups of 32-row tiles per CU, whose phases (weights from L2, LDS + matrix cores, tanh epilogue) can overlap each other's instead of running in lockstep --
+// measured 205 against 177 us (the weights cross L2 -> CU twice per 64 rows) and not launched: only the 8 / 2 form is instantiated.
 template <bool BF, int LOSS = 0, int NW = FU_WAVES, int FMT = 2>
 __global__ __launch_bounds__(64 * NW, NW == FU_WAVES ? 1 : 2) void generic_forward_kernel(const FusedForwardPair pp) {
     static_assert(LOSS == 0 || (NW == FU_WAVES && FMT == 2), "the loss epilogue is written for eight waves and 64-row tiles");
@@ -523,7 +521,7 @@ __global__ __launch_bounds__(64 * NW, NW == FU_WAVES ? 1 : 2) void generic_forwa
             else pf[p] = __builtin_bit_cast(u32x4, *reinterpret_cast<const f32x4a4*>(a.x_f32 + (ok ? row * O + 4 * piece : 0)));
         }
         if constexpr (LOSS != 0) {
-            if (!(FL_ABL & 16)) prec = *reinterpret_cast<const u32x4*>(fl.rec + 2 * (rok ? row : 0) + (sub & 1));   // (every thread loads: no divergent branch around a load)
+            prec = *reinterpret_cast<const u32x4*>(fl.rec + 2 * (rok ? row : 0) + (sub & 1));   // (every thread loads: no divergent branch around a load)
         }
     };
     auto stage = [&](int64_t tile) {
@@ -589,7 +587,7 @@ __global__ __launch_bounds__(64 * NW, NW == FU_WAVES ? 1 : 2) void generic_forwa
                 uint16_t* const oT = (L.n_hidden & 1) ? tile0 : tile1;
                 const int ldA = x.f.ldA;
                 // ---- E1: four lanes per row (lane = head): masked categorical, PPO loss, d logits -- or, in the critic's pass, the value loss and d value ----
-                if (te < 256 && !(FL_ABL & 1)) {
+                if (te < 256) {
                     const int row = te >> 2, h = te & 3;
                     const bool live = row < n_rows;
                     const float4 lr0 = s_rec[2 * row], lr1 = s_rec[2 * row + 1];   // { old log-prob, advantage, return, old value }, { action bytes, mask bits, -, - }
@@ -731,7 +729,7 @@ __global__ __launch_bounds__(64 * NW, NW == FU_WAVES ? 1 : 2) void generic_forwa
                 __syncthreads();
                 // ---- E3: dZ_top block of wave w: rows 32 i + li, columns 32 w + (r & 3) + 8 (r >> 2) + 4 kg; tanh' from the h tile; column sums in f32 ----
                 const bool own_cols = 32 * wave < ld_h;   // a hidden vector of 128 columns: waves 0 .. 3 (wave-uniform)
-                if (own_cols && !(FL_ABL & 2)) {
+                if (own_cols) {
                     // D[row][column] (the rows' d logits as the A operand, W_head^T as the B operand): lane (i, kg) then holds ONE column, 32 w + i, and register r
                     // the row 32 blk + (r & 3) + 8 (r >> 2) + 4 kg -- the column sum is an in-lane sum of registers (the other orientation, lane = row, needed
                     // four DPP steps per register and a read-modify-write per value: two thirds of this phase).  h comes by transposing reads: one ds_read_b64_tr_b16
@@ -764,7 +762,7 @@ __global__ __launch_bounds__(64 * NW, NW == FU_WAVES ? 1 : 2) void generic_forwa
                     s_cs[(2 * net + kg) * ld_h + col] += csum;   // one accumulator per (net, kg half, column): this lane's alone
                 }
                 // ---- E4: dW_head[n][32 w + i] += sum over the tile's rows of dL[row][n] h[row][32 w + i]: four k steps, h by transposing reads ----
-                if (own_cols && !(FL_ABL & 4)) {
+                if (own_cols) {
                     f32x16 acc;
 #pragma unroll
                     for (int r = 0; r < 16; r++) acc[r] = 0.0f;
@@ -788,7 +786,7 @@ __global__ __launch_bounds__(64 * NW, NW == FU_WAVES ? 1 : 2) void generic_forwa
                 }
                 __syncthreads();
                 // ---- E5: the dZ_top tile leaves in 16-byte row pieces ----
-                if (!(FL_ABL & 8)) {
+                {
                     const int p8 = ld_h / 8, total = RB * p8;
                     for (int e0 = te; e0 < total; e0 += 4 * FU_THREADS) {
                         u32x4 v[4];
@@ -802,11 +800,7 @@ __global__ __launch_bounds__(64 * NW, NW == FU_WAVES ? 1 : 2) void generic_forwa
 #pragma unroll
                         for (int j = 0; j < 4; j++)
                             if (e0 + j * FU_THREADS < total && row[j] < n_rows) {
-#ifdef FL_E5_NT
-                                __builtin_nontemporal_store(v[j], reinterpret_cast<u32x4*>(fl.dz_top[net] + (row0 + row[j]) * fl.ld_dz + 8 * c8[j]));
-#else
                                 *reinterpret_cast<u32x4*>(fl.dz_top[net] + (row0 + row[j]) * fl.ld_dz + 8 * c8[j]) = v[j];
-#endif
                             }
                     }
                 }
@@ -895,16 +889,6 @@ static hipError_t fused_forward_launch(const FusedForwardPair& pp, unsigned bloc
                                 : allow_dynamic_lds(lds_ok[1], reinterpret_cast<const void*>(&generic_forward_kernel<false>));
         if (e != hipSuccess) return e;
     }
-#ifdef FU_HALF
-    if (bf && pp.dual) {   // exploration: two workgroups of four waves and 32-row tiles per CU
-        const int64_t t32 = (pp.a[0].rows + 31) / 32;
-        const unsigned hb = (unsigned)(t32 < 512 ? t32 : 512);
-        FusedForwardPair q = pp;
-        q.split = (int)hb;
-        hipLaunchKernelGGL((generic_forward_kernel<true, 0, 4, 1>), dim3(hb), dim3(256), fused_lds_bytes(pp.a[0].f, 32), s, q);
-        return hipGetLastError();
-    }
-#endif
     if (bf) hipLaunchKernelGGL(generic_forward_kernel<true>, dim3(blocks), dim3(FU_THREADS), lds, s, pp);
     else hipLaunchKernelGGL(generic_forward_kernel<false>, dim3(blocks), dim3(FU_THREADS), lds, s, pp);
     return hipGetLastError();
@@ -932,13 +916,8 @@ hipError_t gen_fused_forward_both(const GenericCtx& g, const float* params, cons
     pp.a[1] = fused_forward_args(g, params, 0, nullptr, x_bf, ld_x, rows, true, val, idx);
     const int64_t n_tiles = (rows + 63) / 64;
     const unsigned per = (unsigned)(n_tiles < 256 ? n_tiles : 256);
-#ifdef FU_AB_TWO_HALVES   // A/B build: the actor's workgroups, then the critic's (each fetching its own copy of the rows)
-    pp.split = (int)per;
-    return fused_forward_launch(pp, 2 * per, true, s);
-#else
     pp.split = (int)per; pp.dual = 1;   // every workgroup runs both nets on each of its tiles: the rows are fetched once
     return fused_forward_launch(pp, per, true, s);
-#endif
 }
 
 // Heads, loss and the head layers' backward inside the forward launch (FusedLossArgs above).  Shapes: the slot-wise loss's (<= 4 heads of <= 4 logits, packed row

@@ -1128,7 +1128,7 @@ hipError_t launch_reduce_grads(const float* slab, const double* stat_slab, const
 hipError_t launch_clip_adamw(float* params, float* grads, float* exp_avg, float* exp_avg_sq, const NetLayout& L, float max_grad_norm,
                              const AdamCoef* coef, const double* loss_sums, double global_M, LossParams hp, int world, bool do_step,
                              StepStats* stats_out, double* clipfrac_accum, double* norm2_scratch, hipStream_t s, OptGuard guard) {
-    if (PPO_OPT_GUARD && !guard.error_flag) return hipErrorInvalidValue;   // the kernel reads the word without a null check
+    if (!guard.error_flag) return hipErrorInvalidValue;   // the kernel reads the word without a null check
     hipLaunchKernelGGL(grad_norm_kernel, dim3(L.n_tensors), dim3(NORM_THREADS), 0, s, grads, L, norm2_scratch);
     const int blocks = do_step ? (L.P + ADAM_THREADS - 1) / ADAM_THREADS : 1;
     hipLaunchKernelGGL(clip_adamw_kernel, dim3(blocks), dim3(ADAM_THREADS), 0, s, params, grads, exp_avg, exp_avg_sq, L, max_grad_norm, norm2_scratch,
@@ -1145,7 +1145,7 @@ hipError_t launch_reduce_clip_adamw(const float* slab, const double* stat_slab, 
                                     double* sums_out, float* params, float* exp_avg, float* exp_avg_sq, float max_grad_norm,
                                     const AdamCoef* coef, double global_M, LossParams hp, StepStats* stats_out, double* clipfrac_accum,
                                     double* partial, hipStream_t s, OptGuard guard) {
-    if (PPO_OPT_GUARD && !guard.error_flag) return hipErrorInvalidValue;   // the kernel reads the word without a null check
+    if (!guard.error_flag) return hipErrorInvalidValue;   // the kernel reads the word without a null check
     FusedOptArgs a{};
     a.guard = guard;
     a.slab = slab; a.stat_slab = stat_slab; a.nb0 = n_blocks[0]; a.nb1 = n_blocks[1]; a.L = L; a.grads = grads; a.sums_out = sums_out;
@@ -1164,7 +1164,7 @@ hipError_t launch_reduce_exchange_clip_adamw(const float* slab, const double* st
                                              void* const* peers, int rank, int n_ranks, size_t slot_bytes, uint64_t seq, int32_t* timeout_flag,
                                              hipStream_t s, OptGuard guard) {
     if (n_ranks < 1 || n_ranks > 8 || (size_t)(L.P + 8) * sizeof(float) > slot_bytes) return hipErrorInvalidValue;
-    if (PPO_OPT_GUARD && !guard.error_flag) return hipErrorInvalidValue;   // the kernel reads the word without a null check
+    if (!guard.error_flag) return hipErrorInvalidValue;   // the kernel reads the word without a null check
     FusedOptArgs a{};
     a.guard = guard;
     a.slab = slab; a.stat_slab = stat_slab; a.nb0 = n_blocks[0]; a.nb1 = n_blocks[1]; a.L = L; a.grads = grads; a.sums_out = sums_out;

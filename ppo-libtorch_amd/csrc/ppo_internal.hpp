@@ -79,9 +79,7 @@ struct LossParams {
 
 // Per-minibatch advantage statistics (sum, sum of squares over the GLOBAL minibatch) and the scalars derived from them.
 struct AdvStat { double s1, s2; };
-#ifndef PPO_ADV_PARTS
 #define PPO_ADV_PARTS 32  // partial sums per minibatch (one workgroup each), added in order by the consumer (A/B on one box, tools/ab.sh: 32 parts 56.7 us per update launch and 161.7 M env-steps/s, 8 parts 57.9 us and 158.5 M)
-#endif
 #define PPO_EV_BLOCKS 512 // partial rows of the explained-variance sums, added in order by the host
 // Job-global statistics block of a sharded run (doubles; summed over ranks by the per-update all-reduce, every rank writes only its own slot, so the
 // "sum" is a gather): the reference prints ONE table for the job (PPO_Discrete.cpp:474-480, 647-648, 700-774), so every rank must hold the same numbers.
@@ -697,16 +695,12 @@ hipError_t launch_pack_records(const NetLayout& L, const float* obs, const int32
 struct OptGuard {
     int32_t* error_flag = nullptr;
 };
-#ifndef PPO_OPT_GUARD
-#define PPO_OPT_GUARD 1   /* -DPPO_OPT_GUARD=0: the optimizer kernels without the error-word load (A/B of its cost) */
-#endif
 #ifdef __HIPCC__
 // The error word as a VECTOR load: the address passes through a vector register the compiler cannot see through, so the load is issued in the same batch as
 // the step's other vector loads and waited for with them.  Left to itself hipcc made it two DEPENDENT scalar loads (the pointer out of the kernel arguments,
 // then the word) with a wait behind each at the very top of the kernel, in front of everything else: + 0.15 us on a 5 us launch (trace A/B, NOTES).
 // error_flag is never null here: the launchers refuse a null word (no branch in the kernel: a branch made the compiler wait for the word on the spot).
 __device__ __forceinline__ int32_t opt_guard_word(const int32_t* error_flag) {
-    if (!PPO_OPT_GUARD) return 0;
     uintptr_t p = reinterpret_cast<uintptr_t>(error_flag);
     asm volatile("" : "+v"(p));
     return *reinterpret_cast<const __attribute__((address_space(1))) int32_t*>(p);

@@ -1,6 +1,5 @@
 #!/bin/bash
 # Counters of configs[4]'s share, one rocprofv3 --pmc pass per set (never beside a trace), summarised per kernel:  tools/c4_pmc.sh TAG ["SET" ...]
-# With the nets on one stream (GEN_AB_ONE_STREAM builds) every kernel is alone on the chip and its counters are its own.
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 ROOT=$(pwd); export TMPDIR=/tmp
 TAG=$1; shift
