@@ -140,7 +140,7 @@ enum {
     PPO_BUF_OBS = 0,      /* m_obs        f32 [T,N,O]                       PPO_Discrete.cpp:90  */
     PPO_BUF_ACTIONS,      /* m_actions    i32 [T,N,H] (reference stores f32 [T,N,1], :91,:537)   */
     PPO_BUF_LOGPROBS,     /* m_logprobs   f32 [T,N]                         :92  */
-    PPO_BUF_REWARDS,      /* m_rewards    f32 [T,N]                         :93  */
+    PPO_BUF_REWARDS,      /* m_rewards    f32 [T,N]                         :93   (PPO_ENV_HOST with truncation events: r + gamma V(final obs) there, after ppo_host_rollout_end) */
     PPO_BUF_DONES,        /* m_dones      f32 [T,N]                         :94  */
     PPO_BUF_VALUES,       /* m_values     f32 [T,N]                         :95  */
     PPO_BUF_MASKS,        /* m_action_masks u8 [T,N,A]        PPO_MultiDiscrete.cpp:98 */
@@ -169,7 +169,9 @@ enum {
 PPO_API int32_t ppo_abi_version(void);
 /* PPO_Discrete::PPO_Discrete() (PPO_Discrete.cpp:4-100): allocates every device buffer once (rollout [T,N,*],
  * parameters, AdamW state, env SoA, reset-stream table); no allocation happens afterwards -- except ppo_evaluate's scratch (per-episode arrays, the
- * evaluation reset table), allocated by its first call, kept, and grown only by a call that asks for more episodes than any before it. */
+ * evaluation reset table), allocated by its first call, kept, and grown only by a call that asks for more episodes than any before it; and, by the same
+ * policy, the truncation-event list of caller-stepped rollouts (one pinned host block and its device twin), allocated by the first
+ * ppo_host_observe_truncated / ppo_host_group_observe_truncated call that carries an event and grown by doubling up to num_steps * num_envs entries. */
 PPO_API ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out);
 PPO_API void ppo_ctx_destroy(ppo_ctx* ctx);
 /* Error text of the last failing call on ctx (ctx == NULL: of the last failing ppo_ctx_create in this thread).
@@ -370,7 +372,7 @@ PPO_API ppo_status ppo_host_rollout_begin(ppo_ctx* ctx);
  * mask_h u8 [N,A] or NULL (masked policies; NULL = all valid); returns when action_h i64 [N,H] (host) holds the actions. */
 PPO_API ppo_status ppo_host_act(ppo_ctx* ctx, const uint8_t* mask_h, int64_t* action_h);
 /* stepEnvs' outputs for step t (:413-483): next_obs_h [N,O] (already the reset observation where done), reward_h f32 [N], done_h i32 [N]
- * (truncation included).  fin_len_h i32 [N] / fin_rew_h f32 [N]: the length and reward of the episodes that finished, as the reference reads
+ * (truncation included; ppo_host_observe_truncated tells the two apart).  fin_len_h i32 [N] / fin_rew_h f32 [N]: the length and reward of the episodes that finished, as the reference reads
  * them from env->episode_length / episode_reward (:474-480), read where done only (a length of 0 is not counted as an episode).  NULL = the
  * context keeps them as running sums (steps counted, rewards summed), which is what CartPole and MountainCar report.  The data is copied
  * before the call returns. */
@@ -410,6 +412,44 @@ PPO_API ppo_status ppo_host_group_actions(ppo_ctx* ctx, int32_t g, int64_t* acti
 /* ppo_host_observe for group g's rows (all arrays [n_g, ...]); host memory only, no launch. */
 PPO_API ppo_status ppo_host_group_observe(ppo_ctx* ctx, int32_t g, const float* next_obs_h, const float* reward_h, const int32_t* done_h,
                                           const int32_t* fin_len_h, const float* fin_rew_h);
+
+/* Time-limit truncations (new): bootstrap the value where an episode was cut off instead of ended.
+ *
+ * The reference ends an episode that reaches max_episode_steps exactly like one the env terminated (PPO_Discrete.cpp:443-452: episode_length ==
+ * max_episode_steps sets terminated = true, and the `truncated` flag its envs return is always false and never read): the scan cuts the return there
+ * with a bootstrap of 0, which teaches the critic that the state in front of the limit is worth nothing.  Its framework cannot do better -- it never
+ * sees the observation the episode ended on.  The caller of the ppo_host_* calls does: it holds step()'s observation when it resets the env.  With it
+ * the usual partial-episode bootstrap applies: at a truncation at (t, n) the reward becomes r + gamma * V(final observation), and the scan runs unchanged.
+ *
+ *   T x { ppo_host_act; step the envs; ppo_host_observe_truncated(ctx, obs, reward, done, fin_len, fin_rew, truncated, final_obs) }
+ *
+ * Off unless these calls are used: a rollout without a truncation event is, launch for launch and bit for bit, the rollout of the plain calls.  The
+ * plain and the _truncated observes mix freely within a rollout and across groups.  The observes only append (t * N + n, final observation) to a list
+ * in pinned host memory -- no launch, no sorting per step.  ppo_host_rollout_end, behind the value launch and in front of the scan, with K events:
+ * K == 0 enqueues nothing; K > 0 sorts the list by index on the host (the outcome does not depend on how groups interleaved), enqueues ONE asynchronous
+ * copy of it and one fold launch on PPO_BUF_REWARDS with gamma = cfg.gamma.  V is the value this context's rollout assigns to that observation: the fold
+ * runs the arithmetic of the launch that fills PPO_BUF_VALUES (bootstrap_values_mfma_kernel / bootstrap_values_kernel; generic networks: the engine's
+ * critic forward, then fold_rewards_kernel), so delta = r + gamma V(final) - V(obs_t) is formed from ONE critic.  PPO_BUF_REWARDS holds the folded
+ * rewards after ppo_host_rollout_end; FIN_REW, EP_REW and the episode statistics keep the raw rewards.  Purely local: no collective on a sharded context.
+ * Errors: the PPO_ERR_STATE cases of the plain calls (device-env context, out of sequence, wrong rollout kind); a failing call changes nothing. */
+/* ppo_host_observe plus: truncated_h i32 [N] -- non-zero where the episode that ended at this step was cut off (time limit) rather than terminated;
+ * final_obs_h f32 [N,O] -- the LAST observation of that episode (what step() returned, before the reset), read only in rows where truncated_h != 0.
+ * truncated_h[n] != 0 requires done_h[n] != 0 (else PPO_ERR_INVALID, the message names the row); a non-zero flag with final_obs_h == NULL is
+ * PPO_ERR_INVALID.  truncated_h == NULL means no truncation (then final_obs_h may be NULL) and the call IS ppo_host_observe. */
+PPO_API ppo_status ppo_host_observe_truncated(ppo_ctx* ctx, const float* next_obs_h, const float* reward_h, const int32_t* done_h, const int32_t* fin_len_h,
+                                              const float* fin_rew_h, const int32_t* truncated_h, const float* final_obs_h);
+/* The same for group g's rows (all arrays [n_g, ...]). */
+PPO_API ppo_status ppo_host_group_observe_truncated(ppo_ctx* ctx, int32_t g, const float* next_obs_h, const float* reward_h, const int32_t* done_h,
+                                                    const int32_t* fin_len_h, const float* fin_rew_h, const int32_t* truncated_h, const float* final_obs_h);
+/* Truncation events of the last CLOSED rollout (while a rollout is open: of the one before it; before any rollout: count = 0): count; flat indices
+ * t * N + n ascending; the bootstrap values V(final obs) that were folded in.  index_h / value_h may be NULL (count only); cap = room in the arrays
+ * (cap < count with a non-NULL array -> PPO_ERR_INVALID).  Waits for the fold only, not for the update behind it. */
+PPO_API ppo_status ppo_host_truncations(ppo_ctx* ctx, int64_t* count, int32_t* index_h, float* value_h, int64_t cap);
+/* The fold on caller buffers, with the context's critic (any context kind, any time): for k < K
+ *   v = Critic(final_obs[k]);  rewards[index[k]] = rewards[index[k]] + gamma * v  (two f32 roundings, no FMA);  value_out[k] = v (may be NULL).
+ * final_obs f32 [K,O], index i32 [K] (distinct: the caller's promise; no atomics are used), rewards f32, value_out f32 [K]: device pointers.  v is
+ * bit for bit ppo_get_value's.  K == 0: no launch.  Null pointers with K > 0, or K < 0: PPO_ERR_INVALID. */
+PPO_API ppo_status ppo_bootstrap_rewards(ppo_ctx* ctx, const float* final_obs, const int32_t* index, int64_t K, float gamma, float* rewards, float* value_out);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Evaluation (new; the reference reports only the mean over the last 100 exploration episodes of its training envs, PPO_Discrete.cpp:474-480, Utils.h:72-78)

@@ -51,6 +51,7 @@ ABI_SYMBOLS = [
     "ppo_host_env_reset", "ppo_host_rollout_begin", "ppo_host_act", "ppo_host_observe", "ppo_host_rollout_end",
     "ppo_host_rollout_begin_groups", "ppo_host_group_act", "ppo_host_group_actions", "ppo_host_group_observe",
     "ppo_policy_act_greedy", "ppo_evaluate",
+    "ppo_host_observe_truncated", "ppo_host_group_observe_truncated", "ppo_host_truncations", "ppo_bootstrap_rewards",
 ]
 
 
@@ -139,6 +140,10 @@ def lib():
         L.ppo_stream.restype = C.c_void_p
         L.ppo_param_count.restype = C.c_int64
         L.ppo_ctx_destroy.restype = None
+        L.ppo_host_observe_truncated.argtypes = [C.c_void_p] * 8
+        L.ppo_host_group_observe_truncated.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 7
+        L.ppo_host_truncations.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_int64]
+        L.ppo_bootstrap_rewards.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]
         for name in ABI_SYMBOLS:
             getattr(L, name)  # AttributeError if the build lacks a declared symbol
         if L.ppo_abi_version() != ABI_VERSION:
@@ -393,7 +398,7 @@ class Context:
         _check(lib().ppo_host_group_actions(self.h, C.c_int32(g), out.ctypes.data_as(C.c_void_p)), self.h)
         return out
 
-    def host_group_observe(self, g, obs, reward, done, fin_len=None, fin_rew=None):
+    def host_group_observe(self, g, obs, reward, done, fin_len=None, fin_rew=None, truncated=None, final_obs=None):
         """host_observe for group g's rows (arrays [n_g, ...])."""
         n = self._group_rows(g)
         o = np.ascontiguousarray(obs, np.float32).reshape(n, self.O)
@@ -401,8 +406,13 @@ class Context:
         d = np.ascontiguousarray(done, np.int32).reshape(n)
         fl = np.ascontiguousarray(fin_len, np.int32).reshape(n) if fin_len is not None else None
         fr = np.ascontiguousarray(fin_rew, np.float32).reshape(n) if fin_rew is not None else None
-        _check(lib().ppo_host_group_observe(self.h, C.c_int32(g), *(x.ctypes.data_as(C.c_void_p) if x is not None else None for x in (o, r, d, fl, fr))),
-               self.h)
+        args = [o, r, d, fl, fr]
+        fn = lib().ppo_host_group_observe
+        if truncated is not None or final_obs is not None:
+            fn = lib().ppo_host_group_observe_truncated
+            args.append(np.ascontiguousarray(truncated, np.int32).reshape(n) if truncated is not None else None)
+            args.append(np.ascontiguousarray(final_obs, np.float32).reshape(n, self.O) if final_obs is not None else None)
+        _check(fn(self.h, C.c_int32(g), *(x.ctypes.data_as(C.c_void_p) if x is not None else None for x in args)), self.h)
 
     def host_act(self, mask=None):
         """Step t of the rollout: returns the sampled actions i64 [N,H] (host)."""
@@ -411,14 +421,50 @@ class Context:
         _check(lib().ppo_host_act(self.h, m.ctypes.data_as(C.c_void_p) if m is not None else None, out.ctypes.data_as(C.c_void_p)), self.h)
         return out
 
-    def host_observe(self, obs, reward, done, fin_len=None, fin_rew=None):
-        """The caller's envs' outputs for the step just acted on (obs already the reset observation where done; done includes truncation)."""
+    def host_observe(self, obs, reward, done, fin_len=None, fin_rew=None, truncated=None, final_obs=None):
+        """The caller's envs' outputs for the step just acted on (obs already the reset observation where done; done includes truncation).
+        truncated i32 [N] / final_obs f32 [N,O] (ppo_host_observe_truncated): where the episode that ended was cut off by a time limit, and the
+        observation it ended on; the rollout's end then bootstraps the value there instead of treating the state as terminal."""
         o = np.ascontiguousarray(obs, np.float32).reshape(self.N, self.O)
         r = np.ascontiguousarray(reward, np.float32).reshape(self.N)
         d = np.ascontiguousarray(done, np.int32).reshape(self.N)
         fl = np.ascontiguousarray(fin_len, np.int32).reshape(self.N) if fin_len is not None else None
         fr = np.ascontiguousarray(fin_rew, np.float32).reshape(self.N) if fin_rew is not None else None
-        _check(lib().ppo_host_observe(self.h, *(x.ctypes.data_as(C.c_void_p) if x is not None else None for x in (o, r, d, fl, fr))), self.h)
+        args = [o, r, d, fl, fr]
+        fn = lib().ppo_host_observe
+        if truncated is not None or final_obs is not None:
+            fn = lib().ppo_host_observe_truncated
+            args.append(np.ascontiguousarray(truncated, np.int32).reshape(self.N) if truncated is not None else None)
+            args.append(np.ascontiguousarray(final_obs, np.float32).reshape(self.N, self.O) if final_obs is not None else None)
+        _check(fn(self.h, *(x.ctypes.data_as(C.c_void_p) if x is not None else None for x in args)), self.h)
+
+    def host_truncations(self):
+        """The truncation events of the last closed rollout: (flat indices t * N + n ascending i32 [K], folded-in values V(final obs) f32 [K])."""
+        k = C.c_int64()
+        _check(lib().ppo_host_truncations(self.h, C.byref(k), None, None, C.c_int64(0)), self.h)
+        idx, val = np.empty(k.value, np.int32), np.empty(k.value, np.float32)
+        if k.value:
+            _check(lib().ppo_host_truncations(self.h, C.byref(k), idx.ctypes.data_as(C.c_void_p), val.ctypes.data_as(C.c_void_p), C.c_int64(idx.size)), self.h)
+        return idx, val
+
+    def bootstrap_rewards(self, final_obs, index, gamma, rewards, want_values=True):
+        """ppo_bootstrap_rewards: rewards[index[k]] += gamma * Critic(final_obs[k]) on the device.  rewards: a PPO_BUF name or a device pointer
+        (DeviceArray / c_void_p).  Returns the values f32 [K] (None unless want_values), after waiting for the launch."""
+        final_obs = np.ascontiguousarray(final_obs, np.float32).reshape(-1, self.O)
+        index = np.ascontiguousarray(index, np.int32).ravel()
+        K = index.size
+        assert final_obs.shape[0] == K, (final_obs.shape, K)
+        ptr = self.buffer_ptr(rewards)[0] if isinstance(rewards, str) else getattr(rewards, "ptr", rewards)
+        tmp = [self.dev(final_obs), self.dev(index)] if K else []
+        d_v = self.empty(K, np.float32) if want_values and K else None
+        try:
+            _check(lib().ppo_bootstrap_rewards(self.h, tmp[0].ptr if K else None, tmp[1].ptr if K else None, C.c_int64(K), C.c_float(gamma), ptr,
+                                               d_v.ptr if d_v is not None else None), self.h)
+            self.sync()
+            return (d_v.download() if d_v is not None else np.empty(0, np.float32)) if want_values else None
+        finally:
+            for x in tmp + ([d_v] if d_v is not None else []):
+                x.free()
 
     def host_rollout_end(self):
         """Values, advantages and the update of the rollout (enqueued)."""

@@ -216,6 +216,19 @@ struct ppo_ctx {
     };
     int host_n_groups = 0;
     HostGroup host_grp[PPO_HOST_MAX_GROUPS];
+    // truncation events (ppo_host_observe_truncated / ppo_host_group_observe_truncated): the episodes of the open rollout that a time limit cut off, as
+    // (flat index t * N + n, final observation).  One pinned host block and one device block of the same layout, [index i32 cap | final obs f32 cap * O |
+    // value f32 cap], allocated by the first call that carries an event and grown by doubling up to T * N entries (trunc_reserve).  The observes append to
+    // the front of the host block and launch nothing; ppo_host_rollout_end sorts the list, copies it over once and folds gamma * V(final obs) into REWARDS
+    // (host_fold_truncations).  The value area of the host block holds the values of the last closed rollout, copied back behind the fold.
+    unsigned char* trunc_h = nullptr;
+    unsigned char* trunc_dev = nullptr;
+    int64_t trunc_cap = 0;
+    int64_t trunc_n = 0;                   // events of the open rollout
+    std::vector<int32_t> trunc_last_idx;   // the last closed rollout's, ascending (ppo_host_truncations)
+    hipEvent_t trunc_ev = nullptr;         // behind the fold and the copy of its values (created with the blocks, timing disabled)
+    std::vector<int32_t> trunc_order;      // sorting scratch, kept
+    std::vector<float> trunc_sorted;
     GenericCtx* gen = nullptr;       // non-null: synthetic env / network other than 2 x 64 (generic.hpp); every L-dependent entry point dispatches on it
     uint8_t* cur_mask = nullptr;     // generic path: action mask of the observation in NEXT_OBS, [N, A]
     bool force_collectives = false;  // PPO_COMM_SELFTEST: world == 1 but the multi-rank path (RCCL included) is taken
@@ -433,6 +446,9 @@ extern "C" void ppo_ctx_destroy(ppo_ctx* c) {
     if (c->host_stage) (void)hipHostFree(c->host_stage);
     if (c->host_act) (void)hipHostFree(c->host_act);
     for (auto& hg : c->host_grp) if (hg.ev) (void)hipEventDestroy(hg.ev);
+    if (c->trunc_h) (void)hipHostFree(c->trunc_h);
+    if (c->trunc_dev) (void)hipFree(c->trunc_dev);
+    if (c->trunc_ev) (void)hipEventDestroy(c->trunc_ev);
     if (c->wr_host) (void)hipHostFree(c->wr_host);
     if (c->snap) (void)hipHostFree(c->snap);
     for (hipEvent_t e : c->snap_ev) if (e) (void)hipEventDestroy(e);
@@ -2002,17 +2018,83 @@ extern "C" ppo_status ppo_host_act(ppo_ctx* c, const uint8_t* mask_h, int64_t* a
     return PPO_OK;
 }
 
+// ---- truncation events: the partial-episode bootstrap for episodes a time limit cut off (the reference ends them like terminal states,
+// PPO_Discrete.cpp:443-452).  The observes keep (t * N + n, final observation) on the host; ppo_host_rollout_end folds gamma * V(final obs) into the rewards.
+static inline int32_t* trunc_idx_h(ppo_ctx* c) { return reinterpret_cast<int32_t*>(c->trunc_h); }
+static inline float* trunc_obs_h(ppo_ctx* c) { return reinterpret_cast<float*>(c->trunc_h + (size_t)c->trunc_cap * 4); }
+static inline float* trunc_val_h(ppo_ctx* c) { return reinterpret_cast<float*>(c->trunc_h + (size_t)c->trunc_cap * 4 * (1 + c->O)); }
+static inline int32_t* trunc_idx_d(ppo_ctx* c) { return reinterpret_cast<int32_t*>(c->trunc_dev); }
+static inline float* trunc_obs_d(ppo_ctx* c) { return reinterpret_cast<float*>(c->trunc_dev + (size_t)c->trunc_cap * 4); }
+static inline float* trunc_val_d(ppo_ctx* c) { return reinterpret_cast<float*>(c->trunc_dev + (size_t)c->trunc_cap * 4 * (1 + c->O)); }
+
+// Room for `need` entries: doubling, at most max(T * N, need) (a rollout has at most one event per step and env), the open rollout's events and the
+// last closed rollout's values carried over.  The one place these blocks are allocated -- ppo_evaluate's policy (ppo_ctx_create in ppo_hip.h).
+static ppo_status trunc_reserve(ppo_ctx* c, int64_t need) {
+    if (need <= c->trunc_cap) return PPO_OK;
+    int64_t cap = std::max<int64_t>(c->trunc_cap, 64);
+    while (cap < need) cap *= 2;
+    cap = (std::min<int64_t>(cap, std::max<int64_t>((int64_t)c->T * c->N, need)) + 3) & ~(int64_t)3;   // a multiple of 4: the observation area stays 16-byte aligned
+    const size_t bytes = (size_t)cap * 4 * (2 + c->O);
+    DeviceGuard dev_guard(c);
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // nothing enqueued may still be using the blocks that are replaced
+    if (!c->trunc_ev) HIPCHK(c, hipEventCreateWithFlags(&c->trunc_ev, hipEventDisableTiming));
+    unsigned char *h = nullptr, *d = nullptr;
+    HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&h), bytes, hipHostMallocDefault));
+    if (hipMalloc(reinterpret_cast<void**>(&d), bytes) != hipSuccess) {
+        (void)hipHostFree(h);
+        return fail(c, PPO_ERR_HIP, "no device memory for %lld truncation events", (long long)cap);
+    }
+    if (c->trunc_h) {
+        std::memcpy(h, trunc_idx_h(c), (size_t)c->trunc_n * 4);
+        std::memcpy(h + (size_t)cap * 4, trunc_obs_h(c), (size_t)c->trunc_n * c->O * 4);
+        std::memcpy(h + (size_t)cap * 4 * (1 + c->O), trunc_val_h(c), c->trunc_last_idx.size() * 4);
+        (void)hipHostFree(c->trunc_h);
+        (void)hipFree(c->trunc_dev);
+    }
+    c->trunc_h = h; c->trunc_dev = d; c->trunc_cap = cap;
+    return PPO_OK;
+}
+
+// The checks of a _truncated observe over `rows` rows starting at env row0, then room for its events.  Changes nothing the rollout can see.
+static ppo_status trunc_check(ppo_ctx* c, const char* what, const int32_t* done_h, const int32_t* truncated_h, const float* final_obs_h, size_t row0, size_t rows,
+                              int64_t* n_events) {
+    int64_t k = 0;
+    if (truncated_h)
+        for (size_t n = 0; n < rows; n++) {
+            if (truncated_h[n] == 0) continue;
+            if (done_h[n] == 0) return fail(c, PPO_ERR_INVALID, "%s: env row %lld is flagged truncated but not done (a truncation ends the episode)", what, (long long)(row0 + n));
+            k++;
+        }
+    if (k > 0 && final_obs_h == nullptr) return fail(c, PPO_ERR_INVALID, "%s: %lld rows are flagged truncated and final_obs_h is null", what, (long long)k);
+    *n_events = k;
+    return k > 0 ? trunc_reserve(c, c->trunc_n + k) : PPO_OK;
+}
+// the events of step t, rows row0 .. row0 + rows, behind the list (room was made by trunc_check)
+static void trunc_append(ppo_ctx* c, int t, const int32_t* truncated_h, const float* final_obs_h, size_t row0, size_t rows) {
+    if (c->trunc_n == 0 && !c->trunc_last_idx.empty()) (void)hipEventSynchronize(c->trunc_ev);   // the last rollout's copy has read the list (long since: an act was waited for)
+    for (size_t n = 0; n < rows; n++) {
+        if (truncated_h[n] == 0) continue;
+        trunc_idx_h(c)[c->trunc_n] = (int32_t)((size_t)t * c->N + row0 + n);
+        std::memcpy(trunc_obs_h(c) + (size_t)c->trunc_n * c->O, final_obs_h + n * c->O, (size_t)c->O * 4);
+        c->trunc_n++;
+    }
+}
+
 // stepEnvs' outputs for step t (:413-483), staged for the next launch (host memory only: no launch)
-extern "C" ppo_status ppo_host_observe(ppo_ctx* c, const float* next_obs_h, const float* reward_h, const int32_t* done_h, const int32_t* fin_len_h,
-                                       const float* fin_rew_h) {
+static ppo_status host_observe_common(ppo_ctx* c, const char* what, const float* next_obs_h, const float* reward_h, const int32_t* done_h, const int32_t* fin_len_h,
+                                      const float* fin_rew_h, const int32_t* truncated_h, const float* final_obs_h) {
     NEED(c, c != nullptr, "null ctx");
-    ppo_status s = host_state(c, "ppo_host_observe");
+    ppo_status s = host_state(c, what);
     if (s != PPO_OK) return s;
-    if (c->host_n_groups > 0) return fail(c, PPO_ERR_STATE, "ppo_host_observe: the open rollout is taken by env groups (ppo_host_group_observe)");
-    if (c->host_phase != 2) return fail(c, PPO_ERR_STATE, "ppo_host_observe: no step awaits its observation (ppo_host_act first)");
+    if (c->host_n_groups > 0) return fail(c, PPO_ERR_STATE, "%s: the open rollout is taken by env groups (ppo_host_group_observe)", what);
+    if (c->host_phase != 2) return fail(c, PPO_ERR_STATE, "%s: no step awaits its observation (ppo_host_act first)", what);
     NEED(c, next_obs_h && reward_h && done_h, "null argument");
     NEED(c, (fin_len_h == nullptr) == (fin_rew_h == nullptr), "fin_len_h and fin_rew_h: both or neither");
     const size_t N = (size_t)c->N;
+    int64_t n_events = 0;
+    s = trunc_check(c, what, done_h, truncated_h, final_obs_h, 0, N, &n_events);
+    if (s != PPO_OK) return s;
+    if (n_events > 0) trunc_append(c, c->host_t - 1, truncated_h, final_obs_h, 0, N);
     unsigned char* st = c->host_stage;
     std::memcpy(st, next_obs_h, N * c->O * 4);
     std::memcpy(st + N * c->O * 4, reward_h, N * 4);
@@ -2025,6 +2107,14 @@ extern "C" ppo_status ppo_host_observe(ppo_ctx* c, const float* next_obs_h, cons
     c->host_staged = true;
     c->host_phase = 1;
     return PPO_OK;
+}
+extern "C" ppo_status ppo_host_observe(ppo_ctx* c, const float* next_obs_h, const float* reward_h, const int32_t* done_h, const int32_t* fin_len_h,
+                                       const float* fin_rew_h) {
+    return host_observe_common(c, "ppo_host_observe", next_obs_h, reward_h, done_h, fin_len_h, fin_rew_h, nullptr, nullptr);
+}
+extern "C" ppo_status ppo_host_observe_truncated(ppo_ctx* c, const float* next_obs_h, const float* reward_h, const int32_t* done_h, const int32_t* fin_len_h,
+                                                 const float* fin_rew_h, const int32_t* truncated_h, const float* final_obs_h) {
+    return host_observe_common(c, "ppo_host_observe_truncated", next_obs_h, reward_h, done_h, fin_len_h, fin_rew_h, truncated_h, final_obs_h);
 }
 
 // ---- env groups: the same rollout, group by group.  One stream: launches run in the order they were enqueued, and the activation scratch of the generic
@@ -2119,18 +2209,22 @@ extern "C" ppo_status ppo_host_group_actions(ppo_ctx* c, int32_t g, int64_t* act
     return PPO_OK;
 }
 
-extern "C" ppo_status ppo_host_group_observe(ppo_ctx* c, int32_t g, const float* next_obs_h, const float* reward_h, const int32_t* done_h,
-                                             const int32_t* fin_len_h, const float* fin_rew_h) {
+static ppo_status host_group_observe_common(ppo_ctx* c, const char* what, int32_t g, const float* next_obs_h, const float* reward_h, const int32_t* done_h,
+                                            const int32_t* fin_len_h, const float* fin_rew_h, const int32_t* truncated_h, const float* final_obs_h) {
     NEED(c, c != nullptr, "null ctx");
-    ppo_status s = host_group_state(c, "ppo_host_group_observe", g);
+    ppo_status s = host_group_state(c, what, g);
     if (s != PPO_OK) return s;
     ppo_ctx::HostGroup& G = c->host_grp[g];
     if (G.phase != 3)
-        return fail(c, PPO_ERR_STATE, "ppo_host_group_observe: group %d: no step awaits its observation at step %d (%s)", (int)g, G.t,
+        return fail(c, PPO_ERR_STATE, "%s: group %d: no step awaits its observation at step %d (%s)", what, (int)g, G.t,
                     G.phase == 1 ? "ppo_host_group_act first" : "ppo_host_group_actions first");
     NEED(c, next_obs_h && reward_h && done_h, "null argument");
     NEED(c, (fin_len_h == nullptr) == (fin_rew_h == nullptr), "fin_len_h and fin_rew_h: both or neither");
     const size_t N = (size_t)c->N, b = (size_t)G.row0, n = (size_t)G.rows;
+    int64_t n_events = 0;
+    s = trunc_check(c, what, done_h, truncated_h, final_obs_h, b, n, &n_events);
+    if (s != PPO_OK) return s;
+    if (n_events > 0) trunc_append(c, G.t - 1, truncated_h, final_obs_h, b, n);
     unsigned char* st = c->host_stage;
     std::memcpy(st + b * c->O * 4, next_obs_h, n * c->O * 4);
     std::memcpy(st + N * c->O * 4 + b * 4, reward_h, n * 4);
@@ -2142,6 +2236,92 @@ extern "C" ppo_status ppo_host_group_observe(ppo_ctx* c, int32_t g, const float*
     G.fin_given = fin_len_h != nullptr;
     G.staged = true;
     G.phase = 1;
+    return PPO_OK;
+}
+extern "C" ppo_status ppo_host_group_observe(ppo_ctx* c, int32_t g, const float* next_obs_h, const float* reward_h, const int32_t* done_h,
+                                             const int32_t* fin_len_h, const float* fin_rew_h) {
+    return host_group_observe_common(c, "ppo_host_group_observe", g, next_obs_h, reward_h, done_h, fin_len_h, fin_rew_h, nullptr, nullptr);
+}
+extern "C" ppo_status ppo_host_group_observe_truncated(ppo_ctx* c, int32_t g, const float* next_obs_h, const float* reward_h, const int32_t* done_h,
+                                                       const int32_t* fin_len_h, const float* fin_rew_h, const int32_t* truncated_h, const float* final_obs_h) {
+    return host_group_observe_common(c, "ppo_host_group_observe_truncated", g, next_obs_h, reward_h, done_h, fin_len_h, fin_rew_h, truncated_h, final_obs_h);
+}
+
+// The fold of ppo_bootstrap_rewards with the context's critic, on the path the context's values take (ppo_host_rollout_end, ppo_get_value)
+static ppo_status bootstrap_launch(ppo_ctx* c, const float* final_obs, const int32_t* index, int64_t K, float gamma, float* rewards, float* value_out) {
+    if (c->gen) {
+        const ppo_status s = gen_values(c, final_obs, K, value_out);
+        if (s != PPO_OK) return s;
+        HIPCHK(c, gen_fold_rewards(value_out, index, K, gamma, rewards, c->stream));
+    } else if (c->O == 4 || c->O == 2) {
+        HIPCHK(c, launch_bootstrap_values_mfma(B_<float>(c, PPO_BUF_PARAMS), c->L, final_obs, index, K, gamma, rewards, value_out, c->stream));
+    } else {
+        HIPCHK(c, launch_bootstrap_values(B_<float>(c, PPO_BUF_PARAMS), c->L, final_obs, index, K, gamma, rewards, value_out, c->stream));
+    }
+    return PPO_OK;
+}
+
+extern "C" ppo_status ppo_bootstrap_rewards(ppo_ctx* c, const float* final_obs, const int32_t* index, int64_t K, float gamma, float* rewards, float* value_out) {
+    NEED(c, c != nullptr, "null ctx");
+    NEED(c, K >= 0, "ppo_bootstrap_rewards: K < 0");
+    if (K == 0) return PPO_OK;
+    NEED(c, final_obs && index && rewards, "ppo_bootstrap_rewards: null argument");
+    DeviceGuard dev_guard(c);
+    if (c->gen && !value_out) {   // the generic engine's critic writes its values somewhere: the event block's value area (of the device block; the host's is not touched)
+        const ppo_status s = trunc_reserve(c, std::max<int64_t>(K, c->trunc_n));
+        if (s != PPO_OK) return s;
+        value_out = trunc_val_d(c);
+    }
+    return bootstrap_launch(c, final_obs, index, K, gamma, rewards, value_out);
+}
+
+// ppo_host_rollout_end, behind the value launch and in front of the scan: the open rollout's events, sorted by index so that the outcome does not depend on
+// how groups interleaved, in ONE asynchronous copy; the fold on REWARDS; the values back into the host block.  No event: nothing is enqueued.
+static ppo_status host_fold_truncations(ppo_ctx* c) {
+    const int64_t K = c->trunc_n, cap = c->trunc_cap;
+    c->trunc_n = 0;
+    if (K == 0) { c->trunc_last_idx.clear(); return PPO_OK; }
+    int32_t* ix = trunc_idx_h(c);
+    float* ob = trunc_obs_h(c);
+    const size_t O = (size_t)c->O;
+    if (!std::is_sorted(ix, ix + K)) {
+        c->trunc_order.resize((size_t)K);
+        for (int64_t k = 0; k < K; k++) c->trunc_order[(size_t)k] = (int32_t)k;
+        std::sort(c->trunc_order.begin(), c->trunc_order.end(), [ix](int32_t a, int32_t b) { return ix[a] < ix[b]; });
+        c->trunc_sorted.resize((size_t)K * O);
+        for (int64_t k = 0; k < K; k++) std::memcpy(c->trunc_sorted.data() + (size_t)k * O, ob + (size_t)c->trunc_order[(size_t)k] * O, O * 4);
+        std::memcpy(ob, c->trunc_sorted.data(), (size_t)K * O * 4);
+        for (int64_t k = 0; k < K; k++) c->trunc_order[(size_t)k] = ix[c->trunc_order[(size_t)k]];
+        std::memcpy(ix, c->trunc_order.data(), (size_t)K * 4);
+    }
+    c->trunc_last_idx.assign(ix, ix + K);
+    // the K indices move to the END of the index area, where the observation area begins: indices and observations are then one contiguous range
+    const size_t off = (size_t)(cap - K) * 4;
+    std::memmove(c->trunc_h + off, ix, (size_t)K * 4);
+    HIPCHK(c, hipMemcpyAsync(c->trunc_dev + off, c->trunc_h + off, (size_t)K * 4 * (1 + O), hipMemcpyHostToDevice, c->stream));
+    const ppo_status s = bootstrap_launch(c, trunc_obs_d(c), trunc_idx_d(c) + (cap - K), K, c->cfg.gamma, B_<float>(c, PPO_BUF_REWARDS), trunc_val_d(c));
+    if (s != PPO_OK) return s;
+    HIPCHK(c, hipMemcpyAsync(trunc_val_h(c), trunc_val_d(c), (size_t)K * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipEventRecord(c->trunc_ev, c->stream));
+    return PPO_OK;
+}
+
+// The truncation events of the last closed rollout: flat indices t * N + n ascending and the values V(final obs) that were folded in
+extern "C" ppo_status ppo_host_truncations(ppo_ctx* c, int64_t* count, int32_t* index_h, float* value_h, int64_t cap) {
+    NEED(c, c != nullptr, "null ctx");
+    const ppo_status s = host_state(c, "ppo_host_truncations");
+    if (s != PPO_OK) return s;
+    NEED(c, count != nullptr, "ppo_host_truncations: count is null");
+    const int64_t K = (int64_t)c->trunc_last_idx.size();
+    if ((index_h || value_h) && cap < K)
+        return fail(c, PPO_ERR_INVALID, "ppo_host_truncations: room for %lld events, the last rollout had %lld", (long long)cap, (long long)K);
+    if (K > 0 && index_h) std::memcpy(index_h, c->trunc_last_idx.data(), (size_t)K * 4);
+    if (K > 0 && value_h) {
+        DeviceGuard dev_guard(c);
+        HIPCHK(c, hipEventSynchronize(c->trunc_ev));   // the fold and the copy of its values: the update behind them keeps running
+        std::memcpy(value_h, trunc_val_h(c), (size_t)K * 4);
+    }
+    *count = K;
     return PPO_OK;
 }
 
@@ -2188,6 +2368,8 @@ extern "C" ppo_status ppo_host_rollout_end(ppo_ctx* c) {
     c->rollout_steps += T;
     c->global_step += (int64_t)T * c->cfg.global_num_envs;   // :526
     c->fin_pending = true;
+    s = host_fold_truncations(c);   // (FIN_REW, EP_REW and the episode statistics were committed above: they keep the raw rewards)
+    if (s != PPO_OK) return s;
     s = run_scan(c);
     if (s != PPO_OK) return s;
     return ppo_update(c);

@@ -198,5 +198,7 @@ hipError_t gen_clip_adamw(float* params, float* grads, float* exp_avg, float* ex
 hipError_t gen_synthetic_step(const GenLayout& L, int N, int64_t seed, int64_t env_offset, int64_t step_index, int max_episode_steps, int32_t* ep_len,
                               float* ep_rew, float* obs_out, uint8_t* mask_out, float* reward, int32_t* done, int32_t* fin_len, float* fin_rew,
                               hipStream_t s);
+// rewards[index[k]] += gamma * value[k] for k < K (two f32 roundings; distinct indices): the fold of ppo_bootstrap_rewards behind the engine's critic forward
+hipError_t gen_fold_rewards(const float* value, const int32_t* index, int64_t K, float gamma, float* rewards, hipStream_t s);
 hipError_t gen_store_step(const GenLayout& L, int N, const float* obs, const uint8_t* mask, const int64_t* act64, const float* lp, const int32_t* done_prev,
                           float* obs_t, uint8_t* mask_t, int32_t* act_t, float* lp_t, float* dones_t, hipStream_t s);

@@ -717,6 +717,16 @@ __global__ __launch_bounds__(256) void synthetic_transition_kernel(int N, int64_
     done[env] = term;
     if (fin_len) { fin_len[env] = fl; fin_rew[env] = fr; }
 }
+// Partial-episode bootstrap at time-limit truncations, generic networks (ppo_bootstrap_rewards): value[k] = Critic(final obs of event k) comes from the
+// engine's own critic forward; one thread per event folds it into its reward in two roundings.  Indices are distinct (the caller's promise).
+__global__ __launch_bounds__(256) void fold_rewards_kernel(const float* __restrict__ value, const int32_t* __restrict__ index, int64_t K, float gamma,
+                                                           float* __restrict__ rewards) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= K) return;
+    const int32_t i = index[k];
+    rewards[i] = __fadd_rn(rewards[i], __fmul_rn(gamma, value[k]));
+}
+
 // rollout stores of one step (PPO_MultiDiscrete.cpp:547-562): obs, masks, actions, log-probs, the PREVIOUS step's done flags
 __global__ __launch_bounds__(256) void store_step_kernel(GenLayout L, int N, const float* __restrict__ obs, const uint8_t* __restrict__ mask,
                                                          const int64_t* __restrict__ act64, const float* __restrict__ lp, const int32_t* __restrict__ done_prev,
@@ -1312,6 +1322,12 @@ hipError_t gen_synthetic_step(const GenLayout& L, int N, int64_t seed, int64_t e
     if (reward) hipLaunchKernelGGL(synthetic_transition_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, seed, env_offset, step_index, max_episode_steps, ep_len,
                                    ep_rew, reward, done, fin_len, fin_rew);
     if (obs_out) hipLaunchKernelGGL(synthetic_obs_kernel, dim3(N), dim3(64), 0, s, L, N, seed, env_offset, step_index + (reward ? 1 : 0), obs_out, mask_out);
+    return hipGetLastError();
+}
+
+hipError_t gen_fold_rewards(const float* value, const int32_t* index, int64_t K, float gamma, float* rewards, hipStream_t s) {
+    if (K <= 0) return hipSuccess;
+    hipLaunchKernelGGL(fold_rewards_kernel, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, s, value, index, K, gamma, rewards);
     return hipGetLastError();
 }
 

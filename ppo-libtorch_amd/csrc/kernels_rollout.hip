@@ -1015,6 +1015,31 @@ __global__ __launch_bounds__(64) void values_kernel(const float* __restrict__ pa
     }
 }
 
+// values_kernel over the dense [K, OBS] block of final observations of truncated episodes, with the partial-episode bootstrap as its epilogue
+// (ppo_bootstrap_rewards): rewards[index[k]] += gamma * v in two roundings, value_out[k] = v (may be null).  The same per-row arithmetic, so v is what
+// values_kernel gives the same observation; indices are distinct (the caller's promise), so the read-modify-write is plain.
+template <int OBS>
+__global__ __launch_bounds__(64) void bootstrap_values_kernel(const float* __restrict__ params, NetLayout L, const float* __restrict__ final_obs,
+                                                              const int32_t* __restrict__ index, int64_t K, float gamma, float* __restrict__ rewards,
+                                                              float* __restrict__ value_out) {
+    __shared__ __attribute__((aligned(16))) float lds[PPO_HIDDEN];
+    const int lane = threadIdx.x;
+    LaneNet<OBS> critic;
+    load_lane_net<OBS>(critic, params, L, 0, lane);
+    for (int64_t row = blockIdx.x; row < K; row += gridDim.x) {
+        const float* src = final_obs + row * OBS;
+        float x[OBS];
+#pragma unroll
+        for (int k = 0; k < OBS; k++) x[k] = src[k];
+        const float v = critic_head(params, L, trunk_forward<OBS>(critic, x, lds, lane), lane);
+        if (lane == 0) {
+            const int32_t i = index[row];
+            rewards[i] = __fadd_rn(rewards[i], __fmul_rn(gamma, v));
+            if (value_out) value_out[row] = v;
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // Stand-alone policy evaluation (Agent::getActionAndValueDiscrete / Masked): one wave per row, grid-stride.
 // ---------------------------------------------------------------------------------------------------------
@@ -1436,6 +1461,17 @@ hipError_t launch_values(const float* params, const NetLayout& L, const float* o
     if (L.obs == 4) hipLaunchKernelGGL((values_kernel<4>), dim3(grid), dim3(64), 0, s, params, L, obs0, n0, out0, obs1, n1, out1);
     else if (L.obs == 2) hipLaunchKernelGGL((values_kernel<2>), dim3(grid), dim3(64), 0, s, params, L, obs0, n0, out0, obs1, n1, out1);
     else if (L.obs == 8) hipLaunchKernelGGL((values_kernel<8>), dim3(grid), dim3(64), 0, s, params, L, obs0, n0, out0, obs1, n1, out1);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+hipError_t launch_bootstrap_values(const float* params, const NetLayout& L, const float* final_obs, const int32_t* index, int64_t K, float gamma,
+                                   float* rewards, float* value_out, hipStream_t s) {
+    if (K <= 0) return hipSuccess;
+    const unsigned grid = (unsigned)(K < 8192 ? K : 8192);
+    if (L.obs == 4) hipLaunchKernelGGL((bootstrap_values_kernel<4>), dim3(grid), dim3(64), 0, s, params, L, final_obs, index, K, gamma, rewards, value_out);
+    else if (L.obs == 2) hipLaunchKernelGGL((bootstrap_values_kernel<2>), dim3(grid), dim3(64), 0, s, params, L, final_obs, index, K, gamma, rewards, value_out);
+    else if (L.obs == 8) hipLaunchKernelGGL((bootstrap_values_kernel<8>), dim3(grid), dim3(64), 0, s, params, L, final_obs, index, K, gamma, rewards, value_out);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }

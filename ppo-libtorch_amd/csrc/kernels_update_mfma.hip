@@ -1982,6 +1982,126 @@ __global__ __launch_bounds__(256, 2) void values_mfma_kernel(const float* __rest
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Partial-episode bootstrap at time-limit truncations (ppo_bootstrap_rewards; ppo_host_rollout_end with truncation events): for k < K
+//   v = Critic(final_obs[k]);  rewards[index[k]] += gamma * v;  value_out[k] = v (may be null)
+// A copy of values_mfma_kernel's tile body -- the same products in the same order, so v is, bit for bit, the value the rollout's critic launch gives
+// the same observation -- over the dense [K, OBS] block of final observations, with the scattered fold as its epilogue.  (A body shared through a
+// __device__ function changed values_mfma_kernel's instruction schedule; the copy leaves that kernel as it was.)
+// ---------------------------------------------------------------------------------------------------------
+template <int OBS>
+__global__ __launch_bounds__(256, 2) void bootstrap_values_mfma_kernel(const float* __restrict__ P, NetLayout L, const float* __restrict__ final_obs,
+                                                                       const int32_t* __restrict__ index, int64_t K, float gamma,
+                                                                       float* __restrict__ rewards, float* __restrict__ value_out) {
+    __shared__ __attribute__((aligned(16))) uint16_t sW2p[2 * 64 * WS];
+    __shared__ __attribute__((aligned(16))) float sB1[64], sB2[64], sW3[64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int s = lane & 31, hi = lane >> 5;
+    {
+        float wv[16];
+#pragma unroll
+        for (int i = 0; i < 16; i++) wv[i] = P[L.w2[0] + tid + i * 256];
+#pragma unroll
+        for (int i = 0; i < 16; i++) {
+            const int e = tid + i * 256;
+            const int n = e >> 6, k = e & 63;
+            const float w = wv[i] * TANH_C;
+            uint32_t p1, p2;
+            split2(w, 0.0f, p1, p2);
+            const int pf = n * WS + slot_of_unit(k);
+            sW2p[pf] = (uint16_t)p1; sW2p[64 * WS + pf] = (uint16_t)p2;
+        }
+    }
+    if (tid < 64) { sB1[tid] = P[L.b1[0] + tid] * TANH_C; sB2[tid] = P[L.b2[0] + tid] * TANH_C; sW3[tid] = P[L.w3[0] + tid]; }
+    const float b3 = P[L.b3[0]];
+    constexpr int L1S = (OBS + 1) / 2;
+    float w1op[2][L1S];
+#pragma unroll
+    for (int t = 0; t < 2; t++)
+#pragma unroll
+        for (int stp = 0; stp < L1S; stp++) {
+            const int o = 2 * stp + hi;
+            w1op[t][stp] = o < OBS ? P[L.w1[0] + (s + 32 * t) * OBS + o] * TANH_C : 0.0f;
+        }
+    __syncthreads();
+    const int64_t n_tiles = (K + MT - 1) / MT;
+    // rows one tile ahead, as values_mfma_kernel: a row >= K reads row 0, is zeroed at use and stores nothing
+    auto load_x = [&](int64_t tl, float* xo) {
+        const int64_t r = tl * MT + s;
+        const float* src = r < K ? final_obs + r * OBS : final_obs;
+#pragma unroll
+        for (int stp = 0; stp < L1S; stp++) xo[stp] = src[(2 * stp + 1 < OBS) ? 2 * stp + hi : 2 * stp];
+    };
+    const int64_t tile_step = (int64_t)gridDim.x * 4;
+    float x_n[L1S];
+    load_x((int64_t)blockIdx.x * 4 + wave, x_n);
+    for (int64_t tile = (int64_t)blockIdx.x * 4 + wave; tile < n_tiles; tile += tile_step) {
+        const int64_t row = tile * MT + s;
+        const bool valid = row < K;
+        float xb[L1S];
+#pragma unroll
+        for (int stp = 0; stp < L1S; stp++) xb[stp] = (valid && (2 * stp + 1 < OBS || hi == 0)) ? x_n[stp] : 0.0f;
+        load_x(tile + tile_step, x_n);
+        float h1[32];
+#pragma unroll
+        for (int t = 0; t < 2; t++) {
+            f32x16 acc;
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const float4 b = ld4(&sB1[8 * q + 4 * hi + 32 * t]);
+                acc[4 * q] = b.x; acc[4 * q + 1] = b.y; acc[4 * q + 2] = b.z; acc[4 * q + 3] = b.w;
+            }
+#pragma unroll
+            for (int stp = 0; stp < L1S; stp++) {
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w1op[t][stp], xb[stp], acc, 0, 0, 0);
+            }
+#pragma unroll
+            for (int r = 0; r < 16; r++) h1[16 * t + r] = tanh_scaled(acc[r]);
+        }
+        uint32_t hp[2][16];
+#pragma unroll
+        for (int j = 0; j < 16; j++) split2(h1[2 * j], h1[2 * j + 1], hp[0][j], hp[1][j]);
+        auto aptr = [&](int g, int term) {
+            return reinterpret_cast<const u32x4*>(sW2p + term * 64 * WS + (s + 32 * (g >> 2)) * WS + (g & 3) * 16 + hi * 8);
+        };
+        float part = 0.0f;
+        f32x16 acc;
+        u32x4 an1 = *aptr(0, 0), an2 = *aptr(0, 1);
+#pragma unroll
+        for (int g = 0; g < 8; g++) {
+            const int t = g >> 2, c = g & 3;
+            if (c == 0) {
+#pragma unroll
+                for (int qq = 0; qq < 4; qq++) {
+                    const float4 b = ld4(&sB2[8 * qq + 4 * hi + 32 * t]);
+                    acc[4 * qq] = b.x; acc[4 * qq + 1] = b.y; acc[4 * qq + 2] = b.z; acc[4 * qq + 3] = b.w;
+                }
+            }
+            const u32x4 a1 = an1, a2 = an2;
+            if (g + 1 < 8) { an1 = *aptr(g + 1, 0); an2 = *aptr(g + 1, 1); }
+            MF_PIN();
+            const u32x4 b1 = { hp[0][4 * c], hp[0][4 * c + 1], hp[0][4 * c + 2], hp[0][4 * c + 3] };
+            const u32x4 b2 = { hp[1][4 * c], hp[1][4 * c + 1], hp[1][4 * c + 2], hp[1][4 * c + 3] };
+            acc = mfma_x2(a1, a2, b1, b2, acc);
+            if (c == 3) {
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    const float4 w = ld4(&sW3[8 * q + 4 * hi + 32 * t]);
+                    part = __builtin_fmaf(tanh_scaled(acc[4 * q]), w.x, part); part = __builtin_fmaf(tanh_scaled(acc[4 * q + 1]), w.y, part);
+                    part = __builtin_fmaf(tanh_scaled(acc[4 * q + 2]), w.z, part); part = __builtin_fmaf(tanh_scaled(acc[4 * q + 3]), w.w, part);
+                }
+            }
+        }
+        const float other = __shfl_xor(part, 32, 64);
+        const float v = (part + other) + b3;
+        if (valid && hi == 0) {   // distinct indices: a plain read-modify-write, the product and the sum rounded separately
+            const int32_t i = index[row];
+            rewards[i] = __fadd_rn(rewards[i], __fmul_rn(gamma, v));
+            if (value_out) value_out[row] = v;
+        }
+    }
+}
+
 }  // namespace
 
 // One 8-wave workgroup per CU (256 vector registers per wave: two waves per SIMD is all a CU holds; LDS ~95 KB), half of them per net.
@@ -2091,6 +2211,17 @@ hipError_t launch_values_mfma(const float* params, const NetLayout& L, const flo
     const unsigned grid = (unsigned)(wg_needed < 1024 ? wg_needed : 1024);
     if (L.obs == 4) hipLaunchKernelGGL((values_mfma_kernel<4>), dim3(grid), dim3(256), 0, s, params, L, obs0, n0, out0, obs1, n1, out1);
     else if (L.obs == 2) hipLaunchKernelGGL((values_mfma_kernel<2>), dim3(grid), dim3(256), 0, s, params, L, obs0, n0, out0, obs1, n1, out1);
+    else return hipErrorNotSupported;
+    return hipGetLastError();
+}
+
+hipError_t launch_bootstrap_values_mfma(const float* params, const NetLayout& L, const float* final_obs, const int32_t* index, int64_t K, float gamma,
+                                        float* rewards, float* value_out, hipStream_t s) {
+    if (K <= 0) return hipSuccess;
+    const int64_t wg_needed = ((K + MT - 1) / MT + 3) / 4;
+    const unsigned grid = (unsigned)(wg_needed < 1024 ? wg_needed : 1024);
+    if (L.obs == 4) hipLaunchKernelGGL((bootstrap_values_mfma_kernel<4>), dim3(grid), dim3(256), 0, s, params, L, final_obs, index, K, gamma, rewards, value_out);
+    else if (L.obs == 2) hipLaunchKernelGGL((bootstrap_values_mfma_kernel<2>), dim3(grid), dim3(256), 0, s, params, L, final_obs, index, K, gamma, rewards, value_out);
     else return hipErrorNotSupported;
     return hipGetLastError();
 }

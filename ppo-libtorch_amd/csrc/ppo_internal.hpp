@@ -720,6 +720,12 @@ hipError_t launch_clip_adamw(float* params, float* grads, float* exp_avg, float*
                              StepStats* stats_out, double* clipfrac_accum, double* norm2_scratch, hipStream_t s, OptGuard guard);
 // recomputes the three maxima of OptGuard from the parameters (after the host wrote them): wr_dev and wr_host both
 hipError_t launch_weight_range(const float* params, const NetLayout& L, uint32_t* wr_dev, uint32_t* wr_host, hipStream_t s);
+// partial-episode bootstrap (ppo_bootstrap_rewards): v = Critic(final_obs[k]), rewards[index[k]] += gamma * v (two roundings), value_out[k] = v (may be
+// null), k < K; the critic arithmetic of launch_values_mfma (obs in {2, 4}) / launch_values (obs in {2, 4, 8}).  K <= 0: no launch.
+hipError_t launch_bootstrap_values_mfma(const float* params, const NetLayout& L, const float* final_obs, const int32_t* index, int64_t K, float gamma,
+                                        float* rewards, float* value_out, hipStream_t s);
+hipError_t launch_bootstrap_values(const float* params, const NetLayout& L, const float* final_obs, const int32_t* index, int64_t K, float gamma,
+                                   float* rewards, float* value_out, hipStream_t s);
 // batched critic on the matrix cores (obs in {2, 4}); same contract as launch_values
 hipError_t launch_values_mfma(const float* params, const NetLayout& L, const float* obs0, int64_t n0, float* out0, const float* obs1, int64_t n1,
                               float* out1, hipStream_t s);

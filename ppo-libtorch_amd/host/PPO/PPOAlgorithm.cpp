@@ -72,6 +72,7 @@ void PPOAlgorithm::getArgs() {
         }
         I("environment", "max_episode_steps", m_max_episode_steps);
         I("environment", "env_groups", m_env_groups);   // extension key (PPO_HostEnv); absent in the reference's files: prints nothing then
+        B("environment", "bootstrap_truncated", m_bootstrap_truncated);   // extension key (PPO_HostEnv), likewise
         I("general", "seed", m_seed);
         I("general", "total_timesteps", m_total_timesteps);
         B("general", "use_cuda", m_use_cuda);

@@ -82,6 +82,7 @@ class PPOAlgorithm {
     int64_t m_checkpoint_updates;
     int64_t m_max_episode_steps;
     int64_t m_env_groups = 1;            // extension ([environment] env_groups): PPO_HostEnv's env groups; the device-env algorithms have no use for it
+    bool m_bootstrap_truncated = false;  // extension ([environment] bootstrap_truncated): PPO_HostEnv bootstraps the value where a time limit cut an episode off
 
     int64_t m_batch_size;
     int64_t m_minibatch_size;

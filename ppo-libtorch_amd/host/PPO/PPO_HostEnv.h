@@ -15,6 +15,12 @@
 // groups (the remainder goes to the last) and the rollout is pipelined: while the pool steps group k, the main thread enqueues the policy call of the
 // next group and collects its actions (ppo_host_group_*).  The GPU and host-link round trip of one group then hides behind the env stepping of
 // another.  Training does not depend on g in a single bit.
+//
+// Time limits (setBootstrapTruncated(true), or `bootstrap_truncated = true` in [environment]; default false): the reference ends an episode that reaches
+// max_episode_steps like one the env terminated (PPO_Discrete.cpp:443-452) and never reads the fourth value step() returns, its `truncated` flag.  With
+// the option on, an episode ends when the env terminates, when the env itself reports truncated, or at max_episode_steps; one that ended without the
+// env's `terminated` counts as truncated, the observation it ended on is kept, and the rollout's end bootstraps the value there (r + gamma V(final
+// observation)) instead of treating the state as terminal (include/ppo_hip.h, "Time-limit truncations").  Off, stepEnvs is the reference's.
 #pragma once
 #include <algorithm>
 #include <atomic>
@@ -38,7 +44,7 @@ class PPO_HostEnv : public PPOAlgorithm {
 
     explicit PPO_HostEnv(EnvFactory factory = nullptr)
         : PPOAlgorithm(PPO_ENV_HOST, Masked ? PPO_DIST_MASKED : PPO_DIST_CATEGORICAL, 4, 500) {
-        getArgs();   // (reads the extension key env_groups too)
+        getArgs();   // (reads the extension keys env_groups and bootstrap_truncated too)
         construct();
         setEnvGroups(m_env_groups);
         m_envs.reserve(static_cast<size_t>(m_num_envs));
@@ -49,6 +55,8 @@ class PPO_HostEnv : public PPOAlgorithm {
         m_done.assign(N, 0);
         m_fin_len.assign(N, 0);
         m_fin_rew.assign(N, 0.0f);
+        m_truncated.assign(N, 0);
+        m_final_obs.assign(N * static_cast<size_t>(m_obs_size), 0.0f);
         m_action.assign(N, 0);
         if (Masked) m_mask.assign(N * static_cast<size_t>(m_action_size), 1);
     }
@@ -62,6 +70,10 @@ class PPO_HostEnv : public PPOAlgorithm {
         m_env_groups = g;
     }
     int64_t envGroups() const { return m_env_groups; }
+
+    // bootstrap the value where a time limit (the env's own truncated flag, or max_episode_steps) cut an episode off; false: the reference's stepEnvs
+    void setBootstrapTruncated(bool on) { m_bootstrap_truncated = on; }
+    bool bootstrapTruncated() const { return m_bootstrap_truncated; }
 
     // initEnvs (:365-402): env 0 once for the obs-size check, then every env (env 0 twice, as the reference); NEXT_OBS = the reset observations
     ppo::Tensor initEnvs() {
@@ -189,7 +201,12 @@ class PPO_HostEnv : public PPOAlgorithm {
             if constexpr (Masked) gatherMasks();
             ppo::check(ppo_host_act(m_ctx, Masked ? m_mask.data() : nullptr, m_action.data()), m_ctx, "rollout");
             stepEnvs(m_action);
-            ppo::check(ppo_host_observe(m_ctx, m_next_obs.data(), m_reward.data(), m_done.data(), m_fin_len.data(), m_fin_rew.data()), m_ctx, "rollout");
+            if (m_bootstrap_truncated)
+                ppo::check(ppo_host_observe_truncated(m_ctx, m_next_obs.data(), m_reward.data(), m_done.data(), m_fin_len.data(), m_fin_rew.data(),
+                                                      m_truncated.data(), m_final_obs.data()),
+                           m_ctx, "rollout");
+            else
+                ppo::check(ppo_host_observe(m_ctx, m_next_obs.data(), m_reward.data(), m_done.data(), m_fin_len.data(), m_fin_rew.data()), m_ctx, "rollout");
         }
         ppo::check(ppo_host_rollout_end(m_ctx), m_ctx, "update");
     }
@@ -200,8 +217,20 @@ class PPO_HostEnv : public PPOAlgorithm {
         const size_t k = static_cast<size_t>(i);
         Env& env = *m_envs[k];
         auto [obs, reward, terminated, info] = env.step(action[k]);
-        (void)info;
-        if (static_cast<int64_t>(env.episode_length) == m_max_episode_steps) terminated = true;
+        if (m_bootstrap_truncated) {
+            // the episode ends where the env terminates, where the env's own fourth value says truncated, or at max_episode_steps; it was truncated
+            // when it ended without the env's `terminated`: its last observation is kept for the bootstrap
+            const bool cut = !terminated && (info || static_cast<int64_t>(env.episode_length) == m_max_episode_steps);
+            m_truncated[k] = cut ? 1 : 0;
+            if (cut) {
+                if (static_cast<int64_t>(obs.size()) != m_obs_size) { bad_width = static_cast<int64_t>(obs.size()); return; }
+                std::memcpy(m_final_obs.data() + k * static_cast<size_t>(m_obs_size), obs.data(), sizeof(float) * static_cast<size_t>(m_obs_size));
+                terminated = true;
+            }
+        } else {
+            (void)info;
+            if (static_cast<int64_t>(env.episode_length) == m_max_episode_steps) terminated = true;
+        }
         m_fin_len[k] = 0;
         m_fin_rew[k] = 0.0f;
         if (terminated) {
@@ -257,9 +286,14 @@ class PPO_HostEnv : public PPOAlgorithm {
             const size_t b = static_cast<size_t>(bounds[static_cast<size_t>(g)]);
             latch[static_cast<size_t>(g)].wait();
             if (bad_width >= 0) return;
-            ppo::check(ppo_host_group_observe(m_ctx, static_cast<int32_t>(g), m_next_obs.data() + b * O, m_reward.data() + b, m_done.data() + b,
-                                              m_fin_len.data() + b, m_fin_rew.data() + b),
-                       m_ctx, "rollout");
+            if (m_bootstrap_truncated)
+                ppo::check(ppo_host_group_observe_truncated(m_ctx, static_cast<int32_t>(g), m_next_obs.data() + b * O, m_reward.data() + b, m_done.data() + b,
+                                                            m_fin_len.data() + b, m_fin_rew.data() + b, m_truncated.data() + b, m_final_obs.data() + b * O),
+                           m_ctx, "rollout");
+            else
+                ppo::check(ppo_host_group_observe(m_ctx, static_cast<int32_t>(g), m_next_obs.data() + b * O, m_reward.data() + b, m_done.data() + b,
+                                                  m_fin_len.data() + b, m_fin_rew.data() + b),
+                           m_ctx, "rollout");
             if (++t_of[static_cast<size_t>(g)] < T) act(g);
         };
         ppo::check(ppo_host_rollout_begin_groups(m_ctx, static_cast<int32_t>(G), bounds.data()), m_ctx, "rollout");
@@ -304,8 +338,8 @@ class PPO_HostEnv : public PPOAlgorithm {
         }
     }
 
-    std::vector<float> m_next_obs, m_reward, m_fin_rew;
-    std::vector<int32_t> m_done, m_fin_len;
+    std::vector<float> m_next_obs, m_reward, m_fin_rew, m_final_obs;   // m_final_obs [k]: the observation env k's truncated episode ended on
+    std::vector<int32_t> m_done, m_fin_len, m_truncated;
     std::vector<int64_t> m_action;
     std::vector<uint8_t> m_mask;
 };
