@@ -171,7 +171,9 @@ PPO_API int32_t ppo_abi_version(void);
  * parameters, AdamW state, env SoA, reset-stream table); no allocation happens afterwards -- except ppo_evaluate's scratch (per-episode arrays, the
  * evaluation reset table), allocated by its first call, kept, and grown only by a call that asks for more episodes than any before it; and, by the same
  * policy, the truncation-event list of caller-stepped rollouts (one pinned host block and its device twin), allocated by the first
- * ppo_host_observe_truncated / ppo_host_group_observe_truncated call that carries an event and grown by doubling up to num_steps * num_envs entries. */
+ * ppo_host_observe_truncated / ppo_host_group_observe_truncated call that carries an event and grown by doubling up to num_steps * num_envs entries;
+ * and the ppo_dev_* calls' two hand-over events (created by the first call on a stream other than the context's) and two device event lists
+ * (num_steps * num_envs entries each, a counter, a pinned word and an event per list), made once by the first ppo_dev_observe that passes `truncated`. */
 PPO_API ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out);
 PPO_API void ppo_ctx_destroy(ppo_ctx* ctx);
 /* Error text of the last failing call on ctx (ctx == NULL: of the last failing ppo_ctx_create in this thread).
@@ -450,6 +452,54 @@ PPO_API ppo_status ppo_host_truncations(ppo_ctx* ctx, int64_t* count, int32_t* i
  * final_obs f32 [K,O], index i32 [K] (distinct: the caller's promise; no atomics are used), rewards f32, value_out f32 [K]: device pointers.  v is
  * bit for bit ppo_get_value's.  K == 0: no launch.  Null pointers with K > 0, or K < 0: PPO_ERR_INVALID. */
 PPO_API ppo_status ppo_bootstrap_rewards(ppo_ctx* ctx, const float* final_obs, const int32_t* index, int64_t K, float gamma, float* rewards, float* value_out);
+
+/* Caller-stepped environments on the device (new): act and observe through DEVICE arrays, for envs that already live on the GPU (the caller's own HIP
+ * kernels, PyTorch-ROCm tensors).  The reference steps its envs on the host between two device calls (PPO_Discrete.cpp:365-483, 524-548); with the ppo_host_*
+ * calls above a device-resident env pays two PCIe crossings and one host wait per step for that.  These calls keep the step on the chip:
+ *
+ *   ppo_dev_env_reset(ctx, obs0, stream)                             once
+ *   per iteration:  ppo_host_rollout_begin(ctx)
+ *                   T x { ppo_dev_act(ctx, mask, action, stream); the caller's env kernels on `stream`;
+ *                         ppo_dev_observe(ctx, obs, reward, done, fin_len, fin_rew, truncated, final_obs, stream) }
+ *                   ppo_host_rollout_end(ctx)                        (ppo_host_truncations as usual)
+ *
+ * They serve PPO_ENV_HOST contexts.  Every bulk pointer is a DEVICE pointer; caller_stream is the hipStream_t on which the caller produces and consumes them.
+ * Stream semantics:
+ *   - Every call only enqueues.  None of the three waits for the device or copies to or from host memory.
+ *   - The context's stream (ppo_stream) is created hipStreamNonBlocking, so the hand-over is explicit: on entry the call records an event on
+ *     caller_stream and makes the context's stream wait for it; after its last launch it records an event on the context's stream and makes caller_stream
+ *     wait for that.
+ *   - Input arrays are therefore consumed in stream order, like hipMemcpyAsync's source: work the caller enqueues on caller_stream after the call returns
+ *     may overwrite them.  `action` is valid for work enqueued on caller_stream after ppo_dev_act returns.
+ *   - caller_stream == ppo_stream(ctx) means "the same stream": no events.  NULL is the null stream and gets the event hand-over like any other stream; it
+ *     is NOT shorthand for the context's stream.
+ * Launches per env step: ppo_dev_act one, ppo_dev_observe one, or two when `truncated` is passed.  ppo_dev_observe COMMITS its step at once (the ppo_host_*
+ * calls stage it for the next act), so ppo_host_rollout_end of a device-fed rollout has no step to commit and no events to fold: it goes straight to the
+ * value launch, the scan and the update.  Everything else is as for the host calls: the sampler key (seed, env_offset + row, rollout_steps + t, head), the
+ * choice of arithmetic once per rollout, rollout_steps / global_step / finished episodes, the generic engine's per-step sequence, PPO_BUF_MASKS: a
+ * device-fed rollout equals the host-fed rollout of the same data bit for bit (tests/test_gpu_dev_env.py).
+ * A rollout is host-fed or device-fed AS A WHOLE; its first act decides.  Errors: PPO_ERR_STATE for a ppo_host_act / ppo_host_observe in a device-fed
+ * rollout and a ppo_dev_act / ppo_dev_observe in a host-fed one (the message names both families), for ppo_dev_* on a rollout opened with
+ * ppo_host_rollout_begin_groups (groups hide a host wait that does not exist here), and for the sequence errors of the host calls (act twice, observe
+ * before act, act beyond step T - 1, end early, device-env context).  PPO_ERR_INVALID for a null action / next_obs / reward / done, fin_len / fin_rew
+ * not both-or-neither, and truncated != NULL with final_obs == NULL.  A failing call enqueues nothing and changes nothing.
+ * Truncations: with truncated != NULL one more launch per observe, behind the commit, folds the bootstrap where truncated[n] != 0 AND done[n] != 0:
+ * PPO_BUF_REWARDS[t, n] = f32(r + f32(gamma * V(final_obs[n]))), gamma = cfg.gamma, V bit for bit ppo_get_value's (the kernel ppo_bootstrap_rewards would
+ * run for this context); FIN_REW, EP_REW and the episode statistics keep the raw reward.  A flag on a row with done[n] == 0 is IGNORED -- the host calls
+ * refuse it with PPO_ERR_INVALID, the device call cannot look without a host wait.  Rows of final_obs that are not flagged are never read.  The step's
+ * common case, no flagged row, costs one pass over truncated and done.  The events go to a device list; ppo_host_truncations after a device-fed rollout
+ * waits for that rollout's last fold only (not for the update), copies the list and returns it with indices ascending, as after a host-fed rollout.
+ * Generic networks (anything but the reference's 2 x 64 with obs 2, 4, 8) take the ppo_dev_* calls fully EXCEPT a non-NULL `truncated`, which returns
+ * PPO_ERR_UNSUPPORTED and changes nothing: the generic engine chooses its critic kernel by the row count, that choice changes bits, and a critic launch
+ * that needs no count is a separate piece of work.  Device callers of generic networks can still fold with ppo_bootstrap_rewards where they know K. */
+/* ppo_host_env_reset from a device array: obs f32 [N,O] = every env's reset observation.  Enqueued. */
+PPO_API ppo_status ppo_dev_env_reset(ppo_ctx* ctx, const float* obs /* [N,O] */, void* caller_stream);
+/* ppo_host_act with the actions left on the device: mask u8 [N,A] or NULL (masked policies; NULL = all valid), action i64 [N,H]. */
+PPO_API ppo_status ppo_dev_act(ppo_ctx* ctx, const uint8_t* mask /* [N,A] or NULL */, int64_t* action /* [N,H] */, void* caller_stream);
+/* ppo_host_observe_truncated from device arrays, committed at once (see above). */
+PPO_API ppo_status ppo_dev_observe(ppo_ctx* ctx, const float* next_obs /* [N,O] */, const float* reward /* [N] */, const int32_t* done /* [N] */,
+                                   const int32_t* fin_len /* [N] or NULL */, const float* fin_rew /* [N] or NULL */,
+                                   const int32_t* truncated /* [N] or NULL */, const float* final_obs /* [N,O] or NULL */, void* caller_stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Evaluation (new; the reference reports only the mean over the last 100 exploration episodes of its training envs, PPO_Discrete.cpp:474-480, Utils.h:72-78)

@@ -52,6 +52,7 @@ ABI_SYMBOLS = [
     "ppo_host_rollout_begin_groups", "ppo_host_group_act", "ppo_host_group_actions", "ppo_host_group_observe",
     "ppo_policy_act_greedy", "ppo_evaluate",
     "ppo_host_observe_truncated", "ppo_host_group_observe_truncated", "ppo_host_truncations", "ppo_bootstrap_rewards",
+    "ppo_dev_env_reset", "ppo_dev_act", "ppo_dev_observe",
 ]
 
 
@@ -144,6 +145,9 @@ def lib():
         L.ppo_host_group_observe_truncated.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 7
         L.ppo_host_truncations.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_int64]
         L.ppo_bootstrap_rewards.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]
+        L.ppo_dev_env_reset.argtypes = [C.c_void_p] * 3
+        L.ppo_dev_act.argtypes = [C.c_void_p] * 4
+        L.ppo_dev_observe.argtypes = [C.c_void_p] * 9
         for name in ABI_SYMBOLS:
             getattr(L, name)  # AttributeError if the build lacks a declared symbol
         if L.ppo_abi_version() != ABI_VERSION:
@@ -437,6 +441,41 @@ class Context:
             args.append(np.ascontiguousarray(truncated, np.int32).reshape(self.N) if truncated is not None else None)
             args.append(np.ascontiguousarray(final_obs, np.float32).reshape(self.N, self.O) if final_obs is not None else None)
         _check(fn(self.h, *(x.ctypes.data_as(C.c_void_p) if x is not None else None for x in args)), self.h)
+
+    # ---- caller-stepped environments on the device (include/ppo_hip.h ppo_dev_*): every array stays on the GPU, every call only enqueues
+    @staticmethod
+    def _dev_ptr(a):
+        """A device array argument: None, a DeviceArray, an int / c_void_p, or any object with data_ptr() (a torch tensor)."""
+        if a is None:
+            return None
+        if isinstance(a, DeviceArray):
+            return a.ptr
+        if isinstance(a, C.c_void_p):
+            return a
+        if hasattr(a, "data_ptr"):
+            return C.c_void_p(int(a.data_ptr()))
+        return C.c_void_p(int(a))
+
+    def _dev_stream(self, stream):
+        """None = the context's own stream (no hand-over events); an int / c_void_p (0 = the null stream); an object with .cuda_stream (torch.cuda.Stream)."""
+        if stream is None:
+            return C.c_void_p(self.stream())
+        if isinstance(stream, C.c_void_p):
+            return stream
+        return C.c_void_p(int(getattr(stream, "cuda_stream", stream)))
+
+    def dev_env_reset(self, obs, stream=None):
+        """initEnvs from a device array: obs f32 [N,O] = every env's reset observation."""
+        _check(lib().ppo_dev_env_reset(self.h, self._dev_ptr(obs), self._dev_stream(stream)), self.h)
+
+    def dev_act(self, action, mask=None, stream=None):
+        """Step t of the rollout: the sampled actions go to the device array action i64 [N,H], valid for work enqueued on `stream` after the call."""
+        _check(lib().ppo_dev_act(self.h, self._dev_ptr(mask), self._dev_ptr(action), self._dev_stream(stream)), self.h)
+
+    def dev_observe(self, obs, reward, done, fin_len=None, fin_rew=None, truncated=None, final_obs=None, stream=None):
+        """The envs' outputs for the step just acted on, as device arrays (obs f32 [N,O], reward f32 [N], done i32 [N], ...), consumed in stream order."""
+        _check(lib().ppo_dev_observe(self.h, *(self._dev_ptr(x) for x in (obs, reward, done, fin_len, fin_rew, truncated, final_obs)),
+                                     self._dev_stream(stream)), self.h)
 
     def host_truncations(self):
         """The truncation events of the last closed rollout: (flat indices t * N + n ascending i32 [K], folded-in values V(final obs) f32 [K])."""

@@ -229,6 +229,24 @@ struct ppo_ctx {
     hipEvent_t trunc_ev = nullptr;         // behind the fold and the copy of its values (created with the blocks, timing disabled)
     std::vector<int32_t> trunc_order;      // sorting scratch, kept
     std::vector<float> trunc_sorted;
+    // caller-stepped envs on the device (ppo_dev_*): a rollout is host-fed or device-fed as a whole, decided by its first act.  A device-fed step is
+    // committed by ppo_dev_observe at once (host_staged stays false).  Truncation events of device-fed rollouts live in two device lists used by
+    // alternate rollouts, so that the last CLOSED rollout's events stay readable while the next one is fed; each list: a counter, [T * N] indices, [T * N]
+    // values, allocated by the first ppo_dev_observe that passes flags.  dev_count_h: pinned copies of the two counters, taken at ppo_host_rollout_end.
+    int host_feed = 0;                // the open rollout: 0 = no act yet, 1 = host-fed (ppo_host_act), 2 = device-fed (ppo_dev_act)
+    hipEvent_t dev_ev_in = nullptr, dev_ev_out = nullptr;   // the hand-over between the caller's stream and the context's (created by the first call that needs them)
+    int32_t* dev_count = nullptr;     // device [2] (+ padding)
+    int32_t* dev_count_h = nullptr;   // pinned [2]
+    int32_t* dev_index[2] = { nullptr, nullptr };
+    float* dev_value[2] = { nullptr, nullptr };
+    int64_t dev_cap = 0;
+    hipEvent_t dev_fold_ev[2] = { nullptr, nullptr };   // behind the last fold of the rollout that used the list and the copy of its counter
+    int dev_list = 0;                 // the list of the open (else: the last) device-fed rollout
+    bool dev_list_used = false;       // the open rollout has enqueued a fold (its counter was cleared in front of it)
+    int dev_last = -1;                // >= 0: the last closed rollout was device-fed and enqueued folds into this list
+    bool dev_last_fetched = false;    // ... and its events are in dev_last_idx / dev_last_val already (ppo_host_truncations, sorted by index)
+    std::vector<int32_t> dev_last_idx;
+    std::vector<float> dev_last_val;
     GenericCtx* gen = nullptr;       // non-null: synthetic env / network other than 2 x 64 (generic.hpp); every L-dependent entry point dispatches on it
     uint8_t* cur_mask = nullptr;     // generic path: action mask of the observation in NEXT_OBS, [N, A]
     bool force_collectives = false;  // PPO_COMM_SELFTEST: world == 1 but the multi-rank path (RCCL included) is taken
@@ -449,6 +467,10 @@ extern "C" void ppo_ctx_destroy(ppo_ctx* c) {
     if (c->trunc_h) (void)hipHostFree(c->trunc_h);
     if (c->trunc_dev) (void)hipFree(c->trunc_dev);
     if (c->trunc_ev) (void)hipEventDestroy(c->trunc_ev);
+    if (c->dev_ev_in) (void)hipEventDestroy(c->dev_ev_in);
+    if (c->dev_ev_out) (void)hipEventDestroy(c->dev_ev_out);
+    for (hipEvent_t e : c->dev_fold_ev) if (e) (void)hipEventDestroy(e);
+    if (c->dev_count_h) (void)hipHostFree(c->dev_count_h);
     if (c->wr_host) (void)hipHostFree(c->wr_host);
     if (c->snap) (void)hipHostFree(c->snap);
     for (hipEvent_t e : c->snap_ev) if (e) (void)hipEventDestroy(e);
@@ -1966,6 +1988,7 @@ static ppo_status host_begin(ppo_ctx* c) {
     c->host_staged = false;
     c->host_fin_given = false;
     c->host_n_groups = 0;
+    c->host_feed = 0;
     return PPO_OK;
 }
 extern "C" ppo_status ppo_host_rollout_begin(ppo_ctx* c) {
@@ -1985,6 +2008,8 @@ extern "C" ppo_status ppo_host_act(ppo_ctx* c, const uint8_t* mask_h, int64_t* a
     if (s != PPO_OK) return s;
     if (c->host_n_groups > 0) return fail(c, PPO_ERR_STATE, "ppo_host_act: the open rollout is taken by env groups (ppo_host_group_act)");
     if (c->host_phase == 0) return fail(c, PPO_ERR_STATE, "ppo_host_act: no rollout is open (ppo_host_rollout_begin)");
+    if (c->host_feed == 2)
+        return fail(c, PPO_ERR_STATE, "ppo_host_act: the open rollout is device-fed (ppo_dev_act / ppo_dev_observe); a rollout takes the ppo_host_* or the ppo_dev_* calls, not both");
     if (c->host_phase == 2) return fail(c, PPO_ERR_STATE, "ppo_host_act: step %d was acted on and not observed (ppo_host_observe)", c->host_t - 1);
     if (c->host_t >= c->T) return fail(c, PPO_ERR_STATE, "ppo_host_act: all %d steps of the rollout are taken (ppo_host_rollout_end)", c->T);
     NEED(c, action_h != nullptr, "null argument");
@@ -2015,6 +2040,7 @@ extern "C" ppo_status ppo_host_act(ppo_ctx* c, const uint8_t* mask_h, int64_t* a
     c->host_staged = false;
     c->host_t = t + 1;
     c->host_phase = 2;
+    c->host_feed = 1;
     return PPO_OK;
 }
 
@@ -2087,6 +2113,8 @@ static ppo_status host_observe_common(ppo_ctx* c, const char* what, const float*
     ppo_status s = host_state(c, what);
     if (s != PPO_OK) return s;
     if (c->host_n_groups > 0) return fail(c, PPO_ERR_STATE, "%s: the open rollout is taken by env groups (ppo_host_group_observe)", what);
+    if (c->host_feed == 2)
+        return fail(c, PPO_ERR_STATE, "%s: the open rollout is device-fed (ppo_dev_act / ppo_dev_observe); a rollout takes the ppo_host_* or the ppo_dev_* calls, not both", what);
     if (c->host_phase != 2) return fail(c, PPO_ERR_STATE, "%s: no step awaits its observation (ppo_host_act first)", what);
     NEED(c, next_obs_h && reward_h && done_h, "null argument");
     NEED(c, (fin_len_h == nullptr) == (fin_rew_h == nullptr), "fin_len_h and fin_rew_h: both or neither");
@@ -2312,6 +2340,34 @@ extern "C" ppo_status ppo_host_truncations(ppo_ctx* c, int64_t* count, int32_t* 
     const ppo_status s = host_state(c, "ppo_host_truncations");
     if (s != PPO_OK) return s;
     NEED(c, count != nullptr, "ppo_host_truncations: count is null");
+    if (c->dev_last >= 0) {   // the last closed rollout was device-fed: its list is on the device, in the order the workgroups got there
+        if (!c->dev_last_fetched) {
+            const int l = c->dev_last;
+            DeviceGuard dev_guard(c);
+            HIPCHK(c, hipEventSynchronize(c->dev_fold_ev[l]));   // that rollout's last fold and the copy of its counter: the update behind them keeps running
+            const int64_t n = std::min<int64_t>(std::max<int32_t>(c->dev_count_h[l], 0), c->dev_cap);
+            std::vector<int32_t> ix((size_t)n);
+            std::vector<float> va((size_t)n);
+            if (n > 0) {
+                HIPCHK(c, hipMemcpy(ix.data(), c->dev_index[l], (size_t)n * 4, hipMemcpyDeviceToHost));
+                HIPCHK(c, hipMemcpy(va.data(), c->dev_value[l], (size_t)n * 4, hipMemcpyDeviceToHost));
+            }
+            std::vector<int32_t> order((size_t)n);
+            for (int64_t k = 0; k < n; k++) order[(size_t)k] = (int32_t)k;
+            std::sort(order.begin(), order.end(), [&ix](int32_t a, int32_t b) { return ix[(size_t)a] < ix[(size_t)b]; });
+            c->dev_last_idx.resize((size_t)n);
+            c->dev_last_val.resize((size_t)n);
+            for (int64_t k = 0; k < n; k++) { c->dev_last_idx[(size_t)k] = ix[(size_t)order[(size_t)k]]; c->dev_last_val[(size_t)k] = va[(size_t)order[(size_t)k]]; }
+            c->dev_last_fetched = true;
+        }
+        const int64_t Kd = (int64_t)c->dev_last_idx.size();
+        if ((index_h || value_h) && cap < Kd)
+            return fail(c, PPO_ERR_INVALID, "ppo_host_truncations: room for %lld events, the last rollout had %lld", (long long)cap, (long long)Kd);
+        if (Kd > 0 && index_h) std::memcpy(index_h, c->dev_last_idx.data(), (size_t)Kd * 4);
+        if (Kd > 0 && value_h) std::memcpy(value_h, c->dev_last_val.data(), (size_t)Kd * 4);
+        *count = Kd;
+        return PPO_OK;
+    }
     const int64_t K = (int64_t)c->trunc_last_idx.size();
     if ((index_h || value_h) && cap < K)
         return fail(c, PPO_ERR_INVALID, "ppo_host_truncations: room for %lld events, the last rollout had %lld", (long long)cap, (long long)K);
@@ -2322,6 +2378,161 @@ extern "C" ppo_status ppo_host_truncations(ppo_ctx* c, int64_t* count, int32_t* 
         std::memcpy(value_h, trunc_val_h(c), (size_t)K * 4);
     }
     *count = K;
+    return PPO_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Caller-stepped environments on the device (ppo_dev_*): the same rollout fed from DEVICE arrays in stream order (the reference's loop, PPO_Discrete.cpp:365-483,
+// 524-548, with the envs on the chip).  Every call only enqueues: no host wait, no host copy of per-step data.  The hand-over between the caller's stream
+// and the context's (non-blocking) stream is a pair of events per call; caller_stream == the context's stream needs none.  ppo_dev_act is launch_host_act
+// with commit = 0 on the caller's action array; ppo_dev_observe is host_commit_kernel on the caller's arrays, at once, and -- with flags -- the fold kernel
+// that finds the flagged rows itself (launch_dev_fold*).  ppo_host_rollout_end then has nothing to commit and nothing to fold.
+// ---------------------------------------------------------------------------------------------------------
+static ppo_status dev_handover_in(ppo_ctx* c, hipStream_t caller) {
+    if (caller == c->stream) return PPO_OK;
+    if (!c->dev_ev_in) HIPCHK(c, hipEventCreateWithFlags(&c->dev_ev_in, hipEventDisableTiming));
+    if (!c->dev_ev_out) HIPCHK(c, hipEventCreateWithFlags(&c->dev_ev_out, hipEventDisableTiming));
+    HIPCHK(c, hipEventRecord(c->dev_ev_in, caller));
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->dev_ev_in, 0));
+    return PPO_OK;
+}
+static ppo_status dev_handover_out(ppo_ctx* c, hipStream_t caller) {
+    if (caller == c->stream) return PPO_OK;
+    HIPCHK(c, hipEventRecord(c->dev_ev_out, c->stream));
+    HIPCHK(c, hipStreamWaitEvent(caller, c->dev_ev_out, 0));
+    return PPO_OK;
+}
+// what every ppo_dev_* call of an open rollout checks first
+static ppo_status dev_state(ppo_ctx* c, const char* what) {
+    ppo_status s = host_state(c, what);
+    if (s != PPO_OK) return s;
+    if (c->host_n_groups > 0)
+        return fail(c, PPO_ERR_STATE, "%s: the open rollout is taken by env groups (ppo_host_group_*); groups hide a host wait that the ppo_dev_* calls do not have", what);
+    if (c->host_feed == 1)
+        return fail(c, PPO_ERR_STATE, "%s: the open rollout is host-fed (ppo_host_act / ppo_host_observe); a rollout takes the ppo_host_* or the ppo_dev_* calls, not both", what);
+    return PPO_OK;
+}
+// The two event lists of device-fed rollouts, T * N entries each, made by the first ppo_dev_observe that passes flags (the allocation policy of ppo_ctx_create
+// in ppo_hip.h).  The counters are cleared in stream order in front of a rollout's first fold, not here.
+static ppo_status dev_lists_reserve(ppo_ctx* c) {
+    if (c->dev_cap > 0) return PPO_OK;
+    const int64_t cap = (int64_t)c->T * c->N;
+    for (hipEvent_t& e : c->dev_fold_ev) if (!e) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    if (!c->dev_count_h) {
+        HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->dev_count_h), 4 * sizeof(int32_t), hipHostMallocDefault));
+        c->dev_count_h[0] = c->dev_count_h[1] = 0;
+    }
+    if (!c->dev_count) HIPCHK(c, dalloc(c, &c->dev_count, 4, false));
+    for (int l = 0; l < 2; l++) {
+        if (!c->dev_index[l]) HIPCHK(c, dalloc(c, &c->dev_index[l], (size_t)cap, false));
+        if (!c->dev_value[l]) HIPCHK(c, dalloc(c, &c->dev_value[l], (size_t)cap, false));
+    }
+    c->dev_cap = cap;
+    return PPO_OK;
+}
+
+// initEnvs (PPO_Discrete.cpp:365-402) from a device array: NEXT_OBS = obs, NEXT_DONE = 0, per-env episode sums = 0, in stream order
+extern "C" ppo_status ppo_dev_env_reset(ppo_ctx* c, const float* obs, void* caller_stream) {
+    NEED(c, c != nullptr, "null ctx");
+    ppo_status s = host_state(c, "ppo_dev_env_reset");
+    if (s != PPO_OK) return s;
+    if (c->host_phase != 0) return fail(c, PPO_ERR_STATE, "ppo_dev_env_reset: a rollout is open (ppo_host_rollout_end first)");
+    NEED(c, obs != nullptr, "ppo_dev_env_reset: null argument");
+    DeviceGuard dev_guard(c);
+    hipStream_t caller = static_cast<hipStream_t>(caller_stream);
+    s = dev_handover_in(c, caller);
+    if (s != PPO_OK) return s;
+    HIPCHK(c, hipMemsetAsync(c->buf[PPO_BUF_NEXT_DONE], 0, (size_t)c->N * sizeof(int32_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->buf[PPO_BUF_EP_LEN], 0, (size_t)c->N * sizeof(int32_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->buf[PPO_BUF_EP_REW], 0, (size_t)c->N * sizeof(float), c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->buf[PPO_BUF_NEXT_OBS], obs, (size_t)c->N * c->O * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    return dev_handover_out(c, caller);
+}
+
+// Step t of :524-548 on the committed state (NEXT_OBS / NEXT_DONE): m_obs[t], m_dones[t], the actor forward + sample, m_actions[t], m_logprobs[t] (and
+// masks [t]); the i64 actions go to the caller's device array with plain stores
+extern "C" ppo_status ppo_dev_act(ppo_ctx* c, const uint8_t* mask, int64_t* action, void* caller_stream) {
+    NEED(c, c != nullptr, "null ctx");
+    ppo_status s = dev_state(c, "ppo_dev_act");
+    if (s != PPO_OK) return s;
+    if (c->host_phase == 0) return fail(c, PPO_ERR_STATE, "ppo_dev_act: no rollout is open (ppo_host_rollout_begin)");
+    if (c->host_phase == 2) return fail(c, PPO_ERR_STATE, "ppo_dev_act: step %d was acted on and not observed (ppo_dev_observe)", c->host_t - 1);
+    if (c->host_t >= c->T) return fail(c, PPO_ERR_STATE, "ppo_dev_act: all %d steps of the rollout are taken (ppo_host_rollout_end)", c->T);
+    NEED(c, action != nullptr, "ppo_dev_act: null argument");
+    DeviceGuard dev_guard(c);
+    hipStream_t caller = static_cast<hipStream_t>(caller_stream);
+    const int t = c->host_t, N = c->N;
+    const uint8_t* m = c->cfg.dist_kind == PPO_DIST_MASKED ? mask : nullptr;
+    const HostStepArgs h = host_args_rows(c, t, true, 0, false, false);   // commit = 0: ppo_dev_observe committed step t - 1
+    const int64_t step = c->rollout_steps + t;
+    s = dev_handover_in(c, caller);
+    if (s != PPO_OK) return s;
+    if (c->gen) {   // gen_rollout's per-step sequence on the committed observation
+        GenericCtx& g = *c->gen;
+        s = gen_policy(c, B_<float>(c, PPO_BUF_NEXT_OBS), m, nullptr, N, step, action, g.step_lp, g.step_en);
+        if (s != PPO_OK) return s;
+        HIPCHK(c, gen_store_step(g.L, N, B_<float>(c, PPO_BUF_NEXT_OBS), m, action, g.step_lp, B_<int32_t>(c, PPO_BUF_NEXT_DONE), h.obs_t,
+                                 B_<uint8_t>(c, PPO_BUF_MASKS) + (size_t)t * N * c->A, h.actions_t, B_<float>(c, PPO_BUF_LOGPROBS) + (size_t)t * N, h.dones_t,
+                                 c->stream));
+    } else {
+        HIPCHK(c, launch_host_act(B_<float>(c, PPO_BUF_PARAMS), c->L, c->cfg.dist_kind, m, N, c->cfg.seed, c->cfg.env_offset, step, h, action,
+                                  B_<float>(c, PPO_BUF_LOGPROBS) + (size_t)t * N, c->host_as16, c->error_flag, c->stream));
+    }
+    s = dev_handover_out(c, caller);
+    if (s != PPO_OK) return s;
+    if (c->host_feed == 0) {   // the first act: this rollout is device-fed, and its events go to the other list
+        c->host_feed = 2;
+        c->dev_list ^= 1;
+        c->dev_list_used = false;
+    }
+    c->host_t = t + 1;
+    c->host_phase = 2;
+    return PPO_OK;
+}
+
+// stepEnvs' outputs for step t (:413-483) from device arrays, committed at once: one launch, and the fold launch behind it when flags are passed
+extern "C" ppo_status ppo_dev_observe(ppo_ctx* c, const float* next_obs, const float* reward, const int32_t* done, const int32_t* fin_len, const float* fin_rew,
+                                      const int32_t* truncated, const float* final_obs, void* caller_stream) {
+    NEED(c, c != nullptr, "null ctx");
+    ppo_status s = dev_state(c, "ppo_dev_observe");
+    if (s != PPO_OK) return s;
+    if (c->host_phase != 2) return fail(c, PPO_ERR_STATE, "ppo_dev_observe: no step awaits its observation (ppo_dev_act first)");
+    NEED(c, next_obs && reward && done, "ppo_dev_observe: null argument");
+    NEED(c, (fin_len == nullptr) == (fin_rew == nullptr), "ppo_dev_observe: fin_len and fin_rew: both or neither");
+    NEED(c, truncated == nullptr || final_obs != nullptr, "ppo_dev_observe: truncated is given and final_obs is null");
+    if (truncated && c->gen)
+        return fail(c, PPO_ERR_UNSUPPORTED, "ppo_dev_observe: truncation flags on a generic network (its critic launch is chosen by a row count the host does not "
+                                            "have here); fold with ppo_bootstrap_rewards where the count is known");
+    DeviceGuard dev_guard(c);
+    hipStream_t caller = static_cast<hipStream_t>(caller_stream);
+    const int t = c->host_t - 1, N = c->N;
+    if (truncated) {
+        s = dev_lists_reserve(c);
+        if (s != PPO_OK) return s;
+    }
+    HostStepArgs h = host_args_rows(c, t + 1, false, 0, true, fin_len != nullptr);
+    h.st_obs = next_obs; h.st_rew = reward; h.st_done = done; h.st_fin_len = fin_len; h.st_fin_rew = fin_rew;
+    s = dev_handover_in(c, caller);
+    if (s != PPO_OK) return s;
+    HIPCHK(c, launch_host_commit(h, N, c->O, c->stream));
+    if (truncated) {
+        const int l = c->dev_list;
+        if (!c->dev_list_used) {
+            HIPCHK(c, hipMemsetAsync(c->dev_count + l, 0, sizeof(int32_t), c->stream));
+            c->dev_list_used = true;
+        }
+        DevFoldArgs f{};
+        f.truncated = truncated; f.done = done; f.final_obs = final_obs;
+        f.N = N; f.tN = (int64_t)t * N; f.gamma = c->cfg.gamma;
+        f.rewards = B_<float>(c, PPO_BUF_REWARDS);
+        f.ev_count = c->dev_count + l; f.ev_index = c->dev_index[l]; f.ev_value = c->dev_value[l]; f.ev_cap = c->dev_cap;
+        // the critic bootstrap_launch would pick for this context
+        if (c->O == 4 || c->O == 2) HIPCHK(c, launch_dev_fold_mfma(B_<float>(c, PPO_BUF_PARAMS), c->L, f, c->stream));
+        else HIPCHK(c, launch_dev_fold(B_<float>(c, PPO_BUF_PARAMS), c->L, f, c->stream));
+    }
+    s = dev_handover_out(c, caller);
+    if (s != PPO_OK) return s;
+    c->host_phase = 1;
     return PPO_OK;
 }
 
@@ -2337,11 +2548,19 @@ extern "C" ppo_status ppo_host_rollout_end(ppo_ctx* c) {
         if (G.t != c->T || !G.staged)
             return fail(c, PPO_ERR_STATE, "ppo_host_rollout_end: group %d: %d of %d steps acted on, %d observed", g, G.t, c->T, G.staged ? G.t : (G.t > 0 ? G.t - 1 : 0));
     }
-    if (c->host_n_groups == 0 && (c->host_t != c->T || !c->host_staged))
-        return fail(c, PPO_ERR_STATE, "ppo_host_rollout_end: %d of %d steps acted on, %d observed", c->host_t, c->T, c->host_staged ? c->host_t : c->host_t - 1);
+    const bool dev_fed = c->host_feed == 2;   // every step was committed by its ppo_dev_observe; the events were folded there
+    const bool observed = dev_fed ? c->host_phase == 1 : c->host_staged;
+    if (c->host_n_groups == 0 && (c->host_t != c->T || !observed))
+        return fail(c, PPO_ERR_STATE, "ppo_host_rollout_end: %d of %d steps acted on, %d observed", c->host_t, c->T, observed ? c->host_t : (c->host_t > 0 ? c->host_t - 1 : 0));
     DeviceGuard dev_guard(c);
     const int N = c->N, T = c->T;
-    if (c->host_n_groups > 0) {   // every group's step T - 1 in one launch
+    if (dev_fed) {
+        if (c->dev_list_used) {   // in front of the value launch: ppo_host_truncations waits for the folds only
+            const int l = c->dev_list;
+            HIPCHK(c, hipMemcpyAsync(c->dev_count_h + l, c->dev_count + l, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipEventRecord(c->dev_fold_ev[l], c->stream));
+        }
+    } else if (c->host_n_groups > 0) {   // every group's step T - 1 in one launch
         HostGroupTable tab{};
         tab.n = c->host_n_groups;
         for (int g = 0; g < tab.n; g++) { tab.row0[g] = c->host_grp[g].row0; tab.fin_given[g] = c->host_grp[g].fin_given ? 1 : 0; }
@@ -2368,8 +2587,19 @@ extern "C" ppo_status ppo_host_rollout_end(ppo_ctx* c) {
     c->rollout_steps += T;
     c->global_step += (int64_t)T * c->cfg.global_num_envs;   // :526
     c->fin_pending = true;
-    s = host_fold_truncations(c);   // (FIN_REW, EP_REW and the episode statistics were committed above: they keep the raw rewards)
-    if (s != PPO_OK) return s;
+    c->host_feed = 0;
+    c->dev_last_idx.clear();
+    c->dev_last_val.clear();
+    c->dev_last_fetched = false;
+    if (dev_fed) {
+        c->dev_last = c->dev_list_used ? c->dev_list : -1;
+        c->dev_list_used = false;
+        c->trunc_last_idx.clear();   // (no host-side event can be pending: trunc_n == 0)
+    } else {
+        c->dev_last = -1;
+        s = host_fold_truncations(c);   // (FIN_REW, EP_REW and the episode statistics were committed above: they keep the raw rewards)
+        if (s != PPO_OK) return s;
+    }
     s = run_scan(c);
     if (s != PPO_OK) return s;
     return ppo_update(c);

@@ -1015,6 +1015,16 @@ __global__ __launch_bounds__(64) void values_kernel(const float* __restrict__ pa
     }
 }
 
+// values_kernel's arithmetic for one row (src: its OBS observation elements; lds: 64 floats of this wave): what the two fold kernels below share
+template <int OBS>
+__device__ __forceinline__ float critic_row_value(const LaneNet<OBS>& critic, const float* __restrict__ params, const NetLayout& L, const float* src, float* lds,
+                                                  int lane) {
+    float x[OBS];
+#pragma unroll
+    for (int k = 0; k < OBS; k++) x[k] = src[k];
+    return critic_head(params, L, trunk_forward<OBS>(critic, x, lds, lane), lane);
+}
+
 // values_kernel over the dense [K, OBS] block of final observations of truncated episodes, with the partial-episode bootstrap as its epilogue
 // (ppo_bootstrap_rewards): rewards[index[k]] += gamma * v in two roundings, value_out[k] = v (may be null).  The same per-row arithmetic, so v is what
 // values_kernel gives the same observation; indices are distinct (the caller's promise), so the read-modify-write is plain.
@@ -1027,16 +1037,36 @@ __global__ __launch_bounds__(64) void bootstrap_values_kernel(const float* __res
     LaneNet<OBS> critic;
     load_lane_net<OBS>(critic, params, L, 0, lane);
     for (int64_t row = blockIdx.x; row < K; row += gridDim.x) {
-        const float* src = final_obs + row * OBS;
-        float x[OBS];
-#pragma unroll
-        for (int k = 0; k < OBS; k++) x[k] = src[k];
-        const float v = critic_head(params, L, trunk_forward<OBS>(critic, x, lds, lane), lane);
+        const float v = critic_row_value<OBS>(critic, params, L, final_obs + row * OBS, lds, lane);
         if (lane == 0) {
             const int32_t i = index[row];
             rewards[i] = __fadd_rn(rewards[i], __fmul_rn(gamma, v));
             if (value_out) value_out[row] = v;
         }
+    }
+}
+
+// The fold of a device-fed step (ppo_dev_observe with truncation flags; ppo_internal.hpp: DevFoldArgs) with bootstrap_values_kernel's critic: the flagged
+// rows of this workgroup's 256 env rows, compacted, one row per wave and round.  trunk_forward holds workgroup barriers (real ones here: four waves), so
+// every wave takes every round, each on its own 64 floats of LDS; a wave without a row of its own in the last round repeats the first flagged row and
+// stores nothing.  A workgroup without a flagged row returns before it loads a weight.
+template <int OBS>
+__global__ __launch_bounds__(DEV_FOLD_THREADS) void dev_fold_kernel(const float* __restrict__ params, NetLayout L, DevFoldArgs a) {
+    __shared__ __attribute__((aligned(16))) float lds[(DEV_FOLD_THREADS / 64) * PPO_HIDDEN];
+    __shared__ int list[DEV_FOLD_THREADS], wtot[8];
+    const int cnt = dev_fold_compact(a, list, wtot);
+    if (cnt == 0) return;
+    const int base = wtot[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    LaneNet<OBS> critic;
+    load_lane_net<OBS>(critic, params, L, 0, lane);
+    constexpr int W = DEV_FOLD_THREADS / 64;
+    for (int r = 0; r < (cnt + W - 1) / W; r++) {
+        const int k = r * W + wave;
+        const bool valid = k < cnt;
+        const int n = list[valid ? k : 0];
+        const float v = critic_row_value<OBS>(critic, params, L, a.final_obs + (int64_t)n * OBS, lds + wave * PPO_HIDDEN, lane);
+        if (valid && lane == 0) dev_fold_store(a, base, k, n, v);
     }
 }
 
@@ -1626,6 +1656,14 @@ hipError_t launch_evaluate(const EvalArgs& a, hipStream_t s) {
 #undef PPO_EVAL
 #undef PPO_EVALV
 #undef PPO_EVAL16
+    return hipGetLastError();
+}
+
+hipError_t launch_dev_fold(const float* params, const NetLayout& L, const DevFoldArgs& a, hipStream_t s) {
+    if (a.N <= 0) return hipSuccess;
+    if (L.obs != 8) return hipErrorNotSupported;   // obs 2 and 4 take the matrix-core critic (launch_dev_fold_mfma), as ppo_bootstrap_rewards does
+    const unsigned grid = (unsigned)(((int64_t)a.N + DEV_FOLD_THREADS - 1) / DEV_FOLD_THREADS);
+    hipLaunchKernelGGL((dev_fold_kernel<8>), dim3(grid), dim3(DEV_FOLD_THREADS), 0, s, params, L, a);
     return hipGetLastError();
 }
 

@@ -1983,19 +1983,27 @@ __global__ __launch_bounds__(256, 2) void values_mfma_kernel(const float* __rest
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Partial-episode bootstrap at time-limit truncations (ppo_bootstrap_rewards; ppo_host_rollout_end with truncation events): for k < K
-//   v = Critic(final_obs[k]);  rewards[index[k]] += gamma * v;  value_out[k] = v (may be null)
-// A copy of values_mfma_kernel's tile body -- the same products in the same order, so v is, bit for bit, the value the rollout's critic launch gives
-// the same observation -- over the dense [K, OBS] block of final observations, with the scattered fold as its epilogue.  (A body shared through a
-// __device__ function changed values_mfma_kernel's instruction schedule; the copy leaves that kernel as it was.)
+// Partial-episode bootstrap at time-limit truncations (ppo_bootstrap_rewards; ppo_host_rollout_end with truncation events; ppo_dev_observe with flags):
+//   v = Critic(final observation);  rewards[index] += gamma * v;  the value kept for the caller
+// The critic is a copy of values_mfma_kernel's tile body -- the same products in the same order, so v is, bit for bit, the value the rollout's critic
+// launch gives the same observation.  (A body shared WITH values_mfma_kernel through a __device__ function changed that kernel's instruction schedule;
+// the copy leaves it as it was.)  The copy itself exists once: critic_tile_stage / critic_tile_value below are the prologue and the tile body of both
+// fold kernels, bootstrap_values_mfma_kernel (a dense [K, OBS] block and an index list, K known to the host) and dev_fold_mfma_kernel (flags per env row,
+// the count known to nobody: ppo_internal.hpp, DevFoldArgs).
 // ---------------------------------------------------------------------------------------------------------
 template <int OBS>
-__global__ __launch_bounds__(256, 2) void bootstrap_values_mfma_kernel(const float* __restrict__ P, NetLayout L, const float* __restrict__ final_obs,
-                                                                       const int32_t* __restrict__ index, int64_t K, float gamma,
-                                                                       float* __restrict__ rewards, float* __restrict__ value_out) {
-    __shared__ __attribute__((aligned(16))) uint16_t sW2p[2 * 64 * WS];
-    __shared__ __attribute__((aligned(16))) float sB1[64], sB2[64], sW3[64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+struct CriticTile {
+    static constexpr int L1S = (OBS + 1) / 2;
+    float w1op[2][L1S];   // this lane's layer-1 A operands
+    float b3;
+};
+
+// The critic's weights where a tile wants them: W2 as split fp16 pairs in sW2p [2 * 64 * WS], the scaled biases and W3 in sB1 / sB2 / sW3 [64] (LDS of the
+// workgroup, 256 threads), layer 1 in registers.  Ends with the workgroup's barrier.
+template <int OBS>
+__device__ __forceinline__ void critic_tile_stage(const float* __restrict__ P, const NetLayout& L, uint16_t* sW2p, float* sB1, float* sB2, float* sW3,
+                                                  CriticTile<OBS>& ct) {
+    const int tid = threadIdx.x, lane = tid & 63;
     const int s = lane & 31, hi = lane >> 5;
     {
         float wv[16];
@@ -2013,17 +2021,89 @@ __global__ __launch_bounds__(256, 2) void bootstrap_values_mfma_kernel(const flo
         }
     }
     if (tid < 64) { sB1[tid] = P[L.b1[0] + tid] * TANH_C; sB2[tid] = P[L.b2[0] + tid] * TANH_C; sW3[tid] = P[L.w3[0] + tid]; }
-    const float b3 = P[L.b3[0]];
-    constexpr int L1S = (OBS + 1) / 2;
-    float w1op[2][L1S];
+    ct.b3 = P[L.b3[0]];
 #pragma unroll
     for (int t = 0; t < 2; t++)
 #pragma unroll
-        for (int stp = 0; stp < L1S; stp++) {
+        for (int stp = 0; stp < CriticTile<OBS>::L1S; stp++) {
             const int o = 2 * stp + hi;
-            w1op[t][stp] = o < OBS ? P[L.w1[0] + (s + 32 * t) * OBS + o] * TANH_C : 0.0f;
+            ct.w1op[t][stp] = o < OBS ? P[L.w1[0] + (s + 32 * t) * OBS + o] * TANH_C : 0.0f;
         }
     __syncthreads();
+}
+
+// One 32-row tile of one wave: xb = this lane's layer-1 B operands (row lane & 31 of the tile, observation elements 2 stp + (lane >> 5); zero where the row
+// or the element does not exist).  Returns the row's value in both of its lanes.  No barrier inside: the waves of a workgroup take tiles independently.
+template <int OBS>
+__device__ __forceinline__ float critic_tile_value(const CriticTile<OBS>& ct, const float* xb, const uint16_t* sW2p, const float* sB1, const float* sB2,
+                                                   const float* sW3) {
+    const int lane = threadIdx.x & 63;
+    const int s = lane & 31, hi = lane >> 5;
+    float h1[32];
+#pragma unroll
+    for (int t = 0; t < 2; t++) {
+        f32x16 acc;
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const float4 b = ld4(&sB1[8 * q + 4 * hi + 32 * t]);
+            acc[4 * q] = b.x; acc[4 * q + 1] = b.y; acc[4 * q + 2] = b.z; acc[4 * q + 3] = b.w;
+        }
+#pragma unroll
+        for (int stp = 0; stp < CriticTile<OBS>::L1S; stp++) {
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ct.w1op[t][stp], xb[stp], acc, 0, 0, 0);
+        }
+#pragma unroll
+        for (int r = 0; r < 16; r++) h1[16 * t + r] = tanh_scaled(acc[r]);
+    }
+    uint32_t hp[2][16];
+#pragma unroll
+    for (int j = 0; j < 16; j++) split2(h1[2 * j], h1[2 * j + 1], hp[0][j], hp[1][j]);
+    auto aptr = [&](int g, int term) {
+        return reinterpret_cast<const u32x4*>(sW2p + term * 64 * WS + (s + 32 * (g >> 2)) * WS + (g & 3) * 16 + hi * 8);
+    };
+    float part = 0.0f;
+    f32x16 acc;
+    u32x4 an1 = *aptr(0, 0), an2 = *aptr(0, 1);
+#pragma unroll
+    for (int g = 0; g < 8; g++) {
+        const int t = g >> 2, c = g & 3;
+        if (c == 0) {
+#pragma unroll
+            for (int qq = 0; qq < 4; qq++) {
+                const float4 b = ld4(&sB2[8 * qq + 4 * hi + 32 * t]);
+                acc[4 * qq] = b.x; acc[4 * qq + 1] = b.y; acc[4 * qq + 2] = b.z; acc[4 * qq + 3] = b.w;
+            }
+        }
+        const u32x4 a1 = an1, a2 = an2;
+        if (g + 1 < 8) { an1 = *aptr(g + 1, 0); an2 = *aptr(g + 1, 1); }
+        MF_PIN();
+        const u32x4 b1 = { hp[0][4 * c], hp[0][4 * c + 1], hp[0][4 * c + 2], hp[0][4 * c + 3] };
+        const u32x4 b2 = { hp[1][4 * c], hp[1][4 * c + 1], hp[1][4 * c + 2], hp[1][4 * c + 3] };
+        acc = mfma_x2(a1, a2, b1, b2, acc);
+        if (c == 3) {
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const float4 w = ld4(&sW3[8 * q + 4 * hi + 32 * t]);
+                part = __builtin_fmaf(tanh_scaled(acc[4 * q]), w.x, part); part = __builtin_fmaf(tanh_scaled(acc[4 * q + 1]), w.y, part);
+                part = __builtin_fmaf(tanh_scaled(acc[4 * q + 2]), w.z, part); part = __builtin_fmaf(tanh_scaled(acc[4 * q + 3]), w.w, part);
+            }
+        }
+    }
+    const float other = __shfl_xor(part, 32, 64);
+    return (part + other) + ct.b3;
+}
+
+template <int OBS>
+__global__ __launch_bounds__(256, 2) void bootstrap_values_mfma_kernel(const float* __restrict__ P, NetLayout L, const float* __restrict__ final_obs,
+                                                                       const int32_t* __restrict__ index, int64_t K, float gamma,
+                                                                       float* __restrict__ rewards, float* __restrict__ value_out) {
+    __shared__ __attribute__((aligned(16))) uint16_t sW2p[2 * 64 * WS];
+    __shared__ __attribute__((aligned(16))) float sB1[64], sB2[64], sW3[64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int s = lane & 31, hi = lane >> 5;
+    constexpr int L1S = CriticTile<OBS>::L1S;
+    CriticTile<OBS> ct;
+    critic_tile_stage<OBS>(P, L, sW2p, sB1, sB2, sW3, ct);
     const int64_t n_tiles = (K + MT - 1) / MT;
     // rows one tile ahead, as values_mfma_kernel: a row >= K reads row 0, is zeroed at use and stores nothing
     auto load_x = [&](int64_t tl, float* xo) {
@@ -2042,63 +2122,44 @@ __global__ __launch_bounds__(256, 2) void bootstrap_values_mfma_kernel(const flo
 #pragma unroll
         for (int stp = 0; stp < L1S; stp++) xb[stp] = (valid && (2 * stp + 1 < OBS || hi == 0)) ? x_n[stp] : 0.0f;
         load_x(tile + tile_step, x_n);
-        float h1[32];
-#pragma unroll
-        for (int t = 0; t < 2; t++) {
-            f32x16 acc;
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const float4 b = ld4(&sB1[8 * q + 4 * hi + 32 * t]);
-                acc[4 * q] = b.x; acc[4 * q + 1] = b.y; acc[4 * q + 2] = b.z; acc[4 * q + 3] = b.w;
-            }
-#pragma unroll
-            for (int stp = 0; stp < L1S; stp++) {
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w1op[t][stp], xb[stp], acc, 0, 0, 0);
-            }
-#pragma unroll
-            for (int r = 0; r < 16; r++) h1[16 * t + r] = tanh_scaled(acc[r]);
-        }
-        uint32_t hp[2][16];
-#pragma unroll
-        for (int j = 0; j < 16; j++) split2(h1[2 * j], h1[2 * j + 1], hp[0][j], hp[1][j]);
-        auto aptr = [&](int g, int term) {
-            return reinterpret_cast<const u32x4*>(sW2p + term * 64 * WS + (s + 32 * (g >> 2)) * WS + (g & 3) * 16 + hi * 8);
-        };
-        float part = 0.0f;
-        f32x16 acc;
-        u32x4 an1 = *aptr(0, 0), an2 = *aptr(0, 1);
-#pragma unroll
-        for (int g = 0; g < 8; g++) {
-            const int t = g >> 2, c = g & 3;
-            if (c == 0) {
-#pragma unroll
-                for (int qq = 0; qq < 4; qq++) {
-                    const float4 b = ld4(&sB2[8 * qq + 4 * hi + 32 * t]);
-                    acc[4 * qq] = b.x; acc[4 * qq + 1] = b.y; acc[4 * qq + 2] = b.z; acc[4 * qq + 3] = b.w;
-                }
-            }
-            const u32x4 a1 = an1, a2 = an2;
-            if (g + 1 < 8) { an1 = *aptr(g + 1, 0); an2 = *aptr(g + 1, 1); }
-            MF_PIN();
-            const u32x4 b1 = { hp[0][4 * c], hp[0][4 * c + 1], hp[0][4 * c + 2], hp[0][4 * c + 3] };
-            const u32x4 b2 = { hp[1][4 * c], hp[1][4 * c + 1], hp[1][4 * c + 2], hp[1][4 * c + 3] };
-            acc = mfma_x2(a1, a2, b1, b2, acc);
-            if (c == 3) {
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const float4 w = ld4(&sW3[8 * q + 4 * hi + 32 * t]);
-                    part = __builtin_fmaf(tanh_scaled(acc[4 * q]), w.x, part); part = __builtin_fmaf(tanh_scaled(acc[4 * q + 1]), w.y, part);
-                    part = __builtin_fmaf(tanh_scaled(acc[4 * q + 2]), w.z, part); part = __builtin_fmaf(tanh_scaled(acc[4 * q + 3]), w.w, part);
-                }
-            }
-        }
-        const float other = __shfl_xor(part, 32, 64);
-        const float v = (part + other) + b3;
+        const float v = critic_tile_value<OBS>(ct, xb, sW2p, sB1, sB2, sW3);
         if (valid && hi == 0) {   // distinct indices: a plain read-modify-write, the product and the sum rounded separately
             const int32_t i = index[row];
             rewards[i] = __fadd_rn(rewards[i], __fmul_rn(gamma, v));
             if (value_out) value_out[row] = v;
         }
+    }
+}
+
+// The fold of a device-fed step (ppo_dev_observe with truncation flags; ppo_internal.hpp: DevFoldArgs): the flagged rows of THIS workgroup's 256 env rows,
+// compacted, in 32-row tiles over its four waves.  A workgroup without a flagged row returns before it touches a weight.  Plain stores and one atomicAdd.
+template <int OBS>
+__global__ __launch_bounds__(DEV_FOLD_THREADS, 2) void dev_fold_mfma_kernel(const float* __restrict__ P, NetLayout L, DevFoldArgs a) {
+    __shared__ __attribute__((aligned(16))) uint16_t sW2p[2 * 64 * WS];
+    __shared__ __attribute__((aligned(16))) float sB1[64], sB2[64], sW3[64];
+    __shared__ int list[DEV_FOLD_THREADS], wtot[8];
+    const int cnt = dev_fold_compact(a, list, wtot);
+    if (cnt == 0) return;
+    const int base = wtot[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int s = lane & 31, hi = lane >> 5;
+    constexpr int L1S = CriticTile<OBS>::L1S;
+    CriticTile<OBS> ct;
+    critic_tile_stage<OBS>(P, L, sW2p, sB1, sB2, sW3, ct);
+    const int n_tiles = (cnt + MT - 1) / MT;
+    for (int tile = wave; tile < n_tiles; tile += DEV_FOLD_THREADS / 64) {
+        const int k = tile * MT + s;
+        const bool valid = k < cnt;
+        const int n = list[valid ? k : 0];   // a row past the list reads the first flagged row, is zeroed at use and stores nothing
+        const float* src = a.final_obs + (int64_t)n * OBS;
+        float xb[L1S];
+#pragma unroll
+        for (int stp = 0; stp < L1S; stp++) {
+            const float x = src[(2 * stp + 1 < OBS) ? 2 * stp + hi : 2 * stp];
+            xb[stp] = (valid && (2 * stp + 1 < OBS || hi == 0)) ? x : 0.0f;
+        }
+        const float v = critic_tile_value<OBS>(ct, xb, sW2p, sB1, sB2, sW3);
+        if (valid && hi == 0) dev_fold_store(a, base, k, n, v);
     }
 }
 
@@ -2222,6 +2283,15 @@ hipError_t launch_bootstrap_values_mfma(const float* params, const NetLayout& L,
     const unsigned grid = (unsigned)(wg_needed < 1024 ? wg_needed : 1024);
     if (L.obs == 4) hipLaunchKernelGGL((bootstrap_values_mfma_kernel<4>), dim3(grid), dim3(256), 0, s, params, L, final_obs, index, K, gamma, rewards, value_out);
     else if (L.obs == 2) hipLaunchKernelGGL((bootstrap_values_mfma_kernel<2>), dim3(grid), dim3(256), 0, s, params, L, final_obs, index, K, gamma, rewards, value_out);
+    else return hipErrorNotSupported;
+    return hipGetLastError();
+}
+
+hipError_t launch_dev_fold_mfma(const float* params, const NetLayout& L, const DevFoldArgs& a, hipStream_t s) {
+    if (a.N <= 0) return hipSuccess;
+    const unsigned grid = (unsigned)(((int64_t)a.N + DEV_FOLD_THREADS - 1) / DEV_FOLD_THREADS);
+    if (L.obs == 4) hipLaunchKernelGGL((dev_fold_mfma_kernel<4>), dim3(grid), dim3(DEV_FOLD_THREADS), 0, s, params, L, a);
+    else if (L.obs == 2) hipLaunchKernelGGL((dev_fold_mfma_kernel<2>), dim3(grid), dim3(DEV_FOLD_THREADS), 0, s, params, L, a);
     else return hipErrorNotSupported;
     return hipGetLastError();
 }

@@ -726,6 +726,58 @@ hipError_t launch_bootstrap_values_mfma(const float* params, const NetLayout& L,
                                         float* rewards, float* value_out, hipStream_t s);
 hipError_t launch_bootstrap_values(const float* params, const NetLayout& L, const float* final_obs, const int32_t* index, int64_t K, float gamma,
                                    float* rewards, float* value_out, hipStream_t s);
+// The same fold for caller-stepped envs that live on the device (ppo_dev_observe with truncation flags): nobody on the host knows how many rows of the
+// step are flagged, so ONE launch over all N rows finds them.  A 256-thread workgroup owns env rows [256 b, 256 b + 256): every thread reads truncated[n]
+// and done[n] of its row; a row counts when BOTH are non-zero (a flag on a row that is not done is ignored: the device call cannot refuse it without a
+// host wait).  A workgroup without a flagged row ends there -- the common step: one pass over 2 N int32.  Otherwise the flagged rows are compacted inside
+// the workgroup (wave ballot + mbcnt rank, the four waves' totals through LDS, the row list in LDS, ascending), the critic runs on those rows of
+// final_obs only (other rows are never read: they may hold anything), and for each of them, i = t * N + n:
+//   rewards[i] = f32(rewards[i] + f32(gamma * v));   (ev_index, ev_value)[base + k] = (i, v)
+// base = ONE atomicAdd on *ev_count per workgroup that has events, k = the row's rank in the workgroup: the list's order across workgroups is arbitrary
+// (ppo_host_truncations sorts it on the host; no result depends on it).  Entries at or beyond ev_cap are not stored (T * N holds a whole rollout).
+struct DevFoldArgs {
+    const int32_t* truncated;   // [N]     the caller's arrays of this step
+    const int32_t* done;        // [N]
+    const float* final_obs;     // [N,O]
+    int N;
+    int64_t tN;                 // t * N
+    float gamma;
+    float* rewards;             // PPO_BUF_REWARDS [T,N], step t committed by the launch in front
+    int32_t* ev_count;          // the open rollout's event list
+    int32_t* ev_index;
+    float* ev_value;
+    int64_t ev_cap;
+};
+constexpr int DEV_FOLD_THREADS = 256;
+// The front end both fold kernels share.  list: LDS int [256]; wtot: LDS int [8] ([0..3] the waves' counts, [4] the workgroup's base in the event list).
+// Returns the workgroup's number of flagged rows (the same in every thread; 0: nothing else was written).
+__device__ __forceinline__ int dev_fold_compact(const DevFoldArgs& a, int* list, int* wtot) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t n = (int64_t)blockIdx.x * DEV_FOLD_THREADS + tid;
+    const bool flag = n < a.N && a.truncated[n] != 0 && a.done[n] != 0;
+    const unsigned long long b = __ballot(flag);
+    if (lane == 0) wtot[wave] = __popcll(b);
+    __syncthreads();
+    const int c0 = wtot[0], c1 = wtot[1], c2 = wtot[2], c3 = wtot[3];
+    const int total = c0 + c1 + c2 + c3;
+    if (total == 0) return 0;
+    const int before = (wave > 0 ? c0 : 0) + (wave > 1 ? c1 : 0) + (wave > 2 ? c2 : 0);
+    const int rank = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
+    if (flag) list[before + rank] = (int)n;
+    if (tid == 0) wtot[4] = atomicAdd(a.ev_count, total);
+    __syncthreads();
+    return total;
+}
+// the fold and the event record of compacted row k (env row n, value v): one lane per row
+__device__ __forceinline__ void dev_fold_store(const DevFoldArgs& a, int base, int k, int n, float v) {
+    const int64_t i = a.tN + n;
+    a.rewards[i] = __fadd_rn(a.rewards[i], __fmul_rn(a.gamma, v));
+    const int64_t e = (int64_t)base + k;
+    if (e < a.ev_cap) { a.ev_index[e] = (int32_t)i; a.ev_value[e] = v; }
+}
+// the critic arithmetic of launch_bootstrap_values_mfma (obs in {2, 4}) / of launch_bootstrap_values (obs 8: the one shape ppo_bootstrap_rewards sends there)
+hipError_t launch_dev_fold_mfma(const float* params, const NetLayout& L, const DevFoldArgs& a, hipStream_t s);
+hipError_t launch_dev_fold(const float* params, const NetLayout& L, const DevFoldArgs& a, hipStream_t s);
 // batched critic on the matrix cores (obs in {2, 4}); same contract as launch_values
 hipError_t launch_values_mfma(const float* params, const NetLayout& L, const float* obs0, int64_t n0, float* out0, const float* obs1, int64_t n1,
                               float* out1, hipStream_t s);
