@@ -173,7 +173,9 @@ PPO_API int32_t ppo_abi_version(void);
  * policy, the truncation-event list of caller-stepped rollouts (one pinned host block and its device twin), allocated by the first
  * ppo_host_observe_truncated / ppo_host_group_observe_truncated call that carries an event and grown by doubling up to num_steps * num_envs entries;
  * and the ppo_dev_* calls' two hand-over events (created by the first call on a stream other than the context's) and two device event lists
- * (num_steps * num_envs entries each, a counter, a pinned word and an event per list), made once by the first ppo_dev_observe that passes `truncated`. */
+ * (num_steps * num_envs entries each, a counter, a pinned word and an event per list), made once by the first ppo_dev_observe that passes `truncated`;
+ * and the observation normaliser's statistics (2 * obs_size f64) and its two [num_envs, obs_size] f32 scratches, made once by the first
+ * ppo_obs_norm_enable with mode != 0 (or the first ppo_obs_norm_set_h / ppo_obs_norm_apply) and kept. */
 PPO_API ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out);
 PPO_API void ppo_ctx_destroy(ppo_ctx* ctx);
 /* Error text of the last failing call on ctx (ctx == NULL: of the last failing ppo_ctx_create in this thread).
@@ -500,6 +502,46 @@ PPO_API ppo_status ppo_dev_act(ppo_ctx* ctx, const uint8_t* mask /* [N,A] or NUL
 PPO_API ppo_status ppo_dev_observe(ppo_ctx* ctx, const float* next_obs /* [N,O] */, const float* reward /* [N] */, const int32_t* done /* [N] */,
                                    const int32_t* fin_len /* [N] or NULL */, const float* fin_rew /* [N] or NULL */,
                                    const int32_t* truncated /* [N] or NULL */, const float* final_obs /* [N,O] or NULL */, void* caller_stream);
+
+/* Observation normalisation of caller-stepped environments (new): running mean / variance statistics, the first thing a PPO user adds to a custom env
+ * (gym's NormalizeObservation, SB3's VecNormalize).  The reference has none and never needed one: its envs (CartPole, MountainCar) are of unit scale.
+ * A caller's env is not: positions in metres, velocities in hundreds, counters in thousands -- a poor diet for orthogonal weights and tanh layers, and in
+ * this build an observation beyond 65 504 in PPO_BUF_OBS raises the sticky error word (kernel_flags, "fp16 ranges").  A normalised observation, clipped
+ * to +-clip, can never do that.
+ *
+ * Off unless ppo_obs_norm_enable turns it on: a context that never makes that call runs, launch for launch and bit for bit, what it ran before.
+ * Per context, in f64 on the device: mean[O], var[O] (population variance) and a row count; initially mean = 0, var = 1, count = 0.  Every batch of N
+ * new observations -- the reset observations (ppo_host_env_reset / ppo_dev_env_reset), then each step's next_obs -- is handled the same way:
+ *   update (mode 1 only): batch mean bm[o] and batch M2 = sum (x - bm)^2 over the N rows, in f64; then Chan's merge
+ *       tot = count + N;  delta = bm - mean;  mean += delta * N / tot;  M2 = var * count + bM2 + delta^2 * count * N / tot;  var = M2 / tot;  count = tot
+ *   apply: y = f32(clamp((f64(x) - mean) / sqrt(var + eps), -clip, +clip)) with the statistics as just updated.
+ * Everything downstream sees y only: PPO_BUF_NEXT_OBS, PPO_BUF_OBS[t], the actor, the value launch of ppo_host_rollout_end, the update; none of those
+ * kernels changes.  The raw observation is not kept.  Sums are formed in a fixed order without atomics: the same feed gives the same bits.
+ * Launches: ONE more per env step (update and apply are one kernel, obsnorm_update_apply_kernel), two with truncation flags.  ppo_dev_observe runs it in
+ * front of its commit, on the caller's next_obs into a scratch of the context's (it still only enqueues); a host-fed rollout runs it in ppo_host_act in
+ * front of the commit of the staged step (reading the pinned staging), and in ppo_host_rollout_end for the last step.  A host-fed and a device-fed
+ * rollout of the same data therefore merge the same batches in the same order and agree bit for bit, statistics included.
+ * Truncation bootstrap: a final observation is normalised WITHOUT updating the statistics, by the statistics as they stand when its fold runs.  The two
+ * feeds differ here: ppo_dev_observe folds per step, so a device-fed rollout uses the statistics right behind the same step's update; the host path folds
+ * once per rollout, so a host-fed rollout uses the statistics at ppo_host_rollout_end (all T steps merged).  ppo_bootstrap_rewards on caller buffers
+ * stays raw: the caller normalises with ppo_obs_norm_apply first.
+ * Errors (a failing call changes nothing): PPO_ERR_UNSUPPORTED for any of the four calls on a context that is not PPO_ENV_HOST (device envs are of unit
+ * scale and their fused rollout never leaves the chip), for ppo_obs_norm_enable(mode != 0) on a sharded context (global_num_envs > num_envs or a
+ * communicator initialised: per-rank statistics would make the replicas disagree; reducing them across ranks is later work), for ppo_comm_init /
+ * ppo_comm_init_local / ppo_comm_init_exchange on a context with normalisation on, and for ppo_host_rollout_begin_groups with normalisation on (groups
+ * commit in an order the caller chooses, the statistics would depend on it, and that breaks the groups' promise of interleaving-independent bits).
+ * PPO_ERR_STATE for enable / get / set while a rollout is open.  PPO_ERR_INVALID for a mode outside 0 .. 2, clip <= 0, eps <= 0, O != obs_size, a
+ * negative count or variance, null pointers. */
+/* mode 0 off, 1 update + apply, 2 apply only (frozen statistics: evaluation, fine-tuning).  Defaults of the bindings: clip = 10, eps = 1e-8.  The
+ * statistics are kept across mode changes. */
+PPO_API ppo_status ppo_obs_norm_enable(ppo_ctx* ctx, int32_t mode, float clip, float eps);
+/* The statistics, host arrays f64 [O] (O = obs_size) and the row count.  Synchronous.  Before anything was enabled or set: mean 0, var 1, count 0. */
+PPO_API ppo_status ppo_obs_norm_get_h(ppo_ctx* ctx, double* mean_h, double* var_h, int64_t O, double* count);
+/* Replaces the statistics (a checkpoint's, another context's).  Synchronous.  get then set on a second context, then the same feed: the same bits. */
+PPO_API ppo_status ppo_obs_norm_set_h(ppo_ctx* ctx, const double* mean_h, const double* var_h, int64_t O, double count);
+/* out[n,O] = the apply step on obs[n,O] with the current statistics, clip and eps; no update, whatever the mode.  DEVICE pointers; out may alias obs.
+ * Valid inside an open rollout too.  stream: as caller_stream of the ppo_dev_* calls (hand-over by events unless it is ppo_stream(ctx)). */
+PPO_API ppo_status ppo_obs_norm_apply(ppo_ctx* ctx, const float* obs, int64_t n, float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Evaluation (new; the reference reports only the mean over the last 100 exploration episodes of its training envs, PPO_Discrete.cpp:474-480, Utils.h:72-78)

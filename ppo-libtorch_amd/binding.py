@@ -53,6 +53,7 @@ ABI_SYMBOLS = [
     "ppo_policy_act_greedy", "ppo_evaluate",
     "ppo_host_observe_truncated", "ppo_host_group_observe_truncated", "ppo_host_truncations", "ppo_bootstrap_rewards",
     "ppo_dev_env_reset", "ppo_dev_act", "ppo_dev_observe",
+    "ppo_obs_norm_enable", "ppo_obs_norm_get_h", "ppo_obs_norm_set_h", "ppo_obs_norm_apply",
 ]
 
 
@@ -148,6 +149,10 @@ def lib():
         L.ppo_dev_env_reset.argtypes = [C.c_void_p] * 3
         L.ppo_dev_act.argtypes = [C.c_void_p] * 4
         L.ppo_dev_observe.argtypes = [C.c_void_p] * 9
+        L.ppo_obs_norm_enable.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_float]
+        L.ppo_obs_norm_get_h.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_double)]
+        L.ppo_obs_norm_set_h.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double]
+        L.ppo_obs_norm_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         for name in ABI_SYMBOLS:
             getattr(L, name)  # AttributeError if the build lacks a declared symbol
         if L.ppo_abi_version() != ABI_VERSION:
@@ -476,6 +481,42 @@ class Context:
         """The envs' outputs for the step just acted on, as device arrays (obs f32 [N,O], reward f32 [N], done i32 [N], ...), consumed in stream order."""
         _check(lib().ppo_dev_observe(self.h, *(self._dev_ptr(x) for x in (obs, reward, done, fin_len, fin_rew, truncated, final_obs)),
                                      self._dev_stream(stream)), self.h)
+
+    # ---- observation normalisation of caller-stepped envs (include/ppo_hip.h ppo_obs_norm_*)
+    def obs_norm_enable(self, mode=1, clip=10.0, eps=1e-8):
+        """mode 0 off, 1 update the running statistics with every batch of observations and normalise, 2 normalise with frozen statistics."""
+        _check(lib().ppo_obs_norm_enable(self.h, int(mode), float(clip), float(eps)), self.h)
+
+    def obs_norm_get(self):
+        """-> (mean f64 [O], var f64 [O], count)"""
+        mean, var, count = np.empty(self.O, np.float64), np.empty(self.O, np.float64), C.c_double()
+        _check(lib().ppo_obs_norm_get_h(self.h, mean.ctypes.data_as(C.c_void_p), var.ctypes.data_as(C.c_void_p), C.c_int64(self.O), C.byref(count)), self.h)
+        return mean, var, count.value
+
+    def obs_norm_set(self, mean, var, count):
+        mean, var = np.ascontiguousarray(mean, np.float64).ravel(), np.ascontiguousarray(var, np.float64).ravel()
+        if mean.size != var.size:
+            raise ValueError("mean has %d entries, var %d" % (mean.size, var.size))
+        _check(lib().ppo_obs_norm_set_h(self.h, mean.ctypes.data_as(C.c_void_p), var.ctypes.data_as(C.c_void_p), C.c_int64(mean.size), float(count)), self.h)
+
+    def obs_norm_apply(self, obs, out=None, stream=None):
+        """The apply step with the current statistics, no update.  obs: a host array [n,O] (returns the normalised host array) or a device array
+        (DeviceArray, pointer, object with data_ptr(): then `out`, default obs itself, receives the result, enqueued on `stream`, and is returned)."""
+        if isinstance(obs, np.ndarray):
+            host = np.ascontiguousarray(obs, np.float32).reshape(-1, self.O)
+            d = self.dev(host)
+            try:
+                _check(lib().ppo_obs_norm_apply(self.h, d.ptr, C.c_int64(host.shape[0]), d.ptr, self._dev_stream(None)), self.h)
+                self.sync()
+                return d.download()
+            finally:
+                d.free()
+        if out is None:
+            out = obs
+        n = getattr(obs, "nbytes", None)
+        n = n // (4 * self.O) if n is not None else int(obs.numel()) // self.O
+        _check(lib().ppo_obs_norm_apply(self.h, self._dev_ptr(obs), C.c_int64(n), self._dev_ptr(out), self._dev_stream(stream)), self.h)
+        return out
 
     def host_truncations(self):
         """The truncation events of the last closed rollout: (flat indices t * N + n ascending i32 [K], folded-in values V(final obs) f32 [K])."""

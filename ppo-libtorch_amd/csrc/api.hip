@@ -247,6 +247,15 @@ struct ppo_ctx {
     bool dev_last_fetched = false;    // ... and its events are in dev_last_idx / dev_last_val already (ppo_host_truncations, sorted by index)
     std::vector<int32_t> dev_last_idx;
     std::vector<float> dev_last_val;
+    // observation normalisation (ppo_obs_norm_*): off unless ppo_obs_norm_enable turned it on.  The statistics (f64 mean[O] | var[O]) and the two [N,O]
+    // scratches (the normalised step the commit reads; the normalised final observations of a device-fed fold) are allocated by the first call that needs
+    // them and kept; the row count lives here, on the host: it grows by the batch's rows per update.
+    int on_mode = 0;                  // 0 off, 1 update + apply, 2 apply only
+    float on_clip = 10.0f, on_eps = 1e-8f;
+    double on_count = 0.0;
+    double* on_stats = nullptr;
+    float* on_obs = nullptr;
+    float* on_final = nullptr;
     GenericCtx* gen = nullptr;       // non-null: synthetic env / network other than 2 x 64 (generic.hpp); every L-dependent entry point dispatches on it
     uint8_t* cur_mask = nullptr;     // generic path: action mask of the observation in NEXT_OBS, [N, A]
     bool force_collectives = false;  // PPO_COMM_SELFTEST: world == 1 but the multi-rank path (RCCL included) is taken
@@ -1949,6 +1958,42 @@ static const uint8_t* host_stage_mask(ppo_ctx* c) {
     return c->host_stage_dev + N * c->O * 4 + 4 * N * 4;
 }
 
+// ---- observation normalisation (ppo_obs_norm_*; kernels_obsnorm.hip).  Every batch of new observations -- the reset observations, then each step's
+// next_obs -- goes through on_batch in front of the launch that commits it: mode 1 merges the batch into the running statistics and normalises it with
+// the merged statistics in one launch, mode 2 normalises with the statistics as they stand.  Everything downstream reads the normalised rows only.
+static ppo_status on_reserve(ppo_ctx* c) {
+    if (c->on_stats) return PPO_OK;
+    DeviceGuard dev_guard(c);
+    const size_t O = (size_t)c->O, NO = (size_t)c->N * O;
+    std::vector<double> init(2 * O, 0.0);
+    for (size_t o = 0; o < O; o++) init[O + o] = 1.0;
+    double* st = nullptr;
+    HIPCHK(c, dalloc(c, &st, 2 * O, false));
+    HIPCHK(c, dalloc(c, &c->on_obs, NO, true));
+    HIPCHK(c, dalloc(c, &c->on_final, NO, true));
+    HIPCHK(c, hipMemcpy(st, init.data(), 2 * O * sizeof(double), hipMemcpyHostToDevice));
+    c->on_stats = st;
+    return PPO_OK;
+}
+// one batch [n, O]: src -> dst (dst may be src) on the context's stream
+static ppo_status on_batch(ppo_ctx* c, const float* src, float* dst, int64_t n) {
+    if (c->on_mode == 1) {
+        HIPCHK(c, launch_obsnorm_update_apply(src, dst, n, c->O, c->on_stats, c->on_count, c->on_eps, c->on_clip, c->stream));
+        c->on_count += (double)n;
+    } else {
+        HIPCHK(c, launch_obsnorm_apply(src, dst, n, c->O, c->on_stats, c->on_eps, c->on_clip, nullptr, nullptr, c->stream));
+    }
+    return PPO_OK;
+}
+// the staged step's observations (host-fed rollouts: pinned staging) normalised into the context's scratch, and the commit pointed at the scratch
+static ppo_status on_staged(ppo_ctx* c, HostStepArgs& h) {
+    if (c->on_mode == 0 || !h.commit) return PPO_OK;
+    const ppo_status s = on_batch(c, h.st_obs, c->on_obs, c->N);
+    if (s != PPO_OK) return s;
+    h.st_obs = c->on_obs;
+    return PPO_OK;
+}
+
 // initEnvs (PPO_Discrete.cpp:365-402) for caller-stepped envs: obs_h f32 [N,O] = every env's reset observation
 extern "C" ppo_status ppo_host_env_reset(ppo_ctx* c, const float* obs_h) {
     NEED(c, c != nullptr, "null ctx");
@@ -1961,6 +2006,10 @@ extern "C" ppo_status ppo_host_env_reset(ppo_ctx* c, const float* obs_h) {
     HIPCHK(c, hipMemsetAsync(c->buf[PPO_BUF_EP_LEN], 0, (size_t)c->N * sizeof(int32_t), c->stream));
     HIPCHK(c, hipMemsetAsync(c->buf[PPO_BUF_EP_REW], 0, (size_t)c->N * sizeof(float), c->stream));
     HIPCHK(c, hipMemcpyAsync(c->buf[PPO_BUF_NEXT_OBS], obs_h, (size_t)c->N * c->O * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (c->on_mode != 0) {
+        s = on_batch(c, B_<float>(c, PPO_BUF_NEXT_OBS), B_<float>(c, PPO_BUF_NEXT_OBS), c->N);
+        if (s != PPO_OK) return s;
+    }
     HIPCHK(c, hipStreamSynchronize(c->stream));   // obs_h is the caller's: consumed before return
     return PPO_OK;
 }
@@ -2017,10 +2066,12 @@ extern "C" ppo_status ppo_host_act(ppo_ctx* c, const uint8_t* mask_h, int64_t* a
     const int t = c->host_t, N = c->N;
     const bool masked = c->cfg.dist_kind == PPO_DIST_MASKED && mask_h != nullptr;
     if (masked) std::memcpy(c->host_stage + (size_t)N * c->O * 4 + 4 * (size_t)N * 4, mask_h, (size_t)N * c->A);
-    const HostStepArgs h = host_args(c, t, true);
+    HostStepArgs h = host_args(c, t, true);
     const uint8_t* mask = masked ? host_stage_mask(c) : nullptr;
     const int64_t step = c->rollout_steps + t;
     float* params = B_<float>(c, PPO_BUF_PARAMS);
+    s = on_staged(c, h);   // observation normalisation: one more launch, in front of the commit
+    if (s != PPO_OK) return s;
     if (c->gen) {
         // generic engine: the commit in place of gen_synthetic_step, then gen_rollout's per-step sequence on the committed observation
         GenericCtx& g = *c->gen;
@@ -2165,6 +2216,10 @@ extern "C" ppo_status ppo_host_rollout_begin_groups(ppo_ctx* c, int32_t n_groups
     if (s != PPO_OK) return s;
     if (c->host_n_groups > 0) return fail(c, PPO_ERR_STATE, "ppo_host_rollout_begin_groups: a rollout of %d env groups is already open", c->host_n_groups);
     if (c->host_phase != 0) return fail(c, PPO_ERR_STATE, "ppo_host_rollout_begin_groups: a rollout is already open (%d of %d steps acted on)", c->host_t, c->T);
+    if (c->on_mode != 0)
+        return fail(c, PPO_ERR_UNSUPPORTED, "ppo_host_rollout_begin_groups: observation normalisation is on (ppo_obs_norm_enable): groups commit their steps in an "
+                                            "order the caller chooses and the running statistics would depend on it, which breaks the groups' promise of "
+                                            "interleaving-independent bits; use ppo_host_rollout_begin, or turn the normalisation off");
     NEED(c, bounds_h != nullptr, "null argument");
     if (n_groups < 1 || n_groups > PPO_HOST_MAX_GROUPS)
         return fail(c, PPO_ERR_INVALID, "ppo_host_rollout_begin_groups: n_groups %d outside 1 .. %d", (int)n_groups, PPO_HOST_MAX_GROUPS);
@@ -2327,6 +2382,8 @@ static ppo_status host_fold_truncations(ppo_ctx* c) {
     const size_t off = (size_t)(cap - K) * 4;
     std::memmove(c->trunc_h + off, ix, (size_t)K * 4);
     HIPCHK(c, hipMemcpyAsync(c->trunc_dev + off, c->trunc_h + off, (size_t)K * 4 * (1 + O), hipMemcpyHostToDevice, c->stream));
+    if (c->on_mode != 0)   // the final observations by the statistics as they stand now (the end of the rollout), without updating them
+        HIPCHK(c, launch_obsnorm_apply(trunc_obs_d(c), trunc_obs_d(c), K, c->O, c->on_stats, c->on_eps, c->on_clip, nullptr, nullptr, c->stream));
     const ppo_status s = bootstrap_launch(c, trunc_obs_d(c), trunc_idx_d(c) + (cap - K), K, c->cfg.gamma, B_<float>(c, PPO_BUF_REWARDS), trunc_val_d(c));
     if (s != PPO_OK) return s;
     HIPCHK(c, hipMemcpyAsync(trunc_val_h(c), trunc_val_d(c), (size_t)K * 4, hipMemcpyDeviceToHost, c->stream));
@@ -2445,7 +2502,12 @@ extern "C" ppo_status ppo_dev_env_reset(ppo_ctx* c, const float* obs, void* call
     HIPCHK(c, hipMemsetAsync(c->buf[PPO_BUF_NEXT_DONE], 0, (size_t)c->N * sizeof(int32_t), c->stream));
     HIPCHK(c, hipMemsetAsync(c->buf[PPO_BUF_EP_LEN], 0, (size_t)c->N * sizeof(int32_t), c->stream));
     HIPCHK(c, hipMemsetAsync(c->buf[PPO_BUF_EP_REW], 0, (size_t)c->N * sizeof(float), c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->buf[PPO_BUF_NEXT_OBS], obs, (size_t)c->N * c->O * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    if (c->on_mode != 0) {
+        s = on_batch(c, obs, B_<float>(c, PPO_BUF_NEXT_OBS), c->N);
+        if (s != PPO_OK) return s;
+    } else {
+        HIPCHK(c, hipMemcpyAsync(c->buf[PPO_BUF_NEXT_OBS], obs, (size_t)c->N * c->O * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    }
     return dev_handover_out(c, caller);
 }
 
@@ -2514,6 +2576,15 @@ extern "C" ppo_status ppo_dev_observe(ppo_ctx* c, const float* next_obs, const f
     h.st_obs = next_obs; h.st_rew = reward; h.st_done = done; h.st_fin_len = fin_len; h.st_fin_rew = fin_rew;
     s = dev_handover_in(c, caller);
     if (s != PPO_OK) return s;
+    if (c->on_mode != 0) {   // observation normalisation: the caller's rows into the context's scratch, and the commit reads the scratch
+        s = on_batch(c, next_obs, c->on_obs, N);
+        if (s != PPO_OK) return s;
+        h.st_obs = c->on_obs;
+        if (truncated) {     // the flagged rows of final_obs by the statistics of this step, not updating them; the fold reads the second scratch
+            HIPCHK(c, launch_obsnorm_apply(final_obs, c->on_final, N, c->O, c->on_stats, c->on_eps, c->on_clip, truncated, done, c->stream));
+            final_obs = c->on_final;
+        }
+    }
     HIPCHK(c, launch_host_commit(h, N, c->O, c->stream));
     if (truncated) {
         const int l = c->dev_list;
@@ -2534,6 +2605,91 @@ extern "C" ppo_status ppo_dev_observe(ppo_ctx* c, const float* next_obs, const f
     if (s != PPO_OK) return s;
     c->host_phase = 1;
     return PPO_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Observation normalisation: the four ppo_obs_norm_* calls (ppo_hip.h).  The launches sit in ppo_host_env_reset / ppo_dev_env_reset, ppo_host_act,
+// ppo_dev_observe, ppo_host_rollout_end and host_fold_truncations (on_batch / on_staged above).
+// ---------------------------------------------------------------------------------------------------------
+static ppo_status on_state(ppo_ctx* c, const char* what, bool outside_rollout) {
+    if (!c->host_env)
+        return fail(c, PPO_ERR_UNSUPPORTED, "%s: this context steps its own device environment (env_kind %d), whose observations are of unit scale and never leave "
+                                            "the fused rollout; observation normalisation serves PPO_ENV_HOST contexts", what, c->cfg.env_kind);
+    if (outside_rollout && c->host_phase != 0) return fail(c, PPO_ERR_STATE, "%s: a rollout is open (ppo_host_rollout_end first)", what);
+    return PPO_OK;
+}
+
+extern "C" ppo_status ppo_obs_norm_enable(ppo_ctx* c, int32_t mode, float clip, float eps) {
+    NEED(c, c != nullptr, "null ctx");
+    ppo_status s = on_state(c, "ppo_obs_norm_enable", true);
+    if (s != PPO_OK) return s;
+    if (mode < 0 || mode > 2) return fail(c, PPO_ERR_INVALID, "ppo_obs_norm_enable: mode %d (0 off, 1 update + apply, 2 apply only)", (int)mode);
+    if (!(clip > 0.0f) || !(eps > 0.0f) || !std::isfinite(clip) || !std::isfinite(eps))
+        return fail(c, PPO_ERR_INVALID, "ppo_obs_norm_enable: clip %g and eps %g must be positive and finite", (double)clip, (double)eps);
+    if (mode != 0 && (c->cfg.global_num_envs > c->cfg.num_envs || c->world > 1 || c->comm || c->lgroup || c->xchg))
+        return fail(c, PPO_ERR_UNSUPPORTED, "ppo_obs_norm_enable: this context is a shard of a multi-GPU job: per-rank statistics would make the replicas disagree");
+    if (mode != 0) {
+        s = on_reserve(c);
+        if (s != PPO_OK) return s;
+    }
+    c->on_mode = mode; c->on_clip = clip; c->on_eps = eps;
+    return PPO_OK;
+}
+
+extern "C" ppo_status ppo_obs_norm_get_h(ppo_ctx* c, double* mean_h, double* var_h, int64_t O, double* count) {
+    NEED(c, c != nullptr, "null ctx");
+    const ppo_status s = on_state(c, "ppo_obs_norm_get_h", true);
+    if (s != PPO_OK) return s;
+    NEED(c, mean_h && var_h && count, "ppo_obs_norm_get_h: null argument");
+    if (O != c->O) return fail(c, PPO_ERR_INVALID, "ppo_obs_norm_get_h: O = %lld, the context's obs_size is %d", (long long)O, c->O);
+    if (!c->on_stats) {   // never enabled, never set: the initial statistics
+        for (int o = 0; o < c->O; o++) { mean_h[o] = 0.0; var_h[o] = 1.0; }
+        *count = 0.0;
+        return PPO_OK;
+    }
+    DeviceGuard dev_guard(c);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(mean_h, c->on_stats, (size_t)O * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(var_h, c->on_stats + O, (size_t)O * sizeof(double), hipMemcpyDeviceToHost));
+    *count = c->on_count;
+    return PPO_OK;
+}
+
+extern "C" ppo_status ppo_obs_norm_set_h(ppo_ctx* c, const double* mean_h, const double* var_h, int64_t O, double count) {
+    NEED(c, c != nullptr, "null ctx");
+    ppo_status s = on_state(c, "ppo_obs_norm_set_h", true);
+    if (s != PPO_OK) return s;
+    NEED(c, mean_h && var_h, "ppo_obs_norm_set_h: null argument");
+    if (O != c->O) return fail(c, PPO_ERR_INVALID, "ppo_obs_norm_set_h: O = %lld, the context's obs_size is %d", (long long)O, c->O);
+    if (!(count >= 0.0) || !std::isfinite(count)) return fail(c, PPO_ERR_INVALID, "ppo_obs_norm_set_h: count %g", count);
+    for (int64_t o = 0; o < O; o++)
+        if (!std::isfinite(mean_h[o]) || !(var_h[o] >= 0.0) || !std::isfinite(var_h[o]))
+            return fail(c, PPO_ERR_INVALID, "ppo_obs_norm_set_h: column %lld: mean %g, var %g (finite, var >= 0)", (long long)o, mean_h[o], var_h[o]);
+    s = on_reserve(c);
+    if (s != PPO_OK) return s;
+    DeviceGuard dev_guard(c);
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // nothing enqueued may still be reading the statistics
+    HIPCHK(c, hipMemcpy(c->on_stats, mean_h, (size_t)O * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->on_stats + O, var_h, (size_t)O * sizeof(double), hipMemcpyHostToDevice));
+    c->on_count = count;
+    return PPO_OK;
+}
+
+extern "C" ppo_status ppo_obs_norm_apply(ppo_ctx* c, const float* obs, int64_t n, float* out, void* stream) {
+    NEED(c, c != nullptr, "null ctx");
+    ppo_status s = on_state(c, "ppo_obs_norm_apply", false);
+    if (s != PPO_OK) return s;
+    NEED(c, n >= 0, "ppo_obs_norm_apply: n < 0");
+    if (n == 0) return PPO_OK;
+    NEED(c, obs && out, "ppo_obs_norm_apply: null argument");
+    s = on_reserve(c);
+    if (s != PPO_OK) return s;
+    DeviceGuard dev_guard(c);
+    hipStream_t caller = static_cast<hipStream_t>(stream);
+    s = dev_handover_in(c, caller);
+    if (s != PPO_OK) return s;
+    HIPCHK(c, launch_obsnorm_apply(obs, out, n, c->O, c->on_stats, c->on_eps, c->on_clip, nullptr, nullptr, c->stream));
+    return dev_handover_out(c, caller);
 }
 
 // After T act / observe pairs: commit step T - 1, the values of every stored observation and the bootstrap value (:280) in one batched launch, the
@@ -2567,7 +2723,10 @@ extern "C" ppo_status ppo_host_rollout_end(ppo_ctx* c) {
         tab.row0[tab.n] = N;
         HIPCHK(c, launch_host_commit_groups(host_args_rows(c, T, false, 0, true, false), tab, N, c->O, c->stream));
     } else {
-        HIPCHK(c, launch_host_commit(host_args(c, T, false), N, c->O, c->stream));
+        HostStepArgs h = host_args(c, T, false);
+        s = on_staged(c, h);
+        if (s != PPO_OK) return s;
+        HIPCHK(c, launch_host_commit(h, N, c->O, c->stream));
     }
     float* next_obs = B_<float>(c, PPO_BUF_NEXT_OBS);
     if (c->gen) {
@@ -2795,6 +2954,9 @@ extern "C" ppo_status ppo_profile_read(ppo_ctx* c, ppo_profile* out) {
 // ---------------------------------------------------------------------------------------------------------
 // Multi-GPU
 // ---------------------------------------------------------------------------------------------------------
+static ppo_status on_refuses_comm(ppo_ctx* c, const char* what) {
+    return fail(c, PPO_ERR_UNSUPPORTED, "%s: observation normalisation is on (ppo_obs_norm_enable): per-rank statistics would make the replicas disagree", what);
+}
 extern "C" ppo_status ppo_comm_unique_id(void* id_out_h) {
     if (!id_out_h) return PPO_ERR_INVALID;
     std::string err;
@@ -2809,6 +2971,7 @@ extern "C" ppo_status ppo_comm_unique_id(void* id_out_h) {
 }
 
 extern "C" ppo_status ppo_comm_init(ppo_ctx* c, const void* id_h, int32_t rank, int32_t nranks) {
+    if (c && c->on_mode != 0) return on_refuses_comm(c, "ppo_comm_init");
     NEED(c, c && id_h, "null argument");
     DeviceGuard dev_guard(c);
     NEED(c, nranks >= 1 && rank >= 0 && rank < nranks, "bad rank / nranks");
@@ -2833,6 +2996,7 @@ extern "C" ppo_status ppo_comm_init(ppo_ctx* c, const void* id_h, int32_t rank, 
 
 // Joins the in-process group `group_id` as rank `rank` of `nranks` (all members live in this process, one host thread each).
 extern "C" ppo_status ppo_comm_init_local(ppo_ctx* c, int64_t group_id, int32_t rank, int32_t nranks) {
+    if (c && c->on_mode != 0) return on_refuses_comm(c, "ppo_comm_init_local");
     NEED(c, c != nullptr, "null ctx");
     DeviceGuard dev_guard(c);
     NEED(c, nranks >= 1 && nranks <= 8 && rank >= 0 && rank < nranks, "bad rank / nranks (in-process groups hold at most 8 contexts)");
@@ -2902,6 +3066,7 @@ extern "C" ppo_status ppo_comm_exchange_handle(ppo_ctx* c, void* handle_out_h) {
 // Step 2 (every rank, after all handles have been gathered, e.g. over torch.distributed): map the peers' buffers and switch the context's
 // all-reduces to the exchange.  handles_h: nranks x PPO_COMM_HANDLE_BYTES in rank order.
 extern "C" ppo_status ppo_comm_init_exchange(ppo_ctx* c, const void* handles_h, int32_t rank, int32_t nranks) {
+    if (c && c->on_mode != 0) return on_refuses_comm(c, "ppo_comm_init_exchange");
     NEED(c, c && handles_h, "null argument");
     DeviceGuard dev_guard(c);
     NEED(c, nranks >= 1 && nranks <= 8 && rank >= 0 && rank < nranks, "bad rank / nranks (the direct exchange serves the 8 GPUs of one node)");

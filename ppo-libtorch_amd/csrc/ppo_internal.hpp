@@ -619,6 +619,13 @@ struct HostGroupTable {
 };
 // hs: the whole context's rows at step T (commit = 1; fin_given is taken from the table)
 hipError_t launch_host_commit_groups(const HostStepArgs& hs, const HostGroupTable& tab, int N, int O, hipStream_t s);
+// Observation normalisation of caller-stepped envs (kernels_obsnorm.hip; ppo_obs_norm_* in ppo_hip.h).  stats: f64 [2 O] = mean[O] | var[O]; count: rows merged so far
+// (kept by the host).  update_apply: Chan's merge of the batch src [N,O] into stats, then dst = clamp((src - mean) / sqrt(var + eps), +-clip) with the merged
+// statistics, in one launch (dst may be src).  apply: the same map with the statistics as they stand; truncated / done non-null: only rows where both are
+// non-zero are read and written.
+hipError_t launch_obsnorm_update_apply(const float* src, float* dst, int64_t N, int O, double* stats, double count, float eps, float clip, hipStream_t s);
+hipError_t launch_obsnorm_apply(const float* src, float* dst, int64_t N, int O, const double* stats, float eps, float clip, const int32_t* truncated,
+                                const int32_t* done, hipStream_t s);
 hipError_t launch_categorical(int dist_kind, const float* logits, const uint8_t* mask, const int64_t* value, int64_t n, int A,
                               float* m_logits, float* m_probs, float* log_prob, float* entropy, int64_t* mode, hipStream_t s);
 

@@ -73,6 +73,7 @@ void PPOAlgorithm::getArgs() {
         I("environment", "max_episode_steps", m_max_episode_steps);
         I("environment", "env_groups", m_env_groups);   // extension key (PPO_HostEnv); absent in the reference's files: prints nothing then
         B("environment", "bootstrap_truncated", m_bootstrap_truncated);   // extension key (PPO_HostEnv), likewise
+        B("environment", "norm_obs", m_norm_obs);                         // extension key (PPO_HostEnv), likewise
         I("general", "seed", m_seed);
         I("general", "total_timesteps", m_total_timesteps);
         B("general", "use_cuda", m_use_cuda);
@@ -326,6 +327,13 @@ void PPOAlgorithm::saveCheckpoint(const std::string& agentFile, const std::strin
     // rule of loadPolicyFromCheckpoint would pick it up.  (The archive's internal directory is named after the final file, as LibTorch's is.)
     const std::string ta = agentFile + ".tmp", to = optimizerFile + ".tmp";
     try {
+        if (m_norm_obs) {   // the normaliser's statistics beside the agent file, written BEFORE it: never the newest file of its directory
+            ObsNormFile f;
+            f.mean.resize(static_cast<size_t>(m_obs_size));
+            f.var.resize(static_cast<size_t>(m_obs_size));
+            ppo::check(ppo_obs_norm_get_h(m_ctx, f.mean.data(), f.var.data(), m_obs_size, &f.count), m_ctx, "obs norm");
+            f.write(ObsNormFile::pathFor(agentFile));
+        }
         ppo::pt::writeAgent(ta, m_obs_size, 64, m_action_size, p, fs::path(agentFile).stem().string());
         ppo::pt::writeOptimizer(to, m_obs_size, 64, m_action_size, m, v, step, st.learning_rate, static_cast<double>(1e-5f), 0.01,
                                      fs::path(optimizerFile).stem().string());
@@ -338,11 +346,45 @@ void PPOAlgorithm::saveCheckpoint(const std::string& agentFile, const std::strin
     fs::rename(to, optimizerFile);
 }
 
+void ObsNormFile::write(const std::string& path) const {
+    static_assert(sizeof(double) == 8, "f64");
+    std::vector<double> raw;
+    raw.push_back(static_cast<double>(mean.size()));
+    raw.push_back(count);
+    raw.insert(raw.end(), mean.begin(), mean.end());
+    raw.insert(raw.end(), var.begin(), var.end());
+    const std::string tmp = path + ".tmp";
+    {
+        std::ofstream out(tmp, std::ios::binary | std::ios::trunc);
+        out.write(reinterpret_cast<const char*>(raw.data()), static_cast<std::streamsize>(raw.size() * sizeof(double)));
+        out.flush();
+        if (!out || mean.size() != var.size()) throw std::runtime_error("could not write " + path);
+    }
+    fs::rename(tmp, path);
+}
+ObsNormFile ObsNormFile::read(const std::string& path) {
+    std::ifstream in(path, std::ios::binary);
+    double head[2] = { 0.0, 0.0 };
+    if (!in.read(reinterpret_cast<char*>(head), sizeof head)) throw std::runtime_error(path + ": not an observation-statistics file");
+    const double o = head[0];
+    if (!(o >= 1.0 && o <= 8192.0) || o != std::floor(o) || !(head[1] >= 0.0)) throw std::runtime_error(path + ": not an observation-statistics file");
+    const size_t O = static_cast<size_t>(o);
+    if (fs::file_size(path) != 8 * (2 + 2 * O)) throw std::runtime_error(path + ": " + std::to_string(fs::file_size(path)) + " bytes, expected " + std::to_string(8 * (2 + 2 * O)));
+    ObsNormFile f;
+    f.count = head[1];
+    f.mean.resize(O);
+    f.var.resize(O);
+    if (!in.read(reinterpret_cast<char*>(f.mean.data()), static_cast<std::streamsize>(8 * O)) || !in.read(reinterpret_cast<char*>(f.var.data()), static_cast<std::streamsize>(8 * O)))
+        throw std::runtime_error(path + ": truncated");
+    return f;
+}
+
 static std::string newestFile(const fs::path& dir) {
     std::string best;
     fs::file_time_type when{};
     for (const auto& e : fs::directory_iterator(dir)) {
         if (e.path().extension() == ".tmp") continue;   // an interrupted save
+        if (e.path().extension() == ".obsnorm") continue;   // the normaliser's statistics beside an agent file
         if (best.empty() || fs::last_write_time(e) > when) { best = e.path().string(); when = fs::last_write_time(e); }
     }
     return best;
@@ -387,6 +429,13 @@ void PPOAlgorithm::loadPolicyFromCheckpoint() {
                 m_global_step = PPOUtils::isNumber(steps) ? static_cast<uint64_t>(std::stoll(steps)) : 0;   // :809-811
                 std::cout << "Continuing training from step " << m_global_step << std::endl;
                 ppo::check(ppo_params_set_h(m_ctx, p.data(), P), m_ctx, "load params");
+                const std::string side = ObsNormFile::pathFor(a);   // the normaliser's statistics, when the checkpoint has them
+                if (m_env_kind == PPO_ENV_HOST && fs::exists(side)) {
+                    std::cout << "Loading observation statistics " << side << "..." << std::endl;
+                    const ObsNormFile f = ObsNormFile::read(side);
+                    if (static_cast<int64_t>(f.mean.size()) != m_obs_size) throw std::runtime_error(side + " holds " + std::to_string(f.mean.size()) + " columns, obs_size is " + std::to_string(m_obs_size));
+                    ppo::check(ppo_obs_norm_set_h(m_ctx, f.mean.data(), f.var.data(), m_obs_size, f.count), m_ctx, "load obs norm");
+                }
             }
         } catch (const std::exception& ex) {   // not an archive, truncated, damaged (any exception, bad_alloc / length_error included): say why and start fresh
             std::cout << ex.what() << "; ignoring it." << std::endl;

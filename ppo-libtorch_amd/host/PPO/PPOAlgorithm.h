@@ -18,6 +18,16 @@
 #include "Agent.h"
 
 // What evaluate() returns: the summary ppo_evaluate forms (include/ppo_hip.h ppo_eval_stats) and the per-episode numbers it is formed from.
+// The observation normaliser's statistics as they sit beside a checkpoint (PPO_HostEnv with norm_obs): "<agent file>.obsnorm", raw little-endian f64:
+// O, count, mean[O], var[O] -- 8 * (2 + 2 O) bytes, what ppo_obs_norm_get_h returns and ppo_obs_norm_set_h takes.  The .pt archives stay the reference's.
+struct ObsNormFile {
+    double count = 0.0;
+    std::vector<double> mean, var;
+    static std::string pathFor(const std::string& agentFile) { return agentFile + ".obsnorm"; }
+    void write(const std::string& path) const;          // throws std::runtime_error
+    static ObsNormFile read(const std::string& path);   // throws std::runtime_error (missing, wrong size, O <= 0)
+};
+
 struct EvalResult {
     ppo_eval_stats stats{};
     std::vector<float> returns;
@@ -82,6 +92,7 @@ class PPOAlgorithm {
     int64_t m_checkpoint_updates;
     int64_t m_max_episode_steps;
     int64_t m_env_groups = 1;            // extension ([environment] env_groups): PPO_HostEnv's env groups; the device-env algorithms have no use for it
+    bool m_norm_obs = false;             // extension ([environment] norm_obs): PPO_HostEnv normalises observations with running statistics (ppo_obs_norm_*)
     bool m_bootstrap_truncated = false;  // extension ([environment] bootstrap_truncated): PPO_HostEnv bootstraps the value where a time limit cut an episode off
 
     int64_t m_batch_size;
