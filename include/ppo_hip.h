@@ -175,7 +175,9 @@ PPO_API int32_t ppo_abi_version(void);
  * and the ppo_dev_* calls' two hand-over events (created by the first call on a stream other than the context's) and two device event lists
  * (num_steps * num_envs entries each, a counter, a pinned word and an event per list), made once by the first ppo_dev_observe that passes `truncated`;
  * and the observation normaliser's statistics (2 * obs_size f64) and its two [num_envs, obs_size] f32 scratches, made once by the first
- * ppo_obs_norm_enable with mode != 0 (or the first ppo_obs_norm_set_h / ppo_obs_norm_apply) and kept. */
+ * ppo_obs_norm_enable with mode != 0 (or the first ppo_obs_norm_set_h / ppo_obs_norm_apply) and kept;
+ * and the reward normaliser's discounted-return accumulators (num_envs f64), its two f64 statistics and one [num_envs] f32 scratch, made once by the
+ * first ppo_reward_norm_enable with mode != 0 (or the first ppo_reward_norm_set_h) and kept. */
 PPO_API ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out);
 PPO_API void ppo_ctx_destroy(ppo_ctx* ctx);
 /* Error text of the last failing call on ctx (ctx == NULL: of the last failing ppo_ctx_create in this thread).
@@ -542,6 +544,41 @@ PPO_API ppo_status ppo_obs_norm_set_h(ppo_ctx* ctx, const double* mean_h, const 
 /* out[n,O] = the apply step on obs[n,O] with the current statistics, clip and eps; no update, whatever the mode.  DEVICE pointers; out may alias obs.
  * Valid inside an open rollout too.  stream: as caller_stream of the ppo_dev_* calls (hand-over by events unless it is ppo_stream(ctx)). */
 PPO_API ppo_status ppo_obs_norm_apply(ppo_ctx* ctx, const float* obs, int64_t n, float* out, void* stream);
+
+/* Reward normalisation of caller-stepped environments (new): the other half of gym's NormalizeReward / SB3's VecNormalize -- every reward is divided by
+ * the running standard deviation of the discounted return and clipped.  The reference has none: CartPole and MountainCar pay +-1 per step, and vf_coef,
+ * clip_vloss, max_grad_norm and the learning rate of its TOML are tuned for returns of that scale.  A caller's env pays in its own units (a score in
+ * thousands, a cost in millionths).
+ *
+ * Off unless ppo_reward_norm_enable turns it on: a context that never makes that call runs, launch for launch and bit for bit, what it ran before.
+ * Per context, in f64: a discounted-return accumulator ret[N] and the scalars mean, var (population variance) of the returns seen so far, on the device,
+ * and a row count on the host; initially ret = 0, mean = 0, var = 1, count = 0.  ppo_host_env_reset and ppo_dev_env_reset zero ret and keep the statistics.
+ * Every committed step, with rewards r[N] (f32), this step's done[N] and g = (double)cfg.gamma:
+ *   update (mode 1 only): R[n] = ret[n] * g + (double)r[n];  batch mean bm = (sum R) / N and batch M2 = sum (R - bm)^2, in f64;  then Chan's merge as above
+ *       tot = count + N;  delta = bm - mean;  mean += delta * N / tot;  M2 = var * count + bM2 + delta^2 * count * N / tot;  var = M2 / tot;  count = tot
+ *     and then ret[n] = done[n] ? 0 : R[n].
+ *   apply: y[n] = f32(clamp((double)r[n] / sqrt(var + eps), -clip, +clip)) with var as just updated.  No mean is subtracted, as in gym and SB3.
+ *   mode 2: apply only; ret and the statistics are untouched (SB3's training = False).  mode 0: off; the statistics are kept.
+ * Known consequence: a first batch of identical rewards gives var = 0, so y = r / sqrt(eps) and the clip acts (gym behaves the same way).
+ * Who sees which reward: PPO_BUF_REWARDS[t] holds y, and so do the scan and the update.  PPO_BUF_EP_REW, PPO_BUF_FIN_REW, ep_rew_mean and everything in
+ * ppo_stats about episodes keep the RAW reward.  The truncation fold adds gamma * V(final obs) to the NORMALISED reward (V is in normalised units), in
+ * both feeds: the normalisation of step t precedes the fold of step t.  With reward normalisation alone a host-fed and a device-fed rollout of the same
+ * data agree bit for bit, folded rewards and the values of ppo_host_truncations included; with observation normalisation also on, the difference between
+ * the feeds that its block documents remains, and only that one.  ppo_bootstrap_rewards on caller buffers stays as it is.
+ * Launches: ONE more per env step (rewnorm_update_apply_kernel: one workgroup, sums in a fixed order without atomics, so the same feed gives the same
+ * bits), in front of the commit of the step: in ppo_dev_observe (which still only enqueues), in ppo_host_act for the staged step and in
+ * ppo_host_rollout_end for the last one.
+ * Errors (a failing call changes nothing): PPO_ERR_UNSUPPORTED for any of the three calls on a context that is not PPO_ENV_HOST, for
+ * ppo_reward_norm_enable(mode != 0) on a sharded context (global_num_envs > num_envs or a communicator initialised), for ppo_comm_init /
+ * ppo_comm_init_local / ppo_comm_init_exchange on a context with it on, and for ppo_host_rollout_begin_groups with it on (the statistics would depend on
+ * the order in which groups commit).  PPO_ERR_STATE for enable / get / set while a rollout is open.  PPO_ERR_INVALID for a mode outside 0 .. 2,
+ * clip <= 0, eps <= 0, non-finite arguments, a negative var or count, ret_h != NULL with N != num_envs, null mean / var / count. */
+/* mode 0 off, 1 update + apply, 2 apply only.  Defaults of the bindings: clip = 10, eps = 1e-8.  The statistics are kept across mode changes. */
+PPO_API ppo_status ppo_reward_norm_enable(ppo_ctx* ctx, int32_t mode, float clip, float eps);
+/* The statistics, the row count and (ret_h != NULL) the accumulators, f64 [N], N = num_envs.  Synchronous.  Before anything was enabled or set: 0, 1, 0, zeros. */
+PPO_API ppo_status ppo_reward_norm_get_h(ppo_ctx* ctx, double* mean, double* var, double* count, double* ret_h /* f64 [N] or NULL */, int64_t N);
+/* Replaces the statistics (a checkpoint's, another context's); ret is not touched (the resets zero it).  Synchronous. */
+PPO_API ppo_status ppo_reward_norm_set_h(ppo_ctx* ctx, double mean, double var, double count);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Evaluation (new; the reference reports only the mean over the last 100 exploration episodes of its training envs, PPO_Discrete.cpp:474-480, Utils.h:72-78)

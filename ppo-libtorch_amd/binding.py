@@ -54,6 +54,7 @@ ABI_SYMBOLS = [
     "ppo_host_observe_truncated", "ppo_host_group_observe_truncated", "ppo_host_truncations", "ppo_bootstrap_rewards",
     "ppo_dev_env_reset", "ppo_dev_act", "ppo_dev_observe",
     "ppo_obs_norm_enable", "ppo_obs_norm_get_h", "ppo_obs_norm_set_h", "ppo_obs_norm_apply",
+    "ppo_reward_norm_enable", "ppo_reward_norm_get_h", "ppo_reward_norm_set_h",
 ]
 
 
@@ -153,6 +154,9 @@ def lib():
         L.ppo_obs_norm_get_h.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_double)]
         L.ppo_obs_norm_set_h.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double]
         L.ppo_obs_norm_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.ppo_reward_norm_enable.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_float]
+        L.ppo_reward_norm_get_h.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p, C.c_int64]
+        L.ppo_reward_norm_set_h.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double]
         for name in ABI_SYMBOLS:
             getattr(L, name)  # AttributeError if the build lacks a declared symbol
         if L.ppo_abi_version() != ABI_VERSION:
@@ -517,6 +521,23 @@ class Context:
         n = n // (4 * self.O) if n is not None else int(obs.numel()) // self.O
         _check(lib().ppo_obs_norm_apply(self.h, self._dev_ptr(obs), C.c_int64(n), self._dev_ptr(out), self._dev_stream(stream)), self.h)
         return out
+
+    # ---- reward normalisation of caller-stepped envs (include/ppo_hip.h ppo_reward_norm_*)
+    def reward_norm_enable(self, mode=1, clip=10.0, eps=1e-8):
+        """mode 0 off, 1 update the running statistics of the discounted return with every step and divide the rewards by its standard deviation,
+        2 divide with frozen statistics."""
+        _check(lib().ppo_reward_norm_enable(self.h, int(mode), float(clip), float(eps)), self.h)
+
+    def reward_norm_get(self, returns=False):
+        """-> (mean, var, count), or (mean, var, count, ret f64 [N]) with returns=True"""
+        mean, var, count = C.c_double(), C.c_double(), C.c_double()
+        ret = np.empty(self.N, np.float64) if returns else None
+        _check(lib().ppo_reward_norm_get_h(self.h, C.byref(mean), C.byref(var), C.byref(count), ret.ctypes.data_as(C.c_void_p) if returns else None,
+                                           C.c_int64(self.N)), self.h)
+        return (mean.value, var.value, count.value, ret) if returns else (mean.value, var.value, count.value)
+
+    def reward_norm_set(self, mean, var, count):
+        _check(lib().ppo_reward_norm_set_h(self.h, float(mean), float(var), float(count)), self.h)
 
     def host_truncations(self):
         """The truncation events of the last closed rollout: (flat indices t * N + n ascending i32 [K], folded-in values V(final obs) f32 [K])."""

@@ -256,6 +256,15 @@ struct ppo_ctx {
     double* on_stats = nullptr;
     float* on_obs = nullptr;
     float* on_final = nullptr;
+    // reward normalisation (ppo_reward_norm_*): off unless ppo_reward_norm_enable turned it on.  The accumulators (f64 ret[N]), the statistics (f64
+    // mean | var of the discounted returns) and the [N] scratch the commit stores in the reward row are allocated by the first call that needs them and
+    // kept; the count of merged returns lives here, on the host.
+    int rn_mode = 0;                  // 0 off, 1 update + apply, 2 apply only
+    float rn_clip = 10.0f, rn_eps = 1e-8f;
+    double rn_count = 0.0;
+    double* rn_ret = nullptr;
+    double* rn_stats = nullptr;
+    float* rn_rew = nullptr;
     GenericCtx* gen = nullptr;       // non-null: synthetic env / network other than 2 x 64 (generic.hpp); every L-dependent entry point dispatches on it
     uint8_t* cur_mask = nullptr;     // generic path: action mask of the observation in NEXT_OBS, [N, A]
     bool force_collectives = false;  // PPO_COMM_SELFTEST: world == 1 but the multi-rank path (RCCL included) is taken
@@ -1994,6 +2003,41 @@ static ppo_status on_staged(ppo_ctx* c, HostStepArgs& h) {
     return PPO_OK;
 }
 
+// ---- reward normalisation (ppo_reward_norm_*; kernels_rewnorm.hip).  Every step's rewards go through rn_batch in front of the launch that commits
+// them: mode 1 advances the discounted-return accumulators, merges the N returns into the running statistics and divides the rewards by the merged
+// standard deviation in one launch, mode 2 divides by the statistics as they stand.  The commit stores the scratch in the reward row and still sums the
+// raw reward into the episode totals.
+static ppo_status rn_reserve(ppo_ctx* c) {
+    if (c->rn_stats) return PPO_OK;
+    DeviceGuard dev_guard(c);
+    const double init[2] = {0.0, 1.0};
+    double* st = nullptr;
+    HIPCHK(c, dalloc(c, &c->rn_ret, (size_t)c->N, true));
+    HIPCHK(c, dalloc(c, &c->rn_rew, (size_t)c->N, true));
+    HIPCHK(c, dalloc(c, &st, 2, false));
+    HIPCHK(c, hipMemcpy(st, init, sizeof(init), hipMemcpyHostToDevice));
+    c->rn_stats = st;
+    return PPO_OK;
+}
+// one step: the staged rewards / dones h names -> the context's scratch on the context's stream, and the commit told to store the scratch
+static ppo_status rn_batch(ppo_ctx* c, HostStepArgs& h) {
+    if (c->rn_mode == 0 || !h.commit) return PPO_OK;
+    if (c->rn_mode == 1) {
+        HIPCHK(c, launch_rewnorm_update_apply(h.st_rew, h.st_done, c->rn_rew, c->N, c->rn_ret, c->rn_stats, c->rn_count, c->cfg.gamma, c->rn_eps, c->rn_clip,
+                                              c->stream));
+        c->rn_count += (double)c->N;
+    } else {
+        HIPCHK(c, launch_rewnorm_apply(h.st_rew, c->rn_rew, c->N, c->rn_stats, c->rn_eps, c->rn_clip, c->stream));
+    }
+    h.st_rew_store = c->rn_rew;
+    return PPO_OK;
+}
+// the resets start every env's episode anew: the accumulators go to zero, the statistics stay
+static ppo_status rn_reset_returns(ppo_ctx* c) {
+    if (c->rn_ret) HIPCHK(c, hipMemsetAsync(c->rn_ret, 0, (size_t)c->N * sizeof(double), c->stream));
+    return PPO_OK;
+}
+
 // initEnvs (PPO_Discrete.cpp:365-402) for caller-stepped envs: obs_h f32 [N,O] = every env's reset observation
 extern "C" ppo_status ppo_host_env_reset(ppo_ctx* c, const float* obs_h) {
     NEED(c, c != nullptr, "null ctx");
@@ -2006,6 +2050,8 @@ extern "C" ppo_status ppo_host_env_reset(ppo_ctx* c, const float* obs_h) {
     HIPCHK(c, hipMemsetAsync(c->buf[PPO_BUF_EP_LEN], 0, (size_t)c->N * sizeof(int32_t), c->stream));
     HIPCHK(c, hipMemsetAsync(c->buf[PPO_BUF_EP_REW], 0, (size_t)c->N * sizeof(float), c->stream));
     HIPCHK(c, hipMemcpyAsync(c->buf[PPO_BUF_NEXT_OBS], obs_h, (size_t)c->N * c->O * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    s = rn_reset_returns(c);
+    if (s != PPO_OK) return s;
     if (c->on_mode != 0) {
         s = on_batch(c, B_<float>(c, PPO_BUF_NEXT_OBS), B_<float>(c, PPO_BUF_NEXT_OBS), c->N);
         if (s != PPO_OK) return s;
@@ -2071,6 +2117,8 @@ extern "C" ppo_status ppo_host_act(ppo_ctx* c, const uint8_t* mask_h, int64_t* a
     const int64_t step = c->rollout_steps + t;
     float* params = B_<float>(c, PPO_BUF_PARAMS);
     s = on_staged(c, h);   // observation normalisation: one more launch, in front of the commit
+    if (s != PPO_OK) return s;
+    s = rn_batch(c, h);    // reward normalisation: likewise
     if (s != PPO_OK) return s;
     if (c->gen) {
         // generic engine: the commit in place of gen_synthetic_step, then gen_rollout's per-step sequence on the committed observation
@@ -2218,6 +2266,10 @@ extern "C" ppo_status ppo_host_rollout_begin_groups(ppo_ctx* c, int32_t n_groups
     if (c->host_phase != 0) return fail(c, PPO_ERR_STATE, "ppo_host_rollout_begin_groups: a rollout is already open (%d of %d steps acted on)", c->host_t, c->T);
     if (c->on_mode != 0)
         return fail(c, PPO_ERR_UNSUPPORTED, "ppo_host_rollout_begin_groups: observation normalisation is on (ppo_obs_norm_enable): groups commit their steps in an "
+                                            "order the caller chooses and the running statistics would depend on it, which breaks the groups' promise of "
+                                            "interleaving-independent bits; use ppo_host_rollout_begin, or turn the normalisation off");
+    if (c->rn_mode != 0)
+        return fail(c, PPO_ERR_UNSUPPORTED, "ppo_host_rollout_begin_groups: reward normalisation is on (ppo_reward_norm_enable): groups commit their steps in an "
                                             "order the caller chooses and the running statistics would depend on it, which breaks the groups' promise of "
                                             "interleaving-independent bits; use ppo_host_rollout_begin, or turn the normalisation off");
     NEED(c, bounds_h != nullptr, "null argument");
@@ -2502,6 +2554,8 @@ extern "C" ppo_status ppo_dev_env_reset(ppo_ctx* c, const float* obs, void* call
     HIPCHK(c, hipMemsetAsync(c->buf[PPO_BUF_NEXT_DONE], 0, (size_t)c->N * sizeof(int32_t), c->stream));
     HIPCHK(c, hipMemsetAsync(c->buf[PPO_BUF_EP_LEN], 0, (size_t)c->N * sizeof(int32_t), c->stream));
     HIPCHK(c, hipMemsetAsync(c->buf[PPO_BUF_EP_REW], 0, (size_t)c->N * sizeof(float), c->stream));
+    s = rn_reset_returns(c);
+    if (s != PPO_OK) return s;
     if (c->on_mode != 0) {
         s = on_batch(c, obs, B_<float>(c, PPO_BUF_NEXT_OBS), c->N);
         if (s != PPO_OK) return s;
@@ -2585,6 +2639,8 @@ extern "C" ppo_status ppo_dev_observe(ppo_ctx* c, const float* next_obs, const f
             final_obs = c->on_final;
         }
     }
+    s = rn_batch(c, h);   // reward normalisation: in front of the commit, so that the fold behind it adds gamma * V to the normalised reward
+    if (s != PPO_OK) return s;
     HIPCHK(c, launch_host_commit(h, N, c->O, c->stream));
     if (truncated) {
         const int l = c->dev_list;
@@ -2692,6 +2748,71 @@ extern "C" ppo_status ppo_obs_norm_apply(ppo_ctx* c, const float* obs, int64_t n
     return dev_handover_out(c, caller);
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Reward normalisation: the three ppo_reward_norm_* calls (ppo_hip.h).  The launches sit in ppo_host_act, ppo_dev_observe and ppo_host_rollout_end
+// (rn_batch above), the accumulators are cleared by the two resets.
+// ---------------------------------------------------------------------------------------------------------
+static ppo_status rn_state(ppo_ctx* c, const char* what) {
+    if (!c->host_env)
+        return fail(c, PPO_ERR_UNSUPPORTED, "%s: this context steps its own device environment (env_kind %d), whose rewards are of unit scale and never leave "
+                                            "the fused rollout; reward normalisation serves PPO_ENV_HOST contexts", what, c->cfg.env_kind);
+    if (c->host_phase != 0) return fail(c, PPO_ERR_STATE, "%s: a rollout is open (ppo_host_rollout_end first)", what);
+    return PPO_OK;
+}
+
+extern "C" ppo_status ppo_reward_norm_enable(ppo_ctx* c, int32_t mode, float clip, float eps) {
+    NEED(c, c != nullptr, "null ctx");
+    ppo_status s = rn_state(c, "ppo_reward_norm_enable");
+    if (s != PPO_OK) return s;
+    if (mode < 0 || mode > 2) return fail(c, PPO_ERR_INVALID, "ppo_reward_norm_enable: mode %d (0 off, 1 update + apply, 2 apply only)", (int)mode);
+    if (!(clip > 0.0f) || !(eps > 0.0f) || !std::isfinite(clip) || !std::isfinite(eps))
+        return fail(c, PPO_ERR_INVALID, "ppo_reward_norm_enable: clip %g and eps %g must be positive and finite", (double)clip, (double)eps);
+    if (mode != 0 && (c->cfg.global_num_envs > c->cfg.num_envs || c->world > 1 || c->comm || c->lgroup || c->xchg))
+        return fail(c, PPO_ERR_UNSUPPORTED, "ppo_reward_norm_enable: this context is a shard of a multi-GPU job: per-rank statistics would make the replicas disagree");
+    if (mode != 0) {
+        s = rn_reserve(c);
+        if (s != PPO_OK) return s;
+    }
+    c->rn_mode = mode; c->rn_clip = clip; c->rn_eps = eps;
+    return PPO_OK;
+}
+
+extern "C" ppo_status ppo_reward_norm_get_h(ppo_ctx* c, double* mean, double* var, double* count, double* ret_h, int64_t N) {
+    NEED(c, c != nullptr, "null ctx");
+    const ppo_status s = rn_state(c, "ppo_reward_norm_get_h");
+    if (s != PPO_OK) return s;
+    NEED(c, mean && var && count, "ppo_reward_norm_get_h: null argument");
+    if (ret_h && N != c->N) return fail(c, PPO_ERR_INVALID, "ppo_reward_norm_get_h: N = %lld, the context's num_envs is %d", (long long)N, c->N);
+    if (!c->rn_stats) {   // never enabled, never set: the initial state
+        *mean = 0.0; *var = 1.0; *count = 0.0;
+        if (ret_h) std::memset(ret_h, 0, (size_t)c->N * sizeof(double));
+        return PPO_OK;
+    }
+    DeviceGuard dev_guard(c);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    double st[2];
+    HIPCHK(c, hipMemcpy(st, c->rn_stats, sizeof(st), hipMemcpyDeviceToHost));
+    if (ret_h) HIPCHK(c, hipMemcpy(ret_h, c->rn_ret, (size_t)c->N * sizeof(double), hipMemcpyDeviceToHost));
+    *mean = st[0]; *var = st[1]; *count = c->rn_count;
+    return PPO_OK;
+}
+
+extern "C" ppo_status ppo_reward_norm_set_h(ppo_ctx* c, double mean, double var, double count) {
+    NEED(c, c != nullptr, "null ctx");
+    ppo_status s = rn_state(c, "ppo_reward_norm_set_h");
+    if (s != PPO_OK) return s;
+    if (!std::isfinite(mean) || !(var >= 0.0) || !std::isfinite(var) || !(count >= 0.0) || !std::isfinite(count))
+        return fail(c, PPO_ERR_INVALID, "ppo_reward_norm_set_h: mean %g, var %g, count %g (finite, var >= 0, count >= 0)", mean, var, count);
+    s = rn_reserve(c);
+    if (s != PPO_OK) return s;
+    DeviceGuard dev_guard(c);
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // nothing enqueued may still be reading the statistics
+    const double st[2] = {mean, var};
+    HIPCHK(c, hipMemcpy(c->rn_stats, st, sizeof(st), hipMemcpyHostToDevice));
+    c->rn_count = count;
+    return PPO_OK;
+}
+
 // After T act / observe pairs: commit step T - 1, the values of every stored observation and the bootstrap value (:280) in one batched launch, the
 // scan and the update -- the rest of ppo_train_iteration
 extern "C" ppo_status ppo_host_rollout_end(ppo_ctx* c) {
@@ -2725,6 +2846,8 @@ extern "C" ppo_status ppo_host_rollout_end(ppo_ctx* c) {
     } else {
         HostStepArgs h = host_args(c, T, false);
         s = on_staged(c, h);
+        if (s != PPO_OK) return s;
+        s = rn_batch(c, h);
         if (s != PPO_OK) return s;
         HIPCHK(c, launch_host_commit(h, N, c->O, c->stream));
     }
@@ -2957,6 +3080,9 @@ extern "C" ppo_status ppo_profile_read(ppo_ctx* c, ppo_profile* out) {
 static ppo_status on_refuses_comm(ppo_ctx* c, const char* what) {
     return fail(c, PPO_ERR_UNSUPPORTED, "%s: observation normalisation is on (ppo_obs_norm_enable): per-rank statistics would make the replicas disagree", what);
 }
+static ppo_status rn_refuses_comm(ppo_ctx* c, const char* what) {
+    return fail(c, PPO_ERR_UNSUPPORTED, "%s: reward normalisation is on (ppo_reward_norm_enable): per-rank statistics would make the replicas disagree", what);
+}
 extern "C" ppo_status ppo_comm_unique_id(void* id_out_h) {
     if (!id_out_h) return PPO_ERR_INVALID;
     std::string err;
@@ -2972,6 +3098,7 @@ extern "C" ppo_status ppo_comm_unique_id(void* id_out_h) {
 
 extern "C" ppo_status ppo_comm_init(ppo_ctx* c, const void* id_h, int32_t rank, int32_t nranks) {
     if (c && c->on_mode != 0) return on_refuses_comm(c, "ppo_comm_init");
+    if (c && c->rn_mode != 0) return rn_refuses_comm(c, "ppo_comm_init");
     NEED(c, c && id_h, "null argument");
     DeviceGuard dev_guard(c);
     NEED(c, nranks >= 1 && rank >= 0 && rank < nranks, "bad rank / nranks");
@@ -2997,6 +3124,7 @@ extern "C" ppo_status ppo_comm_init(ppo_ctx* c, const void* id_h, int32_t rank, 
 // Joins the in-process group `group_id` as rank `rank` of `nranks` (all members live in this process, one host thread each).
 extern "C" ppo_status ppo_comm_init_local(ppo_ctx* c, int64_t group_id, int32_t rank, int32_t nranks) {
     if (c && c->on_mode != 0) return on_refuses_comm(c, "ppo_comm_init_local");
+    if (c && c->rn_mode != 0) return rn_refuses_comm(c, "ppo_comm_init_local");
     NEED(c, c != nullptr, "null ctx");
     DeviceGuard dev_guard(c);
     NEED(c, nranks >= 1 && nranks <= 8 && rank >= 0 && rank < nranks, "bad rank / nranks (in-process groups hold at most 8 contexts)");
@@ -3067,6 +3195,7 @@ extern "C" ppo_status ppo_comm_exchange_handle(ppo_ctx* c, void* handle_out_h) {
 // all-reduces to the exchange.  handles_h: nranks x PPO_COMM_HANDLE_BYTES in rank order.
 extern "C" ppo_status ppo_comm_init_exchange(ppo_ctx* c, const void* handles_h, int32_t rank, int32_t nranks) {
     if (c && c->on_mode != 0) return on_refuses_comm(c, "ppo_comm_init_exchange");
+    if (c && c->rn_mode != 0) return rn_refuses_comm(c, "ppo_comm_init_exchange");
     NEED(c, c && handles_h, "null argument");
     DeviceGuard dev_guard(c);
     NEED(c, nranks >= 1 && nranks <= 8 && rank >= 0 && rank < nranks, "bad rank / nranks (the direct exchange serves the 8 GPUs of one node)");

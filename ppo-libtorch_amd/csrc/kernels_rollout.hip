@@ -836,7 +836,7 @@ __device__ __forceinline__ void host_commit_row(const HostStepArgs& hs, int64_t 
         }
         hs.ep_len[row] = len;
         hs.ep_rew[row] = rew;
-        hs.rewards_prev[row] = r;     // :544
+        hs.rewards_prev[row] = hs.st_rew_store ? hs.st_rew_store[row] : r;   // :544 (the normalised reward where reward normalisation is on)
         hs.fin_len_prev[row] = fl;    // :455-456
         hs.fin_rew_prev[row] = fr;
         hs.next_done[row] = d;

@@ -600,6 +600,7 @@ struct HostStepArgs {
     float* dones_t;
     uint8_t* masks_t;
     int32_t* actions_t;
+    const float* st_rew_store;  // [N] or null: what the reward row receives in place of st_rew (reward normalisation); the episode sums always take st_rew
 };
 // commit + act of one step in ONE launch: rollout16_kernel's arithmetic (policy_act16_kernel) when as16 and the shape is one of its, else the vector
 // form (policy_act_kernel).  mask: [N,A] of step t or null; action_h: i64 [N,H], device-visible host memory; logprob_t: LOGPROBS[t]
@@ -626,6 +627,13 @@ hipError_t launch_host_commit_groups(const HostStepArgs& hs, const HostGroupTabl
 hipError_t launch_obsnorm_update_apply(const float* src, float* dst, int64_t N, int O, double* stats, double count, float eps, float clip, hipStream_t s);
 hipError_t launch_obsnorm_apply(const float* src, float* dst, int64_t N, int O, const double* stats, float eps, float clip, const int32_t* truncated,
                                 const int32_t* done, hipStream_t s);
+// Reward normalisation of caller-stepped envs (kernels_rewnorm.hip; ppo_reward_norm_* in ppo_hip.h).  ret: f64 [N] discounted-return accumulators;
+// stats: f64 [2] = mean | var of the returns; count: returns merged so far (kept by the host).  update_apply: R = ret * gamma + rew, Chan's merge of the N
+// values of R into stats, out = clamp(rew / sqrt(var + eps), +-clip) with the merged variance, ret = done ? 0 : R; one launch of one workgroup.  apply: the
+// same map with the statistics as they stand.
+hipError_t launch_rewnorm_update_apply(const float* rew, const int32_t* done, float* out, int64_t N, double* ret, double* stats, double count, float gamma,
+                                       float eps, float clip, hipStream_t s);
+hipError_t launch_rewnorm_apply(const float* rew, float* out, int64_t N, const double* stats, float eps, float clip, hipStream_t s);
 hipError_t launch_categorical(int dist_kind, const float* logits, const uint8_t* mask, const int64_t* value, int64_t n, int A,
                               float* m_logits, float* m_probs, float* log_prob, float* entropy, int64_t* mode, hipStream_t s);
 

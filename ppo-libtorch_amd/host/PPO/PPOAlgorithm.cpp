@@ -74,6 +74,7 @@ void PPOAlgorithm::getArgs() {
         I("environment", "env_groups", m_env_groups);   // extension key (PPO_HostEnv); absent in the reference's files: prints nothing then
         B("environment", "bootstrap_truncated", m_bootstrap_truncated);   // extension key (PPO_HostEnv), likewise
         B("environment", "norm_obs", m_norm_obs);                         // extension key (PPO_HostEnv), likewise
+        B("environment", "norm_reward", m_norm_reward);                   // extension key (PPO_HostEnv), likewise
         I("general", "seed", m_seed);
         I("general", "total_timesteps", m_total_timesteps);
         B("general", "use_cuda", m_use_cuda);
@@ -334,6 +335,11 @@ void PPOAlgorithm::saveCheckpoint(const std::string& agentFile, const std::strin
             ppo::check(ppo_obs_norm_get_h(m_ctx, f.mean.data(), f.var.data(), m_obs_size, &f.count), m_ctx, "obs norm");
             f.write(ObsNormFile::pathFor(agentFile));
         }
+        if (m_norm_reward) {   // likewise the reward normaliser's (ret is not saved: a resume resets the envs, and that zeroes it)
+            RewardNormFile f;
+            ppo::check(ppo_reward_norm_get_h(m_ctx, &f.mean, &f.var, &f.count, nullptr, 0), m_ctx, "reward norm");
+            f.write(RewardNormFile::pathFor(agentFile));
+        }
         ppo::pt::writeAgent(ta, m_obs_size, 64, m_action_size, p, fs::path(agentFile).stem().string());
         ppo::pt::writeOptimizer(to, m_obs_size, 64, m_action_size, m, v, step, st.learning_rate, static_cast<double>(1e-5f), 0.01,
                                      fs::path(optimizerFile).stem().string());
@@ -379,12 +385,36 @@ ObsNormFile ObsNormFile::read(const std::string& path) {
     return f;
 }
 
+void RewardNormFile::write(const std::string& path) const {
+    static_assert(sizeof(double) == 8, "f64");
+    const double raw[3] = { count, mean, var };
+    const std::string tmp = path + ".tmp";
+    {
+        std::ofstream out(tmp, std::ios::binary | std::ios::trunc);
+        out.write(reinterpret_cast<const char*>(raw), sizeof raw);
+        out.flush();
+        if (!out) throw std::runtime_error("could not write " + path);
+    }
+    fs::rename(tmp, path);
+}
+RewardNormFile RewardNormFile::read(const std::string& path) {
+    std::ifstream in(path, std::ios::binary);
+    double raw[3] = { 0.0, 0.0, 0.0 };
+    if (!in.read(reinterpret_cast<char*>(raw), sizeof raw) || fs::file_size(path) != sizeof raw) throw std::runtime_error(path + ": not a reward-statistics file");
+    if (!(raw[0] >= 0.0) || !std::isfinite(raw[0]) || !std::isfinite(raw[1]) || !(raw[2] >= 0.0) || !std::isfinite(raw[2]))
+        throw std::runtime_error(path + ": not a reward-statistics file");
+    RewardNormFile f;
+    f.count = raw[0]; f.mean = raw[1]; f.var = raw[2];
+    return f;
+}
+
 static std::string newestFile(const fs::path& dir) {
     std::string best;
     fs::file_time_type when{};
     for (const auto& e : fs::directory_iterator(dir)) {
         if (e.path().extension() == ".tmp") continue;   // an interrupted save
         if (e.path().extension() == ".obsnorm") continue;   // the normaliser's statistics beside an agent file
+        if (e.path().extension() == ".rewnorm") continue;   // the reward normaliser's, likewise
         if (best.empty() || fs::last_write_time(e) > when) { best = e.path().string(); when = fs::last_write_time(e); }
     }
     return best;
@@ -435,6 +465,12 @@ void PPOAlgorithm::loadPolicyFromCheckpoint() {
                     const ObsNormFile f = ObsNormFile::read(side);
                     if (static_cast<int64_t>(f.mean.size()) != m_obs_size) throw std::runtime_error(side + " holds " + std::to_string(f.mean.size()) + " columns, obs_size is " + std::to_string(m_obs_size));
                     ppo::check(ppo_obs_norm_set_h(m_ctx, f.mean.data(), f.var.data(), m_obs_size, f.count), m_ctx, "load obs norm");
+                }
+                const std::string rside = RewardNormFile::pathFor(a);   // the reward normaliser's, likewise
+                if (m_env_kind == PPO_ENV_HOST && fs::exists(rside)) {
+                    std::cout << "Loading reward statistics " << rside << "..." << std::endl;
+                    const RewardNormFile f = RewardNormFile::read(rside);
+                    ppo::check(ppo_reward_norm_set_h(m_ctx, f.mean, f.var, f.count), m_ctx, "load reward norm");
                 }
             }
         } catch (const std::exception& ex) {   // not an archive, truncated, damaged (any exception, bad_alloc / length_error included): say why and start fresh

@@ -28,6 +28,15 @@ struct ObsNormFile {
     static ObsNormFile read(const std::string& path);   // throws std::runtime_error (missing, wrong size, O <= 0)
 };
 
+// The reward normaliser's statistics beside a checkpoint (PPO_HostEnv with norm_reward): "<agent file>.rewnorm", raw little-endian f64 count, mean, var --
+// 24 bytes, what ppo_reward_norm_get_h returns and ppo_reward_norm_set_h takes.  The discounted-return accumulators are not saved: a resume resets the envs.
+struct RewardNormFile {
+    double count = 0.0, mean = 0.0, var = 1.0;
+    static std::string pathFor(const std::string& agentFile) { return agentFile + ".rewnorm"; }
+    void write(const std::string& path) const;             // throws std::runtime_error
+    static RewardNormFile read(const std::string& path);   // throws std::runtime_error (missing, not 24 bytes, negative or non-finite numbers)
+};
+
 struct EvalResult {
     ppo_eval_stats stats{};
     std::vector<float> returns;
@@ -93,6 +102,7 @@ class PPOAlgorithm {
     int64_t m_max_episode_steps;
     int64_t m_env_groups = 1;            // extension ([environment] env_groups): PPO_HostEnv's env groups; the device-env algorithms have no use for it
     bool m_norm_obs = false;             // extension ([environment] norm_obs): PPO_HostEnv normalises observations with running statistics (ppo_obs_norm_*)
+    bool m_norm_reward = false;          // extension ([environment] norm_reward): PPO_HostEnv divides rewards by the running std of the discounted return (ppo_reward_norm_*)
     bool m_bootstrap_truncated = false;  // extension ([environment] bootstrap_truncated): PPO_HostEnv bootstraps the value where a time limit cut an episode off
 
     int64_t m_batch_size;

@@ -26,6 +26,10 @@
 // observations, then each step's -- updates running mean / variance statistics on the device and is normalised and clipped to +-10 before the network or
 // the rollout buffer sees it (include/ppo_hip.h, "Observation normalisation").  The statistics are saved beside every agent checkpoint
 // ("<agent file>.obsnorm", ObsNormFile) and loaded with it when present.  Not with env groups: the constructor and the setters throw the ABI's message.
+//
+// Reward normalisation (setNormReward(true), or `norm_reward = true` in [environment]; default false): every step's rewards are divided by the running
+// standard deviation of the discounted return and clipped to +-10 before the rollout buffer sees them; the episode statistics keep the raw reward
+// (include/ppo_hip.h, "Reward normalisation").  Saved as "<agent file>.rewnorm" (RewardNormFile), loaded when present, refused with env groups likewise.
 #pragma once
 #include <algorithm>
 #include <atomic>
@@ -49,12 +53,15 @@ class PPO_HostEnv : public PPOAlgorithm {
 
     explicit PPO_HostEnv(EnvFactory factory = nullptr)
         : PPOAlgorithm(PPO_ENV_HOST, Masked ? PPO_DIST_MASKED : PPO_DIST_CATEGORICAL, 4, 500) {
-        getArgs();   // (reads the extension keys env_groups, bootstrap_truncated and norm_obs too)
+        getArgs();   // (reads the extension keys env_groups, bootstrap_truncated, norm_obs and norm_reward too)
         construct();
         const bool norm_obs = m_norm_obs;   // the key; the member follows the context from here on (setNormObs)
         m_norm_obs = false;
+        const bool norm_reward = m_norm_reward;   // likewise (setNormReward)
+        m_norm_reward = false;
         setEnvGroups(m_env_groups);
         if (norm_obs) setNormObs(true);
+        if (norm_reward) setNormReward(true);
         m_envs.reserve(static_cast<size_t>(m_num_envs));
         for (int64_t i = 0; i < m_num_envs; i++) m_envs.push_back(factory ? factory(i) : std::make_shared<Env>(m_seed));
         const size_t N = static_cast<size_t>(m_num_envs);
@@ -76,6 +83,7 @@ class PPO_HostEnv : public PPOAlgorithm {
         if (g < 1 || g > PPO_HOST_MAX_GROUPS || g > m_num_envs)
             throw std::runtime_error("env_groups = " + std::to_string(g) + ": expected 1 .. " + std::to_string(std::min<int64_t>(PPO_HOST_MAX_GROUPS, m_num_envs)));
         if (g > 1 && m_norm_obs) refuseGroupsWithNormObs(g);
+        if (g > 1 && m_norm_reward) refuseGroupsWithNormReward(g);
         m_env_groups = g;
     }
     int64_t envGroups() const { return m_env_groups; }
@@ -91,6 +99,18 @@ class PPO_HostEnv : public PPOAlgorithm {
         }
     }
     bool normObs() const { return m_norm_obs; }
+
+    // rewards divided by the running standard deviation of the discounted return (ppo_reward_norm_enable: update + apply, clip 10, eps 1e-8); false: raw
+    // rewards.  The statistics are kept when it is turned off.
+    void setNormReward(bool on) {
+        ppo::check(ppo_reward_norm_enable(m_ctx, on ? 1 : 0, 10.0f, 1e-8f), m_ctx, "norm_reward");
+        m_norm_reward = on;
+        if (on && m_env_groups > 1) {
+            try { refuseGroupsWithNormReward(m_env_groups); }
+            catch (...) { ppo_reward_norm_enable(m_ctx, 0, 10.0f, 1e-8f); m_norm_reward = false; throw; }
+        }
+    }
+    bool normReward() const { return m_norm_reward; }
 
     // bootstrap the value where a time limit (the env's own truncated flag, or max_episode_steps) cut an episode off; false: the reference's stepEnvs
     void setBootstrapTruncated(bool on) { m_bootstrap_truncated = on; }
@@ -240,6 +260,14 @@ class PPO_HostEnv : public PPOAlgorithm {
         bounds[static_cast<size_t>(g)] = static_cast<int32_t>(m_num_envs);
         ppo::check(ppo_host_rollout_begin_groups(m_ctx, static_cast<int32_t>(g), bounds.data()), m_ctx, "norm_obs with env_groups");
         throw std::runtime_error("norm_obs with env_groups = " + std::to_string(g) + " was not refused");
+    }
+    // norm_reward and env_groups > 1, likewise
+    void refuseGroupsWithNormReward(int64_t g) {
+        std::vector<int32_t> bounds(static_cast<size_t>(g) + 1);
+        for (int64_t k = 0; k < g; k++) bounds[static_cast<size_t>(k)] = static_cast<int32_t>(k * (m_num_envs / g));
+        bounds[static_cast<size_t>(g)] = static_cast<int32_t>(m_num_envs);
+        ppo::check(ppo_host_rollout_begin_groups(m_ctx, static_cast<int32_t>(g), bounds.data()), m_ctx, "norm_reward with env_groups");
+        throw std::runtime_error("norm_reward with env_groups = " + std::to_string(g) + " was not refused");
     }
     // one env's share of stepEnvs (a pool job: must not throw)
     void stepOne(int64_t i, const std::vector<int64_t>& action, std::atomic<int64_t>& bad_width) {
