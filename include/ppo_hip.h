@@ -177,7 +177,8 @@ PPO_API int32_t ppo_abi_version(void);
  * and the observation normaliser's statistics (2 * obs_size f64) and its two [num_envs, obs_size] f32 scratches, made once by the first
  * ppo_obs_norm_enable with mode != 0 (or the first ppo_obs_norm_set_h / ppo_obs_norm_apply) and kept;
  * and the reward normaliser's discounted-return accumulators (num_envs f64), its two f64 statistics and one [num_envs] f32 scratch, made once by the
- * first ppo_reward_norm_enable with mode != 0 (or the first ppo_reward_norm_set_h) and kept. */
+ * first ppo_reward_norm_enable with mode != 0 (or the first ppo_reward_norm_set_h) and kept;
+ * and the event list of ppo_env_truncation_bootstrap (num_steps * num_envs entries plus a counter), allocated by the first enable and kept. */
 PPO_API ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out);
 PPO_API void ppo_ctx_destroy(ppo_ctx* ctx);
 /* Error text of the last failing call on ctx (ctx == NULL: of the last failing ppo_ctx_create in this thread).
@@ -290,6 +291,32 @@ PPO_API ppo_status ppo_env_get_state_h(ppo_ctx* ctx, float* state_h, int32_t* ep
  * T x { store obs/done, policy forward + sample, store value/action/logprob, env step + auto-reset, store reward }.
  * forced_actions i64 [T,N,H] or NULL (teacher-forcing for parity).  Leaves NEXT_OBS / NEXT_DONE for the bootstrap. */
 PPO_API ppo_status ppo_rollout(ppo_ctx* ctx, const int64_t* forced_actions);
+/* Time-limit truncations of the context's own environments (new): bootstrap the value where the time limit cut an episode off.
+ *
+ * The reference ends an episode that reaches max_episode_steps exactly like one the env terminated (PPO_Discrete.cpp:443-452), so the scan cuts the return
+ * there with a bootstrap of 0 and the critic learns that the state in front of the limit is worth nothing -- for CartPole, whose good policies reach the
+ * limit in almost every episode, and MountainCar, which reaches it in every episode until it has learnt.  Callers of the ppo_host_* calls pass the final
+ * observation themselves (ppo_host_observe_truncated below).  For PPO_ENV_CARTPOLE and PPO_ENV_MOUNTAINCAR nothing needs to be passed: the observation IS
+ * the env state, so the final observation of the episode that ended at (t, n) is one env step of PPO_BUF_OBS[t, n] under PPO_BUF_ACTIONS[t, n, 0].
+ *
+ * Off by default, and off is off: a context that never turns the switch on -- or turned it off again -- runs what it ran before, launch for launch and
+ * bit for bit.  With the switch on, ppo_rollout (and hence ppo_train_iteration) enqueues ONE more launch, behind the rollout's value launch and in front of
+ * the scan.  For every i = t * N + n with PPO_BUF_FIN_LEN[i] == max_episode_steps it recomputes that step with the env kernels' own device function; where
+ * the env itself terminated on the step the end is real and nothing happens; elsewhere
+ *   v = Critic(final observation);  PPO_BUF_REWARDS[i] = f32(PPO_BUF_REWARDS[i] + f32(gamma * v)),  gamma = cfg.gamma  (two roundings, no FMA)
+ * and (i, v) joins the rollout's event list, which starts empty.  v is bit for bit the value the launch that fills PPO_BUF_VALUES gives that observation
+ * (the matrix-core critic for both envs, under every kernel_flags value and weight range, as for ppo_bootstrap_rewards; no fall-back is counted), so
+ * delta = r + gamma V(final) - V(obs_t) is formed from ONE critic.  Raw rewards: PPO_BUF_REWARDS holds the folded rewards after ppo_rollout; FIN_REW,
+ * EP_REW, the episode ring and every episode statistic keep the raw reward.  ppo_evaluate is untouched.  The common workgroup -- no episode at the limit
+ * among its 256 samples -- costs one pass over FIN_LEN.  Works with forced_actions; purely local: no collective on a sharded context.
+ * Errors: PPO_ERR_UNSUPPORTED on a PPO_ENV_SYNTHETIC context (its observations are noise: an episode there has no last observation) and on a
+ * PPO_ENV_HOST context (the message names ppo_host_observe_truncated); PPO_ERR_INVALID for `on` outside 0..1 (and a null count, or arrays shorter than the
+ * list, in ppo_env_truncations).  A failing call changes nothing. */
+PPO_API ppo_status ppo_env_truncation_bootstrap(ppo_ctx* ctx, int32_t on);   /* 0 off (default), 1 on */
+/* The events of the last ppo_rollout, with ppo_host_truncations' contract: count; flat indices t * N + n ascending (sorted on the host at read time); the
+ * values V(final obs) that were folded in.  Before any rollout, and after a rollout with the switch off: count = 0.  index_h / value_h may be NULL (count
+ * only); cap = room in the arrays (cap < count with a non-NULL array -> PPO_ERR_INVALID).  Waits for the fold only, not for an update behind it. */
+PPO_API ppo_status ppo_env_truncations(ppo_ctx* ctx, int64_t* count, int32_t* index_h, float* value_h, int64_t cap);
 /* PPO_Discrete::calcAdvantage (PPO_Discrete.cpp:274-331) on the context's buffers: bootstrap NEXT_VALUE = Critic(NEXT_OBS)
  * (:280), then GAE (:283-306) or n-step returns (:309-329) by cfg.use_gae; fills ADVANTAGES and RETURNS. */
 PPO_API ppo_status ppo_calc_advantage(ppo_ctx* ctx);

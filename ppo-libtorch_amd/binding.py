@@ -55,6 +55,7 @@ ABI_SYMBOLS = [
     "ppo_dev_env_reset", "ppo_dev_act", "ppo_dev_observe",
     "ppo_obs_norm_enable", "ppo_obs_norm_get_h", "ppo_obs_norm_set_h", "ppo_obs_norm_apply",
     "ppo_reward_norm_enable", "ppo_reward_norm_get_h", "ppo_reward_norm_set_h",
+    "ppo_env_truncation_bootstrap", "ppo_env_truncations",
 ]
 
 
@@ -157,6 +158,8 @@ def lib():
         L.ppo_reward_norm_enable.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_float]
         L.ppo_reward_norm_get_h.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p, C.c_int64]
         L.ppo_reward_norm_set_h.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double]
+        L.ppo_env_truncation_bootstrap.argtypes = [C.c_void_p, C.c_int32]
+        L.ppo_env_truncations.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_int64]
         for name in ABI_SYMBOLS:
             getattr(L, name)  # AttributeError if the build lacks a declared symbol
         if L.ppo_abi_version() != ABI_VERSION:
@@ -368,6 +371,20 @@ class Context:
         r, k = np.empty(self.N, np.float32), np.empty(self.N, np.int32)
         _check(lib().ppo_env_get_state_h(self.h, *(x.ctypes.data_as(C.c_void_p) for x in (s, l, r, k))), self.h)
         return s, l, r, k
+
+    def env_truncation_bootstrap(self, on=True):
+        """ppo_env_truncation_bootstrap: with the switch on, a rollout of the context's own env (CartPole, MountainCar) folds gamma * V(final observation)
+        into REWARDS where the time limit cut an episode off.  Off by default."""
+        _check(lib().ppo_env_truncation_bootstrap(self.h, int(on)), self.h)
+
+    def env_truncations(self):
+        """The truncation events of the last rollout: (flat indices t * N + n ascending i32 [K], folded-in values V(final obs) f32 [K])."""
+        k = C.c_int64()
+        _check(lib().ppo_env_truncations(self.h, C.byref(k), None, None, C.c_int64(0)), self.h)
+        idx, val = np.empty(k.value, np.int32), np.empty(k.value, np.float32)
+        if k.value:
+            _check(lib().ppo_env_truncations(self.h, C.byref(k), idx.ctypes.data_as(C.c_void_p), val.ctypes.data_as(C.c_void_p), C.c_int64(idx.size)), self.h)
+        return idx, val
 
     # ---- caller-stepped environments (ENV_HOST contexts: include/ppo_hip.h ppo_host_*)
     def host_env_reset(self, obs):

@@ -17,6 +17,7 @@
 
 #include "generic.hpp"
 #include "ppo_internal.hpp"
+#include "trunc_events.hpp"
 
 // ---------------------------------------------------------------------------------------------------------
 // RCCL, bound lazily (single-GPU use never loads it).  One all-reduce per optimizer step.
@@ -247,6 +248,19 @@ struct ppo_ctx {
     bool dev_last_fetched = false;    // ... and its events are in dev_last_idx / dev_last_val already (ppo_host_truncations, sorted by index)
     std::vector<int32_t> dev_last_idx;
     std::vector<float> dev_last_val;
+    // time-limit truncations of the context's own device env (ppo_env_truncation_bootstrap): off unless that call turned it on.  One device event list -- a
+    // counter, [T * N] indices, [T * N] values -- a pinned copy of the counter and an event, made by the first enable and kept.  ppo_rollout clears the counter,
+    // enqueues the fold behind the value launch, copies the counter back and records the event; ppo_env_truncations waits for that event only.
+    bool envt_on = false;
+    int32_t* envt_count = nullptr;    // device [1] (+ padding)
+    int32_t* envt_count_h = nullptr;  // pinned [1]
+    int32_t* envt_index = nullptr;
+    float* envt_value = nullptr;
+    hipEvent_t envt_ev = nullptr;     // behind the last rollout's fold and the copy of its counter
+    bool envt_last = false;           // the last rollout enqueued a fold
+    bool envt_fetched = false;        // ... and its events are in envt_idx / envt_val already (sorted by index)
+    std::vector<int32_t> envt_idx;
+    std::vector<float> envt_val;
     // observation normalisation (ppo_obs_norm_*): off unless ppo_obs_norm_enable turned it on.  The statistics (f64 mean[O] | var[O]) and the two [N,O]
     // scratches (the normalised step the commit reads; the normalised final observations of a device-fed fold) are allocated by the first call that needs
     // them and kept; the row count lives here, on the host: it grows by the batch's rows per update.
@@ -489,6 +503,8 @@ extern "C" void ppo_ctx_destroy(ppo_ctx* c) {
     if (c->dev_ev_out) (void)hipEventDestroy(c->dev_ev_out);
     for (hipEvent_t e : c->dev_fold_ev) if (e) (void)hipEventDestroy(e);
     if (c->dev_count_h) (void)hipHostFree(c->dev_count_h);
+    if (c->envt_count_h) (void)hipHostFree(c->envt_count_h);
+    if (c->envt_ev) (void)hipEventDestroy(c->envt_ev);
     if (c->wr_host) (void)hipHostFree(c->wr_host);
     if (c->snap) (void)hipHostFree(c->snap);
     for (hipEvent_t e : c->snap_ev) if (e) (void)hipEventDestroy(e);
@@ -1199,6 +1215,29 @@ static inline OptGuard opt_guard(const ppo_ctx* c) {
     return g;
 }
 
+// ppo_env_truncation_bootstrap's launch: the episodes of the rollout just enqueued that the time limit cut off get r + gamma V(final observation)
+// (ppo_internal.hpp: EnvFoldArgs).  The critic is the one launch_rollout's tail fills PPO_BUF_VALUES with -- launch_values_mfma for both envs, whatever
+// kernel_flags and the weight range chose for the actor -- as in bootstrap_launch, which counts no fall-back either.
+static ppo_status env_fold_truncations(ppo_ctx* c) {
+    EnvFoldArgs f{};
+    f.obs = B_<float>(c, PPO_BUF_OBS);
+    f.actions = B_<int32_t>(c, PPO_BUF_ACTIONS);
+    f.fin_len = B_<int32_t>(c, PPO_BUF_FIN_LEN);
+    f.B = c->B; f.H = c->H;
+    f.env_kind = c->cfg.env_kind;
+    f.max_episode_steps = c->cfg.max_episode_steps;
+    f.gamma = c->cfg.gamma;
+    f.rewards = B_<float>(c, PPO_BUF_REWARDS);
+    f.ev_count = c->envt_count; f.ev_index = c->envt_index; f.ev_value = c->envt_value; f.ev_cap = c->B;
+    HIPCHK(c, hipMemsetAsync(c->envt_count, 0, sizeof(int32_t), c->stream));
+    HIPCHK(c, launch_env_trunc_fold_mfma(B_<float>(c, PPO_BUF_PARAMS), c->L, f, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->envt_count_h, c->envt_count, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipEventRecord(c->envt_ev, c->stream));
+    c->envt_last = true;
+    c->envt_fetched = false;
+    return PPO_OK;
+}
+
 extern "C" ppo_status ppo_rollout(ppo_ctx* c, const int64_t* forced_actions) {
     NEED(c, c != nullptr, "null ctx");
     if (c->host_env) return host_env_refuses(c, "ppo_rollout");
@@ -1243,6 +1282,11 @@ extern "C" ppo_status ppo_rollout(ppo_ctx* c, const int64_t* forced_actions) {
     {
         ProfScope ps(c, PROF_ROLLOUT);
         HIPCHK(c, launch_rollout(a, c->stream));
+        c->envt_last = false;
+        if (c->envt_on) {   // behind the value launch, in front of the scan (one stream: ppo_calc_advantage and ppo_train_iteration's scan both follow)
+            s = env_fold_truncations(c);
+            if (s != PPO_OK) return s;
+        }
     }
     c->rollout_steps += c->T;
     c->global_step += (int64_t)c->T * c->cfg.global_num_envs;  // global_step += num_envs per step (:526)
@@ -2461,20 +2505,11 @@ extern "C" ppo_status ppo_host_truncations(ppo_ctx* c, int64_t* count, int32_t* 
                 HIPCHK(c, hipMemcpy(ix.data(), c->dev_index[l], (size_t)n * 4, hipMemcpyDeviceToHost));
                 HIPCHK(c, hipMemcpy(va.data(), c->dev_value[l], (size_t)n * 4, hipMemcpyDeviceToHost));
             }
-            std::vector<int32_t> order((size_t)n);
-            for (int64_t k = 0; k < n; k++) order[(size_t)k] = (int32_t)k;
-            std::sort(order.begin(), order.end(), [&ix](int32_t a, int32_t b) { return ix[(size_t)a] < ix[(size_t)b]; });
-            c->dev_last_idx.resize((size_t)n);
-            c->dev_last_val.resize((size_t)n);
-            for (int64_t k = 0; k < n; k++) { c->dev_last_idx[(size_t)k] = ix[(size_t)order[(size_t)k]]; c->dev_last_val[(size_t)k] = va[(size_t)order[(size_t)k]]; }
+            sort_events(ix, va, c->dev_last_idx, c->dev_last_val);
             c->dev_last_fetched = true;
         }
-        const int64_t Kd = (int64_t)c->dev_last_idx.size();
-        if ((index_h || value_h) && cap < Kd)
-            return fail(c, PPO_ERR_INVALID, "ppo_host_truncations: room for %lld events, the last rollout had %lld", (long long)cap, (long long)Kd);
-        if (Kd > 0 && index_h) std::memcpy(index_h, c->dev_last_idx.data(), (size_t)Kd * 4);
-        if (Kd > 0 && value_h) std::memcpy(value_h, c->dev_last_val.data(), (size_t)Kd * 4);
-        *count = Kd;
+        if (!copy_events_out(c->dev_last_idx, c->dev_last_val, count, index_h, value_h, cap))
+            return fail(c, PPO_ERR_INVALID, "ppo_host_truncations: room for %lld events, the last rollout had %lld", (long long)cap, (long long)c->dev_last_idx.size());
         return PPO_OK;
     }
     const int64_t K = (int64_t)c->trunc_last_idx.size();
@@ -2487,6 +2522,61 @@ extern "C" ppo_status ppo_host_truncations(ppo_ctx* c, int64_t* count, int32_t* 
         std::memcpy(value_h, trunc_val_h(c), (size_t)K * 4);
     }
     *count = K;
+    return PPO_OK;
+}
+
+// Time-limit truncations of the context's own device env (ppo_hip.h: ppo_env_truncation_bootstrap).  Which contexts the two calls serve:
+static ppo_status envt_state(ppo_ctx* c, const char* what) {
+    if (c->host_env)
+        return fail(c, PPO_ERR_UNSUPPORTED, "%s: this context's environments are the caller's (PPO_ENV_HOST), and only the caller holds the observation an episode "
+                                            "ended on: pass it with ppo_host_observe_truncated (ppo_dev_observe for device arrays)", what);
+    if (c->cfg.env_kind != PPO_ENV_CARTPOLE && c->cfg.env_kind != PPO_ENV_MOUNTAINCAR)
+        return fail(c, PPO_ERR_UNSUPPORTED, "%s: the synthetic env's observations are noise: an episode there has no last observation to bootstrap from", what);
+    return PPO_OK;
+}
+extern "C" ppo_status ppo_env_truncation_bootstrap(ppo_ctx* c, int32_t on) {
+    NEED(c, c != nullptr, "null ctx");
+    const ppo_status s = envt_state(c, "ppo_env_truncation_bootstrap");
+    if (s != PPO_OK) return s;
+    NEED(c, on == 0 || on == 1, "ppo_env_truncation_bootstrap: on must be 0 or 1");
+    if (on && !c->envt_index) {   // the event list, once (the allocation policy of ppo_ctx_create in ppo_hip.h)
+        DeviceGuard dev_guard(c);
+        if (!c->envt_ev) HIPCHK(c, hipEventCreateWithFlags(&c->envt_ev, hipEventDisableTiming));
+        if (!c->envt_count_h) {
+            HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->envt_count_h), 4 * sizeof(int32_t), hipHostMallocDefault));
+            c->envt_count_h[0] = 0;
+        }
+        if (!c->envt_count) HIPCHK(c, dalloc(c, &c->envt_count, 4, false));
+        if (!c->envt_value) HIPCHK(c, dalloc(c, &c->envt_value, (size_t)c->B, false));
+        HIPCHK(c, dalloc(c, &c->envt_index, (size_t)c->B, false));
+    }
+    c->envt_on = on != 0;
+    return PPO_OK;
+}
+// The events of the last ppo_rollout (ppo_host_truncations' contract): the list is on the device in the order the workgroups got there
+extern "C" ppo_status ppo_env_truncations(ppo_ctx* c, int64_t* count, int32_t* index_h, float* value_h, int64_t cap) {
+    NEED(c, c != nullptr, "null ctx");
+    const ppo_status s = envt_state(c, "ppo_env_truncations");
+    if (s != PPO_OK) return s;
+    NEED(c, count != nullptr, "ppo_env_truncations: count is null");
+    if (!c->envt_last) {   // no rollout yet, or the last one ran with the switch off
+        c->envt_idx.clear();
+        c->envt_val.clear();
+    } else if (!c->envt_fetched) {
+        DeviceGuard dev_guard(c);
+        HIPCHK(c, hipEventSynchronize(c->envt_ev));   // the fold and the copy of its counter: the update behind them keeps running
+        const int64_t n = std::min<int64_t>(std::max<int32_t>(c->envt_count_h[0], 0), c->B);
+        std::vector<int32_t> ix((size_t)n);
+        std::vector<float> va((size_t)n);
+        if (n > 0) {
+            HIPCHK(c, hipMemcpy(ix.data(), c->envt_index, (size_t)n * 4, hipMemcpyDeviceToHost));
+            HIPCHK(c, hipMemcpy(va.data(), c->envt_value, (size_t)n * 4, hipMemcpyDeviceToHost));
+        }
+        sort_events(ix, va, c->envt_idx, c->envt_val);
+        c->envt_fetched = true;
+    }
+    if (!copy_events_out(c->envt_idx, c->envt_val, count, index_h, value_h, cap))
+        return fail(c, PPO_ERR_INVALID, "ppo_env_truncations: room for %lld events, the last rollout had %lld", (long long)cap, (long long)c->envt_idx.size());
     return PPO_OK;
 }
 

@@ -2163,6 +2163,60 @@ __global__ __launch_bounds__(DEV_FOLD_THREADS, 2) void dev_fold_mfma_kernel(cons
     }
 }
 
+// The fold behind a rollout of the library's own envs (ppo_env_truncation_bootstrap; ppo_internal.hpp: EnvFoldArgs).  A 256-thread workgroup owns 256
+// consecutive flat samples.  Every thread reads FIN_LEN[i]; a lane whose episode reached the limit recomputes the step (env_step, the device function the
+// env kernels use: divergent code without a barrier) and keeps the sample unless the env terminated on it.  ONE compaction, on the kept samples: a sample
+// both at the limit and terminated never enters the list, so the critic runs on rows that are folded and on nothing else.  A workgroup that keeps no sample
+// -- the common case, one pass over FIN_LEN -- returns before it loads a weight.  The kept samples' final observations wait in LDS, in list order
+// (ascending), and the four waves take them in 32-row tiles like dev_fold_mfma_kernel.  Plain stores and one atomicAdd per workgroup with events.
+template <int ENV, int OBS>
+__global__ __launch_bounds__(DEV_FOLD_THREADS, 2) void env_trunc_fold_mfma_kernel(const float* __restrict__ P, NetLayout L, EnvFoldArgs a) {
+    __shared__ __attribute__((aligned(16))) uint16_t sW2p[2 * 64 * WS];
+    __shared__ __attribute__((aligned(16))) float sB1[64], sB2[64], sW3[64];
+    __shared__ float fobs[DEV_FOLD_THREADS * OBS];
+    __shared__ int list[DEV_FOLD_THREADS], wtot[8];
+    const int64_t i = (int64_t)blockIdx.x * DEV_FOLD_THREADS + threadIdx.x;
+    bool keep = false;
+    float st[OBS];
+#pragma unroll
+    for (int j = 0; j < OBS; j++) st[j] = 0.0f;
+    if (i < a.B && a.fin_len[i] == a.max_episode_steps) {
+#pragma unroll
+        for (int j = 0; j < OBS; j++) st[j] = a.obs[i * OBS + j];
+        int terminated;
+        (void)env_step<ENV>(st, a.actions[i * a.H], terminated);
+        keep = terminated == 0;
+    }
+    int pos;
+    const int cnt = fold_compact(keep, (int)i, a.ev_count, list, wtot, pos);
+    if (cnt == 0) return;
+    const int base = wtot[4];
+    if (keep) {
+#pragma unroll
+        for (int j = 0; j < OBS; j++) fobs[pos * OBS + j] = st[j];
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int s = lane & 31, hi = lane >> 5;
+    constexpr int L1S = CriticTile<OBS>::L1S;
+    CriticTile<OBS> ct;
+    critic_tile_stage<OBS>(P, L, sW2p, sB1, sB2, sW3, ct);   // ends with the barrier that also publishes fobs
+    const int n_tiles = (cnt + MT - 1) / MT;
+    for (int tile = wave; tile < n_tiles; tile += DEV_FOLD_THREADS / 64) {
+        const int k = tile * MT + s;
+        const bool valid = k < cnt;
+        const int kk = valid ? k : 0;   // a row past the list reads the first kept sample, is zeroed at use and stores nothing
+        const float* src = fobs + kk * OBS;
+        float xb[L1S];
+#pragma unroll
+        for (int stp = 0; stp < L1S; stp++) {
+            const float x = src[(2 * stp + 1 < OBS) ? 2 * stp + hi : 2 * stp];
+            xb[stp] = (valid && (2 * stp + 1 < OBS || hi == 0)) ? x : 0.0f;
+        }
+        const float v = critic_tile_value<OBS>(ct, xb, sW2p, sB1, sB2, sW3);
+        if (valid && hi == 0) fold_store(a.rewards, a.gamma, a.ev_index, a.ev_value, a.ev_cap, (int64_t)base + k, list[kk], v);
+    }
+}
+
 }  // namespace
 
 // One 8-wave workgroup per CU (256 vector registers per wave: two waves per SIMD is all a CU holds; LDS ~95 KB), half of them per net.
@@ -2292,6 +2346,17 @@ hipError_t launch_dev_fold_mfma(const float* params, const NetLayout& L, const D
     const unsigned grid = (unsigned)(((int64_t)a.N + DEV_FOLD_THREADS - 1) / DEV_FOLD_THREADS);
     if (L.obs == 4) hipLaunchKernelGGL((dev_fold_mfma_kernel<4>), dim3(grid), dim3(DEV_FOLD_THREADS), 0, s, params, L, a);
     else if (L.obs == 2) hipLaunchKernelGGL((dev_fold_mfma_kernel<2>), dim3(grid), dim3(DEV_FOLD_THREADS), 0, s, params, L, a);
+    else return hipErrorNotSupported;
+    return hipGetLastError();
+}
+
+hipError_t launch_env_trunc_fold_mfma(const float* params, const NetLayout& L, const EnvFoldArgs& a, hipStream_t s) {
+    if (a.B <= 0 || a.max_episode_steps <= 0) return hipSuccess;   // no limit: no episode is ever cut off
+    const unsigned grid = (unsigned)((a.B + DEV_FOLD_THREADS - 1) / DEV_FOLD_THREADS);
+    if (a.env_kind == PPO_ENV_CARTPOLE && L.obs == 4)
+        hipLaunchKernelGGL((env_trunc_fold_mfma_kernel<PPO_ENV_CARTPOLE, 4>), dim3(grid), dim3(DEV_FOLD_THREADS), 0, s, params, L, a);
+    else if (a.env_kind == PPO_ENV_MOUNTAINCAR && L.obs == 2)
+        hipLaunchKernelGGL((env_trunc_fold_mfma_kernel<PPO_ENV_MOUNTAINCAR, 2>), dim3(grid), dim3(DEV_FOLD_THREADS), 0, s, params, L, a);
     else return hipErrorNotSupported;
     return hipGetLastError();
 }

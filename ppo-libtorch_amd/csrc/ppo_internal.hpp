@@ -764,35 +764,66 @@ struct DevFoldArgs {
     int64_t ev_cap;
 };
 constexpr int DEV_FOLD_THREADS = 256;
-// The front end both fold kernels share.  list: LDS int [256]; wtot: LDS int [8] ([0..3] the waves' counts, [4] the workgroup's base in the event list).
-// Returns the workgroup's number of flagged rows (the same in every thread; 0: nothing else was written).
-__device__ __forceinline__ int dev_fold_compact(const DevFoldArgs& a, int* list, int* wtot) {
+// The compaction every fold kernel shares (256 threads).  flag: this thread has a row to fold; item: what the list keeps for it.  list: LDS int [256], ascending
+// by thread; wtot: LDS int [8] ([0..3] the waves' counts, [4] the workgroup's base in the event list); pos: the thread's place in the list (where flag).
+// Returns the workgroup's number of flagged rows (the same in every thread; 0: nothing else was written, no atomic was issued).
+__device__ __forceinline__ int fold_compact(bool flag, int item, int32_t* ev_count, int* list, int* wtot, int& pos) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t n = (int64_t)blockIdx.x * DEV_FOLD_THREADS + tid;
-    const bool flag = n < a.N && a.truncated[n] != 0 && a.done[n] != 0;
     const unsigned long long b = __ballot(flag);
     if (lane == 0) wtot[wave] = __popcll(b);
     __syncthreads();
     const int c0 = wtot[0], c1 = wtot[1], c2 = wtot[2], c3 = wtot[3];
     const int total = c0 + c1 + c2 + c3;
+    pos = 0;
     if (total == 0) return 0;
     const int before = (wave > 0 ? c0 : 0) + (wave > 1 ? c1 : 0) + (wave > 2 ? c2 : 0);
     const int rank = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
-    if (flag) list[before + rank] = (int)n;
-    if (tid == 0) wtot[4] = atomicAdd(a.ev_count, total);
+    pos = before + rank;
+    if (flag) list[pos] = item;
+    if (tid == 0) wtot[4] = atomicAdd(ev_count, total);
     __syncthreads();
     return total;
 }
-// the fold and the event record of compacted row k (env row n, value v): one lane per row
+// the fold and the event record of one row (flat index i, value v, place e in the event list): one lane per row
+__device__ __forceinline__ void fold_store(float* rewards, float gamma, int32_t* ev_index, float* ev_value, int64_t ev_cap, int64_t e, int64_t i, float v) {
+    rewards[i] = __fadd_rn(rewards[i], __fmul_rn(gamma, v));
+    if (e < ev_cap) { ev_index[e] = (int32_t)i; ev_value[e] = v; }
+}
+// The front end of the two ppo_dev_observe fold kernels: the flagged rows of the workgroup's 256 env rows.
+__device__ __forceinline__ int dev_fold_compact(const DevFoldArgs& a, int* list, int* wtot) {
+    const int64_t n = (int64_t)blockIdx.x * DEV_FOLD_THREADS + threadIdx.x;
+    const bool flag = n < a.N && a.truncated[n] != 0 && a.done[n] != 0;
+    int pos;
+    return fold_compact(flag, (int)n, a.ev_count, list, wtot, pos);
+}
+// compacted row k (env row n, value v)
 __device__ __forceinline__ void dev_fold_store(const DevFoldArgs& a, int base, int k, int n, float v) {
-    const int64_t i = a.tN + n;
-    a.rewards[i] = __fadd_rn(a.rewards[i], __fmul_rn(a.gamma, v));
-    const int64_t e = (int64_t)base + k;
-    if (e < a.ev_cap) { a.ev_index[e] = (int32_t)i; a.ev_value[e] = v; }
+    fold_store(a.rewards, a.gamma, a.ev_index, a.ev_value, a.ev_cap, (int64_t)base + k, a.tN + n, v);
 }
 // the critic arithmetic of launch_bootstrap_values_mfma (obs in {2, 4}) / of launch_bootstrap_values (obs 8: the one shape ppo_bootstrap_rewards sends there)
 hipError_t launch_dev_fold_mfma(const float* params, const NetLayout& L, const DevFoldArgs& a, hipStream_t s);
 hipError_t launch_dev_fold(const float* params, const NetLayout& L, const DevFoldArgs& a, hipStream_t s);
+// The same fold for the environments the library steps itself (ppo_env_truncation_bootstrap): ONE launch behind a rollout finds the episodes the time
+// limit cut off -- FIN_LEN[i] == max_episode_steps, i = t * N + n -- and recomputes their last transition from what the rollout stored: for CartPole and
+// MountainCar the observation IS the env state, so the final observation is env_step of OBS[i] under ACTIONS[i, 0].  Where the env itself terminated on
+// that step the end is real and nothing happens; elsewhere v = Critic(final observation) is folded into REWARDS[i] and (i, v) joins the event list, as above.
+struct EnvFoldArgs {
+    const float* obs;           // PPO_BUF_OBS [B,O]
+    const int32_t* actions;     // PPO_BUF_ACTIONS [B,H]
+    const int32_t* fin_len;     // PPO_BUF_FIN_LEN [B]
+    int64_t B;                  // T * N
+    int H;
+    int env_kind;
+    int max_episode_steps;      // > 0
+    float gamma;
+    float* rewards;             // PPO_BUF_REWARDS [B]
+    int32_t* ev_count;          // the context's event list, cleared in front of the launch
+    int32_t* ev_index;
+    float* ev_value;
+    int64_t ev_cap;
+};
+// the critic arithmetic of launch_values_mfma, which fills PPO_BUF_VALUES for both envs (obs 4 and 2)
+hipError_t launch_env_trunc_fold_mfma(const float* params, const NetLayout& L, const EnvFoldArgs& a, hipStream_t s);
 // batched critic on the matrix cores (obs in {2, 4}); same contract as launch_values
 hipError_t launch_values_mfma(const float* params, const NetLayout& L, const float* obs0, int64_t n0, float* out0, const float* obs1, int64_t n1,
                               float* out1, hipStream_t s);

@@ -72,7 +72,7 @@ void PPOAlgorithm::getArgs() {
         }
         I("environment", "max_episode_steps", m_max_episode_steps);
         I("environment", "env_groups", m_env_groups);   // extension key (PPO_HostEnv); absent in the reference's files: prints nothing then
-        B("environment", "bootstrap_truncated", m_bootstrap_truncated);   // extension key (PPO_HostEnv), likewise
+        B("environment", "bootstrap_truncated", m_bootstrap_truncated);   // extension key (every algorithm class), likewise
         B("environment", "norm_obs", m_norm_obs);                         // extension key (PPO_HostEnv), likewise
         B("environment", "norm_reward", m_norm_reward);                   // extension key (PPO_HostEnv), likewise
         I("general", "seed", m_seed);
@@ -242,6 +242,10 @@ Tensor PPOAlgorithm::getApproxKLAndClippedObj(const Tensor& ratio, const Tensor&
     return Tensor::from_host<float>(m_device, { static_cast<float>(kl / static_cast<double>(r.size())) }, { 1 });
 }
 
+void PPOAlgorithm::setEnvTruncationBootstrap(bool on) {
+    ppo::check(ppo_env_truncation_bootstrap(m_ctx, on ? 1 : 0), m_ctx, "bootstrap_truncated");
+    m_bootstrap_truncated = on;
+}
 void PPOAlgorithm::trainInitEnvs() { ppo::check(ppo_env_reset(m_ctx), m_ctx, "initEnvs"); }
 void PPOAlgorithm::trainRollout() {
     ppo::check(ppo_rollout(m_ctx, nullptr), m_ctx, "rollout");
@@ -550,6 +554,7 @@ void PPOAlgorithm::printPPOResults(int64_t update, int64_t global_step, std::chr
 PPO_Discrete::PPO_Discrete() : PPOAlgorithm(PPO_ENV_CARTPOLE, PPO_DIST_CATEGORICAL, 2, 500) {
     getArgs();
     construct();
+    if (m_bootstrap_truncated) setBootstrapTruncated(true);
 }
 AgentOutput PPO_Discrete::computeActionLogic(const Tensor& next_obs) const { return actImpl(next_obs, nullptr, Tensor()); }
 Tensor PPO_Discrete::initEnvs() { return initEnvsImpl(); }
@@ -557,6 +562,7 @@ Tensor PPO_Discrete::initEnvs() { return initEnvsImpl(); }
 PPO_MultiDiscrete::PPO_MultiDiscrete() : PPOAlgorithm(PPO_ENV_MOUNTAINCAR, PPO_DIST_MASKED, 2, 200) {
     getArgs();
     construct();
+    if (m_bootstrap_truncated) setBootstrapTruncated(true);
 }
 AgentOutput PPO_MultiDiscrete::computeActionLogic(const Tensor& next_obs, const Tensor& action_mask, const Tensor& action) {
     return actImpl(next_obs, &action_mask, action);

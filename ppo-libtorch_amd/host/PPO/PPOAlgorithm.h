@@ -103,7 +103,7 @@ class PPOAlgorithm {
     int64_t m_env_groups = 1;            // extension ([environment] env_groups): PPO_HostEnv's env groups; the device-env algorithms have no use for it
     bool m_norm_obs = false;             // extension ([environment] norm_obs): PPO_HostEnv normalises observations with running statistics (ppo_obs_norm_*)
     bool m_norm_reward = false;          // extension ([environment] norm_reward): PPO_HostEnv divides rewards by the running std of the discounted return (ppo_reward_norm_*)
-    bool m_bootstrap_truncated = false;  // extension ([environment] bootstrap_truncated): PPO_HostEnv bootstraps the value where a time limit cut an episode off
+    bool m_bootstrap_truncated = false;  // extension ([environment] bootstrap_truncated): bootstrap the value where a time limit cut an episode off (every algorithm class; set it with setBootstrapTruncated)
 
     int64_t m_batch_size;
     int64_t m_minibatch_size;
@@ -130,6 +130,7 @@ class PPOAlgorithm {
     virtual void trainRollout();          // rollout (:524-548), advantages (:554) and the update (:567-648) of one iteration, enqueued
     PPOAlgorithm(int env_kind, int dist_kind, int64_t default_obs, int64_t default_max_episode_steps);
     void construct();                     // second half of the reference's constructor: needs the final hyper-parameters
+    void setEnvTruncationBootstrap(bool on);   // the device envs' switch (ppo_env_truncation_bootstrap) and m_bootstrap_truncated with it
     ppo::Tensor initEnvsImpl();
     AgentOutput actImpl(const ppo::Tensor& obs, const ppo::Tensor* mask, const ppo::Tensor& action) const;
     ppo::Tensor bufferView(int which, std::vector<int64_t> shape, ppo::DType dt) const;

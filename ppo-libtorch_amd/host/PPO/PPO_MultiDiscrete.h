@@ -8,4 +8,9 @@ class PPO_MultiDiscrete : public PPOAlgorithm {
     PPO_MultiDiscrete();
     AgentOutput computeActionLogic(const ppo::Tensor& next_obs, const ppo::Tensor& action_mask, const ppo::Tensor& action = ppo::Tensor());  // PPO_MultiDiscrete.cpp:271-277
     ppo::Tensor initEnvs(const ppo::Tensor& action_mask);                // :380-423 (fills the mask with ones)
+    // bootstrap the value where max_episode_steps cut an episode off (`bootstrap_truncated = true` in [environment]; default false): the rollout folds
+    // gamma V(final observation) into the reward there instead of treating the state as terminal (include/ppo_hip.h, ppo_env_truncation_bootstrap);
+    // false: the reference's stepEnvs (PPO_MultiDiscrete.cpp, as PPO_Discrete.cpp:443-452)
+    void setBootstrapTruncated(bool on) { setEnvTruncationBootstrap(on); }
+    bool bootstrapTruncated() const { return m_bootstrap_truncated; }
 };
