@@ -42,8 +42,21 @@ enum { PPO_OK = 0, PPO_ERR_INVALID = 1, PPO_ERR_HIP = 2, PPO_ERR_STATE = 3, PPO_
  * other network (and compute_dtype) on the generic engine with PPO_ENV_SYNTHETIC's limits. */
 enum { PPO_ENV_CARTPOLE = 0, PPO_ENV_MOUNTAINCAR = 1, PPO_ENV_SYNTHETIC = 2, PPO_ENV_HOST = 3 };
 /* PPO_DIST_CATEGORICAL reproduces Distributions/Categorical.cpp including its entropy clamp (:112-119);
- * PPO_DIST_MASKED reproduces Distributions/CategoricalMasked.cpp (true entropy, -1e8 masking). */
-enum { PPO_DIST_CATEGORICAL = 0, PPO_DIST_MASKED = 1 };
+ * PPO_DIST_MASKED reproduces Distributions/CategoricalMasked.cpp (true entropy, -1e8 masking).
+ * PPO_DIST_GAUSSIAN (new; the reference has no continuous policy): a diagonal Gaussian over D = head_dims[0] real-valued actions (n_heads = 1,
+ * 1 <= D <= 32).  The actor's output layer gives the mean mu[D]; a state-independent parameter log_std[D] -- ONE MORE TENSOR, the last in
+ * Agent::parameters() order, behind the actor's layers (ppo_param_count, ppo_param_shapes), initialised to 0 -- gives the scale.  With
+ * z = (a - mu) exp(-log_std):  log-prob = sum_d (-z_d^2 / 2 - log_std_d - log(2 pi) / 2),  entropy = sum_d (1 / 2 + log(2 pi) / 2 + log_std_d), no clamp.
+ * Serves PPO_ENV_HOST contexts with PPO_DTYPE_F32, always on the generic engine (also for a 2 x 64 network); any other env_kind, PPO_DTYPE_BF16 or
+ * n_heads != 1 make ppo_ctx_create return PPO_ERR_UNSUPPORTED.  Actions are f32: PPO_BUF_ACTIONS is f32 [T,N,D], PPO_BUF_MASKS is not used, and the
+ * calls that carry actions have _f32 twins (ppo_host_act_f32, ppo_dev_act_f32, ppo_policy_act_f32); the integer calls return PPO_ERR_UNSUPPORTED on a
+ * Gaussian context and name the twin, and the twins do the same on a categorical context.  Env groups (ppo_host_rollout_begin_groups) return
+ * PPO_ERR_UNSUPPORTED.  Everything up- and downstream of the distribution is shared: ppo_host_observe / ppo_host_observe_truncated /
+ * ppo_host_rollout_end, ppo_dev_observe, ppo_obs_norm_*, ppo_reward_norm_*, ppo_get_value, ppo_update, ppo_minibatch_forward_backward,
+ * ppo_optimizer_step (log_std is clipped, decayed and stepped like any other tensor).
+ * THE ACTION IS THE RAW SAMPLE mu + sigma * eps, stored and returned unclipped: clipping it to the env's bounds is the caller's business (clip the copy
+ * handed to the env, as gym's ClipAction does; the rollout keeps the raw sample, whose log-prob it stored). */
+enum { PPO_DIST_CATEGORICAL = 0, PPO_DIST_MASKED = 1, PPO_DIST_GAUSSIAN = 2 };
 /* PPO_DTYPE_F32: every product carries f32 accuracy (on the matrix cores: f32 operands as three exact bf16 terms, f32 accumulation).
  * PPO_DTYPE_BF16: "bf16 with MFMA GEMMs" of BASELINE configs[4] -- operands and stored activations rounded to bf16 (nearest even),
  * f32 accumulation, f32 master weights, gradients and optimizer state. */
@@ -138,7 +151,7 @@ typedef struct ppo_ctx ppo_ctx;
 /* Internal device buffers (non-owning views).  Element types in brackets. */
 enum {
     PPO_BUF_OBS = 0,      /* m_obs        f32 [T,N,O]                       PPO_Discrete.cpp:90  */
-    PPO_BUF_ACTIONS,      /* m_actions    i32 [T,N,H] (reference stores f32 [T,N,1], :91,:537)   */
+    PPO_BUF_ACTIONS,      /* m_actions    i32 [T,N,H] (reference stores f32 [T,N,1], :91,:537); PPO_DIST_GAUSSIAN: f32 [T,N,D] */
     PPO_BUF_LOGPROBS,     /* m_logprobs   f32 [T,N]                         :92  */
     PPO_BUF_REWARDS,      /* m_rewards    f32 [T,N]                         :93   (PPO_ENV_HOST with truncation events: r + gamma V(final obs) there, after ppo_host_rollout_end) */
     PPO_BUF_DONES,        /* m_dones      f32 [T,N]                         :94  */
@@ -197,7 +210,7 @@ PPO_API ppo_status ppo_memcpy_d2h(ppo_ctx* ctx, void* dst_h, const void* src_dev
  * Agent (PPO/Agent.h:22-54)
  * ------------------------------------------------------------------------------------------------------- */
 PPO_API int64_t ppo_param_count(const ppo_ctx* ctx);
-/* 2*(n_hidden+1) tensors per net, critic first: rows {out,in} for weights and {out,1} for biases. */
+/* 2*(n_hidden+1) tensors per net, critic first: rows {out,in} for weights and {out,1} for biases; PPO_DIST_GAUSSIAN: one more row {D,1}, log_std. */
 PPO_API ppo_status ppo_param_shapes(const ppo_ctx* ctx, int64_t* shapes_h, int32_t* n_tensors);
 /* Agent::ppoLayerInit (Agent.cpp:91-99): orthogonal_(W, gain) with gain sqrt(2) / 1.0 (critic head) / 0.01 (actor
  * head), bias 0.  Own Householder-QR of a Philox Gaussian (LibTorch's LAPACK+mt19937 draw is not reproducible). */
@@ -217,6 +230,16 @@ PPO_API ppo_status ppo_get_value(ppo_ctx* ctx, const float* obs, int64_t n, floa
  *   Arithmetic: that of the kernel ppo_rollout would run in this context now (PPO_KERNEL_ROLLOUT_VECTOR above): bit for bit the rollout's log-probs / actions. */
 PPO_API ppo_status ppo_policy_act(ppo_ctx* ctx, const float* obs, const uint8_t* mask, const int64_t* forced_action, int64_t n,
                           int64_t step_index, int64_t* action, float* logprob, float* entropy, float* value);
+
+/* ppo_policy_act for PPO_DIST_GAUSSIAN contexts (the counterpart of Agent::getActionAndValueDiscrete, Agent.cpp:117-128, for real-valued actions).
+ *   obs [n,O]; forced_action f32 [n,D] or NULL (NULL -> sample); greedy != 0: action = the mean, bit for bit (no random number, forced_action ignored);
+ *   outputs action f32 [n,D], logprob / entropy / value f32 [n] (summed over the D dimensions).  Any output may be NULL (action only with forced_action).
+ *   Draws: eps_d from the context's counter-based generator keyed by (seed, env_offset + row, step_index, d) through Box-Muller with u1 in (0, 1]; the key
+ *   uses a counter word no categorical draw uses, and a draw depends on nothing but its key (not on n, on chunking or on the entry point).
+ *   Arithmetic: that of ppo_host_act_f32 / ppo_dev_act_f32 -- a stepwise loop of this call on the same observations and step indices reproduces a rollout
+ *   bit for bit (tests/test_gpu_gaussian.py). */
+PPO_API ppo_status ppo_policy_act_f32(ppo_ctx* ctx, const float* obs, const float* forced_action, int64_t n, int64_t step_index, int32_t greedy,
+                                      float* action, float* logprob, float* entropy, float* value);
 
 /* Categorical::mode / CategoricalMasked::mode (Categorical.cpp:139-141, CategoricalMasked.cpp:160-162) through the Agent
  * (Agent.cpp:117-170): action[n,H] = per head argmax of m_probs (masked logits set to -1e8 first), FIRST index on equal values;
@@ -240,6 +263,13 @@ PPO_API ppo_status ppo_policy_act_greedy(ppo_ctx* ctx, const float* obs, const u
 PPO_API ppo_status ppo_categorical(int32_t dist_kind, const float* logits, const uint8_t* mask, const int64_t* value, int64_t n,
                            int32_t A, float* m_logits, float* m_probs, float* log_prob, float* entropy, int64_t* mode,
                            void* stream);
+
+/* The diagonal Gaussian alone (beside ppo_categorical; torch.distributions.Normal summed over the last dimension): mean f32 [n,D], log_std f32 [D],
+ * value f32 [n,D] or NULL.  value != NULL: log_prob [n] of value, sample (may be NULL) receives a copy of it.  value == NULL: sample [n,D] = mean +
+ * exp(log_std) * eps with eps keyed by (seed; row_offset + row, step_index, d) as in ppo_policy_act_f32, log_prob of that sample.  entropy [n].
+ * Outputs may be NULL.  1 <= D <= 32. */
+PPO_API ppo_status ppo_gaussian(const float* mean, const float* log_std, const float* value, int64_t n, int32_t D, int64_t seed, int64_t row_offset,
+                                int64_t step_index, float* sample, float* log_prob, float* entropy, void* stream);
 
 /* Categorical::sample / CategoricalMasked::sample (Categorical.cpp:73-79: multinomial(probs, 1, replacement = true)) on given
  * m_probs [n,A]: inverse-CDF draw with the counter-based generator keyed by (seed; row_offset + row, step_index, head). */
@@ -404,6 +434,9 @@ PPO_API ppo_status ppo_host_rollout_begin(ppo_ctx* ctx);
 /* Step t of :524-548: m_obs[t] = next_obs, m_dones[t] = next_done, actor forward + sample, m_actions[t], m_logprobs[t] (and masks [t]);
  * mask_h u8 [N,A] or NULL (masked policies; NULL = all valid); returns when action_h i64 [N,H] (host) holds the actions. */
 PPO_API ppo_status ppo_host_act(ppo_ctx* ctx, const uint8_t* mask_h, int64_t* action_h);
+/* The same step for a PPO_DIST_GAUSSIAN context: returns when action_h f32 [N,D] (host) holds the raw samples mu + sigma * eps (unclipped: clip the copy
+ * given to the env; m_actions[t] keeps the raw sample).  ppo_host_observe / ppo_host_observe_truncated / ppo_host_rollout_end are used unchanged. */
+PPO_API ppo_status ppo_host_act_f32(ppo_ctx* ctx, float* action_h /* [N,D] */);
 /* stepEnvs' outputs for step t (:413-483): next_obs_h [N,O] (already the reset observation where done), reward_h f32 [N], done_h i32 [N]
  * (truncation included; ppo_host_observe_truncated tells the two apart).  fin_len_h i32 [N] / fin_rew_h f32 [N]: the length and reward of the episodes that finished, as the reference reads
  * them from env->episode_length / episode_reward (:474-480), read where done only (a length of 0 is not counted as an episode).  NULL = the
@@ -527,6 +560,8 @@ PPO_API ppo_status ppo_bootstrap_rewards(ppo_ctx* ctx, const float* final_obs, c
 PPO_API ppo_status ppo_dev_env_reset(ppo_ctx* ctx, const float* obs /* [N,O] */, void* caller_stream);
 /* ppo_host_act with the actions left on the device: mask u8 [N,A] or NULL (masked policies; NULL = all valid), action i64 [N,H]. */
 PPO_API ppo_status ppo_dev_act(ppo_ctx* ctx, const uint8_t* mask /* [N,A] or NULL */, int64_t* action /* [N,H] */, void* caller_stream);
+/* ppo_dev_act for a PPO_DIST_GAUSSIAN context: action f32 [N,D], the raw samples; equals ppo_host_act_f32 on the same data bit for bit. */
+PPO_API ppo_status ppo_dev_act_f32(ppo_ctx* ctx, float* action /* device [N,D] */, void* caller_stream);
 /* ppo_host_observe_truncated from device arrays, committed at once (see above). */
 PPO_API ppo_status ppo_dev_observe(ppo_ctx* ctx, const float* next_obs /* [N,O] */, const float* reward /* [N] */, const int32_t* done /* [N] */,
                                    const int32_t* fin_len /* [N] or NULL */, const float* fin_rew /* [N] or NULL */,

@@ -18,7 +18,7 @@ MAX_HEADS = 8
 ENV_CARTPOLE, ENV_MOUNTAINCAR, ENV_SYNTHETIC, ENV_HOST = 0, 1, 2, 3
 MM_EPI_NONE, MM_EPI_BIAS, MM_EPI_BIAS_TANH, MM_EPI_DTANH = 0, 1, 2, 3
 MM_F32X3, MM_BF16 = 0, 1
-DIST_CATEGORICAL, DIST_MASKED = 0, 1
+DIST_CATEGORICAL, DIST_MASKED, DIST_GAUSSIAN = 0, 1, 2   # DIST_GAUSSIAN: f32 actions [.., D], the *_f32 calls (include/ppo_hip.h PPO_DIST_GAUSSIAN)
 DTYPE_F32, DTYPE_BF16 = 0, 1
 KERNEL_ROLLOUT_VECTOR, KERNEL_UPDATE_VECTOR, KERNEL_UPDATE_ONE_WAVE, KERNEL_COMM_SELFTEST, KERNEL_GENERIC_CLASSIC, KERNEL_GENERIC_SPLIT_HEAD = 1, 2, 4, 8, 16, 32   # ppo_config.kernel_flags (include/ppo_hip.h PPO_KERNEL_*)
 ABI_VERSION = 5
@@ -56,6 +56,7 @@ ABI_SYMBOLS = [
     "ppo_obs_norm_enable", "ppo_obs_norm_get_h", "ppo_obs_norm_set_h", "ppo_obs_norm_apply",
     "ppo_reward_norm_enable", "ppo_reward_norm_get_h", "ppo_reward_norm_set_h",
     "ppo_env_truncation_bootstrap", "ppo_env_truncations",
+    "ppo_host_act_f32", "ppo_dev_act_f32", "ppo_policy_act_f32", "ppo_gaussian",
 ]
 
 
@@ -160,6 +161,10 @@ def lib():
         L.ppo_reward_norm_set_h.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double]
         L.ppo_env_truncation_bootstrap.argtypes = [C.c_void_p, C.c_int32]
         L.ppo_env_truncations.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_int64]
+        L.ppo_host_act_f32.argtypes = [C.c_void_p] * 2
+        L.ppo_dev_act_f32.argtypes = [C.c_void_p] * 3
+        L.ppo_policy_act_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32] + [C.c_void_p] * 4
+        L.ppo_gaussian.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 4
         for name in ABI_SYMBOLS:
             getattr(L, name)  # AttributeError if the build lacks a declared symbol
         if L.ppo_abi_version() != ABI_VERSION:
@@ -256,15 +261,19 @@ class Context:
         _check(lib().ppo_buffer(self.h, BUF[name], C.byref(p), C.byref(n)), self.h)
         return p, n.value
 
+    def _buf_dtype(self, name):
+        # a Gaussian context keeps f32 actions [T,N,D] in PPO_BUF_ACTIONS
+        return np.float32 if name == "ACTIONS" and self.cfg.dist_kind == DIST_GAUSSIAN else _BUF_DTYPE[name]
+
     def read(self, name, shape=None):
         p, n = self.buffer_ptr(name)
-        out = np.empty(n // np.dtype(_BUF_DTYPE[name]).itemsize, _BUF_DTYPE[name])
+        out = np.empty(n // np.dtype(self._buf_dtype(name)).itemsize, self._buf_dtype(name))
         _check(lib().ppo_memcpy_d2h(self.h, out.ctypes.data_as(C.c_void_p), p, C.c_size_t(n)), self.h)
         return out.reshape(shape) if shape is not None else out
 
     def write(self, name, host):
         p, n = self.buffer_ptr(name)
-        host = np.ascontiguousarray(host, dtype=_BUF_DTYPE[name])
+        host = np.ascontiguousarray(host, dtype=self._buf_dtype(name))
         assert host.nbytes == n, (name, host.nbytes, n)
         _check(lib().ppo_memcpy_h2d(self.h, p, host.ctypes.data_as(C.c_void_p), C.c_size_t(n)), self.h)
 
@@ -282,7 +291,7 @@ class Context:
         _check(lib().ppo_params_init_orthogonal(self.h, C.c_int64(seed)), self.h)
 
     def param_shapes(self):
-        shapes = np.empty((32, 2), np.int64)   # up to 2 nets x 8 layers x {weight, bias}
+        shapes = np.empty((33, 2), np.int64)   # up to 2 nets x 8 layers x {weight, bias}, and a Gaussian policy's log_std
         n = C.c_int32()
         _check(lib().ppo_param_shapes(self.h, shapes.ctypes.data_as(C.c_void_p), C.byref(n)), self.h)
         return shapes[:n.value]
@@ -317,6 +326,23 @@ class Context:
         _check(lib().ppo_policy_act(self.h, d_obs.ptr, d_mask.ptr if d_mask else None, d_forced.ptr if d_forced else None, C.c_int64(n),
                                     C.c_int64(step_index), d_a.ptr, d_lp.ptr, d_en.ptr, d_v.ptr), self.h)
         return d_a.download(), d_lp.download(), d_en.download(), d_v.download()
+
+    def policy_act_f32(self, obs, action=None, step_index=0, greedy=False):
+        """ppo_policy_act_f32 (DIST_GAUSSIAN contexts): action f32 [n,D] forced, or None to sample (greedy: the mean).
+        Returns (action f32 [n,D], logprob, entropy, value)."""
+        obs = np.ascontiguousarray(obs, np.float32).reshape(-1, self.O)
+        n = obs.shape[0]
+        tmp = [self.dev(obs)]
+        if action is not None:
+            tmp.append(self.dev(np.asarray(action, np.float32).reshape(n, self.A)))
+        out = [self.empty((n, self.A), np.float32), self.empty(n, np.float32), self.empty(n, np.float32), self.empty(n, np.float32)]
+        try:
+            _check(lib().ppo_policy_act_f32(self.h, tmp[0].ptr, tmp[1].ptr if action is not None else None, C.c_int64(n), C.c_int64(step_index),
+                                            C.c_int32(1 if greedy else 0), *(x.ptr for x in out)), self.h)
+            return tuple(x.download() for x in out)
+        finally:
+            for x in tmp + out:
+                x.free()
 
     def policy_act_greedy(self, obs, mask=None):
         """Categorical::mode through the Agent (reference Categorical.cpp:139-141, Agent.cpp:117-170): the deterministic action per head, with the
@@ -451,6 +477,12 @@ class Context:
         _check(lib().ppo_host_act(self.h, m.ctypes.data_as(C.c_void_p) if m is not None else None, out.ctypes.data_as(C.c_void_p)), self.h)
         return out
 
+    def host_act_f32(self):
+        """Step t of the rollout of a DIST_GAUSSIAN context: the raw samples f32 [N,D] (host); clipping to the env's bounds is the caller's."""
+        out = np.empty((self.N, self.A), np.float32)
+        _check(lib().ppo_host_act_f32(self.h, out.ctypes.data_as(C.c_void_p)), self.h)
+        return out
+
     def host_observe(self, obs, reward, done, fin_len=None, fin_rew=None, truncated=None, final_obs=None):
         """The caller's envs' outputs for the step just acted on (obs already the reset observation where done; done includes truncation).
         truncated i32 [N] / final_obs f32 [N,O] (ppo_host_observe_truncated): where the episode that ended was cut off by a time limit, and the
@@ -497,6 +529,10 @@ class Context:
     def dev_act(self, action, mask=None, stream=None):
         """Step t of the rollout: the sampled actions go to the device array action i64 [N,H], valid for work enqueued on `stream` after the call."""
         _check(lib().ppo_dev_act(self.h, self._dev_ptr(mask), self._dev_ptr(action), self._dev_stream(stream)), self.h)
+
+    def dev_act_f32(self, action, stream=None):
+        """dev_act for a DIST_GAUSSIAN context: the raw samples go to the device array action f32 [N,D]."""
+        _check(lib().ppo_dev_act_f32(self.h, self._dev_ptr(action), self._dev_stream(stream)), self.h)
 
     def dev_observe(self, obs, reward, done, fin_len=None, fin_rew=None, truncated=None, final_obs=None, stream=None):
         """The envs' outputs for the step just acted on, as device arrays (obs f32 [N,O], reward f32 [N], done i32 [N], ...), consumed in stream order."""
@@ -742,6 +778,26 @@ def categorical(ctx, dist_kind, logits, mask=None, value=None):
                                  C.c_void_p(ctx.stream())), ctx.h)
     ctx.sync()
     return {k: v.download() for k, v in o.items()}
+
+
+def gaussian(ctx, mean, log_std, value=None, seed=0, row_offset=0, step_index=0):
+    """ppo_gaussian: the diagonal Gaussian alone.  mean [n,D], log_std [D]; value [n,D] -> its log-prob, None -> a sample keyed by
+    (seed, row_offset + row, step_index, d).  Returns dict(sample, log_prob, entropy)."""
+    mean = np.ascontiguousarray(mean, np.float32)
+    n, D = mean.shape
+    tmp = [ctx.dev(mean), ctx.dev(np.ravel(log_std), np.float32)]
+    if value is not None:
+        tmp.append(ctx.dev(np.asarray(value, np.float32).reshape(n, D)))
+    o = dict(sample=ctx.empty((n, D), np.float32), log_prob=ctx.empty(n, np.float32), entropy=ctx.empty(n, np.float32))
+    try:
+        _check(lib().ppo_gaussian(tmp[0].ptr, tmp[1].ptr, tmp[2].ptr if value is not None else None, C.c_int64(n), C.c_int32(D), C.c_int64(seed),
+                                  C.c_int64(row_offset), C.c_int64(step_index), o["sample"].ptr, o["log_prob"].ptr, o["entropy"].ptr,
+                                  C.c_void_p(ctx.stream())), ctx.h)
+        ctx.sync()
+        return {k: v.download() for k, v in o.items()}
+    finally:
+        for x in tmp + list(o.values()):
+            x.free()
 
 
 def matmul_launch(ctx, trans_a, trans_b, M, N, K, d_a, lda, d_b, ldb, d_c, ldc, epilogue=MM_EPI_NONE, d_aux=None, ld_aux=0, precision=MM_F32X3):

@@ -525,7 +525,8 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
     // PPO_ENV_HOST: the caller's envs (ppo_host_*).  The reference's network (2 x 64, f32) at the observation widths the reference-shape kernels are built
     // for runs on them; every other network on the generic engine, with PPO_ENV_SYNTHETIC's limits
     const bool host_env = cfg->env_kind == PPO_ENV_HOST;
-    const bool host_ref = host_env && cfg->hidden == PPO_HIDDEN && cfg->n_hidden == 2 && cfg->compute_dtype == PPO_DTYPE_F32 &&
+    const bool gauss = cfg->dist_kind == PPO_DIST_GAUSSIAN;   // diagonal-Gaussian policies: always the generic engine (kernels_gauss.hip)
+    const bool host_ref = host_env && !gauss && cfg->hidden == PPO_HIDDEN && cfg->n_hidden == 2 && cfg->compute_dtype == PPO_DTYPE_F32 &&
                           (cfg->obs_size == 2 || cfg->obs_size == 4 || cfg->obs_size == 8);
     const bool generic = cfg->env_kind == PPO_ENV_SYNTHETIC || (host_env && !host_ref);
     if (!generic && (cfg->hidden != PPO_HIDDEN || cfg->n_hidden != 2))
@@ -536,8 +537,15 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
                     cfg->n_hidden, GEN_MAX_LAYERS - 1, cfg->obs_size);
     if (cfg->env_kind != PPO_ENV_CARTPOLE && cfg->env_kind != PPO_ENV_MOUNTAINCAR && cfg->env_kind != PPO_ENV_SYNTHETIC && cfg->env_kind != PPO_ENV_HOST)
         return fail(nullptr, PPO_ERR_INVALID, "unknown env_kind %d", cfg->env_kind);
-    if (cfg->dist_kind != PPO_DIST_CATEGORICAL && cfg->dist_kind != PPO_DIST_MASKED) return fail(nullptr, PPO_ERR_INVALID, "unknown dist_kind %d", cfg->dist_kind);
+    if (cfg->dist_kind != PPO_DIST_CATEGORICAL && cfg->dist_kind != PPO_DIST_MASKED && !gauss) return fail(nullptr, PPO_ERR_INVALID, "unknown dist_kind %d", cfg->dist_kind);
     if (cfg->compute_dtype != PPO_DTYPE_F32 && cfg->compute_dtype != PPO_DTYPE_BF16) return fail(nullptr, PPO_ERR_INVALID, "unknown compute_dtype %d", cfg->compute_dtype);
+    if (gauss && !host_env)
+        return fail(nullptr, PPO_ERR_UNSUPPORTED, "dist_kind = PPO_DIST_GAUSSIAN serves caller-stepped environments (env_kind = PPO_ENV_HOST): CartPole, MountainCar and "
+                    "the synthetic env take discrete actions; got env_kind %d", cfg->env_kind);
+    if (gauss && cfg->compute_dtype != PPO_DTYPE_F32)
+        return fail(nullptr, PPO_ERR_UNSUPPORTED, "dist_kind = PPO_DIST_GAUSSIAN is built for compute_dtype = PPO_DTYPE_F32; bf16 storage is not");
+    if (gauss && cfg->n_heads != 1)
+        return fail(nullptr, PPO_ERR_UNSUPPORTED, "dist_kind = PPO_DIST_GAUSSIAN takes n_heads = 1 with head_dims[0] = the action dimension D; got n_heads = %d", cfg->n_heads);
     if (cfg->kernel_flags & ~(PPO_KERNEL_ROLLOUT_VECTOR | PPO_KERNEL_UPDATE_VECTOR | PPO_KERNEL_UPDATE_ONE_WAVE | PPO_KERNEL_COMM_SELFTEST | PPO_KERNEL_GENERIC_CLASSIC | PPO_KERNEL_GENERIC_SPLIT_HEAD)) return fail(nullptr, PPO_ERR_INVALID, "unknown bits in kernel_flags 0x%x", cfg->kernel_flags);
     if (cfg->compute_dtype == PPO_DTYPE_BF16 && !generic)
         return fail(nullptr, PPO_ERR_UNSUPPORTED, "compute_dtype = PPO_DTYPE_BF16 applies to networks whose layers are GEMMs (env_kind = PPO_ENV_SYNTHETIC); the reference's "
@@ -573,7 +581,7 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
     c->L = make_layout(cfg->obs_size, cfg->n_heads, cfg->head_dims);
     if (generic) {
         c->gen = new GenericCtx();
-        c->gen->L = make_gen_layout(cfg->obs_size, cfg->hidden, cfg->n_hidden, cfg->n_heads, cfg->head_dims);
+        c->gen->L = make_gen_layout(cfg->obs_size, cfg->hidden, cfg->n_hidden, cfg->n_heads, cfg->head_dims, gauss);
         // the shared code sizes the flat parameter / gradient / moment buffers from L.P; the 2 x 64 offsets in L are not used
         c->L.P = c->gen->L.P;
         c->L.n_tensors = c->gen->L.n_tensors;
@@ -601,7 +609,7 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
     CK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     const size_t TN = (size_t)c->T * c->N, N = c->N, P = c->L.P;
     CK(dalloc_buf<float>(c, PPO_BUF_OBS, TN * c->O));
-    CK(dalloc_buf<int32_t>(c, PPO_BUF_ACTIONS, TN * c->H));
+    CK(dalloc_buf<int32_t>(c, PPO_BUF_ACTIONS, TN * (gauss ? A : c->H)));   // Gaussian: f32 [T,N,D] (the same 4-byte elements)
     CK(dalloc_buf<float>(c, PPO_BUF_LOGPROBS, TN));
     CK(dalloc_buf<float>(c, PPO_BUF_REWARDS, TN));
     CK(dalloc_buf<float>(c, PPO_BUF_DONES, TN));
@@ -659,7 +667,7 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
     CK(hipEventCreateWithFlags(&c->coef_copied[1], hipEventDisableTiming));
     CK(dalloc(c, &c->step_stats, (size_t)c->steps_per_update + 1));
     CK(dalloc(c, &c->clipfrac_accum, 2));
-    CK(dalloc(c, &c->norm2, 4 * GEN_MAX_LAYERS * GEN_NORM_PARTS));
+    CK(dalloc(c, &c->norm2, (4 * GEN_MAX_LAYERS + 1) * GEN_NORM_PARTS));
     CK(dalloc(c, &c->fused_partial, (size_t)fused_opt_blocks(c->L) * 12));
     CK(dalloc(c, &c->ev_sums, PPO_EV_BLOCKS * 4));
     if (c->use_mfma && !generic) {
@@ -677,7 +685,7 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
         CK(hipHostMalloc(reinterpret_cast<void**>(&c->host_stage), c->host_stage_bytes, hipHostMallocMapped));
         CK(hipHostGetDevicePointer(reinterpret_cast<void**>(&c->host_stage_dev), c->host_stage, 0));
         std::memset(c->host_stage, 0, c->host_stage_bytes);
-        CK(hipHostMalloc(reinterpret_cast<void**>(&c->host_act), N * c->H * sizeof(int64_t), hipHostMallocMapped));
+        CK(hipHostMalloc(reinterpret_cast<void**>(&c->host_act), std::max(N * c->H * sizeof(int64_t), gauss ? N * A * sizeof(float) : (size_t)0), hipHostMallocMapped));
         CK(hipHostGetDevicePointer(reinterpret_cast<void**>(&c->host_act_dev), c->host_act, 0));
         for (auto& hg : c->host_grp) CK(hipEventCreateWithFlags(&hg.ev, hipEventDisableTiming));
     }
@@ -727,7 +735,7 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
         CK(dalloc(c, &g.val, R));
         for (int i = 0; i < 4; i++) CK(dalloc(c, &g.row_f[i], R));
         CK(dalloc(c, &g.row_f[4], R + 2));
-        CK(dalloc(c, &g.row_act, R * GL.n_heads));
+        CK(dalloc(c, &g.row_act, R * gen_action_words(GL)));
         CK(dalloc(c, &g.row_mask, R * GL.act));
 
         CK(dalloc(c, &g.loss_part, (size_t)GEN_LOSS_BLOCKS * 8));
@@ -764,6 +772,10 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
         CK(dalloc(c, &g.act64, N * GL.n_heads));
         CK(dalloc(c, &g.step_lp, N));
         CK(dalloc(c, &g.step_en, N));
+        if (GL.gauss) {
+            CK(dalloc(c, &g.actf, N * GL.gauss));
+            CK(dalloc(c, &g.ls_part, (size_t)GEN_LOSS_BLOCKS * GL.gauss));
+        }
         CK(dalloc(c, &c->cur_mask, N * GL.act));
         // the zero-fills above ran on the null stream, which a non-blocking stream does not wait for: drain them before the first write
         CK(hipDeviceSynchronize());
@@ -848,6 +860,7 @@ extern "C" ppo_status ppo_param_shapes(const ppo_ctx* c, int64_t* shapes_h, int3
                 shapes_h[k++] = GL.out_dim[net][l]; shapes_h[k++] = GL.in_dim[l];
                 shapes_h[k++] = GL.out_dim[net][l]; shapes_h[k++] = 1;
             }
+        if (GL.gauss) { shapes_h[k++] = GL.gauss; shapes_h[k++] = 1; }   // log_std [D], the last tensor
         return PPO_OK;
     }
     if (shapes_h) {
@@ -970,6 +983,7 @@ extern "C" ppo_status ppo_params_init_orthogonal(ppo_ctx* c, int64_t seed) {
                 const double gain = l < GL.n_hidden ? std::sqrt(2.0) : (net == 0 ? 1.0 : 0.01);
                 orthogonal_fill(p.data() + GL.w_off[net][l], GL.out_dim[net][l], GL.in_dim[l], gain, seed, net * GEN_MAX_LAYERS + l);
             }
+        // Gaussian policies: log_std = 0 (sigma = 1), like every bias
         return ppo_params_set_h(c, p.data(), c->L.P);
     }
     for (int net = 0; net < 2; net++) {
@@ -1015,6 +1029,27 @@ static ppo_status gen_policy(ppo_ctx* c, const float* obs, const uint8_t* mask, 
     return PPO_OK;
 }
 
+// gen_policy for a Gaussian context: the actor's forward gives the mean, gauss_heads_kernel the action (f32 [n, D]), its log-prob and the entropy
+static ppo_status gen_policy_gauss(ppo_ctx* c, const float* obs, const float* forced, int64_t n, int64_t step_index, float* action, float* logprob, float* entropy,
+                                   bool greedy = false) {
+    GenericCtx& g = *c->gen;
+    const int D = g.L.gauss;
+    const float* params = B_<float>(c, PPO_BUF_PARAMS);
+    for (int64_t off = 0; off < n; off += g.rows_max) {
+        const int64_t rows = std::min<int64_t>(g.rows_max, n - off);
+        HIPCHK(c, gen_forward(g, params, 1, obs + off * g.L.obs, rows, nullptr, g.dz[0], g.dz[1], g.logits, c->stream));
+        HIPCHK(c, gen_gauss_heads(D, g.logits, params + g.L.logstd_off, forced ? forced + off * D : nullptr, rows, c->cfg.seed, c->cfg.env_offset + off, step_index,
+                                  action ? action + off * D : nullptr, logprob ? logprob + off : nullptr, entropy ? entropy + off : nullptr, c->stream, greedy));
+    }
+    return PPO_OK;
+}
+static inline bool is_gauss(const ppo_ctx* c) { return c->cfg.dist_kind == PPO_DIST_GAUSSIAN; }
+// the integer-action entry points on a Gaussian context, and the _f32 ones on a categorical context
+static ppo_status wrong_action_type(ppo_ctx* c, const char* what, const char* other) {
+    return is_gauss(c) ? fail(c, PPO_ERR_UNSUPPORTED, "%s: this context's policy is PPO_DIST_GAUSSIAN and its actions are f32 [n, D]; call %s", what, other)
+                       : fail(c, PPO_ERR_UNSUPPORTED, "%s: this context's policy is categorical and its actions are i64 [n, H]; call %s", what, other);
+}
+
 extern "C" ppo_status ppo_get_value(ppo_ctx* c, const float* obs, int64_t n, float* value) {
     NEED(c, c && obs && value, "null argument");
     DeviceGuard dev_guard(c);
@@ -1054,14 +1089,28 @@ static ppo_status policy_act_common(ppo_ctx* c, const float* obs, const uint8_t*
 extern "C" ppo_status ppo_policy_act(ppo_ctx* c, const float* obs, const uint8_t* mask, const int64_t* forced_action, int64_t n,
                                      int64_t step_index, int64_t* action, float* logprob, float* entropy, float* value) {
     NEED(c, c && obs, "null argument");
+    if (is_gauss(c)) return wrong_action_type(c, "ppo_policy_act", "ppo_policy_act_f32");
     DeviceGuard dev_guard(c);
     NEED(c, forced_action || action, "sampling needs an action output");
     return policy_act_common(c, obs, mask, forced_action, n, step_index, action, logprob, entropy, value, false);
 }
 
+extern "C" ppo_status ppo_policy_act_f32(ppo_ctx* c, const float* obs, const float* forced_action, int64_t n, int64_t step_index, int32_t greedy,
+                                         float* action, float* logprob, float* entropy, float* value) {
+    NEED(c, c && obs, "null argument");
+    if (!is_gauss(c)) return wrong_action_type(c, "ppo_policy_act_f32", greedy ? "ppo_policy_act_greedy" : "ppo_policy_act");
+    NEED(c, n >= 0, "n < 0");
+    NEED(c, forced_action || action, "sampling needs an action output");
+    DeviceGuard dev_guard(c);
+    ppo_status s = gen_policy_gauss(c, obs, greedy ? nullptr : forced_action, n, step_index, action, logprob, entropy, greedy != 0);
+    if (s == PPO_OK && value) s = gen_values(c, obs, n, value);
+    return s;
+}
+
 extern "C" ppo_status ppo_policy_act_greedy(ppo_ctx* c, const float* obs, const uint8_t* mask, int64_t n, int64_t* action, float* logprob, float* entropy,
                                             float* value) {
     NEED(c, c && obs, "null argument");
+    if (is_gauss(c)) return wrong_action_type(c, "ppo_policy_act_greedy", "ppo_policy_act_f32 with greedy = 1");
     DeviceGuard dev_guard(c);
     NEED(c, action != nullptr, "ppo_policy_act_greedy needs an action output");
     NEED(c, n >= 0, "n < 0");
@@ -1072,6 +1121,12 @@ extern "C" ppo_status ppo_categorical(int32_t dist_kind, const float* logits, co
                                       float* m_logits, float* m_probs, float* log_prob, float* entropy, int64_t* mode, void* stream) {
     if (!logits || n < 0) return PPO_ERR_INVALID;
     return launch_categorical(dist_kind, logits, mask, value, n, A, m_logits, m_probs, log_prob, entropy, mode, (hipStream_t)stream) == hipSuccess ? PPO_OK : PPO_ERR_HIP;
+}
+
+extern "C" ppo_status ppo_gaussian(const float* mean, const float* log_std, const float* value, int64_t n, int32_t D, int64_t seed, int64_t row_offset,
+                                   int64_t step_index, float* sample, float* log_prob, float* entropy, void* stream) {
+    if (!mean || !log_std || n < 0 || D < 1 || D > PPO_MAX_ACT) return PPO_ERR_INVALID;
+    return gen_gauss_heads(D, mean, log_std, value, n, seed, row_offset, step_index, sample, log_prob, entropy, (hipStream_t)stream) == hipSuccess ? PPO_OK : PPO_ERR_HIP;
 }
 
 extern "C" ppo_status ppo_categorical_sample(const float* m_probs, int64_t n, int32_t A, int64_t seed, int64_t row_offset, int64_t step_index,
@@ -1552,7 +1607,7 @@ static ppo_status gen_fwd_bwd(ppo_ctx* c, const int32_t* idx, int64_t M, int slo
         const bool two = !paired && g.bf16 && c->stream2 != nullptr;   // a kernel of one net fills the CUs the other net's kernel is draining
         const bool two_bwd = !paired_bwd && g.bf16 && c->stream2 != nullptr;
         auto gather = [&](const int32_t* rows, int64_t n, hipStream_t st) {
-            return gen_gather(GL, B_<float>(c, PPO_BUF_OBS), B_<int32_t>(c, PPO_BUF_ACTIONS), B_<uint8_t>(c, PPO_BUF_MASKS), B_<float>(c, PPO_BUF_LOGPROBS),
+            return gen_gather(GL, B_<float>(c, PPO_BUF_OBS), B_<int32_t>(c, PPO_BUF_ACTIONS), GL.gauss ? nullptr : B_<uint8_t>(c, PPO_BUF_MASKS), B_<float>(c, PPO_BUF_LOGPROBS),
                               B_<float>(c, PPO_BUF_ADVANTAGES), B_<float>(c, PPO_BUF_RETURNS), B_<float>(c, PPO_BUF_VALUES), rows, n, g, st);
         };
         // the fused kernels read the minibatch's rows in place (generic.hpp: GenericCtx::obs_bf, rows_idx); the observations are rounded once per update --
@@ -1601,7 +1656,10 @@ static ppo_status gen_fwd_bwd(ppo_ctx* c, const int32_t* idx, int64_t M, int slo
             HIPCHK(c, gen_forward(g, params, 0, g.xin, M, g.acts[0], nullptr, nullptr, g.val, s0));
         }
         if (two) HIPCHK(c, join());   // the loss reads the logits and the values
-        if (!head_fused) HIPCHK(c, gen_loss(GL, c->hp, g, M, 1.0 / global_M, global_M, c->cfg.norm_adv ? c->adv_stats + (size_t)slot * PPO_ADV_PARTS : nullptr, c->stream));
+        if (GL.gauss)   // Gaussian policies: their own loss kernel; d(loss)/d(log_std) goes straight to its place behind the actor's layers
+            HIPCHK(c, gen_gauss_loss(GL, c->hp, g, params + GL.logstd_off, M, 1.0 / global_M, global_M, c->cfg.norm_adv ? c->adv_stats + (size_t)slot * PPO_ADV_PARTS : nullptr,
+                                     grads + GL.logstd_off, c->stream));
+        else if (!head_fused) HIPCHK(c, gen_loss(GL, c->hp, g, M, 1.0 / global_M, global_M, c->cfg.norm_adv ? c->adv_stats + (size_t)slot * PPO_ADV_PARTS : nullptr, c->stream));
         // backward: paired too (A/B in one call, configs[4] share: 0.621 ms per optimizer step paired, 0.644 with the backward passes on two streams, 0.683 for
         // round 5's first form -- two streams throughout, gathered copies, four optimizer launches)
         if (two_bwd) HIPCHK(c, fork());
@@ -2145,6 +2203,7 @@ extern "C" ppo_status ppo_host_act(ppo_ctx* c, const uint8_t* mask_h, int64_t* a
     NEED(c, c != nullptr, "null ctx");
     ppo_status s = host_state(c, "ppo_host_act");
     if (s != PPO_OK) return s;
+    if (is_gauss(c)) return wrong_action_type(c, "ppo_host_act", "ppo_host_act_f32");
     if (c->host_n_groups > 0) return fail(c, PPO_ERR_STATE, "ppo_host_act: the open rollout is taken by env groups (ppo_host_group_act)");
     if (c->host_phase == 0) return fail(c, PPO_ERR_STATE, "ppo_host_act: no rollout is open (ppo_host_rollout_begin)");
     if (c->host_feed == 2)
@@ -2180,6 +2239,42 @@ extern "C" ppo_status ppo_host_act(ppo_ctx* c, const uint8_t* mask_h, int64_t* a
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));   // the one wait of a step: the actions
     std::memcpy(action_h, c->host_act, (size_t)N * c->H * sizeof(int64_t));
+    c->host_staged = false;
+    c->host_t = t + 1;
+    c->host_phase = 2;
+    c->host_feed = 1;
+    return PPO_OK;
+}
+
+// ppo_host_act for a Gaussian context (always the generic engine): the same sequence with the mean in the place of the logits and f32 actions [N,D]
+extern "C" ppo_status ppo_host_act_f32(ppo_ctx* c, float* action_h) {
+    NEED(c, c != nullptr, "null ctx");
+    ppo_status s = host_state(c, "ppo_host_act_f32");
+    if (s != PPO_OK) return s;
+    if (!is_gauss(c)) return wrong_action_type(c, "ppo_host_act_f32", "ppo_host_act");
+    if (c->host_phase == 0) return fail(c, PPO_ERR_STATE, "ppo_host_act_f32: no rollout is open (ppo_host_rollout_begin)");
+    if (c->host_feed == 2)
+        return fail(c, PPO_ERR_STATE, "ppo_host_act_f32: the open rollout is device-fed (ppo_dev_act_f32 / ppo_dev_observe); a rollout takes the ppo_host_* or the ppo_dev_* calls, not both");
+    if (c->host_phase == 2) return fail(c, PPO_ERR_STATE, "ppo_host_act_f32: step %d was acted on and not observed (ppo_host_observe)", c->host_t - 1);
+    if (c->host_t >= c->T) return fail(c, PPO_ERR_STATE, "ppo_host_act_f32: all %d steps of the rollout are taken (ppo_host_rollout_end)", c->T);
+    NEED(c, action_h != nullptr, "null argument");
+    DeviceGuard dev_guard(c);
+    GenericCtx& g = *c->gen;
+    const int t = c->host_t, N = c->N, D = g.L.gauss;
+    const size_t action_bytes = (size_t)N * D * sizeof(float);
+    HostStepArgs h = host_args(c, t, true);
+    s = on_staged(c, h);   // observation normalisation: one more launch, in front of the commit
+    if (s != PPO_OK) return s;
+    s = rn_batch(c, h);    // reward normalisation: likewise
+    if (s != PPO_OK) return s;
+    if (h.commit) HIPCHK(c, launch_host_commit(h, N, c->O, c->stream));
+    s = gen_policy_gauss(c, B_<float>(c, PPO_BUF_NEXT_OBS), nullptr, N, c->rollout_steps + t, g.actf, g.step_lp, g.step_en);
+    if (s != PPO_OK) return s;
+    HIPCHK(c, gen_gauss_store_step(g.L, N, B_<float>(c, PPO_BUF_NEXT_OBS), g.actf, g.step_lp, B_<int32_t>(c, PPO_BUF_NEXT_DONE), h.obs_t,
+                                   B_<float>(c, PPO_BUF_ACTIONS) + (size_t)t * N * D, B_<float>(c, PPO_BUF_LOGPROBS) + (size_t)t * N, h.dones_t, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->host_act, g.actf, action_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // the one wait of a step: the actions
+    std::memcpy(action_h, c->host_act, action_bytes);
     c->host_staged = false;
     c->host_t = t + 1;
     c->host_phase = 2;
@@ -2312,6 +2407,8 @@ extern "C" ppo_status ppo_host_rollout_begin_groups(ppo_ctx* c, int32_t n_groups
         return fail(c, PPO_ERR_UNSUPPORTED, "ppo_host_rollout_begin_groups: observation normalisation is on (ppo_obs_norm_enable): groups commit their steps in an "
                                             "order the caller chooses and the running statistics would depend on it, which breaks the groups' promise of "
                                             "interleaving-independent bits; use ppo_host_rollout_begin, or turn the normalisation off");
+    if (is_gauss(c))
+        return fail(c, PPO_ERR_UNSUPPORTED, "ppo_host_rollout_begin_groups: env groups are not built for PPO_DIST_GAUSSIAN contexts; use ppo_host_rollout_begin");
     if (c->rn_mode != 0)
         return fail(c, PPO_ERR_UNSUPPORTED, "ppo_host_rollout_begin_groups: reward normalisation is on (ppo_reward_norm_enable): groups commit their steps in an "
                                             "order the caller chooses and the running statistics would depend on it, which breaks the groups' promise of "
@@ -2661,6 +2758,7 @@ extern "C" ppo_status ppo_dev_act(ppo_ctx* c, const uint8_t* mask, int64_t* acti
     NEED(c, c != nullptr, "null ctx");
     ppo_status s = dev_state(c, "ppo_dev_act");
     if (s != PPO_OK) return s;
+    if (is_gauss(c)) return wrong_action_type(c, "ppo_dev_act", "ppo_dev_act_f32");
     if (c->host_phase == 0) return fail(c, PPO_ERR_STATE, "ppo_dev_act: no rollout is open (ppo_host_rollout_begin)");
     if (c->host_phase == 2) return fail(c, PPO_ERR_STATE, "ppo_dev_act: step %d was acted on and not observed (ppo_dev_observe)", c->host_t - 1);
     if (c->host_t >= c->T) return fail(c, PPO_ERR_STATE, "ppo_dev_act: all %d steps of the rollout are taken (ppo_host_rollout_end)", c->T);
@@ -2684,6 +2782,39 @@ extern "C" ppo_status ppo_dev_act(ppo_ctx* c, const uint8_t* mask, int64_t* acti
         HIPCHK(c, launch_host_act(B_<float>(c, PPO_BUF_PARAMS), c->L, c->cfg.dist_kind, m, N, c->cfg.seed, c->cfg.env_offset, step, h, action,
                                   B_<float>(c, PPO_BUF_LOGPROBS) + (size_t)t * N, c->host_as16, c->error_flag, c->stream));
     }
+    s = dev_handover_out(c, caller);
+    if (s != PPO_OK) return s;
+    if (c->host_feed == 0) {   // the first act: this rollout is device-fed, and its events go to the other list
+        c->host_feed = 2;
+        c->dev_list ^= 1;
+        c->dev_list_used = false;
+    }
+    c->host_t = t + 1;
+    c->host_phase = 2;
+    return PPO_OK;
+}
+
+// ppo_dev_act for a Gaussian context: the f32 actions [N,D] go straight to the caller's device array, and the rollout stores read them there
+extern "C" ppo_status ppo_dev_act_f32(ppo_ctx* c, float* action, void* caller_stream) {
+    NEED(c, c != nullptr, "null ctx");
+    ppo_status s = dev_state(c, "ppo_dev_act_f32");
+    if (s != PPO_OK) return s;
+    if (!is_gauss(c)) return wrong_action_type(c, "ppo_dev_act_f32", "ppo_dev_act");
+    if (c->host_phase == 0) return fail(c, PPO_ERR_STATE, "ppo_dev_act_f32: no rollout is open (ppo_host_rollout_begin)");
+    if (c->host_phase == 2) return fail(c, PPO_ERR_STATE, "ppo_dev_act_f32: step %d was acted on and not observed (ppo_dev_observe)", c->host_t - 1);
+    if (c->host_t >= c->T) return fail(c, PPO_ERR_STATE, "ppo_dev_act_f32: all %d steps of the rollout are taken (ppo_host_rollout_end)", c->T);
+    NEED(c, action != nullptr, "ppo_dev_act_f32: null argument");
+    DeviceGuard dev_guard(c);
+    hipStream_t caller = static_cast<hipStream_t>(caller_stream);
+    const int t = c->host_t, N = c->N;
+    const HostStepArgs h = host_args_rows(c, t, true, 0, false, false);   // commit = 0: ppo_dev_observe committed step t - 1
+    GenericCtx& g = *c->gen;
+    s = dev_handover_in(c, caller);
+    if (s != PPO_OK) return s;
+    s = gen_policy_gauss(c, B_<float>(c, PPO_BUF_NEXT_OBS), nullptr, N, c->rollout_steps + t, action, g.step_lp, g.step_en);
+    if (s != PPO_OK) return s;
+    HIPCHK(c, gen_gauss_store_step(g.L, N, B_<float>(c, PPO_BUF_NEXT_OBS), action, g.step_lp, B_<int32_t>(c, PPO_BUF_NEXT_DONE), h.obs_t,
+                                   B_<float>(c, PPO_BUF_ACTIONS) + (size_t)t * N * g.L.gauss, B_<float>(c, PPO_BUF_LOGPROBS) + (size_t)t * N, h.dones_t, c->stream));
     s = dev_handover_out(c, caller);
     if (s != PPO_OK) return s;
     if (c->host_feed == 0) {   // the first act: this rollout is device-fed, and its events go to the other list

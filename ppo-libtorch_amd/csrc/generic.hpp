@@ -24,10 +24,12 @@ struct GenLayout {
     int net_off[2], net_size[2];
     int P;
     int n_tensors;
-    int tensor_off[4 * GEN_MAX_LAYERS + 1];
+    int tensor_off[4 * GEN_MAX_LAYERS + 2];
+    int gauss;                             // PPO_DIST_GAUSSIAN: the action width D (= act: the actor's output layer is the mean), else 0
+    int logstd_off;                        // ... and the offset of log_std [D], the last tensor (behind the actor's layers)
 };
 
-inline GenLayout make_gen_layout(int obs, int hidden, int n_hidden, int n_heads, const int* head_dims) {
+inline GenLayout make_gen_layout(int obs, int hidden, int n_hidden, int n_heads, const int* head_dims, bool gauss = false) {
     GenLayout L{};
     L.obs = obs; L.hidden = hidden; L.n_hidden = n_hidden; L.n_heads = n_heads; L.n_layers = n_hidden + 1;
     for (int h = 0; h < n_heads; h++) { L.head_dims[h] = head_dims[h]; L.act += head_dims[h]; }
@@ -42,11 +44,14 @@ inline GenLayout make_gen_layout(int obs, int hidden, int n_hidden, int n_heads,
         }
         L.net_size[net] = o - L.net_off[net];
     }
+    if (gauss) { L.gauss = L.act; L.logstd_off = o; L.tensor_off[t++] = o; o += L.act; }
     L.tensor_off[t] = o;
     L.n_tensors = t;
     L.P = o;
     return L;
 }
+// 4-byte words of one action row in PPO_BUF_ACTIONS / row_act: one i32 per head, or the D floats of a Gaussian action
+inline int gen_action_words(const GenLayout& L) { return L.gauss ? L.gauss : L.n_heads; }
 
 // the rollout buffers a step's index list points into (PPO_Discrete.cpp:557-562 flattened, :576-582 indexed)
 struct GenRowSrc { const int32_t* actions; const uint8_t* masks; const float* logprobs; const float* adv; const float* ret; const float* values; };
@@ -71,7 +76,7 @@ struct GenericCtx {
     float* val = nullptr;          // [rows_max]
     float* dval = nullptr;         // [rows_max]
     float* row_f[5] = {};          // gathered per-row scalars: old log-prob, advantage, return, old value; [4] = {adv mean, 1/(std+eps)} then a ones vector
-    int32_t* row_act = nullptr;    // gathered actions [rows_max, n_heads]
+    int32_t* row_act = nullptr;    // gathered actions [rows_max, n_heads] (Gaussian: the f32 bits of [rows_max, D])
     uint8_t* row_mask = nullptr;   // gathered masks [rows_max, act]
     double* loss_part = nullptr;   // [GEN_LOSS_BLOCKS, 8] partial loss sums
     float* wslab = nullptr;        // [GEN_SPLIT + 1][max over layers of out * in + out]: row-chunk partials of one layer's dW | db
@@ -109,6 +114,8 @@ struct GenericCtx {
     int64_t* act64 = nullptr;      // [N, n_heads] actions of the current rollout step (int64, the stand-alone API's type)
     float* step_lp = nullptr;      // [N] log-prob / entropy of the current rollout step
     float* step_en = nullptr;
+    float* actf = nullptr;         // Gaussian: [N, D] actions of the current rollout step
+    float* ls_part = nullptr;      // Gaussian: [GEN_LOSS_BLOCKS][D] block sums of d(loss)/d(log_std) (gauss_loss_kernel -> gauss_logstd_grad_kernel)
 };
 constexpr int GEN_LOSS_BLOCKS = 256;
 constexpr int GEN_DB_CHUNKS = 256, GEN_NORM_PARTS = 16;
@@ -202,3 +209,15 @@ hipError_t gen_synthetic_step(const GenLayout& L, int N, int64_t seed, int64_t e
 hipError_t gen_fold_rewards(const float* value, const int32_t* index, int64_t K, float gamma, float* rewards, hipStream_t s);
 hipError_t gen_store_step(const GenLayout& L, int N, const float* obs, const uint8_t* mask, const int64_t* act64, const float* lp, const int32_t* done_prev,
                           float* obs_t, uint8_t* mask_t, int32_t* act_t, float* lp_t, float* dones_t, hipStream_t s);
+
+// kernels_gauss.hip: diagonal-Gaussian policies (PPO_DIST_GAUSSIAN): mean = the actor's output [n, D], log_std [D] a parameter
+// sample / log-prob / entropy per row; forced f32 [n, D] or null (draw: Philox keyed (seed; row_offset + row, step_index, dimension)); greedy: action = mean
+hipError_t gen_gauss_heads(int D, const float* mean, const float* log_std, const float* forced, int64_t n, int64_t seed, int64_t row_offset, int64_t step_index,
+                           float* action, float* logprob, float* entropy, hipStream_t s, bool greedy = false);
+// gen_loss for a Gaussian context (f32 storage): d(loss)/d(mean) -> g.dlogits, d(loss)/d(value) -> g.dval, the five loss partials -> g.loss_part, and
+// d(loss)/d(log_std) -> grad_logstd [D] (block sums in g.ls_part added in block order by a second launch: no atomics)
+hipError_t gen_gauss_loss(const GenLayout& L, const LossParams& hp, const GenericCtx& g, const float* log_std, int64_t M, double inv_global_M, double global_M,
+                          const AdvStat* adv_stat, float* grad_logstd, hipStream_t s);
+// gen_store_step with f32 actions [N, D] (no masks)
+hipError_t gen_gauss_store_step(const GenLayout& L, int N, const float* obs, const float* actf, const float* lp, const int32_t* done_prev, float* obs_t,
+                                float* act_t, float* lp_t, float* dones_t, hipStream_t s);

@@ -76,7 +76,8 @@ __global__ __launch_bounds__(256) void gather_kernel(GenLayout L, const float* _
     } else {
         for (int o = lane; o < L.obs; o += 64) xin[r * L.obs + o] = obs[src * L.obs + o];
     }
-    if (lane < L.n_heads) row_act[r * L.n_heads + lane] = actions[src * L.n_heads + lane];
+    const int aw = L.gauss ? L.gauss : L.n_heads;   // 4-byte words of an action row (Gaussian: the D floats, moved as their bits)
+    if (lane < aw) row_act[r * aw + lane] = actions[src * aw + lane];
     if (masks && lane < L.act) row_mask[r * L.act + lane] = masks[src * L.act + lane];
     if (lane == 0) { f0[r] = logprobs[src]; f1[r] = adv[src]; f2[r] = ret[src]; f3[r] = values[src]; }
 }
@@ -616,7 +617,7 @@ __global__ __launch_bounds__(256) void gen_adamw_kernel(float* __restrict__ para
                                                         LossParams hp, int world, int do_step, StepStats* stats_out, double* clipfrac_accum) {
     // total norm: thread t adds tensor t's partial sums (all its loads in flight), thread 0 adds the tensors -- the same sums in the same order
     // as one thread doing all of it (which every thread used to do: 320 dependent loads in front of the element-wise step)
-    __shared__ double s_n2[4 * GEN_MAX_LAYERS];
+    __shared__ double s_n2[4 * GEN_MAX_LAYERS + 1];
     __shared__ float s_total;
     if ((int)threadIdx.x < L.n_tensors) {
         double part[GEN_NORM_PARTS];

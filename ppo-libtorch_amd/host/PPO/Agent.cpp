@@ -95,14 +95,15 @@ void Agent::setParameters(const std::vector<float>& flat) {
 void Agent::printAgent() {
     static const char* names[] = { "m_Critic.criticInputLayer", "m_Critic.criticMiddleLayer", "m_Critic.criticOutputLayer",
                                    "m_Actor.actorInputLayer", "m_Actor.actorMiddleLayer", "m_Actor.actorOutputLayer" };
-    int64_t shapes[24];
+    int64_t shapes[26];   // twelve tensors, and a Gaussian policy's log_std
     int32_t nt = 0;
     ppo::check(ppo_param_shapes(m_ctx, shapes, &nt), m_ctx, "param shapes");
     const std::vector<float> p = parameters();
     size_t off = 0;
     for (int t = 0; t < nt; t++) {
         const int64_t rows = shapes[2 * t], cols = shapes[2 * t + 1];
-        std::cout << names[t / 2] << (t % 2 ? ".bias" : ".weight") << " [" << rows << (t % 2 ? "" : " x " + std::to_string(cols)) << "]\n";
+        if (t == 12) std::cout << "m_logStd [" << rows << "]\n";
+        else std::cout << names[t / 2] << (t % 2 ? ".bias" : ".weight") << " [" << rows << (t % 2 ? "" : " x " + std::to_string(cols)) << "]\n";
         for (int64_t i = 0; i < rows * cols && i < 8; i++) std::cout << " " << p[off + static_cast<size_t>(i)];
         std::cout << (rows * cols > 8 ? " ...\n" : "\n");
         off += static_cast<size_t>(rows * cols);

@@ -66,6 +66,7 @@ void PPOAlgorithm::getArgs() {
         auto B = [&](const char* sec, const char* key, bool& dst) { if (auto v = cfg.boolean(sec, key)) { dst = *v; std::cout << "Using config file " << key << " = " << (dst ? "true" : "false") << std::endl; } };
         I("environment", "obs_size", m_obs_size);
         I("environment", "action_size", m_action_size);
+        if (m_dist_kind == PPO_DIST_GAUSSIAN) I("environment", "action_dim", m_action_size);   // extension key (PPO_HostEnvBox): the width D of a Box action
         if (m_env_kind == PPO_ENV_MOUNTAINCAR) {   // PPO_MultiDiscrete only, between action_size and max_episode_steps (PPO_MultiDiscrete.cpp:136-144)
             F("environment", "action_high", m_action_high);
             F("environment", "action_low", m_action_low);
@@ -153,7 +154,7 @@ void PPOAlgorithm::construct() {
 
     const int64_t T = m_num_steps, N = m_num_envs;
     m_obs = bufferView(PPO_BUF_OBS, { T, N, m_obs_size }, DType::f32);
-    m_actions = bufferView(PPO_BUF_ACTIONS, { T, N, 1 }, DType::i32);
+    m_actions = m_dist_kind == PPO_DIST_GAUSSIAN ? bufferView(PPO_BUF_ACTIONS, { T, N, m_action_size }, DType::f32) : bufferView(PPO_BUF_ACTIONS, { T, N, 1 }, DType::i32);
     m_logprobs = bufferView(PPO_BUF_LOGPROBS, { T, N }, DType::f32);
     m_rewards = bufferView(PPO_BUF_REWARDS, { T, N }, DType::f32);
     m_dones = bufferView(PPO_BUF_DONES, { T, N }, DType::f32);
@@ -344,9 +345,10 @@ void PPOAlgorithm::saveCheckpoint(const std::string& agentFile, const std::strin
             ppo::check(ppo_reward_norm_get_h(m_ctx, &f.mean, &f.var, &f.count, nullptr, 0), m_ctx, "reward norm");
             f.write(RewardNormFile::pathFor(agentFile));
         }
-        ppo::pt::writeAgent(ta, m_obs_size, 64, m_action_size, p, fs::path(agentFile).stem().string());
+        const bool log_std = m_dist_kind == PPO_DIST_GAUSSIAN;   // a Gaussian policy's thirteenth tensor
+        ppo::pt::writeAgent(ta, m_obs_size, 64, m_action_size, p, fs::path(agentFile).stem().string(), log_std);
         ppo::pt::writeOptimizer(to, m_obs_size, 64, m_action_size, m, v, step, st.learning_rate, static_cast<double>(1e-5f), 0.01,
-                                     fs::path(optimizerFile).stem().string());
+                                     fs::path(optimizerFile).stem().string(), log_std);
     } catch (const std::exception&) {
         std::error_code ec;
         fs::remove(ta, ec); fs::remove(to, ec);
@@ -450,7 +452,7 @@ void PPOAlgorithm::loadPolicyFromCheckpoint() {
         return;
     }
     const int64_t P = ppo_param_count(m_ctx);
-    const auto shapes = ppo::pt::agentShapes(m_obs_size, 64, m_action_size);
+    const auto shapes = ppo::pt::agentShapes(m_obs_size, 64, m_action_size, m_dist_kind == PPO_DIST_GAUSSIAN);
     const std::string a = newestFile(modelDir);
     if (a.empty()) {
         std::cout << "No previous model checkpoint found at " << modelDir << ", initializing new agent!" << std::endl;

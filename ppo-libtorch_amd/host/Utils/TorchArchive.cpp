@@ -424,9 +424,11 @@ bool isTorchArchive(const std::string& path) {
     return f && m[0] == 'P' && m[1] == 'K' && m[2] == 3 && m[3] == 4;
 }
 
-std::vector<std::vector<int64_t>> agentShapes(int64_t obs, int64_t hidden, int64_t act) {
-    return { { hidden, obs }, { hidden }, { hidden, hidden }, { hidden }, { 1, hidden }, { 1 },
-             { hidden, obs }, { hidden }, { hidden, hidden }, { hidden }, { act, hidden }, { act } };
+std::vector<std::vector<int64_t>> agentShapes(int64_t obs, int64_t hidden, int64_t act, bool log_std) {
+    std::vector<std::vector<int64_t>> s = { { hidden, obs }, { hidden }, { hidden, hidden }, { hidden }, { 1, hidden }, { 1 },
+                                            { hidden, obs }, { hidden }, { hidden, hidden }, { hidden }, { act, hidden }, { act } };
+    if (log_std) s.push_back({ act });
+    return s;
 }
 
 AgentFile readAgent(const std::string& path) {
@@ -471,8 +473,8 @@ OptimizerFile readOptimizer(const std::string& path) {
     return out;
 }
 
-void writeAgent(const std::string& path, int64_t obs, int64_t hidden, int64_t act, const std::vector<float>& flat, const std::string& stem_in) {
-    const auto shapes = agentShapes(obs, hidden, act);
+void writeAgent(const std::string& path, int64_t obs, int64_t hidden, int64_t act, const std::vector<float>& flat, const std::string& stem_in, bool log_std) {
+    const auto shapes = agentShapes(obs, hidden, act, log_std);
     int64_t total = 0;
     for (const auto& s : shapes) { int64_t n = 1; for (int64_t d : s) n *= d; total += n; }
     if ((int64_t)flat.size() != total) throw std::runtime_error("writeAgent: " + std::to_string(flat.size()) + " values for " + std::to_string(total) + " parameters");
@@ -522,8 +524,12 @@ void writeAgent(const std::string& path, int64_t obs, int64_t hidden, int64_t ac
         p.endObject();
         sources.emplace_back(nc, classSource({}, net_attrs));
     }
+    if (log_std) {   // the Gaussian policy's scale: a parameter of the root module, behind the two nets
+        root_attrs.emplace_back("m_logStd", "Tensor");
+        p.str("m_logStd"); p.tensor(std::to_string(next_tensor), shapes[(size_t)next_tensor], true); next_tensor++;
+    }
     p.endObject();
-    sources.emplace_back(root, classSource({}, root_attrs));
+    sources.emplace_back(root, classSource(log_std ? std::vector<std::string>{ "m_logStd" } : std::vector<std::string>{}, root_attrs));
     zip.add(stem + "/data.pkl", p.finish());
     for (int k = 0; k < next_class; k++)
         for (const auto& s : sources) if (s.first == k) zip.add(codePath(stem, k), s.second);
@@ -531,8 +537,8 @@ void writeAgent(const std::string& path, int64_t obs, int64_t hidden, int64_t ac
 }
 
 void writeOptimizer(const std::string& path, int64_t obs, int64_t hidden, int64_t act, const std::vector<float>& exp_avg,
-                    const std::vector<float>& exp_avg_sq, int64_t step, double lr, double eps, double weight_decay, const std::string& stem_in) {
-    const auto shapes = agentShapes(obs, hidden, act);
+                    const std::vector<float>& exp_avg_sq, int64_t step, double lr, double eps, double weight_decay, const std::string& stem_in, bool log_std) {
+    const auto shapes = agentShapes(obs, hidden, act, log_std);
     int64_t total = 0;
     for (const auto& s : shapes) { int64_t n = 1; for (int64_t d : s) n *= d; total += n; }
     if ((int64_t)exp_avg.size() != total || (int64_t)exp_avg_sq.size() != total) throw std::runtime_error("writeOptimizer: moment vectors do not match the parameter count");

@@ -46,13 +46,18 @@ OptimizerFile readOptimizer(const std::string& path);
 // The reference's Agent (Agent.cpp:25-66): m_Critic { criticInputLayer, Tanh1, criticMiddleLayer, Tanh2, criticOutputLayer } then m_Actor
 // { actorInputLayer, Tanh1, actorMiddleLayer, Tanh2, actorOutputLayer }; `flat` holds weight, bias of the six Linear layers in that order.
 // `stem` names the archive's internal directory (LibTorch uses the file's name without extension; empty: derived from `path`).
-void writeAgent(const std::string& path, int64_t obs, int64_t hidden, int64_t act, const std::vector<float>& flat, const std::string& stem = "");
+// log_std (a diagonal-Gaussian policy, PPO_DIST_GAUSSIAN): one more parameter m_logStd [act] behind m_Actor, last in `flat` -- this build's own extension of
+// the layout; no exchange of such files with the reference is claimed.
+void writeAgent(const std::string& path, int64_t obs, int64_t hidden, int64_t act, const std::vector<float>& flat, const std::string& stem = "",
+                bool log_std = false);
 // AdamW state for those twelve parameters, every one at the same step count
 void writeOptimizer(const std::string& path, int64_t obs, int64_t hidden, int64_t act, const std::vector<float>& exp_avg,
-                    const std::vector<float>& exp_avg_sq, int64_t step, double lr, double eps, double weight_decay, const std::string& stem = "");
+                    const std::vector<float>& exp_avg_sq, int64_t step, double lr, double eps, double weight_decay, const std::string& stem = "",
+                    bool log_std = false);
 
 // element counts of the twelve parameters in file order: {hidden*obs, hidden, hidden*hidden, hidden, 1*hidden, 1, hidden*obs, hidden, hidden*hidden, hidden, act*hidden, act}
-std::vector<std::vector<int64_t>> agentShapes(int64_t obs, int64_t hidden, int64_t act);
+// (log_std: and {act} behind them)
+std::vector<std::vector<int64_t>> agentShapes(int64_t obs, int64_t hidden, int64_t act, bool log_std = false);
 
 }  // namespace pt
 }  // namespace ppo

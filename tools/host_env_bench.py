@@ -12,6 +12,10 @@
                           printed as env_us) -- while the main thread makes the policy call of the next group.  Prints, for --envs N and num_steps 128, the
                           ungrouped round trip R (X = 0), and the time of one iteration (rollout + update, stream idle) ungrouped and with each G,
                           at X = 0 and at X = --env-cost-us (default: R), next to the ideal gain (E + R) / max(E, R) with E the measured env_us.
+
+  --dist gaussian         a diagonal-Gaussian context (PPO_DIST_GAUSSIAN, D = 6) beside the categorical context of the same shape on the same generic
+                          engine (obs 11, 2 x 64, one head of 6; --envs N, 64 steps, 4 epochs x 4 minibatches) in ONE process: per-step act + observe
+                          time and the ppo_host_rollout_end time of each (zero-cost env).
 """
 import argparse
 import concurrent.futures
@@ -130,6 +134,43 @@ def device_sps(N=4096, T=128, iters=5):
     return sps
 
 
+def dist_bench(N, T=64, rounds=3, obs=11, width=6):
+    """(act + observe us per step, rollout_end ms) of a Gaussian and of a categorical generic context of the same shape, interleaved round by round"""
+    L = P.binding.lib()
+    rng = np.random.default_rng(0)
+    o = np.ascontiguousarray(rng.uniform(-1, 1, (N, obs)).astype(np.float32))
+    rew, done = np.ones(N, np.float32), (rng.random(N) < 0.02).astype(np.int32)
+    args = [x.ctypes.data_as(C.c_void_p) for x in (o, rew, done)]
+    ctxs, acts = {}, {}
+    for name, dist in (("categorical", P.DIST_CATEGORICAL), ("gaussian", P.DIST_GAUSSIAN)):
+        c = P.Context(P.make_config(env_kind=P.ENV_HOST, dist_kind=dist, obs_size=obs, head_dims=(width,), num_envs=N, num_steps=T, num_minibatches=4,
+                                    update_epochs=4, seed=1, total_timesteps=N * T * (rounds + 2)))
+        c.init_orthogonal(1)
+        c.host_env_reset(o)
+        ctxs[name] = c
+        acts[name] = np.empty((N, width), np.float32) if dist == P.DIST_GAUSSIAN else np.empty((N, 1), np.int64)
+    out = {name: {"act_us": None, "end_ms": None} for name in ctxs}
+    for r in range(rounds + 1):
+        for name, c in ctxs.items():
+            a = acts[name].ctypes.data_as(C.c_void_p)
+            c.host_rollout_begin()
+            t0 = time.perf_counter()
+            for _ in range(T):
+                P.binding._check(L.ppo_host_act_f32(c.h, a) if name == "gaussian" else L.ppo_host_act(c.h, None, a), c.h)
+                P.binding._check(L.ppo_host_observe(c.h, args[0], args[1], args[2], None, None), c.h)
+            t1 = time.perf_counter()
+            c.host_rollout_end()
+            c.sync()
+            t2 = time.perf_counter()
+            if r > 0:
+                us, ms = (t1 - t0) / T * 1e6, (t2 - t1) * 1e3
+                out[name]["act_us"] = us if out[name]["act_us"] is None else min(out[name]["act_us"], us)
+                out[name]["end_ms"] = ms if out[name]["end_ms"] is None else min(out[name]["end_ms"], ms)
+    for c in ctxs.values():
+        c.close()
+    return {"N": N, "T": T, "obs": obs, "width": width, **out}
+
+
 class WorkerEnv:
     """The caller's envs on a thread of their own: step(n) occupies that thread for cost_us * n / N and returns a future."""
 
@@ -236,7 +277,11 @@ def main():
     ap.add_argument("--groups", type=int, nargs="+", default=None, help="env groups to compare with the ungrouped calls, e.g. --groups 2 4")
     ap.add_argument("--env-cost-us", type=float, default=None, help="cost of one step of all N envs on the worker thread (default: the measured round trip)")
     ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--dist", choices=["gaussian"], default=None, help="a Gaussian context beside the categorical generic context of the same shape")
     args = ap.parse_args()
+    if args.dist:
+        print(json.dumps({"dist_bench": dist_bench(args.envs)}))
+        return
     if args.groups:
         print(json.dumps({"groups_bench": groups_bench(args.envs, args.groups, args.env_cost_us)}))
         return
