@@ -1,7 +1,8 @@
 """A float64 restatement of the generic engine's minibatch step (MLP bodies, categorical / masked categorical heads, PPO loss), written with torch autograd
 on the CPU -- TEST INFRASTRUCTURE, NOT PRODUCT CODE, and not a test.  Written from the formulas (PPO_Discrete.cpp:585-631 as oracle/ppo_oracle.c restates
 them) and held to the C oracle's f32 arithmetic by tests/test_grad_oracle_cpu.py; the GPU tests (tests/test_gpu_generic_grads.py) compare the HIP kernels'
-gradient with it TENSOR BY TENSOR, each against its own largest element.
+gradient with it TENSOR BY TENSOR, each against its own largest element.  The same oracle holds the 2 x 64 kernels of caller-stepped contexts
+(REF_SHAPES below, tests/test_gpu_ref_shape_grads.py); stand_in_batch makes their batch without the library, since such a context has no env to roll out.
 
 Every input is the f32 number the library sees, widened to float64; nothing is rounded afterwards.  What the C oracle does in f32 and this file in float64:
 the layer products, tanh, log-softmax, exp of the log-ratio, the advantage normalisation, the clips.  The branch conditions are the same comparisons
@@ -9,6 +10,8 @@ the layer products, tanh, log-softmax, exp of the log-ratio, the advantage norma
 """
 import numpy as np
 import torch
+
+import oracle as O
 
 F64 = torch.float64
 FLT_MIN = float(np.finfo(np.float32).tiny)
@@ -139,6 +142,19 @@ def f32_tensor_bars(d_ref):
     return np.full(d_ref.shape, 1e-4) if K_F32 is None else np.minimum(1e-4, K_F32 * np.maximum(d_ref, 1e-7))
 
 
+# The 2 x 64 kernels (tests/test_gpu_ref_shape_grads.py) get a constant of their own: the matrix-core update kernels cut every f32 operand into fp16 terms, so
+# their distance from float64 is not the generic engine's.  K_REF = twice the worst d_hip / d_ref measured on an MI355X over REF_SHAPES, their flags and lists
+# (table in DESIGN.md, "Per-tensor gradient checks").  None = not measured: the 1e-4 cap alone.
+# Measured: worst ratio 7.28 (obs 4 (2,) under PPO_KERNEL_UPDATE_VECTOR, M = 33, the critic's output bias, where d_ref sits on the 1e-7 floor); worst on the
+# matrix cores 4.72 (the wave-specialised kernel, same shape).
+K_REF = 14.6
+
+
+def ref_tensor_bars(d_ref):
+    d_ref = np.asarray(d_ref, np.float64)
+    return np.full(d_ref.shape, 1e-4) if K_REF is None else np.minimum(1e-4, K_REF * np.maximum(d_ref, 1e-7))
+
+
 def clipped_norm(grad, shapes):
     """clip_grad_norm_'s total norm: the L2 norm of the per-tensor L2 norms (= the L2 norm of the flat gradient), in float64"""
     return float(np.sqrt(sum(float((v.astype(np.float64) ** 2).sum()) for _, _, _, _, v in split(np.asarray(grad), shapes))))
@@ -204,3 +220,113 @@ def single_action_rows(masks, heads):
         one |= masks[:, off:off + w].sum(1) == 1
         off += w
     return float(one.mean())
+
+
+# -------------------------------------------------------------------------------------------------------------------------------------------------------
+# The 2 x 64 kernels' shapes (tests/test_gpu_ref_shape_grads.py): the reference's network (hidden 64 x 2, f32) on a caller-stepped context, one row per
+# dispatch case of api.hip.  flags = the ppo_config.kernel_flags values each shape runs under.  lists: 576 = whole 32-row tiles, 225 = a one-row last tile,
+# 33 = one tile plus a row, 2 = fewer rows than a tile.  Each shape has its own seed, chosen so that the conditions tests/test_grad_oracle_cpu.py asserts hold
+# (the C oracle alone inside every bar of the GPU test, every tensor's float64 gradient non-zero on every list).
+# -------------------------------------------------------------------------------------------------------------------------------------------------------
+VECTOR, ONE_WAVE = 2, 4      # PPO_KERNEL_UPDATE_VECTOR, PPO_KERNEL_UPDATE_ONE_WAVE (include/ppo_hip.h)
+REF_LISTS = (576, 225, 33, 2)
+
+
+def _ref(obs, heads, masked, flags, seed, **kw):
+    return dict(obs=obs, hidden=64, n_hidden=2, heads=tuple(heads), masked=masked, dtype=0, lists=REF_LISTS, seed=seed, flags=tuple(flags), **kw)
+
+
+REF_SHAPES = {
+    "ref cartpole obs4 (2,)":            _ref(4, (2,), False, (0, ONE_WAVE, VECTOR), seed=31),
+    "ref mountaincar obs2 (3,) masked":  _ref(2, (3,), True, (0, ONE_WAVE, VECTOR), seed=32),
+    "ref obs4 (4,)":                     _ref(4, (4,), False, (0, VECTOR), seed=33),
+    "ref obs4 (2,2) masked":             _ref(4, (2, 2), True, (0, VECTOR), seed=34),
+    "ref obs4 (2,) masked":              _ref(4, (2,), True, (0,), seed=35),
+    "ref obs2 (3,)":                     _ref(2, (3,), False, (0, VECTOR), seed=36),
+    "ref obs2 (2,1,1) masked":           _ref(2, (2, 1, 1), True, (0, VECTOR), seed=37),
+    "ref obs4 (3,) plain value loss, raw advantages":
+                                         _ref(4, (3,), False, (0, VECTOR), seed=38, clip_vloss=False, norm_adv=False),
+    "ref obs4 (3,2)":                    _ref(4, (3, 2), False, (0,), seed=39),
+    "ref obs2 (3,3,3,2) masked":         _ref(2, (3, 3, 3, 2), True, (0,), seed=40),
+    "ref obs8 (4,)":                     _ref(8, (4,), False, (0,), seed=41),
+    "ref obs8 eight heads of 4 masked":  _ref(8, (4,) * 8, True, (0,), seed=42),
+    "ref obs8 (2,) masked, plain value loss, raw advantages":
+                                         _ref(8, (2,), True, (0,), seed=43, clip_vloss=False, norm_adv=False),
+}
+ALL_SHAPES = dict(SHAPES, **REF_SHAPES)
+
+
+def choice_rows(masks, heads):
+    """per row: some head of width >= 2 has at least two allowed actions (the row can carry an actor gradient)"""
+    masks = np.asarray(masks)
+    any_choice = np.zeros(masks.shape[0], bool)
+    off = 0
+    for w in heads:
+        if w >= 2:
+            any_choice |= masks[:, off:off + w].sum(1) >= 2
+        off += w
+    return any_choice
+
+
+def ref_index_lists(s, b):
+    """index_lists for REF_SHAPES (b = stand_in_batch(s)), with two more conditions on a two-row list:
+      norm_adv on: the two rows' raw advantages differ by at least 0.5.  (A - mean) / std of two nearly equal advantages is a cancellation: the f32 C oracle
+        alone then sits 1e-4 from float64, above the GPU test's bars before any kernel ran.
+      masked: the row inside both clips has a head with at least two allowed actions.  At narrow head lists most rows have one allowed action in every
+        head; two such rows leave every actor tensor's gradient at zero, and a zero gradient hides any error.
+    The pair is the first (inside, outside) in the permutation's order that satisfies them."""
+    rng = np.random.default_rng(1000 + s["seed"])
+    d_logp, d_values = np.abs(np.asarray(b["d_logp"]).reshape(-1)), np.abs(np.asarray(b["d_values"]).reshape(-1))
+    adv = np.asarray(b["adv"], np.float64).reshape(-1)
+    can_move = choice_rows(b["masks"], s["heads"]) if s["masked"] else np.ones(adv.size, bool)
+    norm_adv = bool(s.get("norm_adv", True))
+    out = []
+    for M in s["lists"]:
+        perm = rng.permutation(d_logp.size)
+        if M == 2:
+            inside = perm[(d_logp[perm] < 0.1) & (d_values[perm] < 0.1) & can_move[perm]]
+            outside = perm[(d_logp[perm] > 0.3) & (d_values[perm] > 0.3)]
+            pairs = ((i, o) for i in inside for o in outside if not norm_adv or abs(adv[i] - adv[o]) >= 0.5)
+            perm = np.array(next(pairs))
+        out.append(perm[:M].astype(np.int32))
+    return out
+
+
+def stand_in_batch(s):
+    """Parameters and one rollout's buffers for a shape, made without the library: normal weights at the scale of the orthogonal init (sqrt(2 / in) per element
+    in the hidden layers, 1 / sqrt(in) in the critic's head, 0.3 / sqrt(in) in the actor's: its 0.01 gain x 30 as the GPU tests scale it), 0.02 noise on
+    every weight and bias."""
+    obs_dim, hidden, n_hidden, heads, masked = s["obs"], s["hidden"], s["n_hidden"], s["heads"], s["masked"]
+    N, T, seed = N_ENVS, N_STEPS, s["seed"]
+    net = O.Net.make(obs_dim, list(heads), hidden=hidden, n_hidden=n_hidden, dist_kind=O.DIST_MASKED if masked else O.DIST_CATEGORICAL, dtype=0)
+    shp = O.param_shapes(net)
+    rng = np.random.default_rng(seed)
+    parts = []
+    for i, net_i, layer, kind, v in split(np.zeros(O.param_count(net)), shp):
+        if kind == "w":
+            gain = np.sqrt(2.0) if layer < n_hidden else (1.0 if net_i == 0 else 0.3)
+            parts.append(gain / np.sqrt(v.shape[1]) * rng.standard_normal(v.shape) + 0.02 * rng.standard_normal(v.shape))
+        else:
+            parts.append(0.02 * rng.standard_normal(v.shape))
+    params = np.concatenate([p.ravel() for p in parts]).astype(np.float32)
+    envs = np.arange(N)
+    obs = np.stack([O.synthetic_obs(seed, envs, t, obs_dim) for t in range(T)])
+    masks = np.stack([O.synthetic_mask(seed, envs, t, list(heads)) for t in range(T)]) if masked else None
+    actions, logp, values = np.empty((T, N, len(heads)), np.int64), np.empty((T, N), np.float32), np.empty((T, N), np.float32)
+    rewards, dones = np.empty((T, N), np.float32), np.zeros((T, N), np.float32)
+    for t in range(T):
+        actions[t], logp[t], _, values[t] = O.act(net, params, obs[t], seed, t, 0, masks[t] if masked else None)
+        rewards[t], d = O.synthetic_transition(seed, envs, t)
+        if t + 1 < T:
+            dones[t + 1] = d
+    next_done = d.astype(np.int32)
+    next_value = O.get_value(net, params, O.synthetic_obs(seed, envs, T, obs_dim))
+    adv, ret = O.gae(rewards, values, dones, next_value, next_done, BASE_HP["gamma"], BASE_HP["gae_lambda"])
+    B = T * N
+    # teacher-forced evaluation equals what the sampler reported (the stand-in data is a rollout of these parameters: ratio = 1 before the perturbation)
+    lp_e, _, v_e = O.evaluate(net, params, obs.reshape(B, obs_dim), actions.reshape(B, -1), masks.reshape(B, -1) if masked else None)
+    assert np.abs(lp_e - logp.reshape(B)).max() <= 1e-5 and np.abs(v_e - values.reshape(B)).max() <= 1e-5
+    logp2, values2 = make_off_policy(np.random.default_rng(seed + 1), logp, values)
+    return dict(net=net, shapes=shp, params=params, d_logp=(logp2 - logp).reshape(B), d_values=(values2 - values).reshape(B), obs=obs.reshape(B, obs_dim),
+                masks=masks.reshape(B, -1) if masked else None,
+                actions=actions.reshape(B, -1), logp=logp2.reshape(B), values=values2.reshape(B), adv=adv.reshape(B), ret=ret.reshape(B))
