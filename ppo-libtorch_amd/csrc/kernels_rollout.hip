@@ -475,7 +475,10 @@ __device__ __forceinline__ r16_f32x4 r16_mfma(const r16_u32x4 a, const r16_u32x4
 __device__ __forceinline__ void r16_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 template <int ENV, int DIST, int OBS, int EXACTA>
-__global__ __launch_bounds__(384, 1) void rollout16_kernel(RolloutArgs a) {
+__global__ __launch_bounds__(384, 1) void rollout16_kernel(const float* __restrict__ params, float* env_state, int32_t* ep_len_p, float* ep_rew_p, int32_t* reset_count,
+                                                          int32_t* next_done, int N, int n_tiles, RolloutArgs a) {
+    // the leading scalars (6 pointers + 2 ints = 14 dwords) are preloaded into SGPRs at wave launch (csrc/Makefile: kernel-argument preloading): the operands
+    // of the prologue's loads -- weights and env state -- and the grid size, which gridDim would fetch from the implicit arguments
     __shared__ __attribute__((aligned(16))) uint32_t s_h1[2][2][2][64][4];      // [step parity][term][chunk c][lane][wave 2c: 2 dwords | wave 2c + 1: 2 dwords]
     __shared__ __attribute__((aligned(16))) float s_part[2][EXACTA][16][4];     // [step parity][logit][env][policy wave]: each wave's 16-unit share of a logit
     __shared__ float s_x[2][4][16];                                             // [step parity][obs component][env]: the observation the policy sees next
@@ -487,17 +490,16 @@ __global__ __launch_bounds__(384, 1) void rollout16_kernel(RolloutArgs a) {
     const int mw = wave & 3;            // the env wave loads (and ignores) block 0's weights: every index stays in bounds
     int tile = blockIdx.x;
     {   // contiguous env ranges per XCD, as in rollout_kernel
-        const int nb = gridDim.x, q = nb / 8, r = nb % 8, x = blockIdx.x % 8, i = blockIdx.x / 8;
+        const int nb = n_tiles, q = nb / 8, r = nb % 8, x = blockIdx.x % 8, i = blockIdx.x / 8;
         tile = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
     }
-    const int N = a.N;
     int env = 16 * tile + e;
     const bool live = env < N;          // the last tile may be ragged: its idle columns compute on env N - 1 and store nothing
     if (!live) env = N - 1;
     const NetLayout& L = a.L;
     constexpr int H = 1, A = EXACTA;
     const int64_t env_global = a.env_offset + env;
-    const float* __restrict__ P = a.params;
+    const float* __restrict__ P = params;
 
     // ---- a policy wave's block of the actor's weights as MFMA A operands, once per launch ----
     // layer 1 (16x16x4 f32): lane (i = e, k = kg) holds W1[16 w + i][k]
@@ -547,11 +549,11 @@ __global__ __launch_bounds__(384, 1) void rollout16_kernel(RolloutArgs a) {
     // ---- the env wave's state (lanes kg = 0 .. 3 of an env hold identical copies; lane kg = 0 stores) ----
     float st[OBS];
 #pragma unroll
-    for (int k = 0; k < OBS; k++) st[k] = a.env_state[(size_t)k * N + env];
-    int ep_len = a.ep_len[env];
-    float ep_rew = a.ep_rew[env];
-    int resets = a.reset_count[env];
-    int done = a.next_done[env];
+    for (int k = 0; k < OBS; k++) st[k] = env_state[(size_t)k * N + env];
+    int ep_len = ep_len_p[env];
+    float ep_rew = ep_rew_p[env];
+    int resets = reset_count[env];
+    int done = next_done[env];
     uint4 philox_words = make_uint4(0u, 0u, 0u, 0u);
     bool philox_valid = false;
     const bool writer = live && envw;
@@ -796,17 +798,17 @@ __global__ __launch_bounds__(384, 1) void rollout16_kernel(RolloutArgs a) {
                ph[0] / a.T, ph[1] / a.T, ph[2] / a.T, ph[3] / a.T, ph[4] / a.T, ph[5] / a.T, a.T);
 #endif
     if (writer && kg == 0) {
-        a.next_done[env] = done;
-        a.ep_len[env] = ep_len;
-        a.ep_rew[env] = ep_rew;
-        a.reset_count[env] = resets;
+        next_done[env] = done;
+        ep_len_p[env] = ep_len;
+        ep_rew_p[env] = ep_rew;
+        reset_count[env] = resets;
     }
     if (writer && kg < OBS) {
         float xk = 0.0f;
 #pragma unroll
         for (int k = 0; k < OBS; k++) xk = kg == k ? st[k] : xk;
         a.next_obs[(size_t)env * OBS + kg] = xk;
-        a.env_state[(size_t)kg * N + env] = xk;
+        env_state[(size_t)kg * N + env] = xk;
     }
 }
 
@@ -1456,7 +1458,8 @@ hipError_t launch_rollout(const RolloutArgs& a, hipStream_t s) {
 #define PPO_ROLLOUT_FAST(ENV, DIST, OBS, AA)                                                                                  \
     do {                                                                                                                      \
         if (a.vector_kernel) hipLaunchKernelGGL((rollout2_kernel<ENV, DIST, OBS, AA>), grid2, block, 0, s, a);                \
-        else hipLaunchKernelGGL((rollout16_kernel<ENV, DIST, OBS, AA>), grid16, dim3(384), 0, s, a);                          \
+        else hipLaunchKernelGGL((rollout16_kernel<ENV, DIST, OBS, AA>), grid16, dim3(384), 0, s, a.params, a.env_state, a.ep_len, a.ep_rew,   \
+                                a.reset_count, a.next_done, a.N, (int)grid16.x, a);                                                  \
     } while (0)
 #define PPO_LAUNCH_ROLLOUT(ENV, DIST, OBS)                                                                       \
     do {                                                                                                         \

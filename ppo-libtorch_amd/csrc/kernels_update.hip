@@ -50,7 +50,7 @@ __host__ __device__ inline SmemLayout smem_layout(int obs, int aout) {
 }
 
 template <int NET, int DIST, int OBS>
-__device__ __forceinline__ void fwd_bwd_body(const UpdateArgs& a, float* smem) {
+__device__ __forceinline__ void fwd_bwd_body(const UpdLead& h, const UpdateArgs& a, float* smem) {
     const NetLayout& L = a.L;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -68,7 +68,7 @@ __device__ __forceinline__ void fwd_bwd_body(const UpdateArgs& a, float* smem) {
     float* sH1 = smem + m.h1;
     float* sH2 = smem + m.h2;
     float* sD = smem + m.dout;
-    const float* __restrict__ P = a.params;
+    const float* __restrict__ P = h.params;
 
     // ---- weights of this net -> LDS (once per launch) ----
     for (int e = tid; e < 64 * 64; e += UPD_THREADS) {
@@ -111,8 +111,8 @@ __device__ __forceinline__ void fwd_bwd_body(const UpdateArgs& a, float* smem) {
     }
     __syncthreads();
 
-    const int n_tiles = (a.M + TILE - 1) / TILE;
-    for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    const int n_tiles = (h.M + TILE - 1) / TILE;
+    for (int tile = blockIdx.x; tile < n_tiles; tile += h.nb0) {   // the grid is (n_blocks[0], 2): not gridDim, a load from the implicit arguments
         // ---------------- gather (K5): wave 0, lane = sample ----------------
         bool valid = false;
         int row = 0;
@@ -121,8 +121,8 @@ __device__ __forceinline__ void fwd_bwd_body(const UpdateArgs& a, float* smem) {
         uint32_t s_mask = 0xffffffffu;
         if (tid < TILE) {
             const int j = tile * TILE + tid;
-            valid = j < a.M;
-            row = valid ? a.idx[j] : 0;
+            valid = j < h.M;
+            row = valid ? h.idx[j] : 0;
 #pragma unroll
             for (int o = 0; o < OBS; o++) sX[o * S + tid] = valid ? a.obs[(size_t)row * OBS + o] : 0.0f;
             if (NET == 1) {
@@ -405,7 +405,7 @@ __device__ __forceinline__ void fwd_bwd_body(const UpdateArgs& a, float* smem) {
 
     // ---------------- write this workgroup's partial gradient slab (net-local flat layout) ----------------
     const int Pmax = L.net_size[0] > L.net_size[1] ? L.net_size[0] : L.net_size[1];
-    float* slab = a.slab + ((size_t)(NET == 0 ? 0 : a.n_blocks[0]) + blockIdx.x) * Pmax;
+    float* slab = a.slab + ((size_t)(NET == 0 ? 0 : h.nb0) + blockIdx.x) * Pmax;
     const int base = L.net_off[NET];
 #pragma unroll
     for (int j = 0; j < 4; j++)
@@ -426,17 +426,18 @@ __device__ __forceinline__ void fwd_bwd_body(const UpdateArgs& a, float* smem) {
     if (tid < 64) {
         st0 = wave_sum_d(st0); st1 = wave_sum_d(st1); st2 = wave_sum_d(st2); st3 = wave_sum_d(st3);
         if (lane == 0) {
-            double* o = a.stat_slab + ((size_t)(NET == 0 ? 0 : a.n_blocks[0]) + blockIdx.x) * 8;
+            double* o = a.stat_slab + ((size_t)(NET == 0 ? 0 : h.nb0) + blockIdx.x) * 8;
             o[0] = st0; o[1] = st1; o[2] = st2; o[3] = st3;
         }
     }
 }
 
 template <int DIST, int OBS>
-__global__ __launch_bounds__(UPD_THREADS, 2) void fwd_bwd_kernel(UpdateArgs a) {
+__global__ __launch_bounds__(UPD_THREADS, 2) void fwd_bwd_kernel(UPD_LEAD_PARAMS, UpdateArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    if (blockIdx.y == 0) fwd_bwd_body<0, DIST, OBS>(a, smem);
-    else fwd_bwd_body<1, DIST, OBS>(a, smem);
+    const UpdLead h{idx, rec_critic, rec_actor, params, M, nb0};   // leading scalars: preloaded into SGPRs (ppo_internal.hpp)
+    if (blockIdx.y == 0) fwd_bwd_body<0, DIST, OBS>(h, a, smem);
+    else fwd_bwd_body<1, DIST, OBS>(h, a, smem);
 }
 
 // grads[p] = sum_b slab[net(p)][b][p - net_off] in a fixed order (16 contiguous groups of slabs, each summed in order by one
@@ -662,14 +663,14 @@ __device__ __forceinline__ unsigned int* xchg_count(void* base, size_t slot_byte
 }
 // The caller's stores into the peers' slots are done: make them visible system-wide, count this workgroup in (one lane), and let the last
 // workgroup of the grid stamp this rank's flag in every peer's buffer (lane p stamps peer p).  Called by one whole wave per workgroup.
-__device__ __forceinline__ void xchg_publish_done(void* const* peers, int rank, int n, size_t slot_bytes, int parity, unsigned long long seq) {
+__device__ __forceinline__ void xchg_publish_done(void* const* peers, int rank, int n, size_t slot_bytes, int parity, unsigned long long seq, unsigned int n_wg) {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
     const int lane = threadIdx.x & 63;
     int last = 0;
     if (lane == 0) {
         unsigned int* cnt = xchg_count(peers[rank], slot_bytes, parity);
         const unsigned int arrived = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        if (arrived == gridDim.x - 1) { __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); last = 1; }
+        if (arrived == n_wg - 1) { __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); last = 1; }
     }
     last = __builtin_amdgcn_readfirstlane(last);
     if (last && lane < n && lane != rank) __hip_atomic_store(xchg_flag(peers[lane], slot_bytes, parity, rank), seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -699,21 +700,30 @@ __device__ __forceinline__ unsigned xchg_wait_all(void* own, int rank, int n, si
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");   // every lane reads the slots after the polling lanes saw the flags
     return (unsigned)(m & 0xffu) | ~0xffu;
 }
+// Kernel-argument preloading (gfx940 and later; csrc/Makefile: -amdgpu-kernarg-preload-count): the LEADING scalar parameters of a kernel, up to 14 dwords,
+// arrive in user SGPRs at wave launch -- the dispatcher fetches them while the launch ramps.  A by-value struct is never preloaded: its members come by
+// s_load from the kernel-argument segment, which the host wrote for this dispatch and which is therefore cold in every cache, with a wait in front of the
+// first data load.  So everything on the head of the dependent chain (pointers and sizes of the first batch of loads) leads as scalars, in the launchers'
+// hands copies of the struct's members; what is consumed only behind the data loads stays in FusedOptArgs, which follows as the last parameter.
+// Leading dwords: 4 pointers + 6 ints = 14.  The grid is (P + 63) / 64 gradient workgroups + 1 for the loss sums (fused_opt_blocks): formed from P, not
+// read from gridDim (a load from the implicit arguments).
 template <bool XCHG>
-__global__ __launch_bounds__(64 * RED_WAVES) void reduce_grads_sumsq_kernel(FusedOptArgs a) {
+__global__ __launch_bounds__(64 * RED_WAVES) void reduce_grads_sumsq_kernel(const float* __restrict__ slab, float* __restrict__ grads, double* __restrict__ partial,
+                                                                            const double* __restrict__ stat_slab, int nb0, int nb1, int P, int net_off0,
+                                                                            int net_off1, int Pmax, FusedOptArgs a) {
     __shared__ double part[RED_WAVES][64];
     const NetLayout& L = a.L;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (blockIdx.x + 1 < gridDim.x) {
+    const int grad_wgs = (P + 63) / 64;
+    if ((int)blockIdx.x < grad_wgs) {
         const int p = blockIdx.x * 64 + lane;
-        const int Pmax = L.net_size[0] > L.net_size[1] ? L.net_size[0] : L.net_size[1];
         double acc = 0.0;
-        if (p < L.P) {
+        if (p < P) {
             // (selects between the two nets' constants, not L.net_off[net]: indexing the kernel-argument struct with a per-lane value is a VECTOR load
             // from the argument segment -- a memory round trip in front of the slab loads)
-            const bool net1 = p >= L.net_off[1];
-            const int nb = net1 ? a.nb1 : a.nb0;
-            const float* col = a.slab + (size_t)(net1 ? a.nb0 : 0) * Pmax + (p - (net1 ? L.net_off[1] : L.net_off[0]));
+            const bool net1 = p >= net_off1;
+            const int nb = net1 ? nb1 : nb0;
+            const float* col = slab + (size_t)(net1 ? nb0 : 0) * Pmax + (p - (net1 ? net_off1 : net_off0));
             const int b0 = (nb * w) / RED_WAVES, b1 = (nb * (w + 1)) / RED_WAVES;
             int b = b0;
             for (; b + 16 <= b1; b += 16) {   // a wave's 16 slabs of the 128-workgroup update kernel: ONE batch of loads, one round trip
@@ -736,7 +746,7 @@ __global__ __launch_bounds__(64 * RED_WAVES) void reduce_grads_sumsq_kernel(Fuse
         __syncthreads();
         if (w == 0) {
             float g = 0.0f;
-            if (p < L.P) {
+            if (p < P) {
                 double sacc = 0.0;
 #pragma unroll
                 for (int i = 0; i < RED_WAVES; i++) sacc += part[i][lane];
@@ -747,15 +757,15 @@ __global__ __launch_bounds__(64 * RED_WAVES) void reduce_grads_sumsq_kernel(Fuse
                 const int parity = (int)(a.seq & 1ull);
 #pragma unroll
                 for (int r = 0; r < 8; r++)
-                    if (r < a.n_ranks && r != a.rank && p < L.P)
+                    if (r < a.n_ranks && r != a.rank && p < P)
                         __hip_atomic_store(reinterpret_cast<float*>(xchg_slot(a.peers[r], a.slot_bytes, parity, a.rank)) + p, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                xchg_publish_done(a.peers, a.rank, a.n_ranks, a.slot_bytes, parity, a.seq);
+                xchg_publish_done(a.peers, a.rank, a.n_ranks, a.slot_bytes, parity, a.seq, (unsigned int)grad_wgs + 1u);
                 const unsigned okm = xchg_wait_all(a.peers[a.rank], a.rank, a.n_ranks, a.slot_bytes, parity, a.seq, a.timeout_flag);
                 float v[8];
 #pragma unroll
                 for (int r = 0; r < 8; r++) {
                     v[r] = 0.0f;
-                    if (r < a.n_ranks && r != a.rank && ((okm >> r) & 1u) && p < L.P)
+                    if (r < a.n_ranks && r != a.rank && ((okm >> r) & 1u) && p < P)
                         v[r] = __hip_atomic_load(reinterpret_cast<const float*>(xchg_slot(a.peers[a.rank], a.slot_bytes, parity, r)) + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                 }
                 float acc = 0.0f;
@@ -763,17 +773,17 @@ __global__ __launch_bounds__(64 * RED_WAVES) void reduce_grads_sumsq_kernel(Fuse
                 for (int r = 0; r < 8; r++) if (r < a.n_ranks) acc += r == a.rank ? g : v[r];   // rank order: every rank forms the same sum
                 g = acc;
             }
-            if (p < L.P) a.grads[p] = g;
+            if (p < P) grads[p] = g;
             // sums of squares per tensor of this workgroup's 64 gradients (a workgroup touches at most a few tensors)
             int tl = 0;
 #pragma unroll
             for (int t = 0; t < 12; t++) if (t < L.n_tensors && p >= L.tensor_off[t]) tl = t;   // fixed bound: the offsets stay scalar constants
-            const double g2 = p < L.P ? (double)g * (double)g : 0.0;
+            const double g2 = p < P ? (double)g * (double)g : 0.0;
             for (int t = 0; t < 12; t++) {
                 double v = 0.0;
                 const bool touches = t < L.n_tensors && L.tensor_off[t] < (int)(blockIdx.x + 1) * 64 && L.tensor_off[t + 1] > (int)blockIdx.x * 64;
                 if (touches) v = wave_sum_d_dpp(tl == t ? g2 : 0.0);
-                if (lane == 0) a.partial[(size_t)blockIdx.x * 12 + t] = v;
+                if (lane == 0) partial[(size_t)blockIdx.x * 12 + t] = v;
             }
         }
     } else {
@@ -781,13 +791,13 @@ __global__ __launch_bounds__(64 * RED_WAVES) void reduce_grads_sumsq_kernel(Fuse
         // together and reduced together: one memory round trip and one barrier (they used to be five of each, one column after the other --
         // this workgroup alone set the kernel's duration).  Fixed order: a thread's workgroups in index order, lanes on the DPP network, waves in order.
         double v5[5] = { 0.0, 0.0, 0.0, 0.0, 0.0 };
-        for (int b = threadIdx.x; b < a.nb0 || b < a.nb1; b += 64 * RED_WAVES) {
+        for (int b = threadIdx.x; b < nb0 || b < nb1; b += 64 * RED_WAVES) {
             double t[5] = { 0.0, 0.0, 0.0, 0.0, 0.0 };
-            if (b < a.nb1) {
-                const double* r = a.stat_slab + ((size_t)a.nb0 + b) * 8;
+            if (b < nb1) {
+                const double* r = stat_slab + ((size_t)nb0 + b) * 8;
                 t[0] = r[0]; t[1] = r[1]; t[2] = r[2]; t[3] = r[3];
             }
-            if (b < a.nb0) t[4] = a.stat_slab[(size_t)b * 8];
+            if (b < nb0) t[4] = stat_slab[(size_t)b * 8];
 #pragma unroll
             for (int kk = 0; kk < 5; kk++) v5[kk] += t[kk];
         }
@@ -812,16 +822,16 @@ __global__ __launch_bounds__(64 * RED_WAVES) void reduce_grads_sumsq_kernel(Fuse
                 const float mine = threadIdx.x < 5 ? (float)part[RED_WAVES - 1][8 + threadIdx.x] : 0.0f;
                 for (int r = 0; r < a.n_ranks; r++)
                     if (r != a.rank && threadIdx.x < 8)
-                        __hip_atomic_store(reinterpret_cast<float*>(xchg_slot(a.peers[r], a.slot_bytes, parity, a.rank)) + L.P + threadIdx.x, mine, __ATOMIC_RELAXED,
+                        __hip_atomic_store(reinterpret_cast<float*>(xchg_slot(a.peers[r], a.slot_bytes, parity, a.rank)) + P + threadIdx.x, mine, __ATOMIC_RELAXED,
                                            __HIP_MEMORY_SCOPE_SYSTEM);
-                xchg_publish_done(a.peers, a.rank, a.n_ranks, a.slot_bytes, parity, a.seq);
+                xchg_publish_done(a.peers, a.rank, a.n_ranks, a.slot_bytes, parity, a.seq, (unsigned int)grad_wgs + 1u);
                 const unsigned okm = xchg_wait_all(a.peers[a.rank], a.rank, a.n_ranks, a.slot_bytes, parity, a.seq, a.timeout_flag);
                 float acc = 0.0f;
                 for (int r = 0; r < a.n_ranks; r++) {
                     if (r == a.rank) { acc += mine; continue; }
                     if (!((okm >> r) & 1u)) continue;
                     if (threadIdx.x < 8)
-                        acc += __hip_atomic_load(reinterpret_cast<const float*>(xchg_slot(a.peers[a.rank], a.slot_bytes, parity, r)) + L.P + threadIdx.x, __ATOMIC_RELAXED,
+                        acc += __hip_atomic_load(reinterpret_cast<const float*>(xchg_slot(a.peers[a.rank], a.slot_bytes, parity, r)) + P + threadIdx.x, __ATOMIC_RELAXED,
                                                  __HIP_MEMORY_SCOPE_SYSTEM);
                 }
                 if (threadIdx.x < 8) a.sums_out[threadIdx.x] = (double)acc;
@@ -830,23 +840,28 @@ __global__ __launch_bounds__(64 * RED_WAVES) void reduce_grads_sumsq_kernel(Fuse
     }
 }
 
-__global__ __launch_bounds__(ADAM_THREADS) void clip_adamw_sumsq_kernel(FusedOptArgs a) {
+// Leading scalars (preloaded into SGPRs, see reduce_grads_sumsq_kernel): the operands of the first batch of loads, 6 pointers + 1 int = 13 dwords.  The
+// error word's pointer, the tensor offsets of opt_total_norm, the statistics' pointers and the hyper-parameters stay in the struct: their s_loads are
+// issued at the top and waited for behind the gradient / parameter / moment loads.
+__global__ __launch_bounds__(ADAM_THREADS) void clip_adamw_sumsq_kernel(const float* __restrict__ grads, const float* p_src, const float* m_src, const float* v_src,
+                                                                        const double* __restrict__ partial, const AdamCoef* __restrict__ coef, int P,
+                                                                        FusedOptArgs a) {
     __shared__ double n2s[12];
     const NetLayout& L = a.L;
     const int tid = threadIdx.x;
     const int p = blockIdx.x * ADAM_THREADS + tid;
-    const bool own = p < L.P;
+    const bool own = p < P;
     float u_g = 0.0f, u_p = 0.0f, u_m = 0.0f, u_v = 0.0f;
-    if (own) { u_g = a.grads[p]; u_p = a.p_src[p]; u_m = a.m_src[p]; u_v = a.v_src[p]; }
+    if (own) { u_g = grads[p]; u_p = p_src[p]; u_m = m_src[p]; u_v = v_src[p]; }
     const int32_t err = opt_guard_word(a.guard.error_flag);   // requested with the step's other loads
-    const AdamCoef k = *a.coef;
+    const AdamCoef k = *coef;
     double ls[5] = { 0, 0, 0, 0, 0 }, cf0 = 0.0, cf1 = 0.0;
     const bool stat_thread = tid == 0 && blockIdx.x == 0;
     if (stat_thread) {
         for (int i = 0; i < 5; i++) ls[i] = a.sums_out[i];
         if (a.clipfrac_accum) { cf0 = a.clipfrac_accum[0]; cf1 = a.clipfrac_accum[1]; }
     }
-    const float total = opt_total_norm(L, a.partial, n2s, tid);
+    const float total = opt_total_norm(L, partial, n2s, tid);
     const float c = opt_clip_coef(total, a.max_norm);
     if (own && !(err & PPO_ERRFLAG_SKIP_STEP)) {   // a step the device knows is garbage is not applied (OptGuard, ppo_internal.hpp)
         adamw_apply(u_g, c, k, u_p, u_m, u_v);
@@ -1018,7 +1033,7 @@ __global__ __launch_bounds__(256) void exchange_allreduce_kernel(Tp* __restrict_
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");   // system scope: this thread's stores have landed before the workgroup is counted in
     __syncthreads();
     if (threadIdx.x < 64) {
-        xchg_publish_done(peers.p, rank, n, slot_bytes, parity, seq);
+        xchg_publish_done(peers.p, rank, n, slot_bytes, parity, seq, gridDim.x);
         const unsigned okm = xchg_wait_all(peers.p[rank], rank, n, slot_bytes, parity, seq, timeout_flag);
         if (threadIdx.x == 0) s_okm = okm;
     }
@@ -1104,7 +1119,7 @@ hipError_t launch_minibatch_fwd_bwd(const UpdateArgs& a, hipStream_t s) {
         static std::atomic<unsigned long long> lds_ok{0};                                                             \
         const hipError_t e = allow_dynamic_lds(lds_ok, reinterpret_cast<const void*>(&fwd_bwd_kernel<DIST, OBS>));    \
         if (e != hipSuccess) return e;                                                                                \
-        hipLaunchKernelGGL((fwd_bwd_kernel<DIST, OBS>), grid, block, shmem, s, a);                                    \
+        hipLaunchKernelGGL((fwd_bwd_kernel<DIST, OBS>), grid, block, shmem, s, UPD_LEAD_ARGS(a), a);                                   \
     } while (0)
     if (a.L.obs == 4) {
         if (a.hp.dist_kind == PPO_DIST_CATEGORICAL) PPO_LAUNCH_UPD(PPO_DIST_CATEGORICAL, 4); else PPO_LAUNCH_UPD(PPO_DIST_MASKED, 4);
@@ -1141,6 +1156,10 @@ hipError_t launch_weight_range(const float* params, const NetLayout& L, uint32_t
 }
 
 int fused_opt_blocks(const NetLayout& L) { return (L.P + 63) / 64 + 1; }
+// the two kernels' leading (preloaded) parameters out of the filled struct, in the order of their signatures
+#define FUSED_REDUCE_LEAD(a) (a).slab, (a).grads, (a).partial, (a).stat_slab, (a).nb0, (a).nb1, (a).L.P, (a).L.net_off[0], (a).L.net_off[1], \
+                             ((a).L.net_size[0] > (a).L.net_size[1] ? (a).L.net_size[0] : (a).L.net_size[1])
+#define FUSED_ADAMW_LEAD(a) (a).grads, (a).p_src, (a).m_src, (a).v_src, (a).partial, (a).coef, (a).L.P
 hipError_t launch_reduce_clip_adamw(const float* slab, const double* stat_slab, const int n_blocks[2], const NetLayout& L, float* grads,
                                     double* sums_out, float* params, float* exp_avg, float* exp_avg_sq, float max_grad_norm,
                                     const AdamCoef* coef, double global_M, LossParams hp, StepStats* stats_out, double* clipfrac_accum,
@@ -1152,8 +1171,8 @@ hipError_t launch_reduce_clip_adamw(const float* slab, const double* stat_slab, 
     a.params = params; a.exp_avg = exp_avg; a.exp_avg_sq = exp_avg_sq; a.max_norm = max_grad_norm; a.coef = coef; a.global_M = global_M;
     a.p_src = params; a.m_src = exp_avg; a.v_src = exp_avg_sq;
     a.hp = hp; a.stats_out = stats_out; a.clipfrac_accum = clipfrac_accum; a.partial = partial;
-    hipLaunchKernelGGL(reduce_grads_sumsq_kernel<false>, dim3(fused_opt_blocks(L)), dim3(64 * RED_WAVES), 0, s, a);
-    hipLaunchKernelGGL(clip_adamw_sumsq_kernel, dim3((L.P + ADAM_THREADS - 1) / ADAM_THREADS), dim3(ADAM_THREADS), 0, s, a);
+    hipLaunchKernelGGL(reduce_grads_sumsq_kernel<false>, dim3(fused_opt_blocks(L)), dim3(64 * RED_WAVES), 0, s, FUSED_REDUCE_LEAD(a), a);
+    hipLaunchKernelGGL(clip_adamw_sumsq_kernel, dim3((L.P + ADAM_THREADS - 1) / ADAM_THREADS), dim3(ADAM_THREADS), 0, s, FUSED_ADAMW_LEAD(a), a);
     return hipGetLastError();
 }
 // The same two launches for a sharded context on the direct-exchange transport: the reduction also publishes this rank's gradient (and loss
@@ -1173,8 +1192,8 @@ hipError_t launch_reduce_exchange_clip_adamw(const float* slab, const double* st
     a.hp = hp; a.stats_out = stats_out; a.clipfrac_accum = clipfrac_accum; a.partial = partial;
     for (int r = 0; r < 8; r++) a.peers[r] = r < n_ranks ? peers[r] : nullptr;
     a.rank = rank; a.n_ranks = n_ranks; a.slot_bytes = slot_bytes; a.seq = seq; a.timeout_flag = timeout_flag;
-    hipLaunchKernelGGL(reduce_grads_sumsq_kernel<true>, dim3(fused_opt_blocks(L)), dim3(64 * RED_WAVES), 0, s, a);
-    hipLaunchKernelGGL(clip_adamw_sumsq_kernel, dim3((L.P + ADAM_THREADS - 1) / ADAM_THREADS), dim3(ADAM_THREADS), 0, s, a);
+    hipLaunchKernelGGL(reduce_grads_sumsq_kernel<true>, dim3(fused_opt_blocks(L)), dim3(64 * RED_WAVES), 0, s, FUSED_REDUCE_LEAD(a), a);
+    hipLaunchKernelGGL(clip_adamw_sumsq_kernel, dim3((L.P + ADAM_THREADS - 1) / ADAM_THREADS), dim3(ADAM_THREADS), 0, s, FUSED_ADAMW_LEAD(a), a);
     return hipGetLastError();
 }
 // One thread per minibatch slot: the PPO_ADV_PARTS partial sums in order, then mean and Bessel std in binary64 as the update kernels used to do in

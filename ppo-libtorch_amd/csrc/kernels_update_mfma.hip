@@ -219,7 +219,7 @@ __device__ __forceinline__ float pow2i(int e) { return u2f((uint32_t)(127 + e) <
 // 64 x |c W2| < 2^21 for |W2| < 0.7; larger weights saturate to inf and the update fails loudly like an oversized c W2 does).  Used where the
 // register file has room for the 16 accumulator registers (the reference's two shapes); the generic variants keep the vector form.
 template <int NET, int DIST, int OBS, int AMAX, bool EXACT, bool STAMP, bool DW1M>
-__device__ __forceinline__ void mf_body(const UpdateArgs& a, float* smem, const int blk, const int nblk) {
+__device__ __forceinline__ void mf_body(const UpdLead& h, const UpdateArgs& a, float* smem, const int blk, const int nblk) {
     unsigned long long ph[12] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
     unsigned long long t_prev = 0;
     if constexpr (STAMP) t_prev = __builtin_amdgcn_s_memtime();
@@ -241,17 +241,17 @@ __device__ __forceinline__ void mf_body(const UpdateArgs& a, float* smem, const 
     uint16_t* zimg = reinterpret_cast<uint16_t*>(img);   // the same bytes as two fp16 term images [term][sample][NS]
     float* sX = wbase + m.s_x;
     float* sDo = wbase + m.s_do;
-    const float* __restrict__ P = a.params;
+    const float* __restrict__ P = h.params;
 
     // ---- the first tile's batch rows: requested before anything else (see the gather pipeline below) ----
-    const int n_tiles = (a.M + MT - 1) / MT;
+    const int n_tiles = (h.M + MT - 1) / MT;
     const int tile_step = nblk * MF_WAVES;
     int tile = blk * MF_WAVES + wave;
-    const float4* __restrict__ rec = reinterpret_cast<const float4*>(NET == 0 ? a.rec_critic : a.rec_actor);
+    const float4* __restrict__ rec = reinterpret_cast<const float4*>(NET == 0 ? h.rec_critic : h.rec_actor);
     auto fetch_row = [&](int tl) -> int {
         const int j = tl * MT + s;
-        const bool ok = tl < n_tiles && j < a.M;
-        const int v = a.idx[ok ? j : 0];
+        const bool ok = tl < n_tiles && j < h.M;
+        const int v = h.idx[ok ? j : 0];
         return ok ? v : -1;
     };
     int row_n = fetch_row(tile);
@@ -930,7 +930,7 @@ __device__ __forceinline__ void mf_body(const UpdateArgs& a, float* smem, const 
     }
     __syncthreads();
     const int Pmax = L.net_size[0] > L.net_size[1] ? L.net_size[0] : L.net_size[1];
-    float* slab = a.slab + ((size_t)(NET == 0 ? 0 : a.n_blocks[0]) + blk) * Pmax;
+    float* slab = a.slab + ((size_t)(NET == 0 ? 0 : h.nb0) + blk) * Pmax;
     for (int e = tid; e < nsz; e += MF_THREADS) {
         float t = smem[e];
 #pragma unroll
@@ -938,7 +938,7 @@ __device__ __forceinline__ void mf_body(const UpdateArgs& a, float* smem, const 
         slab[e] = t;
     }
     if (tid < 4) {
-        double* o = a.stat_slab + ((size_t)(NET == 0 ? 0 : a.n_blocks[0]) + blk) * 8;
+        double* o = a.stat_slab + ((size_t)(NET == 0 ? 0 : h.nb0) + blk) * 8;
         double t = dred[tid];
 #pragma unroll
         for (int w = 1; w < MF_WAVES; w++) t += dred[4 * w + tid];
@@ -953,13 +953,14 @@ __device__ __forceinline__ void mf_body(const UpdateArgs& a, float* smem, const 
 }
 
 template <int DIST, int OBS, int AMAX, bool EXACT, bool STAMP>
-__global__ __launch_bounds__(MF_THREADS, 1) void fwd_bwd_mfma_kernel(UpdateArgs a) {
+__global__ __launch_bounds__(MF_THREADS, 1) void fwd_bwd_mfma_kernel(UPD_LEAD_PARAMS, UpdateArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
+    const UpdLead h{idx, rec_critic, rec_actor, params, M, nb0};
     // 1-D grid: the first n_blocks[0] workgroups run the critic, the rest the actor
     const int b = blockIdx.x;
     constexpr bool DW1M = EXACT;   // the reference's two shapes: 234 / 237 vector registers leave room for 12 more; the generic variants (245 - 247) do not
-    if (b < a.n_blocks[0]) mf_body<0, DIST, OBS, 1, true, STAMP, DW1M>(a, smem, b, a.n_blocks[0]);
-    else mf_body<1, DIST, OBS, AMAX, EXACT, STAMP, DW1M>(a, smem, b - a.n_blocks[0], a.n_blocks[1]);
+    if (b < nb0) mf_body<0, DIST, OBS, 1, true, STAMP, DW1M>(h, a, smem, b, nb0);
+    else mf_body<1, DIST, OBS, AMAX, EXACT, STAMP, DW1M>(h, a, smem, b - nb0, nb1);
 }
 
 
@@ -1068,9 +1069,20 @@ __device__ __forceinline__ void mg_post(lds_flag_t* flag, uint32_t v, int lane) 
 #define MG_TR_F(slot_a, slot_b) do { } while (0)
 #define MG_TR_G(slot) do { } while (0)
 #endif
+// The argument struct as seen from BEHIND this point of the program: the same kernel-argument bytes, through a pointer the compiler cannot trace back to the
+// kernel's parameter, so that none of the struct's scalar loads is hoisted in front of what the program issued before.  (Hoisted to the kernel's entry they were
+// all in flight when the first batch-row load needed a fresh scalar register, the allocator handed out the dead dword of one of them, and the wait for that load
+// stood in front of the row load: tests/test_kernarg_preload.py.)  Constant address space: still scalar loads.
+// The struct follows the leading parameters at UPD_ARGS_OFFSET (ppo_internal.hpp: from the same image of UPD_LEAD_PARAMS the kernel's signature is held to below).
+// This buys NO measured time -- the headline is the same within noise with the struct read as the kernel's plain parameter (NOTES 2026-10-18, third call) -- only
+// the guarantee that the row loads never wait for the struct, which tests/test_kernarg_preload.py holds in the assembly.
+__device__ __forceinline__ const UpdateArgs& mg_args_behind_here() {
+    uintptr_t p = reinterpret_cast<uintptr_t>(__builtin_amdgcn_kernarg_segment_ptr()) + UPD_ARGS_OFFSET;
+    asm volatile("" : "+s"(p) : : "memory");
+    return *(const UpdateArgs*)reinterpret_cast<const __attribute__((address_space(4))) UpdateArgs*>(p);
+}
 template <int NET, int DIST, int OBS, int AMAX>
-__device__ __forceinline__ void mg_body(const UpdateArgs& a, float* smem, const int blk, const int nblk) {
-    const NetLayout& L = a.L;
+__device__ __forceinline__ void mg_body(const UpdLead& h, float* smem, const int blk, const int nblk) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int s = lane & 31, hi = lane >> 5;
     constexpr int AOUT = NET == 0 ? 1 : AMAX;
@@ -1082,10 +1094,10 @@ __device__ __forceinline__ void mg_body(const UpdateArgs& a, float* smem, const 
     float* sW3 = smem + m.w3;
     float* sB3 = smem + m.b3;
     lds_flag_t* flags = (lds_flag_t*)(smem + m.flags);   // explicit LDS address space: a generic volatile access is a FLAT instruction and waits for vmcnt too
-    const float* __restrict__ P = a.params;
-    const int n_tiles = (a.M + MT - 1) / MT;
+    const float* __restrict__ P = h.params;
+    const int n_tiles = (h.M + MT - 1) / MT;
     const int tile_step = nblk * MG_FW;
-    const float4* __restrict__ rec = reinterpret_cast<const float4*>(NET == 0 ? a.rec_critic : a.rec_actor);
+    const float4* __restrict__ rec = reinterpret_cast<const float4*>(NET == 0 ? h.rec_critic : h.rec_actor);
     const int tq = (lane & 15) >> 2, tp = lane & 3, tb = (lane >> 4) & 1;
     bool proto_ok = true;
 #ifdef MG_STAMP
@@ -1097,12 +1109,15 @@ __device__ __forceinline__ void mg_body(const UpdateArgs& a, float* smem, const 
     int tile = blk * MG_FW + (wave < MG_FW ? wave : 0);
     auto fetch_row = [&](int tl) -> int {
         const int j = tl * MT + s;
-        const bool ok = tl < n_tiles && j < a.M;
-        const int v = a.idx[ok ? j : 0];
+        const bool ok = tl < n_tiles && j < h.M;
+        const int v = h.idx[ok ? j : 0];
         return ok ? v : -1;
     };
     int row_n = -1, row_nn = -1;
     if (wave < MG_FW) { row_n = fetch_row(tile); row_nn = fetch_row(tile + tile_step); }
+    const UpdateArgs& a = mg_args_behind_here();   // everything above came from the preloaded arguments
+    const NetLayout& L = a.L;
+    const LossParams hp = a.hp;   // by value, here: read where they are used, the tile loops would fetch them again for every tile (nothing marks this pointer's target as safe to read early)
 
     // ---- weights of this net -> LDS (once per launch, all twelve waves; W1, b1, W2, b2 multiplied by c = 2 log2(e), W2 cut into its fp16 terms) ----
     constexpr int NW2 = (4096 + MG_THREADS - 1) / MG_THREADS;
@@ -1152,11 +1167,11 @@ __device__ __forceinline__ void mg_body(const UpdateArgs& a, float* smem, const 
         lds_flag_t* prod = flags + MG_PROD + wave;
         const lds_flag_t* cons = flags + MG_CONS + wave;
         float st0 = 0.0f, st1 = 0.0f, st2 = 0.0f, st3 = 0.0f;
-        const float clip = a.hp.clip_coef;
+        const float clip = hp.clip_coef;
         const float lo = uniform_f(1 - clip), hi_c = uniform_f(1 + clip);
         const float invM = uniform_f((float)a.inv_global_M);
         float mean_f = 0.0f, inv_std = 0.0f;
-        if (NET == 1 && a.hp.norm_adv) {
+        if (NET == 1 && hp.norm_adv) {
             const float4 an = *a.adv_norm;
             mean_f = uniform_f(an.x);
             inv_std = uniform_f(an.y);
@@ -1309,7 +1324,7 @@ __device__ __forceinline__ void mg_body(const UpdateArgs& a, float* smem, const 
                 const float R = s_f0, vold = s_f1;
                 const float un = (v - R) * (v - R);
                 float g_v, lossv;
-                if (a.hp.clip_vloss) {   // PPO_Discrete.cpp:603-620
+                if (hp.clip_vloss) {   // PPO_Discrete.cpp:603-620
                     const float dv = v - vold;
                     const float dvc = dv < -clip ? -clip : (dv > clip ? clip : dv);
                     const float vc = vold + dvc;
@@ -1318,10 +1333,10 @@ __device__ __forceinline__ void mg_body(const UpdateArgs& a, float* smem, const 
                     const bool vin = (dv >= -clip && dv <= clip);
                     const float d_un = 2.0f * (v - R), d_cl = vin ? 2.0f * (vc - R) : 0.0f;
                     const float d = un > cl ? d_un : (un < cl ? d_cl : 0.5f * d_un + 0.5f * d_cl);
-                    g_v = a.hp.vf_coef * 0.5f * invM * d;
+                    g_v = hp.vf_coef * 0.5f * invM * d;
                 } else {                 // :622-625
                     lossv = un;
-                    g_v = a.hp.vf_coef * 0.5f * invM * 2.0f * (v - R);
+                    g_v = hp.vf_coef * 0.5f * invM * 2.0f * (v - R);
                 }
                 if (valid && hi == 0) st0 += lossv;
                 dOut[0] = valid ? g_v : 0.0f;
@@ -1370,7 +1385,7 @@ __device__ __forceinline__ void mg_body(const UpdateArgs& a, float* smem, const 
                 const float logratio = nlp - s_oldlp;           // :585
                 const float ratio = fast_exp(logratio);         // :586
                 float adv = s_adv;
-                if (a.hp.norm_adv) adv = (adv - mean_f) * inv_std;           // :593
+                if (hp.norm_adv) adv = (adv - mean_f) * inv_std;           // :593
                 const float rc = ratio < lo ? lo : (ratio > hi_c ? hi_c : ratio);
                 const float l1 = -adv * ratio, l2 = -adv * rc;  // :597-598
                 const bool inside = (ratio >= lo && ratio <= hi_c);
@@ -1379,7 +1394,7 @@ __device__ __forceinline__ void mg_body(const UpdateArgs& a, float* smem, const 
                 else if (l1 < l2) d_ratio = inside ? -adv : 0.0f;
                 else d_ratio = 0.5f * -adv + (inside ? 0.5f * -adv : 0.0f);   // torch::max splits ties half/half
                 const float g_nlp = invM * d_ratio * ratio;
-                const float g_ent = -a.hp.ent_coef * invM;
+                const float g_ent = -hp.ent_coef * invM;
                 if (valid && hi == 0) {
                     st0 += l1 > l2 ? l1 : l2;
                     st1 += ent;
@@ -1780,7 +1795,7 @@ __device__ __forceinline__ void mg_body(const UpdateArgs& a, float* smem, const 
     }
     // ---- every thread adds the four gradient images in a fixed order into the workgroup's slab ----
     const int Pmax = L.net_size[0] > L.net_size[1] ? L.net_size[0] : L.net_size[1];
-    float* slab = a.slab + ((size_t)(NET == 0 ? 0 : a.n_blocks[0]) + blk) * Pmax;
+    float* slab = a.slab + ((size_t)(NET == 0 ? 0 : h.nb0) + blk) * Pmax;
     {
         constexpr int NSZ = 64 * OBS + 64 + 4096 + 64 + 64 * AOUT + AOUT;   // = L.net_size[NET] (checked by the launcher)
         constexpr int NE = (NSZ + MG_THREADS - 1) / MG_THREADS;
@@ -1801,7 +1816,7 @@ __device__ __forceinline__ void mg_body(const UpdateArgs& a, float* smem, const 
         }
     }
     if (tid < 4) {
-        double* o = a.stat_slab + ((size_t)(NET == 0 ? 0 : a.n_blocks[0]) + blk) * 8;
+        double* o = a.stat_slab + ((size_t)(NET == 0 ? 0 : h.nb0) + blk) * 8;
         double t = dred[tid];
 #pragma unroll
         for (int w = 1; w < MG_FW; w++) t += dred[4 * w + tid];
@@ -1816,12 +1831,20 @@ __device__ __forceinline__ void mg_body(const UpdateArgs& a, float* smem, const 
 }
 
 template <int DIST, int OBS, int AMAX>
-__global__ __launch_bounds__(MG_THREADS, 1) void fwd_bwd_mfma_ws_kernel(UpdateArgs a) {
+__global__ __launch_bounds__(MG_THREADS, 1) void fwd_bwd_mfma_ws_kernel(UPD_LEAD_PARAMS, UpdateArgs /* read inside the bodies, through mg_args_behind_here */) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
+    const UpdLead h{idx, rec_critic, rec_actor, params, M, nb0};
     const int b = blockIdx.x;   // 1-D grid: the first n_blocks[0] workgroups run the critic, the rest the actor
-    if (b < a.n_blocks[0]) mg_body<0, DIST, OBS, 1>(a, smem, b, a.n_blocks[0]);
-    else mg_body<1, DIST, OBS, AMAX>(a, smem, b - a.n_blocks[0], a.n_blocks[1]);
+    if (b < nb0) mg_body<0, DIST, OBS, 1>(h, smem, b, nb0);   // `a` is read inside, behind the first row loads (mg_args_behind_here)
+    else mg_body<1, DIST, OBS, AMAX>(h, smem, b - nb0, nb1);
 }
+
+// the signature above against the image UPD_ARGS_OFFSET is computed from: parameter for parameter, the struct last
+static_assert(std::is_same<decltype(&fwd_bwd_mfma_ws_kernel<PPO_DIST_CATEGORICAL, 4, 2>),
+                           void (*)(decltype(UpdLeadImage::idx), decltype(UpdLeadImage::rec_critic), decltype(UpdLeadImage::rec_actor), decltype(UpdLeadImage::params),
+                                    decltype(UpdLeadImage::M), decltype(UpdLeadImage::nb0), decltype(UpdLeadImage::nb1), UpdateArgs)>::value,
+              "fwd_bwd_mfma_ws_kernel's leading parameters are not UpdLeadImage's members: UPD_ARGS_OFFSET would point beside the struct");
+static_assert(UPD_LEAD_DWORDS == 11 && UPD_ARGS_OFFSET == 48, "the leading parameters no longer fit the preload: see tests/test_kernarg_preload.py");
 
 // One 32-byte record per sample and net for the update kernel's gather (K5): critic {obs[0..3], return, old value, 0, 0}, actor
 // {obs[0..3], old log-prob, advantage, actions (8 bits per head), mask bits} (obs zero-padded to 4).  The flattened rollout buffers
@@ -1870,9 +1893,9 @@ __global__ __launch_bounds__(256) void pack_records_kernel(const float* __restri
 // "gather" is one coalesced 16-byte load per row.
 // ---------------------------------------------------------------------------------------------------------
 template <int OBS>
-__global__ __launch_bounds__(256, 2) void values_mfma_kernel(const float* __restrict__ P, NetLayout L, const float* __restrict__ obs0, int64_t n0,
+__global__ __launch_bounds__(256, 2) void values_mfma_kernel(const float* __restrict__ P, const float* __restrict__ obs0, int64_t n0,
                                                              float* __restrict__ out0, const float* __restrict__ obs1, int64_t n1,
-                                                             float* __restrict__ out1) {
+                                                             float* __restrict__ out1, NetLayout L) {   // the layout LAST: 14 leading dwords are preloaded
     __shared__ __attribute__((aligned(16))) uint16_t sW2p[2 * 64 * WS];
     __shared__ __attribute__((aligned(16))) float sB1[64], sB2[64], sW3[64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -2247,8 +2270,8 @@ hipError_t launch_minibatch_fwd_bwd_mfma(const UpdateArgs& a, hipStream_t s) {
         hipError_t e = allow_dynamic_lds(lds_ok, reinterpret_cast<const void*>(&fwd_bwd_mfma_kernel<DIST, OBS, AMAX, EXACT, false>)); \
         if (e == hipSuccess && a.stamps) e = allow_dynamic_lds(lds_ok_stamp, reinterpret_cast<const void*>(&fwd_bwd_mfma_kernel<DIST, OBS, AMAX, EXACT, true>)); \
         if (e != hipSuccess) return e;                                                                                 \
-        if (a.stamps) hipLaunchKernelGGL((fwd_bwd_mfma_kernel<DIST, OBS, AMAX, EXACT, true>), grid, block, shmem, s, a); \
-        else hipLaunchKernelGGL((fwd_bwd_mfma_kernel<DIST, OBS, AMAX, EXACT, false>), grid, block, shmem, s, a);       \
+        if (a.stamps) hipLaunchKernelGGL((fwd_bwd_mfma_kernel<DIST, OBS, AMAX, EXACT, true>), grid, block, shmem, s, UPD_LEAD_ARGS(a), a); \
+        else hipLaunchKernelGGL((fwd_bwd_mfma_kernel<DIST, OBS, AMAX, EXACT, false>), grid, block, shmem, s, UPD_LEAD_ARGS(a), a);       \
     } while (0)
     // the reference's two shapes get fully folded head code: CartPole (obs 4, one head of 2) and MountainCar (obs 2, one masked
     // head of 3); anything else with <= 4 logits runs the generic variant
@@ -2273,11 +2296,11 @@ hipError_t launch_minibatch_fwd_bwd_mfma(const UpdateArgs& a, hipStream_t s) {
             if (cart) {
                 hipError_t e = allow_dynamic_lds(ws_ok_c, reinterpret_cast<const void*>(&fwd_bwd_mfma_ws_kernel<PPO_DIST_CATEGORICAL, 4, 2>));
                 if (e != hipSuccess) return e;
-                hipLaunchKernelGGL((fwd_bwd_mfma_ws_kernel<PPO_DIST_CATEGORICAL, 4, 2>), grid, ws_block, ws_shmem, s, a);
+                hipLaunchKernelGGL((fwd_bwd_mfma_ws_kernel<PPO_DIST_CATEGORICAL, 4, 2>), grid, ws_block, ws_shmem, s, UPD_LEAD_ARGS(a), a);
             } else {
                 hipError_t e = allow_dynamic_lds(ws_ok_m, reinterpret_cast<const void*>(&fwd_bwd_mfma_ws_kernel<PPO_DIST_MASKED, 2, 3>));
                 if (e != hipSuccess) return e;
-                hipLaunchKernelGGL((fwd_bwd_mfma_ws_kernel<PPO_DIST_MASKED, 2, 3>), grid, ws_block, ws_shmem, s, a);
+                hipLaunchKernelGGL((fwd_bwd_mfma_ws_kernel<PPO_DIST_MASKED, 2, 3>), grid, ws_block, ws_shmem, s, UPD_LEAD_ARGS(a), a);
             }
             return hipGetLastError();
         }
@@ -2324,8 +2347,8 @@ hipError_t launch_values_mfma(const float* params, const NetLayout& L, const flo
     if (n <= 0) return hipSuccess;
     const int64_t wg_needed = ((n + MT - 1) / MT + 3) / 4;
     const unsigned grid = (unsigned)(wg_needed < 1024 ? wg_needed : 1024);
-    if (L.obs == 4) hipLaunchKernelGGL((values_mfma_kernel<4>), dim3(grid), dim3(256), 0, s, params, L, obs0, n0, out0, obs1, n1, out1);
-    else if (L.obs == 2) hipLaunchKernelGGL((values_mfma_kernel<2>), dim3(grid), dim3(256), 0, s, params, L, obs0, n0, out0, obs1, n1, out1);
+    if (L.obs == 4) hipLaunchKernelGGL((values_mfma_kernel<4>), dim3(grid), dim3(256), 0, s, params, obs0, n0, out0, obs1, n1, out1, L);
+    else if (L.obs == 2) hipLaunchKernelGGL((values_mfma_kernel<2>), dim3(grid), dim3(256), 0, s, params, obs0, n0, out0, obs1, n1, out1, L);
     else return hipErrorNotSupported;
     return hipGetLastError();
 }

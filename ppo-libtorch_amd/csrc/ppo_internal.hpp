@@ -7,7 +7,9 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
+#include <type_traits>
 #include <cstdio>
 #include <string>
 
@@ -678,6 +680,18 @@ struct UpdateArgs {
     int32_t* error_flag;     // the context's device error word (bit 0: reset table exhausted; PPO_ERRFLAG_UPDATE_PROTOCOL: a bounded wait of the wave-specialised update kernel ran out)
     int single_wave;         // 1: the one-wave-per-tile matrix-core kernel even for the reference's two shapes (A/B; ppo_config.kernel_flags)
 };
+// The update kernels' LEADING kernel parameters: copies of the UpdateArgs members at the head of their dependent chain (fetch_row's operands, the first
+// record load, the weight staging's base), passed as scalars in front of the struct so that they are preloaded into SGPRs at wave launch (csrc/Makefile:
+// kernel-argument preloading; a by-value struct never is).  4 pointers + 3 ints = 11 dwords.  The bodies take them as an UpdLead.
+struct UpdLead { const int32_t* idx; const float* rec_critic; const float* rec_actor; const float* params; int M; int nb0; };
+#define UPD_LEAD_PARAMS const int32_t* idx, const float* rec_critic, const float* rec_actor, const float* params, int M, int nb0, int nb1
+#define UPD_LEAD_ARGS(a) (a).idx, (a).rec_critic, (a).rec_actor, (a).params, (a).M, (a).n_blocks[0], (a).n_blocks[1]
+// UPD_LEAD_PARAMS as the kernel-argument segment lays them out, and where the struct behind them starts there.  kernels_update_mfma.hip holds the
+// wave-specialised kernel's real signature to this image (a static_assert on its function type), so a leading parameter added or reordered in one place only
+// does not compile.
+struct UpdLeadImage { const int32_t* idx; const float* rec_critic; const float* rec_actor; const float* params; int M; int nb0; int nb1; };
+constexpr size_t UPD_LEAD_DWORDS = (offsetof(UpdLeadImage, nb1) + sizeof(int)) / 4;
+constexpr size_t UPD_ARGS_OFFSET = (UPD_LEAD_DWORDS * 4 + alignof(UpdateArgs) - 1) / alignof(UpdateArgs) * alignof(UpdateArgs);
 constexpr int32_t PPO_ERRFLAG_UPDATE_PROTOCOL = 2;
 constexpr int32_t PPO_ERRFLAG_GAE_PROTOCOL = 16;   // gae_pipe_kernel: a bounded wait between its mover waves and its walker ran out (that strip's advantages / returns are NaN)
 constexpr int32_t PPO_ERRFLAG_UPDATE_RANGE = 8;    // a matrix-core update kernel met an observation that does not fit its fp16 operand (|obs| >= 65 504)
