@@ -5,9 +5,9 @@ mlp_backward1) and restates the synthetic env with integer arithmetic (orc_synth
 Per shape: the env's observations / masks / rewards / done flags in the rollout buffers bit-exact; log-probs, values and the sampler
 against the oracle's forward; advantages / returns bit-exact; one minibatch step (losses 1e-5, gradient 1e-4 of max) and the
 optimizer step; then whole updates run.  The gradient is held twice: as one flat vector within 1e-4 (f32) / 6e-4 (bf16) of its largest element, and tensor by
-tensor, each against its OWN largest element (f32: the float64 oracle of tests/grad_oracle.py and the bar of tests/test_gpu_generic_grads.py; bf16: a fence at
-3 x the worst per-tensor distance to the bf16 oracle measured for the shape, TENSOR_FENCE_BF16 -- unmeasured so far, printed only).  That step is at ratio = 1; the step off it is
-tests/test_gpu_generic_grads.py's.
+tensor, each against its OWN largest element (f32: the float64 oracle of tests/grad_oracle.py and the bar of tests/test_gpu_generic_grads.py; bf16: the bf16
+oracle, tensor t within grad_oracle.bf16_tensor_bars = max(d_b16[t], median(d_b16)), d_b16 = that oracle's own distance from float64 on the same rows).  That step
+is at ratio = 1 and v = v_old, so no row is near a branch and the rows need no filtering; the step off it is tests/test_gpu_generic_grads.py's.
 """
 import numpy as np
 import pytest
@@ -42,13 +42,7 @@ def P():
 TOL = {0: dict(fwd=5e-6, fwd_v=5e-6, agree=0.995, loss=1e-5, grad=1e-4, same=1e-6), 1: dict(fwd=2e-3, fwd_v=4e-3, agree=0.98, loss=6e-6, grad=6e-4, same=1e-6)}
 
 
-# bf16, per tensor: the worst distance of any tensor to the bf16 oracle (of the tensor's own largest element) measured on an MI355X at the shape, by test; bar = 3 x.
-# UNMEASURED so far (no value is invented): a shape without an entry prints its per-tensor distances and is held by the whole-vector bar alone.
-TENSOR_FENCE_BF16 = {
-}
-
-
-def _check_shape(P, obs_dim, hidden, n_hidden, heads, N, T, nmb, masked, seed, max_steps=40, dtype=0, fence_key=None):
+def _check_shape(P, obs_dim, hidden, n_hidden, heads, N, T, nmb, masked, seed, max_steps=40, dtype=0):
     A, H = sum(heads), len(heads)
     tol = TOL[dtype]
     hp = dict(gamma=0.99, gae_lambda=0.95, clip_coef=0.2, ent_coef=0.01, vf_coef=0.5, max_grad_norm=0.5)
@@ -128,15 +122,14 @@ def _check_shape(P, obs_dim, hidden, n_hidden, heads, N, T, nmb, masked, seed, m
     assert np.abs(grads - g_o).max() <= 1e-6 + tol["grad"] * np.abs(g_o).max(), np.abs(grads - g_o).max() / np.abs(g_o).max()
     # ... and tensor by tensor, each against its own largest element (the actor's x 30 head dominates the flat vector)
     names = [GO.tensor_name(n_, l_, k_) for _, n_, l_, k_, _ in GO.split(g_o, shp)]
+    g64 = GO.minibatch_grads(shp, heads, masked, dict(hp, norm_adv=True, clip_vloss=True), params, flat_obs, flat_act, logp.reshape(B), adv.reshape(B), ret.reshape(B),
+                             values.reshape(B), idx, flat_mask if masked else None)[0]
+    d_ref = GO.tensor_distance(g_o, g64, shp)          # the oracle's own distance from float64 in this arithmetic: the unit of either bar
     if dtype == 0:
-        g64 = GO.minibatch_grads(shp, heads, masked, dict(hp, norm_adv=True, clip_vloss=True), params, flat_obs, flat_act, logp.reshape(B), adv.reshape(B), ret.reshape(B),
-                                 values.reshape(B), idx, flat_mask if masked else None)[0]
-        d_ref, d_t = GO.tensor_distance(g_o, g64, shp), GO.tensor_distance(grads, g64, shp)
-        bars = GO.f32_tensor_bars(d_ref)
+        d_t, bars = GO.tensor_distance(grads, g64, shp), GO.f32_tensor_bars(d_ref)
     else:
-        d_t = GO.tensor_distance(grads, g_o, shp)
-        bars = np.full(d_t.size, 3 * TENSOR_FENCE_BF16.get(fence_key, np.inf))   # (no entry: not measured yet -- printed, not fenced)
-    print("per tensor:", ", ".join("%s %.1e" % (n_, x) for n_, x in zip(names, d_t)), "| worst %.1e" % d_t.max())
+        d_t, bars = GO.tensor_distance(grads, g_o, shp), GO.bf16_tensor_bars(d_ref)
+    print("per tensor:", ", ".join("%s %.1e (bar %.1e)" % (n_, x, b_) for n_, x, b_ in zip(names, d_t, bars)), "| worst %.1e, worst of bar %.2f" % (d_t.max(), (d_t / bars).max()))
     assert (d_t <= bars).all(), [(n_, float(x), float(b_)) for n_, x, b_ in zip(names, d_t, bars) if not x <= b_]
     ctx.set_learning_rate(1e-3)
     ctx.optimizer_step()
@@ -185,21 +178,20 @@ def test_config4_shape_in_bf16(P):
     stored activations, f32 accumulation, f32 master weights) -- end to end against the oracle's bf16 mode (oracle/ppo_oracle.h: ORC_DTYPE_BF16),
     which rounds at the same points: rollout log-probs / values, the sampler, one minibatch step's losses and gradient, the optimizer step.  The bars are regression fences
     (TOL above), not parity with the reference: the f32 path carries that (tests/test_gpu_config4_ref.py)."""
-    _check_shape(P, obs_dim=376, hidden=256, n_hidden=4, heads=(3, 3, 3, 2), N=256, T=32, nmb=4, masked=True, seed=3, max_steps=25, dtype=1, fence_key="config4")
+    _check_shape(P, obs_dim=376, hidden=256, n_hidden=4, heads=(3, 3, 3, 2), N=256, T=32, nmb=4, masked=True, seed=3, max_steps=25, dtype=1)
 
 
 def test_bf16_ragged_shapes(P):
     """bf16 storage with widths that fill neither a tile nor a chunk (hidden 48 in a 128-wide pitch, obs 20, 5 logits) and a minibatch that is
     not a multiple of the 64-row contraction step (48 envs x 10 steps / 2 = 240 rows): the zero padding of every buffer is what the
     unguarded staging relies on."""
-    _check_shape(P, obs_dim=20, hidden=48, n_hidden=2, heads=(2, 3), N=48, T=10, nmb=2, masked=True, seed=13, dtype=1, fence_key="ragged")
+    _check_shape(P, obs_dim=20, hidden=48, n_hidden=2, heads=(2, 3), N=48, T=10, nmb=2, masked=True, seed=13, dtype=1)
 
 
 @pytest.mark.parametrize("masked", [True, False])
 def test_bf16_many_heads(P, masked):
     """bf16 storage beyond four heads / sixteen logits: the loss kernel's second register layout (eight heads, 32 logits -- the ABI's maximum)."""
-    _check_shape(P, obs_dim=24, hidden=64, n_hidden=2, heads=(5, 3, 4, 2, 3, 3), N=64, T=12, nmb=2, masked=masked, seed=21, dtype=1,
-                 fence_key="many heads masked" if masked else "many heads")
+    _check_shape(P, obs_dim=24, hidden=64, n_hidden=2, heads=(5, 3, 4, 2, 3, 3), N=64, T=12, nmb=2, masked=masked, seed=21, dtype=1)
 
 
 @pytest.mark.parametrize("dtype", [0, 1])
