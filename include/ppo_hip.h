@@ -408,6 +408,35 @@ PPO_API ppo_status ppo_stats_snapshot_read(ppo_ctx* ctx, ppo_stats* out);
 PPO_API ppo_status ppo_set_learning_rate(ppo_ctx* ctx, double lr);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Early stop at a target KL (extension: the reference's epoch loop, PPO_Discrete.cpp:567-644, is CleanRL's without
+ * `if target_kl is not None and approx_kl > target_kl: break`; the estimator is the reference's, :352)
+ * ------------------------------------------------------------------------------------------------------- */
+/* CleanRL's semantics, decided on the device: ppo_update enqueues all update_epochs x num_minibatches steps at once, as always, and nothing inside it waits
+ * for the GPU.  With target_kl > 0, behind the optimizer step of the LAST minibatch of every epoch e a one-workgroup launch compares that step's approx_kl
+ * -- the float the step writes to its statistics, the job's value on sharded contexts, so every rank decides alike -- with the target (a NaN compares
+ * false).  Above it, no later optimizer step of this update is applied: parameters, both AdamW moments and the applied-step count stay as epoch e left
+ * them, and the update's statistics stay those of the last applied step (all of ppo_stats: clipfrac_mean is the mean over the applied steps,
+ * optimizer_steps counts applied steps; explained variance does not depend on the steps).  The stop travels as one more bit of the context's device error
+ * word, which the optimizer kernels already read (they apply no step behind a device-side error either); it is not an error, no reader reports it, and it
+ * is cleared before the update ends: the stand-alone ppo_minibatch_forward_backward / ppo_allreduce_grads / ppo_optimizer_step never stop.
+ * Cost: update_epochs + 1 small launches per update, and ppo_update first waits for the PREVIOUS update's outcome (one event behind one small copy; for
+ * nothing enqueued after that update) to know how many steps were applied: the AdamW bias corrections are formed on the host per applied step.  A caller-
+ * stepped context never blocks there (a whole host rollout lies between two updates); a host that runs ahead on the device envs loses part of its lead.
+ * NOT built: the forward / backward launches of the unapplied steps still run and their results are discarded, so an update that stops early takes as long
+ * as one that does not.
+ * target_kl = 0 (the default) is off, and off is off: a context that never sets a target, or sets it back to 0, enqueues exactly the launches it always
+ * did and produces the same bits.  A negative or non-finite target returns PPO_ERR_INVALID and changes nothing.  Valid on every context kind, at any time;
+ * takes effect at the next ppo_update (the one inside ppo_train_iteration and ppo_host_rollout_end included). */
+PPO_API ppo_status ppo_target_kl_set(ppo_ctx* ctx, double target_kl);
+PPO_API ppo_status ppo_target_kl_get(ppo_ctx* ctx, double* out);
+/* The last ppo_update's outcome: epochs whose steps were applied, whether a stop was raised, the approx_kl that raised it (0.0 when none did), and the sum of
+ * epochs_run over all updates of the context.  Waits for that update only, not for work enqueued behind it.  Before any update: 0, 0, 0.0, 0.  With the
+ * feature off: epochs_run = update_epochs, stopped = 0 (no wait at all).  Any output may be NULL.  ppo_stats.optimizer_steps, ppo_optimizer_get_h's step and
+ * the statistics snapshots report applied steps as well, and a stand-alone ppo_optimizer_step behind a stopped update continues from them.  After a
+ * ppo_update that FAILED with a target set the stop is still cleared, but the step and epoch counts are undefined. */
+PPO_API ppo_status ppo_early_stop_read(ppo_ctx* ctx, int32_t* epochs_run, int32_t* stopped, double* kl_at_stop, int64_t* epochs_total);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Caller-stepped environments (PPO_ENV_HOST contexts; PPO_Discrete::initEnvs / stepEnvs / train, PPO_Discrete.cpp:365-483, 511-548)
  *
  *   ppo_host_env_reset(ctx, obs0)                                    once: every env's reset observation

@@ -57,6 +57,7 @@ ABI_SYMBOLS = [
     "ppo_reward_norm_enable", "ppo_reward_norm_get_h", "ppo_reward_norm_set_h",
     "ppo_env_truncation_bootstrap", "ppo_env_truncations",
     "ppo_host_act_f32", "ppo_dev_act_f32", "ppo_policy_act_f32", "ppo_gaussian",
+    "ppo_target_kl_set", "ppo_target_kl_get", "ppo_early_stop_read",
 ]
 
 
@@ -165,6 +166,9 @@ def lib():
         L.ppo_dev_act_f32.argtypes = [C.c_void_p] * 3
         L.ppo_policy_act_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32] + [C.c_void_p] * 4
         L.ppo_gaussian.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 4
+        L.ppo_target_kl_set.argtypes = [C.c_void_p, C.c_double]
+        L.ppo_target_kl_get.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        L.ppo_early_stop_read.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int64)]
         for name in ABI_SYMBOLS:
             getattr(L, name)  # AttributeError if the build lacks a declared symbol
         if L.ppo_abi_version() != ABI_VERSION:
@@ -647,6 +651,21 @@ class Context:
 
     def set_learning_rate(self, lr):
         _check(lib().ppo_set_learning_rate(self.h, C.c_double(lr)), self.h)
+
+    def target_kl_set(self, target_kl):
+        """Early stop at a target KL (ppo_hip.h: ppo_target_kl_set): 0 = off; takes effect at the next update."""
+        _check(lib().ppo_target_kl_set(self.h, float(target_kl)), self.h)
+
+    def target_kl_get(self):
+        out = C.c_double(0.0)
+        _check(lib().ppo_target_kl_get(self.h, C.byref(out)), self.h)
+        return out.value
+
+    def early_stop(self):
+        """The last update's outcome (ppo_early_stop_read); waits for that update only."""
+        run, stopped, kl, total = C.c_int32(0), C.c_int32(0), C.c_double(0.0), C.c_int64(0)
+        _check(lib().ppo_early_stop_read(self.h, C.byref(run), C.byref(stopped), C.byref(kl), C.byref(total)), self.h)
+        return {"epochs_run": run.value, "stopped": stopped.value, "kl_at_stop": kl.value, "epochs_total": total.value}
 
     def update(self):
         _check(lib().ppo_update(self.h), self.h)

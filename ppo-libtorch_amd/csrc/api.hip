@@ -109,7 +109,9 @@ struct StatsSnap {
     EpisodeRing ring;
     double gstats[PPO_GSTAT_DOUBLES];
     int32_t error_flag, xchg_flag;
+    int64_t es_applied;   // early stop: the applied optimizer steps as the last update's epilogue left them (copied only while that update is unresolved)
     // host side
+    int64_t es_nominal;   // ... and what the host counted for the same steps (0 with es_applied 0: opt_step is exact)
     bool have_step, have_ev, have_gstats;
     int world;
     int64_t B, global_step, opt_step, updates;
@@ -301,6 +303,20 @@ struct ppo_ctx {
     bool have_ev = false;
     int last_stat_slot = -1;
     double last_global_M = 1.0;
+
+    // early stop at a target KL (ppo_target_kl_set; kernels_earlystop.hip).  Nothing here is allocated, and nothing is launched, until a positive target is set.
+    // An update with a target counts every enqueued step in opt_step (es_nominal = its value behind the loop) and leaves es_pending set; es_resolve
+    // waits for that update's epilogue only and takes the steps it did not apply off opt_step and the epochs off epochs_total.
+    double target_kl = 0.0;
+    EarlyStopDev* es_dev = nullptr;
+    EarlyStopHost* es_host = nullptr;   // pinned; the head of *es_dev as the last update with a target left it
+    hipEvent_t es_ev = nullptr;         // behind that copy
+    bool es_pending = false;
+    int64_t es_nominal = 0;
+    int32_t es_E = 0;                   // update_epochs of the pending update
+    bool es_last_on = false;            // the last update ran with a target
+    EarlyStopHost es_last{};            // its outcome, once resolved
+    int64_t epochs_total = 0;           // epochs applied by all updates so far
 
     // statistics snapshot (ppo_stats_snapshot / ppo_stats_snapshot_read): everything ppo_read_stats decodes, copied asynchronously into ONE pinned block
     // behind the work enqueued so far; the reader waits for the snapshot's event only, so a host may enqueue the next iteration before it reads
@@ -507,6 +523,8 @@ extern "C" void ppo_ctx_destroy(ppo_ctx* c) {
     if (c->envt_ev) (void)hipEventDestroy(c->envt_ev);
     if (c->wr_host) (void)hipHostFree(c->wr_host);
     if (c->snap) (void)hipHostFree(c->snap);
+    if (c->es_host) (void)hipHostFree(c->es_host);
+    if (c->es_ev) (void)hipEventDestroy(c->es_ev);
     for (hipEvent_t e : c->snap_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->coef_copied) if (e) (void)hipEventDestroy(e);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
@@ -884,12 +902,16 @@ extern "C" ppo_status ppo_params_get_h(ppo_ctx* c, float* params_h, int64_t coun
     NEED(c, count == c->L.P, "parameter count mismatch");
     return ppo_memcpy_d2h(c, params_h, c->buf[PPO_BUF_PARAMS], (size_t)count * sizeof(float));
 }
+static ppo_status es_resolve(ppo_ctx* c);
 extern "C" ppo_status ppo_optimizer_set_h(ppo_ctx* c, const float* m_h, const float* v_h, int64_t count, int64_t step) {
     NEED(c, c && m_h && v_h, "null argument");
     NEED(c, count == c->L.P, "parameter count mismatch");
     ppo_status s = ppo_memcpy_h2d(c, c->buf[PPO_BUF_EXP_AVG], m_h, (size_t)count * sizeof(float));
     if (s != PPO_OK) return s;
     s = ppo_memcpy_h2d(c, c->buf[PPO_BUF_EXP_AVG_SQ], v_h, (size_t)count * sizeof(float));
+    if (s != PPO_OK) return s;
+    s = es_resolve(c);
+    if (s != PPO_OK) return s;
     c->opt_step = step;
     return s;
 }
@@ -899,7 +921,10 @@ extern "C" ppo_status ppo_optimizer_get_h(ppo_ctx* c, float* m_h, float* v_h, in
     ppo_status s = PPO_OK;
     if (m_h) s = ppo_memcpy_d2h(c, m_h, c->buf[PPO_BUF_EXP_AVG], (size_t)count * sizeof(float));
     if (s == PPO_OK && v_h) s = ppo_memcpy_d2h(c, v_h, c->buf[PPO_BUF_EXP_AVG_SQ], (size_t)count * sizeof(float));
-    if (step) *step = c->opt_step;
+    if (s == PPO_OK && step) {
+        s = es_resolve(c);   // applied steps: an update that stopped at its target KL applied fewer than it enqueued
+        *step = c->opt_step;
+    }
     return s;
 }
 
@@ -1811,7 +1836,7 @@ static hipError_t clip_adamw_any(ppo_ctx* c, int slot, double global_M, int worl
         if (do_step) c->gen->planes_dirty = true;
         return gen_clip_adamw(B_<float>(c, PPO_BUF_PARAMS), B_<float>(c, PPO_BUF_GRADS), B_<float>(c, PPO_BUF_EXP_AVG), B_<float>(c, PPO_BUF_EXP_AVG_SQ),
                               c->gen->L, c->cfg.max_grad_norm, c->adam_coefs + slot, c->loss_sums, global_M, c->hp, world, do_step,
-                              c->step_stats + slot, clipfrac_accum, c->norm2, c->stream);
+                              c->step_stats + slot, clipfrac_accum, c->norm2, c->error_flag, c->stream);
     }
     return launch_clip_adamw(B_<float>(c, PPO_BUF_PARAMS), B_<float>(c, PPO_BUF_GRADS), B_<float>(c, PPO_BUF_EXP_AVG), B_<float>(c, PPO_BUF_EXP_AVG_SQ),
                              c->L, c->cfg.max_grad_norm, c->adam_coefs + slot, c->loss_sums, global_M, c->hp, world, do_step,
@@ -1874,6 +1899,9 @@ extern "C" ppo_status ppo_optimizer_step(ppo_ctx* c) {
     DeviceGuard dev_guard(c);
     // stand-alone use: the slot's pinned coefficient must not be rewritten while a previous copy is in flight
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    // the coefficient is formed from the APPLIED step count: an update that stopped at its target KL enqueued more steps than it applied
+    const ppo_status rs = es_resolve(c);
+    if (rs != PPO_OK) return rs;
     const ppo_status s = optimizer_step_slot(c, c->steps_per_update, c->last_global_M, false);
     return s != PPO_OK ? s : sweep_weight_range(c, c->stream);
 }
@@ -1881,6 +1909,51 @@ extern "C" ppo_status ppo_optimizer_step(ppo_ctx* c) {
 extern "C" ppo_status ppo_set_learning_rate(ppo_ctx* c, double lr) {
     NEED(c, c != nullptr, "null ctx");
     c->lr = lr;
+    return PPO_OK;
+}
+
+// Early stop at a target KL: the host's view of the last update that ran with a target.  Waits for that update's epilogue only (one event behind one
+// small copy), never for work enqueued behind it.
+static ppo_status es_resolve(ppo_ctx* c) {
+    if (!c->es_pending) return PPO_OK;
+    DeviceGuard dev_guard(c);
+    HIPCHK(c, hipEventSynchronize(c->es_ev));
+    c->es_pending = false;
+    c->es_last = *c->es_host;
+    c->opt_step -= c->es_nominal - c->es_last.applied_total;   // (stand-alone steps taken since stay counted)
+    c->epochs_total -= c->es_E - c->es_last.epochs_run;
+    return PPO_OK;
+}
+
+extern "C" ppo_status ppo_target_kl_set(ppo_ctx* c, double target_kl) {
+    NEED(c, c != nullptr, "null ctx");
+    if (!std::isfinite(target_kl) || target_kl < 0.0) return fail(c, PPO_ERR_INVALID, "target_kl must be finite and >= 0 (0 = off), got %g", target_kl);
+    if (target_kl > 0.0 && !c->es_dev) {
+        DeviceGuard dev_guard(c);
+        if (!c->es_host) HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->es_host), sizeof(EarlyStopHost)));
+        std::memset(c->es_host, 0, sizeof(EarlyStopHost));
+        if (!c->es_ev) HIPCHK(c, hipEventCreateWithFlags(&c->es_ev, hipEventDisableTiming));
+        HIPCHK(c, dalloc(c, &c->es_dev, 1));   // last: the launches ask for this one
+    }
+    c->target_kl = target_kl;
+    return PPO_OK;
+}
+
+extern "C" ppo_status ppo_target_kl_get(ppo_ctx* c, double* out) {
+    NEED(c, c && out, "null argument");
+    *out = c->target_kl;
+    return PPO_OK;
+}
+
+extern "C" ppo_status ppo_early_stop_read(ppo_ctx* c, int32_t* epochs_run, int32_t* stopped, double* kl_at_stop, int64_t* epochs_total) {
+    NEED(c, c != nullptr, "null ctx");
+    const ppo_status s = es_resolve(c);
+    if (s != PPO_OK) return s;
+    const bool any = c->updates > 0;
+    if (epochs_run) *epochs_run = !any ? 0 : (c->es_last_on ? c->es_last.epochs_run : c->cfg.update_epochs);
+    if (stopped) *stopped = any && c->es_last_on ? c->es_last.stopped : 0;
+    if (kl_at_stop) *kl_at_stop = any && c->es_last_on ? c->es_last.kl_at_stop : 0.0;
+    if (epochs_total) *epochs_total = c->epochs_total;
     return PPO_OK;
 }
 
@@ -1941,12 +2014,35 @@ extern "C" ppo_status ppo_update(ppo_ctx* c) {
         c->coef_half ^= 1;
         AdamCoef* h = c->adam_coefs_h + (size_t)half * (c->steps_per_update + 1);
         HIPCHK(c, hipEventSynchronize(c->coef_copied[half]));
+        // the table starts at the APPLIED step count: an update that stopped at its target KL applied fewer steps than it enqueued (es_resolve waits for
+        // that update's epilogue, nothing behind it; no-op unless such an update is unresolved)
+        s = es_resolve(c);
+        if (s != PPO_OK) return s;
         for (int k = 0; k < E * nmb; k++) h[k] = adam_coef(c->lr, c->opt_step + 1 + k);
         HIPCHK(c, hipMemcpyAsync(c->adam_coefs, h, (size_t)E * nmb * sizeof(AdamCoef), hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipEventRecord(c->coef_copied[half], c->stream));
     }
     if (!c->cfg.norm_adv) HIPCHK(c, hipMemsetAsync(c->clipfrac_accum, 0, 2 * sizeof(double), c->stream));  // m_clipfracs reset, :564 (with norm_adv: cleared by the adv_norm launch above)
     c->gen_pre_idx = nullptr;   // nothing gathered ahead survives an update (an error return may have left a claim behind)
+    // early stop at a target KL: one small launch behind the optimizer launch of every epoch's last minibatch, one behind the update (kernels_earlystop.hip);
+    // with no target set, none
+    const bool gated = c->target_kl > 0.0;
+    const int64_t applied_before = c->opt_step;
+    // an update that returns early with an error must not leave a raised stop behind: the epilogue is enqueued on every way out.  The step and epoch
+    // counts are undefined after such a failed update (include/ppo_hip.h): nobody knows how much of it was enqueued.
+    struct StopScope {
+        ppo_ctx* c; bool armed; int E, nmb; int64_t before;
+        ~StopScope() {
+            if (armed && c->last_stat_slot >= 0)
+                (void)launch_kl_gate_end(c->step_stats + c->last_stat_slot, c->clipfrac_accum, c->error_flag, c->es_dev, E, nmb, before, c->stream);
+        }
+    } stop_scope{ c, false, E, nmb, applied_before };
+    auto kl_gate = [&](int e, int mbi, int slot) -> ppo_status {
+        if (!gated || mbi != nmb - 1) return PPO_OK;
+        HIPCHK(c, launch_kl_gate(c->step_stats + slot, c->target_kl, e, c->clipfrac_accum, c->error_flag, c->es_dev, c->stream));
+        stop_scope.armed = true;
+        return PPO_OK;
+    };
     int k = 0;
     for (int e = 0; e < E; e++) {
         for (int mbi = 0; mbi < nmb; mbi++, k++) {
@@ -1976,6 +2072,8 @@ extern "C" ppo_status ppo_update(ppo_ctx* c) {
                                                             c->clipfrac_accum, c->fused_partial, x.peer, c->rank, c->world, x.slot_bytes, x.seq, x.timeout_flag,
                                                             c->stream, opt_guard(c)));
                 c->last_stat_slot = k;
+                s = kl_gate(e, mbi, k);
+                if (s != PPO_OK) return s;
                 continue;
             }
             if (fused) {
@@ -1986,13 +2084,28 @@ extern "C" ppo_status ppo_update(ppo_ctx* c) {
                                                    B_<float>(c, PPO_BUF_EXP_AVG), B_<float>(c, PPO_BUF_EXP_AVG_SQ), c->cfg.max_grad_norm, c->adam_coefs + k, (double)M,
                                                    c->hp, c->step_stats + k, c->clipfrac_accum, c->fused_partial, c->stream, opt_guard(c)));
                 c->last_stat_slot = k;
+                s = kl_gate(e, mbi, k);
+                if (s != PPO_OK) return s;
                 continue;
             }
             s = ppo_allreduce_grads(c);
             if (s != PPO_OK) return s;
             s = optimizer_step_slot(c, k, (double)M * c->world, true);
             if (s != PPO_OK) return s;
+            s = kl_gate(e, mbi, k);
+            if (s != PPO_OK) return s;
         }
+    }
+    c->es_last_on = gated;
+    c->epochs_total += E;
+    if (gated) {
+        stop_scope.armed = false;
+        HIPCHK(c, launch_kl_gate_end(c->step_stats + c->last_stat_slot, c->clipfrac_accum, c->error_flag, c->es_dev, E, nmb, applied_before, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->es_host, c->es_dev, sizeof(EarlyStopHost), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipEventRecord(c->es_ev, c->stream));
+        c->es_pending = true;
+        c->es_nominal = c->opt_step;
+        c->es_E = E;
     }
     c->have_ev = true;
     c->updates += 1;
@@ -3127,6 +3240,11 @@ extern "C" ppo_status ppo_stats_snapshot(ppo_ctx* c) {
     h->have_gstats = c->have_gstats;
     h->world = c->world; h->B = c->B; h->global_step = c->global_step; h->opt_step = c->opt_step; h->updates = c->updates; h->lr = c->lr;
     h->xchg_flag = 0;
+    h->es_applied = h->es_nominal = 0;
+    if (c->es_pending) {   // an update with a target KL whose outcome the host has not seen: the applied-step count its epilogue forms rides along
+        h->es_nominal = c->es_nominal;
+        HIPCHK(c, hipMemcpyAsync(&h->es_applied, &c->es_dev->applied_total, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    }
     HIPCHK(c, hipMemcpyAsync(&h->error_flag, c->error_flag, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     if (c->xchg && c->xchg->timeout_flag) HIPCHK(c, hipMemcpyAsync(&h->xchg_flag, c->xchg->timeout_flag, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     if (h->have_step) HIPCHK(c, hipMemcpyAsync(&h->st, c->step_stats + c->last_stat_slot, sizeof h->st, hipMemcpyDeviceToHost, c->stream));
@@ -3150,7 +3268,8 @@ extern "C" ppo_status ppo_stats_snapshot_read(ppo_ctx* c, ppo_stats* out) {
     HIPCHK(c, hipEventSynchronize(c->snap_ev[slot]));
     c->snap_oldest ^= 1;
     c->snap_count -= 1;
-    const StatsSnap& h = c->snap[slot];
+    StatsSnap& h = c->snap[slot];
+    h.error_flag &= ~PPO_ERRFLAG_NOT_ERRORS;   // the KL gate's stop is not an error (and an update has cleared it by the time a snapshot behind it is taken)
     if (h.error_flag & 1) return fail(c, PPO_ERR_STATE, "CartPole reset-stream table exhausted (capacity %d resets per env)", c->reset_cap);
     if (h.error_flag & PPO_ERRFLAG_ROLLOUT_RANGE)
         return fail(c, PPO_ERR_STATE, "rollout: an output-layer weight of the actor is >= 255 in magnitude and does not fit the fp16 operand of the matrix-core rollout "
@@ -3225,7 +3344,7 @@ extern "C" ppo_status ppo_stats_snapshot_read(ppo_ctx* c, ppo_stats* out) {
     }
     out->learning_rate = h.lr;
     out->global_step = h.global_step;
-    out->optimizer_steps = h.opt_step;
+    out->optimizer_steps = h.opt_step - (h.es_nominal - h.es_applied);   // applied steps
     out->updates = h.updates;
     return PPO_OK;
 }

@@ -201,7 +201,7 @@ hipError_t gen_loss_sums(const GenericCtx& g, double* sums_out, float* grads_tai
 hipError_t gen_fill(float* p, int64_t n, float v, hipStream_t s);
 hipError_t gen_clip_adamw(float* params, float* grads, float* exp_avg, float* exp_avg_sq, const GenLayout& L, float max_grad_norm, const AdamCoef* coef,
                           const double* loss_sums, double global_M, LossParams hp, int world, bool do_step, StepStats* stats_out,
-                          double* clipfrac_accum, double* norm2_scratch, hipStream_t s);
+                          double* clipfrac_accum, double* norm2_scratch, const int32_t* error_flag, hipStream_t s);
 hipError_t gen_synthetic_step(const GenLayout& L, int N, int64_t seed, int64_t env_offset, int64_t step_index, int max_episode_steps, int32_t* ep_len,
                               float* ep_rew, float* obs_out, uint8_t* mask_out, float* reward, int32_t* done, int32_t* fin_len, float* fin_rew,
                               hipStream_t s);

@@ -614,7 +614,9 @@ __global__ __launch_bounds__(256) void gen_norm_kernel(const float* __restrict__
 __global__ __launch_bounds__(256) void gen_adamw_kernel(float* __restrict__ params, const float* __restrict__ grads, float* __restrict__ exp_avg,
                                                         float* __restrict__ exp_avg_sq, GenLayout L, float max_norm, const double* __restrict__ norm2,
                                                         const AdamCoef* __restrict__ coef_p, const double* __restrict__ loss_sums, double global_M,
-                                                        LossParams hp, int world, int do_step, StepStats* stats_out, double* clipfrac_accum) {
+                                                        LossParams hp, int world, int do_step, StepStats* stats_out, double* clipfrac_accum,
+                                                        const int32_t* error_flag) {
+    const int32_t err = opt_guard_word(error_flag);   // requested with the step's other loads (OptGuard, ppo_internal.hpp)
     // total norm: thread t adds tensor t's partial sums (all its loads in flight), thread 0 adds the tensors -- the same sums in the same order
     // as one thread doing all of it (which every thread used to do: 320 dependent loads in front of the element-wise step)
     __shared__ double s_n2[4 * GEN_MAX_LAYERS + 1];
@@ -641,7 +643,7 @@ __global__ __launch_bounds__(256) void gen_adamw_kernel(float* __restrict__ para
     if (c > 1.0f) c = 1.0f;
     const AdamCoef k = *coef_p;
     const float b1 = 0.9f, b2 = 0.999f, omb1 = (float)(1.0 - 0.9), omb2 = (float)(1.0 - 0.999), eps = 1e-5f;
-    if (do_step) {
+    if (do_step && !(err & PPO_ERRFLAG_SKIP_STEP)) {   // a step the device knows is garbage, or one behind the update's KL stop, is not applied
         for (int p = blockIdx.x * 256 + threadIdx.x; p < L.P; p += gridDim.x * 256) {
             const float g = grads[p] * c;
             const float pi = params[p] * k.decay;
@@ -1307,11 +1309,12 @@ hipError_t gen_loss_sums(const GenericCtx& g, double* sums_out, float* grads_tai
 
 hipError_t gen_clip_adamw(float* params, float* grads, float* exp_avg, float* exp_avg_sq, const GenLayout& L, float max_grad_norm, const AdamCoef* coef,
                           const double* loss_sums, double global_M, LossParams hp, int world, bool do_step, StepStats* stats_out,
-                          double* clipfrac_accum, double* norm2_scratch, hipStream_t s) {
+                          double* clipfrac_accum, double* norm2_scratch, const int32_t* error_flag, hipStream_t s) {
+    if (!error_flag) return hipErrorInvalidValue;   // the kernel reads the word without a null check
     hipLaunchKernelGGL(gen_norm_kernel, dim3(L.n_tensors, GEN_NORM_PARTS), dim3(256), 0, s, grads, L, norm2_scratch);
     const int blocks = do_step ? (int)grid_for(L.P, 256) : 1;
     hipLaunchKernelGGL(gen_adamw_kernel, dim3(blocks), dim3(256), 0, s, params, grads, exp_avg, exp_avg_sq, L, max_grad_norm, norm2_scratch, coef, loss_sums,
-                       global_M, hp, world, do_step ? 1 : 0, stats_out, clipfrac_accum);
+                       global_M, hp, world, do_step ? 1 : 0, stats_out, clipfrac_accum, error_flag);
     return hipGetLastError();
 }
 

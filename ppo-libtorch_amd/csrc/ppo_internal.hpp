@@ -696,7 +696,11 @@ constexpr int32_t PPO_ERRFLAG_UPDATE_PROTOCOL = 2;
 constexpr int32_t PPO_ERRFLAG_GAE_PROTOCOL = 16;   // gae_pipe_kernel: a bounded wait between its mover waves and its walker ran out (that strip's advantages / returns are NaN)
 constexpr int32_t PPO_ERRFLAG_UPDATE_RANGE = 8;    // a matrix-core update kernel met an observation that does not fit its fp16 operand (|obs| >= 65 504)
 constexpr int32_t PPO_ERRFLAG_ROLLOUT_RANGE = 4;   // rollout16_kernel: |W3| does not fit the fp16 operand (pre-scaled by 2^8)
-constexpr int32_t PPO_ERRFLAG_SKIP_STEP = PPO_ERRFLAG_UPDATE_PROTOCOL | PPO_ERRFLAG_UPDATE_RANGE | PPO_ERRFLAG_GAE_PROTOCOL;   // the optimizer does not apply a step behind these
+// NOT an error: the update's KL gate (kernels_earlystop.hip) found approx_kl above the context's target; raised and cleared inside one ppo_update, and
+// masked out by every host-side reader of the word (PPO_ERRFLAG_NOT_ERRORS)
+constexpr int32_t PPO_ERRFLAG_KL_STOP = 32;
+constexpr int32_t PPO_ERRFLAG_NOT_ERRORS = PPO_ERRFLAG_KL_STOP;
+constexpr int32_t PPO_ERRFLAG_SKIP_STEP = PPO_ERRFLAG_UPDATE_PROTOCOL | PPO_ERRFLAG_UPDATE_RANGE | PPO_ERRFLAG_GAE_PROTOCOL | PPO_ERRFLAG_KL_STOP;   // the optimizer does not apply a step behind these
 int update_blocks_per_net(int M);
 hipError_t launch_minibatch_fwd_bwd(const UpdateArgs& a, hipStream_t s);
 // matrix-core version of the same kernel; sum(head_dims) <= 4, obs in {2, 4}: fp32 carried as two fp16 terms, three
@@ -747,6 +751,23 @@ hipError_t launch_reduce_grads(const float* slab, const double* stat_slab, const
 hipError_t launch_clip_adamw(float* params, float* grads, float* exp_avg, float* exp_avg_sq, const NetLayout& L, float max_grad_norm,
                              const AdamCoef* coef, const double* loss_sums, double global_M, LossParams hp, int world, bool do_step,
                              StepStats* stats_out, double* clipfrac_accum, double* norm2_scratch, hipStream_t s, OptGuard guard);
+// Early stop at a target KL (ppo_target_kl_set; kernels_earlystop.hip).  The device's record of one update: the head is what the host reads (copied into a
+// pinned EarlyStopHost behind the update's last launch), the tail what the unapplied steps overwrite.
+struct EarlyStopHost {
+    double kl_at_stop;       // approx_kl of the step that raised the stop (0 when none did)
+    int64_t applied_total;   // optimizer steps applied so far, this update included
+    int32_t epochs_run;      // epochs of this update whose steps were applied
+    int32_t stopped;
+};
+struct EarlyStopDev : EarlyStopHost {
+    StepStats saved;         // the statistics of the last applied step
+    double cf[2];            // clipfrac_accum as that step left it
+};
+// behind the optimizer launch of the last minibatch of epoch `epoch`: step_stat = that step's statistics
+hipError_t launch_kl_gate(const StepStats* step_stat, double target, int epoch, double* clipfrac_accum, int32_t* error_flag, EarlyStopDev* es, hipStream_t s);
+// behind the update's last step: last_stat = the slot the host reads (ppo_ctx::last_stat_slot); applied_before = the applied steps before this update
+hipError_t launch_kl_gate_end(StepStats* last_stat, double* clipfrac_accum, int32_t* error_flag, EarlyStopDev* es, int epochs, int n_mb, int64_t applied_before,
+                              hipStream_t s);
 // recomputes the three maxima of OptGuard from the parameters (after the host wrote them): wr_dev and wr_host both
 hipError_t launch_weight_range(const float* params, const NetLayout& L, uint32_t* wr_dev, uint32_t* wr_host, hipStream_t s);
 // partial-episode bootstrap (ppo_bootstrap_rewards): v = Critic(final_obs[k]), rewards[index[k]] += gamma * v (two roundings), value_out[k] = v (may be

@@ -96,6 +96,7 @@ void PPOAlgorithm::getArgs() {
         F("ppo", "ent_coef", m_ent_coef);
         F("ppo", "vf_coef", m_vf_coef);
         F("ppo", "max_grad_norm", m_max_grad_norm);
+        F("ppo", "target_kl", m_target_kl);   // extension key (every algorithm class); absent in the reference's files: prints nothing then
         m_batch_size = m_num_envs * m_num_steps;                 // :246-247
         m_minibatch_size = m_batch_size / m_num_minibatches;
     } catch (const ppo::FlatToml::ParseError& err) {
@@ -150,6 +151,7 @@ void PPOAlgorithm::construct() {
     m_agent = std::make_shared<Agent>(m_ctx, m_device, std::vector<int64_t>{ m_action_size });
 
     loadPolicyFromCheckpoint();
+    setTargetKL(m_target_kl);   // on the new context, behind whatever a resume loaded
     std::cout << "made envs" << std::endl;
 
     const int64_t T = m_num_steps, N = m_num_envs;
@@ -261,6 +263,11 @@ void PPOAlgorithm::train() {
     auto update_time = start_time;
     const int64_t num_updates = (m_total_timesteps - static_cast<int64_t>(global_step)) / m_batch_size;   // :496
     trainInitEnvs();
+    double target_kl = 0.0;
+    int64_t steps_before = 0;   // the optimizer steps a resume brought along
+    ppo::check(ppo_target_kl_get(m_ctx, &target_kl), m_ctx, "target_kl");
+    ppo::check(ppo_optimizer_get_h(m_ctx, nullptr, nullptr, ppo_param_count(m_ctx), &steps_before), m_ctx, "optimizer step");
+    const bool target_on = target_kl > 0.0;
 
     // One iteration = LR anneal (:514-518), rollout (:524-548), advantages (:554), all epochs x minibatches (:567-644), explained variance (:647-648),
     // and a statistics snapshot behind them.  Everything here is ENQUEUED: nothing waits for the GPU.
@@ -281,6 +288,9 @@ void PPOAlgorithm::train() {
         if (update < num_updates && !checkpoint_due) enqueue(update + 1);
         ppo::check(ppo_stats_snapshot_read(m_ctx, &m_last_stats), m_ctx, "stats");   // waits for iteration `update` only
         const ppo_stats& st = m_last_stats;
+        // with a target KL the table's n_updates row counts the epochs actually run: the snapshot's applied optimizer steps, a whole number of epochs per
+        // update (nothing more is waited for; the context says whether a target is set)
+        m_epochs_total = target_on ? (st.optimizer_steps - steps_before) / m_num_minibatches : -1;
         if (m_on_update) m_on_update(update, st);
         global_step += static_cast<uint64_t>(m_batch_size);
         m_episode_stats->assign(st.ep_len_mean, static_cast<float>(st.ep_rew_mean), static_cast<size_t>(st.ep_count));
@@ -315,6 +325,7 @@ void PPOAlgorithm::train() {
     std::cout << "Saving optimizer " << o << "..." << std::endl;
     saveCheckpoint(a, o);
     m_global_step = global_step;
+    m_epochs_total = -1;
     m_threadPool->stop();
 }
 
@@ -445,6 +456,11 @@ static bool flattenFor(const std::vector<ppo::pt::NamedTensor>& tensors, const s
     return true;
 }
 
+void PPOAlgorithm::setTargetKL(float target_kl) {
+    ppo::check(ppo_target_kl_set(m_ctx, static_cast<double>(target_kl)), m_ctx, "target_kl");
+    m_target_kl = target_kl;
+}
+
 void PPOAlgorithm::loadPolicyFromCheckpoint() {
     const fs::path modelDir = "./ModelCheckpoints/", optimDir = "./OptimizerCheckpoints/";
     if (!fs::exists(modelDir) || !fs::exists(optimDir)) {
@@ -545,7 +561,7 @@ void PPOAlgorithm::printPPOResults(int64_t update, int64_t global_step, std::chr
         row("learning_rate"); printElement(static_cast<float>(st.learning_rate), w);
         std::cout << std::fixed << std::setprecision(9);
         row("loss"); printElement(loss.item<float>(), w);
-        row("n_updates"); printElement(update * m_update_epochs, w);
+        row("n_updates"); printElement(m_epochs_total >= 0 ? m_epochs_total : update * m_update_epochs, w);
         row("policy_gradient_loss"); printElement(pg_loss.item<float>(), w);
         row("value_loss"); printElement(v_loss.item<float>(), w);
     }

@@ -50,6 +50,7 @@ class PPOAlgorithm {
     // Setup
     void getArgs();                       // ./PPOConfig.toml, sections [environment] [general] [ppo] (PPO_Discrete.cpp:107-255)
     void loadPolicyFromCheckpoint();      // newest file of ./ModelCheckpoints + ./OptimizerCheckpoints (:782-835)
+    void setTargetKL(float target_kl);    // m_target_kl and the context's switch (ppo_target_kl_set); 0 = off
 
     // ALGO LOGIC
     std::array<ppo::Tensor, 2> calcAdvantage(const ppo::Tensor& next_obs, const ppo::Tensor& next_done) const;  // {returns, advantages}, :274-331
@@ -104,6 +105,7 @@ class PPOAlgorithm {
     bool m_norm_obs = false;             // extension ([environment] norm_obs): PPO_HostEnv normalises observations with running statistics (ppo_obs_norm_*)
     bool m_norm_reward = false;          // extension ([environment] norm_reward): PPO_HostEnv divides rewards by the running std of the discounted return (ppo_reward_norm_*)
     bool m_bootstrap_truncated = false;  // extension ([environment] bootstrap_truncated): bootstrap the value where a time limit cut an episode off (every algorithm class; set it with setBootstrapTruncated)
+    float m_target_kl = 0.0f;            // extension ([ppo] target_kl): stop an update's optimizer steps once an epoch's last approx_kl exceeds it (ppo_target_kl_set); absent or 0: off
 
     int64_t m_batch_size;
     int64_t m_minibatch_size;
@@ -117,6 +119,7 @@ class PPOAlgorithm {
 
     std::vector<float> m_clipfracs;
     ppo_stats m_last_stats{};             // the statistics snapshot train() is printing (printPPOResults reads its learning rate from here, not from
+    int64_t m_epochs_total = -1;          // train() with a target KL set on the context: the epochs its updates have applied so far, the table's n_updates row; else -1
     bool m_last_stats_valid = false;      // the context, which may already be an iteration ahead); false outside train(): the context is asked
     std::unique_ptr<CircularBuffer> m_episode_stats;
     uint64_t m_global_step;
