@@ -238,7 +238,8 @@ SHAPES = {
     # name: obs, hidden, n_hidden, heads, masked, dtype, lists, clip_vloss / norm_adv, seed
     "f32 obs5 h30x2 (3,)":            dict(obs=5, hidden=30, n_hidden=2, heads=(3,), masked=False, dtype=0, lists=(576, 225, 200, 2), seed=11),
     "f32 obs20 h160x2 (2,3) masked":  dict(obs=20, hidden=160, n_hidden=2, heads=(2, 3), masked=True, dtype=0, lists=(576, 225, 65, 2), seed=13),
-    "f32 obs7 h48x1 (4,)":            dict(obs=7, hidden=48, n_hidden=1, heads=(4,), masked=False, dtype=0, lists=(576, 225, 2), seed=9),
+    "f32 obs7 h48x1 (4,)":            dict(obs=7, hidden=48, n_hidden=1, heads=(4,), masked=False, dtype=0, lists=(576, 225, 2), seed=9,
+                                           max_grad_norm=0.25),   # its eight steps' norms are 0.32 .. 0.49: 0.5 never clips (tests/test_gpu_generic_update.py)
     "f32 obs24 h64x2 six heads masked, plain value loss, raw advantages":
                                       dict(obs=24, hidden=64, n_hidden=2, heads=(5, 3, 4, 2, 3, 3), masked=True, dtype=0, lists=(576, 225, 2), seed=21,
                                            clip_vloss=False, norm_adv=False),
@@ -259,7 +260,38 @@ SHAPES = {
 
 
 def shape_hp(s):
-    return dict(BASE_HP, norm_adv=bool(s.get("norm_adv", True)), clip_vloss=bool(s.get("clip_vloss", True)))
+    return dict(BASE_HP, norm_adv=bool(s.get("norm_adv", True)), clip_vloss=bool(s.get("clip_vloss", True)), max_grad_norm=s.get("max_grad_norm", BASE_HP["max_grad_norm"]))
+
+
+def context(P, s, flags=0, num_minibatches=2, update_epochs=1, **over):
+    """A synthetic-env context of a SHAPES entry (P = the loaded package): 48 envs x 24 steps, the shape's own shape_hp; `over` replaces config fields"""
+    kw = dict(env_kind=P.ENV_SYNTHETIC, dist_kind=P.DIST_MASKED if s["masked"] else P.DIST_CATEGORICAL, obs_size=s["obs"], head_dims=tuple(s["heads"]),
+              hidden=s["hidden"], n_hidden=s["n_hidden"], num_envs=N_ENVS, num_steps=N_STEPS, num_minibatches=num_minibatches, update_epochs=update_epochs,
+              max_episode_steps=30, seed=s["seed"], total_timesteps=8 * N_ENVS * N_STEPS, learning_rate=1e-3, anneal_lr=False,
+              compute_dtype=s["dtype"], kernel_flags=flags, **shape_hp(s))
+    kw.update(over)
+    return P.Context(P.make_config(**kw))
+
+
+def make_params(P, s):
+    """init_orthogonal, 0.02 normal noise on every parameter (biases away from zero), the actor's head x 30 (a policy that is not uniform)"""
+    ctx = context(P, s, 0)
+    ctx.init_orthogonal(s["seed"])
+    params = ctx.get_params()
+    ctx.close()
+    A = sum(s["heads"])
+    params = (params + 0.02 * np.random.default_rng(s["seed"]).standard_normal(params.shape)).astype(np.float32)
+    params[-(A * s["hidden"] + A):] *= 30.0
+    return params
+
+
+def clip_scale(grad, total, max_norm):
+    """clip_grad_norm_'s scaling given the total norm as an f32 number (the device's published one, or the C oracle's): every step in float32, as
+    oracle/ppo_oracle.c:orc_clip_grad_norm and the kernels do it -- c = min(1, max_norm / (total + 1e-6f)), g * c (also when c is 1).
+    Returns (the scaled f32 gradient, c)."""
+    c = np.float32(max_norm) / (np.float32(total) + np.float32(1e-6))
+    c = np.float32(1.0) if c > np.float32(1.0) else np.float32(c)
+    return (np.asarray(grad, np.float32) * c).astype(np.float32), c
 
 
 def index_lists(s, d_logp, d_values):

@@ -66,24 +66,11 @@ def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
-def make_params(P, s):
-    """init_orthogonal, 0.02 normal noise on every parameter (biases away from zero), the actor's head x 30 (a policy that is not uniform)"""
-    ctx = _context(P, s, 0)
-    ctx.init_orthogonal(s["seed"])
-    params = ctx.get_params()
-    ctx.close()
-    A = sum(s["heads"])
-    params = (params + 0.02 * np.random.default_rng(s["seed"]).standard_normal(params.shape)).astype(np.float32)
-    params[-(A * s["hidden"] + A):] *= 30.0
-    return params
+make_params = G.make_params   # (moved to grad_oracle.py: tests/test_gpu_generic_update.py starts from the same parameters)
 
 
 def _context(P, s, flags):
-    hp = G.shape_hp(s)
-    return P.Context(P.make_config(env_kind=P.ENV_SYNTHETIC, dist_kind=P.DIST_MASKED if s["masked"] else P.DIST_CATEGORICAL, obs_size=s["obs"], head_dims=tuple(s["heads"]),
-                                   hidden=s["hidden"], n_hidden=s["n_hidden"], num_envs=G.N_ENVS, num_steps=G.N_STEPS, num_minibatches=2, update_epochs=1,
-                                   max_episode_steps=30, seed=s["seed"], total_timesteps=8 * G.N_ENVS * G.N_STEPS, learning_rate=1e-3, anneal_lr=False,
-                                   compute_dtype=s["dtype"], kernel_flags=flags, **hp))
+    return G.context(P, s, flags)
 
 
 def rolled_out(P, s, params, flags=0, off_policy=None):

@@ -250,3 +250,31 @@ def test_bf16_oracle_stays_within_its_own_bar_on_branch_safe_rows(name):
         worst_noise, worst_ratio, top = max(worst_noise, float(noise.max())), max(worst_ratio, float((noise / bars).max())), max(top, float(d_b16.max()))
         med.append(float(np.median(d_b16)))
     print("BF16_TABLE %-45s %5.1f %%   %.1e   %.2f   %.1e .. %.1e" % (name, 100 * share, worst_noise, worst_ratio, min(med), top))
+
+
+# -------------------------------------------------------------------------------------------------------------------------------------------------------
+# The clip arithmetic of tests/test_gpu_generic_update.py, held on the C oracle alone
+# -------------------------------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("max_grad_norm", [None, 1e30], ids=["the shape's max_grad_norm", "1e30"])
+@pytest.mark.parametrize("name", list(G.SHAPES))
+def test_clip_scale_reproduces_the_c_oracles_clipped_gradient(name, max_grad_norm):
+    """grad_oracle.clip_scale, fed the C oracle's own total norm as an f32 number, gives orc_clip_grad_norm's scaled gradient bit for bit: the GPU test feeds it
+    the device's published norm instead and hands the result to the C oracle's AdamW, so its arithmetic is pinned here before any kernel runs.  Also at a
+    max_grad_norm below the total (0.37 of it), so that every shape walks the c < 1 side whatever its gradient's size."""
+    s = G.SHAPES[name]
+    max_grad_norm = G.shape_hp(s)["max_grad_norm"] if max_grad_norm is None else max_grad_norm
+    b = stand_in_batch(s)
+    idx = G.index_lists(s, b["d_logp"], b["d_values"])[0]
+    g = O.minibatch_grads(*_oracle_args(s, b, idx, s["dtype"]))[0]
+    assert np.isfinite(g).all() and np.abs(g).max() > 0
+    _, total = O.clip_grad_norm(b["net"], g, 1.0)
+    assert float(np.float32(total)) == total           # the oracle returns its f32 total, widened
+    assert abs(total - G.clipped_norm(g, b["shapes"])) <= 2e-6 * total
+    for mgn in (max_grad_norm, float(np.float32(0.37) * np.float32(total))):
+        gc, total_again = O.clip_grad_norm(b["net"], g, mgn)
+        mine, c = G.clip_scale(g, np.float32(total), mgn)
+        print("%-70s max_grad_norm %-12g total %.6f c %.8f" % (name, mgn, total, c))
+        assert total_again == total and mine.dtype == np.float32 and c.dtype == np.float32
+        assert (c == 1.0) == (mgn >= total + 1e-6), (name, mgn, total, c)
+        assert np.array_equal(mine.view(np.uint32), gc.view(np.uint32)), (name, mgn, int((mine.view(np.uint32) != gc.view(np.uint32)).sum()))
+    assert G.clip_scale(g, np.float32(total), 1e30)[1] == 1.0
