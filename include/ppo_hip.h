@@ -47,7 +47,7 @@ enum { PPO_ENV_CARTPOLE = 0, PPO_ENV_MOUNTAINCAR = 1, PPO_ENV_SYNTHETIC = 2, PPO
  * 1 <= D <= 32).  The actor's output layer gives the mean mu[D]; a state-independent parameter log_std[D] -- ONE MORE TENSOR, the last in
  * Agent::parameters() order, behind the actor's layers (ppo_param_count, ppo_param_shapes), initialised to 0 -- gives the scale.  With
  * z = (a - mu) exp(-log_std):  log-prob = sum_d (-z_d^2 / 2 - log_std_d - log(2 pi) / 2),  entropy = sum_d (1 / 2 + log(2 pi) / 2 + log_std_d), no clamp.
- * Serves PPO_ENV_HOST contexts with PPO_DTYPE_F32, always on the generic engine (also for a 2 x 64 network); any other env_kind, PPO_DTYPE_BF16 or
+ * Serves PPO_ENV_HOST contexts with PPO_DTYPE_F32, on the generic engine (also for a 2 x 64 network, unless kernel_flags has PPO_KERNEL_GAUSS_FUSED); any other env_kind, PPO_DTYPE_BF16 or
  * n_heads != 1 make ppo_ctx_create return PPO_ERR_UNSUPPORTED.  Actions are f32: PPO_BUF_ACTIONS is f32 [T,N,D], PPO_BUF_MASKS is not used, and the
  * calls that carry actions have _f32 twins (ppo_host_act_f32, ppo_dev_act_f32, ppo_policy_act_f32); the integer calls return PPO_ERR_UNSUPPORTED on a
  * Gaussian context and name the twin, and the twins do the same on a categorical context.  Env groups (ppo_host_rollout_begin_groups) return
@@ -128,9 +128,21 @@ typedef struct ppo_config {
  *                               (loss_lanes_kernel, bwd_layer_kernel<1, ...>) behind a forward launch that writes logits, values and the top hidden activation
  *                               to memory -- round 5's step -- instead of in the forward launch's epilogue, on the tile still in LDS (ABI 5 default where the
  *                               shape allows: <= 4 heads of <= 4 logits).  Same arithmetic (the same bf16 roundings, f32 sums); partial sums are formed per
- *                               forward workgroup instead of per row range, so the two agree to f32 summation order.  For A/B runs and tests. */
+ *                               forward workgroup instead of per row range, so the two agree to f32 summation order.  For A/B runs and tests.
+ *   PPO_KERNEL_GAUSS_FUSED      dist_kind = PPO_DIST_GAUSSIAN on a 2 x 64 f32 network (hidden = 64, n_hidden = 2, PPO_DTYPE_F32, 1 <= D <= 32, obs_size <= 64):
+ *                               its own kernels (kernels_gauss_fused.hip) in the place of the generic engine's per-layer products -- ONE launch per env step
+ *                               (actor, draw, log-prob, entropy and the step's rollout stores: ppo_host_act_f32, ppo_dev_act_f32, ppo_policy_act_f32), ONE per
+ *                               critic batch (ppo_get_value, ppo_host_rollout_end's two, ppo_bootstrap_rewards and the truncation folds), and a minibatch
+ *                               step of five: forward / loss / backward of both nets, the partial slabs' sum, then the engine's own loss sums, norm and
+ *                               AdamW.  Plain f32 multiply-adds, one forward function for all three kernels (an observation gets the same mean and value from
+ *                               every entry point, bit for bit); the draw, log-prob and entropy are the generic path's own device functions, so a mean gives
+ *                               the same action and log-prob bits as ppo_gaussian.  Parameter layout and order are unchanged (log_std the 13th tensor).
+ *                               Against the same context without the flag: means and values agree to f32 summation order (both within the forward bar of
+ *                               float64), not bit for bit.  Opt-in; any other shape or policy with the flag set is refused by ppo_ctx_create with
+ *                               PPO_ERR_UNSUPPORTED and a message that names the limit -- never served by the generic engine instead.
+ *                               ppo_gauss_fused_launches counts the three kernels' launches. */
 enum { PPO_KERNEL_ROLLOUT_VECTOR = 1, PPO_KERNEL_UPDATE_VECTOR = 2, PPO_KERNEL_UPDATE_ONE_WAVE = 4, PPO_KERNEL_COMM_SELFTEST = 8, PPO_KERNEL_GENERIC_CLASSIC = 16,
-       PPO_KERNEL_GENERIC_SPLIT_HEAD = 32 };
+       PPO_KERNEL_GENERIC_SPLIT_HEAD = 32, PPO_KERNEL_GAUSS_FUSED = 64 };
 
 /* Scalars the reference prints per update (PPO_Discrete.cpp:700-774) plus per-step diagnostics. */
 typedef struct ppo_stats {
@@ -270,6 +282,11 @@ PPO_API ppo_status ppo_categorical(int32_t dist_kind, const float* logits, const
  * Outputs may be NULL.  1 <= D <= 32. */
 PPO_API ppo_status ppo_gaussian(const float* mean, const float* log_std, const float* value, int64_t n, int32_t D, int64_t seed, int64_t row_offset,
                                 int64_t step_index, float* sample, float* log_prob, float* entropy, void* stream);
+
+/* Host-side counts, since the context's creation, of the launches of the three PPO_KERNEL_GAUSS_FUSED kernels: act (one per env step / ppo_policy_act_f32),
+ * value (one per critic batch) and update (one per minibatch step).  All three are 0 on a context without the flag: proof of which path ran, like
+ * ppo_profile.vector_fallback_launches.  Outputs may be NULL. */
+PPO_API ppo_status ppo_gauss_fused_launches(ppo_ctx* ctx, int64_t* act, int64_t* value, int64_t* update);
 
 /* Categorical::sample / CategoricalMasked::sample (Categorical.cpp:73-79: multinomial(probs, 1, replacement = true)) on given
  * m_probs [n,A]: inverse-CDF draw with the counter-based generator keyed by (seed; row_offset + row, step_index, head). */

@@ -20,7 +20,7 @@ MM_EPI_NONE, MM_EPI_BIAS, MM_EPI_BIAS_TANH, MM_EPI_DTANH = 0, 1, 2, 3
 MM_F32X3, MM_BF16 = 0, 1
 DIST_CATEGORICAL, DIST_MASKED, DIST_GAUSSIAN = 0, 1, 2   # DIST_GAUSSIAN: f32 actions [.., D], the *_f32 calls (include/ppo_hip.h PPO_DIST_GAUSSIAN)
 DTYPE_F32, DTYPE_BF16 = 0, 1
-KERNEL_ROLLOUT_VECTOR, KERNEL_UPDATE_VECTOR, KERNEL_UPDATE_ONE_WAVE, KERNEL_COMM_SELFTEST, KERNEL_GENERIC_CLASSIC, KERNEL_GENERIC_SPLIT_HEAD = 1, 2, 4, 8, 16, 32   # ppo_config.kernel_flags (include/ppo_hip.h PPO_KERNEL_*)
+KERNEL_ROLLOUT_VECTOR, KERNEL_UPDATE_VECTOR, KERNEL_UPDATE_ONE_WAVE, KERNEL_COMM_SELFTEST, KERNEL_GENERIC_CLASSIC, KERNEL_GENERIC_SPLIT_HEAD, KERNEL_GAUSS_FUSED = 1, 2, 4, 8, 16, 32, 64   # ppo_config.kernel_flags (include/ppo_hip.h PPO_KERNEL_*)
 ABI_VERSION = 5
 COMM_ID_BYTES = 128
 COMM_HANDLE_BYTES = 64
@@ -58,6 +58,7 @@ ABI_SYMBOLS = [
     "ppo_env_truncation_bootstrap", "ppo_env_truncations",
     "ppo_host_act_f32", "ppo_dev_act_f32", "ppo_policy_act_f32", "ppo_gaussian",
     "ppo_target_kl_set", "ppo_target_kl_get", "ppo_early_stop_read",
+    "ppo_gauss_fused_launches",
 ]
 
 
@@ -169,6 +170,7 @@ def lib():
         L.ppo_target_kl_set.argtypes = [C.c_void_p, C.c_double]
         L.ppo_target_kl_get.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         L.ppo_early_stop_read.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+        L.ppo_gauss_fused_launches.argtypes = [C.c_void_p] + [C.POINTER(C.c_int64)] * 3
         for name in ABI_SYMBOLS:
             getattr(L, name)  # AttributeError if the build lacks a declared symbol
         if L.ppo_abi_version() != ABI_VERSION:
@@ -690,6 +692,12 @@ class Context:
     def profile_enable(self, on=1):
         """0 = off, 1 = every instrumented launch, 2 = only the dominant kernel (1 launch in 8) and the GAE scan, 4 = the same with 1 launch in 41."""
         _check(lib().ppo_profile_enable(self.h, C.c_int32(int(on))), self.h)
+
+    def gauss_fused_launches(self):
+        """ppo_gauss_fused_launches: (act, value, update) launches of the KERNEL_GAUSS_FUSED kernels since creation; (0, 0, 0) without the flag."""
+        a, v, u = C.c_int64(), C.c_int64(), C.c_int64()
+        _check(lib().ppo_gauss_fused_launches(self.h, C.byref(a), C.byref(v), C.byref(u)), self.h)
+        return a.value, v.value, u.value
 
     def profile_read(self):
         p = Profile()

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "generic.hpp"
+#include "gauss_fused.hpp"
 #include "ppo_internal.hpp"
 #include "trunc_events.hpp"
 
@@ -192,6 +193,11 @@ struct ppo_ctx {
     bool gen_obs_bf_valid = false;             // generic bf16 path: GenericCtx::obs_bf holds THIS update's observations (set by the update's first step)
     bool wr_in_update = false;                 // rollout / update / stand-alone step, not per launch (an update moves a weight by less than 40 lr: the thresholds' margin)
     int64_t vector_fallback_launches = 0;   // launches that took a vector kernel because a weight did not fit fp16 (ppo_profile.vector_fallback_launches)
+    // PPO_KERNEL_GAUSS_FUSED (kernels_gauss_fused.hip): the Gaussian 2 x 64 context's act / critic / minibatch kernels, their launch counts since creation
+    // (ppo_gauss_fused_launches) and the update kernel's partial slabs [2][GAUSS_FUSED_MAX_BLOCKS][gauss_fused_slab_stride]
+    bool gauss_fused = false;
+    int64_t gf_launches[3] = { 0, 0, 0 };
+    float* gf_slab = nullptr;
     unsigned long long* stamps = nullptr;  // [2][12] phase cycles of the diagnostic kernel variant
     // caller-stepped envs (PPO_ENV_HOST: ppo_host_*).  The staging block is pinned host memory the GPU can read: ppo_host_observe copies the caller's step
     // outputs into it (no launch), the next launch commits them reading the block in place (measured faster than one async copy of it ahead of every
@@ -564,7 +570,7 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
         return fail(nullptr, PPO_ERR_UNSUPPORTED, "dist_kind = PPO_DIST_GAUSSIAN is built for compute_dtype = PPO_DTYPE_F32; bf16 storage is not");
     if (gauss && cfg->n_heads != 1)
         return fail(nullptr, PPO_ERR_UNSUPPORTED, "dist_kind = PPO_DIST_GAUSSIAN takes n_heads = 1 with head_dims[0] = the action dimension D; got n_heads = %d", cfg->n_heads);
-    if (cfg->kernel_flags & ~(PPO_KERNEL_ROLLOUT_VECTOR | PPO_KERNEL_UPDATE_VECTOR | PPO_KERNEL_UPDATE_ONE_WAVE | PPO_KERNEL_COMM_SELFTEST | PPO_KERNEL_GENERIC_CLASSIC | PPO_KERNEL_GENERIC_SPLIT_HEAD)) return fail(nullptr, PPO_ERR_INVALID, "unknown bits in kernel_flags 0x%x", cfg->kernel_flags);
+    if (cfg->kernel_flags & ~(PPO_KERNEL_ROLLOUT_VECTOR | PPO_KERNEL_UPDATE_VECTOR | PPO_KERNEL_UPDATE_ONE_WAVE | PPO_KERNEL_COMM_SELFTEST | PPO_KERNEL_GENERIC_CLASSIC | PPO_KERNEL_GENERIC_SPLIT_HEAD | PPO_KERNEL_GAUSS_FUSED)) return fail(nullptr, PPO_ERR_INVALID, "unknown bits in kernel_flags 0x%x", cfg->kernel_flags);
     if (cfg->compute_dtype == PPO_DTYPE_BF16 && !generic)
         return fail(nullptr, PPO_ERR_UNSUPPORTED, "compute_dtype = PPO_DTYPE_BF16 applies to networks whose layers are GEMMs (env_kind = PPO_ENV_SYNTHETIC); the reference's "
                     "2 x 64 networks always compute in f32");
@@ -582,6 +588,20 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
         A += cfg->head_dims[h];
     }
     if (A > PPO_MAX_ACT) return fail(nullptr, PPO_ERR_UNSUPPORTED, "sum(head_dims) = %d exceeds %d", A, PPO_MAX_ACT);
+    // PPO_KERNEL_GAUSS_FUSED: the one shape kernels_gauss_fused.hip is built for, or a refusal -- never the generic engine in its place
+    const bool gauss_fused = (cfg->kernel_flags & PPO_KERNEL_GAUSS_FUSED) != 0;
+    if (gauss_fused) {
+        if (!gauss)
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_GAUSS_FUSED serves dist_kind = PPO_DIST_GAUSSIAN only; this context's policy is categorical (dist_kind %d)",
+                        cfg->dist_kind);
+        if (cfg->hidden != 64) return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_GAUSS_FUSED is built for hidden = 64; got hidden = %d", cfg->hidden);
+        if (cfg->n_hidden != 2) return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_GAUSS_FUSED is built for n_hidden = 2; got n_hidden = %d", cfg->n_hidden);
+        if (cfg->obs_size > GAUSS_FUSED_MAX_OBS)
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_GAUSS_FUSED is built for obs_size <= %d; got obs_size = %d", GAUSS_FUSED_MAX_OBS, cfg->obs_size);
+        if (!gauss_fused_serves_shape(cfg->obs_size, cfg->hidden, cfg->n_hidden, A))
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_GAUSS_FUSED is built for 1 <= D <= %d and 1 <= obs_size <= %d; got D = %d, obs_size = %d", PPO_MAX_ACT,
+                        GAUSS_FUSED_MAX_OBS, A, cfg->obs_size);
+    }
     if (cfg->num_envs < 1 || cfg->num_steps < 1 || cfg->num_minibatches < 1 || cfg->update_epochs < 1)
         return fail(nullptr, PPO_ERR_INVALID, "num_envs, num_steps, num_minibatches, update_epochs must be >= 1");
     const int64_t B = (int64_t)cfg->num_envs * cfg->num_steps;
@@ -793,6 +813,10 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
         if (GL.gauss) {
             CK(dalloc(c, &g.actf, N * GL.gauss));
             CK(dalloc(c, &g.ls_part, (size_t)GEN_LOSS_BLOCKS * GL.gauss));
+        }
+        if (gauss_fused) {
+            c->gauss_fused = true;
+            CK(dalloc(c, &c->gf_slab, (size_t)2 * GAUSS_FUSED_MAX_BLOCKS * gauss_fused_slab_stride(GL)));
         }
         CK(dalloc(c, &c->cur_mask, N * GL.act));
         // the zero-fills above ran on the null stream, which a non-blocking stream does not wait for: drain them before the first write
@@ -1023,6 +1047,12 @@ extern "C" ppo_status ppo_params_init_orthogonal(ppo_ctx* c, int64_t seed) {
 // ---- generic networks (generic.hpp): critic / actor over n rows, chunked to the workspace size ----
 static ppo_status gen_values(ppo_ctx* c, const float* obs, int64_t n, float* value) {
     GenericCtx& g = *c->gen;
+    if (c->gauss_fused) {   // PPO_KERNEL_GAUSS_FUSED: the critic over all n rows in one launch
+        NEED(c, n < (1ll << 31), "more than 2^31 rows");
+        if (n > 0) c->gf_launches[1] += 1;
+        HIPCHK(c, gauss_fused_values(g.L, B_<float>(c, PPO_BUF_PARAMS), obs, n, value, c->stream));
+        return PPO_OK;
+    }
     if (gen_fused_forward_ok(g) && n <= GEN_FUSED_MAX_ROWS) {   // bf16 storage, small batch: the whole critic in one launch
         HIPCHK(c, gen_fused_forward(g, B_<float>(c, PPO_BUF_PARAMS), 0, obs, nullptr, 0, n, false, value, c->stream));
         return PPO_OK;
@@ -1054,12 +1084,22 @@ static ppo_status gen_policy(ppo_ctx* c, const float* obs, const uint8_t* mask, 
     return PPO_OK;
 }
 
-// gen_policy for a Gaussian context: the actor's forward gives the mean, gauss_heads_kernel the action (f32 [n, D]), its log-prob and the entropy
+// gen_policy for a Gaussian context: the actor's forward gives the mean, gauss_heads_kernel the action (f32 [n, D]), its log-prob and the entropy.
+// PPO_KERNEL_GAUSS_FUSED: all of it, and the step's rollout stores when `stores` is given, in ONE launch; returns true in *stored then (the caller skips
+// gen_gauss_store_step)
 static ppo_status gen_policy_gauss(ppo_ctx* c, const float* obs, const float* forced, int64_t n, int64_t step_index, float* action, float* logprob, float* entropy,
-                                   bool greedy = false) {
+                                   bool greedy = false, const GaussStepStores* stores = nullptr, bool* stored = nullptr) {
     GenericCtx& g = *c->gen;
     const int D = g.L.gauss;
     const float* params = B_<float>(c, PPO_BUF_PARAMS);
+    if (stored) *stored = false;
+    if (c->gauss_fused) {
+        NEED(c, n < (1ll << 31), "more than 2^31 rows");
+        if (n > 0) c->gf_launches[0] += 1;
+        HIPCHK(c, gauss_fused_act(g.L, params, obs, forced, n, c->cfg.seed, c->cfg.env_offset, step_index, greedy, action, logprob, entropy, stores, c->stream));
+        if (stored) *stored = stores != nullptr;
+        return PPO_OK;
+    }
     for (int64_t off = 0; off < n; off += g.rows_max) {
         const int64_t rows = std::min<int64_t>(g.rows_max, n - off);
         HIPCHK(c, gen_forward(g, params, 1, obs + off * g.L.obs, rows, nullptr, g.dz[0], g.dz[1], g.logits, c->stream));
@@ -1140,6 +1180,14 @@ extern "C" ppo_status ppo_policy_act_greedy(ppo_ctx* c, const float* obs, const 
     NEED(c, action != nullptr, "ppo_policy_act_greedy needs an action output");
     NEED(c, n >= 0, "n < 0");
     return policy_act_common(c, obs, mask, nullptr, n, 0, action, logprob, entropy, value, true);
+}
+
+extern "C" ppo_status ppo_gauss_fused_launches(ppo_ctx* c, int64_t* act, int64_t* value, int64_t* update) {
+    NEED(c, c != nullptr, "null ctx");
+    if (act) *act = c->gf_launches[0];
+    if (value) *value = c->gf_launches[1];
+    if (update) *update = c->gf_launches[2];
+    return PPO_OK;
 }
 
 extern "C" ppo_status ppo_categorical(int32_t dist_kind, const float* logits, const uint8_t* mask, const int64_t* value, int64_t n, int32_t A,
@@ -1621,6 +1669,22 @@ static ppo_status gen_fwd_bwd(ppo_ctx* c, const int32_t* idx, int64_t M, int slo
     c->last_global_M = global_M;
     float* params = B_<float>(c, PPO_BUF_PARAMS);
     float* grads = B_<float>(c, PPO_BUF_GRADS);
+    if (c->gauss_fused) {
+        // PPO_KERNEL_GAUSS_FUSED: gather, both nets' forward, loss and backward in one launch, the slab sums in a second; behind them the engine's own
+        // loss sums, all-reduce, norm and AdamW
+        {
+            ProfScope ps(c, PROF_FWD_BWD);
+            c->gen_opt_fused_ok = false;
+            c->gen_pre_idx = nullptr;
+            c->gf_launches[2] += 1;
+            HIPCHK(c, gauss_fused_fwd_bwd(GL, c->hp, params, B_<float>(c, PPO_BUF_OBS), B_<float>(c, PPO_BUF_ACTIONS), B_<float>(c, PPO_BUF_LOGPROBS),
+                                          B_<float>(c, PPO_BUF_ADVANTAGES), B_<float>(c, PPO_BUF_RETURNS), B_<float>(c, PPO_BUF_VALUES), idx, M, 1.0 / global_M, global_M,
+                                          c->cfg.norm_adv ? c->adv_stats + (size_t)slot * PPO_ADV_PARTS : nullptr, c->gf_slab, g.loss_part, grads, c->stream));
+        }
+        ProfScope ps(c, PROF_REDUCE);
+        HIPCHK(c, gen_loss_sums(g, c->loss_sums, grads + GL.P, c->stream));
+        return PPO_OK;
+    }
     {
         ProfScope ps(c, PROF_FWD_BWD);
         // Both fused passes available (bf16 storage, widths the kernels are built for): the two nets share every launch -- forward, each layer's backward, the
@@ -2381,10 +2445,13 @@ extern "C" ppo_status ppo_host_act_f32(ppo_ctx* c, float* action_h) {
     s = rn_batch(c, h);    // reward normalisation: likewise
     if (s != PPO_OK) return s;
     if (h.commit) HIPCHK(c, launch_host_commit(h, N, c->O, c->stream));
-    s = gen_policy_gauss(c, B_<float>(c, PPO_BUF_NEXT_OBS), nullptr, N, c->rollout_steps + t, g.actf, g.step_lp, g.step_en);
+    const GaussStepStores stores{ B_<int32_t>(c, PPO_BUF_NEXT_DONE), h.obs_t, B_<float>(c, PPO_BUF_ACTIONS) + (size_t)t * N * D, B_<float>(c, PPO_BUF_LOGPROBS) + (size_t)t * N, h.dones_t };
+    bool stored = false;
+    s = gen_policy_gauss(c, B_<float>(c, PPO_BUF_NEXT_OBS), nullptr, N, c->rollout_steps + t, g.actf, g.step_lp, g.step_en, false, &stores, &stored);
     if (s != PPO_OK) return s;
-    HIPCHK(c, gen_gauss_store_step(g.L, N, B_<float>(c, PPO_BUF_NEXT_OBS), g.actf, g.step_lp, B_<int32_t>(c, PPO_BUF_NEXT_DONE), h.obs_t,
-                                   B_<float>(c, PPO_BUF_ACTIONS) + (size_t)t * N * D, B_<float>(c, PPO_BUF_LOGPROBS) + (size_t)t * N, h.dones_t, c->stream));
+    if (!stored)
+        HIPCHK(c, gen_gauss_store_step(g.L, N, B_<float>(c, PPO_BUF_NEXT_OBS), g.actf, g.step_lp, stores.done_prev, stores.obs_t, stores.act_t, stores.lp_t, stores.dones_t,
+                                       c->stream));
     HIPCHK(c, hipMemcpyAsync(c->host_act, g.actf, action_bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));   // the one wait of a step: the actions
     std::memcpy(action_h, c->host_act, action_bytes);
@@ -2924,10 +2991,14 @@ extern "C" ppo_status ppo_dev_act_f32(ppo_ctx* c, float* action, void* caller_st
     GenericCtx& g = *c->gen;
     s = dev_handover_in(c, caller);
     if (s != PPO_OK) return s;
-    s = gen_policy_gauss(c, B_<float>(c, PPO_BUF_NEXT_OBS), nullptr, N, c->rollout_steps + t, action, g.step_lp, g.step_en);
+    const GaussStepStores stores{ B_<int32_t>(c, PPO_BUF_NEXT_DONE), h.obs_t, B_<float>(c, PPO_BUF_ACTIONS) + (size_t)t * N * g.L.gauss, B_<float>(c, PPO_BUF_LOGPROBS) + (size_t)t * N,
+                                  h.dones_t };
+    bool stored = false;
+    s = gen_policy_gauss(c, B_<float>(c, PPO_BUF_NEXT_OBS), nullptr, N, c->rollout_steps + t, action, g.step_lp, g.step_en, false, &stores, &stored);
     if (s != PPO_OK) return s;
-    HIPCHK(c, gen_gauss_store_step(g.L, N, B_<float>(c, PPO_BUF_NEXT_OBS), action, g.step_lp, B_<int32_t>(c, PPO_BUF_NEXT_DONE), h.obs_t,
-                                   B_<float>(c, PPO_BUF_ACTIONS) + (size_t)t * N * g.L.gauss, B_<float>(c, PPO_BUF_LOGPROBS) + (size_t)t * N, h.dones_t, c->stream));
+    if (!stored)
+        HIPCHK(c, gen_gauss_store_step(g.L, N, B_<float>(c, PPO_BUF_NEXT_OBS), action, g.step_lp, stores.done_prev, stores.obs_t, stores.act_t, stores.lp_t, stores.dones_t,
+                                       c->stream));
     s = dev_handover_out(c, caller);
     if (s != PPO_OK) return s;
     if (c->host_feed == 0) {   // the first act: this rollout is device-fed, and its events go to the other list

@@ -8,15 +8,9 @@
 // Everything else of a Gaussian context -- layer products, the backward pass with d(loss)/d(mu) in the place of d(loss)/d(logits), slab sums, gradient
 // norm, clip, AdamW -- is the generic engine's own (kernels_generic.hip, kernels_gemm.hip).
 #include "generic.hpp"
+#include "gauss_dist.hpp"   // gauss_z / gauss_logp / gauss_entropy, the draw (gauss_eps4, gauss_sample): shared with kernels_gauss_fused.hip
 
 namespace {
-
-constexpr double HALF_LOG_2PI = 0.91893853320467274178;
-
-// the standardised action and its log-density; inv_sigma = expf(-log_std)
-__device__ __forceinline__ float gauss_z(float a, float mu, float inv_sigma) { return (a - mu) * inv_sigma; }
-__device__ __forceinline__ double gauss_logp(float z, float log_std) { return (-0.5 * (double)z * (double)z - (double)log_std) - HALF_LOG_2PI; }
-__device__ __forceinline__ double gauss_entropy(float log_std) { return (0.5 + HALF_LOG_2PI) + (double)log_std; }
 
 // One thread per row, D a run-time bound <= PPO_MAX_ACT, no per-row array: dimensions are walked four at a time (one Philox block gives two Box-Muller
 // pairs).  The draw of dimension d of row r at step s is a function of (seed, row_offset + r, s, d) alone: counter (row, s mod 2^32, d / 4 | (s >> 32) << 8,
@@ -33,15 +27,7 @@ __global__ __launch_bounds__(128) void gauss_heads_kernel(int D, const float* __
     double lp = 0.0, en = 0.0;
     for (int k4 = 0; k4 < D; k4 += 4) {
         float eps[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
-        if (!GREEDY && !forced) {
-            const uint4 w = philox4x32_10((uint32_t)seed, (uint32_t)((uint64_t)seed >> 32), (uint32_t)(row_offset + r), (uint32_t)step_index,
-                                          (uint32_t)(k4 >> 2) | ((uint32_t)((uint64_t)step_index >> 32) << 8), 0x20u);
-            const float ra = sqrtf(-2.0f * logf((float)((w.x >> 8) + 1u) * 0x1p-24f)), rb = sqrtf(-2.0f * logf((float)((w.z >> 8) + 1u) * 0x1p-24f));
-            float sa, ca, sb, cb;
-            sincospif((float)(w.y >> 8) * 0x1p-23f, &sa, &ca);
-            sincospif((float)(w.w >> 8) * 0x1p-23f, &sb, &cb);
-            eps[0] = ra * ca; eps[1] = ra * sa; eps[2] = rb * cb; eps[3] = rb * sb;
-        }
+        if (!GREEDY && !forced) gauss_eps4(seed, row_offset + r, step_index, k4, eps);
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const int k = k4 + j;
@@ -50,7 +36,7 @@ __global__ __launch_bounds__(128) void gauss_heads_kernel(int D, const float* __
                 float a;
                 if (GREEDY) a = mu;
                 else if (forced) a = forced[r * D + k];
-                else a = mu + expf(ls) * eps[j];
+                else a = gauss_sample(mu, ls, eps[j]);
                 if (action) action[r * D + k] = a;
                 lp += gauss_logp(gauss_z(a, mu, expf(-ls)), ls);
                 en += gauss_entropy(ls);

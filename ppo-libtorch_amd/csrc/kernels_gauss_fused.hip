@@ -1,0 +1,581 @@
+// ppo-libtorch_amd/csrc/kernels_gauss_fused.hip -- diagonal-Gaussian policies on a 2 x 64 f32 network (PPO_KERNEL_GAUSS_FUSED): the env step, the critic
+// batch and the minibatch step as ONE launch each, in the place of the generic engine's per-layer products (kernels_gemm.hip pads every 64-wide product to
+// 128-wide tiles and takes a launch per layer and direction).
+//
+// One workgroup = 4 waves = one 64-sample tile at a time.  The net's weights are resident in LDS for the whole launch, activations are [unit][sample] images of
+// stride PPO_LDS_STRIDE (the model is fwd_bwd_body, kernels_update.hip); obs_size is a run-time value, padded with zeros to a multiple of 4 in LDS.  All three
+// kernels go through gf_forward_tile, so an observation gets the same mean and the same value from every entry point, bit for bit: plain f32, every product an
+// explicit fmaf in ascending k, bias first.  No reduced-precision operand anywhere.
+//
+// LDS (floats; obsP = obs rounded up to 4, outP = the output width rounded up to 4; the update kernel carves for the wider net, the actor):
+//   W1 64 obsP | W2 4096 | W3 64 outP | b1 64 | b2 64 | b3 32 | log_std 32 | exp(-log_std) 32 | row index 64 | X obsP 68 | H1 64 68 | H2 64 68 | OUT outP 68
+//   obs 64, D 32 (the largest shape served): 4096 + 4096 + 2048 + 288 + 4352 + 4352 + 4352 + 2176 = 25 760 floats = 103 040 bytes of 163 840.
+//   obs 17, D 6: 1280 + 4096 + 512 + 288 + 1360 + 4352 + 4352 + 544 = 16 784 floats = 67 136 bytes: two workgroups per CU.
+#include <algorithm>
+
+#include "generic.hpp"
+#include "gauss_dist.hpp"
+#include "gauss_fused.hpp"
+
+namespace {
+
+constexpr int GF_THREADS = 256;
+constexpr int GF_S = PPO_LDS_STRIDE;
+
+// what the kernels need of GenLayout: offsets (floats, into the flat parameter vector) of {W1, b1, W2, b2, W3, b3} per net, log_std behind the actor
+struct GfShape {
+    int obs, D;
+    int off[2][6];
+    int logstd_off;
+};
+
+GfShape gf_shape(const GenLayout& L) {
+    GfShape sh{};
+    sh.obs = L.obs; sh.D = L.gauss;
+    for (int net = 0; net < 2; net++)
+        for (int l = 0; l < 3; l++) { sh.off[net][2 * l] = L.w_off[net][l]; sh.off[net][2 * l + 1] = L.b_off[net][l]; }
+    sh.logstd_off = L.logstd_off;
+    return sh;
+}
+
+struct GfLds {
+    float *w1, *w2, *w3, *b1, *b2, *b3, *ls, *inv;
+    int* ridx;
+    float *x, *h1, *h2, *o;
+    int obsP, outP;
+};
+
+__host__ __device__ inline int gf_pad4(int v) { return (v + 3) & ~3; }
+__host__ __device__ inline int gf_lds_floats(int obsP, int outP) { return 64 * obsP + 4096 + 64 * outP + 64 + 64 + 32 + 32 + 32 + 64 + obsP * GF_S + 64 * GF_S + 64 * GF_S + outP * GF_S; }
+
+__device__ __forceinline__ GfLds gf_carve(float* base, int obsP, int outP) {
+    GfLds m;
+    m.obsP = obsP; m.outP = outP;
+    float* p = base;
+    m.w1 = p; p += 64 * obsP;
+    m.w2 = p; p += 4096;
+    m.w3 = p; p += 64 * outP;
+    m.b1 = p; p += 64;
+    m.b2 = p; p += 64;
+    m.b3 = p; p += 32;
+    m.ls = p; p += 32;
+    m.inv = p; p += 32;
+    m.ridx = reinterpret_cast<int*>(p); p += 64;
+    m.x = p; p += obsP * GF_S;
+    m.h1 = p; p += 64 * GF_S;
+    m.h2 = p; p += 64 * GF_S;
+    m.o = p;
+    return m;
+}
+
+// one net's weights into LDS (zero padded), log_std and exp(-log_std); every thread of the workgroup calls it; the caller's next barrier publishes it
+__device__ __forceinline__ void gf_stage_weights(const GfLds& m, const GfShape& sh, const float* __restrict__ params, int net, int tid) {
+    const int obs = sh.obs, obsP = m.obsP, out = net == 0 ? 1 : sh.D;
+    const float* W1 = params + sh.off[net][0];
+    const float* W2 = params + sh.off[net][2];
+    const float* W3 = params + sh.off[net][4];
+    for (int i = tid; i < 64 * obsP; i += GF_THREADS) {
+        const int u = i / obsP, k = i - u * obsP;
+        m.w1[i] = k < obs ? W1[u * obs + k] : 0.0f;
+    }
+    for (int i = tid; i < 4096; i += GF_THREADS) m.w2[i] = W2[i];
+    for (int i = tid; i < 64 * m.outP; i += GF_THREADS) m.w3[i] = (i >> 6) < out ? W3[i] : 0.0f;
+    if (tid < 64) { m.b1[tid] = params[sh.off[net][1] + tid]; m.b2[tid] = params[sh.off[net][3] + tid]; }
+    if (tid < 32) {
+        m.b3[tid] = tid < out ? params[sh.off[net][5] + tid] : 0.0f;
+        const float ls = tid < sh.D ? params[sh.logstd_off + tid] : 0.0f;
+        m.ls[tid] = ls;
+        m.inv[tid] = expf(-ls);
+    }
+}
+
+// the tile's observations as the [k][sample] image: row m.ridx[s] of obs [., O], zeros for a sample without a row (ridx < 0) and for k >= O
+__device__ __forceinline__ void gf_load_x(const GfLds& m, const float* __restrict__ obs, int O, int tid) {
+    const int obsP = m.obsP;
+    for (int i = tid; i < 64 * obsP; i += GF_THREADS) {
+        const int s = i / obsP, k = i - s * obsP;
+        const int r = m.ridx[s];
+        m.x[k * GF_S + s] = (k < O && r >= 0) ? obs[(int64_t)r * O + k] : 0.0f;
+    }
+}
+
+// a hidden layer: out[u][s] = tanh(b[u] + sum_k W[u][k] in[k][s]), k ascending; lane = sample, wave w owns units 16 w .. 16 w + 15; K a multiple of 4
+__device__ __forceinline__ void gf_hidden_layer(const float* __restrict__ W, const float* __restrict__ b, const float* __restrict__ in, float* __restrict__ out, int K,
+                                                int s, int w) {
+    float acc[16];
+#pragma unroll
+    for (int i = 0; i < 16; i++) acc[i] = b[16 * w + i];
+    for (int k = 0; k < K; k += 4) {
+        const float x0 = in[(k + 0) * GF_S + s], x1 = in[(k + 1) * GF_S + s], x2 = in[(k + 2) * GF_S + s], x3 = in[(k + 3) * GF_S + s];
+#pragma unroll
+        for (int i = 0; i < 16; i++) {
+            const float4 wv = *reinterpret_cast<const float4*>(&W[(16 * w + i) * K + k]);
+            acc[i] = __builtin_fmaf(wv.x, x0, acc[i]);
+            acc[i] = __builtin_fmaf(wv.y, x1, acc[i]);
+            acc[i] = __builtin_fmaf(wv.z, x2, acc[i]);
+            acc[i] = __builtin_fmaf(wv.w, x3, acc[i]);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 16; i++) out[(16 * w + i) * GF_S + s] = tanh_fast(acc[i]);
+}
+
+// THE forward pass of all three kernels: the tile in m.x through obs -> 64 -> 64 -> out; leaves H1, H2 (post-tanh) and OUT rows 0 .. out - 1.
+// Every thread of the workgroup calls it; barriers: one at entry (m.x and the weights are complete), one behind every layer.
+__device__ __forceinline__ void gf_forward_tile(const GfLds& m, int out, int tid) {
+    const int s = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    __syncthreads();
+    gf_hidden_layer(m.w1, m.b1, m.x, m.h1, m.obsP, s, w);
+    __syncthreads();
+    gf_hidden_layer(m.w2, m.b2, m.h1, m.h2, 64, s, w);
+    __syncthreads();
+    {   // output layer: wave w owns units w, w + 4, ... (< out <= 32)
+        const int nu = (out - w + 3) >> 2;
+        float acc[8];
+#pragma unroll
+        for (int i = 0; i < 8; i++) acc[i] = m.b3[(4 * i + w) & 31];
+        for (int k = 0; k < 64; k += 4) {
+            const float x0 = m.h2[(k + 0) * GF_S + s], x1 = m.h2[(k + 1) * GF_S + s], x2 = m.h2[(k + 2) * GF_S + s], x3 = m.h2[(k + 3) * GF_S + s];
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                if (i < nu) {
+                    const float4 wv = *reinterpret_cast<const float4*>(&m.w3[(4 * i + w) * 64 + k]);
+                    acc[i] = __builtin_fmaf(wv.x, x0, acc[i]);
+                    acc[i] = __builtin_fmaf(wv.y, x1, acc[i]);
+                    acc[i] = __builtin_fmaf(wv.z, x2, acc[i]);
+                    acc[i] = __builtin_fmaf(wv.w, x3, acc[i]);
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 8; i++) if (i < nu) m.o[(4 * i + w) * GF_S + s] = acc[i];
+    }
+    __syncthreads();
+}
+
+// rows row0 .. row0 + 63 of a dense batch of n
+__device__ __forceinline__ void gf_dense_rows(const GfLds& m, int64_t row0, int64_t n, int tid) {
+    if (tid < 64) m.ridx[tid] = row0 + tid < n ? (int)(row0 + tid) : -1;
+    __syncthreads();
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// gauss_act_kernel: actor forward + gauss_heads_kernel's sample / log-prob / entropy (the same device functions, gauss_dist.hpp) + the rollout stores of
+// the step (gauss_store_step_kernel's; st.obs_t == nullptr: the stand-alone policy, none)
+// ---------------------------------------------------------------------------------------------------------
+struct GfStepStores { const int32_t* done_prev; float* obs_t; float* act_t; float* lp_t; float* dones_t; };
+
+template <bool GREEDY>
+__global__ __launch_bounds__(GF_THREADS) void gauss_act_kernel(GfShape sh, const float* __restrict__ params, const float* __restrict__ obs,
+                                                               const float* __restrict__ forced, int64_t n, int64_t seed, int64_t row_offset, int64_t step_index,
+                                                               float* action, float* logprob, float* entropy, GfStepStores st) {
+    extern __shared__ __attribute__((aligned(16))) float gf_lds[];
+    const int tid = threadIdx.x, D = sh.D, O = sh.obs;
+    const GfLds m = gf_carve(gf_lds, gf_pad4(O), gf_pad4(D));
+    gf_stage_weights(m, sh, params, 1, tid);
+    const int64_t tiles = (n + 63) / 64;
+    for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const int64_t row0 = tile * 64;
+        gf_dense_rows(m, row0, n, tid);
+        gf_load_x(m, obs, O, tid);
+        gf_forward_tile(m, D, tid);
+        const int64_t r = row0 + (tid & 63);
+        if (tid < 64) {
+            if (r < n) {
+                double lp = 0.0, en = 0.0;
+                for (int k4 = 0; k4 < D; k4 += 4) {
+                    float eps[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
+                    if (!GREEDY && !forced) gauss_eps4(seed, row_offset + r, step_index, k4, eps);
+#pragma unroll
+                    for (int j = 0; j < 4; j++) {
+                        const int k = k4 + j;
+                        if (k < D) {
+                            const float mu = m.o[k * GF_S + tid], ls = m.ls[k];
+                            float a;
+                            if (GREEDY) a = mu;
+                            else if (forced) a = forced[r * D + k];
+                            else a = gauss_sample(mu, ls, eps[j]);
+                            if (action) action[r * D + k] = a;
+                            if (st.act_t) st.act_t[r * D + k] = a;
+                            lp += gauss_logp(gauss_z(a, mu, expf(-ls)), ls);
+                            en += gauss_entropy(ls);
+                        }
+                    }
+                }
+                if (logprob) logprob[r] = (float)lp;
+                if (st.lp_t) st.lp_t[r] = (float)lp;
+                if (entropy) entropy[r] = (float)en;
+            }
+        } else if (st.obs_t) {   // waves 1 .. 3: the step's other stores
+            const int64_t rows = n - row0 < 64 ? n - row0 : 64;
+            for (int64_t i = tid - 64; i < rows * O; i += GF_THREADS - 64) st.obs_t[row0 * O + i] = obs[row0 * O + i];
+            if (tid < 128 && r < n) st.dones_t[r] = (float)st.done_prev[r];
+        }
+        __syncthreads();   // OUT and the row list are read: the next tile may overwrite them
+    }
+}
+
+// gauss_values_kernel: the critic over n rows
+__global__ __launch_bounds__(GF_THREADS) void gauss_values_kernel(GfShape sh, const float* __restrict__ params, const float* __restrict__ obs, int64_t n,
+                                                                  float* __restrict__ value) {
+    extern __shared__ __attribute__((aligned(16))) float gf_lds[];
+    const int tid = threadIdx.x, O = sh.obs;
+    const GfLds m = gf_carve(gf_lds, gf_pad4(O), 4);
+    gf_stage_weights(m, sh, params, 0, tid);
+    const int64_t tiles = (n + 63) / 64;
+    for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const int64_t row0 = tile * 64;
+        gf_dense_rows(m, row0, n, tid);
+        gf_load_x(m, obs, O, tid);
+        gf_forward_tile(m, 1, tid);
+        if (tid < 64 && row0 + tid < n) value[row0 + tid] = m.o[tid];
+        __syncthreads();
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// gauss_fwd_bwd_kernel: one minibatch step of one net per workgroup column (blockIdx.y = net): gather through the index list, forward, PPO loss
+// (gauss_loss_kernel's arithmetic), backward.  Gradients accumulate in registers over the workgroup's tiles and leave as one partial slab.
+// ---------------------------------------------------------------------------------------------------------
+struct GfUpdArgs {
+    GfShape sh;
+    LossParams hp;
+    const float* params;
+    const float* obs;        // [B, O] and the other flattened rollout buffers, read in place through idx
+    const float* actions;    // [B, D]
+    const float* oldlp;
+    const float* adv;
+    const float* ret;
+    const float* oldv;
+    const int32_t* idx;      // [M]
+    int M;
+    float invM;              // 1 / rows of the global minibatch
+    const AdvStat* adv_stat; // PPO_ADV_PARTS partial sums, or null (norm_adv off)
+    double global_M;
+    float* slab;             // [2][nb][slab_stride]
+    int slab_stride, nb;
+    double* loss_part;       // [GEN_LOSS_BLOCKS][8]
+};
+
+// dW[4 ub + i][4 kb + j] += sum_s dz[4 ub + i][s] in[4 kb + j][s], db[4 ub + i] += sum_s dz[4 ub + i][s]: the tile's sum from zero in ascending s, then
+// added to the running sum (the workgroup's tiles in order)
+__device__ __forceinline__ void gf_dw_tile(const float* __restrict__ dz, const float* __restrict__ in, int ub, int kb, float* acc, float* accb) {
+    float t[16], tb[4];
+#pragma unroll
+    for (int i = 0; i < 16; i++) t[i] = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 4; i++) tb[i] = 0.0f;
+    for (int s4 = 0; s4 < 64; s4 += 4) {
+        float4 d[4], h[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) d[i] = *reinterpret_cast<const float4*>(&dz[(4 * ub + i) * GF_S + s4]);
+#pragma unroll
+        for (int j = 0; j < 4; j++) h[j] = *reinterpret_cast<const float4*>(&in[(4 * kb + j) * GF_S + s4]);
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                float v = t[i * 4 + j];
+                v = __builtin_fmaf(d[i].x, h[j].x, v);
+                v = __builtin_fmaf(d[i].y, h[j].y, v);
+                v = __builtin_fmaf(d[i].z, h[j].z, v);
+                v = __builtin_fmaf(d[i].w, h[j].w, v);
+                t[i * 4 + j] = v;
+            }
+            tb[i] = (((tb[i] + d[i].x) + d[i].y) + d[i].z) + d[i].w;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 16; i++) acc[i] += t[i];
+#pragma unroll
+    for (int i = 0; i < 4; i++) accb[i] += tb[i];
+}
+
+// h[k][s] <- (sum_o W[o][k] dout[o][s]) (1 - h[k][s]^2), o ascending below n_out: d(pre-activation) of the layer under `dout`, in the activation's place.
+// lane = sample, wave w owns k = 16 w .. 16 w + 15; a thread reads and writes only its own elements of h
+__device__ __forceinline__ void gf_dz_tile(const float* __restrict__ dout, int n_out, const float* __restrict__ W, float* h, int s, int w) {
+    float acc[16];
+#pragma unroll
+    for (int i = 0; i < 16; i++) acc[i] = 0.0f;
+    for (int o = 0; o < n_out; o++) {
+        const float d = dout[o * GF_S + s];
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const float4 wv = *reinterpret_cast<const float4*>(&W[o * 64 + 16 * w + 4 * q]);
+            acc[4 * q + 0] = __builtin_fmaf(wv.x, d, acc[4 * q + 0]);
+            acc[4 * q + 1] = __builtin_fmaf(wv.y, d, acc[4 * q + 1]);
+            acc[4 * q + 2] = __builtin_fmaf(wv.z, d, acc[4 * q + 2]);
+            acc[4 * q + 3] = __builtin_fmaf(wv.w, d, acc[4 * q + 3]);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+        const float a = h[(16 * w + i) * GF_S + s];
+        h[(16 * w + i) * GF_S + s] = acc[i] * (1.0f - a * a);
+    }
+}
+
+constexpr int AM = PPO_MAX_ACT;
+
+__global__ __launch_bounds__(GF_THREADS) void gauss_fwd_bwd_kernel(GfUpdArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float gf_lds[];
+    const int tid = threadIdx.x, D = a.sh.D, O = a.sh.obs;
+    const int net = blockIdx.y, b = blockIdx.x, nb = a.nb;
+    const int out = net == 0 ? 1 : D, outP = gf_pad4(out);
+    const GfLds m = gf_carve(gf_lds, gf_pad4(O), gf_pad4(D));
+    const int obsP = m.obsP;
+    gf_stage_weights(m, a.sh, a.params, net, tid);
+    const int s = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int ub = tid >> 4, kb = tid & 15;
+    const LossParams hp = a.hp;
+    const float invM = a.invM;
+
+    float gW1[16], gW2[16], gW3[16], gb1[4], gb2[4], gb3[4];
+#pragma unroll
+    for (int i = 0; i < 16; i++) gW1[i] = gW2[i] = gW3[i] = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 4; i++) gb1[i] = gb2[i] = gb3[i] = 0.0f;
+    float dls[AM];
+#pragma unroll
+    for (int k = 0; k < AM; k++) dls[k] = 0.0f;
+    double sums[5] = { 0, 0, 0, 0, 0 };
+
+    // mean and 1 / (Bessel std + 1e-8) of the (global) minibatch's advantages from the PPO_ADV_PARTS partial sums: gauss_loss_kernel's arithmetic
+    float mean_f = 0.0f, std_f = 0.0f;
+    if (a.adv_stat && net == 1 && w == 0) {
+        double t1 = 0.0, t2 = 0.0;
+        for (int i = 0; i < PPO_ADV_PARTS; i++) { t1 += a.adv_stat[i].s1; t2 += a.adv_stat[i].s2; }
+        const double mean_a = t1 / a.global_M;
+        const double var = (t2 - t1 * mean_a) / (a.global_M - 1.0);
+        mean_f = (float)mean_a;
+        std_f = (float)sqrt(var < 0.0 ? 0.0 : var);
+    }
+    const float inv_std = 1.0f / (std_f + 1e-8f);
+    const float clip = hp.clip_coef, lo = 1 - clip, hi_c = 1 + clip;
+
+    const int tiles = (a.M + 63) / 64;
+    for (int tile = b; tile < tiles; tile += nb) {
+        if (tid < 64) m.ridx[tid] = tile * 64 + tid < a.M ? a.idx[tile * 64 + tid] : -1;
+        __syncthreads();
+        gf_load_x(m, a.obs, O, tid);
+        gf_forward_tile(m, out, tid);
+        // ---- loss: wave 0, lane = sample; d(loss)/d(output) replaces the output in OUT (zero for a sample without a row and for rows out .. outP - 1) ----
+        if (w == 0) {
+            const int r = m.ridx[s];
+            if (net == 1) {
+                float z[AM];
+                float g_nlp = 0.0f, g_ent = 0.0f;
+                if (r >= 0) {
+                    double ent_d = 0.0;   // the same on every row
+#pragma unroll
+                    for (int k = 0; k < AM; k++) if (k < D) ent_d += gauss_entropy(m.ls[k]);
+                    const float ent = (float)ent_d;
+                    double nlp_d = 0.0;
+#pragma unroll
+                    for (int k = 0; k < AM; k++) {
+                        z[k] = 0.0f;
+                        if (k < D) {
+                            z[k] = gauss_z(a.actions[(int64_t)r * D + k], m.o[k * GF_S + s], m.inv[k]);
+                            nlp_d += gauss_logp(z[k], m.ls[k]);
+                        }
+                    }
+                    const float logratio = (float)(nlp_d - (double)a.oldlp[r]);
+                    const float ratio = expf(logratio);
+                    float adv = a.adv[r];
+                    if (hp.norm_adv) adv = (adv - mean_f) * inv_std;
+                    const float rc = ratio < lo ? lo : (ratio > hi_c ? hi_c : ratio);
+                    const float l1 = -adv * ratio, l2 = -adv * rc;
+                    const bool inside = (ratio >= lo && ratio <= hi_c);
+                    float d_ratio;
+                    if (l1 > l2) d_ratio = -adv;
+                    else if (l1 < l2) d_ratio = inside ? -adv : 0.0f;
+                    else d_ratio = 0.5f * -adv + (inside ? 0.5f * -adv : 0.0f);   // torch::max splits ties half/half
+                    g_nlp = invM * d_ratio * ratio;
+                    g_ent = -hp.ent_coef * invM;
+                    sums[0] += (double)(l1 > l2 ? l1 : l2);
+                    sums[1] += (double)ent;
+                    sums[2] += (double)((ratio - 1.0f) - logratio);
+                    sums[3] += (fabsf(ratio - 1.0f) > clip) ? 1.0 : 0.0;
+                }
+#pragma unroll
+                for (int k = 0; k < AM; k++) {
+                    if (k < outP) {
+                        float dm = 0.0f;
+                        if (r >= 0 && k < D) {
+                            dm = g_nlp * z[k] * m.inv[k];
+                            dls[k] += g_nlp * (z[k] * z[k] - 1.0f) + g_ent;
+                        }
+                        m.o[k * GF_S + s] = dm;
+                    }
+                }
+            } else {
+                float g_v = 0.0f;
+                if (r >= 0) {   // value loss (PPO_Discrete.cpp:603-625)
+                    const float v = m.o[s], R = a.ret[r], vold = a.oldv[r];
+                    const float un = (v - R) * (v - R);
+                    float lossv;
+                    if (hp.clip_vloss) {
+                        const float dv = v - vold;
+                        const float dvc = dv < -clip ? -clip : (dv > clip ? clip : dv);
+                        const float vc = vold + dvc;
+                        const float cl = (vc - R) * (vc - R);
+                        lossv = un > cl ? un : cl;
+                        const bool vin = (dv >= -clip && dv <= clip);
+                        const float d_un = 2.0f * (v - R), d_cl = vin ? 2.0f * (vc - R) : 0.0f;
+                        const float d = un > cl ? d_un : (un < cl ? d_cl : 0.5f * d_un + 0.5f * d_cl);
+                        g_v = hp.vf_coef * 0.5f * invM * d;
+                    } else {
+                        lossv = un;
+                        g_v = hp.vf_coef * 0.5f * invM * 2.0f * (v - R);
+                    }
+                    sums[4] += (double)lossv;
+                }
+                m.o[s] = g_v;
+                m.o[1 * GF_S + s] = 0.0f; m.o[2 * GF_S + s] = 0.0f; m.o[3 * GF_S + s] = 0.0f;
+            }
+        }
+        __syncthreads();
+        // ---- backward ----
+        if (4 * ub < outP) gf_dw_tile(m.o, m.h2, ub, kb, gW3, gb3);     // dW3 = dOUT H2^T, db3
+        __syncthreads();                                                // ... has read H2
+        gf_dz_tile(m.o, out, m.w3, m.h2, s, w);                         // H2 <- dZ2
+        __syncthreads();
+        gf_dw_tile(m.h2, m.h1, ub, kb, gW2, gb2);                       // dW2 = dZ2 H1^T, db2
+        __syncthreads();                                                // ... has read H1
+        gf_dz_tile(m.h2, 64, m.w2, m.h1, s, w);                         // H1 <- dZ1
+        __syncthreads();
+        if (4 * kb < obsP) gf_dw_tile(m.h1, m.x, ub, kb, gW1, gb1);     // dW1 = dZ1 X^T, db1 (the threads of kb = 0 are always among them)
+        __syncthreads();                                                // the images are free for the next tile
+    }
+
+    // ---- the workgroup's partial slab, in the net's own parameter order: W1 b1 W2 b2 W3 b3 (actor: then log_std, which sits behind it in the flat vector) ----
+    float* slab = a.slab + ((size_t)net * nb + b) * a.slab_stride;
+    const int base = a.sh.off[net][0];
+    {
+        float* dW1 = slab + (a.sh.off[net][0] - base);
+        float* dW2 = slab + (a.sh.off[net][2] - base);
+        float* dW3 = slab + (a.sh.off[net][4] - base);
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int u = 4 * ub + i, k = 4 * kb + j;
+                if (k < O) dW1[u * O + k] = gW1[i * 4 + j];
+                dW2[u * 64 + k] = gW2[i * 4 + j];
+                if (u < out) dW3[u * 64 + k] = gW3[i * 4 + j];
+            }
+        }
+        if (kb == 0) {
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const int u = 4 * ub + i;
+                slab[a.sh.off[net][1] - base + u] = gb1[i];
+                slab[a.sh.off[net][3] - base + u] = gb2[i];
+                if (u < out) slab[a.sh.off[net][5] - base + u] = gb3[i];
+            }
+        }
+    }
+    if (w == 0) {
+        if (net == 1) {
+#pragma unroll
+            for (int k = 0; k < AM; k++) {
+                if (k < D) {
+                    const float t = wave_sum(dls[k]);
+                    if (s == 0) slab[a.sh.logstd_off - base + k] = t;
+                }
+            }
+        }
+        // loss partials in gen_loss_sums's layout: the actor's workgroup b writes columns 0 .. 3 (and the padding 5 .. 7), the critic's column 4, of row b;
+        // together the nb workgroups of a net write ALL GEN_LOSS_BLOCKS rows, the rows without a workgroup as zeros
+        double t[5];
+#pragma unroll
+        for (int k = 0; k < 5; k++) t[k] = wave_sum_d_dpp(sums[k]);
+        if (s < 8 && (net == 1 ? s != 4 : s == 4)) {
+            double v = 0.0;
+#pragma unroll
+            for (int k = 0; k < 5; k++) v = s == k ? t[k] : v;
+            for (int row = b; row < GEN_LOSS_BLOCKS; row += nb) a.loss_part[row * 8 + s] = row == b ? v : 0.0;
+        }
+    }
+}
+
+// grads[i] = the slabs' elements in workgroup order (one thread per element; the actor's range runs on through log_std)
+__global__ __launch_bounds__(256) void gauss_slab_reduce_kernel(const float* __restrict__ slab, int slab_stride, int nb, int net1_off, int P, float* __restrict__ grads) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= P) return;
+    const int net = i >= net1_off ? 1 : 0;
+    const float* p = slab + (size_t)net * nb * slab_stride + (i - (net ? net1_off : 0));
+    float acc = 0.0f;
+    for (int k = 0; k < nb; k++) acc += p[(size_t)k * slab_stride];
+    grads[i] = acc;
+}
+
+template <typename K>
+hipError_t gf_allow(std::atomic<unsigned long long>& done, K kernel, int bytes) {
+    return bytes > 64 * 1024 ? allow_dynamic_lds(done, reinterpret_cast<const void*>(kernel)) : hipSuccess;
+}
+
+}  // namespace
+
+bool gauss_fused_serves_shape(int obs, int hidden, int n_hidden, int D) { return hidden == 64 && n_hidden == 2 && D >= 1 && D <= PPO_MAX_ACT && obs >= 1 && obs <= GAUSS_FUSED_MAX_OBS; }
+
+int64_t gauss_fused_slab_stride(const GenLayout& L) { return ((int64_t)std::max(L.net_size[0], L.net_size[1] + L.gauss) + 3) & ~3ll; }
+
+hipError_t gauss_fused_act(const GenLayout& L, const float* params, const float* obs, const float* forced, int64_t n, int64_t seed, int64_t row_offset,
+                           int64_t step_index, bool greedy, float* action, float* logprob, float* entropy, const GaussStepStores* st, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    const GfShape sh = gf_shape(L);
+    const int bytes = gf_lds_floats(gf_pad4(L.obs), gf_pad4(L.gauss)) * 4;
+    const int64_t tiles = (n + 63) / 64;
+    const dim3 grid((unsigned)std::min<int64_t>(tiles, 1024)), block(GF_THREADS);
+    GfStepStores ss{};
+    if (st) ss = GfStepStores{ st->done_prev, st->obs_t, st->act_t, st->lp_t, st->dones_t };
+    static std::atomic<unsigned long long> done_g{ 0 }, done_s{ 0 };
+    if (greedy) {
+        const hipError_t e = gf_allow(done_g, gauss_act_kernel<true>, bytes);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(gauss_act_kernel<true>, grid, block, bytes, s, sh, params, obs, nullptr, n, seed, row_offset, step_index, action, logprob, entropy, ss);
+    } else {
+        const hipError_t e = gf_allow(done_s, gauss_act_kernel<false>, bytes);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(gauss_act_kernel<false>, grid, block, bytes, s, sh, params, obs, forced, n, seed, row_offset, step_index, action, logprob, entropy, ss);
+    }
+    return hipGetLastError();
+}
+
+hipError_t gauss_fused_values(const GenLayout& L, const float* params, const float* obs, int64_t n, float* value, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    const GfShape sh = gf_shape(L);
+    const int bytes = gf_lds_floats(gf_pad4(L.obs), 4) * 4;
+    const int64_t tiles = (n + 63) / 64;
+    static std::atomic<unsigned long long> done{ 0 };
+    const hipError_t e = gf_allow(done, gauss_values_kernel, bytes);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(gauss_values_kernel, dim3((unsigned)std::min<int64_t>(tiles, 1024)), dim3(GF_THREADS), bytes, s, sh, params, obs, n, value);
+    return hipGetLastError();
+}
+
+hipError_t gauss_fused_fwd_bwd(const GenLayout& L, const LossParams& hp, const float* params, const float* obs, const float* actions, const float* oldlp,
+                               const float* adv, const float* ret, const float* oldv, const int32_t* idx, int64_t M, double inv_global_M, double global_M,
+                               const AdvStat* adv_stat, float* slab, double* loss_part, float* grads, hipStream_t s) {
+    if (M < 1 || M >= (1ll << 31) - 64 || !slab || !loss_part) return hipErrorInvalidValue;
+    GfUpdArgs a{};
+    a.sh = gf_shape(L);
+    a.hp = hp;
+    a.params = params; a.obs = obs; a.actions = actions; a.oldlp = oldlp; a.adv = adv; a.ret = ret; a.oldv = oldv; a.idx = idx;
+    a.M = (int)M;
+    a.invM = (float)inv_global_M;
+    a.adv_stat = (adv_stat && hp.norm_adv) ? adv_stat : nullptr;
+    a.global_M = global_M;
+    a.slab = slab;
+    a.slab_stride = (int)gauss_fused_slab_stride(L);
+    a.nb = (int)std::min<int64_t>((M + 63) / 64, GAUSS_FUSED_MAX_BLOCKS);
+    a.loss_part = loss_part;
+    const int bytes = gf_lds_floats(gf_pad4(L.obs), gf_pad4(L.gauss)) * 4;
+    static std::atomic<unsigned long long> done{ 0 };
+    const hipError_t e = gf_allow(done, gauss_fwd_bwd_kernel, bytes);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(gauss_fwd_bwd_kernel, dim3(a.nb, 2), dim3(GF_THREADS), bytes, s, a);
+    hipLaunchKernelGGL(gauss_slab_reduce_kernel, dim3((L.P + 255) / 256), dim3(256), 0, s, slab, a.slab_stride, a.nb, L.net_off[1], L.P, grads);
+    return hipGetLastError();
+}

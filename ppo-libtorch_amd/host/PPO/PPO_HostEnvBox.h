@@ -8,7 +8,8 @@
 // episode_reward.  step() receives the policy's RAW sample mu + sigma * eps, D = action_dim values: an env with bounds clips its own copy (the rollout keeps
 // the raw sample, whose log-prob it stored).  The envs are made by a factory (default std::make_shared<Env>(m_seed)); each is stepped by one pool job at a time.
 // The extension keys of PPO_HostEnv work the same way: norm_obs, norm_reward (statistics beside every checkpoint), bootstrap_truncated.  Env groups are
-// not built for Gaussian contexts: env_groups > 1 throws the library's message.  Checkpoints keep the reference's container with one more tensor, m_logStd
+// not built for Gaussian contexts: env_groups > 1 throws the library's message.  `fused_policy = true` in [environment] (default false) runs the context
+// on the fused Gaussian kernels (PPO_KERNEL_GAUSS_FUSED in ppo_hip.h: obs_size <= 64, action_dim <= 32); ppo_gauss_fused_launches(m_ctx, ...) tells.  Checkpoints keep the reference's container with one more tensor, m_logStd
 // (Utils/TorchArchive.h); no exchange of such files with the reference is claimed.
 #pragma once
 #include <algorithm>
