@@ -40,14 +40,42 @@ enum { PPO_OK = 0, PPO_ERR_INVALID = 1, PPO_ERR_HIP = 2, PPO_ERR_STATE = 3, PPO_
  * ppo_host_* calls ("Caller-stepped environments" below); ppo_rollout / ppo_train_iteration / ppo_env_reset / ppo_env_step return PPO_ERR_UNSUPPORTED.
  * obs_size is not checked against any env.  The reference's network (2 x 64, f32) with obs_size 2, 4 or 8 runs on the reference-shape kernels, every
  * other network (and compute_dtype) on the generic engine with PPO_ENV_SYNTHETIC's limits. */
-enum { PPO_ENV_CARTPOLE = 0, PPO_ENV_MOUNTAINCAR = 1, PPO_ENV_SYNTHETIC = 2, PPO_ENV_HOST = 3 };
+/* PPO_ENV_PENDULUM (new; the reference has no continuous-action env): gymnasium's Pendulum-v1 on the device, the env of the Gaussian policy's fused rollout.
+ * State (theta, theta_dot) f32 -- PPO_BUF_ENV_STATE is [2, N], ppo_env_set_state_h / ppo_env_get_state_h take [N, 2] -- observation
+ * (cos theta, sin theta, theta_dot), obs_size 3, one real-valued action.  One step with the RAW action a, every operation rounded on its own:
+ *   u      = min(max(a, -2), 2)
+ *   x      = theta + PI_F;  thn = (x - TWO_PI_F * floorf(x / TWO_PI_F)) - PI_F                      (gym's angle_normalize; PI_F = (float)pi, TWO_PI_F = (float)(2 pi))
+ *   reward = -((thn * thn + 0.1f * (theta_dot * theta_dot)) + 0.001f * (u * u))
+ *   td'    = theta_dot + (15.0f * sinf(theta) + 3.0f * u) * 0.05f;  td' = min(max(td', -8), 8)
+ *   th'    = theta + td' * 0.05f                                                                     (not wrapped, as in gym)
+ *   obs'   = (cosf(th'), sinf(th'), td');  terminated = 0 always
+ * with sinf / cosf the library's own device functions (glibc 2.35's sinf / cosf, bit for bit).  Only the env's copy of the action is clipped: PPO_BUF_ACTIONS
+ * keeps the raw sample, whose log-prob is the stored one (PPO_DIST_GAUSSIAN's rule below: the rollout never clips what it stores).  An episode ends only when its length reaches max_episode_steps
+ * (done = 1, FIN_LEN / FIN_REW written, auto-reset: ppo_env_step's bookkeeping).  Reset number k of global env e: w = philox4x32_10(seed; e, k, 0, 1),
+ * theta = uniform(w.x, -PI_F, PI_F), theta_dot = uniform(w.y, -1, 1) (MountainCar's keying and uniform mapping); PPO_BUF_RESET_COUNT counts them.
+ * ppo_ctx_create accepts the env in exactly one form: dist_kind = PPO_DIST_GAUSSIAN, n_heads = 1, head_dims[0] = 1, obs_size = 3, hidden = 64,
+ * n_hidden = 2, PPO_DTYPE_F32, kernel_flags containing PPO_KERNEL_GAUSS_FUSED (required, never implied: another engine never serves in the flag's place)
+ * and 1 <= max_episode_steps <= 290 (theta is not wrapped and moves by at most 0.4 a step; the device sinf / cosf are glibc's for |theta| < 120).  A wrong
+ * obs_size returns PPO_ERR_INVALID with the reference's obs-size message, anything else PPO_ERR_UNSUPPORTED with a message that names the limit.
+ * Calls: ppo_env_reset, ppo_env_set_state_h / ppo_env_get_state_h, ppo_rollout(ctx, NULL) / ppo_rollout_f32, ppo_env_step_f32, ppo_env_transition_f32,
+ * ppo_calc_advantage, ppo_update, ppo_train_iteration, ppo_policy_act_f32, ppo_get_value, ppo_target_kl_set, the statistics and profile calls,
+ * ppo_gauss_fused_launches.  ppo_rollout is THREE launches: gauss_rollout_kernel (all T steps; a workgroup of 256 threads owns 64 envs for the whole rollout,
+ * the actor's weights resident in LDS) and the critic over the T * N stored observations and over NEXT_OBS; a stepwise loop of ppo_policy_act_f32(obs,
+ * step_index = rollout_steps + t) and ppo_env_step_f32 reproduces every buffer it fills bit for bit (tests/test_gpu_pendulum.py).
+ * Refused, each with its reason, changing nothing: the ppo_host_* / ppo_dev_* calls (PPO_ERR_STATE, as on any device-env context); ppo_evaluate
+ * (PPO_ERR_UNSUPPORTED: step episodes through ppo_policy_act_f32 with greedy = 1 and ppo_env_transition_f32); ppo_env_truncation_bootstrap
+ * (PPO_ERR_UNSUPPORTED: its fold rebuilds the final observation from PPO_BUF_OBS, and a Pendulum observation does not hold theta); ppo_obs_norm_* and
+ * ppo_reward_norm_* (PPO_ERR_UNSUPPORTED, as on every device env); ppo_env_step and ppo_rollout with an i64 array (PPO_ERR_UNSUPPORTED, naming the _f32 call).
+ * Sharding (ppo_comm_init*) is neither claimed nor tested for this env. */
+enum { PPO_ENV_CARTPOLE = 0, PPO_ENV_MOUNTAINCAR = 1, PPO_ENV_SYNTHETIC = 2, PPO_ENV_HOST = 3, PPO_ENV_PENDULUM = 4 };
 /* PPO_DIST_CATEGORICAL reproduces Distributions/Categorical.cpp including its entropy clamp (:112-119);
  * PPO_DIST_MASKED reproduces Distributions/CategoricalMasked.cpp (true entropy, -1e8 masking).
  * PPO_DIST_GAUSSIAN (new; the reference has no continuous policy): a diagonal Gaussian over D = head_dims[0] real-valued actions (n_heads = 1,
  * 1 <= D <= 32).  The actor's output layer gives the mean mu[D]; a state-independent parameter log_std[D] -- ONE MORE TENSOR, the last in
  * Agent::parameters() order, behind the actor's layers (ppo_param_count, ppo_param_shapes), initialised to 0 -- gives the scale.  With
  * z = (a - mu) exp(-log_std):  log-prob = sum_d (-z_d^2 / 2 - log_std_d - log(2 pi) / 2),  entropy = sum_d (1 / 2 + log(2 pi) / 2 + log_std_d), no clamp.
- * Serves PPO_ENV_HOST contexts with PPO_DTYPE_F32, on the generic engine (also for a 2 x 64 network, unless kernel_flags has PPO_KERNEL_GAUSS_FUSED); any other env_kind, PPO_DTYPE_BF16 or
+ * Serves PPO_ENV_HOST contexts with PPO_DTYPE_F32, on the generic engine (also for a 2 x 64 network, unless kernel_flags has PPO_KERNEL_GAUSS_FUSED), and PPO_ENV_PENDULUM
+ * contexts in the one form that env accepts (above); any other env_kind, PPO_DTYPE_BF16 or
  * n_heads != 1 make ppo_ctx_create return PPO_ERR_UNSUPPORTED.  Actions are f32: PPO_BUF_ACTIONS is f32 [T,N,D], PPO_BUF_MASKS is not used, and the
  * calls that carry actions have _f32 twins (ppo_host_act_f32, ppo_dev_act_f32, ppo_policy_act_f32); the integer calls return PPO_ERR_UNSUPPORTED on a
  * Gaussian context and name the twin, and the twins do the same on a categorical context.  Env groups (ppo_host_rollout_begin_groups) return
@@ -285,7 +313,8 @@ PPO_API ppo_status ppo_gaussian(const float* mean, const float* log_std, const f
 
 /* Host-side counts, since the context's creation, of the launches of the three PPO_KERNEL_GAUSS_FUSED kernels: act (one per env step / ppo_policy_act_f32),
  * value (one per critic batch) and update (one per minibatch step).  All three are 0 on a context without the flag: proof of which path ran, like
- * ppo_profile.vector_fallback_launches.  Outputs may be NULL. */
+ * ppo_profile.vector_fallback_launches.  Outputs may be NULL.  PPO_ENV_PENDULUM's rollout launch (gauss_rollout_kernel) is none of the three: a ppo_rollout there
+ * moves `value` by 2 and `act` not at all. */
 PPO_API ppo_status ppo_gauss_fused_launches(ppo_ctx* ctx, int64_t* act, int64_t* value, int64_t* update);
 
 /* Categorical::sample / CategoricalMasked::sample (Categorical.cpp:73-79: multinomial(probs, 1, replacement = true)) on given
@@ -326,6 +355,14 @@ PPO_API ppo_status ppo_env_reset(ppo_ctx* ctx);
 /* PPO_Discrete::stepEnvs (PPO_Discrete.cpp:413-483): action i64 [N,H] (column 0 drives the env);
  * outputs obs [N,O] (first obs of the new episode where done), reward f32 [N], done i32 [N]. */
 PPO_API ppo_status ppo_env_step(ppo_ctx* ctx, const int64_t* action, float* obs, float* reward, int32_t* done);
+/* ppo_env_step for a context whose env takes real-valued actions (PPO_ENV_PENDULUM): action f32 [N,D] (the raw action; the env clips its own copy), the same
+ * outputs and the same auto-reset bookkeeping.  ppo_env_step on such a context returns PPO_ERR_UNSUPPORTED and names this call; this call returns
+ * PPO_ERR_UNSUPPORTED on a context with integer actions and on PPO_ENV_HOST contexts. */
+PPO_API ppo_status ppo_env_step_f32(ppo_ctx* ctx, const float* action /* [N,D] */, float* obs, float* reward, int32_t* done);
+/* ppo_env_transition for PPO_ENV_PENDULUM (any other env_kind: PPO_ERR_UNSUPPORTED): stateless; state_in f32 [n,2], action f32 [n,D] (D = 1, raw);
+ * outputs next_state [n,2], obs_out [n,3] = the observation of next_state or NULL, reward f32 [n], terminated i32 [n] (always 0). */
+PPO_API ppo_status ppo_env_transition_f32(int32_t env_kind, const float* state_in, const float* action, int64_t n, float* next_state, float* obs_out,
+                                          float* reward, int32_t* terminated, void* stream);
 /* Inject / read env state for teacher-forced parity: state_h [N,O] AoS, ep_len i32, ep_rew f32, reset_count i32 (NULL = skip). */
 PPO_API ppo_status ppo_env_set_state_h(ppo_ctx* ctx, const float* state_h, const int32_t* ep_len_h, const float* ep_rew_h,
                                const int32_t* reset_count_h);
@@ -338,6 +375,10 @@ PPO_API ppo_status ppo_env_get_state_h(ppo_ctx* ctx, float* state_h, int32_t* ep
  * T x { store obs/done, policy forward + sample, store value/action/logprob, env step + auto-reset, store reward }.
  * forced_actions i64 [T,N,H] or NULL (teacher-forcing for parity).  Leaves NEXT_OBS / NEXT_DONE for the bootstrap. */
 PPO_API ppo_status ppo_rollout(ppo_ctx* ctx, const int64_t* forced_actions);
+/* ppo_rollout for Gaussian device-env contexts (PPO_ENV_PENDULUM): forced_actions f32 [T,N,D] or NULL; a forced action is stored in PPO_BUF_ACTIONS as given,
+ * with the log-prob ppo_policy_act_f32 gives it, and steps the env.  ppo_rollout(ctx, NULL) on such a context is this call with NULL; ppo_rollout with a
+ * non-NULL i64 array there returns PPO_ERR_UNSUPPORTED and names this call.  PPO_ERR_UNSUPPORTED on a categorical context and on PPO_ENV_HOST contexts. */
+PPO_API ppo_status ppo_rollout_f32(ppo_ctx* ctx, const float* forced_actions /* [T,N,D] or NULL */);
 /* Time-limit truncations of the context's own environments (new): bootstrap the value where the time limit cut an episode off.
  *
  * The reference ends an episode that reaches max_episode_steps exactly like one the env terminated (PPO_Discrete.cpp:443-452), so the scan cuts the return
@@ -356,7 +397,8 @@ PPO_API ppo_status ppo_rollout(ppo_ctx* ctx, const int64_t* forced_actions);
  * delta = r + gamma V(final) - V(obs_t) is formed from ONE critic.  Raw rewards: PPO_BUF_REWARDS holds the folded rewards after ppo_rollout; FIN_REW,
  * EP_REW, the episode ring and every episode statistic keep the raw reward.  ppo_evaluate is untouched.  The common workgroup -- no episode at the limit
  * among its 256 samples -- costs one pass over FIN_LEN.  Works with forced_actions; purely local: no collective on a sharded context.
- * Errors: PPO_ERR_UNSUPPORTED on a PPO_ENV_SYNTHETIC context (its observations are noise: an episode there has no last observation) and on a
+ * Errors: PPO_ERR_UNSUPPORTED on a PPO_ENV_SYNTHETIC context (its observations are noise: an episode there has no last observation), on a PPO_ENV_PENDULUM
+ * context (the fold rebuilds the final observation from PPO_BUF_OBS, and a Pendulum observation does not hold theta) and on a
  * PPO_ENV_HOST context (the message names ppo_host_observe_truncated); PPO_ERR_INVALID for `on` outside 0..1 (and a null count, or arrays shorter than the
  * list, in ppo_env_truncations).  A failing call changes nothing. */
 PPO_API ppo_status ppo_env_truncation_bootstrap(ppo_ctx* ctx, int32_t on);   /* 0 off (default), 1 on */
@@ -715,6 +757,7 @@ typedef struct ppo_eval_stats {
  *   (a vector-kernel fallback of this launch is not counted).  Purely local: no collective on a sharded context (every rank that asks the same question
  *   gets the same answer).
  *   Errors: PPO_ENV_SYNTHETIC and PPO_ENV_HOST contexts -> PPO_ERR_UNSUPPORTED (step the episodes yourself around ppo_policy_act_greedy);
+ *   PPO_ENV_PENDULUM contexts -> PPO_ERR_UNSUPPORTED (step the episodes through ppo_policy_act_f32 with greedy = 1 and ppo_env_transition_f32);
  *   n_episodes <= 0, out_h == NULL, max_episode_steps <= 0 -> PPO_ERR_INVALID.  A failing call changes nothing. */
 PPO_API ppo_status ppo_evaluate(ppo_ctx* ctx, int64_t n_episodes, int64_t seed, int32_t greedy,
                                 float* ep_return /* dev f32[n] or NULL */, int32_t* ep_length /* dev i32[n] or NULL */,

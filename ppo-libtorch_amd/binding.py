@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PPO_HIP_LIBRARY") or os.path.join(_HERE, "libppo_hip.so")
 
 MAX_HEADS = 8
-ENV_CARTPOLE, ENV_MOUNTAINCAR, ENV_SYNTHETIC, ENV_HOST = 0, 1, 2, 3
+ENV_CARTPOLE, ENV_MOUNTAINCAR, ENV_SYNTHETIC, ENV_HOST, ENV_PENDULUM = 0, 1, 2, 3, 4   # ENV_PENDULUM: Pendulum-v1 on the device, DIST_GAUSSIAN + KERNEL_GAUSS_FUSED only
 MM_EPI_NONE, MM_EPI_BIAS, MM_EPI_BIAS_TANH, MM_EPI_DTANH = 0, 1, 2, 3
 MM_F32X3, MM_BF16 = 0, 1
 DIST_CATEGORICAL, DIST_MASKED, DIST_GAUSSIAN = 0, 1, 2   # DIST_GAUSSIAN: f32 actions [.., D], the *_f32 calls (include/ppo_hip.h PPO_DIST_GAUSSIAN)
@@ -59,6 +59,7 @@ ABI_SYMBOLS = [
     "ppo_host_act_f32", "ppo_dev_act_f32", "ppo_policy_act_f32", "ppo_gaussian",
     "ppo_target_kl_set", "ppo_target_kl_get", "ppo_early_stop_read",
     "ppo_gauss_fused_launches",
+    "ppo_rollout_f32", "ppo_env_step_f32", "ppo_env_transition_f32",
 ]
 
 
@@ -171,6 +172,9 @@ def lib():
         L.ppo_target_kl_get.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         L.ppo_early_stop_read.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int64)]
         L.ppo_gauss_fused_launches.argtypes = [C.c_void_p] + [C.POINTER(C.c_int64)] * 3
+        L.ppo_rollout_f32.argtypes = [C.c_void_p] * 2
+        L.ppo_env_step_f32.argtypes = [C.c_void_p] * 5
+        L.ppo_env_transition_f32.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 5
         for name in ABI_SYMBOLS:
             getattr(L, name)  # AttributeError if the build lacks a declared symbol
         if L.ppo_abi_version() != ABI_VERSION:
@@ -233,6 +237,7 @@ class Context:
         self.T, self.N, self.O, self.H = cfg.num_steps, cfg.num_envs, cfg.obs_size, cfg.n_heads
         self.A = sum(cfg.head_dims[i] for i in range(cfg.n_heads))
         self.B = self.T * self.N
+        self.S = 2 if cfg.env_kind == ENV_PENDULUM else self.O   # width of the env state (Pendulum: theta, theta_dot behind 3 observations)
         self.P = int(lib().ppo_param_count(self.h))
 
     def close(self):
@@ -392,6 +397,17 @@ class Context:
         _check(lib().ppo_env_step(self.h, d_a.ptr, d_o.ptr, d_r.ptr, d_d.ptr), self.h)
         return d_o.download(), d_r.download(), d_d.download()
 
+    def env_step_f32(self, action):
+        """ppo_env_step_f32 (ENV_PENDULUM): action f32 [N,D], the raw action (the env clips its own copy).  Returns (obs [N,O], reward [N], done i32 [N])."""
+        tmp = [self.dev(np.asarray(action, np.float32).reshape(self.N, self.A)), self.empty((self.N, self.O), np.float32), self.empty(self.N, np.float32),
+               self.empty(self.N, np.int32)]
+        try:
+            _check(lib().ppo_env_step_f32(self.h, *(x.ptr for x in tmp)), self.h)
+            return tuple(x.download() for x in tmp[1:])
+        finally:
+            for x in tmp:
+                x.free()
+
     def env_set_state(self, state=None, ep_len=None, ep_rew=None, reset_count=None):
         def p(a, dt):
             return None if a is None else np.ascontiguousarray(a, dt)
@@ -399,7 +415,7 @@ class Context:
         _check(lib().ppo_env_set_state_h(self.h, *(x.ctypes.data_as(C.c_void_p) if x is not None else None for x in (s, l, r, k))), self.h)
 
     def env_get_state(self):
-        s, l = np.empty((self.N, self.O), np.float32), np.empty(self.N, np.int32)
+        s, l = np.empty((self.N, self.S), np.float32), np.empty(self.N, np.int32)
         r, k = np.empty(self.N, np.float32), np.empty(self.N, np.int32)
         _check(lib().ppo_env_get_state_h(self.h, *(x.ctypes.data_as(C.c_void_p) for x in (s, l, r, k))), self.h)
         return s, l, r, k
@@ -632,7 +648,16 @@ class Context:
 
     # ---- rollout / advantages / update
     def rollout(self, forced_actions=None):
-        d = self.dev(np.asarray(forced_actions).reshape(self.T, self.N, self.H), np.int64) if forced_actions is not None else None
+        """ppo_rollout; on a DIST_GAUSSIAN context with forced actions ppo_rollout_f32 (f32 [T,N,D]); an integer array there is passed to ppo_rollout, which
+        refuses it."""
+        if forced_actions is not None and self.cfg.dist_kind == DIST_GAUSSIAN and np.asarray(forced_actions).dtype.kind == "f":
+            d = self.dev(np.asarray(forced_actions, np.float32).reshape(self.T, self.N, self.A))
+            try:
+                _check(lib().ppo_rollout_f32(self.h, d.ptr), self.h)
+            finally:
+                d.free()
+            return
+        d = self.dev(np.asarray(forced_actions).reshape(self.T, self.N, -1), np.int64) if forced_actions is not None else None
         _check(lib().ppo_rollout(self.h, d.ptr if d else None), self.h)
 
     def calc_advantage(self):
@@ -790,6 +815,22 @@ def env_transition(ctx, env_kind, state, action):
     _check(lib().ppo_env_transition(C.c_int32(env_kind), d_s.ptr, d_a.ptr, C.c_int64(n), d_ns.ptr, d_r.ptr, d_t.ptr, C.c_void_p(ctx.stream())), ctx.h)
     ctx.sync()
     return d_ns.download(), d_r.download(), d_t.download()
+
+
+def env_transition_f32(ctx, env_kind, state, action, want_obs=True):
+    """ppo_env_transition_f32 (ENV_PENDULUM): state f32 [n,2], action f32 [n,1] raw.  Returns (next_state, obs [n,3] or None, reward, terminated)."""
+    state = np.ascontiguousarray(state, np.float32)
+    n, S = state.shape
+    tmp = [ctx.dev(state), ctx.dev(np.asarray(action, np.float32).reshape(n, -1)), ctx.empty((n, S), np.float32), ctx.empty((n, 3), np.float32),
+           ctx.empty(n, np.float32), ctx.empty(n, np.int32)]
+    try:
+        _check(lib().ppo_env_transition_f32(C.c_int32(env_kind), tmp[0].ptr, tmp[1].ptr, C.c_int64(n), tmp[2].ptr, tmp[3].ptr if want_obs else None, tmp[4].ptr,
+                                            tmp[5].ptr, C.c_void_p(ctx.stream())), ctx.h)
+        ctx.sync()
+        return tmp[2].download(), (tmp[3].download() if want_obs else None), tmp[4].download(), tmp[5].download()
+    finally:
+        for x in tmp:
+            x.free()
 
 
 def categorical(ctx, dist_kind, logits, mask=None, value=None):

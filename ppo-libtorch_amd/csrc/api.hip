@@ -552,19 +552,43 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
     const bool gauss = cfg->dist_kind == PPO_DIST_GAUSSIAN;   // diagonal-Gaussian policies: always the generic engine (kernels_gauss.hip)
     const bool host_ref = host_env && !gauss && cfg->hidden == PPO_HIDDEN && cfg->n_hidden == 2 && cfg->compute_dtype == PPO_DTYPE_F32 &&
                           (cfg->obs_size == 2 || cfg->obs_size == 4 || cfg->obs_size == 8);
-    const bool generic = cfg->env_kind == PPO_ENV_SYNTHETIC || (host_env && !host_ref);
+    // PPO_ENV_PENDULUM: the device env of the fused Gaussian kernels; the network lives in the generic engine's layout (GenericCtx), as a PPO_ENV_HOST
+    // context with PPO_KERNEL_GAUSS_FUSED does, and only the rollout differs (gauss_rollout_kernel)
+    const bool pendulum = cfg->env_kind == PPO_ENV_PENDULUM;
+    const bool generic = cfg->env_kind == PPO_ENV_SYNTHETIC || (host_env && !host_ref) || pendulum;
     if (!generic && (cfg->hidden != PPO_HIDDEN || cfg->n_hidden != 2))
         return fail(nullptr, PPO_ERR_UNSUPPORTED, "only the reference architecture (2 hidden layers of 64, Agent.cpp:25-59) is built for the reference's "
                     "environments; got %d x %d (other shapes run with env_kind = PPO_ENV_SYNTHETIC)", cfg->n_hidden, cfg->hidden);
-    if (generic && (cfg->hidden < 1 || cfg->hidden > 2048 || cfg->n_hidden < 1 || cfg->n_hidden > GEN_MAX_LAYERS - 1 || cfg->obs_size < 1 || cfg->obs_size > 8192))
+    if (generic && !pendulum && (cfg->hidden < 1 || cfg->hidden > 2048 || cfg->n_hidden < 1 || cfg->n_hidden > GEN_MAX_LAYERS - 1 || cfg->obs_size < 1 || cfg->obs_size > 8192))
         return fail(nullptr, PPO_ERR_UNSUPPORTED, "generic network out of range: hidden %d (1..2048), n_hidden %d (1..%d), obs %d (1..8192)", cfg->hidden,
                     cfg->n_hidden, GEN_MAX_LAYERS - 1, cfg->obs_size);
-    if (cfg->env_kind != PPO_ENV_CARTPOLE && cfg->env_kind != PPO_ENV_MOUNTAINCAR && cfg->env_kind != PPO_ENV_SYNTHETIC && cfg->env_kind != PPO_ENV_HOST)
+    if (cfg->env_kind != PPO_ENV_CARTPOLE && cfg->env_kind != PPO_ENV_MOUNTAINCAR && cfg->env_kind != PPO_ENV_SYNTHETIC && cfg->env_kind != PPO_ENV_HOST && !pendulum)
         return fail(nullptr, PPO_ERR_INVALID, "unknown env_kind %d", cfg->env_kind);
     if (cfg->dist_kind != PPO_DIST_CATEGORICAL && cfg->dist_kind != PPO_DIST_MASKED && !gauss) return fail(nullptr, PPO_ERR_INVALID, "unknown dist_kind %d", cfg->dist_kind);
     if (cfg->compute_dtype != PPO_DTYPE_F32 && cfg->compute_dtype != PPO_DTYPE_BF16) return fail(nullptr, PPO_ERR_INVALID, "unknown compute_dtype %d", cfg->compute_dtype);
-    if (gauss && !host_env)
-        return fail(nullptr, PPO_ERR_UNSUPPORTED, "dist_kind = PPO_DIST_GAUSSIAN serves caller-stepped environments (env_kind = PPO_ENV_HOST): CartPole, MountainCar and "
+    if (pendulum) {   // accepted in exactly one form (ppo_hip.h: PPO_ENV_PENDULUM); a wrong obs_size first, with the reference's message (below)
+        if (cfg->obs_size == 3) {
+            if (!gauss)
+                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_PENDULUM takes one real-valued action: it is built for dist_kind = PPO_DIST_GAUSSIAN; got "
+                            "dist_kind %d", cfg->dist_kind);
+            if (cfg->n_heads != 1 || cfg->head_dims[0] != 1)
+                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_PENDULUM has one action dimension, the torque: n_heads = 1 and head_dims[0] = 1; got "
+                            "n_heads = %d, head_dims[0] = %d", cfg->n_heads, cfg->head_dims[0]);
+            if (cfg->hidden != 64 || cfg->n_hidden != 2)
+                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_PENDULUM is built for the 2 x 64 network (hidden = 64, n_hidden = 2) of the fused Gaussian "
+                            "kernels; got %d x %d", cfg->n_hidden, cfg->hidden);
+            if (cfg->compute_dtype != PPO_DTYPE_F32)
+                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_PENDULUM is built for compute_dtype = PPO_DTYPE_F32; bf16 storage is not");
+            if (!(cfg->kernel_flags & PPO_KERNEL_GAUSS_FUSED))
+                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_PENDULUM needs PPO_KERNEL_GAUSS_FUSED in kernel_flags: its rollout exists on the fused Gaussian "
+                            "kernels only, and the flag is never implied (no other engine serves in its place)");
+            if (cfg->max_episode_steps < 1 || cfg->max_episode_steps > PENDULUM_MAX_EPISODE_STEPS)
+                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_PENDULUM is built for 1 <= max_episode_steps <= %d (the angle is not wrapped and the device "
+                            "sinf / cosf hold for |theta| < 120); got %d", PENDULUM_MAX_EPISODE_STEPS, cfg->max_episode_steps);
+        }
+    }
+    if (gauss && !host_env && !pendulum)
+        return fail(nullptr, PPO_ERR_UNSUPPORTED, "dist_kind = PPO_DIST_GAUSSIAN serves caller-stepped environments (env_kind = PPO_ENV_HOST) and PPO_ENV_PENDULUM: CartPole, MountainCar and "
                     "the synthetic env take discrete actions; got env_kind %d", cfg->env_kind);
     if (gauss && cfg->compute_dtype != PPO_DTYPE_F32)
         return fail(nullptr, PPO_ERR_UNSUPPORTED, "dist_kind = PPO_DIST_GAUSSIAN is built for compute_dtype = PPO_DTYPE_F32; bf16 storage is not");
@@ -574,7 +598,7 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
     if (cfg->compute_dtype == PPO_DTYPE_BF16 && !generic)
         return fail(nullptr, PPO_ERR_UNSUPPORTED, "compute_dtype = PPO_DTYPE_BF16 applies to networks whose layers are GEMMs (env_kind = PPO_ENV_SYNTHETIC); the reference's "
                     "2 x 64 networks always compute in f32");
-    const int env_obs = cfg->env_kind == PPO_ENV_CARTPOLE ? 4 : (cfg->env_kind == PPO_ENV_MOUNTAINCAR ? 2 : cfg->obs_size);   // host / synthetic: no check
+    const int env_obs = cfg->env_kind == PPO_ENV_CARTPOLE ? 4 : (cfg->env_kind == PPO_ENV_MOUNTAINCAR ? 2 : (pendulum ? 3 : cfg->obs_size));   // host / synthetic: no check
     if (cfg->obs_size != env_obs) {
         // the reference's runtime check in initEnvs (PPO_Discrete.cpp:370-375), same wording
         return fail(nullptr, PPO_ERR_INVALID,
@@ -1223,10 +1247,24 @@ static ppo_status host_env_refuses(ppo_ctx* c, const char* what) {
                                         "them with ppo_host_env_reset, ppo_host_rollout_begin, ppo_host_act, ppo_host_observe and ppo_host_rollout_end", what);
 }
 
+static inline bool is_pendulum(const ppo_ctx* c) { return c->cfg.env_kind == PPO_ENV_PENDULUM; }
+
+extern "C" ppo_status ppo_env_transition_f32(int32_t env_kind, const float* state_in, const float* action, int64_t n, float* next_state, float* obs_out,
+                                             float* reward, int32_t* terminated, void* stream) {
+    if (!state_in || !action || !next_state || !reward || !terminated || n < 0) return PPO_ERR_INVALID;
+    if (env_kind != PPO_ENV_PENDULUM) return PPO_ERR_UNSUPPORTED;   // the envs with integer actions: ppo_env_transition
+    return launch_pendulum_transition(state_in, action, n, next_state, obs_out, reward, terminated, (hipStream_t)stream) == hipSuccess ? PPO_OK : PPO_ERR_HIP;
+}
+
 extern "C" ppo_status ppo_env_reset(ppo_ctx* c) {
     NEED(c, c != nullptr, "null ctx");
     if (c->host_env) return host_env_refuses(c, "ppo_env_reset");
     DeviceGuard dev_guard(c);
+    if (is_pendulum(c)) {
+        HIPCHK(c, launch_pendulum_reset(c->N, c->cfg.seed, c->cfg.env_offset, B_<float>(c, PPO_BUF_ENV_STATE), B_<int32_t>(c, PPO_BUF_EP_LEN), B_<float>(c, PPO_BUF_EP_REW),
+                                        B_<int32_t>(c, PPO_BUF_RESET_COUNT), B_<float>(c, PPO_BUF_NEXT_OBS), B_<int32_t>(c, PPO_BUF_NEXT_DONE), c->stream));
+        return PPO_OK;
+    }
     if (c->gen) {   // synthetic env: memoryless, the observation of global step `rollout_steps` (0 after creation)
         HIPCHK(c, hipMemsetAsync(c->buf[PPO_BUF_EP_LEN], 0, (size_t)c->N * sizeof(int32_t), c->stream));
         HIPCHK(c, hipMemsetAsync(c->buf[PPO_BUF_EP_REW], 0, (size_t)c->N * sizeof(float), c->stream));
@@ -1244,6 +1282,7 @@ extern "C" ppo_status ppo_env_reset(ppo_ctx* c) {
 extern "C" ppo_status ppo_env_step(ppo_ctx* c, const int64_t* action, float* obs, float* reward, int32_t* done) {
     NEED(c, c && action && obs && reward && done, "null argument");
     if (c->host_env) return host_env_refuses(c, "ppo_env_step");
+    if (is_pendulum(c)) return fail(c, PPO_ERR_UNSUPPORTED, "ppo_env_step: this context's env (PPO_ENV_PENDULUM) takes real-valued actions f32 [N, D]; call ppo_env_step_f32");
     DeviceGuard dev_guard(c);
     if (c->gen) {   // synthetic env: one step at the context's global step counter (the action does not influence it)
         HIPCHK(c, gen_synthetic_step(c->gen->L, c->N, c->cfg.seed, c->cfg.env_offset, c->rollout_steps, c->cfg.max_episode_steps,
@@ -1257,14 +1296,30 @@ extern "C" ppo_status ppo_env_step(ppo_ctx* c, const int64_t* action, float* obs
     return PPO_OK;
 }
 
+extern "C" ppo_status ppo_env_step_f32(ppo_ctx* c, const float* action, float* obs, float* reward, int32_t* done) {
+    NEED(c, c && action && obs && reward && done, "null argument");
+    if (c->host_env) return host_env_refuses(c, "ppo_env_step_f32");
+    if (!is_pendulum(c))
+        return fail(c, PPO_ERR_UNSUPPORTED, "ppo_env_step_f32: this context's env (env_kind %d) takes integer actions i64 [N, H]; call ppo_env_step", c->cfg.env_kind);
+    DeviceGuard dev_guard(c);
+    HIPCHK(c, launch_pendulum_step(c->N, c->cfg.max_episode_steps, c->cfg.seed, c->cfg.env_offset, B_<float>(c, PPO_BUF_ENV_STATE), B_<int32_t>(c, PPO_BUF_EP_LEN),
+                                   B_<float>(c, PPO_BUF_EP_REW), B_<int32_t>(c, PPO_BUF_RESET_COUNT), action, obs, reward, done, c->stream));
+    return PPO_OK;
+}
+
+// the env state's width: the observation IS the state for CartPole and MountainCar; Pendulum keeps (theta, theta_dot) behind a 3-wide observation
+static inline int env_state_dim(const ppo_ctx* c) { return is_pendulum(c) ? 2 : c->O; }
+
 extern "C" ppo_status ppo_env_set_state_h(ppo_ctx* c, const float* state_h, const int32_t* ep_len_h, const float* ep_rew_h, const int32_t* reset_count_h) {
     NEED(c, c != nullptr, "null ctx");
     DeviceGuard dev_guard(c);
     if (state_h) {
-        ppo_status s = ppo_memcpy_h2d(c, c->scratch_obs, state_h, (size_t)c->N * c->O * sizeof(float));
+        const int S = env_state_dim(c);
+        ppo_status s = ppo_memcpy_h2d(c, c->scratch_obs, state_h, (size_t)c->N * S * sizeof(float));
         if (s != PPO_OK) return s;
-        HIPCHK(c, launch_aos_to_soa(c->scratch_obs, B_<float>(c, PPO_BUF_ENV_STATE), c->N, c->O, true, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->buf[PPO_BUF_NEXT_OBS], c->scratch_obs, (size_t)c->N * c->O * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, launch_aos_to_soa(c->scratch_obs, B_<float>(c, PPO_BUF_ENV_STATE), c->N, S, true, c->stream));
+        if (is_pendulum(c)) HIPCHK(c, launch_pendulum_obs(c->N, B_<float>(c, PPO_BUF_ENV_STATE), B_<float>(c, PPO_BUF_NEXT_OBS), c->stream));
+        else HIPCHK(c, hipMemcpyAsync(c->buf[PPO_BUF_NEXT_OBS], c->scratch_obs, (size_t)c->N * c->O * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     }
     ppo_status s = PPO_OK;
     if (ep_len_h) s = ppo_memcpy_h2d(c, c->buf[PPO_BUF_EP_LEN], ep_len_h, (size_t)c->N * sizeof(int32_t));
@@ -1279,8 +1334,9 @@ extern "C" ppo_status ppo_env_get_state_h(ppo_ctx* c, float* state_h, int32_t* e
     DeviceGuard dev_guard(c);
     ppo_status s = PPO_OK;
     if (state_h) {
-        HIPCHK(c, launch_aos_to_soa(c->scratch_obs, B_<float>(c, PPO_BUF_ENV_STATE), c->N, c->O, false, c->stream));
-        s = ppo_memcpy_d2h(c, state_h, c->scratch_obs, (size_t)c->N * c->O * sizeof(float));
+        const int S = env_state_dim(c);
+        HIPCHK(c, launch_aos_to_soa(c->scratch_obs, B_<float>(c, PPO_BUF_ENV_STATE), c->N, S, false, c->stream));
+        s = ppo_memcpy_d2h(c, state_h, c->scratch_obs, (size_t)c->N * S * sizeof(float));
     }
     if (s == PPO_OK && ep_len_h) s = ppo_memcpy_d2h(c, ep_len_h, c->buf[PPO_BUF_EP_LEN], (size_t)c->N * sizeof(int32_t));
     if (s == PPO_OK && ep_rew_h) s = ppo_memcpy_d2h(c, ep_rew_h, c->buf[PPO_BUF_EP_REW], (size_t)c->N * sizeof(float));
@@ -1366,9 +1422,57 @@ static ppo_status env_fold_truncations(ppo_ctx* c) {
     return PPO_OK;
 }
 
+// PPO_ENV_PENDULUM: gauss_rollout_kernel (all T steps), then gen_rollout's tail -- the critic over the stored observations and over NEXT_OBS: three launches
+static ppo_status pendulum_rollout(ppo_ctx* c, const float* forced) {
+    ppo_status s = consume_finished_episodes(c);
+    if (s != PPO_OK) return s;
+    GaussRolloutArgs r{};
+    r.params = B_<float>(c, PPO_BUF_PARAMS);
+    r.N = c->N; r.T = c->T; r.max_episode_steps = c->cfg.max_episode_steps;
+    r.seed = c->cfg.seed; r.env_offset = c->cfg.env_offset; r.step_base = c->rollout_steps;
+    r.env_state = B_<float>(c, PPO_BUF_ENV_STATE);
+    r.ep_len = B_<int32_t>(c, PPO_BUF_EP_LEN);
+    r.ep_rew = B_<float>(c, PPO_BUF_EP_REW);
+    r.reset_count = B_<int32_t>(c, PPO_BUF_RESET_COUNT);
+    r.obs = B_<float>(c, PPO_BUF_OBS);
+    r.actions = B_<float>(c, PPO_BUF_ACTIONS);
+    r.logprobs = B_<float>(c, PPO_BUF_LOGPROBS);
+    r.rewards = B_<float>(c, PPO_BUF_REWARDS);
+    r.dones = B_<float>(c, PPO_BUF_DONES);
+    r.fin_len = B_<int32_t>(c, PPO_BUF_FIN_LEN);
+    r.fin_rew = B_<float>(c, PPO_BUF_FIN_REW);
+    r.next_obs = B_<float>(c, PPO_BUF_NEXT_OBS);
+    r.next_done = B_<int32_t>(c, PPO_BUF_NEXT_DONE);
+    r.forced = forced;
+    {
+        ProfScope ps(c, PROF_ROLLOUT);
+        HIPCHK(c, gauss_fused_rollout(c->gen->L, r, c->stream));
+        s = gen_values(c, r.obs, (int64_t)c->T * c->N, B_<float>(c, PPO_BUF_VALUES));
+        if (s == PPO_OK) s = gen_values(c, r.next_obs, c->N, B_<float>(c, PPO_BUF_NEXT_VALUE));
+        if (s != PPO_OK) return s;
+    }
+    c->rollout_steps += c->T;
+    c->global_step += (int64_t)c->T * c->cfg.global_num_envs;
+    c->fin_pending = true;
+    return PPO_OK;
+}
+
+extern "C" ppo_status ppo_rollout_f32(ppo_ctx* c, const float* forced_actions) {
+    NEED(c, c != nullptr, "null ctx");
+    if (c->host_env) return host_env_refuses(c, "ppo_rollout_f32");
+    if (!is_gauss(c)) return wrong_action_type(c, "ppo_rollout_f32", "ppo_rollout");
+    DeviceGuard dev_guard(c);
+    return pendulum_rollout(c, forced_actions);   // a Gaussian context with a device env is a PPO_ENV_PENDULUM context (ppo_ctx_create)
+}
+
 extern "C" ppo_status ppo_rollout(ppo_ctx* c, const int64_t* forced_actions) {
     NEED(c, c != nullptr, "null ctx");
     if (c->host_env) return host_env_refuses(c, "ppo_rollout");
+    if (is_pendulum(c)) {
+        if (forced_actions) return wrong_action_type(c, "ppo_rollout with forced actions", "ppo_rollout_f32");
+        DeviceGuard dev_guard(c);
+        return pendulum_rollout(c, nullptr);
+    }
     DeviceGuard dev_guard(c);
     ppo_status s = consume_finished_episodes(c);
     if (s != PPO_OK) return s;
@@ -1466,6 +1570,9 @@ static ppo_status eval_scratch(ppo_ctx* c, int64_t n, int64_t seed) {
 
 extern "C" ppo_status ppo_evaluate(ppo_ctx* c, int64_t n_episodes, int64_t seed, int32_t greedy, float* ep_return, int32_t* ep_length, ppo_eval_stats* out_h) {
     NEED(c, c != nullptr, "null ctx");
+    if (is_pendulum(c))
+        return fail(c, PPO_ERR_UNSUPPORTED, "ppo_evaluate is not built for PPO_ENV_PENDULUM: step the episodes through ppo_policy_act_f32 with greedy = 1 and "
+                                            "ppo_env_transition_f32");
     if (c->host_env || c->gen || c->cfg.env_kind == PPO_ENV_SYNTHETIC)
         return fail(c, PPO_ERR_UNSUPPORTED, "ppo_evaluate steps the context's device environment (CartPole, MountainCar); this context's environment is %s: "
                                             "run the episodes on the host with one ppo_policy_act_greedy launch per step",
@@ -2807,6 +2914,9 @@ static ppo_status envt_state(ppo_ctx* c, const char* what) {
     if (c->host_env)
         return fail(c, PPO_ERR_UNSUPPORTED, "%s: this context's environments are the caller's (PPO_ENV_HOST), and only the caller holds the observation an episode "
                                             "ended on: pass it with ppo_host_observe_truncated (ppo_dev_observe for device arrays)", what);
+    if (is_pendulum(c))
+        return fail(c, PPO_ERR_UNSUPPORTED, "%s: the fold rebuilds the final observation of a cut-off episode from PPO_BUF_OBS, and a PPO_ENV_PENDULUM observation "
+                                            "(cos, sin, theta_dot) does not hold theta: not built for this env", what);
     if (c->cfg.env_kind != PPO_ENV_CARTPOLE && c->cfg.env_kind != PPO_ENV_MOUNTAINCAR)
         return fail(c, PPO_ERR_UNSUPPORTED, "%s: the synthetic env's observations are noise: an episode there has no last observation to bootstrap from", what);
     return PPO_OK;

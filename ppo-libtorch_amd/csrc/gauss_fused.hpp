@@ -22,3 +22,24 @@ hipError_t gauss_fused_values(const GenLayout& L, const float* params, const flo
 hipError_t gauss_fused_fwd_bwd(const GenLayout& L, const LossParams& hp, const float* params, const float* obs, const float* actions, const float* oldlp,
                                const float* adv, const float* ret, const float* oldv, const int32_t* idx, int64_t M, double inv_global_M, double global_M,
                                const AdvStat* adv_stat, float* slab, double* loss_part, float* grads, hipStream_t s);
+
+// PPO_ENV_PENDULUM: the T steps of a rollout in one launch (gauss_rollout_kernel: one workgroup per 64 envs, the actor's weights resident, the env in wave 0's
+// registers); the context's buffers, the teacher-forcing actions f32 [T, N, 1] or null.  The critic is not in it: two gauss_fused_values launches follow.
+struct GaussRolloutArgs {
+    const float* params;
+    int N, T, max_episode_steps;
+    int64_t seed, env_offset, step_base;
+    float* env_state; int32_t* ep_len; float* ep_rew; int32_t* reset_count;
+    float *obs, *actions, *logprobs, *rewards, *dones; int32_t* fin_len; float* fin_rew;
+    float* next_obs; int32_t* next_done;
+    const float* forced;
+};
+hipError_t gauss_fused_rollout(const GenLayout& L, const GaussRolloutArgs& r, hipStream_t s);
+// Pendulum's stand-alone env kernels, one thread per env, on the rollout kernel's device functions (ppo_internal.hpp: pendulum_step, pendulum_reset)
+hipError_t launch_pendulum_reset(int N, int64_t seed, int64_t env_offset, float* env_state, int32_t* ep_len, float* ep_rew, int32_t* reset_count, float* next_obs,
+                                 int32_t* next_done, hipStream_t s);
+hipError_t launch_pendulum_step(int N, int max_episode_steps, int64_t seed, int64_t env_offset, float* env_state, int32_t* ep_len, float* ep_rew,
+                                int32_t* reset_count, const float* action, float* obs, float* reward, int32_t* done, hipStream_t s);
+hipError_t launch_pendulum_transition(const float* state_in, const float* action, int64_t n, float* next_state, float* obs_out, float* reward, int32_t* terminated,
+                                      hipStream_t s);
+hipError_t launch_pendulum_obs(int N, const float* env_state, float* next_obs, hipStream_t s);

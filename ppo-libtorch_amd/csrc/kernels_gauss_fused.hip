@@ -11,6 +11,10 @@
 //   W1 64 obsP | W2 4096 | W3 64 outP | b1 64 | b2 64 | b3 32 | log_std 32 | exp(-log_std) 32 | row index 64 | X obsP 68 | H1 64 68 | H2 64 68 | OUT outP 68
 //   obs 64, D 32 (the largest shape served): 4096 + 4096 + 2048 + 288 + 4352 + 4352 + 4352 + 2176 = 25 760 floats = 103 040 bytes of 163 840.
 //   obs 17, D 6: 1280 + 4096 + 512 + 288 + 1360 + 4352 + 4352 + 544 = 16 784 floats = 67 136 bytes: two workgroups per CU.
+//   obs 3, D 1 (PPO_ENV_PENDULUM): 256 + 4096 + 256 + 288 + 272 + 4352 + 4352 + 272 = 14 144 floats = 56 576 bytes: two workgroups per CU.
+//
+// PPO_ENV_PENDULUM adds a fourth kernel on the same forward, gauss_rollout_kernel: the T steps of a rollout in one launch, the env in registers (below), and
+// the env's small stand-alone kernels.
 #include <algorithm>
 
 #include "generic.hpp"
@@ -510,6 +514,172 @@ __global__ __launch_bounds__(256) void gauss_slab_reduce_kernel(const float* __r
     grads[i] = acc;
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// gauss_rollout_kernel (PPO_ENV_PENDULUM): the T steps of a rollout as ONE launch.  A workgroup owns one tile of 64 envs for the whole rollout; the actor's
+// weights are staged once.  Lanes 0 .. 63 of wave 0 keep their env (state, episode sums, reset count, previous done flag, the current observation) in
+// registers and do, per step, what gauss_act_kernel's wave 0 does behind the same forward -- the same draw, sample and log-prob expressions, so a stepwise
+// loop of ppo_policy_act_f32 + ppo_env_step_f32 reproduces every stored bit -- then the env step (pendulum_step_episode).  Waves 1 .. 3 store the step's
+// observation and done flag from LDS meanwhile (the done flag rides in the row-index words, which this kernel does not need as indices).
+// Barriers per step: gf_forward_tile's four and one behind the stores (X and the done words are rewritten for the next step); every thread runs every
+// barrier, a short tile masks its stores only.  No workgroup talks to another.  LDS: gf_lds_floats(4, 4) = 14 144 floats = 56 576 bytes, two workgroups per CU.
+// ---------------------------------------------------------------------------------------------------------
+struct GfRolloutArgs {
+    GfShape sh;
+    const float* params;
+    int N, T, max_episode_steps;
+    int64_t seed, env_offset, step_base;
+    float* env_state;        // [2, N]
+    int32_t* ep_len;
+    float* ep_rew;
+    int32_t* reset_count;
+    float* obs;              // [T, N, 3]
+    float* actions;          // [T, N, 1]
+    float* logprobs;
+    float* rewards;
+    float* dones;
+    int32_t* fin_len;
+    float* fin_rew;
+    float* next_obs;         // [N, 3]
+    int32_t* next_done;
+    const float* forced;     // [T, N, 1] or null
+};
+
+__global__ __launch_bounds__(GF_THREADS) void gauss_rollout_kernel(GfRolloutArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float gf_lds[];
+    const int tid = threadIdx.x, N = a.N;
+    const GfLds m = gf_carve(gf_lds, 4, 4);
+    gf_stage_weights(m, a.sh, a.params, 1, tid);
+    const int row0 = blockIdx.x * 64;
+    const int env = row0 + (tid & 63);
+    const bool owner = tid < 64 && env < N;
+    const int64_t env_global = a.env_offset + env;
+    float st[2] = { 0.0f, 0.0f }, ob[3] = { 0.0f, 0.0f, 0.0f }, ep_rew = 0.0f;
+    int ep_len = 0, resets = 0, done = 0;
+    if (owner) {
+        st[0] = a.env_state[env];
+        st[1] = a.env_state[(size_t)N + env];
+        ep_len = a.ep_len[env];
+        ep_rew = a.ep_rew[env];
+        resets = a.reset_count[env];
+        done = a.next_done[env];
+        pendulum_obs(st, ob);
+    }
+    if (tid < 64) m.x[3 * GF_S + tid] = 0.0f;   // the padding row of the observation image, once
+    const int rows = N - row0 < 64 ? N - row0 : 64;
+    for (int t = 0; t < a.T; t++) {
+        const size_t tn = (size_t)t * N;
+        if (tid < 64) {
+            m.x[0 * GF_S + tid] = ob[0];
+            m.x[1 * GF_S + tid] = ob[1];
+            m.x[2 * GF_S + tid] = ob[2];
+            m.ridx[tid] = done;
+        }
+        gf_forward_tile(m, 1, tid);
+        if (tid < 64) {
+            if (owner) {
+                const float mu = m.o[tid], ls = m.ls[0];
+                float eps[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
+                if (!a.forced) gauss_eps4(a.seed, env_global, a.step_base + t, 0, eps);
+                const float act = a.forced ? a.forced[tn + env] : gauss_sample(mu, ls, eps[0]);
+                double lp = 0.0;
+                lp += gauss_logp(gauss_z(act, mu, expf(-ls)), ls);
+                int fin_len;
+                float fin_rew;
+                const float r = pendulum_step_episode(st, act, a.max_episode_steps, a.seed, env_global, ep_len, ep_rew, resets, done, fin_len, fin_rew);
+                pendulum_obs(st, ob);
+                a.actions[tn + env] = act;
+                a.logprobs[tn + env] = (float)lp;
+                a.rewards[tn + env] = r;
+                a.fin_len[tn + env] = fin_len;
+                a.fin_rew[tn + env] = fin_rew;
+            }
+        } else {   // waves 1 .. 3: the step's observation rows and done flags, out of LDS
+            float* obs_t = a.obs + (tn + row0) * 3;
+            for (int i = tid - 64; i < rows * 3; i += GF_THREADS - 64) {
+                const int s = i / 3, k = i - 3 * s;
+                obs_t[i] = m.x[k * GF_S + s];
+            }
+            if (tid < 128 && env < N) a.dones[tn + env] = (float)m.ridx[tid & 63];
+        }
+        __syncthreads();   // X and the done words are read: wave 0 may write the next step's
+    }
+    if (owner) {
+        a.next_obs[(size_t)env * 3 + 0] = ob[0];
+        a.next_obs[(size_t)env * 3 + 1] = ob[1];
+        a.next_obs[(size_t)env * 3 + 2] = ob[2];
+        a.next_done[env] = done;
+        a.env_state[env] = st[0];
+        a.env_state[(size_t)N + env] = st[1];
+        a.ep_len[env] = ep_len;
+        a.ep_rew[env] = ep_rew;
+        a.reset_count[env] = resets;
+    }
+}
+
+// ---- Pendulum's stand-alone env kernels: one thread per env, on the device functions the rollout kernel uses (ppo_internal.hpp) ----
+// ppo_env_reset: env_reset_kernel's bookkeeping (global env 0 takes reset 1: initEnvs probes it once before it resets everybody)
+__global__ void pendulum_reset_kernel(int N, int64_t seed, int64_t env_offset, float* env_state, int32_t* ep_len, float* ep_rew, int32_t* reset_count,
+                                      float* next_obs, int32_t* next_done) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    const int k = (env_offset + i == 0) ? 1 : 0;
+    float st[2], ob[3];
+    pendulum_reset(st, k, seed, env_offset + i);
+    pendulum_obs(st, ob);
+    env_state[i] = st[0];
+    env_state[(size_t)N + i] = st[1];
+    for (int j = 0; j < 3; j++) next_obs[(size_t)i * 3 + j] = ob[j];
+    ep_len[i] = 0;
+    ep_rew[i] = 0.0f;
+    reset_count[i] = k + 1;
+    next_done[i] = 0;
+}
+// ppo_env_step_f32: action f32 [N, 1]
+__global__ void pendulum_step_kernel(int N, int max_episode_steps, int64_t seed, int64_t env_offset, float* env_state, int32_t* ep_len, float* ep_rew,
+                                     int32_t* reset_count, const float* __restrict__ action, float* obs, float* reward, int32_t* done) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    float st[2] = { env_state[i], env_state[(size_t)N + i] }, ob[3];
+    int len = ep_len[i], resets = reset_count[i], d, fin_len;
+    float rew = ep_rew[i], fin_rew;
+    const float r = pendulum_step_episode(st, action[i], max_episode_steps, seed, env_offset + i, len, rew, resets, d, fin_len, fin_rew);
+    pendulum_obs(st, ob);
+    env_state[i] = st[0];
+    env_state[(size_t)N + i] = st[1];
+    ep_len[i] = len;
+    ep_rew[i] = rew;
+    reset_count[i] = resets;
+    for (int j = 0; j < 3; j++) obs[(size_t)i * 3 + j] = ob[j];
+    reward[i] = r;
+    done[i] = d;
+}
+// ppo_env_transition_f32: stateless; state [n, 2], action [n, 1], obs_out [n, 3] or null
+__global__ void pendulum_transition_kernel(const float* __restrict__ state_in, const float* __restrict__ action, int64_t n, float* next_state, float* obs_out,
+                                           float* reward, int32_t* terminated) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float st[2] = { state_in[i * 2], state_in[i * 2 + 1] };
+    const float r = pendulum_step(st, action[i]);
+    next_state[i * 2] = st[0];
+    next_state[i * 2 + 1] = st[1];
+    if (obs_out) {
+        float ob[3];
+        pendulum_obs(st, ob);
+        for (int j = 0; j < 3; j++) obs_out[i * 3 + j] = ob[j];
+    }
+    reward[i] = r;
+    terminated[i] = 0;
+}
+// ppo_env_set_state_h: NEXT_OBS from the injected states
+__global__ void pendulum_obs_kernel(int N, const float* __restrict__ env_state, float* next_obs) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    const float st[2] = { env_state[i], env_state[(size_t)N + i] };
+    float ob[3];
+    pendulum_obs(st, ob);
+    for (int j = 0; j < 3; j++) next_obs[(size_t)i * 3 + j] = ob[j];
+}
+
 template <typename K>
 hipError_t gf_allow(std::atomic<unsigned long long>& done, K kernel, int bytes) {
     return bytes > 64 * 1024 ? allow_dynamic_lds(done, reinterpret_cast<const void*>(kernel)) : hipSuccess;
@@ -577,5 +747,51 @@ hipError_t gauss_fused_fwd_bwd(const GenLayout& L, const LossParams& hp, const f
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(gauss_fwd_bwd_kernel, dim3(a.nb, 2), dim3(GF_THREADS), bytes, s, a);
     hipLaunchKernelGGL(gauss_slab_reduce_kernel, dim3((L.P + 255) / 256), dim3(256), 0, s, slab, a.slab_stride, a.nb, L.net_off[1], L.P, grads);
+    return hipGetLastError();
+}
+
+// ---- PPO_ENV_PENDULUM (the context's shape is fixed by ppo_ctx_create: obs 3, D 1) ----
+hipError_t gauss_fused_rollout(const GenLayout& L, const GaussRolloutArgs& r, hipStream_t s) {
+    if (r.N <= 0 || r.T <= 0) return hipSuccess;
+    if (L.obs != 3 || L.gauss != 1) return hipErrorInvalidValue;
+    GfRolloutArgs a{};
+    a.sh = gf_shape(L);
+    a.params = r.params;
+    a.N = r.N; a.T = r.T; a.max_episode_steps = r.max_episode_steps;
+    a.seed = r.seed; a.env_offset = r.env_offset; a.step_base = r.step_base;
+    a.env_state = r.env_state; a.ep_len = r.ep_len; a.ep_rew = r.ep_rew; a.reset_count = r.reset_count;
+    a.obs = r.obs; a.actions = r.actions; a.logprobs = r.logprobs; a.rewards = r.rewards; a.dones = r.dones; a.fin_len = r.fin_len; a.fin_rew = r.fin_rew;
+    a.next_obs = r.next_obs; a.next_done = r.next_done; a.forced = r.forced;
+    const int bytes = gf_lds_floats(4, 4) * 4;
+    static std::atomic<unsigned long long> done{ 0 };
+    const hipError_t e = gf_allow(done, gauss_rollout_kernel, bytes);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(gauss_rollout_kernel, dim3((unsigned)((r.N + 63) / 64)), dim3(GF_THREADS), bytes, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_pendulum_reset(int N, int64_t seed, int64_t env_offset, float* env_state, int32_t* ep_len, float* ep_rew, int32_t* reset_count, float* next_obs,
+                                 int32_t* next_done, hipStream_t s) {
+    if (N <= 0) return hipSuccess;
+    hipLaunchKernelGGL(pendulum_reset_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, seed, env_offset, env_state, ep_len, ep_rew, reset_count, next_obs, next_done);
+    return hipGetLastError();
+}
+hipError_t launch_pendulum_step(int N, int max_episode_steps, int64_t seed, int64_t env_offset, float* env_state, int32_t* ep_len, float* ep_rew,
+                                int32_t* reset_count, const float* action, float* obs, float* reward, int32_t* done, hipStream_t s) {
+    if (N <= 0) return hipSuccess;
+    hipLaunchKernelGGL(pendulum_step_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, max_episode_steps, seed, env_offset, env_state, ep_len, ep_rew, reset_count,
+                       action, obs, reward, done);
+    return hipGetLastError();
+}
+hipError_t launch_pendulum_transition(const float* state_in, const float* action, int64_t n, float* next_state, float* obs_out, float* reward, int32_t* terminated,
+                                      hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    if (n >= (1ll << 31) * 256) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(pendulum_transition_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, state_in, action, n, next_state, obs_out, reward, terminated);
+    return hipGetLastError();
+}
+hipError_t launch_pendulum_obs(int N, const float* env_state, float* next_obs, hipStream_t s) {
+    if (N <= 0) return hipSuccess;
+    hipLaunchKernelGGL(pendulum_obs_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, env_state, next_obs);
     return hipGetLastError();
 }

@@ -239,6 +239,61 @@ __device__ __forceinline__ float mountaincar_step(float* st, int action, int& te
     return mountaincar_tail(st, action, glibc_cosf(3.0f * st[0]), terminated);
 }
 
+// Pendulum-v1 (gymnasium's classic_control/pendulum.py; no reference counterpart: PPO_ENV_PENDULUM).  st = {theta, theta_dot}; a = the RAW action, clipped
+// here to the torque range (the rollout keeps the raw sample).  Every operation rounds on its own (-ffp-contract=off), in exactly this association:
+//   u      = min(max(a, -2), 2)
+//   x      = theta + PI_F;  thn = (x - TWO_PI_F * floorf(x / TWO_PI_F)) - PI_F                    (gym's angle_normalize)
+//   reward = -((thn * thn + 0.1f * (theta_dot * theta_dot)) + 0.001f * (u * u))
+//   td'    = theta_dot + (15.0f * glibc_sinf(theta) + 3.0f * u) * 0.05f;  td' = min(max(td', -8), 8)    (3 g / (2 l) = 15, 3 / (m l^2) = 3, dt = 0.05)
+//   th'    = theta + td' * 0.05f                                                                   (not wrapped, as in gym)
+// The env never terminates; an episode ends at the time limit only.  |theta| grows by at most 8 * 0.05 a step, and glibc_sinf / glibc_cosf hold for
+// |x| < 120: ppo_ctx_create bounds max_episode_steps accordingly (PENDULUM_MAX_EPISODE_STEPS).
+constexpr float PEND_PI_F = 3.14159265358979323846f, PEND_TWO_PI_F = 6.28318530717958647692f;
+constexpr int PENDULUM_MAX_EPISODE_STEPS = 290;   // pi + 290 * 0.4 = 119.14 < 120
+__device__ __forceinline__ float pendulum_step(float* st, float a) {
+    const float theta = st[0], theta_dot = st[1];
+    const float u = a < -2.0f ? -2.0f : (a > 2.0f ? 2.0f : a);
+    const float x = theta + PEND_PI_F;
+    const float thn = (x - PEND_TWO_PI_F * floorf(x / PEND_TWO_PI_F)) - PEND_PI_F;
+    const float reward = -((thn * thn + 0.1f * (theta_dot * theta_dot)) + 0.001f * (u * u));
+    float td = theta_dot + (15.0f * glibc_sinf(theta) + 3.0f * u) * 0.05f;
+    td = td < -8.0f ? -8.0f : (td > 8.0f ? 8.0f : td);
+    st[0] = theta + td * 0.05f;
+    st[1] = td;
+    return reward;
+}
+// the observation of a state: (cos theta, sin theta, theta_dot)
+__device__ __forceinline__ void pendulum_obs(const float* st, float* obs) {
+    obs[0] = glibc_cosf(st[0]);
+    obs[1] = glibc_sinf(st[0]);
+    obs[2] = st[1];
+}
+// reset number k of global env e: MountainCar's keying, philox(seed; e, k, 0, 1); theta ~ U(-pi, pi) from word x, theta_dot ~ U(-1, 1) from word y
+__device__ __forceinline__ void pendulum_reset(float* st, int k, int64_t seed, int64_t env_global) {
+    const uint4 w = philox4x32_10((uint32_t)seed, (uint32_t)((uint64_t)seed >> 32), (uint32_t)env_global, (uint32_t)k, 0u, 1u);
+    st[0] = canon_to_uniform(w.x, -PEND_PI_F, PEND_PI_F);
+    st[1] = canon_to_uniform(w.y, -1.0f, 1.0f);
+}
+// One step of a Pendulum env with its bookkeeping (env_step_kernel's: episode sums, the time limit, the finished episode's numbers, auto-reset): ONE
+// definition for the fused rollout and the stand-alone step.  Returns the reward; done / fin_len / fin_rew are the step's.
+__device__ __forceinline__ float pendulum_step_episode(float* st, float a, int max_episode_steps, int64_t seed, int64_t env_global, int& ep_len, float& ep_rew,
+                                                       int& resets, int& done, int& fin_len, float& fin_rew) {
+    const float r = pendulum_step(st, a);
+    ep_len += 1;
+    ep_rew += r;
+    done = ep_len == max_episode_steps ? 1 : 0;
+    fin_len = 0;
+    fin_rew = 0.0f;
+    if (done) {
+        fin_len = ep_len;
+        fin_rew = ep_rew;
+        pendulum_reset(st, resets++, seed, env_global);
+        ep_len = 0;
+        ep_rew = 0.0f;
+    }
+    return r;
+}
+
 template <int ENV>
 __device__ __forceinline__ float env_step(float* st, int action, int& terminated) {
     if constexpr (ENV == PPO_ENV_CARTPOLE) return cartpole_step(st, action, terminated);
