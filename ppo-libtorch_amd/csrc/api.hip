@@ -201,7 +201,7 @@ struct ppo_ctx {
     unsigned long long* stamps = nullptr;  // [2][12] phase cycles of the diagnostic kernel variant
     // caller-stepped envs (PPO_ENV_HOST: ppo_host_*).  The staging block is pinned host memory the GPU can read: ppo_host_observe copies the caller's step
     // outputs into it (no launch), the next launch commits them reading the block in place (measured faster than one async copy of it ahead of every
-    // launch at N = 256 .. 16384: DESIGN.md section 6a).  Layout: [obs N*O f32 | reward N f32 | done N i32 | fin_len N i32 | fin_rew N f32 | mask N*A u8]
+    // launch at N = 256 .. 16384: DESIGN.md section 6a).  Layout (host_stage_layout): [obs N*O f32 | reward N f32 | done N i32 | fin_len N i32 | fin_rew N f32 | mask N*A u8]
     bool host_env = false;
     int host_phase = 0;               // 0: no rollout open, 1: ppo_host_act is next, 2: ppo_host_observe is next
     int host_t = 0;                   // steps acted on in the open rollout
@@ -542,6 +542,16 @@ extern "C" void ppo_ctx_destroy(ppo_ctx* c) {
     delete c;
 }
 
+// The pinned staging block of caller-stepped envs (ppo_ctx::host_stage): the byte offset of each area and the block's size, written down here only
+struct HostStage { size_t obs, rew, done, fin_len, fin_rew, mask, bytes; };
+static HostStage host_stage_layout(size_t N, size_t O, size_t A) {
+    HostStage l{};   // obs f32 [N,O] at 0, then four 4-byte [N] columns, then the mask u8 [N,A]
+    l.rew = l.obs + N * O * 4; l.done = l.rew + N * 4; l.fin_len = l.done + N * 4; l.fin_rew = l.fin_len + N * 4; l.mask = l.fin_rew + N * 4;
+    l.bytes = (l.mask + N * A + 15) / 16 * 16;
+    return l;
+}
+static HostStage host_stage_layout(const ppo_ctx* c) { return host_stage_layout((size_t)c->N, (size_t)c->O, (size_t)c->A); }
+
 extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
     if (!cfg || !out) return fail(nullptr, PPO_ERR_INVALID, "null argument");
     *out = nullptr;
@@ -743,7 +753,7 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
     CK(dalloc(c, &c->stamps, 24));
     if (host_env) {
         c->host_env = true;
-        c->host_stage_bytes = ((size_t)N * c->O * 4 + 4 * N * 4 + N * (size_t)A + 15) / 16 * 16;
+        c->host_stage_bytes = host_stage_layout(c).bytes;
         CK(hipHostMalloc(reinterpret_cast<void**>(&c->host_stage), c->host_stage_bytes, hipHostMallocMapped));
         CK(hipHostGetDevicePointer(reinterpret_cast<void**>(&c->host_stage_dev), c->host_stage, 0));
         std::memset(c->host_stage, 0, c->host_stage_bytes);
@@ -2307,8 +2317,9 @@ extern "C" ppo_status ppo_train_iteration(ppo_ctx* c) {
 
 // ---------------------------------------------------------------------------------------------------------
 // Caller-stepped environments (PPO_ENV_HOST): the rollout of PPO_Discrete::train (:524-548) with the caller's envs stepped between the launches.
-// One launch per env step: ppo_host_act commits what ppo_host_observe staged for step t - 1 and acts on step t (launch_host_act); the host waits for
-// that launch only, to read the actions.  ppo_host_rollout_end commits step T - 1 and runs the rest of ppo_train_iteration.
+// One step path (act_slice / act_slice_f32) with three feeds: the host feed (ppo_host_act commits what ppo_host_observe staged for step t - 1 and acts on
+// step t in one launch; the host waits for that launch only, to read the actions), env groups (the same, a group's rows at a time) and the device feed
+// (ppo_dev_*).  ppo_host_rollout_end commits step T - 1 and runs the rest of ppo_train_iteration.
 // ---------------------------------------------------------------------------------------------------------
 static ppo_status host_state(ppo_ctx* c, const char* what) {
     if (!c->host_env)
@@ -2319,15 +2330,16 @@ static ppo_status host_state(ppo_ctx* c, const char* what) {
 
 // the staged step and the rollout rows it lands in; t = the step about to be acted on (T at the end of the rollout)
 // row0 (env groups): every pointer names row row0 of its array, so that a launch over the group's n_g rows indexes them 0 .. n_g - 1
-static HostStepArgs host_args_rows(ppo_ctx* c, int t, bool act_stores, size_t row0, bool staged, bool fin_given) {
+static HostStepArgs host_args(ppo_ctx* c, int t, bool act_stores, size_t row0, bool staged, bool fin_given) {
     const size_t N = (size_t)c->N;
     const unsigned char* st = c->host_stage_dev;
+    const HostStage l = host_stage_layout(c);
     HostStepArgs h{};
-    h.st_obs = reinterpret_cast<const float*>(st) + row0 * c->O;
-    h.st_rew = reinterpret_cast<const float*>(st + N * c->O * 4) + row0;
-    h.st_done = reinterpret_cast<const int32_t*>(st + N * c->O * 4 + N * 4) + row0;
-    h.st_fin_len = reinterpret_cast<const int32_t*>(st + N * c->O * 4 + 2 * N * 4) + row0;
-    h.st_fin_rew = reinterpret_cast<const float*>(st + N * c->O * 4 + 3 * N * 4) + row0;
+    h.st_obs = reinterpret_cast<const float*>(st + l.obs) + row0 * c->O;
+    h.st_rew = reinterpret_cast<const float*>(st + l.rew) + row0;
+    h.st_done = reinterpret_cast<const int32_t*>(st + l.done) + row0;
+    h.st_fin_len = reinterpret_cast<const int32_t*>(st + l.fin_len) + row0;
+    h.st_fin_rew = reinterpret_cast<const float*>(st + l.fin_rew) + row0;
     h.commit = staged ? 1 : 0;
     h.fin_given = fin_given ? 1 : 0;
     const size_t prev = (t > 0 ? (size_t)(t - 1) * N : 0) + row0;
@@ -2347,10 +2359,26 @@ static HostStepArgs host_args_rows(ppo_ctx* c, int t, bool act_stores, size_t ro
     }
     return h;
 }
-static HostStepArgs host_args(ppo_ctx* c, int t, bool act_stores) { return host_args_rows(c, t, act_stores, 0, c->host_staged, c->host_fin_given); }
-static const uint8_t* host_stage_mask(ppo_ctx* c) {
-    const size_t N = (size_t)c->N;
-    return c->host_stage_dev + N * c->O * 4 + 4 * N * 4;
+// stepEnvs' outputs (:413-483) for env rows row0 .. row0 + rows, copied into the staging block for the next launch (host memory only: no launch)
+static void stage_rows(ppo_ctx* c, size_t row0, size_t rows, const float* next_obs_h, const float* reward_h, const int32_t* done_h, const int32_t* fin_len_h,
+                       const float* fin_rew_h) {
+    const HostStage l = host_stage_layout(c);
+    unsigned char* st = c->host_stage;
+    std::memcpy(st + l.obs + row0 * c->O * 4, next_obs_h, rows * c->O * 4);
+    std::memcpy(st + l.rew + row0 * 4, reward_h, rows * 4);
+    std::memcpy(st + l.done + row0 * 4, done_h, rows * 4);
+    if (fin_len_h) {
+        std::memcpy(st + l.fin_len + row0 * 4, fin_len_h, rows * 4);
+        std::memcpy(st + l.fin_rew + row0 * 4, fin_rew_h, rows * 4);
+    }
+}
+// a host feed's mask rows for the step about to be acted on, copied into the staging block; returns the device's address of the copy, or null when the
+// policy is not masked or the caller passed none
+static const uint8_t* stage_mask(ppo_ctx* c, size_t row0, size_t rows, const uint8_t* mask_h) {
+    if (c->cfg.dist_kind != PPO_DIST_MASKED || mask_h == nullptr) return nullptr;
+    const size_t at = host_stage_layout(c).mask + row0 * c->A;
+    std::memcpy(c->host_stage + at, mask_h, rows * c->A);
+    return c->host_stage_dev + at;
 }
 
 // ---- observation normalisation (ppo_obs_norm_*; kernels_obsnorm.hip).  Every batch of new observations -- the reset observations, then each step's
@@ -2418,9 +2446,74 @@ static ppo_status rn_batch(ppo_ctx* c, HostStepArgs& h) {
     h.st_rew_store = c->rn_rew;
     return PPO_OK;
 }
-// the resets start every env's episode anew: the accumulators go to zero, the statistics stay
-static ppo_status rn_reset_returns(ppo_ctx* c) {
+// Both resets start every env's episode anew: NEXT_DONE = 0, the per-env episode sums = 0, the return accumulators = 0 (reward normalisation: the statistics stay)
+static ppo_status reset_episode_state(ppo_ctx* c) {
+    HIPCHK(c, hipMemsetAsync(c->buf[PPO_BUF_NEXT_DONE], 0, (size_t)c->N * sizeof(int32_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->buf[PPO_BUF_EP_LEN], 0, (size_t)c->N * sizeof(int32_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->buf[PPO_BUF_EP_REW], 0, (size_t)c->N * sizeof(float), c->stream));
     if (c->rn_ret) HIPCHK(c, hipMemsetAsync(c->rn_ret, 0, (size_t)c->N * sizeof(double), c->stream));
+    return PPO_OK;
+}
+
+// ---- the step, enqueued once for every feed.  A slice is rows row0 .. row0 + rows of step t: the whole batch for ppo_host_act* and ppo_dev_act*, a group's
+// rows for ppo_host_group_act.  commit / fin_given: the slice's step t - 1 is staged and not committed yet (never in a device-fed act: ppo_dev_observe
+// committed it).  Step t of :524-548: the normalisers over the staged step, its commit, m_obs[t], m_dones[t], the actor forward + sample, m_actions[t],
+// m_logprobs[t] (and masks [t]).  action_dev: a device-fed caller's own array; null for a host feed, whose actions go to rows row0 .. of the pinned block.
+// The entry points keep their checks, the caller's wait and the state behind the enqueue.
+struct StepSlice { int t; size_t row0; int rows; bool commit, fin_given; };
+static ppo_status act_slice(ppo_ctx* c, const StepSlice& sl, const uint8_t* mask, int64_t* action_dev) {
+    const int N = c->N, n = sl.rows;
+    const size_t b = sl.row0, tn = (size_t)sl.t * N + b;
+    HostStepArgs h = host_args(c, sl.t, true, b, sl.commit, sl.fin_given);
+    // on_staged / rn_batch work on all N rows; groups refuse both normalisers (ppo_host_rollout_begin_groups), so a normaliser implies the whole batch
+    NEED(c, (c->on_mode == 0 && c->rn_mode == 0) || (b == 0 && n == N), "a normaliser is on and the step is not the whole batch");
+    ppo_status s = on_staged(c, h);   // observation normalisation: one more launch, in front of the commit
+    if (s != PPO_OK) return s;
+    s = rn_batch(c, h);               // reward normalisation: likewise
+    if (s != PPO_OK) return s;
+    const int64_t step = c->rollout_steps + sl.t;
+    float* logprob_t = B_<float>(c, PPO_BUF_LOGPROBS) + tn;
+    if (!c->gen) {   // commit + act in one launch; env_offset + row0 is the sampler's row origin
+        HIPCHK(c, launch_host_act(B_<float>(c, PPO_BUF_PARAMS), c->L, c->cfg.dist_kind, mask, n, c->cfg.seed, c->cfg.env_offset + (int64_t)b, step, h,
+                                  action_dev ? action_dev : c->host_act_dev + b * c->H, logprob_t, c->host_as16, c->error_flag, c->stream));
+        return PPO_OK;
+    }
+    // generic engine: the commit in place of gen_synthetic_step, then gen_rollout's per-step sequence on the committed observation
+    GenericCtx& g = *c->gen;
+    int64_t* act64 = action_dev ? action_dev : g.act64 + b * c->H;
+    if (h.commit) HIPCHK(c, launch_host_commit(h, n, c->O, c->stream));
+    // key_rows = N for every slice.  For a group that is what it always passed.  For the whole batch (n = N, where the callers used to pass 0) it picks
+    // the same launch: rows_max = max(MB, N) rounded up to 128 >= N, so the loop in gen_policy is one chunk of rows = N, and its test reads
+    // min(rows_max, N) = N <= GEN_FUSED_MAX_ROWS with key_rows = N and rows = N <= GEN_FUSED_MAX_ROWS with key_rows = 0.
+    s = gen_policy(c, h.next_obs, mask, nullptr, n, step, act64, g.step_lp + b, g.step_en + b, false, (int64_t)b, N);
+    if (s != PPO_OK) return s;
+    HIPCHK(c, gen_store_step(g.L, n, h.next_obs, mask, act64, g.step_lp + b, h.next_done, h.obs_t, B_<uint8_t>(c, PPO_BUF_MASKS) + tn * c->A, h.actions_t,
+                             logprob_t, h.dones_t, c->stream));
+    if (!action_dev) HIPCHK(c, hipMemcpyAsync(c->host_act + b * c->H, act64, (size_t)n * c->H * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    return PPO_OK;
+}
+
+// act_slice for a Gaussian context (always the generic engine): the mean in the place of the logits and f32 actions [N,D].  gen_policy_gauss takes no row
+// origin and groups refuse Gaussian contexts, so the slice is the whole batch.  action_dev null: the engine's scratch, then one copy into the pinned block.
+static ppo_status act_slice_f32(ppo_ctx* c, const StepSlice& sl, float* action_dev) {
+    GenericCtx& g = *c->gen;
+    const int N = c->N, D = g.L.gauss;
+    NEED(c, sl.row0 == 0 && sl.rows == N, "a Gaussian step is not the whole batch");
+    HostStepArgs h = host_args(c, sl.t, true, 0, sl.commit, sl.fin_given);
+    ppo_status s = on_staged(c, h);
+    if (s != PPO_OK) return s;
+    s = rn_batch(c, h);
+    if (s != PPO_OK) return s;
+    if (h.commit) HIPCHK(c, launch_host_commit(h, N, c->O, c->stream));
+    float* act = action_dev ? action_dev : g.actf;
+    const size_t tn = (size_t)sl.t * N;
+    const GaussStepStores stores{ h.next_done, h.obs_t, B_<float>(c, PPO_BUF_ACTIONS) + tn * D, B_<float>(c, PPO_BUF_LOGPROBS) + tn, h.dones_t };
+    bool stored = false;
+    s = gen_policy_gauss(c, h.next_obs, nullptr, N, c->rollout_steps + sl.t, act, g.step_lp, g.step_en, false, &stores, &stored);
+    if (s != PPO_OK) return s;
+    if (!stored)
+        HIPCHK(c, gen_gauss_store_step(g.L, N, h.next_obs, act, g.step_lp, stores.done_prev, stores.obs_t, stores.act_t, stores.lp_t, stores.dones_t, c->stream));
+    if (!action_dev) HIPCHK(c, hipMemcpyAsync(c->host_act, act, (size_t)N * D * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     return PPO_OK;
 }
 
@@ -2432,12 +2525,9 @@ extern "C" ppo_status ppo_host_env_reset(ppo_ctx* c, const float* obs_h) {
     if (c->host_phase != 0) return fail(c, PPO_ERR_STATE, "ppo_host_env_reset: a rollout is open (ppo_host_rollout_end first)");
     NEED(c, obs_h != nullptr, "null argument");
     DeviceGuard dev_guard(c);
-    HIPCHK(c, hipMemsetAsync(c->buf[PPO_BUF_NEXT_DONE], 0, (size_t)c->N * sizeof(int32_t), c->stream));
-    HIPCHK(c, hipMemsetAsync(c->buf[PPO_BUF_EP_LEN], 0, (size_t)c->N * sizeof(int32_t), c->stream));
-    HIPCHK(c, hipMemsetAsync(c->buf[PPO_BUF_EP_REW], 0, (size_t)c->N * sizeof(float), c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->buf[PPO_BUF_NEXT_OBS], obs_h, (size_t)c->N * c->O * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    s = rn_reset_returns(c);
+    s = reset_episode_state(c);
     if (s != PPO_OK) return s;
+    HIPCHK(c, hipMemcpyAsync(c->buf[PPO_BUF_NEXT_OBS], obs_h, (size_t)c->N * c->O * sizeof(float), hipMemcpyHostToDevice, c->stream));
     if (c->on_mode != 0) {
         s = on_batch(c, B_<float>(c, PPO_BUF_NEXT_OBS), B_<float>(c, PPO_BUF_NEXT_OBS), c->N);
         if (s != PPO_OK) return s;
@@ -2481,8 +2571,18 @@ extern "C" ppo_status ppo_host_rollout_begin(ppo_ctx* c) {
     return host_begin(c);
 }
 
-// Step t of :524-548: commit step t - 1, then m_obs[t], m_dones[t], the actor forward + sample, m_actions[t], m_logprobs[t] (and masks [t]); returns
-// when action_h holds the actions
+// how a host-fed act ends: the one wait of a step, the actions into the caller's array, and the state behind the enqueue
+static ppo_status host_acted(ppo_ctx* c, void* action_h, size_t bytes) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::memcpy(action_h, c->host_act, bytes);
+    c->host_staged = false;
+    c->host_t += 1;
+    c->host_phase = 2;
+    c->host_feed = 1;
+    return PPO_OK;
+}
+
+// Step t for the whole batch, the mask through the staging block; returns when action_h holds the actions
 extern "C" ppo_status ppo_host_act(ppo_ctx* c, const uint8_t* mask_h, int64_t* action_h) {
     NEED(c, c != nullptr, "null ctx");
     ppo_status s = host_state(c, "ppo_host_act");
@@ -2496,41 +2596,13 @@ extern "C" ppo_status ppo_host_act(ppo_ctx* c, const uint8_t* mask_h, int64_t* a
     if (c->host_t >= c->T) return fail(c, PPO_ERR_STATE, "ppo_host_act: all %d steps of the rollout are taken (ppo_host_rollout_end)", c->T);
     NEED(c, action_h != nullptr, "null argument");
     DeviceGuard dev_guard(c);
-    const int t = c->host_t, N = c->N;
-    const bool masked = c->cfg.dist_kind == PPO_DIST_MASKED && mask_h != nullptr;
-    if (masked) std::memcpy(c->host_stage + (size_t)N * c->O * 4 + 4 * (size_t)N * 4, mask_h, (size_t)N * c->A);
-    HostStepArgs h = host_args(c, t, true);
-    const uint8_t* mask = masked ? host_stage_mask(c) : nullptr;
-    const int64_t step = c->rollout_steps + t;
-    float* params = B_<float>(c, PPO_BUF_PARAMS);
-    s = on_staged(c, h);   // observation normalisation: one more launch, in front of the commit
+    const int N = c->N;
+    s = act_slice(c, StepSlice{ c->host_t, 0, N, c->host_staged, c->host_fin_given }, stage_mask(c, 0, (size_t)N, mask_h), nullptr);
     if (s != PPO_OK) return s;
-    s = rn_batch(c, h);    // reward normalisation: likewise
-    if (s != PPO_OK) return s;
-    if (c->gen) {
-        // generic engine: the commit in place of gen_synthetic_step, then gen_rollout's per-step sequence on the committed observation
-        GenericCtx& g = *c->gen;
-        if (h.commit) HIPCHK(c, launch_host_commit(h, N, c->O, c->stream));
-        s = gen_policy(c, B_<float>(c, PPO_BUF_NEXT_OBS), mask, nullptr, N, step, g.act64, g.step_lp, g.step_en);
-        if (s != PPO_OK) return s;
-        HIPCHK(c, gen_store_step(g.L, N, B_<float>(c, PPO_BUF_NEXT_OBS), mask, g.act64, g.step_lp, B_<int32_t>(c, PPO_BUF_NEXT_DONE), h.obs_t,
-                                 B_<uint8_t>(c, PPO_BUF_MASKS) + (size_t)t * N * c->A, h.actions_t, B_<float>(c, PPO_BUF_LOGPROBS) + (size_t)t * N, h.dones_t,
-                                 c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->host_act, g.act64, (size_t)N * c->H * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-    } else {
-        HIPCHK(c, launch_host_act(params, c->L, c->cfg.dist_kind, mask, N, c->cfg.seed, c->cfg.env_offset, step, h, c->host_act_dev,
-                                  B_<float>(c, PPO_BUF_LOGPROBS) + (size_t)t * N, c->host_as16, c->error_flag, c->stream));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));   // the one wait of a step: the actions
-    std::memcpy(action_h, c->host_act, (size_t)N * c->H * sizeof(int64_t));
-    c->host_staged = false;
-    c->host_t = t + 1;
-    c->host_phase = 2;
-    c->host_feed = 1;
-    return PPO_OK;
+    return host_acted(c, action_h, (size_t)N * c->H * sizeof(int64_t));
 }
 
-// ppo_host_act for a Gaussian context (always the generic engine): the same sequence with the mean in the place of the logits and f32 actions [N,D]
+// ppo_host_act for a Gaussian context: f32 actions [N,D]
 extern "C" ppo_status ppo_host_act_f32(ppo_ctx* c, float* action_h) {
     NEED(c, c != nullptr, "null ctx");
     ppo_status s = host_state(c, "ppo_host_act_f32");
@@ -2543,30 +2615,9 @@ extern "C" ppo_status ppo_host_act_f32(ppo_ctx* c, float* action_h) {
     if (c->host_t >= c->T) return fail(c, PPO_ERR_STATE, "ppo_host_act_f32: all %d steps of the rollout are taken (ppo_host_rollout_end)", c->T);
     NEED(c, action_h != nullptr, "null argument");
     DeviceGuard dev_guard(c);
-    GenericCtx& g = *c->gen;
-    const int t = c->host_t, N = c->N, D = g.L.gauss;
-    const size_t action_bytes = (size_t)N * D * sizeof(float);
-    HostStepArgs h = host_args(c, t, true);
-    s = on_staged(c, h);   // observation normalisation: one more launch, in front of the commit
+    s = act_slice_f32(c, StepSlice{ c->host_t, 0, c->N, c->host_staged, c->host_fin_given }, nullptr);
     if (s != PPO_OK) return s;
-    s = rn_batch(c, h);    // reward normalisation: likewise
-    if (s != PPO_OK) return s;
-    if (h.commit) HIPCHK(c, launch_host_commit(h, N, c->O, c->stream));
-    const GaussStepStores stores{ B_<int32_t>(c, PPO_BUF_NEXT_DONE), h.obs_t, B_<float>(c, PPO_BUF_ACTIONS) + (size_t)t * N * D, B_<float>(c, PPO_BUF_LOGPROBS) + (size_t)t * N, h.dones_t };
-    bool stored = false;
-    s = gen_policy_gauss(c, B_<float>(c, PPO_BUF_NEXT_OBS), nullptr, N, c->rollout_steps + t, g.actf, g.step_lp, g.step_en, false, &stores, &stored);
-    if (s != PPO_OK) return s;
-    if (!stored)
-        HIPCHK(c, gen_gauss_store_step(g.L, N, B_<float>(c, PPO_BUF_NEXT_OBS), g.actf, g.step_lp, stores.done_prev, stores.obs_t, stores.act_t, stores.lp_t, stores.dones_t,
-                                       c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->host_act, g.actf, action_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));   // the one wait of a step: the actions
-    std::memcpy(action_h, c->host_act, action_bytes);
-    c->host_staged = false;
-    c->host_t = t + 1;
-    c->host_phase = 2;
-    c->host_feed = 1;
-    return PPO_OK;
+    return host_acted(c, action_h, (size_t)c->N * c->gen->L.gauss * sizeof(float));
 }
 
 // ---- truncation events: the partial-episode bootstrap for episodes a time limit cut off (the reference ends them like terminal states,
@@ -2648,14 +2699,7 @@ static ppo_status host_observe_common(ppo_ctx* c, const char* what, const float*
     s = trunc_check(c, what, done_h, truncated_h, final_obs_h, 0, N, &n_events);
     if (s != PPO_OK) return s;
     if (n_events > 0) trunc_append(c, c->host_t - 1, truncated_h, final_obs_h, 0, N);
-    unsigned char* st = c->host_stage;
-    std::memcpy(st, next_obs_h, N * c->O * 4);
-    std::memcpy(st + N * c->O * 4, reward_h, N * 4);
-    std::memcpy(st + N * c->O * 4 + N * 4, done_h, N * 4);
-    if (fin_len_h) {
-        std::memcpy(st + N * c->O * 4 + 2 * N * 4, fin_len_h, N * 4);
-        std::memcpy(st + N * c->O * 4 + 3 * N * 4, fin_rew_h, N * 4);
-    }
+    stage_rows(c, 0, N, next_obs_h, reward_h, done_h, fin_len_h, fin_rew_h);
     c->host_fin_given = fin_len_h != nullptr;
     c->host_staged = true;
     c->host_phase = 1;
@@ -2728,30 +2772,12 @@ extern "C" ppo_status ppo_host_group_act(ppo_ctx* c, int32_t g, const uint8_t* m
     if (G.phase == 3) return fail(c, PPO_ERR_STATE, "ppo_host_group_act: group %d: step %d was acted on and not observed (ppo_host_group_observe)", (int)g, G.t - 1);
     if (G.t >= c->T) return fail(c, PPO_ERR_STATE, "ppo_host_group_act: group %d: all %d steps of the rollout are taken (ppo_host_rollout_end)", (int)g, c->T);
     DeviceGuard dev_guard(c);
-    const int t = G.t, N = c->N, n = G.rows;
-    const size_t b = (size_t)G.row0;
-    const bool masked = c->cfg.dist_kind == PPO_DIST_MASKED && mask_h != nullptr;
-    if (masked) std::memcpy(c->host_stage + (size_t)N * c->O * 4 + 4 * (size_t)N * 4 + b * c->A, mask_h, (size_t)n * c->A);
-    const HostStepArgs h = host_args_rows(c, t, true, b, G.staged, G.fin_given);
-    const uint8_t* mask = masked ? host_stage_mask(c) + b * c->A : nullptr;
-    const int64_t step = c->rollout_steps + t;
-    float* logprob_t = B_<float>(c, PPO_BUF_LOGPROBS) + (size_t)t * N + b;
-    if (c->gen) {
-        GenericCtx& ge = *c->gen;
-        int64_t* act64 = ge.act64 + b * c->H;
-        if (h.commit) HIPCHK(c, launch_host_commit(h, n, c->O, c->stream));
-        s = gen_policy(c, h.next_obs, mask, nullptr, n, step, act64, ge.step_lp + b, ge.step_en + b, false, (int64_t)b, N);
-        if (s != PPO_OK) return s;
-        HIPCHK(c, gen_store_step(ge.L, n, h.next_obs, mask, act64, ge.step_lp + b, h.next_done, h.obs_t, B_<uint8_t>(c, PPO_BUF_MASKS) + ((size_t)t * N + b) * c->A,
-                                 h.actions_t, logprob_t, h.dones_t, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->host_act + b * c->H, act64, (size_t)n * c->H * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-    } else {
-        HIPCHK(c, launch_host_act(B_<float>(c, PPO_BUF_PARAMS), c->L, c->cfg.dist_kind, mask, n, c->cfg.seed, c->cfg.env_offset + (int64_t)b, step, h,
-                                  c->host_act_dev + b * c->H, logprob_t, c->host_as16, c->error_flag, c->stream));
-    }
+    const uint8_t* mask = stage_mask(c, (size_t)G.row0, (size_t)G.rows, mask_h);
+    s = act_slice(c, StepSlice{ G.t, (size_t)G.row0, G.rows, G.staged, G.fin_given }, mask, nullptr);
+    if (s != PPO_OK) return s;
     HIPCHK(c, hipEventRecord(G.ev, c->stream));
     G.staged = false;
-    G.t = t + 1;
+    G.t += 1;
     G.phase = 2;
     return PPO_OK;
 }
@@ -2783,19 +2809,12 @@ static ppo_status host_group_observe_common(ppo_ctx* c, const char* what, int32_
                     G.phase == 1 ? "ppo_host_group_act first" : "ppo_host_group_actions first");
     NEED(c, next_obs_h && reward_h && done_h, "null argument");
     NEED(c, (fin_len_h == nullptr) == (fin_rew_h == nullptr), "fin_len_h and fin_rew_h: both or neither");
-    const size_t N = (size_t)c->N, b = (size_t)G.row0, n = (size_t)G.rows;
+    const size_t b = (size_t)G.row0, n = (size_t)G.rows;
     int64_t n_events = 0;
     s = trunc_check(c, what, done_h, truncated_h, final_obs_h, b, n, &n_events);
     if (s != PPO_OK) return s;
     if (n_events > 0) trunc_append(c, G.t - 1, truncated_h, final_obs_h, b, n);
-    unsigned char* st = c->host_stage;
-    std::memcpy(st + b * c->O * 4, next_obs_h, n * c->O * 4);
-    std::memcpy(st + N * c->O * 4 + b * 4, reward_h, n * 4);
-    std::memcpy(st + N * c->O * 4 + N * 4 + b * 4, done_h, n * 4);
-    if (fin_len_h) {
-        std::memcpy(st + N * c->O * 4 + 2 * N * 4 + b * 4, fin_len_h, n * 4);
-        std::memcpy(st + N * c->O * 4 + 3 * N * 4 + b * 4, fin_rew_h, n * 4);
-    }
+    stage_rows(c, b, n, next_obs_h, reward_h, done_h, fin_len_h, fin_rew_h);
     G.fin_given = fin_len_h != nullptr;
     G.staged = true;
     G.phase = 1;
@@ -2970,7 +2989,7 @@ extern "C" ppo_status ppo_env_truncations(ppo_ctx* c, int64_t* count, int32_t* i
 // ---------------------------------------------------------------------------------------------------------
 // Caller-stepped environments on the device (ppo_dev_*): the same rollout fed from DEVICE arrays in stream order (the reference's loop, PPO_Discrete.cpp:365-483,
 // 524-548, with the envs on the chip).  Every call only enqueues: no host wait, no host copy of per-step data.  The hand-over between the caller's stream
-// and the context's (non-blocking) stream is a pair of events per call; caller_stream == the context's stream needs none.  ppo_dev_act is launch_host_act
+// and the context's (non-blocking) stream is a pair of events per call; caller_stream == the context's stream needs none.  ppo_dev_act is act_slice
 // with commit = 0 on the caller's action array; ppo_dev_observe is host_commit_kernel on the caller's arrays, at once, and -- with flags -- the fold kernel
 // that finds the flagged rows itself (launch_dev_fold*).  ppo_host_rollout_end then has nothing to commit and nothing to fold.
 // ---------------------------------------------------------------------------------------------------------
@@ -3028,10 +3047,7 @@ extern "C" ppo_status ppo_dev_env_reset(ppo_ctx* c, const float* obs, void* call
     hipStream_t caller = static_cast<hipStream_t>(caller_stream);
     s = dev_handover_in(c, caller);
     if (s != PPO_OK) return s;
-    HIPCHK(c, hipMemsetAsync(c->buf[PPO_BUF_NEXT_DONE], 0, (size_t)c->N * sizeof(int32_t), c->stream));
-    HIPCHK(c, hipMemsetAsync(c->buf[PPO_BUF_EP_LEN], 0, (size_t)c->N * sizeof(int32_t), c->stream));
-    HIPCHK(c, hipMemsetAsync(c->buf[PPO_BUF_EP_REW], 0, (size_t)c->N * sizeof(float), c->stream));
-    s = rn_reset_returns(c);
+    s = reset_episode_state(c);
     if (s != PPO_OK) return s;
     if (c->on_mode != 0) {
         s = on_batch(c, obs, B_<float>(c, PPO_BUF_NEXT_OBS), c->N);
@@ -3042,8 +3058,21 @@ extern "C" ppo_status ppo_dev_env_reset(ppo_ctx* c, const float* obs, void* call
     return dev_handover_out(c, caller);
 }
 
-// Step t of :524-548 on the committed state (NEXT_OBS / NEXT_DONE): m_obs[t], m_dones[t], the actor forward + sample, m_actions[t], m_logprobs[t] (and
-// masks [t]); the i64 actions go to the caller's device array with plain stores
+// how a device-fed act ends: the hand-over back to the caller's stream, and the state behind the enqueue
+static ppo_status dev_acted(ppo_ctx* c, hipStream_t caller) {
+    const ppo_status s = dev_handover_out(c, caller);
+    if (s != PPO_OK) return s;
+    if (c->host_feed == 0) {   // the first act: this rollout is device-fed, and its events go to the other list
+        c->host_feed = 2;
+        c->dev_list ^= 1;
+        c->dev_list_used = false;
+    }
+    c->host_t += 1;
+    c->host_phase = 2;
+    return PPO_OK;
+}
+
+// Step t on the committed state (NEXT_OBS / NEXT_DONE); the i64 actions go to the caller's device array with plain stores
 extern "C" ppo_status ppo_dev_act(ppo_ctx* c, const uint8_t* mask, int64_t* action, void* caller_stream) {
     NEED(c, c != nullptr, "null ctx");
     ppo_status s = dev_state(c, "ppo_dev_act");
@@ -3055,33 +3084,12 @@ extern "C" ppo_status ppo_dev_act(ppo_ctx* c, const uint8_t* mask, int64_t* acti
     NEED(c, action != nullptr, "ppo_dev_act: null argument");
     DeviceGuard dev_guard(c);
     hipStream_t caller = static_cast<hipStream_t>(caller_stream);
-    const int t = c->host_t, N = c->N;
-    const uint8_t* m = c->cfg.dist_kind == PPO_DIST_MASKED ? mask : nullptr;
-    const HostStepArgs h = host_args_rows(c, t, true, 0, false, false);   // commit = 0: ppo_dev_observe committed step t - 1
-    const int64_t step = c->rollout_steps + t;
     s = dev_handover_in(c, caller);
     if (s != PPO_OK) return s;
-    if (c->gen) {   // gen_rollout's per-step sequence on the committed observation
-        GenericCtx& g = *c->gen;
-        s = gen_policy(c, B_<float>(c, PPO_BUF_NEXT_OBS), m, nullptr, N, step, action, g.step_lp, g.step_en);
-        if (s != PPO_OK) return s;
-        HIPCHK(c, gen_store_step(g.L, N, B_<float>(c, PPO_BUF_NEXT_OBS), m, action, g.step_lp, B_<int32_t>(c, PPO_BUF_NEXT_DONE), h.obs_t,
-                                 B_<uint8_t>(c, PPO_BUF_MASKS) + (size_t)t * N * c->A, h.actions_t, B_<float>(c, PPO_BUF_LOGPROBS) + (size_t)t * N, h.dones_t,
-                                 c->stream));
-    } else {
-        HIPCHK(c, launch_host_act(B_<float>(c, PPO_BUF_PARAMS), c->L, c->cfg.dist_kind, m, N, c->cfg.seed, c->cfg.env_offset, step, h, action,
-                                  B_<float>(c, PPO_BUF_LOGPROBS) + (size_t)t * N, c->host_as16, c->error_flag, c->stream));
-    }
-    s = dev_handover_out(c, caller);
+    // commit = 0: ppo_dev_observe committed step t - 1.  The caller's mask is read in place, and its action array is also what the rollout stores read.
+    s = act_slice(c, StepSlice{ c->host_t, 0, c->N, false, false }, c->cfg.dist_kind == PPO_DIST_MASKED ? mask : nullptr, action);
     if (s != PPO_OK) return s;
-    if (c->host_feed == 0) {   // the first act: this rollout is device-fed, and its events go to the other list
-        c->host_feed = 2;
-        c->dev_list ^= 1;
-        c->dev_list_used = false;
-    }
-    c->host_t = t + 1;
-    c->host_phase = 2;
-    return PPO_OK;
+    return dev_acted(c, caller);
 }
 
 // ppo_dev_act for a Gaussian context: the f32 actions [N,D] go straight to the caller's device array, and the rollout stores read them there
@@ -3096,29 +3104,11 @@ extern "C" ppo_status ppo_dev_act_f32(ppo_ctx* c, float* action, void* caller_st
     NEED(c, action != nullptr, "ppo_dev_act_f32: null argument");
     DeviceGuard dev_guard(c);
     hipStream_t caller = static_cast<hipStream_t>(caller_stream);
-    const int t = c->host_t, N = c->N;
-    const HostStepArgs h = host_args_rows(c, t, true, 0, false, false);   // commit = 0: ppo_dev_observe committed step t - 1
-    GenericCtx& g = *c->gen;
     s = dev_handover_in(c, caller);
     if (s != PPO_OK) return s;
-    const GaussStepStores stores{ B_<int32_t>(c, PPO_BUF_NEXT_DONE), h.obs_t, B_<float>(c, PPO_BUF_ACTIONS) + (size_t)t * N * g.L.gauss, B_<float>(c, PPO_BUF_LOGPROBS) + (size_t)t * N,
-                                  h.dones_t };
-    bool stored = false;
-    s = gen_policy_gauss(c, B_<float>(c, PPO_BUF_NEXT_OBS), nullptr, N, c->rollout_steps + t, action, g.step_lp, g.step_en, false, &stores, &stored);
+    s = act_slice_f32(c, StepSlice{ c->host_t, 0, c->N, false, false }, action);   // commit = 0, as in ppo_dev_act
     if (s != PPO_OK) return s;
-    if (!stored)
-        HIPCHK(c, gen_gauss_store_step(g.L, N, B_<float>(c, PPO_BUF_NEXT_OBS), action, g.step_lp, stores.done_prev, stores.obs_t, stores.act_t, stores.lp_t, stores.dones_t,
-                                       c->stream));
-    s = dev_handover_out(c, caller);
-    if (s != PPO_OK) return s;
-    if (c->host_feed == 0) {   // the first act: this rollout is device-fed, and its events go to the other list
-        c->host_feed = 2;
-        c->dev_list ^= 1;
-        c->dev_list_used = false;
-    }
-    c->host_t = t + 1;
-    c->host_phase = 2;
-    return PPO_OK;
+    return dev_acted(c, caller);
 }
 
 // stepEnvs' outputs for step t (:413-483) from device arrays, committed at once: one launch, and the fold launch behind it when flags are passed
@@ -3141,7 +3131,7 @@ extern "C" ppo_status ppo_dev_observe(ppo_ctx* c, const float* next_obs, const f
         s = dev_lists_reserve(c);
         if (s != PPO_OK) return s;
     }
-    HostStepArgs h = host_args_rows(c, t + 1, false, 0, true, fin_len != nullptr);
+    HostStepArgs h = host_args(c, t + 1, false, 0, true, fin_len != nullptr);
     h.st_obs = next_obs; h.st_rew = reward; h.st_done = done; h.st_fin_len = fin_len; h.st_fin_rew = fin_rew;
     s = dev_handover_in(c, caller);
     if (s != PPO_OK) return s;
@@ -3179,7 +3169,7 @@ extern "C" ppo_status ppo_dev_observe(ppo_ctx* c, const float* next_obs, const f
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Observation normalisation: the four ppo_obs_norm_* calls (ppo_hip.h).  The launches sit in ppo_host_env_reset / ppo_dev_env_reset, ppo_host_act,
+// Observation normalisation: the four ppo_obs_norm_* calls (ppo_hip.h).  The launches sit in ppo_host_env_reset / ppo_dev_env_reset, the acts (act_slice*),
 // ppo_dev_observe, ppo_host_rollout_end and host_fold_truncations (on_batch / on_staged above).
 // ---------------------------------------------------------------------------------------------------------
 static ppo_status on_state(ppo_ctx* c, const char* what, bool outside_rollout) {
@@ -3264,8 +3254,8 @@ extern "C" ppo_status ppo_obs_norm_apply(ppo_ctx* c, const float* obs, int64_t n
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Reward normalisation: the three ppo_reward_norm_* calls (ppo_hip.h).  The launches sit in ppo_host_act, ppo_dev_observe and ppo_host_rollout_end
-// (rn_batch above), the accumulators are cleared by the two resets.
+// Reward normalisation: the three ppo_reward_norm_* calls (ppo_hip.h).  The launches sit in the acts (act_slice*), ppo_dev_observe and ppo_host_rollout_end
+// (rn_batch above), the accumulators are cleared by the two resets (reset_episode_state).
 // ---------------------------------------------------------------------------------------------------------
 static ppo_status rn_state(ppo_ctx* c, const char* what) {
     if (!c->host_env)
@@ -3357,9 +3347,9 @@ extern "C" ppo_status ppo_host_rollout_end(ppo_ctx* c) {
         tab.n = c->host_n_groups;
         for (int g = 0; g < tab.n; g++) { tab.row0[g] = c->host_grp[g].row0; tab.fin_given[g] = c->host_grp[g].fin_given ? 1 : 0; }
         tab.row0[tab.n] = N;
-        HIPCHK(c, launch_host_commit_groups(host_args_rows(c, T, false, 0, true, false), tab, N, c->O, c->stream));
+        HIPCHK(c, launch_host_commit_groups(host_args(c, T, false, 0, true, false), tab, N, c->O, c->stream));
     } else {
-        HostStepArgs h = host_args(c, T, false);
+        HostStepArgs h = host_args(c, T, false, 0, c->host_staged, c->host_fin_given);
         s = on_staged(c, h);
         if (s != PPO_OK) return s;
         s = rn_batch(c, h);

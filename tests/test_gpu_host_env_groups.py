@@ -356,6 +356,64 @@ def test_given_finished_episodes_that_differ_from_the_running_sums(P):
     u.close()
 
 
+# ---- one group of all N rows: the slice where the group calls and the whole-batch calls must be the same rollout ----
+def _one_group_cases(P):
+    """case -> (device env that steps both sides, or None for pre-drawn transitions; masked; config)"""
+    return dict(
+        cartpole_mfma=(P.ENV_CARTPOLE, False, dict(max_episode_steps=2)),
+        cartpole_vector=(P.ENV_CARTPOLE, False, dict(max_episode_steps=2, kernel_flags=P.KERNEL_ROLLOUT_VECTOR)),
+        mountaincar_masked=(P.ENV_MOUNTAINCAR, True, dict(obs_size=2, head_dims=(3,), dist_kind=P.DIST_MASKED, max_episode_steps=2)),
+        generic_f32=(None, False, dict(obs_size=6, head_dims=(3, 2))),
+        generic_bf16_masked=(None, True, dict(obs_size=376, head_dims=(3, 3, 3, 2), hidden=256, n_hidden=4, compute_dtype=P.DTYPE_BF16,
+                                              dist_kind=P.DIST_MASKED)))
+
+
+@pytest.mark.parametrize("N", [7, 33])   # a partial wave; one wave and a tail
+@pytest.mark.parametrize("case", ["cartpole_mfma", "cartpole_vector", "mountaincar_masked", "generic_f32", "generic_bf16_masked"])
+def test_one_group_of_all_rows_is_the_ungrouped_rollout(P, case, N):
+    """bounds [0, N]: one iteration through the group calls and one through ppo_host_act / ppo_host_observe, from the same parameters and seed, leave
+    the same bits in every rollout buffer (ACTIONS, LOGPROBS, OBS, DONES, REWARDS, MASKS among BUFS) and in the parameters after the update"""
+    T, bounds = 4, [0, N]
+    env_kind, masked, cfg = _one_group_cases(P)[case]
+    base = dict(num_envs=N, num_steps=T, num_minibatches=2, update_epochs=1, seed=5, total_timesteps=N * T * 4, **cfg)
+    u = P.Context(P.make_config(env_kind=P.ENV_HOST, **base))
+    b = P.Context(P.make_config(env_kind=P.ENV_HOST, **base))
+    u.init_orthogonal(4)
+    b.set_params(u.get_params())
+    rng = np.random.default_rng(31)
+    masks = None
+    if masked:
+        masks = (rng.random((T, N, u.A)) < 0.7).astype(np.uint8)
+        off = 0
+        for h in range(u.H):   # every head keeps a valid action
+            masks[..., off] = 1
+            off += u.cfg.head_dims[h]
+    if env_kind is None:
+        obs0 = rng.standard_normal((N, u.O)).astype(np.float32)
+        done = (rng.random((T, N)) < 0.2).astype(np.int32)
+        done[1, 0] = 1
+        envs = [ReplayEnvs(bounds, rng.standard_normal((T, N, u.O)).astype(np.float32), rng.uniform(-1, 1, (T, N)).astype(np.float32), done)] * 2
+    else:
+        envs = [ShardEnvs(P, bounds, env_kind=env_kind, **base) for _ in range(2)]   # each side steps envs of its own with its own actions
+        obs0 = envs[0].reset()
+        assert np.array_equal(bits(obs0), bits(envs[1].reset()))
+    u.host_env_reset(obs0)
+    b.host_env_reset(obs0)
+    u.host_rollout_begin()
+    want = np.empty((T, N, u.H), np.int64)
+    for t in range(T):
+        want[t] = u.host_act(None if masks is None else masks[t])
+        u.host_observe(*envs[0].step(0, t, want[t]))
+    u.host_rollout_end()
+    seen = np.full((T, N, u.H), -1, np.int64)
+    grouped_iteration(b, envs[1], bounds, order_lockstep(1, T), masks, seen)
+    assert np.array_equal(seen, want), (case, N)
+    assert_same_state(u, b, tag=(case, N))
+    assert int(u.read("DONES").sum()) > 0   # an episode ended inside the rollout: the commit's reset rows were exercised
+    for c in [u, b] + [e for e in envs if isinstance(e, ShardEnvs)]:
+        c.close()
+
+
 # ---- errors: host-side state checks only ----
 def test_group_call_errors_leave_the_context_unchanged(P):
     N, T = 16, 8

@@ -95,7 +95,15 @@ def test_the_launch_sits_in_front_of_the_commit_and_the_device_calls_never_wait(
     body = src[start:src.index("\n}\n", start)]
     assert body.index("rn_batch(c, h)") < body.index("launch_host_commit(h") < body.index("launch_dev_fold")
     assert not re.search(r"Synchronize|hipMemcpy\(", body)
-    for name in ("ppo_host_act", "ppo_host_rollout_end"):
-        start = src.index('extern "C" ppo_status %s(' % name)
+    # the acts enqueue through the shared step bodies: there the launch sits in front of the commit, and of the 2 x 64 launch that commits and acts
+    for name, decl in (("act_slice", "static"), ("act_slice_f32", "static"), ("ppo_host_rollout_end", 'extern "C"')):
+        start = src.index('%s ppo_status %s(' % (decl, name))
         body = src[start:src.index("\n}\n", start)]
         assert body.index("rn_batch(c, h)") < body.index("launch_host_commit(h"), name
+        if decl == "static":   # shared with the device feed: they only enqueue
+            assert not re.search(r"Synchronize|hipMemcpy\(", body), name
+    body = src[src.index("static ppo_status act_slice("):]
+    assert body.index("rn_batch(c, h)") < body.index("launch_host_act(")
+    for name, via in (("ppo_host_act", "act_slice("), ("ppo_host_act_f32", "act_slice_f32("), ("ppo_dev_act", "act_slice("), ("ppo_dev_act_f32", "act_slice_f32(")):
+        start = src.index('extern "C" ppo_status %s(' % name)
+        assert via in src[start:src.index("\n}\n", start)], name
