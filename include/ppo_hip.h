@@ -168,9 +168,18 @@ typedef struct ppo_config {
  *                               Against the same context without the flag: means and values agree to f32 summation order (both within the forward bar of
  *                               float64), not bit for bit.  Opt-in; any other shape or policy with the flag set is refused by ppo_ctx_create with
  *                               PPO_ERR_UNSUPPORTED and a message that names the limit -- never served by the generic engine instead.
- *                               ppo_gauss_fused_launches counts the three kernels' launches. */
+ *                               ppo_gauss_fused_launches counts the three kernels' launches.
+ *   PPO_KERNEL_SEPARATE_LAUNCHES  the once-per-iteration launches of a CartPole / MountainCar context in their stand-alone form, eight of them: the episode
+ *                               ring's two kernels in front of the NEXT rollout (or the next statistics read), the critic batch, the record pack, the
+ *                               permutations / advantage sums and the normalisation each a launch of its own.  Without the flag ppo_rollout's critic launch
+ *                               also counts and pushes the rollout's finished episodes (values_ring_mfma_kernel: they are in the ring BEHIND their own
+ *                               rollout), and ppo_update's first launch packs the records, forms the permutations and the advantage sums and -- in a context
+ *                               that is not sharded -- the 40 normalisations (pack_perm_stats_kernel).  Every workgroup does the arithmetic it does in the
+ *                               stand-alone kernel, on the same elements in the same order: parameters, buffers and statistics are the same bit for bit, and
+ *                               every reader consumes pending episodes first, so nothing observable moves.  For A/B runs and tests. */
 enum { PPO_KERNEL_ROLLOUT_VECTOR = 1, PPO_KERNEL_UPDATE_VECTOR = 2, PPO_KERNEL_UPDATE_ONE_WAVE = 4, PPO_KERNEL_COMM_SELFTEST = 8, PPO_KERNEL_GENERIC_CLASSIC = 16,
        PPO_KERNEL_GENERIC_SPLIT_HEAD = 32, PPO_KERNEL_GAUSS_FUSED = 64 };
+#define PPO_KERNEL_SEPARATE_LAUNCHES 128   /* the next free bit of kernel_flags, 1 << 7; a macro beside the enumerators: same type in an expression, same use */
 
 /* Scalars the reference prints per update (PPO_Discrete.cpp:700-774) plus per-step diagnostics. */
 typedef struct ppo_stats {

@@ -168,6 +168,8 @@ struct ppo_ctx {
     int32_t* row_counts = nullptr;      // [T]
     uint64_t* group_bits = nullptr;     // [T, ceil(N/64)] ballots of finished episodes
     EpisodeRing* ring = nullptr;
+    unsigned int* pair_tickets = nullptr;   // [0] values_ring_mfma_kernel's, [1] pack_perm_stats_kernel's last-arriver tickets: 0 between launches
+    bool separate_launches = false;    // PPO_KERNEL_SEPARATE_LAUNCHES
     float* scratch_obs = nullptr;       // [N,O] staging for AoS<->SoA conversions
     // ppo_evaluate's scratch, allocated on first use and kept (grown when a call asks for more episodes): per-episode results and, for CartPole, the
     // evaluation reset table (rows of ppo_cartpole_reset_stream_h(eval_table_seed, .); the host copy is kept so that a larger n extends, not redraws)
@@ -604,7 +606,7 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
         return fail(nullptr, PPO_ERR_UNSUPPORTED, "dist_kind = PPO_DIST_GAUSSIAN is built for compute_dtype = PPO_DTYPE_F32; bf16 storage is not");
     if (gauss && cfg->n_heads != 1)
         return fail(nullptr, PPO_ERR_UNSUPPORTED, "dist_kind = PPO_DIST_GAUSSIAN takes n_heads = 1 with head_dims[0] = the action dimension D; got n_heads = %d", cfg->n_heads);
-    if (cfg->kernel_flags & ~(PPO_KERNEL_ROLLOUT_VECTOR | PPO_KERNEL_UPDATE_VECTOR | PPO_KERNEL_UPDATE_ONE_WAVE | PPO_KERNEL_COMM_SELFTEST | PPO_KERNEL_GENERIC_CLASSIC | PPO_KERNEL_GENERIC_SPLIT_HEAD | PPO_KERNEL_GAUSS_FUSED)) return fail(nullptr, PPO_ERR_INVALID, "unknown bits in kernel_flags 0x%x", cfg->kernel_flags);
+    if (cfg->kernel_flags & ~(PPO_KERNEL_ROLLOUT_VECTOR | PPO_KERNEL_UPDATE_VECTOR | PPO_KERNEL_UPDATE_ONE_WAVE | PPO_KERNEL_COMM_SELFTEST | PPO_KERNEL_GENERIC_CLASSIC | PPO_KERNEL_GENERIC_SPLIT_HEAD | PPO_KERNEL_GAUSS_FUSED | PPO_KERNEL_SEPARATE_LAUNCHES)) return fail(nullptr, PPO_ERR_INVALID, "unknown bits in kernel_flags 0x%x", cfg->kernel_flags);
     if (cfg->compute_dtype == PPO_DTYPE_BF16 && !generic)
         return fail(nullptr, PPO_ERR_UNSUPPORTED, "compute_dtype = PPO_DTYPE_BF16 applies to networks whose layers are GEMMs (env_kind = PPO_ENV_SYNTHETIC); the reference's "
                     "2 x 64 networks always compute in f32");
@@ -718,6 +720,7 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
     if (!generic && c->O != 2 && c->O != 4) c->use_mfma = false;
     c->update_single_wave = (cfg->kernel_flags & PPO_KERNEL_UPDATE_ONE_WAVE) != 0;
     c->rollout_vector = (cfg->kernel_flags & PPO_KERNEL_ROLLOUT_VECTOR) != 0;
+    c->separate_launches = (cfg->kernel_flags & PPO_KERNEL_SEPARATE_LAUNCHES) != 0;
     c->max_blocks_per_net = 512;
     const int Pmax = std::max(c->L.net_size[0], c->L.net_size[1]);
     CK(dalloc(c, &c->slab, (size_t)2 * c->max_blocks_per_net * Pmax));
@@ -749,6 +752,7 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
     CK(dalloc(c, &c->row_counts, (size_t)c->T));
     CK(dalloc(c, &c->group_bits, (size_t)c->T * ((N + 63) / 64)));
     CK(dalloc(c, &c->ring, 1));
+    CK(dalloc(c, &c->pair_tickets, 4));
     CK(dalloc(c, &c->scratch_obs, N * c->O));
     CK(dalloc(c, &c->stamps, 24));
     if (host_env) {
@@ -1521,9 +1525,16 @@ extern "C" ppo_status ppo_rollout(ppo_ctx* c, const int64_t* forced_actions) {
     a.next_done = B_<int32_t>(c, PPO_BUF_NEXT_DONE);
     a.next_value = B_<float>(c, PPO_BUF_NEXT_VALUE);
     a.forced_actions = forced_actions;
+    bool ring_pushed = false;
     {
         ProfScope ps(c, PROF_ROLLOUT);
-        HIPCHK(c, launch_rollout(a, c->stream));
+        // the critic launch also counts and pushes this rollout's finished episodes (launch_values_ring_mfma) unless PPO_KERNEL_SEPARATE_LAUNCHES asks for
+        // the two stand-alone kernels, which then run in front of the next reader (consume_finished_episodes)
+        RingFuseArgs rf{};
+        rf.fin_len = a.fin_len; rf.fin_rew = a.fin_rew; rf.row_counts = c->row_counts; rf.group_bits = c->group_bits; rf.ring = c->ring;
+        rf.ticket = c->pair_tickets; rf.step_base = c->rollout_steps; rf.global_num_envs = c->cfg.global_num_envs; rf.env_offset = c->cfg.env_offset;
+        ring_pushed = !c->separate_launches && (c->L.obs == 4 || c->L.obs == 2);
+        HIPCHK(c, launch_rollout(a, c->stream, ring_pushed ? &rf : nullptr));
         c->envt_last = false;
         if (c->envt_on) {   // behind the value launch, in front of the scan (one stream: ppo_calc_advantage and ppo_train_iteration's scan both follow)
             s = env_fold_truncations(c);
@@ -1532,7 +1543,7 @@ extern "C" ppo_status ppo_rollout(ppo_ctx* c, const int64_t* forced_actions) {
     }
     c->rollout_steps += c->T;
     c->global_step += (int64_t)c->T * c->cfg.global_num_envs;  // global_step += num_envs per step (:526)
-    c->fin_pending = true;
+    c->fin_pending = !ring_pushed;
     return PPO_OK;
 }
 
@@ -1944,11 +1955,28 @@ static ppo_status gen_rollout(ppo_ctx* c, const int64_t* forced) {
 
 // The matrix-core update kernel gathers from one packed record per sample and net: (re)build them from the flattened rollout buffers
 // (PPO_Discrete.cpp:557-562).  Also leaves the explained-variance partial sums (:647-648), which read the same returns / values.
-static ppo_status pack_records(ppo_ctx* c) {
+// with_perm (ppo_update with norm_adv, unless PPO_KERNEL_SEPARATE_LAUNCHES): the same launch also forms the update's permutations and advantage sums, and
+// with fold_norm (a context that is not sharded) the normalisations of every minibatch slot and the reset of the clip-fraction accumulator
+// (launch_pack_perm_stats)
+static ppo_status pack_records(ppo_ctx* c, bool with_perm = false, bool fold_norm = false) {
     if (!c->use_mfma || c->gen) return PPO_OK;
     // the observation's fp16 range is an error only where the wave-specialised matrix-core kernel will read the records: not with the one-wave kernel, and
     // not in an update whose weights send every launch to the vector kernel (the caller has refreshed the range snapshot: ppo_update, stand-alone step)
     const bool ws_will_run = !c->update_single_wave && weights_fit_update_mfma(c);
+    if (with_perm) {
+        PackPermArgs a{};
+        a.actions = B_<int32_t>(c, PPO_BUF_ACTIONS); a.n_heads = c->L.n_heads;
+        a.masks = c->cfg.dist_kind == PPO_DIST_MASKED ? B_<uint8_t>(c, PPO_BUF_MASKS) : nullptr; a.A = c->L.act;
+        a.logprobs = B_<float>(c, PPO_BUF_LOGPROBS); a.returns = B_<float>(c, PPO_BUF_RETURNS); a.values = B_<float>(c, PPO_BUF_VALUES);
+        a.rec_critic = reinterpret_cast<float4*>(c->rec_critic); a.rec_actor = reinterpret_cast<float4*>(c->rec_actor);
+        a.ev_out = c->ev_sums; a.error_flag = ws_will_run ? c->error_flag : nullptr;
+        a.update_index = c->updates; a.rank_salt = c->rank; a.stat_out = c->adv_stats;
+        a.n_slots = c->cfg.update_epochs * c->n_mb;
+        a.norm_out = fold_norm ? c->adv_norm : nullptr; a.zero2 = fold_norm ? c->clipfrac_accum : nullptr; a.ticket = c->pair_tickets + 1;
+        HIPCHK(c, launch_pack_perm_stats(c->L, B_<float>(c, PPO_BUF_OBS), B_<float>(c, PPO_BUF_ADVANTAGES), B_<int32_t>(c, PPO_BUF_PERM), c->B,
+                                         c->cfg.update_epochs, c->MB, c->cfg.seed, a, c->stream));
+        return PPO_OK;
+    }
     HIPCHK(c, launch_pack_records(c->L, B_<float>(c, PPO_BUF_OBS), B_<int32_t>(c, PPO_BUF_ACTIONS),
                                   c->cfg.dist_kind == PPO_DIST_MASKED ? B_<uint8_t>(c, PPO_BUF_MASKS) : nullptr, B_<float>(c, PPO_BUF_LOGPROBS),
                                   B_<float>(c, PPO_BUF_ADVANTAGES), B_<float>(c, PPO_BUF_RETURNS), B_<float>(c, PPO_BUF_VALUES), c->B, c->rec_critic,
@@ -2153,7 +2181,12 @@ extern "C" ppo_status ppo_update(ppo_ctx* c) {
         if (s != PPO_OK) return s;
         wr_snapshot(c);
     }
-    s = pack_records(c);
+    // the record pack and the permutations / advantage sums need only the scan's output: ONE launch where the update would launch both, and in a context
+    // that is not sharded its last workgroup also carries the normalisations (PPO_KERNEL_SEPARATE_LAUNCHES: the three stand-alone launches)
+    const bool sharded = (c->world > 1 || c->force_collectives) && c->world <= 8;
+    const bool paired = c->use_mfma && !c->gen && c->cfg.norm_adv && !c->separate_launches;
+    const bool norm_folded = paired && c->world == 1 && !c->force_collectives;
+    s = pack_records(c, paired, norm_folded);
     if (s != PPO_OK) return s;
     struct InUpdate {
         ppo_ctx* c;
@@ -2164,7 +2197,6 @@ extern "C" ppo_status ppo_update(ppo_ctx* c) {
         HIPCHK(c, launch_explained_variance(B_<float>(c, PPO_BUF_RETURNS), B_<float>(c, PPO_BUF_VALUES), c->B, c->ev_sums, c->stream));
     // sharded: this rank's slot of the job-global statistics block (explained-variance sums, its ring of finished episodes with their positions in
     // the reference's push order) rides in front of the advantage sums -- one all-reduce per update, and ppo_read_stats is the same on every rank
-    const bool sharded = (c->world > 1 || c->force_collectives) && c->world <= 8;
     if (sharded) {
         s = consume_finished_episodes(c);
         if (s != PPO_OK) return s;
@@ -2173,12 +2205,13 @@ extern "C" ppo_status ppo_update(ppo_ctx* c) {
     if (c->cfg.norm_adv) {
         // the advantages and the permutations are fixed for the whole update: the permutations of all epochs and the statistics of ALL
         // minibatches in one launch (and, when sharded, one small all-reduce) instead of a reduction inside every optimizer step
-        HIPCHK(c, launch_permutations_adv_stats(B_<float>(c, PPO_BUF_ADVANTAGES), B_<int32_t>(c, PPO_BUF_PERM), c->B, E, c->MB, c->cfg.seed, c->updates,
-                                                c->rank, c->adv_stats, c->stream));
+        if (!paired)
+            HIPCHK(c, launch_permutations_adv_stats(B_<float>(c, PPO_BUF_ADVANTAGES), B_<int32_t>(c, PPO_BUF_PERM), c->B, E, c->MB, c->cfg.seed, c->updates,
+                                                    c->rank, c->adv_stats, c->stream));
         if (sharded) s = allreduce_sum(c, c->gstats, (size_t)PPO_GSTAT_DOUBLES + (size_t)2 * E * nmb * PPO_ADV_PARTS, true);
         else s = allreduce_sum(c, c->adv_stats, (size_t)2 * E * nmb * PPO_ADV_PARTS, true);
         if (s != PPO_OK) return s;
-        HIPCHK(c, launch_adv_norm(c->adv_stats, E * nmb, nmb, c->B, c->MB, 0, c->world, c->adv_norm, c->stream, c->clipfrac_accum));   // also: m_clipfracs reset, :564
+        if (!norm_folded) HIPCHK(c, launch_adv_norm(c->adv_stats, E * nmb, nmb, c->B, c->MB, 0, c->world, c->adv_norm, c->stream, c->clipfrac_accum));   // also: m_clipfracs reset, :564
     } else {
         s = ppo_generate_permutations(c);
         if (s != PPO_OK) return s;

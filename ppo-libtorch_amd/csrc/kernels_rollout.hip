@@ -1450,7 +1450,9 @@ __global__ void categorical_sample_kernel(const float* __restrict__ probs, int64
 // ---------------------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------------------
-hipError_t launch_rollout(const RolloutArgs& a, hipStream_t s) {
+hipError_t launch_rollout(const RolloutArgs& a, hipStream_t s) { return launch_rollout(a, s, nullptr); }
+
+hipError_t launch_rollout(const RolloutArgs& a, hipStream_t s, const RingFuseArgs* ring) {
     const dim3 grid((unsigned)a.N), block(64);
     const dim3 grid2((unsigned)((a.N + 1) / 2));
     const dim3 grid16((unsigned)((a.N + 15) / 16));
@@ -1481,7 +1483,9 @@ hipError_t launch_rollout(const RolloutArgs& a, hipStream_t s) {
 #undef PPO_ROLLOUT_FAST
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    // m_values and the bootstrap value in one batched launch (matrix cores for the reference's observation widths)
+    // m_values and the bootstrap value in one batched launch (matrix cores for the reference's observation widths); with `ring` the same launch also
+    // pushes this rollout's finished episodes (launch_values_ring_mfma)
+    if (ring && (a.L.obs == 4 || a.L.obs == 2)) return launch_values_ring_mfma(a.params, a.L, a.obs, a.values, a.next_obs, a.next_value, a.T, a.N, *ring, s);
     if (a.L.obs == 4 || a.L.obs == 2) return launch_values_mfma(a.params, a.L, a.obs, (int64_t)a.T * a.N, a.values, a.next_obs, a.N, a.next_value, s);
     return launch_values(a.params, a.L, a.obs, (int64_t)a.T * a.N, a.values, a.next_obs, a.N, a.next_value, s);
 }

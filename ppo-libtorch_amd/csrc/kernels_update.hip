@@ -903,15 +903,7 @@ __global__ __launch_bounds__(256) void adv_stats_kernel(const float* __restrict_
     }
 }
 
-// Keyed bijection of [0, 2^bits) (xor / odd multiply / xorshift are each invertible mod 2^bits), cycle-walked into [0, B).
-__device__ __forceinline__ uint32_t mix_bits(uint32_t x, uint32_t mask, int bits, uint4 k) {
-    const int sh = bits > 1 ? bits / 2 : 1;
-    x ^= k.x & mask; x = (x * 0x9E3779B1u) & mask; x ^= x >> sh;
-    x ^= k.y & mask; x = (x * 0x85EBCA77u) & mask; x ^= x >> sh;
-    x ^= k.z & mask; x = (x * 0xC2B2AE3Du) & mask; x ^= x >> sh;
-    x ^= k.w & mask; x = (x * 0x27D4EB2Fu) & mask; x ^= x >> sh;
-    return x;
-}
+// mix_bits (ppo_internal.hpp): the keyed bijection of [0, 2^bits), cycle-walked into [0, B) here.
 __global__ void permutation_kernel(int32_t* perm, int64_t B, int E, int64_t seed, int64_t update_index, int64_t rank_salt) {
     // the round keys depend only on (seed, update, epoch, rank): one Philox call per workgroup, not per element
     __shared__ uint4 s_key;

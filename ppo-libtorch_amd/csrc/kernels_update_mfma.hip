@@ -2240,6 +2240,275 @@ __global__ __launch_bounds__(DEV_FOLD_THREADS, 2) void env_trunc_fold_mfma_kerne
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Paired launches: two jobs that do not depend on each other as workgroups of ONE launch, picked by block index.  What one workgroup leaves for another
+// inside such a launch goes through the last-arriver hand-off below (as exchange_allreduce_kernel's counter, kernels_update.hip): nobody waits, so the
+// launch ends whatever order its workgroups run in.
+// ---------------------------------------------------------------------------------------------------------
+// Called by thread 0 of a workgroup behind the workgroup's barrier.  What the workgroup hands over it has stored with agent_store (write-through to
+// memory: the eight XCDs' L2s are not coherent with each other), and every storing wave has drained its stores (s_waitcnt vmcnt(0)) in front of that
+// barrier: that is the release, without the L2 write-back a release FENCE costs every workgroup (measured: profiles/NOTES.md, 2026-10-19).  Takes a ticket
+// with ONE atomic add and returns true in the ONE workgroup that drew the last of `n` -- which has then (acquire) invalidated its stale lines at agent
+// scope and put the ticket back to 0 for the next launch.  The others' words are read behind the caller's next barrier.
+__device__ __forceinline__ bool last_arriver(unsigned int* ticket, unsigned int n) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const unsigned int drew = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (drew != n - 1u) return false;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return true;
+}
+template <class Tp>
+__device__ __forceinline__ Tp agent_load(const Tp* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+template <class Tp>
+__device__ __forceinline__ void agent_store(Tp* p, Tp v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// episode_count_kernel's job for step row blockIdx.x (kernels_rollout.hip), then -- in the workgroup that finishes last -- episode_push_kernel's walk by
+// the first wave.  s_cnt: >= 2048 ints of the workgroup's LDS, red: >= 5.
+__device__ __forceinline__ void ring_count_then_push(const RingFuseArgs& r, int T, int N, int* s_cnt, int* red) {
+    const int t = blockIdx.x;
+    const int lane = threadIdx.x & 63;
+    const int G = (N + 63) / 64;
+    int c = 0;
+    for (int g = threadIdx.x >> 6; g < G; g += 4) {
+        const int n = g * 64 + lane;
+        const bool f = n < N && r.fin_len[(size_t)t * N + n] > 0;
+        const unsigned long long m = __ballot(f);
+        if (lane == 0) { agent_store(reinterpret_cast<unsigned long long*>(r.group_bits) + (size_t)t * G + g, m); c += __popcll(m); }
+    }
+    if (lane == 0) red[threadIdx.x >> 6] = c;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        agent_store(r.row_counts + t, red[0] + red[1] + red[2] + red[3]);
+        red[4] = last_arriver(r.ticket, (unsigned int)T) ? 1 : 0;
+    }
+    __syncthreads();
+    if (red[4] == 0 || threadIdx.x >= 64) return;
+    // episode_push_kernel's body, statement for statement; the counts and the ballots are the other workgroups' words
+    constexpr int MAXT = 2048;
+    int64_t total = 0;
+    for (int tt = lane; tt < T; tt += 64) {
+        const int cc = agent_load(r.row_counts + tt);
+        if (tt < MAXT) s_cnt[tt] = cc;
+        total += cc;
+    }
+    for (int o = 32; o > 0; o >>= 1) total += __shfl_xor(total, o, 64);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");   // one wave: its own LDS stores in front of its own reads
+    auto cnt = [&](int tt) { return tt < MAXT ? s_cnt[tt] : agent_load(r.row_counts + tt); };
+    int t_start = T, W = 0;
+    while (t_start > 0 && W < 100) { t_start--; W += cnt(t_start); }
+    EpisodeRing* ring = r.ring;
+    const int head = ring->head;
+    const int first = W > 100 ? W - 100 : 0;   // rank of the oldest episode that is still in the ring afterwards
+    int rowbase = 0;
+    for (int tt = t_start; tt < T; tt++) {
+        const int rc = cnt(tt);
+        if (rc == 0) continue;
+        int gbase = rowbase;
+        for (int g0 = 0; g0 < G; g0 += 64) {
+            const int g = g0 + lane;
+            unsigned long long bits = g < G ? agent_load(reinterpret_cast<const unsigned long long*>(r.group_bits) + (size_t)tt * G + g) : 0ull;
+            const int mine = __popcll(bits);
+            int incl = mine;   // inclusive prefix of the per-group counts across the lanes of this stripe
+            for (int o = 1; o < 64; o <<= 1) { const int up = __shfl_up(incl, o, 64); if (lane >= o) incl += up; }
+            int j = gbase + incl - mine;
+            while (bits) {
+                const int b = __ffsll((long long)bits) - 1;
+                bits &= bits - 1;
+                if (j >= first) {
+                    const int n = g * 64 + b;
+                    const int slot = (head + j) % 100;
+                    ring->len[slot] = r.fin_len[(size_t)tt * N + n];
+                    ring->rew[slot] = r.fin_rew[(size_t)tt * N + n];
+                    ring->key[slot] = (r.step_base + tt) * r.global_num_envs + r.env_offset + n;
+                }
+                j++;
+            }
+            gbase += __shfl(incl, 63, 64);
+        }
+        rowbase += rc;
+    }
+    if (lane == 0) {
+        ring->head = (head + W) % 100;
+        const int64_t sz = (int64_t)ring->size + total;
+        ring->size = (int32_t)(sz > 100 ? 100 : sz);
+        ring->total += total;
+    }
+}
+
+// values_mfma_kernel over [n0 rows of obs0 | n1 rows of obs1] with the episode ring's two kernels as workgroups [0, T) of the same launch (ppo_internal.hpp:
+// launch_values_ring_mfma; n1 = N envs, n0 = T * N).  A critic workgroup takes the tiles values_mfma_kernel gives workgroup blockIdx.x - T of a grid of
+// gridDim.x - T, through the fold kernels' copy of its tile body: the same products in the same order.  Fourteen leading dwords, the structs last.
+template <int OBS>
+__global__ __launch_bounds__(256, 2) void values_ring_mfma_kernel(const float* __restrict__ P, const float* __restrict__ obs0, int64_t n0,
+                                                                  float* __restrict__ out0, const float* __restrict__ obs1, float* __restrict__ out1,
+                                                                  int n1, int T, NetLayout L, RingFuseArgs r) {
+    __shared__ __attribute__((aligned(16))) uint16_t sW2p[2 * 64 * WS];   // an episode workgroup's row counts live here: a workgroup does one job or the other
+    __shared__ __attribute__((aligned(16))) float sB1[64], sB2[64], sW3[64];
+    static_assert(sizeof(uint16_t) * 2 * 64 * WS >= sizeof(int) * 2048, "the push walk keeps 2048 row counts in the weight image's LDS");
+    if ((int)blockIdx.x < T) {
+        ring_count_then_push(r, T, n1, reinterpret_cast<int*>(sW2p), reinterpret_cast<int*>(sB1));
+        return;
+    }
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int s = lane & 31, hi = lane >> 5;
+    constexpr int L1S = CriticTile<OBS>::L1S;
+    CriticTile<OBS> ct;
+    critic_tile_stage<OBS>(P, L, sW2p, sB1, sB2, sW3, ct);
+    const int64_t n = n0 + n1;
+    const int64_t n_tiles = (n + MT - 1) / MT;
+    auto load_x = [&](int64_t tl, float* xo) {   // as values_mfma_kernel: one tile ahead, a missing row reads row 0 and is zeroed at use
+        const int64_t rr = tl * MT + s;
+        const bool ok = rr < n;
+        const float* src = !ok ? obs0 : (rr < n0 ? obs0 + rr * OBS : obs1 + (rr - n0) * OBS);
+#pragma unroll
+        for (int stp = 0; stp < L1S; stp++) xo[stp] = src[(2 * stp + 1 < OBS) ? 2 * stp + hi : 2 * stp];
+    };
+    const int64_t vb = (int64_t)blockIdx.x - T;
+    const int64_t tile_step = ((int64_t)gridDim.x - T) * 4;
+    float x_n[L1S];
+    load_x(vb * 4 + wave, x_n);
+    for (int64_t tile = vb * 4 + wave; tile < n_tiles; tile += tile_step) {
+        const int64_t row = tile * MT + s;
+        const bool valid = row < n;
+        float xb[L1S];
+#pragma unroll
+        for (int stp = 0; stp < L1S; stp++) xb[stp] = (valid && (2 * stp + 1 < OBS || hi == 0)) ? x_n[stp] : 0.0f;
+        load_x(tile + tile_step, x_n);
+        const float v = critic_tile_value<OBS>(ct, xb, sW2p, sB1, sB2, sW3);
+        if (valid && hi == 0) { if (row < n0) out0[row] = v; else out1[row - n0] = v; }
+    }
+}
+
+// pack_records_kernel's job for workgroup `blk` of PPO_EV_BLOCKS: statement for statement, so ev_out[blk] holds the same partial sums
+template <int OBS>
+__device__ __forceinline__ void pack_records_body(const float* __restrict__ obs, const float* __restrict__ advantages, int64_t B, const PackPermArgs& a, int blk,
+                                                  double (*red)[4]) {
+    double sy = 0, sy2 = 0, sd = 0, sd2 = 0;
+    float x_absmax = 0.0f;
+    for (int64_t i = (int64_t)blk * 256 + threadIdx.x; i < B; i += (int64_t)PPO_EV_BLOCKS * 256) {
+        float4 x = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if constexpr (OBS == 4) x = *reinterpret_cast<const float4*>(obs + i * 4);
+        else { const float2 v = *reinterpret_cast<const float2*>(obs + i * 2); x.x = v.x; x.y = v.y; }
+        uint32_t ab = 0u, mb = 0xffffffffu;
+        for (int h = 0; h < a.n_heads; h++) ab |= ((uint32_t)a.actions[i * a.n_heads + h] & 0xffu) << (8 * h);
+        if (a.masks) { mb = 0u; for (int k = 0; k < a.A; k++) mb |= (a.masks[i * a.A + k] ? 1u : 0u) << k; }
+        x_absmax = fmaxf(fmaxf(x_absmax, fmaxf(fabsf(x.x), fabsf(x.y))), fmaxf(fabsf(x.z), fabsf(x.w)));
+        const float R = a.returns[i], V = a.values[i];
+        a.rec_critic[4 * i] = x;
+        a.rec_critic[4 * i + 1] = make_float4(R, V, 0.0f, 0.0f);
+        a.rec_actor[4 * i] = x;
+        a.rec_actor[4 * i + 1] = make_float4(a.logprobs[i], advantages[i], u2f(ab), u2f(mb));
+        const double y = R, d = (double)(R - V);
+        sy += y; sy2 += y * y; sd += d; sd2 += d * d;
+    }
+    if (!(x_absmax < 65504.0f) && a.error_flag) atomicOr(a.error_flag, PPO_ERRFLAG_UPDATE_RANGE);
+    sy = wave_sum_d_dpp(sy); sy2 = wave_sum_d_dpp(sy2); sd = wave_sum_d_dpp(sd); sd2 = wave_sum_d_dpp(sd2);
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { red[w][0] = sy; red[w][1] = sy2; red[w][2] = sd; red[w][3] = sd2; }
+    __syncthreads();
+    if (threadIdx.x < 4) a.ev_out[blk * 4 + threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+}
+
+// perm_adv_stats_kernel's job for (minibatch mb of the update, part) (kernels_update.hip): the same bijection and keys, the same eight-deep loop, the same
+// per-thread order of the sums.  With a.norm_out the workgroup that finishes last of n_blocks then does adv_norm_kernel's job for every slot.
+__device__ __forceinline__ void perm_stats_body(const float* __restrict__ adv, int32_t* __restrict__ perm, int64_t B, int64_t MB, int n_mb_per_epoch, int64_t seed,
+                                                const PackPermArgs& a, int mb, int part, int n_blocks, double* r1, double* r2, uint4* s_key, int* s_last) {
+    const int e = mb / n_mb_per_epoch, m = mb % n_mb_per_epoch;
+    if (threadIdx.x == 0) *s_key = philox4x32_10((uint32_t)seed, (uint32_t)((uint64_t)seed >> 32), (uint32_t)a.update_index, (uint32_t)e, (uint32_t)a.rank_salt, 2u);
+    int bits = 1;
+    while ((1ll << bits) < B) bits++;
+    const uint32_t mask = bits >= 32 ? 0xffffffffu : ((1u << bits) - 1u);
+    __syncthreads();
+    const uint4 k = *s_key;
+    const int64_t start = (int64_t)m * MB;
+    const int64_t end = start + MB < B ? start + MB : B;
+    const int64_t len = end - start;
+    const int64_t p0 = start + (len * part) / PPO_ADV_PARTS, p1 = start + (len * (part + 1)) / PPO_ADV_PARTS;
+    int32_t* idx = perm + (size_t)e * B;
+    double s1 = 0.0, s2 = 0.0;
+    int64_t j = p0 + threadIdx.x;
+    for (; j + 7 * 256 < p1; j += 8 * 256) {
+        uint32_t x[8];
+        float v[8];
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            x[i] = (uint32_t)(j + i * 256);
+            do { x[i] = mix_bits(x[i], mask, bits, k); } while (x[i] >= (uint64_t)B);
+        }
+#pragma unroll
+        for (int i = 0; i < 8; i++) v[i] = adv[x[i]];
+#pragma unroll
+        for (int i = 0; i < 8; i++) idx[j + i * 256] = (int32_t)x[i];
+#pragma unroll
+        for (int i = 0; i < 8; i++) { const double t = v[i]; s1 += t; s2 += t * t; }
+    }
+    for (; j < p1; j += 256) {
+        uint32_t x = (uint32_t)j;
+        do { x = mix_bits(x, mask, bits, k); } while (x >= (uint64_t)B);
+        idx[j] = (int32_t)x;
+        const double t = adv[x]; s1 += t; s2 += t * t;
+    }
+    s1 = wave_sum_d(s1); s2 = wave_sum_d(s2);
+    if ((threadIdx.x & 63) == 0) { r1[threadIdx.x >> 6] = s1; r2[threadIdx.x >> 6] = s2; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        AdvStat* o = a.stat_out + (size_t)mb * PPO_ADV_PARTS + part;
+        agent_store(&o->s1, ((r1[0] + r1[1]) + r1[2]) + r1[3]);
+        agent_store(&o->s2, ((r2[0] + r2[1]) + r2[2]) + r2[3]);
+        if (a.norm_out) *s_last = last_arriver(a.ticket, (unsigned int)n_blocks) ? 1 : 0;
+    }
+    if (!a.norm_out) return;
+    __syncthreads();
+    if (*s_last == 0) return;
+    // adv_norm_kernel's arithmetic (kernels_update.hip) for every slot: world = 1, no explicit row count
+    for (int kk = threadIdx.x; kk < a.n_slots; kk += 256) {
+        // plain vector loads behind the acquire, eight parts in flight together (one agent-scope load at a time made this epilogue 40 us long; all 32
+        // together cost the whole kernel its occupancy); summed in order
+        const AdvStat* st_k = a.stat_out + (size_t)kk * PPO_ADV_PARTS;
+        double t1 = 0.0, t2 = 0.0;
+        static_assert(PPO_ADV_PARTS % 8 == 0, "eight parts per round");
+#pragma unroll 1
+        for (int i0 = 0; i0 < PPO_ADV_PARTS; i0 += 8) {
+            AdvStat part_sums[8];
+#pragma unroll
+            for (int i = 0; i < 8; i++) part_sums[i] = st_k[i0 + i];
+#pragma unroll
+            for (int i = 0; i < 8; i++) { t1 += part_sums[i].s1; t2 += part_sums[i].s2; }
+        }
+        const int64_t st = (int64_t)(kk % n_mb_per_epoch) * MB;
+        const int64_t M = MB < B - st ? MB : B - st;
+        const double global_M = (double)M * 1;
+        const double mean = t1 / global_M;
+        const double var = (t2 - t1 * mean) / (global_M - 1.0);
+        const float mean_f = (float)mean;
+        const float std_f = (float)sqrt(var < 0.0 ? 0.0 : var);
+        a.norm_out[kk] = make_float4(mean_f, 1.0f / (std_f + 1e-8f), std_f, 0.0f);
+    }
+    if (threadIdx.x == 0 && a.zero2) { a.zero2[0] = 0.0; a.zero2[1] = 0.0; }
+}
+
+// The record pack and the update's permutations / advantage sums as workgroups of one launch (ppo_internal.hpp: launch_pack_perm_stats).  The permutation
+// workgroups own the low block indices: theirs is the longer job (integer mixing, 25 us at 4096 x 128 against the pack's 14 us of streaming), and the
+// last of them to finish carries the 40 normalisations.  Workgroup b < n_perm is perm_adv_stats_kernel's (blockIdx.x = b % n_mb, blockIdx.y = b / n_mb): the
+// order its two-dimensional grid is dispatched in.
+template <int OBS>
+__global__ __launch_bounds__(256) void pack_perm_stats_kernel(const float* __restrict__ obs, const float* __restrict__ advantages, int32_t* __restrict__ perm,
+                                                              int64_t B, int64_t MB, int64_t seed, int n_perm, int n_mb_per_epoch, PackPermArgs a) {
+    __shared__ double red[4][4];
+    __shared__ uint4 s_key;
+    __shared__ int s_last;
+    const int b = blockIdx.x;
+    if (b < n_perm) {
+        const int n_mb = n_perm / PPO_ADV_PARTS;
+        perm_stats_body(advantages, perm, B, MB, n_mb_per_epoch, seed, a, b % n_mb, b / n_mb, n_perm, red[0], red[1], &s_key, &s_last);
+    } else {
+        pack_records_body<OBS>(obs, advantages, B, a, b - n_perm, red);
+    }
+}
+
 }  // namespace
 
 // One 8-wave workgroup per CU (256 vector registers per wave: two waves per SIMD is all a CU holds; LDS ~95 KB), half of them per net.
@@ -2349,6 +2618,37 @@ hipError_t launch_values_mfma(const float* params, const NetLayout& L, const flo
     const unsigned grid = (unsigned)(wg_needed < 1024 ? wg_needed : 1024);
     if (L.obs == 4) hipLaunchKernelGGL((values_mfma_kernel<4>), dim3(grid), dim3(256), 0, s, params, obs0, n0, out0, obs1, n1, out1, L);
     else if (L.obs == 2) hipLaunchKernelGGL((values_mfma_kernel<2>), dim3(grid), dim3(256), 0, s, params, obs0, n0, out0, obs1, n1, out1, L);
+    else return hipErrorNotSupported;
+    return hipGetLastError();
+}
+
+constexpr int VALUES_RING_GRID_CAP = 1024;   // workgroups of 256 threads at 128 registers: four per CU
+hipError_t launch_values_ring_mfma(const float* params, const NetLayout& L, const float* obs0, float* out0, const float* obs1, float* out1, int T, int N,
+                                   const RingFuseArgs& r, hipStream_t s) {
+    if (T <= 0 || N <= 0 || !r.ticket) return hipErrorInvalidValue;
+    const int64_t n0 = (int64_t)T * N;
+    const int64_t wg_needed = ((n0 + N + MT - 1) / MT + 3) / 4;
+    // launch_values_mfma caps its grid at the 1024 workgroups the chip holds at once (four per CU).  Here the T episode workgroups hold T of those places
+    // when the launch starts, and critic workgroups beyond the rest would start only as places come free and end the launch that much later (measured: 29.4 us
+    // in trace against values_mfma_kernel's 24.0 with the cap at 1024): the cap is 1024 - T.  A row's value does not depend on which workgroup computes it.
+    const int64_t vcap = VALUES_RING_GRID_CAP - (T < VALUES_RING_GRID_CAP / 2 ? T : VALUES_RING_GRID_CAP / 2);
+    const unsigned vgrid = (unsigned)(wg_needed < vcap ? wg_needed : vcap);
+    const dim3 grid(vgrid + (unsigned)T);
+    if (L.obs == 4) hipLaunchKernelGGL((values_ring_mfma_kernel<4>), grid, dim3(256), 0, s, params, obs0, n0, out0, obs1, out1, N, T, L, r);
+    else if (L.obs == 2) hipLaunchKernelGGL((values_ring_mfma_kernel<2>), grid, dim3(256), 0, s, params, obs0, n0, out0, obs1, out1, N, T, L, r);
+    else return hipErrorNotSupported;
+    return hipGetLastError();
+}
+
+hipError_t launch_pack_perm_stats(const NetLayout& L, const float* obs, const float* advantages, int32_t* perm, int64_t B, int E, int64_t MB, int64_t seed,
+                                  const PackPermArgs& a, hipStream_t s) {
+    if (L.act > 4 || L.n_heads > 4) return hipErrorNotSupported;
+    if (a.norm_out && !a.ticket) return hipErrorInvalidValue;
+    const int per_epoch = (int)((B + MB - 1) / MB);
+    const int n_perm = E * per_epoch * PPO_ADV_PARTS;
+    const dim3 grid((unsigned)(n_perm + PPO_EV_BLOCKS)), block(256);
+    if (L.obs == 4) hipLaunchKernelGGL((pack_perm_stats_kernel<4>), grid, block, 0, s, obs, advantages, perm, B, MB, seed, n_perm, per_epoch, a);
+    else if (L.obs == 2) hipLaunchKernelGGL((pack_perm_stats_kernel<2>), grid, block, 0, s, obs, advantages, perm, B, MB, seed, n_perm, per_epoch, a);
     else return hipErrorNotSupported;
     return hipGetLastError();
 }

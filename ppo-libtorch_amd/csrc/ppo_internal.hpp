@@ -118,6 +118,17 @@ __device__ __forceinline__ uint4 philox4x32_10(uint32_t k0, uint32_t k1, uint32_
     return make_uint4(c0, c1, c2, c3);
 }
 
+// Keyed bijection of [0, 2^bits) (xor / odd multiply / xorshift are each invertible mod 2^bits), cycle-walked into [0, B) by its callers: the update's
+// permutations (kernels_update.hip: permutation_kernel, perm_adv_stats_kernel; kernels_update_mfma.hip: pack_perm_stats_kernel).
+__device__ __forceinline__ uint32_t mix_bits(uint32_t x, uint32_t mask, int bits, uint4 k) {
+    const int sh = bits > 1 ? bits / 2 : 1;
+    x ^= k.x & mask; x = (x * 0x9E3779B1u) & mask; x ^= x >> sh;
+    x ^= k.y & mask; x = (x * 0x85EBCA77u) & mask; x ^= x >> sh;
+    x ^= k.z & mask; x = (x * 0xC2B2AE3Du) & mask; x ^= x >> sh;
+    x ^= k.w & mask; x = (x * 0x27D4EB2Fu) & mask; x ^= x >> sh;
+    return x;
+}
+
 // libstdc++ uniform_real_distribution<float>(a,b) on one 32-bit word (reference Environments/CartPole.cpp:96-100).
 __device__ __forceinline__ float canon_to_uniform(uint32_t u, float a, float b) {
     float r = (float)u / 4294967296.0f;
@@ -938,6 +949,45 @@ struct EpisodeRing {
 };
 hipError_t launch_episode_ring_update(const int32_t* fin_len, const float* fin_rew, int T, int N, int32_t* row_counts, uint64_t* group_bits,
                                       EpisodeRing* ring, int64_t step_base, int64_t global_num_envs, int64_t env_offset, hipStream_t s);
+// The same two jobs as workgroups of the rollout's critic launch (kernels_update_mfma.hip: values_ring_mfma_kernel): launch_episode_ring_update's arguments
+// and `ticket`, one device word that is 0 between launches.  The T count workgroups each take a ticket behind their row; the one that draws the last does
+// the push.  Nobody waits for anybody.
+struct RingFuseArgs {
+    const int32_t* fin_len;
+    const float* fin_rew;
+    int32_t* row_counts;
+    uint64_t* group_bits;
+    EpisodeRing* ring;
+    unsigned int* ticket;
+    int64_t step_base, global_num_envs, env_offset;
+};
+// launch_values_mfma over [T * N rows of obs0 | N rows of obs1] and launch_episode_ring_update(T, N) in ONE launch: workgroups [0, T) count a step row each
+// (the push's serial walk is the longest chain of the launch, so its feeders start first), the rest run the critic's tiles with the block index and grid
+// size launch_values_mfma gives them -- the values are that launch's, bit for bit.  The critic keeps the vector ALUs busy for ~24 us (4096 x 128); the
+// ring's 20 us are one round trip and ONE wave walking rows, and hide behind it.
+hipError_t launch_values_ring_mfma(const float* params, const NetLayout& L, const float* obs0, float* out0, const float* obs1, float* out1, int T, int N,
+                                   const RingFuseArgs& r, hipStream_t s);
+// launch_rollout with `ring`: its critic launch is launch_values_ring_mfma, and the rollout's finished episodes are in the ring behind it
+hipError_t launch_rollout(const RolloutArgs& a, hipStream_t s, const RingFuseArgs* ring);
+// launch_pack_records and launch_permutations_adv_stats in ONE launch (kernels_update_mfma.hip: pack_perm_stats_kernel): both need only the scan's output;
+// the pack streams 64 B per sample with idle ALUs, the permutations are integer mixing and a cache-resident gather.  Workgroups [0, E * per_epoch *
+// PPO_ADV_PARTS) form the permutations and the advantage sums with perm_adv_stats_kernel's (minibatch, part) -> element mapping, the next PPO_EV_BLOCKS pack
+// with pack_records_kernel's grid-stride mapping; every sum keeps its order.  norm_out != nullptr (a context that is not sharded): the permutation
+// workgroup that finishes last also does launch_adv_norm's job for all slots (the partial sums in order, in binary64) and clears zero2 -- `ticket` is its
+// device word, 0 between launches.  norm_out == nullptr: the caller all-reduces the sums and launches launch_adv_norm.
+struct PackPermArgs {
+    // pack_records_kernel's
+    const int32_t* actions; int n_heads; const uint8_t* masks; int A;
+    const float* logprobs; const float* returns; const float* values;
+    float4* rec_critic; float4* rec_actor; double* ev_out; int32_t* error_flag;
+    // perm_adv_stats_kernel's
+    int64_t update_index, rank_salt;
+    AdvStat* stat_out;
+    // adv_norm_kernel's
+    int n_slots; float4* norm_out; double* zero2; unsigned int* ticket;
+};
+hipError_t launch_pack_perm_stats(const NetLayout& L, const float* obs, const float* advantages, int32_t* perm, int64_t B, int E, int64_t MB, int64_t seed,
+                                  const PackPermArgs& a, hipStream_t s);
 // this rank's contribution to the job-global statistics block (PPO_GSTAT_*): zeroes the block, then writes the head and the rank's own slot
 hipError_t launch_gstats_pack(const double* ev_sums, const EpisodeRing* ring, int rank, double* gstats, hipStream_t s);
 hipError_t launch_adv_stats(const float* advantages, const int32_t* perm, int64_t B, int64_t MB, int n_mb_total, AdvStat* out,
