@@ -67,15 +67,40 @@ enum { PPO_OK = 0, PPO_ERR_INVALID = 1, PPO_ERR_HIP = 2, PPO_ERR_STATE = 3, PPO_
  * (PPO_ERR_UNSUPPORTED: its fold rebuilds the final observation from PPO_BUF_OBS, and a Pendulum observation does not hold theta); ppo_obs_norm_* and
  * ppo_reward_norm_* (PPO_ERR_UNSUPPORTED, as on every device env); ppo_env_step and ppo_rollout with an i64 array (PPO_ERR_UNSUPPORTED, naming the _f32 call).
  * Sharding (ppo_comm_init*) is neither claimed nor tested for this env. */
-enum { PPO_ENV_CARTPOLE = 0, PPO_ENV_MOUNTAINCAR = 1, PPO_ENV_SYNTHETIC = 2, PPO_ENV_HOST = 3, PPO_ENV_PENDULUM = 4 };
+/* PPO_ENV_MOUNTAINCAR_CONTINUOUS (new; value 5): gymnasium's MountainCarContinuous-v0 on the device, the second env of the Gaussian policy's fused rollout and
+ * the sibling of PPO_ENV_MOUNTAINCAR: the same track, the same reset, one cosine per step.  State (position p, velocity v) f32, and the observation IS the
+ * state: obs_size 2, PPO_BUF_ENV_STATE is [2, N], ppo_env_set_state_h / ppo_env_get_state_h take [N, 2].  One real-valued action.  One step with the RAW
+ * action a, every operation rounded on its own, in this association:
+ *   u   = min(max(a, -1), 1)
+ *   v'  = v + (u * 0.0015f - 0.0025f * cosf(3.0f * p));   v' = min(max(v', -0.07f), 0.07f)
+ *   p'  = p + v';                                          p' = min(max(p', -1.2f), 0.6f)
+ *   if (p' == -1.2f && v' < 0) v' = 0
+ *   terminated = (p' >= 0.45f && v' >= 0.0f)
+ *   reward = (terminated ? 100.0f : 0.0f) - 0.1f * (a * a)                                          (the RAW action, as gym's math.pow(action[0], 2))
+ * with cosf the library's own device function (glibc 2.35's cosf, bit for bit; its argument stays within [-3.6, 1.8]).  Only the env's copy of the action is
+ * clipped: PPO_BUF_ACTIONS keeps the raw sample.  An episode ends where the env terminates or its length reaches max_episode_steps (any value >= 1; gym: 999):
+ * done = 1, FIN_LEN / FIN_REW written, auto-reset -- ppo_env_step's bookkeeping.  Reset number k of global env e is MountainCar's own:
+ * p = uniform(philox4x32_10(seed; e, k, 0, 1).x, -0.6, -0.4), v = 0; global env 0 takes reset 1 at ppo_env_reset; PPO_BUF_RESET_COUNT counts them.
+ * ppo_ctx_create accepts the env in exactly one form: dist_kind = PPO_DIST_GAUSSIAN, n_heads = 1, head_dims[0] = 1, obs_size = 2, hidden = 64, n_hidden = 2,
+ * PPO_DTYPE_F32, kernel_flags containing PPO_KERNEL_GAUSS_FUSED (required, never implied) and max_episode_steps >= 1.  A wrong obs_size returns
+ * PPO_ERR_INVALID with the reference's obs-size message, anything else PPO_ERR_UNSUPPORTED with a message that names the limit.
+ * Calls: those of PPO_ENV_PENDULUM (above; ppo_env_transition_f32 with state_in [n, 2], action [n, 1], obs_out [n, 2] = the next state or NULL, and
+ * `terminated` as the step computes it), and -- because a stored observation is enough to step from -- ppo_env_truncation_bootstrap, ppo_env_truncations and
+ * ppo_evaluate.  ppo_rollout is THREE launches, as for Pendulum -- the same kernel, gauss_rollout_kernel, instantiated for this env -- and a stepwise loop of
+ * ppo_policy_act_f32(obs, step_index = rollout_steps + t) and ppo_env_step_f32 reproduces every buffer bit for bit
+ * (tests/test_gpu_mountaincar_continuous.py); with ppo_env_truncation_bootstrap on, a fourth launch folds the cut-off episodes (below).
+ * Refused exactly as on Pendulum, changing nothing: ppo_host_* / ppo_dev_* (PPO_ERR_STATE); ppo_obs_norm_* and ppo_reward_norm_* (PPO_ERR_UNSUPPORTED);
+ * ppo_env_step, ppo_rollout with an i64 array and ppo_policy_act (PPO_ERR_UNSUPPORTED, naming the _f32 twin).
+ * Sharding (ppo_comm_init*) is neither claimed nor tested for this env. */
+enum { PPO_ENV_CARTPOLE = 0, PPO_ENV_MOUNTAINCAR = 1, PPO_ENV_SYNTHETIC = 2, PPO_ENV_HOST = 3, PPO_ENV_PENDULUM = 4, PPO_ENV_MOUNTAINCAR_CONTINUOUS = 5 };
 /* PPO_DIST_CATEGORICAL reproduces Distributions/Categorical.cpp including its entropy clamp (:112-119);
  * PPO_DIST_MASKED reproduces Distributions/CategoricalMasked.cpp (true entropy, -1e8 masking).
  * PPO_DIST_GAUSSIAN (new; the reference has no continuous policy): a diagonal Gaussian over D = head_dims[0] real-valued actions (n_heads = 1,
  * 1 <= D <= 32).  The actor's output layer gives the mean mu[D]; a state-independent parameter log_std[D] -- ONE MORE TENSOR, the last in
  * Agent::parameters() order, behind the actor's layers (ppo_param_count, ppo_param_shapes), initialised to 0 -- gives the scale.  With
  * z = (a - mu) exp(-log_std):  log-prob = sum_d (-z_d^2 / 2 - log_std_d - log(2 pi) / 2),  entropy = sum_d (1 / 2 + log(2 pi) / 2 + log_std_d), no clamp.
- * Serves PPO_ENV_HOST contexts with PPO_DTYPE_F32, on the generic engine (also for a 2 x 64 network, unless kernel_flags has PPO_KERNEL_GAUSS_FUSED), and PPO_ENV_PENDULUM
- * contexts in the one form that env accepts (above); any other env_kind, PPO_DTYPE_BF16 or
+ * Serves PPO_ENV_HOST contexts with PPO_DTYPE_F32, on the generic engine (also for a 2 x 64 network, unless kernel_flags has PPO_KERNEL_GAUSS_FUSED), and PPO_ENV_PENDULUM /
+ * PPO_ENV_MOUNTAINCAR_CONTINUOUS contexts in the one form each env accepts (above); any other env_kind, PPO_DTYPE_BF16 or
  * n_heads != 1 make ppo_ctx_create return PPO_ERR_UNSUPPORTED.  Actions are f32: PPO_BUF_ACTIONS is f32 [T,N,D], PPO_BUF_MASKS is not used, and the
  * calls that carry actions have _f32 twins (ppo_host_act_f32, ppo_dev_act_f32, ppo_policy_act_f32); the integer calls return PPO_ERR_UNSUPPORTED on a
  * Gaussian context and name the twin, and the twins do the same on a categorical context.  Env groups (ppo_host_rollout_begin_groups) return
@@ -323,7 +348,8 @@ PPO_API ppo_status ppo_gaussian(const float* mean, const float* log_std, const f
 /* Host-side counts, since the context's creation, of the launches of the three PPO_KERNEL_GAUSS_FUSED kernels: act (one per env step / ppo_policy_act_f32),
  * value (one per critic batch) and update (one per minibatch step).  All three are 0 on a context without the flag: proof of which path ran, like
  * ppo_profile.vector_fallback_launches.  Outputs may be NULL.  PPO_ENV_PENDULUM's rollout launch (gauss_rollout_kernel) is none of the three: a ppo_rollout there
- * moves `value` by 2 and `act` not at all. */
+ * moves `value` by 2 and `act` not at all.  The same holds on PPO_ENV_MOUNTAINCAR_CONTINUOUS, whose truncation fold (gauss_trunc_fold_kernel) and evaluation
+ * launch (gauss_eval_kernel) are none of the three either: a rollout moves `value` by 2 with ppo_env_truncation_bootstrap on or off, ppo_evaluate moves nothing. */
 PPO_API ppo_status ppo_gauss_fused_launches(ppo_ctx* ctx, int64_t* act, int64_t* value, int64_t* update);
 
 /* Categorical::sample / CategoricalMasked::sample (Categorical.cpp:73-79: multinomial(probs, 1, replacement = true)) on given
@@ -364,12 +390,14 @@ PPO_API ppo_status ppo_env_reset(ppo_ctx* ctx);
 /* PPO_Discrete::stepEnvs (PPO_Discrete.cpp:413-483): action i64 [N,H] (column 0 drives the env);
  * outputs obs [N,O] (first obs of the new episode where done), reward f32 [N], done i32 [N]. */
 PPO_API ppo_status ppo_env_step(ppo_ctx* ctx, const int64_t* action, float* obs, float* reward, int32_t* done);
-/* ppo_env_step for a context whose env takes real-valued actions (PPO_ENV_PENDULUM): action f32 [N,D] (the raw action; the env clips its own copy), the same
+/* ppo_env_step for a context whose env takes real-valued actions (PPO_ENV_PENDULUM, PPO_ENV_MOUNTAINCAR_CONTINUOUS): action f32 [N,D] (the raw action; the env clips its own copy), the same
  * outputs and the same auto-reset bookkeeping.  ppo_env_step on such a context returns PPO_ERR_UNSUPPORTED and names this call; this call returns
  * PPO_ERR_UNSUPPORTED on a context with integer actions and on PPO_ENV_HOST contexts. */
 PPO_API ppo_status ppo_env_step_f32(ppo_ctx* ctx, const float* action /* [N,D] */, float* obs, float* reward, int32_t* done);
 /* ppo_env_transition for PPO_ENV_PENDULUM (any other env_kind: PPO_ERR_UNSUPPORTED): stateless; state_in f32 [n,2], action f32 [n,D] (D = 1, raw);
- * outputs next_state [n,2], obs_out [n,3] = the observation of next_state or NULL, reward f32 [n], terminated i32 [n] (always 0). */
+ * outputs next_state [n,2], obs_out [n,3] = the observation of next_state or NULL, reward f32 [n], terminated i32 [n] (always 0).
+ * PPO_ENV_MOUNTAINCAR_CONTINUOUS: the same call with obs_out [n,2] (= next_state, bit for bit) or NULL and terminated as the step computes it (the goal
+ * reached with a velocity >= 0).  Null pointers (obs_out aside) or n < 0: PPO_ERR_INVALID; n = 0: PPO_OK, nothing is launched. */
 PPO_API ppo_status ppo_env_transition_f32(int32_t env_kind, const float* state_in, const float* action, int64_t n, float* next_state, float* obs_out,
                                           float* reward, int32_t* terminated, void* stream);
 /* Inject / read env state for teacher-forced parity: state_h [N,O] AoS, ep_len i32, ep_rew f32, reset_count i32 (NULL = skip). */
@@ -384,7 +412,7 @@ PPO_API ppo_status ppo_env_get_state_h(ppo_ctx* ctx, float* state_h, int32_t* ep
  * T x { store obs/done, policy forward + sample, store value/action/logprob, env step + auto-reset, store reward }.
  * forced_actions i64 [T,N,H] or NULL (teacher-forcing for parity).  Leaves NEXT_OBS / NEXT_DONE for the bootstrap. */
 PPO_API ppo_status ppo_rollout(ppo_ctx* ctx, const int64_t* forced_actions);
-/* ppo_rollout for Gaussian device-env contexts (PPO_ENV_PENDULUM): forced_actions f32 [T,N,D] or NULL; a forced action is stored in PPO_BUF_ACTIONS as given,
+/* ppo_rollout for Gaussian device-env contexts (PPO_ENV_PENDULUM, PPO_ENV_MOUNTAINCAR_CONTINUOUS): forced_actions f32 [T,N,D] or NULL; a forced action is stored in PPO_BUF_ACTIONS as given,
  * with the log-prob ppo_policy_act_f32 gives it, and steps the env.  ppo_rollout(ctx, NULL) on such a context is this call with NULL; ppo_rollout with a
  * non-NULL i64 array there returns PPO_ERR_UNSUPPORTED and names this call.  PPO_ERR_UNSUPPORTED on a categorical context and on PPO_ENV_HOST contexts. */
 PPO_API ppo_status ppo_rollout_f32(ppo_ctx* ctx, const float* forced_actions /* [T,N,D] or NULL */);
@@ -409,7 +437,12 @@ PPO_API ppo_status ppo_rollout_f32(ppo_ctx* ctx, const float* forced_actions /* 
  * Errors: PPO_ERR_UNSUPPORTED on a PPO_ENV_SYNTHETIC context (its observations are noise: an episode there has no last observation), on a PPO_ENV_PENDULUM
  * context (the fold rebuilds the final observation from PPO_BUF_OBS, and a Pendulum observation does not hold theta) and on a
  * PPO_ENV_HOST context (the message names ppo_host_observe_truncated); PPO_ERR_INVALID for `on` outside 0..1 (and a null count, or arrays shorter than the
- * list, in ppo_env_truncations).  A failing call changes nothing. */
+ * list, in ppo_env_truncations).  A failing call changes nothing.
+ * PPO_ENV_MOUNTAINCAR_CONTINUOUS (obs_size 2: the observation is the state there too) is served with the same contract, word for word, on the fused Gaussian
+ * critic: the fold is one launch of gauss_trunc_fold_kernel behind the rollout's two critic launches and in front of the scan; the step is recomputed from
+ * PPO_BUF_OBS[i] under the RAW f32 action PPO_BUF_ACTIONS[i, 0] with the env's own device function; v is bit for bit what ppo_get_value gives the final
+ * observation (gauss_values_kernel's forward); the grid covers the T * N rows in workgroups of 256, and the critic's weights are staged only by workgroups
+ * that found an event.  The fold launch is none of the kernels ppo_gauss_fused_launches counts. */
 PPO_API ppo_status ppo_env_truncation_bootstrap(ppo_ctx* ctx, int32_t on);   /* 0 off (default), 1 on */
 /* The events of the last ppo_rollout, with ppo_host_truncations' contract: count; flat indices t * N + n ascending (sorted on the host at read time); the
  * values V(final obs) that were folded in.  Before any rollout, and after a rollout with the switch off: count = 0.  index_h / value_h may be NULL (count
@@ -767,7 +800,13 @@ typedef struct ppo_eval_stats {
  *   gets the same answer).
  *   Errors: PPO_ENV_SYNTHETIC and PPO_ENV_HOST contexts -> PPO_ERR_UNSUPPORTED (step the episodes yourself around ppo_policy_act_greedy);
  *   PPO_ENV_PENDULUM contexts -> PPO_ERR_UNSUPPORTED (step the episodes through ppo_policy_act_f32 with greedy = 1 and ppo_env_transition_f32);
- *   n_episodes <= 0, out_h == NULL, max_episode_steps <= 0 -> PPO_ERR_INVALID.  A failing call changes nothing. */
+ *   n_episodes <= 0, out_h == NULL, max_episode_steps <= 0 -> PPO_ERR_INVALID.  A failing call changes nothing.
+ *   PPO_ENV_MOUNTAINCAR_CONTINUOUS: served, also as ONE launch (gauss_eval_kernel: a workgroup owns 64 episodes for their whole length, the actor's weights
+ *   resident in LDS, as in the rollout kernel).  Episode e starts at reset 0 of env e under `seed` (p = uniform(philox4x32_10(seed; e, 0, 0, 1).x, -0.6, -0.4),
+ *   v = 0).  greedy != 0: the action is the mean, bit for bit ppo_policy_act_f32 with greedy = 1; greedy == 0: mu + sigma * eps with eps keyed (seed, e, step t
+ *   within the episode, d = 0), bit for bit ppo_policy_act_f32(step_index = t) on row e of a context whose seed is `seed` and whose env_offset is 0.  The env
+ *   step, the f32 reward sum in step order, the end at termination or at max_episode_steps, the independence of how episodes are spread over workgroups and
+ *   everything about the outputs and the untouched training state (ppo_gauss_fused_launches included) are as above.  No reset table is needed. */
 PPO_API ppo_status ppo_evaluate(ppo_ctx* ctx, int64_t n_episodes, int64_t seed, int32_t greedy,
                                 float* ep_return /* dev f32[n] or NULL */, int32_t* ep_length /* dev i32[n] or NULL */,
                                 ppo_eval_stats* out_h);

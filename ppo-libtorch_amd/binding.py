@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("PPO_HIP_LIBRARY") or os.path.join(_HERE, "libppo_hip.
 
 MAX_HEADS = 8
 ENV_CARTPOLE, ENV_MOUNTAINCAR, ENV_SYNTHETIC, ENV_HOST, ENV_PENDULUM = 0, 1, 2, 3, 4   # ENV_PENDULUM: Pendulum-v1 on the device, DIST_GAUSSIAN + KERNEL_GAUSS_FUSED only
+ENV_MOUNTAINCAR_CONTINUOUS = 5   # MountainCarContinuous-v0 on the device, in the same one form; obs = state [2]; also env_truncation_bootstrap and evaluate
 MM_EPI_NONE, MM_EPI_BIAS, MM_EPI_BIAS_TANH, MM_EPI_DTANH = 0, 1, 2, 3
 MM_F32X3, MM_BF16 = 0, 1
 DIST_CATEGORICAL, DIST_MASKED, DIST_GAUSSIAN = 0, 1, 2   # DIST_GAUSSIAN: f32 actions [.., D], the *_f32 calls (include/ppo_hip.h PPO_DIST_GAUSSIAN)
@@ -371,7 +372,8 @@ class Context:
         return out
 
     def evaluate(self, n_episodes, seed, greedy=True):
-        """ppo_evaluate: n_episodes whole episodes of the context's device env under the current policy in one launch.
+        """ppo_evaluate: n_episodes whole episodes of the context's device env (CartPole, MountainCar, ENV_MOUNTAINCAR_CONTINUOUS) under the current policy in
+        one launch.
         Returns (stats dict, returns f32 [n], lengths i32 [n])."""
         n = int(n_episodes)
         d_r = self.empty(max(n, 1), np.float32)
@@ -398,7 +400,7 @@ class Context:
         return d_o.download(), d_r.download(), d_d.download()
 
     def env_step_f32(self, action):
-        """ppo_env_step_f32 (ENV_PENDULUM): action f32 [N,D], the raw action (the env clips its own copy).  Returns (obs [N,O], reward [N], done i32 [N])."""
+        """ppo_env_step_f32 (ENV_PENDULUM, ENV_MOUNTAINCAR_CONTINUOUS): action f32 [N,D], the raw action (the env clips its own copy).  Returns (obs [N,O], reward [N], done i32 [N])."""
         tmp = [self.dev(np.asarray(action, np.float32).reshape(self.N, self.A)), self.empty((self.N, self.O), np.float32), self.empty(self.N, np.float32),
                self.empty(self.N, np.int32)]
         try:
@@ -421,7 +423,7 @@ class Context:
         return s, l, r, k
 
     def env_truncation_bootstrap(self, on=True):
-        """ppo_env_truncation_bootstrap: with the switch on, a rollout of the context's own env (CartPole, MountainCar) folds gamma * V(final observation)
+        """ppo_env_truncation_bootstrap: with the switch on, a rollout of the context's own env (CartPole, MountainCar, ENV_MOUNTAINCAR_CONTINUOUS) folds gamma * V(final observation)
         into REWARDS where the time limit cut an episode off.  Off by default."""
         _check(lib().ppo_env_truncation_bootstrap(self.h, int(on)), self.h)
 
@@ -818,10 +820,12 @@ def env_transition(ctx, env_kind, state, action):
 
 
 def env_transition_f32(ctx, env_kind, state, action, want_obs=True):
-    """ppo_env_transition_f32 (ENV_PENDULUM): state f32 [n,2], action f32 [n,1] raw.  Returns (next_state, obs [n,3] or None, reward, terminated)."""
+    """ppo_env_transition_f32 (ENV_PENDULUM, ENV_MOUNTAINCAR_CONTINUOUS): state f32 [n,2], action f32 [n,1] raw.  Returns (next_state, obs or None, reward,
+    terminated); obs is [n,3] for ENV_PENDULUM and [n,2] (the next state) for ENV_MOUNTAINCAR_CONTINUOUS."""
     state = np.ascontiguousarray(state, np.float32)
     n, S = state.shape
-    tmp = [ctx.dev(state), ctx.dev(np.asarray(action, np.float32).reshape(n, -1)), ctx.empty((n, S), np.float32), ctx.empty((n, 3), np.float32),
+    O = 3 if env_kind == ENV_PENDULUM else S
+    tmp = [ctx.dev(state), ctx.dev(np.asarray(action, np.float32).reshape(n, -1)), ctx.empty((n, S), np.float32), ctx.empty((n, O), np.float32),
            ctx.empty(n, np.float32), ctx.empty(n, np.int32)]
     try:
         _check(lib().ppo_env_transition_f32(C.c_int32(env_kind), tmp[0].ptr, tmp[1].ptr, C.c_int64(n), tmp[2].ptr, tmp[3].ptr if want_obs else None, tmp[4].ptr,

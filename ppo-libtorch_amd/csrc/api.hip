@@ -567,14 +567,18 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
     // PPO_ENV_PENDULUM: the device env of the fused Gaussian kernels; the network lives in the generic engine's layout (GenericCtx), as a PPO_ENV_HOST
     // context with PPO_KERNEL_GAUSS_FUSED does, and only the rollout differs (gauss_rollout_kernel)
     const bool pendulum = cfg->env_kind == PPO_ENV_PENDULUM;
-    const bool generic = cfg->env_kind == PPO_ENV_SYNTHETIC || (host_env && !host_ref) || pendulum;
+    // PPO_ENV_MOUNTAINCAR_CONTINUOUS: the second such env, the same kernels instantiated for it (its observation is its state: it also has the truncation fold
+    // and the evaluation launch)
+    const bool mcc = cfg->env_kind == PPO_ENV_MOUNTAINCAR_CONTINUOUS;
+    const bool gauss_env = pendulum || mcc;
+    const bool generic = cfg->env_kind == PPO_ENV_SYNTHETIC || (host_env && !host_ref) || gauss_env;
     if (!generic && (cfg->hidden != PPO_HIDDEN || cfg->n_hidden != 2))
         return fail(nullptr, PPO_ERR_UNSUPPORTED, "only the reference architecture (2 hidden layers of 64, Agent.cpp:25-59) is built for the reference's "
                     "environments; got %d x %d (other shapes run with env_kind = PPO_ENV_SYNTHETIC)", cfg->n_hidden, cfg->hidden);
-    if (generic && !pendulum && (cfg->hidden < 1 || cfg->hidden > 2048 || cfg->n_hidden < 1 || cfg->n_hidden > GEN_MAX_LAYERS - 1 || cfg->obs_size < 1 || cfg->obs_size > 8192))
+    if (generic && !gauss_env && (cfg->hidden < 1 || cfg->hidden > 2048 || cfg->n_hidden < 1 || cfg->n_hidden > GEN_MAX_LAYERS - 1 || cfg->obs_size < 1 || cfg->obs_size > 8192))
         return fail(nullptr, PPO_ERR_UNSUPPORTED, "generic network out of range: hidden %d (1..2048), n_hidden %d (1..%d), obs %d (1..8192)", cfg->hidden,
                     cfg->n_hidden, GEN_MAX_LAYERS - 1, cfg->obs_size);
-    if (cfg->env_kind != PPO_ENV_CARTPOLE && cfg->env_kind != PPO_ENV_MOUNTAINCAR && cfg->env_kind != PPO_ENV_SYNTHETIC && cfg->env_kind != PPO_ENV_HOST && !pendulum)
+    if (cfg->env_kind != PPO_ENV_CARTPOLE && cfg->env_kind != PPO_ENV_MOUNTAINCAR && cfg->env_kind != PPO_ENV_SYNTHETIC && cfg->env_kind != PPO_ENV_HOST && !gauss_env)
         return fail(nullptr, PPO_ERR_INVALID, "unknown env_kind %d", cfg->env_kind);
     if (cfg->dist_kind != PPO_DIST_CATEGORICAL && cfg->dist_kind != PPO_DIST_MASKED && !gauss) return fail(nullptr, PPO_ERR_INVALID, "unknown dist_kind %d", cfg->dist_kind);
     if (cfg->compute_dtype != PPO_DTYPE_F32 && cfg->compute_dtype != PPO_DTYPE_BF16) return fail(nullptr, PPO_ERR_INVALID, "unknown compute_dtype %d", cfg->compute_dtype);
@@ -599,9 +603,30 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
                             "sinf / cosf hold for |theta| < 120); got %d", PENDULUM_MAX_EPISODE_STEPS, cfg->max_episode_steps);
         }
     }
-    if (gauss && !host_env && !pendulum)
-        return fail(nullptr, PPO_ERR_UNSUPPORTED, "dist_kind = PPO_DIST_GAUSSIAN serves caller-stepped environments (env_kind = PPO_ENV_HOST) and PPO_ENV_PENDULUM: CartPole, MountainCar and "
-                    "the synthetic env take discrete actions; got env_kind %d", cfg->env_kind);
+    if (mcc) {   // accepted in exactly one form (ppo_hip.h: PPO_ENV_MOUNTAINCAR_CONTINUOUS); a wrong obs_size first, with the reference's message (below)
+        if (cfg->obs_size == 2) {
+            if (!gauss)
+                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_MOUNTAINCAR_CONTINUOUS takes one real-valued action: it is built for dist_kind = PPO_DIST_GAUSSIAN; "
+                            "got dist_kind %d", cfg->dist_kind);
+            if (cfg->n_heads != 1 || cfg->head_dims[0] != 1)
+                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_MOUNTAINCAR_CONTINUOUS has one action dimension, the force: n_heads = 1 and head_dims[0] = 1; got "
+                            "n_heads = %d, head_dims[0] = %d", cfg->n_heads, cfg->head_dims[0]);
+            if (cfg->hidden != 64 || cfg->n_hidden != 2)
+                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_MOUNTAINCAR_CONTINUOUS is built for the 2 x 64 network (hidden = 64, n_hidden = 2) of the fused "
+                            "Gaussian kernels; got %d x %d", cfg->n_hidden, cfg->hidden);
+            if (cfg->compute_dtype != PPO_DTYPE_F32)
+                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_MOUNTAINCAR_CONTINUOUS is built for compute_dtype = PPO_DTYPE_F32; bf16 storage is not");
+            if (!(cfg->kernel_flags & PPO_KERNEL_GAUSS_FUSED))
+                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_MOUNTAINCAR_CONTINUOUS needs PPO_KERNEL_GAUSS_FUSED in kernel_flags: its rollout exists on the fused "
+                            "Gaussian kernels only, and the flag is never implied (no other engine serves in its place)");
+            if (cfg->max_episode_steps < 1)
+                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_MOUNTAINCAR_CONTINUOUS is built for max_episode_steps >= 1 (an episode that never reaches the goal "
+                            "ends at the time limit only); got %d", cfg->max_episode_steps);
+        }
+    }
+    if (gauss && !host_env && !gauss_env)
+        return fail(nullptr, PPO_ERR_UNSUPPORTED, "dist_kind = PPO_DIST_GAUSSIAN serves caller-stepped environments (env_kind = PPO_ENV_HOST), PPO_ENV_PENDULUM and "
+                    "PPO_ENV_MOUNTAINCAR_CONTINUOUS: CartPole, MountainCar and the synthetic env take discrete actions; got env_kind %d", cfg->env_kind);
     if (gauss && cfg->compute_dtype != PPO_DTYPE_F32)
         return fail(nullptr, PPO_ERR_UNSUPPORTED, "dist_kind = PPO_DIST_GAUSSIAN is built for compute_dtype = PPO_DTYPE_F32; bf16 storage is not");
     if (gauss && cfg->n_heads != 1)
@@ -610,7 +635,7 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
     if (cfg->compute_dtype == PPO_DTYPE_BF16 && !generic)
         return fail(nullptr, PPO_ERR_UNSUPPORTED, "compute_dtype = PPO_DTYPE_BF16 applies to networks whose layers are GEMMs (env_kind = PPO_ENV_SYNTHETIC); the reference's "
                     "2 x 64 networks always compute in f32");
-    const int env_obs = cfg->env_kind == PPO_ENV_CARTPOLE ? 4 : (cfg->env_kind == PPO_ENV_MOUNTAINCAR ? 2 : (pendulum ? 3 : cfg->obs_size));   // host / synthetic: no check
+    const int env_obs = cfg->env_kind == PPO_ENV_CARTPOLE ? 4 : (cfg->env_kind == PPO_ENV_MOUNTAINCAR || mcc ? 2 : (pendulum ? 3 : cfg->obs_size));   // host / synthetic: no check
     if (cfg->obs_size != env_obs) {
         // the reference's runtime check in initEnvs (PPO_Discrete.cpp:370-375), same wording
         return fail(nullptr, PPO_ERR_INVALID,
@@ -1262,20 +1287,24 @@ static ppo_status host_env_refuses(ppo_ctx* c, const char* what) {
 }
 
 static inline bool is_pendulum(const ppo_ctx* c) { return c->cfg.env_kind == PPO_ENV_PENDULUM; }
+static inline bool is_mcc(const ppo_ctx* c) { return c->cfg.env_kind == PPO_ENV_MOUNTAINCAR_CONTINUOUS; }
+// the device envs with real-valued actions: the env of the fused Gaussian rollout (gauss_fused.hpp)
+static inline bool is_gauss_env(const ppo_ctx* c) { return is_pendulum(c) || is_mcc(c); }
+static inline const char* gauss_env_name(const ppo_ctx* c) { return is_mcc(c) ? "PPO_ENV_MOUNTAINCAR_CONTINUOUS" : "PPO_ENV_PENDULUM"; }
 
 extern "C" ppo_status ppo_env_transition_f32(int32_t env_kind, const float* state_in, const float* action, int64_t n, float* next_state, float* obs_out,
                                              float* reward, int32_t* terminated, void* stream) {
     if (!state_in || !action || !next_state || !reward || !terminated || n < 0) return PPO_ERR_INVALID;
-    if (env_kind != PPO_ENV_PENDULUM) return PPO_ERR_UNSUPPORTED;   // the envs with integer actions: ppo_env_transition
-    return launch_pendulum_transition(state_in, action, n, next_state, obs_out, reward, terminated, (hipStream_t)stream) == hipSuccess ? PPO_OK : PPO_ERR_HIP;
+    if (env_kind != PPO_ENV_PENDULUM && env_kind != PPO_ENV_MOUNTAINCAR_CONTINUOUS) return PPO_ERR_UNSUPPORTED;   // the envs with integer actions: ppo_env_transition
+    return launch_gauss_env_transition(env_kind, state_in, action, n, next_state, obs_out, reward, terminated, (hipStream_t)stream) == hipSuccess ? PPO_OK : PPO_ERR_HIP;
 }
 
 extern "C" ppo_status ppo_env_reset(ppo_ctx* c) {
     NEED(c, c != nullptr, "null ctx");
     if (c->host_env) return host_env_refuses(c, "ppo_env_reset");
     DeviceGuard dev_guard(c);
-    if (is_pendulum(c)) {
-        HIPCHK(c, launch_pendulum_reset(c->N, c->cfg.seed, c->cfg.env_offset, B_<float>(c, PPO_BUF_ENV_STATE), B_<int32_t>(c, PPO_BUF_EP_LEN), B_<float>(c, PPO_BUF_EP_REW),
+    if (is_gauss_env(c)) {
+        HIPCHK(c, launch_gauss_env_reset(c->cfg.env_kind, c->N, c->cfg.seed, c->cfg.env_offset, B_<float>(c, PPO_BUF_ENV_STATE), B_<int32_t>(c, PPO_BUF_EP_LEN), B_<float>(c, PPO_BUF_EP_REW),
                                         B_<int32_t>(c, PPO_BUF_RESET_COUNT), B_<float>(c, PPO_BUF_NEXT_OBS), B_<int32_t>(c, PPO_BUF_NEXT_DONE), c->stream));
         return PPO_OK;
     }
@@ -1296,7 +1325,7 @@ extern "C" ppo_status ppo_env_reset(ppo_ctx* c) {
 extern "C" ppo_status ppo_env_step(ppo_ctx* c, const int64_t* action, float* obs, float* reward, int32_t* done) {
     NEED(c, c && action && obs && reward && done, "null argument");
     if (c->host_env) return host_env_refuses(c, "ppo_env_step");
-    if (is_pendulum(c)) return fail(c, PPO_ERR_UNSUPPORTED, "ppo_env_step: this context's env (PPO_ENV_PENDULUM) takes real-valued actions f32 [N, D]; call ppo_env_step_f32");
+    if (is_gauss_env(c)) return fail(c, PPO_ERR_UNSUPPORTED, "ppo_env_step: this context's env (%s) takes real-valued actions f32 [N, D]; call ppo_env_step_f32", gauss_env_name(c));
     DeviceGuard dev_guard(c);
     if (c->gen) {   // synthetic env: one step at the context's global step counter (the action does not influence it)
         HIPCHK(c, gen_synthetic_step(c->gen->L, c->N, c->cfg.seed, c->cfg.env_offset, c->rollout_steps, c->cfg.max_episode_steps,
@@ -1313,15 +1342,15 @@ extern "C" ppo_status ppo_env_step(ppo_ctx* c, const int64_t* action, float* obs
 extern "C" ppo_status ppo_env_step_f32(ppo_ctx* c, const float* action, float* obs, float* reward, int32_t* done) {
     NEED(c, c && action && obs && reward && done, "null argument");
     if (c->host_env) return host_env_refuses(c, "ppo_env_step_f32");
-    if (!is_pendulum(c))
+    if (!is_gauss_env(c))
         return fail(c, PPO_ERR_UNSUPPORTED, "ppo_env_step_f32: this context's env (env_kind %d) takes integer actions i64 [N, H]; call ppo_env_step", c->cfg.env_kind);
     DeviceGuard dev_guard(c);
-    HIPCHK(c, launch_pendulum_step(c->N, c->cfg.max_episode_steps, c->cfg.seed, c->cfg.env_offset, B_<float>(c, PPO_BUF_ENV_STATE), B_<int32_t>(c, PPO_BUF_EP_LEN),
+    HIPCHK(c, launch_gauss_env_step(c->cfg.env_kind, c->N, c->cfg.max_episode_steps, c->cfg.seed, c->cfg.env_offset, B_<float>(c, PPO_BUF_ENV_STATE), B_<int32_t>(c, PPO_BUF_EP_LEN),
                                    B_<float>(c, PPO_BUF_EP_REW), B_<int32_t>(c, PPO_BUF_RESET_COUNT), action, obs, reward, done, c->stream));
     return PPO_OK;
 }
 
-// the env state's width: the observation IS the state for CartPole and MountainCar; Pendulum keeps (theta, theta_dot) behind a 3-wide observation
+// the env state's width: the observation IS the state for CartPole and both MountainCars; Pendulum keeps (theta, theta_dot) behind a 3-wide observation
 static inline int env_state_dim(const ppo_ctx* c) { return is_pendulum(c) ? 2 : c->O; }
 
 extern "C" ppo_status ppo_env_set_state_h(ppo_ctx* c, const float* state_h, const int32_t* ep_len_h, const float* ep_rew_h, const int32_t* reset_count_h) {
@@ -1332,7 +1361,7 @@ extern "C" ppo_status ppo_env_set_state_h(ppo_ctx* c, const float* state_h, cons
         ppo_status s = ppo_memcpy_h2d(c, c->scratch_obs, state_h, (size_t)c->N * S * sizeof(float));
         if (s != PPO_OK) return s;
         HIPCHK(c, launch_aos_to_soa(c->scratch_obs, B_<float>(c, PPO_BUF_ENV_STATE), c->N, S, true, c->stream));
-        if (is_pendulum(c)) HIPCHK(c, launch_pendulum_obs(c->N, B_<float>(c, PPO_BUF_ENV_STATE), B_<float>(c, PPO_BUF_NEXT_OBS), c->stream));
+        if (is_pendulum(c)) HIPCHK(c, launch_gauss_env_obs(c->cfg.env_kind, c->N, B_<float>(c, PPO_BUF_ENV_STATE), B_<float>(c, PPO_BUF_NEXT_OBS), c->stream));
         else HIPCHK(c, hipMemcpyAsync(c->buf[PPO_BUF_NEXT_OBS], c->scratch_obs, (size_t)c->N * c->O * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     }
     ppo_status s = PPO_OK;
@@ -1436,8 +1465,31 @@ static ppo_status env_fold_truncations(ppo_ctx* c) {
     return PPO_OK;
 }
 
-// PPO_ENV_PENDULUM: gauss_rollout_kernel (all T steps), then gen_rollout's tail -- the critic over the stored observations and over NEXT_OBS: three launches
-static ppo_status pendulum_rollout(ppo_ctx* c, const float* forced) {
+// ppo_env_truncation_bootstrap's launch on PPO_ENV_MOUNTAINCAR_CONTINUOUS: env_fold_truncations on the fused Gaussian critic, the one gen_values fills
+// PPO_BUF_VALUES with (gauss_fused.hpp: GaussFoldArgs).  None of the launches ppo_gauss_fused_launches counts.
+static ppo_status gauss_env_fold_truncations(ppo_ctx* c) {
+    GaussFoldArgs f{};
+    f.params = B_<float>(c, PPO_BUF_PARAMS);
+    f.obs = B_<float>(c, PPO_BUF_OBS);
+    f.actions = B_<float>(c, PPO_BUF_ACTIONS);
+    f.fin_len = B_<int32_t>(c, PPO_BUF_FIN_LEN);
+    f.B = c->B;
+    f.max_episode_steps = c->cfg.max_episode_steps;
+    f.gamma = c->cfg.gamma;
+    f.rewards = B_<float>(c, PPO_BUF_REWARDS);
+    f.ev_count = c->envt_count; f.ev_index = c->envt_index; f.ev_value = c->envt_value; f.ev_cap = c->B;
+    HIPCHK(c, hipMemsetAsync(c->envt_count, 0, sizeof(int32_t), c->stream));
+    HIPCHK(c, gauss_fused_trunc_fold(c->cfg.env_kind, c->gen->L, f, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->envt_count_h, c->envt_count, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipEventRecord(c->envt_ev, c->stream));
+    c->envt_last = true;
+    c->envt_fetched = false;
+    return PPO_OK;
+}
+
+// PPO_ENV_PENDULUM, PPO_ENV_MOUNTAINCAR_CONTINUOUS: gauss_rollout_kernel (all T steps), then gen_rollout's tail -- the critic over the stored observations and
+// over NEXT_OBS: three launches; with ppo_env_truncation_bootstrap on (the second env only), the fold behind them
+static ppo_status gauss_env_rollout(ppo_ctx* c, const float* forced) {
     ppo_status s = consume_finished_episodes(c);
     if (s != PPO_OK) return s;
     GaussRolloutArgs r{};
@@ -1460,10 +1512,15 @@ static ppo_status pendulum_rollout(ppo_ctx* c, const float* forced) {
     r.forced = forced;
     {
         ProfScope ps(c, PROF_ROLLOUT);
-        HIPCHK(c, gauss_fused_rollout(c->gen->L, r, c->stream));
+        HIPCHK(c, gauss_fused_rollout(c->cfg.env_kind, c->gen->L, r, c->stream));
         s = gen_values(c, r.obs, (int64_t)c->T * c->N, B_<float>(c, PPO_BUF_VALUES));
         if (s == PPO_OK) s = gen_values(c, r.next_obs, c->N, B_<float>(c, PPO_BUF_NEXT_VALUE));
         if (s != PPO_OK) return s;
+        c->envt_last = false;
+        if (c->envt_on) {   // behind the two critic launches, in front of the scan (envt_on is never set on a Pendulum context: envt_state)
+            s = gauss_env_fold_truncations(c);
+            if (s != PPO_OK) return s;
+        }
     }
     c->rollout_steps += c->T;
     c->global_step += (int64_t)c->T * c->cfg.global_num_envs;
@@ -1476,16 +1533,16 @@ extern "C" ppo_status ppo_rollout_f32(ppo_ctx* c, const float* forced_actions) {
     if (c->host_env) return host_env_refuses(c, "ppo_rollout_f32");
     if (!is_gauss(c)) return wrong_action_type(c, "ppo_rollout_f32", "ppo_rollout");
     DeviceGuard dev_guard(c);
-    return pendulum_rollout(c, forced_actions);   // a Gaussian context with a device env is a PPO_ENV_PENDULUM context (ppo_ctx_create)
+    return gauss_env_rollout(c, forced_actions);   // a Gaussian context with a device env is one of the two envs of the fused rollout (ppo_ctx_create)
 }
 
 extern "C" ppo_status ppo_rollout(ppo_ctx* c, const int64_t* forced_actions) {
     NEED(c, c != nullptr, "null ctx");
     if (c->host_env) return host_env_refuses(c, "ppo_rollout");
-    if (is_pendulum(c)) {
+    if (is_gauss_env(c)) {
         if (forced_actions) return wrong_action_type(c, "ppo_rollout with forced actions", "ppo_rollout_f32");
         DeviceGuard dev_guard(c);
-        return pendulum_rollout(c, nullptr);
+        return gauss_env_rollout(c, nullptr);
     }
     DeviceGuard dev_guard(c);
     ppo_status s = consume_finished_episodes(c);
@@ -1589,23 +1646,9 @@ static ppo_status eval_scratch(ppo_ctx* c, int64_t n, int64_t seed) {
     return PPO_OK;
 }
 
-extern "C" ppo_status ppo_evaluate(ppo_ctx* c, int64_t n_episodes, int64_t seed, int32_t greedy, float* ep_return, int32_t* ep_length, ppo_eval_stats* out_h) {
-    NEED(c, c != nullptr, "null ctx");
-    if (is_pendulum(c))
-        return fail(c, PPO_ERR_UNSUPPORTED, "ppo_evaluate is not built for PPO_ENV_PENDULUM: step the episodes through ppo_policy_act_f32 with greedy = 1 and "
-                                            "ppo_env_transition_f32");
-    if (c->host_env || c->gen || c->cfg.env_kind == PPO_ENV_SYNTHETIC)
-        return fail(c, PPO_ERR_UNSUPPORTED, "ppo_evaluate steps the context's device environment (CartPole, MountainCar); this context's environment is %s: "
-                                            "run the episodes on the host with one ppo_policy_act_greedy launch per step",
-                    c->host_env ? "the caller's (PPO_ENV_HOST)" : "synthetic (PPO_ENV_SYNTHETIC)");
-    NEED(c, out_h != nullptr, "ppo_evaluate: out_h is null");
-    NEED(c, n_episodes > 0, "ppo_evaluate: n_episodes <= 0");
-    NEED(c, n_episodes < (1ll << 28), "ppo_evaluate: more than 2^28 episodes");
-    NEED(c, c->cfg.max_episode_steps > 0, "ppo_evaluate: max_episode_steps <= 0 (an episode would never be truncated)");
-    NEED(c, c->O == (c->cfg.env_kind == PPO_ENV_CARTPOLE ? 4 : 2), "ppo_evaluate: obs_size does not match the environment");
-    DeviceGuard dev_guard(c);
-    ppo_status s = eval_scratch(c, n_episodes, seed);
-    if (s != PPO_OK) return s;
+// ppo_evaluate's launch on CartPole / MountainCar (kernels_rollout.hip: eval16_kernel / evalv_kernel)
+static ppo_status eval_launch_categorical(ppo_ctx* c, int64_t n_episodes, int64_t seed, int32_t greedy) {
+    ppo_status s = PPO_OK;
     EvalArgs a{};
     a.params = B_<float>(c, PPO_BUF_PARAMS);
     a.L = c->L;
@@ -1631,6 +1674,39 @@ extern "C" ppo_status ppo_evaluate(ppo_ctx* c, int64_t n_episodes, int64_t seed,
         if (!(w3 < WR_LIMIT_W3)) a.vector_kernel = 1;
     }
     HIPCHK(c, launch_evaluate(a, c->stream));
+    return PPO_OK;
+}
+
+extern "C" ppo_status ppo_evaluate(ppo_ctx* c, int64_t n_episodes, int64_t seed, int32_t greedy, float* ep_return, int32_t* ep_length, ppo_eval_stats* out_h) {
+    NEED(c, c != nullptr, "null ctx");
+    if (is_pendulum(c))
+        return fail(c, PPO_ERR_UNSUPPORTED, "ppo_evaluate is not built for PPO_ENV_PENDULUM: step the episodes through ppo_policy_act_f32 with greedy = 1 and "
+                                            "ppo_env_transition_f32");
+    const bool gauss_env = is_mcc(c);   // the episodes run on the fused Gaussian kernels (gauss_eval_kernel); everything on the host side is shared
+    if (c->host_env || (c->gen && !gauss_env) || c->cfg.env_kind == PPO_ENV_SYNTHETIC)
+        return fail(c, PPO_ERR_UNSUPPORTED, "ppo_evaluate steps the context's device environment (CartPole, MountainCar); this context's environment is %s: "
+                                            "run the episodes on the host with one ppo_policy_act_greedy launch per step",
+                    c->host_env ? "the caller's (PPO_ENV_HOST)" : "synthetic (PPO_ENV_SYNTHETIC)");
+    NEED(c, out_h != nullptr, "ppo_evaluate: out_h is null");
+    NEED(c, n_episodes > 0, "ppo_evaluate: n_episodes <= 0");
+    NEED(c, n_episodes < (1ll << 28), "ppo_evaluate: more than 2^28 episodes");
+    NEED(c, c->cfg.max_episode_steps > 0, "ppo_evaluate: max_episode_steps <= 0 (an episode would never be truncated)");
+    NEED(c, c->O == (c->cfg.env_kind == PPO_ENV_CARTPOLE ? 4 : 2), "ppo_evaluate: obs_size does not match the environment");
+    DeviceGuard dev_guard(c);
+    ppo_status s = eval_scratch(c, n_episodes, seed);
+    if (s != PPO_OK) return s;
+    if (gauss_env) {
+        GaussEvalArgs g{};
+        g.params = B_<float>(c, PPO_BUF_PARAMS);
+        g.n_episodes = n_episodes; g.seed = seed;
+        g.max_episode_steps = c->cfg.max_episode_steps;
+        g.greedy = greedy != 0;
+        g.ep_return = c->eval_ret; g.ep_length = c->eval_len; g.ep_trunc = c->eval_len + c->eval_cap;
+        HIPCHK(c, gauss_fused_evaluate(c->cfg.env_kind, c->gen->L, g, c->stream));
+    } else {
+        s = eval_launch_categorical(c, n_episodes, seed, greedy);
+        if (s != PPO_OK) return s;
+    }
     if (ep_return) HIPCHK(c, hipMemcpyAsync(ep_return, c->eval_ret, (size_t)n_episodes * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     if (ep_length) HIPCHK(c, hipMemcpyAsync(ep_length, c->eval_len, (size_t)n_episodes * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
     std::vector<float> ret((size_t)n_episodes);
@@ -2969,6 +3045,7 @@ static ppo_status envt_state(ppo_ctx* c, const char* what) {
     if (is_pendulum(c))
         return fail(c, PPO_ERR_UNSUPPORTED, "%s: the fold rebuilds the final observation of a cut-off episode from PPO_BUF_OBS, and a PPO_ENV_PENDULUM observation "
                                             "(cos, sin, theta_dot) does not hold theta: not built for this env", what);
+    if (is_mcc(c)) return PPO_OK;   // its observation is its state: the fold runs on the fused Gaussian critic (gauss_env_fold_truncations)
     if (c->cfg.env_kind != PPO_ENV_CARTPOLE && c->cfg.env_kind != PPO_ENV_MOUNTAINCAR)
         return fail(c, PPO_ERR_UNSUPPORTED, "%s: the synthetic env's observations are noise: an episode there has no last observation to bootstrap from", what);
     return PPO_OK;

@@ -23,8 +23,9 @@ hipError_t gauss_fused_fwd_bwd(const GenLayout& L, const LossParams& hp, const f
                                const float* adv, const float* ret, const float* oldv, const int32_t* idx, int64_t M, double inv_global_M, double global_M,
                                const AdvStat* adv_stat, float* slab, double* loss_part, float* grads, hipStream_t s);
 
-// PPO_ENV_PENDULUM: the T steps of a rollout in one launch (gauss_rollout_kernel: one workgroup per 64 envs, the actor's weights resident, the env in wave 0's
-// registers); the context's buffers, the teacher-forcing actions f32 [T, N, 1] or null.  The critic is not in it: two gauss_fused_values launches follow.
+// The device envs with real-valued actions (PPO_ENV_PENDULUM, PPO_ENV_MOUNTAINCAR_CONTINUOUS; the traits are ppo_internal.hpp's GaussEnv*): the T steps of a
+// rollout in one launch (gauss_rollout_kernel<Env>: one workgroup per 64 envs, the actor's weights resident, the env in wave 0's registers); the context's
+// buffers, the teacher-forcing actions f32 [T, N, 1] or null.  The critic is not in it: two gauss_fused_values launches follow.
 struct GaussRolloutArgs {
     const float* params;
     int N, T, max_episode_steps;
@@ -34,12 +35,48 @@ struct GaussRolloutArgs {
     float* next_obs; int32_t* next_done;
     const float* forced;
 };
-hipError_t gauss_fused_rollout(const GenLayout& L, const GaussRolloutArgs& r, hipStream_t s);
-// Pendulum's stand-alone env kernels, one thread per env, on the rollout kernel's device functions (ppo_internal.hpp: pendulum_step, pendulum_reset)
-hipError_t launch_pendulum_reset(int N, int64_t seed, int64_t env_offset, float* env_state, int32_t* ep_len, float* ep_rew, int32_t* reset_count, float* next_obs,
-                                 int32_t* next_done, hipStream_t s);
-hipError_t launch_pendulum_step(int N, int max_episode_steps, int64_t seed, int64_t env_offset, float* env_state, int32_t* ep_len, float* ep_rew,
-                                int32_t* reset_count, const float* action, float* obs, float* reward, int32_t* done, hipStream_t s);
-hipError_t launch_pendulum_transition(const float* state_in, const float* action, int64_t n, float* next_state, float* obs_out, float* reward, int32_t* terminated,
-                                      hipStream_t s);
-hipError_t launch_pendulum_obs(int N, const float* env_state, float* next_obs, hipStream_t s);
+// by env kind: the launcher is a template over the trait like the kernel (hipErrorInvalidValue for an env without one)
+hipError_t gauss_fused_rollout(int env_kind, const GenLayout& L, const GaussRolloutArgs& r, hipStream_t s);
+// The envs' stand-alone kernels, one thread per env, on the rollout kernel's device functions (ppo_internal.hpp: GaussEnv*)
+hipError_t launch_gauss_env_reset(int env_kind, int N, int64_t seed, int64_t env_offset, float* env_state, int32_t* ep_len, float* ep_rew, int32_t* reset_count,
+                                  float* next_obs, int32_t* next_done, hipStream_t s);
+hipError_t launch_gauss_env_step(int env_kind, int N, int max_episode_steps, int64_t seed, int64_t env_offset, float* env_state, int32_t* ep_len, float* ep_rew,
+                                 int32_t* reset_count, const float* action, float* obs, float* reward, int32_t* done, hipStream_t s);
+hipError_t launch_gauss_env_transition(int env_kind, const float* state_in, const float* action, int64_t n, float* next_state, float* obs_out, float* reward,
+                                       int32_t* terminated, hipStream_t s);
+hipError_t launch_gauss_env_obs(int env_kind, int N, const float* env_state, float* next_obs, hipStream_t s);
+
+// ppo_env_truncation_bootstrap on a Gaussian device env whose observation is its state (PPO_ENV_MOUNTAINCAR_CONTINUOUS): ONE launch over the B = T * N stored
+// samples (gauss_trunc_fold_kernel).  For every i with fin_len[i] == max_episode_steps the last transition is recomputed from obs[i] under actions[i] (f32, the
+// raw action) with the env's own step; where the env terminated nothing happens, elsewhere v = Critic(final observation) -- gauss_values_kernel's forward, bit
+// for bit -- is folded into rewards[i] (fold_store: two roundings) and (i, v) joins the event list.  A workgroup (256 samples) without such a row costs one
+// pass over fin_len; the critic's weights are staged only by workgroups that found one.
+struct GaussFoldArgs {
+    const float* params;
+    const float* obs;           // PPO_BUF_OBS [B, O]
+    const float* actions;       // PPO_BUF_ACTIONS f32 [B, 1]
+    const int32_t* fin_len;     // PPO_BUF_FIN_LEN [B]
+    int64_t B;
+    int max_episode_steps;      // > 0
+    float gamma;
+    float* rewards;             // PPO_BUF_REWARDS [B]
+    int32_t* ev_count;          // the context's event list, cleared in front of the launch
+    int32_t* ev_index;
+    float* ev_value;
+    int64_t ev_cap;
+};
+hipError_t gauss_fused_trunc_fold(int env_kind, const GenLayout& L, const GaussFoldArgs& a, hipStream_t s);
+
+// ppo_evaluate on such an env: n_episodes whole episodes as ONE launch (gauss_eval_kernel: a workgroup owns 64 episodes, the actor's weights resident; episode
+// e starts at reset 0 of env e under `seed`; greedy: the mean, else mu + sigma * eps keyed (seed, e, step of the episode, 0)); only the return (f32 sum in step
+// order), the length and the truncated flag (the length reached max_episode_steps) leave the chip.
+struct GaussEvalArgs {
+    const float* params;
+    int64_t n_episodes, seed;
+    int max_episode_steps;      // >= 1
+    int greedy;
+    float* ep_return;           // [n_episodes]
+    int32_t* ep_length;
+    int32_t* ep_trunc;
+};
+hipError_t gauss_fused_evaluate(int env_kind, const GenLayout& L, const GaussEvalArgs& a, hipStream_t s);

@@ -12,9 +12,11 @@
 //   obs 64, D 32 (the largest shape served): 4096 + 4096 + 2048 + 288 + 4352 + 4352 + 4352 + 2176 = 25 760 floats = 103 040 bytes of 163 840.
 //   obs 17, D 6: 1280 + 4096 + 512 + 288 + 1360 + 4352 + 4352 + 544 = 16 784 floats = 67 136 bytes: two workgroups per CU.
 //   obs 3, D 1 (PPO_ENV_PENDULUM): 256 + 4096 + 256 + 288 + 272 + 4352 + 4352 + 272 = 14 144 floats = 56 576 bytes: two workgroups per CU.
+//   obs 2, D 1 (PPO_ENV_MOUNTAINCAR_CONTINUOUS): the same carve, gf_carve(4, 4); rows 2 and 3 of the X image are zero padding.
 //
-// PPO_ENV_PENDULUM adds a fourth kernel on the same forward, gauss_rollout_kernel: the T steps of a rollout in one launch, the env in registers (below), and
-// the env's small stand-alone kernels.
+// The device envs with real-valued actions (ppo_internal.hpp: GaussEnvPendulum, GaussEnvMountainCarContinuous) add kernels on the same forward, each a
+// template over the env trait: gauss_rollout_kernel, the T steps of a rollout in one launch with the env in registers (below); the envs' small stand-alone
+// kernels; and, for an env whose observation is its state, gauss_trunc_fold_kernel (ppo_env_truncation_bootstrap) and gauss_eval_kernel (ppo_evaluate).
 #include <algorithm>
 
 #include "generic.hpp"
@@ -515,13 +517,14 @@ __global__ __launch_bounds__(256) void gauss_slab_reduce_kernel(const float* __r
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// gauss_rollout_kernel (PPO_ENV_PENDULUM): the T steps of a rollout as ONE launch.  A workgroup owns one tile of 64 envs for the whole rollout; the actor's
+// gauss_rollout_kernel<Env> (PPO_ENV_PENDULUM, PPO_ENV_MOUNTAINCAR_CONTINUOUS): the T steps of a rollout as ONE launch.  A workgroup owns one tile of 64 envs for the whole rollout; the actor's
 // weights are staged once.  Lanes 0 .. 63 of wave 0 keep their env (state, episode sums, reset count, previous done flag, the current observation) in
 // registers and do, per step, what gauss_act_kernel's wave 0 does behind the same forward -- the same draw, sample and log-prob expressions, so a stepwise
-// loop of ppo_policy_act_f32 + ppo_env_step_f32 reproduces every stored bit -- then the env step (pendulum_step_episode).  Waves 1 .. 3 store the step's
+// loop of ppo_policy_act_f32 + ppo_env_step_f32 reproduces every stored bit -- then the env step (Env::step_episode).  Waves 1 .. 3 store the step's
 // observation and done flag from LDS meanwhile (the done flag rides in the row-index words, which this kernel does not need as indices).
 // Barriers per step: gf_forward_tile's four and one behind the stores (X and the done words are rewritten for the next step); every thread runs every
-// barrier, a short tile masks its stores only.  No workgroup talks to another.  LDS: gf_lds_floats(4, 4) = 14 144 floats = 56 576 bytes, two workgroups per CU.
+// barrier, a short tile masks its stores only.  No workgroup talks to another.  LDS: gf_lds_floats(4, 4) = 14 144 floats = 56 576 bytes, two workgroups per CU
+// (Env::OBS <= 4: rows Env::OBS .. 3 of the X image are zero padding, written once).
 // ---------------------------------------------------------------------------------------------------------
 struct GfRolloutArgs {
     GfShape sh;
@@ -532,19 +535,22 @@ struct GfRolloutArgs {
     int32_t* ep_len;
     float* ep_rew;
     int32_t* reset_count;
-    float* obs;              // [T, N, 3]
+    float* obs;              // [T, N, Env::OBS]
     float* actions;          // [T, N, 1]
     float* logprobs;
     float* rewards;
     float* dones;
     int32_t* fin_len;
     float* fin_rew;
-    float* next_obs;         // [N, 3]
+    float* next_obs;         // [N, Env::OBS]
     int32_t* next_done;
     const float* forced;     // [T, N, 1] or null
 };
 
+template <class Env>
 __global__ __launch_bounds__(GF_THREADS) void gauss_rollout_kernel(GfRolloutArgs a) {
+    constexpr int OBS = Env::OBS;
+    static_assert(OBS <= 4 && Env::STATE == 2, "the rollout kernel carves its LDS for an observation of at most 4 floats and keeps a state of 2 in registers");
     extern __shared__ __attribute__((aligned(16))) float gf_lds[];
     const int tid = threadIdx.x, N = a.N;
     const GfLds m = gf_carve(gf_lds, 4, 4);
@@ -553,7 +559,9 @@ __global__ __launch_bounds__(GF_THREADS) void gauss_rollout_kernel(GfRolloutArgs
     const int env = row0 + (tid & 63);
     const bool owner = tid < 64 && env < N;
     const int64_t env_global = a.env_offset + env;
-    float st[2] = { 0.0f, 0.0f }, ob[3] = { 0.0f, 0.0f, 0.0f }, ep_rew = 0.0f;
+    float st[2] = { 0.0f, 0.0f }, ob[OBS], ep_rew = 0.0f;
+#pragma unroll
+    for (int k = 0; k < OBS; k++) ob[k] = 0.0f;
     int ep_len = 0, resets = 0, done = 0;
     if (owner) {
         st[0] = a.env_state[env];
@@ -562,16 +570,18 @@ __global__ __launch_bounds__(GF_THREADS) void gauss_rollout_kernel(GfRolloutArgs
         ep_rew = a.ep_rew[env];
         resets = a.reset_count[env];
         done = a.next_done[env];
-        pendulum_obs(st, ob);
+        Env::obs(st, ob);
     }
-    if (tid < 64) m.x[3 * GF_S + tid] = 0.0f;   // the padding row of the observation image, once
+    if (tid < 64) {   // the padding rows of the observation image, once
+#pragma unroll
+        for (int k = OBS; k < 4; k++) m.x[k * GF_S + tid] = 0.0f;
+    }
     const int rows = N - row0 < 64 ? N - row0 : 64;
     for (int t = 0; t < a.T; t++) {
         const size_t tn = (size_t)t * N;
         if (tid < 64) {
-            m.x[0 * GF_S + tid] = ob[0];
-            m.x[1 * GF_S + tid] = ob[1];
-            m.x[2 * GF_S + tid] = ob[2];
+#pragma unroll
+            for (int k = 0; k < OBS; k++) m.x[k * GF_S + tid] = ob[k];
             m.ridx[tid] = done;
         }
         gf_forward_tile(m, 1, tid);
@@ -585,8 +595,8 @@ __global__ __launch_bounds__(GF_THREADS) void gauss_rollout_kernel(GfRolloutArgs
                 lp += gauss_logp(gauss_z(act, mu, expf(-ls)), ls);
                 int fin_len;
                 float fin_rew;
-                const float r = pendulum_step_episode(st, act, a.max_episode_steps, a.seed, env_global, ep_len, ep_rew, resets, done, fin_len, fin_rew);
-                pendulum_obs(st, ob);
+                const float r = Env::step_episode(st, act, a.max_episode_steps, a.seed, env_global, ep_len, ep_rew, resets, done, fin_len, fin_rew);
+                Env::obs(st, ob);
                 a.actions[tn + env] = act;
                 a.logprobs[tn + env] = (float)lp;
                 a.rewards[tn + env] = r;
@@ -594,9 +604,9 @@ __global__ __launch_bounds__(GF_THREADS) void gauss_rollout_kernel(GfRolloutArgs
                 a.fin_rew[tn + env] = fin_rew;
             }
         } else {   // waves 1 .. 3: the step's observation rows and done flags, out of LDS
-            float* obs_t = a.obs + (tn + row0) * 3;
-            for (int i = tid - 64; i < rows * 3; i += GF_THREADS - 64) {
-                const int s = i / 3, k = i - 3 * s;
+            float* obs_t = a.obs + (tn + row0) * OBS;
+            for (int i = tid - 64; i < rows * OBS; i += GF_THREADS - 64) {
+                const int s = i / OBS, k = i - OBS * s;
                 obs_t[i] = m.x[k * GF_S + s];
             }
             if (tid < 128 && env < N) a.dones[tn + env] = (float)m.ridx[tid & 63];
@@ -604,9 +614,8 @@ __global__ __launch_bounds__(GF_THREADS) void gauss_rollout_kernel(GfRolloutArgs
         __syncthreads();   // X and the done words are read: wave 0 may write the next step's
     }
     if (owner) {
-        a.next_obs[(size_t)env * 3 + 0] = ob[0];
-        a.next_obs[(size_t)env * 3 + 1] = ob[1];
-        a.next_obs[(size_t)env * 3 + 2] = ob[2];
+#pragma unroll
+        for (int k = 0; k < OBS; k++) a.next_obs[(size_t)env * OBS + k] = ob[k];
         a.next_done[env] = done;
         a.env_state[env] = st[0];
         a.env_state[(size_t)N + env] = st[1];
@@ -616,68 +625,224 @@ __global__ __launch_bounds__(GF_THREADS) void gauss_rollout_kernel(GfRolloutArgs
     }
 }
 
-// ---- Pendulum's stand-alone env kernels: one thread per env, on the device functions the rollout kernel uses (ppo_internal.hpp) ----
+// ---- the envs' stand-alone kernels: one thread per env, on the device functions the rollout kernel uses (ppo_internal.hpp: GaussEnv*) ----
 // ppo_env_reset: env_reset_kernel's bookkeeping (global env 0 takes reset 1: initEnvs probes it once before it resets everybody)
-__global__ void pendulum_reset_kernel(int N, int64_t seed, int64_t env_offset, float* env_state, int32_t* ep_len, float* ep_rew, int32_t* reset_count,
-                                      float* next_obs, int32_t* next_done) {
+template <class Env>
+__global__ void gauss_env_reset_kernel(int N, int64_t seed, int64_t env_offset, float* env_state, int32_t* ep_len, float* ep_rew, int32_t* reset_count,
+                                       float* next_obs, int32_t* next_done) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N) return;
     const int k = (env_offset + i == 0) ? 1 : 0;
-    float st[2], ob[3];
-    pendulum_reset(st, k, seed, env_offset + i);
-    pendulum_obs(st, ob);
+    float st[2], ob[Env::OBS];
+    Env::reset(st, k, seed, env_offset + i);
+    Env::obs(st, ob);
     env_state[i] = st[0];
     env_state[(size_t)N + i] = st[1];
-    for (int j = 0; j < 3; j++) next_obs[(size_t)i * 3 + j] = ob[j];
+    for (int j = 0; j < Env::OBS; j++) next_obs[(size_t)i * Env::OBS + j] = ob[j];
     ep_len[i] = 0;
     ep_rew[i] = 0.0f;
     reset_count[i] = k + 1;
     next_done[i] = 0;
 }
 // ppo_env_step_f32: action f32 [N, 1]
-__global__ void pendulum_step_kernel(int N, int max_episode_steps, int64_t seed, int64_t env_offset, float* env_state, int32_t* ep_len, float* ep_rew,
-                                     int32_t* reset_count, const float* __restrict__ action, float* obs, float* reward, int32_t* done) {
+template <class Env>
+__global__ void gauss_env_step_kernel(int N, int max_episode_steps, int64_t seed, int64_t env_offset, float* env_state, int32_t* ep_len, float* ep_rew,
+                                      int32_t* reset_count, const float* __restrict__ action, float* obs, float* reward, int32_t* done) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N) return;
-    float st[2] = { env_state[i], env_state[(size_t)N + i] }, ob[3];
+    float st[2] = { env_state[i], env_state[(size_t)N + i] }, ob[Env::OBS];
     int len = ep_len[i], resets = reset_count[i], d, fin_len;
     float rew = ep_rew[i], fin_rew;
-    const float r = pendulum_step_episode(st, action[i], max_episode_steps, seed, env_offset + i, len, rew, resets, d, fin_len, fin_rew);
-    pendulum_obs(st, ob);
+    const float r = Env::step_episode(st, action[i], max_episode_steps, seed, env_offset + i, len, rew, resets, d, fin_len, fin_rew);
+    Env::obs(st, ob);
     env_state[i] = st[0];
     env_state[(size_t)N + i] = st[1];
     ep_len[i] = len;
     ep_rew[i] = rew;
     reset_count[i] = resets;
-    for (int j = 0; j < 3; j++) obs[(size_t)i * 3 + j] = ob[j];
+    for (int j = 0; j < Env::OBS; j++) obs[(size_t)i * Env::OBS + j] = ob[j];
     reward[i] = r;
     done[i] = d;
 }
-// ppo_env_transition_f32: stateless; state [n, 2], action [n, 1], obs_out [n, 3] or null
-__global__ void pendulum_transition_kernel(const float* __restrict__ state_in, const float* __restrict__ action, int64_t n, float* next_state, float* obs_out,
-                                           float* reward, int32_t* terminated) {
+// ppo_env_transition_f32: stateless; state [n, 2], action [n, 1], obs_out [n, Env::OBS] or null
+template <class Env>
+__global__ void gauss_env_transition_kernel(const float* __restrict__ state_in, const float* __restrict__ action, int64_t n, float* next_state, float* obs_out,
+                                            float* reward, int32_t* terminated) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     float st[2] = { state_in[i * 2], state_in[i * 2 + 1] };
-    const float r = pendulum_step(st, action[i]);
+    int term;
+    const float r = Env::step(st, action[i], term);
     next_state[i * 2] = st[0];
     next_state[i * 2 + 1] = st[1];
     if (obs_out) {
-        float ob[3];
-        pendulum_obs(st, ob);
-        for (int j = 0; j < 3; j++) obs_out[i * 3 + j] = ob[j];
+        float ob[Env::OBS];
+        Env::obs(st, ob);
+        for (int j = 0; j < Env::OBS; j++) obs_out[i * Env::OBS + j] = ob[j];
     }
     reward[i] = r;
-    terminated[i] = 0;
+    terminated[i] = term;
 }
 // ppo_env_set_state_h: NEXT_OBS from the injected states
-__global__ void pendulum_obs_kernel(int N, const float* __restrict__ env_state, float* next_obs) {
+template <class Env>
+__global__ void gauss_env_obs_kernel(int N, const float* __restrict__ env_state, float* next_obs) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N) return;
     const float st[2] = { env_state[i], env_state[(size_t)N + i] };
-    float ob[3];
-    pendulum_obs(st, ob);
-    for (int j = 0; j < 3; j++) next_obs[(size_t)i * 3 + j] = ob[j];
+    float ob[Env::OBS];
+    Env::obs(st, ob);
+    for (int j = 0; j < Env::OBS; j++) next_obs[(size_t)i * Env::OBS + j] = ob[j];
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// gauss_trunc_fold_kernel<Env> (ppo_env_truncation_bootstrap on an env whose observation is its state): env_trunc_fold_mfma_kernel's plan (kernels_update_mfma.hip)
+// on this file's critic.  A 256-thread workgroup owns 256 consecutive flat samples.  Every thread reads FIN_LEN[i]; a lane whose episode reached the limit
+// recomputes the step (Env::step on OBS[i] under the raw action ACTIONS[i]: divergent code without a barrier) and keeps the sample unless the env terminated
+// on it.  ONE compaction (fold_compact), on the kept samples; a workgroup that keeps none -- the common case, one pass over FIN_LEN -- returns before it
+// loads a weight (the count is the same in every thread, so the return is uniform).  The kept samples' final observations wait in LDS in list order
+// (ascending); the critic's weights are staged, and the workgroup runs gf_forward_tile on the list in tiles of 64 -- gauss_values_kernel's forward on the same
+// carve, so v is that kernel's value of the final observation, bit for bit.  Lane k of wave 0 folds row k of the tile (fold_store).
+// LDS: gf_lds_floats(4, 4) dynamic + 256 * OBS floats + 264 ints static = 59 680 bytes for OBS 2: no attribute needed, two workgroups per CU.
+// ---------------------------------------------------------------------------------------------------------
+struct GfFoldArgs {
+    GfShape sh;
+    const float* params;
+    const float* obs;
+    const float* actions;
+    const int32_t* fin_len;
+    int64_t B;
+    int max_episode_steps;
+    float gamma;
+    float* rewards;
+    int32_t* ev_count;
+    int32_t* ev_index;
+    float* ev_value;
+    int64_t ev_cap;
+};
+
+template <class Env>
+__global__ __launch_bounds__(DEV_FOLD_THREADS) void gauss_trunc_fold_kernel(GfFoldArgs a) {
+    constexpr int OBS = Env::OBS;
+    static_assert(Env::OBS_IS_STATE && OBS == Env::STATE && OBS <= 4, "the fold steps the env from a stored observation");
+    static_assert(DEV_FOLD_THREADS == GF_THREADS, "fold_compact and gf_forward_tile are written for the same workgroup");
+    extern __shared__ __attribute__((aligned(16))) float gf_lds[];
+    __shared__ float fobs[DEV_FOLD_THREADS * OBS];
+    __shared__ int list[DEV_FOLD_THREADS], wtot[8];
+    const int tid = threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * DEV_FOLD_THREADS + tid;
+    bool keep = false;
+    float st[OBS];
+#pragma unroll
+    for (int j = 0; j < OBS; j++) st[j] = 0.0f;
+    if (i < a.B && a.fin_len[i] == a.max_episode_steps) {
+#pragma unroll
+        for (int j = 0; j < OBS; j++) st[j] = a.obs[i * OBS + j];
+        int terminated;
+        (void)Env::step(st, a.actions[i], terminated);
+        keep = terminated == 0;
+    }
+    int pos;
+    const int cnt = fold_compact(keep, (int)i, a.ev_count, list, wtot, pos);
+    if (cnt == 0) return;
+    const int base = wtot[4];
+    if (keep) {
+#pragma unroll
+        for (int j = 0; j < OBS; j++) fobs[pos * OBS + j] = st[j];
+    }
+    const GfLds m = gf_carve(gf_lds, 4, 4);
+    gf_stage_weights(m, a.sh, a.params, 0, tid);
+    if (tid < 64) {   // the padding rows of the observation image, once
+#pragma unroll
+        for (int k = OBS; k < 4; k++) m.x[k * GF_S + tid] = 0.0f;
+    }
+    __syncthreads();   // fobs is complete
+    for (int k0 = 0; k0 < cnt; k0 += 64) {
+        const int k = k0 + tid;   // tid < 64: this lane's place in the list
+        if (tid < 64) {
+#pragma unroll
+            for (int j = 0; j < OBS; j++) m.x[j * GF_S + tid] = k < cnt ? fobs[k * OBS + j] : 0.0f;
+        }
+        gf_forward_tile(m, 1, tid);
+        if (tid < 64 && k < cnt) fold_store(a.rewards, a.gamma, a.ev_index, a.ev_value, a.ev_cap, (int64_t)base + k, list[k], m.o[tid]);
+        __syncthreads();   // X and OUT are read: the next tile may overwrite them
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// gauss_eval_kernel<Env> (ppo_evaluate on an env whose observation is its state): whole episodes in ONE launch.  A workgroup owns 64 episodes for their whole
+// length with the actor's weights resident, as in gauss_rollout_kernel: lane l of wave 0 keeps episode 64 b + l (state, return, length) in registers, writes
+// its observation into the X image, every thread runs gf_forward_tile, and wave 0 takes the mean (greedy) or mu + sigma * eps with eps keyed (seed, episode,
+// step of the episode, 0) -- gauss_act_kernel's expressions -- and steps the env (Env::step).  An episode ends where the env terminates or its length reaches
+// max_episode_steps; a finished lane keeps feeding its last observation through the forward and ignores the result.
+// The step loop's exit must be uniform across the workgroup (every thread runs the forward's barriers): wave 0 ballots its live lanes and publishes the count
+// in the row-index words, which this kernel does not need as indices; the step's closing barrier, which every thread runs, hands it to the other waves.
+// The loop ends after at most max_episode_steps steps.  Nothing depends on the tile an episode sits in.
+// ---------------------------------------------------------------------------------------------------------
+struct GfEvalArgs {
+    GfShape sh;
+    const float* params;
+    int64_t n_episodes, seed;
+    int max_episode_steps, greedy;
+    float* ep_return;
+    int32_t* ep_length;
+    int32_t* ep_trunc;
+};
+
+template <class Env>
+__global__ __launch_bounds__(GF_THREADS) void gauss_eval_kernel(GfEvalArgs a) {
+    constexpr int OBS = Env::OBS;
+    static_assert(Env::OBS_IS_STATE && OBS <= 4 && Env::STATE == 2, "as gauss_rollout_kernel");
+    extern __shared__ __attribute__((aligned(16))) float gf_lds[];
+    const int tid = threadIdx.x;
+    const GfLds m = gf_carve(gf_lds, 4, 4);
+    gf_stage_weights(m, a.sh, a.params, 1, tid);
+    const int64_t ep = (int64_t)blockIdx.x * 64 + (tid & 63);
+    bool alive = tid < 64 && ep < a.n_episodes;
+    const bool owner = alive;
+    float st[2] = { 0.0f, 0.0f }, ob[OBS], ep_rew = 0.0f;
+#pragma unroll
+    for (int k = 0; k < OBS; k++) ob[k] = 0.0f;
+    int ep_len = 0, trunc = 0;
+    if (owner) {
+        Env::reset(st, 0, a.seed, ep);
+        Env::obs(st, ob);
+    }
+    if (tid < 64) {
+#pragma unroll
+        for (int k = OBS; k < 4; k++) m.x[k * GF_S + tid] = 0.0f;
+    }
+    for (;;) {
+        if (tid < 64) {
+#pragma unroll
+            for (int k = 0; k < OBS; k++) m.x[k * GF_S + tid] = ob[k];
+        }
+        gf_forward_tile(m, 1, tid);
+        if (tid < 64) {
+            if (alive) {
+                const float mu = m.o[tid], ls = m.ls[0];
+                float eps[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
+                if (!a.greedy) gauss_eps4(a.seed, ep, (int64_t)ep_len, 0, eps);
+                const float act = a.greedy ? mu : gauss_sample(mu, ls, eps[0]);
+                int term;
+                const float r = Env::step(st, act, term);
+                ep_len += 1;
+                ep_rew += r;
+                trunc = ep_len == a.max_episode_steps ? 1 : 0;
+                if (term || trunc) alive = false;
+                Env::obs(st, ob);
+            }
+            const unsigned long long live = __ballot(alive);
+            if (tid == 0) m.ridx[0] = __popcll(live);
+        }
+        __syncthreads();   // the live count is published; OUT is read
+        if (m.ridx[0] == 0) break;
+        // the next write of the count is behind the next forward's four barriers: every wave has read this one by then
+    }
+    if (owner) {
+        a.ep_return[ep] = ep_rew;
+        a.ep_length[ep] = ep_len;
+        a.ep_trunc[ep] = trunc;
+    }
 }
 
 template <typename K>
@@ -750,10 +915,11 @@ hipError_t gauss_fused_fwd_bwd(const GenLayout& L, const LossParams& hp, const f
     return hipGetLastError();
 }
 
-// ---- PPO_ENV_PENDULUM (the context's shape is fixed by ppo_ctx_create: obs 3, D 1) ----
-hipError_t gauss_fused_rollout(const GenLayout& L, const GaussRolloutArgs& r, hipStream_t s) {
+// ---- the device envs with real-valued actions (the context's shape is fixed by ppo_ctx_create: obs Env::OBS, D 1) ----
+template <class Env>
+static hipError_t gauss_fused_rollout(const GenLayout& L, const GaussRolloutArgs& r, hipStream_t s) {
     if (r.N <= 0 || r.T <= 0) return hipSuccess;
-    if (L.obs != 3 || L.gauss != 1) return hipErrorInvalidValue;
+    if (L.obs != Env::OBS || L.gauss != 1) return hipErrorInvalidValue;
     GfRolloutArgs a{};
     a.sh = gf_shape(L);
     a.params = r.params;
@@ -764,34 +930,87 @@ hipError_t gauss_fused_rollout(const GenLayout& L, const GaussRolloutArgs& r, hi
     a.next_obs = r.next_obs; a.next_done = r.next_done; a.forced = r.forced;
     const int bytes = gf_lds_floats(4, 4) * 4;
     static std::atomic<unsigned long long> done{ 0 };
-    const hipError_t e = gf_allow(done, gauss_rollout_kernel, bytes);
+    const hipError_t e = gf_allow(done, gauss_rollout_kernel<Env>, bytes);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(gauss_rollout_kernel, dim3((unsigned)((r.N + 63) / 64)), dim3(GF_THREADS), bytes, s, a);
+    hipLaunchKernelGGL(gauss_rollout_kernel<Env>, dim3((unsigned)((r.N + 63) / 64)), dim3(GF_THREADS), bytes, s, a);
     return hipGetLastError();
 }
 
-hipError_t launch_pendulum_reset(int N, int64_t seed, int64_t env_offset, float* env_state, int32_t* ep_len, float* ep_rew, int32_t* reset_count, float* next_obs,
-                                 int32_t* next_done, hipStream_t s) {
-    if (N <= 0) return hipSuccess;
-    hipLaunchKernelGGL(pendulum_reset_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, seed, env_offset, env_state, ep_len, ep_rew, reset_count, next_obs, next_done);
-    return hipGetLastError();
+// env_kind -> trait: f is called with a value of the env's trait type; an env without one gives hipErrorInvalidValue
+template <class F>
+static hipError_t gauss_env_dispatch(int env_kind, F f) {
+    if (env_kind == PPO_ENV_PENDULUM) return f(GaussEnvPendulum{});
+    if (env_kind == PPO_ENV_MOUNTAINCAR_CONTINUOUS) return f(GaussEnvMountainCarContinuous{});
+    return hipErrorInvalidValue;
 }
-hipError_t launch_pendulum_step(int N, int max_episode_steps, int64_t seed, int64_t env_offset, float* env_state, int32_t* ep_len, float* ep_rew,
-                                int32_t* reset_count, const float* action, float* obs, float* reward, int32_t* done, hipStream_t s) {
-    if (N <= 0) return hipSuccess;
-    hipLaunchKernelGGL(pendulum_step_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, max_episode_steps, seed, env_offset, env_state, ep_len, ep_rew, reset_count,
-                       action, obs, reward, done);
-    return hipGetLastError();
+
+hipError_t gauss_fused_rollout(int env_kind, const GenLayout& L, const GaussRolloutArgs& r, hipStream_t s) {
+    return gauss_env_dispatch(env_kind, [&](auto env) { return gauss_fused_rollout<decltype(env)>(L, r, s); });
 }
-hipError_t launch_pendulum_transition(const float* state_in, const float* action, int64_t n, float* next_state, float* obs_out, float* reward, int32_t* terminated,
-                                      hipStream_t s) {
+
+hipError_t launch_gauss_env_reset(int env_kind, int N, int64_t seed, int64_t env_offset, float* env_state, int32_t* ep_len, float* ep_rew, int32_t* reset_count,
+                                  float* next_obs, int32_t* next_done, hipStream_t s) {
+    if (N <= 0) return hipSuccess;
+    return gauss_env_dispatch(env_kind, [&](auto env) {
+        hipLaunchKernelGGL(gauss_env_reset_kernel<decltype(env)>, dim3((N + 255) / 256), dim3(256), 0, s, N, seed, env_offset, env_state, ep_len, ep_rew, reset_count,
+                           next_obs, next_done);
+        return hipGetLastError();
+    });
+}
+hipError_t launch_gauss_env_step(int env_kind, int N, int max_episode_steps, int64_t seed, int64_t env_offset, float* env_state, int32_t* ep_len, float* ep_rew,
+                                 int32_t* reset_count, const float* action, float* obs, float* reward, int32_t* done, hipStream_t s) {
+    if (N <= 0) return hipSuccess;
+    return gauss_env_dispatch(env_kind, [&](auto env) {
+        hipLaunchKernelGGL(gauss_env_step_kernel<decltype(env)>, dim3((N + 255) / 256), dim3(256), 0, s, N, max_episode_steps, seed, env_offset, env_state, ep_len,
+                           ep_rew, reset_count, action, obs, reward, done);
+        return hipGetLastError();
+    });
+}
+hipError_t launch_gauss_env_transition(int env_kind, const float* state_in, const float* action, int64_t n, float* next_state, float* obs_out, float* reward,
+                                       int32_t* terminated, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     if (n >= (1ll << 31) * 256) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(pendulum_transition_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, state_in, action, n, next_state, obs_out, reward, terminated);
+    return gauss_env_dispatch(env_kind, [&](auto env) {
+        hipLaunchKernelGGL(gauss_env_transition_kernel<decltype(env)>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, state_in, action, n, next_state, obs_out,
+                           reward, terminated);
+        return hipGetLastError();
+    });
+}
+hipError_t launch_gauss_env_obs(int env_kind, int N, const float* env_state, float* next_obs, hipStream_t s) {
+    if (N <= 0) return hipSuccess;
+    return gauss_env_dispatch(env_kind, [&](auto env) {
+        hipLaunchKernelGGL(gauss_env_obs_kernel<decltype(env)>, dim3((N + 255) / 256), dim3(256), 0, s, N, env_state, next_obs);
+        return hipGetLastError();
+    });
+}
+
+// the fold and the evaluation exist for the envs whose observation is their state
+hipError_t gauss_fused_trunc_fold(int env_kind, const GenLayout& L, const GaussFoldArgs& f, hipStream_t s) {
+    if (f.B <= 0 || f.max_episode_steps <= 0) return hipSuccess;   // no limit: no episode is ever cut off
+    if (env_kind != PPO_ENV_MOUNTAINCAR_CONTINUOUS || L.obs != GaussEnvMountainCarContinuous::OBS || L.gauss != 1) return hipErrorInvalidValue;
+    if (f.B >= (1ll << 31)) return hipErrorInvalidValue;
+    GfFoldArgs a{};
+    a.sh = gf_shape(L);
+    a.params = f.params; a.obs = f.obs; a.actions = f.actions; a.fin_len = f.fin_len;
+    a.B = f.B; a.max_episode_steps = f.max_episode_steps; a.gamma = f.gamma;
+    a.rewards = f.rewards; a.ev_count = f.ev_count; a.ev_index = f.ev_index; a.ev_value = f.ev_value; a.ev_cap = f.ev_cap;
+    const int bytes = gf_lds_floats(4, 4) * 4;
+    const unsigned grid = (unsigned)((f.B + DEV_FOLD_THREADS - 1) / DEV_FOLD_THREADS);
+    hipLaunchKernelGGL(gauss_trunc_fold_kernel<GaussEnvMountainCarContinuous>, dim3(grid), dim3(DEV_FOLD_THREADS), bytes, s, a);
     return hipGetLastError();
 }
-hipError_t launch_pendulum_obs(int N, const float* env_state, float* next_obs, hipStream_t s) {
-    if (N <= 0) return hipSuccess;
-    hipLaunchKernelGGL(pendulum_obs_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, env_state, next_obs);
+
+hipError_t gauss_fused_evaluate(int env_kind, const GenLayout& L, const GaussEvalArgs& e, hipStream_t s) {
+    if (e.n_episodes <= 0) return hipSuccess;
+    if (env_kind != PPO_ENV_MOUNTAINCAR_CONTINUOUS || L.obs != GaussEnvMountainCarContinuous::OBS || L.gauss != 1) return hipErrorInvalidValue;
+    if (e.max_episode_steps < 1 || e.n_episodes >= (1ll << 31) * 64 || !e.ep_return || !e.ep_length || !e.ep_trunc) return hipErrorInvalidValue;
+    GfEvalArgs a{};
+    a.sh = gf_shape(L);
+    a.params = e.params;
+    a.n_episodes = e.n_episodes; a.seed = e.seed;
+    a.max_episode_steps = e.max_episode_steps; a.greedy = e.greedy != 0;
+    a.ep_return = e.ep_return; a.ep_length = e.ep_length; a.ep_trunc = e.ep_trunc;
+    const int bytes = gf_lds_floats(4, 4) * 4;
+    hipLaunchKernelGGL(gauss_eval_kernel<GaussEnvMountainCarContinuous>, dim3((unsigned)((e.n_episodes + 63) / 64)), dim3(GF_THREADS), bytes, s, a);
     return hipGetLastError();
 }

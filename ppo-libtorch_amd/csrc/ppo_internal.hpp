@@ -305,6 +305,83 @@ __device__ __forceinline__ float pendulum_step_episode(float* st, float a, int m
     return r;
 }
 
+// MountainCarContinuous-v0 (gymnasium's classic_control/continuous_mountain_car.py; no reference counterpart: PPO_ENV_MOUNTAINCAR_CONTINUOUS).  The discrete
+// MountainCar's track with a real-valued force: st = {position, velocity}, and the observation IS the state.  a = the RAW action, clipped here to the force
+// range (the rollout keeps the raw sample); the penalty is on the RAW action, as gym's math.pow(action[0], 2).  Every operation rounds on its own
+// (-ffp-contract=off), in exactly this association:
+//   u  = min(max(a, -1), 1)
+//   v' = v + (u * 0.0015f - 0.0025f * glibc_cosf(3.0f * p));   v' = min(max(v', -0.07f), 0.07f)
+//   p' = p + v';                                                p' = min(max(p', -1.2f), 0.6f)
+//   if (p' == -1.2f && v' < 0) v' = 0
+//   terminated = (p' >= 0.45f && v' >= 0.0f);   reward = (terminated ? 100.0f : 0.0f) - 0.1f * (a * a)
+// The cosine's argument stays within [-3.6, 1.8].
+__device__ __forceinline__ float mcc_step(float* st, float a, int& terminated) {
+    const float min_position = -1.2f, max_position = 0.6f, max_speed = 0.07f, goal_position = 0.45f, goal_velocity = 0.0f;
+    const float power = 0.0015f, gravity = 0.0025f;
+    float position = st[0], velocity = st[1];
+    const float u = a < -1.0f ? -1.0f : (a > 1.0f ? 1.0f : a);
+    velocity = velocity + (u * power - gravity * glibc_cosf(3.0f * position));
+    velocity = velocity < -max_speed ? -max_speed : (velocity > max_speed ? max_speed : velocity);
+    position = position + velocity;
+    position = position < min_position ? min_position : (position > max_position ? max_position : position);
+    if (position == min_position && velocity < 0.0f) velocity = 0.0f;
+    terminated = (position >= goal_position && velocity >= goal_velocity) ? 1 : 0;
+    st[0] = position; st[1] = velocity;
+    return (terminated ? 100.0f : 0.0f) - 0.1f * (a * a);
+}
+// reset number k of global env e: the discrete MountainCar's own (env_reset below): philox(seed; e, k, 0, 1).x mapped to [-0.6, -0.4), velocity 0
+__device__ __forceinline__ void mcc_reset(float* st, int k, int64_t seed, int64_t env_global) {
+    const uint4 w = philox4x32_10((uint32_t)seed, (uint32_t)((uint64_t)seed >> 32), (uint32_t)env_global, (uint32_t)k, 0u, 1u);
+    st[0] = canon_to_uniform(w.x, -0.6f, -0.4f);
+    st[1] = 0.0f;
+}
+// One step of a continuous MountainCar env with env_step_kernel's bookkeeping (the episode ends where the env terminates or its length reaches the limit):
+// ONE definition for the fused rollout and the stand-alone step.  Returns the reward; done / fin_len / fin_rew are the step's.
+__device__ __forceinline__ float mcc_step_episode(float* st, float a, int max_episode_steps, int64_t seed, int64_t env_global, int& ep_len, float& ep_rew,
+                                                  int& resets, int& done, int& fin_len, float& fin_rew) {
+    int term;
+    const float r = mcc_step(st, a, term);
+    ep_len += 1;
+    ep_rew += r;
+    done = (term || ep_len == max_episode_steps) ? 1 : 0;
+    fin_len = 0;
+    fin_rew = 0.0f;
+    if (done) {
+        fin_len = ep_len;
+        fin_rew = ep_rew;
+        mcc_reset(st, resets++, seed, env_global);
+        ep_len = 0;
+        ep_rew = 0.0f;
+    }
+    return r;
+}
+
+// What the fused Gaussian kernels need of a device env with real-valued actions (kernels_gauss_fused.hip: gauss_rollout_kernel, the stand-alone env kernels,
+// gauss_trunc_fold_kernel, gauss_eval_kernel): the observation's width, the per-lane state (STATE floats), obs(state), the bare step (the raw action in,
+// `terminated` out), the reset and step_episode.  OBS_IS_STATE: the fold and the evaluation's contract -- a stored observation is enough to step from.
+struct GaussEnvPendulum {
+    static constexpr int OBS = 3, STATE = 2;
+    static constexpr bool OBS_IS_STATE = false;
+    __device__ static __forceinline__ void obs(const float* st, float* ob) { pendulum_obs(st, ob); }
+    __device__ static __forceinline__ float step(float* st, float a, int& terminated) { terminated = 0; return pendulum_step(st, a); }
+    __device__ static __forceinline__ void reset(float* st, int k, int64_t seed, int64_t env_global) { pendulum_reset(st, k, seed, env_global); }
+    __device__ static __forceinline__ float step_episode(float* st, float a, int max_episode_steps, int64_t seed, int64_t env_global, int& ep_len, float& ep_rew,
+                                                         int& resets, int& done, int& fin_len, float& fin_rew) {
+        return pendulum_step_episode(st, a, max_episode_steps, seed, env_global, ep_len, ep_rew, resets, done, fin_len, fin_rew);
+    }
+};
+struct GaussEnvMountainCarContinuous {
+    static constexpr int OBS = 2, STATE = 2;
+    static constexpr bool OBS_IS_STATE = true;
+    __device__ static __forceinline__ void obs(const float* st, float* ob) { ob[0] = st[0]; ob[1] = st[1]; }
+    __device__ static __forceinline__ float step(float* st, float a, int& terminated) { return mcc_step(st, a, terminated); }
+    __device__ static __forceinline__ void reset(float* st, int k, int64_t seed, int64_t env_global) { mcc_reset(st, k, seed, env_global); }
+    __device__ static __forceinline__ float step_episode(float* st, float a, int max_episode_steps, int64_t seed, int64_t env_global, int& ep_len, float& ep_rew,
+                                                         int& resets, int& done, int& fin_len, float& fin_rew) {
+        return mcc_step_episode(st, a, max_episode_steps, seed, env_global, ep_len, ep_rew, resets, done, fin_len, fin_rew);
+    }
+};
+
 template <int ENV>
 __device__ __forceinline__ float env_step(float* st, int action, int& terminated) {
     if constexpr (ENV == PPO_ENV_CARTPOLE) return cartpole_step(st, action, terminated);
