@@ -201,10 +201,25 @@ typedef struct ppo_config {
  *                               rollout), and ppo_update's first launch packs the records, forms the permutations and the advantage sums and -- in a context
  *                               that is not sharded -- the 40 normalisations (pack_perm_stats_kernel).  Every workgroup does the arithmetic it does in the
  *                               stand-alone kernel, on the same elements in the same order: parameters, buffers and statistics are the same bit for bit, and
- *                               every reader consumes pending episodes first, so nothing observable moves.  For A/B runs and tests. */
+ *                               every reader consumes pending episodes first, so nothing observable moves.  For A/B runs and tests.
+ *   PPO_KERNEL_CAT_FUSED        PPO_KERNEL_GAUSS_FUSED's twin for the reference's own policies: env_kind = PPO_ENV_HOST with dist_kind = PPO_DIST_CATEGORICAL or
+ *                               PPO_DIST_MASKED on a 2 x 64 f32 network (hidden = 64, n_hidden = 2, PPO_DTYPE_F32), 1 <= obs_size <= 64, any head list within
+ *                               PPO_MAX_HEADS / sum(head_dims) <= 32.  The same kernel family (kernels_gauss_fused.hip: cat_act_kernel, gauss_values_kernel,
+ *                               cat_fwd_bwd_kernel) in the place of the generic engine's per-layer products: ONE launch per env step (actor, masked
+ *                               log-softmax, draw, log-prob, entropy and the step's rollout stores: ppo_host_act, ppo_host_group_act, ppo_dev_act,
+ *                               ppo_policy_act, ppo_policy_act_greedy), ONE per critic batch, and a minibatch step of five.  The heads are the generic path's
+ *                               own device functions (equal logits give equal action, log-prob and entropy bits); a row gets the same logits and value from
+ *                               every entry point, bit for bit.  The context always lives in the generic engine's layout -- also at obs_size 2, 4 and 8, where
+ *                               the flag takes it off the reference-shape kernels; the parameter order is Agent::parameters() order either way.  Against the
+ *                               same context without the flag: log-probs and values agree to f32 summation order, not bit for bit.  Opt-in; a Gaussian
+ *                               policy, a device env, PPO_ENV_SYNTHETIC, another width or depth, bf16, obs_size > 64 or PPO_KERNEL_GAUSS_FUSED beside it make
+ *                               ppo_ctx_create return PPO_ERR_UNSUPPORTED with a message that names the limit -- never served by another engine instead.
+ *                               ppo_evaluate and truncation flags in ppo_dev_observe stay refused as on the generic engine.  ppo_gauss_fused_launches
+ *                               counts the three kernels' launches (one set of counters for the family; no symbol of its own). */
 enum { PPO_KERNEL_ROLLOUT_VECTOR = 1, PPO_KERNEL_UPDATE_VECTOR = 2, PPO_KERNEL_UPDATE_ONE_WAVE = 4, PPO_KERNEL_COMM_SELFTEST = 8, PPO_KERNEL_GENERIC_CLASSIC = 16,
        PPO_KERNEL_GENERIC_SPLIT_HEAD = 32, PPO_KERNEL_GAUSS_FUSED = 64 };
 #define PPO_KERNEL_SEPARATE_LAUNCHES 128   /* the next free bit of kernel_flags, 1 << 7; a macro beside the enumerators: same type in an expression, same use */
+#define PPO_KERNEL_CAT_FUSED 256           /* 1 << 8, likewise */
 
 /* Scalars the reference prints per update (PPO_Discrete.cpp:700-774) plus per-step diagnostics. */
 typedef struct ppo_stats {
@@ -346,10 +361,12 @@ PPO_API ppo_status ppo_gaussian(const float* mean, const float* log_std, const f
                                 int64_t step_index, float* sample, float* log_prob, float* entropy, void* stream);
 
 /* Host-side counts, since the context's creation, of the launches of the three PPO_KERNEL_GAUSS_FUSED kernels: act (one per env step / ppo_policy_act_f32),
- * value (one per critic batch) and update (one per minibatch step).  All three are 0 on a context without the flag: proof of which path ran, like
+ * value (one per critic batch) and update (one per minibatch step).  All three are 0 on a context with neither fused flag: proof of which path ran, like
  * ppo_profile.vector_fallback_launches.  Outputs may be NULL.  PPO_ENV_PENDULUM's rollout launch (gauss_rollout_kernel) is none of the three: a ppo_rollout there
  * moves `value` by 2 and `act` not at all.  The same holds on PPO_ENV_MOUNTAINCAR_CONTINUOUS, whose truncation fold (gauss_trunc_fold_kernel) and evaluation
- * launch (gauss_eval_kernel) are none of the three either: a rollout moves `value` by 2 with ppo_env_truncation_bootstrap on or off, ppo_evaluate moves nothing. */
+ * launch (gauss_eval_kernel) are none of the three either: a rollout moves `value` by 2 with ppo_env_truncation_bootstrap on or off, ppo_evaluate moves nothing.
+ * A PPO_KERNEL_CAT_FUSED context counts its three kernels of the same family here (the two flags exclude each other, so a context has one set of counters): act =
+ * one per env step or env group's step / ppo_policy_act / ppo_policy_act_greedy, value and update as above.  No symbol was added for it. */
 PPO_API ppo_status ppo_gauss_fused_launches(ppo_ctx* ctx, int64_t* act, int64_t* value, int64_t* update);
 
 /* Categorical::sample / CategoricalMasked::sample (Categorical.cpp:73-79: multinomial(probs, 1, replacement = true)) on given

@@ -22,6 +22,7 @@ MM_F32X3, MM_BF16 = 0, 1
 DIST_CATEGORICAL, DIST_MASKED, DIST_GAUSSIAN = 0, 1, 2   # DIST_GAUSSIAN: f32 actions [.., D], the *_f32 calls (include/ppo_hip.h PPO_DIST_GAUSSIAN)
 DTYPE_F32, DTYPE_BF16 = 0, 1
 KERNEL_ROLLOUT_VECTOR, KERNEL_UPDATE_VECTOR, KERNEL_UPDATE_ONE_WAVE, KERNEL_COMM_SELFTEST, KERNEL_GENERIC_CLASSIC, KERNEL_GENERIC_SPLIT_HEAD, KERNEL_GAUSS_FUSED, KERNEL_SEPARATE_LAUNCHES = 1, 2, 4, 8, 16, 32, 64, 128   # ppo_config.kernel_flags (include/ppo_hip.h PPO_KERNEL_*)
+KERNEL_CAT_FUSED = 256   # categorical / masked policies of a 2 x 64 f32 ENV_HOST context on the fused kernel family (include/ppo_hip.h PPO_KERNEL_CAT_FUSED)
 ABI_VERSION = 5
 COMM_ID_BYTES = 128
 COMM_HANDLE_BYTES = 64
@@ -721,10 +722,18 @@ class Context:
         _check(lib().ppo_profile_enable(self.h, C.c_int32(int(on))), self.h)
 
     def gauss_fused_launches(self):
-        """ppo_gauss_fused_launches: (act, value, update) launches of the KERNEL_GAUSS_FUSED kernels since creation; (0, 0, 0) without the flag."""
+        """ppo_gauss_fused_launches: (act, value, update) launches of the fused 2 x 64 kernels (KERNEL_GAUSS_FUSED, or KERNEL_CAT_FUSED: cat_fused_launches) since
+        creation; (0, 0, 0) with neither flag."""
         a, v, u = C.c_int64(), C.c_int64(), C.c_int64()
         _check(lib().ppo_gauss_fused_launches(self.h, C.byref(a), C.byref(v), C.byref(u)), self.h)
         return a.value, v.value, u.value
+
+    def cat_fused_launches(self):
+        """(act, value, update) launches of the KERNEL_CAT_FUSED kernels since creation; (0, 0, 0) without the flag.  The library keeps one set of counters for
+        the fused kernel family and ppo_gauss_fused_launches reads it for either flag (the flags exclude each other): this is that call on a flagged context."""
+        if not self.cfg.kernel_flags & KERNEL_CAT_FUSED:
+            return 0, 0, 0
+        return self.gauss_fused_launches()
 
     def profile_read(self):
         p = Profile()

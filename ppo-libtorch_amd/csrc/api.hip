@@ -198,6 +198,8 @@ struct ppo_ctx {
     // PPO_KERNEL_GAUSS_FUSED (kernels_gauss_fused.hip): the Gaussian 2 x 64 context's act / critic / minibatch kernels, their launch counts since creation
     // (ppo_gauss_fused_launches) and the update kernel's partial slabs [2][GAUSS_FUSED_MAX_BLOCKS][gauss_fused_slab_stride]
     bool gauss_fused = false;
+    // PPO_KERNEL_CAT_FUSED: the categorical twin on the same kernel family; it shares the counters (ppo_gauss_fused_launches reads them for either flag) and the slabs
+    bool cat_fused = false;
     int64_t gf_launches[3] = { 0, 0, 0 };
     float* gf_slab = nullptr;
     unsigned long long* stamps = nullptr;  // [2][12] phase cycles of the diagnostic kernel variant
@@ -562,7 +564,9 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
     // for runs on them; every other network on the generic engine, with PPO_ENV_SYNTHETIC's limits
     const bool host_env = cfg->env_kind == PPO_ENV_HOST;
     const bool gauss = cfg->dist_kind == PPO_DIST_GAUSSIAN;   // diagonal-Gaussian policies: always the generic engine (kernels_gauss.hip)
-    const bool host_ref = host_env && !gauss && cfg->hidden == PPO_HIDDEN && cfg->n_hidden == 2 && cfg->compute_dtype == PPO_DTYPE_F32 &&
+    // PPO_KERNEL_CAT_FUSED: always the generic engine's layout, also at the observation widths of the reference-shape kernels (checked below)
+    const bool cat_fused = (cfg->kernel_flags & PPO_KERNEL_CAT_FUSED) != 0;
+    const bool host_ref = host_env && !gauss && !cat_fused && cfg->hidden == PPO_HIDDEN && cfg->n_hidden == 2 && cfg->compute_dtype == PPO_DTYPE_F32 &&
                           (cfg->obs_size == 2 || cfg->obs_size == 4 || cfg->obs_size == 8);
     // PPO_ENV_PENDULUM: the device env of the fused Gaussian kernels; the network lives in the generic engine's layout (GenericCtx), as a PPO_ENV_HOST
     // context with PPO_KERNEL_GAUSS_FUSED does, and only the rollout differs (gauss_rollout_kernel)
@@ -631,7 +635,23 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
         return fail(nullptr, PPO_ERR_UNSUPPORTED, "dist_kind = PPO_DIST_GAUSSIAN is built for compute_dtype = PPO_DTYPE_F32; bf16 storage is not");
     if (gauss && cfg->n_heads != 1)
         return fail(nullptr, PPO_ERR_UNSUPPORTED, "dist_kind = PPO_DIST_GAUSSIAN takes n_heads = 1 with head_dims[0] = the action dimension D; got n_heads = %d", cfg->n_heads);
-    if (cfg->kernel_flags & ~(PPO_KERNEL_ROLLOUT_VECTOR | PPO_KERNEL_UPDATE_VECTOR | PPO_KERNEL_UPDATE_ONE_WAVE | PPO_KERNEL_COMM_SELFTEST | PPO_KERNEL_GENERIC_CLASSIC | PPO_KERNEL_GENERIC_SPLIT_HEAD | PPO_KERNEL_GAUSS_FUSED | PPO_KERNEL_SEPARATE_LAUNCHES)) return fail(nullptr, PPO_ERR_INVALID, "unknown bits in kernel_flags 0x%x", cfg->kernel_flags);
+    if (cfg->kernel_flags & ~(PPO_KERNEL_ROLLOUT_VECTOR | PPO_KERNEL_UPDATE_VECTOR | PPO_KERNEL_UPDATE_ONE_WAVE | PPO_KERNEL_COMM_SELFTEST | PPO_KERNEL_GENERIC_CLASSIC | PPO_KERNEL_GENERIC_SPLIT_HEAD | PPO_KERNEL_GAUSS_FUSED | PPO_KERNEL_SEPARATE_LAUNCHES | PPO_KERNEL_CAT_FUSED)) return fail(nullptr, PPO_ERR_INVALID, "unknown bits in kernel_flags 0x%x", cfg->kernel_flags);
+    // PPO_KERNEL_CAT_FUSED: the one form kernels_gauss_fused.hip's categorical kernels are built for, or a refusal -- never another engine in its place
+    if (cat_fused) {
+        if (cfg->kernel_flags & PPO_KERNEL_GAUSS_FUSED)
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED and PPO_KERNEL_GAUSS_FUSED exclude each other: a policy is categorical or Gaussian");
+        if (gauss)
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED serves dist_kind = PPO_DIST_CATEGORICAL and PPO_DIST_MASKED only; this context's policy is "
+                        "PPO_DIST_GAUSSIAN (its twin is PPO_KERNEL_GAUSS_FUSED)");
+        if (!host_env)
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED serves caller-stepped environments (env_kind = PPO_ENV_HOST) only; got env_kind %d", cfg->env_kind);
+        if (cfg->hidden != 64) return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED is built for hidden = 64; got hidden = %d", cfg->hidden);
+        if (cfg->n_hidden != 2) return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED is built for n_hidden = 2; got n_hidden = %d", cfg->n_hidden);
+        if (cfg->compute_dtype != PPO_DTYPE_F32)
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED is built for compute_dtype = PPO_DTYPE_F32; bf16 storage is not");
+        if (cfg->obs_size < 1 || cfg->obs_size > GAUSS_FUSED_MAX_OBS)
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED is built for 1 <= obs_size <= %d; got obs_size = %d", GAUSS_FUSED_MAX_OBS, cfg->obs_size);
+    }
     if (cfg->compute_dtype == PPO_DTYPE_BF16 && !generic)
         return fail(nullptr, PPO_ERR_UNSUPPORTED, "compute_dtype = PPO_DTYPE_BF16 applies to networks whose layers are GEMMs (env_kind = PPO_ENV_SYNTHETIC); the reference's "
                     "2 x 64 networks always compute in f32");
@@ -663,6 +683,9 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
             return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_GAUSS_FUSED is built for 1 <= D <= %d and 1 <= obs_size <= %d; got D = %d, obs_size = %d", PPO_MAX_ACT,
                         GAUSS_FUSED_MAX_OBS, A, cfg->obs_size);
     }
+    if (cat_fused && !cat_fused_serves_shape(cfg->obs_size, cfg->hidden, cfg->n_hidden, A))   // the head list's limits are the ABI's own, checked above
+        return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED is built for sum(head_dims) <= %d and 1 <= obs_size <= %d; got %d, obs_size = %d", PPO_MAX_ACT,
+                    GAUSS_FUSED_MAX_OBS, A, cfg->obs_size);
     if (cfg->num_envs < 1 || cfg->num_steps < 1 || cfg->num_minibatches < 1 || cfg->update_epochs < 1)
         return fail(nullptr, PPO_ERR_INVALID, "num_envs, num_steps, num_minibatches, update_epochs must be >= 1");
     const int64_t B = (int64_t)cfg->num_envs * cfg->num_steps;
@@ -877,8 +900,9 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
             CK(dalloc(c, &g.actf, N * GL.gauss));
             CK(dalloc(c, &g.ls_part, (size_t)GEN_LOSS_BLOCKS * GL.gauss));
         }
-        if (gauss_fused) {
-            c->gauss_fused = true;
+        if (gauss_fused || cat_fused) {
+            c->gauss_fused = gauss_fused;
+            c->cat_fused = cat_fused;
             CK(dalloc(c, &c->gf_slab, (size_t)2 * GAUSS_FUSED_MAX_BLOCKS * gauss_fused_slab_stride(GL)));
         }
         CK(dalloc(c, &c->cur_mask, N * GL.act));
@@ -1110,7 +1134,7 @@ extern "C" ppo_status ppo_params_init_orthogonal(ppo_ctx* c, int64_t seed) {
 // ---- generic networks (generic.hpp): critic / actor over n rows, chunked to the workspace size ----
 static ppo_status gen_values(ppo_ctx* c, const float* obs, int64_t n, float* value) {
     GenericCtx& g = *c->gen;
-    if (c->gauss_fused) {   // PPO_KERNEL_GAUSS_FUSED: the critic over all n rows in one launch
+    if (c->gauss_fused || c->cat_fused) {   // PPO_KERNEL_GAUSS_FUSED / PPO_KERNEL_CAT_FUSED: the critic over all n rows in one launch (the kernel is distribution-free)
         NEED(c, n < (1ll << 31), "more than 2^31 rows");
         if (n > 0) c->gf_launches[1] += 1;
         HIPCHK(c, gauss_fused_values(g.L, B_<float>(c, PPO_BUF_PARAMS), obs, n, value, c->stream));
@@ -1133,9 +1157,21 @@ static ppo_status gen_values(ppo_ctx* c, const float* obs, int64_t n, float* val
 // double-buffered variant for M <= 8192 (three-term product), and both variants walk the k chunks in ascending order with the same MFMAs per chunk; its
 // 32 x 128 tile for M <= 32 is never taken here (gen_forward always passes weight planes).  tests/test_gpu_host_env_groups.py covers groups of 7 .. 32
 // rows in batches of 50 / 64; equality for N > 8192 cut into groups <= 8192 rests on that reading.
+// PPO_KERNEL_CAT_FUSED: forward, heads and -- when `stores` is given -- the step's rollout stores in ONE launch over the n rows, whose sampler origin is
+// env_offset + row0; returns true in *stored then (the caller skips gen_store_step)
 static ppo_status gen_policy(ppo_ctx* c, const float* obs, const uint8_t* mask, const int64_t* forced, int64_t n, int64_t step_index, int64_t* action,
-                             float* logprob, float* entropy, bool greedy = false, int64_t row0 = 0, int64_t key_rows = 0) {
+                             float* logprob, float* entropy, bool greedy = false, int64_t row0 = 0, int64_t key_rows = 0, const CatStepStores* stores = nullptr,
+                             bool* stored = nullptr) {
     GenericCtx& g = *c->gen;
+    if (stored) *stored = false;
+    if (c->cat_fused) {
+        NEED(c, n < (1ll << 31), "more than 2^31 rows");
+        if (n > 0) c->gf_launches[0] += 1;
+        HIPCHK(c, cat_fused_act(g.L, c->cfg.dist_kind, B_<float>(c, PPO_BUF_PARAMS), obs, mask, greedy ? nullptr : forced, n, c->cfg.seed, c->cfg.env_offset + row0,
+                                step_index, greedy, action, logprob, entropy, stores, c->stream));
+        if (stored) *stored = stores != nullptr;
+        return PPO_OK;
+    }
     for (int64_t off = 0; off < n; off += g.rows_max) {
         const int64_t rows = std::min<int64_t>(g.rows_max, n - off);
         if (gen_fused_forward_ok(g) && (key_rows > 0 ? std::min<int64_t>(g.rows_max, key_rows) : rows) <= GEN_FUSED_MAX_ROWS) HIPCHK(c, gen_fused_forward(g, B_<float>(c, PPO_BUF_PARAMS), 1, obs + off * g.L.obs, nullptr, 0, rows, false, g.logits, c->stream));
@@ -1873,17 +1909,23 @@ static ppo_status gen_fwd_bwd(ppo_ctx* c, const int32_t* idx, int64_t M, int slo
     c->last_global_M = global_M;
     float* params = B_<float>(c, PPO_BUF_PARAMS);
     float* grads = B_<float>(c, PPO_BUF_GRADS);
-    if (c->gauss_fused) {
-        // PPO_KERNEL_GAUSS_FUSED: gather, both nets' forward, loss and backward in one launch, the slab sums in a second; behind them the engine's own
-        // loss sums, all-reduce, norm and AdamW
+    if (c->gauss_fused || c->cat_fused) {
+        // PPO_KERNEL_GAUSS_FUSED / PPO_KERNEL_CAT_FUSED: gather, both nets' forward, loss and backward in one launch, the slab sums in a second; behind them
+        // the engine's own loss sums, all-reduce, norm and AdamW
         {
             ProfScope ps(c, PROF_FWD_BWD);
             c->gen_opt_fused_ok = false;
             c->gen_pre_idx = nullptr;
             c->gf_launches[2] += 1;
-            HIPCHK(c, gauss_fused_fwd_bwd(GL, c->hp, params, B_<float>(c, PPO_BUF_OBS), B_<float>(c, PPO_BUF_ACTIONS), B_<float>(c, PPO_BUF_LOGPROBS),
-                                          B_<float>(c, PPO_BUF_ADVANTAGES), B_<float>(c, PPO_BUF_RETURNS), B_<float>(c, PPO_BUF_VALUES), idx, M, 1.0 / global_M, global_M,
-                                          c->cfg.norm_adv ? c->adv_stats + (size_t)slot * PPO_ADV_PARTS : nullptr, c->gf_slab, g.loss_part, grads, c->stream));
+            if (c->cat_fused)
+                HIPCHK(c, cat_fused_fwd_bwd(GL, c->hp, params, B_<float>(c, PPO_BUF_OBS), B_<int32_t>(c, PPO_BUF_ACTIONS), B_<uint8_t>(c, PPO_BUF_MASKS),
+                                            B_<float>(c, PPO_BUF_LOGPROBS), B_<float>(c, PPO_BUF_ADVANTAGES), B_<float>(c, PPO_BUF_RETURNS), B_<float>(c, PPO_BUF_VALUES), idx, M,
+                                            1.0 / global_M, global_M, c->cfg.norm_adv ? c->adv_stats + (size_t)slot * PPO_ADV_PARTS : nullptr, c->gf_slab, g.loss_part, grads,
+                                            c->stream));
+            else
+                HIPCHK(c, gauss_fused_fwd_bwd(GL, c->hp, params, B_<float>(c, PPO_BUF_OBS), B_<float>(c, PPO_BUF_ACTIONS), B_<float>(c, PPO_BUF_LOGPROBS),
+                                              B_<float>(c, PPO_BUF_ADVANTAGES), B_<float>(c, PPO_BUF_RETURNS), B_<float>(c, PPO_BUF_VALUES), idx, M, 1.0 / global_M, global_M,
+                                              c->cfg.norm_adv ? c->adv_stats + (size_t)slot * PPO_ADV_PARTS : nullptr, c->gf_slab, g.loss_part, grads, c->stream));
         }
         ProfScope ps(c, PROF_REDUCE);
         HIPCHK(c, gen_loss_sums(g, c->loss_sums, grads + GL.P, c->stream));
@@ -2594,10 +2636,14 @@ static ppo_status act_slice(ppo_ctx* c, const StepSlice& sl, const uint8_t* mask
     // key_rows = N for every slice.  For a group that is what it always passed.  For the whole batch (n = N, where the callers used to pass 0) it picks
     // the same launch: rows_max = max(MB, N) rounded up to 128 >= N, so the loop in gen_policy is one chunk of rows = N, and its test reads
     // min(rows_max, N) = N <= GEN_FUSED_MAX_ROWS with key_rows = N and rows = N <= GEN_FUSED_MAX_ROWS with key_rows = 0.
-    s = gen_policy(c, h.next_obs, mask, nullptr, n, step, act64, g.step_lp + b, g.step_en + b, false, (int64_t)b, N);
+    // PPO_KERNEL_CAT_FUSED: the act launch stores the step too
+    const CatStepStores stores{ h.next_done, h.obs_t, B_<uint8_t>(c, PPO_BUF_MASKS) + tn * c->A, h.actions_t, logprob_t, h.dones_t };
+    bool stored = false;
+    s = gen_policy(c, h.next_obs, mask, nullptr, n, step, act64, g.step_lp + b, g.step_en + b, false, (int64_t)b, N, &stores, &stored);
     if (s != PPO_OK) return s;
-    HIPCHK(c, gen_store_step(g.L, n, h.next_obs, mask, act64, g.step_lp + b, h.next_done, h.obs_t, B_<uint8_t>(c, PPO_BUF_MASKS) + tn * c->A, h.actions_t,
-                             logprob_t, h.dones_t, c->stream));
+    if (!stored)
+        HIPCHK(c, gen_store_step(g.L, n, h.next_obs, mask, act64, g.step_lp + b, stores.done_prev, stores.obs_t, stores.mask_t, stores.act_t, stores.lp_t, stores.dones_t,
+                                 c->stream));
     if (!action_dev) HIPCHK(c, hipMemcpyAsync(c->host_act + b * c->H, act64, (size_t)n * c->H * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
     return PPO_OK;
 }

@@ -23,6 +23,20 @@ hipError_t gauss_fused_fwd_bwd(const GenLayout& L, const LossParams& hp, const f
                                const float* adv, const float* ret, const float* oldv, const int32_t* idx, int64_t M, double inv_global_M, double global_M,
                                const AdvStat* adv_stat, float* slab, double* loss_part, float* grads, hipStream_t s);
 
+// PPO_KERNEL_CAT_FUSED: the same kernel family for categorical / masked multi-head policies (GenLayout with gauss = 0; A = L.act <= PPO_MAX_ACT logits in the
+// place of the mean).  The critic is gauss_fused_values, the slab stride gauss_fused_slab_stride (no log_std behind the actor).
+bool cat_fused_serves_shape(int obs, int hidden, int n_hidden, int A);
+// the rollout stores of one step (gen_store_step's): rows of step t, every pointer at the first row of the launch; null: the stand-alone policy
+struct CatStepStores { const int32_t* done_prev; float* obs_t; uint8_t* mask_t; int32_t* act_t; float* lp_t; float* dones_t; };
+// gen_forward (actor) + gen_heads (+ gen_store_step) in one launch over n rows; every pointer names the first of them, row_offset is the sampler's row origin
+// (env_offset + the slice's first row); mask u8 [n, A] or null, forced i64 [n, H] or null; action (i64 [n, H]) / logprob / entropy may be null
+hipError_t cat_fused_act(const GenLayout& L, int dist_kind, const float* params, const float* obs, const uint8_t* mask, const int64_t* forced, int64_t n, int64_t seed,
+                         int64_t row_offset, int64_t step_index, bool greedy, int64_t* action, float* logprob, float* entropy, const CatStepStores* st, hipStream_t s);
+// gauss_fused_fwd_bwd for such a policy: actions i32 [B, H], masks u8 [B, A] (read for PPO_DIST_MASKED), both read in place through idx
+hipError_t cat_fused_fwd_bwd(const GenLayout& L, const LossParams& hp, const float* params, const float* obs, const int32_t* actions, const uint8_t* masks,
+                             const float* oldlp, const float* adv, const float* ret, const float* oldv, const int32_t* idx, int64_t M, double inv_global_M,
+                             double global_M, const AdvStat* adv_stat, float* slab, double* loss_part, float* grads, hipStream_t s);
+
 // The device envs with real-valued actions (PPO_ENV_PENDULUM, PPO_ENV_MOUNTAINCAR_CONTINUOUS; the traits are ppo_internal.hpp's GaussEnv*): the T steps of a
 // rollout in one launch (gauss_rollout_kernel<Env>: one workgroup per 64 envs, the actor's weights resident, the env in wave 0's registers); the context's
 // buffers, the teacher-forcing actions f32 [T, N, 1] or null.  The critic is not in it: two gauss_fused_values launches follow.

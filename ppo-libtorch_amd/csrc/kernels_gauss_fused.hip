@@ -14,6 +14,11 @@
 //   obs 3, D 1 (PPO_ENV_PENDULUM): 256 + 4096 + 256 + 288 + 272 + 4352 + 4352 + 272 = 14 144 floats = 56 576 bytes: two workgroups per CU.
 //   obs 2, D 1 (PPO_ENV_MOUNTAINCAR_CONTINUOUS): the same carve, gf_carve(4, 4); rows 2 and 3 of the X image are zero padding.
 //
+// PPO_KERNEL_CAT_FUSED: the same family for categorical / masked multi-head policies of a caller-stepped context (the actor's output = up to 32 logits): the
+// family depends on the distribution in two places only, what wave 0 does with the output tile in the act kernel (cat_act_kernel) and what the actor's
+// loss lane does in the update kernel (cat_fwd_bwd_kernel = gf_fwd_bwd_body<DIST>, the body gauss_fwd_bwd_kernel instantiates for the Gaussian); the critic
+// kernel is shared.  obs 17, 12 logits: 1280 + 4096 + 768 + 288 + 1360 + 4352 + 4352 + 816 = 17 312 floats = 69 248 bytes.
+//
 // The device envs with real-valued actions (ppo_internal.hpp: GaussEnvPendulum, GaussEnvMountainCarContinuous) add kernels on the same forward, each a
 // template over the env trait: gauss_rollout_kernel, the T steps of a rollout in one launch with the env in registers (below); the envs' small stand-alone
 // kernels; and, for an env whose observation is its state, gauss_trunc_fold_kernel (ppo_env_truncation_bootstrap) and gauss_eval_kernel (ppo_evaluate).
@@ -30,14 +35,18 @@ constexpr int GF_S = PPO_LDS_STRIDE;
 
 // what the kernels need of GenLayout: offsets (floats, into the flat parameter vector) of {W1, b1, W2, b2, W3, b3} per net, log_std behind the actor
 struct GfShape {
-    int obs, D;
+    int obs, D;              // D: the Gaussian action width; 0 for a categorical policy (no log_std is read then)
+    int A;                   // the actor's output width: D, or the sum of the categorical heads' widths
+    int n_heads;
+    int head_dims[PPO_MAX_HEADS];
     int off[2][6];
     int logstd_off;
 };
 
 GfShape gf_shape(const GenLayout& L) {
     GfShape sh{};
-    sh.obs = L.obs; sh.D = L.gauss;
+    sh.obs = L.obs; sh.D = L.gauss; sh.A = L.act; sh.n_heads = L.n_heads;
+    for (int h = 0; h < L.n_heads; h++) sh.head_dims[h] = L.head_dims[h];
     for (int net = 0; net < 2; net++)
         for (int l = 0; l < 3; l++) { sh.off[net][2 * l] = L.w_off[net][l]; sh.off[net][2 * l + 1] = L.b_off[net][l]; }
     sh.logstd_off = L.logstd_off;
@@ -76,7 +85,7 @@ __device__ __forceinline__ GfLds gf_carve(float* base, int obsP, int outP) {
 
 // one net's weights into LDS (zero padded), log_std and exp(-log_std); every thread of the workgroup calls it; the caller's next barrier publishes it
 __device__ __forceinline__ void gf_stage_weights(const GfLds& m, const GfShape& sh, const float* __restrict__ params, int net, int tid) {
-    const int obs = sh.obs, obsP = m.obsP, out = net == 0 ? 1 : sh.D;
+    const int obs = sh.obs, obsP = m.obsP, out = net == 0 ? 1 : sh.A;
     const float* W1 = params + sh.off[net][0];
     const float* W2 = params + sh.off[net][2];
     const float* W3 = params + sh.off[net][4];
@@ -240,6 +249,73 @@ __global__ __launch_bounds__(GF_THREADS) void gauss_values_kernel(GfShape sh, co
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// cat_act_kernel (PPO_KERNEL_CAT_FUSED): gauss_act_kernel's plan for a categorical / masked multi-head policy.  The forward leaves the logits [A][sample] in
+// OUT; wave 0, lane = row, then does what heads_kernel (kernels_generic.hip) does with a row of logits, on the same device functions (categorical_head,
+// sample_head, the same Philox keying), so equal logits give equal action, log-prob and entropy bits.  The row's logits stay where they are: z is the lane's
+// column of OUT (log-probs in place), p the lane's column of the H1 image, which nobody reads behind the forward's last barrier -- run-time head offsets index
+// LDS, no per-lane array exists.  Waves 1 .. 3 do the step's other stores meanwhile (store_step_kernel's: OBS[t], MASKS[t] -- all ones without a mask --
+// and DONES[t] from the previous done flags).  Every pointer names the first of the launch's n rows (an env group's slice: row_offset carries its origin).
+// ---------------------------------------------------------------------------------------------------------
+struct CfStepStores { const int32_t* done_prev; float* obs_t; uint8_t* mask_t; int32_t* act_t; float* lp_t; float* dones_t; };
+
+template <int DIST, bool GREEDY>
+__global__ __launch_bounds__(GF_THREADS) void cat_act_kernel(GfShape sh, const float* __restrict__ params, const float* __restrict__ obs,
+                                                             const uint8_t* __restrict__ mask, const int64_t* __restrict__ forced, int64_t n, int64_t seed,
+                                                             int64_t row_offset, int64_t step_index, int64_t* action, float* logprob, float* entropy, CfStepStores st) {
+    extern __shared__ __attribute__((aligned(16))) float gf_lds[];
+    const int tid = threadIdx.x, A = sh.A, O = sh.obs, H = sh.n_heads;
+    const GfLds m = gf_carve(gf_lds, gf_pad4(O), gf_pad4(A));
+    gf_stage_weights(m, sh, params, 1, tid);
+    const int64_t tiles = (n + 63) / 64;
+    for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const int64_t row0 = tile * 64;
+        gf_dense_rows(m, row0, n, tid);
+        gf_load_x(m, obs, O, tid);
+        gf_forward_tile(m, A, tid);
+        const int64_t r = row0 + (tid & 63);
+        if (tid < 64) {
+            if (r < n) {
+                float lp_sum = 0.0f, en_sum = 0.0f;
+                int off = 0;
+                for (int h = 0; h < H; h++) {
+                    const int Ah = sh.head_dims[h];
+                    float* z = m.o + off * GF_S + tid;
+                    float* p = m.h1 + off * GF_S + tid;
+                    const uint8_t* mrow = (DIST == PPO_DIST_MASKED && mask) ? mask + r * A + off : nullptr;
+                    const float en = categorical_head<DIST, GF_S>(z, p, mrow, Ah);
+                    int a;
+                    if constexpr (GREEDY) {
+                        a = 0;
+                        for (int k = 1; k < Ah; k++) if (p[k * GF_S] > p[a * GF_S]) a = k;
+                    } else if (forced) {
+                        a = (int)forced[r * H + h];
+                    } else {
+                        const uint4 w = philox4x32_10((uint32_t)seed, (uint32_t)((uint64_t)seed >> 32), (uint32_t)(row_offset + r), (uint32_t)(step_index >> 2), (uint32_t)h, 0u);
+                        const uint32_t ws = (step_index & 3) == 0 ? w.x : ((step_index & 3) == 1 ? w.y : ((step_index & 3) == 2 ? w.z : w.w));
+                        a = sample_head<GF_S>(p, Ah, (float)(ws >> 8) * 0x1p-24f);
+                    }
+                    if (action) action[r * H + h] = a;
+                    if (st.act_t) st.act_t[r * H + h] = a;
+                    float lp = 0.0f;
+                    for (int k = 0; k < Ah; k++) if (k == a) lp = z[k * GF_S];
+                    if (h == 0) { lp_sum = lp; en_sum = en; } else { lp_sum += lp; en_sum += en; }   // stack(...).sum(0), Agent.cpp:165-168
+                    off += Ah;
+                }
+                if (logprob) logprob[r] = lp_sum;
+                if (st.lp_t) st.lp_t[r] = lp_sum;
+                if (entropy) entropy[r] = en_sum;
+            }
+        } else if (st.obs_t) {   // waves 1 .. 3: the step's other stores
+            const int64_t rows = n - row0 < 64 ? n - row0 : 64;
+            for (int64_t i = tid - 64; i < rows * O; i += GF_THREADS - 64) st.obs_t[row0 * O + i] = obs[row0 * O + i];
+            for (int64_t i = tid - 64; i < rows * A; i += GF_THREADS - 64) st.mask_t[row0 * A + i] = mask ? mask[row0 * A + i] : (uint8_t)1;
+            if (tid < 128 && r < n) st.dones_t[r] = (float)st.done_prev[r];
+        }
+        __syncthreads();   // OUT, the H1 columns and the row list are read: the next tile may overwrite them
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // gauss_fwd_bwd_kernel: one minibatch step of one net per workgroup column (blockIdx.y = net): gather through the index list, forward, PPO loss
 // (gauss_loss_kernel's arithmetic), backward.  Gradients accumulate in registers over the workgroup's tiles and leave as one partial slab.
 // ---------------------------------------------------------------------------------------------------------
@@ -248,7 +324,8 @@ struct GfUpdArgs {
     LossParams hp;
     const float* params;
     const float* obs;        // [B, O] and the other flattened rollout buffers, read in place through idx
-    const float* actions;    // [B, D]
+    const float* actions;    // [B, D]; a categorical policy: the i32 actions [B, H] behind the same pointer
+    const uint8_t* masks;    // [B, A] (PPO_DIST_MASKED), else null
     const float* oldlp;
     const float* adv;
     const float* ret;
@@ -323,12 +400,71 @@ __device__ __forceinline__ void gf_dz_tile(const float* __restrict__ dout, int n
 
 constexpr int AM = PPO_MAX_ACT;
 
-__global__ __launch_bounds__(GF_THREADS) void gauss_fwd_bwd_kernel(GfUpdArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float gf_lds[];
+// The actor's loss lane of a categorical policy (cat_fwd_bwd_kernel): loss_kernel's arithmetic (kernels_generic.hip) on one row, whose logits arrive in z.
+// Every array is indexed by an unrolled k: a logit takes part in head h's pass when off <= k < off + head_dims[h], a wave-uniform predicate, so the arrays
+// stay in registers.  Leaves p = m_probs and q[k] = -p_k (log p_k + H_head(k)), the entropy's derivative (PPO_DIST_MASKED); `valid` = the mask bits (all
+// ones without a mask); returns the summed log-prob of the stored actions and the summed entropy.
+template <int DIST>
+__device__ __forceinline__ float cat_row_heads(const GfShape& sh, float (&z)[PPO_MAX_ACT], float (&p)[PPO_MAX_ACT], float (&q)[PPO_MAX_ACT], uint32_t valid,
+                                               const int32_t* __restrict__ act_row, uint32_t& chosen, float& ent_out) {
+    float nlp = 0.0f, ent = 0.0f;
+    int off = 0;
+    chosen = 0u;
+    for (int h = 0; h < sh.n_heads; h++) {
+        const int Ah = sh.head_dims[h], end = off + Ah;
+        float mx = -INFINITY;
+#pragma unroll
+        for (int k = 0; k < PPO_MAX_ACT; k++) {
+            if (k >= off && k < end) {
+                if (DIST == PPO_DIST_MASKED && !((valid >> k) & 1u)) z[k] = -1e8f;
+                mx = z[k] > mx ? z[k] : mx;
+            }
+        }
+        float se = 0.0f;
+#pragma unroll
+        for (int k = 0; k < PPO_MAX_ACT; k++) if (k >= off && k < end) { p[k] = expf(z[k] - mx); se += p[k]; }
+        const float lse = logf(se) + mx;
+        float e = 0.0f;
+#pragma unroll
+        for (int k = 0; k < PPO_MAX_ACT; k++) {
+            if (k >= off && k < end) {
+                z[k] = z[k] - lse;
+                p[k] = p[k] / se;
+                if (DIST == PPO_DIST_CATEGORICAL) {
+                    const float l = z[k] > 1.17549435e-38f ? z[k] : 1.17549435e-38f;   // torch::clamp(m_logits, FLT_MIN), Categorical.cpp:115
+                    e += l * p[k];
+                } else {
+                    const float plp = z[k] * p[k];
+                    e += ((valid >> k) & 1u) ? plp : 0.0f;
+                }
+            }
+        }
+        const float headH = -e;
+        const int a = off + act_row[h];
+        float lp = 0.0f;
+#pragma unroll
+        for (int k = 0; k < PPO_MAX_ACT; k++) {
+            if (k >= off && k < end) {
+                if (k == a) { lp = z[k]; chosen |= 1u << k; }
+                q[k] = -p[k] * (z[k] + headH);
+            }
+        }
+        if (h == 0) { nlp = lp; ent = headH; } else { nlp += lp; ent += headH; }
+        off = end;
+    }
+    ent_out = ent;
+    return nlp;
+}
+
+// DIST: PPO_DIST_GAUSSIAN (gauss_fwd_bwd_kernel) or PPO_DIST_CATEGORICAL / PPO_DIST_MASKED (cat_fwd_bwd_kernel); only the actor's loss lane and the
+// log_std gradient depend on it
+template <int DIST>
+__device__ __forceinline__ void gf_fwd_bwd_body(const GfUpdArgs& a, float* gf_lds) {
+    constexpr bool GAUSS = DIST == PPO_DIST_GAUSSIAN;
     const int tid = threadIdx.x, D = a.sh.D, O = a.sh.obs;
     const int net = blockIdx.y, b = blockIdx.x, nb = a.nb;
-    const int out = net == 0 ? 1 : D, outP = gf_pad4(out);
-    const GfLds m = gf_carve(gf_lds, gf_pad4(O), gf_pad4(D));
+    const int out = net == 0 ? 1 : a.sh.A, outP = gf_pad4(out);
+    const GfLds m = gf_carve(gf_lds, gf_pad4(O), gf_pad4(a.sh.A));
     const int obsP = m.obsP;
     gf_stage_weights(m, a.sh, a.params, net, tid);
     const int s = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -368,7 +504,53 @@ __global__ __launch_bounds__(GF_THREADS) void gauss_fwd_bwd_kernel(GfUpdArgs a) 
         // ---- loss: wave 0, lane = sample; d(loss)/d(output) replaces the output in OUT (zero for a sample without a row and for rows out .. outP - 1) ----
         if (w == 0) {
             const int r = m.ridx[s];
-            if (net == 1) {
+            if (net == 1 && !GAUSS) {
+                // categorical heads: new log-prob and entropy from the row's logits, its stored actions and (masked) its mask row; d(loss)/d(logits) -> OUT
+                float z[AM], p[AM], q[AM];
+                float g_nlp = 0.0f, g_ent = 0.0f;
+                uint32_t valid = 0xffffffffu, chosen = 0u;
+                if (r >= 0) {
+#pragma unroll
+                    for (int k = 0; k < AM; k++) z[k] = k < out ? m.o[k * GF_S + s] : 0.0f;
+                    if (DIST == PPO_DIST_MASKED && a.masks) {
+                        const uint8_t* mrow = a.masks + (int64_t)r * out;
+#pragma unroll
+                        for (int k = 0; k < AM; k++) if (k < out && mrow[k] == 0) valid &= ~(1u << k);
+                    }
+                    float ent;
+                    const float nlp = cat_row_heads<DIST>(a.sh, z, p, q, valid, reinterpret_cast<const int32_t*>(a.actions) + (int64_t)r * a.sh.n_heads, chosen, ent);
+                    const float logratio = nlp - a.oldlp[r];
+                    const float ratio = expf(logratio);
+                    float adv = a.adv[r];
+                    if (hp.norm_adv) adv = (adv - mean_f) * inv_std;
+                    const float rc = ratio < lo ? lo : (ratio > hi_c ? hi_c : ratio);
+                    const float l1 = -adv * ratio, l2 = -adv * rc;
+                    const bool inside = (ratio >= lo && ratio <= hi_c);
+                    float d_ratio;
+                    if (l1 > l2) d_ratio = -adv;
+                    else if (l1 < l2) d_ratio = inside ? -adv : 0.0f;
+                    else d_ratio = 0.5f * -adv + (inside ? 0.5f * -adv : 0.0f);   // torch::max splits ties half/half
+                    g_nlp = invM * d_ratio * ratio;
+                    g_ent = -hp.ent_coef * invM;
+                    sums[0] += (double)(l1 > l2 ? l1 : l2);
+                    sums[1] += (double)ent;
+                    sums[2] += (double)((ratio - 1.0f) - logratio);
+                    sums[3] += (fabsf(ratio - 1.0f) > clip) ? 1.0 : 0.0;
+                }
+#pragma unroll
+                for (int k = 0; k < AM; k++) {
+                    if (k < outP) {
+                        float d = 0.0f;
+                        if (r >= 0 && k < out) {
+                            d = g_nlp * ((((chosen >> k) & 1u) ? 1.0f : 0.0f) - p[k]);
+                            // CategoricalMasked's entropy is the true entropy: dH/dz_k = -p_k (log p_k + H); the plain Categorical's clamped form has none
+                            if (DIST == PPO_DIST_MASKED) d += g_ent * q[k];
+                            d = ((valid >> k) & 1u) ? d : 0.0f;
+                        }
+                        m.o[k * GF_S + s] = d;
+                    }
+                }
+            } else if (net == 1) {
                 float z[AM];
                 float g_nlp = 0.0f, g_ent = 0.0f;
                 if (r >= 0) {
@@ -482,7 +664,7 @@ __global__ __launch_bounds__(GF_THREADS) void gauss_fwd_bwd_kernel(GfUpdArgs a) 
         }
     }
     if (w == 0) {
-        if (net == 1) {
+        if (GAUSS && net == 1) {
 #pragma unroll
             for (int k = 0; k < AM; k++) {
                 if (k < D) {
@@ -503,6 +685,17 @@ __global__ __launch_bounds__(GF_THREADS) void gauss_fwd_bwd_kernel(GfUpdArgs a) 
             for (int row = b; row < GEN_LOSS_BLOCKS; row += nb) a.loss_part[row * 8 + s] = row == b ? v : 0.0;
         }
     }
+}
+
+__global__ __launch_bounds__(GF_THREADS) void gauss_fwd_bwd_kernel(GfUpdArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float gf_lds[];
+    gf_fwd_bwd_body<PPO_DIST_GAUSSIAN>(a, gf_lds);
+}
+// cat_fwd_bwd_kernel (PPO_KERNEL_CAT_FUSED): the same plan for a categorical / masked multi-head policy; there is no log_std tensor
+template <int DIST>
+__global__ __launch_bounds__(GF_THREADS) void cat_fwd_bwd_kernel(GfUpdArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float gf_lds[];
+    gf_fwd_bwd_body<DIST>(a, gf_lds);
 }
 
 // grads[i] = the slabs' elements in workgroup order (one thread per element; the actor's range runs on through log_std)
@@ -911,6 +1104,71 @@ hipError_t gauss_fused_fwd_bwd(const GenLayout& L, const LossParams& hp, const f
     const hipError_t e = gf_allow(done, gauss_fwd_bwd_kernel, bytes);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(gauss_fwd_bwd_kernel, dim3(a.nb, 2), dim3(GF_THREADS), bytes, s, a);
+    hipLaunchKernelGGL(gauss_slab_reduce_kernel, dim3((L.P + 255) / 256), dim3(256), 0, s, slab, a.slab_stride, a.nb, L.net_off[1], L.P, grads);
+    return hipGetLastError();
+}
+
+// ---- PPO_KERNEL_CAT_FUSED: categorical / masked multi-head policies on the same forward (the critic is gauss_fused_values: with L.gauss = 0 no log_std is read) ----
+bool cat_fused_serves_shape(int obs, int hidden, int n_hidden, int A) { return hidden == 64 && n_hidden == 2 && A >= 1 && A <= PPO_MAX_ACT && obs >= 1 && obs <= GAUSS_FUSED_MAX_OBS; }
+
+template <int DIST, bool GREEDY>
+static hipError_t cat_fused_act_launch(const GfShape& sh, int bytes, dim3 grid, const float* params, const float* obs, const uint8_t* mask, const int64_t* forced, int64_t n,
+                                       int64_t seed, int64_t row_offset, int64_t step_index, int64_t* action, float* logprob, float* entropy, const CfStepStores& ss,
+                                       hipStream_t s) {
+    static std::atomic<unsigned long long> done{ 0 };
+    const hipError_t e = gf_allow(done, cat_act_kernel<DIST, GREEDY>, bytes);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((cat_act_kernel<DIST, GREEDY>), grid, dim3(GF_THREADS), bytes, s, sh, params, obs, mask, forced, n, seed, row_offset, step_index, action, logprob,
+                       entropy, ss);
+    return hipGetLastError();
+}
+
+hipError_t cat_fused_act(const GenLayout& L, int dist_kind, const float* params, const float* obs, const uint8_t* mask, const int64_t* forced, int64_t n, int64_t seed,
+                         int64_t row_offset, int64_t step_index, bool greedy, int64_t* action, float* logprob, float* entropy, const CatStepStores* st, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    if (L.gauss || (dist_kind != PPO_DIST_CATEGORICAL && dist_kind != PPO_DIST_MASKED)) return hipErrorInvalidValue;
+    const GfShape sh = gf_shape(L);
+    const int bytes = gf_lds_floats(gf_pad4(L.obs), gf_pad4(L.act)) * 4;
+    const dim3 grid((unsigned)std::min<int64_t>((n + 63) / 64, 1024));
+    CfStepStores ss{};
+    if (st) ss = CfStepStores{ st->done_prev, st->obs_t, st->mask_t, st->act_t, st->lp_t, st->dones_t };
+    const bool masked = dist_kind == PPO_DIST_MASKED;
+    if (greedy)
+        return masked ? cat_fused_act_launch<PPO_DIST_MASKED, true>(sh, bytes, grid, params, obs, mask, nullptr, n, seed, row_offset, step_index, action, logprob, entropy, ss, s)
+                      : cat_fused_act_launch<PPO_DIST_CATEGORICAL, true>(sh, bytes, grid, params, obs, mask, nullptr, n, seed, row_offset, step_index, action, logprob, entropy, ss, s);
+    return masked ? cat_fused_act_launch<PPO_DIST_MASKED, false>(sh, bytes, grid, params, obs, mask, forced, n, seed, row_offset, step_index, action, logprob, entropy, ss, s)
+                  : cat_fused_act_launch<PPO_DIST_CATEGORICAL, false>(sh, bytes, grid, params, obs, mask, forced, n, seed, row_offset, step_index, action, logprob, entropy, ss, s);
+}
+
+hipError_t cat_fused_fwd_bwd(const GenLayout& L, const LossParams& hp, const float* params, const float* obs, const int32_t* actions, const uint8_t* masks,
+                             const float* oldlp, const float* adv, const float* ret, const float* oldv, const int32_t* idx, int64_t M, double inv_global_M,
+                             double global_M, const AdvStat* adv_stat, float* slab, double* loss_part, float* grads, hipStream_t s) {
+    if (M < 1 || M >= (1ll << 31) - 64 || !slab || !loss_part || L.gauss) return hipErrorInvalidValue;
+    if (hp.dist_kind != PPO_DIST_CATEGORICAL && hp.dist_kind != PPO_DIST_MASKED) return hipErrorInvalidValue;
+    GfUpdArgs a{};
+    a.sh = gf_shape(L);
+    a.hp = hp;
+    a.params = params; a.obs = obs; a.actions = reinterpret_cast<const float*>(actions); a.oldlp = oldlp; a.adv = adv; a.ret = ret; a.oldv = oldv; a.idx = idx;
+    a.masks = hp.dist_kind == PPO_DIST_MASKED ? masks : nullptr;
+    a.M = (int)M;
+    a.invM = (float)inv_global_M;
+    a.adv_stat = (adv_stat && hp.norm_adv) ? adv_stat : nullptr;
+    a.global_M = global_M;
+    a.slab = slab;
+    a.slab_stride = (int)gauss_fused_slab_stride(L);
+    a.nb = (int)std::min<int64_t>((M + 63) / 64, GAUSS_FUSED_MAX_BLOCKS);
+    a.loss_part = loss_part;
+    const int bytes = gf_lds_floats(gf_pad4(L.obs), gf_pad4(L.act)) * 4;
+    static std::atomic<unsigned long long> done_c{ 0 }, done_m{ 0 };
+    if (hp.dist_kind == PPO_DIST_MASKED) {
+        const hipError_t e = gf_allow(done_m, cat_fwd_bwd_kernel<PPO_DIST_MASKED>, bytes);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(cat_fwd_bwd_kernel<PPO_DIST_MASKED>, dim3(a.nb, 2), dim3(GF_THREADS), bytes, s, a);
+    } else {
+        const hipError_t e = gf_allow(done_c, cat_fwd_bwd_kernel<PPO_DIST_CATEGORICAL>, bytes);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(cat_fwd_bwd_kernel<PPO_DIST_CATEGORICAL>, dim3(a.nb, 2), dim3(GF_THREADS), bytes, s, a);
+    }
     hipLaunchKernelGGL(gauss_slab_reduce_kernel, dim3((L.P + 255) / 256), dim3(256), 0, s, slab, a.slab_stride, a.nb, L.net_off[1], L.P, grads);
     return hipGetLastError();
 }

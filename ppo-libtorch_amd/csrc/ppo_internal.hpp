@@ -419,40 +419,43 @@ __device__ __forceinline__ void env_reset(float* st, const float* __restrict__ r
 // Categorical / CategoricalMasked over one head of width A held in a small array (uniform across the wave or per-thread).
 // reference Distributions/Categorical.cpp:28-39,92-119; CategoricalMasked.cpp:31-46,107-144.
 //   z[a] in: raw logits; out: m_logits (log-probs).  p[a] out: m_probs.  returns entropy.
+//   ZS: the stride (floats) between two elements of z and of p; 1 = a plain array.  The fused 2 x 64 kernels keep both as columns of [logit][sample]
+//   LDS images (stride PPO_LDS_STRIDE), where a run-time index costs nothing; the arithmetic does not depend on it.
 // ---------------------------------------------------------------------------------------------------------
-template <int DIST>
+template <int DIST, int ZS = 1>
 __device__ __forceinline__ float categorical_head(float* z, float* p, const uint8_t* mask, int A) {
     float mx = -INFINITY;
     for (int a = 0; a < A; a++) {
-        if (DIST == PPO_DIST_MASKED && mask && !mask[a]) z[a] = -1e8f;
-        mx = z[a] > mx ? z[a] : mx;
+        if (DIST == PPO_DIST_MASKED && mask && !mask[a]) z[a * ZS] = -1e8f;
+        mx = z[a * ZS] > mx ? z[a * ZS] : mx;
     }
     float se = 0.0f;
-    for (int a = 0; a < A; a++) { p[a] = expf(z[a] - mx); se += p[a]; }
+    for (int a = 0; a < A; a++) { p[a * ZS] = expf(z[a * ZS] - mx); se += p[a * ZS]; }
     const float lse = logf(se) + mx;
     float ent = 0.0f;
     for (int a = 0; a < A; a++) {
-        z[a] = z[a] - lse;
-        p[a] = p[a] / se;
+        z[a * ZS] = z[a * ZS] - lse;
+        p[a * ZS] = p[a * ZS] / se;
         if (DIST == PPO_DIST_CATEGORICAL) {
-            const float l = z[a] > 1.17549435e-38f ? z[a] : 1.17549435e-38f;  // torch::clamp(m_logits, FLT_MIN), Categorical.cpp:115
-            ent += l * p[a];
+            const float l = z[a * ZS] > 1.17549435e-38f ? z[a * ZS] : 1.17549435e-38f;  // torch::clamp(m_logits, FLT_MIN), Categorical.cpp:115
+            ent += l * p[a * ZS];
         } else {
-            const float plp = z[a] * p[a];
+            const float plp = z[a * ZS] * p[a * ZS];
             ent += (mask == nullptr || mask[a]) ? plp : 0.0f;
         }
     }
     return -ent;
 }
 
-// Inverse-CDF draw on m_probs with u in [0,1) (mirrors oracle/ppo_oracle.c:orc_act).
+// Inverse-CDF draw on m_probs with u in [0,1) (mirrors oracle/ppo_oracle.c:orc_act).  ZS: as above.
+template <int ZS = 1>
 __device__ __forceinline__ int sample_head(const float* p, int A, float u) {
     int a = 0, last = 0;
     float acc = 0.0f;
     bool hit = false;
     for (int k = 0; k < A; k++) {
-        if (p[k] > 0.0f) last = k;
-        acc += p[k];
+        if (p[k * ZS] > 0.0f) last = k;
+        acc += p[k * ZS];
         if (!hit && u < acc) { a = k; hit = true; }
     }
     return hit ? a : last;

@@ -77,6 +77,7 @@ void PPOAlgorithm::getArgs() {
         B("environment", "norm_obs", m_norm_obs);                         // extension key (PPO_HostEnv), likewise
         B("environment", "norm_reward", m_norm_reward);                   // extension key (PPO_HostEnv), likewise
         B("environment", "fused_policy", m_fused_policy);                 // extension key (PPO_HostEnvBox), likewise
+        B("environment", "fused_categorical", m_fused_categorical);       // extension key (PPO_HostEnv), likewise
         I("general", "seed", m_seed);
         I("general", "total_timesteps", m_total_timesteps);
         B("general", "use_cuda", m_use_cuda);
@@ -148,6 +149,7 @@ void PPOAlgorithm::construct() {
     c.learning_rate = m_learning_rate; c.gamma = m_gamma; c.gae_lambda = m_gae_lambda; c.clip_coef = m_clip_coef;
     c.ent_coef = m_ent_coef; c.vf_coef = m_vf_coef; c.max_grad_norm = m_max_grad_norm;
     c.kernel_flags = m_fused_policy ? PPO_KERNEL_GAUSS_FUSED : 0;   // a class whose policy is not Gaussian: the library's refusal is thrown below, with its message
+    if (m_fused_categorical) c.kernel_flags |= PPO_KERNEL_CAT_FUSED;   // likewise for a class whose context is not a caller-stepped categorical one
     ppo::check(ppo_ctx_create(&c, &m_ctx), nullptr, "PPO");    // obs-size mismatch surfaces here with the reference's message (:370-375)
     ppo::check(ppo_params_init_orthogonal(m_ctx, m_seed), m_ctx, "agent init");
     m_agent = std::make_shared<Agent>(m_ctx, m_device, std::vector<int64_t>{ m_action_size });

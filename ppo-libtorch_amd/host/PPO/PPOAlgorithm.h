@@ -103,6 +103,7 @@ class PPOAlgorithm {
     int64_t m_max_episode_steps;
     int64_t m_env_groups = 1;            // extension ([environment] env_groups): PPO_HostEnv's env groups; the device-env algorithms have no use for it
     bool m_norm_obs = false;             // extension ([environment] norm_obs): PPO_HostEnv normalises observations with running statistics (ppo_obs_norm_*)
+    bool m_fused_categorical = false;    // extension ([environment] fused_categorical): PPO_HostEnv's context runs the fused categorical 2 x 64 kernels (PPO_KERNEL_CAT_FUSED); on any other class the library refuses the context
     bool m_fused_policy = false;         // extension ([environment] fused_policy): PPO_HostEnvBox's context runs the fused Gaussian 2 x 64 kernels (PPO_KERNEL_GAUSS_FUSED); on any other class the library refuses the context
     bool m_norm_reward = false;          // extension ([environment] norm_reward): PPO_HostEnv divides rewards by the running std of the discounted return (ppo_reward_norm_*)
     bool m_bootstrap_truncated = false;  // extension ([environment] bootstrap_truncated): bootstrap the value where a time limit cut an episode off (every algorithm class; set it with setBootstrapTruncated)

@@ -30,6 +30,9 @@
 // Reward normalisation (setNormReward(true), or `norm_reward = true` in [environment]; default false): every step's rewards are divided by the running
 // standard deviation of the discounted return and clipped to +-10 before the rollout buffer sees them; the episode statistics keep the raw reward
 // (include/ppo_hip.h, "Reward normalisation").  Saved as "<agent file>.rewnorm" (RewardNormFile), loaded when present, refused with env groups likewise.
+//
+// `fused_categorical = true` in [environment] (default false) runs the context on the fused categorical 2 x 64 kernels (PPO_KERNEL_CAT_FUSED in ppo_hip.h:
+// obs_size <= 64); ppo_gauss_fused_launches(m_ctx, ...), the family's counters, tells.  Same parameter order: checkpoints move between runs with and without the key.
 #pragma once
 #include <algorithm>
 #include <atomic>
@@ -53,7 +56,7 @@ class PPO_HostEnv : public PPOAlgorithm {
 
     explicit PPO_HostEnv(EnvFactory factory = nullptr)
         : PPOAlgorithm(PPO_ENV_HOST, Masked ? PPO_DIST_MASKED : PPO_DIST_CATEGORICAL, 4, 500) {
-        getArgs();   // (reads the extension keys env_groups, bootstrap_truncated, norm_obs and norm_reward too)
+        getArgs();   // (reads the extension keys env_groups, bootstrap_truncated, norm_obs, norm_reward and fused_categorical too)
         construct();
         const bool norm_obs = m_norm_obs;   // the key; the member follows the context from here on (setNormObs)
         m_norm_obs = false;
