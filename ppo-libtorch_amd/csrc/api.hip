@@ -1152,11 +1152,14 @@ static ppo_status gen_values(ppo_ctx* c, const float* obs, int64_t n, float* val
 }
 // row0 / key_rows (env groups: the n rows are rows row0 .. of a batch of key_rows): the sampler's row origin, and the row count that picks between the fused
 // forward and the per-layer products -- the one launch choice here that follows the row count and changes bits -- so that a group's rows get what the
-// whole batch would.  It only matters for N > GEN_FUSED_MAX_ROWS (rows_max >= N: the ungrouped call is one chunk of N rows), which no test reaches.
-// gen_forward's own choices by row count are left alone, on a reading of gemm_kernel, not on a test beyond the sizes the suite has: launch_prec takes the
-// double-buffered variant for M <= 8192 (three-term product), and both variants walk the k chunks in ascending order with the same MFMAs per chunk; its
-// 32 x 128 tile for M <= 32 is never taken here (gen_forward always passes weight planes).  tests/test_gpu_host_env_groups.py covers groups of 7 .. 32
-// rows in batches of 50 / 64; equality for N > 8192 cut into groups <= 8192 rests on that reading.
+// whole batch would.  It only matters for N > GEN_FUSED_MAX_ROWS = 2^20 (rows_max >= N: the ungrouped call is one chunk of N rows).  THAT switch stays
+// untested: a context of more than 2^20 envs needs workspaces of several gigabytes, too much for a suite that shares its machines.
+// gen_forward's own choices by row count are left alone: launch_prec takes the double-buffered variant for M <= 8192 (three-term product), and both variants
+// walk the k chunks in ascending order with the same MFMAs per chunk, so a row's bits do not depend on the variant; its 32 x 128 tile for M <= 32 is never
+// taken here (gen_forward always passes weight planes).  Two tests hold that: tests/test_gpu_matmul.py::test_matmul_main_loops_agree_bit_for_bit (8320 rows
+// in one product against the same rows as 8192 + 128, every operand orientation, with and without the bias + tanh epilogue) and
+// tests/test_gpu_host_env_groups.py::test_grouped_generic_f32_across_the_gemm_threshold (8320 envs ungrouped against two groups of 4160, weight planes,
+// every buffer and the parameters after the update); the same file covers groups of 7 .. 32 rows in batches of 50 / 64.
 // PPO_KERNEL_CAT_FUSED: forward, heads and -- when `stores` is given -- the step's rollout stores in ONE launch over the n rows, whose sampler origin is
 // env_offset + row0; returns true in *stored then (the caller skips gen_store_step)
 static ppo_status gen_policy(ppo_ctx* c, const float* obs, const uint8_t* mask, const int64_t* forced, int64_t n, int64_t step_index, int64_t* action,

@@ -13,7 +13,9 @@ import numpy as np
 import pytest
 
 from __graft_entry__ import load_package
+from test_gpu_beyond_first_trip import ACT16_CAP, FUSED_CAP, VECTOR_CAP, assert_past_the_cap
 from test_gpu_host_env import BUFS, NumpyFin, assert_same_state, bits
+from test_gpu_matmul import DB_MAX_ROWS
 
 pytestmark = pytest.mark.gpu
 
@@ -305,6 +307,63 @@ def test_grouped_reference_shape_random_masks(P, vector):
     its own (the staged mask is offset by the group's first row on both sides of the host link)"""
     run_generic_against_ungrouped(P, [0, 9, 25, 40], 12, "pipeline", True, obs_size=2, head_dims=(3,), dist_kind=P.DIST_MASKED, update_epochs=2, seed=5,
                                   kernel_flags=P.KERNEL_ROLLOUT_VECTOR if vector else 0)
+
+
+# ---- batches past a launcher's grid cap or launch threshold, cut into groups that stay under it (tests/test_gpu_beyond_first_trip.py has the caps) ----
+def groups_under_whole_over(bounds, cap):
+    """the ungrouped call over bounds[-1] rows gives workgroup 0 a second tile, every group's call is one tile per workgroup"""
+    assert_past_the_cap(bounds[-1], cap)
+    return all(hi - lo <= cap[0] * cap[1] for lo, hi in zip(bounds, bounds[1:]))
+
+
+def test_grouped_generic_f32_across_the_gemm_threshold(P):
+    """obs 6, heads (3, 2), f32, 8320 envs in two groups of 4160: the ungrouped side runs every layer product of ppo_host_act at 8320 rows (gemm_kernel's
+    two-workgroup loop, weight planes), each group at 4160 rows (the double-buffered loop) -- the header's promise that env groups reproduce the ungrouped
+    rollout bit for bit, at the one launch choice of gen_forward that follows the row count (tests/test_gpu_matmul.py holds the loops to each other on
+    plain operands)."""
+    bounds = [0, 4160, 8320]
+    assert bounds[-1] > DB_MAX_ROWS and all(hi - lo <= DB_MAX_ROWS for lo, hi in zip(bounds, bounds[1:]))
+    run_generic_against_ungrouped(P, bounds, 2, "pipeline", False, iters=1, obs_size=6, head_dims=(3, 2), update_epochs=1, seed=3, max_episode_steps=9)
+
+
+def test_grouped_cat_fused_past_the_grid_cap(P):
+    """PPO_KERNEL_CAT_FUSED, obs 17, heads (5, 3, 4), masked, 65 605 envs in groups of 32 768 and 32 837: the ungrouped ppo_host_act is ONE launch of
+    cat_act_kernel whose workgroups 0 and 1 walk a second tile (sampled actions, the per-tile OBS / MASKS / DONES stores); the groups' launches stay on the
+    first trip and carry their row origin.  ppo_host_rollout_end's critic batch is 3 x 65 605 = 196 815 rows: four trips of gauss_values_kernel."""
+    bounds = [0, 32768, 65605]
+    assert groups_under_whole_over(bounds, FUSED_CAP)
+    assert 3 * bounds[-1] > 3 * FUSED_CAP[0] * FUSED_CAP[1]
+    run_generic_against_ungrouped(P, bounds, 2, "pipeline", True, iters=1, obs_size=17, head_dims=(5, 3, 4), dist_kind=P.DIST_MASKED, update_epochs=1, seed=3,
+                                  kernel_flags=P.KERNEL_CAT_FUSED)
+
+
+@pytest.mark.parametrize("case", ["cartpole", "cartpole_vector", "mountaincar_masked", "mountaincar_masked_vector"])
+def test_grouped_reference_shape_past_the_grid_cap(P, case):
+    """The reference-shape act kernels as ppo_host_act launches them (HOST = true: the row's OBS / MASKS / ACTIONS stores and the commit of the previous
+    step in the same launch), ungrouped over more rows than the grid has workgroups against groups under the cap: 65 557 rows of policy_act16_kernel
+    (4096 workgroups x 16 rows), 8197 rows of policy_act_kernel under PPO_KERNEL_ROLLOUT_VECTOR (8192 one-row workgroups)."""
+    vector = case.endswith("_vector")
+    bounds, cap = ([0, 4100, 8197], VECTOR_CAP) if vector else ([0, 32768, 65557], ACT16_CAP)
+    assert groups_under_whole_over(bounds, cap)
+    masked = case.startswith("mountaincar")
+    cfg = dict(obs_size=2, head_dims=(3,), dist_kind=P.DIST_MASKED) if masked else dict(obs_size=4, head_dims=(2,))
+    run_generic_against_ungrouped(P, bounds, 2, "pipeline", masked, iters=1, update_epochs=1, seed=5, kernel_flags=P.KERNEL_ROLLOUT_VECTOR if vector else 0, **cfg)
+
+
+@pytest.mark.parametrize("case", ["cartpole", "cartpole_vector", "mountaincar_masked_vector"])
+def test_device_rollout_of_many_envs_against_shard_stepped_groups(P, case):
+    """ppo_train_iteration on 65 557 envs (rollout16_kernel: 4098 tiles of 16 envs; the critic batch of 3 x 65 557 rows walks values_mfma_kernel's capped
+    grid several times) and, in the vector form, on 8197 envs (rollout2_kernel), against a caller-stepped context whose groups are stepped by shard contexts.
+    A time limit of one step ends every episode at once, so the auto-reset and the finished-episode rows of every tile are exercised in T = 2 steps."""
+    vector = case.endswith("_vector")
+    bounds, cap = ([0, 4100, 8197], VECTOR_CAP) if vector else ([0, 32768, 65557], ACT16_CAP)
+    assert groups_under_whole_over(bounds, cap)   # the env counts of test_grouped_reference_shape_past_the_grid_cap (the rollout launches themselves are uncapped)
+    if case.startswith("mountaincar"):
+        fa, fb, st = run_against_device(P, P.ENV_MOUNTAINCAR, bounds, 2, order="pipeline", iters=1, vector=vector, masked=True, max_episode_steps=1, gamma=0.99,
+                                        ent_coef=0.01)
+    else:
+        fa, fb, st = run_against_device(P, P.ENV_CARTPOLE, bounds, 2, iters=1, vector=vector, max_episode_steps=1)
+    assert fa == fb == 0 and st["updates"] == 1 and st["ep_count"] > 0
 
 
 def test_given_finished_episodes_that_differ_from_the_running_sums(P):

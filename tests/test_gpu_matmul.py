@@ -102,6 +102,41 @@ def test_matmul_both_main_loops(P, ctx, ta, tb):
         assert np.all(np.abs(c - ref) <= 2e-6 * bound + 1e-30), (M, N, K)
 
 
+DB_MAX_ROWS = 8192   # kernels_gemm.hip, launch_prec: the double-buffered eight-wave loop for M <= 8192 (PPO_MM_F32X3), the two-workgroup loop above
+
+
+@pytest.mark.parametrize("bias_tanh", [False, True], ids=["plain", "bias+tanh"])
+@pytest.mark.parametrize("ta,tb", [(False, False), (False, True), (True, True)])
+def test_matmul_main_loops_agree_bit_for_bit(P, ctx, ta, tb, bias_tanh):
+    """The two main loops against EACH OTHER (test_matmul_both_main_loops holds each to float64): M = 8320 rows in one product take the two-workgroup loop,
+    with ragged m and n tiles (8320 = 65 x 128, N = 136 = 128 + 8, K = 72 ends inside a chunk); the same rows as [0, 8192) and [8192, 8320) take the
+    double-buffered loop.  Both run the same MFMAs per chunk in ascending k, so a row of C has the same bits either way -- which is what lets an env group's
+    forward (at most 8192 rows) reproduce the ungrouped batch's (tests/test_gpu_host_env_groups.py::test_grouped_generic_f32_across_the_gemm_threshold)."""
+    B_ = P.binding
+    M, N, K = 8320, 136, 72
+    cuts = [0, DB_MAX_ROWS, M]
+    assert M > DB_MAX_ROWS and all(32 < hi - lo <= DB_MAX_ROWS for lo, hi in zip(cuts, cuts[1:])) and N > 32   # neither narrow-tile variant on either side
+    rng = np.random.default_rng(M + N + K + 2 * ta + tb)
+    A = rng.standard_normal((M, K)).astype(np.float32)
+    B = (rng.standard_normal((N, K)) * 0.3).astype(np.float32)
+    bias = rng.standard_normal(N).astype(np.float32)
+    b = np.ascontiguousarray(B.T) if tb else B
+    kw = dict(epilogue=B_.MM_EPI_BIAS_TANH, aux=bias) if bias_tanh else {}
+
+    def product(rows):
+        return B_.matmul(ctx, np.ascontiguousarray(rows.T) if ta else rows, b, ta, tb, **kw)
+
+    whole = product(A)
+    parts = np.concatenate([product(A[lo:hi]) for lo, hi in zip(cuts, cuts[1:])])
+    assert whole.shape == parts.shape == (M, N)
+    differ = (whole.view(np.uint32) != parts.view(np.uint32)).any(axis=1)
+    assert not differ.any(), (int(differ.sum()), "first differing row %d" % int(np.argwhere(differ)[0][0]))
+    if not bias_tanh:   # and it is the product: the file's float64 bound on the large call
+        ref = A.astype(np.float64) @ B.astype(np.float64).T
+        bound = np.abs(A).astype(np.float64) @ np.abs(B).astype(np.float64).T
+        assert np.all(np.abs(whole - ref) <= 2e-6 * bound + 1e-30)
+
+
 def test_matmul_degenerate_sizes_and_bad_arguments(P, ctx):
     B_ = P.binding
     # K = 0: the product is empty, the epilogue still applies
