@@ -193,7 +193,8 @@ typedef struct ppo_config {
  *                               Against the same context without the flag: means and values agree to f32 summation order (both within the forward bar of
  *                               float64), not bit for bit.  Opt-in; any other shape or policy with the flag set is refused by ppo_ctx_create with
  *                               PPO_ERR_UNSUPPORTED and a message that names the limit -- never served by the generic engine instead.
- *                               ppo_gauss_fused_launches counts the three kernels' launches.
+ *                               ppo_gauss_fused_launches counts the three kernels' launches.  Truncation flags in ppo_dev_observe are served: the fold is
+ *                               one launch on the critic kernel's forward (gauss_dev_fold_kernel), counted as a `value` launch.
  *   PPO_KERNEL_SEPARATE_LAUNCHES  the once-per-iteration launches of a CartPole / MountainCar context in their stand-alone form, eight of them: the episode
  *                               ring's two kernels in front of the NEXT rollout (or the next statistics read), the critic batch, the record pack, the
  *                               permutations / advantage sums and the normalisation each a launch of its own.  Without the flag ppo_rollout's critic launch
@@ -214,8 +215,9 @@ typedef struct ppo_config {
  *                               same context without the flag: log-probs and values agree to f32 summation order, not bit for bit.  Opt-in; a Gaussian
  *                               policy, a device env, PPO_ENV_SYNTHETIC, another width or depth, bf16, obs_size > 64 or PPO_KERNEL_GAUSS_FUSED beside it make
  *                               ppo_ctx_create return PPO_ERR_UNSUPPORTED with a message that names the limit -- never served by another engine instead.
- *                               ppo_evaluate and truncation flags in ppo_dev_observe stay refused as on the generic engine.  ppo_gauss_fused_launches
- *                               counts the three kernels' launches (one set of counters for the family; no symbol of its own). */
+ *                               ppo_evaluate stays refused as on the generic engine; truncation flags in ppo_dev_observe are served as on a
+ *                               PPO_KERNEL_GAUSS_FUSED context (the critic kernel is shared, and so is the fold: gauss_dev_fold_kernel).
+ *                               ppo_gauss_fused_launches counts the three kernels' launches (one set of counters for the family; no symbol of its own). */
 enum { PPO_KERNEL_ROLLOUT_VECTOR = 1, PPO_KERNEL_UPDATE_VECTOR = 2, PPO_KERNEL_UPDATE_ONE_WAVE = 4, PPO_KERNEL_COMM_SELFTEST = 8, PPO_KERNEL_GENERIC_CLASSIC = 16,
        PPO_KERNEL_GENERIC_SPLIT_HEAD = 32, PPO_KERNEL_GAUSS_FUSED = 64 };
 #define PPO_KERNEL_SEPARATE_LAUNCHES 128   /* the next free bit of kernel_flags, 1 << 7; a macro beside the enumerators: same type in an expression, same use */
@@ -366,7 +368,9 @@ PPO_API ppo_status ppo_gaussian(const float* mean, const float* log_std, const f
  * moves `value` by 2 and `act` not at all.  The same holds on PPO_ENV_MOUNTAINCAR_CONTINUOUS, whose truncation fold (gauss_trunc_fold_kernel) and evaluation
  * launch (gauss_eval_kernel) are none of the three either: a rollout moves `value` by 2 with ppo_env_truncation_bootstrap on or off, ppo_evaluate moves nothing.
  * A PPO_KERNEL_CAT_FUSED context counts its three kernels of the same family here (the two flags exclude each other, so a context has one set of counters): act =
- * one per env step or env group's step / ppo_policy_act / ppo_policy_act_greedy, value and update as above.  No symbol was added for it. */
+ * one per env step or env group's step / ppo_policy_act / ppo_policy_act_greedy, value and update as above.  No symbol was added for it.
+ * On either family every ppo_dev_observe that passes `truncated` adds 1 to `value`: its fold launch (gauss_dev_fold_kernel) is the critic kernel's forward
+ * on the flagged rows, whether or not a row is flagged. */
 PPO_API ppo_status ppo_gauss_fused_launches(ppo_ctx* ctx, int64_t* act, int64_t* value, int64_t* update);
 
 /* Categorical::sample / CategoricalMasked::sample (Categorical.cpp:73-79: multinomial(probs, 1, replacement = true)) on given
@@ -700,9 +704,16 @@ PPO_API ppo_status ppo_bootstrap_rewards(ppo_ctx* ctx, const float* final_obs, c
  * refuse it with PPO_ERR_INVALID, the device call cannot look without a host wait.  Rows of final_obs that are not flagged are never read.  The step's
  * common case, no flagged row, costs one pass over truncated and done.  The events go to a device list; ppo_host_truncations after a device-fed rollout
  * waits for that rollout's last fold only (not for the update), copies the list and returns it with indices ascending, as after a host-fed rollout.
- * Generic networks (anything but the reference's 2 x 64 with obs 2, 4, 8) take the ppo_dev_* calls fully EXCEPT a non-NULL `truncated`, which returns
- * PPO_ERR_UNSUPPORTED and changes nothing: the generic engine chooses its critic kernel by the row count, that choice changes bits, and a critic launch
- * that needs no count is a separate piece of work.  Device callers of generic networks can still fold with ppo_bootstrap_rewards where they know K. */
+ * The fused families (PPO_KERNEL_GAUSS_FUSED and PPO_KERNEL_CAT_FUSED contexts: 2 x 64 f32, obs_size 1 .. 64) take the flags like the reference's own
+ * shapes: their critic is ONE kernel whatever the row count (gauss_values_kernel, the kernel behind ppo_get_value and ppo_bootstrap_rewards on such a
+ * context), and the fold launch (gauss_dev_fold_kernel: ceil(N / 256) workgroups, the critic's weights staged only by a workgroup that found a flagged
+ * row) runs that kernel's forward on the flagged rows, so V is ppo_get_value's bit for bit and a device-fed rollout equals the host-fed one bit for bit
+ * (tests/test_gpu_fused_dev_truncation.py).  An observe is one launch there too, two with `truncated`, three with observation normalisation on top (the
+ * flagged rows of final_obs are normalised in front of the commit); each fold launch counts in ppo_gauss_fused_launches' `value`.
+ * The plain generic engine (any other network: another width or depth, bf16, or a 2 x 64 f32 network without either flag) takes the ppo_dev_* calls fully
+ * EXCEPT a non-NULL `truncated`, which returns PPO_ERR_UNSUPPORTED and changes nothing: that engine chooses its critic kernel by the row count, that
+ * choice changes bits, and the host does not have the count here.  Device callers of such networks can still fold with ppo_bootstrap_rewards where they
+ * know K. */
 /* ppo_host_env_reset from a device array: obs f32 [N,O] = every env's reset observation.  Enqueued. */
 PPO_API ppo_status ppo_dev_env_reset(ppo_ctx* ctx, const float* obs /* [N,O] */, void* caller_stream);
 /* ppo_host_act with the actions left on the device: mask u8 [N,A] or NULL (masked policies; NULL = all valid), action i64 [N,H]. */
@@ -734,7 +745,9 @@ PPO_API ppo_status ppo_dev_observe(ppo_ctx* ctx, const float* next_obs /* [N,O] 
  * rollout of the same data therefore merge the same batches in the same order and agree bit for bit, statistics included.
  * Truncation bootstrap: a final observation is normalised WITHOUT updating the statistics, by the statistics as they stand when its fold runs.  The two
  * feeds differ here: ppo_dev_observe folds per step, so a device-fed rollout uses the statistics right behind the same step's update; the host path folds
- * once per rollout, so a host-fed rollout uses the statistics at ppo_host_rollout_end (all T steps merged).  ppo_bootstrap_rewards on caller buffers
+ * once per rollout, so a host-fed rollout uses the statistics at ppo_host_rollout_end (all T steps merged).  This holds for every context whose
+ * ppo_dev_observe takes the flags: the reference's shapes and the PPO_KERNEL_GAUSS_FUSED / PPO_KERNEL_CAT_FUSED families (with frozen statistics, mode 2,
+ * the two feeds agree bit for bit there as well).  ppo_bootstrap_rewards on caller buffers
  * stays raw: the caller normalises with ppo_obs_norm_apply first.
  * Errors (a failing call changes nothing): PPO_ERR_UNSUPPORTED for any of the four calls on a context that is not PPO_ENV_HOST (device envs are of unit
  * scale and their fused rollout never leaves the chip), for ppo_obs_norm_enable(mode != 0) on a sharded context (global_num_envs > num_envs or a

@@ -560,7 +560,10 @@ class Context:
         _check(lib().ppo_dev_act_f32(self.h, self._dev_ptr(action), self._dev_stream(stream)), self.h)
 
     def dev_observe(self, obs, reward, done, fin_len=None, fin_rew=None, truncated=None, final_obs=None, stream=None):
-        """The envs' outputs for the step just acted on, as device arrays (obs f32 [N,O], reward f32 [N], done i32 [N], ...), consumed in stream order."""
+        """The envs' outputs for the step just acted on, as device arrays (obs f32 [N,O], reward f32 [N], done i32 [N], ...), consumed in stream order.
+        truncated i32 [N] / final_obs f32 [N,O]: one more launch folds gamma * V(final_obs[n]) into the step's reward where truncated[n] and done[n] are both
+        set.  Served on the reference's 2 x 64 shapes (obs 2, 4, 8) and on KERNEL_GAUSS_FUSED / KERNEL_CAT_FUSED contexts (any obs_size up to 64); any other
+        network refuses the flags with status 5."""
         _check(lib().ppo_dev_observe(self.h, *(self._dev_ptr(x) for x in (obs, reward, done, fin_len, fin_rew, truncated, final_obs)),
                                      self._dev_stream(stream)), self.h)
 

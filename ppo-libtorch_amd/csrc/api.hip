@@ -3150,7 +3150,7 @@ extern "C" ppo_status ppo_env_truncations(ppo_ctx* c, int64_t* count, int32_t* i
 // 524-548, with the envs on the chip).  Every call only enqueues: no host wait, no host copy of per-step data.  The hand-over between the caller's stream
 // and the context's (non-blocking) stream is a pair of events per call; caller_stream == the context's stream needs none.  ppo_dev_act is act_slice
 // with commit = 0 on the caller's action array; ppo_dev_observe is host_commit_kernel on the caller's arrays, at once, and -- with flags -- the fold kernel
-// that finds the flagged rows itself (launch_dev_fold*).  ppo_host_rollout_end then has nothing to commit and nothing to fold.
+// that finds the flagged rows itself (launch_dev_fold*; gauss_fused_dev_fold for the two fused families).  ppo_host_rollout_end then has nothing to commit and nothing to fold.
 // ---------------------------------------------------------------------------------------------------------
 static ppo_status dev_handover_in(ppo_ctx* c, hipStream_t caller) {
     if (caller == c->stream) return PPO_OK;
@@ -3280,7 +3280,7 @@ extern "C" ppo_status ppo_dev_observe(ppo_ctx* c, const float* next_obs, const f
     NEED(c, next_obs && reward && done, "ppo_dev_observe: null argument");
     NEED(c, (fin_len == nullptr) == (fin_rew == nullptr), "ppo_dev_observe: fin_len and fin_rew: both or neither");
     NEED(c, truncated == nullptr || final_obs != nullptr, "ppo_dev_observe: truncated is given and final_obs is null");
-    if (truncated && c->gen)
+    if (truncated && c->gen && !c->gauss_fused && !c->cat_fused)   // the two fused families have ONE critic kernel, whatever the row count: they fold below
         return fail(c, PPO_ERR_UNSUPPORTED, "ppo_dev_observe: truncation flags on a generic network (its critic launch is chosen by a row count the host does not "
                                             "have here); fold with ppo_bootstrap_rewards where the count is known");
     DeviceGuard dev_guard(c);
@@ -3318,7 +3318,10 @@ extern "C" ppo_status ppo_dev_observe(ppo_ctx* c, const float* next_obs, const f
         f.rewards = B_<float>(c, PPO_BUF_REWARDS);
         f.ev_count = c->dev_count + l; f.ev_index = c->dev_index[l]; f.ev_value = c->dev_value[l]; f.ev_cap = c->dev_cap;
         // the critic bootstrap_launch would pick for this context
-        if (c->O == 4 || c->O == 2) HIPCHK(c, launch_dev_fold_mfma(B_<float>(c, PPO_BUF_PARAMS), c->L, f, c->stream));
+        if (c->gen) {   // PPO_KERNEL_GAUSS_FUSED / PPO_KERNEL_CAT_FUSED: gen_values' kernel, counted like its launches
+            c->gf_launches[1] += 1;
+            HIPCHK(c, gauss_fused_dev_fold(c->gen->L, B_<float>(c, PPO_BUF_PARAMS), f, c->stream));
+        } else if (c->O == 4 || c->O == 2) HIPCHK(c, launch_dev_fold_mfma(B_<float>(c, PPO_BUF_PARAMS), c->L, f, c->stream));
         else HIPCHK(c, launch_dev_fold(B_<float>(c, PPO_BUF_PARAMS), c->L, f, c->stream));
     }
     s = dev_handover_out(c, caller);

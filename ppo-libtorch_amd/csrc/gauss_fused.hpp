@@ -17,6 +17,11 @@ hipError_t gauss_fused_act(const GenLayout& L, const float* params, const float*
                            int64_t step_index, bool greedy, float* action, float* logprob, float* entropy, const GaussStepStores* st, hipStream_t s);
 // the critic over n rows in one launch
 hipError_t gauss_fused_values(const GenLayout& L, const float* params, const float* obs, int64_t n, float* value, hipStream_t s);
+// ppo_dev_observe with truncation flags on either fused family (gauss_dev_fold_kernel): ONE launch of ceil(N / 256) workgroups finds the rows with
+// truncated && done (ppo_internal.hpp: DevFoldArgs), runs gauss_fused_values' forward on those rows of final_obs [N, O] only -- v is that launch's value of
+// the row, bit for bit -- and folds: rewards[t N + n] = f32(r + f32(gamma v)), (t N + n, v) into the event list, one atomicAdd per workgroup with events.
+// A workgroup without a flagged row reads its 2 x 256 flags and returns; the critic's weights are staged only by workgroups that found one.
+hipError_t gauss_fused_dev_fold(const GenLayout& L, const float* params, const DevFoldArgs& a, hipStream_t s);
 // one minibatch step's gradient: gather through idx, forward, loss, backward (one launch, partial slabs [2][GAUSS_FUSED_MAX_BLOCKS][stride]) and the slab
 // sums into grads [P] (a second launch); the five loss partials go to loss_part [GEN_LOSS_BLOCKS][8] for gen_loss_sums
 hipError_t gauss_fused_fwd_bwd(const GenLayout& L, const LossParams& hp, const float* params, const float* obs, const float* actions, const float* oldlp,

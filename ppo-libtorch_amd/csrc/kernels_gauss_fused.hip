@@ -22,6 +22,9 @@
 // The device envs with real-valued actions (ppo_internal.hpp: GaussEnvPendulum, GaussEnvMountainCarContinuous) add kernels on the same forward, each a
 // template over the env trait: gauss_rollout_kernel, the T steps of a rollout in one launch with the env in registers (below); the envs' small stand-alone
 // kernels; and, for an env whose observation is its state, gauss_trunc_fold_kernel (ppo_env_truncation_bootstrap) and gauss_eval_kernel (ppo_evaluate).
+//
+// Caller-stepped contexts of either family fold time-limit truncations per step in gauss_dev_fold_kernel (ppo_dev_observe with flags): the critic kernel's
+// forward on the flagged rows of the step, found on the device.
 #include <algorithm>
 
 #include "generic.hpp"
@@ -962,6 +965,41 @@ __global__ __launch_bounds__(DEV_FOLD_THREADS) void gauss_trunc_fold_kernel(GfFo
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// gauss_dev_fold_kernel (ppo_dev_observe with truncation flags on a PPO_KERNEL_GAUSS_FUSED / PPO_KERNEL_CAT_FUSED context): dev_fold_mfma_kernel's front end
+// (ppo_internal.hpp: DevFoldArgs, dev_fold_compact) on this file's critic.  A 256-thread workgroup owns env rows [256 b, 256 b + 256); every thread reads
+// truncated[n] and done[n], ONE compaction, and a workgroup without a flagged row -- the common step, one pass over 2 N int32 -- returns before it loads a
+// weight (the count is the same in every thread, so the return is uniform).  Otherwise the critic's weights are staged on gauss_values_kernel's carve and the
+// workgroup walks its list (ascending, up to 256 rows) in tiles of 64: the list's row numbers, or -1, are the tile's row indices, gf_load_x reads those rows
+// of final_obs [N, O] and no other (an unflagged row may hold anything), gf_forward_tile is gauss_values_kernel's forward, so v is that kernel's value of
+// the row, bit for bit.  Lane k of wave 0 folds row k of the tile (dev_fold_store).
+// LDS: all dynamic -- gf_lds_floats(obsP, 4) floats and, behind them, the row list [256] and the waves' totals [8]: 54 464 + 528 obsP + 1 056 bytes, which
+// passes 64 KB between obs 16 and obs 17 .. 20; the launcher decides on the attribute from this sum, so no static LDS sits outside what it counted.
+// ---------------------------------------------------------------------------------------------------------
+constexpr int GF_DEV_FOLD_LIST_INTS = DEV_FOLD_THREADS + 8;
+
+__global__ __launch_bounds__(DEV_FOLD_THREADS) void gauss_dev_fold_kernel(GfShape sh, const float* __restrict__ params, DevFoldArgs a) {
+    static_assert(DEV_FOLD_THREADS == GF_THREADS, "fold_compact and gf_forward_tile are written for the same workgroup");
+    extern __shared__ __attribute__((aligned(16))) float gf_lds[];
+    const int tid = threadIdx.x, O = sh.obs, obsP = gf_pad4(O);
+    int* list = reinterpret_cast<int*>(gf_lds + gf_lds_floats(obsP, 4));
+    int* wtot = list + DEV_FOLD_THREADS;
+    const int cnt = dev_fold_compact(a, list, wtot);
+    if (cnt == 0) return;
+    const int base = wtot[4];
+    const GfLds m = gf_carve(gf_lds, obsP, 4);
+    gf_stage_weights(m, sh, params, 0, tid);
+    for (int k0 = 0; k0 < cnt; k0 += 64) {
+        const int k = k0 + tid;   // tid < 64: this lane's place in the list
+        if (tid < 64) m.ridx[tid] = k < cnt ? list[k] : -1;
+        __syncthreads();
+        gf_load_x(m, a.final_obs, O, tid);
+        gf_forward_tile(m, 1, tid);
+        if (tid < 64 && k < cnt) dev_fold_store(a, base, k, list[k], m.o[tid]);
+        __syncthreads();   // OUT and the row indices are read: the next tile may overwrite them
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // gauss_eval_kernel<Env> (ppo_evaluate on an env whose observation is its state): whole episodes in ONE launch.  A workgroup owns 64 episodes for their whole
 // length with the actor's weights resident, as in gauss_rollout_kernel: lane l of wave 0 keeps episode 64 b + l (state, return, length) in registers, writes
 // its observation into the X image, every thread runs gf_forward_tile, and wave 0 takes the mean (greedy) or mu + sigma * eps with eps keyed (seed, episode,
@@ -1080,6 +1118,19 @@ hipError_t gauss_fused_values(const GenLayout& L, const float* params, const flo
     const hipError_t e = gf_allow(done, gauss_values_kernel, bytes);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(gauss_values_kernel, dim3((unsigned)std::min<int64_t>(tiles, 1024)), dim3(GF_THREADS), bytes, s, sh, params, obs, n, value);
+    return hipGetLastError();
+}
+
+hipError_t gauss_fused_dev_fold(const GenLayout& L, const float* params, const DevFoldArgs& a, hipStream_t s) {
+    if (a.N <= 0) return hipSuccess;
+    const GfShape sh = gf_shape(L);
+    // the row list and the waves' totals are part of the dynamic allocation: the attribute is decided on every byte of LDS the kernel uses
+    const int bytes = gf_lds_floats(gf_pad4(L.obs), 4) * 4 + GF_DEV_FOLD_LIST_INTS * (int)sizeof(int);
+    static std::atomic<unsigned long long> done{ 0 };
+    const hipError_t e = gf_allow(done, gauss_dev_fold_kernel, bytes);
+    if (e != hipSuccess) return e;
+    const unsigned grid = (unsigned)(((int64_t)a.N + DEV_FOLD_THREADS - 1) / DEV_FOLD_THREADS);
+    hipLaunchKernelGGL(gauss_dev_fold_kernel, dim3(grid), dim3(DEV_FOLD_THREADS), bytes, s, sh, params, a);
     return hipGetLastError();
 }
 
