@@ -92,7 +92,54 @@ enum { PPO_OK = 0, PPO_ERR_INVALID = 1, PPO_ERR_HIP = 2, PPO_ERR_STATE = 3, PPO_
  * Refused exactly as on Pendulum, changing nothing: ppo_host_* / ppo_dev_* (PPO_ERR_STATE); ppo_obs_norm_* and ppo_reward_norm_* (PPO_ERR_UNSUPPORTED);
  * ppo_env_step, ppo_rollout with an i64 array and ppo_policy_act (PPO_ERR_UNSUPPORTED, naming the _f32 twin).
  * Sharding (ppo_comm_init*) is neither claimed nor tested for this env. */
+/* PPO_ENV_ACROBOT (new; value 6): gymnasium's Acrobot-v1 on the device ("book" dynamics, no torque noise), the first device env of the fused 2 x 64 family
+ * with a categorical policy.  State (theta1, theta2, w1, w2) f32 -- PPO_BUF_ENV_STATE is [4, N], ppo_env_set_state_h / ppo_env_get_state_h take [N, 4] --
+ * observation (cos th1, sin th1, cos th2, sin th2, w1, w2), obs_size 6, which is NOT the state.  Action a in {0, 1, 2}, torque tau = (float)a - 1.0f.
+ * One step, every operation rounded to f32 on its own, in exactly this association (PI_F = (float)pi, TWO_PI_F = (float)(2 pi), HALF_PI_F = (float)(pi / 2);
+ * m1 = m2 = l1 = 1, lc1 = lc2 = 0.5, I1 = I2 = 1, g = 9.8, dt = 0.2, products of the constants folded: 4.9f = m2 lc2 g, 14.7f = (m1 lc1 + m2 l1) g):
+ *   dsdt(th1, th2, w1, w2):
+ *     c2   = cosr(th2);  s2 = sinr(th2)
+ *     d1   = (0.25f + (1.25f + c2)) + 2.0f                            (m1 lc1^2 + m2 (l1^2 + lc2^2 + 2 l1 lc2 cos th2) + I1 + I2)
+ *     d2   = (0.25f + 0.5f * c2) + 1.0f                               (m2 (lc2^2 + l1 lc2 cos th2) + I2)
+ *     phi2 = 4.9f * cosr((th1 + th2) - HALF_PI_F)
+ *     phi1 = (((-0.5f * (w2 * w2)) * s2 - (w2 * w1) * s2) + 14.7f * cosr(th1 - HALF_PI_F)) + phi2
+ *     dw2  = (((tau + (d2 / d1) * phi1) - (0.5f * (w1 * w1)) * s2) - phi2) / (1.25f - (d2 * d2) / d1)
+ *     dw1  = -(d2 * dw2 + phi1) / d1
+ *     dsdt = (w1, w2, dw1, dw2)
+ *   one classical RK4 step: k1 = dsdt(s), k2 = dsdt(s + 0.1f * k1), k3 = dsdt(s + 0.1f * k2), k4 = dsdt(s + 0.2f * k3)   (component by component)
+ *     s'   = s + DT6 * (((k1 + 2.0f * k2) + 2.0f * k3) + k4),  DT6 = (float)(0.2 / 6)
+ *   th1', th2': while (x > PI_F) x -= TWO_PI_F; while (x < -PI_F) x += TWO_PI_F          (gym's wrap; each loop gives up after 1024 turns, which no finite
+ *                                                                                          state of the box below comes near: a non-finite input cannot hang)
+ *   w1' = min(max(w1', -W1MAX), W1MAX), W1MAX = (float)(4 pi);  w2' likewise with W2MAX = (float)(9 pi)
+ *   terminated = ((-cosr(th1')) - cosr(th2' + th1') > 1.0f);  reward = terminated ? 0.0f : -1.0f
+ *   obs' = (cosr(th1'), sinr(th1'), cosr(th2'), sinr(th2'), w1', w2')
+ * sinr / cosr, the trigonometric range: the library's device sinf / cosf (glibc 2.35's, bit for bit) hold for |x| < 120, and the RK4 stage angles leave that
+ * range in the corners of the state box [-pi, pi]^2 x [-4 pi, 4 pi] x [-9 pi, 9 pi] (raw stage velocities reach ~2000 rad/s there).  So
+ *   sinr(x) = |x| < 64.0f ? sinf(x) : sinf((float)((double)x - TWO_PI_D * rint((double)x / TWO_PI_D))),  TWO_PI_D = 2 pi in binary64
+ * and cosr likewise: a large argument is reduced in binary64 (one division, one rint, one multiply, one subtraction, each rounded on its own), rounded to f32,
+ * and handed to the same function.  Below 64 nothing changes.  The step is finite and inside the box for every state of the box.
+ * An episode ends where the env terminates or its length reaches max_episode_steps (any value >= 1; gym: 500): done = 1, FIN_LEN / FIN_REW written,
+ * auto-reset -- ppo_env_step's bookkeeping.  Reset number k of global env e: w = philox4x32_10(seed; e, k, 0, 1), (th1, th2, w1, w2) =
+ * uniform(w.x | w.y | w.z | w.w, -0.1f, 0.1f) (MountainCar's keying and uniform mapping); global env 0 takes reset 1 at ppo_env_reset; PPO_BUF_RESET_COUNT
+ * counts them.
+ * ppo_ctx_create accepts the env in exactly one form: dist_kind = PPO_DIST_CATEGORICAL, n_heads = 1, head_dims[0] = 3, obs_size = 6, hidden = 64,
+ * n_hidden = 2, PPO_DTYPE_F32, kernel_flags containing PPO_KERNEL_CAT_FUSED (required, never implied) and max_episode_steps >= 1.  A wrong obs_size returns
+ * PPO_ERR_INVALID with the reference's obs-size message, anything else PPO_ERR_UNSUPPORTED with a message that names the limit.  The context lives in the
+ * generic engine's layout, like a PPO_ENV_HOST context with PPO_KERNEL_CAT_FUSED.
+ * Calls: ppo_env_reset, ppo_env_set_state_h (refills NEXT_OBS from the state) / ppo_env_get_state_h, ppo_env_step (action i64 [N, 1], obs [N, 6]),
+ * ppo_env_transition(6, state [n, 4], action i64 [n], ...; the observation of a state comes from ppo_env_set_state_h, which refills PPO_BUF_NEXT_OBS -- no
+ * symbol was added for it: the exported set stays at 92), ppo_rollout (forced i64 [T, N, 1] or NULL), ppo_calc_advantage, ppo_update,
+ * ppo_train_iteration, ppo_policy_act, ppo_policy_act_greedy, ppo_get_value, ppo_target_kl_set, ppo_evaluate, the statistics and profile calls,
+ * ppo_gauss_fused_launches.  ppo_rollout is THREE launches: cat_rollout_kernel (all T steps; a workgroup of 256 threads owns 64 envs for the whole rollout,
+ * the actor's weights resident in LDS; PPO_BUF_MASKS is filled with ones, as a host-fed PPO_KERNEL_CAT_FUSED context without a mask holds it) and the critic
+ * over the T * N stored observations and over NEXT_OBS: `value` moves by 2, `act` by 0.  A stepwise loop of ppo_policy_act(obs, step_index = rollout_steps + t)
+ * and ppo_env_step reproduces every buffer it fills bit for bit (tests/test_gpu_acrobot.py).  ppo_evaluate is ONE launch (cat_eval_kernel) and moves no counter.
+ * Refused, each with its reason, changing nothing: ppo_host_* / ppo_dev_* (PPO_ERR_STATE, as on any device env); ppo_obs_norm_* and ppo_reward_norm_*
+ * (PPO_ERR_UNSUPPORTED); ppo_env_step_f32, ppo_rollout_f32, ppo_policy_act_f32 (PPO_ERR_UNSUPPORTED, naming the integer twin);
+ * ppo_env_truncation_bootstrap and ppo_env_truncations (PPO_ERR_UNSUPPORTED: the fold rebuilds the final observation of a cut-off episode from PPO_BUF_OBS,
+ * and an Acrobot observation does not hold the angles).  Sharding (ppo_comm_init*) is neither claimed nor tested for this env. */
 enum { PPO_ENV_CARTPOLE = 0, PPO_ENV_MOUNTAINCAR = 1, PPO_ENV_SYNTHETIC = 2, PPO_ENV_HOST = 3, PPO_ENV_PENDULUM = 4, PPO_ENV_MOUNTAINCAR_CONTINUOUS = 5 };
+enum { PPO_ENV_ACROBOT = PPO_ENV_MOUNTAINCAR_CONTINUOUS + 1 };   /* 6: the next env_kind, in an enum of its own -- the list above is kept as it was published */
 /* PPO_DIST_CATEGORICAL reproduces Distributions/Categorical.cpp including its entropy clamp (:112-119);
  * PPO_DIST_MASKED reproduces Distributions/CategoricalMasked.cpp (true entropy, -1e8 masking).
  * PPO_DIST_GAUSSIAN (new; the reference has no continuous policy): a diagonal Gaussian over D = head_dims[0] real-valued actions (n_heads = 1,
@@ -212,8 +259,9 @@ typedef struct ppo_config {
  *                               own device functions (equal logits give equal action, log-prob and entropy bits); a row gets the same logits and value from
  *                               every entry point, bit for bit.  The context always lives in the generic engine's layout -- also at obs_size 2, 4 and 8, where
  *                               the flag takes it off the reference-shape kernels; the parameter order is Agent::parameters() order either way.  Against the
- *                               same context without the flag: log-probs and values agree to f32 summation order, not bit for bit.  Opt-in; a Gaussian
- *                               policy, a device env, PPO_ENV_SYNTHETIC, another width or depth, bf16, obs_size > 64 or PPO_KERNEL_GAUSS_FUSED beside it make
+ *                               same context without the flag: log-probs and values agree to f32 summation order, not bit for bit.  One device env runs on
+ *                               the family too, PPO_ENV_ACROBOT (above), in the one form it accepts; there the flag is required.  Opt-in; a Gaussian
+ *                               policy, any other device env, PPO_ENV_SYNTHETIC, another width or depth, bf16, obs_size > 64 or PPO_KERNEL_GAUSS_FUSED beside it make
  *                               ppo_ctx_create return PPO_ERR_UNSUPPORTED with a message that names the limit -- never served by another engine instead.
  *                               ppo_evaluate stays refused as on the generic engine; truncation flags in ppo_dev_observe are served as on a
  *                               PPO_KERNEL_GAUSS_FUSED context (the critic kernel is shared, and so is the fold: gauss_dev_fold_kernel).
@@ -399,7 +447,8 @@ PPO_API ppo_status ppo_matmul(int32_t trans_a, int32_t trans_b, int64_t M, int64
  * ------------------------------------------------------------------------------------------------------- */
 /* Stateless batched CartPole::step (CartPole.cpp:47-94) / MountainCar::step (MountainCar.cpp:29-57) on injected
  * states: state_in [n,O] (array-of-structs like the reference's std::vector<float> state), action i64 [n];
- * outputs next_state [n,O], reward f32 [n], terminated i32 [n]. */
+ * outputs next_state [n,O], reward f32 [n], terminated i32 [n].  PPO_ENV_ACROBOT: the same call with state_in / next_state [n,4] (the state, not the
+ * observation) and action in {0, 1, 2}. */
 PPO_API ppo_status ppo_env_transition(int32_t env_kind, const float* state_in, const int64_t* action, int64_t n, float* next_state,
                               float* reward, int32_t* terminated, void* stream);
 /* First n_resets reset states [n_resets,4] of std::mt19937(seed) + uniform_real_distribution<float>(-0.05,0.05)
@@ -836,7 +885,11 @@ typedef struct ppo_eval_stats {
  *   v = 0).  greedy != 0: the action is the mean, bit for bit ppo_policy_act_f32 with greedy = 1; greedy == 0: mu + sigma * eps with eps keyed (seed, e, step t
  *   within the episode, d = 0), bit for bit ppo_policy_act_f32(step_index = t) on row e of a context whose seed is `seed` and whose env_offset is 0.  The env
  *   step, the f32 reward sum in step order, the end at termination or at max_episode_steps, the independence of how episodes are spread over workgroups and
- *   everything about the outputs and the untouched training state (ppo_gauss_fused_launches included) are as above.  No reset table is needed. */
+ *   everything about the outputs and the untouched training state (ppo_gauss_fused_launches included) are as above.  No reset table is needed.
+ *   PPO_ENV_ACROBOT: served likewise as ONE launch (cat_eval_kernel; the lane keeps the state, the observation goes through the forward).  Episode e starts
+ *   at reset 0 of env e under `seed` (the four words of philox4x32_10(seed; e, 0, 0, 1) mapped to [-0.1, 0.1)).  greedy != 0: the first-index argmax of
+ *   ppo_policy_act_greedy; greedy == 0: the draw keyed (seed, e, step t within the episode, head 0), bit for bit ppo_policy_act(step_index = t) on row e of
+ *   a context whose seed is `seed` and whose env_offset is 0. */
 PPO_API ppo_status ppo_evaluate(ppo_ctx* ctx, int64_t n_episodes, int64_t seed, int32_t greedy,
                                 float* ep_return /* dev f32[n] or NULL */, int32_t* ep_length /* dev i32[n] or NULL */,
                                 ppo_eval_stats* out_h);

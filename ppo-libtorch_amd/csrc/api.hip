@@ -575,14 +575,17 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
     // and the evaluation launch)
     const bool mcc = cfg->env_kind == PPO_ENV_MOUNTAINCAR_CONTINUOUS;
     const bool gauss_env = pendulum || mcc;
-    const bool generic = cfg->env_kind == PPO_ENV_SYNTHETIC || (host_env && !host_ref) || gauss_env;
+    // PPO_ENV_ACROBOT: the device env of the fused categorical kernels (cat_rollout_kernel); the network lives in the generic engine's layout, as a
+    // PPO_ENV_HOST context with PPO_KERNEL_CAT_FUSED does
+    const bool acrobot = cfg->env_kind == PPO_ENV_ACROBOT;
+    const bool generic = cfg->env_kind == PPO_ENV_SYNTHETIC || (host_env && !host_ref) || gauss_env || acrobot;
     if (!generic && (cfg->hidden != PPO_HIDDEN || cfg->n_hidden != 2))
         return fail(nullptr, PPO_ERR_UNSUPPORTED, "only the reference architecture (2 hidden layers of 64, Agent.cpp:25-59) is built for the reference's "
                     "environments; got %d x %d (other shapes run with env_kind = PPO_ENV_SYNTHETIC)", cfg->n_hidden, cfg->hidden);
-    if (generic && !gauss_env && (cfg->hidden < 1 || cfg->hidden > 2048 || cfg->n_hidden < 1 || cfg->n_hidden > GEN_MAX_LAYERS - 1 || cfg->obs_size < 1 || cfg->obs_size > 8192))
+    if (generic && !gauss_env && !acrobot && (cfg->hidden < 1 || cfg->hidden > 2048 || cfg->n_hidden < 1 || cfg->n_hidden > GEN_MAX_LAYERS - 1 || cfg->obs_size < 1 || cfg->obs_size > 8192))
         return fail(nullptr, PPO_ERR_UNSUPPORTED, "generic network out of range: hidden %d (1..2048), n_hidden %d (1..%d), obs %d (1..8192)", cfg->hidden,
                     cfg->n_hidden, GEN_MAX_LAYERS - 1, cfg->obs_size);
-    if (cfg->env_kind != PPO_ENV_CARTPOLE && cfg->env_kind != PPO_ENV_MOUNTAINCAR && cfg->env_kind != PPO_ENV_SYNTHETIC && cfg->env_kind != PPO_ENV_HOST && !gauss_env)
+    if (cfg->env_kind != PPO_ENV_CARTPOLE && cfg->env_kind != PPO_ENV_MOUNTAINCAR && cfg->env_kind != PPO_ENV_SYNTHETIC && cfg->env_kind != PPO_ENV_HOST && !gauss_env && !acrobot)
         return fail(nullptr, PPO_ERR_INVALID, "unknown env_kind %d", cfg->env_kind);
     if (cfg->dist_kind != PPO_DIST_CATEGORICAL && cfg->dist_kind != PPO_DIST_MASKED && !gauss) return fail(nullptr, PPO_ERR_INVALID, "unknown dist_kind %d", cfg->dist_kind);
     if (cfg->compute_dtype != PPO_DTYPE_F32 && cfg->compute_dtype != PPO_DTYPE_BF16) return fail(nullptr, PPO_ERR_INVALID, "unknown compute_dtype %d", cfg->compute_dtype);
@@ -628,6 +631,27 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
                             "ends at the time limit only); got %d", cfg->max_episode_steps);
         }
     }
+    if (acrobot) {   // accepted in exactly one form (ppo_hip.h: PPO_ENV_ACROBOT); a wrong obs_size first, with the reference's message (below)
+        if (cfg->obs_size == 6) {
+            if (cfg->dist_kind != PPO_DIST_CATEGORICAL)
+                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_ACROBOT takes one of three discrete actions without a mask: it is built for dist_kind = "
+                            "PPO_DIST_CATEGORICAL; got dist_kind %d", cfg->dist_kind);
+            if (cfg->n_heads != 1 || cfg->head_dims[0] != 3)
+                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_ACROBOT has one head of three actions, the torque -1, 0 or +1: n_heads = 1 and head_dims[0] = 3; got "
+                            "n_heads = %d, head_dims[0] = %d", cfg->n_heads, cfg->head_dims[0]);
+            if (cfg->hidden != 64 || cfg->n_hidden != 2)
+                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_ACROBOT is built for the 2 x 64 network (hidden = 64, n_hidden = 2) of the fused categorical "
+                            "kernels; got %d x %d", cfg->n_hidden, cfg->hidden);
+            if (cfg->compute_dtype != PPO_DTYPE_F32)
+                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_ACROBOT is built for compute_dtype = PPO_DTYPE_F32; bf16 storage is not");
+            if (!cat_fused)
+                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_ACROBOT needs PPO_KERNEL_CAT_FUSED in kernel_flags: its rollout exists on the fused categorical "
+                            "kernels only, and the flag is never implied (no other engine serves in its place)");
+            if (cfg->max_episode_steps < 1)
+                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_ACROBOT is built for max_episode_steps >= 1 (an episode that never swings up ends at the "
+                            "time limit only); got %d", cfg->max_episode_steps);
+        }
+    }
     if (gauss && !host_env && !gauss_env)
         return fail(nullptr, PPO_ERR_UNSUPPORTED, "dist_kind = PPO_DIST_GAUSSIAN serves caller-stepped environments (env_kind = PPO_ENV_HOST), PPO_ENV_PENDULUM and "
                     "PPO_ENV_MOUNTAINCAR_CONTINUOUS: CartPole, MountainCar and the synthetic env take discrete actions; got env_kind %d", cfg->env_kind);
@@ -643,8 +667,9 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
         if (gauss)
             return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED serves dist_kind = PPO_DIST_CATEGORICAL and PPO_DIST_MASKED only; this context's policy is "
                         "PPO_DIST_GAUSSIAN (its twin is PPO_KERNEL_GAUSS_FUSED)");
-        if (!host_env)
-            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED serves caller-stepped environments (env_kind = PPO_ENV_HOST) only; got env_kind %d", cfg->env_kind);
+        if (!host_env && !acrobot)
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED serves caller-stepped environments (env_kind = PPO_ENV_HOST) and PPO_ENV_ACROBOT only; got "
+                        "env_kind %d", cfg->env_kind);
         if (cfg->hidden != 64) return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED is built for hidden = 64; got hidden = %d", cfg->hidden);
         if (cfg->n_hidden != 2) return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED is built for n_hidden = 2; got n_hidden = %d", cfg->n_hidden);
         if (cfg->compute_dtype != PPO_DTYPE_F32)
@@ -655,7 +680,7 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
     if (cfg->compute_dtype == PPO_DTYPE_BF16 && !generic)
         return fail(nullptr, PPO_ERR_UNSUPPORTED, "compute_dtype = PPO_DTYPE_BF16 applies to networks whose layers are GEMMs (env_kind = PPO_ENV_SYNTHETIC); the reference's "
                     "2 x 64 networks always compute in f32");
-    const int env_obs = cfg->env_kind == PPO_ENV_CARTPOLE ? 4 : (cfg->env_kind == PPO_ENV_MOUNTAINCAR || mcc ? 2 : (pendulum ? 3 : cfg->obs_size));   // host / synthetic: no check
+    const int env_obs = cfg->env_kind == PPO_ENV_CARTPOLE ? 4 : (cfg->env_kind == PPO_ENV_MOUNTAINCAR || mcc ? 2 : (pendulum ? 3 : (acrobot ? 6 : cfg->obs_size)));   // host / synthetic: no check
     if (cfg->obs_size != env_obs) {
         // the reference's runtime check in initEnvs (PPO_Discrete.cpp:370-375), same wording
         return fail(nullptr, PPO_ERR_INVALID,
@@ -1316,6 +1341,8 @@ extern "C" ppo_status ppo_categorical_sample(const float* m_probs, int64_t n, in
 extern "C" ppo_status ppo_env_transition(int32_t env_kind, const float* state_in, const int64_t* action, int64_t n, float* next_state,
                                          float* reward, int32_t* terminated, void* stream) {
     if (!state_in || !action || !next_state || !reward || !terminated || n < 0) return PPO_ERR_INVALID;
+    if (cat_fused_env_serves(env_kind))   // PPO_ENV_ACROBOT: state [n, 4]
+        return launch_cat_env_transition(env_kind, state_in, action, n, next_state, reward, terminated, (hipStream_t)stream) == hipSuccess ? PPO_OK : PPO_ERR_HIP;
     return launch_env_transition(env_kind, state_in, action, n, next_state, reward, terminated, (hipStream_t)stream) == hipSuccess ? PPO_OK : PPO_ERR_HIP;
 }
 
@@ -1329,6 +1356,8 @@ static inline bool is_pendulum(const ppo_ctx* c) { return c->cfg.env_kind == PPO
 static inline bool is_mcc(const ppo_ctx* c) { return c->cfg.env_kind == PPO_ENV_MOUNTAINCAR_CONTINUOUS; }
 // the device envs with real-valued actions: the env of the fused Gaussian rollout (gauss_fused.hpp)
 static inline bool is_gauss_env(const ppo_ctx* c) { return is_pendulum(c) || is_mcc(c); }
+// the device env with integer actions of the fused categorical rollout (gauss_fused.hpp: cat_fused_rollout)
+static inline bool is_acrobot(const ppo_ctx* c) { return c->cfg.env_kind == PPO_ENV_ACROBOT; }
 static inline const char* gauss_env_name(const ppo_ctx* c) { return is_mcc(c) ? "PPO_ENV_MOUNTAINCAR_CONTINUOUS" : "PPO_ENV_PENDULUM"; }
 
 extern "C" ppo_status ppo_env_transition_f32(int32_t env_kind, const float* state_in, const float* action, int64_t n, float* next_state, float* obs_out,
@@ -1342,6 +1371,11 @@ extern "C" ppo_status ppo_env_reset(ppo_ctx* c) {
     NEED(c, c != nullptr, "null ctx");
     if (c->host_env) return host_env_refuses(c, "ppo_env_reset");
     DeviceGuard dev_guard(c);
+    if (is_acrobot(c)) {
+        HIPCHK(c, launch_cat_env_reset(c->cfg.env_kind, c->N, c->cfg.seed, c->cfg.env_offset, B_<float>(c, PPO_BUF_ENV_STATE), B_<int32_t>(c, PPO_BUF_EP_LEN), B_<float>(c, PPO_BUF_EP_REW),
+                                      B_<int32_t>(c, PPO_BUF_RESET_COUNT), B_<float>(c, PPO_BUF_NEXT_OBS), B_<int32_t>(c, PPO_BUF_NEXT_DONE), c->stream));
+        return PPO_OK;
+    }
     if (is_gauss_env(c)) {
         HIPCHK(c, launch_gauss_env_reset(c->cfg.env_kind, c->N, c->cfg.seed, c->cfg.env_offset, B_<float>(c, PPO_BUF_ENV_STATE), B_<int32_t>(c, PPO_BUF_EP_LEN), B_<float>(c, PPO_BUF_EP_REW),
                                         B_<int32_t>(c, PPO_BUF_RESET_COUNT), B_<float>(c, PPO_BUF_NEXT_OBS), B_<int32_t>(c, PPO_BUF_NEXT_DONE), c->stream));
@@ -1366,6 +1400,11 @@ extern "C" ppo_status ppo_env_step(ppo_ctx* c, const int64_t* action, float* obs
     if (c->host_env) return host_env_refuses(c, "ppo_env_step");
     if (is_gauss_env(c)) return fail(c, PPO_ERR_UNSUPPORTED, "ppo_env_step: this context's env (%s) takes real-valued actions f32 [N, D]; call ppo_env_step_f32", gauss_env_name(c));
     DeviceGuard dev_guard(c);
+    if (is_acrobot(c)) {
+        HIPCHK(c, launch_cat_env_step(c->cfg.env_kind, c->N, c->cfg.max_episode_steps, c->cfg.seed, c->cfg.env_offset, B_<float>(c, PPO_BUF_ENV_STATE), B_<int32_t>(c, PPO_BUF_EP_LEN),
+                                     B_<float>(c, PPO_BUF_EP_REW), B_<int32_t>(c, PPO_BUF_RESET_COUNT), action, obs, reward, done, c->stream));
+        return PPO_OK;
+    }
     if (c->gen) {   // synthetic env: one step at the context's global step counter (the action does not influence it)
         HIPCHK(c, gen_synthetic_step(c->gen->L, c->N, c->cfg.seed, c->cfg.env_offset, c->rollout_steps, c->cfg.max_episode_steps,
                                      B_<int32_t>(c, PPO_BUF_EP_LEN), B_<float>(c, PPO_BUF_EP_REW), obs, c->cur_mask, reward, done, nullptr, nullptr, c->stream));
@@ -1390,7 +1429,7 @@ extern "C" ppo_status ppo_env_step_f32(ppo_ctx* c, const float* action, float* o
 }
 
 // the env state's width: the observation IS the state for CartPole and both MountainCars; Pendulum keeps (theta, theta_dot) behind a 3-wide observation
-static inline int env_state_dim(const ppo_ctx* c) { return is_pendulum(c) ? 2 : c->O; }
+static inline int env_state_dim(const ppo_ctx* c) { return is_pendulum(c) ? 2 : (is_acrobot(c) ? 4 : c->O); }
 
 extern "C" ppo_status ppo_env_set_state_h(ppo_ctx* c, const float* state_h, const int32_t* ep_len_h, const float* ep_rew_h, const int32_t* reset_count_h) {
     NEED(c, c != nullptr, "null ctx");
@@ -1401,6 +1440,7 @@ extern "C" ppo_status ppo_env_set_state_h(ppo_ctx* c, const float* state_h, cons
         if (s != PPO_OK) return s;
         HIPCHK(c, launch_aos_to_soa(c->scratch_obs, B_<float>(c, PPO_BUF_ENV_STATE), c->N, S, true, c->stream));
         if (is_pendulum(c)) HIPCHK(c, launch_gauss_env_obs(c->cfg.env_kind, c->N, B_<float>(c, PPO_BUF_ENV_STATE), B_<float>(c, PPO_BUF_NEXT_OBS), c->stream));
+        else if (is_acrobot(c)) HIPCHK(c, launch_cat_env_obs(c->cfg.env_kind, c->N, B_<float>(c, PPO_BUF_ENV_STATE), B_<float>(c, PPO_BUF_NEXT_OBS), c->stream));
         else HIPCHK(c, hipMemcpyAsync(c->buf[PPO_BUF_NEXT_OBS], c->scratch_obs, (size_t)c->N * c->O * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     }
     ppo_status s = PPO_OK;
@@ -1567,6 +1607,43 @@ static ppo_status gauss_env_rollout(ppo_ctx* c, const float* forced) {
     return PPO_OK;
 }
 
+// PPO_ENV_ACROBOT: cat_rollout_kernel (all T steps), then the critic over the stored observations and over NEXT_OBS: three launches, gauss_env_rollout's plan
+static ppo_status cat_env_rollout(ppo_ctx* c, const int64_t* forced) {
+    ppo_status s = consume_finished_episodes(c);
+    if (s != PPO_OK) return s;
+    CatRolloutArgs r{};
+    r.params = B_<float>(c, PPO_BUF_PARAMS);
+    r.N = c->N; r.T = c->T; r.max_episode_steps = c->cfg.max_episode_steps;
+    r.seed = c->cfg.seed; r.env_offset = c->cfg.env_offset; r.step_base = c->rollout_steps;
+    r.env_state = B_<float>(c, PPO_BUF_ENV_STATE);
+    r.ep_len = B_<int32_t>(c, PPO_BUF_EP_LEN);
+    r.ep_rew = B_<float>(c, PPO_BUF_EP_REW);
+    r.reset_count = B_<int32_t>(c, PPO_BUF_RESET_COUNT);
+    r.obs = B_<float>(c, PPO_BUF_OBS);
+    r.masks = B_<uint8_t>(c, PPO_BUF_MASKS);
+    r.actions = B_<int32_t>(c, PPO_BUF_ACTIONS);
+    r.logprobs = B_<float>(c, PPO_BUF_LOGPROBS);
+    r.rewards = B_<float>(c, PPO_BUF_REWARDS);
+    r.dones = B_<float>(c, PPO_BUF_DONES);
+    r.fin_len = B_<int32_t>(c, PPO_BUF_FIN_LEN);
+    r.fin_rew = B_<float>(c, PPO_BUF_FIN_REW);
+    r.next_obs = B_<float>(c, PPO_BUF_NEXT_OBS);
+    r.next_done = B_<int32_t>(c, PPO_BUF_NEXT_DONE);
+    r.forced = forced;
+    {
+        ProfScope ps(c, PROF_ROLLOUT);
+        HIPCHK(c, cat_fused_rollout(c->cfg.env_kind, c->gen->L, r, c->stream));
+        s = gen_values(c, r.obs, (int64_t)c->T * c->N, B_<float>(c, PPO_BUF_VALUES));
+        if (s == PPO_OK) s = gen_values(c, r.next_obs, c->N, B_<float>(c, PPO_BUF_NEXT_VALUE));
+        if (s != PPO_OK) return s;
+        c->envt_last = false;   // envt_on is never set on this env (envt_state)
+    }
+    c->rollout_steps += c->T;
+    c->global_step += (int64_t)c->T * c->cfg.global_num_envs;
+    c->fin_pending = true;
+    return PPO_OK;
+}
+
 extern "C" ppo_status ppo_rollout_f32(ppo_ctx* c, const float* forced_actions) {
     NEED(c, c != nullptr, "null ctx");
     if (c->host_env) return host_env_refuses(c, "ppo_rollout_f32");
@@ -1584,6 +1661,7 @@ extern "C" ppo_status ppo_rollout(ppo_ctx* c, const int64_t* forced_actions) {
         return gauss_env_rollout(c, nullptr);
     }
     DeviceGuard dev_guard(c);
+    if (is_acrobot(c)) return cat_env_rollout(c, forced_actions);
     ppo_status s = consume_finished_episodes(c);
     if (s != PPO_OK) return s;
     if (c->gen) return gen_rollout(c, forced_actions);
@@ -1722,7 +1800,8 @@ extern "C" ppo_status ppo_evaluate(ppo_ctx* c, int64_t n_episodes, int64_t seed,
         return fail(c, PPO_ERR_UNSUPPORTED, "ppo_evaluate is not built for PPO_ENV_PENDULUM: step the episodes through ppo_policy_act_f32 with greedy = 1 and "
                                             "ppo_env_transition_f32");
     const bool gauss_env = is_mcc(c);   // the episodes run on the fused Gaussian kernels (gauss_eval_kernel); everything on the host side is shared
-    if (c->host_env || (c->gen && !gauss_env) || c->cfg.env_kind == PPO_ENV_SYNTHETIC)
+    const bool cat_env = is_acrobot(c);   // ... or on the fused categorical kernels (cat_eval_kernel)
+    if (c->host_env || (c->gen && !gauss_env && !cat_env) || c->cfg.env_kind == PPO_ENV_SYNTHETIC)
         return fail(c, PPO_ERR_UNSUPPORTED, "ppo_evaluate steps the context's device environment (CartPole, MountainCar); this context's environment is %s: "
                                             "run the episodes on the host with one ppo_policy_act_greedy launch per step",
                     c->host_env ? "the caller's (PPO_ENV_HOST)" : "synthetic (PPO_ENV_SYNTHETIC)");
@@ -1730,18 +1809,19 @@ extern "C" ppo_status ppo_evaluate(ppo_ctx* c, int64_t n_episodes, int64_t seed,
     NEED(c, n_episodes > 0, "ppo_evaluate: n_episodes <= 0");
     NEED(c, n_episodes < (1ll << 28), "ppo_evaluate: more than 2^28 episodes");
     NEED(c, c->cfg.max_episode_steps > 0, "ppo_evaluate: max_episode_steps <= 0 (an episode would never be truncated)");
-    NEED(c, c->O == (c->cfg.env_kind == PPO_ENV_CARTPOLE ? 4 : 2), "ppo_evaluate: obs_size does not match the environment");
+    NEED(c, c->O == (c->cfg.env_kind == PPO_ENV_CARTPOLE ? 4 : (cat_env ? 6 : 2)), "ppo_evaluate: obs_size does not match the environment");
     DeviceGuard dev_guard(c);
     ppo_status s = eval_scratch(c, n_episodes, seed);
     if (s != PPO_OK) return s;
-    if (gauss_env) {
+    if (gauss_env || cat_env) {
         GaussEvalArgs g{};
         g.params = B_<float>(c, PPO_BUF_PARAMS);
         g.n_episodes = n_episodes; g.seed = seed;
         g.max_episode_steps = c->cfg.max_episode_steps;
         g.greedy = greedy != 0;
         g.ep_return = c->eval_ret; g.ep_length = c->eval_len; g.ep_trunc = c->eval_len + c->eval_cap;
-        HIPCHK(c, gauss_fused_evaluate(c->cfg.env_kind, c->gen->L, g, c->stream));
+        if (cat_env) HIPCHK(c, cat_fused_evaluate(c->cfg.env_kind, c->gen->L, g, c->stream));
+        else HIPCHK(c, gauss_fused_evaluate(c->cfg.env_kind, c->gen->L, g, c->stream));
     } else {
         s = eval_launch_categorical(c, n_episodes, seed, greedy);
         if (s != PPO_OK) return s;
@@ -3094,6 +3174,9 @@ static ppo_status envt_state(ppo_ctx* c, const char* what) {
     if (is_pendulum(c))
         return fail(c, PPO_ERR_UNSUPPORTED, "%s: the fold rebuilds the final observation of a cut-off episode from PPO_BUF_OBS, and a PPO_ENV_PENDULUM observation "
                                             "(cos, sin, theta_dot) does not hold theta: not built for this env", what);
+    if (is_acrobot(c))
+        return fail(c, PPO_ERR_UNSUPPORTED, "%s: the fold rebuilds the final observation of a cut-off episode from PPO_BUF_OBS, and a PPO_ENV_ACROBOT observation "
+                                            "(cos, sin of two angles, two velocities) does not hold the angles: not built for this env", what);
     if (is_mcc(c)) return PPO_OK;   // its observation is its state: the fold runs on the fused Gaussian critic (gauss_env_fold_truncations)
     if (c->cfg.env_kind != PPO_ENV_CARTPOLE && c->cfg.env_kind != PPO_ENV_MOUNTAINCAR)
         return fail(c, PPO_ERR_UNSUPPORTED, "%s: the synthetic env's observations are noise: an episode there has no last observation to bootstrap from", what);

@@ -99,3 +99,28 @@ struct GaussEvalArgs {
     int32_t* ep_trunc;
 };
 hipError_t gauss_fused_evaluate(int env_kind, const GenLayout& L, const GaussEvalArgs& a, hipStream_t s);
+
+// The device envs with integer actions (PPO_ENV_ACROBOT; the trait is ppo_internal.hpp's CatEnvAcrobot), on PPO_KERNEL_CAT_FUSED's forward: the T steps of a
+// categorical rollout in one launch (cat_rollout_kernel<Env>: gauss_rollout_kernel's plan with cat_act_kernel's wave-0 work); the context's buffers, the
+// teacher-forcing actions i64 [T, N, 1] or null.  PPO_BUF_MASKS is filled with ones.  The critic is not in it: two gauss_fused_values launches follow.
+bool cat_fused_env_serves(int env_kind);
+struct CatRolloutArgs {
+    const float* params;
+    int N, T, max_episode_steps;
+    int64_t seed, env_offset, step_base;
+    float* env_state; int32_t* ep_len; float* ep_rew; int32_t* reset_count;
+    float* obs; uint8_t* masks; int32_t* actions; float *logprobs, *rewards, *dones; int32_t* fin_len; float* fin_rew;
+    float* next_obs; int32_t* next_done;
+    const int64_t* forced;
+};
+hipError_t cat_fused_rollout(int env_kind, const GenLayout& L, const CatRolloutArgs& r, hipStream_t s);
+// The env's stand-alone kernels, one thread per env, on the rollout kernel's device functions; env_state is [STATE, N]
+hipError_t launch_cat_env_reset(int env_kind, int N, int64_t seed, int64_t env_offset, float* env_state, int32_t* ep_len, float* ep_rew, int32_t* reset_count,
+                                float* next_obs, int32_t* next_done, hipStream_t s);
+hipError_t launch_cat_env_step(int env_kind, int N, int max_episode_steps, int64_t seed, int64_t env_offset, float* env_state, int32_t* ep_len, float* ep_rew,
+                               int32_t* reset_count, const int64_t* action, float* obs, float* reward, int32_t* done, hipStream_t s);
+hipError_t launch_cat_env_transition(int env_kind, const float* state_in, const int64_t* action, int64_t n, float* next_state, float* reward, int32_t* terminated,
+                                     hipStream_t s);
+hipError_t launch_cat_env_obs(int env_kind, int N, const float* env_state, float* next_obs, hipStream_t s);
+// ppo_evaluate on such an env: GaussEvalArgs' contract on cat_eval_kernel (greedy: the first-index argmax; else the draw keyed (seed, e, step of the episode, 0))
+hipError_t cat_fused_evaluate(int env_kind, const GenLayout& L, const GaussEvalArgs& a, hipStream_t s);

@@ -23,6 +23,10 @@
 // template over the env trait: gauss_rollout_kernel, the T steps of a rollout in one launch with the env in registers (below); the envs' small stand-alone
 // kernels; and, for an env whose observation is its state, gauss_trunc_fold_kernel (ppo_env_truncation_bootstrap) and gauss_eval_kernel (ppo_evaluate).
 //
+// The device env with integer actions (ppo_internal.hpp: CatEnvAcrobot, PPO_ENV_ACROBOT) adds the categorical twins on the same forward: cat_rollout_kernel
+// (gauss_rollout_kernel's plan with cat_act_kernel's wave-0 work; obs 6, 3 logits: gf_carve(8, 4) = 14 672 floats = 58 688 bytes, two workgroups per CU), its
+// stand-alone env kernels and cat_eval_kernel (ppo_evaluate); the lanes keep the env's STATE, so the observation need not be the state.
+//
 // Caller-stepped contexts of either family fold time-limit truncations per step in gauss_dev_fold_kernel (ppo_dev_observe with flags): the critic kernel's
 // forward on the flagged rows of the step, found on the device.
 #include <algorithm>
@@ -1076,6 +1080,274 @@ __global__ __launch_bounds__(GF_THREADS) void gauss_eval_kernel(GfEvalArgs a) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// cat_rollout_kernel<Env> (PPO_ENV_ACROBOT): gauss_rollout_kernel's plan with cat_act_kernel's wave-0 work -- the T steps of a categorical rollout as ONE
+// launch.  A workgroup owns one tile of 64 envs for the whole rollout; the actor's weights are staged once.  Lanes 0 .. 63 of wave 0 keep their env (state,
+// episode sums, reset count, previous done flag, the current observation) in registers and do, per step, what cat_act_kernel<PPO_DIST_CATEGORICAL>'s wave 0
+// does behind the same forward -- categorical_head and sample_head on the lane's columns of OUT and H1, the same Philox key (seed, env_offset + env,
+// (step_base + t) >> 2, head 0) and word select (step_base + t) & 3 -- so a stepwise loop of ppo_policy_act + ppo_env_step reproduces every stored bit; then
+// the env step (Env::step_episode under head 0's action).  Waves 1 .. 3 store the step's observation, its mask row (all ones: PPO_BUF_MASKS as a host-fed
+// context without a mask holds it) and the done flag meanwhile (the flag rides in the row-index words).  Barriers per step: gf_forward_tile's four and one
+// behind the stores; every thread runs every barrier, a short tile masks its stores only.  No workgroup talks to another.
+// LDS: gf_carve(8, 4) for PPO_ENV_ACROBOT (OBS 6, 3 logits) = 14 672 floats = 58 688 bytes, two workgroups per CU; rows OBS .. obsP - 1 of the X image are zero
+// padding, written once.  The policy has ONE head (ppo_ctx_create), of Env::ACTIONS logits.
+// ---------------------------------------------------------------------------------------------------------
+struct CfRolloutArgs {
+    GfShape sh;
+    const float* params;
+    int N, T, max_episode_steps;
+    int64_t seed, env_offset, step_base;
+    float* env_state;        // [Env::STATE, N]
+    int32_t* ep_len;
+    float* ep_rew;
+    int32_t* reset_count;
+    float* obs;              // [T, N, Env::OBS]
+    uint8_t* masks;          // [T, N, Env::ACTIONS]
+    int32_t* actions;        // [T, N, 1]
+    float* logprobs;
+    float* rewards;
+    float* dones;
+    int32_t* fin_len;
+    float* fin_rew;
+    float* next_obs;         // [N, Env::OBS]
+    int32_t* next_done;
+    const int64_t* forced;   // [T, N, 1] or null
+};
+
+// wave 0's lane behind the forward: the row's head on the lane's columns (z: OUT, log-probs in place; p: H1), the action (GREEDY: the first-index argmax of
+// the probabilities; forced; or the draw with uniform word `ws`) and its log-prob -- cat_act_kernel's expressions for one unmasked head
+template <bool GREEDY>
+__device__ __forceinline__ int cat_lane_head(const GfLds& m, int lane, int Ah, bool has_forced, int forced, uint32_t ws, float& lp) {
+    float* z = m.o + lane;
+    float* p = m.h1 + lane;
+    (void)categorical_head<PPO_DIST_CATEGORICAL, GF_S>(z, p, nullptr, Ah);
+    int a;
+    if constexpr (GREEDY) {
+        a = 0;
+        for (int k = 1; k < Ah; k++) if (p[k * GF_S] > p[a * GF_S]) a = k;
+    } else if (has_forced) {
+        a = forced;
+    } else {
+        a = sample_head<GF_S>(p, Ah, (float)(ws >> 8) * 0x1p-24f);
+    }
+    lp = 0.0f;
+    for (int k = 0; k < Ah; k++) if (k == a) lp = z[k * GF_S];
+    return a;
+}
+__device__ __forceinline__ uint32_t cat_draw_word(int64_t seed, int64_t row, int64_t step_index) {
+    const uint4 w = philox4x32_10((uint32_t)seed, (uint32_t)((uint64_t)seed >> 32), (uint32_t)row, (uint32_t)(step_index >> 2), 0u, 0u);
+    return (step_index & 3) == 0 ? w.x : ((step_index & 3) == 1 ? w.y : ((step_index & 3) == 2 ? w.z : w.w));
+}
+
+template <class Env>
+__global__ __launch_bounds__(GF_THREADS) void cat_rollout_kernel(CfRolloutArgs a) {
+    constexpr int OBS = Env::OBS, ST = Env::STATE, A = Env::ACTIONS, OBSP = (OBS + 3) & ~3;
+    static_assert(OBS <= 8 && A <= 4, "the rollout kernel carves its LDS for an observation of at most 8 floats and a head of at most 4 logits");
+    extern __shared__ __attribute__((aligned(16))) float gf_lds[];
+    const int tid = threadIdx.x, N = a.N;
+    const GfLds m = gf_carve(gf_lds, OBSP, 4);
+    gf_stage_weights(m, a.sh, a.params, 1, tid);
+    const int row0 = blockIdx.x * 64;
+    const int env = row0 + (tid & 63);
+    const bool owner = tid < 64 && env < N;
+    const int64_t env_global = a.env_offset + env;
+    float st[ST], ob[OBS], ep_rew = 0.0f;
+#pragma unroll
+    for (int k = 0; k < ST; k++) st[k] = 0.0f;
+#pragma unroll
+    for (int k = 0; k < OBS; k++) ob[k] = 0.0f;
+    int ep_len = 0, resets = 0, done = 0;
+    if (owner) {
+#pragma unroll
+        for (int k = 0; k < ST; k++) st[k] = a.env_state[(size_t)k * N + env];
+        ep_len = a.ep_len[env];
+        ep_rew = a.ep_rew[env];
+        resets = a.reset_count[env];
+        done = a.next_done[env];
+        Env::obs(st, ob);
+    }
+    if (tid < 64) {   // the padding rows of the observation image, once
+#pragma unroll
+        for (int k = OBS; k < OBSP; k++) m.x[k * GF_S + tid] = 0.0f;
+    }
+    const int rows = N - row0 < 64 ? N - row0 : 64;
+    for (int t = 0; t < a.T; t++) {
+        const size_t tn = (size_t)t * N;
+        if (tid < 64) {
+#pragma unroll
+            for (int k = 0; k < OBS; k++) m.x[k * GF_S + tid] = ob[k];
+            m.ridx[tid] = done;
+        }
+        gf_forward_tile(m, A, tid);
+        if (tid < 64) {
+            if (owner) {
+                const int64_t step_index = a.step_base + t;
+                const uint32_t ws = a.forced ? 0u : cat_draw_word(a.seed, env_global, step_index);
+                float lp;
+                const int act = cat_lane_head<false>(m, tid, A, a.forced != nullptr, a.forced ? (int)a.forced[tn + env] : 0, ws, lp);
+                int fin_len;
+                float fin_rew;
+                const float r = Env::step_episode(st, act, a.max_episode_steps, a.seed, env_global, ep_len, ep_rew, resets, done, fin_len, fin_rew);
+                Env::obs(st, ob);
+                a.actions[tn + env] = act;
+                a.logprobs[tn + env] = lp;
+                a.rewards[tn + env] = r;
+                a.fin_len[tn + env] = fin_len;
+                a.fin_rew[tn + env] = fin_rew;
+            }
+        } else {   // waves 1 .. 3: the step's observation rows, mask rows and done flags; X and the done words are not touched by wave 0's head work
+            float* obs_t = a.obs + (tn + row0) * OBS;
+            for (int i = tid - 64; i < rows * OBS; i += GF_THREADS - 64) {
+                const int s = i / OBS, k = i - OBS * s;
+                obs_t[i] = m.x[k * GF_S + s];
+            }
+            uint8_t* mask_t = a.masks + (tn + row0) * A;
+            for (int i = tid - 64; i < rows * A; i += GF_THREADS - 64) mask_t[i] = (uint8_t)1;
+            if (tid < 128 && env < N) a.dones[tn + env] = (float)m.ridx[tid & 63];
+        }
+        __syncthreads();   // X, OUT, the H1 columns and the done words are read: wave 0 may write the next step's
+    }
+    if (owner) {
+#pragma unroll
+        for (int k = 0; k < OBS; k++) a.next_obs[(size_t)env * OBS + k] = ob[k];
+        a.next_done[env] = done;
+#pragma unroll
+        for (int k = 0; k < ST; k++) a.env_state[(size_t)k * N + env] = st[k];
+        a.ep_len[env] = ep_len;
+        a.ep_rew[env] = ep_rew;
+        a.reset_count[env] = resets;
+    }
+}
+
+// ---- the stand-alone kernels of a device env with integer actions: one thread per env, on the device functions the rollout kernel uses (CatEnv*) ----
+template <class Env>
+__global__ void cat_env_reset_kernel(int N, int64_t seed, int64_t env_offset, float* env_state, int32_t* ep_len, float* ep_rew, int32_t* reset_count,
+                                     float* next_obs, int32_t* next_done) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    const int k = (env_offset + i == 0) ? 1 : 0;   // global env 0 takes reset 1, as elsewhere (env_reset_kernel)
+    float st[Env::STATE], ob[Env::OBS];
+    Env::reset(st, k, seed, env_offset + i);
+    Env::obs(st, ob);
+    for (int j = 0; j < Env::STATE; j++) env_state[(size_t)j * N + i] = st[j];
+    for (int j = 0; j < Env::OBS; j++) next_obs[(size_t)i * Env::OBS + j] = ob[j];
+    ep_len[i] = 0;
+    ep_rew[i] = 0.0f;
+    reset_count[i] = k + 1;
+    next_done[i] = 0;
+}
+// ppo_env_step: action i64 [N, 1]
+template <class Env>
+__global__ void cat_env_step_kernel(int N, int max_episode_steps, int64_t seed, int64_t env_offset, float* env_state, int32_t* ep_len, float* ep_rew,
+                                    int32_t* reset_count, const int64_t* __restrict__ action, float* obs, float* reward, int32_t* done) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    float st[Env::STATE], ob[Env::OBS];
+    for (int j = 0; j < Env::STATE; j++) st[j] = env_state[(size_t)j * N + i];
+    int len = ep_len[i], resets = reset_count[i], d, fin_len;
+    float rew = ep_rew[i], fin_rew;
+    const float r = Env::step_episode(st, (int)action[i], max_episode_steps, seed, env_offset + i, len, rew, resets, d, fin_len, fin_rew);
+    Env::obs(st, ob);
+    for (int j = 0; j < Env::STATE; j++) env_state[(size_t)j * N + i] = st[j];
+    ep_len[i] = len;
+    ep_rew[i] = rew;
+    reset_count[i] = resets;
+    for (int j = 0; j < Env::OBS; j++) obs[(size_t)i * Env::OBS + j] = ob[j];
+    reward[i] = r;
+    done[i] = d;
+}
+// ppo_env_transition: stateless; state [n, Env::STATE], action i64 [n]
+template <class Env>
+__global__ void cat_env_transition_kernel(const float* __restrict__ state_in, const int64_t* __restrict__ action, int64_t n, float* next_state, float* reward,
+                                          int32_t* terminated) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float st[Env::STATE];
+    for (int j = 0; j < Env::STATE; j++) st[j] = state_in[i * Env::STATE + j];
+    int term;
+    const float r = Env::step(st, (int)action[i], term);
+    for (int j = 0; j < Env::STATE; j++) next_state[i * Env::STATE + j] = st[j];
+    reward[i] = r;
+    terminated[i] = term;
+}
+// ppo_env_set_state_h: NEXT_OBS from the injected states ([Env::STATE, N])
+template <class Env>
+__global__ void cat_env_obs_kernel(int N, const float* __restrict__ state, float* obs_out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    float st[Env::STATE], ob[Env::OBS];
+    for (int j = 0; j < Env::STATE; j++) st[j] = state[(size_t)j * N + i];
+    Env::obs(st, ob);
+    for (int j = 0; j < Env::OBS; j++) obs_out[(size_t)i * Env::OBS + j] = ob[j];
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// cat_eval_kernel<Env> (ppo_evaluate on PPO_ENV_ACROBOT): gauss_eval_kernel's plan with a categorical head.  A workgroup owns 64 episodes for their whole
+// length with the actor's weights resident: lane l of wave 0 keeps episode 64 b + l (state, return, length) in registers -- the STATE, not the observation:
+// nothing here needs an observation to be a state -- writes its observation into the X image, every thread runs gf_forward_tile, and wave 0 takes the
+// first-index argmax of the probabilities (greedy: ppo_policy_act_greedy's) or the draw keyed (seed, episode, step of the episode, head 0) --
+// ppo_policy_act(step_index = step) on row `episode` -- and steps the env (Env::step).  The loop's exit is uniform: wave 0 publishes its live count in the
+// row-index words, the step's closing barrier hands it to the other waves (gauss_eval_kernel).  At most max_episode_steps steps.
+// ---------------------------------------------------------------------------------------------------------
+template <class Env>
+__global__ __launch_bounds__(GF_THREADS) void cat_eval_kernel(GfEvalArgs a) {
+    constexpr int OBS = Env::OBS, ST = Env::STATE, A = Env::ACTIONS, OBSP = (OBS + 3) & ~3;
+    static_assert(OBS <= 8 && A <= 4, "as cat_rollout_kernel");
+    extern __shared__ __attribute__((aligned(16))) float gf_lds[];
+    const int tid = threadIdx.x;
+    const GfLds m = gf_carve(gf_lds, OBSP, 4);
+    gf_stage_weights(m, a.sh, a.params, 1, tid);
+    const int64_t ep = (int64_t)blockIdx.x * 64 + (tid & 63);
+    bool alive = tid < 64 && ep < a.n_episodes;
+    const bool owner = alive;
+    float st[ST], ob[OBS], ep_rew = 0.0f;
+#pragma unroll
+    for (int k = 0; k < ST; k++) st[k] = 0.0f;
+#pragma unroll
+    for (int k = 0; k < OBS; k++) ob[k] = 0.0f;
+    int ep_len = 0, trunc = 0;
+    if (owner) {
+        Env::reset(st, 0, a.seed, ep);
+        Env::obs(st, ob);
+    }
+    if (tid < 64) {
+#pragma unroll
+        for (int k = OBS; k < OBSP; k++) m.x[k * GF_S + tid] = 0.0f;
+    }
+    for (;;) {
+        if (tid < 64) {
+#pragma unroll
+            for (int k = 0; k < OBS; k++) m.x[k * GF_S + tid] = ob[k];
+        }
+        gf_forward_tile(m, A, tid);
+        if (tid < 64) {
+            if (alive) {
+                float lp;
+                int act;
+                if (a.greedy) act = cat_lane_head<true>(m, tid, A, false, 0, 0u, lp);
+                else act = cat_lane_head<false>(m, tid, A, false, 0, cat_draw_word(a.seed, ep, (int64_t)ep_len), lp);
+                int term;
+                const float r = Env::step(st, act, term);
+                ep_len += 1;
+                ep_rew += r;
+                trunc = ep_len == a.max_episode_steps ? 1 : 0;
+                if (term || trunc) alive = false;
+                Env::obs(st, ob);
+            }
+            const unsigned long long live = __ballot(alive);
+            if (tid == 0) m.ridx[0] = __popcll(live);
+        }
+        __syncthreads();   // the live count is published; OUT and the H1 columns are read
+        if (m.ridx[0] == 0) break;
+        // the next write of the count is behind the next forward's four barriers: every wave has read this one by then
+    }
+    if (owner) {
+        a.ep_return[ep] = ep_rew;
+        a.ep_length[ep] = ep_len;
+        a.ep_trunc[ep] = trunc;
+    }
+}
+
 template <typename K>
 hipError_t gf_allow(std::atomic<unsigned long long>& done, K kernel, int bytes) {
     return bytes > 64 * 1024 ? allow_dynamic_lds(done, reinterpret_cast<const void*>(kernel)) : hipSuccess;
@@ -1322,4 +1594,93 @@ hipError_t gauss_fused_evaluate(int env_kind, const GenLayout& L, const GaussEva
     const int bytes = gf_lds_floats(4, 4) * 4;
     hipLaunchKernelGGL(gauss_eval_kernel<GaussEnvMountainCarContinuous>, dim3((unsigned)((e.n_episodes + 63) / 64)), dim3(GF_THREADS), bytes, s, a);
     return hipGetLastError();
+}
+
+// ---- the device envs with integer actions (PPO_ENV_ACROBOT; the context's shape is fixed by ppo_ctx_create: obs Env::OBS, one head of Env::ACTIONS logits) ----
+template <class F>
+static hipError_t cat_env_dispatch(int env_kind, F f) {
+    if (env_kind == PPO_ENV_ACROBOT) return f(CatEnvAcrobot{});
+    return hipErrorInvalidValue;
+}
+template <class Env>
+static bool cat_env_shape_ok(const GenLayout& L) { return L.obs == Env::OBS && L.gauss == 0 && L.n_heads == 1 && L.act == Env::ACTIONS; }
+template <class Env>
+static int cat_env_lds_bytes() { return gf_lds_floats(gf_pad4(Env::OBS), 4) * 4; }
+
+bool cat_fused_env_serves(int env_kind) { return env_kind == PPO_ENV_ACROBOT; }
+
+hipError_t cat_fused_rollout(int env_kind, const GenLayout& L, const CatRolloutArgs& r, hipStream_t s) {
+    if (r.N <= 0 || r.T <= 0) return hipSuccess;
+    return cat_env_dispatch(env_kind, [&](auto env) {
+        using Env = decltype(env);
+        if (!cat_env_shape_ok<Env>(L)) return hipErrorInvalidValue;
+        CfRolloutArgs a{};
+        a.sh = gf_shape(L);
+        a.params = r.params;
+        a.N = r.N; a.T = r.T; a.max_episode_steps = r.max_episode_steps;
+        a.seed = r.seed; a.env_offset = r.env_offset; a.step_base = r.step_base;
+        a.env_state = r.env_state; a.ep_len = r.ep_len; a.ep_rew = r.ep_rew; a.reset_count = r.reset_count;
+        a.obs = r.obs; a.masks = r.masks; a.actions = r.actions; a.logprobs = r.logprobs; a.rewards = r.rewards; a.dones = r.dones;
+        a.fin_len = r.fin_len; a.fin_rew = r.fin_rew;
+        a.next_obs = r.next_obs; a.next_done = r.next_done; a.forced = r.forced;
+        const int bytes = cat_env_lds_bytes<Env>();
+        static std::atomic<unsigned long long> done{ 0 };
+        const hipError_t e = gf_allow(done, cat_rollout_kernel<Env>, bytes);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(cat_rollout_kernel<Env>, dim3((unsigned)((r.N + 63) / 64)), dim3(GF_THREADS), bytes, s, a);
+        return hipGetLastError();
+    });
+}
+
+hipError_t launch_cat_env_reset(int env_kind, int N, int64_t seed, int64_t env_offset, float* env_state, int32_t* ep_len, float* ep_rew, int32_t* reset_count,
+                                float* next_obs, int32_t* next_done, hipStream_t s) {
+    if (N <= 0) return hipSuccess;
+    return cat_env_dispatch(env_kind, [&](auto env) {
+        hipLaunchKernelGGL(cat_env_reset_kernel<decltype(env)>, dim3((N + 255) / 256), dim3(256), 0, s, N, seed, env_offset, env_state, ep_len, ep_rew, reset_count,
+                           next_obs, next_done);
+        return hipGetLastError();
+    });
+}
+hipError_t launch_cat_env_step(int env_kind, int N, int max_episode_steps, int64_t seed, int64_t env_offset, float* env_state, int32_t* ep_len, float* ep_rew,
+                               int32_t* reset_count, const int64_t* action, float* obs, float* reward, int32_t* done, hipStream_t s) {
+    if (N <= 0) return hipSuccess;
+    return cat_env_dispatch(env_kind, [&](auto env) {
+        hipLaunchKernelGGL(cat_env_step_kernel<decltype(env)>, dim3((N + 255) / 256), dim3(256), 0, s, N, max_episode_steps, seed, env_offset, env_state, ep_len,
+                           ep_rew, reset_count, action, obs, reward, done);
+        return hipGetLastError();
+    });
+}
+hipError_t launch_cat_env_transition(int env_kind, const float* state_in, const int64_t* action, int64_t n, float* next_state, float* reward, int32_t* terminated,
+                                     hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    if (n >= (1ll << 31) * 256) return hipErrorInvalidValue;
+    return cat_env_dispatch(env_kind, [&](auto env) {
+        hipLaunchKernelGGL(cat_env_transition_kernel<decltype(env)>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, state_in, action, n, next_state, reward,
+                           terminated);
+        return hipGetLastError();
+    });
+}
+hipError_t launch_cat_env_obs(int env_kind, int N, const float* env_state, float* next_obs, hipStream_t s) {
+    if (N <= 0) return hipSuccess;
+    return cat_env_dispatch(env_kind, [&](auto env) {
+        hipLaunchKernelGGL(cat_env_obs_kernel<decltype(env)>, dim3((N + 255) / 256), dim3(256), 0, s, N, env_state, next_obs);
+        return hipGetLastError();
+    });
+}
+hipError_t cat_fused_evaluate(int env_kind, const GenLayout& L, const GaussEvalArgs& e, hipStream_t s) {
+    if (e.n_episodes <= 0) return hipSuccess;
+    if (e.max_episode_steps < 1 || e.n_episodes >= (1ll << 31) * 64 || !e.ep_return || !e.ep_length || !e.ep_trunc) return hipErrorInvalidValue;
+    return cat_env_dispatch(env_kind, [&](auto env) {
+        using Env = decltype(env);
+        if (!cat_env_shape_ok<Env>(L)) return hipErrorInvalidValue;
+        GfEvalArgs a{};
+        a.sh = gf_shape(L);
+        a.params = e.params;
+        a.n_episodes = e.n_episodes; a.seed = e.seed;
+        a.max_episode_steps = e.max_episode_steps; a.greedy = e.greedy != 0;
+        a.ep_return = e.ep_return; a.ep_length = e.ep_length; a.ep_trunc = e.ep_trunc;
+        const int bytes = cat_env_lds_bytes<Env>();
+        hipLaunchKernelGGL(cat_eval_kernel<Env>, dim3((unsigned)((e.n_episodes + 63) / 64)), dim3(GF_THREADS), bytes, s, a);
+        return hipGetLastError();
+    });
 }

@@ -382,6 +382,123 @@ struct GaussEnvMountainCarContinuous {
     }
 };
 
+// Acrobot-v1 (gymnasium's classic_control/acrobot.py, "book" dynamics, no torque noise; no reference counterpart: PPO_ENV_ACROBOT).  st = {th1, th2, w1, w2};
+// action a in {0, 1, 2}, tau = (float)a - 1.0f.  Every operation rounds on its own (-ffp-contract=off), in exactly this association (ppo_hip.h repeats it;
+// m1 = m2 = l1 = 1, lc1 = lc2 = 0.5, I1 = I2 = 1, g = 9.8, dt = 0.2; 4.9f = m2 lc2 g, 14.7f = (m1 lc1 + m2 l1) g):
+//   dsdt:  c2 = cosr(th2);  s2 = sinr(th2)
+//          d1   = (0.25f + (1.25f + c2)) + 2.0f
+//          d2   = (0.25f + 0.5f * c2) + 1.0f
+//          phi2 = 4.9f * cosr((th1 + th2) - HALF_PI_F)
+//          phi1 = (((-0.5f * (w2 * w2)) * s2 - (w2 * w1) * s2) + 14.7f * cosr(th1 - HALF_PI_F)) + phi2
+//          dw2  = (((tau + (d2 / d1) * phi1) - (0.5f * (w1 * w1)) * s2) - phi2) / (1.25f - (d2 * d2) / d1)
+//          dw1  = -(d2 * dw2 + phi1) / d1
+//          dsdt = (w1, w2, dw1, dw2)
+//   RK4:   k1 = dsdt(s), k2 = dsdt(s + 0.1f * k1), k3 = dsdt(s + 0.1f * k2), k4 = dsdt(s + 0.2f * k3);  s' = s + DT6 * (((k1 + 2.0f * k2) + 2.0f * k3) + k4)
+//   wrap th1', th2' into [-PI_F, PI_F] by gym's loops of -+ TWO_PI_F (capped at 1024 turns each: a non-finite input cannot hang a wave);
+//   clip w1' to -+ (float)(4 pi), w2' to -+ (float)(9 pi);  terminated = ((-cosr(th1')) - cosr(th2' + th1') > 1.0f);  reward = terminated ? 0 : -1
+// cosr / sinr: glibc_cosf / glibc_sinf hold for |x| < 120, and the RK4 stage angles leave that range in the corners of the state box (stage velocities of
+// ~2000 rad/s): an argument of 64 or more is first reduced in binary64, x - TWO_PI_D * rint(x / TWO_PI_D), each operation rounded on its own, and rounded
+// to f32.  1.25 - d2^2 / d1 >= 0.56 for every c2 in [-1, 1], so a finite state gives a finite step.
+constexpr float ACRO_PI_F = 3.14159265358979323846f, ACRO_TWO_PI_F = 6.28318530717958647692f, ACRO_HALF_PI_F = 1.57079632679489661923f;
+constexpr float ACRO_MAX_W1 = 12.566370614359172f, ACRO_MAX_W2 = 28.274333882308138f, ACRO_DT6 = (float)(0.2 / 6.0);
+constexpr double ACRO_TWO_PI_D = 6.283185307179586476925;
+__device__ __forceinline__ float acro_reduce(float x) {
+    const double xd = (double)x;
+    const double q = rint(xd / ACRO_TWO_PI_D);
+    const double p = ACRO_TWO_PI_D * q;
+    return (float)(xd - p);
+}
+__device__ __forceinline__ float acro_sinr(float x) { return glibc_sinf(fabsf(x) < 64.0f ? x : acro_reduce(x)); }
+__device__ __forceinline__ float acro_cosr(float x) { return glibc_cosf(fabsf(x) < 64.0f ? x : acro_reduce(x)); }
+__device__ __forceinline__ void acrobot_dsdt(const float* s, float tau, float* k) {
+    const float th1 = s[0], th2 = s[1], w1 = s[2], w2 = s[3];
+    const float c2 = acro_cosr(th2), s2 = acro_sinr(th2);
+    const float d1 = (0.25f + (1.25f + c2)) + 2.0f;
+    const float d2 = (0.25f + 0.5f * c2) + 1.0f;
+    const float phi2 = 4.9f * acro_cosr((th1 + th2) - ACRO_HALF_PI_F);
+    const float phi1 = (((-0.5f * (w2 * w2)) * s2 - (w2 * w1) * s2) + 14.7f * acro_cosr(th1 - ACRO_HALF_PI_F)) + phi2;
+    const float dw2 = (((tau + (d2 / d1) * phi1) - (0.5f * (w1 * w1)) * s2) - phi2) / (1.25f - (d2 * d2) / d1);
+    const float dw1 = -(d2 * dw2 + phi1) / d1;
+    k[0] = w1; k[1] = w2; k[2] = dw1; k[3] = dw2;
+}
+__device__ __forceinline__ float acro_wrap(float x) {
+    for (int i = 0; i < 1024 && x > ACRO_PI_F; i++) x -= ACRO_TWO_PI_F;
+    for (int i = 0; i < 1024 && x < -ACRO_PI_F; i++) x += ACRO_TWO_PI_F;
+    return x;
+}
+__device__ __forceinline__ float acrobot_step(float* st, int action, int& terminated) {
+    const float tau = (float)action - 1.0f;
+    float k1[4], k2[4], k3[4], k4[4], y[4];
+    acrobot_dsdt(st, tau, k1);
+#pragma unroll
+    for (int i = 0; i < 4; i++) y[i] = st[i] + 0.1f * k1[i];
+    acrobot_dsdt(y, tau, k2);
+#pragma unroll
+    for (int i = 0; i < 4; i++) y[i] = st[i] + 0.1f * k2[i];
+    acrobot_dsdt(y, tau, k3);
+#pragma unroll
+    for (int i = 0; i < 4; i++) y[i] = st[i] + 0.2f * k3[i];
+    acrobot_dsdt(y, tau, k4);
+#pragma unroll
+    for (int i = 0; i < 4; i++) y[i] = st[i] + ACRO_DT6 * (((k1[i] + 2.0f * k2[i]) + 2.0f * k3[i]) + k4[i]);
+    const float th1 = acro_wrap(y[0]), th2 = acro_wrap(y[1]);
+    const float w1 = y[2] < -ACRO_MAX_W1 ? -ACRO_MAX_W1 : (y[2] > ACRO_MAX_W1 ? ACRO_MAX_W1 : y[2]);
+    const float w2 = y[3] < -ACRO_MAX_W2 ? -ACRO_MAX_W2 : (y[3] > ACRO_MAX_W2 ? ACRO_MAX_W2 : y[3]);
+    st[0] = th1; st[1] = th2; st[2] = w1; st[3] = w2;
+    terminated = ((-acro_cosr(th1)) - acro_cosr(th2 + th1) > 1.0f) ? 1 : 0;
+    return terminated ? 0.0f : -1.0f;
+}
+// the observation of a state: (cos th1, sin th1, cos th2, sin th2, w1, w2)
+__device__ __forceinline__ void acrobot_obs(const float* st, float* obs) {
+    obs[0] = acro_cosr(st[0]);
+    obs[1] = acro_sinr(st[0]);
+    obs[2] = acro_cosr(st[1]);
+    obs[3] = acro_sinr(st[1]);
+    obs[4] = st[2];
+    obs[5] = st[3];
+}
+// reset number k of global env e: MountainCar's keying, philox(seed; e, k, 0, 1); the four words, in state order, mapped to [-0.1, 0.1)
+__device__ __forceinline__ void acrobot_reset(float* st, int k, int64_t seed, int64_t env_global) {
+    const uint4 w = philox4x32_10((uint32_t)seed, (uint32_t)((uint64_t)seed >> 32), (uint32_t)env_global, (uint32_t)k, 0u, 1u);
+    st[0] = canon_to_uniform(w.x, -0.1f, 0.1f);
+    st[1] = canon_to_uniform(w.y, -0.1f, 0.1f);
+    st[2] = canon_to_uniform(w.z, -0.1f, 0.1f);
+    st[3] = canon_to_uniform(w.w, -0.1f, 0.1f);
+}
+// One step of an Acrobot env with env_step_kernel's bookkeeping (the episode ends where the env terminates or its length reaches the limit): ONE definition
+// for the fused rollout and the stand-alone step.  Returns the reward; done / fin_len / fin_rew are the step's.
+__device__ __forceinline__ float acrobot_step_episode(float* st, int action, int max_episode_steps, int64_t seed, int64_t env_global, int& ep_len, float& ep_rew,
+                                                      int& resets, int& done, int& fin_len, float& fin_rew) {
+    int term;
+    const float r = acrobot_step(st, action, term);
+    ep_len += 1;
+    ep_rew += r;
+    done = (term || ep_len == max_episode_steps) ? 1 : 0;
+    fin_len = 0;
+    fin_rew = 0.0f;
+    if (done) {
+        fin_len = ep_len;
+        fin_rew = ep_rew;
+        acrobot_reset(st, resets++, seed, env_global);
+        ep_len = 0;
+        ep_rew = 0.0f;
+    }
+    return r;
+}
+// What the fused categorical kernels need of a device env with integer actions (kernels_gauss_fused.hip: cat_rollout_kernel, the stand-alone env kernels,
+// cat_eval_kernel): GaussEnv*'s members with an int action.  The env takes head 0's action.
+struct CatEnvAcrobot {
+    static constexpr int OBS = 6, STATE = 4, ACTIONS = 3;
+    static constexpr bool OBS_IS_STATE = false;
+    __device__ static __forceinline__ void obs(const float* st, float* ob) { acrobot_obs(st, ob); }
+    __device__ static __forceinline__ float step(float* st, int a, int& terminated) { return acrobot_step(st, a, terminated); }
+    __device__ static __forceinline__ void reset(float* st, int k, int64_t seed, int64_t env_global) { acrobot_reset(st, k, seed, env_global); }
+    __device__ static __forceinline__ float step_episode(float* st, int a, int max_episode_steps, int64_t seed, int64_t env_global, int& ep_len, float& ep_rew,
+                                                         int& resets, int& done, int& fin_len, float& fin_rew) {
+        return acrobot_step_episode(st, a, max_episode_steps, seed, env_global, ep_len, ep_rew, resets, done, fin_len, fin_rew);
+    }
+};
+
 template <int ENV>
 __device__ __forceinline__ float env_step(float* st, int action, int& terminated) {
     if constexpr (ENV == PPO_ENV_CARTPOLE) return cartpole_step(st, action, terminated);
