@@ -265,11 +265,40 @@ typedef struct ppo_config {
  *                               ppo_ctx_create return PPO_ERR_UNSUPPORTED with a message that names the limit -- never served by another engine instead.
  *                               ppo_evaluate stays refused as on the generic engine; truncation flags in ppo_dev_observe are served as on a
  *                               PPO_KERNEL_GAUSS_FUSED context (the critic kernel is shared, and so is the fold: gauss_dev_fold_kernel).
- *                               ppo_gauss_fused_launches counts the three kernels' launches (one set of counters for the family; no symbol of its own). */
+ *                               ppo_gauss_fused_launches counts the three kernels' launches (one set of counters for the family; no symbol of its own).
+ *   PPO_KERNEL_ENV_GENERIC      env_kind = PPO_ENV_CARTPOLE or PPO_ENV_MOUNTAINCAR on a network of any width and depth: the context lives in the generic
+ *                               engine's layout, with PPO_ENV_SYNTHETIC's network limits (hidden 1 .. 2048, n_hidden 1 .. 7, PPO_DTYPE_F32 or PPO_DTYPE_BF16)
+ *                               and its parameter order (Agent::parameters() order generalised, as ppo_param_shapes reports it).  dist_kind, n_heads,
+ *                               head_dims, obs_size, the wrong-obs-size message and the masks are those of the same context without the flag (PPO_BUF_MASKS:
+ *                               ones under PPO_DIST_MASKED, untouched otherwise).  The env is the unflagged context's, kernel for kernel: PPO_BUF_ENV_STATE,
+ *                               EP_LEN, EP_REW, RESET_COUNT, CartPole's shared reset table, ppo_env_reset (env 0's probe reset included), ppo_env_step,
+ *                               ppo_env_set_state_h / ppo_env_get_state_h, max_episode_steps, FIN_LEN / FIN_REW, the episode ring and the statistics.
+ *                               ppo_rollout (forced i64 [T,N,H] or NULL), ppo_calc_advantage, ppo_update, ppo_minibatch_forward_backward, ppo_optimizer_step,
+ *                               ppo_train_iteration, ppo_policy_act, ppo_policy_act_greedy, ppo_get_value, ppo_target_kl_set and the statistics and profile
+ *                               calls run on the generic engine's paths.  The rollout, f32 storage: per step the engine's forward, heads and stores, then
+ *                               the env's step kernel on the context's buffers -- the launches of ppo_policy_act(step_index = rollout_steps + t) +
+ *                               ppo_env_step, same bits.  bf16 storage, wherever the engine's fused forward serves the network (sum(head_dims) <= 32, both
+ *                               LDS tiles fit): generic_env_rollout_kernel, all T steps in ONE launch -- 32 envs per workgroup, the actor's layers on the
+ *                               matrix cores with the activations in LDS, lanes 0 .. 31 of wave 0 sample the heads and keep state, episode sums, reset
+ *                               count and done flag in registers, step the env and write the next observation themselves; two critic launches follow on
+ *                               CartPole.  MountainCar with bf16 storage: the fused forward stages f32 rows as 16-byte pieces (obs_size % 4 == 0), which an
+ *                               observation of 2 is not, so every critic or actor batch outside the rollout kernel -- the rollout's critic over the T N
+ *                               stored rows and over NEXT_OBS, ppo_get_value, ppo_policy_act, ppo_policy_act_greedy -- first rounds its rows to bf16
+ *                               (one conversion launch) and then runs the same fused layers, per chunk of the workspace's rows (max(minibatch, N) rounded
+ *                               up to 128): 2 launches per chunk, about 2 (num_minibatches + 1) behind a rollout instead of 2, same bits as the rollout's.
+ *                               Also at 2 x 64: the flag takes the context off the reference-shape kernels, as their A/B partner (log-probs and values then
+ *                               agree to summation order, not bit for bit; the env's bits do not change under the same actions).  Opt-in, never implied;
+ *                               ppo_ctx_create returns PPO_ERR_UNSUPPORTED with a message naming the flag and the limit for any other env_kind, for
+ *                               PPO_KERNEL_GAUSS_FUSED or PPO_KERNEL_CAT_FUSED beside it and for PPO_DIST_GAUSSIAN -- another engine never serves in the
+ *                               flag's place.  Refused on such a context, changing nothing: ppo_host_* / ppo_dev_* (PPO_ERR_STATE, as on any device env),
+ *                               ppo_obs_norm_* / ppo_reward_norm_* (PPO_ERR_UNSUPPORTED), ppo_evaluate (PPO_ERR_UNSUPPORTED: step the episodes with
+ *                               ppo_policy_act_greedy + ppo_env_transition), ppo_env_truncation_bootstrap and ppo_env_truncations (PPO_ERR_UNSUPPORTED: the
+ *                               fold is built on the reference-shape critic).  Sharding (ppo_comm_init*) of a flagged context is neither claimed nor tested. */
 enum { PPO_KERNEL_ROLLOUT_VECTOR = 1, PPO_KERNEL_UPDATE_VECTOR = 2, PPO_KERNEL_UPDATE_ONE_WAVE = 4, PPO_KERNEL_COMM_SELFTEST = 8, PPO_KERNEL_GENERIC_CLASSIC = 16,
        PPO_KERNEL_GENERIC_SPLIT_HEAD = 32, PPO_KERNEL_GAUSS_FUSED = 64 };
 #define PPO_KERNEL_SEPARATE_LAUNCHES 128   /* the next free bit of kernel_flags, 1 << 7; a macro beside the enumerators: same type in an expression, same use */
 #define PPO_KERNEL_CAT_FUSED 256           /* 1 << 8, likewise */
+#define PPO_KERNEL_ENV_GENERIC 512         /* 1 << 9, likewise */
 
 /* Scalars the reference prints per update (PPO_Discrete.cpp:700-774) plus per-step diagnostics. */
 typedef struct ppo_stats {

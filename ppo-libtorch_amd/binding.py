@@ -24,6 +24,7 @@ DIST_CATEGORICAL, DIST_MASKED, DIST_GAUSSIAN = 0, 1, 2   # DIST_GAUSSIAN: f32 ac
 DTYPE_F32, DTYPE_BF16 = 0, 1
 KERNEL_ROLLOUT_VECTOR, KERNEL_UPDATE_VECTOR, KERNEL_UPDATE_ONE_WAVE, KERNEL_COMM_SELFTEST, KERNEL_GENERIC_CLASSIC, KERNEL_GENERIC_SPLIT_HEAD, KERNEL_GAUSS_FUSED, KERNEL_SEPARATE_LAUNCHES = 1, 2, 4, 8, 16, 32, 64, 128   # ppo_config.kernel_flags (include/ppo_hip.h PPO_KERNEL_*)
 KERNEL_CAT_FUSED = 256   # categorical / masked policies of a 2 x 64 f32 ENV_HOST context on the fused kernel family (include/ppo_hip.h PPO_KERNEL_CAT_FUSED)
+KERNEL_ENV_GENERIC = 512   # ENV_CARTPOLE / ENV_MOUNTAINCAR on a network of any width and depth, f32 or bf16 (include/ppo_hip.h PPO_KERNEL_ENV_GENERIC)
 ABI_VERSION = 5
 COMM_ID_BYTES = 128
 COMM_HANDLE_BYTES = 64

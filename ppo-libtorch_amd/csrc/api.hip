@@ -200,6 +200,8 @@ struct ppo_ctx {
     bool gauss_fused = false;
     // PPO_KERNEL_CAT_FUSED: the categorical twin on the same kernel family; it shares the counters (ppo_gauss_fused_launches reads them for either flag) and the slabs
     bool cat_fused = false;
+    // PPO_KERNEL_ENV_GENERIC: CartPole / MountainCar (their own env kernels, state layout and reset table) under a network in the generic engine's layout
+    bool env_generic = false;
     int64_t gf_launches[3] = { 0, 0, 0 };
     float* gf_slab = nullptr;
     unsigned long long* stamps = nullptr;  // [2][12] phase cycles of the diagnostic kernel variant
@@ -578,7 +580,10 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
     // PPO_ENV_ACROBOT: the device env of the fused categorical kernels (cat_rollout_kernel); the network lives in the generic engine's layout, as a
     // PPO_ENV_HOST context with PPO_KERNEL_CAT_FUSED does
     const bool acrobot = cfg->env_kind == PPO_ENV_ACROBOT;
-    const bool generic = cfg->env_kind == PPO_ENV_SYNTHETIC || (host_env && !host_ref) || gauss_env || acrobot;
+    // PPO_KERNEL_ENV_GENERIC on CartPole / MountainCar: the network lives in the generic engine's layout, with PPO_ENV_SYNTHETIC's limits (the flag anywhere
+    // else is refused below, behind the checks of env_kind, dist_kind, compute_dtype and of the flag word itself)
+    const bool env_generic = (cfg->kernel_flags & PPO_KERNEL_ENV_GENERIC) != 0 && (cfg->env_kind == PPO_ENV_CARTPOLE || cfg->env_kind == PPO_ENV_MOUNTAINCAR);
+    const bool generic = cfg->env_kind == PPO_ENV_SYNTHETIC || (host_env && !host_ref) || gauss_env || acrobot || env_generic;
     if (!generic && (cfg->hidden != PPO_HIDDEN || cfg->n_hidden != 2))
         return fail(nullptr, PPO_ERR_UNSUPPORTED, "only the reference architecture (2 hidden layers of 64, Agent.cpp:25-59) is built for the reference's "
                     "environments; got %d x %d (other shapes run with env_kind = PPO_ENV_SYNTHETIC)", cfg->n_hidden, cfg->hidden);
@@ -589,6 +594,22 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
         return fail(nullptr, PPO_ERR_INVALID, "unknown env_kind %d", cfg->env_kind);
     if (cfg->dist_kind != PPO_DIST_CATEGORICAL && cfg->dist_kind != PPO_DIST_MASKED && !gauss) return fail(nullptr, PPO_ERR_INVALID, "unknown dist_kind %d", cfg->dist_kind);
     if (cfg->compute_dtype != PPO_DTYPE_F32 && cfg->compute_dtype != PPO_DTYPE_BF16) return fail(nullptr, PPO_ERR_INVALID, "unknown compute_dtype %d", cfg->compute_dtype);
+    constexpr int32_t known_flags = PPO_KERNEL_ROLLOUT_VECTOR | PPO_KERNEL_UPDATE_VECTOR | PPO_KERNEL_UPDATE_ONE_WAVE | PPO_KERNEL_COMM_SELFTEST | PPO_KERNEL_GENERIC_CLASSIC |
+                                  PPO_KERNEL_GENERIC_SPLIT_HEAD | PPO_KERNEL_GAUSS_FUSED | PPO_KERNEL_SEPARATE_LAUNCHES | PPO_KERNEL_CAT_FUSED | PPO_KERNEL_ENV_GENERIC;
+    // PPO_KERNEL_ENV_GENERIC: CartPole / MountainCar with a categorical policy and neither flag of the fused 2 x 64 family, or a refusal that names the flag --
+    // never another engine in its place.  In front of the envs' own blocks, so that the flag on one of them is answered here
+    if (cfg->kernel_flags & PPO_KERNEL_ENV_GENERIC) {
+        if (cfg->kernel_flags & ~known_flags) return fail(nullptr, PPO_ERR_INVALID, "unknown bits in kernel_flags 0x%x", cfg->kernel_flags);
+        if (!env_generic)
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_ENV_GENERIC serves env_kind = PPO_ENV_CARTPOLE and PPO_ENV_MOUNTAINCAR only (the other device envs "
+                        "run on their own kernel families, PPO_ENV_SYNTHETIC and PPO_ENV_HOST are on the generic engine without it); got env_kind %d", cfg->env_kind);
+        if (cfg->kernel_flags & (PPO_KERNEL_GAUSS_FUSED | PPO_KERNEL_CAT_FUSED))
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_ENV_GENERIC excludes PPO_KERNEL_GAUSS_FUSED and PPO_KERNEL_CAT_FUSED: those flags name the fused 2 x 64 "
+                        "kernel family, this one the generic engine; a context runs on one of them");
+        if (gauss)
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_ENV_GENERIC serves dist_kind = PPO_DIST_CATEGORICAL and PPO_DIST_MASKED only: CartPole and MountainCar take "
+                        "discrete actions; got PPO_DIST_GAUSSIAN");
+    }
     if (pendulum) {   // accepted in exactly one form (ppo_hip.h: PPO_ENV_PENDULUM); a wrong obs_size first, with the reference's message (below)
         if (cfg->obs_size == 3) {
             if (!gauss)
@@ -659,7 +680,7 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
         return fail(nullptr, PPO_ERR_UNSUPPORTED, "dist_kind = PPO_DIST_GAUSSIAN is built for compute_dtype = PPO_DTYPE_F32; bf16 storage is not");
     if (gauss && cfg->n_heads != 1)
         return fail(nullptr, PPO_ERR_UNSUPPORTED, "dist_kind = PPO_DIST_GAUSSIAN takes n_heads = 1 with head_dims[0] = the action dimension D; got n_heads = %d", cfg->n_heads);
-    if (cfg->kernel_flags & ~(PPO_KERNEL_ROLLOUT_VECTOR | PPO_KERNEL_UPDATE_VECTOR | PPO_KERNEL_UPDATE_ONE_WAVE | PPO_KERNEL_COMM_SELFTEST | PPO_KERNEL_GENERIC_CLASSIC | PPO_KERNEL_GENERIC_SPLIT_HEAD | PPO_KERNEL_GAUSS_FUSED | PPO_KERNEL_SEPARATE_LAUNCHES | PPO_KERNEL_CAT_FUSED)) return fail(nullptr, PPO_ERR_INVALID, "unknown bits in kernel_flags 0x%x", cfg->kernel_flags);
+    if (cfg->kernel_flags & ~known_flags) return fail(nullptr, PPO_ERR_INVALID, "unknown bits in kernel_flags 0x%x", cfg->kernel_flags);
     // PPO_KERNEL_CAT_FUSED: the one form kernels_gauss_fused.hip's categorical kernels are built for, or a refusal -- never another engine in its place
     if (cat_fused) {
         if (cfg->kernel_flags & PPO_KERNEL_GAUSS_FUSED)
@@ -931,6 +952,10 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
             CK(dalloc(c, &c->gf_slab, (size_t)2 * GAUSS_FUSED_MAX_BLOCKS * gauss_fused_slab_stride(GL)));
         }
         CK(dalloc(c, &c->cur_mask, N * GL.act));
+        if (env_generic) {   // CartPole::getActionMask / MountainCar::getActionMask are all ones (MountainCar.cpp:69-77): the mask of every step under PPO_DIST_MASKED
+            c->env_generic = true;
+            CK(hipMemset(c->cur_mask, 1, N * GL.act));
+        }
         // the zero-fills above ran on the null stream, which a non-blocking stream does not wait for: drain them before the first write
         CK(hipDeviceSynchronize());
         CK(gen_fill(g.row_f[4] + 2, (int64_t)R, 1.0f, c->stream));   // the ones vector of the bias-gradient gemv
@@ -1156,9 +1181,28 @@ extern "C" ppo_status ppo_params_init_orthogonal(ppo_ctx* c, int64_t seed) {
     return ppo_params_set_h(c, p.data(), c->L.P);
 }
 
+// PPO_KERNEL_ENV_GENERIC with bf16 storage on MountainCar: generic_forward_kernel stages f32 rows as 16-byte pieces (obs_size % 4 == 0), which an observation
+// of 2 is not.  Rounded to bf16 into g.xin_bf first (gen_forward's own first launch), the rows go through the fused layers the rollout kernel runs, so
+// ppo_policy_act and ppo_get_value give a row the one-launch rollout's logits and value, bit for bit, as they do on CartPole.
+static inline bool env_generic_via_bf16(const ppo_ctx* c) { return c->env_generic && gen_fused_ok(*c->gen) && !gen_fused_forward_ok(*c->gen); }
+static ppo_status gen_fused_rows_via_bf16(ppo_ctx* c, int net, const float* obs, int64_t rows, float* out) {
+    GenericCtx& g = *c->gen;
+    NEED(c, rows <= g.rows_max, "more rows than the workspace holds");
+    HIPCHK(c, launch_to_bf16_pad(obs, rows, g.L.obs, g.xin_bf, g.ld_in0, c->stream));
+    HIPCHK(c, gen_fused_forward(g, B_<float>(c, PPO_BUF_PARAMS), net, nullptr, g.xin_bf, g.ld_in0, rows, false, out, c->stream));
+    return PPO_OK;
+}
+
 // ---- generic networks (generic.hpp): critic / actor over n rows, chunked to the workspace size ----
 static ppo_status gen_values(ppo_ctx* c, const float* obs, int64_t n, float* value) {
     GenericCtx& g = *c->gen;
+    if (env_generic_via_bf16(c)) {
+        for (int64_t off = 0; off < n; off += g.rows_max) {
+            const ppo_status s = gen_fused_rows_via_bf16(c, 0, obs + off * g.L.obs, std::min<int64_t>(g.rows_max, n - off), value + off);
+            if (s != PPO_OK) return s;
+        }
+        return PPO_OK;
+    }
     if (c->gauss_fused || c->cat_fused) {   // PPO_KERNEL_GAUSS_FUSED / PPO_KERNEL_CAT_FUSED: the critic over all n rows in one launch (the kernel is distribution-free)
         NEED(c, n < (1ll << 31), "more than 2^31 rows");
         if (n > 0) c->gf_launches[1] += 1;
@@ -1202,7 +1246,10 @@ static ppo_status gen_policy(ppo_ctx* c, const float* obs, const uint8_t* mask, 
     }
     for (int64_t off = 0; off < n; off += g.rows_max) {
         const int64_t rows = std::min<int64_t>(g.rows_max, n - off);
-        if (gen_fused_forward_ok(g) && (key_rows > 0 ? std::min<int64_t>(g.rows_max, key_rows) : rows) <= GEN_FUSED_MAX_ROWS) HIPCHK(c, gen_fused_forward(g, B_<float>(c, PPO_BUF_PARAMS), 1, obs + off * g.L.obs, nullptr, 0, rows, false, g.logits, c->stream));
+        if (env_generic_via_bf16(c)) {
+            const ppo_status s = gen_fused_rows_via_bf16(c, 1, obs + off * g.L.obs, rows, g.logits);
+            if (s != PPO_OK) return s;
+        } else if (gen_fused_forward_ok(g) && (key_rows > 0 ? std::min<int64_t>(g.rows_max, key_rows) : rows) <= GEN_FUSED_MAX_ROWS) HIPCHK(c, gen_fused_forward(g, B_<float>(c, PPO_BUF_PARAMS), 1, obs + off * g.L.obs, nullptr, 0, rows, false, g.logits, c->stream));
         else HIPCHK(c, gen_forward(g, B_<float>(c, PPO_BUF_PARAMS), 1, obs + off * g.L.obs, rows, nullptr, g.dz[0], g.dz[1], g.logits, c->stream));
         HIPCHK(c, gen_heads(g.L, c->cfg.dist_kind, g.logits, mask ? mask + off * g.L.act : nullptr, forced ? forced + off * g.L.n_heads : nullptr, rows,
                             c->cfg.seed, c->cfg.env_offset + row0 + off, step_index, action ? action + off * g.L.n_heads : nullptr,
@@ -1352,6 +1399,8 @@ static ppo_status host_env_refuses(ppo_ctx* c, const char* what) {
                                         "them with ppo_host_env_reset, ppo_host_rollout_begin, ppo_host_act, ppo_host_observe and ppo_host_rollout_end", what);
 }
 
+// what the refusals of the caller-stepped entry points add on a PPO_KERNEL_ENV_GENERIC context: the flag changes the network's engine, not whose env it is
+static inline const char* env_generic_note(const ppo_ctx* c) { return c->env_generic ? ", on the generic engine under PPO_KERNEL_ENV_GENERIC" : ""; }
 static inline bool is_pendulum(const ppo_ctx* c) { return c->cfg.env_kind == PPO_ENV_PENDULUM; }
 static inline bool is_mcc(const ppo_ctx* c) { return c->cfg.env_kind == PPO_ENV_MOUNTAINCAR_CONTINUOUS; }
 // the device envs with real-valued actions: the env of the fused Gaussian rollout (gauss_fused.hpp)
@@ -1381,7 +1430,7 @@ extern "C" ppo_status ppo_env_reset(ppo_ctx* c) {
                                         B_<int32_t>(c, PPO_BUF_RESET_COUNT), B_<float>(c, PPO_BUF_NEXT_OBS), B_<int32_t>(c, PPO_BUF_NEXT_DONE), c->stream));
         return PPO_OK;
     }
-    if (c->gen) {   // synthetic env: memoryless, the observation of global step `rollout_steps` (0 after creation)
+    if (c->gen && !c->env_generic) {   // synthetic env: memoryless, the observation of global step `rollout_steps` (0 after creation)
         HIPCHK(c, hipMemsetAsync(c->buf[PPO_BUF_EP_LEN], 0, (size_t)c->N * sizeof(int32_t), c->stream));
         HIPCHK(c, hipMemsetAsync(c->buf[PPO_BUF_EP_REW], 0, (size_t)c->N * sizeof(float), c->stream));
         HIPCHK(c, hipMemsetAsync(c->buf[PPO_BUF_NEXT_DONE], 0, (size_t)c->N * sizeof(int32_t), c->stream));
@@ -1405,7 +1454,7 @@ extern "C" ppo_status ppo_env_step(ppo_ctx* c, const int64_t* action, float* obs
                                      B_<float>(c, PPO_BUF_EP_REW), B_<int32_t>(c, PPO_BUF_RESET_COUNT), action, obs, reward, done, c->stream));
         return PPO_OK;
     }
-    if (c->gen) {   // synthetic env: one step at the context's global step counter (the action does not influence it)
+    if (c->gen && !c->env_generic) {   // synthetic env: one step at the context's global step counter (the action does not influence it)
         HIPCHK(c, gen_synthetic_step(c->gen->L, c->N, c->cfg.seed, c->cfg.env_offset, c->rollout_steps, c->cfg.max_episode_steps,
                                      B_<int32_t>(c, PPO_BUF_EP_LEN), B_<float>(c, PPO_BUF_EP_REW), obs, c->cur_mask, reward, done, nullptr, nullptr, c->stream));
         c->rollout_steps += 1;
@@ -1664,10 +1713,11 @@ extern "C" ppo_status ppo_rollout(ppo_ctx* c, const int64_t* forced_actions) {
     if (is_acrobot(c)) return cat_env_rollout(c, forced_actions);
     ppo_status s = consume_finished_episodes(c);
     if (s != PPO_OK) return s;
-    if (c->gen) return gen_rollout(c, forced_actions);
+    if (c->gen && !c->env_generic) return gen_rollout(c, forced_actions);
     // worst case one reset per env per step
     s = ensure_reset_table(c, c->rollout_steps + c->T + 4);
     if (s != PPO_OK) return s;
+    if (c->env_generic) return gen_rollout(c, forced_actions);   // PPO_KERNEL_ENV_GENERIC: the same reset table under the generic engine's rollout
     RolloutArgs a{};
     a.params = B_<float>(c, PPO_BUF_PARAMS);
     a.L = c->L;
@@ -1801,6 +1851,9 @@ extern "C" ppo_status ppo_evaluate(ppo_ctx* c, int64_t n_episodes, int64_t seed,
                                             "ppo_env_transition_f32");
     const bool gauss_env = is_mcc(c);   // the episodes run on the fused Gaussian kernels (gauss_eval_kernel); everything on the host side is shared
     const bool cat_env = is_acrobot(c);   // ... or on the fused categorical kernels (cat_eval_kernel)
+    if (c->env_generic)
+        return fail(c, PPO_ERR_UNSUPPORTED, "ppo_evaluate is not built for PPO_KERNEL_ENV_GENERIC contexts: its episode kernels hold the reference's 2 x 64 network; step "
+                                            "the episodes with ppo_policy_act_greedy + ppo_env_transition");
     if (c->host_env || (c->gen && !gauss_env && !cat_env) || c->cfg.env_kind == PPO_ENV_SYNTHETIC)
         return fail(c, PPO_ERR_UNSUPPORTED, "ppo_evaluate steps the context's device environment (CartPole, MountainCar); this context's environment is %s: "
                                             "run the episodes on the host with one ppo_policy_act_greedy launch per step",
@@ -2118,7 +2171,40 @@ static ppo_status gen_rollout(ppo_ctx* c, const int64_t* forced) {
     float* params = B_<float>(c, PPO_BUF_PARAMS);
     float* next_obs = B_<float>(c, PPO_BUF_NEXT_OBS);
     const uint8_t* mask = c->cfg.dist_kind == PPO_DIST_MASKED ? c->cur_mask : nullptr;
-    if (gen_fused_ok(g)) {
+    if (c->env_generic) {
+        // PPO_KERNEL_ENV_GENERIC: the same plan around CartPole / MountainCar.  The env's masks are all ones (cur_mask, filled once), and PPO_BUF_MASKS is held as
+        // the reference-shape rollout holds it: ones under PPO_DIST_MASKED, untouched otherwise
+        uint8_t* masks_t = mask ? B_<uint8_t>(c, PPO_BUF_MASKS) : nullptr;
+        ProfScope ps(c, PROF_ROLLOUT);
+        if (gen_fused_ok(g)) {   // bf16 storage: all T steps in ONE launch (generic_env_rollout_kernel)
+            GenEnvRolloutArgs r{};
+            r.env_kind = c->cfg.env_kind; r.dist_kind = c->cfg.dist_kind; r.N = N; r.T = c->T; r.max_episode_steps = c->cfg.max_episode_steps;
+            r.seed = c->cfg.seed; r.env_offset = c->cfg.env_offset; r.step_base = c->rollout_steps;
+            r.env_state = B_<float>(c, PPO_BUF_ENV_STATE); r.ep_len = B_<int32_t>(c, PPO_BUF_EP_LEN); r.ep_rew = B_<float>(c, PPO_BUF_EP_REW);
+            r.reset_count = B_<int32_t>(c, PPO_BUF_RESET_COUNT); r.reset_table = c->reset_table; r.reset_cap = c->reset_cap; r.error_flag = c->error_flag;
+            r.obs = B_<float>(c, PPO_BUF_OBS); r.masks = masks_t; r.actions = B_<int32_t>(c, PPO_BUF_ACTIONS); r.logprobs = B_<float>(c, PPO_BUF_LOGPROBS);
+            r.rewards = B_<float>(c, PPO_BUF_REWARDS); r.dones = B_<float>(c, PPO_BUF_DONES); r.fin_len = B_<int32_t>(c, PPO_BUF_FIN_LEN);
+            r.fin_rew = B_<float>(c, PPO_BUF_FIN_REW); r.next_obs = next_obs; r.next_done = B_<int32_t>(c, PPO_BUF_NEXT_DONE); r.forced = forced;
+            HIPCHK(c, gen_fused_env_rollout(g, params, r, c->stream));
+        } else {
+            for (int t = 0; t < c->T; t++) {   // per step: ppo_policy_act's launches (forward, heads), the stores, ppo_env_step's kernel on the context's buffers
+                const size_t tn = (size_t)t * N;
+                HIPCHK(c, gen_forward(g, params, 1, next_obs, N, nullptr, g.dz[0], g.dz[1], g.logits, c->stream));
+                HIPCHK(c, gen_heads(GL, c->cfg.dist_kind, g.logits, mask, forced ? forced + tn * GL.n_heads : nullptr, N, c->cfg.seed, c->cfg.env_offset,
+                                    c->rollout_steps + t, g.act64, g.step_lp, g.step_en, c->stream));
+                HIPCHK(c, gen_store_step(GL, N, next_obs, mask, g.act64, g.step_lp, B_<int32_t>(c, PPO_BUF_NEXT_DONE), B_<float>(c, PPO_BUF_OBS) + tn * GL.obs,
+                                         masks_t ? masks_t + tn * GL.act : nullptr, B_<int32_t>(c, PPO_BUF_ACTIONS) + tn * GL.n_heads, B_<float>(c, PPO_BUF_LOGPROBS) + tn,
+                                         B_<float>(c, PPO_BUF_DONES) + tn, c->stream));
+                HIPCHK(c, launch_env_step(c->cfg.env_kind, N, c->H, c->cfg.max_episode_steps, c->cfg.seed, c->cfg.env_offset, B_<float>(c, PPO_BUF_ENV_STATE),
+                                          B_<int32_t>(c, PPO_BUF_EP_LEN), B_<float>(c, PPO_BUF_EP_REW), B_<int32_t>(c, PPO_BUF_RESET_COUNT), c->reset_table, c->reset_cap,
+                                          g.act64, next_obs, B_<float>(c, PPO_BUF_REWARDS) + tn, B_<int32_t>(c, PPO_BUF_NEXT_DONE), c->error_flag, c->stream,
+                                          B_<int32_t>(c, PPO_BUF_FIN_LEN) + tn, B_<float>(c, PPO_BUF_FIN_REW) + tn));
+            }
+        }
+        ppo_status s = gen_values(c, B_<float>(c, PPO_BUF_OBS), (int64_t)c->T * N, B_<float>(c, PPO_BUF_VALUES));
+        if (s == PPO_OK) s = gen_values(c, next_obs, N, B_<float>(c, PPO_BUF_NEXT_VALUE));
+        if (s != PPO_OK) return s;
+    } else if (gen_fused_ok(g)) {
         // bf16 storage: the T steps { observation, actor, heads, stores, env transition } in ONE launch, then the critic over all stored observations
         ProfScope ps(c, PROF_ROLLOUT);
         HIPCHK(c, gen_fused_rollout(g, params, c->cfg.dist_kind, N, c->T, c->cfg.max_episode_steps, c->cfg.seed, c->cfg.env_offset, c->rollout_steps,
@@ -2557,8 +2643,8 @@ extern "C" ppo_status ppo_train_iteration(ppo_ctx* c) {
 // ---------------------------------------------------------------------------------------------------------
 static ppo_status host_state(ppo_ctx* c, const char* what) {
     if (!c->host_env)
-        return fail(c, PPO_ERR_STATE, "%s: this context steps its own device environment (env_kind %d); the ppo_host_* calls serve PPO_ENV_HOST contexts", what,
-                    c->cfg.env_kind);
+        return fail(c, PPO_ERR_STATE, "%s: this context steps its own device environment (env_kind %d%s); the ppo_host_* calls serve PPO_ENV_HOST contexts", what,
+                    c->cfg.env_kind, env_generic_note(c));
     return PPO_OK;
 }
 
@@ -3178,6 +3264,9 @@ static ppo_status envt_state(ppo_ctx* c, const char* what) {
         return fail(c, PPO_ERR_UNSUPPORTED, "%s: the fold rebuilds the final observation of a cut-off episode from PPO_BUF_OBS, and a PPO_ENV_ACROBOT observation "
                                             "(cos, sin of two angles, two velocities) does not hold the angles: not built for this env", what);
     if (is_mcc(c)) return PPO_OK;   // its observation is its state: the fold runs on the fused Gaussian critic (gauss_env_fold_truncations)
+    if (c->env_generic)
+        return fail(c, PPO_ERR_UNSUPPORTED, "%s: the fold of CartPole / MountainCar is built on the reference-shape critic (2 x 64), and this context's network lives "
+                                            "on the generic engine (PPO_KERNEL_ENV_GENERIC): not built for it", what);
     if (c->cfg.env_kind != PPO_ENV_CARTPOLE && c->cfg.env_kind != PPO_ENV_MOUNTAINCAR)
         return fail(c, PPO_ERR_UNSUPPORTED, "%s: the synthetic env's observations are noise: an episode there has no last observation to bootstrap from", what);
     return PPO_OK;
@@ -3419,8 +3508,8 @@ extern "C" ppo_status ppo_dev_observe(ppo_ctx* c, const float* next_obs, const f
 // ---------------------------------------------------------------------------------------------------------
 static ppo_status on_state(ppo_ctx* c, const char* what, bool outside_rollout) {
     if (!c->host_env)
-        return fail(c, PPO_ERR_UNSUPPORTED, "%s: this context steps its own device environment (env_kind %d), whose observations are of unit scale and never leave "
-                                            "the fused rollout; observation normalisation serves PPO_ENV_HOST contexts", what, c->cfg.env_kind);
+        return fail(c, PPO_ERR_UNSUPPORTED, "%s: this context steps its own device environment (env_kind %d%s), whose observations are of unit scale and never leave "
+                                            "the fused rollout; observation normalisation serves PPO_ENV_HOST contexts", what, c->cfg.env_kind, env_generic_note(c));
     if (outside_rollout && c->host_phase != 0) return fail(c, PPO_ERR_STATE, "%s: a rollout is open (ppo_host_rollout_end first)", what);
     return PPO_OK;
 }
@@ -3504,8 +3593,8 @@ extern "C" ppo_status ppo_obs_norm_apply(ppo_ctx* c, const float* obs, int64_t n
 // ---------------------------------------------------------------------------------------------------------
 static ppo_status rn_state(ppo_ctx* c, const char* what) {
     if (!c->host_env)
-        return fail(c, PPO_ERR_UNSUPPORTED, "%s: this context steps its own device environment (env_kind %d), whose rewards are of unit scale and never leave "
-                                            "the fused rollout; reward normalisation serves PPO_ENV_HOST contexts", what, c->cfg.env_kind);
+        return fail(c, PPO_ERR_UNSUPPORTED, "%s: this context steps its own device environment (env_kind %d%s), whose rewards are of unit scale and never leave "
+                                            "the fused rollout; reward normalisation serves PPO_ENV_HOST contexts", what, c->cfg.env_kind, env_generic_note(c));
     if (c->host_phase != 0) return fail(c, PPO_ERR_STATE, "%s: a rollout is open (ppo_host_rollout_end first)", what);
     return PPO_OK;
 }

@@ -159,6 +159,17 @@ hipError_t gen_fused_rollout(const GenericCtx& g, const float* params, int dist_
                              int64_t step_base, int32_t* ep_len, float* ep_rew, float* obs, uint8_t* masks, int32_t* actions, float* logprobs, float* rewards,
                              float* dones, int32_t* fin_len, float* fin_rew, float* next_obs, int32_t* next_done, uint8_t* cur_mask, const int64_t* forced,
                              hipStream_t s);
+// PPO_KERNEL_ENV_GENERIC: the T-step rollout of a bf16-storage network around CartPole / MountainCar in one launch (generic_env_rollout_kernel; needs
+// gen_fused_ok).  env_state is env_step_kernel's struct of arrays [obs][N]; masks may be null (PPO_DIST_MASKED: filled with ones); forced [T, N, H] or null
+struct GenEnvRolloutArgs {
+    int env_kind, dist_kind, N, T, max_episode_steps;
+    int64_t seed, env_offset, step_base;
+    float* env_state; int32_t* ep_len; float* ep_rew; int32_t* reset_count; const float* reset_table; int reset_cap; int32_t* error_flag;
+    float* obs; uint8_t* masks; int32_t* actions; float* logprobs; float* rewards; float* dones; int32_t* fin_len; float* fin_rew;
+    float* next_obs; int32_t* next_done;
+    const int64_t* forced;
+};
+hipError_t gen_fused_env_rollout(const GenericCtx& g, const float* params, const GenEnvRolloutArgs& r, hipStream_t s);
 
 // kernels_generic_bwd.hip: a layer's weight gradient and the gradient handed to the layer below in ONE launch (bf16 storage, widths padded to 128 / 256)
 bool gen_fused_backward_ok(const GenericCtx& g);

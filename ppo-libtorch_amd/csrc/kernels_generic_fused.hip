@@ -367,6 +367,129 @@ __global__ __launch_bounds__(FU_THREADS, 1) void generic_rollout_kernel(const Fu
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------------
+// PPO_KERNEL_ENV_GENERIC: the same T-step rollout around CartPole / MountainCar (PPO_Discrete.cpp:524-548 with the env of ppo_internal.hpp: env_step<ENV>,
+// env_reset<ENV>, and env_step_kernel's bookkeeping -- episode sums, the time limit, the finished episode's numbers, auto-reset from the shared table).
+// generic_rollout_kernel's plan: 32 envs per workgroup, fused_layers<1> for the actor, the heads sampled by lanes 0 .. 31 of wave 0.  Those lanes also keep
+// their env -- state (the observation IS the state), episode length and return, reset count, previous done flag -- in registers for the whole rollout, step
+// it and write the next observation themselves: f32 to OBS[t + 1] (NEXT_OBS after the last step), bf16 into their row of the layer-0 tile.  Here the next
+// observation depends on the action, so nothing of step t + 1 can be formed while wave 0 samples: a step is forward -> sample + env step -> barrier, and
+// waves 1 .. 7 only clear what the hidden layers left behind the observation's columns.  Every thread runs every barrier; a short tile masks its stores.
+// ---------------------------------------------------------------------------------------------------------------------------------------
+struct FusedEnvRolloutArgs { FusedNet f; GenEnvRolloutArgs r; };
+
+template <int DIST, int ENV>
+__global__ __launch_bounds__(FU_THREADS, 1) void generic_env_rollout_kernel(const FusedEnvRolloutArgs a) {
+    constexpr int OBS = ENV == PPO_ENV_CARTPOLE ? 4 : 2;
+    extern __shared__ __attribute__((aligned(16))) uint16_t fu_lds[];
+    const GenLayout& L = a.f.L;
+    const GenEnvRolloutArgs& r = a.r;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    uint16_t* tile0 = fu_lds;
+    uint16_t* tile1 = fu_lds + 32 * a.f.ldA;
+    float* s_out = reinterpret_cast<float*>(fu_lds + 2 * 32 * a.f.ldA);      // [32][32]
+    const int e0 = blockIdx.x * 32;
+    const int N = r.N, A = L.act, H = L.n_heads;
+    BFrags pre;
+    load_bfrags(pre, a.f, 0, wave, 0, lane);   // layer 0's first weight fragments travel while the env state is loaded
+    const bool env_lane = tid < 32 && e0 + tid < N;
+    const int env = e0 + tid;
+    const int64_t env_g = r.env_offset + env;
+    float st[OBS];
+#pragma unroll
+    for (int k = 0; k < OBS; k++) st[k] = 0.0f;   // (a lane without an env keeps zeros: its row of the tile stays finite)
+    int len = 0, resets = 0, prev_done = 0;
+    float rew = 0.0f;
+    if (env_lane) {
+#pragma unroll
+        for (int k = 0; k < OBS; k++) st[k] = r.env_state[(size_t)k * N + env];   // struct of arrays (env_step_kernel)
+        len = r.ep_len[env]; rew = r.ep_rew[env]; resets = r.reset_count[env]; prev_done = r.next_done[env];
+    }
+    // the lane's observation: f32 to dst [N, OBS], bf16 into its row of tile0 (columns 0 .. OBS - 1; the k padding behind them is zero)
+    auto put_obs = [&](float* dst) {
+        if (tid >= 32) return;
+        if (env_lane) {
+            if constexpr (OBS == 4) *reinterpret_cast<float4*>(dst + (size_t)env * 4) = make_float4(st[0], st[1], st[2], st[3]);
+            else *reinterpret_cast<float2*>(dst + (size_t)env * 2) = make_float2(st[0], st[1]);
+        }
+        uint32_t* trow = reinterpret_cast<uint32_t*>(tile0 + tid * a.f.ldA);
+#pragma unroll
+        for (int k = 0; k < OBS; k += 2) trow[k / 2] = fu_pack(st[k], st[k + 1]);
+    };
+    for (int e = tid; e < 2 * 32 * a.f.ldA / 8; e += FU_THREADS) { const u32x4 z = { 0u, 0u, 0u, 0u }; reinterpret_cast<u32x4*>(fu_lds)[e] = z; }   // finite everywhere
+    __syncthreads();
+    put_obs(r.obs);   // m_obs[0] = next_obs (:529)
+    __syncthreads();
+    // what a hidden layer's output (written to tile0 two layers ago) left behind the observation: layer 0 reads it against zero weights (generic_forward_kernel)
+    const int zw = ((L.hidden + 31) / 32 * 32 - OBS) / 2;   // 4-byte words per row: columns OBS .. the hidden width padded to a column block
+    for (int t = 0; t < r.T; t++) {
+        const int64_t step = r.step_base + t;
+        const size_t tn = (size_t)t * N;
+        fused_layers<1>(a.f, a.f.wp_off[0], tile0, tile1, s_out, nullptr, 0, 0, 32, pre);   // ends with a barrier: logits in s_out, tile0 free again
+        if (wave != 0) {
+            for (int e = tid - 64; e < 32 * zw; e += FU_THREADS - 64) reinterpret_cast<uint32_t*>(tile0 + (e / zw) * a.f.ldA + OBS)[e % zw] = 0u;
+            if (DIST == PPO_DIST_MASKED && r.masks)   // m_action_masks[step] = all ones (PPO_MultiDiscrete.cpp:555), off wave 0's chain
+                for (int e = tid - 64; e < 32 * A; e += FU_THREADS - 64) if (e0 + e / A < N) r.masks[(tn + e0 + e / A) * A + e % A] = 1;
+        } else {
+            if (env_lane) {
+                // per-head (masked) categorical on the row's logits, sample or forced action, summed log-prob (Agent.cpp:137-170; heads_kernel).  The env's
+                // masks are all ones (MountainCar.cpp:69-77), under which the masked head is the unmasked one
+                float lp_sum = 0.0f;
+                int off = 0, act0 = 0;
+                for (int h = 0; h < H; h++) {
+                    const int Ah = L.head_dims[h];
+                    float z[PPO_MAX_ACT], p[PPO_MAX_ACT];
+                    for (int k = 0; k < Ah; k++) z[k] = s_out[tid * 32 + off + k];
+                    categorical_head_fast<DIST>(z, p, nullptr, Ah);
+                    int act;
+                    if (r.forced) {
+                        act = (int)r.forced[(tn + env) * H + h];
+                    } else {
+                        const uint4 w = philox4x32_10((uint32_t)r.seed, (uint32_t)((uint64_t)r.seed >> 32), (uint32_t)env_g, (uint32_t)(step >> 2), (uint32_t)h, 0u);
+                        const uint32_t ws = (step & 3) == 0 ? w.x : ((step & 3) == 1 ? w.y : ((step & 3) == 2 ? w.z : w.w));
+                        act = sample_head(p, Ah, (float)(ws >> 8) * 0x1p-24f);
+                    }
+                    r.actions[(tn + env) * H + h] = act;
+                    if (h == 0) act0 = act;
+                    float lp = 0.0f;
+                    for (int k = 0; k < Ah; k++) if (k == act) lp = z[k];
+                    lp_sum = h == 0 ? lp : lp_sum + lp;
+                    off += Ah;
+                }
+                r.logprobs[tn + env] = lp_sum;
+                r.dones[tn + env] = (float)prev_done;                       // m_dones[step] = next_done (:530)
+                // env step + truncation + auto-reset (PPO_Discrete.cpp:440-458; env_step_kernel, bit for bit): head 0's action steps the env
+                int term;
+                const float reward = env_step<ENV>(st, act0, term);
+                len += 1;
+                rew += reward;
+                if (len == r.max_episode_steps) term = 1;
+                int fl = 0;
+                float fr = 0.0f;
+                if (term) {
+                    fl = len; fr = rew;
+                    int k = resets++;
+                    if (ENV == PPO_ENV_CARTPOLE && k >= r.reset_cap) { k = r.reset_cap - 1; atomicOr(r.error_flag, 1); }
+                    env_reset<ENV>(st, r.reset_table, k, r.seed, env_g);
+                    len = 0; rew = 0.0f;
+                }
+                r.rewards[tn + env] = reward;
+                r.fin_len[tn + env] = fl;
+                r.fin_rew[tn + env] = fr;
+                prev_done = term;
+            }
+            // the observation the agent sees next: row t + 1 of the buffer, or NEXT_OBS after the last step
+            put_obs(t + 1 < r.T ? r.obs + (tn + N) * OBS : r.next_obs);
+        }
+        __syncthreads();   // tile0 holds the next observation; s_out is free
+    }
+    if (env_lane) {
+#pragma unroll
+        for (int k = 0; k < OBS; k++) r.env_state[(size_t)k * N + env] = st[k];
+        r.ep_len[env] = len; r.ep_rew[env] = rew; r.reset_count[env] = resets; r.next_done[env] = prev_done;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
 // Heads + PPO loss + the HEAD LAYER'S BACKWARD inside the forward kernel (round 6; PPO_MultiDiscrete.cpp:593-668 on a 64-row tile).  When a pass of a tile
 // ends, the tile's logits (or values) sit in s_out and the top hidden activation h sits in an LDS tile -- everything the loss and the head layer's backward
 // need.  Instead of writing logits and h to HBM, reading them back in loss_lanes_kernel (heads, masked categorical, loss, d logits) and again in
@@ -984,4 +1107,24 @@ hipError_t gen_fused_rollout(const GenericCtx& g, const float* params, int dist_
     if (dist_kind == PPO_DIST_MASKED) hipLaunchKernelGGL(generic_rollout_kernel<PPO_DIST_MASKED>, grid, block, lds, s, a);
     else hipLaunchKernelGGL(generic_rollout_kernel<PPO_DIST_CATEGORICAL>, grid, block, lds, s, a);
     return hipGetLastError();
+}
+
+template <int DIST, int ENV>
+static hipError_t fused_env_rollout_launch(const FusedEnvRolloutArgs& a, hipStream_t s) {
+    static std::atomic<unsigned long long> lds_ok{0};
+    const hipError_t e = allow_dynamic_lds(lds_ok, reinterpret_cast<const void*>(&generic_env_rollout_kernel<DIST, ENV>));
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((generic_env_rollout_kernel<DIST, ENV>), dim3((unsigned)((a.r.N + 31) / 32)), dim3(FU_THREADS), fused_lds_bytes(a.f, 32), s, a);
+    return hipGetLastError();
+}
+hipError_t gen_fused_env_rollout(const GenericCtx& g, const float* params, const GenEnvRolloutArgs& r, hipStream_t s) {
+    const bool cartpole = r.env_kind == PPO_ENV_CARTPOLE;
+    if (!gen_fused_ok(g) || (!cartpole && r.env_kind != PPO_ENV_MOUNTAINCAR) || g.L.obs != (cartpole ? 4 : 2) || r.N < 1) return hipErrorInvalidValue;
+    if (g.planes_dirty) { const hipError_t pe = gen_weight_planes(g, params, s); if (pe != hipSuccess) return pe; g.planes_dirty = false; }
+    FusedEnvRolloutArgs a{};
+    a.f = make_fused_net(g, params, 1);
+    a.r = r;
+    if (r.dist_kind == PPO_DIST_MASKED)
+        return cartpole ? fused_env_rollout_launch<PPO_DIST_MASKED, PPO_ENV_CARTPOLE>(a, s) : fused_env_rollout_launch<PPO_DIST_MASKED, PPO_ENV_MOUNTAINCAR>(a, s);
+    return cartpole ? fused_env_rollout_launch<PPO_DIST_CATEGORICAL, PPO_ENV_CARTPOLE>(a, s) : fused_env_rollout_launch<PPO_DIST_CATEGORICAL, PPO_ENV_MOUNTAINCAR>(a, s);
 }

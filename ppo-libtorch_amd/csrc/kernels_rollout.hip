@@ -1277,7 +1277,8 @@ __global__ void env_reset_kernel(int N, int64_t seed, int64_t env_offset, float*
 template <int ENV, int OBS>
 __global__ void env_step_kernel(int N, int H, int max_episode_steps, int64_t seed, int64_t env_offset, float* env_state,
                                 int32_t* ep_len, float* ep_rew, int32_t* reset_count, const float* reset_table, int reset_cap,
-                                const int64_t* __restrict__ action, float* obs, float* reward, int32_t* done, int32_t* error_flag) {
+                                const int64_t* __restrict__ action, float* obs, float* reward, int32_t* done, int32_t* error_flag,
+                                int32_t* fin_len, float* fin_rew) {   // fin_len / fin_rew (may be null): the finished episode's numbers, 0 where none ended
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N) return;
     float st[OBS];
@@ -1288,6 +1289,7 @@ __global__ void env_step_kernel(int N, int H, int max_episode_steps, int64_t see
     int len = ep_len[i] + 1;
     float rew = ep_rew[i] + r;
     if (len == max_episode_steps) term = 1;
+    if (fin_len) { fin_len[i] = term ? len : 0; fin_rew[i] = term ? rew : 0.0f; }
     if (term) {
         int k = reset_count[i];
         reset_count[i] = k + 1;
@@ -1528,14 +1530,15 @@ hipError_t launch_env_reset(int env_kind, int N, int64_t seed, int64_t env_offse
 
 hipError_t launch_env_step(int env_kind, int N, int H, int max_episode_steps, int64_t seed, int64_t env_offset, float* env_state,
                            int32_t* ep_len, float* ep_rew, int32_t* reset_count, const float* reset_table, int reset_cap,
-                           const int64_t* action, float* obs, float* reward, int32_t* done, int32_t* error_flag, hipStream_t s) {
+                           const int64_t* action, float* obs, float* reward, int32_t* done, int32_t* error_flag, hipStream_t s, int32_t* fin_len,
+                           float* fin_rew) {
     const dim3 block(256), grid((N + 255) / 256);
     if (env_kind == PPO_ENV_CARTPOLE)
         hipLaunchKernelGGL((env_step_kernel<PPO_ENV_CARTPOLE, 4>), grid, block, 0, s, N, H, max_episode_steps, seed, env_offset, env_state,
-                           ep_len, ep_rew, reset_count, reset_table, reset_cap, action, obs, reward, done, error_flag);
+                           ep_len, ep_rew, reset_count, reset_table, reset_cap, action, obs, reward, done, error_flag, fin_len, fin_rew);
     else
         hipLaunchKernelGGL((env_step_kernel<PPO_ENV_MOUNTAINCAR, 2>), grid, block, 0, s, N, H, max_episode_steps, seed, env_offset, env_state,
-                           ep_len, ep_rew, reset_count, reset_table, reset_cap, action, obs, reward, done, error_flag);
+                           ep_len, ep_rew, reset_count, reset_table, reset_cap, action, obs, reward, done, error_flag, fin_len, fin_rew);
     return hipGetLastError();
 }
 

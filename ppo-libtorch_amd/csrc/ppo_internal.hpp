@@ -815,7 +815,8 @@ hipError_t launch_env_reset(int env_kind, int N, int64_t seed, int64_t env_offse
                             int32_t* error_flag, hipStream_t s);
 hipError_t launch_env_step(int env_kind, int N, int H, int max_episode_steps, int64_t seed, int64_t env_offset, float* env_state,
                            int32_t* ep_len, float* ep_rew, int32_t* reset_count, const float* reset_table, int reset_cap,
-                           const int64_t* action, float* obs, float* reward, int32_t* done, int32_t* error_flag, hipStream_t s);
+                           const int64_t* action, float* obs, float* reward, int32_t* done, int32_t* error_flag, hipStream_t s,
+                           int32_t* fin_len = nullptr, float* fin_rew = nullptr);   // fin_*: the finished episodes' numbers of this step (a rollout's FIN_LEN / FIN_REW row)
 hipError_t launch_env_transition(int env_kind, const float* state_in, const int64_t* action, int64_t n, float* next_state,
                                  float* reward, int32_t* terminated, hipStream_t s);
 hipError_t launch_aos_to_soa(const float* aos, float* soa, int N, int O, bool to_soa, hipStream_t s);

@@ -78,6 +78,10 @@ void PPOAlgorithm::getArgs() {
         B("environment", "norm_reward", m_norm_reward);                   // extension key (PPO_HostEnv), likewise
         B("environment", "fused_policy", m_fused_policy);                 // extension key (PPO_HostEnvBox), likewise
         B("environment", "fused_categorical", m_fused_categorical);       // extension key (PPO_HostEnv), likewise
+        if (m_env_kind == PPO_ENV_CARTPOLE || m_env_kind == PPO_ENV_MOUNTAINCAR) {   // extension key (PPO_Discrete, PPO_MultiDiscrete), likewise
+            I("network", "hidden_size", m_hidden_size);
+            m_hidden_size_given = cfg.integer("network", "hidden_size").has_value();
+        }
         I("general", "seed", m_seed);
         I("general", "total_timesteps", m_total_timesteps);
         B("general", "use_cuda", m_use_cuda);
@@ -134,7 +138,7 @@ void PPOAlgorithm::construct() {
     c.obs_size = static_cast<int32_t>(m_obs_size);
     c.n_heads = 1;
     c.head_dims[0] = static_cast<int32_t>(m_action_size);      // m_actionSpace = { actionSize }, Agent.cpp:21
-    c.hidden = 64; c.n_hidden = 2;
+    c.hidden = static_cast<int32_t>(m_hidden_size); c.n_hidden = 2;   // 64 unless [network] hidden_size says otherwise
     c.num_envs = static_cast<int32_t>(m_num_envs);
     c.num_steps = static_cast<int32_t>(m_num_steps);
     c.num_minibatches = static_cast<int32_t>(m_num_minibatches);
@@ -150,6 +154,7 @@ void PPOAlgorithm::construct() {
     c.ent_coef = m_ent_coef; c.vf_coef = m_vf_coef; c.max_grad_norm = m_max_grad_norm;
     c.kernel_flags = m_fused_policy ? PPO_KERNEL_GAUSS_FUSED : 0;   // a class whose policy is not Gaussian: the library's refusal is thrown below, with its message
     if (m_fused_categorical) c.kernel_flags |= PPO_KERNEL_CAT_FUSED;   // likewise for a class whose context is not a caller-stepped categorical one
+    if (m_hidden_size_given) c.kernel_flags |= PPO_KERNEL_ENV_GENERIC;   // CartPole / MountainCar on the generic engine, also at hidden_size = 64; a width out of range is the library's refusal
     ppo::check(ppo_ctx_create(&c, &m_ctx), nullptr, "PPO");    // obs-size mismatch surfaces here with the reference's message (:370-375)
     ppo::check(ppo_params_init_orthogonal(m_ctx, m_seed), m_ctx, "agent init");
     m_agent = std::make_shared<Agent>(m_ctx, m_device, std::vector<int64_t>{ m_action_size });
@@ -361,8 +366,8 @@ void PPOAlgorithm::saveCheckpoint(const std::string& agentFile, const std::strin
             f.write(RewardNormFile::pathFor(agentFile));
         }
         const bool log_std = m_dist_kind == PPO_DIST_GAUSSIAN;   // a Gaussian policy's thirteenth tensor
-        ppo::pt::writeAgent(ta, m_obs_size, 64, m_action_size, p, fs::path(agentFile).stem().string(), log_std);
-        ppo::pt::writeOptimizer(to, m_obs_size, 64, m_action_size, m, v, step, st.learning_rate, static_cast<double>(1e-5f), 0.01,
+        ppo::pt::writeAgent(ta, m_obs_size, m_hidden_size, m_action_size, p, fs::path(agentFile).stem().string(), log_std);
+        ppo::pt::writeOptimizer(to, m_obs_size, m_hidden_size, m_action_size, m, v, step, st.learning_rate, static_cast<double>(1e-5f), 0.01,
                                      fs::path(optimizerFile).stem().string(), log_std);
     } catch (const std::exception&) {
         std::error_code ec;
@@ -472,7 +477,7 @@ void PPOAlgorithm::loadPolicyFromCheckpoint() {
         return;
     }
     const int64_t P = ppo_param_count(m_ctx);
-    const auto shapes = ppo::pt::agentShapes(m_obs_size, 64, m_action_size, m_dist_kind == PPO_DIST_GAUSSIAN);
+    const auto shapes = ppo::pt::agentShapes(m_obs_size, m_hidden_size, m_action_size, m_dist_kind == PPO_DIST_GAUSSIAN);
     const std::string a = newestFile(modelDir);
     if (a.empty()) {
         std::cout << "No previous model checkpoint found at " << modelDir << ", initializing new agent!" << std::endl;

@@ -107,6 +107,11 @@ class PPOAlgorithm {
     bool m_fused_policy = false;         // extension ([environment] fused_policy): PPO_HostEnvBox's context runs the fused Gaussian 2 x 64 kernels (PPO_KERNEL_GAUSS_FUSED); on any other class the library refuses the context
     bool m_norm_reward = false;          // extension ([environment] norm_reward): PPO_HostEnv divides rewards by the running std of the discounted return (ppo_reward_norm_*)
     bool m_bootstrap_truncated = false;  // extension ([environment] bootstrap_truncated): bootstrap the value where a time limit cut an episode off (every algorithm class; set it with setBootstrapTruncated)
+    // extension ([network] hidden_size = H; PPO_Discrete and PPO_MultiDiscrete only): the two hidden layers are H wide and the context runs on the generic engine
+    // (PPO_KERNEL_ENV_GENERIC).  Absent: 64, no flag, the reference-shape kernels, nothing printed.  Depth other than 2 and bf16 storage stay with the C-ABI and
+    // the Python binding: the reference's archive has names for two hidden layers only (TorchArchive.h), so a checkpoint of another depth could not be written
+    int64_t m_hidden_size = 64;
+    bool m_hidden_size_given = false;
     float m_target_kl = 0.0f;            // extension ([ppo] target_kl): stop an update's optimizer steps once an epoch's last approx_kl exceeds it (ppo_target_kl_set); absent or 0: off
 
     int64_t m_batch_size;

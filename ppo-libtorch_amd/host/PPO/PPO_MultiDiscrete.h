@@ -1,4 +1,7 @@
 // Drop-in for the reference's PPO/PPO_MultiDiscrete.h: masked (multi-)categorical heads on MountainCar envs.
+// One extension key, `[network] hidden_size = H`, as in PPO_Discrete.h: two hidden layers of H on the generic engine (PPO_KERNEL_ENV_GENERIC); absent: 64 and
+// today's kernels.  Depth other than 2 and bf16 storage stay with the C-ABI and the Python binding (the reference's archive names two hidden layers only).
+// With the key present evaluate() and `bootstrap_truncated = true` / setBootstrapTruncated(true) throw the library's refusal, as in PPO_Discrete.h.
 #pragma once
 #include "PPOAlgorithm.h"
 #include "../Environments/MountainCar.h"
