@@ -140,6 +140,53 @@ enum { PPO_OK = 0, PPO_ERR_INVALID = 1, PPO_ERR_HIP = 2, PPO_ERR_STATE = 3, PPO_
  * and an Acrobot observation does not hold the angles).  Sharding (ppo_comm_init*) is neither claimed nor tested for this env. */
 enum { PPO_ENV_CARTPOLE = 0, PPO_ENV_MOUNTAINCAR = 1, PPO_ENV_SYNTHETIC = 2, PPO_ENV_HOST = 3, PPO_ENV_PENDULUM = 4, PPO_ENV_MOUNTAINCAR_CONTINUOUS = 5 };
 enum { PPO_ENV_ACROBOT = PPO_ENV_MOUNTAINCAR_CONTINUOUS + 1 };   /* 6: the next env_kind, in an enum of its own -- the list above is kept as it was published */
+/* PPO_ENV_TAXI (new; value 8): gymnasium's Taxi-v3 on the device (no rain, no fickle passenger), the first device env whose action mask means something:
+ * the env of PPO_DIST_MASKED on the fused 2 x 64 family.  Every quantity is a small integer, held exactly in f32; nothing below rounds.
+ * State (row, col, pass, dest): row, col in 0..4; pass in 0..4 (0..3: the passenger waits at stand R, G, Y, B; 4: in the taxi); dest in 0..3.
+ * PPO_BUF_ENV_STATE is f32 [4, N]; ppo_env_set_state_h / ppo_env_get_state_h take [N, 4].
+ * Stands, as (row, col): R = (0,0), G = (0,4), Y = (4,0), B = (4,3).
+ * Walls: a move east from (r, c) is blocked when c == 4, or r in {0,1} and c == 1, or r in {3,4} and c in {0,2}; a move west from (r, c) is blocked when
+ * c == 0 or east from (r, c-1) is blocked.
+ * Step under action a, starting from reward -1 and terminated 0:
+ *   0 south:   row = min(row+1, 4)
+ *   1 north:   row = max(row-1, 0)
+ *   2 east / 3 west: move one column unless blocked
+ *   4 pickup:  if pass < 4 and the taxi stands on stand `pass`: pass = 4; else reward -10
+ *   5 dropoff: if pass == 4 and the taxi stands on stand `dest`: pass = dest, terminated 1, reward +20;
+ *              else if pass == 4 and the taxi stands on any stand s: pass = s; else reward -10
+ * Any action in 0..5 is legal for the env, masked or not; an action outside 0..5 is clamped into 0..5.
+ * Mask (u8, 6 wide): [row < 4, row > 0, !east_blocked, !west_blocked, pass < 4 && on stand pass, pass == 4 && on a stand] -- an action is allowed exactly
+ * when it changes the state (all 500 x 6 pairs: tests/test_taxi_cpu.py).  A mask is never empty (south or north is always allowed).  Allowed bits per
+ * action over the 500 states: 400, 400, 280, 280, 16, 16.
+ * Observation, obs_size 19: four one-hot groups of 0.0f / 1.0f -- row in [0..4], col in [5..9], pass in [10..14], dest in [15..18].  It is not the state,
+ * but the state is recoverable from it: the index of the largest entry of each group, the first index on ties.
+ * Reset number k of global env e: w = philox4x32_10(seed; e, k, 0, 1) (MountainCar's keying); cell = (uint64(w.x) * 25) >> 32, row = cell / 5,
+ * col = cell % 5; pass = (uint64(w.y) * 4) >> 32; d = (uint64(w.z) * 3) >> 32, dest = d + (d >= pass): uniform over gymnasium's 300 start states (passenger
+ * waiting, not at the destination).  Global env 0 takes reset 1 at ppo_env_reset; PPO_BUF_RESET_COUNT counts them.
+ * An episode ends where the env terminates or its length reaches max_episode_steps (any value >= 1; gym: 200): done = 1, FIN_LEN / FIN_REW written,
+ * auto-reset -- ppo_env_step's bookkeeping.  Returns are integer sums, exact in f32.
+ * Memory safety: ppo_env_set_state_h checks the host array -- a component that is not an integer of its range returns PPO_ERR_INVALID and changes nothing;
+ * the device functions convert and clamp each component into its range (ppo_env_transition on device arrays cannot be checked without a host wait).
+ * ppo_ctx_create accepts the env in exactly these forms: dist_kind = PPO_DIST_MASKED or PPO_DIST_CATEGORICAL, n_heads = 1, head_dims[0] = 6, obs_size = 19,
+ * hidden = 64, n_hidden = 2, PPO_DTYPE_F32, kernel_flags containing PPO_KERNEL_CAT_FUSED (required, never implied) and max_episode_steps >= 1.  A wrong
+ * obs_size returns PPO_ERR_INVALID with the reference's obs-size message, anything else PPO_ERR_UNSUPPORTED with a message that names the limit.  The context
+ * lives in the generic engine's layout, as a PPO_ENV_ACROBOT context does.
+ * Calls: PPO_ENV_ACROBOT's list -- ppo_env_reset, ppo_env_set_state_h (refills NEXT_OBS) / ppo_env_get_state_h, ppo_env_step (action i64 [N, 1], obs
+ * [N, 19]), ppo_env_transition(8, state [n, 4], action i64 [n], ...), ppo_rollout (forced i64 [T, N, 1] or NULL), ppo_calc_advantage, ppo_update,
+ * ppo_train_iteration, ppo_policy_act / ppo_policy_act_greedy (the caller passes the mask, as on any masked context), ppo_get_value, ppo_target_kl_set,
+ * ppo_evaluate, the statistics and profile calls, ppo_gauss_fused_launches -- plus ppo_env_truncation_bootstrap and ppo_env_truncations.
+ * PPO_BUF_MASKS (u8 [T, N, 6]): under PPO_DIST_MASKED the env's mask of the state each action was drawn in, formed on the chip (ppo_update reads it); under
+ * PPO_DIST_CATEGORICAL ones (Acrobot's rule) and the policy is unmasked -- the A/B partner that shows what the mask is worth.
+ * ppo_rollout is THREE launches, as on Acrobot (cat_rollout_kernel, LDS 67 136 bytes; `value` moves by 2, `act` by 0); a stepwise loop of
+ * ppo_policy_act(obs, mask, step_index = rollout_steps + t) and ppo_env_step reproduces every buffer it fills bit for bit, PPO_BUF_MASKS included
+ * (tests/test_gpu_taxi.py).  With ppo_env_truncation_bootstrap on, ONE more launch follows the two critic launches (cat_trunc_fold_kernel: the state of a
+ * cut-off episode's last step is decoded from PPO_BUF_OBS, stepped again under the stored action, and the critic's value of the final observation is folded
+ * into the reward); it is none of the launches ppo_gauss_fused_launches counts.  ppo_evaluate is ONE launch (cat_eval_kernel; under PPO_DIST_MASKED greedy is
+ * the first-index argmax of the masked probabilities) and moves no counter.
+ * Refused, changing nothing, with Acrobot's statuses: ppo_host_* / ppo_dev_* (PPO_ERR_STATE); ppo_obs_norm_* and ppo_reward_norm_* (PPO_ERR_UNSUPPORTED);
+ * ppo_env_step_f32, ppo_rollout_f32, ppo_policy_act_f32 (PPO_ERR_UNSUPPORTED, naming the integer twin).  Sharding is neither claimed nor tested. */
+enum { PPO_ENV_TAXI = PPO_ENV_ACROBOT + 2 };   /* 8, not 7: value 7 stays unassigned and keeps answering "unknown env_kind 7", as 9 does -- existing tests
+                                                * hold both; in an enum of its own and written as a sum, as PPO_ENV_ACROBOT is: the first list's text is pinned */
 /* PPO_DIST_CATEGORICAL reproduces Distributions/Categorical.cpp including its entropy clamp (:112-119);
  * PPO_DIST_MASKED reproduces Distributions/CategoricalMasked.cpp (true entropy, -1e8 masking).
  * PPO_DIST_GAUSSIAN (new; the reference has no continuous policy): a diagonal Gaussian over D = head_dims[0] real-valued actions (n_heads = 1,
@@ -259,8 +306,8 @@ typedef struct ppo_config {
  *                               own device functions (equal logits give equal action, log-prob and entropy bits); a row gets the same logits and value from
  *                               every entry point, bit for bit.  The context always lives in the generic engine's layout -- also at obs_size 2, 4 and 8, where
  *                               the flag takes it off the reference-shape kernels; the parameter order is Agent::parameters() order either way.  Against the
- *                               same context without the flag: log-probs and values agree to f32 summation order, not bit for bit.  One device env runs on
- *                               the family too, PPO_ENV_ACROBOT (above), in the one form it accepts; there the flag is required.  Opt-in; a Gaussian
+ *                               same context without the flag: log-probs and values agree to f32 summation order, not bit for bit.  Two device envs run on
+ *                               the family too, PPO_ENV_ACROBOT and PPO_ENV_TAXI (above), in the forms they accept; there the flag is required.  Opt-in; a Gaussian
  *                               policy, any other device env, PPO_ENV_SYNTHETIC, another width or depth, bf16, obs_size > 64 or PPO_KERNEL_GAUSS_FUSED beside it make
  *                               ppo_ctx_create return PPO_ERR_UNSUPPORTED with a message that names the limit -- never served by another engine instead.
  *                               ppo_evaluate stays refused as on the generic engine; truncation flags in ppo_dev_observe are served as on a
@@ -477,7 +524,7 @@ PPO_API ppo_status ppo_matmul(int32_t trans_a, int32_t trans_b, int64_t M, int64
 /* Stateless batched CartPole::step (CartPole.cpp:47-94) / MountainCar::step (MountainCar.cpp:29-57) on injected
  * states: state_in [n,O] (array-of-structs like the reference's std::vector<float> state), action i64 [n];
  * outputs next_state [n,O], reward f32 [n], terminated i32 [n].  PPO_ENV_ACROBOT: the same call with state_in / next_state [n,4] (the state, not the
- * observation) and action in {0, 1, 2}. */
+ * observation) and action in {0, 1, 2}.  PPO_ENV_TAXI: likewise with state (row, col, pass, dest) [n,4] and action in 0..5 (clamped; state components too). */
 PPO_API ppo_status ppo_env_transition(int32_t env_kind, const float* state_in, const int64_t* action, int64_t n, float* next_state,
                               float* reward, int32_t* terminated, void* stream);
 /* First n_resets reset states [n_resets,4] of std::mt19937(seed) + uniform_real_distribution<float>(-0.05,0.05)
@@ -918,7 +965,9 @@ typedef struct ppo_eval_stats {
  *   PPO_ENV_ACROBOT: served likewise as ONE launch (cat_eval_kernel; the lane keeps the state, the observation goes through the forward).  Episode e starts
  *   at reset 0 of env e under `seed` (the four words of philox4x32_10(seed; e, 0, 0, 1) mapped to [-0.1, 0.1)).  greedy != 0: the first-index argmax of
  *   ppo_policy_act_greedy; greedy == 0: the draw keyed (seed, e, step t within the episode, head 0), bit for bit ppo_policy_act(step_index = t) on row e of
- *   a context whose seed is `seed` and whose env_offset is 0. */
+ *   a context whose seed is `seed` and whose env_offset is 0.
+ *   PPO_ENV_TAXI: the same launch; episode e starts at reset 0 of env e under `seed` (the reset map above).  Under PPO_DIST_MASKED the lane forms the mask of
+ *   its state and both the argmax and the draw run on the masked probabilities: a masked-out action has probability 0 and is never chosen. */
 PPO_API ppo_status ppo_evaluate(ppo_ctx* ctx, int64_t n_episodes, int64_t seed, int32_t greedy,
                                 float* ep_return /* dev f32[n] or NULL */, int32_t* ep_length /* dev i32[n] or NULL */,
                                 ppo_eval_stats* out_h);

@@ -580,17 +580,20 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
     // PPO_ENV_ACROBOT: the device env of the fused categorical kernels (cat_rollout_kernel); the network lives in the generic engine's layout, as a
     // PPO_ENV_HOST context with PPO_KERNEL_CAT_FUSED does
     const bool acrobot = cfg->env_kind == PPO_ENV_ACROBOT;
+    // PPO_ENV_TAXI: the second such env, the same kernels instantiated for it; the one env that forms a mask, so it takes PPO_DIST_MASKED as well
+    const bool taxi = cfg->env_kind == PPO_ENV_TAXI;
+    const bool cat_env = acrobot || taxi;
     // PPO_KERNEL_ENV_GENERIC on CartPole / MountainCar: the network lives in the generic engine's layout, with PPO_ENV_SYNTHETIC's limits (the flag anywhere
     // else is refused below, behind the checks of env_kind, dist_kind, compute_dtype and of the flag word itself)
     const bool env_generic = (cfg->kernel_flags & PPO_KERNEL_ENV_GENERIC) != 0 && (cfg->env_kind == PPO_ENV_CARTPOLE || cfg->env_kind == PPO_ENV_MOUNTAINCAR);
-    const bool generic = cfg->env_kind == PPO_ENV_SYNTHETIC || (host_env && !host_ref) || gauss_env || acrobot || env_generic;
+    const bool generic = cfg->env_kind == PPO_ENV_SYNTHETIC || (host_env && !host_ref) || gauss_env || cat_env || env_generic;
     if (!generic && (cfg->hidden != PPO_HIDDEN || cfg->n_hidden != 2))
         return fail(nullptr, PPO_ERR_UNSUPPORTED, "only the reference architecture (2 hidden layers of 64, Agent.cpp:25-59) is built for the reference's "
                     "environments; got %d x %d (other shapes run with env_kind = PPO_ENV_SYNTHETIC)", cfg->n_hidden, cfg->hidden);
-    if (generic && !gauss_env && !acrobot && (cfg->hidden < 1 || cfg->hidden > 2048 || cfg->n_hidden < 1 || cfg->n_hidden > GEN_MAX_LAYERS - 1 || cfg->obs_size < 1 || cfg->obs_size > 8192))
+    if (generic && !gauss_env && !cat_env && (cfg->hidden < 1 || cfg->hidden > 2048 || cfg->n_hidden < 1 || cfg->n_hidden > GEN_MAX_LAYERS - 1 || cfg->obs_size < 1 || cfg->obs_size > 8192))
         return fail(nullptr, PPO_ERR_UNSUPPORTED, "generic network out of range: hidden %d (1..2048), n_hidden %d (1..%d), obs %d (1..8192)", cfg->hidden,
                     cfg->n_hidden, GEN_MAX_LAYERS - 1, cfg->obs_size);
-    if (cfg->env_kind != PPO_ENV_CARTPOLE && cfg->env_kind != PPO_ENV_MOUNTAINCAR && cfg->env_kind != PPO_ENV_SYNTHETIC && cfg->env_kind != PPO_ENV_HOST && !gauss_env && !acrobot)
+    if (cfg->env_kind != PPO_ENV_CARTPOLE && cfg->env_kind != PPO_ENV_MOUNTAINCAR && cfg->env_kind != PPO_ENV_SYNTHETIC && cfg->env_kind != PPO_ENV_HOST && !gauss_env && !cat_env)
         return fail(nullptr, PPO_ERR_INVALID, "unknown env_kind %d", cfg->env_kind);
     if (cfg->dist_kind != PPO_DIST_CATEGORICAL && cfg->dist_kind != PPO_DIST_MASKED && !gauss) return fail(nullptr, PPO_ERR_INVALID, "unknown dist_kind %d", cfg->dist_kind);
     if (cfg->compute_dtype != PPO_DTYPE_F32 && cfg->compute_dtype != PPO_DTYPE_BF16) return fail(nullptr, PPO_ERR_INVALID, "unknown compute_dtype %d", cfg->compute_dtype);
@@ -673,6 +676,27 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
                             "time limit only); got %d", cfg->max_episode_steps);
         }
     }
+    if (taxi) {   // accepted in exactly the forms ppo_hip.h states (PPO_ENV_TAXI); a wrong obs_size first, with the reference's message (below)
+        if (cfg->obs_size == 19) {
+            if (cfg->dist_kind != PPO_DIST_MASKED && cfg->dist_kind != PPO_DIST_CATEGORICAL)
+                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_TAXI takes one of six discrete actions, drawn under the env's action mask or without it: it is "
+                            "built for dist_kind = PPO_DIST_MASKED and PPO_DIST_CATEGORICAL; got dist_kind %d", cfg->dist_kind);
+            if (cfg->n_heads != 1 || cfg->head_dims[0] != 6)
+                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_TAXI has one head of six actions (south, north, east, west, pickup, dropoff): n_heads = 1 and "
+                            "head_dims[0] = 6; got n_heads = %d, head_dims[0] = %d", cfg->n_heads, cfg->head_dims[0]);
+            if (cfg->hidden != 64 || cfg->n_hidden != 2)
+                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_TAXI is built for the 2 x 64 network (hidden = 64, n_hidden = 2) of the fused categorical "
+                            "kernels; got %d x %d", cfg->n_hidden, cfg->hidden);
+            if (cfg->compute_dtype != PPO_DTYPE_F32)
+                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_TAXI is built for compute_dtype = PPO_DTYPE_F32; bf16 storage is not");
+            if (!cat_fused)
+                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_TAXI needs PPO_KERNEL_CAT_FUSED in kernel_flags: its rollout exists on the fused categorical "
+                            "kernels only, and the flag is never implied (no other engine serves in its place)");
+            if (cfg->max_episode_steps < 1)
+                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_TAXI is built for max_episode_steps >= 1 (an episode that never delivers the passenger ends at "
+                            "the time limit only); got %d", cfg->max_episode_steps);
+        }
+    }
     if (gauss && !host_env && !gauss_env)
         return fail(nullptr, PPO_ERR_UNSUPPORTED, "dist_kind = PPO_DIST_GAUSSIAN serves caller-stepped environments (env_kind = PPO_ENV_HOST), PPO_ENV_PENDULUM and "
                     "PPO_ENV_MOUNTAINCAR_CONTINUOUS: CartPole, MountainCar and the synthetic env take discrete actions; got env_kind %d", cfg->env_kind);
@@ -688,8 +712,8 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
         if (gauss)
             return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED serves dist_kind = PPO_DIST_CATEGORICAL and PPO_DIST_MASKED only; this context's policy is "
                         "PPO_DIST_GAUSSIAN (its twin is PPO_KERNEL_GAUSS_FUSED)");
-        if (!host_env && !acrobot)
-            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED serves caller-stepped environments (env_kind = PPO_ENV_HOST) and PPO_ENV_ACROBOT only; got "
+        if (!host_env && !cat_env)
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED serves caller-stepped environments (env_kind = PPO_ENV_HOST), PPO_ENV_ACROBOT and PPO_ENV_TAXI only; got "
                         "env_kind %d", cfg->env_kind);
         if (cfg->hidden != 64) return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED is built for hidden = 64; got hidden = %d", cfg->hidden);
         if (cfg->n_hidden != 2) return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED is built for n_hidden = 2; got n_hidden = %d", cfg->n_hidden);
@@ -701,7 +725,7 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
     if (cfg->compute_dtype == PPO_DTYPE_BF16 && !generic)
         return fail(nullptr, PPO_ERR_UNSUPPORTED, "compute_dtype = PPO_DTYPE_BF16 applies to networks whose layers are GEMMs (env_kind = PPO_ENV_SYNTHETIC); the reference's "
                     "2 x 64 networks always compute in f32");
-    const int env_obs = cfg->env_kind == PPO_ENV_CARTPOLE ? 4 : (cfg->env_kind == PPO_ENV_MOUNTAINCAR || mcc ? 2 : (pendulum ? 3 : (acrobot ? 6 : cfg->obs_size)));   // host / synthetic: no check
+    const int env_obs = cfg->env_kind == PPO_ENV_CARTPOLE ? 4 : (cfg->env_kind == PPO_ENV_MOUNTAINCAR || mcc ? 2 : (pendulum ? 3 : (acrobot ? 6 : (taxi ? 19 : cfg->obs_size))));   // host / synthetic: no check
     if (cfg->obs_size != env_obs) {
         // the reference's runtime check in initEnvs (PPO_Discrete.cpp:370-375), same wording
         return fail(nullptr, PPO_ERR_INVALID,
@@ -1388,7 +1412,7 @@ extern "C" ppo_status ppo_categorical_sample(const float* m_probs, int64_t n, in
 extern "C" ppo_status ppo_env_transition(int32_t env_kind, const float* state_in, const int64_t* action, int64_t n, float* next_state,
                                          float* reward, int32_t* terminated, void* stream) {
     if (!state_in || !action || !next_state || !reward || !terminated || n < 0) return PPO_ERR_INVALID;
-    if (cat_fused_env_serves(env_kind))   // PPO_ENV_ACROBOT: state [n, 4]
+    if (cat_fused_env_serves(env_kind))   // PPO_ENV_ACROBOT, PPO_ENV_TAXI: state [n, 4]
         return launch_cat_env_transition(env_kind, state_in, action, n, next_state, reward, terminated, (hipStream_t)stream) == hipSuccess ? PPO_OK : PPO_ERR_HIP;
     return launch_env_transition(env_kind, state_in, action, n, next_state, reward, terminated, (hipStream_t)stream) == hipSuccess ? PPO_OK : PPO_ERR_HIP;
 }
@@ -1407,6 +1431,9 @@ static inline bool is_mcc(const ppo_ctx* c) { return c->cfg.env_kind == PPO_ENV_
 static inline bool is_gauss_env(const ppo_ctx* c) { return is_pendulum(c) || is_mcc(c); }
 // the device env with integer actions of the fused categorical rollout (gauss_fused.hpp: cat_fused_rollout)
 static inline bool is_acrobot(const ppo_ctx* c) { return c->cfg.env_kind == PPO_ENV_ACROBOT; }
+static inline bool is_taxi(const ppo_ctx* c) { return c->cfg.env_kind == PPO_ENV_TAXI; }
+// the device envs with integer actions: the envs of the fused categorical rollout (gauss_fused.hpp)
+static inline bool is_cat_env(const ppo_ctx* c) { return is_acrobot(c) || is_taxi(c); }
 static inline const char* gauss_env_name(const ppo_ctx* c) { return is_mcc(c) ? "PPO_ENV_MOUNTAINCAR_CONTINUOUS" : "PPO_ENV_PENDULUM"; }
 
 extern "C" ppo_status ppo_env_transition_f32(int32_t env_kind, const float* state_in, const float* action, int64_t n, float* next_state, float* obs_out,
@@ -1420,7 +1447,7 @@ extern "C" ppo_status ppo_env_reset(ppo_ctx* c) {
     NEED(c, c != nullptr, "null ctx");
     if (c->host_env) return host_env_refuses(c, "ppo_env_reset");
     DeviceGuard dev_guard(c);
-    if (is_acrobot(c)) {
+    if (is_cat_env(c)) {
         HIPCHK(c, launch_cat_env_reset(c->cfg.env_kind, c->N, c->cfg.seed, c->cfg.env_offset, B_<float>(c, PPO_BUF_ENV_STATE), B_<int32_t>(c, PPO_BUF_EP_LEN), B_<float>(c, PPO_BUF_EP_REW),
                                       B_<int32_t>(c, PPO_BUF_RESET_COUNT), B_<float>(c, PPO_BUF_NEXT_OBS), B_<int32_t>(c, PPO_BUF_NEXT_DONE), c->stream));
         return PPO_OK;
@@ -1449,7 +1476,7 @@ extern "C" ppo_status ppo_env_step(ppo_ctx* c, const int64_t* action, float* obs
     if (c->host_env) return host_env_refuses(c, "ppo_env_step");
     if (is_gauss_env(c)) return fail(c, PPO_ERR_UNSUPPORTED, "ppo_env_step: this context's env (%s) takes real-valued actions f32 [N, D]; call ppo_env_step_f32", gauss_env_name(c));
     DeviceGuard dev_guard(c);
-    if (is_acrobot(c)) {
+    if (is_cat_env(c)) {
         HIPCHK(c, launch_cat_env_step(c->cfg.env_kind, c->N, c->cfg.max_episode_steps, c->cfg.seed, c->cfg.env_offset, B_<float>(c, PPO_BUF_ENV_STATE), B_<int32_t>(c, PPO_BUF_EP_LEN),
                                      B_<float>(c, PPO_BUF_EP_REW), B_<int32_t>(c, PPO_BUF_RESET_COUNT), action, obs, reward, done, c->stream));
         return PPO_OK;
@@ -1478,18 +1505,27 @@ extern "C" ppo_status ppo_env_step_f32(ppo_ctx* c, const float* action, float* o
 }
 
 // the env state's width: the observation IS the state for CartPole and both MountainCars; Pendulum keeps (theta, theta_dot) behind a 3-wide observation
-static inline int env_state_dim(const ppo_ctx* c) { return is_pendulum(c) ? 2 : (is_acrobot(c) ? 4 : c->O); }
+static inline int env_state_dim(const ppo_ctx* c) { return is_pendulum(c) ? 2 : (is_cat_env(c) ? 4 : c->O); }
 
 extern "C" ppo_status ppo_env_set_state_h(ppo_ctx* c, const float* state_h, const int32_t* ep_len_h, const float* ep_rew_h, const int32_t* reset_count_h) {
     NEED(c, c != nullptr, "null ctx");
     DeviceGuard dev_guard(c);
+    if (state_h && is_taxi(c)) {   // a Taxi state is four small integers (row, col in 0..4, pass in 0..4, dest in 0..3): checked here, on the host array
+        static const float hi[4] = { 4.0f, 4.0f, 4.0f, 3.0f };
+        for (int64_t i = 0; i < (int64_t)c->N * 4; i++) {
+            const float v = state_h[i];
+            if (!(v >= 0.0f && v <= hi[i & 3] && v == (float)(int)v))
+                return fail(c, PPO_ERR_INVALID, "ppo_env_set_state_h: state[%lld][%d] = %g is not an integer in 0..%d (PPO_ENV_TAXI: row, col, pass in 0..4, dest in "
+                            "0..3); nothing was changed", (long long)(i >> 2), (int)(i & 3), (double)v, (int)hi[i & 3]);
+        }
+    }
     if (state_h) {
         const int S = env_state_dim(c);
         ppo_status s = ppo_memcpy_h2d(c, c->scratch_obs, state_h, (size_t)c->N * S * sizeof(float));
         if (s != PPO_OK) return s;
         HIPCHK(c, launch_aos_to_soa(c->scratch_obs, B_<float>(c, PPO_BUF_ENV_STATE), c->N, S, true, c->stream));
         if (is_pendulum(c)) HIPCHK(c, launch_gauss_env_obs(c->cfg.env_kind, c->N, B_<float>(c, PPO_BUF_ENV_STATE), B_<float>(c, PPO_BUF_NEXT_OBS), c->stream));
-        else if (is_acrobot(c)) HIPCHK(c, launch_cat_env_obs(c->cfg.env_kind, c->N, B_<float>(c, PPO_BUF_ENV_STATE), B_<float>(c, PPO_BUF_NEXT_OBS), c->stream));
+        else if (is_cat_env(c)) HIPCHK(c, launch_cat_env_obs(c->cfg.env_kind, c->N, B_<float>(c, PPO_BUF_ENV_STATE), B_<float>(c, PPO_BUF_NEXT_OBS), c->stream));
         else HIPCHK(c, hipMemcpyAsync(c->buf[PPO_BUF_NEXT_OBS], c->scratch_obs, (size_t)c->N * c->O * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     }
     ppo_status s = PPO_OK;
@@ -1656,7 +1692,30 @@ static ppo_status gauss_env_rollout(ppo_ctx* c, const float* forced) {
     return PPO_OK;
 }
 
-// PPO_ENV_ACROBOT: cat_rollout_kernel (all T steps), then the critic over the stored observations and over NEXT_OBS: three launches, gauss_env_rollout's plan
+// ppo_env_truncation_bootstrap's launch on PPO_ENV_TAXI: gauss_env_fold_truncations with the state recovered from the stored observation and i32 actions
+// (gauss_fused.hpp: CatFoldArgs).  None of the launches ppo_gauss_fused_launches counts.
+static ppo_status cat_env_fold_truncations(ppo_ctx* c) {
+    CatFoldArgs f{};
+    f.params = B_<float>(c, PPO_BUF_PARAMS);
+    f.obs = B_<float>(c, PPO_BUF_OBS);
+    f.actions = B_<int32_t>(c, PPO_BUF_ACTIONS);
+    f.fin_len = B_<int32_t>(c, PPO_BUF_FIN_LEN);
+    f.B = c->B;
+    f.max_episode_steps = c->cfg.max_episode_steps;
+    f.gamma = c->cfg.gamma;
+    f.rewards = B_<float>(c, PPO_BUF_REWARDS);
+    f.ev_count = c->envt_count; f.ev_index = c->envt_index; f.ev_value = c->envt_value; f.ev_cap = c->B;
+    HIPCHK(c, hipMemsetAsync(c->envt_count, 0, sizeof(int32_t), c->stream));
+    HIPCHK(c, cat_fused_trunc_fold(c->cfg.env_kind, c->gen->L, f, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->envt_count_h, c->envt_count, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipEventRecord(c->envt_ev, c->stream));
+    c->envt_last = true;
+    c->envt_fetched = false;
+    return PPO_OK;
+}
+
+// PPO_ENV_ACROBOT, PPO_ENV_TAXI: cat_rollout_kernel (all T steps), then the critic over the stored observations and over NEXT_OBS: three launches,
+// gauss_env_rollout's plan; with ppo_env_truncation_bootstrap on (PPO_ENV_TAXI only), the fold behind them
 static ppo_status cat_env_rollout(ppo_ctx* c, const int64_t* forced) {
     ppo_status s = consume_finished_episodes(c);
     if (s != PPO_OK) return s;
@@ -1681,11 +1740,15 @@ static ppo_status cat_env_rollout(ppo_ctx* c, const int64_t* forced) {
     r.forced = forced;
     {
         ProfScope ps(c, PROF_ROLLOUT);
-        HIPCHK(c, cat_fused_rollout(c->cfg.env_kind, c->gen->L, r, c->stream));
+        HIPCHK(c, cat_fused_rollout(c->cfg.env_kind, c->cfg.dist_kind, c->gen->L, r, c->stream));
         s = gen_values(c, r.obs, (int64_t)c->T * c->N, B_<float>(c, PPO_BUF_VALUES));
         if (s == PPO_OK) s = gen_values(c, r.next_obs, c->N, B_<float>(c, PPO_BUF_NEXT_VALUE));
         if (s != PPO_OK) return s;
-        c->envt_last = false;   // envt_on is never set on this env (envt_state)
+        c->envt_last = false;
+        if (c->envt_on) {   // behind the two critic launches, in front of the scan (envt_on is never set on an Acrobot context: envt_state)
+            s = cat_env_fold_truncations(c);
+            if (s != PPO_OK) return s;
+        }
     }
     c->rollout_steps += c->T;
     c->global_step += (int64_t)c->T * c->cfg.global_num_envs;
@@ -1710,7 +1773,7 @@ extern "C" ppo_status ppo_rollout(ppo_ctx* c, const int64_t* forced_actions) {
         return gauss_env_rollout(c, nullptr);
     }
     DeviceGuard dev_guard(c);
-    if (is_acrobot(c)) return cat_env_rollout(c, forced_actions);
+    if (is_cat_env(c)) return cat_env_rollout(c, forced_actions);
     ppo_status s = consume_finished_episodes(c);
     if (s != PPO_OK) return s;
     if (c->gen && !c->env_generic) return gen_rollout(c, forced_actions);
@@ -1850,7 +1913,7 @@ extern "C" ppo_status ppo_evaluate(ppo_ctx* c, int64_t n_episodes, int64_t seed,
         return fail(c, PPO_ERR_UNSUPPORTED, "ppo_evaluate is not built for PPO_ENV_PENDULUM: step the episodes through ppo_policy_act_f32 with greedy = 1 and "
                                             "ppo_env_transition_f32");
     const bool gauss_env = is_mcc(c);   // the episodes run on the fused Gaussian kernels (gauss_eval_kernel); everything on the host side is shared
-    const bool cat_env = is_acrobot(c);   // ... or on the fused categorical kernels (cat_eval_kernel)
+    const bool cat_env = is_cat_env(c);   // ... or on the fused categorical kernels (cat_eval_kernel)
     if (c->env_generic)
         return fail(c, PPO_ERR_UNSUPPORTED, "ppo_evaluate is not built for PPO_KERNEL_ENV_GENERIC contexts: its episode kernels hold the reference's 2 x 64 network; step "
                                             "the episodes with ppo_policy_act_greedy + ppo_env_transition");
@@ -1862,7 +1925,7 @@ extern "C" ppo_status ppo_evaluate(ppo_ctx* c, int64_t n_episodes, int64_t seed,
     NEED(c, n_episodes > 0, "ppo_evaluate: n_episodes <= 0");
     NEED(c, n_episodes < (1ll << 28), "ppo_evaluate: more than 2^28 episodes");
     NEED(c, c->cfg.max_episode_steps > 0, "ppo_evaluate: max_episode_steps <= 0 (an episode would never be truncated)");
-    NEED(c, c->O == (c->cfg.env_kind == PPO_ENV_CARTPOLE ? 4 : (cat_env ? 6 : 2)), "ppo_evaluate: obs_size does not match the environment");
+    NEED(c, c->O == (c->cfg.env_kind == PPO_ENV_CARTPOLE ? 4 : (cat_env ? (is_taxi(c) ? 19 : 6) : 2)), "ppo_evaluate: obs_size does not match the environment");
     DeviceGuard dev_guard(c);
     ppo_status s = eval_scratch(c, n_episodes, seed);
     if (s != PPO_OK) return s;
@@ -1873,7 +1936,7 @@ extern "C" ppo_status ppo_evaluate(ppo_ctx* c, int64_t n_episodes, int64_t seed,
         g.max_episode_steps = c->cfg.max_episode_steps;
         g.greedy = greedy != 0;
         g.ep_return = c->eval_ret; g.ep_length = c->eval_len; g.ep_trunc = c->eval_len + c->eval_cap;
-        if (cat_env) HIPCHK(c, cat_fused_evaluate(c->cfg.env_kind, c->gen->L, g, c->stream));
+        if (cat_env) HIPCHK(c, cat_fused_evaluate(c->cfg.env_kind, c->cfg.dist_kind, c->gen->L, g, c->stream));
         else HIPCHK(c, gauss_fused_evaluate(c->cfg.env_kind, c->gen->L, g, c->stream));
     } else {
         s = eval_launch_categorical(c, n_episodes, seed, greedy);
@@ -3264,6 +3327,7 @@ static ppo_status envt_state(ppo_ctx* c, const char* what) {
         return fail(c, PPO_ERR_UNSUPPORTED, "%s: the fold rebuilds the final observation of a cut-off episode from PPO_BUF_OBS, and a PPO_ENV_ACROBOT observation "
                                             "(cos, sin of two angles, two velocities) does not hold the angles: not built for this env", what);
     if (is_mcc(c)) return PPO_OK;   // its observation is its state: the fold runs on the fused Gaussian critic (gauss_env_fold_truncations)
+    if (is_taxi(c)) return PPO_OK;  // its observation holds its state (four one-hot groups): the fold decodes it (cat_env_fold_truncations)
     if (c->env_generic)
         return fail(c, PPO_ERR_UNSUPPORTED, "%s: the fold of CartPole / MountainCar is built on the reference-shape critic (2 x 64), and this context's network lives "
                                             "on the generic engine (PPO_KERNEL_ENV_GENERIC): not built for it", what);

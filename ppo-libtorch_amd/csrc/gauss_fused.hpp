@@ -113,7 +113,26 @@ struct CatRolloutArgs {
     float* next_obs; int32_t* next_done;
     const int64_t* forced;
 };
-hipError_t cat_fused_rollout(int env_kind, const GenLayout& L, const CatRolloutArgs& r, hipStream_t s);
+hipError_t cat_fused_rollout(int env_kind, int dist_kind, const GenLayout& L, const CatRolloutArgs& r, hipStream_t s);
+// PPO_ENV_TAXI (CatEnvTaxi) is the env of this family that forms a mask (HAS_MASK): under dist_kind = PPO_DIST_MASKED a lane draws under the mask of its state
+// and PPO_BUF_MASKS holds those masks; under PPO_DIST_CATEGORICAL it holds ones, as on PPO_ENV_ACROBOT.  Its observation holds its state (STATE_FROM_OBS), so
+// it also has the time-limit fold (ppo_env_truncation_bootstrap): GaussFoldArgs' contract with i32 actions [B, 1], on cat_trunc_fold_kernel.
+bool cat_fused_env_folds(int env_kind);
+struct CatFoldArgs {
+    const float* params;
+    const float* obs;
+    const int32_t* actions;
+    const int32_t* fin_len;
+    int64_t B;
+    int max_episode_steps;
+    float gamma;
+    float* rewards;
+    int32_t* ev_count;
+    int32_t* ev_index;
+    float* ev_value;
+    int64_t ev_cap;
+};
+hipError_t cat_fused_trunc_fold(int env_kind, const GenLayout& L, const CatFoldArgs& f, hipStream_t s);
 // The env's stand-alone kernels, one thread per env, on the rollout kernel's device functions; env_state is [STATE, N]
 hipError_t launch_cat_env_reset(int env_kind, int N, int64_t seed, int64_t env_offset, float* env_state, int32_t* ep_len, float* ep_rew, int32_t* reset_count,
                                 float* next_obs, int32_t* next_done, hipStream_t s);
@@ -123,4 +142,4 @@ hipError_t launch_cat_env_transition(int env_kind, const float* state_in, const 
                                      hipStream_t s);
 hipError_t launch_cat_env_obs(int env_kind, int N, const float* env_state, float* next_obs, hipStream_t s);
 // ppo_evaluate on such an env: GaussEvalArgs' contract on cat_eval_kernel (greedy: the first-index argmax; else the draw keyed (seed, e, step of the episode, 0))
-hipError_t cat_fused_evaluate(int env_kind, const GenLayout& L, const GaussEvalArgs& a, hipStream_t s);
+hipError_t cat_fused_evaluate(int env_kind, int dist_kind, const GenLayout& L, const GaussEvalArgs& a, hipStream_t s);

@@ -26,6 +26,10 @@
 // The device env with integer actions (ppo_internal.hpp: CatEnvAcrobot, PPO_ENV_ACROBOT) adds the categorical twins on the same forward: cat_rollout_kernel
 // (gauss_rollout_kernel's plan with cat_act_kernel's wave-0 work; obs 6, 3 logits: gf_carve(8, 4) = 14 672 floats = 58 688 bytes, two workgroups per CU), its
 // stand-alone env kernels and cat_eval_kernel (ppo_evaluate); the lanes keep the env's STATE, so the observation need not be the state.
+// PPO_ENV_TAXI (CatEnvTaxi) instantiates the same kernels for an env whose mask means something (HAS_MASK: under PPO_DIST_MASKED a lane forms the mask of its
+// state, draws under it, and waves 1 .. 3 store it), whose observation is 19 wide (OBS_ONE_HOT: the lane moves four ones in the X image; gf_carve(20, 8) =
+// 16 784 floats = 67 136 bytes, above 64 KB: the attribute is asked for, two workgroups per CU still fit in 160 KB -- arithmetic, not a measurement) and holds
+// the state (STATE_FROM_OBS: cat_trunc_fold_kernel, the time-limit fold).  The traits are compile-time: the Acrobot instantiations are what they were.
 //
 // Caller-stepped contexts of either family fold time-limit truncations per step in gauss_dev_fold_kernel (ppo_dev_observe with flags): the critic kernel's
 // forward on the flagged rows of the step, found on the device.
@@ -1081,7 +1085,7 @@ __global__ __launch_bounds__(GF_THREADS) void gauss_eval_kernel(GfEvalArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// cat_rollout_kernel<Env> (PPO_ENV_ACROBOT): gauss_rollout_kernel's plan with cat_act_kernel's wave-0 work -- the T steps of a categorical rollout as ONE
+// cat_rollout_kernel<Env, DIST> (PPO_ENV_ACROBOT, PPO_ENV_TAXI): gauss_rollout_kernel's plan with cat_act_kernel's wave-0 work -- the T steps of a categorical rollout as ONE
 // launch.  A workgroup owns one tile of 64 envs for the whole rollout; the actor's weights are staged once.  Lanes 0 .. 63 of wave 0 keep their env (state,
 // episode sums, reset count, previous done flag, the current observation) in registers and do, per step, what cat_act_kernel<PPO_DIST_CATEGORICAL>'s wave 0
 // does behind the same forward -- categorical_head and sample_head on the lane's columns of OUT and H1, the same Philox key (seed, env_offset + env,
@@ -1091,6 +1095,13 @@ __global__ __launch_bounds__(GF_THREADS) void gauss_eval_kernel(GfEvalArgs a) {
 // behind the stores; every thread runs every barrier, a short tile masks its stores only.  No workgroup talks to another.
 // LDS: gf_carve(8, 4) for PPO_ENV_ACROBOT (OBS 6, 3 logits) = 14 672 floats = 58 688 bytes, two workgroups per CU; rows OBS .. obsP - 1 of the X image are zero
 // padding, written once.  The policy has ONE head (ppo_ctx_create), of Env::ACTIONS logits.
+// PPO_ENV_TAXI: gf_carve(20, 8) = 16 784 floats = 67 136 bytes (the launcher asks for the attribute through gf_allow).  Env::HAS_MASK and DIST = PPO_DIST_MASKED:
+// the lane forms the mask bits of its state in front of the forward, publishes them next to the done flag in the row-index words (bit 0 the flag, bits 1 ..
+// the mask), and behind the forward draws under them with cat_act_kernel<PPO_DIST_MASKED>'s expressions (categorical_head<PPO_DIST_MASKED, GF_S> on the lane's
+// columns, the same key and word select), so ppo_policy_act(obs, mask, step_index) + ppo_env_step reproduces every stored bit; waves 1 .. 3 store the real mask
+// rows meanwhile.  DIST = PPO_DIST_CATEGORICAL on such an env: ones, and an unmasked draw -- Acrobot's rule.  Env::OBS_ONE_HOT: the lane keeps no observation;
+// its column of the X image is zeroed once and per step the HOT old ones are cleared and the HOT new ones set -- 8 LDS stores at computed rows (and about as
+// many address computations) against 19 compares, 19 selects and 19 stores for writing the column out: the smaller instruction count, chosen for that.
 // ---------------------------------------------------------------------------------------------------------
 struct CfRolloutArgs {
     GfShape sh;
@@ -1115,12 +1126,20 @@ struct CfRolloutArgs {
 };
 
 // wave 0's lane behind the forward: the row's head on the lane's columns (z: OUT, log-probs in place; p: H1), the action (GREEDY: the first-index argmax of
-// the probabilities; forced; or the draw with uniform word `ws`) and its log-prob -- cat_act_kernel's expressions for one unmasked head
-template <bool GREEDY>
-__device__ __forceinline__ int cat_lane_head(const GfLds& m, int lane, int Ah, bool has_forced, int forced, uint32_t ws, float& lp) {
+// the probabilities; forced; or the draw with uniform word `ws`) and its log-prob -- cat_act_kernel<DIST>'s expressions for one head.  PPO_DIST_MASKED:
+// bit k of `allowed` is the row's mask byte k (the lane formed it from its env's state; a masked-out logit becomes -1e8f, its probability 0)
+template <int DIST, bool GREEDY>
+__device__ __forceinline__ int cat_lane_head(const GfLds& m, int lane, int Ah, uint32_t allowed, bool has_forced, int forced, uint32_t ws, float& lp) {
     float* z = m.o + lane;
     float* p = m.h1 + lane;
-    (void)categorical_head<PPO_DIST_CATEGORICAL, GF_S>(z, p, nullptr, Ah);
+    if constexpr (DIST == PPO_DIST_MASKED) {
+        uint8_t mrow[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) mrow[k] = (uint8_t)((allowed >> k) & 1u);
+        (void)categorical_head<PPO_DIST_MASKED, GF_S>(z, p, mrow, Ah);
+    } else {
+        (void)categorical_head<PPO_DIST_CATEGORICAL, GF_S>(z, p, nullptr, Ah);
+    }
     int a;
     if constexpr (GREEDY) {
         a = 0;
@@ -1134,28 +1153,36 @@ __device__ __forceinline__ int cat_lane_head(const GfLds& m, int lane, int Ah, b
     for (int k = 0; k < Ah; k++) if (k == a) lp = z[k * GF_S];
     return a;
 }
+// a caller's i64 action as the env's int: saturated, not truncated, so that an env that clamps its action clamps the caller's number
+__device__ __forceinline__ int cat_action_int(int64_t a) { return a < -2147483647ll ? -2147483647 : (a > 2147483647ll ? 2147483647 : (int)a); }
 __device__ __forceinline__ uint32_t cat_draw_word(int64_t seed, int64_t row, int64_t step_index) {
     const uint4 w = philox4x32_10((uint32_t)seed, (uint32_t)((uint64_t)seed >> 32), (uint32_t)row, (uint32_t)(step_index >> 2), 0u, 0u);
     return (step_index & 3) == 0 ? w.x : ((step_index & 3) == 1 ? w.y : ((step_index & 3) == 2 ? w.z : w.w));
 }
 
-template <class Env>
+template <class Env, int DIST>
 __global__ __launch_bounds__(GF_THREADS) void cat_rollout_kernel(CfRolloutArgs a) {
-    constexpr int OBS = Env::OBS, ST = Env::STATE, A = Env::ACTIONS, OBSP = (OBS + 3) & ~3;
-    static_assert(OBS <= 8 && A <= 4, "the rollout kernel carves its LDS for an observation of at most 8 floats and a head of at most 4 logits");
+    constexpr int OBS = Env::OBS, ST = Env::STATE, A = Env::ACTIONS, OBSP = (OBS + 3) & ~3, OUTP = (A + 3) & ~3;
+    constexpr bool MASKED = Env::HAS_MASK && DIST == PPO_DIST_MASKED;   // the env's mask is drawn under and stored; otherwise PPO_BUF_MASKS holds ones
+    static_assert(OBS <= 20 && A <= 8, "the rollout kernel carves its LDS for an observation of at most 20 floats and a head of at most 8 logits");
+    static_assert(DIST == PPO_DIST_CATEGORICAL || Env::HAS_MASK, "a masked policy needs an env that forms a mask");
     extern __shared__ __attribute__((aligned(16))) float gf_lds[];
     const int tid = threadIdx.x, N = a.N;
-    const GfLds m = gf_carve(gf_lds, OBSP, 4);
+    const GfLds m = gf_carve(gf_lds, OBSP, OUTP);
     gf_stage_weights(m, a.sh, a.params, 1, tid);
     const int row0 = blockIdx.x * 64;
     const int env = row0 + (tid & 63);
     const bool owner = tid < 64 && env < N;
     const int64_t env_global = a.env_offset + env;
-    float st[ST], ob[OBS], ep_rew = 0.0f;
+    // a one-hot env keeps no observation: its lane moves the ones in the X image (hot: the rows that hold them)
+    float st[ST], ob[Env::OBS_ONE_HOT ? 1 : OBS], ep_rew = 0.0f;
+    int hot[Env::OBS_ONE_HOT ? Env::HOT : 1];
 #pragma unroll
     for (int k = 0; k < ST; k++) st[k] = 0.0f;
+    if constexpr (!Env::OBS_ONE_HOT) {
 #pragma unroll
-    for (int k = 0; k < OBS; k++) ob[k] = 0.0f;
+        for (int k = 0; k < OBS; k++) ob[k] = 0.0f;
+    }
     int ep_len = 0, resets = 0, done = 0;
     if (owner) {
 #pragma unroll
@@ -1164,19 +1191,39 @@ __global__ __launch_bounds__(GF_THREADS) void cat_rollout_kernel(CfRolloutArgs a
         ep_rew = a.ep_rew[env];
         resets = a.reset_count[env];
         done = a.next_done[env];
-        Env::obs(st, ob);
+        if constexpr (!Env::OBS_ONE_HOT) Env::obs(st, ob);
     }
-    if (tid < 64) {   // the padding rows of the observation image, once
+    if (tid < 64) {
+        if constexpr (Env::OBS_ONE_HOT) {   // the whole column of the observation image, once: per step 2 HOT stores move the ones (19 selects and stores otherwise)
 #pragma unroll
-        for (int k = OBS; k < OBSP; k++) m.x[k * GF_S + tid] = 0.0f;
+            for (int k = 0; k < OBSP; k++) m.x[k * GF_S + tid] = 0.0f;
+            Env::hot(st, hot);   // a lane without an env: the all-zero state, whose rows are inside the image like any other's
+        } else {   // the padding rows of the observation image, once
+#pragma unroll
+            for (int k = OBS; k < OBSP; k++) m.x[k * GF_S + tid] = 0.0f;
+        }
     }
     const int rows = N - row0 < 64 ? N - row0 : 64;
     for (int t = 0; t < a.T; t++) {
         const size_t tn = (size_t)t * N;
+        uint32_t allowed = 0xffu;
         if (tid < 64) {
+            if constexpr (Env::OBS_ONE_HOT) {
 #pragma unroll
-            for (int k = 0; k < OBS; k++) m.x[k * GF_S + tid] = ob[k];
-            m.ridx[tid] = done;
+                for (int k = 0; k < Env::HOT; k++) m.x[hot[k] * GF_S + tid] = 0.0f;   // the previous step's ones (the first step: zeros over zeros)
+                Env::hot(st, hot);
+#pragma unroll
+                for (int k = 0; k < Env::HOT; k++) m.x[hot[k] * GF_S + tid] = 1.0f;
+            } else {
+#pragma unroll
+                for (int k = 0; k < OBS; k++) m.x[k * GF_S + tid] = ob[k];
+            }
+            if constexpr (MASKED) {   // the mask of the state the action is drawn in rides next to the done flag: waves 1 .. 3 store its row
+                allowed = Env::mask_bits(st);
+                m.ridx[tid] = done | (int)(allowed << 1);
+            } else {
+                m.ridx[tid] = done;
+            }
         }
         gf_forward_tile(m, A, tid);
         if (tid < 64) {
@@ -1184,11 +1231,12 @@ __global__ __launch_bounds__(GF_THREADS) void cat_rollout_kernel(CfRolloutArgs a
                 const int64_t step_index = a.step_base + t;
                 const uint32_t ws = a.forced ? 0u : cat_draw_word(a.seed, env_global, step_index);
                 float lp;
-                const int act = cat_lane_head<false>(m, tid, A, a.forced != nullptr, a.forced ? (int)a.forced[tn + env] : 0, ws, lp);
+                const int act = cat_lane_head<MASKED ? PPO_DIST_MASKED : PPO_DIST_CATEGORICAL, false>(m, tid, A, allowed, a.forced != nullptr,
+                                                                                                      a.forced ? cat_action_int(a.forced[tn + env]) : 0, ws, lp);
                 int fin_len;
                 float fin_rew;
                 const float r = Env::step_episode(st, act, a.max_episode_steps, a.seed, env_global, ep_len, ep_rew, resets, done, fin_len, fin_rew);
-                Env::obs(st, ob);
+                if constexpr (!Env::OBS_ONE_HOT) Env::obs(st, ob);
                 a.actions[tn + env] = act;
                 a.logprobs[tn + env] = lp;
                 a.rewards[tn + env] = r;
@@ -1202,14 +1250,29 @@ __global__ __launch_bounds__(GF_THREADS) void cat_rollout_kernel(CfRolloutArgs a
                 obs_t[i] = m.x[k * GF_S + s];
             }
             uint8_t* mask_t = a.masks + (tn + row0) * A;
-            for (int i = tid - 64; i < rows * A; i += GF_THREADS - 64) mask_t[i] = (uint8_t)1;
-            if (tid < 128 && env < N) a.dones[tn + env] = (float)m.ridx[tid & 63];
+            if constexpr (MASKED) {
+                for (int i = tid - 64; i < rows * A; i += GF_THREADS - 64) {
+                    const int s = i / A, k = i - A * s;
+                    mask_t[i] = (uint8_t)((m.ridx[s] >> (1 + k)) & 1);
+                }
+                if (tid < 128 && env < N) a.dones[tn + env] = (float)(m.ridx[tid & 63] & 1);
+            } else {
+                for (int i = tid - 64; i < rows * A; i += GF_THREADS - 64) mask_t[i] = (uint8_t)1;
+                if (tid < 128 && env < N) a.dones[tn + env] = (float)m.ridx[tid & 63];
+            }
         }
         __syncthreads();   // X, OUT, the H1 columns and the done words are read: wave 0 may write the next step's
     }
     if (owner) {
+        if constexpr (Env::OBS_ONE_HOT) {
+            float fo[OBS];
+            Env::obs(st, fo);
 #pragma unroll
-        for (int k = 0; k < OBS; k++) a.next_obs[(size_t)env * OBS + k] = ob[k];
+            for (int k = 0; k < OBS; k++) a.next_obs[(size_t)env * OBS + k] = fo[k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < OBS; k++) a.next_obs[(size_t)env * OBS + k] = ob[k];
+        }
         a.next_done[env] = done;
 #pragma unroll
         for (int k = 0; k < ST; k++) a.env_state[(size_t)k * N + env] = st[k];
@@ -1246,7 +1309,7 @@ __global__ void cat_env_step_kernel(int N, int max_episode_steps, int64_t seed, 
     for (int j = 0; j < Env::STATE; j++) st[j] = env_state[(size_t)j * N + i];
     int len = ep_len[i], resets = reset_count[i], d, fin_len;
     float rew = ep_rew[i], fin_rew;
-    const float r = Env::step_episode(st, (int)action[i], max_episode_steps, seed, env_offset + i, len, rew, resets, d, fin_len, fin_rew);
+    const float r = Env::step_episode(st, cat_action_int(action[i]), max_episode_steps, seed, env_offset + i, len, rew, resets, d, fin_len, fin_rew);
     Env::obs(st, ob);
     for (int j = 0; j < Env::STATE; j++) env_state[(size_t)j * N + i] = st[j];
     ep_len[i] = len;
@@ -1265,7 +1328,7 @@ __global__ void cat_env_transition_kernel(const float* __restrict__ state_in, co
     float st[Env::STATE];
     for (int j = 0; j < Env::STATE; j++) st[j] = state_in[i * Env::STATE + j];
     int term;
-    const float r = Env::step(st, (int)action[i], term);
+    const float r = Env::step(st, cat_action_int(action[i]), term);
     for (int j = 0; j < Env::STATE; j++) next_state[i * Env::STATE + j] = st[j];
     reward[i] = r;
     terminated[i] = term;
@@ -1282,57 +1345,81 @@ __global__ void cat_env_obs_kernel(int N, const float* __restrict__ state, float
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// cat_eval_kernel<Env> (ppo_evaluate on PPO_ENV_ACROBOT): gauss_eval_kernel's plan with a categorical head.  A workgroup owns 64 episodes for their whole
+// cat_eval_kernel<Env, DIST> (ppo_evaluate on PPO_ENV_ACROBOT, PPO_ENV_TAXI): gauss_eval_kernel's plan with a categorical head.  A workgroup owns 64 episodes for their whole
 // length with the actor's weights resident: lane l of wave 0 keeps episode 64 b + l (state, return, length) in registers -- the STATE, not the observation:
 // nothing here needs an observation to be a state -- writes its observation into the X image, every thread runs gf_forward_tile, and wave 0 takes the
 // first-index argmax of the probabilities (greedy: ppo_policy_act_greedy's) or the draw keyed (seed, episode, step of the episode, head 0) --
 // ppo_policy_act(step_index = step) on row `episode` -- and steps the env (Env::step).  The loop's exit is uniform: wave 0 publishes its live count in the
 // row-index words, the step's closing barrier hands it to the other waves (gauss_eval_kernel).  At most max_episode_steps steps.
+// PPO_ENV_TAXI under PPO_DIST_MASKED: the same widening and the same masked head as cat_rollout_kernel; greedy is the first-index argmax of the MASKED
+// probabilities (a masked-out action has probability 0 and is never chosen: an allowed one has a positive probability, and the comparison is strict).
 // ---------------------------------------------------------------------------------------------------------
-template <class Env>
+template <class Env, int DIST>
 __global__ __launch_bounds__(GF_THREADS) void cat_eval_kernel(GfEvalArgs a) {
-    constexpr int OBS = Env::OBS, ST = Env::STATE, A = Env::ACTIONS, OBSP = (OBS + 3) & ~3;
-    static_assert(OBS <= 8 && A <= 4, "as cat_rollout_kernel");
+    constexpr int OBS = Env::OBS, ST = Env::STATE, A = Env::ACTIONS, OBSP = (OBS + 3) & ~3, OUTP = (A + 3) & ~3;
+    constexpr bool MASKED = Env::HAS_MASK && DIST == PPO_DIST_MASKED;
+    constexpr int HEAD = MASKED ? PPO_DIST_MASKED : PPO_DIST_CATEGORICAL;
+    static_assert(OBS <= 20 && A <= 8, "as cat_rollout_kernel");
+    static_assert(DIST == PPO_DIST_CATEGORICAL || Env::HAS_MASK, "a masked policy needs an env that forms a mask");
     extern __shared__ __attribute__((aligned(16))) float gf_lds[];
     const int tid = threadIdx.x;
-    const GfLds m = gf_carve(gf_lds, OBSP, 4);
+    const GfLds m = gf_carve(gf_lds, OBSP, OUTP);
     gf_stage_weights(m, a.sh, a.params, 1, tid);
     const int64_t ep = (int64_t)blockIdx.x * 64 + (tid & 63);
     bool alive = tid < 64 && ep < a.n_episodes;
     const bool owner = alive;
-    float st[ST], ob[OBS], ep_rew = 0.0f;
+    float st[ST], ob[Env::OBS_ONE_HOT ? 1 : OBS], ep_rew = 0.0f;
+    int hot[Env::OBS_ONE_HOT ? Env::HOT : 1];
 #pragma unroll
     for (int k = 0; k < ST; k++) st[k] = 0.0f;
+    if constexpr (!Env::OBS_ONE_HOT) {
 #pragma unroll
-    for (int k = 0; k < OBS; k++) ob[k] = 0.0f;
+        for (int k = 0; k < OBS; k++) ob[k] = 0.0f;
+    }
     int ep_len = 0, trunc = 0;
     if (owner) {
         Env::reset(st, 0, a.seed, ep);
-        Env::obs(st, ob);
+        if constexpr (!Env::OBS_ONE_HOT) Env::obs(st, ob);
     }
     if (tid < 64) {
+        if constexpr (Env::OBS_ONE_HOT) {   // as cat_rollout_kernel: the column is zeroed once and the ones move
 #pragma unroll
-        for (int k = OBS; k < OBSP; k++) m.x[k * GF_S + tid] = 0.0f;
+            for (int k = 0; k < OBSP; k++) m.x[k * GF_S + tid] = 0.0f;
+            Env::hot(st, hot);
+        } else {
+#pragma unroll
+            for (int k = OBS; k < OBSP; k++) m.x[k * GF_S + tid] = 0.0f;
+        }
     }
     for (;;) {
         if (tid < 64) {
+            if constexpr (Env::OBS_ONE_HOT) {
 #pragma unroll
-            for (int k = 0; k < OBS; k++) m.x[k * GF_S + tid] = ob[k];
+                for (int k = 0; k < Env::HOT; k++) m.x[hot[k] * GF_S + tid] = 0.0f;
+                Env::hot(st, hot);
+#pragma unroll
+                for (int k = 0; k < Env::HOT; k++) m.x[hot[k] * GF_S + tid] = 1.0f;
+            } else {
+#pragma unroll
+                for (int k = 0; k < OBS; k++) m.x[k * GF_S + tid] = ob[k];
+            }
         }
         gf_forward_tile(m, A, tid);
         if (tid < 64) {
             if (alive) {
+                uint32_t allowed = 0xffu;
+                if constexpr (MASKED) allowed = Env::mask_bits(st);
                 float lp;
                 int act;
-                if (a.greedy) act = cat_lane_head<true>(m, tid, A, false, 0, 0u, lp);
-                else act = cat_lane_head<false>(m, tid, A, false, 0, cat_draw_word(a.seed, ep, (int64_t)ep_len), lp);
+                if (a.greedy) act = cat_lane_head<HEAD, true>(m, tid, A, allowed, false, 0, 0u, lp);
+                else act = cat_lane_head<HEAD, false>(m, tid, A, allowed, false, 0, cat_draw_word(a.seed, ep, (int64_t)ep_len), lp);
                 int term;
                 const float r = Env::step(st, act, term);
                 ep_len += 1;
                 ep_rew += r;
                 trunc = ep_len == a.max_episode_steps ? 1 : 0;
                 if (term || trunc) alive = false;
-                Env::obs(st, ob);
+                if constexpr (!Env::OBS_ONE_HOT) Env::obs(st, ob);
             }
             const unsigned long long live = __ballot(alive);
             if (tid == 0) m.ridx[0] = __popcll(live);
@@ -1345,6 +1432,99 @@ __global__ __launch_bounds__(GF_THREADS) void cat_eval_kernel(GfEvalArgs a) {
         a.ep_return[ep] = ep_rew;
         a.ep_length[ep] = ep_len;
         a.ep_trunc[ep] = trunc;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// cat_trunc_fold_kernel<Env> (ppo_env_truncation_bootstrap on an env with STATE_FROM_OBS: PPO_ENV_TAXI): gauss_trunc_fold_kernel's plan for an env whose
+// observation is not its state but holds it.  A 256-thread workgroup owns 256 consecutive flat samples.  A lane whose episode reached the limit
+// (FIN_LEN[i] == max_episode_steps) decodes OBS[i] to the state (Env::state_of), steps it under ACTIONS[i, 0] (i32; divergent code without a barrier) and
+// keeps the sample unless the env terminated on that step.  ONE compaction (fold_compact); a workgroup that keeps none returns before it loads a weight (the
+// count is the same in every thread, so the return is uniform).  The kept samples' final STATES (Env::STATE words, not Env::OBS) wait in LDS in list order;
+// the critic's weights are staged on gauss_values_kernel's carve, and a tile's X image is the observations of 64 of those states, expanded as it is written.
+// gf_forward_tile is gauss_values_kernel's forward, so v is that kernel's value of the final observation, bit for bit -- the critic that fills PPO_BUF_VALUES
+// on this family.  Lane k of wave 0 folds row k of the tile (fold_store: two roundings).
+// LDS: all dynamic, counted by the launcher (cat_fold_lds_bytes) -- gf_lds_floats(obsP, 4) floats, behind them the kept states [256][STATE] and the row list
+// [256] with the waves' totals [8]: 65 024 + 4 096 + 1 056 = 70 176 bytes for PPO_ENV_TAXI, above 64 KB: the attribute is asked for (gf_allow).
+// ---------------------------------------------------------------------------------------------------------
+struct CfFoldArgs {
+    GfShape sh;
+    const float* params;
+    const float* obs;          // [B, Env::OBS]
+    const int32_t* actions;    // [B, 1]
+    const int32_t* fin_len;
+    int64_t B;
+    int max_episode_steps;
+    float gamma;
+    float* rewards;
+    int32_t* ev_count;
+    int32_t* ev_index;
+    float* ev_value;
+    int64_t ev_cap;
+};
+
+template <class Env>
+int cat_fold_lds_bytes() {   // every byte of LDS the kernel uses: the attribute is decided on this sum
+    return (gf_lds_floats(gf_pad4(Env::OBS), 4) + DEV_FOLD_THREADS * Env::STATE) * (int)sizeof(float) + GF_DEV_FOLD_LIST_INTS * (int)sizeof(int);
+}
+
+template <class Env>
+__global__ __launch_bounds__(DEV_FOLD_THREADS) void cat_trunc_fold_kernel(CfFoldArgs a) {
+    constexpr int OBS = Env::OBS, ST = Env::STATE, OBSP = (OBS + 3) & ~3;
+    static_assert(Env::STATE_FROM_OBS, "the fold steps the env from the state behind a stored observation");
+    static_assert(DEV_FOLD_THREADS == GF_THREADS, "fold_compact and gf_forward_tile are written for the same workgroup");
+    extern __shared__ __attribute__((aligned(16))) float gf_lds[];
+    float* fst = gf_lds + gf_lds_floats(OBSP, 4);
+    int* list = reinterpret_cast<int*>(fst + DEV_FOLD_THREADS * ST);
+    int* wtot = list + DEV_FOLD_THREADS;
+    const int tid = threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * DEV_FOLD_THREADS + tid;
+    bool keep = false;
+    float st[ST];
+#pragma unroll
+    for (int j = 0; j < ST; j++) st[j] = 0.0f;
+    if (i < a.B && a.fin_len[i] == a.max_episode_steps) {
+        float ob[OBS];
+#pragma unroll
+        for (int j = 0; j < OBS; j++) ob[j] = a.obs[i * OBS + j];
+        Env::state_of(ob, st);
+        int terminated;
+        (void)Env::step(st, a.actions[i], terminated);
+        keep = terminated == 0;
+    }
+    int pos;
+    const int cnt = fold_compact(keep, (int)i, a.ev_count, list, wtot, pos);
+    if (cnt == 0) return;
+    const int base = wtot[4];
+    if (keep) {
+#pragma unroll
+        for (int j = 0; j < ST; j++) fst[pos * ST + j] = st[j];
+    }
+    const GfLds m = gf_carve(gf_lds, OBSP, 4);
+    gf_stage_weights(m, a.sh, a.params, 0, tid);
+    if (tid < 64) {   // the padding rows of the observation image, once
+#pragma unroll
+        for (int k = OBS; k < OBSP; k++) m.x[k * GF_S + tid] = 0.0f;
+    }
+    __syncthreads();   // the kept states are complete
+    for (int k0 = 0; k0 < cnt; k0 += 64) {
+        const int k = k0 + tid;   // tid < 64: this lane's place in the list
+        if (tid < 64) {
+            float ob[OBS];
+#pragma unroll
+            for (int j = 0; j < OBS; j++) ob[j] = 0.0f;
+            if (k < cnt) {
+                float fs[ST];
+#pragma unroll
+                for (int j = 0; j < ST; j++) fs[j] = fst[k * ST + j];
+                Env::obs(fs, ob);
+            }
+#pragma unroll
+            for (int j = 0; j < OBS; j++) m.x[j * GF_S + tid] = ob[j];
+        }
+        gf_forward_tile(m, 1, tid);
+        if (tid < 64 && k < cnt) fold_store(a.rewards, a.gamma, a.ev_index, a.ev_value, a.ev_cap, (int64_t)base + k, list[k], m.o[tid]);
+        __syncthreads();   // X and OUT are read: the next tile may overwrite them
     }
 }
 
@@ -1596,24 +1776,49 @@ hipError_t gauss_fused_evaluate(int env_kind, const GenLayout& L, const GaussEva
     return hipGetLastError();
 }
 
-// ---- the device envs with integer actions (PPO_ENV_ACROBOT; the context's shape is fixed by ppo_ctx_create: obs Env::OBS, one head of Env::ACTIONS logits) ----
+// ---- the device envs with integer actions (PPO_ENV_ACROBOT, PPO_ENV_TAXI; the context's shape is fixed by ppo_ctx_create: obs Env::OBS, one head of
+// Env::ACTIONS logits) ----
 template <class F>
 static hipError_t cat_env_dispatch(int env_kind, F f) {
     if (env_kind == PPO_ENV_ACROBOT) return f(CatEnvAcrobot{});
+    if (env_kind == PPO_ENV_TAXI) return f(CatEnvTaxi{});
     return hipErrorInvalidValue;
 }
 template <class Env>
 static bool cat_env_shape_ok(const GenLayout& L) { return L.obs == Env::OBS && L.gauss == 0 && L.n_heads == 1 && L.act == Env::ACTIONS; }
+// a masked policy runs on an env that forms a mask, and on no other (ppo_ctx_create)
 template <class Env>
-static int cat_env_lds_bytes() { return gf_lds_floats(gf_pad4(Env::OBS), 4) * 4; }
+static bool cat_env_dist_ok(int dist_kind) { return dist_kind == PPO_DIST_CATEGORICAL || (dist_kind == PPO_DIST_MASKED && Env::HAS_MASK); }
+template <class Env>
+static int cat_env_lds_bytes() { return gf_lds_floats(gf_pad4(Env::OBS), gf_pad4(Env::ACTIONS)) * 4; }
 
-bool cat_fused_env_serves(int env_kind) { return env_kind == PPO_ENV_ACROBOT; }
+bool cat_fused_env_serves(int env_kind) { return env_kind == PPO_ENV_ACROBOT || env_kind == PPO_ENV_TAXI; }
 
-hipError_t cat_fused_rollout(int env_kind, const GenLayout& L, const CatRolloutArgs& r, hipStream_t s) {
+// cat_rollout_kernel<Env, DIST> for the context's distribution; the attribute where the carve passes 64 KB (PPO_ENV_TAXI: 67 136 bytes)
+template <class Env, int DIST>
+static hipError_t cat_rollout_launch(const CfRolloutArgs& a, int N, hipStream_t s) {
+    const int bytes = cat_env_lds_bytes<Env>();
+    static std::atomic<unsigned long long> done{ 0 };
+    const hipError_t e = gf_allow(done, cat_rollout_kernel<Env, DIST>, bytes);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((cat_rollout_kernel<Env, DIST>), dim3((unsigned)((N + 63) / 64)), dim3(GF_THREADS), bytes, s, a);
+    return hipGetLastError();
+}
+template <class Env, int DIST>
+static hipError_t cat_eval_launch(const GfEvalArgs& a, hipStream_t s) {
+    const int bytes = cat_env_lds_bytes<Env>();
+    static std::atomic<unsigned long long> done{ 0 };
+    const hipError_t e = gf_allow(done, cat_eval_kernel<Env, DIST>, bytes);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((cat_eval_kernel<Env, DIST>), dim3((unsigned)((a.n_episodes + 63) / 64)), dim3(GF_THREADS), bytes, s, a);
+    return hipGetLastError();
+}
+
+hipError_t cat_fused_rollout(int env_kind, int dist_kind, const GenLayout& L, const CatRolloutArgs& r, hipStream_t s) {
     if (r.N <= 0 || r.T <= 0) return hipSuccess;
     return cat_env_dispatch(env_kind, [&](auto env) {
         using Env = decltype(env);
-        if (!cat_env_shape_ok<Env>(L)) return hipErrorInvalidValue;
+        if (!cat_env_shape_ok<Env>(L) || !cat_env_dist_ok<Env>(dist_kind)) return hipErrorInvalidValue;
         CfRolloutArgs a{};
         a.sh = gf_shape(L);
         a.params = r.params;
@@ -1623,12 +1828,37 @@ hipError_t cat_fused_rollout(int env_kind, const GenLayout& L, const CatRolloutA
         a.obs = r.obs; a.masks = r.masks; a.actions = r.actions; a.logprobs = r.logprobs; a.rewards = r.rewards; a.dones = r.dones;
         a.fin_len = r.fin_len; a.fin_rew = r.fin_rew;
         a.next_obs = r.next_obs; a.next_done = r.next_done; a.forced = r.forced;
-        const int bytes = cat_env_lds_bytes<Env>();
-        static std::atomic<unsigned long long> done{ 0 };
-        const hipError_t e = gf_allow(done, cat_rollout_kernel<Env>, bytes);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(cat_rollout_kernel<Env>, dim3((unsigned)((r.N + 63) / 64)), dim3(GF_THREADS), bytes, s, a);
-        return hipGetLastError();
+        if constexpr (Env::HAS_MASK) {
+            if (dist_kind == PPO_DIST_MASKED) return cat_rollout_launch<Env, PPO_DIST_MASKED>(a, r.N, s);
+        }
+        return cat_rollout_launch<Env, PPO_DIST_CATEGORICAL>(a, r.N, s);
+    });
+}
+
+// ppo_env_truncation_bootstrap on an env whose observation holds its state (cat_trunc_fold_kernel)
+bool cat_fused_env_folds(int env_kind) { return env_kind == PPO_ENV_TAXI; }
+hipError_t cat_fused_trunc_fold(int env_kind, const GenLayout& L, const CatFoldArgs& f, hipStream_t s) {
+    if (f.B <= 0 || f.max_episode_steps <= 0) return hipSuccess;   // no limit: no episode is ever cut off
+    if (f.B >= (1ll << 31)) return hipErrorInvalidValue;
+    return cat_env_dispatch(env_kind, [&](auto env) {
+        using Env = decltype(env);
+        if constexpr (Env::STATE_FROM_OBS) {
+            if (!cat_env_shape_ok<Env>(L)) return hipErrorInvalidValue;
+            CfFoldArgs a{};
+            a.sh = gf_shape(L);
+            a.params = f.params; a.obs = f.obs; a.actions = f.actions; a.fin_len = f.fin_len;
+            a.B = f.B; a.max_episode_steps = f.max_episode_steps; a.gamma = f.gamma;
+            a.rewards = f.rewards; a.ev_count = f.ev_count; a.ev_index = f.ev_index; a.ev_value = f.ev_value; a.ev_cap = f.ev_cap;
+            const int bytes = cat_fold_lds_bytes<Env>();
+            static std::atomic<unsigned long long> done{ 0 };
+            const hipError_t e = gf_allow(done, cat_trunc_fold_kernel<Env>, bytes);
+            if (e != hipSuccess) return e;
+            const unsigned grid = (unsigned)((f.B + DEV_FOLD_THREADS - 1) / DEV_FOLD_THREADS);
+            hipLaunchKernelGGL(cat_trunc_fold_kernel<Env>, dim3(grid), dim3(DEV_FOLD_THREADS), bytes, s, a);
+            return hipGetLastError();
+        } else {
+            return hipErrorInvalidValue;
+        }
     });
 }
 
@@ -1667,20 +1897,21 @@ hipError_t launch_cat_env_obs(int env_kind, int N, const float* env_state, float
         return hipGetLastError();
     });
 }
-hipError_t cat_fused_evaluate(int env_kind, const GenLayout& L, const GaussEvalArgs& e, hipStream_t s) {
+hipError_t cat_fused_evaluate(int env_kind, int dist_kind, const GenLayout& L, const GaussEvalArgs& e, hipStream_t s) {
     if (e.n_episodes <= 0) return hipSuccess;
     if (e.max_episode_steps < 1 || e.n_episodes >= (1ll << 31) * 64 || !e.ep_return || !e.ep_length || !e.ep_trunc) return hipErrorInvalidValue;
     return cat_env_dispatch(env_kind, [&](auto env) {
         using Env = decltype(env);
-        if (!cat_env_shape_ok<Env>(L)) return hipErrorInvalidValue;
+        if (!cat_env_shape_ok<Env>(L) || !cat_env_dist_ok<Env>(dist_kind)) return hipErrorInvalidValue;
         GfEvalArgs a{};
         a.sh = gf_shape(L);
         a.params = e.params;
         a.n_episodes = e.n_episodes; a.seed = e.seed;
         a.max_episode_steps = e.max_episode_steps; a.greedy = e.greedy != 0;
         a.ep_return = e.ep_return; a.ep_length = e.ep_length; a.ep_trunc = e.ep_trunc;
-        const int bytes = cat_env_lds_bytes<Env>();
-        hipLaunchKernelGGL(cat_eval_kernel<Env>, dim3((unsigned)((e.n_episodes + 63) / 64)), dim3(GF_THREADS), bytes, s, a);
-        return hipGetLastError();
+        if constexpr (Env::HAS_MASK) {
+            if (dist_kind == PPO_DIST_MASKED) return cat_eval_launch<Env, PPO_DIST_MASKED>(a, s);
+        }
+        return cat_eval_launch<Env, PPO_DIST_CATEGORICAL>(a, s);
     });
 }

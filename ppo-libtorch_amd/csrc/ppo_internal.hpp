@@ -488,14 +488,124 @@ __device__ __forceinline__ float acrobot_step_episode(float* st, int action, int
 // What the fused categorical kernels need of a device env with integer actions (kernels_gauss_fused.hip: cat_rollout_kernel, the stand-alone env kernels,
 // cat_eval_kernel): GaussEnv*'s members with an int action.  The env takes head 0's action.
 struct CatEnvAcrobot {
-    static constexpr int OBS = 6, STATE = 4, ACTIONS = 3;
+    static constexpr int OBS = 6, STATE = 4, ACTIONS = 3, HOT = 0;
     static constexpr bool OBS_IS_STATE = false;
+    static constexpr bool HAS_MASK = false;         // every action is always allowed: PPO_BUF_MASKS holds ones
+    static constexpr bool STATE_FROM_OBS = false;   // the observation does not hold the angles: no truncation fold
+    static constexpr bool OBS_ONE_HOT = false;
     __device__ static __forceinline__ void obs(const float* st, float* ob) { acrobot_obs(st, ob); }
     __device__ static __forceinline__ float step(float* st, int a, int& terminated) { return acrobot_step(st, a, terminated); }
     __device__ static __forceinline__ void reset(float* st, int k, int64_t seed, int64_t env_global) { acrobot_reset(st, k, seed, env_global); }
     __device__ static __forceinline__ float step_episode(float* st, int a, int max_episode_steps, int64_t seed, int64_t env_global, int& ep_len, float& ep_rew,
                                                          int& resets, int& done, int& fin_len, float& fin_rew) {
         return acrobot_step_episode(st, a, max_episode_steps, seed, env_global, ep_len, ep_rew, resets, done, fin_len, fin_rew);
+    }
+};
+
+// Taxi-v3 (gymnasium's toy_text/taxi.py, no rain, no fickle passenger; no reference counterpart: PPO_ENV_TAXI; ppo_hip.h states the table).  st = {row, col,
+// pass, dest}, small integers held exactly in f32: row, col in 0..4, pass in 0..4 (0..3 waiting at R, G, Y, B; 4 in the taxi), dest in 0..3.  Stands, as
+// (row, col): R (0,0), G (0,4), Y (4,0), B (4,3).  The walls and stands are a few compares: no table in memory.  Every function converts and clamps each
+// component into its range first (a NaN becomes 0), so a foreign state can index nothing outside the observation.
+struct TaxiState { int r, c, p, d; };
+__device__ __forceinline__ int taxi_clamp(float v, int hi) { return v >= 0.0f ? (v >= (float)hi ? hi : (int)v) : 0; }
+__device__ __forceinline__ TaxiState taxi_load(const float* st) { return TaxiState{ taxi_clamp(st[0], 4), taxi_clamp(st[1], 4), taxi_clamp(st[2], 4), taxi_clamp(st[3], 3) }; }
+__device__ __forceinline__ bool taxi_east_blocked(int r, int c) { return c == 4 || (r <= 1 && c == 1) || (r >= 3 && (c == 0 || c == 2)); }
+__device__ __forceinline__ bool taxi_west_blocked(int r, int c) { return c == 0 || taxi_east_blocked(r, c - 1); }
+// the stand the taxi is on, or -1
+__device__ __forceinline__ int taxi_stand(int r, int c) { return r == 0 ? (c == 0 ? 0 : (c == 4 ? 1 : -1)) : (r == 4 ? (c == 0 ? 2 : (c == 3 ? 3 : -1)) : -1); }
+// bit a: action a is allowed (exactly when it changes the state); never 0: south or north is always allowed
+__device__ __forceinline__ uint32_t taxi_mask_bits(const float* st) {
+    const TaxiState s = taxi_load(st);
+    const int on = taxi_stand(s.r, s.c);
+    return (s.r < 4 ? 1u : 0u) | (s.r > 0 ? 2u : 0u) | (taxi_east_blocked(s.r, s.c) ? 0u : 4u) | (taxi_west_blocked(s.r, s.c) ? 0u : 8u) |
+           ((s.p < 4 && on == s.p) ? 16u : 0u) | ((s.p == 4 && on >= 0) ? 32u : 0u);
+}
+__device__ __forceinline__ float taxi_step(float* st, int action, int& terminated) {
+    TaxiState s = taxi_load(st);
+    const int a = action < 0 ? 0 : (action > 5 ? 5 : action);
+    const int on = taxi_stand(s.r, s.c);
+    float reward = -1.0f;
+    terminated = 0;
+    if (a == 0) s.r = s.r < 4 ? s.r + 1 : 4;
+    else if (a == 1) s.r = s.r > 0 ? s.r - 1 : 0;
+    else if (a == 2) { if (!taxi_east_blocked(s.r, s.c)) s.c += 1; }
+    else if (a == 3) { if (!taxi_west_blocked(s.r, s.c)) s.c -= 1; }
+    else if (a == 4) {
+        if (s.p < 4 && on == s.p) s.p = 4;
+        else reward = -10.0f;
+    } else {
+        if (s.p == 4 && on == s.d) { s.p = s.d; terminated = 1; reward = 20.0f; }
+        else if (s.p == 4 && on >= 0) s.p = on;
+        else reward = -10.0f;
+    }
+    st[0] = (float)s.r; st[1] = (float)s.c; st[2] = (float)s.p; st[3] = (float)s.d;
+    return reward;
+}
+// the rows of the observation that hold 1.0f: one per one-hot group (row [0..4], col [5..9], pass [10..14], dest [15..18])
+__device__ __forceinline__ void taxi_hot(const float* st, int* hot) {
+    const TaxiState s = taxi_load(st);
+    hot[0] = s.r; hot[1] = 5 + s.c; hot[2] = 10 + s.p; hot[3] = 15 + s.d;
+}
+__device__ __forceinline__ void taxi_obs(const float* st, float* ob) {
+    int hot[4];
+    taxi_hot(st, hot);
+#pragma unroll
+    for (int k = 0; k < 19; k++) ob[k] = (k == hot[0] || k == hot[1] || k == hot[2] || k == hot[3]) ? 1.0f : 0.0f;
+}
+// the state behind an observation: the index of the largest entry of each group, the first on ties (any 19 floats give a state inside the ranges)
+__device__ __forceinline__ void taxi_state_of(const float* ob, float* st) {
+    constexpr int lo[4] = { 0, 5, 10, 15 }, n[4] = { 5, 5, 5, 4 };
+#pragma unroll
+    for (int g = 0; g < 4; g++) {
+        int best = 0;
+#pragma unroll
+        for (int k = 1; k < n[g]; k++) if (ob[lo[g] + k] > ob[lo[g] + best]) best = k;
+        st[g] = (float)best;
+    }
+}
+// reset number k of global env e: MountainCar's keying, philox(seed; e, k, 0, 1); uniform over gymnasium's 300 start states (passenger waiting, not at the
+// destination): cell = (x * 25) >> 32, pass = (y * 4) >> 32, d = (z * 3) >> 32, dest = d + (d >= pass)
+__device__ __forceinline__ void taxi_reset(float* st, int k, int64_t seed, int64_t env_global) {
+    const uint4 w = philox4x32_10((uint32_t)seed, (uint32_t)((uint64_t)seed >> 32), (uint32_t)env_global, (uint32_t)k, 0u, 1u);
+    const int cell = (int)(((uint64_t)w.x * 25u) >> 32);
+    const int pass = (int)(((uint64_t)w.y * 4u) >> 32);
+    const int d = (int)(((uint64_t)w.z * 3u) >> 32);
+    st[0] = (float)(cell / 5); st[1] = (float)(cell % 5); st[2] = (float)pass; st[3] = (float)(d + (d >= pass ? 1 : 0));
+}
+// The second device env with integer actions (PPO_ENV_TAXI), the first with a mask that means something and with a state the fold can recover:
+//   HAS_MASK        mask_bits(st): bit a = action a is allowed in st (cat_rollout_kernel / cat_eval_kernel draw under it when the policy is PPO_DIST_MASKED)
+//   STATE_FROM_OBS  state_of(ob, st): the state behind a stored observation (cat_trunc_fold_kernel)
+//   OBS_ONE_HOT     hot(st, rows): the observation is HOT ones, at these rows, over zeros -- a lane moves the ones in the X image, it keeps no observation
+struct CatEnvTaxi {
+    static constexpr int OBS = 19, STATE = 4, ACTIONS = 6, HOT = 4;
+    static constexpr bool OBS_IS_STATE = false;
+    static constexpr bool HAS_MASK = true;
+    static constexpr bool STATE_FROM_OBS = true;
+    static constexpr bool OBS_ONE_HOT = true;
+    __device__ static __forceinline__ void obs(const float* st, float* ob) { taxi_obs(st, ob); }
+    __device__ static __forceinline__ void hot(const float* st, int* rows) { taxi_hot(st, rows); }
+    __device__ static __forceinline__ uint32_t mask_bits(const float* st) { return taxi_mask_bits(st); }
+    __device__ static __forceinline__ void state_of(const float* ob, float* st) { taxi_state_of(ob, st); }
+    __device__ static __forceinline__ float step(float* st, int a, int& terminated) { return taxi_step(st, a, terminated); }
+    __device__ static __forceinline__ void reset(float* st, int k, int64_t seed, int64_t env_global) { taxi_reset(st, k, seed, env_global); }
+    // env_step_kernel's bookkeeping, as acrobot_step_episode
+    __device__ static __forceinline__ float step_episode(float* st, int a, int max_episode_steps, int64_t seed, int64_t env_global, int& ep_len, float& ep_rew,
+                                                         int& resets, int& done, int& fin_len, float& fin_rew) {
+        int term;
+        const float r = taxi_step(st, a, term);
+        ep_len += 1;
+        ep_rew += r;
+        done = (term || ep_len == max_episode_steps) ? 1 : 0;
+        fin_len = 0;
+        fin_rew = 0.0f;
+        if (done) {
+            fin_len = ep_len;
+            fin_rew = ep_rew;
+            taxi_reset(st, resets++, seed, env_global);
+            ep_len = 0;
+            ep_rew = 0.0f;
+        }
+        return r;
     }
 };
 
