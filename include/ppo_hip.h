@@ -187,6 +187,47 @@ enum { PPO_ENV_ACROBOT = PPO_ENV_MOUNTAINCAR_CONTINUOUS + 1 };   /* 6: the next 
  * ppo_env_step_f32, ppo_rollout_f32, ppo_policy_act_f32 (PPO_ERR_UNSUPPORTED, naming the integer twin).  Sharding is neither claimed nor tested. */
 enum { PPO_ENV_TAXI = PPO_ENV_ACROBOT + 2 };   /* 8, not 7: value 7 stays unassigned and keeps answering "unknown env_kind 7", as 9 does -- existing tests
                                                 * hold both; in an enum of its own and written as a sum, as PPO_ENV_ACROBOT is: the first list's text is pinned */
+/* PPO_ENV_FROZENLAKE (new; value 10) and PPO_ENV_FROZENLAKE8X8 (new; value 11): gymnasium's FrozenLake-v1 and FrozenLake8x8-v1 with is_slippery = True, the
+ * first device envs whose transitions draw random numbers.  ppo_env_transition takes neither a seed nor a step index and stays stateless, so THE STATE CARRIES
+ * THE RANDOMNESS: a reset draws a per-episode key into the state, a step draws from Philox keyed by that key and the episode's step count, both state words.
+ * The transition is a pure function of (state, action); every contract of the family holds (a one-launch rollout equals a loop of ppo_policy_act +
+ * ppo_env_step bit for bit; ppo_evaluate's episode e is a pure function of (parameters, seed, e)).  Two env kinds, because ppo_env_transition(env_kind, ..)
+ * has no other way to know the map.  Every quantity is an integer held exactly in f32; nothing below rounds.
+ * Maps (gymnasium's; cells row-major, cell = row * n + col; the start is cell 0; S = n * n cells):
+ *   4x4 (PPO_ENV_FROZENLAKE, S = 16):    SFFF FHFH FFFH HFFG; holes {5, 7, 11, 12}, as a bit mask 0x18a0; goal 15
+ *   8x8 (PPO_ENV_FROZENLAKE8X8, S = 64): SFFFFFFF FFFFFFFF FFFHFFFF FFFFFHFF FFFHFFFF FHHFFFHF FHFFHFHF FFFHFFFG; holes {19, 29, 35, 41, 42, 46, 49, 52, 54, 59},
+ *                                        as a bit mask 0x0852460820080000; goal 63
+ * State (cell, j, k0, k1): cell in 0..S-1; j, the steps taken in this episode, in 0..2^24-1; k0, k1 (the episode's key) in 0..2^24-1.
+ * PPO_BUF_ENV_STATE is f32 [4, N]; ppo_env_set_state_h / ppo_env_get_state_h take [N, 4].
+ * Step under action a (clamped into 0..3: 0 left, 1 down, 2 right, 3 up):
+ *   cell is a hole or the goal (reachable only through an injected state): reward 0, terminated 1, cell unchanged, j' = min(j + 1, 2^24 - 1);
+ *   otherwise: w = philox4x32_10(key = (k0, k1); counter = (j >> 2, 0, 0, 0x20)) -- the argument order of philox4x32_10(k0, k1, c0, c1, c2, c3); tag 0x20 is
+ *   used by no other draw -- word = w[j & 3], d = (uint64(word) * 3) >> 32, eff = (a + d + 3) & 3 (gym's [(a-1)%4, a, (a+1)%4], one third each); move one cell
+ *   in direction eff, clamped at the border; terminated = cell' is a hole or the goal; reward = cell' == goal ? 1.0f : 0.0f; j' = j + 1 (held at 2^24 - 1,
+ *   which only an injected j meets: the time limit ends an episode first); k0 and k1 stay.
+ * Reset number k of global env e: w = philox4x32_10(seed; e, k, 0, 1) (MountainCar's keying); cell = 0, j = 0, k0 = w.x >> 8, k1 = w.y >> 8.  Global env 0
+ * takes reset 1 at ppo_env_reset; PPO_BUF_RESET_COUNT counts them.
+ * Observation, obs_size 16 resp. 64: the one-hot of cell (0.0f / 1.0f).  It holds the cell but not j, k0, k1.
+ * An episode ends where the env terminates or its length reaches max_episode_steps (1..16 777 215; gym: 100 and 200): done = 1, FIN_LEN / FIN_REW written,
+ * auto-reset -- ppo_env_step's bookkeeping.  Returns are 0 or 1.
+ * Memory safety, as for PPO_ENV_TAXI: ppo_env_set_state_h checks the host array -- a component that is not an integer of its range returns PPO_ERR_INVALID and
+ * changes nothing; the device functions convert and clamp each component into its range (a NaN becomes 0); a caller's i64 action is saturated, not truncated.
+ * ppo_ctx_create accepts the envs in exactly this form: dist_kind = PPO_DIST_CATEGORICAL (PPO_DIST_MASKED is refused as on PPO_ENV_ACROBOT: the env forms no
+ * mask), n_heads = 1, head_dims[0] = 4, obs_size = 16 resp. 64, hidden = 64, n_hidden = 2, PPO_DTYPE_F32, kernel_flags containing PPO_KERNEL_CAT_FUSED
+ * (required, never implied) and 1 <= max_episode_steps <= 16 777 215.  A wrong obs_size returns PPO_ERR_INVALID with the reference's obs-size message,
+ * anything else PPO_ERR_UNSUPPORTED with a message that names the limit.
+ * Calls: PPO_ENV_ACROBOT's list -- ppo_env_reset, ppo_env_set_state_h (refills NEXT_OBS) / ppo_env_get_state_h, ppo_env_step (action i64 [N, 1], obs
+ * [N, S]), ppo_env_transition(10 | 11, state [n, 4], action i64 [n], ...), ppo_rollout (forced i64 [T, N, 1] or NULL), ppo_calc_advantage, ppo_update,
+ * ppo_train_iteration, ppo_policy_act / ppo_policy_act_greedy, ppo_get_value, ppo_target_kl_set, ppo_evaluate, the statistics and profile calls,
+ * ppo_gauss_fused_launches.  ppo_rollout is THREE launches, as on Acrobot (cat_rollout_kernel; LDS 62 912 bytes at 4x4, 88 256 bytes at 8x8: one workgroup
+ * per CU there; `value` moves by 2, `act` by 0); a stepwise loop of ppo_policy_act(step_index = rollout_steps + t) and ppo_env_step reproduces every buffer
+ * it fills bit for bit (tests/test_gpu_frozenlake.py).  ppo_evaluate is ONE launch (cat_eval_kernel) and moves no counter.
+ * Refused, changing nothing: ppo_host_* / ppo_dev_* (PPO_ERR_STATE); ppo_obs_norm_* and ppo_reward_norm_* (PPO_ERR_UNSUPPORTED); ppo_env_step_f32,
+ * ppo_rollout_f32, ppo_policy_act_f32 (PPO_ERR_UNSUPPORTED, naming the integer twin); ppo_env_truncation_bootstrap and ppo_env_truncations
+ * (PPO_ERR_UNSUPPORTED: the final observation of a cut-off episode depends on j and the key, which the stored observation does not hold).  Sharding is
+ * neither claimed nor tested. */
+enum { PPO_ENV_FROZENLAKE = PPO_ENV_TAXI + 2 };      /* 10, not 9: value 9 stays unassigned, as 7 does; an enum of its own, written as a sum */
+enum { PPO_ENV_FROZENLAKE8X8 = PPO_ENV_TAXI + 3 };   /* 11 */
 /* PPO_DIST_CATEGORICAL reproduces Distributions/Categorical.cpp including its entropy clamp (:112-119);
  * PPO_DIST_MASKED reproduces Distributions/CategoricalMasked.cpp (true entropy, -1e8 masking).
  * PPO_DIST_GAUSSIAN (new; the reference has no continuous policy): a diagonal Gaussian over D = head_dims[0] real-valued actions (n_heads = 1,

@@ -117,6 +117,8 @@ hipError_t cat_fused_rollout(int env_kind, int dist_kind, const GenLayout& L, co
 // PPO_ENV_TAXI (CatEnvTaxi) is the env of this family that forms a mask (HAS_MASK): under dist_kind = PPO_DIST_MASKED a lane draws under the mask of its state
 // and PPO_BUF_MASKS holds those masks; under PPO_DIST_CATEGORICAL it holds ones, as on PPO_ENV_ACROBOT.  Its observation holds its state (STATE_FROM_OBS), so
 // it also has the time-limit fold (ppo_env_truncation_bootstrap): GaussFoldArgs' contract with i32 actions [B, 1], on cat_trunc_fold_kernel.
+// PPO_ENV_FROZENLAKE / PPO_ENV_FROZENLAKE8X8 (CatEnvFrozenLake<4>, <8>) are the envs of this family whose step draws random numbers; the key and the count of
+// the draw are words of the env state, so every entry point below serves them through the same arguments.  Their observation does not hold the state: no fold.
 bool cat_fused_env_folds(int env_kind);
 struct CatFoldArgs {
     const float* params;

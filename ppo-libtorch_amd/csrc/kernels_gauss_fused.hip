@@ -30,6 +30,10 @@
 // state, draws under it, and waves 1 .. 3 store it), whose observation is 19 wide (OBS_ONE_HOT: the lane moves four ones in the X image; gf_carve(20, 8) =
 // 16 784 floats = 67 136 bytes, above 64 KB: the attribute is asked for, two workgroups per CU still fit in 160 KB -- arithmetic, not a measurement) and holds
 // the state (STATE_FROM_OBS: cat_trunc_fold_kernel, the time-limit fold).  The traits are compile-time: the Acrobot instantiations are what they were.
+// PPO_ENV_FROZENLAKE / PPO_ENV_FROZENLAKE8X8 (CatEnvFrozenLake<4>, <8>) instantiate them for an env whose step draws random numbers.  No trait says so: the key
+// and the step count of the draw are state words (ppo_internal.hpp), so Env::step(st, a) is as pure here as Taxi's and the kernels did not change for it.  What
+// did is the observation width, 16 and 64: gf_carve(16, 4) = 15 728 floats = 62 912 bytes, two workgroups per CU; gf_carve(64, 4) = 22 064 floats =
+// 88 256 bytes, above 64 KB (the attribute is asked for) and ONE workgroup per CU of 160 KB -- arithmetic, not a measurement.
 //
 // Caller-stepped contexts of either family fold time-limit truncations per step in gauss_dev_fold_kernel (ppo_dev_observe with flags): the critic kernel's
 // forward on the flagged rows of the step, found on the device.
@@ -1102,6 +1106,11 @@ __global__ __launch_bounds__(GF_THREADS) void gauss_eval_kernel(GfEvalArgs a) {
 // rows meanwhile.  DIST = PPO_DIST_CATEGORICAL on such an env: ones, and an unmasked draw -- Acrobot's rule.  Env::OBS_ONE_HOT: the lane keeps no observation;
 // its column of the X image is zeroed once and per step the HOT old ones are cleared and the HOT new ones set -- 8 LDS stores at computed rows (and about as
 // many address computations) against 19 compares, 19 selects and 19 stores for writing the column out: the smaller instruction count, chosen for that.
+// PPO_ENV_FROZENLAKE / PPO_ENV_FROZENLAKE8X8 (OBS 16 / 64, 4 logits, HOT 1): gf_carve(16, 4) = 15 728 floats = 62 912 bytes; gf_carve(64, 4) = 22 064 floats =
+// 88 256 bytes (the attribute; one workgroup per CU).  The env's slip is drawn inside Env::step_episode, in wave 0's lane right behind the action draw: one
+// Philox call keyed by the state's own words (k0, k1) at counter (j >> 2, 0, 0, 0x20), every step -- the definition's bits by construction, since it IS the
+// definition the stand-alone step and the stateless transition run.  Waves 1 .. 3 store the step's observation rows from the X image as on the other envs: at
+// OBS 64 that is 16 KB per workgroup and step.
 // ---------------------------------------------------------------------------------------------------------
 struct CfRolloutArgs {
     GfShape sh;
@@ -1164,7 +1173,7 @@ template <class Env, int DIST>
 __global__ __launch_bounds__(GF_THREADS) void cat_rollout_kernel(CfRolloutArgs a) {
     constexpr int OBS = Env::OBS, ST = Env::STATE, A = Env::ACTIONS, OBSP = (OBS + 3) & ~3, OUTP = (A + 3) & ~3;
     constexpr bool MASKED = Env::HAS_MASK && DIST == PPO_DIST_MASKED;   // the env's mask is drawn under and stored; otherwise PPO_BUF_MASKS holds ones
-    static_assert(OBS <= 20 && A <= 8, "the rollout kernel carves its LDS for an observation of at most 20 floats and a head of at most 8 logits");
+    static_assert(OBS <= 64 && A <= 8, "the rollout kernel carves its LDS for an observation of at most 64 floats and a head of at most 8 logits");
     static_assert(DIST == PPO_DIST_CATEGORICAL || Env::HAS_MASK, "a masked policy needs an env that forms a mask");
     extern __shared__ __attribute__((aligned(16))) float gf_lds[];
     const int tid = threadIdx.x, N = a.N;
@@ -1345,7 +1354,7 @@ __global__ void cat_env_obs_kernel(int N, const float* __restrict__ state, float
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// cat_eval_kernel<Env, DIST> (ppo_evaluate on PPO_ENV_ACROBOT, PPO_ENV_TAXI): gauss_eval_kernel's plan with a categorical head.  A workgroup owns 64 episodes for their whole
+// cat_eval_kernel<Env, DIST> (ppo_evaluate on PPO_ENV_ACROBOT, PPO_ENV_TAXI, PPO_ENV_FROZENLAKE, PPO_ENV_FROZENLAKE8X8): gauss_eval_kernel's plan with a categorical head.  A workgroup owns 64 episodes for their whole
 // length with the actor's weights resident: lane l of wave 0 keeps episode 64 b + l (state, return, length) in registers -- the STATE, not the observation:
 // nothing here needs an observation to be a state -- writes its observation into the X image, every thread runs gf_forward_tile, and wave 0 takes the
 // first-index argmax of the probabilities (greedy: ppo_policy_act_greedy's) or the draw keyed (seed, episode, step of the episode, head 0) --
@@ -1353,13 +1362,15 @@ __global__ void cat_env_obs_kernel(int N, const float* __restrict__ state, float
 // row-index words, the step's closing barrier hands it to the other waves (gauss_eval_kernel).  At most max_episode_steps steps.
 // PPO_ENV_TAXI under PPO_DIST_MASKED: the same widening and the same masked head as cat_rollout_kernel; greedy is the first-index argmax of the MASKED
 // probabilities (a masked-out action has probability 0 and is never chosen: an allowed one has a positive probability, and the comparison is strict).
+// PPO_ENV_FROZENLAKE / PPO_ENV_FROZENLAKE8X8: the rollout's carves (62 912 and 88 256 bytes).  Episode e's slips come from the key its reset drew from (seed, e)
+// and from its own step count, both in the lane's state: the episode is a pure function of (parameters, seed, e), whatever its neighbours do.
 // ---------------------------------------------------------------------------------------------------------
 template <class Env, int DIST>
 __global__ __launch_bounds__(GF_THREADS) void cat_eval_kernel(GfEvalArgs a) {
     constexpr int OBS = Env::OBS, ST = Env::STATE, A = Env::ACTIONS, OBSP = (OBS + 3) & ~3, OUTP = (A + 3) & ~3;
     constexpr bool MASKED = Env::HAS_MASK && DIST == PPO_DIST_MASKED;
     constexpr int HEAD = MASKED ? PPO_DIST_MASKED : PPO_DIST_CATEGORICAL;
-    static_assert(OBS <= 20 && A <= 8, "as cat_rollout_kernel");
+    static_assert(OBS <= 64 && A <= 8, "as cat_rollout_kernel");
     static_assert(DIST == PPO_DIST_CATEGORICAL || Env::HAS_MASK, "a masked policy needs an env that forms a mask");
     extern __shared__ __attribute__((aligned(16))) float gf_lds[];
     const int tid = threadIdx.x;
@@ -1776,12 +1787,14 @@ hipError_t gauss_fused_evaluate(int env_kind, const GenLayout& L, const GaussEva
     return hipGetLastError();
 }
 
-// ---- the device envs with integer actions (PPO_ENV_ACROBOT, PPO_ENV_TAXI; the context's shape is fixed by ppo_ctx_create: obs Env::OBS, one head of
+// ---- the device envs with integer actions (PPO_ENV_ACROBOT, PPO_ENV_TAXI, PPO_ENV_FROZENLAKE, PPO_ENV_FROZENLAKE8X8; the context's shape is fixed by ppo_ctx_create: obs Env::OBS, one head of
 // Env::ACTIONS logits) ----
 template <class F>
 static hipError_t cat_env_dispatch(int env_kind, F f) {
     if (env_kind == PPO_ENV_ACROBOT) return f(CatEnvAcrobot{});
     if (env_kind == PPO_ENV_TAXI) return f(CatEnvTaxi{});
+    if (env_kind == PPO_ENV_FROZENLAKE) return f(CatEnvFrozenLake<4>{});
+    if (env_kind == PPO_ENV_FROZENLAKE8X8) return f(CatEnvFrozenLake<8>{});
     return hipErrorInvalidValue;
 }
 template <class Env>
@@ -1792,9 +1805,11 @@ static bool cat_env_dist_ok(int dist_kind) { return dist_kind == PPO_DIST_CATEGO
 template <class Env>
 static int cat_env_lds_bytes() { return gf_lds_floats(gf_pad4(Env::OBS), gf_pad4(Env::ACTIONS)) * 4; }
 
-bool cat_fused_env_serves(int env_kind) { return env_kind == PPO_ENV_ACROBOT || env_kind == PPO_ENV_TAXI; }
+bool cat_fused_env_serves(int env_kind) {
+    return env_kind == PPO_ENV_ACROBOT || env_kind == PPO_ENV_TAXI || env_kind == PPO_ENV_FROZENLAKE || env_kind == PPO_ENV_FROZENLAKE8X8;
+}
 
-// cat_rollout_kernel<Env, DIST> for the context's distribution; the attribute where the carve passes 64 KB (PPO_ENV_TAXI: 67 136 bytes)
+// cat_rollout_kernel<Env, DIST> for the context's distribution; the attribute where the carve passes 64 KB (PPO_ENV_TAXI: 67 136 bytes; PPO_ENV_FROZENLAKE8X8: 88 256)
 template <class Env, int DIST>
 static hipError_t cat_rollout_launch(const CfRolloutArgs& a, int N, hipStream_t s) {
     const int bytes = cat_env_lds_bytes<Env>();

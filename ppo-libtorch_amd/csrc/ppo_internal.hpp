@@ -609,6 +609,104 @@ struct CatEnvTaxi {
     }
 };
 
+// FrozenLake-v1 / FrozenLake8x8-v1 (gymnasium's toy_text/frozen_lake.py, is_slippery = True; no reference counterpart: PPO_ENV_FROZENLAKE, PPO_ENV_FROZENLAKE8X8;
+// ppo_hip.h states the maps and the step).  The first device env whose transitions draw random numbers, and the state carries the randomness: st = {cell, j,
+// k0, k1}, integers held exactly in f32 -- cell in 0..S-1 (row-major, S = SIDE * SIDE), j the steps taken in this episode, (k0, k1) the episode's 2 x 24-bit
+// key, drawn at the reset.  A step's slip is a word of philox4x32_10(key = (k0, k1); counter = (j >> 2, 0, 0, 0x20)), so the step stays a pure function of
+// (state, action): the stateless transition, the stand-alone step, the rollout and the evaluation share ONE definition and no seed or step index is passed.
+// Holes and goal are compares against a bit mask: no table in memory.  Every function converts and clamps each component into its range first (a NaN becomes
+// 0), so a foreign state can index nothing outside the observation.
+constexpr int FROZENLAKE_WORD_MAX = (1 << 24) - 1;   // j, k0 and k1 are at most this: every integer up to it is an f32
+constexpr uint32_t FROZENLAKE_SLIP_TAG = 0x20u;      // the Philox counter word that names this draw (no other draw of the library uses it)
+template <int SIDE>
+struct FrozenLakeMap;
+template <>
+struct FrozenLakeMap<4> {   // SFFF FHFH FFFH HFFG: holes {5, 7, 11, 12}
+    static constexpr uint64_t HOLES = 0x18a0ull;
+    static constexpr int SHIFT = 2;
+};
+template <>
+struct FrozenLakeMap<8> {   // gymnasium's 8x8: holes {19, 29, 35, 41, 42, 46, 49, 52, 54, 59}
+    static constexpr uint64_t HOLES = 0x0852460820080000ull;
+    static constexpr int SHIFT = 3;
+};
+__device__ __forceinline__ int frozenlake_clamp(float v, int hi) { return v >= 0.0f ? (v >= (float)hi ? hi : (int)v) : 0; }
+template <int SIDE>
+__device__ __forceinline__ bool frozenlake_terminal(int cell) { return cell == SIDE * SIDE - 1 || ((FrozenLakeMap<SIDE>::HOLES >> cell) & 1ull) != 0; }
+template <int SIDE>
+__device__ __forceinline__ int frozenlake_cell(const float* st) { return frozenlake_clamp(st[0], SIDE * SIDE - 1); }
+template <int SIDE>
+__device__ __forceinline__ float frozenlake_step(float* st, int action, int& terminated) {
+    constexpr int S = SIDE * SIDE, SH = FrozenLakeMap<SIDE>::SHIFT;
+    int cell = frozenlake_clamp(st[0], S - 1);
+    const int j = frozenlake_clamp(st[1], FROZENLAKE_WORD_MAX), k0 = frozenlake_clamp(st[2], FROZENLAKE_WORD_MAX), k1 = frozenlake_clamp(st[3], FROZENLAKE_WORD_MAX);
+    const int a = action < 0 ? 0 : (action > 3 ? 3 : action);
+    float reward = 0.0f;
+    terminated = 1;
+    if (!frozenlake_terminal<SIDE>(cell)) {   // a hole or the goal is reachable through an injected state only: nothing moves, nothing is drawn
+        const uint4 w = philox4x32_10((uint32_t)k0, (uint32_t)k1, (uint32_t)(j >> 2), 0u, 0u, FROZENLAKE_SLIP_TAG);
+        const uint32_t word = (j & 3) == 0 ? w.x : ((j & 3) == 1 ? w.y : ((j & 3) == 2 ? w.z : w.w));
+        const int d = (int)(((uint64_t)word * 3u) >> 32);   // 0, 1, 2: one third each
+        const int eff = (a + d + 3) & 3;                    // gym's [(a - 1) % 4, a, (a + 1) % 4]; 0 left, 1 down, 2 right, 3 up
+        int row = cell >> SH, col = cell & (SIDE - 1);
+        if (eff == 0) col = col > 0 ? col - 1 : 0;
+        else if (eff == 1) row = row < SIDE - 1 ? row + 1 : SIDE - 1;
+        else if (eff == 2) col = col < SIDE - 1 ? col + 1 : SIDE - 1;
+        else row = row > 0 ? row - 1 : 0;
+        cell = (row << SH) | col;
+        terminated = frozenlake_terminal<SIDE>(cell) ? 1 : 0;
+        reward = cell == S - 1 ? 1.0f : 0.0f;
+    }
+    st[0] = (float)cell;
+    st[1] = (float)(j < FROZENLAKE_WORD_MAX ? j + 1 : FROZENLAKE_WORD_MAX);   // the cap is met by an injected j only: max_episode_steps ends an episode first
+    st[2] = (float)k0;
+    st[3] = (float)k1;
+    return reward;
+}
+// reset number k of global env e: MountainCar's keying, philox(seed; e, k, 0, 1); the start cell, no steps taken, and the episode's key from the top 24 bits of x, y
+__device__ __forceinline__ void frozenlake_reset(float* st, int k, int64_t seed, int64_t env_global) {
+    const uint4 w = philox4x32_10((uint32_t)seed, (uint32_t)((uint64_t)seed >> 32), (uint32_t)env_global, (uint32_t)k, 0u, 1u);
+    st[0] = 0.0f; st[1] = 0.0f; st[2] = (float)(w.x >> 8); st[3] = (float)(w.y >> 8);
+}
+// The third device env with integer actions (PPO_ENV_FROZENLAKE: SIDE 4, PPO_ENV_FROZENLAKE8X8: SIDE 8), the first whose step draws: nothing of the drawing
+// shows in the traits -- step(st, a) reads its key and its count from st.  The observation is one one of `cell` over zeros (OBS_ONE_HOT, HOT 1); it holds the
+// cell but neither j nor the key, so no state can be rebuilt from it (no STATE_FROM_OBS, no truncation fold).
+template <int SIDE>
+struct CatEnvFrozenLake {
+    static constexpr int OBS = SIDE * SIDE, STATE = 4, ACTIONS = 4, HOT = 1;
+    static constexpr bool OBS_IS_STATE = false;
+    static constexpr bool HAS_MASK = false;
+    static constexpr bool STATE_FROM_OBS = false;
+    static constexpr bool OBS_ONE_HOT = true;
+    __device__ static __forceinline__ void hot(const float* st, int* rows) { rows[0] = frozenlake_cell<SIDE>(st); }
+    __device__ static __forceinline__ void obs(const float* st, float* ob) {
+        const int cell = frozenlake_cell<SIDE>(st);
+#pragma unroll
+        for (int k = 0; k < OBS; k++) ob[k] = k == cell ? 1.0f : 0.0f;
+    }
+    __device__ static __forceinline__ float step(float* st, int a, int& terminated) { return frozenlake_step<SIDE>(st, a, terminated); }
+    __device__ static __forceinline__ void reset(float* st, int k, int64_t seed, int64_t env_global) { frozenlake_reset(st, k, seed, env_global); }
+    // env_step_kernel's bookkeeping, as acrobot_step_episode
+    __device__ static __forceinline__ float step_episode(float* st, int a, int max_episode_steps, int64_t seed, int64_t env_global, int& ep_len, float& ep_rew,
+                                                         int& resets, int& done, int& fin_len, float& fin_rew) {
+        int term;
+        const float r = frozenlake_step<SIDE>(st, a, term);
+        ep_len += 1;
+        ep_rew += r;
+        done = (term || ep_len == max_episode_steps) ? 1 : 0;
+        fin_len = 0;
+        fin_rew = 0.0f;
+        if (done) {
+            fin_len = ep_len;
+            fin_rew = ep_rew;
+            frozenlake_reset(st, resets++, seed, env_global);
+            ep_len = 0;
+            ep_rew = 0.0f;
+        }
+        return r;
+    }
+};
+
 template <int ENV>
 __device__ __forceinline__ float env_step(float* st, int action, int& terminated) {
     if constexpr (ENV == PPO_ENV_CARTPOLE) return cartpole_step(st, action, terminated);
