@@ -228,6 +228,51 @@ enum { PPO_ENV_TAXI = PPO_ENV_ACROBOT + 2 };   /* 8, not 7: value 7 stays unassi
  * neither claimed nor tested. */
 enum { PPO_ENV_FROZENLAKE = PPO_ENV_TAXI + 2 };      /* 10, not 9: value 9 stays unassigned, as 7 does; an enum of its own, written as a sum */
 enum { PPO_ENV_FROZENLAKE8X8 = PPO_ENV_TAXI + 3 };   /* 11 */
+/* PPO_ENV_BLACKJACK (new; value 13): gymnasium's Blackjack-v1 with its defaults (natural = False, sab = False) and the infinite deck, on PPO_ENV_FROZENLAKE's
+ * mechanism -- THE STATE CARRIES THE RANDOMNESS -- with a reset that deals and a step whose NUMBER OF DRAWS DEPENDS ON THE DATA: a hit draws one card, a stick
+ * plays out the dealer, up to ten cards, inside one env step.  The transition is a pure function of (state, action); every contract of the family holds (a
+ * one-launch rollout equals a loop of ppo_policy_act + ppo_env_step bit for bit; ppo_evaluate's episode e is a pure function of (parameters, seed, e)).
+ * Every quantity is an integer held exactly in f32; nothing below rounds.  Returns have both signs: -1, 0 or +1.
+ * Cards: card(word) = min(1 + ((uint64(word) * 13) >> 32), 10) -- gym's deck [1..10, 10, 10, 10]: ace = 1, a ten has probability 4/13.  Card number i of an
+ *   episode with key (k0, k1) is card(w[i & 3]) of w = philox4x32_10(key = (k0, k1); counter = (i >> 2, 0, 0, 0x21)) -- the argument order of
+ *   philox4x32_10(k0, k1, c0, c1, c2, c3); tag 0x21 is used by no other draw.  Cards 0 and 1 are the player's first two, card 2 is the dealer's showing card,
+ *   card 3 the dealer's hidden card; cards 4, 5, ... are drawn in order by whoever draws next.
+ * State (hand, n, k0, k1): hand = t + 32 * ace + 64 * show with t in 2..31 the player's total with every ace counted as 1, ace in 0..1 whether the player
+ *   holds an ace, show in 1..10 the dealer's showing card; n in 0..2^24-1 the index of the next card to be drawn (4 after a reset); k0, k1 (the episode's
+ *   key) in 0..2^24-1.  Derived: usable = ace && t + 10 <= 21; sum = t + 10 * usable.  PPO_BUF_ENV_STATE is f32 [4, N]; ppo_env_set_state_h /
+ *   ppo_env_get_state_h take [N, 4].
+ * Step under action a (clamped into 0..1: 0 stick, 1 hit):
+ *   t > 21 (reachable only through an injected state): reward -1, terminated 1, nothing is drawn and the state is unchanged;
+ *   hit: c = card n; t += c; ace |= (c == 1); n' = min(n + 1, 2^24 - 1); t > 21: reward -1, terminated 1; otherwise reward 0, terminated 0;
+ *   stick: terminated 1.  The dealer's hand is (show, card 3): dt = show + card 3, dace = either of them is 1.  While dt + (dace && dt + 10 <= 21 ? 10 : 0)
+ *   < 17 the dealer draws card n, n + 1, ... (dt += c; dace |= (c == 1)).  Dealer's score = 0 if dt > 21, else that sum; player's score = sum; reward = +1, 0
+ *   or -1 as the player's score is above, equal to or below the dealer's.  n' = n + (cards the dealer drew), held at 2^24 - 1; the player's part of hand
+ *   stays.  k0 and k1 stay in every case.
+ *   The dealer draws at most 10 cards from any two-card start (the hard total rises by at least 1 per card; enumerated over all 100 (show, hidden) pairs), so
+ *   the device's loop has exactly that compile-time bound with a predicate and is never a `while` on data: no foreign state can spin a lane.
+ * Reset number k of global env e: w = philox4x32_10(seed; e, k, 0, 1) (MountainCar's keying); k0 = w.x >> 8, k1 = w.y >> 8; one more call (counter 0, tag
+ *   0x21) gives all four dealt cards: t = card 0 + card 1, ace = either is 1, show = card 2, n = 4.  Global env 0 takes reset 1 at ppo_env_reset;
+ *   PPO_BUF_RESET_COUNT counts them.
+ * Observation, obs_size 45: gymnasium's flattened Tuple(Discrete(32), Discrete(11), Discrete(2)) -- three one-hot groups of 0.0f / 1.0f: sum at [0..31],
+ *   32 + show at [32..42], 43 + usable at [43..44].  It holds neither n nor the key.
+ * An episode ends where the env terminates or its length reaches max_episode_steps (1..16 777 215): done = 1, FIN_LEN / FIN_REW written, auto-reset --
+ * ppo_env_step's bookkeeping.  Without a limit in the way an episode takes at most 20 steps.
+ * Memory safety, as for PPO_ENV_FROZENLAKE: ppo_env_set_state_h checks the host array -- hand must decode into t 2..31, ace 0..1, show 1..10 with no bits
+ * above (an integer in 0..703), n, k0, k1 must be integers in 0..2^24-1; a bad array returns PPO_ERR_INVALID and changes nothing; the device functions
+ * convert and clamp each component (a NaN becomes 0; hand into 0..703, then t into 2..31 and show into 1..10; n, k0, k1 into 0..2^24-1); a caller's i64
+ * action is saturated, not truncated.
+ * ppo_ctx_create accepts the env in exactly this form: dist_kind = PPO_DIST_CATEGORICAL (PPO_DIST_MASKED is refused: the env forms no mask), n_heads = 1,
+ * head_dims[0] = 2, obs_size = 45, hidden = 64, n_hidden = 2, PPO_DTYPE_F32, kernel_flags containing PPO_KERNEL_CAT_FUSED (required, never implied) and
+ * 1 <= max_episode_steps <= 16 777 215.  A wrong obs_size returns PPO_ERR_INVALID with the reference's obs-size message, anything else PPO_ERR_UNSUPPORTED
+ * with a message that names the limit.
+ * Calls: PPO_ENV_FROZENLAKE's list, with ppo_env_step's obs [N, 45] and ppo_env_transition(13, state [n, 4], action i64 [n], ...).  ppo_rollout is THREE
+ * launches (cat_rollout_kernel; LDS 79 808 bytes; `value` moves by 2, `act` by 0); a stepwise loop of ppo_policy_act(step_index = rollout_steps + t) and
+ * ppo_env_step reproduces every buffer it fills bit for bit (tests/test_gpu_blackjack.py).  ppo_evaluate is ONE launch (cat_eval_kernel) and moves no counter.
+ * Refused, changing nothing: PPO_ENV_FROZENLAKE's list -- ppo_host_* / ppo_dev_* (PPO_ERR_STATE); ppo_obs_norm_* and ppo_reward_norm_*
+ * (PPO_ERR_UNSUPPORTED); ppo_env_step_f32, ppo_rollout_f32, ppo_policy_act_f32 (PPO_ERR_UNSUPPORTED, naming the integer twin);
+ * ppo_env_truncation_bootstrap and ppo_env_truncations (PPO_ERR_UNSUPPORTED: the final observation of a cut-off episode depends on n and the key, which the
+ * stored observation does not hold).  Sharding is neither claimed nor tested. */
+enum { PPO_ENV_BLACKJACK = PPO_ENV_TAXI + 5 };   /* 13, not 12: value 12 stays unassigned, as 7 and 9 do; an enum of its own, written as a sum */
 /* PPO_DIST_CATEGORICAL reproduces Distributions/Categorical.cpp including its entropy clamp (:112-119);
  * PPO_DIST_MASKED reproduces Distributions/CategoricalMasked.cpp (true entropy, -1e8 masking).
  * PPO_DIST_GAUSSIAN (new; the reference has no continuous policy): a diagonal Gaussian over D = head_dims[0] real-valued actions (n_heads = 1,

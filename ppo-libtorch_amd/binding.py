@@ -21,6 +21,9 @@ ENV_TAXI = 8   # Taxi-v3 on the device: DIST_MASKED or DIST_CATEGORICAL, heads (
 # FrozenLake-v1 / FrozenLake8x8-v1 (slippery) on the device: DIST_CATEGORICAL, heads (4,), obs 16 / 64 (one-hot of the cell), state [4] = (cell, j, k0, k1) -- the
 # state carries the key the env's slip is drawn from; KERNEL_CAT_FUSED required
 ENV_FROZENLAKE, ENV_FROZENLAKE8X8 = 10, 11
+# Blackjack-v1 (infinite deck, natural = False, sab = False) on the device: DIST_CATEGORICAL, heads (2,), obs 45 (three one-hot groups), state [4] = (hand, n, k0,
+# k1) with hand = t + 32 * ace + 64 * show -- the state carries the key and the index of the next card; KERNEL_CAT_FUSED required
+ENV_BLACKJACK = 13
 ENV_MOUNTAINCAR_CONTINUOUS = 5   # MountainCarContinuous-v0 on the device, in the same one form; obs = state [2]; also env_truncation_bootstrap and evaluate
 MM_EPI_NONE, MM_EPI_BIAS, MM_EPI_BIAS_TANH, MM_EPI_DTANH = 0, 1, 2, 3
 MM_F32X3, MM_BF16 = 0, 1
@@ -246,8 +249,8 @@ class Context:
         self.A = sum(cfg.head_dims[i] for i in range(cfg.n_heads))
         self.B = self.T * self.N
         # width of the env state (Pendulum: theta, theta_dot behind 3 observations; Acrobot: two angles and two velocities behind 6; Taxi: 4 integers behind 19;
-        # FrozenLake: cell, step count and key behind 16 / 64)
-        self.S = 2 if cfg.env_kind == ENV_PENDULUM else (4 if cfg.env_kind in (ENV_ACROBOT, ENV_TAXI, ENV_FROZENLAKE, ENV_FROZENLAKE8X8) else self.O)
+        # FrozenLake: cell, step count and key behind 16 / 64; Blackjack: hand, card index and key behind 45)
+        self.S = 2 if cfg.env_kind == ENV_PENDULUM else (4 if cfg.env_kind in (ENV_ACROBOT, ENV_TAXI, ENV_FROZENLAKE, ENV_FROZENLAKE8X8, ENV_BLACKJACK) else self.O)
         self.P = int(lib().ppo_param_count(self.h))
 
     def close(self):
@@ -830,7 +833,7 @@ def gae_launch(ctx, d_rewards, d_values, d_dones, d_next_value, d_next_done, T, 
 
 
 def env_transition(ctx, env_kind, state, action):
-    """ppo_env_transition: state f32 [n,S] (S = 4 for ENV_CARTPOLE, ENV_ACROBOT, ENV_TAXI and both ENV_FROZENLAKE kinds, 2 for ENV_MOUNTAINCAR), action i64 [n].  Returns (next_state, reward,
+    """ppo_env_transition: state f32 [n,S] (S = 4 for ENV_CARTPOLE, ENV_ACROBOT, ENV_TAXI, both ENV_FROZENLAKE kinds and ENV_BLACKJACK, 2 for ENV_MOUNTAINCAR), action i64 [n].  Returns (next_state, reward,
     terminated).  The observation of an ENV_ACROBOT state is what ppo_env_set_state_h leaves in NEXT_OBS."""
     state = np.ascontiguousarray(state, np.float32)
     n, O = state.shape

@@ -585,7 +585,9 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
     // PPO_ENV_FROZENLAKE / PPO_ENV_FROZENLAKE8X8: the envs whose step draws random numbers, from a key the state carries; the 4x4 and the 8x8 map
     const bool frozenlake = cfg->env_kind == PPO_ENV_FROZENLAKE || cfg->env_kind == PPO_ENV_FROZENLAKE8X8;
     const int frozenlake_obs = cfg->env_kind == PPO_ENV_FROZENLAKE8X8 ? 64 : 16;
-    const bool cat_env = acrobot || taxi || frozenlake;
+    // PPO_ENV_BLACKJACK: the env whose step draws a variable number of cards, keyed like FrozenLake's slip by state words
+    const bool blackjack = cfg->env_kind == PPO_ENV_BLACKJACK;
+    const bool cat_env = acrobot || taxi || frozenlake || blackjack;
     // PPO_KERNEL_ENV_GENERIC on CartPole / MountainCar: the network lives in the generic engine's layout, with PPO_ENV_SYNTHETIC's limits (the flag anywhere
     // else is refused below, behind the checks of env_kind, dist_kind, compute_dtype and of the flag word itself)
     const bool env_generic = (cfg->kernel_flags & PPO_KERNEL_ENV_GENERIC) != 0 && (cfg->env_kind == PPO_ENV_CARTPOLE || cfg->env_kind == PPO_ENV_MOUNTAINCAR);
@@ -722,6 +724,25 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
                             "in f32, and it keys the env's draws); got %d", name, FROZENLAKE_WORD_MAX, cfg->max_episode_steps);
         }
     }
+    if (blackjack && cfg->obs_size == 45) {   // accepted in exactly one form (ppo_hip.h: PPO_ENV_BLACKJACK); a wrong obs_size first, with the reference's message (below)
+        if (cfg->dist_kind != PPO_DIST_CATEGORICAL)
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_BLACKJACK takes one of two discrete actions without a mask: it is built for dist_kind = "
+                        "PPO_DIST_CATEGORICAL; got dist_kind %d", cfg->dist_kind);
+        if (cfg->n_heads != 1 || cfg->head_dims[0] != 2)
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_BLACKJACK has one head of two actions (stick, hit): n_heads = 1 and head_dims[0] = 2; got "
+                        "n_heads = %d, head_dims[0] = %d", cfg->n_heads, cfg->head_dims[0]);
+        if (cfg->hidden != 64 || cfg->n_hidden != 2)
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_BLACKJACK is built for the 2 x 64 network (hidden = 64, n_hidden = 2) of the fused categorical "
+                        "kernels; got %d x %d", cfg->n_hidden, cfg->hidden);
+        if (cfg->compute_dtype != PPO_DTYPE_F32)
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_BLACKJACK is built for compute_dtype = PPO_DTYPE_F32; bf16 storage is not");
+        if (!cat_fused)
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_BLACKJACK needs PPO_KERNEL_CAT_FUSED in kernel_flags: its rollout exists on the fused categorical "
+                        "kernels only, and the flag is never implied (no other engine serves in its place)");
+        if (cfg->max_episode_steps < 1 || cfg->max_episode_steps > BLACKJACK_WORD_MAX)
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_BLACKJACK is built for 1 <= max_episode_steps <= %d (as on PPO_ENV_FROZENLAKE: the state's words "
+                        "are integers held exactly in f32); got %d", BLACKJACK_WORD_MAX, cfg->max_episode_steps);
+    }
     if (gauss && !host_env && !gauss_env)
         return fail(nullptr, PPO_ERR_UNSUPPORTED, "dist_kind = PPO_DIST_GAUSSIAN serves caller-stepped environments (env_kind = PPO_ENV_HOST), PPO_ENV_PENDULUM and "
                     "PPO_ENV_MOUNTAINCAR_CONTINUOUS: CartPole, MountainCar and the synthetic env take discrete actions; got env_kind %d", cfg->env_kind);
@@ -738,7 +759,7 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
             return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED serves dist_kind = PPO_DIST_CATEGORICAL and PPO_DIST_MASKED only; this context's policy is "
                         "PPO_DIST_GAUSSIAN (its twin is PPO_KERNEL_GAUSS_FUSED)");
         if (!host_env && !cat_env)
-            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED serves caller-stepped environments (env_kind = PPO_ENV_HOST), PPO_ENV_ACROBOT, PPO_ENV_TAXI and the two PPO_ENV_FROZENLAKE kinds only; got "
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED serves caller-stepped environments (env_kind = PPO_ENV_HOST), PPO_ENV_ACROBOT, PPO_ENV_TAXI, the two PPO_ENV_FROZENLAKE kinds and PPO_ENV_BLACKJACK only; got "
                         "env_kind %d", cfg->env_kind);
         if (cfg->hidden != 64) return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED is built for hidden = 64; got hidden = %d", cfg->hidden);
         if (cfg->n_hidden != 2) return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED is built for n_hidden = 2; got n_hidden = %d", cfg->n_hidden);
@@ -750,7 +771,7 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
     if (cfg->compute_dtype == PPO_DTYPE_BF16 && !generic)
         return fail(nullptr, PPO_ERR_UNSUPPORTED, "compute_dtype = PPO_DTYPE_BF16 applies to networks whose layers are GEMMs (env_kind = PPO_ENV_SYNTHETIC); the reference's "
                     "2 x 64 networks always compute in f32");
-    const int env_obs = cfg->env_kind == PPO_ENV_CARTPOLE ? 4 : (cfg->env_kind == PPO_ENV_MOUNTAINCAR || mcc ? 2 : (pendulum ? 3 : (acrobot ? 6 : (taxi ? 19 : (frozenlake ? frozenlake_obs : cfg->obs_size)))));   // host / synthetic: no check
+    const int env_obs = cfg->env_kind == PPO_ENV_CARTPOLE ? 4 : (cfg->env_kind == PPO_ENV_MOUNTAINCAR || mcc ? 2 : (pendulum ? 3 : (acrobot ? 6 : (taxi ? 19 : (frozenlake ? frozenlake_obs : (blackjack ? 45 : cfg->obs_size))))));   // host / synthetic: no check
     if (cfg->obs_size != env_obs) {
         // the reference's runtime check in initEnvs (PPO_Discrete.cpp:370-375), same wording
         return fail(nullptr, PPO_ERR_INVALID,
@@ -1437,7 +1458,7 @@ extern "C" ppo_status ppo_categorical_sample(const float* m_probs, int64_t n, in
 extern "C" ppo_status ppo_env_transition(int32_t env_kind, const float* state_in, const int64_t* action, int64_t n, float* next_state,
                                          float* reward, int32_t* terminated, void* stream) {
     if (!state_in || !action || !next_state || !reward || !terminated || n < 0) return PPO_ERR_INVALID;
-    if (cat_fused_env_serves(env_kind))   // PPO_ENV_ACROBOT, PPO_ENV_TAXI, PPO_ENV_FROZENLAKE, PPO_ENV_FROZENLAKE8X8: state [n, 4]
+    if (cat_fused_env_serves(env_kind))   // PPO_ENV_ACROBOT, PPO_ENV_TAXI, PPO_ENV_FROZENLAKE, PPO_ENV_FROZENLAKE8X8, PPO_ENV_BLACKJACK: state [n, 4]
         return launch_cat_env_transition(env_kind, state_in, action, n, next_state, reward, terminated, (hipStream_t)stream) == hipSuccess ? PPO_OK : PPO_ERR_HIP;
     return launch_env_transition(env_kind, state_in, action, n, next_state, reward, terminated, (hipStream_t)stream) == hipSuccess ? PPO_OK : PPO_ERR_HIP;
 }
@@ -1460,7 +1481,8 @@ static inline bool is_taxi(const ppo_ctx* c) { return c->cfg.env_kind == PPO_ENV
 // the device envs with integer actions: the envs of the fused categorical rollout (gauss_fused.hpp)
 static inline bool is_frozenlake(const ppo_ctx* c) { return c->cfg.env_kind == PPO_ENV_FROZENLAKE || c->cfg.env_kind == PPO_ENV_FROZENLAKE8X8; }
 static inline int frozenlake_cells(const ppo_ctx* c) { return c->cfg.env_kind == PPO_ENV_FROZENLAKE8X8 ? 64 : 16; }
-static inline bool is_cat_env(const ppo_ctx* c) { return is_acrobot(c) || is_taxi(c) || is_frozenlake(c); }
+static inline bool is_blackjack(const ppo_ctx* c) { return c->cfg.env_kind == PPO_ENV_BLACKJACK; }
+static inline bool is_cat_env(const ppo_ctx* c) { return is_acrobot(c) || is_taxi(c) || is_frozenlake(c) || is_blackjack(c); }
 static inline const char* gauss_env_name(const ppo_ctx* c) { return is_mcc(c) ? "PPO_ENV_MOUNTAINCAR_CONTINUOUS" : "PPO_ENV_PENDULUM"; }
 
 extern "C" ppo_status ppo_env_transition_f32(int32_t env_kind, const float* state_in, const float* action, int64_t n, float* next_state, float* obs_out,
@@ -1553,6 +1575,18 @@ extern "C" ppo_status ppo_env_set_state_h(ppo_ctx* c, const float* state_h, cons
             if (!(v >= 0.0f && v <= hi[i & 3] && v == (float)(int)v))
                 return fail(c, PPO_ERR_INVALID, "ppo_env_set_state_h: state[%lld][%d] = %g is not an integer in 0..%d (PPO_ENV_FROZENLAKE: cell in 0..%d; j, k0, k1 in "
                             "0..%d); nothing was changed", (long long)(i >> 2), (int)(i & 3), (double)v, (int)hi[i & 3], frozenlake_cells(c) - 1, FROZENLAKE_WORD_MAX);
+        }
+    }
+    if (state_h && is_blackjack(c)) {   // a Blackjack state is four integers (hand = t + 32 * ace + 64 * show; n, k0, k1 in 0..2^24-1): checked here, on the host array
+        for (int64_t i = 0; i < (int64_t)c->N * 4; i++) {
+            const float v = state_h[i];
+            const int hi = (i & 3) == 0 ? BLACKJACK_HAND_MAX : BLACKJACK_WORD_MAX;
+            bool ok = v >= 0.0f && v <= (float)hi && v == (float)(int)v;
+            if (ok && (i & 3) == 0) ok = ((int)v & 31) >= 2 && ((int)v >> 6) >= 1;   // t in 2..31, show in 1..10; no bits above: v <= 703
+            if (!ok)
+                return fail(c, PPO_ERR_INVALID, "ppo_env_set_state_h: state[%lld][%d] = %g is not an integer of its range (PPO_ENV_BLACKJACK: hand = t + 32 * ace + "
+                            "64 * show with t in 2..31, ace in 0..1, show in 1..10; n, k0, k1 in 0..%d); nothing was changed", (long long)(i >> 2), (int)(i & 3),
+                            (double)v, BLACKJACK_WORD_MAX);
         }
     }
     if (state_h) {
@@ -1961,7 +1995,7 @@ extern "C" ppo_status ppo_evaluate(ppo_ctx* c, int64_t n_episodes, int64_t seed,
     NEED(c, n_episodes > 0, "ppo_evaluate: n_episodes <= 0");
     NEED(c, n_episodes < (1ll << 28), "ppo_evaluate: more than 2^28 episodes");
     NEED(c, c->cfg.max_episode_steps > 0, "ppo_evaluate: max_episode_steps <= 0 (an episode would never be truncated)");
-    NEED(c, c->O == (c->cfg.env_kind == PPO_ENV_CARTPOLE ? 4 : (cat_env ? (is_taxi(c) ? 19 : (is_frozenlake(c) ? frozenlake_cells(c) : 6)) : 2)), "ppo_evaluate: obs_size does not match the environment");
+    NEED(c, c->O == (c->cfg.env_kind == PPO_ENV_CARTPOLE ? 4 : (cat_env ? (is_taxi(c) ? 19 : (is_frozenlake(c) ? frozenlake_cells(c) : (is_blackjack(c) ? 45 : 6))) : 2)), "ppo_evaluate: obs_size does not match the environment");
     DeviceGuard dev_guard(c);
     ppo_status s = eval_scratch(c, n_episodes, seed);
     if (s != PPO_OK) return s;
@@ -3365,6 +3399,10 @@ static ppo_status envt_state(ppo_ctx* c, const char* what) {
     if (is_frozenlake(c))
         return fail(c, PPO_ERR_UNSUPPORTED, "%s: the fold rebuilds the final observation of a cut-off episode from PPO_BUF_OBS, and a PPO_ENV_FROZENLAKE observation "
                                             "(the one-hot of the cell) holds neither the step count nor the key the env's slip is drawn from: not built for this env", what);
+    if (is_blackjack(c))
+        return fail(c, PPO_ERR_UNSUPPORTED, "%s: the fold rebuilds the final observation of a cut-off episode from PPO_BUF_OBS, and a PPO_ENV_BLACKJACK observation "
+                                            "(the player's sum, the dealer's showing card, the usable ace) holds neither the card count nor the key the env's cards are "
+                                            "drawn from: not built for this env", what);
     if (is_mcc(c)) return PPO_OK;   // its observation is its state: the fold runs on the fused Gaussian critic (gauss_env_fold_truncations)
     if (is_taxi(c)) return PPO_OK;  // its observation holds its state (four one-hot groups): the fold decodes it (cat_env_fold_truncations)
     if (c->env_generic)

@@ -119,6 +119,8 @@ hipError_t cat_fused_rollout(int env_kind, int dist_kind, const GenLayout& L, co
 // it also has the time-limit fold (ppo_env_truncation_bootstrap): GaussFoldArgs' contract with i32 actions [B, 1], on cat_trunc_fold_kernel.
 // PPO_ENV_FROZENLAKE / PPO_ENV_FROZENLAKE8X8 (CatEnvFrozenLake<4>, <8>) are the envs of this family whose step draws random numbers; the key and the count of
 // the draw are words of the env state, so every entry point below serves them through the same arguments.  Their observation does not hold the state: no fold.
+// PPO_ENV_BLACKJACK (CatEnvBlackjack) rides on the same mechanism with a number of draws per step that depends on the data (a hit one card, a stick the dealer's
+// play-out, a reset the deal); no fold either.
 bool cat_fused_env_folds(int env_kind);
 struct CatFoldArgs {
     const float* params;

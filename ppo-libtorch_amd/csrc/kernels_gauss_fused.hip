@@ -34,6 +34,9 @@
 // and the step count of the draw are state words (ppo_internal.hpp), so Env::step(st, a) is as pure here as Taxi's and the kernels did not change for it.  What
 // did is the observation width, 16 and 64: gf_carve(16, 4) = 15 728 floats = 62 912 bytes, two workgroups per CU; gf_carve(64, 4) = 22 064 floats =
 // 88 256 bytes, above 64 KB (the attribute is asked for) and ONE workgroup per CU of 160 KB -- arithmetic, not a measurement.
+// PPO_ENV_BLACKJACK (CatEnvBlackjack) instantiates them for an env whose step draws a NUMBER of cards that depends on the data: a hit one, a stick the dealer's
+// play-out of up to ten, a reset four.  Again no trait says so and the kernels did not change: the draws are inside Env::step / Env::reset, keyed by state
+// words, and the dealer's loop has a compile-time bound.  gf_carve(48, 4) = 19 952 floats = 79 808 bytes: the attribute, and two workgroups per CU still fit.
 //
 // Caller-stepped contexts of either family fold time-limit truncations per step in gauss_dev_fold_kernel (ppo_dev_observe with flags): the critic kernel's
 // forward on the flagged rows of the step, found on the device.
@@ -1111,6 +1114,9 @@ __global__ __launch_bounds__(GF_THREADS) void gauss_eval_kernel(GfEvalArgs a) {
 // Philox call keyed by the state's own words (k0, k1) at counter (j >> 2, 0, 0, 0x20), every step -- the definition's bits by construction, since it IS the
 // definition the stand-alone step and the stateless transition run.  Waves 1 .. 3 store the step's observation rows from the X image as on the other envs: at
 // OBS 64 that is 16 KB per workgroup and step.
+// PPO_ENV_BLACKJACK (OBS 45, 2 logits, HOT 3): gf_carve(48, 4) = 79 808 bytes (the attribute).  What differs between the lanes of wave 0 here is the WORK of a
+// step: a hit is one Philox call, a stick the call of the hidden card, the dealer's (one more, seldom two) and the two of the reset that follows -- lanes that
+// hit wait for lanes that stick, the wave pays the longest lane's path each step.
 // ---------------------------------------------------------------------------------------------------------
 struct CfRolloutArgs {
     GfShape sh;
@@ -1354,7 +1360,7 @@ __global__ void cat_env_obs_kernel(int N, const float* __restrict__ state, float
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// cat_eval_kernel<Env, DIST> (ppo_evaluate on PPO_ENV_ACROBOT, PPO_ENV_TAXI, PPO_ENV_FROZENLAKE, PPO_ENV_FROZENLAKE8X8): gauss_eval_kernel's plan with a categorical head.  A workgroup owns 64 episodes for their whole
+// cat_eval_kernel<Env, DIST> (ppo_evaluate on PPO_ENV_ACROBOT, PPO_ENV_TAXI, PPO_ENV_FROZENLAKE, PPO_ENV_FROZENLAKE8X8, PPO_ENV_BLACKJACK): gauss_eval_kernel's plan with a categorical head.  A workgroup owns 64 episodes for their whole
 // length with the actor's weights resident: lane l of wave 0 keeps episode 64 b + l (state, return, length) in registers -- the STATE, not the observation:
 // nothing here needs an observation to be a state -- writes its observation into the X image, every thread runs gf_forward_tile, and wave 0 takes the
 // first-index argmax of the probabilities (greedy: ppo_policy_act_greedy's) or the draw keyed (seed, episode, step of the episode, head 0) --
@@ -1362,6 +1368,7 @@ __global__ void cat_env_obs_kernel(int N, const float* __restrict__ state, float
 // row-index words, the step's closing barrier hands it to the other waves (gauss_eval_kernel).  At most max_episode_steps steps.
 // PPO_ENV_TAXI under PPO_DIST_MASKED: the same widening and the same masked head as cat_rollout_kernel; greedy is the first-index argmax of the MASKED
 // probabilities (a masked-out action has probability 0 and is never chosen: an allowed one has a positive probability, and the comparison is strict).
+// PPO_ENV_BLACKJACK: the rollout's carve (79 808 bytes); an episode's cards come from the key its reset drew from (seed, e), as FrozenLake's slips do.
 // PPO_ENV_FROZENLAKE / PPO_ENV_FROZENLAKE8X8: the rollout's carves (62 912 and 88 256 bytes).  Episode e's slips come from the key its reset drew from (seed, e)
 // and from its own step count, both in the lane's state: the episode is a pure function of (parameters, seed, e), whatever its neighbours do.
 // ---------------------------------------------------------------------------------------------------------
@@ -1787,7 +1794,7 @@ hipError_t gauss_fused_evaluate(int env_kind, const GenLayout& L, const GaussEva
     return hipGetLastError();
 }
 
-// ---- the device envs with integer actions (PPO_ENV_ACROBOT, PPO_ENV_TAXI, PPO_ENV_FROZENLAKE, PPO_ENV_FROZENLAKE8X8; the context's shape is fixed by ppo_ctx_create: obs Env::OBS, one head of
+// ---- the device envs with integer actions (PPO_ENV_ACROBOT, PPO_ENV_TAXI, PPO_ENV_FROZENLAKE, PPO_ENV_FROZENLAKE8X8, PPO_ENV_BLACKJACK; the context's shape is fixed by ppo_ctx_create: obs Env::OBS, one head of
 // Env::ACTIONS logits) ----
 template <class F>
 static hipError_t cat_env_dispatch(int env_kind, F f) {
@@ -1795,6 +1802,7 @@ static hipError_t cat_env_dispatch(int env_kind, F f) {
     if (env_kind == PPO_ENV_TAXI) return f(CatEnvTaxi{});
     if (env_kind == PPO_ENV_FROZENLAKE) return f(CatEnvFrozenLake<4>{});
     if (env_kind == PPO_ENV_FROZENLAKE8X8) return f(CatEnvFrozenLake<8>{});
+    if (env_kind == PPO_ENV_BLACKJACK) return f(CatEnvBlackjack{});
     return hipErrorInvalidValue;
 }
 template <class Env>
@@ -1806,10 +1814,11 @@ template <class Env>
 static int cat_env_lds_bytes() { return gf_lds_floats(gf_pad4(Env::OBS), gf_pad4(Env::ACTIONS)) * 4; }
 
 bool cat_fused_env_serves(int env_kind) {
-    return env_kind == PPO_ENV_ACROBOT || env_kind == PPO_ENV_TAXI || env_kind == PPO_ENV_FROZENLAKE || env_kind == PPO_ENV_FROZENLAKE8X8;
+    return env_kind == PPO_ENV_ACROBOT || env_kind == PPO_ENV_TAXI || env_kind == PPO_ENV_FROZENLAKE || env_kind == PPO_ENV_FROZENLAKE8X8 ||
+           env_kind == PPO_ENV_BLACKJACK;
 }
 
-// cat_rollout_kernel<Env, DIST> for the context's distribution; the attribute where the carve passes 64 KB (PPO_ENV_TAXI: 67 136 bytes; PPO_ENV_FROZENLAKE8X8: 88 256)
+// cat_rollout_kernel<Env, DIST> for the context's distribution; the attribute where the carve passes 64 KB (PPO_ENV_TAXI: 67 136 bytes; PPO_ENV_FROZENLAKE8X8: 88 256; PPO_ENV_BLACKJACK: 79 808)
 template <class Env, int DIST>
 static hipError_t cat_rollout_launch(const CfRolloutArgs& a, int N, hipStream_t s) {
     const int bytes = cat_env_lds_bytes<Env>();

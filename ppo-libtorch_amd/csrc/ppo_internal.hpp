@@ -707,6 +707,130 @@ struct CatEnvFrozenLake {
     }
 };
 
+// Blackjack-v1 (gymnasium's toy_text/blackjack.py, natural = False, sab = False, the infinite deck; no reference counterpart: PPO_ENV_BLACKJACK; ppo_hip.h
+// states the cards and the step).  FrozenLake's mechanism with a NUMBER OF DRAWS THAT DEPENDS ON THE DATA: st = {hand, n, k0, k1}, integers held exactly in
+// f32 -- hand = t + 32 * ace + 64 * show (t the player's total with aces as 1, ace whether the player holds one, show the dealer's showing card), n the index
+// of the next card, (k0, k1) the episode's 2 x 24-bit key.  Card i of an episode is word i & 3 of philox4x32_10(key = (k0, k1); counter = (i >> 2, 0, 0,
+// 0x21)): a hit draws card n, a stick plays the dealer out from (show, card 3) with cards n, n + 1, ..  The step stays a pure function of (state, action).
+// Every function converts and clamps each component into its range first (a NaN becomes 0), so a foreign state can index nothing outside the observation,
+// and the dealer's loop has a compile-time bound with a predicate: no state can spin a lane.
+constexpr int BLACKJACK_WORD_MAX = (1 << 24) - 1;         // n, k0 and k1 are at most this: every integer up to it is an f32
+constexpr int BLACKJACK_HAND_MAX = 31 + 32 + 64 * 10;     // 703: the largest hand word
+constexpr uint32_t BLACKJACK_CARD_TAG = 0x21u;            // the Philox counter word that names this draw (no other draw of the library uses it)
+constexpr int BLACKJACK_DEALER_DRAWS = 10;                // the most cards a dealer draws from any two-card start (enumerated in tests/test_blackjack_cpu.py)
+struct BlackjackHand { int t, ace, show; };
+__device__ __forceinline__ int blackjack_clamp(float v, int hi) { return v >= 0.0f ? (v >= (float)hi ? hi : (int)v) : 0; }
+// the hand word clamped into 0..703, then its fields: t into 2..31, show into 1..10 (703 >> 6 = 10)
+__device__ __forceinline__ BlackjackHand blackjack_hand(const float* st) {
+    const int h = blackjack_clamp(st[0], BLACKJACK_HAND_MAX);
+    const int t = h & 31, show = h >> 6;
+    return BlackjackHand{ t < 2 ? 2 : t, (h >> 5) & 1, show < 1 ? 1 : show };
+}
+__device__ __forceinline__ int blackjack_usable(const BlackjackHand& h) { return (h.ace && h.t + 10 <= 21) ? 1 : 0; }
+// gym's deck [1..10, 10, 10, 10]: thirteen equal buckets of a word, the last four are tens
+__device__ __forceinline__ int blackjack_card(uint32_t word) {
+    const int c = 1 + (int)(((uint64_t)word * 13u) >> 32);
+    return c < 10 ? c : 10;
+}
+// the four words of one Philox call are kept while consecutive card indices share i >> 2 (blk = ~0: nothing kept; a card index is below 2^24 + 10)
+struct BlackjackDeck { uint32_t k0, k1, blk; uint4 w; };
+__device__ __forceinline__ int blackjack_draw(BlackjackDeck& d, uint32_t i) {
+    if ((i >> 2) != d.blk) {
+        d.blk = i >> 2;
+        d.w = philox4x32_10(d.k0, d.k1, d.blk, 0u, 0u, BLACKJACK_CARD_TAG);
+    }
+    return blackjack_card((i & 3) == 0 ? d.w.x : ((i & 3) == 1 ? d.w.y : ((i & 3) == 2 ? d.w.z : d.w.w)));
+}
+__device__ __forceinline__ float blackjack_step(float* st, int action, int& terminated) {
+    BlackjackHand h = blackjack_hand(st);
+    const int n = blackjack_clamp(st[1], BLACKJACK_WORD_MAX), k0 = blackjack_clamp(st[2], BLACKJACK_WORD_MAX), k1 = blackjack_clamp(st[3], BLACKJACK_WORD_MAX);
+    const int a = action < 0 ? 0 : (action > 1 ? 1 : action);
+    uint32_t next = (uint32_t)n;
+    float reward = -1.0f;
+    terminated = 1;
+    if (h.t <= 21) {   // a bust hand is reachable through an injected state only: nothing is drawn, the state stays
+        BlackjackDeck deck{ (uint32_t)k0, (uint32_t)k1, ~0u, uint4{ 0u, 0u, 0u, 0u } };
+        if (a == 1) {   // hit
+            const int c = blackjack_draw(deck, next++);
+            h.t += c;
+            h.ace |= c == 1 ? 1 : 0;
+            terminated = h.t > 21 ? 1 : 0;
+            reward = h.t > 21 ? -1.0f : 0.0f;
+        } else {        // stick: the dealer plays out from (show, card 3)
+            const int hidden = blackjack_draw(deck, 3u);
+            int dt = h.show + hidden, dace = (h.show == 1 || hidden == 1) ? 1 : 0;
+#pragma unroll 1
+            for (int d = 0; d < BLACKJACK_DEALER_DRAWS; d++) {
+                if (dt + ((dace && dt + 10 <= 21) ? 10 : 0) < 17) {
+                    const int c = blackjack_draw(deck, next++);
+                    dt += c;
+                    dace |= c == 1 ? 1 : 0;
+                }
+            }
+            const int dealer = dt > 21 ? 0 : dt + ((dace && dt + 10 <= 21) ? 10 : 0);
+            const int player = h.t + 10 * blackjack_usable(h);
+            reward = player > dealer ? 1.0f : (player == dealer ? 0.0f : -1.0f);
+        }
+    }
+    st[0] = (float)(h.t + 32 * h.ace + 64 * h.show);
+    st[1] = (float)(next < (uint32_t)BLACKJACK_WORD_MAX ? (int)next : BLACKJACK_WORD_MAX);
+    st[2] = (float)k0;
+    st[3] = (float)k1;
+    return reward;
+}
+// reset number k of global env e: MountainCar's keying, philox(seed; e, k, 0, 1) gives the episode's key; the key's first call deals cards 0 .. 3
+__device__ __forceinline__ void blackjack_reset(float* st, int k, int64_t seed, int64_t env_global) {
+    const uint4 w = philox4x32_10((uint32_t)seed, (uint32_t)((uint64_t)seed >> 32), (uint32_t)env_global, (uint32_t)k, 0u, 1u);
+    const uint32_t k0 = w.x >> 8, k1 = w.y >> 8;
+    const uint4 c = philox4x32_10(k0, k1, 0u, 0u, 0u, BLACKJACK_CARD_TAG);
+    const int c0 = blackjack_card(c.x), c1 = blackjack_card(c.y), show = blackjack_card(c.z);
+    st[0] = (float)(c0 + c1 + ((c0 == 1 || c1 == 1) ? 32 : 0) + 64 * show);
+    st[1] = 4.0f;
+    st[2] = (float)k0;
+    st[3] = (float)k1;
+}
+// The fourth kind of device env with integer actions (PPO_ENV_BLACKJACK).  The observation is gymnasium's flattened Tuple(Discrete(32), Discrete(11),
+// Discrete(2)): three ones over zeros (OBS_ONE_HOT, HOT 3) at sum, 32 + show and 43 + usable; it holds neither n nor the key (no STATE_FROM_OBS, no fold).
+struct CatEnvBlackjack {
+    static constexpr int OBS = 45, STATE = 4, ACTIONS = 2, HOT = 3;
+    static constexpr bool OBS_IS_STATE = false;
+    static constexpr bool HAS_MASK = false;
+    static constexpr bool STATE_FROM_OBS = false;
+    static constexpr bool OBS_ONE_HOT = true;
+    __device__ static __forceinline__ void hot(const float* st, int* rows) {
+        const BlackjackHand h = blackjack_hand(st);
+        const int u = blackjack_usable(h);
+        rows[0] = h.t + 10 * u; rows[1] = 32 + h.show; rows[2] = 43 + u;
+    }
+    __device__ static __forceinline__ void obs(const float* st, float* ob) {
+        int rows[3];
+        hot(st, rows);
+#pragma unroll
+        for (int k = 0; k < OBS; k++) ob[k] = (k == rows[0] || k == rows[1] || k == rows[2]) ? 1.0f : 0.0f;
+    }
+    __device__ static __forceinline__ float step(float* st, int a, int& terminated) { return blackjack_step(st, a, terminated); }
+    __device__ static __forceinline__ void reset(float* st, int k, int64_t seed, int64_t env_global) { blackjack_reset(st, k, seed, env_global); }
+    // env_step_kernel's bookkeeping, as acrobot_step_episode
+    __device__ static __forceinline__ float step_episode(float* st, int a, int max_episode_steps, int64_t seed, int64_t env_global, int& ep_len, float& ep_rew,
+                                                         int& resets, int& done, int& fin_len, float& fin_rew) {
+        int term;
+        const float r = blackjack_step(st, a, term);
+        ep_len += 1;
+        ep_rew += r;
+        done = (term || ep_len == max_episode_steps) ? 1 : 0;
+        fin_len = 0;
+        fin_rew = 0.0f;
+        if (done) {
+            fin_len = ep_len;
+            fin_rew = ep_rew;
+            blackjack_reset(st, resets++, seed, env_global);
+            ep_len = 0;
+            ep_rew = 0.0f;
+        }
+        return r;
+    }
+};
+
 template <int ENV>
 __device__ __forceinline__ float env_step(float* st, int action, int& terminated) {
     if constexpr (ENV == PPO_ENV_CARTPOLE) return cartpole_step(st, action, terminated);
