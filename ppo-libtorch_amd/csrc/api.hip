@@ -202,6 +202,8 @@ struct ppo_ctx {
     bool cat_fused = false;
     // PPO_KERNEL_ENV_GENERIC: CartPole / MountainCar (their own env kernels, state layout and reset table) under a network in the generic engine's layout
     bool env_generic = false;
+    // a device env of the fused families: its row (gauss_fused.hpp: FusedEnvInfo), looked up once by ppo_ctx_create; null on every other env
+    const FusedEnvInfo* env = nullptr;
     int64_t gf_launches[3] = { 0, 0, 0 };
     float* gf_slab = nullptr;
     unsigned long long* stamps = nullptr;  // [2][12] phase cycles of the diagnostic kernel variant
@@ -570,24 +572,10 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
     const bool cat_fused = (cfg->kernel_flags & PPO_KERNEL_CAT_FUSED) != 0;
     const bool host_ref = host_env && !gauss && !cat_fused && cfg->hidden == PPO_HIDDEN && cfg->n_hidden == 2 && cfg->compute_dtype == PPO_DTYPE_F32 &&
                           (cfg->obs_size == 2 || cfg->obs_size == 4 || cfg->obs_size == 8);
-    // PPO_ENV_PENDULUM: the device env of the fused Gaussian kernels; the network lives in the generic engine's layout (GenericCtx), as a PPO_ENV_HOST
-    // context with PPO_KERNEL_GAUSS_FUSED does, and only the rollout differs (gauss_rollout_kernel)
-    const bool pendulum = cfg->env_kind == PPO_ENV_PENDULUM;
-    // PPO_ENV_MOUNTAINCAR_CONTINUOUS: the second such env, the same kernels instantiated for it (its observation is its state: it also has the truncation fold
-    // and the evaluation launch)
-    const bool mcc = cfg->env_kind == PPO_ENV_MOUNTAINCAR_CONTINUOUS;
-    const bool gauss_env = pendulum || mcc;
-    // PPO_ENV_ACROBOT: the device env of the fused categorical kernels (cat_rollout_kernel); the network lives in the generic engine's layout, as a
-    // PPO_ENV_HOST context with PPO_KERNEL_CAT_FUSED does
-    const bool acrobot = cfg->env_kind == PPO_ENV_ACROBOT;
-    // PPO_ENV_TAXI: the second such env, the same kernels instantiated for it; the one env that forms a mask, so it takes PPO_DIST_MASKED as well
-    const bool taxi = cfg->env_kind == PPO_ENV_TAXI;
-    // PPO_ENV_FROZENLAKE / PPO_ENV_FROZENLAKE8X8: the envs whose step draws random numbers, from a key the state carries; the 4x4 and the 8x8 map
-    const bool frozenlake = cfg->env_kind == PPO_ENV_FROZENLAKE || cfg->env_kind == PPO_ENV_FROZENLAKE8X8;
-    const int frozenlake_obs = cfg->env_kind == PPO_ENV_FROZENLAKE8X8 ? 64 : 16;
-    // PPO_ENV_BLACKJACK: the env whose step draws a variable number of cards, keyed like FrozenLake's slip by state words
-    const bool blackjack = cfg->env_kind == PPO_ENV_BLACKJACK;
-    const bool cat_env = acrobot || taxi || frozenlake || blackjack;
+    // a device env of the fused 2 x 64 kernel families (gauss_fused.hpp: FusedEnvInfo): the network lives in the generic engine's layout (GenericCtx), as a
+    // PPO_ENV_HOST context with the family's flag does, and only the rollout differs (gauss_rollout_kernel / cat_rollout_kernel)
+    const FusedEnvInfo* env = fused_env_info(cfg->env_kind);
+    const bool gauss_env = env && env->family == FUSED_GAUSS, cat_env = env && env->family == FUSED_CAT;
     // PPO_KERNEL_ENV_GENERIC on CartPole / MountainCar: the network lives in the generic engine's layout, with PPO_ENV_SYNTHETIC's limits (the flag anywhere
     // else is refused below, behind the checks of env_kind, dist_kind, compute_dtype and of the flag word itself)
     const bool env_generic = (cfg->kernel_flags & PPO_KERNEL_ENV_GENERIC) != 0 && (cfg->env_kind == PPO_ENV_CARTPOLE || cfg->env_kind == PPO_ENV_MOUNTAINCAR);
@@ -618,134 +606,33 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
             return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_ENV_GENERIC serves dist_kind = PPO_DIST_CATEGORICAL and PPO_DIST_MASKED only: CartPole and MountainCar take "
                         "discrete actions; got PPO_DIST_GAUSSIAN");
     }
-    if (pendulum) {   // accepted in exactly one form (ppo_hip.h: PPO_ENV_PENDULUM); a wrong obs_size first, with the reference's message (below)
-        if (cfg->obs_size == 3) {
-            if (!gauss)
-                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_PENDULUM takes one real-valued action: it is built for dist_kind = PPO_DIST_GAUSSIAN; got "
-                            "dist_kind %d", cfg->dist_kind);
-            if (cfg->n_heads != 1 || cfg->head_dims[0] != 1)
-                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_PENDULUM has one action dimension, the torque: n_heads = 1 and head_dims[0] = 1; got "
-                            "n_heads = %d, head_dims[0] = %d", cfg->n_heads, cfg->head_dims[0]);
-            if (cfg->hidden != 64 || cfg->n_hidden != 2)
-                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_PENDULUM is built for the 2 x 64 network (hidden = 64, n_hidden = 2) of the fused Gaussian "
-                            "kernels; got %d x %d", cfg->n_hidden, cfg->hidden);
-            if (cfg->compute_dtype != PPO_DTYPE_F32)
-                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_PENDULUM is built for compute_dtype = PPO_DTYPE_F32; bf16 storage is not");
-            if (!(cfg->kernel_flags & PPO_KERNEL_GAUSS_FUSED))
-                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_PENDULUM needs PPO_KERNEL_GAUSS_FUSED in kernel_flags: its rollout exists on the fused Gaussian "
-                            "kernels only, and the flag is never implied (no other engine serves in its place)");
-            if (cfg->max_episode_steps < 1 || cfg->max_episode_steps > PENDULUM_MAX_EPISODE_STEPS)
-                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_PENDULUM is built for 1 <= max_episode_steps <= %d (the angle is not wrapped and the device "
-                            "sinf / cosf hold for |theta| < 120); got %d", PENDULUM_MAX_EPISODE_STEPS, cfg->max_episode_steps);
-        }
-    }
-    if (mcc) {   // accepted in exactly one form (ppo_hip.h: PPO_ENV_MOUNTAINCAR_CONTINUOUS); a wrong obs_size first, with the reference's message (below)
-        if (cfg->obs_size == 2) {
-            if (!gauss)
-                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_MOUNTAINCAR_CONTINUOUS takes one real-valued action: it is built for dist_kind = PPO_DIST_GAUSSIAN; "
-                            "got dist_kind %d", cfg->dist_kind);
-            if (cfg->n_heads != 1 || cfg->head_dims[0] != 1)
-                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_MOUNTAINCAR_CONTINUOUS has one action dimension, the force: n_heads = 1 and head_dims[0] = 1; got "
-                            "n_heads = %d, head_dims[0] = %d", cfg->n_heads, cfg->head_dims[0]);
-            if (cfg->hidden != 64 || cfg->n_hidden != 2)
-                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_MOUNTAINCAR_CONTINUOUS is built for the 2 x 64 network (hidden = 64, n_hidden = 2) of the fused "
-                            "Gaussian kernels; got %d x %d", cfg->n_hidden, cfg->hidden);
-            if (cfg->compute_dtype != PPO_DTYPE_F32)
-                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_MOUNTAINCAR_CONTINUOUS is built for compute_dtype = PPO_DTYPE_F32; bf16 storage is not");
-            if (!(cfg->kernel_flags & PPO_KERNEL_GAUSS_FUSED))
-                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_MOUNTAINCAR_CONTINUOUS needs PPO_KERNEL_GAUSS_FUSED in kernel_flags: its rollout exists on the fused "
-                            "Gaussian kernels only, and the flag is never implied (no other engine serves in its place)");
-            if (cfg->max_episode_steps < 1)
-                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_MOUNTAINCAR_CONTINUOUS is built for max_episode_steps >= 1 (an episode that never reaches the goal "
-                            "ends at the time limit only); got %d", cfg->max_episode_steps);
-        }
-    }
-    if (acrobot) {   // accepted in exactly one form (ppo_hip.h: PPO_ENV_ACROBOT); a wrong obs_size first, with the reference's message (below)
-        if (cfg->obs_size == 6) {
-            if (cfg->dist_kind != PPO_DIST_CATEGORICAL)
-                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_ACROBOT takes one of three discrete actions without a mask: it is built for dist_kind = "
-                            "PPO_DIST_CATEGORICAL; got dist_kind %d", cfg->dist_kind);
-            if (cfg->n_heads != 1 || cfg->head_dims[0] != 3)
-                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_ACROBOT has one head of three actions, the torque -1, 0 or +1: n_heads = 1 and head_dims[0] = 3; got "
-                            "n_heads = %d, head_dims[0] = %d", cfg->n_heads, cfg->head_dims[0]);
-            if (cfg->hidden != 64 || cfg->n_hidden != 2)
-                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_ACROBOT is built for the 2 x 64 network (hidden = 64, n_hidden = 2) of the fused categorical "
-                            "kernels; got %d x %d", cfg->n_hidden, cfg->hidden);
-            if (cfg->compute_dtype != PPO_DTYPE_F32)
-                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_ACROBOT is built for compute_dtype = PPO_DTYPE_F32; bf16 storage is not");
-            if (!cat_fused)
-                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_ACROBOT needs PPO_KERNEL_CAT_FUSED in kernel_flags: its rollout exists on the fused categorical "
-                            "kernels only, and the flag is never implied (no other engine serves in its place)");
-            if (cfg->max_episode_steps < 1)
-                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_ACROBOT is built for max_episode_steps >= 1 (an episode that never swings up ends at the "
-                            "time limit only); got %d", cfg->max_episode_steps);
-        }
-    }
-    if (taxi) {   // accepted in exactly the forms ppo_hip.h states (PPO_ENV_TAXI); a wrong obs_size first, with the reference's message (below)
-        if (cfg->obs_size == 19) {
-            if (cfg->dist_kind != PPO_DIST_MASKED && cfg->dist_kind != PPO_DIST_CATEGORICAL)
-                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_TAXI takes one of six discrete actions, drawn under the env's action mask or without it: it is "
-                            "built for dist_kind = PPO_DIST_MASKED and PPO_DIST_CATEGORICAL; got dist_kind %d", cfg->dist_kind);
-            if (cfg->n_heads != 1 || cfg->head_dims[0] != 6)
-                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_TAXI has one head of six actions (south, north, east, west, pickup, dropoff): n_heads = 1 and "
-                            "head_dims[0] = 6; got n_heads = %d, head_dims[0] = %d", cfg->n_heads, cfg->head_dims[0]);
-            if (cfg->hidden != 64 || cfg->n_hidden != 2)
-                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_TAXI is built for the 2 x 64 network (hidden = 64, n_hidden = 2) of the fused categorical "
-                            "kernels; got %d x %d", cfg->n_hidden, cfg->hidden);
-            if (cfg->compute_dtype != PPO_DTYPE_F32)
-                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_TAXI is built for compute_dtype = PPO_DTYPE_F32; bf16 storage is not");
-            if (!cat_fused)
-                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_TAXI needs PPO_KERNEL_CAT_FUSED in kernel_flags: its rollout exists on the fused categorical "
-                            "kernels only, and the flag is never implied (no other engine serves in its place)");
-            if (cfg->max_episode_steps < 1)
-                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_TAXI is built for max_episode_steps >= 1 (an episode that never delivers the passenger ends at "
-                            "the time limit only); got %d", cfg->max_episode_steps);
-        }
-    }
-    if (frozenlake) {   // accepted in exactly one form per map (ppo_hip.h: PPO_ENV_FROZENLAKE); a wrong obs_size first, with the reference's message (below)
-        const char* name = cfg->env_kind == PPO_ENV_FROZENLAKE8X8 ? "PPO_ENV_FROZENLAKE8X8" : "PPO_ENV_FROZENLAKE";
-        if (cfg->obs_size == frozenlake_obs) {
-            if (cfg->dist_kind != PPO_DIST_CATEGORICAL)
-                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = %s takes one of four discrete actions without a mask: it is built for dist_kind = "
-                            "PPO_DIST_CATEGORICAL; got dist_kind %d", name, cfg->dist_kind);
-            if (cfg->n_heads != 1 || cfg->head_dims[0] != 4)
-                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = %s has one head of four actions (left, down, right, up): n_heads = 1 and head_dims[0] = 4; got "
-                            "n_heads = %d, head_dims[0] = %d", name, cfg->n_heads, cfg->head_dims[0]);
-            if (cfg->hidden != 64 || cfg->n_hidden != 2)
-                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = %s is built for the 2 x 64 network (hidden = 64, n_hidden = 2) of the fused categorical "
-                            "kernels; got %d x %d", name, cfg->n_hidden, cfg->hidden);
-            if (cfg->compute_dtype != PPO_DTYPE_F32)
-                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = %s is built for compute_dtype = PPO_DTYPE_F32; bf16 storage is not", name);
-            if (!cat_fused)
-                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = %s needs PPO_KERNEL_CAT_FUSED in kernel_flags: its rollout exists on the fused categorical "
-                            "kernels only, and the flag is never implied (no other engine serves in its place)", name);
-            if (cfg->max_episode_steps < 1 || cfg->max_episode_steps > FROZENLAKE_WORD_MAX)
-                return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = %s is built for 1 <= max_episode_steps <= %d (the episode's step count is a state word held exactly "
-                            "in f32, and it keys the env's draws); got %d", name, FROZENLAKE_WORD_MAX, cfg->max_episode_steps);
-        }
-    }
-    if (blackjack && cfg->obs_size == 45) {   // accepted in exactly one form (ppo_hip.h: PPO_ENV_BLACKJACK); a wrong obs_size first, with the reference's message (below)
-        if (cfg->dist_kind != PPO_DIST_CATEGORICAL)
-            return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_BLACKJACK takes one of two discrete actions without a mask: it is built for dist_kind = "
-                        "PPO_DIST_CATEGORICAL; got dist_kind %d", cfg->dist_kind);
-        if (cfg->n_heads != 1 || cfg->head_dims[0] != 2)
-            return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_BLACKJACK has one head of two actions (stick, hit): n_heads = 1 and head_dims[0] = 2; got "
-                        "n_heads = %d, head_dims[0] = %d", cfg->n_heads, cfg->head_dims[0]);
+    if (env && cfg->obs_size == env->obs) {   // accepted in exactly the forms ppo_hip.h states; a wrong obs_size first, with the reference's message (below)
+        const bool g = env->family == FUSED_GAUSS;
+        const char* kernels = g ? "fused Gaussian" : "fused categorical";
+        if (!(env->dist_mask >> cfg->dist_kind & 1))
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = %s takes %s: it is built for dist_kind = %s; got dist_kind %d", env->name, env->text.takes,
+                        g ? "PPO_DIST_GAUSSIAN" : (env->dist_mask >> PPO_DIST_MASKED & 1 ? "PPO_DIST_MASKED and PPO_DIST_CATEGORICAL" : "PPO_DIST_CATEGORICAL"),
+                        cfg->dist_kind);
+        if (cfg->n_heads != 1 || cfg->head_dims[0] != env->actions)
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = %s has %s: n_heads = 1 and head_dims[0] = %d; got n_heads = %d, head_dims[0] = %d", env->name,
+                        env->text.head, env->actions, cfg->n_heads, cfg->head_dims[0]);
         if (cfg->hidden != 64 || cfg->n_hidden != 2)
-            return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_BLACKJACK is built for the 2 x 64 network (hidden = 64, n_hidden = 2) of the fused categorical "
-                        "kernels; got %d x %d", cfg->n_hidden, cfg->hidden);
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = %s is built for the 2 x 64 network (hidden = 64, n_hidden = 2) of the %s kernels; got %d x %d",
+                        env->name, kernels, cfg->n_hidden, cfg->hidden);
         if (cfg->compute_dtype != PPO_DTYPE_F32)
-            return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_BLACKJACK is built for compute_dtype = PPO_DTYPE_F32; bf16 storage is not");
-        if (!cat_fused)
-            return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_BLACKJACK needs PPO_KERNEL_CAT_FUSED in kernel_flags: its rollout exists on the fused categorical "
-                        "kernels only, and the flag is never implied (no other engine serves in its place)");
-        if (cfg->max_episode_steps < 1 || cfg->max_episode_steps > BLACKJACK_WORD_MAX)
-            return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = PPO_ENV_BLACKJACK is built for 1 <= max_episode_steps <= %d (as on PPO_ENV_FROZENLAKE: the state's words "
-                        "are integers held exactly in f32); got %d", BLACKJACK_WORD_MAX, cfg->max_episode_steps);
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = %s is built for compute_dtype = PPO_DTYPE_F32; bf16 storage is not", env->name);
+        if (!(cfg->kernel_flags & (g ? PPO_KERNEL_GAUSS_FUSED : PPO_KERNEL_CAT_FUSED)))
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = %s needs %s in kernel_flags: its rollout exists on the %s kernels only, and the flag is never "
+                        "implied (no other engine serves in its place)", env->name, g ? "PPO_KERNEL_GAUSS_FUSED" : "PPO_KERNEL_CAT_FUSED", kernels);
+        if (cfg->max_episode_steps < 1 || (env->max_steps && cfg->max_episode_steps > env->max_steps))
+            return env->max_steps ? fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = %s is built for 1 <= max_episode_steps <= %d (%s); got %d", env->name,
+                                         env->max_steps, env->text.steps_why, cfg->max_episode_steps)
+                                  : fail(nullptr, PPO_ERR_UNSUPPORTED, "env_kind = %s is built for max_episode_steps >= 1 (%s); got %d", env->name, env->text.steps_why,
+                                         cfg->max_episode_steps);
     }
     if (gauss && !host_env && !gauss_env)
-        return fail(nullptr, PPO_ERR_UNSUPPORTED, "dist_kind = PPO_DIST_GAUSSIAN serves caller-stepped environments (env_kind = PPO_ENV_HOST), PPO_ENV_PENDULUM and "
-                    "PPO_ENV_MOUNTAINCAR_CONTINUOUS: CartPole, MountainCar and the synthetic env take discrete actions; got env_kind %d", cfg->env_kind);
+        return fail(nullptr, PPO_ERR_UNSUPPORTED, "dist_kind = PPO_DIST_GAUSSIAN serves caller-stepped environments (env_kind = PPO_ENV_HOST), %s: CartPole, MountainCar "
+                    "and the synthetic env take discrete actions; got env_kind %d", fused_env_names(FUSED_GAUSS), cfg->env_kind);
     if (gauss && cfg->compute_dtype != PPO_DTYPE_F32)
         return fail(nullptr, PPO_ERR_UNSUPPORTED, "dist_kind = PPO_DIST_GAUSSIAN is built for compute_dtype = PPO_DTYPE_F32; bf16 storage is not");
     if (gauss && cfg->n_heads != 1)
@@ -759,8 +646,8 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
             return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED serves dist_kind = PPO_DIST_CATEGORICAL and PPO_DIST_MASKED only; this context's policy is "
                         "PPO_DIST_GAUSSIAN (its twin is PPO_KERNEL_GAUSS_FUSED)");
         if (!host_env && !cat_env)
-            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED serves caller-stepped environments (env_kind = PPO_ENV_HOST), PPO_ENV_ACROBOT, PPO_ENV_TAXI, the two PPO_ENV_FROZENLAKE kinds and PPO_ENV_BLACKJACK only; got "
-                        "env_kind %d", cfg->env_kind);
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED serves caller-stepped environments (env_kind = PPO_ENV_HOST), %s only; got env_kind %d",
+                        fused_env_names(FUSED_CAT), cfg->env_kind);
         if (cfg->hidden != 64) return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED is built for hidden = 64; got hidden = %d", cfg->hidden);
         if (cfg->n_hidden != 2) return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED is built for n_hidden = 2; got n_hidden = %d", cfg->n_hidden);
         if (cfg->compute_dtype != PPO_DTYPE_F32)
@@ -771,7 +658,7 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
     if (cfg->compute_dtype == PPO_DTYPE_BF16 && !generic)
         return fail(nullptr, PPO_ERR_UNSUPPORTED, "compute_dtype = PPO_DTYPE_BF16 applies to networks whose layers are GEMMs (env_kind = PPO_ENV_SYNTHETIC); the reference's "
                     "2 x 64 networks always compute in f32");
-    const int env_obs = cfg->env_kind == PPO_ENV_CARTPOLE ? 4 : (cfg->env_kind == PPO_ENV_MOUNTAINCAR || mcc ? 2 : (pendulum ? 3 : (acrobot ? 6 : (taxi ? 19 : (frozenlake ? frozenlake_obs : (blackjack ? 45 : cfg->obs_size))))));   // host / synthetic: no check
+    const int env_obs = env ? env->obs : (cfg->env_kind == PPO_ENV_CARTPOLE ? 4 : (cfg->env_kind == PPO_ENV_MOUNTAINCAR ? 2 : cfg->obs_size));   // host / synthetic: no check
     if (cfg->obs_size != env_obs) {
         // the reference's runtime check in initEnvs (PPO_Discrete.cpp:370-375), same wording
         return fail(nullptr, PPO_ERR_INVALID,
@@ -815,6 +702,7 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
     if (e != hipSuccess) return fail(nullptr, PPO_ERR_HIP, "hipSetDevice(%d): %s", cfg->device, hipGetErrorString(e));
     ppo_ctx* c = new ppo_ctx();
     c->cfg = *cfg;
+    c->env = env;
     if (c->cfg.global_num_envs <= 0) c->cfg.global_num_envs = cfg->num_envs;
     c->L = make_layout(cfg->obs_size, cfg->n_heads, cfg->head_dims);
     if (generic) {
@@ -1458,7 +1346,8 @@ extern "C" ppo_status ppo_categorical_sample(const float* m_probs, int64_t n, in
 extern "C" ppo_status ppo_env_transition(int32_t env_kind, const float* state_in, const int64_t* action, int64_t n, float* next_state,
                                          float* reward, int32_t* terminated, void* stream) {
     if (!state_in || !action || !next_state || !reward || !terminated || n < 0) return PPO_ERR_INVALID;
-    if (cat_fused_env_serves(env_kind))   // PPO_ENV_ACROBOT, PPO_ENV_TAXI, PPO_ENV_FROZENLAKE, PPO_ENV_FROZENLAKE8X8, PPO_ENV_BLACKJACK: state [n, 4]
+    const FusedEnvInfo* env = fused_env_info(env_kind);
+    if (env && env->family == FUSED_CAT)   // state [n, STATE]
         return launch_cat_env_transition(env_kind, state_in, action, n, next_state, reward, terminated, (hipStream_t)stream) == hipSuccess ? PPO_OK : PPO_ERR_HIP;
     return launch_env_transition(env_kind, state_in, action, n, next_state, reward, terminated, (hipStream_t)stream) == hipSuccess ? PPO_OK : PPO_ERR_HIP;
 }
@@ -1471,24 +1360,15 @@ static ppo_status host_env_refuses(ppo_ctx* c, const char* what) {
 
 // what the refusals of the caller-stepped entry points add on a PPO_KERNEL_ENV_GENERIC context: the flag changes the network's engine, not whose env it is
 static inline const char* env_generic_note(const ppo_ctx* c) { return c->env_generic ? ", on the generic engine under PPO_KERNEL_ENV_GENERIC" : ""; }
-static inline bool is_pendulum(const ppo_ctx* c) { return c->cfg.env_kind == PPO_ENV_PENDULUM; }
-static inline bool is_mcc(const ppo_ctx* c) { return c->cfg.env_kind == PPO_ENV_MOUNTAINCAR_CONTINUOUS; }
-// the device envs with real-valued actions: the env of the fused Gaussian rollout (gauss_fused.hpp)
-static inline bool is_gauss_env(const ppo_ctx* c) { return is_pendulum(c) || is_mcc(c); }
-// the device env with integer actions of the fused categorical rollout (gauss_fused.hpp: cat_fused_rollout)
-static inline bool is_acrobot(const ppo_ctx* c) { return c->cfg.env_kind == PPO_ENV_ACROBOT; }
-static inline bool is_taxi(const ppo_ctx* c) { return c->cfg.env_kind == PPO_ENV_TAXI; }
-// the device envs with integer actions: the envs of the fused categorical rollout (gauss_fused.hpp)
-static inline bool is_frozenlake(const ppo_ctx* c) { return c->cfg.env_kind == PPO_ENV_FROZENLAKE || c->cfg.env_kind == PPO_ENV_FROZENLAKE8X8; }
-static inline int frozenlake_cells(const ppo_ctx* c) { return c->cfg.env_kind == PPO_ENV_FROZENLAKE8X8 ? 64 : 16; }
-static inline bool is_blackjack(const ppo_ctx* c) { return c->cfg.env_kind == PPO_ENV_BLACKJACK; }
-static inline bool is_cat_env(const ppo_ctx* c) { return is_acrobot(c) || is_taxi(c) || is_frozenlake(c) || is_blackjack(c); }
-static inline const char* gauss_env_name(const ppo_ctx* c) { return is_mcc(c) ? "PPO_ENV_MOUNTAINCAR_CONTINUOUS" : "PPO_ENV_PENDULUM"; }
+// the device envs of the fused rollouts (gauss_fused.hpp: FusedEnvInfo), with real-valued and with integer actions
+static inline bool is_gauss_env(const ppo_ctx* c) { return c->env && c->env->family == FUSED_GAUSS; }
+static inline bool is_cat_env(const ppo_ctx* c) { return c->env && c->env->family == FUSED_CAT; }
 
 extern "C" ppo_status ppo_env_transition_f32(int32_t env_kind, const float* state_in, const float* action, int64_t n, float* next_state, float* obs_out,
                                              float* reward, int32_t* terminated, void* stream) {
     if (!state_in || !action || !next_state || !reward || !terminated || n < 0) return PPO_ERR_INVALID;
-    if (env_kind != PPO_ENV_PENDULUM && env_kind != PPO_ENV_MOUNTAINCAR_CONTINUOUS) return PPO_ERR_UNSUPPORTED;   // the envs with integer actions: ppo_env_transition
+    const FusedEnvInfo* env = fused_env_info(env_kind);
+    if (!env || env->family != FUSED_GAUSS) return PPO_ERR_UNSUPPORTED;   // the envs with integer actions: ppo_env_transition
     return launch_gauss_env_transition(env_kind, state_in, action, n, next_state, obs_out, reward, terminated, (hipStream_t)stream) == hipSuccess ? PPO_OK : PPO_ERR_HIP;
 }
 
@@ -1496,13 +1376,8 @@ extern "C" ppo_status ppo_env_reset(ppo_ctx* c) {
     NEED(c, c != nullptr, "null ctx");
     if (c->host_env) return host_env_refuses(c, "ppo_env_reset");
     DeviceGuard dev_guard(c);
-    if (is_cat_env(c)) {
-        HIPCHK(c, launch_cat_env_reset(c->cfg.env_kind, c->N, c->cfg.seed, c->cfg.env_offset, B_<float>(c, PPO_BUF_ENV_STATE), B_<int32_t>(c, PPO_BUF_EP_LEN), B_<float>(c, PPO_BUF_EP_REW),
-                                      B_<int32_t>(c, PPO_BUF_RESET_COUNT), B_<float>(c, PPO_BUF_NEXT_OBS), B_<int32_t>(c, PPO_BUF_NEXT_DONE), c->stream));
-        return PPO_OK;
-    }
-    if (is_gauss_env(c)) {
-        HIPCHK(c, launch_gauss_env_reset(c->cfg.env_kind, c->N, c->cfg.seed, c->cfg.env_offset, B_<float>(c, PPO_BUF_ENV_STATE), B_<int32_t>(c, PPO_BUF_EP_LEN), B_<float>(c, PPO_BUF_EP_REW),
+    if (c->env) {
+        HIPCHK(c, launch_fused_env_reset(c->cfg.env_kind, c->N, c->cfg.seed, c->cfg.env_offset, B_<float>(c, PPO_BUF_ENV_STATE), B_<int32_t>(c, PPO_BUF_EP_LEN), B_<float>(c, PPO_BUF_EP_REW),
                                         B_<int32_t>(c, PPO_BUF_RESET_COUNT), B_<float>(c, PPO_BUF_NEXT_OBS), B_<int32_t>(c, PPO_BUF_NEXT_DONE), c->stream));
         return PPO_OK;
     }
@@ -1523,7 +1398,7 @@ extern "C" ppo_status ppo_env_reset(ppo_ctx* c) {
 extern "C" ppo_status ppo_env_step(ppo_ctx* c, const int64_t* action, float* obs, float* reward, int32_t* done) {
     NEED(c, c && action && obs && reward && done, "null argument");
     if (c->host_env) return host_env_refuses(c, "ppo_env_step");
-    if (is_gauss_env(c)) return fail(c, PPO_ERR_UNSUPPORTED, "ppo_env_step: this context's env (%s) takes real-valued actions f32 [N, D]; call ppo_env_step_f32", gauss_env_name(c));
+    if (is_gauss_env(c)) return fail(c, PPO_ERR_UNSUPPORTED, "ppo_env_step: this context's env (%s) takes real-valued actions f32 [N, D]; call ppo_env_step_f32", c->env->name);
     DeviceGuard dev_guard(c);
     if (is_cat_env(c)) {
         HIPCHK(c, launch_cat_env_step(c->cfg.env_kind, c->N, c->cfg.max_episode_steps, c->cfg.seed, c->cfg.env_offset, B_<float>(c, PPO_BUF_ENV_STATE), B_<int32_t>(c, PPO_BUF_EP_LEN),
@@ -1553,40 +1428,25 @@ extern "C" ppo_status ppo_env_step_f32(ppo_ctx* c, const float* action, float* o
     return PPO_OK;
 }
 
-// the env state's width: the observation IS the state for CartPole and both MountainCars; Pendulum keeps (theta, theta_dot) behind a 3-wide observation
-static inline int env_state_dim(const ppo_ctx* c) { return is_pendulum(c) ? 2 : (is_cat_env(c) ? 4 : c->O); }
+// the env state's width: a fused device env's row has it; the observation IS the state for CartPole and MountainCar
+static inline int env_state_dim(const ppo_ctx* c) { return c->env ? c->env->state : c->O; }
 
 extern "C" ppo_status ppo_env_set_state_h(ppo_ctx* c, const float* state_h, const int32_t* ep_len_h, const float* ep_rew_h, const int32_t* reset_count_h) {
     NEED(c, c != nullptr, "null ctx");
     DeviceGuard dev_guard(c);
-    if (state_h && is_taxi(c)) {   // a Taxi state is four small integers (row, col in 0..4, pass in 0..4, dest in 0..3): checked here, on the host array
-        static const float hi[4] = { 4.0f, 4.0f, 4.0f, 3.0f };
-        for (int64_t i = 0; i < (int64_t)c->N * 4; i++) {
+    if (state_h && c->env && c->env->check.words) {   // the state's words are integers of known ranges: checked here, on the host array
+        const FusedStateCheck& k = c->env->check;
+        const int S = c->env->state;
+        for (int64_t i = 0; i < (int64_t)c->N * S; i++) {
             const float v = state_h[i];
-            if (!(v >= 0.0f && v <= hi[i & 3] && v == (float)(int)v))
-                return fail(c, PPO_ERR_INVALID, "ppo_env_set_state_h: state[%lld][%d] = %g is not an integer in 0..%d (PPO_ENV_TAXI: row, col, pass in 0..4, dest in "
-                            "0..3); nothing was changed", (long long)(i >> 2), (int)(i & 3), (double)v, (int)hi[i & 3]);
-        }
-    }
-    if (state_h && is_frozenlake(c)) {   // a FrozenLake state is four integers (cell in 0..S-1; j, k0, k1 in 0..2^24-1): checked here, on the host array
-        const float hi[4] = { (float)(frozenlake_cells(c) - 1), (float)FROZENLAKE_WORD_MAX, (float)FROZENLAKE_WORD_MAX, (float)FROZENLAKE_WORD_MAX };
-        for (int64_t i = 0; i < (int64_t)c->N * 4; i++) {
-            const float v = state_h[i];
-            if (!(v >= 0.0f && v <= hi[i & 3] && v == (float)(int)v))
-                return fail(c, PPO_ERR_INVALID, "ppo_env_set_state_h: state[%lld][%d] = %g is not an integer in 0..%d (PPO_ENV_FROZENLAKE: cell in 0..%d; j, k0, k1 in "
-                            "0..%d); nothing was changed", (long long)(i >> 2), (int)(i & 3), (double)v, (int)hi[i & 3], frozenlake_cells(c) - 1, FROZENLAKE_WORD_MAX);
-        }
-    }
-    if (state_h && is_blackjack(c)) {   // a Blackjack state is four integers (hand = t + 32 * ace + 64 * show; n, k0, k1 in 0..2^24-1): checked here, on the host array
-        for (int64_t i = 0; i < (int64_t)c->N * 4; i++) {
-            const float v = state_h[i];
-            const int hi = (i & 3) == 0 ? BLACKJACK_HAND_MAX : BLACKJACK_WORD_MAX;
-            bool ok = v >= 0.0f && v <= (float)hi && v == (float)(int)v;
-            if (ok && (i & 3) == 0) ok = ((int)v & 31) >= 2 && ((int)v >> 6) >= 1;   // t in 2..31, show in 1..10; no bits above: v <= 703
+            const int w = (int)(i % S), hi = k.hi[w];
+            const bool ok = v >= 0.0f && v <= (float)hi && v == (float)(int)v && (!k.word_ok || k.word_ok(w, (int)v));
+            if (!ok && k.word_ok)   // a word with a condition beyond its bound: the message gives the ranges only
+                return fail(c, PPO_ERR_INVALID, "ppo_env_set_state_h: state[%lld][%d] = %g is not an integer of its range (%s); nothing was changed",
+                            (long long)(i / S), w, (double)v, k.words);
             if (!ok)
-                return fail(c, PPO_ERR_INVALID, "ppo_env_set_state_h: state[%lld][%d] = %g is not an integer of its range (PPO_ENV_BLACKJACK: hand = t + 32 * ace + "
-                            "64 * show with t in 2..31, ace in 0..1, show in 1..10; n, k0, k1 in 0..%d); nothing was changed", (long long)(i >> 2), (int)(i & 3),
-                            (double)v, BLACKJACK_WORD_MAX);
+                return fail(c, PPO_ERR_INVALID, "ppo_env_set_state_h: state[%lld][%d] = %g is not an integer in 0..%d (%s); nothing was changed",
+                            (long long)(i / S), w, (double)v, hi, k.words);
         }
     }
     if (state_h) {
@@ -1594,8 +1454,7 @@ extern "C" ppo_status ppo_env_set_state_h(ppo_ctx* c, const float* state_h, cons
         ppo_status s = ppo_memcpy_h2d(c, c->scratch_obs, state_h, (size_t)c->N * S * sizeof(float));
         if (s != PPO_OK) return s;
         HIPCHK(c, launch_aos_to_soa(c->scratch_obs, B_<float>(c, PPO_BUF_ENV_STATE), c->N, S, true, c->stream));
-        if (is_pendulum(c)) HIPCHK(c, launch_gauss_env_obs(c->cfg.env_kind, c->N, B_<float>(c, PPO_BUF_ENV_STATE), B_<float>(c, PPO_BUF_NEXT_OBS), c->stream));
-        else if (is_cat_env(c)) HIPCHK(c, launch_cat_env_obs(c->cfg.env_kind, c->N, B_<float>(c, PPO_BUF_ENV_STATE), B_<float>(c, PPO_BUF_NEXT_OBS), c->stream));
+        if (c->env && !c->env->obs_is_state) HIPCHK(c, launch_fused_env_obs(c->cfg.env_kind, c->N, B_<float>(c, PPO_BUF_ENV_STATE), B_<float>(c, PPO_BUF_NEXT_OBS), c->stream));
         else HIPCHK(c, hipMemcpyAsync(c->buf[PPO_BUF_NEXT_OBS], c->scratch_obs, (size_t)c->N * c->O * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     }
     ppo_status s = PPO_OK;
@@ -1699,13 +1558,13 @@ static ppo_status env_fold_truncations(ppo_ctx* c) {
     return PPO_OK;
 }
 
-// ppo_env_truncation_bootstrap's launch on PPO_ENV_MOUNTAINCAR_CONTINUOUS: env_fold_truncations on the fused Gaussian critic, the one gen_values fills
-// PPO_BUF_VALUES with (gauss_fused.hpp: GaussFoldArgs).  None of the launches ppo_gauss_fused_launches counts.
-static ppo_status gauss_env_fold_truncations(ppo_ctx* c) {
-    GaussFoldArgs f{};
+// ppo_env_truncation_bootstrap's launch on a fused device env that folds: env_fold_truncations on the fused critic, the one gen_values fills PPO_BUF_VALUES
+// with (gauss_fused.hpp: FusedFoldArgs).  None of the launches ppo_gauss_fused_launches counts.
+static ppo_status fused_env_fold_truncations(ppo_ctx* c) {
+    FusedFoldArgs f{};
     f.params = B_<float>(c, PPO_BUF_PARAMS);
     f.obs = B_<float>(c, PPO_BUF_OBS);
-    f.actions = B_<float>(c, PPO_BUF_ACTIONS);
+    f.actions = c->buf[PPO_BUF_ACTIONS];
     f.fin_len = B_<int32_t>(c, PPO_BUF_FIN_LEN);
     f.B = c->B;
     f.max_episode_steps = c->cfg.max_episode_steps;
@@ -1713,7 +1572,7 @@ static ppo_status gauss_env_fold_truncations(ppo_ctx* c) {
     f.rewards = B_<float>(c, PPO_BUF_REWARDS);
     f.ev_count = c->envt_count; f.ev_index = c->envt_index; f.ev_value = c->envt_value; f.ev_cap = c->B;
     HIPCHK(c, hipMemsetAsync(c->envt_count, 0, sizeof(int32_t), c->stream));
-    HIPCHK(c, gauss_fused_trunc_fold(c->cfg.env_kind, c->gen->L, f, c->stream));
+    HIPCHK(c, fused_env_trunc_fold(c->cfg.env_kind, c->gen->L, f, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->envt_count_h, c->envt_count, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipEventRecord(c->envt_ev, c->stream));
     c->envt_last = true;
@@ -1721,75 +1580,12 @@ static ppo_status gauss_env_fold_truncations(ppo_ctx* c) {
     return PPO_OK;
 }
 
-// PPO_ENV_PENDULUM, PPO_ENV_MOUNTAINCAR_CONTINUOUS: gauss_rollout_kernel (all T steps), then gen_rollout's tail -- the critic over the stored observations and
-// over NEXT_OBS: three launches; with ppo_env_truncation_bootstrap on (the second env only), the fold behind them
-static ppo_status gauss_env_rollout(ppo_ctx* c, const float* forced) {
+// A fused device env: gauss_rollout_kernel / cat_rollout_kernel (all T steps), then gen_rollout's tail -- the critic over the stored observations and over
+// NEXT_OBS: three launches; with ppo_env_truncation_bootstrap on (an env that folds only), the fold behind them.  forced: the family's action type, or null
+static ppo_status fused_env_rollout(ppo_ctx* c, const void* forced) {
     ppo_status s = consume_finished_episodes(c);
     if (s != PPO_OK) return s;
-    GaussRolloutArgs r{};
-    r.params = B_<float>(c, PPO_BUF_PARAMS);
-    r.N = c->N; r.T = c->T; r.max_episode_steps = c->cfg.max_episode_steps;
-    r.seed = c->cfg.seed; r.env_offset = c->cfg.env_offset; r.step_base = c->rollout_steps;
-    r.env_state = B_<float>(c, PPO_BUF_ENV_STATE);
-    r.ep_len = B_<int32_t>(c, PPO_BUF_EP_LEN);
-    r.ep_rew = B_<float>(c, PPO_BUF_EP_REW);
-    r.reset_count = B_<int32_t>(c, PPO_BUF_RESET_COUNT);
-    r.obs = B_<float>(c, PPO_BUF_OBS);
-    r.actions = B_<float>(c, PPO_BUF_ACTIONS);
-    r.logprobs = B_<float>(c, PPO_BUF_LOGPROBS);
-    r.rewards = B_<float>(c, PPO_BUF_REWARDS);
-    r.dones = B_<float>(c, PPO_BUF_DONES);
-    r.fin_len = B_<int32_t>(c, PPO_BUF_FIN_LEN);
-    r.fin_rew = B_<float>(c, PPO_BUF_FIN_REW);
-    r.next_obs = B_<float>(c, PPO_BUF_NEXT_OBS);
-    r.next_done = B_<int32_t>(c, PPO_BUF_NEXT_DONE);
-    r.forced = forced;
-    {
-        ProfScope ps(c, PROF_ROLLOUT);
-        HIPCHK(c, gauss_fused_rollout(c->cfg.env_kind, c->gen->L, r, c->stream));
-        s = gen_values(c, r.obs, (int64_t)c->T * c->N, B_<float>(c, PPO_BUF_VALUES));
-        if (s == PPO_OK) s = gen_values(c, r.next_obs, c->N, B_<float>(c, PPO_BUF_NEXT_VALUE));
-        if (s != PPO_OK) return s;
-        c->envt_last = false;
-        if (c->envt_on) {   // behind the two critic launches, in front of the scan (envt_on is never set on a Pendulum context: envt_state)
-            s = gauss_env_fold_truncations(c);
-            if (s != PPO_OK) return s;
-        }
-    }
-    c->rollout_steps += c->T;
-    c->global_step += (int64_t)c->T * c->cfg.global_num_envs;
-    c->fin_pending = true;
-    return PPO_OK;
-}
-
-// ppo_env_truncation_bootstrap's launch on PPO_ENV_TAXI: gauss_env_fold_truncations with the state recovered from the stored observation and i32 actions
-// (gauss_fused.hpp: CatFoldArgs).  None of the launches ppo_gauss_fused_launches counts.
-static ppo_status cat_env_fold_truncations(ppo_ctx* c) {
-    CatFoldArgs f{};
-    f.params = B_<float>(c, PPO_BUF_PARAMS);
-    f.obs = B_<float>(c, PPO_BUF_OBS);
-    f.actions = B_<int32_t>(c, PPO_BUF_ACTIONS);
-    f.fin_len = B_<int32_t>(c, PPO_BUF_FIN_LEN);
-    f.B = c->B;
-    f.max_episode_steps = c->cfg.max_episode_steps;
-    f.gamma = c->cfg.gamma;
-    f.rewards = B_<float>(c, PPO_BUF_REWARDS);
-    f.ev_count = c->envt_count; f.ev_index = c->envt_index; f.ev_value = c->envt_value; f.ev_cap = c->B;
-    HIPCHK(c, hipMemsetAsync(c->envt_count, 0, sizeof(int32_t), c->stream));
-    HIPCHK(c, cat_fused_trunc_fold(c->cfg.env_kind, c->gen->L, f, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->envt_count_h, c->envt_count, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipEventRecord(c->envt_ev, c->stream));
-    c->envt_last = true;
-    c->envt_fetched = false;
-    return PPO_OK;
-}
-
-// PPO_ENV_ACROBOT, PPO_ENV_TAXI: cat_rollout_kernel (all T steps), then the critic over the stored observations and over NEXT_OBS: three launches,
-// gauss_env_rollout's plan; with ppo_env_truncation_bootstrap on (PPO_ENV_TAXI only), the fold behind them
-static ppo_status cat_env_rollout(ppo_ctx* c, const int64_t* forced) {
-    ppo_status s = consume_finished_episodes(c);
-    if (s != PPO_OK) return s;
-    CatRolloutArgs r{};
+    FusedRolloutArgs r{};
     r.params = B_<float>(c, PPO_BUF_PARAMS);
     r.N = c->N; r.T = c->T; r.max_episode_steps = c->cfg.max_episode_steps;
     r.seed = c->cfg.seed; r.env_offset = c->cfg.env_offset; r.step_base = c->rollout_steps;
@@ -1799,7 +1595,7 @@ static ppo_status cat_env_rollout(ppo_ctx* c, const int64_t* forced) {
     r.reset_count = B_<int32_t>(c, PPO_BUF_RESET_COUNT);
     r.obs = B_<float>(c, PPO_BUF_OBS);
     r.masks = B_<uint8_t>(c, PPO_BUF_MASKS);
-    r.actions = B_<int32_t>(c, PPO_BUF_ACTIONS);
+    r.actions = c->buf[PPO_BUF_ACTIONS];
     r.logprobs = B_<float>(c, PPO_BUF_LOGPROBS);
     r.rewards = B_<float>(c, PPO_BUF_REWARDS);
     r.dones = B_<float>(c, PPO_BUF_DONES);
@@ -1810,13 +1606,13 @@ static ppo_status cat_env_rollout(ppo_ctx* c, const int64_t* forced) {
     r.forced = forced;
     {
         ProfScope ps(c, PROF_ROLLOUT);
-        HIPCHK(c, cat_fused_rollout(c->cfg.env_kind, c->cfg.dist_kind, c->gen->L, r, c->stream));
+        HIPCHK(c, launch_fused_env_rollout(c->cfg.env_kind, c->cfg.dist_kind, c->gen->L, r, c->stream));
         s = gen_values(c, r.obs, (int64_t)c->T * c->N, B_<float>(c, PPO_BUF_VALUES));
         if (s == PPO_OK) s = gen_values(c, r.next_obs, c->N, B_<float>(c, PPO_BUF_NEXT_VALUE));
         if (s != PPO_OK) return s;
         c->envt_last = false;
-        if (c->envt_on) {   // behind the two critic launches, in front of the scan (envt_on is never set on an Acrobot context: envt_state)
-            s = cat_env_fold_truncations(c);
+        if (c->envt_on) {   // behind the two critic launches, in front of the scan (envt_on is never set on an env that does not fold: envt_state)
+            s = fused_env_fold_truncations(c);
             if (s != PPO_OK) return s;
         }
     }
@@ -1831,7 +1627,7 @@ extern "C" ppo_status ppo_rollout_f32(ppo_ctx* c, const float* forced_actions) {
     if (c->host_env) return host_env_refuses(c, "ppo_rollout_f32");
     if (!is_gauss(c)) return wrong_action_type(c, "ppo_rollout_f32", "ppo_rollout");
     DeviceGuard dev_guard(c);
-    return gauss_env_rollout(c, forced_actions);   // a Gaussian context with a device env is one of the two envs of the fused rollout (ppo_ctx_create)
+    return fused_env_rollout(c, forced_actions);   // a Gaussian context with a device env is an env of the fused rollout (ppo_ctx_create)
 }
 
 extern "C" ppo_status ppo_rollout(ppo_ctx* c, const int64_t* forced_actions) {
@@ -1840,10 +1636,10 @@ extern "C" ppo_status ppo_rollout(ppo_ctx* c, const int64_t* forced_actions) {
     if (is_gauss_env(c)) {
         if (forced_actions) return wrong_action_type(c, "ppo_rollout with forced actions", "ppo_rollout_f32");
         DeviceGuard dev_guard(c);
-        return gauss_env_rollout(c, nullptr);
+        return fused_env_rollout(c, nullptr);
     }
     DeviceGuard dev_guard(c);
-    if (is_cat_env(c)) return cat_env_rollout(c, forced_actions);
+    if (is_cat_env(c)) return fused_env_rollout(c, forced_actions);
     ppo_status s = consume_finished_episodes(c);
     if (s != PPO_OK) return s;
     if (c->gen && !c->env_generic) return gen_rollout(c, forced_actions);
@@ -1979,15 +1775,14 @@ static ppo_status eval_launch_categorical(ppo_ctx* c, int64_t n_episodes, int64_
 
 extern "C" ppo_status ppo_evaluate(ppo_ctx* c, int64_t n_episodes, int64_t seed, int32_t greedy, float* ep_return, int32_t* ep_length, ppo_eval_stats* out_h) {
     NEED(c, c != nullptr, "null ctx");
-    if (is_pendulum(c))
-        return fail(c, PPO_ERR_UNSUPPORTED, "ppo_evaluate is not built for PPO_ENV_PENDULUM: step the episodes through ppo_policy_act_f32 with greedy = 1 and "
-                                            "ppo_env_transition_f32");
-    const bool gauss_env = is_mcc(c);   // the episodes run on the fused Gaussian kernels (gauss_eval_kernel); everything on the host side is shared
-    const bool cat_env = is_cat_env(c);   // ... or on the fused categorical kernels (cat_eval_kernel)
+    if (is_gauss_env(c) && !c->env->evaluates)
+        return fail(c, PPO_ERR_UNSUPPORTED, "ppo_evaluate is not built for %s: step the episodes through ppo_policy_act_f32 with greedy = 1 and "
+                                            "ppo_env_transition_f32", c->env->name);
+    const bool fused_env = c->env && c->env->evaluates;   // the episodes run on the fused kernels (gauss_eval_kernel, cat_eval_kernel); the host side is shared
     if (c->env_generic)
         return fail(c, PPO_ERR_UNSUPPORTED, "ppo_evaluate is not built for PPO_KERNEL_ENV_GENERIC contexts: its episode kernels hold the reference's 2 x 64 network; step "
                                             "the episodes with ppo_policy_act_greedy + ppo_env_transition");
-    if (c->host_env || (c->gen && !gauss_env && !cat_env) || c->cfg.env_kind == PPO_ENV_SYNTHETIC)
+    if (c->host_env || (c->gen && !fused_env) || c->cfg.env_kind == PPO_ENV_SYNTHETIC)
         return fail(c, PPO_ERR_UNSUPPORTED, "ppo_evaluate steps the context's device environment (CartPole, MountainCar); this context's environment is %s: "
                                             "run the episodes on the host with one ppo_policy_act_greedy launch per step",
                     c->host_env ? "the caller's (PPO_ENV_HOST)" : "synthetic (PPO_ENV_SYNTHETIC)");
@@ -1995,19 +1790,18 @@ extern "C" ppo_status ppo_evaluate(ppo_ctx* c, int64_t n_episodes, int64_t seed,
     NEED(c, n_episodes > 0, "ppo_evaluate: n_episodes <= 0");
     NEED(c, n_episodes < (1ll << 28), "ppo_evaluate: more than 2^28 episodes");
     NEED(c, c->cfg.max_episode_steps > 0, "ppo_evaluate: max_episode_steps <= 0 (an episode would never be truncated)");
-    NEED(c, c->O == (c->cfg.env_kind == PPO_ENV_CARTPOLE ? 4 : (cat_env ? (is_taxi(c) ? 19 : (is_frozenlake(c) ? frozenlake_cells(c) : (is_blackjack(c) ? 45 : 6))) : 2)), "ppo_evaluate: obs_size does not match the environment");
+    NEED(c, c->O == (fused_env ? c->env->obs : (c->cfg.env_kind == PPO_ENV_CARTPOLE ? 4 : 2)), "ppo_evaluate: obs_size does not match the environment");
     DeviceGuard dev_guard(c);
     ppo_status s = eval_scratch(c, n_episodes, seed);
     if (s != PPO_OK) return s;
-    if (gauss_env || cat_env) {
-        GaussEvalArgs g{};
+    if (fused_env) {
+        FusedEvalArgs g{};
         g.params = B_<float>(c, PPO_BUF_PARAMS);
         g.n_episodes = n_episodes; g.seed = seed;
         g.max_episode_steps = c->cfg.max_episode_steps;
         g.greedy = greedy != 0;
         g.ep_return = c->eval_ret; g.ep_length = c->eval_len; g.ep_trunc = c->eval_len + c->eval_cap;
-        if (cat_env) HIPCHK(c, cat_fused_evaluate(c->cfg.env_kind, c->cfg.dist_kind, c->gen->L, g, c->stream));
-        else HIPCHK(c, gauss_fused_evaluate(c->cfg.env_kind, c->gen->L, g, c->stream));
+        HIPCHK(c, fused_env_evaluate(c->cfg.env_kind, c->cfg.dist_kind, c->gen->L, g, c->stream));
     } else {
         s = eval_launch_categorical(c, n_episodes, seed, greedy);
         if (s != PPO_OK) return s;
@@ -3390,21 +3184,10 @@ static ppo_status envt_state(ppo_ctx* c, const char* what) {
     if (c->host_env)
         return fail(c, PPO_ERR_UNSUPPORTED, "%s: this context's environments are the caller's (PPO_ENV_HOST), and only the caller holds the observation an episode "
                                             "ended on: pass it with ppo_host_observe_truncated (ppo_dev_observe for device arrays)", what);
-    if (is_pendulum(c))
-        return fail(c, PPO_ERR_UNSUPPORTED, "%s: the fold rebuilds the final observation of a cut-off episode from PPO_BUF_OBS, and a PPO_ENV_PENDULUM observation "
-                                            "(cos, sin, theta_dot) does not hold theta: not built for this env", what);
-    if (is_acrobot(c))
-        return fail(c, PPO_ERR_UNSUPPORTED, "%s: the fold rebuilds the final observation of a cut-off episode from PPO_BUF_OBS, and a PPO_ENV_ACROBOT observation "
-                                            "(cos, sin of two angles, two velocities) does not hold the angles: not built for this env", what);
-    if (is_frozenlake(c))
-        return fail(c, PPO_ERR_UNSUPPORTED, "%s: the fold rebuilds the final observation of a cut-off episode from PPO_BUF_OBS, and a PPO_ENV_FROZENLAKE observation "
-                                            "(the one-hot of the cell) holds neither the step count nor the key the env's slip is drawn from: not built for this env", what);
-    if (is_blackjack(c))
-        return fail(c, PPO_ERR_UNSUPPORTED, "%s: the fold rebuilds the final observation of a cut-off episode from PPO_BUF_OBS, and a PPO_ENV_BLACKJACK observation "
-                                            "(the player's sum, the dealer's showing card, the usable ace) holds neither the card count nor the key the env's cards are "
-                                            "drawn from: not built for this env", what);
-    if (is_mcc(c)) return PPO_OK;   // its observation is its state: the fold runs on the fused Gaussian critic (gauss_env_fold_truncations)
-    if (is_taxi(c)) return PPO_OK;  // its observation holds its state (four one-hot groups): the fold decodes it (cat_env_fold_truncations)
+    if (c->env)   // its observation holds its state and the fold runs on the fused critic (fused_env_fold_truncations), or the row says why not
+        return c->env->folds ? PPO_OK
+                             : fail(c, PPO_ERR_UNSUPPORTED, "%s: the fold rebuilds the final observation of a cut-off episode from PPO_BUF_OBS, and a %s: not built "
+                                                            "for this env", what, c->env->text.no_fold);
     if (c->env_generic)
         return fail(c, PPO_ERR_UNSUPPORTED, "%s: the fold of CartPole / MountainCar is built on the reference-shape critic (2 x 64), and this context's network lives "
                                             "on the generic engine (PPO_KERNEL_ENV_GENERIC): not built for it", what);

@@ -42,38 +42,59 @@ hipError_t cat_fused_fwd_bwd(const GenLayout& L, const LossParams& hp, const flo
                              const float* oldlp, const float* adv, const float* ret, const float* oldv, const int32_t* idx, int64_t M, double inv_global_M,
                              double global_M, const AdvStat* adv_stat, float* slab, double* loss_part, float* grads, hipStream_t s);
 
-// The device envs with real-valued actions (PPO_ENV_PENDULUM, PPO_ENV_MOUNTAINCAR_CONTINUOUS; the traits are ppo_internal.hpp's GaussEnv*): the T steps of a
-// rollout in one launch (gauss_rollout_kernel<Env>: one workgroup per 64 envs, the actor's weights resident, the env in wave 0's registers); the context's
-// buffers, the teacher-forcing actions f32 [T, N, 1] or null.  The critic is not in it: two gauss_fused_values launches follow.
-struct GaussRolloutArgs {
+// ---- The device envs of the two fused families.  An env is a trait in ppo_internal.hpp (GaussEnv*: one real-valued action; CatEnv*: one head of integer
+// actions), one line of its family's dispatcher and one row of the table in kernels_gauss_fused.hip; everything the C-ABI layer knows about an env it reads
+// from the row.  The numbers of a row come from the trait. ----
+enum FusedFamily { FUSED_GAUSS, FUSED_CAT };   // PPO_KERNEL_GAUSS_FUSED with dist_kind PPO_DIST_GAUSSIAN / PPO_KERNEL_CAT_FUSED with a categorical one
+// the words in which ppo_ctx_create's refusals differ between envs: "takes <takes>", "has <head>", "max_episode_steps ... (<steps_why>)"; and what envt_state
+// says of an env without the fold ("a <no_fold>: not built for this env"; null where it folds)
+struct FusedEnvTexts { const char *takes, *head, *steps_why, *no_fold; };
+// ppo_env_set_state_h on an env whose state words are integers: word w is an integer in 0..hi[w] that also passes word_ok (null: no further condition), and
+// `words` describes the ranges; words = null: the state is not checked
+struct FusedStateCheck { const char* words; int hi[4]; bool (*word_ok)(int word, int value); };
+struct FusedEnvInfo {
+    int env_kind;
+    const char* name;            // "PPO_ENV_..."
+    FusedFamily family;
+    int obs, state, actions;     // Env::OBS, Env::STATE, Env::ACTIONS (FUSED_GAUSS: the action dimension, 1)
+    unsigned dist_mask;          // bit d: dist_kind d is accepted (PPO_DIST_MASKED where the env forms a mask, Env::HAS_MASK)
+    bool obs_is_state;           // Env::OBS_IS_STATE: ppo_env_set_state_h copies the state into PPO_BUF_NEXT_OBS; elsewhere launch_fused_env_obs forms it
+    bool folds;                  // ppo_env_truncation_bootstrap: the stored observation holds the state (fused_env_trunc_fold)
+    bool evaluates;              // ppo_evaluate (fused_env_evaluate)
+    int max_steps;               // the upper bound of max_episode_steps; 0: none
+    FusedEnvTexts text;
+    FusedStateCheck check;
+};
+// the row of a device env of the fused families; null for every other env_kind
+const FusedEnvInfo* fused_env_info(int env_kind);
+// a family's rows by name, as ppo_ctx_create's refusals of PPO_DIST_GAUSSIAN and of PPO_KERNEL_CAT_FUSED on another env list them
+const char* fused_env_names(FusedFamily family);
+
+// The T steps of a rollout in one launch (gauss_rollout_kernel<Env> / cat_rollout_kernel<Env, DIST>: one workgroup per 64 envs, the actor's weights resident,
+// the env in wave 0's registers); the context's buffers.  actions / forced (teacher forcing, or null) are f32 [T, N, 1] on a FUSED_GAUSS env, i32 / i64 [T, N, 1]
+// on a FUSED_CAT one; masks is read by FUSED_CAT only: PPO_BUF_MASKS holds the masks of the env's states under PPO_DIST_MASKED, ones otherwise.  The critic is
+// not in it: two gauss_fused_values launches follow.
+struct FusedRolloutArgs {
     const float* params;
     int N, T, max_episode_steps;
     int64_t seed, env_offset, step_base;
-    float* env_state; int32_t* ep_len; float* ep_rew; int32_t* reset_count;
-    float *obs, *actions, *logprobs, *rewards, *dones; int32_t* fin_len; float* fin_rew;
+    float* env_state; int32_t* ep_len; float* ep_rew; int32_t* reset_count;   // env_state is [STATE, N]
+    float* obs; uint8_t* masks; void* actions; float *logprobs, *rewards, *dones; int32_t* fin_len; float* fin_rew;
     float* next_obs; int32_t* next_done;
-    const float* forced;
+    const void* forced;
 };
-// by env kind: the launcher is a template over the trait like the kernel (hipErrorInvalidValue for an env without one)
-hipError_t gauss_fused_rollout(int env_kind, const GenLayout& L, const GaussRolloutArgs& r, hipStream_t s);
-// The envs' stand-alone kernels, one thread per env, on the rollout kernel's device functions (ppo_internal.hpp: GaussEnv*)
-hipError_t launch_gauss_env_reset(int env_kind, int N, int64_t seed, int64_t env_offset, float* env_state, int32_t* ep_len, float* ep_rew, int32_t* reset_count,
-                                  float* next_obs, int32_t* next_done, hipStream_t s);
-hipError_t launch_gauss_env_step(int env_kind, int N, int max_episode_steps, int64_t seed, int64_t env_offset, float* env_state, int32_t* ep_len, float* ep_rew,
-                                 int32_t* reset_count, const float* action, float* obs, float* reward, int32_t* done, hipStream_t s);
-hipError_t launch_gauss_env_transition(int env_kind, const float* state_in, const float* action, int64_t n, float* next_state, float* obs_out, float* reward,
-                                       int32_t* terminated, hipStream_t s);
-hipError_t launch_gauss_env_obs(int env_kind, int N, const float* env_state, float* next_obs, hipStream_t s);
+// by env kind: the launchers are templates over the trait like the kernels (hipErrorInvalidValue for an env without a row, or without the call)
+hipError_t launch_fused_env_rollout(int env_kind, int dist_kind, const GenLayout& L, const FusedRolloutArgs& r, hipStream_t s);
 
-// ppo_env_truncation_bootstrap on a Gaussian device env whose observation is its state (PPO_ENV_MOUNTAINCAR_CONTINUOUS): ONE launch over the B = T * N stored
-// samples (gauss_trunc_fold_kernel).  For every i with fin_len[i] == max_episode_steps the last transition is recomputed from obs[i] under actions[i] (f32, the
-// raw action) with the env's own step; where the env terminated nothing happens, elsewhere v = Critic(final observation) -- gauss_values_kernel's forward, bit
-// for bit -- is folded into rewards[i] (fold_store: two roundings) and (i, v) joins the event list.  A workgroup (256 samples) without such a row costs one
-// pass over fin_len; the critic's weights are staged only by workgroups that found one.
-struct GaussFoldArgs {
+// ppo_env_truncation_bootstrap on an env that folds: ONE launch over the B = T * N stored samples (gauss_trunc_fold_kernel / cat_trunc_fold_kernel).  For every
+// i with fin_len[i] == max_episode_steps the last transition is recomputed from obs[i] (the state, or its one-hot groups decoded) under actions[i] with the env's
+// own step; where the env terminated nothing happens, elsewhere v = Critic(final observation) -- gauss_values_kernel's forward, bit for bit -- is folded into
+// rewards[i] (fold_store: two roundings) and (i, v) joins the event list.  A workgroup (256 samples) without such a row costs one pass over fin_len; the
+// critic's weights are staged only by workgroups that found one.
+struct FusedFoldArgs {
     const float* params;
     const float* obs;           // PPO_BUF_OBS [B, O]
-    const float* actions;       // PPO_BUF_ACTIONS f32 [B, 1]
+    const void* actions;        // PPO_BUF_ACTIONS [B, 1]: f32, the raw action (FUSED_GAUSS) / i32 (FUSED_CAT)
     const int32_t* fin_len;     // PPO_BUF_FIN_LEN [B]
     int64_t B;
     int max_episode_steps;      // > 0
@@ -84,12 +105,12 @@ struct GaussFoldArgs {
     float* ev_value;
     int64_t ev_cap;
 };
-hipError_t gauss_fused_trunc_fold(int env_kind, const GenLayout& L, const GaussFoldArgs& a, hipStream_t s);
+hipError_t fused_env_trunc_fold(int env_kind, const GenLayout& L, const FusedFoldArgs& f, hipStream_t s);
 
-// ppo_evaluate on such an env: n_episodes whole episodes as ONE launch (gauss_eval_kernel: a workgroup owns 64 episodes, the actor's weights resident; episode
-// e starts at reset 0 of env e under `seed`; greedy: the mean, else mu + sigma * eps keyed (seed, e, step of the episode, 0)); only the return (f32 sum in step
-// order), the length and the truncated flag (the length reached max_episode_steps) leave the chip.
-struct GaussEvalArgs {
+// ppo_evaluate on an env that evaluates: n_episodes whole episodes as ONE launch (gauss_eval_kernel / cat_eval_kernel: a workgroup owns 64 episodes, the actor's
+// weights resident; episode e starts at reset 0 of env e under `seed`; greedy: the mean / the first-index argmax, else the draw keyed (seed, e, step of the
+// episode, 0)); only the return (f32 sum in step order), the length and the truncated flag (the length reached max_episode_steps) leave the chip.
+struct FusedEvalArgs {
     const float* params;
     int64_t n_episodes, seed;
     int max_episode_steps;      // >= 1
@@ -98,52 +119,18 @@ struct GaussEvalArgs {
     int32_t* ep_length;
     int32_t* ep_trunc;
 };
-hipError_t gauss_fused_evaluate(int env_kind, const GenLayout& L, const GaussEvalArgs& a, hipStream_t s);
+hipError_t fused_env_evaluate(int env_kind, int dist_kind, const GenLayout& L, const FusedEvalArgs& e, hipStream_t s);
 
-// The device envs with integer actions (PPO_ENV_ACROBOT; the trait is ppo_internal.hpp's CatEnvAcrobot), on PPO_KERNEL_CAT_FUSED's forward: the T steps of a
-// categorical rollout in one launch (cat_rollout_kernel<Env>: gauss_rollout_kernel's plan with cat_act_kernel's wave-0 work); the context's buffers, the
-// teacher-forcing actions i64 [T, N, 1] or null.  PPO_BUF_MASKS is filled with ones.  The critic is not in it: two gauss_fused_values launches follow.
-bool cat_fused_env_serves(int env_kind);
-struct CatRolloutArgs {
-    const float* params;
-    int N, T, max_episode_steps;
-    int64_t seed, env_offset, step_base;
-    float* env_state; int32_t* ep_len; float* ep_rew; int32_t* reset_count;
-    float* obs; uint8_t* masks; int32_t* actions; float *logprobs, *rewards, *dones; int32_t* fin_len; float* fin_rew;
-    float* next_obs; int32_t* next_done;
-    const int64_t* forced;
-};
-hipError_t cat_fused_rollout(int env_kind, int dist_kind, const GenLayout& L, const CatRolloutArgs& r, hipStream_t s);
-// PPO_ENV_TAXI (CatEnvTaxi) is the env of this family that forms a mask (HAS_MASK): under dist_kind = PPO_DIST_MASKED a lane draws under the mask of its state
-// and PPO_BUF_MASKS holds those masks; under PPO_DIST_CATEGORICAL it holds ones, as on PPO_ENV_ACROBOT.  Its observation holds its state (STATE_FROM_OBS), so
-// it also has the time-limit fold (ppo_env_truncation_bootstrap): GaussFoldArgs' contract with i32 actions [B, 1], on cat_trunc_fold_kernel.
-// PPO_ENV_FROZENLAKE / PPO_ENV_FROZENLAKE8X8 (CatEnvFrozenLake<4>, <8>) are the envs of this family whose step draws random numbers; the key and the count of
-// the draw are words of the env state, so every entry point below serves them through the same arguments.  Their observation does not hold the state: no fold.
-// PPO_ENV_BLACKJACK (CatEnvBlackjack) rides on the same mechanism with a number of draws per step that depends on the data (a hit one card, a stick the dealer's
-// play-out, a reset the deal); no fold either.
-bool cat_fused_env_folds(int env_kind);
-struct CatFoldArgs {
-    const float* params;
-    const float* obs;
-    const int32_t* actions;
-    const int32_t* fin_len;
-    int64_t B;
-    int max_episode_steps;
-    float gamma;
-    float* rewards;
-    int32_t* ev_count;
-    int32_t* ev_index;
-    float* ev_value;
-    int64_t ev_cap;
-};
-hipError_t cat_fused_trunc_fold(int env_kind, const GenLayout& L, const CatFoldArgs& f, hipStream_t s);
-// The env's stand-alone kernels, one thread per env, on the rollout kernel's device functions; env_state is [STATE, N]
-hipError_t launch_cat_env_reset(int env_kind, int N, int64_t seed, int64_t env_offset, float* env_state, int32_t* ep_len, float* ep_rew, int32_t* reset_count,
-                                float* next_obs, int32_t* next_done, hipStream_t s);
+// The envs' stand-alone kernels, one thread per env, on the rollout kernel's device functions.  The step and the transition take the family's action type, as
+// the C ABI does (ppo_env_step / ppo_env_step_f32): each serves the envs of its family only.
+hipError_t launch_fused_env_reset(int env_kind, int N, int64_t seed, int64_t env_offset, float* env_state, int32_t* ep_len, float* ep_rew, int32_t* reset_count,
+                                  float* next_obs, int32_t* next_done, hipStream_t s);
+hipError_t launch_fused_env_obs(int env_kind, int N, const float* env_state, float* next_obs, hipStream_t s);
+hipError_t launch_gauss_env_step(int env_kind, int N, int max_episode_steps, int64_t seed, int64_t env_offset, float* env_state, int32_t* ep_len, float* ep_rew,
+                                 int32_t* reset_count, const float* action, float* obs, float* reward, int32_t* done, hipStream_t s);
 hipError_t launch_cat_env_step(int env_kind, int N, int max_episode_steps, int64_t seed, int64_t env_offset, float* env_state, int32_t* ep_len, float* ep_rew,
                                int32_t* reset_count, const int64_t* action, float* obs, float* reward, int32_t* done, hipStream_t s);
+hipError_t launch_gauss_env_transition(int env_kind, const float* state_in, const float* action, int64_t n, float* next_state, float* obs_out, float* reward,
+                                       int32_t* terminated, hipStream_t s);
 hipError_t launch_cat_env_transition(int env_kind, const float* state_in, const int64_t* action, int64_t n, float* next_state, float* reward, int32_t* terminated,
                                      hipStream_t s);
-hipError_t launch_cat_env_obs(int env_kind, int N, const float* env_state, float* next_obs, hipStream_t s);
-// ppo_evaluate on such an env: GaussEvalArgs' contract on cat_eval_kernel (greedy: the first-index argmax; else the draw keyed (seed, e, step of the episode, 0))
-hipError_t cat_fused_evaluate(int env_kind, int dist_kind, const GenLayout& L, const GaussEvalArgs& a, hipStream_t s);

@@ -1694,27 +1694,8 @@ hipError_t cat_fused_fwd_bwd(const GenLayout& L, const LossParams& hp, const flo
     return hipGetLastError();
 }
 
-// ---- the device envs with real-valued actions (the context's shape is fixed by ppo_ctx_create: obs Env::OBS, D 1) ----
-template <class Env>
-static hipError_t gauss_fused_rollout(const GenLayout& L, const GaussRolloutArgs& r, hipStream_t s) {
-    if (r.N <= 0 || r.T <= 0) return hipSuccess;
-    if (L.obs != Env::OBS || L.gauss != 1) return hipErrorInvalidValue;
-    GfRolloutArgs a{};
-    a.sh = gf_shape(L);
-    a.params = r.params;
-    a.N = r.N; a.T = r.T; a.max_episode_steps = r.max_episode_steps;
-    a.seed = r.seed; a.env_offset = r.env_offset; a.step_base = r.step_base;
-    a.env_state = r.env_state; a.ep_len = r.ep_len; a.ep_rew = r.ep_rew; a.reset_count = r.reset_count;
-    a.obs = r.obs; a.actions = r.actions; a.logprobs = r.logprobs; a.rewards = r.rewards; a.dones = r.dones; a.fin_len = r.fin_len; a.fin_rew = r.fin_rew;
-    a.next_obs = r.next_obs; a.next_done = r.next_done; a.forced = r.forced;
-    const int bytes = gf_lds_floats(4, 4) * 4;
-    static std::atomic<unsigned long long> done{ 0 };
-    const hipError_t e = gf_allow(done, gauss_rollout_kernel<Env>, bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(gauss_rollout_kernel<Env>, dim3((unsigned)((r.N + 63) / 64)), dim3(GF_THREADS), bytes, s, a);
-    return hipGetLastError();
-}
-
+// ---- the device envs of the two fused families (gauss_fused.hpp; the context's shape is fixed by ppo_ctx_create from the env's row: obs Env::OBS, one head of
+// Env::ACTIONS logits, or D = 1) ----
 // env_kind -> trait: f is called with a value of the env's trait type; an env without one gives hipErrorInvalidValue
 template <class F>
 static hipError_t gauss_env_dispatch(int env_kind, F f) {
@@ -1722,80 +1703,6 @@ static hipError_t gauss_env_dispatch(int env_kind, F f) {
     if (env_kind == PPO_ENV_MOUNTAINCAR_CONTINUOUS) return f(GaussEnvMountainCarContinuous{});
     return hipErrorInvalidValue;
 }
-
-hipError_t gauss_fused_rollout(int env_kind, const GenLayout& L, const GaussRolloutArgs& r, hipStream_t s) {
-    return gauss_env_dispatch(env_kind, [&](auto env) { return gauss_fused_rollout<decltype(env)>(L, r, s); });
-}
-
-hipError_t launch_gauss_env_reset(int env_kind, int N, int64_t seed, int64_t env_offset, float* env_state, int32_t* ep_len, float* ep_rew, int32_t* reset_count,
-                                  float* next_obs, int32_t* next_done, hipStream_t s) {
-    if (N <= 0) return hipSuccess;
-    return gauss_env_dispatch(env_kind, [&](auto env) {
-        hipLaunchKernelGGL(gauss_env_reset_kernel<decltype(env)>, dim3((N + 255) / 256), dim3(256), 0, s, N, seed, env_offset, env_state, ep_len, ep_rew, reset_count,
-                           next_obs, next_done);
-        return hipGetLastError();
-    });
-}
-hipError_t launch_gauss_env_step(int env_kind, int N, int max_episode_steps, int64_t seed, int64_t env_offset, float* env_state, int32_t* ep_len, float* ep_rew,
-                                 int32_t* reset_count, const float* action, float* obs, float* reward, int32_t* done, hipStream_t s) {
-    if (N <= 0) return hipSuccess;
-    return gauss_env_dispatch(env_kind, [&](auto env) {
-        hipLaunchKernelGGL(gauss_env_step_kernel<decltype(env)>, dim3((N + 255) / 256), dim3(256), 0, s, N, max_episode_steps, seed, env_offset, env_state, ep_len,
-                           ep_rew, reset_count, action, obs, reward, done);
-        return hipGetLastError();
-    });
-}
-hipError_t launch_gauss_env_transition(int env_kind, const float* state_in, const float* action, int64_t n, float* next_state, float* obs_out, float* reward,
-                                       int32_t* terminated, hipStream_t s) {
-    if (n <= 0) return hipSuccess;
-    if (n >= (1ll << 31) * 256) return hipErrorInvalidValue;
-    return gauss_env_dispatch(env_kind, [&](auto env) {
-        hipLaunchKernelGGL(gauss_env_transition_kernel<decltype(env)>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, state_in, action, n, next_state, obs_out,
-                           reward, terminated);
-        return hipGetLastError();
-    });
-}
-hipError_t launch_gauss_env_obs(int env_kind, int N, const float* env_state, float* next_obs, hipStream_t s) {
-    if (N <= 0) return hipSuccess;
-    return gauss_env_dispatch(env_kind, [&](auto env) {
-        hipLaunchKernelGGL(gauss_env_obs_kernel<decltype(env)>, dim3((N + 255) / 256), dim3(256), 0, s, N, env_state, next_obs);
-        return hipGetLastError();
-    });
-}
-
-// the fold and the evaluation exist for the envs whose observation is their state
-hipError_t gauss_fused_trunc_fold(int env_kind, const GenLayout& L, const GaussFoldArgs& f, hipStream_t s) {
-    if (f.B <= 0 || f.max_episode_steps <= 0) return hipSuccess;   // no limit: no episode is ever cut off
-    if (env_kind != PPO_ENV_MOUNTAINCAR_CONTINUOUS || L.obs != GaussEnvMountainCarContinuous::OBS || L.gauss != 1) return hipErrorInvalidValue;
-    if (f.B >= (1ll << 31)) return hipErrorInvalidValue;
-    GfFoldArgs a{};
-    a.sh = gf_shape(L);
-    a.params = f.params; a.obs = f.obs; a.actions = f.actions; a.fin_len = f.fin_len;
-    a.B = f.B; a.max_episode_steps = f.max_episode_steps; a.gamma = f.gamma;
-    a.rewards = f.rewards; a.ev_count = f.ev_count; a.ev_index = f.ev_index; a.ev_value = f.ev_value; a.ev_cap = f.ev_cap;
-    const int bytes = gf_lds_floats(4, 4) * 4;
-    const unsigned grid = (unsigned)((f.B + DEV_FOLD_THREADS - 1) / DEV_FOLD_THREADS);
-    hipLaunchKernelGGL(gauss_trunc_fold_kernel<GaussEnvMountainCarContinuous>, dim3(grid), dim3(DEV_FOLD_THREADS), bytes, s, a);
-    return hipGetLastError();
-}
-
-hipError_t gauss_fused_evaluate(int env_kind, const GenLayout& L, const GaussEvalArgs& e, hipStream_t s) {
-    if (e.n_episodes <= 0) return hipSuccess;
-    if (env_kind != PPO_ENV_MOUNTAINCAR_CONTINUOUS || L.obs != GaussEnvMountainCarContinuous::OBS || L.gauss != 1) return hipErrorInvalidValue;
-    if (e.max_episode_steps < 1 || e.n_episodes >= (1ll << 31) * 64 || !e.ep_return || !e.ep_length || !e.ep_trunc) return hipErrorInvalidValue;
-    GfEvalArgs a{};
-    a.sh = gf_shape(L);
-    a.params = e.params;
-    a.n_episodes = e.n_episodes; a.seed = e.seed;
-    a.max_episode_steps = e.max_episode_steps; a.greedy = e.greedy != 0;
-    a.ep_return = e.ep_return; a.ep_length = e.ep_length; a.ep_trunc = e.ep_trunc;
-    const int bytes = gf_lds_floats(4, 4) * 4;
-    hipLaunchKernelGGL(gauss_eval_kernel<GaussEnvMountainCarContinuous>, dim3((unsigned)((e.n_episodes + 63) / 64)), dim3(GF_THREADS), bytes, s, a);
-    return hipGetLastError();
-}
-
-// ---- the device envs with integer actions (PPO_ENV_ACROBOT, PPO_ENV_TAXI, PPO_ENV_FROZENLAKE, PPO_ENV_FROZENLAKE8X8, PPO_ENV_BLACKJACK; the context's shape is fixed by ppo_ctx_create: obs Env::OBS, one head of
-// Env::ACTIONS logits) ----
 template <class F>
 static hipError_t cat_env_dispatch(int env_kind, F f) {
     if (env_kind == PPO_ENV_ACROBOT) return f(CatEnvAcrobot{});
@@ -1805,6 +1712,80 @@ static hipError_t cat_env_dispatch(int env_kind, F f) {
     if (env_kind == PPO_ENV_BLACKJACK) return f(CatEnvBlackjack{});
     return hipErrorInvalidValue;
 }
+
+// One row per line of the two dispatchers.  A Gaussian env folds and evaluates where its observation is its state; a categorical env folds where the
+// observation holds the state, and every one evaluates.
+template <class Env>
+static constexpr FusedEnvInfo gauss_env_row(int kind, const char* name, int max_steps, FusedEnvTexts t) {
+    return { kind, name, FUSED_GAUSS, Env::OBS, Env::STATE, 1, 1u << PPO_DIST_GAUSSIAN, Env::OBS_IS_STATE, Env::OBS_IS_STATE, Env::OBS_IS_STATE, max_steps,
+             t, {} };
+}
+template <class Env>
+static constexpr FusedEnvInfo cat_env_row(int kind, const char* name, int max_steps, FusedEnvTexts t, FusedStateCheck c = {}) {
+    static_assert(Env::STATE == 4, "FusedStateCheck::hi");
+    return { kind, name, FUSED_CAT, Env::OBS, Env::STATE, Env::ACTIONS, 1u << PPO_DIST_CATEGORICAL | (Env::HAS_MASK ? 1u << PPO_DIST_MASKED : 0u),
+             Env::OBS_IS_STATE, Env::STATE_FROM_OBS, true, max_steps, t, c };
+}
+// hand = t + 32 * ace + 64 * show: t in 2..31, show in 1..10; no bits above: hand <= BLACKJACK_HAND_MAX
+static bool blackjack_word_ok(int word, int value) { return word != 0 || ((value & 31) >= 2 && (value >> 6) >= 1); }
+static_assert(FROZENLAKE_WORD_MAX == 16777215 && BLACKJACK_WORD_MAX == 16777215, "the rows' FusedStateCheck::words");
+
+static const FusedEnvInfo fused_env_rows[] = {
+    gauss_env_row<GaussEnvPendulum>(PPO_ENV_PENDULUM, "PPO_ENV_PENDULUM", PENDULUM_MAX_EPISODE_STEPS,
+        { "one real-valued action", "one action dimension, the torque", "the angle is not wrapped and the device sinf / cosf hold for |theta| < 120",
+          "PPO_ENV_PENDULUM observation (cos, sin, theta_dot) does not hold theta" }),
+    gauss_env_row<GaussEnvMountainCarContinuous>(PPO_ENV_MOUNTAINCAR_CONTINUOUS, "PPO_ENV_MOUNTAINCAR_CONTINUOUS", 0,
+        { "one real-valued action", "one action dimension, the force", "an episode that never reaches the goal ends at the time limit only", nullptr }),
+    cat_env_row<CatEnvAcrobot>(PPO_ENV_ACROBOT, "PPO_ENV_ACROBOT", 0,
+        { "one of three discrete actions without a mask", "one head of three actions, the torque -1, 0 or +1",
+          "an episode that never swings up ends at the time limit only",
+          "PPO_ENV_ACROBOT observation (cos, sin of two angles, two velocities) does not hold the angles" }),
+    cat_env_row<CatEnvTaxi>(PPO_ENV_TAXI, "PPO_ENV_TAXI", 0,
+        { "one of six discrete actions, drawn under the env's action mask or without it", "one head of six actions (south, north, east, west, pickup, dropoff)",
+          "an episode that never delivers the passenger ends at the time limit only", nullptr },
+        { "PPO_ENV_TAXI: row, col, pass in 0..4, dest in 0..3", { 4, 4, 4, 3 }, nullptr }),
+    // both maps say "PPO_ENV_FROZENLAKE" where they speak of the observation and of the state
+    cat_env_row<CatEnvFrozenLake<4>>(PPO_ENV_FROZENLAKE, "PPO_ENV_FROZENLAKE", FROZENLAKE_WORD_MAX,
+        { "one of four discrete actions without a mask", "one head of four actions (left, down, right, up)",
+          "the episode's step count is a state word held exactly in f32, and it keys the env's draws",
+          "PPO_ENV_FROZENLAKE observation (the one-hot of the cell) holds neither the step count nor the key the env's slip is drawn from" },
+        { "PPO_ENV_FROZENLAKE: cell in 0..15; j, k0, k1 in 0..16777215", { CatEnvFrozenLake<4>::OBS - 1, FROZENLAKE_WORD_MAX, FROZENLAKE_WORD_MAX, FROZENLAKE_WORD_MAX },
+          nullptr }),
+    cat_env_row<CatEnvFrozenLake<8>>(PPO_ENV_FROZENLAKE8X8, "PPO_ENV_FROZENLAKE8X8", FROZENLAKE_WORD_MAX,
+        { "one of four discrete actions without a mask", "one head of four actions (left, down, right, up)",
+          "the episode's step count is a state word held exactly in f32, and it keys the env's draws",
+          "PPO_ENV_FROZENLAKE observation (the one-hot of the cell) holds neither the step count nor the key the env's slip is drawn from" },
+        { "PPO_ENV_FROZENLAKE: cell in 0..63; j, k0, k1 in 0..16777215", { CatEnvFrozenLake<8>::OBS - 1, FROZENLAKE_WORD_MAX, FROZENLAKE_WORD_MAX, FROZENLAKE_WORD_MAX },
+          nullptr }),
+    cat_env_row<CatEnvBlackjack>(PPO_ENV_BLACKJACK, "PPO_ENV_BLACKJACK", BLACKJACK_WORD_MAX,
+        { "one of two discrete actions without a mask", "one head of two actions (stick, hit)",
+          "as on PPO_ENV_FROZENLAKE: the state's words are integers held exactly in f32",
+          "PPO_ENV_BLACKJACK observation (the player's sum, the dealer's showing card, the usable ace) holds neither the card count nor the key the env's cards "
+          "are drawn from" },
+        { "PPO_ENV_BLACKJACK: hand = t + 32 * ace + 64 * show with t in 2..31, ace in 0..1, show in 1..10; n, k0, k1 in 0..16777215",
+          { BLACKJACK_HAND_MAX, BLACKJACK_WORD_MAX, BLACKJACK_WORD_MAX, BLACKJACK_WORD_MAX }, blackjack_word_ok }),
+};
+const char* fused_env_names(FusedFamily family) {
+    return family == FUSED_GAUSS ? "PPO_ENV_PENDULUM and PPO_ENV_MOUNTAINCAR_CONTINUOUS"
+                                 : "PPO_ENV_ACROBOT, PPO_ENV_TAXI, the two PPO_ENV_FROZENLAKE kinds and PPO_ENV_BLACKJACK";
+}
+
+const FusedEnvInfo* fused_env_info(int env_kind) {
+    for (const FusedEnvInfo& e : fused_env_rows)
+        if (e.env_kind == env_kind) return &e;
+    return nullptr;
+}
+
+// the family's dispatcher: fg is called with a GaussEnv* trait, fc with a CatEnv* one
+template <class FG, class FC>
+static hipError_t fused_env_dispatch(int env_kind, FG fg, FC fc) {
+    const FusedEnvInfo* e = fused_env_info(env_kind);
+    if (!e) return hipErrorInvalidValue;
+    return e->family == FUSED_GAUSS ? gauss_env_dispatch(env_kind, fg) : cat_env_dispatch(env_kind, fc);
+}
+
+template <class Env>
+static bool gauss_env_shape_ok(const GenLayout& L) { return L.obs == Env::OBS && L.gauss == 1; }
 template <class Env>
 static bool cat_env_shape_ok(const GenLayout& L) { return L.obs == Env::OBS && L.gauss == 0 && L.n_heads == 1 && L.act == Env::ACTIONS; }
 // a masked policy runs on an env that forms a mask, and on no other (ppo_ctx_create)
@@ -1813,11 +1794,50 @@ static bool cat_env_dist_ok(int dist_kind) { return dist_kind == PPO_DIST_CATEGO
 template <class Env>
 static int cat_env_lds_bytes() { return gf_lds_floats(gf_pad4(Env::OBS), gf_pad4(Env::ACTIONS)) * 4; }
 
-bool cat_fused_env_serves(int env_kind) {
-    return env_kind == PPO_ENV_ACROBOT || env_kind == PPO_ENV_TAXI || env_kind == PPO_ENV_FROZENLAKE || env_kind == PPO_ENV_FROZENLAKE8X8 ||
-           env_kind == PPO_ENV_BLACKJACK;
+// the kernels' argument structs from the launchers' (GfRolloutArgs / CfRolloutArgs, GfFoldArgs / CfFoldArgs: the same fields, the family's action types)
+template <class KernelArgs>
+static KernelArgs rollout_kernel_args(const GenLayout& L, const FusedRolloutArgs& r) {
+    KernelArgs a{};
+    a.sh = gf_shape(L);
+    a.params = r.params;
+    a.N = r.N; a.T = r.T; a.max_episode_steps = r.max_episode_steps;
+    a.seed = r.seed; a.env_offset = r.env_offset; a.step_base = r.step_base;
+    a.env_state = r.env_state; a.ep_len = r.ep_len; a.ep_rew = r.ep_rew; a.reset_count = r.reset_count;
+    a.obs = r.obs; a.actions = static_cast<decltype(a.actions)>(r.actions); a.logprobs = r.logprobs; a.rewards = r.rewards; a.dones = r.dones;
+    a.fin_len = r.fin_len; a.fin_rew = r.fin_rew;
+    a.next_obs = r.next_obs; a.next_done = r.next_done; a.forced = static_cast<decltype(a.forced)>(r.forced);
+    return a;
+}
+template <class KernelArgs>
+static KernelArgs fold_kernel_args(const GenLayout& L, const FusedFoldArgs& f) {
+    KernelArgs a{};
+    a.sh = gf_shape(L);
+    a.params = f.params; a.obs = f.obs; a.actions = static_cast<decltype(a.actions)>(f.actions); a.fin_len = f.fin_len;
+    a.B = f.B; a.max_episode_steps = f.max_episode_steps; a.gamma = f.gamma;
+    a.rewards = f.rewards; a.ev_count = f.ev_count; a.ev_index = f.ev_index; a.ev_value = f.ev_value; a.ev_cap = f.ev_cap;
+    return a;
+}
+static GfEvalArgs eval_kernel_args(const GenLayout& L, const FusedEvalArgs& e) {
+    GfEvalArgs a{};
+    a.sh = gf_shape(L);
+    a.params = e.params;
+    a.n_episodes = e.n_episodes; a.seed = e.seed;
+    a.max_episode_steps = e.max_episode_steps; a.greedy = e.greedy != 0;
+    a.ep_return = e.ep_return; a.ep_length = e.ep_length; a.ep_trunc = e.ep_trunc;
+    return a;
 }
 
+template <class Env>
+static hipError_t gauss_rollout_launch(const GenLayout& L, const FusedRolloutArgs& r, hipStream_t s) {
+    if (!gauss_env_shape_ok<Env>(L)) return hipErrorInvalidValue;
+    const GfRolloutArgs a = rollout_kernel_args<GfRolloutArgs>(L, r);
+    const int bytes = gf_lds_floats(4, 4) * 4;
+    static std::atomic<unsigned long long> done{ 0 };
+    const hipError_t e = gf_allow(done, gauss_rollout_kernel<Env>, bytes);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(gauss_rollout_kernel<Env>, dim3((unsigned)((r.N + 63) / 64)), dim3(GF_THREADS), bytes, s, a);
+    return hipGetLastError();
+}
 // cat_rollout_kernel<Env, DIST> for the context's distribution; the attribute where the carve passes 64 KB (PPO_ENV_TAXI: 67 136 bytes; PPO_ENV_FROZENLAKE8X8: 88 256; PPO_ENV_BLACKJACK: 79 808)
 template <class Env, int DIST>
 static hipError_t cat_rollout_launch(const CfRolloutArgs& a, int N, hipStream_t s) {
@@ -1838,20 +1858,13 @@ static hipError_t cat_eval_launch(const GfEvalArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t cat_fused_rollout(int env_kind, int dist_kind, const GenLayout& L, const CatRolloutArgs& r, hipStream_t s) {
+hipError_t launch_fused_env_rollout(int env_kind, int dist_kind, const GenLayout& L, const FusedRolloutArgs& r, hipStream_t s) {
     if (r.N <= 0 || r.T <= 0) return hipSuccess;
-    return cat_env_dispatch(env_kind, [&](auto env) {
+    return fused_env_dispatch(env_kind, [&](auto env) { return gauss_rollout_launch<decltype(env)>(L, r, s); }, [&](auto env) {
         using Env = decltype(env);
         if (!cat_env_shape_ok<Env>(L) || !cat_env_dist_ok<Env>(dist_kind)) return hipErrorInvalidValue;
-        CfRolloutArgs a{};
-        a.sh = gf_shape(L);
-        a.params = r.params;
-        a.N = r.N; a.T = r.T; a.max_episode_steps = r.max_episode_steps;
-        a.seed = r.seed; a.env_offset = r.env_offset; a.step_base = r.step_base;
-        a.env_state = r.env_state; a.ep_len = r.ep_len; a.ep_rew = r.ep_rew; a.reset_count = r.reset_count;
-        a.obs = r.obs; a.masks = r.masks; a.actions = r.actions; a.logprobs = r.logprobs; a.rewards = r.rewards; a.dones = r.dones;
-        a.fin_len = r.fin_len; a.fin_rew = r.fin_rew;
-        a.next_obs = r.next_obs; a.next_done = r.next_done; a.forced = r.forced;
+        CfRolloutArgs a = rollout_kernel_args<CfRolloutArgs>(L, r);
+        a.masks = r.masks;
         if constexpr (Env::HAS_MASK) {
             if (dist_kind == PPO_DIST_MASKED) return cat_rollout_launch<Env, PPO_DIST_MASKED>(a, r.N, s);
         }
@@ -1859,26 +1872,30 @@ hipError_t cat_fused_rollout(int env_kind, int dist_kind, const GenLayout& L, co
     });
 }
 
-// ppo_env_truncation_bootstrap on an env whose observation holds its state (cat_trunc_fold_kernel)
-bool cat_fused_env_folds(int env_kind) { return env_kind == PPO_ENV_TAXI; }
-hipError_t cat_fused_trunc_fold(int env_kind, const GenLayout& L, const CatFoldArgs& f, hipStream_t s) {
+// the fold exists for the envs whose stored observation holds the state
+hipError_t fused_env_trunc_fold(int env_kind, const GenLayout& L, const FusedFoldArgs& f, hipStream_t s) {
     if (f.B <= 0 || f.max_episode_steps <= 0) return hipSuccess;   // no limit: no episode is ever cut off
     if (f.B >= (1ll << 31)) return hipErrorInvalidValue;
-    return cat_env_dispatch(env_kind, [&](auto env) {
+    const unsigned grid = (unsigned)((f.B + DEV_FOLD_THREADS - 1) / DEV_FOLD_THREADS);
+    return fused_env_dispatch(env_kind, [&](auto env) {
+        using Env = decltype(env);
+        if constexpr (Env::OBS_IS_STATE) {
+            if (!gauss_env_shape_ok<Env>(L)) return hipErrorInvalidValue;
+            const int bytes = gf_lds_floats(4, 4) * 4;
+            hipLaunchKernelGGL(gauss_trunc_fold_kernel<Env>, dim3(grid), dim3(DEV_FOLD_THREADS), bytes, s, fold_kernel_args<GfFoldArgs>(L, f));
+            return hipGetLastError();
+        } else {
+            return hipErrorInvalidValue;
+        }
+    }, [&](auto env) {
         using Env = decltype(env);
         if constexpr (Env::STATE_FROM_OBS) {
             if (!cat_env_shape_ok<Env>(L)) return hipErrorInvalidValue;
-            CfFoldArgs a{};
-            a.sh = gf_shape(L);
-            a.params = f.params; a.obs = f.obs; a.actions = f.actions; a.fin_len = f.fin_len;
-            a.B = f.B; a.max_episode_steps = f.max_episode_steps; a.gamma = f.gamma;
-            a.rewards = f.rewards; a.ev_count = f.ev_count; a.ev_index = f.ev_index; a.ev_value = f.ev_value; a.ev_cap = f.ev_cap;
             const int bytes = cat_fold_lds_bytes<Env>();
             static std::atomic<unsigned long long> done{ 0 };
             const hipError_t e = gf_allow(done, cat_trunc_fold_kernel<Env>, bytes);
             if (e != hipSuccess) return e;
-            const unsigned grid = (unsigned)((f.B + DEV_FOLD_THREADS - 1) / DEV_FOLD_THREADS);
-            hipLaunchKernelGGL(cat_trunc_fold_kernel<Env>, dim3(grid), dim3(DEV_FOLD_THREADS), bytes, s, a);
+            hipLaunchKernelGGL(cat_trunc_fold_kernel<Env>, dim3(grid), dim3(DEV_FOLD_THREADS), bytes, s, fold_kernel_args<CfFoldArgs>(L, f));
             return hipGetLastError();
         } else {
             return hipErrorInvalidValue;
@@ -1886,12 +1903,60 @@ hipError_t cat_fused_trunc_fold(int env_kind, const GenLayout& L, const CatFoldA
     });
 }
 
-hipError_t launch_cat_env_reset(int env_kind, int N, int64_t seed, int64_t env_offset, float* env_state, int32_t* ep_len, float* ep_rew, int32_t* reset_count,
-                                float* next_obs, int32_t* next_done, hipStream_t s) {
+// the Gaussian evaluation exists for the envs whose observation is their state
+hipError_t fused_env_evaluate(int env_kind, int dist_kind, const GenLayout& L, const FusedEvalArgs& e, hipStream_t s) {
+    if (e.n_episodes <= 0) return hipSuccess;
+    if (e.max_episode_steps < 1 || e.n_episodes >= (1ll << 31) * 64 || !e.ep_return || !e.ep_length || !e.ep_trunc) return hipErrorInvalidValue;
+    return fused_env_dispatch(env_kind, [&](auto env) {
+        using Env = decltype(env);
+        if constexpr (Env::OBS_IS_STATE) {
+            if (!gauss_env_shape_ok<Env>(L)) return hipErrorInvalidValue;
+            const int bytes = gf_lds_floats(4, 4) * 4;
+            hipLaunchKernelGGL(gauss_eval_kernel<Env>, dim3((unsigned)((e.n_episodes + 63) / 64)), dim3(GF_THREADS), bytes, s, eval_kernel_args(L, e));
+            return hipGetLastError();
+        } else {
+            return hipErrorInvalidValue;
+        }
+    }, [&](auto env) {
+        using Env = decltype(env);
+        if (!cat_env_shape_ok<Env>(L) || !cat_env_dist_ok<Env>(dist_kind)) return hipErrorInvalidValue;
+        const GfEvalArgs a = eval_kernel_args(L, e);
+        if constexpr (Env::HAS_MASK) {
+            if (dist_kind == PPO_DIST_MASKED) return cat_eval_launch<Env, PPO_DIST_MASKED>(a, s);
+        }
+        return cat_eval_launch<Env, PPO_DIST_CATEGORICAL>(a, s);
+    });
+}
+
+hipError_t launch_fused_env_reset(int env_kind, int N, int64_t seed, int64_t env_offset, float* env_state, int32_t* ep_len, float* ep_rew, int32_t* reset_count,
+                                  float* next_obs, int32_t* next_done, hipStream_t s) {
     if (N <= 0) return hipSuccess;
-    return cat_env_dispatch(env_kind, [&](auto env) {
+    return fused_env_dispatch(env_kind, [&](auto env) {
+        hipLaunchKernelGGL(gauss_env_reset_kernel<decltype(env)>, dim3((N + 255) / 256), dim3(256), 0, s, N, seed, env_offset, env_state, ep_len, ep_rew, reset_count,
+                           next_obs, next_done);
+        return hipGetLastError();
+    }, [&](auto env) {
         hipLaunchKernelGGL(cat_env_reset_kernel<decltype(env)>, dim3((N + 255) / 256), dim3(256), 0, s, N, seed, env_offset, env_state, ep_len, ep_rew, reset_count,
                            next_obs, next_done);
+        return hipGetLastError();
+    });
+}
+hipError_t launch_fused_env_obs(int env_kind, int N, const float* env_state, float* next_obs, hipStream_t s) {
+    if (N <= 0) return hipSuccess;
+    return fused_env_dispatch(env_kind, [&](auto env) {
+        hipLaunchKernelGGL(gauss_env_obs_kernel<decltype(env)>, dim3((N + 255) / 256), dim3(256), 0, s, N, env_state, next_obs);
+        return hipGetLastError();
+    }, [&](auto env) {
+        hipLaunchKernelGGL(cat_env_obs_kernel<decltype(env)>, dim3((N + 255) / 256), dim3(256), 0, s, N, env_state, next_obs);
+        return hipGetLastError();
+    });
+}
+hipError_t launch_gauss_env_step(int env_kind, int N, int max_episode_steps, int64_t seed, int64_t env_offset, float* env_state, int32_t* ep_len, float* ep_rew,
+                                 int32_t* reset_count, const float* action, float* obs, float* reward, int32_t* done, hipStream_t s) {
+    if (N <= 0) return hipSuccess;
+    return gauss_env_dispatch(env_kind, [&](auto env) {
+        hipLaunchKernelGGL(gauss_env_step_kernel<decltype(env)>, dim3((N + 255) / 256), dim3(256), 0, s, N, max_episode_steps, seed, env_offset, env_state, ep_len,
+                           ep_rew, reset_count, action, obs, reward, done);
         return hipGetLastError();
     });
 }
@@ -1904,6 +1969,16 @@ hipError_t launch_cat_env_step(int env_kind, int N, int max_episode_steps, int64
         return hipGetLastError();
     });
 }
+hipError_t launch_gauss_env_transition(int env_kind, const float* state_in, const float* action, int64_t n, float* next_state, float* obs_out, float* reward,
+                                       int32_t* terminated, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    if (n >= (1ll << 31) * 256) return hipErrorInvalidValue;
+    return gauss_env_dispatch(env_kind, [&](auto env) {
+        hipLaunchKernelGGL(gauss_env_transition_kernel<decltype(env)>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, state_in, action, n, next_state, obs_out,
+                           reward, terminated);
+        return hipGetLastError();
+    });
+}
 hipError_t launch_cat_env_transition(int env_kind, const float* state_in, const int64_t* action, int64_t n, float* next_state, float* reward, int32_t* terminated,
                                      hipStream_t s) {
     if (n <= 0) return hipSuccess;
@@ -1912,30 +1987,5 @@ hipError_t launch_cat_env_transition(int env_kind, const float* state_in, const 
         hipLaunchKernelGGL(cat_env_transition_kernel<decltype(env)>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, state_in, action, n, next_state, reward,
                            terminated);
         return hipGetLastError();
-    });
-}
-hipError_t launch_cat_env_obs(int env_kind, int N, const float* env_state, float* next_obs, hipStream_t s) {
-    if (N <= 0) return hipSuccess;
-    return cat_env_dispatch(env_kind, [&](auto env) {
-        hipLaunchKernelGGL(cat_env_obs_kernel<decltype(env)>, dim3((N + 255) / 256), dim3(256), 0, s, N, env_state, next_obs);
-        return hipGetLastError();
-    });
-}
-hipError_t cat_fused_evaluate(int env_kind, int dist_kind, const GenLayout& L, const GaussEvalArgs& e, hipStream_t s) {
-    if (e.n_episodes <= 0) return hipSuccess;
-    if (e.max_episode_steps < 1 || e.n_episodes >= (1ll << 31) * 64 || !e.ep_return || !e.ep_length || !e.ep_trunc) return hipErrorInvalidValue;
-    return cat_env_dispatch(env_kind, [&](auto env) {
-        using Env = decltype(env);
-        if (!cat_env_shape_ok<Env>(L) || !cat_env_dist_ok<Env>(dist_kind)) return hipErrorInvalidValue;
-        GfEvalArgs a{};
-        a.sh = gf_shape(L);
-        a.params = e.params;
-        a.n_episodes = e.n_episodes; a.seed = e.seed;
-        a.max_episode_steps = e.max_episode_steps; a.greedy = e.greedy != 0;
-        a.ep_return = e.ep_return; a.ep_length = e.ep_length; a.ep_trunc = e.ep_trunc;
-        if constexpr (Env::HAS_MASK) {
-            if (dist_kind == PPO_DIST_MASKED) return cat_eval_launch<Env, PPO_DIST_MASKED>(a, s);
-        }
-        return cat_eval_launch<Env, PPO_DIST_CATEGORICAL>(a, s);
     });
 }
