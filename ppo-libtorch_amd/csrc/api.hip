@@ -119,6 +119,25 @@ struct StatsSnap {
     double lr;
 };
 
+// One device list of truncation events, (flat index t * N + n, V(final obs)), that a fold kernel appends to with one atomicAdd per workgroup.  A context holds
+// three: one for its own env (ppo_env_truncation_bootstrap) and two for device-fed rollouts (ppo_dev_observe with flags), used by alternate rollouts so that
+// the last CLOSED rollout's events stay readable while the next one is fed.  A list is made by the first call that needs it and kept (the allocation policy of
+// ppo_ctx_create in ppo_hip.h).  Its life, one rollout at a time (events_* below): clear the counter in stream order in front of the rollout's first fold;
+// hand count / index / value / cap to every fold launch; close -- copy the counter to the pinned word and record the event, behind the last fold; read --
+// wait for THAT event only (the update behind it keeps running), copy the entries, sort them by index on the host (trunc_events.hpp) and keep them.
+struct DevEventList {
+    int32_t* count = nullptr;     // device [1] (+ padding)
+    int32_t* count_h = nullptr;   // pinned [1]
+    int32_t* index = nullptr;
+    float* value = nullptr;
+    int64_t cap = 0;              // entries of index / value; 0 until every piece is there
+    hipEvent_t ev = nullptr;      // behind the rollout's last fold and the copy of its counter
+    bool closed = false;          // the last rollout folded into this list, and its folds and the counter copy are behind ev
+    bool fetched = false;         // ... and its events are in idx / val already (sorted by index)
+    std::vector<int32_t> idx;
+    std::vector<float> val;
+};
+
 struct ppo_ctx {
     ppo_config cfg{};
     NetLayout L{};
@@ -247,36 +266,17 @@ struct ppo_ctx {
     std::vector<int32_t> trunc_order;      // sorting scratch, kept
     std::vector<float> trunc_sorted;
     // caller-stepped envs on the device (ppo_dev_*): a rollout is host-fed or device-fed as a whole, decided by its first act.  A device-fed step is
-    // committed by ppo_dev_observe at once (host_staged stays false).  Truncation events of device-fed rollouts live in two device lists used by
-    // alternate rollouts, so that the last CLOSED rollout's events stay readable while the next one is fed; each list: a counter, [T * N] indices, [T * N]
-    // values, allocated by the first ppo_dev_observe that passes flags.  dev_count_h: pinned copies of the two counters, taken at ppo_host_rollout_end.
+    // committed by ppo_dev_observe at once (host_staged stays false), and its truncation events go to one of two lists (DevEventList).
     int host_feed = 0;                // the open rollout: 0 = no act yet, 1 = host-fed (ppo_host_act), 2 = device-fed (ppo_dev_act)
     hipEvent_t dev_ev_in = nullptr, dev_ev_out = nullptr;   // the hand-over between the caller's stream and the context's (created by the first call that needs them)
-    int32_t* dev_count = nullptr;     // device [2] (+ padding)
-    int32_t* dev_count_h = nullptr;   // pinned [2]
-    int32_t* dev_index[2] = { nullptr, nullptr };
-    float* dev_value[2] = { nullptr, nullptr };
-    int64_t dev_cap = 0;
-    hipEvent_t dev_fold_ev[2] = { nullptr, nullptr };   // behind the last fold of the rollout that used the list and the copy of its counter
+    DevEventList dev_events[2];
     int dev_list = 0;                 // the list of the open (else: the last) device-fed rollout
-    bool dev_list_used = false;       // the open rollout has enqueued a fold (its counter was cleared in front of it)
+    bool dev_list_used = false;       // the open rollout has enqueued a fold (the list's counter was cleared in front of it)
     int dev_last = -1;                // >= 0: the last closed rollout was device-fed and enqueued folds into this list
-    bool dev_last_fetched = false;    // ... and its events are in dev_last_idx / dev_last_val already (ppo_host_truncations, sorted by index)
-    std::vector<int32_t> dev_last_idx;
-    std::vector<float> dev_last_val;
-    // time-limit truncations of the context's own device env (ppo_env_truncation_bootstrap): off unless that call turned it on.  One device event list -- a
-    // counter, [T * N] indices, [T * N] values -- a pinned copy of the counter and an event, made by the first enable and kept.  ppo_rollout clears the counter,
-    // enqueues the fold behind the value launch, copies the counter back and records the event; ppo_env_truncations waits for that event only.
+    // time-limit truncations of the context's own device env (ppo_env_truncation_bootstrap): off unless that call turned it on.  With the switch on,
+    // ppo_rollout enqueues the fold behind the value launch and closes the list at once (env_fold_truncations).
     bool envt_on = false;
-    int32_t* envt_count = nullptr;    // device [1] (+ padding)
-    int32_t* envt_count_h = nullptr;  // pinned [1]
-    int32_t* envt_index = nullptr;
-    float* envt_value = nullptr;
-    hipEvent_t envt_ev = nullptr;     // behind the last rollout's fold and the copy of its counter
-    bool envt_last = false;           // the last rollout enqueued a fold
-    bool envt_fetched = false;        // ... and its events are in envt_idx / envt_val already (sorted by index)
-    std::vector<int32_t> envt_idx;
-    std::vector<float> envt_val;
+    DevEventList env_events;
     // observation normalisation (ppo_obs_norm_*): off unless ppo_obs_norm_enable turned it on.  The statistics (f64 mean[O] | var[O]) and the two [N,O]
     // scratches (the normalised step the commit reads; the normalised final observations of a device-fed fold) are allocated by the first call that needs
     // them and kept; the row count lives here, on the host: it grows by the batch's rows per update.
@@ -425,6 +425,62 @@ static hipError_t dalloc_buf(ppo_ctx* c, int which, size_t count) {
 template <class Tp>
 static Tp* B_(ppo_ctx* c, int which) { return static_cast<Tp*>(c->buf[which]); }
 
+// DevEventList's life cycle.  Every step but events_read only enqueues or allocates: ppo_dev_observe, which must not wait, goes through the first three.
+// Each piece is made once, so a call repeated after a failed allocation completes the list.  The counter is cleared in stream order (events_clear), not here.
+static ppo_status events_reserve(ppo_ctx* c, DevEventList& l, int64_t cap) {
+    if (l.cap > 0) return PPO_OK;
+    if (!l.ev) HIPCHK(c, hipEventCreateWithFlags(&l.ev, hipEventDisableTiming));
+    if (!l.count_h) {
+        HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&l.count_h), 4 * sizeof(int32_t), hipHostMallocDefault));
+        l.count_h[0] = 0;
+    }
+    if (!l.count) HIPCHK(c, dalloc(c, &l.count, 4, false));
+    if (!l.index) HIPCHK(c, dalloc(c, &l.index, (size_t)cap, false));
+    if (!l.value) HIPCHK(c, dalloc(c, &l.value, (size_t)cap, false));
+    l.cap = cap;
+    return PPO_OK;
+}
+static ppo_status events_clear(ppo_ctx* c, DevEventList& l) {
+    l.closed = false;
+    HIPCHK(c, hipMemsetAsync(l.count, 0, sizeof(int32_t), c->stream));
+    return PPO_OK;
+}
+template <class FoldArgs>   // DevFoldArgs, EnvFoldArgs, FusedFoldArgs
+static void events_sink(const DevEventList& l, FoldArgs& f) { f.ev_count = l.count; f.ev_index = l.index; f.ev_value = l.value; f.ev_cap = l.cap; }
+static ppo_status events_close(ppo_ctx* c, DevEventList& l) {
+    HIPCHK(c, hipMemcpyAsync(l.count_h, l.count, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipEventRecord(l.ev, c->stream));
+    l.closed = true;
+    l.fetched = false;
+    return PPO_OK;
+}
+// The array rules of ppo_host_truncations (trunc_events.hpp: copy_events_out).  A list that is not closed holds no event of the last rollout.
+static ppo_status events_read(ppo_ctx* c, DevEventList& l, const char* what, int64_t* count, int32_t* index_h, float* value_h, int64_t cap) {
+    if (!l.closed) {
+        l.idx.clear();
+        l.val.clear();
+    } else if (!l.fetched) {   // on the device, in the order the workgroups got there
+        DeviceGuard dev_guard(c);
+        HIPCHK(c, hipEventSynchronize(l.ev));
+        const int64_t n = clamp_event_count(l.count_h[0], l.cap);
+        std::vector<int32_t> ix((size_t)n);
+        std::vector<float> va((size_t)n);
+        if (n > 0) {
+            HIPCHK(c, hipMemcpy(ix.data(), l.index, (size_t)n * 4, hipMemcpyDeviceToHost));
+            HIPCHK(c, hipMemcpy(va.data(), l.value, (size_t)n * 4, hipMemcpyDeviceToHost));
+        }
+        sort_events(ix, va, l.idx, l.val);
+        l.fetched = true;
+    }
+    if (!copy_events_out(l.idx, l.val, count, index_h, value_h, cap))
+        return fail(c, PPO_ERR_INVALID, "%s: room for %lld events, the last rollout had %lld", what, (long long)cap, (long long)l.idx.size());
+    return PPO_OK;
+}
+static void events_release(DevEventList& l) {
+    if (l.count_h) (void)hipHostFree(l.count_h);
+    if (l.ev) (void)hipEventDestroy(l.ev);
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // host helpers
 // ---------------------------------------------------------------------------------------------------------
@@ -531,10 +587,7 @@ extern "C" void ppo_ctx_destroy(ppo_ctx* c) {
     if (c->trunc_ev) (void)hipEventDestroy(c->trunc_ev);
     if (c->dev_ev_in) (void)hipEventDestroy(c->dev_ev_in);
     if (c->dev_ev_out) (void)hipEventDestroy(c->dev_ev_out);
-    for (hipEvent_t e : c->dev_fold_ev) if (e) (void)hipEventDestroy(e);
-    if (c->dev_count_h) (void)hipHostFree(c->dev_count_h);
-    if (c->envt_count_h) (void)hipHostFree(c->envt_count_h);
-    if (c->envt_ev) (void)hipEventDestroy(c->envt_ev);
+    for (DevEventList* l : { &c->dev_events[0], &c->dev_events[1], &c->env_events }) events_release(*l);
     if (c->wr_host) (void)hipHostFree(c->wr_host);
     if (c->snap) (void)hipHostFree(c->snap);
     if (c->es_host) (void)hipHostFree(c->es_host);
@@ -1535,49 +1588,46 @@ static inline OptGuard opt_guard(const ppo_ctx* c) {
     return g;
 }
 
-// ppo_env_truncation_bootstrap's launch: the episodes of the rollout just enqueued that the time limit cut off get r + gamma V(final observation)
-// (ppo_internal.hpp: EnvFoldArgs).  The critic is the one launch_rollout's tail fills PPO_BUF_VALUES with -- launch_values_mfma for both envs, whatever
-// kernel_flags and the weight range chose for the actor -- as in bootstrap_launch, which counts no fall-back either.
-static ppo_status env_fold_truncations(ppo_ctx* c) {
-    EnvFoldArgs f{};
-    f.obs = B_<float>(c, PPO_BUF_OBS);
-    f.actions = B_<int32_t>(c, PPO_BUF_ACTIONS);
-    f.fin_len = B_<int32_t>(c, PPO_BUF_FIN_LEN);
-    f.B = c->B; f.H = c->H;
-    f.env_kind = c->cfg.env_kind;
-    f.max_episode_steps = c->cfg.max_episode_steps;
-    f.gamma = c->cfg.gamma;
-    f.rewards = B_<float>(c, PPO_BUF_REWARDS);
-    f.ev_count = c->envt_count; f.ev_index = c->envt_index; f.ev_value = c->envt_value; f.ev_cap = c->B;
-    HIPCHK(c, hipMemsetAsync(c->envt_count, 0, sizeof(int32_t), c->stream));
-    HIPCHK(c, launch_env_trunc_fold_mfma(B_<float>(c, PPO_BUF_PARAMS), c->L, f, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->envt_count_h, c->envt_count, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipEventRecord(c->envt_ev, c->stream));
-    c->envt_last = true;
-    c->envt_fetched = false;
-    return PPO_OK;
-}
+// The reference-shape critic on the matrix cores (values_mfma_kernel and the kernels that share its tile body) serves these observation widths; the vector
+// critic takes the others.  A context on the generic engine (c->gen) asks neither.
+static inline bool critic_is_mfma(const ppo_ctx* c) { return c->O == 4 || c->O == 2; }
 
-// ppo_env_truncation_bootstrap's launch on a fused device env that folds: env_fold_truncations on the fused critic, the one gen_values fills PPO_BUF_VALUES
-// with (gauss_fused.hpp: FusedFoldArgs).  None of the launches ppo_gauss_fused_launches counts.
-static ppo_status fused_env_fold_truncations(ppo_ctx* c) {
-    FusedFoldArgs f{};
-    f.params = B_<float>(c, PPO_BUF_PARAMS);
-    f.obs = B_<float>(c, PPO_BUF_OBS);
-    f.actions = c->buf[PPO_BUF_ACTIONS];
-    f.fin_len = B_<int32_t>(c, PPO_BUF_FIN_LEN);
-    f.B = c->B;
-    f.max_episode_steps = c->cfg.max_episode_steps;
-    f.gamma = c->cfg.gamma;
-    f.rewards = B_<float>(c, PPO_BUF_REWARDS);
-    f.ev_count = c->envt_count; f.ev_index = c->envt_index; f.ev_value = c->envt_value; f.ev_cap = c->B;
-    HIPCHK(c, hipMemsetAsync(c->envt_count, 0, sizeof(int32_t), c->stream));
-    HIPCHK(c, fused_env_trunc_fold(c->cfg.env_kind, c->gen->L, f, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->envt_count_h, c->envt_count, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipEventRecord(c->envt_ev, c->stream));
-    c->envt_last = true;
-    c->envt_fetched = false;
-    return PPO_OK;
+// ppo_env_truncation_bootstrap's launch, behind a rollout's critic launches and in front of the scan: the episodes of the rollout just enqueued that the
+// time limit cut off get r + gamma V(final observation).  With the switch off the last rollout has no events.  The critic is the one that fills
+// PPO_BUF_VALUES: on a fused device env that folds, gen_values' (gauss_fused.hpp: FusedFoldArgs; none of the launches ppo_gauss_fused_launches counts); on
+// CartPole / MountainCar, launch_values_mfma for both envs (ppo_internal.hpp: EnvFoldArgs), whatever kernel_flags and the weight range chose for the
+// actor -- as in bootstrap_launch, which counts no fall-back either.  envt_on is never set on an env that does not fold (envt_state).
+static ppo_status env_fold_truncations(ppo_ctx* c) {
+    DevEventList& l = c->env_events;
+    if (!c->envt_on) { l.closed = false; return PPO_OK; }
+    const ppo_status s = events_clear(c, l);
+    if (s != PPO_OK) return s;
+    if (c->env) {
+        FusedFoldArgs f{};
+        f.params = B_<float>(c, PPO_BUF_PARAMS);
+        f.obs = B_<float>(c, PPO_BUF_OBS);
+        f.actions = c->buf[PPO_BUF_ACTIONS];
+        f.fin_len = B_<int32_t>(c, PPO_BUF_FIN_LEN);
+        f.B = c->B;
+        f.max_episode_steps = c->cfg.max_episode_steps;
+        f.gamma = c->cfg.gamma;
+        f.rewards = B_<float>(c, PPO_BUF_REWARDS);
+        events_sink(l, f);
+        HIPCHK(c, fused_env_trunc_fold(c->cfg.env_kind, c->gen->L, f, c->stream));
+    } else {
+        EnvFoldArgs f{};
+        f.obs = B_<float>(c, PPO_BUF_OBS);
+        f.actions = B_<int32_t>(c, PPO_BUF_ACTIONS);
+        f.fin_len = B_<int32_t>(c, PPO_BUF_FIN_LEN);
+        f.B = c->B; f.H = c->H;
+        f.env_kind = c->cfg.env_kind;
+        f.max_episode_steps = c->cfg.max_episode_steps;
+        f.gamma = c->cfg.gamma;
+        f.rewards = B_<float>(c, PPO_BUF_REWARDS);
+        events_sink(l, f);
+        HIPCHK(c, launch_env_trunc_fold_mfma(B_<float>(c, PPO_BUF_PARAMS), c->L, f, c->stream));
+    }
+    return events_close(c, l);
 }
 
 // A fused device env: gauss_rollout_kernel / cat_rollout_kernel (all T steps), then gen_rollout's tail -- the critic over the stored observations and over
@@ -1610,11 +1660,8 @@ static ppo_status fused_env_rollout(ppo_ctx* c, const void* forced) {
         s = gen_values(c, r.obs, (int64_t)c->T * c->N, B_<float>(c, PPO_BUF_VALUES));
         if (s == PPO_OK) s = gen_values(c, r.next_obs, c->N, B_<float>(c, PPO_BUF_NEXT_VALUE));
         if (s != PPO_OK) return s;
-        c->envt_last = false;
-        if (c->envt_on) {   // behind the two critic launches, in front of the scan (envt_on is never set on an env that does not fold: envt_state)
-            s = fused_env_fold_truncations(c);
-            if (s != PPO_OK) return s;
-        }
+        s = env_fold_truncations(c);
+        if (s != PPO_OK) return s;
     }
     c->rollout_steps += c->T;
     c->global_step += (int64_t)c->T * c->cfg.global_num_envs;
@@ -1686,13 +1733,10 @@ extern "C" ppo_status ppo_rollout(ppo_ctx* c, const int64_t* forced_actions) {
         RingFuseArgs rf{};
         rf.fin_len = a.fin_len; rf.fin_rew = a.fin_rew; rf.row_counts = c->row_counts; rf.group_bits = c->group_bits; rf.ring = c->ring;
         rf.ticket = c->pair_tickets; rf.step_base = c->rollout_steps; rf.global_num_envs = c->cfg.global_num_envs; rf.env_offset = c->cfg.env_offset;
-        ring_pushed = !c->separate_launches && (c->L.obs == 4 || c->L.obs == 2);
+        ring_pushed = !c->separate_launches && critic_is_mfma(c);
         HIPCHK(c, launch_rollout(a, c->stream, ring_pushed ? &rf : nullptr));
-        c->envt_last = false;
-        if (c->envt_on) {   // behind the value launch, in front of the scan (one stream: ppo_calc_advantage and ppo_train_iteration's scan both follow)
-            s = env_fold_truncations(c);
-            if (s != PPO_OK) return s;
-        }
+        s = env_fold_truncations(c);   // (one stream: ppo_calc_advantage and ppo_train_iteration's scan both follow)
+        if (s != PPO_OK) return s;
     }
     c->rollout_steps += c->T;
     c->global_step += (int64_t)c->T * c->cfg.global_num_envs;  // global_step += num_envs per step (:526)
@@ -3086,7 +3130,7 @@ static ppo_status bootstrap_launch(ppo_ctx* c, const float* final_obs, const int
         const ppo_status s = gen_values(c, final_obs, K, value_out);
         if (s != PPO_OK) return s;
         HIPCHK(c, gen_fold_rewards(value_out, index, K, gamma, rewards, c->stream));
-    } else if (c->O == 4 || c->O == 2) {
+    } else if (critic_is_mfma(c)) {
         HIPCHK(c, launch_bootstrap_values_mfma(B_<float>(c, PPO_BUF_PARAMS), c->L, final_obs, index, K, gamma, rewards, value_out, c->stream));
     } else {
         HIPCHK(c, launch_bootstrap_values(B_<float>(c, PPO_BUF_PARAMS), c->L, final_obs, index, K, gamma, rewards, value_out, c->stream));
@@ -3147,25 +3191,8 @@ extern "C" ppo_status ppo_host_truncations(ppo_ctx* c, int64_t* count, int32_t* 
     const ppo_status s = host_state(c, "ppo_host_truncations");
     if (s != PPO_OK) return s;
     NEED(c, count != nullptr, "ppo_host_truncations: count is null");
-    if (c->dev_last >= 0) {   // the last closed rollout was device-fed: its list is on the device, in the order the workgroups got there
-        if (!c->dev_last_fetched) {
-            const int l = c->dev_last;
-            DeviceGuard dev_guard(c);
-            HIPCHK(c, hipEventSynchronize(c->dev_fold_ev[l]));   // that rollout's last fold and the copy of its counter: the update behind them keeps running
-            const int64_t n = std::min<int64_t>(std::max<int32_t>(c->dev_count_h[l], 0), c->dev_cap);
-            std::vector<int32_t> ix((size_t)n);
-            std::vector<float> va((size_t)n);
-            if (n > 0) {
-                HIPCHK(c, hipMemcpy(ix.data(), c->dev_index[l], (size_t)n * 4, hipMemcpyDeviceToHost));
-                HIPCHK(c, hipMemcpy(va.data(), c->dev_value[l], (size_t)n * 4, hipMemcpyDeviceToHost));
-            }
-            sort_events(ix, va, c->dev_last_idx, c->dev_last_val);
-            c->dev_last_fetched = true;
-        }
-        if (!copy_events_out(c->dev_last_idx, c->dev_last_val, count, index_h, value_h, cap))
-            return fail(c, PPO_ERR_INVALID, "ppo_host_truncations: room for %lld events, the last rollout had %lld", (long long)cap, (long long)c->dev_last_idx.size());
-        return PPO_OK;
-    }
+    if (c->dev_last >= 0)   // the last closed rollout was device-fed and folded: its list is on the device
+        return events_read(c, c->dev_events[c->dev_last], "ppo_host_truncations", count, index_h, value_h, cap);
     const int64_t K = (int64_t)c->trunc_last_idx.size();
     if ((index_h || value_h) && cap < K)
         return fail(c, PPO_ERR_INVALID, "ppo_host_truncations: room for %lld events, the last rollout had %lld", (long long)cap, (long long)K);
@@ -3200,45 +3227,21 @@ extern "C" ppo_status ppo_env_truncation_bootstrap(ppo_ctx* c, int32_t on) {
     const ppo_status s = envt_state(c, "ppo_env_truncation_bootstrap");
     if (s != PPO_OK) return s;
     NEED(c, on == 0 || on == 1, "ppo_env_truncation_bootstrap: on must be 0 or 1");
-    if (on && !c->envt_index) {   // the event list, once (the allocation policy of ppo_ctx_create in ppo_hip.h)
+    if (on) {   // the event list, made by the first enable
         DeviceGuard dev_guard(c);
-        if (!c->envt_ev) HIPCHK(c, hipEventCreateWithFlags(&c->envt_ev, hipEventDisableTiming));
-        if (!c->envt_count_h) {
-            HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->envt_count_h), 4 * sizeof(int32_t), hipHostMallocDefault));
-            c->envt_count_h[0] = 0;
-        }
-        if (!c->envt_count) HIPCHK(c, dalloc(c, &c->envt_count, 4, false));
-        if (!c->envt_value) HIPCHK(c, dalloc(c, &c->envt_value, (size_t)c->B, false));
-        HIPCHK(c, dalloc(c, &c->envt_index, (size_t)c->B, false));
+        const ppo_status r = events_reserve(c, c->env_events, c->B);
+        if (r != PPO_OK) return r;
     }
     c->envt_on = on != 0;
     return PPO_OK;
 }
-// The events of the last ppo_rollout (ppo_host_truncations' contract): the list is on the device in the order the workgroups got there
+// The events of the last ppo_rollout (ppo_host_truncations' contract); none before the first rollout, or when the last one ran with the switch off
 extern "C" ppo_status ppo_env_truncations(ppo_ctx* c, int64_t* count, int32_t* index_h, float* value_h, int64_t cap) {
     NEED(c, c != nullptr, "null ctx");
     const ppo_status s = envt_state(c, "ppo_env_truncations");
     if (s != PPO_OK) return s;
     NEED(c, count != nullptr, "ppo_env_truncations: count is null");
-    if (!c->envt_last) {   // no rollout yet, or the last one ran with the switch off
-        c->envt_idx.clear();
-        c->envt_val.clear();
-    } else if (!c->envt_fetched) {
-        DeviceGuard dev_guard(c);
-        HIPCHK(c, hipEventSynchronize(c->envt_ev));   // the fold and the copy of its counter: the update behind them keeps running
-        const int64_t n = std::min<int64_t>(std::max<int32_t>(c->envt_count_h[0], 0), c->B);
-        std::vector<int32_t> ix((size_t)n);
-        std::vector<float> va((size_t)n);
-        if (n > 0) {
-            HIPCHK(c, hipMemcpy(ix.data(), c->envt_index, (size_t)n * 4, hipMemcpyDeviceToHost));
-            HIPCHK(c, hipMemcpy(va.data(), c->envt_value, (size_t)n * 4, hipMemcpyDeviceToHost));
-        }
-        sort_events(ix, va, c->envt_idx, c->envt_val);
-        c->envt_fetched = true;
-    }
-    if (!copy_events_out(c->envt_idx, c->envt_val, count, index_h, value_h, cap))
-        return fail(c, PPO_ERR_INVALID, "ppo_env_truncations: room for %lld events, the last rollout had %lld", (long long)cap, (long long)c->envt_idx.size());
-    return PPO_OK;
+    return events_read(c, c->env_events, "ppo_env_truncations", count, index_h, value_h, cap);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -3272,25 +3275,6 @@ static ppo_status dev_state(ppo_ctx* c, const char* what) {
         return fail(c, PPO_ERR_STATE, "%s: the open rollout is host-fed (ppo_host_act / ppo_host_observe); a rollout takes the ppo_host_* or the ppo_dev_* calls, not both", what);
     return PPO_OK;
 }
-// The two event lists of device-fed rollouts, T * N entries each, made by the first ppo_dev_observe that passes flags (the allocation policy of ppo_ctx_create
-// in ppo_hip.h).  The counters are cleared in stream order in front of a rollout's first fold, not here.
-static ppo_status dev_lists_reserve(ppo_ctx* c) {
-    if (c->dev_cap > 0) return PPO_OK;
-    const int64_t cap = (int64_t)c->T * c->N;
-    for (hipEvent_t& e : c->dev_fold_ev) if (!e) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    if (!c->dev_count_h) {
-        HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->dev_count_h), 4 * sizeof(int32_t), hipHostMallocDefault));
-        c->dev_count_h[0] = c->dev_count_h[1] = 0;
-    }
-    if (!c->dev_count) HIPCHK(c, dalloc(c, &c->dev_count, 4, false));
-    for (int l = 0; l < 2; l++) {
-        if (!c->dev_index[l]) HIPCHK(c, dalloc(c, &c->dev_index[l], (size_t)cap, false));
-        if (!c->dev_value[l]) HIPCHK(c, dalloc(c, &c->dev_value[l], (size_t)cap, false));
-    }
-    c->dev_cap = cap;
-    return PPO_OK;
-}
-
 // initEnvs (PPO_Discrete.cpp:365-402) from a device array: NEXT_OBS = obs, NEXT_DONE = 0, per-env episode sums = 0, in stream order
 extern "C" ppo_status ppo_dev_env_reset(ppo_ctx* c, const float* obs, void* caller_stream) {
     NEED(c, c != nullptr, "null ctx");
@@ -3382,10 +3366,11 @@ extern "C" ppo_status ppo_dev_observe(ppo_ctx* c, const float* next_obs, const f
     DeviceGuard dev_guard(c);
     hipStream_t caller = static_cast<hipStream_t>(caller_stream);
     const int t = c->host_t - 1, N = c->N;
-    if (truncated) {
-        s = dev_lists_reserve(c);
-        if (s != PPO_OK) return s;
-    }
+    if (truncated)   // both lists, T * N entries each, made by the first call that passes flags
+        for (DevEventList& l : c->dev_events) {
+            s = events_reserve(c, l, (int64_t)c->T * N);
+            if (s != PPO_OK) return s;
+        }
     HostStepArgs h = host_args(c, t + 1, false, 0, true, fin_len != nullptr);
     h.st_obs = next_obs; h.st_rew = reward; h.st_done = done; h.st_fin_len = fin_len; h.st_fin_rew = fin_rew;
     s = dev_handover_in(c, caller);
@@ -3403,21 +3388,22 @@ extern "C" ppo_status ppo_dev_observe(ppo_ctx* c, const float* next_obs, const f
     if (s != PPO_OK) return s;
     HIPCHK(c, launch_host_commit(h, N, c->O, c->stream));
     if (truncated) {
-        const int l = c->dev_list;
-        if (!c->dev_list_used) {
-            HIPCHK(c, hipMemsetAsync(c->dev_count + l, 0, sizeof(int32_t), c->stream));
+        DevEventList& l = c->dev_events[c->dev_list];
+        if (!c->dev_list_used) {   // in front of the rollout's first fold
+            s = events_clear(c, l);
+            if (s != PPO_OK) return s;
             c->dev_list_used = true;
         }
         DevFoldArgs f{};
         f.truncated = truncated; f.done = done; f.final_obs = final_obs;
         f.N = N; f.tN = (int64_t)t * N; f.gamma = c->cfg.gamma;
         f.rewards = B_<float>(c, PPO_BUF_REWARDS);
-        f.ev_count = c->dev_count + l; f.ev_index = c->dev_index[l]; f.ev_value = c->dev_value[l]; f.ev_cap = c->dev_cap;
+        events_sink(l, f);
         // the critic bootstrap_launch would pick for this context
         if (c->gen) {   // PPO_KERNEL_GAUSS_FUSED / PPO_KERNEL_CAT_FUSED: gen_values' kernel, counted like its launches
             c->gf_launches[1] += 1;
             HIPCHK(c, gauss_fused_dev_fold(c->gen->L, B_<float>(c, PPO_BUF_PARAMS), f, c->stream));
-        } else if (c->O == 4 || c->O == 2) HIPCHK(c, launch_dev_fold_mfma(B_<float>(c, PPO_BUF_PARAMS), c->L, f, c->stream));
+        } else if (critic_is_mfma(c)) HIPCHK(c, launch_dev_fold_mfma(B_<float>(c, PPO_BUF_PARAMS), c->L, f, c->stream));
         else HIPCHK(c, launch_dev_fold(B_<float>(c, PPO_BUF_PARAMS), c->L, f, c->stream));
     }
     s = dev_handover_out(c, caller);
@@ -3596,9 +3582,8 @@ extern "C" ppo_status ppo_host_rollout_end(ppo_ctx* c) {
     const int N = c->N, T = c->T;
     if (dev_fed) {
         if (c->dev_list_used) {   // in front of the value launch: ppo_host_truncations waits for the folds only
-            const int l = c->dev_list;
-            HIPCHK(c, hipMemcpyAsync(c->dev_count_h + l, c->dev_count + l, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipEventRecord(c->dev_fold_ev[l], c->stream));
+            s = events_close(c, c->dev_events[c->dev_list]);
+            if (s != PPO_OK) return s;
         }
     } else if (c->host_n_groups > 0) {   // every group's step T - 1 in one launch
         HostGroupTable tab{};
@@ -3619,7 +3604,7 @@ extern "C" ppo_status ppo_host_rollout_end(ppo_ctx* c) {
         s = gen_values(c, B_<float>(c, PPO_BUF_OBS), (int64_t)T * N, B_<float>(c, PPO_BUF_VALUES));
         if (s == PPO_OK) s = gen_values(c, next_obs, N, B_<float>(c, PPO_BUF_NEXT_VALUE));
         if (s != PPO_OK) return s;
-    } else if (c->O == 4 || c->O == 2) {   // launch_rollout's tail
+    } else if (critic_is_mfma(c)) {   // launch_rollout's tail
         HIPCHK(c, launch_values_mfma(B_<float>(c, PPO_BUF_PARAMS), c->L, B_<float>(c, PPO_BUF_OBS), (int64_t)T * N, B_<float>(c, PPO_BUF_VALUES), next_obs, N,
                                      B_<float>(c, PPO_BUF_NEXT_VALUE), c->stream));
     } else {
@@ -3633,9 +3618,6 @@ extern "C" ppo_status ppo_host_rollout_end(ppo_ctx* c) {
     c->global_step += (int64_t)T * c->cfg.global_num_envs;   // :526
     c->fin_pending = true;
     c->host_feed = 0;
-    c->dev_last_idx.clear();
-    c->dev_last_val.clear();
-    c->dev_last_fetched = false;
     if (dev_fed) {
         c->dev_last = c->dev_list_used ? c->dev_list : -1;
         c->dev_list_used = false;

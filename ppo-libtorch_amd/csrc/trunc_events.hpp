@@ -7,6 +7,9 @@
 #include <cstring>
 #include <vector>
 
+// The counter as copied back -> the entries the list holds: the fold kernels count every event and store only those below the capacity
+inline int64_t clamp_event_count(int32_t raw, int64_t cap) { return std::min<int64_t>(std::max<int32_t>(raw, 0), cap); }
+
 // (index, value) pairs in the order the workgroups got to the list -> ascending by index (indices are distinct: one event per sample)
 inline void sort_events(const std::vector<int32_t>& ix, const std::vector<float>& va, std::vector<int32_t>& ix_out, std::vector<float>& va_out) {
     const size_t n = ix.size();
