@@ -39,6 +39,9 @@ def P():
 # counterpart in the reference: its bars are distances (measured, x 3), not parity.
 # bf16 bars = REGRESSION FENCES at ~3x the measured values above (log-prob 6e-4 -> 2e-3, value 2e-3 -> 4e-3 (2x), losses 2e-6 -> 6e-6, gradient 2e-4 -> 6e-4 of max): they
 # say "the bf16 kernels have not moved away from the bf16 oracle", not "the bf16 kernels are within a derived bound of the reference" (DESIGN.md section 0, row x1).
+# The fences remain the END-TO-END check of the bf16 forward (a row's log-prob, value and entropy through all layers and the heads).  The DERIVED check is
+# tests/test_gpu_bf16_layers.py: every hidden layer element by element against float64 on the layer's own inputs (tests/bf16_layers.py), which sees what the
+# fences absorb -- a store that truncates, a tanh 1e-4 off, a lost k chunk, a few rows off by less than the fence.
 TOL = {0: dict(fwd=5e-6, fwd_v=5e-6, agree=0.995, loss=1e-5, grad=1e-4, same=1e-6), 1: dict(fwd=2e-3, fwd_v=4e-3, agree=0.98, loss=6e-6, grad=6e-4, same=1e-6)}
 
 
