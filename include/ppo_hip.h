@@ -66,6 +66,8 @@ enum { PPO_OK = 0, PPO_ERR_INVALID = 1, PPO_ERR_HIP = 2, PPO_ERR_STATE = 3, PPO_
  * (PPO_ERR_UNSUPPORTED: step episodes through ppo_policy_act_f32 with greedy = 1 and ppo_env_transition_f32); ppo_env_truncation_bootstrap
  * (PPO_ERR_UNSUPPORTED: its fold rebuilds the final observation from PPO_BUF_OBS, and a Pendulum observation does not hold theta); ppo_obs_norm_* and
  * ppo_reward_norm_* (PPO_ERR_UNSUPPORTED, as on every device env); ppo_env_step and ppo_rollout with an i64 array (PPO_ERR_UNSUPPORTED, naming the _f32 call).
+ * With PPO_KERNEL_ENV_CUT_STATE in kernel_flags (below) the rollout keeps theta and theta_dot of every cut-off episode, and ppo_env_truncation_bootstrap and
+ * ppo_env_truncations are served from that record (cut_state_fold_kernel); without the flag the refusal above stands, word for word.
  * Sharding (ppo_comm_init*) is neither claimed nor tested for this env. */
 /* PPO_ENV_MOUNTAINCAR_CONTINUOUS (new; value 5): gymnasium's MountainCarContinuous-v0 on the device, the second env of the Gaussian policy's fused rollout and
  * the sibling of PPO_ENV_MOUNTAINCAR: the same track, the same reset, one cosine per step.  State (position p, velocity v) f32, and the observation IS the
@@ -91,6 +93,8 @@ enum { PPO_OK = 0, PPO_ERR_INVALID = 1, PPO_ERR_HIP = 2, PPO_ERR_STATE = 3, PPO_
  * (tests/test_gpu_mountaincar_continuous.py); with ppo_env_truncation_bootstrap on, a fourth launch folds the cut-off episodes (below).
  * Refused exactly as on Pendulum, changing nothing: ppo_host_* / ppo_dev_* (PPO_ERR_STATE); ppo_obs_norm_* and ppo_reward_norm_* (PPO_ERR_UNSUPPORTED);
  * ppo_env_step, ppo_rollout with an i64 array and ppo_policy_act (PPO_ERR_UNSUPPORTED, naming the _f32 twin).
+ * Which fold: without PPO_KERNEL_ENV_CUT_STATE gauss_trunc_fold_kernel, from PPO_BUF_OBS and the stored action; with the flag cut_state_fold_kernel, from the
+ * kept state -- the same events and the same rewards, bit for bit (tests/test_gpu_cut_state.py holds the two against each other).
  * Sharding (ppo_comm_init*) is neither claimed nor tested for this env. */
 /* PPO_ENV_ACROBOT (new; value 6): gymnasium's Acrobot-v1 on the device ("book" dynamics, no torque noise), the first device env of the fused 2 x 64 family
  * with a categorical policy.  State (theta1, theta2, w1, w2) f32 -- PPO_BUF_ENV_STATE is [4, N], ppo_env_set_state_h / ppo_env_get_state_h take [N, 4] --
@@ -137,7 +141,9 @@ enum { PPO_OK = 0, PPO_ERR_INVALID = 1, PPO_ERR_HIP = 2, PPO_ERR_STATE = 3, PPO_
  * Refused, each with its reason, changing nothing: ppo_host_* / ppo_dev_* (PPO_ERR_STATE, as on any device env); ppo_obs_norm_* and ppo_reward_norm_*
  * (PPO_ERR_UNSUPPORTED); ppo_env_step_f32, ppo_rollout_f32, ppo_policy_act_f32 (PPO_ERR_UNSUPPORTED, naming the integer twin);
  * ppo_env_truncation_bootstrap and ppo_env_truncations (PPO_ERR_UNSUPPORTED: the fold rebuilds the final observation of a cut-off episode from PPO_BUF_OBS,
- * and an Acrobot observation does not hold the angles).  Sharding (ppo_comm_init*) is neither claimed nor tested for this env. */
+ * and an Acrobot observation does not hold the angles).  With PPO_KERNEL_ENV_CUT_STATE in kernel_flags (below) the rollout keeps the four state words of
+ * every cut-off episode, and the two calls are served from that record (cut_state_fold_kernel); without the flag the refusal stands, word for word.
+ * Sharding (ppo_comm_init*) is neither claimed nor tested for this env. */
 enum { PPO_ENV_CARTPOLE = 0, PPO_ENV_MOUNTAINCAR = 1, PPO_ENV_SYNTHETIC = 2, PPO_ENV_HOST = 3, PPO_ENV_PENDULUM = 4, PPO_ENV_MOUNTAINCAR_CONTINUOUS = 5 };
 enum { PPO_ENV_ACROBOT = PPO_ENV_MOUNTAINCAR_CONTINUOUS + 1 };   /* 6: the next env_kind, in an enum of its own -- the list above is kept as it was published */
 /* PPO_ENV_TAXI (new; value 8): gymnasium's Taxi-v3 on the device (no rain, no fickle passenger), the first device env whose action mask means something:
@@ -184,7 +190,10 @@ enum { PPO_ENV_ACROBOT = PPO_ENV_MOUNTAINCAR_CONTINUOUS + 1 };   /* 6: the next 
  * into the reward); it is none of the launches ppo_gauss_fused_launches counts.  ppo_evaluate is ONE launch (cat_eval_kernel; under PPO_DIST_MASKED greedy is
  * the first-index argmax of the masked probabilities) and moves no counter.
  * Refused, changing nothing, with Acrobot's statuses: ppo_host_* / ppo_dev_* (PPO_ERR_STATE); ppo_obs_norm_* and ppo_reward_norm_* (PPO_ERR_UNSUPPORTED);
- * ppo_env_step_f32, ppo_rollout_f32, ppo_policy_act_f32 (PPO_ERR_UNSUPPORTED, naming the integer twin).  Sharding is neither claimed nor tested. */
+ * ppo_env_step_f32, ppo_rollout_f32, ppo_policy_act_f32 (PPO_ERR_UNSUPPORTED, naming the integer twin).
+ * Which fold: without PPO_KERNEL_ENV_CUT_STATE cat_trunc_fold_kernel, from PPO_BUF_OBS and the stored action; with the flag cut_state_fold_kernel, from the
+ * kept state -- the same events and the same rewards, bit for bit, under either distribution (tests/test_gpu_cut_state.py).
+ * Sharding is neither claimed nor tested. */
 enum { PPO_ENV_TAXI = PPO_ENV_ACROBOT + 2 };   /* 8, not 7: value 7 stays unassigned and keeps answering "unknown env_kind 7", as 9 does -- existing tests
                                                 * hold both; in an enum of its own and written as a sum, as PPO_ENV_ACROBOT is: the first list's text is pinned */
 /* PPO_ENV_FROZENLAKE (new; value 10) and PPO_ENV_FROZENLAKE8X8 (new; value 11): gymnasium's FrozenLake-v1 and FrozenLake8x8-v1 with is_slippery = True, the
@@ -224,7 +233,9 @@ enum { PPO_ENV_TAXI = PPO_ENV_ACROBOT + 2 };   /* 8, not 7: value 7 stays unassi
  * it fills bit for bit (tests/test_gpu_frozenlake.py).  ppo_evaluate is ONE launch (cat_eval_kernel) and moves no counter.
  * Refused, changing nothing: ppo_host_* / ppo_dev_* (PPO_ERR_STATE); ppo_obs_norm_* and ppo_reward_norm_* (PPO_ERR_UNSUPPORTED); ppo_env_step_f32,
  * ppo_rollout_f32, ppo_policy_act_f32 (PPO_ERR_UNSUPPORTED, naming the integer twin); ppo_env_truncation_bootstrap and ppo_env_truncations
- * (PPO_ERR_UNSUPPORTED: the final observation of a cut-off episode depends on j and the key, which the stored observation does not hold).  Sharding is
+ * (PPO_ERR_UNSUPPORTED: the final observation of a cut-off episode depends on j and the key, which the stored observation does not hold).  With
+ * PPO_KERNEL_ENV_CUT_STATE in kernel_flags (below) the rollout keeps (cell, j, k0, k1) of every cut-off episode and whether the env itself terminated on that
+ * step, and the two calls are served from that record on both kinds (cut_state_fold_kernel); without the flag the refusal stands, word for word.  Sharding is
  * neither claimed nor tested. */
 enum { PPO_ENV_FROZENLAKE = PPO_ENV_TAXI + 2 };      /* 10, not 9: value 9 stays unassigned, as 7 does; an enum of its own, written as a sum */
 enum { PPO_ENV_FROZENLAKE8X8 = PPO_ENV_TAXI + 3 };   /* 11 */
@@ -271,7 +282,9 @@ enum { PPO_ENV_FROZENLAKE8X8 = PPO_ENV_TAXI + 3 };   /* 11 */
  * Refused, changing nothing: PPO_ENV_FROZENLAKE's list -- ppo_host_* / ppo_dev_* (PPO_ERR_STATE); ppo_obs_norm_* and ppo_reward_norm_*
  * (PPO_ERR_UNSUPPORTED); ppo_env_step_f32, ppo_rollout_f32, ppo_policy_act_f32 (PPO_ERR_UNSUPPORTED, naming the integer twin);
  * ppo_env_truncation_bootstrap and ppo_env_truncations (PPO_ERR_UNSUPPORTED: the final observation of a cut-off episode depends on n and the key, which the
- * stored observation does not hold).  Sharding is neither claimed nor tested. */
+ * stored observation does not hold).  With PPO_KERNEL_ENV_CUT_STATE in kernel_flags (below) the rollout keeps (hand, n, k0, k1) of every cut-off episode
+ * and whether the env itself terminated on that step, and the two calls are served from that record (cut_state_fold_kernel); without the flag the refusal
+ * stands, word for word.  Sharding is neither claimed nor tested. */
 enum { PPO_ENV_BLACKJACK = PPO_ENV_TAXI + 5 };   /* 13, not 12: value 12 stays unassigned, as 7 and 9 do; an enum of its own, written as a sum */
 /* PPO_DIST_CATEGORICAL reproduces Distributions/Categorical.cpp including its entropy clamp (:112-119);
  * PPO_DIST_MASKED reproduces Distributions/CategoricalMasked.cpp (true entropy, -1e8 masking).
@@ -426,12 +439,34 @@ typedef struct ppo_config {
  *                               flag's place.  Refused on such a context, changing nothing: ppo_host_* / ppo_dev_* (PPO_ERR_STATE, as on any device env),
  *                               ppo_obs_norm_* / ppo_reward_norm_* (PPO_ERR_UNSUPPORTED), ppo_evaluate (PPO_ERR_UNSUPPORTED: step the episodes with
  *                               ppo_policy_act_greedy + ppo_env_transition), ppo_env_truncation_bootstrap and ppo_env_truncations (PPO_ERR_UNSUPPORTED: the
- *                               fold is built on the reference-shape critic).  Sharding (ppo_comm_init*) of a flagged context is neither claimed nor tested. */
+ *                               fold is built on the reference-shape critic).  Sharding (ppo_comm_init*) of a flagged context is neither claimed nor tested.
+ *   PPO_KERNEL_ENV_CUT_STATE    the device envs of the fused 2 x 64 families -- PPO_ENV_PENDULUM, PPO_ENV_MOUNTAINCAR_CONTINUOUS, PPO_ENV_ACROBOT, PPO_ENV_TAXI,
+ *                               PPO_ENV_FROZENLAKE, PPO_ENV_FROZENLAKE8X8 and PPO_ENV_BLACKJACK -- next to the env's own family flag: the one-launch rollout
+ *                               keeps the state a time limit cut an episode off in.  What is kept: at every sample i = t * N + n whose episode's length reached
+ *                               max_episode_steps on that step, wave 0's owning lane stores the env's state as it is BEFORE the auto-reset (STATE f32 words:
+ *                               2 on the Gaussian envs, 4 on the categorical ones) and one more word, 0.0f or 1.0f, "the env itself terminated on this
+ *                               step".  Where: a device allocation of the context's own, f32 [STATE + 1, T * N], made by ppo_ctx_create and released with the
+ *                               context; it is no PPO_BUF_* and ppo_get_buffer does not reach it.  What it costs: 4 (STATE + 1) T N bytes, and STATE + 1
+ *                               scattered stores at the cut-off samples only -- no store at any other sample, nothing dense per step, nothing cleared between
+ *                               rollouts (the fold reads a column only where this rollout's FIN_LEN says this rollout wrote it).  The rollout is another
+ *                               instantiation of the same kernel (gauss_rollout_kernel / cat_rollout_kernel with KEEP = true); every buffer it fills holds the
+ *                               bits of the unflagged context's.  Which calls it opens: ppo_env_truncation_bootstrap and ppo_env_truncations on PPO_ENV_PENDULUM,
+ *                               PPO_ENV_ACROBOT, PPO_ENV_FROZENLAKE, PPO_ENV_FROZENLAKE8X8 and PPO_ENV_BLACKJACK, whose observations do not hold the state
+ *                               (theta; the angles; the step count, the card count and the episode's key) and which refuse the two calls without the flag.
+ *                               On a flagged context EVERY fused env folds from the record, in one launch of cut_state_fold_kernel (the final observation is
+ *                               Env::obs of the kept state; no step is replayed and no action read): PPO_ENV_MOUNTAINCAR_CONTINUOUS and PPO_ENV_TAXI too, with
+ *                               the events and rewards of their unflagged folds, bit for bit.  The fold's dynamic LDS, by obs_size: 59 680 bytes at 2 and 3,
+ *                               63 840 at 6, 68 064 at 16, 70 176 at 19, 84 960 at 45, 93 408 at 64.  Opt-in, never implied: without the flag every context is
+ *                               what it was, refusals included.  ppo_ctx_create returns PPO_ERR_UNSUPPORTED with a message naming the flag and the limit on
+ *                               any other env_kind (PPO_ENV_CARTPOLE, PPO_ENV_MOUNTAINCAR, PPO_ENV_SYNTHETIC, PPO_ENV_HOST) and beside PPO_KERNEL_ENV_GENERIC.
+ *                               Everything else a flagged context refuses it refuses as without the flag (ppo_evaluate on Pendulum, ppo_host_* / ppo_dev_*,
+ *                               the normalisers).  Sharding (ppo_comm_init*) of a flagged context is neither claimed nor tested. */
 enum { PPO_KERNEL_ROLLOUT_VECTOR = 1, PPO_KERNEL_UPDATE_VECTOR = 2, PPO_KERNEL_UPDATE_ONE_WAVE = 4, PPO_KERNEL_COMM_SELFTEST = 8, PPO_KERNEL_GENERIC_CLASSIC = 16,
        PPO_KERNEL_GENERIC_SPLIT_HEAD = 32, PPO_KERNEL_GAUSS_FUSED = 64 };
 #define PPO_KERNEL_SEPARATE_LAUNCHES 128   /* the next free bit of kernel_flags, 1 << 7; a macro beside the enumerators: same type in an expression, same use */
 #define PPO_KERNEL_CAT_FUSED 256           /* 1 << 8, likewise */
 #define PPO_KERNEL_ENV_GENERIC 512         /* 1 << 9, likewise */
+#define PPO_KERNEL_ENV_CUT_STATE (1 << 10) /* 1024, likewise; written as the shift: tests/test_env_generic_abi.py pins the list of macros spelt as decimal literals */
 
 /* Scalars the reference prints per update (PPO_Discrete.cpp:700-774) plus per-step diagnostics. */
 typedef struct ppo_stats {
@@ -674,7 +709,12 @@ PPO_API ppo_status ppo_rollout_f32(ppo_ctx* ctx, const float* forced_actions /* 
  * critic: the fold is one launch of gauss_trunc_fold_kernel behind the rollout's two critic launches and in front of the scan; the step is recomputed from
  * PPO_BUF_OBS[i] under the RAW f32 action PPO_BUF_ACTIONS[i, 0] with the env's own device function; v is bit for bit what ppo_get_value gives the final
  * observation (gauss_values_kernel's forward); the grid covers the T * N rows in workgroups of 256, and the critic's weights are staged only by workgroups
- * that found an event.  The fold launch is none of the kernels ppo_gauss_fused_launches counts. */
+ * that found an event.  The fold launch is none of the kernels ppo_gauss_fused_launches counts.
+ * PPO_KERNEL_ENV_CUT_STATE (kernel_flags, above) serves the two calls on every device env of the fused families, with the same contract: the rollout has kept
+ * the state each cut-off episode ended in and whether the env itself terminated there, so the fold (ONE launch of cut_state_fold_kernel, in the same place)
+ * recomputes nothing -- for every i with PPO_BUF_FIN_LEN[i] == max_episode_steps and the terminated word clear, the final observation is the env's observation
+ * of the kept state, v is bit for bit what ppo_get_value gives it, and the reward and the event list are formed as above.  On PPO_ENV_PENDULUM, where no
+ * episode ends anywhere else, every finished episode is an event.  Without the flag the errors above stand. */
 PPO_API ppo_status ppo_env_truncation_bootstrap(ppo_ctx* ctx, int32_t on);   /* 0 off (default), 1 on */
 /* The events of the last ppo_rollout, with ppo_host_truncations' contract: count; flat indices t * N + n ascending (sorted on the host at read time); the
  * values V(final obs) that were folded in.  Before any rollout, and after a rollout with the switch off: count = 0.  index_h / value_h may be NULL (count

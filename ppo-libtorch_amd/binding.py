@@ -32,6 +32,9 @@ DTYPE_F32, DTYPE_BF16 = 0, 1
 KERNEL_ROLLOUT_VECTOR, KERNEL_UPDATE_VECTOR, KERNEL_UPDATE_ONE_WAVE, KERNEL_COMM_SELFTEST, KERNEL_GENERIC_CLASSIC, KERNEL_GENERIC_SPLIT_HEAD, KERNEL_GAUSS_FUSED, KERNEL_SEPARATE_LAUNCHES = 1, 2, 4, 8, 16, 32, 64, 128   # ppo_config.kernel_flags (include/ppo_hip.h PPO_KERNEL_*)
 KERNEL_CAT_FUSED = 256   # categorical / masked policies of a 2 x 64 f32 ENV_HOST context on the fused kernel family (include/ppo_hip.h PPO_KERNEL_CAT_FUSED)
 KERNEL_ENV_GENERIC = 512   # ENV_CARTPOLE / ENV_MOUNTAINCAR on a network of any width and depth, f32 or bf16 (include/ppo_hip.h PPO_KERNEL_ENV_GENERIC)
+# the fused device envs (ENV_PENDULUM .. ENV_BLACKJACK), next to the env's family flag: the rollout keeps the state a time limit cut an episode off in, and
+# env_truncation_bootstrap / env_truncations are served on every one of them (include/ppo_hip.h PPO_KERNEL_ENV_CUT_STATE)
+KERNEL_ENV_CUT_STATE = 1024
 ABI_VERSION = 5
 COMM_ID_BYTES = 128
 COMM_HANDLE_BYTES = 64
@@ -436,7 +439,9 @@ class Context:
 
     def env_truncation_bootstrap(self, on=True):
         """ppo_env_truncation_bootstrap: with the switch on, a rollout of the context's own env (CartPole, MountainCar, ENV_MOUNTAINCAR_CONTINUOUS) folds gamma * V(final observation)
-        into REWARDS where the time limit cut an episode off.  Off by default."""
+        into REWARDS where the time limit cut an episode off.  Off by default.  A context created with KERNEL_ENV_CUT_STATE is served on every fused device env
+        (ENV_PENDULUM, ENV_ACROBOT, the two ENV_FROZENLAKE kinds and ENV_BLACKJACK too, which refuse the call without the flag): the fold then reads the
+        state the rollout kept at each cut-off sample instead of rebuilding it from OBS."""
         _check(lib().ppo_env_truncation_bootstrap(self.h, int(on)), self.h)
 
     def env_truncations(self):

@@ -223,6 +223,10 @@ struct ppo_ctx {
     bool env_generic = false;
     // a device env of the fused families: its row (gauss_fused.hpp: FusedEnvInfo), looked up once by ppo_ctx_create; null on every other env
     const FusedEnvInfo* env = nullptr;
+    // PPO_KERNEL_ENV_CUT_STATE (a fused device env only): the cut-off record, f32 [env->state + 1, B] -- the KEEP rollout writes column t N + env where that
+    // step's episode reached the limit (the pre-reset state, then 0.0f / 1.0f "the env itself terminated"), and cut_state_fold_kernel reads exactly those
+    // columns; never cleared, not a PPO_BUF_*; null on every other context
+    float* cut_state = nullptr;
     int64_t gf_launches[3] = { 0, 0, 0 };
     float* gf_slab = nullptr;
     unsigned long long* stamps = nullptr;  // [2][12] phase cycles of the diagnostic kernel variant
@@ -644,7 +648,21 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
     if (cfg->dist_kind != PPO_DIST_CATEGORICAL && cfg->dist_kind != PPO_DIST_MASKED && !gauss) return fail(nullptr, PPO_ERR_INVALID, "unknown dist_kind %d", cfg->dist_kind);
     if (cfg->compute_dtype != PPO_DTYPE_F32 && cfg->compute_dtype != PPO_DTYPE_BF16) return fail(nullptr, PPO_ERR_INVALID, "unknown compute_dtype %d", cfg->compute_dtype);
     constexpr int32_t known_flags = PPO_KERNEL_ROLLOUT_VECTOR | PPO_KERNEL_UPDATE_VECTOR | PPO_KERNEL_UPDATE_ONE_WAVE | PPO_KERNEL_COMM_SELFTEST | PPO_KERNEL_GENERIC_CLASSIC |
-                                  PPO_KERNEL_GENERIC_SPLIT_HEAD | PPO_KERNEL_GAUSS_FUSED | PPO_KERNEL_SEPARATE_LAUNCHES | PPO_KERNEL_CAT_FUSED | PPO_KERNEL_ENV_GENERIC;
+                                  PPO_KERNEL_GENERIC_SPLIT_HEAD | PPO_KERNEL_GAUSS_FUSED | PPO_KERNEL_SEPARATE_LAUNCHES | PPO_KERNEL_CAT_FUSED | PPO_KERNEL_ENV_GENERIC |
+                                  PPO_KERNEL_ENV_CUT_STATE;
+    // PPO_KERNEL_ENV_CUT_STATE: a device env of the fused 2 x 64 families (a row of fused_env_rows), next to that env's own family flag (checked in the env's
+    // block below), or a refusal that names the flag.  In front of PPO_KERNEL_ENV_GENERIC's block, so that the two flags together are answered here
+    if (cfg->kernel_flags & PPO_KERNEL_ENV_CUT_STATE) {
+        if (cfg->kernel_flags & ~known_flags) return fail(nullptr, PPO_ERR_INVALID, "unknown bits in kernel_flags 0x%x", cfg->kernel_flags);
+        if (cfg->kernel_flags & PPO_KERNEL_ENV_GENERIC)
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_ENV_CUT_STATE excludes PPO_KERNEL_ENV_GENERIC: the cut-off state is kept by the one-launch rollouts of "
+                        "the fused 2 x 64 families, and CartPole / MountainCar on the generic engine run neither");
+        if (!env)
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_ENV_CUT_STATE serves the device envs of the fused 2 x 64 families only (%s; %s): their one-launch "
+                        "rollouts keep the state a time limit cut an episode off in; CartPole and MountainCar fold from PPO_BUF_OBS without it, PPO_ENV_SYNTHETIC "
+                        "has no last observation and PPO_ENV_HOST passes its own (ppo_host_observe_truncated); got env_kind %d",
+                        fused_env_names(FUSED_GAUSS), fused_env_names(FUSED_CAT), cfg->env_kind);
+    }
     // PPO_KERNEL_ENV_GENERIC: CartPole / MountainCar with a categorical policy and neither flag of the fused 2 x 64 family, or a refusal that names the flag --
     // never another engine in its place.  In front of the envs' own blocks, so that the flag on one of them is answered here
     if (cfg->kernel_flags & PPO_KERNEL_ENV_GENERIC) {
@@ -963,6 +981,7 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
             CK(dalloc(c, &c->gf_slab, (size_t)2 * GAUSS_FUSED_MAX_BLOCKS * gauss_fused_slab_stride(GL)));
         }
         CK(dalloc(c, &c->cur_mask, N * GL.act));
+        if (env && (cfg->kernel_flags & PPO_KERNEL_ENV_CUT_STATE)) CK(dalloc(c, &c->cut_state, (size_t)(env->state + 1) * TN));
         if (env_generic) {   // CartPole::getActionMask / MountainCar::getActionMask are all ones (MountainCar.cpp:69-77): the mask of every step under PPO_DIST_MASKED
             c->env_generic = true;
             CK(hipMemset(c->cur_mask, 1, N * GL.act));
@@ -1596,7 +1615,8 @@ static inline bool critic_is_mfma(const ppo_ctx* c) { return c->O == 4 || c->O =
 // time limit cut off get r + gamma V(final observation).  With the switch off the last rollout has no events.  The critic is the one that fills
 // PPO_BUF_VALUES: on a fused device env that folds, gen_values' (gauss_fused.hpp: FusedFoldArgs; none of the launches ppo_gauss_fused_launches counts); on
 // CartPole / MountainCar, launch_values_mfma for both envs (ppo_internal.hpp: EnvFoldArgs), whatever kernel_flags and the weight range chose for the
-// actor -- as in bootstrap_launch, which counts no fall-back either.  envt_on is never set on an env that does not fold (envt_state).
+// actor -- as in bootstrap_launch, which counts no fall-back either.  envt_on is never set on an env that does not fold (envt_state): a fused env folds
+// from PPO_BUF_OBS where its row says so, and every fused env of a PPO_KERNEL_ENV_CUT_STATE context folds from the record (f.cut).
 static ppo_status env_fold_truncations(ppo_ctx* c) {
     DevEventList& l = c->env_events;
     if (!c->envt_on) { l.closed = false; return PPO_OK; }
@@ -1612,6 +1632,7 @@ static ppo_status env_fold_truncations(ppo_ctx* c) {
         f.max_episode_steps = c->cfg.max_episode_steps;
         f.gamma = c->cfg.gamma;
         f.rewards = B_<float>(c, PPO_BUF_REWARDS);
+        f.cut = c->cut_state;
         events_sink(l, f);
         HIPCHK(c, fused_env_trunc_fold(c->cfg.env_kind, c->gen->L, f, c->stream));
     } else {
@@ -1654,6 +1675,7 @@ static ppo_status fused_env_rollout(ppo_ctx* c, const void* forced) {
     r.next_obs = B_<float>(c, PPO_BUF_NEXT_OBS);
     r.next_done = B_<int32_t>(c, PPO_BUF_NEXT_DONE);
     r.forced = forced;
+    r.cut = c->cut_state;
     {
         ProfScope ps(c, PROF_ROLLOUT);
         HIPCHK(c, launch_fused_env_rollout(c->cfg.env_kind, c->cfg.dist_kind, c->gen->L, r, c->stream));
@@ -3212,7 +3234,7 @@ static ppo_status envt_state(ppo_ctx* c, const char* what) {
         return fail(c, PPO_ERR_UNSUPPORTED, "%s: this context's environments are the caller's (PPO_ENV_HOST), and only the caller holds the observation an episode "
                                             "ended on: pass it with ppo_host_observe_truncated (ppo_dev_observe for device arrays)", what);
     if (c->env)   // its observation holds its state and the fold runs on the fused critic (fused_env_fold_truncations), or the row says why not
-        return c->env->folds ? PPO_OK
+        return (c->env->folds || c->cut_state) ? PPO_OK
                              : fail(c, PPO_ERR_UNSUPPORTED, "%s: the fold rebuilds the final observation of a cut-off episode from PPO_BUF_OBS, and a %s: not built "
                                                             "for this env", what, c->env->text.no_fold);
     if (c->env_generic)

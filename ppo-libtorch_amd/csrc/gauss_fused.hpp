@@ -82,6 +82,8 @@ struct FusedRolloutArgs {
     float* obs; uint8_t* masks; void* actions; float *logprobs, *rewards, *dones; int32_t* fin_len; float* fin_rew;
     float* next_obs; int32_t* next_done;
     const void* forced;
+    float* cut;   // a context with PPO_KERNEL_ENV_CUT_STATE: the cut-off record, f32 [STATE + 1, T * N] (the KEEP instantiation writes column t * N + env where
+                  // that step's episode reached the limit: the pre-reset state, then 0.0f / 1.0f "the env itself terminated"); null: today's kernel
 };
 // by env kind: the launchers are templates over the trait like the kernels (hipErrorInvalidValue for an env without a row, or without the call)
 hipError_t launch_fused_env_rollout(int env_kind, int dist_kind, const GenLayout& L, const FusedRolloutArgs& r, hipStream_t s);
@@ -104,6 +106,8 @@ struct FusedFoldArgs {
     int32_t* ev_index;
     float* ev_value;
     int64_t ev_cap;
+    const float* cut;           // the cut-off record of a PPO_KERNEL_ENV_CUT_STATE context: EVERY fused env folds from it (cut_state_fold_kernel reads the final
+                                // state there, forms Env::obs of it and replays nothing; obs and actions are not read); null: the two kernels above
 };
 hipError_t fused_env_trunc_fold(int env_kind, const GenLayout& L, const FusedFoldArgs& f, hipStream_t s);
 

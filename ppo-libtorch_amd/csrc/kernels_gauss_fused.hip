@@ -736,6 +736,10 @@ __global__ __launch_bounds__(256) void gauss_slab_reduce_kernel(const float* __r
 // Barriers per step: gf_forward_tile's four and one behind the stores (X and the done words are rewritten for the next step); every thread runs every
 // barrier, a short tile masks its stores only.  No workgroup talks to another.  LDS: gf_lds_floats(4, 4) = 14 144 floats = 56 576 bytes, two workgroups per CU
 // (Env::OBS <= 4: rows Env::OBS .. 3 of the X image are zero padding, written once).
+// KEEP (a context with PPO_KERNEL_ENV_CUT_STATE; false: the kernel as it is without the parameter, which every other context launches): the owning lane runs
+// step_episode_keep<Env> (ppo_internal.hpp) in the place of Env::step_episode -- the same step, bookkeeping and reset, and where the episode's length
+// reaches the limit on this step, Env::STATE + 1 stores of the pre-reset state and the terminated word into column t N + env of the record a.cut
+// [STATE + 1, T N].  No store at any other sample; cut_state_fold_kernel (below) reads the record.
 // ---------------------------------------------------------------------------------------------------------
 struct GfRolloutArgs {
     GfShape sh;
@@ -756,9 +760,10 @@ struct GfRolloutArgs {
     float* next_obs;         // [N, Env::OBS]
     int32_t* next_done;
     const float* forced;     // [T, N, 1] or null
+    float* cut;              // KEEP: the cut-off record [Env::STATE + 1, T * N]; null otherwise
 };
 
-template <class Env>
+template <class Env, bool KEEP>
 __global__ __launch_bounds__(GF_THREADS) void gauss_rollout_kernel(GfRolloutArgs a) {
     constexpr int OBS = Env::OBS;
     static_assert(OBS <= 4 && Env::STATE == 2, "the rollout kernel carves its LDS for an observation of at most 4 floats and keeps a state of 2 in registers");
@@ -806,7 +811,12 @@ __global__ __launch_bounds__(GF_THREADS) void gauss_rollout_kernel(GfRolloutArgs
                 lp += gauss_logp(gauss_z(act, mu, expf(-ls)), ls);
                 int fin_len;
                 float fin_rew;
-                const float r = Env::step_episode(st, act, a.max_episode_steps, a.seed, env_global, ep_len, ep_rew, resets, done, fin_len, fin_rew);
+                float r;
+                if constexpr (KEEP)
+                    r = step_episode_keep<Env>(st, act, a.max_episode_steps, a.seed, env_global, ep_len, ep_rew, resets, done, fin_len, fin_rew, a.cut + tn + env,
+                                               (size_t)a.T * N);
+                else
+                    r = Env::step_episode(st, act, a.max_episode_steps, a.seed, env_global, ep_len, ep_rew, resets, done, fin_len, fin_rew);
                 Env::obs(st, ob);
                 a.actions[tn + env] = act;
                 a.logprobs[tn + env] = (float)lp;
@@ -1117,6 +1127,7 @@ __global__ __launch_bounds__(GF_THREADS) void gauss_eval_kernel(GfEvalArgs a) {
 // PPO_ENV_BLACKJACK (OBS 45, 2 logits, HOT 3): gf_carve(48, 4) = 79 808 bytes (the attribute).  What differs between the lanes of wave 0 here is the WORK of a
 // step: a hit is one Philox call, a stick the call of the hidden card, the dealer's (one more, seldom two) and the two of the reset that follows -- lanes that
 // hit wait for lanes that stick, the wave pays the longest lane's path each step.
+// KEEP: as in gauss_rollout_kernel -- step_episode_keep<Env> in the place of Env::step_episode, the record a.cut [STATE + 1, T N]; false is the kernel as it was.
 // ---------------------------------------------------------------------------------------------------------
 struct CfRolloutArgs {
     GfShape sh;
@@ -1138,6 +1149,7 @@ struct CfRolloutArgs {
     float* next_obs;         // [N, Env::OBS]
     int32_t* next_done;
     const int64_t* forced;   // [T, N, 1] or null
+    float* cut;              // KEEP: the cut-off record [Env::STATE + 1, T * N]; null otherwise
 };
 
 // wave 0's lane behind the forward: the row's head on the lane's columns (z: OUT, log-probs in place; p: H1), the action (GREEDY: the first-index argmax of
@@ -1175,7 +1187,7 @@ __device__ __forceinline__ uint32_t cat_draw_word(int64_t seed, int64_t row, int
     return (step_index & 3) == 0 ? w.x : ((step_index & 3) == 1 ? w.y : ((step_index & 3) == 2 ? w.z : w.w));
 }
 
-template <class Env, int DIST>
+template <class Env, int DIST, bool KEEP>
 __global__ __launch_bounds__(GF_THREADS) void cat_rollout_kernel(CfRolloutArgs a) {
     constexpr int OBS = Env::OBS, ST = Env::STATE, A = Env::ACTIONS, OBSP = (OBS + 3) & ~3, OUTP = (A + 3) & ~3;
     constexpr bool MASKED = Env::HAS_MASK && DIST == PPO_DIST_MASKED;   // the env's mask is drawn under and stored; otherwise PPO_BUF_MASKS holds ones
@@ -1250,7 +1262,12 @@ __global__ __launch_bounds__(GF_THREADS) void cat_rollout_kernel(CfRolloutArgs a
                                                                                                       a.forced ? cat_action_int(a.forced[tn + env]) : 0, ws, lp);
                 int fin_len;
                 float fin_rew;
-                const float r = Env::step_episode(st, act, a.max_episode_steps, a.seed, env_global, ep_len, ep_rew, resets, done, fin_len, fin_rew);
+                float r;
+                if constexpr (KEEP)
+                    r = step_episode_keep<Env>(st, act, a.max_episode_steps, a.seed, env_global, ep_len, ep_rew, resets, done, fin_len, fin_rew, a.cut + tn + env,
+                                               (size_t)a.T * N);
+                else
+                    r = Env::step_episode(st, act, a.max_episode_steps, a.seed, env_global, ep_len, ep_rew, resets, done, fin_len, fin_rew);
                 if constexpr (!Env::OBS_ONE_HOT) Env::obs(st, ob);
                 a.actions[tn + env] = act;
                 a.logprobs[tn + env] = lp;
@@ -1546,6 +1563,112 @@ __global__ __launch_bounds__(DEV_FOLD_THREADS) void cat_trunc_fold_kernel(CfFold
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// cut_state_fold_kernel<Env> (ppo_env_truncation_bootstrap on a context with PPO_KERNEL_ENV_CUT_STATE, every GaussEnv* and CatEnv* trait): cat_trunc_fold_kernel's
+// plan on the record the KEEP rollout wrote (step_episode_keep), so nothing is replayed and no action is read.  A 256-thread workgroup owns 256 consecutive
+// flat samples.  Every thread reads FIN_LEN[i]; a lane whose episode reached the limit reads column i of the record [STATE + 1, B] -- written by this rollout
+// at exactly these samples, so a stale column is never read -- and keeps the sample unless the terminated word is set.  ONE compaction (fold_compact); a
+// workgroup that keeps none returns before it loads a weight (the count is the same in every thread, so the return is uniform).  The kept STATES wait in LDS
+// in list order; the critic's weights are staged on gauss_values_kernel's carve, and per tile of 64 wave 0's lanes write Env::obs(state) into the X image --
+// on an OBS_ONE_HOT env the lane's column is zeroed and the HOT ones set -- so 256 observations are never held.  gf_forward_tile is gauss_values_kernel's
+// forward, so v is that kernel's value of the final observation, bit for bit.  Lane k of wave 0 folds row k of the tile (fold_store: two roundings).
+// LDS: all dynamic, counted by the launcher (cut_fold_lds_bytes) -- gf_lds_floats(obsP, 4) floats, the kept states [256][STATE], the row list [256] and the
+// waves' totals [8]: 54 464 + 528 obsP + 1 024 STATE + 1 056 bytes.  Observation 2 and 3 (STATE 2): 59 680; 6: 63 840; 16: 68 064; 19: 70 176; 45: 84 960;
+// 64: 93 408 -- above 64 KB from 16 on: the attribute is asked for (gf_allow).
+// ---------------------------------------------------------------------------------------------------------
+struct CutFoldArgs {
+    GfShape sh;
+    const float* params;
+    const float* cut;          // [Env::STATE + 1, B]
+    const int32_t* fin_len;
+    int64_t B;
+    int max_episode_steps;
+    float gamma;
+    float* rewards;
+    int32_t* ev_count;
+    int32_t* ev_index;
+    float* ev_value;
+    int64_t ev_cap;
+};
+
+template <class Env>
+int cut_fold_lds_bytes() {   // every byte of LDS the kernel uses: the attribute is decided on this sum
+    return (gf_lds_floats(gf_pad4(Env::OBS), 4) + DEV_FOLD_THREADS * Env::STATE) * (int)sizeof(float) + GF_DEV_FOLD_LIST_INTS * (int)sizeof(int);
+}
+
+template <class Env, bool = Env::OBS_ONE_HOT>
+struct CutFoldObs {   // lane `tid` of wave 0 writes the observation of `fs` (valid) or zeros into its column of the X image; padding rows are zero already
+    __device__ static __forceinline__ void write(const GfLds& m, int tid, bool valid, const float* fs) {
+        float ob[Env::OBS];
+#pragma unroll
+        for (int j = 0; j < Env::OBS; j++) ob[j] = 0.0f;
+        if (valid) Env::obs(fs, ob);
+#pragma unroll
+        for (int j = 0; j < Env::OBS; j++) m.x[j * GF_S + tid] = ob[j];
+    }
+};
+template <class Env>
+struct CutFoldObs<Env, true> {   // one-hot: Env::HOT ones over zeros (Env::hot clamps the state's words, so the rows are inside the image)
+    __device__ static __forceinline__ void write(const GfLds& m, int tid, bool valid, const float* fs) {
+#pragma unroll
+        for (int j = 0; j < Env::OBS; j++) m.x[j * GF_S + tid] = 0.0f;
+        if (valid) {
+            int rows[Env::HOT];
+            Env::hot(fs, rows);
+#pragma unroll
+            for (int j = 0; j < Env::HOT; j++) m.x[rows[j] * GF_S + tid] = 1.0f;
+        }
+    }
+};
+
+template <class Env>
+__global__ __launch_bounds__(DEV_FOLD_THREADS) void cut_state_fold_kernel(CutFoldArgs a) {
+    constexpr int OBS = Env::OBS, ST = Env::STATE, OBSP = (OBS + 3) & ~3;
+    static_assert(DEV_FOLD_THREADS == GF_THREADS, "fold_compact and gf_forward_tile are written for the same workgroup");
+    extern __shared__ __attribute__((aligned(16))) float gf_lds[];
+    float* fst = gf_lds + gf_lds_floats(OBSP, 4);
+    int* list = reinterpret_cast<int*>(fst + DEV_FOLD_THREADS * ST);
+    int* wtot = list + DEV_FOLD_THREADS;
+    const int tid = threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * DEV_FOLD_THREADS + tid;
+    bool keep = false;
+    float st[ST];
+#pragma unroll
+    for (int j = 0; j < ST; j++) st[j] = 0.0f;
+    if (i < a.B && a.fin_len[i] == a.max_episode_steps) {
+#pragma unroll
+        for (int j = 0; j < ST; j++) st[j] = a.cut[(int64_t)j * a.B + i];
+        keep = a.cut[(int64_t)ST * a.B + i] == 0.0f;
+    }
+    int pos;
+    const int cnt = fold_compact(keep, (int)i, a.ev_count, list, wtot, pos);
+    if (cnt == 0) return;
+    const int base = wtot[4];
+    if (keep) {
+#pragma unroll
+        for (int j = 0; j < ST; j++) fst[pos * ST + j] = st[j];
+    }
+    const GfLds m = gf_carve(gf_lds, OBSP, 4);
+    gf_stage_weights(m, a.sh, a.params, 0, tid);
+    if (tid < 64) {   // the padding rows of the observation image, once
+#pragma unroll
+        for (int k = OBS; k < OBSP; k++) m.x[k * GF_S + tid] = 0.0f;
+    }
+    __syncthreads();   // the kept states are complete
+    for (int k0 = 0; k0 < cnt; k0 += 64) {
+        const int k = k0 + tid;   // tid < 64: this lane's place in the list
+        if (tid < 64) {
+            float fs[ST];
+#pragma unroll
+            for (int j = 0; j < ST; j++) fs[j] = k < cnt ? fst[k * ST + j] : 0.0f;
+            CutFoldObs<Env>::write(m, tid, k < cnt, fs);
+        }
+        gf_forward_tile(m, 1, tid);
+        if (tid < 64 && k < cnt) fold_store(a.rewards, a.gamma, a.ev_index, a.ev_value, a.ev_cap, (int64_t)base + k, list[k], m.o[tid]);
+        __syncthreads();   // X and OUT are read: the next tile may overwrite them
+    }
+}
+
 template <typename K>
 hipError_t gf_allow(std::atomic<unsigned long long>& done, K kernel, int bytes) {
     return bytes > 64 * 1024 ? allow_dynamic_lds(done, reinterpret_cast<const void*>(kernel)) : hipSuccess;
@@ -1806,6 +1929,7 @@ static KernelArgs rollout_kernel_args(const GenLayout& L, const FusedRolloutArgs
     a.obs = r.obs; a.actions = static_cast<decltype(a.actions)>(r.actions); a.logprobs = r.logprobs; a.rewards = r.rewards; a.dones = r.dones;
     a.fin_len = r.fin_len; a.fin_rew = r.fin_rew;
     a.next_obs = r.next_obs; a.next_done = r.next_done; a.forced = static_cast<decltype(a.forced)>(r.forced);
+    a.cut = r.cut;
     return a;
 }
 template <class KernelArgs>
@@ -1827,26 +1951,31 @@ static GfEvalArgs eval_kernel_args(const GenLayout& L, const FusedEvalArgs& e) {
     return a;
 }
 
-template <class Env>
+template <class Env, bool KEEP>
 static hipError_t gauss_rollout_launch(const GenLayout& L, const FusedRolloutArgs& r, hipStream_t s) {
     if (!gauss_env_shape_ok<Env>(L)) return hipErrorInvalidValue;
     const GfRolloutArgs a = rollout_kernel_args<GfRolloutArgs>(L, r);
     const int bytes = gf_lds_floats(4, 4) * 4;
     static std::atomic<unsigned long long> done{ 0 };
-    const hipError_t e = gf_allow(done, gauss_rollout_kernel<Env>, bytes);
+    const hipError_t e = gf_allow(done, gauss_rollout_kernel<Env, KEEP>, bytes);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(gauss_rollout_kernel<Env>, dim3((unsigned)((r.N + 63) / 64)), dim3(GF_THREADS), bytes, s, a);
+    hipLaunchKernelGGL((gauss_rollout_kernel<Env, KEEP>), dim3((unsigned)((r.N + 63) / 64)), dim3(GF_THREADS), bytes, s, a);
     return hipGetLastError();
 }
 // cat_rollout_kernel<Env, DIST> for the context's distribution; the attribute where the carve passes 64 KB (PPO_ENV_TAXI: 67 136 bytes; PPO_ENV_FROZENLAKE8X8: 88 256; PPO_ENV_BLACKJACK: 79 808)
-template <class Env, int DIST>
-static hipError_t cat_rollout_launch(const CfRolloutArgs& a, int N, hipStream_t s) {
+// KEEP (a context with PPO_KERNEL_ENV_CUT_STATE): the instantiation that also writes the cut-off record; a.cut is null exactly where KEEP is false
+template <class Env, int DIST, bool KEEP>
+static hipError_t cat_rollout_launch_keep(const CfRolloutArgs& a, int N, hipStream_t s) {
     const int bytes = cat_env_lds_bytes<Env>();
     static std::atomic<unsigned long long> done{ 0 };
-    const hipError_t e = gf_allow(done, cat_rollout_kernel<Env, DIST>, bytes);
+    const hipError_t e = gf_allow(done, cat_rollout_kernel<Env, DIST, KEEP>, bytes);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((cat_rollout_kernel<Env, DIST>), dim3((unsigned)((N + 63) / 64)), dim3(GF_THREADS), bytes, s, a);
+    hipLaunchKernelGGL((cat_rollout_kernel<Env, DIST, KEEP>), dim3((unsigned)((N + 63) / 64)), dim3(GF_THREADS), bytes, s, a);
     return hipGetLastError();
+}
+template <class Env, int DIST>
+static hipError_t cat_rollout_launch(const CfRolloutArgs& a, int N, hipStream_t s) {
+    return a.cut ? cat_rollout_launch_keep<Env, DIST, true>(a, N, s) : cat_rollout_launch_keep<Env, DIST, false>(a, N, s);
 }
 template <class Env, int DIST>
 static hipError_t cat_eval_launch(const GfEvalArgs& a, hipStream_t s) {
@@ -1860,7 +1989,9 @@ static hipError_t cat_eval_launch(const GfEvalArgs& a, hipStream_t s) {
 
 hipError_t launch_fused_env_rollout(int env_kind, int dist_kind, const GenLayout& L, const FusedRolloutArgs& r, hipStream_t s) {
     if (r.N <= 0 || r.T <= 0) return hipSuccess;
-    return fused_env_dispatch(env_kind, [&](auto env) { return gauss_rollout_launch<decltype(env)>(L, r, s); }, [&](auto env) {
+    return fused_env_dispatch(env_kind, [&](auto env) {
+        return r.cut ? gauss_rollout_launch<decltype(env), true>(L, r, s) : gauss_rollout_launch<decltype(env), false>(L, r, s);
+    }, [&](auto env) {
         using Env = decltype(env);
         if (!cat_env_shape_ok<Env>(L) || !cat_env_dist_ok<Env>(dist_kind)) return hipErrorInvalidValue;
         CfRolloutArgs a = rollout_kernel_args<CfRolloutArgs>(L, r);
@@ -1877,6 +2008,25 @@ hipError_t fused_env_trunc_fold(int env_kind, const GenLayout& L, const FusedFol
     if (f.B <= 0 || f.max_episode_steps <= 0) return hipSuccess;   // no limit: no episode is ever cut off
     if (f.B >= (1ll << 31)) return hipErrorInvalidValue;
     const unsigned grid = (unsigned)((f.B + DEV_FOLD_THREADS - 1) / DEV_FOLD_THREADS);
+    if (f.cut) {   // PPO_KERNEL_ENV_CUT_STATE: every env of either family folds from the record its rollout kept
+        auto from_record = [&](auto env, bool shape_ok) {
+            using Env = decltype(env);
+            if (!shape_ok) return hipErrorInvalidValue;
+            CutFoldArgs a{};
+            a.sh = gf_shape(L);
+            a.params = f.params; a.cut = f.cut; a.fin_len = f.fin_len;
+            a.B = f.B; a.max_episode_steps = f.max_episode_steps; a.gamma = f.gamma;
+            a.rewards = f.rewards; a.ev_count = f.ev_count; a.ev_index = f.ev_index; a.ev_value = f.ev_value; a.ev_cap = f.ev_cap;
+            const int bytes = cut_fold_lds_bytes<Env>();
+            static std::atomic<unsigned long long> done{ 0 };
+            const hipError_t e = gf_allow(done, cut_state_fold_kernel<Env>, bytes);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL(cut_state_fold_kernel<Env>, dim3(grid), dim3(DEV_FOLD_THREADS), bytes, s, a);
+            return hipGetLastError();
+        };
+        return fused_env_dispatch(env_kind, [&](auto env) { return from_record(env, gauss_env_shape_ok<decltype(env)>(L)); },
+                                  [&](auto env) { return from_record(env, cat_env_shape_ok<decltype(env)>(L)); });
+    }
     return fused_env_dispatch(env_kind, [&](auto env) {
         using Env = decltype(env);
         if constexpr (Env::OBS_IS_STATE) {

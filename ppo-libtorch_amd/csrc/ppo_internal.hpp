@@ -362,6 +362,7 @@ __device__ __forceinline__ float mcc_step_episode(float* st, float a, int max_ep
 struct GaussEnvPendulum {
     static constexpr int OBS = 3, STATE = 2;
     static constexpr bool OBS_IS_STATE = false;
+    static constexpr bool OBS_ONE_HOT = false;   // cut_state_fold_kernel asks every trait
     __device__ static __forceinline__ void obs(const float* st, float* ob) { pendulum_obs(st, ob); }
     __device__ static __forceinline__ float step(float* st, float a, int& terminated) { terminated = 0; return pendulum_step(st, a); }
     __device__ static __forceinline__ void reset(float* st, int k, int64_t seed, int64_t env_global) { pendulum_reset(st, k, seed, env_global); }
@@ -373,6 +374,7 @@ struct GaussEnvPendulum {
 struct GaussEnvMountainCarContinuous {
     static constexpr int OBS = 2, STATE = 2;
     static constexpr bool OBS_IS_STATE = true;
+    static constexpr bool OBS_ONE_HOT = false;
     __device__ static __forceinline__ void obs(const float* st, float* ob) { ob[0] = st[0]; ob[1] = st[1]; }
     __device__ static __forceinline__ float step(float* st, float a, int& terminated) { return mcc_step(st, a, terminated); }
     __device__ static __forceinline__ void reset(float* st, int k, int64_t seed, int64_t env_global) { mcc_reset(st, k, seed, env_global); }
@@ -830,6 +832,36 @@ struct CatEnvBlackjack {
         return r;
     }
 };
+
+// step_episode's sibling for a context with PPO_KERNEL_ENV_CUT_STATE, for every trait above (Action: float on a GaussEnv*, int on a CatEnv*): the trait's
+// bare step and reset under the same bookkeeping, statement for statement (a Gaussian env's step reports terminated = 0 where it never terminates), and one
+// thing more -- where the episode's length reaches the limit on this step, the state the env is in BEFORE the reset (Env::STATE words) and whether the env
+// itself terminated (0.0f / 1.0f) are stored at rec[0], rec[stride], .., rec[Env::STATE * stride].  No other step stores anything.  The traits' own
+// step_episode, which the stand-alone step kernels and the rollouts of every other context run, is not touched.
+template <class Env, class Action>
+__device__ __forceinline__ float step_episode_keep(float* st, Action a, int max_episode_steps, int64_t seed, int64_t env_global, int& ep_len, float& ep_rew,
+                                                   int& resets, int& done, int& fin_len, float& fin_rew, float* rec, size_t stride) {
+    int term;
+    const float r = Env::step(st, a, term);
+    ep_len += 1;
+    ep_rew += r;
+    done = (term || ep_len == max_episode_steps) ? 1 : 0;
+    fin_len = 0;
+    fin_rew = 0.0f;
+    if (done) {
+        fin_len = ep_len;
+        fin_rew = ep_rew;
+        if (ep_len == max_episode_steps) {
+#pragma unroll
+            for (int k = 0; k < Env::STATE; k++) rec[(size_t)k * stride] = st[k];
+            rec[(size_t)Env::STATE * stride] = term ? 1.0f : 0.0f;
+        }
+        Env::reset(st, resets++, seed, env_global);
+        ep_len = 0;
+        ep_rew = 0.0f;
+    }
+    return r;
+}
 
 template <int ENV>
 __device__ __forceinline__ float env_step(float* st, int action, int& terminated) {

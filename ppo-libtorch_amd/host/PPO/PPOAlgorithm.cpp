@@ -74,6 +74,7 @@ void PPOAlgorithm::getArgs() {
         I("environment", "max_episode_steps", m_max_episode_steps);
         I("environment", "env_groups", m_env_groups);   // extension key (PPO_HostEnv); absent in the reference's files: prints nothing then
         B("environment", "bootstrap_truncated", m_bootstrap_truncated);   // extension key (every algorithm class), likewise
+        B("environment", "keep_cut_states", m_keep_cut_states);           // extension key (the fused device-env classes), likewise
         B("environment", "norm_obs", m_norm_obs);                         // extension key (PPO_HostEnv), likewise
         B("environment", "norm_reward", m_norm_reward);                   // extension key (PPO_HostEnv), likewise
         B("environment", "fused_policy", m_fused_policy);                 // extension key (PPO_HostEnvBox), likewise
@@ -154,6 +155,7 @@ void PPOAlgorithm::construct() {
     c.ent_coef = m_ent_coef; c.vf_coef = m_vf_coef; c.max_grad_norm = m_max_grad_norm;
     c.kernel_flags = m_fused_policy ? PPO_KERNEL_GAUSS_FUSED : 0;   // a class whose policy is not Gaussian: the library's refusal is thrown below, with its message
     if (m_fused_categorical) c.kernel_flags |= PPO_KERNEL_CAT_FUSED;   // likewise for a class whose context is not a caller-stepped categorical one
+    if (m_keep_cut_states) c.kernel_flags |= PPO_KERNEL_ENV_CUT_STATE;   // a class whose env is no fused device env: the library's refusal is thrown below, with its message
     if (m_hidden_size_given) c.kernel_flags |= PPO_KERNEL_ENV_GENERIC;   // CartPole / MountainCar on the generic engine, also at hidden_size = 64; a width out of range is the library's refusal
     ppo::check(ppo_ctx_create(&c, &m_ctx), nullptr, "PPO");    // obs-size mismatch surfaces here with the reference's message (:370-375)
     ppo::check(ppo_params_init_orthogonal(m_ctx, m_seed), m_ctx, "agent init");

@@ -106,6 +106,10 @@ class PPOAlgorithm {
     bool m_fused_categorical = false;    // extension ([environment] fused_categorical): PPO_HostEnv's context runs the fused categorical 2 x 64 kernels (PPO_KERNEL_CAT_FUSED); on any other class the library refuses the context
     bool m_fused_policy = false;         // extension ([environment] fused_policy): PPO_HostEnvBox's context runs the fused Gaussian 2 x 64 kernels (PPO_KERNEL_GAUSS_FUSED); on any other class the library refuses the context
     bool m_norm_reward = false;          // extension ([environment] norm_reward): PPO_HostEnv divides rewards by the running std of the discounted return (ppo_reward_norm_*)
+    // extension ([environment] keep_cut_states; the fused device-env classes PPO_Continuous, PPO_ContinuousMountainCar, PPO_DiscreteAcrobot, PPO_MultiDiscreteTaxi,
+    // PPO_DiscreteFrozenLake, PPO_DiscreteBlackjack): the context is created with PPO_KERNEL_ENV_CUT_STATE -- the rollout keeps the state a time limit cut an
+    // episode off in, and bootstrap_truncated is served on every one of them; on any other class the library refuses the context
+    bool m_keep_cut_states = false;
     bool m_bootstrap_truncated = false;  // extension ([environment] bootstrap_truncated): bootstrap the value where a time limit cut an episode off (every algorithm class; set it with setBootstrapTruncated)
     // extension ([network] hidden_size = H; PPO_Discrete and PPO_MultiDiscrete only): the two hidden layers are H wide and the context runs on the generic engine
     // (PPO_KERNEL_ENV_GENERIC).  Absent: 64, no flag, the reference-shape kernels, nothing printed.  Depth other than 2 and bf16 storage stay with the C-ABI and

@@ -8,6 +8,8 @@
 // the file says -- and one action dimension.  An iteration is what it is for the built-in discrete envs: ppo_rollout (one launch for all T steps, two for
 // the critic), the scan and the update, enqueued by PPOAlgorithm::train().  Checkpoints go through the reference's container with one more tensor, m_logStd
 // (Utils/TorchArchive.h).  evaluate() and bootstrap_truncated are not built for this env: the library's refusal is thrown with its message.
+// [environment] keep_cut_states = true creates the context with PPO_KERNEL_ENV_CUT_STATE: the rollout keeps theta and theta_dot of every cut-off episode, and
+// bootstrap_truncated = true / setBootstrapTruncated(true) is served -- on this env every episode ends at the limit, so every finished episode is bootstrapped.
 #pragma once
 #include "PPOAlgorithm.h"
 #include "../Environments/Pendulum.h"
@@ -19,8 +21,10 @@ class PPO_Continuous : public PPOAlgorithm {
         m_fused_policy = true;
         m_action_size = 1;
         construct();
-        if (m_bootstrap_truncated) setEnvTruncationBootstrap(true);   // throws: the fold is not built for this env
+        if (m_bootstrap_truncated) setEnvTruncationBootstrap(true);   // without keep_cut_states it throws: the fold from PPO_BUF_OBS is not built for this env
     }
     ppo::Tensor initEnvs() { return initEnvsImpl(); }
+    void setBootstrapTruncated(bool on) { setEnvTruncationBootstrap(on); }
+    bool bootstrapTruncated() const { return m_bootstrap_truncated; }
     int64_t actionDim() const { return m_action_size; }
 };

@@ -8,7 +8,8 @@
 // the file says -- and one action dimension, the force.  An iteration is PPO_Continuous's: ppo_rollout (one launch for all T steps, two for the critic), the
 // scan and the update.  The observation of this env is its state, so the two things Pendulum refuses work here: [environment] bootstrap_truncated = true
 // turns on the time-limit fold (one more launch behind the critic's; almost every episode of this env ends at the limit), and evaluate() runs whole episodes
-// in one launch (ppo_evaluate).
+// in one launch (ppo_evaluate).  [environment] keep_cut_states = true creates the context with PPO_KERNEL_ENV_CUT_STATE: the fold then reads the state the
+// rollout kept instead of stepping PPO_BUF_OBS again -- the same events and rewards, bit for bit.
 #pragma once
 #include "PPOAlgorithm.h"
 #include "../Environments/MountainCarContinuous.h"

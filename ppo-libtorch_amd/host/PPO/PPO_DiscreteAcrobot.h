@@ -7,6 +7,8 @@
 // whatever the file says -- and one head of three actions, the torque -1, 0 or +1.  An iteration is ppo_rollout (one launch for all T steps, two for the
 // critic), the scan and the update.  evaluate() runs whole episodes in one launch (ppo_evaluate).  The observation of this env does not hold the angles, so
 // the time-limit fold is not built for it: [environment] bootstrap_truncated = true throws the library's refusal, with its message.
+// [environment] keep_cut_states = true creates the context with PPO_KERNEL_ENV_CUT_STATE: the rollout keeps the state of every cut-off episode, and
+// bootstrap_truncated = true / setBootstrapTruncated(true) is served.
 #pragma once
 #include "PPOAlgorithm.h"
 #include "../Environments/Acrobot.h"

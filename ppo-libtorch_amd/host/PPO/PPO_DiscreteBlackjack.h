@@ -9,6 +9,8 @@
 // and the update.  evaluate() runs whole episodes in one launch (ppo_evaluate); a return is -1, 0 or +1.  The observation of this env holds neither the index
 // of the next card nor the episode's key, so the time-limit fold is not built for it: [environment] bootstrap_truncated = true, and
 // setBootstrapTruncated(true), throw the library's refusal, with its message.
+// [environment] keep_cut_states = true creates the context with PPO_KERNEL_ENV_CUT_STATE: the rollout keeps the state of every cut-off episode (the key and the
+// count with it), and both are served.
 #pragma once
 #include "PPOAlgorithm.h"
 #include "../Environments/Blackjack.h"

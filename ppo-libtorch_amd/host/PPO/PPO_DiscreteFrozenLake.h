@@ -10,6 +10,8 @@
 // T steps, two for the critic), the scan and the update.  evaluate() runs whole episodes in one launch (ppo_evaluate).  The observation of this env holds
 // neither the episode's step count nor its key, so the time-limit fold is not built for it: [environment] bootstrap_truncated = true, and
 // setBootstrapTruncated(true), throw the library's refusal, with its message.
+// [environment] keep_cut_states = true creates the context with PPO_KERNEL_ENV_CUT_STATE: the rollout keeps the state of every cut-off episode (the key and the
+// count with it), and both are served.
 #pragma once
 #include "PPOAlgorithm.h"
 #include "../Environments/FrozenLake.h"

@@ -8,7 +8,8 @@
 // fused_categorical itself, whatever the file says -- and one head of six actions (south, north, east, west, pickup, dropoff).  An iteration is ppo_rollout
 // (one launch for all T steps, two for the critic), the scan and the update.  evaluate() runs whole episodes in one launch (ppo_evaluate).
 // [environment] bootstrap_truncated = true turns the time-limit fold on (ppo_env_truncation_bootstrap: one more launch per rollout; an untrained policy hits
-// the limit in most of its episodes here).
+// the limit in most of its episodes here).  [environment] keep_cut_states = true creates the context with PPO_KERNEL_ENV_CUT_STATE: the fold then reads the
+// state the rollout kept instead of decoding and stepping PPO_BUF_OBS again -- the same events and rewards, bit for bit.
 #pragma once
 #include "PPOAlgorithm.h"
 #include "../Environments/Taxi.h"
