@@ -460,13 +460,26 @@ typedef struct ppo_config {
  *                               what it was, refusals included.  ppo_ctx_create returns PPO_ERR_UNSUPPORTED with a message naming the flag and the limit on
  *                               any other env_kind (PPO_ENV_CARTPOLE, PPO_ENV_MOUNTAINCAR, PPO_ENV_SYNTHETIC, PPO_ENV_HOST) and beside PPO_KERNEL_ENV_GENERIC.
  *                               Everything else a flagged context refuses it refuses as without the flag (ppo_evaluate on Pendulum, ppo_host_* / ppo_dev_*,
- *                               the normalisers).  Sharding (ppo_comm_init*) of a flagged context is neither claimed nor tested. */
+ *                               the normalisers).  Sharding (ppo_comm_init*) of a flagged context is neither claimed nor tested.
+ *   PPO_KERNEL_ENV_REWARD_NORM  the same seven device envs, next to the family flag (and beside PPO_KERNEL_ENV_CUT_STATE if wanted): opens ppo_reward_norm_* on
+ *                               their one-launch rollouts.  Its entry stands at its #define below; the contract in "Reward normalisation". */
 enum { PPO_KERNEL_ROLLOUT_VECTOR = 1, PPO_KERNEL_UPDATE_VECTOR = 2, PPO_KERNEL_UPDATE_ONE_WAVE = 4, PPO_KERNEL_COMM_SELFTEST = 8, PPO_KERNEL_GENERIC_CLASSIC = 16,
        PPO_KERNEL_GENERIC_SPLIT_HEAD = 32, PPO_KERNEL_GAUSS_FUSED = 64 };
 #define PPO_KERNEL_SEPARATE_LAUNCHES 128   /* the next free bit of kernel_flags, 1 << 7; a macro beside the enumerators: same type in an expression, same use */
 #define PPO_KERNEL_CAT_FUSED 256           /* 1 << 8, likewise */
 #define PPO_KERNEL_ENV_GENERIC 512         /* 1 << 9, likewise */
 #define PPO_KERNEL_ENV_CUT_STATE (1 << 10) /* 1024, likewise; written as the shift: tests/test_env_generic_abi.py pins the list of macros spelt as decimal literals */
+/* PPO_KERNEL_ENV_REWARD_NORM (8192; bits 11 and 12 stay unassigned and are refused as unknown): the device envs of the fused 2 x 64 families -- PPO_ENV_PENDULUM,
+ * PPO_ENV_MOUNTAINCAR_CONTINUOUS, PPO_ENV_ACROBOT, PPO_ENV_TAXI, PPO_ENV_FROZENLAKE, PPO_ENV_FROZENLAKE8X8 and PPO_ENV_BLACKJACK -- next to the env's own family
+ * flag, and beside PPO_KERNEL_ENV_CUT_STATE if wanted: it opens ppo_reward_norm_enable / _get_h / _set_h on such a context ("Reward normalisation" below has the
+ * contract).  What it costs: one allocation of the context's own, f64 [T N + 2 T + 2] (8 T N bytes and O(T)), made by ppo_ctx_create and released with the
+ * context; it is no PPO_BUF_* and ppo_get_buffer does not reach it.  The rollout launch is the unflagged context's: a flagged context that never calls
+ * ppo_reward_norm_enable(mode != 0) runs, launch for launch and bit for bit, what its unflagged twin runs.  Opt-in, never implied: without the flag the three
+ * calls refuse a device-env context as before, word for word.  ppo_ctx_create returns PPO_ERR_UNSUPPORTED with a message naming the flag and the limit on any
+ * other env_kind (PPO_ENV_CARTPOLE, PPO_ENV_MOUNTAINCAR, PPO_ENV_SYNTHETIC, PPO_ENV_HOST -- which has the three calls without a flag) and beside
+ * PPO_KERNEL_ENV_GENERIC.  Observation normalisation stays refused (its statistics feed back into the policy inside the one launch).  Sharding (ppo_comm_init*)
+ * of a flagged context is neither claimed nor tested; with the normaliser on it is refused, as on PPO_ENV_HOST. */
+#define PPO_KERNEL_ENV_REWARD_NORM (1 << 13)
 
 /* Scalars the reference prints per update (PPO_Discrete.cpp:700-774) plus per-step diagnostics. */
 typedef struct ppo_stats {
@@ -1041,7 +1054,22 @@ PPO_API ppo_status ppo_obs_norm_apply(ppo_ctx* ctx, const float* obs, int64_t n,
  * Launches: ONE more per env step (rewnorm_update_apply_kernel: one workgroup, sums in a fixed order without atomics, so the same feed gives the same
  * bits), in front of the commit of the step: in ppo_dev_observe (which still only enqueues), in ppo_host_act for the staged step and in
  * ppo_host_rollout_end for the last one.
- * Errors (a failing call changes nothing): PPO_ERR_UNSUPPORTED for any of the three calls on a context that is not PPO_ENV_HOST, for
+ * The fused device envs (PPO_KERNEL_ENV_REWARD_NORM in kernel_flags, above; the library's own Pendulum pays down to -16 a step, MountainCarContinuous +100
+ * at the goal, Taxi -10 to +20): the three calls are served on a flagged context with the same argument checks, modes, defaults and initial state, the same
+ * refusal on a sharded context and of ppo_comm_init* while the normaliser is on.  ppo_env_reset zeroes ret and keeps the statistics; ppo_env_set_state_h
+ * touches neither.  A device-env rollout is ONE launch for all T steps and its rewards never feed back into it (actions, states and stored observations do
+ * not depend on how rewards are scaled), so the normalisation is a post-process of PPO_BUF_REWARDS and PPO_BUF_FIN_LEN: with mode 1, ppo_rollout /
+ * ppo_rollout_f32 / ppo_train_iteration leave in PPO_BUF_REWARDS, ret, mean, var and the count EXACTLY -- the same bits -- what T successive updates as
+ * above would leave, applied to rows t = 0 .. T - 1 of the raw rewards in order with done[t][n] = (PPO_BUF_FIN_LEN[t][n] != 0) and g = (double)cfg.gamma.
+ * The summation order is rewnorm_update_apply_kernel's: slot w of 256 takes envs w, w + 256, ... ascending, the 256 slots are then added in slot order, all
+ * in f64.  Mode 2 applies the frozen variance to all T N rewards and changes nothing else.  The raw reward stays in PPO_BUF_EP_REW, PPO_BUF_FIN_REW,
+ * ep_rew_mean and ppo_evaluate.  The normalisation precedes the time-limit fold (ppo_env_truncation_bootstrap): the events and V of ppo_env_truncations are
+ * what they are without it, and f32(gamma * V) is added to the NORMALISED reward -- by the fold from PPO_BUF_OBS and by the fold from the cut-state record
+ * alike.  Launches: THREE per rollout whatever T is (rewnorm_scan_kernel: one thread per env walks the T steps; rewnorm_moments_kernel: one workgroup per
+ * step; rewnorm_merge_apply_kernel: Chan's chain of T scalar merges, then the apply), one with mode 2, none with mode 0; enqueued behind the two critic
+ * launches and in front of the fold, with no host wait, no floating-point atomics and no hand-over inside a launch.  The rollout kernels are untouched.
+ * The first-batch consequence above is the rule on envs whose first rewards are all equal (Acrobot's -1, FrozenLake's 0): var = 0 there and the clip acts.
+ * Errors (a failing call changes nothing): PPO_ERR_UNSUPPORTED for any of the three calls on a context that is not PPO_ENV_HOST (nor a flagged fused device env), for
  * ppo_reward_norm_enable(mode != 0) on a sharded context (global_num_envs > num_envs or a communicator initialised), for ppo_comm_init /
  * ppo_comm_init_local / ppo_comm_init_exchange on a context with it on, and for ppo_host_rollout_begin_groups with it on (the statistics would depend on
  * the order in which groups commit).  PPO_ERR_STATE for enable / get / set while a rollout is open.  PPO_ERR_INVALID for a mode outside 0 .. 2,

@@ -35,6 +35,9 @@ KERNEL_ENV_GENERIC = 512   # ENV_CARTPOLE / ENV_MOUNTAINCAR on a network of any 
 # the fused device envs (ENV_PENDULUM .. ENV_BLACKJACK), next to the env's family flag: the rollout keeps the state a time limit cut an episode off in, and
 # env_truncation_bootstrap / env_truncations are served on every one of them (include/ppo_hip.h PPO_KERNEL_ENV_CUT_STATE)
 KERNEL_ENV_CUT_STATE = 1024
+# the same envs, next to the family flag: reward_norm_enable / reward_norm_get / reward_norm_set are served on their one-launch rollouts (bits 11 and 12 stay
+# unassigned; include/ppo_hip.h PPO_KERNEL_ENV_REWARD_NORM)
+KERNEL_ENV_REWARD_NORM = 1 << 13
 ABI_VERSION = 5
 COMM_ID_BYTES = 128
 COMM_HANDLE_BYTES = 64
@@ -619,10 +622,11 @@ class Context:
         _check(lib().ppo_obs_norm_apply(self.h, self._dev_ptr(obs), C.c_int64(n), self._dev_ptr(out), self._dev_stream(stream)), self.h)
         return out
 
-    # ---- reward normalisation of caller-stepped envs (include/ppo_hip.h ppo_reward_norm_*)
+    # ---- reward normalisation of caller-stepped envs, and of the fused device envs under KERNEL_ENV_REWARD_NORM (include/ppo_hip.h ppo_reward_norm_*)
     def reward_norm_enable(self, mode=1, clip=10.0, eps=1e-8):
         """mode 0 off, 1 update the running statistics of the discounted return with every step and divide the rewards by its standard deviation,
-        2 divide with frozen statistics."""
+        2 divide with frozen statistics.  On a fused device env created with KERNEL_ENV_REWARD_NORM the T steps of a rollout are normalised behind its
+        one launch, with the bits the per-step path leaves."""
         _check(lib().ppo_reward_norm_enable(self.h, int(mode), float(clip), float(eps)), self.h)
 
     def reward_norm_get(self, returns=False):

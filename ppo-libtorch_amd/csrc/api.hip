@@ -299,6 +299,10 @@ struct ppo_ctx {
     double* rn_ret = nullptr;
     double* rn_stats = nullptr;
     float* rn_rew = nullptr;
+    // PPO_KERNEL_ENV_REWARD_NORM (a fused device env only): the f64 workspace of the whole-rollout normaliser, rewnorm_rollout_workspace(N, T) doubles --
+    // R [T, N], the batch moments [2, T] and the statistics a rollout started from [2]; made by ppo_ctx_create under the flag, no PPO_BUF_*.  Null: the
+    // three ppo_reward_norm_* calls refuse a device-env context (rn_state)
+    double* rn_ws = nullptr;
     GenericCtx* gen = nullptr;       // non-null: synthetic env / network other than 2 x 64 (generic.hpp); every L-dependent entry point dispatches on it
     uint8_t* cur_mask = nullptr;     // generic path: action mask of the observation in NEXT_OBS, [N, A]
     bool force_collectives = false;  // PPO_COMM_SELFTEST: world == 1 but the multi-rank path (RCCL included) is taken
@@ -649,7 +653,7 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
     if (cfg->compute_dtype != PPO_DTYPE_F32 && cfg->compute_dtype != PPO_DTYPE_BF16) return fail(nullptr, PPO_ERR_INVALID, "unknown compute_dtype %d", cfg->compute_dtype);
     constexpr int32_t known_flags = PPO_KERNEL_ROLLOUT_VECTOR | PPO_KERNEL_UPDATE_VECTOR | PPO_KERNEL_UPDATE_ONE_WAVE | PPO_KERNEL_COMM_SELFTEST | PPO_KERNEL_GENERIC_CLASSIC |
                                   PPO_KERNEL_GENERIC_SPLIT_HEAD | PPO_KERNEL_GAUSS_FUSED | PPO_KERNEL_SEPARATE_LAUNCHES | PPO_KERNEL_CAT_FUSED | PPO_KERNEL_ENV_GENERIC |
-                                  PPO_KERNEL_ENV_CUT_STATE;
+                                  PPO_KERNEL_ENV_CUT_STATE | PPO_KERNEL_ENV_REWARD_NORM;
     // PPO_KERNEL_ENV_CUT_STATE: a device env of the fused 2 x 64 families (a row of fused_env_rows), next to that env's own family flag (checked in the env's
     // block below), or a refusal that names the flag.  In front of PPO_KERNEL_ENV_GENERIC's block, so that the two flags together are answered here
     if (cfg->kernel_flags & PPO_KERNEL_ENV_CUT_STATE) {
@@ -661,6 +665,18 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
             return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_ENV_CUT_STATE serves the device envs of the fused 2 x 64 families only (%s; %s): their one-launch "
                         "rollouts keep the state a time limit cut an episode off in; CartPole and MountainCar fold from PPO_BUF_OBS without it, PPO_ENV_SYNTHETIC "
                         "has no last observation and PPO_ENV_HOST passes its own (ppo_host_observe_truncated); got env_kind %d",
+                        fused_env_names(FUSED_GAUSS), fused_env_names(FUSED_CAT), cfg->env_kind);
+    }
+    // PPO_KERNEL_ENV_REWARD_NORM: accepted exactly where PPO_KERNEL_ENV_CUT_STATE is (and beside it), or a refusal that names the flag
+    if (cfg->kernel_flags & PPO_KERNEL_ENV_REWARD_NORM) {
+        if (cfg->kernel_flags & ~known_flags) return fail(nullptr, PPO_ERR_INVALID, "unknown bits in kernel_flags 0x%x", cfg->kernel_flags);
+        if (cfg->kernel_flags & PPO_KERNEL_ENV_GENERIC)
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_ENV_REWARD_NORM excludes PPO_KERNEL_ENV_GENERIC: the rewards are normalised behind the one-launch "
+                        "rollouts of the fused 2 x 64 families, and CartPole / MountainCar on the generic engine run neither");
+        if (!env)
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_ENV_REWARD_NORM serves the device envs of the fused 2 x 64 families only (%s; %s): it opens "
+                        "ppo_reward_norm_* on their one-launch rollouts; CartPole, MountainCar and PPO_ENV_SYNTHETIC pay rewards of unit scale and "
+                        "PPO_ENV_HOST has the three calls without a flag; got env_kind %d",
                         fused_env_names(FUSED_GAUSS), fused_env_names(FUSED_CAT), cfg->env_kind);
     }
     // PPO_KERNEL_ENV_GENERIC: CartPole / MountainCar with a categorical policy and neither flag of the fused 2 x 64 family, or a refusal that names the flag --
@@ -982,6 +998,7 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
         }
         CK(dalloc(c, &c->cur_mask, N * GL.act));
         if (env && (cfg->kernel_flags & PPO_KERNEL_ENV_CUT_STATE)) CK(dalloc(c, &c->cut_state, (size_t)(env->state + 1) * TN));
+        if (env && (cfg->kernel_flags & PPO_KERNEL_ENV_REWARD_NORM)) CK(dalloc(c, &c->rn_ws, rewnorm_rollout_workspace(cfg->num_envs, cfg->num_steps)));
         if (env_generic) {   // CartPole::getActionMask / MountainCar::getActionMask are all ones (MountainCar.cpp:69-77): the mask of every step under PPO_DIST_MASKED
             c->env_generic = true;
             CK(hipMemset(c->cur_mask, 1, N * GL.act));
@@ -1451,6 +1468,8 @@ extern "C" ppo_status ppo_env_reset(ppo_ctx* c) {
     if (c->env) {
         HIPCHK(c, launch_fused_env_reset(c->cfg.env_kind, c->N, c->cfg.seed, c->cfg.env_offset, B_<float>(c, PPO_BUF_ENV_STATE), B_<int32_t>(c, PPO_BUF_EP_LEN), B_<float>(c, PPO_BUF_EP_REW),
                                         B_<int32_t>(c, PPO_BUF_RESET_COUNT), B_<float>(c, PPO_BUF_NEXT_OBS), B_<int32_t>(c, PPO_BUF_NEXT_DONE), c->stream));
+        // reward normalisation (PPO_KERNEL_ENV_REWARD_NORM): every episode starts anew, so the return accumulators do; the statistics stay
+        if (c->rn_ret) HIPCHK(c, hipMemsetAsync(c->rn_ret, 0, (size_t)c->N * sizeof(double), c->stream));
         return PPO_OK;
     }
     if (c->gen && !c->env_generic) {   // synthetic env: memoryless, the observation of global step `rollout_steps` (0 after creation)
@@ -1651,6 +1670,19 @@ static ppo_status env_fold_truncations(ppo_ctx* c) {
     return events_close(c, l);
 }
 
+// Reward normalisation of a fused device env's rollout (PPO_KERNEL_ENV_REWARD_NORM + ppo_reward_norm_enable; kernels_rewnorm.hip: launch_rewnorm_rollout):
+// behind the rollout and its critic launches PPO_BUF_REWARDS [T, N] holds the raw rewards and PPO_BUF_FIN_LEN the dones; rewards never feed back into a
+// rollout, so the T per-step updates of a caller-stepped env are three launches here whatever T is (mode 2: one), enqueued without a wait, and they leave the
+// bits rn_batch's T launches would.  The episode sums (EP_REW, FIN_REW, the ring) were formed inside the rollout from the raw rewards.  Off: no launch.
+static ppo_status env_normalise_rewards(ppo_ctx* c) {
+    if (c->rn_mode == 0) return PPO_OK;
+    HIPCHK(c, launch_rewnorm_rollout(c->rn_mode, B_<float>(c, PPO_BUF_REWARDS), B_<int32_t>(c, PPO_BUF_FIN_LEN), c->N, c->T, c->rn_ret, c->rn_stats, c->rn_ws,
+                                     c->rn_count, c->cfg.gamma, c->rn_eps, c->rn_clip, c->stream));
+    if (c->rn_mode == 1)
+        for (int t = 0; t < c->T; t++) c->rn_count += (double)c->N;   // step by step, as rn_batch counts (and the merge kernel with it)
+    return PPO_OK;
+}
+
 // A fused device env: gauss_rollout_kernel / cat_rollout_kernel (all T steps), then gen_rollout's tail -- the critic over the stored observations and over
 // NEXT_OBS: three launches; with ppo_env_truncation_bootstrap on (an env that folds only), the fold behind them.  forced: the family's action type, or null
 static ppo_status fused_env_rollout(ppo_ctx* c, const void* forced) {
@@ -1681,6 +1713,8 @@ static ppo_status fused_env_rollout(ppo_ctx* c, const void* forced) {
         HIPCHK(c, launch_fused_env_rollout(c->cfg.env_kind, c->cfg.dist_kind, c->gen->L, r, c->stream));
         s = gen_values(c, r.obs, (int64_t)c->T * c->N, B_<float>(c, PPO_BUF_VALUES));
         if (s == PPO_OK) s = gen_values(c, r.next_obs, c->N, B_<float>(c, PPO_BUF_NEXT_VALUE));
+        if (s != PPO_OK) return s;
+        s = env_normalise_rewards(c);   // in front of the fold: gamma * V is added to the normalised reward, as on a caller-stepped env
         if (s != PPO_OK) return s;
         s = env_fold_truncations(c);
         if (s != PPO_OK) return s;
@@ -3524,6 +3558,7 @@ extern "C" ppo_status ppo_obs_norm_apply(ppo_ctx* c, const float* obs, int64_t n
 // (rn_batch above), the accumulators are cleared by the two resets (reset_episode_state).
 // ---------------------------------------------------------------------------------------------------------
 static ppo_status rn_state(ppo_ctx* c, const char* what) {
+    if (c->rn_ws) return PPO_OK;   // a fused device env with PPO_KERNEL_ENV_REWARD_NORM: the launches sit behind its rollout (env_normalise_rewards)
     if (!c->host_env)
         return fail(c, PPO_ERR_UNSUPPORTED, "%s: this context steps its own device environment (env_kind %d%s), whose rewards are of unit scale and never leave "
                                             "the fused rollout; reward normalisation serves PPO_ENV_HOST contexts", what, c->cfg.env_kind, env_generic_note(c));

@@ -1264,6 +1264,12 @@ hipError_t launch_obsnorm_apply(const float* src, float* dst, int64_t N, int O, 
 hipError_t launch_rewnorm_update_apply(const float* rew, const int32_t* done, float* out, int64_t N, double* ret, double* stats, double count, float gamma,
                                        float eps, float clip, hipStream_t s);
 hipError_t launch_rewnorm_apply(const float* rew, float* out, int64_t N, const double* stats, float eps, float clip, hipStream_t s);
+// A whole rollout of a fused device env (PPO_KERNEL_ENV_REWARD_NORM), in place on rew [T, N] with done = (fin_len != 0): mode 1 leaves in rew, ret and stats
+// the bits T launches of update_apply on rows 0 .. T - 1 would leave, in three launches whatever T is (the host advances its count by N per step, as there);
+// mode 2 is the apply over all T N rewards, one launch.  ws: rewnorm_rollout_workspace(N, T) doubles of the context's own (mode 2 does not touch it).
+size_t rewnorm_rollout_workspace(int64_t N, int T);
+hipError_t launch_rewnorm_rollout(int mode, float* rew, const int32_t* fin_len, int64_t N, int T, double* ret, double* stats, double* ws, double count,
+                                  float gamma, float eps, float clip, hipStream_t s);
 hipError_t launch_categorical(int dist_kind, const float* logits, const uint8_t* mask, const int64_t* value, int64_t n, int A,
                               float* m_logits, float* m_probs, float* log_prob, float* entropy, int64_t* mode, hipStream_t s);
 

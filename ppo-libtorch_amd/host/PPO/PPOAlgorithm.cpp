@@ -156,9 +156,12 @@ void PPOAlgorithm::construct() {
     c.kernel_flags = m_fused_policy ? PPO_KERNEL_GAUSS_FUSED : 0;   // a class whose policy is not Gaussian: the library's refusal is thrown below, with its message
     if (m_fused_categorical) c.kernel_flags |= PPO_KERNEL_CAT_FUSED;   // likewise for a class whose context is not a caller-stepped categorical one
     if (m_keep_cut_states) c.kernel_flags |= PPO_KERNEL_ENV_CUT_STATE;   // a class whose env is no fused device env: the library's refusal is thrown below, with its message
+    if (m_env_norm_reward) c.kernel_flags |= PPO_KERNEL_ENV_REWARD_NORM;   // set by the fused device-env classes alone (normRewardOnDeviceEnv): ppo_reward_norm_* on the one-launch rollout
     if (m_hidden_size_given) c.kernel_flags |= PPO_KERNEL_ENV_GENERIC;   // CartPole / MountainCar on the generic engine, also at hidden_size = 64; a width out of range is the library's refusal
     ppo::check(ppo_ctx_create(&c, &m_ctx), nullptr, "PPO");    // obs-size mismatch surfaces here with the reference's message (:370-375)
     ppo::check(ppo_params_init_orthogonal(m_ctx, m_seed), m_ctx, "agent init");
+    // update + apply, clip 10, eps 1e-8, as PPO_HostEnv::setNormReward; in front of the resume, which sets a checkpoint's statistics
+    if (m_env_norm_reward) ppo::check(ppo_reward_norm_enable(m_ctx, 1, 10.0f, 1e-8f), m_ctx, "norm_reward");
     m_agent = std::make_shared<Agent>(m_ctx, m_device, std::vector<int64_t>{ m_action_size });
 
     loadPolicyFromCheckpoint();
@@ -500,7 +503,7 @@ void PPOAlgorithm::loadPolicyFromCheckpoint() {
                     ppo::check(ppo_obs_norm_set_h(m_ctx, f.mean.data(), f.var.data(), m_obs_size, f.count), m_ctx, "load obs norm");
                 }
                 const std::string rside = RewardNormFile::pathFor(a);   // the reward normaliser's, likewise
-                if (m_env_kind == PPO_ENV_HOST && fs::exists(rside)) {
+                if ((m_env_kind == PPO_ENV_HOST || m_env_norm_reward) && fs::exists(rside)) {
                     std::cout << "Loading reward statistics " << rside << "..." << std::endl;
                     const RewardNormFile f = RewardNormFile::read(rside);
                     ppo::check(ppo_reward_norm_set_h(m_ctx, f.mean, f.var, f.count), m_ctx, "load reward norm");

@@ -106,6 +106,11 @@ class PPOAlgorithm {
     bool m_fused_categorical = false;    // extension ([environment] fused_categorical): PPO_HostEnv's context runs the fused categorical 2 x 64 kernels (PPO_KERNEL_CAT_FUSED); on any other class the library refuses the context
     bool m_fused_policy = false;         // extension ([environment] fused_policy): PPO_HostEnvBox's context runs the fused Gaussian 2 x 64 kernels (PPO_KERNEL_GAUSS_FUSED); on any other class the library refuses the context
     bool m_norm_reward = false;          // extension ([environment] norm_reward): PPO_HostEnv divides rewards by the running std of the discounted return (ppo_reward_norm_*)
+    // norm_reward on a fused device-env class (PPO_Continuous, PPO_ContinuousMountainCar, PPO_DiscreteAcrobot, PPO_MultiDiscreteTaxi, PPO_DiscreteFrozenLake,
+    // PPO_DiscreteBlackjack): the class calls normRewardOnDeviceEnv() behind getArgs(), and construct() creates the context with PPO_KERNEL_ENV_REWARD_NORM and
+    // turns the normaliser on.  PPO_Discrete and PPO_MultiDiscrete never set it (CartPole and MountainCar pay rewards of unit scale), nor does PPO_HostEnv
+    bool m_env_norm_reward = false;
+    void normRewardOnDeviceEnv() { m_env_norm_reward = m_norm_reward; }
     // extension ([environment] keep_cut_states; the fused device-env classes PPO_Continuous, PPO_ContinuousMountainCar, PPO_DiscreteAcrobot, PPO_MultiDiscreteTaxi,
     // PPO_DiscreteFrozenLake, PPO_DiscreteBlackjack): the context is created with PPO_KERNEL_ENV_CUT_STATE -- the rollout keeps the state a time limit cut an
     // episode off in, and bootstrap_truncated is served on every one of them; on any other class the library refuses the context

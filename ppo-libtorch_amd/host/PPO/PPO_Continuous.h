@@ -18,6 +18,7 @@ class PPO_Continuous : public PPOAlgorithm {
   public:
     PPO_Continuous() : PPOAlgorithm(PPO_ENV_PENDULUM, PPO_DIST_GAUSSIAN, 3, 200) {
         getArgs();
+        normRewardOnDeviceEnv();   // [environment] norm_reward = true: rewards divided by the running std of the discounted return
         m_fused_policy = true;
         m_action_size = 1;
         construct();

@@ -18,6 +18,7 @@ class PPO_ContinuousMountainCar : public PPOAlgorithm {
   public:
     PPO_ContinuousMountainCar() : PPOAlgorithm(PPO_ENV_MOUNTAINCAR_CONTINUOUS, PPO_DIST_GAUSSIAN, 2, 999) {
         getArgs();
+        normRewardOnDeviceEnv();   // [environment] norm_reward = true: rewards divided by the running std of the discounted return
         m_fused_policy = true;
         m_action_size = 1;
         construct();

@@ -17,6 +17,7 @@ class PPO_DiscreteAcrobot : public PPOAlgorithm {
   public:
     PPO_DiscreteAcrobot() : PPOAlgorithm(PPO_ENV_ACROBOT, PPO_DIST_CATEGORICAL, 6, 500) {
         getArgs();
+        normRewardOnDeviceEnv();   // [environment] norm_reward = true: rewards divided by the running std of the discounted return
         m_fused_categorical = true;
         m_action_size = 3;
         construct();

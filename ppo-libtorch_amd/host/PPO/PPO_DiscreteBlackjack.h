@@ -19,6 +19,7 @@ class PPO_DiscreteBlackjack : public PPOAlgorithm {
   public:
     PPO_DiscreteBlackjack() : PPOAlgorithm(PPO_ENV_BLACKJACK, PPO_DIST_CATEGORICAL, Blackjack::OBS, 100) {
         getArgs();
+        normRewardOnDeviceEnv();   // [environment] norm_reward = true: rewards divided by the running std of the discounted return
         m_fused_categorical = true;
         m_action_size = 2;
         construct();

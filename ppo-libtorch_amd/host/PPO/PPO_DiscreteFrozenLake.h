@@ -20,6 +20,7 @@ class PPO_DiscreteFrozenLake : public PPOAlgorithm {
   public:
     PPO_DiscreteFrozenLake() : PPOAlgorithm(PPO_ENV_FROZENLAKE, PPO_DIST_CATEGORICAL, 16, 100) {
         getArgs();
+        normRewardOnDeviceEnv();   // [environment] norm_reward = true: rewards divided by the running std of the discounted return
         if (m_obs_size == 64) m_env_kind = PPO_ENV_FROZENLAKE8X8;
         m_fused_categorical = true;
         m_action_size = 4;

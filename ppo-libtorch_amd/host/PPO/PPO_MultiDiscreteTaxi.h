@@ -18,6 +18,7 @@ class PPO_MultiDiscreteTaxi : public PPOAlgorithm {
   public:
     PPO_MultiDiscreteTaxi() : PPOAlgorithm(PPO_ENV_TAXI, PPO_DIST_MASKED, 19, 200) {
         getArgs();
+        normRewardOnDeviceEnv();   // [environment] norm_reward = true: rewards divided by the running std of the discounted return
         m_fused_categorical = true;
         m_action_size = 6;
         construct();

@@ -2,8 +2,8 @@
 
     python tools/pendulum_curve.py [--iters 300] [--eval-every 1] [--seeds 1 2 3 4 5] [--gamma 0.95] [--lr 3e-4] [--epochs 10] [--minibatches 8] ...
 
-Hyper-parameters (the defaults below): gamma 0.95 and gae_lambda 0.95 (the rewards are unnormalised, up to -16 a step, and reward normalisation does not
-exist on device envs: a short horizon keeps the returns small), learning rate 3e-4 without annealing, 10 epochs x 8 minibatches of 8192 rows, clip 0.2,
+Hyper-parameters (the defaults below): gamma 0.95 and gae_lambda 0.95 (the rewards are unnormalised, up to -16 a step -- these settings were chosen
+without PPO_KERNEL_ENV_REWARD_NORM, tools/env_reward_norm_curve.py runs them with it: a short horizon keeps the returns small), learning rate 3e-4 without annealing, 10 epochs x 8 minibatches of 8192 rows, clip 0.2,
 ent_coef 0, vf_coef 0.5, max_grad_norm 0.5, norm_adv on, clip_vloss off (a value clip of 0.2 on returns of order -100 would freeze the critic),
 orthogonal init, log_std 0.  300 iterations = 19.7 M env steps take 2.3 s of training on an MI355X (profiles/NOTES.md has the curves; gamma 0.9 with
 lr 1e-3 gets to -245 in 30 iterations and then wanders).
