@@ -480,6 +480,22 @@ enum { PPO_KERNEL_ROLLOUT_VECTOR = 1, PPO_KERNEL_UPDATE_VECTOR = 2, PPO_KERNEL_U
  * PPO_KERNEL_ENV_GENERIC.  Observation normalisation stays refused (its statistics feed back into the policy inside the one launch).  Sharding (ppo_comm_init*)
  * of a flagged context is neither claimed nor tested; with the normaliser on it is refused, as on PPO_ENV_HOST. */
 #define PPO_KERNEL_ENV_REWARD_NORM (1 << 13)
+/* PPO_KERNEL_FUSED_WIDE_OBS (32768; bits 11, 12 and 14 stay unassigned and are refused as unknown): widens the two fused 2 x 64 families to observations of up
+ * to 384 columns on caller-stepped contexts.  Valid only next to exactly one of PPO_KERNEL_GAUSS_FUSED or PPO_KERNEL_CAT_FUSED and only on env_kind =
+ * PPO_ENV_HOST; everything else of that family's contract stands (hidden = 64, n_hidden = 2, PPO_DTYPE_F32, D <= 32 / sum(head_dims) <= 32 within
+ * PPO_MAX_HEADS).  With the flag 1 <= obs_size <= 384 is accepted.  At obs_size <= 64 the launchers pick the family's resident kernels: the flagged context
+ * is its unflagged twin, launch for launch and bit for bit.  At 65 .. 384 they pick kernels_fused_wide.hip's: the same launches (ONE per env step, ONE per
+ * critic batch, ONE per truncation fold of ppo_dev_observe, the update kernel and the slab sum per minibatch step; ppo_gauss_fused_launches counts them in the
+ * same three counters), with layer 1 streamed through LDS in chunks of 64 observation columns -- two buffers of a W1 chunk and two of an X chunk, the next
+ * chunk's loads issued in front of this chunk's products, the lane's 16 accumulators in registers across all chunks (one ascending-k fmaf chain from the bias,
+ * so columns of zeros change no bit).  One forward function serves every entry point: an observation gets the same mean / logits and the same value from
+ * ppo_policy_act*, ppo_host_act* / ppo_dev_act* (env groups included), ppo_get_value, the fold and the update, bit for bit.  LDS: 136 832 bytes at 32 outputs,
+ * 122 048 for the critic (+ 1 056 in the fold), whatever the obs_size: one workgroup per CU.  Known cost: W1 is re-read from L2 once per 64-row tile (up to
+ * 96 KB).  Opt-in, never implied: without the flag every context is what it was, the refusals of obs_size > 64 under either family flag included, word for
+ * word.  ppo_ctx_create returns PPO_ERR_UNSUPPORTED with a message naming the flag and the limit on any other env_kind (the device envs, whose observations are
+ * at most 64 wide; PPO_ENV_CARTPOLE, PPO_ENV_MOUNTAINCAR, PPO_ENV_SYNTHETIC), without a family flag, beside PPO_KERNEL_ENV_GENERIC, and at obs_size > 384.
+ * No symbol and no buffer id of its own.  Sharding (ppo_comm_init*) of a flagged context is neither claimed nor tested. */
+#define PPO_KERNEL_FUSED_WIDE_OBS (1 << 15)
 
 /* Scalars the reference prints per update (PPO_Discrete.cpp:700-774) plus per-step diagnostics. */
 typedef struct ppo_stats {

@@ -38,6 +38,9 @@ KERNEL_ENV_CUT_STATE = 1024
 # the same envs, next to the family flag: reward_norm_enable / reward_norm_get / reward_norm_set are served on their one-launch rollouts (bits 11 and 12 stay
 # unassigned; include/ppo_hip.h PPO_KERNEL_ENV_REWARD_NORM)
 KERNEL_ENV_REWARD_NORM = 1 << 13
+# next to KERNEL_GAUSS_FUSED or KERNEL_CAT_FUSED on an ENV_HOST context: obs_size up to 384, layer 1 streamed in chunks of 64 columns (bits 11, 12 and 14 stay
+# unassigned; include/ppo_hip.h PPO_KERNEL_FUSED_WIDE_OBS)
+KERNEL_FUSED_WIDE_OBS = 1 << 15
 ABI_VERSION = 5
 COMM_ID_BYTES = 128
 COMM_HANDLE_BYTES = 64

@@ -653,7 +653,30 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
     if (cfg->compute_dtype != PPO_DTYPE_F32 && cfg->compute_dtype != PPO_DTYPE_BF16) return fail(nullptr, PPO_ERR_INVALID, "unknown compute_dtype %d", cfg->compute_dtype);
     constexpr int32_t known_flags = PPO_KERNEL_ROLLOUT_VECTOR | PPO_KERNEL_UPDATE_VECTOR | PPO_KERNEL_UPDATE_ONE_WAVE | PPO_KERNEL_COMM_SELFTEST | PPO_KERNEL_GENERIC_CLASSIC |
                                   PPO_KERNEL_GENERIC_SPLIT_HEAD | PPO_KERNEL_GAUSS_FUSED | PPO_KERNEL_SEPARATE_LAUNCHES | PPO_KERNEL_CAT_FUSED | PPO_KERNEL_ENV_GENERIC |
-                                  PPO_KERNEL_ENV_CUT_STATE | PPO_KERNEL_ENV_REWARD_NORM;
+                                  PPO_KERNEL_ENV_CUT_STATE | PPO_KERNEL_ENV_REWARD_NORM | PPO_KERNEL_FUSED_WIDE_OBS;
+    // PPO_KERNEL_FUSED_WIDE_OBS: a PPO_ENV_HOST context next to exactly one of the two family flags, at obs_size <= FUSED_WIDE_MAX_OBS, or a refusal that names the
+    // flag and the limit.  In front of the other flags' blocks, so that the flag beside one of them is answered here.  The family's own blocks below then check
+    // hidden, n_hidden, dtype, the policy's kind and the output width in their own words, against the wider observation limit
+    const bool wide_obs = (cfg->kernel_flags & PPO_KERNEL_FUSED_WIDE_OBS) != 0;
+    if (wide_obs) {
+        if (cfg->kernel_flags & ~known_flags) return fail(nullptr, PPO_ERR_INVALID, "unknown bits in kernel_flags 0x%x", cfg->kernel_flags);
+        if (cfg->kernel_flags & PPO_KERNEL_ENV_GENERIC)
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_FUSED_WIDE_OBS excludes PPO_KERNEL_ENV_GENERIC: it widens the fused 2 x 64 kernel family to obs_size <= %d, "
+                        "and CartPole / MountainCar on the generic engine run none of its kernels", FUSED_WIDE_MAX_OBS);
+        if (!host_env)
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_FUSED_WIDE_OBS serves caller-stepped environments (env_kind = PPO_ENV_HOST) only: it widens the fused "
+                        "2 x 64 kernel family to obs_size <= %d there; the device envs' observations are at most %d wide and run on the family's resident kernels, "
+                        "PPO_ENV_SYNTHETIC is on the generic engine; got env_kind %d", FUSED_WIDE_MAX_OBS, GAUSS_FUSED_MAX_OBS, cfg->env_kind);
+        if (!(cfg->kernel_flags & (PPO_KERNEL_GAUSS_FUSED | PPO_KERNEL_CAT_FUSED)))
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_FUSED_WIDE_OBS needs PPO_KERNEL_GAUSS_FUSED or PPO_KERNEL_CAT_FUSED beside it: it widens that family's kernels "
+                        "to obs_size <= %d and names no engine of its own (the family flag is never implied)", FUSED_WIDE_MAX_OBS);
+        if (!fused_wide_serves_obs(cfg->obs_size))
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_FUSED_WIDE_OBS is built for 1 <= obs_size <= %d (six chunks of %d observation columns); got obs_size = %d",
+                        FUSED_WIDE_MAX_OBS, FUSED_WIDE_CHUNK, cfg->obs_size);
+    }
+    // the observation limit of the two family flags' own checks, and the width their shape predicates see (above GAUSS_FUSED_MAX_OBS the launchers pick the wide kernels)
+    const int fused_max_obs = wide_obs ? FUSED_WIDE_MAX_OBS : GAUSS_FUSED_MAX_OBS;
+    const int fused_obs = wide_obs ? std::min(cfg->obs_size, GAUSS_FUSED_MAX_OBS) : cfg->obs_size;
     // PPO_KERNEL_ENV_CUT_STATE: a device env of the fused 2 x 64 families (a row of fused_env_rows), next to that env's own family flag (checked in the env's
     // block below), or a refusal that names the flag.  In front of PPO_KERNEL_ENV_GENERIC's block, so that the two flags together are answered here
     if (cfg->kernel_flags & PPO_KERNEL_ENV_CUT_STATE) {
@@ -739,8 +762,8 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
         if (cfg->n_hidden != 2) return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED is built for n_hidden = 2; got n_hidden = %d", cfg->n_hidden);
         if (cfg->compute_dtype != PPO_DTYPE_F32)
             return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED is built for compute_dtype = PPO_DTYPE_F32; bf16 storage is not");
-        if (cfg->obs_size < 1 || cfg->obs_size > GAUSS_FUSED_MAX_OBS)
-            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED is built for 1 <= obs_size <= %d; got obs_size = %d", GAUSS_FUSED_MAX_OBS, cfg->obs_size);
+        if (cfg->obs_size < 1 || cfg->obs_size > fused_max_obs)
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED is built for 1 <= obs_size <= %d; got obs_size = %d", fused_max_obs, cfg->obs_size);
     }
     if (cfg->compute_dtype == PPO_DTYPE_BF16 && !generic)
         return fail(nullptr, PPO_ERR_UNSUPPORTED, "compute_dtype = PPO_DTYPE_BF16 applies to networks whose layers are GEMMs (env_kind = PPO_ENV_SYNTHETIC); the reference's "
@@ -767,15 +790,15 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
                         cfg->dist_kind);
         if (cfg->hidden != 64) return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_GAUSS_FUSED is built for hidden = 64; got hidden = %d", cfg->hidden);
         if (cfg->n_hidden != 2) return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_GAUSS_FUSED is built for n_hidden = 2; got n_hidden = %d", cfg->n_hidden);
-        if (cfg->obs_size > GAUSS_FUSED_MAX_OBS)
-            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_GAUSS_FUSED is built for obs_size <= %d; got obs_size = %d", GAUSS_FUSED_MAX_OBS, cfg->obs_size);
-        if (!gauss_fused_serves_shape(cfg->obs_size, cfg->hidden, cfg->n_hidden, A))
+        if (cfg->obs_size > fused_max_obs)
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_GAUSS_FUSED is built for obs_size <= %d; got obs_size = %d", fused_max_obs, cfg->obs_size);
+        if (!gauss_fused_serves_shape(fused_obs, cfg->hidden, cfg->n_hidden, A))
             return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_GAUSS_FUSED is built for 1 <= D <= %d and 1 <= obs_size <= %d; got D = %d, obs_size = %d", PPO_MAX_ACT,
-                        GAUSS_FUSED_MAX_OBS, A, cfg->obs_size);
+                        fused_max_obs, A, cfg->obs_size);
     }
-    if (cat_fused && !cat_fused_serves_shape(cfg->obs_size, cfg->hidden, cfg->n_hidden, A))   // the head list's limits are the ABI's own, checked above
+    if (cat_fused && !cat_fused_serves_shape(fused_obs, cfg->hidden, cfg->n_hidden, A))   // the head list's limits are the ABI's own, checked above
         return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED is built for sum(head_dims) <= %d and 1 <= obs_size <= %d; got %d, obs_size = %d", PPO_MAX_ACT,
-                    GAUSS_FUSED_MAX_OBS, A, cfg->obs_size);
+                    fused_max_obs, A, cfg->obs_size);
     if (cfg->num_envs < 1 || cfg->num_steps < 1 || cfg->num_minibatches < 1 || cfg->update_epochs < 1)
         return fail(nullptr, PPO_ERR_INVALID, "num_envs, num_steps, num_minibatches, update_epochs must be >= 1");
     const int64_t B = (int64_t)cfg->num_envs * cfg->num_steps;

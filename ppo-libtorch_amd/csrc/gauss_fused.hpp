@@ -42,6 +42,22 @@ hipError_t cat_fused_fwd_bwd(const GenLayout& L, const LossParams& hp, const flo
                              const float* oldlp, const float* adv, const float* ret, const float* oldv, const int32_t* idx, int64_t M, double inv_global_M,
                              double global_M, const AdvStat* adv_stat, float* slab, double* loss_part, float* grads, hipStream_t s);
 
+// ---- PPO_KERNEL_FUSED_WIDE_OBS (kernels_fused_wide.hip): the two families at GAUSS_FUSED_MAX_OBS < obs_size <= FUSED_WIDE_MAX_OBS on a PPO_ENV_HOST context,
+// layer 1 streamed through LDS in chunks of 64 observation columns.  The six launchers above hand such a shape to these, argument for argument (the update's as
+// the kernel arguments they have filled: gauss_fused_dev.hpp); nobody else calls them.  ppo_ctx_create admits the shape only under the flag. ----
+constexpr int FUSED_WIDE_CHUNK = 64;                         // observation columns per chunk of layer 1
+constexpr int FUSED_WIDE_MAX_OBS = 6 * FUSED_WIDE_CHUNK;     // 384: six chunks = 96 dW1 accumulators per lane of the update kernel
+bool fused_wide_serves_obs(int obs);                         // 1 <= obs <= FUSED_WIDE_MAX_OBS (at obs <= GAUSS_FUSED_MAX_OBS the resident kernels run)
+struct GfUpdArgs;
+hipError_t fused_wide_gauss_act(const GenLayout& L, const float* params, const float* obs, const float* forced, int64_t n, int64_t seed, int64_t row_offset,
+                                int64_t step_index, bool greedy, float* action, float* logprob, float* entropy, const GaussStepStores* st, hipStream_t s);
+hipError_t fused_wide_cat_act(const GenLayout& L, int dist_kind, const float* params, const float* obs, const uint8_t* mask, const int64_t* forced, int64_t n,
+                              int64_t seed, int64_t row_offset, int64_t step_index, bool greedy, int64_t* action, float* logprob, float* entropy,
+                              const CatStepStores* st, hipStream_t s);
+hipError_t fused_wide_values(const GenLayout& L, const float* params, const float* obs, int64_t n, float* value, hipStream_t s);
+hipError_t fused_wide_dev_fold(const GenLayout& L, const float* params, const DevFoldArgs& a, hipStream_t s);
+hipError_t fused_wide_fwd_bwd(const GenLayout& L, const GfUpdArgs& a, float* grads, hipStream_t s);   // the policy's kind is a.hp.dist_kind
+
 // ---- The device envs of the two fused families.  An env is a trait in ppo_internal.hpp (GaussEnv*: one real-valued action; CatEnv*: one head of integer
 // actions), one line of its family's dispatcher and one row of the table in kernels_gauss_fused.hip; everything the C-ABI layer knows about an env it reads
 // from the row.  The numbers of a row come from the trait. ----
