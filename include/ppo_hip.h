@@ -496,6 +496,23 @@ enum { PPO_KERNEL_ROLLOUT_VECTOR = 1, PPO_KERNEL_UPDATE_VECTOR = 2, PPO_KERNEL_U
  * at most 64 wide; PPO_ENV_CARTPOLE, PPO_ENV_MOUNTAINCAR, PPO_ENV_SYNTHETIC), without a family flag, beside PPO_KERNEL_ENV_GENERIC, and at obs_size > 384.
  * No symbol and no buffer id of its own.  Sharding (ppo_comm_init*) of a flagged context is neither claimed nor tested. */
 #define PPO_KERNEL_FUSED_WIDE_OBS (1 << 15)
+/* PPO_KERNEL_FUSED_MATRIX (65536; bits 11, 12 and 14 stay unassigned and are refused as unknown): runs the 64-wide layer products of the two fused 2 x 64
+ * families on the f32 matrix cores (v_mfma_f32_16x16x4_f32) on caller-stepped contexts.  Valid only next to exactly one of PPO_KERNEL_GAUSS_FUSED or
+ * PPO_KERNEL_CAT_FUSED and only on env_kind = PPO_ENV_HOST, with or without PPO_KERNEL_FUSED_WIDE_OBS; everything else of that family's contract stands
+ * (hidden = 64, n_hidden = 2, PPO_DTYPE_F32, D <= 32 / sum(head_dims) <= 32 within PPO_MAX_HEADS, obs_size <= 64, or <= 384 beside the wide flag).  A flagged
+ * context runs kernels_fused_matrix.hip's kernels at every observation width: the same launches (ONE per env step, ONE per critic batch, ONE per truncation
+ * fold of ppo_dev_observe, the update kernel and the slab sum per minibatch step; ppo_gauss_fused_launches counts them in the same three counters), the same
+ * workgroup, LDS images, heads, draws, loss lanes and slab layout.  What moves: layer 1 (in chunks of 64 observation columns, W1 from global memory straight
+ * into the waves' operand registers), layer 2, dZ1 = (W2^T dZ2)(1 - H1^2), dW2 and dW1; layer 3 and its backward stay on the vector ALU.  The operands are
+ * plain f32 and the accumulation is f32, but the summation order is the instruction's, not the ascending-k fmaf chain: the bits differ from the unflagged
+ * context's, within the family's f32 bars.  One forward function serves every entry point: an observation gets the same mean / logits and the same value from
+ * ppo_policy_act*, ppo_host_act* / ppo_dev_act* (env groups included), ppo_get_value, the fold and the update, bit for bit; no float atomics, so equal inputs
+ * give equal bits on every run.  LDS: 104 064 bytes at 32 outputs, 89 280 for the critic (+ 1 056 in the fold), whatever the obs_size.  Opt-in, never implied:
+ * without the flag every context is what it was, refusals included, word for word.  ppo_ctx_create returns PPO_ERR_UNSUPPORTED with a message naming the flag
+ * and the limit on any other env_kind (the device envs, PPO_ENV_CARTPOLE, PPO_ENV_MOUNTAINCAR, PPO_ENV_SYNTHETIC), without a family flag, with both family
+ * flags, and beside PPO_KERNEL_ENV_GENERIC.  No symbol and no buffer id of its own.  Sharding (ppo_comm_init*) of a flagged context is neither claimed nor
+ * tested. */
+#define PPO_KERNEL_FUSED_MATRIX (1 << 16)
 
 /* Scalars the reference prints per update (PPO_Discrete.cpp:700-774) plus per-step diagnostics. */
 typedef struct ppo_stats {

@@ -41,6 +41,9 @@ KERNEL_ENV_REWARD_NORM = 1 << 13
 # next to KERNEL_GAUSS_FUSED or KERNEL_CAT_FUSED on an ENV_HOST context: obs_size up to 384, layer 1 streamed in chunks of 64 columns (bits 11, 12 and 14 stay
 # unassigned; include/ppo_hip.h PPO_KERNEL_FUSED_WIDE_OBS)
 KERNEL_FUSED_WIDE_OBS = 1 << 15
+# next to KERNEL_GAUSS_FUSED or KERNEL_CAT_FUSED on an ENV_HOST context, with or without KERNEL_FUSED_WIDE_OBS: the 64-wide layer products on the f32 matrix
+# cores (include/ppo_hip.h PPO_KERNEL_FUSED_MATRIX)
+KERNEL_FUSED_MATRIX = 1 << 16
 ABI_VERSION = 5
 COMM_ID_BYTES = 128
 COMM_HANDLE_BYTES = 64

@@ -653,7 +653,27 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
     if (cfg->compute_dtype != PPO_DTYPE_F32 && cfg->compute_dtype != PPO_DTYPE_BF16) return fail(nullptr, PPO_ERR_INVALID, "unknown compute_dtype %d", cfg->compute_dtype);
     constexpr int32_t known_flags = PPO_KERNEL_ROLLOUT_VECTOR | PPO_KERNEL_UPDATE_VECTOR | PPO_KERNEL_UPDATE_ONE_WAVE | PPO_KERNEL_COMM_SELFTEST | PPO_KERNEL_GENERIC_CLASSIC |
                                   PPO_KERNEL_GENERIC_SPLIT_HEAD | PPO_KERNEL_GAUSS_FUSED | PPO_KERNEL_SEPARATE_LAUNCHES | PPO_KERNEL_CAT_FUSED | PPO_KERNEL_ENV_GENERIC |
-                                  PPO_KERNEL_ENV_CUT_STATE | PPO_KERNEL_ENV_REWARD_NORM | PPO_KERNEL_FUSED_WIDE_OBS;
+                                  PPO_KERNEL_ENV_CUT_STATE | PPO_KERNEL_ENV_REWARD_NORM | PPO_KERNEL_FUSED_WIDE_OBS | PPO_KERNEL_FUSED_MATRIX;
+    // PPO_KERNEL_FUSED_MATRIX: a PPO_ENV_HOST context next to exactly one of the two family flags (with or without PPO_KERNEL_FUSED_WIDE_OBS), or a refusal that
+    // names the flag and the limit.  In front of the other flags' blocks, so that the flag beside one of them is answered here.  The family's own blocks below
+    // then check hidden, n_hidden, dtype, the policy's kind, the output width and the observation width in their own words
+    const bool fused_matrix = (cfg->kernel_flags & PPO_KERNEL_FUSED_MATRIX) != 0;
+    if (fused_matrix) {
+        if (cfg->kernel_flags & ~known_flags) return fail(nullptr, PPO_ERR_INVALID, "unknown bits in kernel_flags 0x%x", cfg->kernel_flags);
+        if (cfg->kernel_flags & PPO_KERNEL_ENV_GENERIC)
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_FUSED_MATRIX excludes PPO_KERNEL_ENV_GENERIC: it moves the 64-wide products of the fused 2 x 64 kernel "
+                        "family (hidden = 64, n_hidden = 2) to the matrix cores, and CartPole / MountainCar on the generic engine run none of its kernels");
+        if (!host_env)
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_FUSED_MATRIX serves caller-stepped environments (env_kind = PPO_ENV_HOST) only: its kernels are the "
+                        "act, critic, fold and update kernels of the fused 2 x 64 family there; the device envs' one-launch rollouts, CartPole, MountainCar and "
+                        "PPO_ENV_SYNTHETIC run none of them; got env_kind %d", cfg->env_kind);
+        if (!(cfg->kernel_flags & (PPO_KERNEL_GAUSS_FUSED | PPO_KERNEL_CAT_FUSED)))
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_FUSED_MATRIX needs PPO_KERNEL_GAUSS_FUSED or PPO_KERNEL_CAT_FUSED beside it: it moves that family's 64-wide "
+                        "products (hidden = 64, n_hidden = 2) to the matrix cores and names no engine of its own (the family flag is never implied)");
+        if ((cfg->kernel_flags & PPO_KERNEL_GAUSS_FUSED) && (cfg->kernel_flags & PPO_KERNEL_CAT_FUSED))
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_FUSED_MATRIX takes exactly one of PPO_KERNEL_GAUSS_FUSED and PPO_KERNEL_CAT_FUSED beside it: a policy is "
+                        "categorical or Gaussian; got both");
+    }
     // PPO_KERNEL_FUSED_WIDE_OBS: a PPO_ENV_HOST context next to exactly one of the two family flags, at obs_size <= FUSED_WIDE_MAX_OBS, or a refusal that names the
     // flag and the limit.  In front of the other flags' blocks, so that the flag beside one of them is answered here.  The family's own blocks below then check
     // hidden, n_hidden, dtype, the policy's kind and the output width in their own words, against the wider observation limit
@@ -818,6 +838,7 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
     if (generic) {
         c->gen = new GenericCtx();
         c->gen->L = make_gen_layout(cfg->obs_size, cfg->hidden, cfg->n_hidden, cfg->n_heads, cfg->head_dims, gauss);
+        c->gen->L.fused_matrix = fused_matrix;
         // the shared code sizes the flat parameter / gradient / moment buffers from L.P; the 2 x 64 offsets in L are not used
         c->L.P = c->gen->L.P;
         c->L.n_tensors = c->gen->L.n_tensors;

@@ -58,6 +58,18 @@ hipError_t fused_wide_values(const GenLayout& L, const float* params, const floa
 hipError_t fused_wide_dev_fold(const GenLayout& L, const float* params, const DevFoldArgs& a, hipStream_t s);
 hipError_t fused_wide_fwd_bwd(const GenLayout& L, const GfUpdArgs& a, float* grads, hipStream_t s);   // the policy's kind is a.hp.dist_kind
 
+// ---- PPO_KERNEL_FUSED_MATRIX (kernels_fused_matrix.hip): the two families' 64-wide products on the f32 matrix cores, at every observation width the context
+// accepts (1 .. FUSED_WIDE_MAX_OBS: one to six chunks).  The six launchers above hand a layout with L.fused_matrix set to these, in front of the wide test and
+// argument for argument; nobody else calls them.  ppo_ctx_create sets the field only under the flag. ----
+hipError_t fused_matrix_gauss_act(const GenLayout& L, const float* params, const float* obs, const float* forced, int64_t n, int64_t seed, int64_t row_offset,
+                                  int64_t step_index, bool greedy, float* action, float* logprob, float* entropy, const GaussStepStores* st, hipStream_t s);
+hipError_t fused_matrix_cat_act(const GenLayout& L, int dist_kind, const float* params, const float* obs, const uint8_t* mask, const int64_t* forced, int64_t n,
+                                int64_t seed, int64_t row_offset, int64_t step_index, bool greedy, int64_t* action, float* logprob, float* entropy,
+                                const CatStepStores* st, hipStream_t s);
+hipError_t fused_matrix_values(const GenLayout& L, const float* params, const float* obs, int64_t n, float* value, hipStream_t s);
+hipError_t fused_matrix_dev_fold(const GenLayout& L, const float* params, const DevFoldArgs& a, hipStream_t s);
+hipError_t fused_matrix_fwd_bwd(const GenLayout& L, const GfUpdArgs& a, float* grads, hipStream_t s);   // the policy's kind is a.hp.dist_kind
+
 // ---- The device envs of the two fused families.  An env is a trait in ppo_internal.hpp (GaussEnv*: one real-valued action; CatEnv*: one head of integer
 // actions), one line of its family's dispatcher and one row of the table in kernels_gauss_fused.hip; everything the C-ABI layer knows about an env it reads
 // from the row.  The numbers of a row come from the trait. ----

@@ -1,7 +1,8 @@
 // ppo-libtorch_amd/csrc/gauss_fused_dev.hpp -- the device functions of the fused 2 x 64 family (PPO_KERNEL_GAUSS_FUSED / PPO_KERNEL_CAT_FUSED) that its two
 // kernel files share: kernels_gauss_fused.hip (W1 and the whole X image resident in LDS, obs_size <= GAUSS_FUSED_MAX_OBS) and kernels_fused_wide.hip
 // (PPO_KERNEL_FUSED_WIDE_OBS: layer 1 streamed in K-chunks).  The carve, the weight staging, the layers, the heads' and the loss lanes' arithmetic and the
-// backward's tile functions are written once, here; a kernel file adds its kernels and launchers.  Included by those two files only.
+// backward's tile functions are written once, here; a kernel file adds its kernels and launchers.  Included by those two files and by
+// kernels_fused_matrix.hip (PPO_KERNEL_FUSED_MATRIX: the same plan with the 64-wide products on the matrix cores).
 #pragma once
 #include <algorithm>
 
@@ -120,31 +121,34 @@ __device__ __forceinline__ void gf_hidden_layer(const float* __restrict__ W, con
     for (int i = 0; i < 16; i++) out[(16 * w + i) * GF_S + s] = tanh_fast(acc[i]);
 }
 
+// the output layer: H2 (post-tanh, complete behind the caller's barrier) -> OUT rows 0 .. out - 1; wave w owns units w, w + 4, ... (< out <= 32)
+__device__ __forceinline__ void gf_output_layer(const GfLds& m, int out, int s, int w) {
+    const int nu = (out - w + 3) >> 2;
+    float acc[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) acc[i] = m.b3[(4 * i + w) & 31];
+    for (int k = 0; k < 64; k += 4) {
+        const float x0 = m.h2[(k + 0) * GF_S + s], x1 = m.h2[(k + 1) * GF_S + s], x2 = m.h2[(k + 2) * GF_S + s], x3 = m.h2[(k + 3) * GF_S + s];
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            if (i < nu) {
+                const float4 wv = *reinterpret_cast<const float4*>(&m.w3[(4 * i + w) * 64 + k]);
+                acc[i] = __builtin_fmaf(wv.x, x0, acc[i]);
+                acc[i] = __builtin_fmaf(wv.y, x1, acc[i]);
+                acc[i] = __builtin_fmaf(wv.z, x2, acc[i]);
+                acc[i] = __builtin_fmaf(wv.w, x3, acc[i]);
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 8; i++) if (i < nu) m.o[(4 * i + w) * GF_S + s] = acc[i];
+}
+
 // layers 2 and 3 of the forward pass: H1 (post-tanh, complete behind the caller's barrier) -> H2 -> OUT rows 0 .. out - 1; a barrier behind each layer
 __device__ __forceinline__ void gf_forward_upper(const GfLds& m, int out, int s, int w) {
     gf_hidden_layer(m.w2, m.b2, m.h1, m.h2, 64, s, w);
     __syncthreads();
-    {   // output layer: wave w owns units w, w + 4, ... (< out <= 32)
-        const int nu = (out - w + 3) >> 2;
-        float acc[8];
-#pragma unroll
-        for (int i = 0; i < 8; i++) acc[i] = m.b3[(4 * i + w) & 31];
-        for (int k = 0; k < 64; k += 4) {
-            const float x0 = m.h2[(k + 0) * GF_S + s], x1 = m.h2[(k + 1) * GF_S + s], x2 = m.h2[(k + 2) * GF_S + s], x3 = m.h2[(k + 3) * GF_S + s];
-#pragma unroll
-            for (int i = 0; i < 8; i++) {
-                if (i < nu) {
-                    const float4 wv = *reinterpret_cast<const float4*>(&m.w3[(4 * i + w) * 64 + k]);
-                    acc[i] = __builtin_fmaf(wv.x, x0, acc[i]);
-                    acc[i] = __builtin_fmaf(wv.y, x1, acc[i]);
-                    acc[i] = __builtin_fmaf(wv.z, x2, acc[i]);
-                    acc[i] = __builtin_fmaf(wv.w, x3, acc[i]);
-                }
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 8; i++) if (i < nu) m.o[(4 * i + w) * GF_S + s] = acc[i];
-    }
+    gf_output_layer(m, out, s, w);
     __syncthreads();
 }
 
@@ -162,6 +166,32 @@ __device__ __forceinline__ void gf_forward_tile(const GfLds& m, int out, int tid
 __device__ __forceinline__ void gf_dense_rows(const GfLds& m, int64_t row0, int64_t n, int tid) {
     if (tid < 64) m.ridx[tid] = row0 + tid < n ? (int)(row0 + tid) : -1;
     __syncthreads();
+}
+
+// ---- layer 1 in chunks of GW_K observation columns (kernels_fused_wide.hip, kernels_fused_matrix.hip): the tile's X image one chunk at a time; a thread owns
+// 16 elements of a chunk (element tid + 256 j: column 64 c + (tid & 63) of sample (tid >> 6) + 4 j -- a wave reads 64 consecutive floats of a row) ----
+constexpr int GW_K = FUSED_WIDE_CHUNK;
+__device__ __forceinline__ int gw_chunks(int O) { return (O + GW_K - 1) / GW_K; }
+// chunk c of the tile's observations: rows ridx[s] of obs [., O]; zeros for a sample without a row (ridx < 0) and behind column O
+__device__ __forceinline__ void gw_fetch_x(const float* __restrict__ obs, int O, const int* ridx, int c, int tid, float (&r)[16]) {
+    const int k = GW_K * c + (tid & 63), s0 = tid >> 6;
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+        const int row = ridx[s0 + 4 * j];
+        r[j] = (k < O && row >= 0) ? obs[(int64_t)row * O + k] : 0.0f;
+    }
+}
+// ... as the [k][sample] image of the chunk
+__device__ __forceinline__ void gw_store_x(float* __restrict__ x, int tid, const float (&r)[16]) {
+    const int k = tid & 63, s0 = tid >> 6;
+#pragma unroll
+    for (int j = 0; j < 16; j++) x[k * GF_S + s0 + 4 * j] = r[j];
+}
+
+// columns of chunk c that take part in a product: 64, or what is left of O rounded up to 4 (the padding columns hold zeros on both sides)
+__device__ __forceinline__ int gw_chunk_cols(int O, int c) {
+    const int left = gf_pad4(O - GW_K * c);
+    return left < GW_K ? left : GW_K;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -574,35 +604,11 @@ __device__ __forceinline__ void gf_backward_upper(const GfLds& m, int out, int o
     __syncthreads();
 }
 
-// The workgroup's partial slab above W1, in the net's own parameter order: b1 W2 b2 W3 b3 (actor: then log_std, which sits behind it in the flat vector),
-// and its loss partials.  The caller stores dW1 at slab + 0.
+// log_std's gradient (a Gaussian actor: behind the net's layers in the slab) and the workgroup's loss partials: wave 0, the loss lanes' state
 template <int DIST>
-__device__ __forceinline__ void gf_store_upper(const GfUpdArgs& a, float* slab, int net, int b, int out, int s, int w, int ub, int kb, const float* gW2,
-                                               const float* gW3, const float* gb1, const float* gb2, const float* gb3, GfLossState& ls) {
+__device__ __forceinline__ void gf_store_loss(const GfUpdArgs& a, float* slab, int net, int b, int s, int w, GfLossState& ls) {
     constexpr bool GAUSS = DIST == PPO_DIST_GAUSSIAN;
     const int base = a.sh.off[net][0], nb = a.nb, D = a.sh.D;
-    {
-        float* dW2 = slab + (a.sh.off[net][2] - base);
-        float* dW3 = slab + (a.sh.off[net][4] - base);
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const int u = 4 * ub + i, k = 4 * kb + j;
-                dW2[u * 64 + k] = gW2[i * 4 + j];
-                if (u < out) dW3[u * 64 + k] = gW3[i * 4 + j];
-            }
-        }
-        if (kb == 0) {
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const int u = 4 * ub + i;
-                slab[a.sh.off[net][1] - base + u] = gb1[i];
-                slab[a.sh.off[net][3] - base + u] = gb2[i];
-                if (u < out) slab[a.sh.off[net][5] - base + u] = gb3[i];
-            }
-        }
-    }
     if (w == 0) {
         if (GAUSS && net == 1) {
 #pragma unroll
@@ -625,6 +631,37 @@ __device__ __forceinline__ void gf_store_upper(const GfUpdArgs& a, float* slab, 
             for (int row = b; row < GEN_LOSS_BLOCKS; row += nb) a.loss_part[row * 8 + s] = row == b ? v : 0.0;
         }
     }
+}
+
+// The workgroup's partial slab above W1, in the net's own parameter order: b1 W2 b2 W3 b3 (actor: then log_std, which sits behind it in the flat vector),
+// and its loss partials.  The caller stores dW1 at slab + 0.
+template <int DIST>
+__device__ __forceinline__ void gf_store_upper(const GfUpdArgs& a, float* slab, int net, int b, int out, int s, int w, int ub, int kb, const float* gW2,
+                                               const float* gW3, const float* gb1, const float* gb2, const float* gb3, GfLossState& ls) {
+    const int base = a.sh.off[net][0];
+    {
+        float* dW2 = slab + (a.sh.off[net][2] - base);
+        float* dW3 = slab + (a.sh.off[net][4] - base);
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int u = 4 * ub + i, k = 4 * kb + j;
+                dW2[u * 64 + k] = gW2[i * 4 + j];
+                if (u < out) dW3[u * 64 + k] = gW3[i * 4 + j];
+            }
+        }
+        if (kb == 0) {
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const int u = 4 * ub + i;
+                slab[a.sh.off[net][1] - base + u] = gb1[i];
+                slab[a.sh.off[net][3] - base + u] = gb2[i];
+                if (u < out) slab[a.sh.off[net][5] - base + u] = gb3[i];
+            }
+        }
+    }
+    gf_store_loss<DIST>(a, slab, net, b, s, w, ls);
 }
 
 // what an update launcher fills of the kernel's arguments from its own (gauss_fused_fwd_bwd's / cat_fused_fwd_bwd's, either kernel file)

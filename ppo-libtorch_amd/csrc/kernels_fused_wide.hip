@@ -31,7 +31,6 @@
 
 namespace {
 
-constexpr int GW_K = FUSED_WIDE_CHUNK;
 static_assert(GW_K == 64 && GF_THREADS == 256, "a thread owns elements tid + 256 j, j < 16, of a 64 x 64 chunk; tid & 63 is its column");
 
 struct GwLds {
@@ -75,28 +74,6 @@ __device__ __forceinline__ void gw_store_w(float* __restrict__ w1, int tid, cons
 #pragma unroll
     for (int j = 0; j < 16; j++) w1[(u0 + 4 * j) * GW_K + k] = r[j];
 }
-// chunk c of the tile's observations: rows ridx[s] of obs [., O]; zeros for a sample without a row (ridx < 0) and behind column O
-__device__ __forceinline__ void gw_fetch_x(const float* __restrict__ obs, int O, const int* ridx, int c, int tid, float (&r)[16]) {
-    const int k = GW_K * c + (tid & 63), s0 = tid >> 6;
-#pragma unroll
-    for (int j = 0; j < 16; j++) {
-        const int row = ridx[s0 + 4 * j];
-        r[j] = (k < O && row >= 0) ? obs[(int64_t)row * O + k] : 0.0f;
-    }
-}
-// ... as the [k][sample] image of the chunk
-__device__ __forceinline__ void gw_store_x(float* __restrict__ x, int tid, const float (&r)[16]) {
-    const int k = tid & 63, s0 = tid >> 6;
-#pragma unroll
-    for (int j = 0; j < 16; j++) x[k * GF_S + s0 + 4 * j] = r[j];
-}
-
-// columns of chunk c that take part in a product: 64, or what is left of O rounded up to 4 (the padding columns hold zeros on both sides)
-__device__ __forceinline__ int gw_chunk_cols(int O, int c) {
-    const int left = gf_pad4(O - GW_K * c);
-    return left < GW_K ? left : GW_K;
-}
-
 // one chunk of layer 1 onto the lane's accumulators: gf_hidden_layer's loop between the bias and the tanh
 __device__ __forceinline__ void gw_l1_chunk(const float* __restrict__ W, const float* __restrict__ in, int K, int s, int w, float (&acc)[16]) {
     for (int k = 0; k < K; k += 4) {
@@ -147,8 +124,6 @@ __device__ __forceinline__ void gw_forward_tile(const GwLds& g, const GfShape& s
     __syncthreads();
     gf_forward_upper(m, out, s, w);
 }
-
-__device__ __forceinline__ int gw_chunks(int O) { return (O + GW_K - 1) / GW_K; }
 
 // ---------------------------------------------------------------------------------------------------------
 // The act kernels: gauss_act_kernel's / cat_act_kernel's plan (wave 0 the heads, waves 1 .. 3 the step's stores: gauss_act_rows / cat_act_rows) behind the

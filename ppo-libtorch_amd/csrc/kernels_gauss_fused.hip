@@ -1144,6 +1144,7 @@ hipError_t gauss_fused_slab_reduce(const GenLayout& L, const float* slab, int sl
 hipError_t gauss_fused_act(const GenLayout& L, const float* params, const float* obs, const float* forced, int64_t n, int64_t seed, int64_t row_offset,
                            int64_t step_index, bool greedy, float* action, float* logprob, float* entropy, const GaussStepStores* st, hipStream_t s) {
     if (n <= 0) return hipSuccess;
+    if (L.fused_matrix) return fused_matrix_gauss_act(L, params, obs, forced, n, seed, row_offset, step_index, greedy, action, logprob, entropy, st, s);
     if (L.obs > GAUSS_FUSED_MAX_OBS) return fused_wide_gauss_act(L, params, obs, forced, n, seed, row_offset, step_index, greedy, action, logprob, entropy, st, s);
     const GfShape sh = gf_shape(L);
     const int bytes = gf_lds_floats(gf_pad4(L.obs), gf_pad4(L.gauss)) * 4;
@@ -1166,6 +1167,7 @@ hipError_t gauss_fused_act(const GenLayout& L, const float* params, const float*
 
 hipError_t gauss_fused_values(const GenLayout& L, const float* params, const float* obs, int64_t n, float* value, hipStream_t s) {
     if (n <= 0) return hipSuccess;
+    if (L.fused_matrix) return fused_matrix_values(L, params, obs, n, value, s);
     if (L.obs > GAUSS_FUSED_MAX_OBS) return fused_wide_values(L, params, obs, n, value, s);
     const GfShape sh = gf_shape(L);
     const int bytes = gf_lds_floats(gf_pad4(L.obs), 4) * 4;
@@ -1179,6 +1181,7 @@ hipError_t gauss_fused_values(const GenLayout& L, const float* params, const flo
 
 hipError_t gauss_fused_dev_fold(const GenLayout& L, const float* params, const DevFoldArgs& a, hipStream_t s) {
     if (a.N <= 0) return hipSuccess;
+    if (L.fused_matrix) return fused_matrix_dev_fold(L, params, a, s);
     if (L.obs > GAUSS_FUSED_MAX_OBS) return fused_wide_dev_fold(L, params, a, s);
     const GfShape sh = gf_shape(L);
     // the row list and the waves' totals are part of the dynamic allocation: the attribute is decided on every byte of LDS the kernel uses
@@ -1196,6 +1199,7 @@ hipError_t gauss_fused_fwd_bwd(const GenLayout& L, const LossParams& hp, const f
                                const AdvStat* adv_stat, float* slab, double* loss_part, float* grads, hipStream_t s) {
     if (M < 1 || M >= (1ll << 31) - 64 || !slab || !loss_part) return hipErrorInvalidValue;
     const GfUpdArgs a = gf_upd_args(L, hp, params, obs, actions, nullptr, oldlp, adv, ret, oldv, idx, M, inv_global_M, global_M, adv_stat, slab, loss_part);
+    if (L.fused_matrix) return fused_matrix_fwd_bwd(L, a, grads, s);
     if (L.obs > GAUSS_FUSED_MAX_OBS) return fused_wide_fwd_bwd(L, a, grads, s);
     const int bytes = gf_lds_floats(gf_pad4(L.obs), gf_pad4(L.gauss)) * 4;
     static std::atomic<unsigned long long> done{ 0 };
@@ -1224,6 +1228,7 @@ hipError_t cat_fused_act(const GenLayout& L, int dist_kind, const float* params,
                          int64_t row_offset, int64_t step_index, bool greedy, int64_t* action, float* logprob, float* entropy, const CatStepStores* st, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     if (L.gauss || (dist_kind != PPO_DIST_CATEGORICAL && dist_kind != PPO_DIST_MASKED)) return hipErrorInvalidValue;
+    if (L.fused_matrix) return fused_matrix_cat_act(L, dist_kind, params, obs, mask, forced, n, seed, row_offset, step_index, greedy, action, logprob, entropy, st, s);
     if (L.obs > GAUSS_FUSED_MAX_OBS)
         return fused_wide_cat_act(L, dist_kind, params, obs, mask, forced, n, seed, row_offset, step_index, greedy, action, logprob, entropy, st, s);
     const GfShape sh = gf_shape(L);
@@ -1246,6 +1251,7 @@ hipError_t cat_fused_fwd_bwd(const GenLayout& L, const LossParams& hp, const flo
     if (hp.dist_kind != PPO_DIST_CATEGORICAL && hp.dist_kind != PPO_DIST_MASKED) return hipErrorInvalidValue;
     const GfUpdArgs a = gf_upd_args(L, hp, params, obs, reinterpret_cast<const float*>(actions), hp.dist_kind == PPO_DIST_MASKED ? masks : nullptr, oldlp, adv, ret, oldv,
                                     idx, M, inv_global_M, global_M, adv_stat, slab, loss_part);
+    if (L.fused_matrix) return fused_matrix_fwd_bwd(L, a, grads, s);
     if (L.obs > GAUSS_FUSED_MAX_OBS) return fused_wide_fwd_bwd(L, a, grads, s);
     const int bytes = gf_lds_floats(gf_pad4(L.obs), gf_pad4(L.act)) * 4;
     static std::atomic<unsigned long long> done_c{ 0 }, done_m{ 0 };
