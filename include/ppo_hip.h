@@ -513,6 +513,24 @@ enum { PPO_KERNEL_ROLLOUT_VECTOR = 1, PPO_KERNEL_UPDATE_VECTOR = 2, PPO_KERNEL_U
  * flags, and beside PPO_KERNEL_ENV_GENERIC.  No symbol and no buffer id of its own.  Sharding (ppo_comm_init*) of a flagged context is neither claimed nor
  * tested. */
 #define PPO_KERNEL_FUSED_MATRIX (1 << 16)
+/* PPO_KERNEL_ENV_MATRIX (131072; bits 11, 12 and 14 stay unassigned and are refused as unknown, as is bit 18): PPO_KERNEL_FUSED_MATRIX's forward for the seven
+ * fused device envs (PPO_ENV_PENDULUM, PPO_ENV_MOUNTAINCAR_CONTINUOUS, PPO_ENV_ACROBOT, PPO_ENV_TAXI, PPO_ENV_FROZENLAKE, PPO_ENV_FROZENLAKE8X8,
+ * PPO_ENV_BLACKJACK).  Valid only on one of them, in the form it accepts without the flag and next to its family flag; PPO_KERNEL_ENV_REWARD_NORM may stand
+ * beside it.  A flagged context runs its one-launch rollout and ppo_evaluate on kernels_env_matrix.hip's kernels: the same workgroup (4 waves, one 64-env tile
+ * for all T steps), the same heads, draws, env steps and stores, but layers 1 and 2 on the f32 matrix cores (v_mfma_f32_16x16x4_f32) with the wave's slices of
+ * W1 and W2 fetched once and held in registers for the whole launch; LDS holds no W1 image (71 872 bytes, 73 984 on PPO_ENV_TAXI: two workgroups per CU on
+ * every env).  Every other launch that runs the network -- the rollout's critic launches, ppo_get_value, ppo_policy_act*, the update -- is
+ * PPO_KERNEL_FUSED_MATRIX's kernel, and all of them end in one forward function: an observation gets the same mean / logits and the same value from
+ * ppo_rollout*, ppo_policy_act*, ppo_get_value, ppo_evaluate and the update, bit for bit, so a flagged rollout equals a stepwise loop of ppo_policy_act* +
+ * ppo_env_step* on the same context.  Against the unflagged context the bits differ (the summation order is the instruction's), within the family's f32 bars.
+ * ppo_gauss_fused_launches counts as before.  NOT built under the flag: the time-limit bootstrap -- ppo_env_truncation_bootstrap and ppo_env_truncations
+ * return PPO_ERR_UNSUPPORTED with a message naming the flag (the fold's value must be ppo_get_value's bit for bit, and the fold kernels have no matrix form
+ * yet), which is why PPO_KERNEL_ENV_CUT_STATE beside it is refused at creation; ppo_evaluate on PPO_ENV_PENDULUM stays refused as without the flag.  Opt-in,
+ * never implied: without the flag every context is what it was, refusals included, word for word.  ppo_ctx_create returns PPO_ERR_UNSUPPORTED with a message
+ * naming the flag and the limit on env_kind = PPO_ENV_HOST (the flag there is PPO_KERNEL_FUSED_MATRIX), PPO_ENV_CARTPOLE, PPO_ENV_MOUNTAINCAR and
+ * PPO_ENV_SYNTHETIC, without the env's family flag, and beside PPO_KERNEL_ENV_GENERIC, PPO_KERNEL_FUSED_MATRIX, PPO_KERNEL_FUSED_WIDE_OBS or
+ * PPO_KERNEL_ENV_CUT_STATE.  No symbol and no buffer id of its own.  Sharding (ppo_comm_init*) of a flagged context is neither claimed nor tested. */
+#define PPO_KERNEL_ENV_MATRIX (1 << 17)
 
 /* Scalars the reference prints per update (PPO_Discrete.cpp:700-774) plus per-step diagnostics. */
 typedef struct ppo_stats {

@@ -44,6 +44,9 @@ KERNEL_FUSED_WIDE_OBS = 1 << 15
 # next to KERNEL_GAUSS_FUSED or KERNEL_CAT_FUSED on an ENV_HOST context, with or without KERNEL_FUSED_WIDE_OBS: the 64-wide layer products on the f32 matrix
 # cores (include/ppo_hip.h PPO_KERNEL_FUSED_MATRIX)
 KERNEL_FUSED_MATRIX = 1 << 16
+# the fused device envs (ENV_PENDULUM .. ENV_BLACKJACK), next to the env's family flag: the one-launch rollout, the evaluation and every other launch that
+# runs the network use the f32 matrix-core forward; env_truncation_bootstrap is refused there (include/ppo_hip.h PPO_KERNEL_ENV_MATRIX)
+KERNEL_ENV_MATRIX = 1 << 17
 ABI_VERSION = 5
 COMM_ID_BYTES = 128
 COMM_HANDLE_BYTES = 64

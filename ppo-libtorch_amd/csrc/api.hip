@@ -653,7 +653,33 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
     if (cfg->compute_dtype != PPO_DTYPE_F32 && cfg->compute_dtype != PPO_DTYPE_BF16) return fail(nullptr, PPO_ERR_INVALID, "unknown compute_dtype %d", cfg->compute_dtype);
     constexpr int32_t known_flags = PPO_KERNEL_ROLLOUT_VECTOR | PPO_KERNEL_UPDATE_VECTOR | PPO_KERNEL_UPDATE_ONE_WAVE | PPO_KERNEL_COMM_SELFTEST | PPO_KERNEL_GENERIC_CLASSIC |
                                   PPO_KERNEL_GENERIC_SPLIT_HEAD | PPO_KERNEL_GAUSS_FUSED | PPO_KERNEL_SEPARATE_LAUNCHES | PPO_KERNEL_CAT_FUSED | PPO_KERNEL_ENV_GENERIC |
-                                  PPO_KERNEL_ENV_CUT_STATE | PPO_KERNEL_ENV_REWARD_NORM | PPO_KERNEL_FUSED_WIDE_OBS | PPO_KERNEL_FUSED_MATRIX;
+                                  PPO_KERNEL_ENV_CUT_STATE | PPO_KERNEL_ENV_REWARD_NORM | PPO_KERNEL_FUSED_WIDE_OBS | PPO_KERNEL_FUSED_MATRIX | PPO_KERNEL_ENV_MATRIX;
+    // PPO_KERNEL_ENV_MATRIX: a device env of the fused 2 x 64 families next to that env's own family flag (with or without PPO_KERNEL_ENV_REWARD_NORM), or a
+    // refusal that names the flag and the limit.  In front of every other flag's block, so that the flag beside one of them is answered here.  The env's own
+    // block below then checks the policy's kind, the head, the network, the dtype and max_episode_steps in its own words
+    const bool env_matrix = (cfg->kernel_flags & PPO_KERNEL_ENV_MATRIX) != 0;
+    if (env_matrix) {
+        if (cfg->kernel_flags & ~known_flags) return fail(nullptr, PPO_ERR_INVALID, "unknown bits in kernel_flags 0x%x", cfg->kernel_flags);
+        if (host_env)
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_ENV_MATRIX serves the device envs of the fused 2 x 64 families only (%s; %s): it moves their "
+                        "one-launch rollouts and evaluations to the matrix cores; on caller-stepped environments (env_kind = PPO_ENV_HOST) the flag is "
+                        "PPO_KERNEL_FUSED_MATRIX", fused_env_names(FUSED_GAUSS), fused_env_names(FUSED_CAT));
+        if (!env)
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_ENV_MATRIX serves the device envs of the fused 2 x 64 families only (%s; %s): it moves their "
+                        "one-launch rollouts and evaluations to the matrix cores; CartPole, MountainCar and PPO_ENV_SYNTHETIC run none of those kernels; got "
+                        "env_kind %d", fused_env_names(FUSED_GAUSS), fused_env_names(FUSED_CAT), cfg->env_kind);
+        if (cfg->kernel_flags & (PPO_KERNEL_ENV_GENERIC | PPO_KERNEL_FUSED_MATRIX | PPO_KERNEL_FUSED_WIDE_OBS))
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_ENV_MATRIX excludes PPO_KERNEL_ENV_GENERIC, PPO_KERNEL_FUSED_MATRIX and PPO_KERNEL_FUSED_WIDE_OBS: "
+                        "the first names another engine, the other two serve env_kind = PPO_ENV_HOST only, and a device env's matrix kernels are named by this "
+                        "flag alone");
+        if (cfg->kernel_flags & PPO_KERNEL_ENV_CUT_STATE)
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_ENV_MATRIX excludes PPO_KERNEL_ENV_CUT_STATE: the time-limit fold's value must be ppo_get_value's bit "
+                        "for bit, and the fold kernels have no matrix form yet; the time-limit bootstrap is not built under this flag");
+        if (!(cfg->kernel_flags & (env->family == FUSED_GAUSS ? PPO_KERNEL_GAUSS_FUSED : PPO_KERNEL_CAT_FUSED)))
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_ENV_MATRIX needs %s beside it on env_kind = %s: it moves that family's one-launch rollout to the "
+                        "matrix cores and names no engine of its own (the family flag is never implied)",
+                        env->family == FUSED_GAUSS ? "PPO_KERNEL_GAUSS_FUSED" : "PPO_KERNEL_CAT_FUSED", env->name);
+    }
     // PPO_KERNEL_FUSED_MATRIX: a PPO_ENV_HOST context next to exactly one of the two family flags (with or without PPO_KERNEL_FUSED_WIDE_OBS), or a refusal that
     // names the flag and the limit.  In front of the other flags' blocks, so that the flag beside one of them is answered here.  The family's own blocks below
     // then check hidden, n_hidden, dtype, the policy's kind, the output width and the observation width in their own words
@@ -838,7 +864,8 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
     if (generic) {
         c->gen = new GenericCtx();
         c->gen->L = make_gen_layout(cfg->obs_size, cfg->hidden, cfg->n_hidden, cfg->n_heads, cfg->head_dims, gauss);
-        c->gen->L.fused_matrix = fused_matrix;
+        c->gen->L.fused_matrix = fused_matrix || env_matrix;   // a flagged device env's act, critic and update launches are kernels_fused_matrix.hip's
+        c->gen->L.env_matrix = env_matrix;
         // the shared code sizes the flat parameter / gradient / moment buffers from L.P; the 2 x 64 offsets in L are not used
         c->L.P = c->gen->L.P;
         c->L.n_tensors = c->gen->L.n_tensors;
@@ -3311,6 +3338,10 @@ static ppo_status envt_state(ppo_ctx* c, const char* what) {
     if (c->host_env)
         return fail(c, PPO_ERR_UNSUPPORTED, "%s: this context's environments are the caller's (PPO_ENV_HOST), and only the caller holds the observation an episode "
                                             "ended on: pass it with ppo_host_observe_truncated (ppo_dev_observe for device arrays)", what);
+    if (c->gen && c->gen->L.env_matrix)
+        return fail(c, PPO_ERR_UNSUPPORTED, "%s: this context runs its network on the matrix cores (PPO_KERNEL_ENV_MATRIX), and the fold's value must be "
+                                            "ppo_get_value's bit for bit: the fold kernels have no matrix form yet, so the time-limit bootstrap is not built "
+                                            "under the flag", what);
     if (c->env)   // its observation holds its state and the fold runs on the fused critic (fused_env_fold_truncations), or the row says why not
         return (c->env->folds || c->cut_state) ? PPO_OK
                              : fail(c, PPO_ERR_UNSUPPORTED, "%s: the fold rebuilds the final observation of a cut-off episode from PPO_BUF_OBS, and a %s: not built "

@@ -153,6 +153,14 @@ struct FusedEvalArgs {
 };
 hipError_t fused_env_evaluate(int env_kind, int dist_kind, const GenLayout& L, const FusedEvalArgs& e, hipStream_t s);
 
+// ---- PPO_KERNEL_ENV_MATRIX (kernels_env_matrix.hip): the two launches above with the policy's 64-wide products on the f32 matrix cores, the wave's W1 and W2
+// slices resident in registers for all T steps (gm_gauss_rollout_kernel / gm_cat_rollout_kernel, gm_gauss_eval_kernel / gm_cat_eval_kernel).  The two launchers
+// above hand a layout with L.env_matrix set to these, argument for argument; nobody else calls them.  ppo_ctx_create sets the field only under the flag, and
+// L.fused_matrix with it: the act, critic and update launchers of such a context run kernels_fused_matrix.hip's kernels, whose forward is the same function.
+// r.cut is null there (PPO_KERNEL_ENV_CUT_STATE beside the flag is refused). ----
+hipError_t env_matrix_rollout(int env_kind, int dist_kind, const GenLayout& L, const FusedRolloutArgs& r, hipStream_t s);
+hipError_t env_matrix_evaluate(int env_kind, int dist_kind, const GenLayout& L, const FusedEvalArgs& e, hipStream_t s);
+
 // The envs' stand-alone kernels, one thread per env, on the rollout kernel's device functions.  The step and the transition take the family's action type, as
 // the C ABI does (ppo_env_step / ppo_env_step_f32): each serves the envs of its family only.
 hipError_t launch_fused_env_reset(int env_kind, int N, int64_t seed, int64_t env_offset, float* env_state, int32_t* ep_len, float* ep_rew, int32_t* reset_count,

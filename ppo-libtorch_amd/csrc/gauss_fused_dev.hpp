@@ -2,7 +2,8 @@
 // kernel files share: kernels_gauss_fused.hip (W1 and the whole X image resident in LDS, obs_size <= GAUSS_FUSED_MAX_OBS) and kernels_fused_wide.hip
 // (PPO_KERNEL_FUSED_WIDE_OBS: layer 1 streamed in K-chunks).  The carve, the weight staging, the layers, the heads' and the loss lanes' arithmetic and the
 // backward's tile functions are written once, here; a kernel file adds its kernels and launchers.  Included by those two files and by
-// kernels_fused_matrix.hip (PPO_KERNEL_FUSED_MATRIX: the same plan with the 64-wide products on the matrix cores).
+// kernels_fused_matrix.hip (PPO_KERNEL_FUSED_MATRIX: the same plan with the 64-wide products on the matrix cores) and, through fused_matrix_dev.hpp, by
+// kernels_env_matrix.hip (PPO_KERNEL_ENV_MATRIX: the device envs' one-launch rollouts behind that forward).
 #pragma once
 #include <algorithm>
 
@@ -290,6 +291,157 @@ __device__ __forceinline__ void cat_act_rows(const GfLds& m, const GfShape& sh, 
         for (int64_t i = tid - 64; i < rows * A; i += GF_THREADS - 64) st.mask_t[row0 * A + i] = mask ? mask[row0 * A + i] : (uint8_t)1;
         if (tid < 128 && r < n) st.dones_t[r] = (float)st.done_prev[r];
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// The device envs' one-launch rollouts and evaluations (kernels_gauss_fused.hip; kernels_env_matrix.hip under PPO_KERNEL_ENV_MATRIX): the kernels' arguments,
+// wave 0's per-lane functions, the dispatchers and what the launchers of either file fill.
+// ---------------------------------------------------------------------------------------------------------
+struct GfRolloutArgs {
+    GfShape sh;
+    const float* params;
+    int N, T, max_episode_steps;
+    int64_t seed, env_offset, step_base;
+    float* env_state;        // [2, N]
+    int32_t* ep_len;
+    float* ep_rew;
+    int32_t* reset_count;
+    float* obs;              // [T, N, Env::OBS]
+    float* actions;          // [T, N, 1]
+    float* logprobs;
+    float* rewards;
+    float* dones;
+    int32_t* fin_len;
+    float* fin_rew;
+    float* next_obs;         // [N, Env::OBS]
+    int32_t* next_done;
+    const float* forced;     // [T, N, 1] or null
+    float* cut;              // KEEP: the cut-off record [Env::STATE + 1, T * N]; null otherwise
+};
+
+struct GfEvalArgs {
+    GfShape sh;
+    const float* params;
+    int64_t n_episodes, seed;
+    int max_episode_steps, greedy;
+    float* ep_return;
+    int32_t* ep_length;
+    int32_t* ep_trunc;
+};
+
+struct CfRolloutArgs {
+    GfShape sh;
+    const float* params;
+    int N, T, max_episode_steps;
+    int64_t seed, env_offset, step_base;
+    float* env_state;        // [Env::STATE, N]
+    int32_t* ep_len;
+    float* ep_rew;
+    int32_t* reset_count;
+    float* obs;              // [T, N, Env::OBS]
+    uint8_t* masks;          // [T, N, Env::ACTIONS]
+    int32_t* actions;        // [T, N, 1]
+    float* logprobs;
+    float* rewards;
+    float* dones;
+    int32_t* fin_len;
+    float* fin_rew;
+    float* next_obs;         // [N, Env::OBS]
+    int32_t* next_done;
+    const int64_t* forced;   // [T, N, 1] or null
+    float* cut;              // KEEP: the cut-off record [Env::STATE + 1, T * N]; null otherwise
+};
+
+// wave 0's lane behind the forward: the row's head on the lane's columns (z: OUT, log-probs in place; p: H1), the action (GREEDY: the first-index argmax of
+// the probabilities; forced; or the draw with uniform word `ws`) and its log-prob -- cat_act_kernel<DIST>'s expressions for one head.  PPO_DIST_MASKED:
+// bit k of `allowed` is the row's mask byte k (the lane formed it from its env's state; a masked-out logit becomes -1e8f, its probability 0)
+template <int DIST, bool GREEDY>
+__device__ __forceinline__ int cat_lane_head(const GfLds& m, int lane, int Ah, uint32_t allowed, bool has_forced, int forced, uint32_t ws, float& lp) {
+    float* z = m.o + lane;
+    float* p = m.h1 + lane;
+    if constexpr (DIST == PPO_DIST_MASKED) {
+        uint8_t mrow[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) mrow[k] = (uint8_t)((allowed >> k) & 1u);
+        (void)categorical_head<PPO_DIST_MASKED, GF_S>(z, p, mrow, Ah);
+    } else {
+        (void)categorical_head<PPO_DIST_CATEGORICAL, GF_S>(z, p, nullptr, Ah);
+    }
+    int a;
+    if constexpr (GREEDY) {
+        a = 0;
+        for (int k = 1; k < Ah; k++) if (p[k * GF_S] > p[a * GF_S]) a = k;
+    } else if (has_forced) {
+        a = forced;
+    } else {
+        a = sample_head<GF_S>(p, Ah, (float)(ws >> 8) * 0x1p-24f);
+    }
+    lp = 0.0f;
+    for (int k = 0; k < Ah; k++) if (k == a) lp = z[k * GF_S];
+    return a;
+}
+// a caller's i64 action as the env's int: saturated, not truncated, so that an env that clamps its action clamps the caller's number
+__device__ __forceinline__ int cat_action_int(int64_t a) { return a < -2147483647ll ? -2147483647 : (a > 2147483647ll ? 2147483647 : (int)a); }
+__device__ __forceinline__ uint32_t cat_draw_word(int64_t seed, int64_t row, int64_t step_index) {
+    const uint4 w = philox4x32_10((uint32_t)seed, (uint32_t)((uint64_t)seed >> 32), (uint32_t)row, (uint32_t)(step_index >> 2), 0u, 0u);
+    return (step_index & 3) == 0 ? w.x : ((step_index & 3) == 1 ? w.y : ((step_index & 3) == 2 ? w.z : w.w));
+}
+
+// env_kind -> trait: f is called with a value of the env's trait type; an env without one gives hipErrorInvalidValue
+template <class F>
+static hipError_t gauss_env_dispatch(int env_kind, F f) {
+    if (env_kind == PPO_ENV_PENDULUM) return f(GaussEnvPendulum{});
+    if (env_kind == PPO_ENV_MOUNTAINCAR_CONTINUOUS) return f(GaussEnvMountainCarContinuous{});
+    return hipErrorInvalidValue;
+}
+template <class F>
+static hipError_t cat_env_dispatch(int env_kind, F f) {
+    if (env_kind == PPO_ENV_ACROBOT) return f(CatEnvAcrobot{});
+    if (env_kind == PPO_ENV_TAXI) return f(CatEnvTaxi{});
+    if (env_kind == PPO_ENV_FROZENLAKE) return f(CatEnvFrozenLake<4>{});
+    if (env_kind == PPO_ENV_FROZENLAKE8X8) return f(CatEnvFrozenLake<8>{});
+    if (env_kind == PPO_ENV_BLACKJACK) return f(CatEnvBlackjack{});
+    return hipErrorInvalidValue;
+}
+// the family's dispatcher: fg is called with a GaussEnv* trait, fc with a CatEnv* one
+template <class FG, class FC>
+static hipError_t fused_env_dispatch(int env_kind, FG fg, FC fc) {
+    const FusedEnvInfo* e = fused_env_info(env_kind);
+    if (!e) return hipErrorInvalidValue;
+    return e->family == FUSED_GAUSS ? gauss_env_dispatch(env_kind, fg) : cat_env_dispatch(env_kind, fc);
+}
+
+template <class Env>
+static bool gauss_env_shape_ok(const GenLayout& L) { return L.obs == Env::OBS && L.gauss == 1; }
+template <class Env>
+static bool cat_env_shape_ok(const GenLayout& L) { return L.obs == Env::OBS && L.gauss == 0 && L.n_heads == 1 && L.act == Env::ACTIONS; }
+// a masked policy runs on an env that forms a mask, and on no other (ppo_ctx_create)
+template <class Env>
+static bool cat_env_dist_ok(int dist_kind) { return dist_kind == PPO_DIST_CATEGORICAL || (dist_kind == PPO_DIST_MASKED && Env::HAS_MASK); }
+
+// the kernels' argument structs from the launchers' (GfRolloutArgs / CfRolloutArgs: the same fields, the family's action types)
+template <class KernelArgs>
+static KernelArgs rollout_kernel_args(const GenLayout& L, const FusedRolloutArgs& r) {
+    KernelArgs a{};
+    a.sh = gf_shape(L);
+    a.params = r.params;
+    a.N = r.N; a.T = r.T; a.max_episode_steps = r.max_episode_steps;
+    a.seed = r.seed; a.env_offset = r.env_offset; a.step_base = r.step_base;
+    a.env_state = r.env_state; a.ep_len = r.ep_len; a.ep_rew = r.ep_rew; a.reset_count = r.reset_count;
+    a.obs = r.obs; a.actions = static_cast<decltype(a.actions)>(r.actions); a.logprobs = r.logprobs; a.rewards = r.rewards; a.dones = r.dones;
+    a.fin_len = r.fin_len; a.fin_rew = r.fin_rew;
+    a.next_obs = r.next_obs; a.next_done = r.next_done; a.forced = static_cast<decltype(a.forced)>(r.forced);
+    a.cut = r.cut;
+    return a;
+}
+static GfEvalArgs eval_kernel_args(const GenLayout& L, const FusedEvalArgs& e) {
+    GfEvalArgs a{};
+    a.sh = gf_shape(L);
+    a.params = e.params;
+    a.n_episodes = e.n_episodes; a.seed = e.seed;
+    a.max_episode_steps = e.max_episode_steps; a.greedy = e.greedy != 0;
+    a.ep_return = e.ep_return; a.ep_length = e.ep_length; a.ep_trunc = e.ep_trunc;
+    return a;
 }
 
 // ---------------------------------------------------------------------------------------------------------

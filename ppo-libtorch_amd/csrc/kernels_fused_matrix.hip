@@ -37,66 +37,16 @@
 //   = 89 280 bytes (the fold adds its list, 1 056).  One workgroup per CU.  The size does not depend on obs_size.
 // Resources (hipcc -O3, gfx950, -Rpass-analysis=kernel-resource-usage; __launch_bounds__(256): one wave per SIMD, 512 registers; scratch 0 bytes/lane in every
 // kernel of this file; LDS is all dynamic, the sizes above):
-//   gm_fwd_bwd_kernel<GAUSSIAN, 6>: 256 VGPRs + 201 AGPRs, LDS 104 064 bytes at D = 32 (D = 17: 97 728), scratch 0
-//   gm_fwd_bwd_kernel<MASKED, 6>:   256 VGPRs + 247 AGPRs, scratch 0; <CATEGORICAL, 6>: 256 + 207, scratch 0
+//   gm_fwd_bwd_kernel<GAUSSIAN, 6>: 256 VGPRs + 205 AGPRs, LDS 104 064 bytes at D = 32 (D = 17: 97 728), scratch 0
+//   gm_fwd_bwd_kernel<MASKED, 6>:   256 VGPRs + 250 AGPRs, scratch 0; <CATEGORICAL, 6>: 256 + 209, scratch 0
 //   gm_fwd_bwd_kernel<GAUSSIAN, 1>: 222 VGPRs + 48 AGPRs, scratch 0
-//   gm_gauss_act_kernel / gm_cat_act_kernel: 128 .. 132 VGPRs + 16 AGPRs; gm_values_kernel: 128 + 16; gm_dev_fold_kernel: 132 + 16; scratch 0
+//   gm_gauss_act_kernel / gm_cat_act_kernel: 128 .. 132 VGPRs + 28 AGPRs; gm_values_kernel: 114 + 28; gm_dev_fold_kernel: 116 + 28; scratch 0
 //   "Must not spill" is met in the sense that nothing goes to memory.  Where the 256 architectural VGPRs run out the compiler parks values in AGPRs (its
 //   "VGPRs Spill" count; v_accvgpr moves, register to register): 54 in <MASKED, 6>, 38 / 19 / 2 in <MASKED, 5 / 4 / 3>, 16 in <CATEGORICAL, 6>, 0 in every
 //   other instantiation, the Gaussian ones included.
-#include "gauss_fused_dev.hpp"
+#include "fused_matrix_dev.hpp"
 
 namespace {
-
-static_assert(GW_K == 64 && GF_THREADS == 256, "four waves own 16 units each of a 64-wide layer; a chunk is one 64-deep product");
-
-typedef float gm_f4 __attribute__((ext_vector_type(4)));
-
-// the k of step t in k-slot kg (the head of the file)
-__device__ __forceinline__ int gm_k(int t, int kg) { return 16 * (t >> 2) + 4 * kg + (t & 3); }
-
-__host__ __device__ inline int gm_lds_floats(int outP) { return 4096 + 64 * outP + 64 + 64 + 32 + 32 + 32 + 64 + 2 * GW_K * GF_S + 64 * GF_S + 64 * GF_S + outP * GF_S; }
-
-// the family's images without a W1 image; m.x names buffer 0 of the two X chunk buffers, m.obsP is the chunk width
-__device__ __forceinline__ GfLds gm_carve(float* base, int outP) {
-    GfLds m;
-    m.obsP = GW_K; m.outP = outP;
-    float* p = base;
-    m.w1 = nullptr;
-    m.w2 = p; p += 4096;
-    m.w3 = p; p += 64 * outP;
-    m.b1 = p; p += 64;
-    m.b2 = p; p += 64;
-    m.b3 = p; p += 32;
-    m.ls = p; p += 32;
-    m.inv = p; p += 32;
-    m.ridx = reinterpret_cast<int*>(p); p += 64;
-    m.x = p; p += 2 * GW_K * GF_S;
-    m.h1 = p; p += 64 * GF_S;
-    m.h2 = p; p += 64 * GF_S;
-    m.o = p;
-    return m;
-}
-__device__ __forceinline__ float* gm_x(const GfLds& m, int b) { return m.x + b * (GW_K * GF_S); }
-
-// the A operand of a 64-deep product out of a row-major matrix W [64, ld] in global memory: row u, columns k0 + gm_k(t, kg), zero behind column K
-__device__ __forceinline__ void gm_fetch_a(const float* __restrict__ W, int ld, int K, int k0, int u, int kg, float (&a)[16]) {
-    const float* row = W + u * ld + k0;
-#pragma unroll
-    for (int t = 0; t < 16; t++) a[t] = k0 + gm_k(t, kg) < K ? row[gm_k(t, kg)] : 0.0f;
-}
-
-// acc[j] += A B_j over quarters 0 .. nq - 1 (16 k each): B_j [k][16 j + e] out of an image [k][sample]
-__device__ __forceinline__ void gm_mma_k(const float (&a)[16], const float* __restrict__ img, int nq, int e, int kg, gm_f4 (&acc)[4]) {
-#pragma unroll
-    for (int t = 0; t < 16; t++) {
-        if ((t >> 2) < nq) {   // uniform
-            const float* row = img + gm_k(t, kg) * GF_S + e;
-#pragma unroll
-            for (int j = 0; j < 4; j++) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t], row[16 * j], acc[j], 0, 0, 0);
-        }
-    }
-}
 
 // the A operand of a product over the tile's samples: row u of an image [unit][sample], sample gm_k(t, kg) at step t (four 16-byte reads)
 __device__ __forceinline__ void gm_load_a_s(const float* __restrict__ img, int u, int kg, float (&a)[16]) {
@@ -133,62 +83,33 @@ __device__ __forceinline__ float gm_row_sum(const float (&a)[16]) {
     return v;
 }
 
-// acc[j][r] = b[16 w + 4 kg + r]: a hidden layer's accumulators start at the bias
-__device__ __forceinline__ void gm_bias(const float* __restrict__ b, int w, int kg, gm_f4 (&acc)[4]) {
-    const float4 v = *reinterpret_cast<const float4*>(&b[16 * w + 4 * kg]);
-#pragma unroll
-    for (int j = 0; j < 4; j++) acc[j] = gm_f4{ v.x, v.y, v.z, v.w };
-}
-// out[16 w + 4 kg + r][16 j + e] = tanh(acc[j][r])
-__device__ __forceinline__ void gm_store_tanh(float* __restrict__ out, int w, int e, int kg, const gm_f4 (&acc)[4]) {
-#pragma unroll
-    for (int j = 0; j < 4; j++)
-#pragma unroll
-        for (int r = 0; r < 4; r++) out[(16 * w + 4 * kg + r) * GF_S + 16 * j + e] = tanh_fast(acc[j][r]);
-}
-
 // THE forward pass of every kernel in this file: the tile whose row indices are in m.ridx (published by the caller's barrier, as are the staged upper layers)
 // through obs -> 64 -> 64 -> out, layer 1 over nc = ceil(O / 64) chunks.  a2 is the wave's slice of W2 (gm_fetch_a, once per kernel).  Leaves H1, H2
 // (post-tanh), OUT rows 0 .. out - 1, chunk nc - 1 of X in buffer (nc - 1) & 1 and chunk nc - 2 in the other.  Every thread of the workgroup calls it; the
 // caller's barrier behind the previous tile has freed every image.
 __device__ __forceinline__ void gm_forward_tile(const GfLds& m, const GfShape& sh, const float* __restrict__ params, int net, const float* __restrict__ obs, int nc,
                                                 int out, int tid, const float (&a2)[16]) {
-    const int s = tid & 63, e = tid & 15, kg = (tid >> 4) & 3, w = __builtin_amdgcn_readfirstlane(tid >> 6), O = sh.obs;
+    const int e = tid & 15, kg = (tid >> 4) & 3, w = __builtin_amdgcn_readfirstlane(tid >> 6), O = sh.obs;
     const float* W1 = params + sh.off[net][0];
     float ra[16], rn[16], rx[16];
     gm_f4 acc[4];
+    // the fetch: every chunk's operands, and the products of the chunks in front of the last
     gm_fetch_a(W1, O, O, 0, 16 * w + e, kg, ra);
     gw_fetch_x(obs, O, m.ridx, 0, tid, rx);
     gm_bias(m.b1, w, kg, acc);
     gw_store_x(gm_x(m, 0), tid, rx);
     __syncthreads();
-    for (int c = 0; c < nc; c++) {
-        const bool more = c + 1 < nc;   // uniform
-        if (more) {
-            gm_fetch_a(W1, O, O, GW_K * (c + 1), 16 * w + e, kg, rn);
-            gw_fetch_x(obs, O, m.ridx, c + 1, tid, rx);
-        }
+    for (int c = 0; c + 1 < nc; c++) {
+        gm_fetch_a(W1, O, O, GW_K * (c + 1), 16 * w + e, kg, rn);
+        gw_fetch_x(obs, O, m.ridx, c + 1, tid, rx);
         gm_mma_k(ra, gm_x(m, c & 1), (gw_chunk_cols(O, c) + 15) >> 4, e, kg, acc);
-        if (more) {
 #pragma unroll
-            for (int t = 0; t < 16; t++) ra[t] = rn[t];
-            gw_store_x(gm_x(m, (c + 1) & 1), tid, rx);
-            __syncthreads();
-        }
+        for (int t = 0; t < 16; t++) ra[t] = rn[t];
+        gw_store_x(gm_x(m, (c + 1) & 1), tid, rx);
+        __syncthreads();
     }
-    gm_store_tanh(m.h1, w, e, kg, acc);
-    __syncthreads();
-    gm_bias(m.b2, w, kg, acc);
-    gm_mma_k(a2, m.h1, 4, e, kg, acc);
-    gm_store_tanh(m.h2, w, e, kg, acc);
-    __syncthreads();
-    gf_output_layer(m, out, s, w);
-    __syncthreads();
-}
-
-// the wave's slice of one net's W2, the A operand of layer 2
-__device__ __forceinline__ void gm_fetch_w2(const GfShape& sh, const float* __restrict__ params, int net, int tid, float (&a2)[16]) {
-    gm_fetch_a(params + sh.off[net][2], 64, 64, 0, 16 * (tid >> 6) + (tid & 15), (tid >> 4) & 3, a2);
+    // the products on the operand registers (fused_matrix_dev.hpp), shared with the device envs' rollouts
+    gm_forward_regs(m, ra, gm_x(m, (nc - 1) & 1), (gw_chunk_cols(O, nc - 1) + 15) >> 4, acc, a2, out, tid);
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -204,28 +204,6 @@ __global__ __launch_bounds__(256) void gauss_slab_reduce_kernel(const float* __r
 // reaches the limit on this step, Env::STATE + 1 stores of the pre-reset state and the terminated word into column t N + env of the record a.cut
 // [STATE + 1, T N].  No store at any other sample; cut_state_fold_kernel (below) reads the record.
 // ---------------------------------------------------------------------------------------------------------
-struct GfRolloutArgs {
-    GfShape sh;
-    const float* params;
-    int N, T, max_episode_steps;
-    int64_t seed, env_offset, step_base;
-    float* env_state;        // [2, N]
-    int32_t* ep_len;
-    float* ep_rew;
-    int32_t* reset_count;
-    float* obs;              // [T, N, Env::OBS]
-    float* actions;          // [T, N, 1]
-    float* logprobs;
-    float* rewards;
-    float* dones;
-    int32_t* fin_len;
-    float* fin_rew;
-    float* next_obs;         // [N, Env::OBS]
-    int32_t* next_done;
-    const float* forced;     // [T, N, 1] or null
-    float* cut;              // KEEP: the cut-off record [Env::STATE + 1, T * N]; null otherwise
-};
-
 template <class Env, bool KEEP>
 __global__ __launch_bounds__(GF_THREADS) void gauss_rollout_kernel(GfRolloutArgs a) {
     constexpr int OBS = Env::OBS;
@@ -495,16 +473,6 @@ __global__ __launch_bounds__(DEV_FOLD_THREADS) void gauss_dev_fold_kernel(GfShap
 // in the row-index words, which this kernel does not need as indices; the step's closing barrier, which every thread runs, hands it to the other waves.
 // The loop ends after at most max_episode_steps steps.  Nothing depends on the tile an episode sits in.
 // ---------------------------------------------------------------------------------------------------------
-struct GfEvalArgs {
-    GfShape sh;
-    const float* params;
-    int64_t n_episodes, seed;
-    int max_episode_steps, greedy;
-    float* ep_return;
-    int32_t* ep_length;
-    int32_t* ep_trunc;
-};
-
 template <class Env>
 __global__ __launch_bounds__(GF_THREADS) void gauss_eval_kernel(GfEvalArgs a) {
     constexpr int OBS = Env::OBS;
@@ -590,64 +558,6 @@ __global__ __launch_bounds__(GF_THREADS) void gauss_eval_kernel(GfEvalArgs a) {
 // hit wait for lanes that stick, the wave pays the longest lane's path each step.
 // KEEP: as in gauss_rollout_kernel -- step_episode_keep<Env> in the place of Env::step_episode, the record a.cut [STATE + 1, T N]; false is the kernel as it was.
 // ---------------------------------------------------------------------------------------------------------
-struct CfRolloutArgs {
-    GfShape sh;
-    const float* params;
-    int N, T, max_episode_steps;
-    int64_t seed, env_offset, step_base;
-    float* env_state;        // [Env::STATE, N]
-    int32_t* ep_len;
-    float* ep_rew;
-    int32_t* reset_count;
-    float* obs;              // [T, N, Env::OBS]
-    uint8_t* masks;          // [T, N, Env::ACTIONS]
-    int32_t* actions;        // [T, N, 1]
-    float* logprobs;
-    float* rewards;
-    float* dones;
-    int32_t* fin_len;
-    float* fin_rew;
-    float* next_obs;         // [N, Env::OBS]
-    int32_t* next_done;
-    const int64_t* forced;   // [T, N, 1] or null
-    float* cut;              // KEEP: the cut-off record [Env::STATE + 1, T * N]; null otherwise
-};
-
-// wave 0's lane behind the forward: the row's head on the lane's columns (z: OUT, log-probs in place; p: H1), the action (GREEDY: the first-index argmax of
-// the probabilities; forced; or the draw with uniform word `ws`) and its log-prob -- cat_act_kernel<DIST>'s expressions for one head.  PPO_DIST_MASKED:
-// bit k of `allowed` is the row's mask byte k (the lane formed it from its env's state; a masked-out logit becomes -1e8f, its probability 0)
-template <int DIST, bool GREEDY>
-__device__ __forceinline__ int cat_lane_head(const GfLds& m, int lane, int Ah, uint32_t allowed, bool has_forced, int forced, uint32_t ws, float& lp) {
-    float* z = m.o + lane;
-    float* p = m.h1 + lane;
-    if constexpr (DIST == PPO_DIST_MASKED) {
-        uint8_t mrow[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) mrow[k] = (uint8_t)((allowed >> k) & 1u);
-        (void)categorical_head<PPO_DIST_MASKED, GF_S>(z, p, mrow, Ah);
-    } else {
-        (void)categorical_head<PPO_DIST_CATEGORICAL, GF_S>(z, p, nullptr, Ah);
-    }
-    int a;
-    if constexpr (GREEDY) {
-        a = 0;
-        for (int k = 1; k < Ah; k++) if (p[k * GF_S] > p[a * GF_S]) a = k;
-    } else if (has_forced) {
-        a = forced;
-    } else {
-        a = sample_head<GF_S>(p, Ah, (float)(ws >> 8) * 0x1p-24f);
-    }
-    lp = 0.0f;
-    for (int k = 0; k < Ah; k++) if (k == a) lp = z[k * GF_S];
-    return a;
-}
-// a caller's i64 action as the env's int: saturated, not truncated, so that an env that clamps its action clamps the caller's number
-__device__ __forceinline__ int cat_action_int(int64_t a) { return a < -2147483647ll ? -2147483647 : (a > 2147483647ll ? 2147483647 : (int)a); }
-__device__ __forceinline__ uint32_t cat_draw_word(int64_t seed, int64_t row, int64_t step_index) {
-    const uint4 w = philox4x32_10((uint32_t)seed, (uint32_t)((uint64_t)seed >> 32), (uint32_t)row, (uint32_t)(step_index >> 2), 0u, 0u);
-    return (step_index & 3) == 0 ? w.x : ((step_index & 3) == 1 ? w.y : ((step_index & 3) == 2 ? w.z : w.w));
-}
-
 template <class Env, int DIST, bool KEEP>
 __global__ __launch_bounds__(GF_THREADS) void cat_rollout_kernel(CfRolloutArgs a) {
     constexpr int OBS = Env::OBS, ST = Env::STATE, A = Env::ACTIONS, OBSP = (OBS + 3) & ~3, OUTP = (A + 3) & ~3;
@@ -1269,24 +1179,7 @@ hipError_t cat_fused_fwd_bwd(const GenLayout& L, const LossParams& hp, const flo
 
 // ---- the device envs of the two fused families (gauss_fused.hpp; the context's shape is fixed by ppo_ctx_create from the env's row: obs Env::OBS, one head of
 // Env::ACTIONS logits, or D = 1) ----
-// env_kind -> trait: f is called with a value of the env's trait type; an env without one gives hipErrorInvalidValue
-template <class F>
-static hipError_t gauss_env_dispatch(int env_kind, F f) {
-    if (env_kind == PPO_ENV_PENDULUM) return f(GaussEnvPendulum{});
-    if (env_kind == PPO_ENV_MOUNTAINCAR_CONTINUOUS) return f(GaussEnvMountainCarContinuous{});
-    return hipErrorInvalidValue;
-}
-template <class F>
-static hipError_t cat_env_dispatch(int env_kind, F f) {
-    if (env_kind == PPO_ENV_ACROBOT) return f(CatEnvAcrobot{});
-    if (env_kind == PPO_ENV_TAXI) return f(CatEnvTaxi{});
-    if (env_kind == PPO_ENV_FROZENLAKE) return f(CatEnvFrozenLake<4>{});
-    if (env_kind == PPO_ENV_FROZENLAKE8X8) return f(CatEnvFrozenLake<8>{});
-    if (env_kind == PPO_ENV_BLACKJACK) return f(CatEnvBlackjack{});
-    return hipErrorInvalidValue;
-}
-
-// One row per line of the two dispatchers.  A Gaussian env folds and evaluates where its observation is its state; a categorical env folds where the
+// One row per line of the two dispatchers (gauss_env_dispatch, cat_env_dispatch: gauss_fused_dev.hpp).  A Gaussian env folds and evaluates where its observation is its state; a categorical env folds where the
 // observation holds the state, and every one evaluates.
 template <class Env>
 static constexpr FusedEnvInfo gauss_env_row(int kind, const char* name, int max_steps, FusedEnvTexts t) {
@@ -1349,39 +1242,10 @@ const FusedEnvInfo* fused_env_info(int env_kind) {
     return nullptr;
 }
 
-// the family's dispatcher: fg is called with a GaussEnv* trait, fc with a CatEnv* one
-template <class FG, class FC>
-static hipError_t fused_env_dispatch(int env_kind, FG fg, FC fc) {
-    const FusedEnvInfo* e = fused_env_info(env_kind);
-    if (!e) return hipErrorInvalidValue;
-    return e->family == FUSED_GAUSS ? gauss_env_dispatch(env_kind, fg) : cat_env_dispatch(env_kind, fc);
-}
-
-template <class Env>
-static bool gauss_env_shape_ok(const GenLayout& L) { return L.obs == Env::OBS && L.gauss == 1; }
-template <class Env>
-static bool cat_env_shape_ok(const GenLayout& L) { return L.obs == Env::OBS && L.gauss == 0 && L.n_heads == 1 && L.act == Env::ACTIONS; }
-// a masked policy runs on an env that forms a mask, and on no other (ppo_ctx_create)
-template <class Env>
-static bool cat_env_dist_ok(int dist_kind) { return dist_kind == PPO_DIST_CATEGORICAL || (dist_kind == PPO_DIST_MASKED && Env::HAS_MASK); }
 template <class Env>
 static int cat_env_lds_bytes() { return gf_lds_floats(gf_pad4(Env::OBS), gf_pad4(Env::ACTIONS)) * 4; }
 
-// the kernels' argument structs from the launchers' (GfRolloutArgs / CfRolloutArgs, GfFoldArgs / CfFoldArgs: the same fields, the family's action types)
-template <class KernelArgs>
-static KernelArgs rollout_kernel_args(const GenLayout& L, const FusedRolloutArgs& r) {
-    KernelArgs a{};
-    a.sh = gf_shape(L);
-    a.params = r.params;
-    a.N = r.N; a.T = r.T; a.max_episode_steps = r.max_episode_steps;
-    a.seed = r.seed; a.env_offset = r.env_offset; a.step_base = r.step_base;
-    a.env_state = r.env_state; a.ep_len = r.ep_len; a.ep_rew = r.ep_rew; a.reset_count = r.reset_count;
-    a.obs = r.obs; a.actions = static_cast<decltype(a.actions)>(r.actions); a.logprobs = r.logprobs; a.rewards = r.rewards; a.dones = r.dones;
-    a.fin_len = r.fin_len; a.fin_rew = r.fin_rew;
-    a.next_obs = r.next_obs; a.next_done = r.next_done; a.forced = static_cast<decltype(a.forced)>(r.forced);
-    a.cut = r.cut;
-    return a;
-}
+// the fold kernels' argument structs from the launcher's (GfFoldArgs / CfFoldArgs: the same fields, the family's action types)
 template <class KernelArgs>
 static KernelArgs fold_kernel_args(const GenLayout& L, const FusedFoldArgs& f) {
     KernelArgs a{};
@@ -1391,16 +1255,6 @@ static KernelArgs fold_kernel_args(const GenLayout& L, const FusedFoldArgs& f) {
     a.rewards = f.rewards; a.ev_count = f.ev_count; a.ev_index = f.ev_index; a.ev_value = f.ev_value; a.ev_cap = f.ev_cap;
     return a;
 }
-static GfEvalArgs eval_kernel_args(const GenLayout& L, const FusedEvalArgs& e) {
-    GfEvalArgs a{};
-    a.sh = gf_shape(L);
-    a.params = e.params;
-    a.n_episodes = e.n_episodes; a.seed = e.seed;
-    a.max_episode_steps = e.max_episode_steps; a.greedy = e.greedy != 0;
-    a.ep_return = e.ep_return; a.ep_length = e.ep_length; a.ep_trunc = e.ep_trunc;
-    return a;
-}
-
 template <class Env, bool KEEP>
 static hipError_t gauss_rollout_launch(const GenLayout& L, const FusedRolloutArgs& r, hipStream_t s) {
     if (!gauss_env_shape_ok<Env>(L)) return hipErrorInvalidValue;
@@ -1439,6 +1293,7 @@ static hipError_t cat_eval_launch(const GfEvalArgs& a, hipStream_t s) {
 
 hipError_t launch_fused_env_rollout(int env_kind, int dist_kind, const GenLayout& L, const FusedRolloutArgs& r, hipStream_t s) {
     if (r.N <= 0 || r.T <= 0) return hipSuccess;
+    if (L.env_matrix) return env_matrix_rollout(env_kind, dist_kind, L, r, s);
     return fused_env_dispatch(env_kind, [&](auto env) {
         return r.cut ? gauss_rollout_launch<decltype(env), true>(L, r, s) : gauss_rollout_launch<decltype(env), false>(L, r, s);
     }, [&](auto env) {
@@ -1507,6 +1362,7 @@ hipError_t fused_env_trunc_fold(int env_kind, const GenLayout& L, const FusedFol
 hipError_t fused_env_evaluate(int env_kind, int dist_kind, const GenLayout& L, const FusedEvalArgs& e, hipStream_t s) {
     if (e.n_episodes <= 0) return hipSuccess;
     if (e.max_episode_steps < 1 || e.n_episodes >= (1ll << 31) * 64 || !e.ep_return || !e.ep_length || !e.ep_trunc) return hipErrorInvalidValue;
+    if (L.env_matrix) return env_matrix_evaluate(env_kind, dist_kind, L, e, s);
     return fused_env_dispatch(env_kind, [&](auto env) {
         using Env = decltype(env);
         if constexpr (Env::OBS_IS_STATE) {

@@ -158,7 +158,12 @@ void PPOAlgorithm::construct() {
     c.kernel_flags = m_fused_policy ? PPO_KERNEL_GAUSS_FUSED : 0;   // a class whose policy is not Gaussian: the library's refusal is thrown below, with its message
     if (m_fused_categorical) c.kernel_flags |= PPO_KERNEL_CAT_FUSED;   // likewise for a class whose context is not a caller-stepped categorical one
     if (m_wide_obs) c.kernel_flags |= PPO_KERNEL_FUSED_WIDE_OBS;   // obs_size up to 384 on the fused family the class runs; any other context: the library's refusal is thrown below
-    if (m_matrix_cores) c.kernel_flags |= PPO_KERNEL_FUSED_MATRIX;   // the fused family's 64-wide products on the f32 matrix cores; any other context: the library's refusal is thrown below
+    // the fused family's 64-wide products on the f32 matrix cores: PPO_KERNEL_ENV_MATRIX on the fused device-env classes (the one-launch rollout with resident
+    // weight operands), PPO_KERNEL_FUSED_MATRIX on every other class; a context neither flag serves: the library's refusal is thrown below
+    const bool fused_device_env = m_env_kind == PPO_ENV_PENDULUM || m_env_kind == PPO_ENV_MOUNTAINCAR_CONTINUOUS || m_env_kind == PPO_ENV_ACROBOT ||
+                                  m_env_kind == PPO_ENV_TAXI || m_env_kind == PPO_ENV_FROZENLAKE || m_env_kind == PPO_ENV_FROZENLAKE8X8 ||
+                                  m_env_kind == PPO_ENV_BLACKJACK;
+    if (m_matrix_cores) c.kernel_flags |= fused_device_env ? PPO_KERNEL_ENV_MATRIX : PPO_KERNEL_FUSED_MATRIX;
     if (m_keep_cut_states) c.kernel_flags |= PPO_KERNEL_ENV_CUT_STATE;   // a class whose env is no fused device env: the library's refusal is thrown below, with its message
     if (m_env_norm_reward) c.kernel_flags |= PPO_KERNEL_ENV_REWARD_NORM;   // set by the fused device-env classes alone (normRewardOnDeviceEnv): ppo_reward_norm_* on the one-launch rollout
     if (m_hidden_size_given) c.kernel_flags |= PPO_KERNEL_ENV_GENERIC;   // CartPole / MountainCar on the generic engine, also at hidden_size = 64; a width out of range is the library's refusal

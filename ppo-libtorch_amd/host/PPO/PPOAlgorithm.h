@@ -104,7 +104,7 @@ class PPOAlgorithm {
     int64_t m_env_groups = 1;            // extension ([environment] env_groups): PPO_HostEnv's env groups; the device-env algorithms have no use for it
     bool m_norm_obs = false;             // extension ([environment] norm_obs): PPO_HostEnv normalises observations with running statistics (ppo_obs_norm_*)
     bool m_wide_obs = false;             // extension ([environment] wide_obs; PPO_HostEnv with fused_categorical, PPO_HostEnvBox with fused_policy): PPO_KERNEL_FUSED_WIDE_OBS, obs_size up to 384 on the fused kernels; on any other context the library refuses it
-    bool m_matrix_cores = false;         // extension ([environment] matrix_cores; PPO_HostEnv with fused_categorical, PPO_HostEnvBox with fused_policy, with or without wide_obs): PPO_KERNEL_FUSED_MATRIX, the fused kernels' 64-wide products on the f32 matrix cores; on any other context the library refuses it
+    bool m_matrix_cores = false;         // extension ([environment] matrix_cores; PPO_HostEnv with fused_categorical, PPO_HostEnvBox with fused_policy, with or without wide_obs): PPO_KERNEL_FUSED_MATRIX, the fused kernels' 64-wide products on the f32 matrix cores; on the six fused device-env classes (PPO_Continuous, PPO_ContinuousMountainCar, PPO_DiscreteAcrobot, PPO_MultiDiscreteTaxi, PPO_DiscreteFrozenLake, PPO_DiscreteBlackjack): PPO_KERNEL_ENV_MATRIX, the one-launch rollout and the evaluation behind the same forward (bootstrap_truncated beside it: the library's refusal); on any other context the library refuses it
     bool m_fused_categorical = false;    // extension ([environment] fused_categorical): PPO_HostEnv's context runs the fused categorical 2 x 64 kernels (PPO_KERNEL_CAT_FUSED); on any other class the library refuses the context
     bool m_fused_policy = false;         // extension ([environment] fused_policy): PPO_HostEnvBox's context runs the fused Gaussian 2 x 64 kernels (PPO_KERNEL_GAUSS_FUSED); on any other class the library refuses the context
     bool m_norm_reward = false;          // extension ([environment] norm_reward): PPO_HostEnv divides rewards by the running std of the discounted return (ppo_reward_norm_*)
