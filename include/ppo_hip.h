@@ -511,7 +511,14 @@ enum { PPO_KERNEL_ROLLOUT_VECTOR = 1, PPO_KERNEL_UPDATE_VECTOR = 2, PPO_KERNEL_U
  * without the flag every context is what it was, refusals included, word for word.  ppo_ctx_create returns PPO_ERR_UNSUPPORTED with a message naming the flag
  * and the limit on any other env_kind (the device envs, PPO_ENV_CARTPOLE, PPO_ENV_MOUNTAINCAR, PPO_ENV_SYNTHETIC), without a family flag, with both family
  * flags, and beside PPO_KERNEL_ENV_GENERIC.  No symbol and no buffer id of its own.  Sharding (ppo_comm_init*) of a flagged context is neither claimed nor
- * tested. */
+ * tested.
+ * hidden = 128 (n_hidden = 2): the one value of ppo_config.hidden besides 64 that a flagged context accepts, and only a flagged one -- under a family flag
+ * alone the width is refused as before.  It runs kernels_fused_matrix_h128.hip: the same launches, counters, observation limits, output widths and
+ * entry-point guarantee (one forward function; no float atomics), four waves owning 32 units each, W1 and W2 from global memory straight into operand
+ * registers (W2 does not fit in LDS beside the images), dW1 and dW2 summed per tile and accumulated in the workgroup's own slab.  LDS: 131 200 bytes at 32
+ * outputs, 109 248 for the critic (+ 1 056 in the fold).  Any other width beside the flag is PPO_ERR_UNSUPPORTED with a message naming the flag and the two
+ * widths; hidden = 256 is not built: two [256][68] f32 images and the two X chunk buffers are 174 080 bytes against 163 840 bytes of LDS, before any weight.
+ * The device envs (PPO_KERNEL_ENV_MATRIX) stay at 2 x 64. */
 #define PPO_KERNEL_FUSED_MATRIX (1 << 16)
 /* PPO_KERNEL_ENV_MATRIX (131072; bits 11, 12 and 14 stay unassigned and are refused as unknown, as is bit 18): PPO_KERNEL_FUSED_MATRIX's forward for the seven
  * fused device envs (PPO_ENV_PENDULUM, PPO_ENV_MOUNTAINCAR_CONTINUOUS, PPO_ENV_ACROBOT, PPO_ENV_TAXI, PPO_ENV_FROZENLAKE, PPO_ENV_FROZENLAKE8X8,

@@ -682,7 +682,8 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
     }
     // PPO_KERNEL_FUSED_MATRIX: a PPO_ENV_HOST context next to exactly one of the two family flags (with or without PPO_KERNEL_FUSED_WIDE_OBS), or a refusal that
     // names the flag and the limit.  In front of the other flags' blocks, so that the flag beside one of them is answered here.  The family's own blocks below
-    // then check hidden, n_hidden, dtype, the policy's kind, the output width and the observation width in their own words
+    // then check hidden (64, or FUSED_MATRIX_WIDE_HIDDEN = 128: kernels_fused_matrix_h128.hip -- the one value of ppo_config.hidden that only this flag admits),
+    // n_hidden, dtype, the policy's kind, the output width and the observation width in their own words
     const bool fused_matrix = (cfg->kernel_flags & PPO_KERNEL_FUSED_MATRIX) != 0;
     if (fused_matrix) {
         if (cfg->kernel_flags & ~known_flags) return fail(nullptr, PPO_ERR_INVALID, "unknown bits in kernel_flags 0x%x", cfg->kernel_flags);
@@ -804,7 +805,12 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
         if (!host_env && !cat_env)
             return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED serves caller-stepped environments (env_kind = PPO_ENV_HOST), %s only; got env_kind %d",
                         fused_env_names(FUSED_CAT), cfg->env_kind);
-        if (cfg->hidden != 64) return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED is built for hidden = 64; got hidden = %d", cfg->hidden);
+        if (fused_matrix && !fused_matrix_serves_hidden(cfg->hidden))
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED beside PPO_KERNEL_FUSED_MATRIX is built for hidden = 64 and hidden = %d; got hidden = %d "
+                        "(hidden = 256 needs two [256][68] f32 images and two X chunk buffers, 174080 bytes against %d bytes of LDS per workgroup, before "
+                        "any weight: it is not built)", FUSED_MATRIX_WIDE_HIDDEN, cfg->hidden, 160 * 1024);
+        if (!fused_matrix && cfg->hidden != 64)
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED is built for hidden = 64; got hidden = %d", cfg->hidden);
         if (cfg->n_hidden != 2) return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED is built for n_hidden = 2; got n_hidden = %d", cfg->n_hidden);
         if (cfg->compute_dtype != PPO_DTYPE_F32)
             return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED is built for compute_dtype = PPO_DTYPE_F32; bf16 storage is not");
@@ -834,15 +840,20 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
         if (!gauss)
             return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_GAUSS_FUSED serves dist_kind = PPO_DIST_GAUSSIAN only; this context's policy is categorical (dist_kind %d)",
                         cfg->dist_kind);
-        if (cfg->hidden != 64) return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_GAUSS_FUSED is built for hidden = 64; got hidden = %d", cfg->hidden);
+        if (fused_matrix && !fused_matrix_serves_hidden(cfg->hidden))
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_GAUSS_FUSED beside PPO_KERNEL_FUSED_MATRIX is built for hidden = 64 and hidden = %d; got hidden = %d "
+                        "(hidden = 256 needs two [256][68] f32 images and two X chunk buffers, 174080 bytes against %d bytes of LDS per workgroup, before "
+                        "any weight: it is not built)", FUSED_MATRIX_WIDE_HIDDEN, cfg->hidden, 160 * 1024);
+        if (!fused_matrix && cfg->hidden != 64)
+            return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_GAUSS_FUSED is built for hidden = 64; got hidden = %d", cfg->hidden);
         if (cfg->n_hidden != 2) return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_GAUSS_FUSED is built for n_hidden = 2; got n_hidden = %d", cfg->n_hidden);
         if (cfg->obs_size > fused_max_obs)
             return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_GAUSS_FUSED is built for obs_size <= %d; got obs_size = %d", fused_max_obs, cfg->obs_size);
-        if (!gauss_fused_serves_shape(fused_obs, cfg->hidden, cfg->n_hidden, A))
+        if (!gauss_fused_serves_shape(fused_obs, cfg->hidden, cfg->n_hidden, A, fused_matrix))
             return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_GAUSS_FUSED is built for 1 <= D <= %d and 1 <= obs_size <= %d; got D = %d, obs_size = %d", PPO_MAX_ACT,
                         fused_max_obs, A, cfg->obs_size);
     }
-    if (cat_fused && !cat_fused_serves_shape(fused_obs, cfg->hidden, cfg->n_hidden, A))   // the head list's limits are the ABI's own, checked above
+    if (cat_fused && !cat_fused_serves_shape(fused_obs, cfg->hidden, cfg->n_hidden, A, fused_matrix))   // the head list's limits are the ABI's own, checked above
         return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED is built for sum(head_dims) <= %d and 1 <= obs_size <= %d; got %d, obs_size = %d", PPO_MAX_ACT,
                     fused_max_obs, A, cfg->obs_size);
     if (cfg->num_envs < 1 || cfg->num_steps < 1 || cfg->num_minibatches < 1 || cfg->update_epochs < 1)

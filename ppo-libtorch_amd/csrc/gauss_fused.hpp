@@ -5,7 +5,8 @@
 constexpr int GAUSS_FUSED_MAX_OBS = 64;      // the X image and W1 are sized by it (the LDS budget is at the head of kernels_gauss_fused.hip)
 constexpr int GAUSS_FUSED_MAX_BLOCKS = 128;  // workgroups per net of the update kernel = partial slabs; a minibatch of more than 64 x this many rows gives a workgroup several tiles
 
-bool gauss_fused_serves_shape(int obs, int hidden, int n_hidden, int D);
+// matrix: the context carries PPO_KERNEL_FUSED_MATRIX, whose kernels also serve hidden = FUSED_MATRIX_WIDE_HIDDEN (below)
+bool gauss_fused_serves_shape(int obs, int hidden, int n_hidden, int D, bool matrix = false);
 // floats between two partial slabs: the wider net's parameters (the actor's, with log_std behind them)
 int64_t gauss_fused_slab_stride(const GenLayout& L);
 
@@ -30,7 +31,7 @@ hipError_t gauss_fused_fwd_bwd(const GenLayout& L, const LossParams& hp, const f
 
 // PPO_KERNEL_CAT_FUSED: the same kernel family for categorical / masked multi-head policies (GenLayout with gauss = 0; A = L.act <= PPO_MAX_ACT logits in the
 // place of the mean).  The critic is gauss_fused_values, the slab stride gauss_fused_slab_stride (no log_std behind the actor).
-bool cat_fused_serves_shape(int obs, int hidden, int n_hidden, int A);
+bool cat_fused_serves_shape(int obs, int hidden, int n_hidden, int A, bool matrix = false);
 // the rollout stores of one step (gen_store_step's): rows of step t, every pointer at the first row of the launch; null: the stand-alone policy
 struct CatStepStores { const int32_t* done_prev; float* obs_t; uint8_t* mask_t; int32_t* act_t; float* lp_t; float* dones_t; };
 // gen_forward (actor) + gen_heads (+ gen_store_step) in one launch over n rows; every pointer names the first of them, row_offset is the sampler's row origin
@@ -69,6 +70,21 @@ hipError_t fused_matrix_cat_act(const GenLayout& L, int dist_kind, const float* 
 hipError_t fused_matrix_values(const GenLayout& L, const float* params, const float* obs, int64_t n, float* value, hipStream_t s);
 hipError_t fused_matrix_dev_fold(const GenLayout& L, const float* params, const DevFoldArgs& a, hipStream_t s);
 hipError_t fused_matrix_fwd_bwd(const GenLayout& L, const GfUpdArgs& a, float* grads, hipStream_t s);   // the policy's kind is a.hp.dist_kind
+
+// ---- PPO_KERNEL_FUSED_MATRIX at hidden = 128 (kernels_fused_matrix_h128.hip): the same five launches for a 2 x 128 network, a kernel set of its own (four
+// waves of 32 units, W2 from L2 into operand registers, dW1 / dW2 through the workgroup's slab).  The six launchers above hand a layout with L.fused_matrix
+// set and L.hidden == FUSED_MATRIX_WIDE_HIDDEN to these, argument for argument; nobody else calls them.  ppo_ctx_create admits the width only under the flag.
+// hidden = 256 is not built: two [256][68] f32 images and the two X chunk buffers are 174 080 bytes against 163 840 bytes of LDS, before any weight. ----
+constexpr int FUSED_MATRIX_WIDE_HIDDEN = 128;
+bool fused_matrix_serves_hidden(int hidden);   // 64 or FUSED_MATRIX_WIDE_HIDDEN
+hipError_t fused_matrix_h128_gauss_act(const GenLayout& L, const float* params, const float* obs, const float* forced, int64_t n, int64_t seed, int64_t row_offset,
+                                       int64_t step_index, bool greedy, float* action, float* logprob, float* entropy, const GaussStepStores* st, hipStream_t s);
+hipError_t fused_matrix_h128_cat_act(const GenLayout& L, int dist_kind, const float* params, const float* obs, const uint8_t* mask, const int64_t* forced, int64_t n,
+                                     int64_t seed, int64_t row_offset, int64_t step_index, bool greedy, int64_t* action, float* logprob, float* entropy,
+                                     const CatStepStores* st, hipStream_t s);
+hipError_t fused_matrix_h128_values(const GenLayout& L, const float* params, const float* obs, int64_t n, float* value, hipStream_t s);
+hipError_t fused_matrix_h128_dev_fold(const GenLayout& L, const float* params, const DevFoldArgs& a, hipStream_t s);
+hipError_t fused_matrix_h128_fwd_bwd(const GenLayout& L, const GfUpdArgs& a, float* grads, hipStream_t s);   // the policy's kind is a.hp.dist_kind
 
 // ---- The device envs of the two fused families.  An env is a trait in ppo_internal.hpp (GaussEnv*: one real-valued action; CatEnv*: one head of integer
 // actions), one line of its family's dispatcher and one row of the table in kernels_gauss_fused.hip; everything the C-ABI layer knows about an env it reads

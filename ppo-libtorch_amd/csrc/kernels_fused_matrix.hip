@@ -345,8 +345,8 @@ hipError_t gm_cat_act_launch(const GfShape& sh, int bytes, dim3 grid, const floa
     return hipGetLastError();
 }
 
-// the shapes this file's kernels are launched for: one to six chunks
-bool gm_shape_ok(const GenLayout& L) { return L.fused_matrix && L.obs >= 1 && L.obs <= FUSED_WIDE_MAX_OBS && L.act >= 1 && L.act <= PPO_MAX_ACT; }
+// the shapes this file's kernels are launched for: 2 x 64, one to six chunks
+bool gm_shape_ok(const GenLayout& L) { return L.fused_matrix && L.hidden == 64 && L.obs >= 1 && L.obs <= FUSED_WIDE_MAX_OBS && L.act >= 1 && L.act <= PPO_MAX_ACT; }
 
 }  // namespace
 

@@ -1042,7 +1042,9 @@ __global__ __launch_bounds__(DEV_FOLD_THREADS) void cut_state_fold_kernel(CutFol
 
 }  // namespace
 
-bool gauss_fused_serves_shape(int obs, int hidden, int n_hidden, int D) { return hidden == 64 && n_hidden == 2 && D >= 1 && D <= PPO_MAX_ACT && obs >= 1 && obs <= GAUSS_FUSED_MAX_OBS; }
+bool fused_matrix_serves_hidden(int hidden) { return hidden == 64 || hidden == FUSED_MATRIX_WIDE_HIDDEN; }
+
+bool gauss_fused_serves_shape(int obs, int hidden, int n_hidden, int D, bool matrix) { return (matrix ? fused_matrix_serves_hidden(hidden) : hidden == 64) && n_hidden == 2 && D >= 1 && D <= PPO_MAX_ACT && obs >= 1 && obs <= GAUSS_FUSED_MAX_OBS; }
 
 int64_t gauss_fused_slab_stride(const GenLayout& L) { return ((int64_t)std::max(L.net_size[0], L.net_size[1] + L.gauss) + 3) & ~3ll; }
 
@@ -1054,6 +1056,7 @@ hipError_t gauss_fused_slab_reduce(const GenLayout& L, const float* slab, int sl
 hipError_t gauss_fused_act(const GenLayout& L, const float* params, const float* obs, const float* forced, int64_t n, int64_t seed, int64_t row_offset,
                            int64_t step_index, bool greedy, float* action, float* logprob, float* entropy, const GaussStepStores* st, hipStream_t s) {
     if (n <= 0) return hipSuccess;
+    if (L.fused_matrix && L.hidden == FUSED_MATRIX_WIDE_HIDDEN) return fused_matrix_h128_gauss_act(L, params, obs, forced, n, seed, row_offset, step_index, greedy, action, logprob, entropy, st, s);
     if (L.fused_matrix) return fused_matrix_gauss_act(L, params, obs, forced, n, seed, row_offset, step_index, greedy, action, logprob, entropy, st, s);
     if (L.obs > GAUSS_FUSED_MAX_OBS) return fused_wide_gauss_act(L, params, obs, forced, n, seed, row_offset, step_index, greedy, action, logprob, entropy, st, s);
     const GfShape sh = gf_shape(L);
@@ -1077,6 +1080,7 @@ hipError_t gauss_fused_act(const GenLayout& L, const float* params, const float*
 
 hipError_t gauss_fused_values(const GenLayout& L, const float* params, const float* obs, int64_t n, float* value, hipStream_t s) {
     if (n <= 0) return hipSuccess;
+    if (L.fused_matrix && L.hidden == FUSED_MATRIX_WIDE_HIDDEN) return fused_matrix_h128_values(L, params, obs, n, value, s);
     if (L.fused_matrix) return fused_matrix_values(L, params, obs, n, value, s);
     if (L.obs > GAUSS_FUSED_MAX_OBS) return fused_wide_values(L, params, obs, n, value, s);
     const GfShape sh = gf_shape(L);
@@ -1091,6 +1095,7 @@ hipError_t gauss_fused_values(const GenLayout& L, const float* params, const flo
 
 hipError_t gauss_fused_dev_fold(const GenLayout& L, const float* params, const DevFoldArgs& a, hipStream_t s) {
     if (a.N <= 0) return hipSuccess;
+    if (L.fused_matrix && L.hidden == FUSED_MATRIX_WIDE_HIDDEN) return fused_matrix_h128_dev_fold(L, params, a, s);
     if (L.fused_matrix) return fused_matrix_dev_fold(L, params, a, s);
     if (L.obs > GAUSS_FUSED_MAX_OBS) return fused_wide_dev_fold(L, params, a, s);
     const GfShape sh = gf_shape(L);
@@ -1109,6 +1114,7 @@ hipError_t gauss_fused_fwd_bwd(const GenLayout& L, const LossParams& hp, const f
                                const AdvStat* adv_stat, float* slab, double* loss_part, float* grads, hipStream_t s) {
     if (M < 1 || M >= (1ll << 31) - 64 || !slab || !loss_part) return hipErrorInvalidValue;
     const GfUpdArgs a = gf_upd_args(L, hp, params, obs, actions, nullptr, oldlp, adv, ret, oldv, idx, M, inv_global_M, global_M, adv_stat, slab, loss_part);
+    if (L.fused_matrix && L.hidden == FUSED_MATRIX_WIDE_HIDDEN) return fused_matrix_h128_fwd_bwd(L, a, grads, s);
     if (L.fused_matrix) return fused_matrix_fwd_bwd(L, a, grads, s);
     if (L.obs > GAUSS_FUSED_MAX_OBS) return fused_wide_fwd_bwd(L, a, grads, s);
     const int bytes = gf_lds_floats(gf_pad4(L.obs), gf_pad4(L.gauss)) * 4;
@@ -1120,7 +1126,7 @@ hipError_t gauss_fused_fwd_bwd(const GenLayout& L, const LossParams& hp, const f
 }
 
 // ---- PPO_KERNEL_CAT_FUSED: categorical / masked multi-head policies on the same forward (the critic is gauss_fused_values: with L.gauss = 0 no log_std is read) ----
-bool cat_fused_serves_shape(int obs, int hidden, int n_hidden, int A) { return hidden == 64 && n_hidden == 2 && A >= 1 && A <= PPO_MAX_ACT && obs >= 1 && obs <= GAUSS_FUSED_MAX_OBS; }
+bool cat_fused_serves_shape(int obs, int hidden, int n_hidden, int A, bool matrix) { return (matrix ? fused_matrix_serves_hidden(hidden) : hidden == 64) && n_hidden == 2 && A >= 1 && A <= PPO_MAX_ACT && obs >= 1 && obs <= GAUSS_FUSED_MAX_OBS; }
 
 template <int DIST, bool GREEDY>
 static hipError_t cat_fused_act_launch(const GfShape& sh, int bytes, dim3 grid, const float* params, const float* obs, const uint8_t* mask, const int64_t* forced, int64_t n,
@@ -1138,6 +1144,7 @@ hipError_t cat_fused_act(const GenLayout& L, int dist_kind, const float* params,
                          int64_t row_offset, int64_t step_index, bool greedy, int64_t* action, float* logprob, float* entropy, const CatStepStores* st, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     if (L.gauss || (dist_kind != PPO_DIST_CATEGORICAL && dist_kind != PPO_DIST_MASKED)) return hipErrorInvalidValue;
+    if (L.fused_matrix && L.hidden == FUSED_MATRIX_WIDE_HIDDEN) return fused_matrix_h128_cat_act(L, dist_kind, params, obs, mask, forced, n, seed, row_offset, step_index, greedy, action, logprob, entropy, st, s);
     if (L.fused_matrix) return fused_matrix_cat_act(L, dist_kind, params, obs, mask, forced, n, seed, row_offset, step_index, greedy, action, logprob, entropy, st, s);
     if (L.obs > GAUSS_FUSED_MAX_OBS)
         return fused_wide_cat_act(L, dist_kind, params, obs, mask, forced, n, seed, row_offset, step_index, greedy, action, logprob, entropy, st, s);
@@ -1161,6 +1168,7 @@ hipError_t cat_fused_fwd_bwd(const GenLayout& L, const LossParams& hp, const flo
     if (hp.dist_kind != PPO_DIST_CATEGORICAL && hp.dist_kind != PPO_DIST_MASKED) return hipErrorInvalidValue;
     const GfUpdArgs a = gf_upd_args(L, hp, params, obs, reinterpret_cast<const float*>(actions), hp.dist_kind == PPO_DIST_MASKED ? masks : nullptr, oldlp, adv, ret, oldv,
                                     idx, M, inv_global_M, global_M, adv_stat, slab, loss_part);
+    if (L.fused_matrix && L.hidden == FUSED_MATRIX_WIDE_HIDDEN) return fused_matrix_h128_fwd_bwd(L, a, grads, s);
     if (L.fused_matrix) return fused_matrix_fwd_bwd(L, a, grads, s);
     if (L.obs > GAUSS_FUSED_MAX_OBS) return fused_wide_fwd_bwd(L, a, grads, s);
     const int bytes = gf_lds_floats(gf_pad4(L.obs), gf_pad4(L.act)) * 4;

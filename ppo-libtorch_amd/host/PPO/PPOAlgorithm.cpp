@@ -81,7 +81,9 @@ void PPOAlgorithm::getArgs() {
         B("environment", "fused_categorical", m_fused_categorical);       // extension key (PPO_HostEnv), likewise
         B("environment", "wide_obs", m_wide_obs);                         // extension key (PPO_HostEnv, PPO_HostEnvBox), likewise
         B("environment", "matrix_cores", m_matrix_cores);                 // extension key (PPO_HostEnv, PPO_HostEnvBox), likewise
-        if (m_env_kind == PPO_ENV_CARTPOLE || m_env_kind == PPO_ENV_MOUNTAINCAR) {   // extension key (PPO_Discrete, PPO_MultiDiscrete), likewise
+        // extension key (PPO_Discrete, PPO_MultiDiscrete: the generic engine; PPO_HostEnv, PPO_HostEnvBox: the width of the context's own engine -- 128 beside
+        // matrix_cores and the family key runs the fused 2 x 128 kernels), likewise
+        if (m_env_kind == PPO_ENV_CARTPOLE || m_env_kind == PPO_ENV_MOUNTAINCAR || m_env_kind == PPO_ENV_HOST) {
             I("network", "hidden_size", m_hidden_size);
             m_hidden_size_given = cfg.integer("network", "hidden_size").has_value();
         }
@@ -166,7 +168,7 @@ void PPOAlgorithm::construct() {
     if (m_matrix_cores) c.kernel_flags |= fused_device_env ? PPO_KERNEL_ENV_MATRIX : PPO_KERNEL_FUSED_MATRIX;
     if (m_keep_cut_states) c.kernel_flags |= PPO_KERNEL_ENV_CUT_STATE;   // a class whose env is no fused device env: the library's refusal is thrown below, with its message
     if (m_env_norm_reward) c.kernel_flags |= PPO_KERNEL_ENV_REWARD_NORM;   // set by the fused device-env classes alone (normRewardOnDeviceEnv): ppo_reward_norm_* on the one-launch rollout
-    if (m_hidden_size_given) c.kernel_flags |= PPO_KERNEL_ENV_GENERIC;   // CartPole / MountainCar on the generic engine, also at hidden_size = 64; a width out of range is the library's refusal
+    if (m_hidden_size_given && m_env_kind != PPO_ENV_HOST) c.kernel_flags |= PPO_KERNEL_ENV_GENERIC;   // CartPole / MountainCar on the generic engine, also at hidden_size = 64; a width out of range is the library's refusal
     ppo::check(ppo_ctx_create(&c, &m_ctx), nullptr, "PPO");    // obs-size mismatch surfaces here with the reference's message (:370-375)
     ppo::check(ppo_params_init_orthogonal(m_ctx, m_seed), m_ctx, "agent init");
     // update + apply, clip 10, eps 1e-8, as PPO_HostEnv::setNormReward; in front of the resume, which sets a checkpoint's statistics

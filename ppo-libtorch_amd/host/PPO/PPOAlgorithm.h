@@ -118,8 +118,11 @@ class PPOAlgorithm {
     // episode off in, and bootstrap_truncated is served on every one of them; on any other class the library refuses the context
     bool m_keep_cut_states = false;
     bool m_bootstrap_truncated = false;  // extension ([environment] bootstrap_truncated): bootstrap the value where a time limit cut an episode off (every algorithm class; set it with setBootstrapTruncated)
-    // extension ([network] hidden_size = H; PPO_Discrete and PPO_MultiDiscrete only): the two hidden layers are H wide and the context runs on the generic engine
-    // (PPO_KERNEL_ENV_GENERIC).  Absent: 64, no flag, the reference-shape kernels, nothing printed.  Depth other than 2 and bf16 storage stay with the C-ABI and
+    // extension ([network] hidden_size = H): the two hidden layers are H wide.  PPO_Discrete and PPO_MultiDiscrete: the context runs on the generic engine
+    // (PPO_KERNEL_ENV_GENERIC).  Every class on a caller-stepped context (env_kind = PPO_ENV_HOST: PPO_HostEnv, PPO_HostEnvBox and what derives from them):
+    // the key sets the width of the context's own engine and no flag -- the generic engine without a family key (a file that carried the key there, ignored
+    // until now, changes width), the fused 2 x 128 kernels beside matrix_cores and the family key; a width the context cannot serve is the library's refusal,
+    // thrown at construction.  Absent: 64, no flag, the reference-shape kernels, nothing printed.  Depth other than 2 and bf16 storage stay with the C-ABI and
     // the Python binding: the reference's archive has names for two hidden layers only (TorchArchive.h), so a checkpoint of another depth could not be written
     int64_t m_hidden_size = 64;
     bool m_hidden_size_given = false;
