@@ -331,6 +331,7 @@ typedef struct ppo_config {
     int64_t global_num_envs;    /* 0 or num_envs when not sharded */
     float learning_rate, gamma, gae_lambda, clip_coef, ent_coef, vf_coef, max_grad_norm;
     int32_t compute_dtype;      /* PPO_DTYPE_*: arithmetic of the layer GEMMs of a PPO_ENV_SYNTHETIC network; the 2 x 64 paths are always f32 */
+                                /* ... except beside PPO_KERNEL_FUSED_MATRIX on PPO_ENV_HOST, where PPO_DTYPE_BF16 runs that flag's bf16 kernels at hidden 64 and 128 (its text) */
     int32_t kernel_flags;       /* PPO_KERNEL_* (0 = the defaults): which hand-written kernel runs a stage, for A/B runs and for bit-exact replays */
 } ppo_config;
 
@@ -518,7 +519,13 @@ enum { PPO_KERNEL_ROLLOUT_VECTOR = 1, PPO_KERNEL_UPDATE_VECTOR = 2, PPO_KERNEL_U
  * registers (W2 does not fit in LDS beside the images), dW1 and dW2 summed per tile and accumulated in the workgroup's own slab.  LDS: 131 200 bytes at 32
  * outputs, 109 248 for the critic (+ 1 056 in the fold).  Any other width beside the flag is PPO_ERR_UNSUPPORTED with a message naming the flag and the two
  * widths; hidden = 256 is not built: two [256][68] f32 images and the two X chunk buffers are 174 080 bytes against 163 840 bytes of LDS, before any weight.
- * The device envs (PPO_KERNEL_ENV_MATRIX) stay at 2 x 64. */
+ * The device envs (PPO_KERNEL_ENV_MATRIX) stay at 2 x 64.
+ * compute_dtype = PPO_DTYPE_BF16 beside this flag (env_kind = PPO_ENV_HOST, exactly one family flag, n_hidden = 2, hidden 64 or 128, the family's observation
+ * and output limits): the same launches, counters and entry-point guarantee on kernels_fused_matrix_bf16.hip, v_mfma_f32_16x16x32_bf16 with bf16 operands
+ * rounded to nearest even and f32 accumulation from the f32 bias: x, W1, W2, tanh(z1), tanh(z2), dz2 and dz1 are rounded where they enter a product; layer 3,
+ * the heads, the loss, dW3, db3, dz2 and the bias gradients are f32.  Parameters, gradients, checkpoints, ppo_get_params / ppo_set_params, the optimizer and
+ * the normalisers are f32 as on every context; the weights are converted in registers at every fetch, nothing is prepared or cached.  Refused as before: bf16
+ * under a family flag without this one, on a device env (also beside PPO_KERNEL_ENV_MATRIX), and at any hidden other than 64 and 128. */
 #define PPO_KERNEL_FUSED_MATRIX (1 << 16)
 /* PPO_KERNEL_ENV_MATRIX (131072; bits 11, 12 and 14 stay unassigned and are refused as unknown, as is bit 18): PPO_KERNEL_FUSED_MATRIX's forward for the seven
  * fused device envs (PPO_ENV_PENDULUM, PPO_ENV_MOUNTAINCAR_CONTINUOUS, PPO_ENV_ACROBOT, PPO_ENV_TAXI, PPO_ENV_FROZENLAKE, PPO_ENV_FROZENLAKE8X8,

@@ -790,7 +790,10 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
     if (gauss && !host_env && !gauss_env)
         return fail(nullptr, PPO_ERR_UNSUPPORTED, "dist_kind = PPO_DIST_GAUSSIAN serves caller-stepped environments (env_kind = PPO_ENV_HOST), %s: CartPole, MountainCar "
                     "and the synthetic env take discrete actions; got env_kind %d", fused_env_names(FUSED_GAUSS), cfg->env_kind);
-    if (gauss && cfg->compute_dtype != PPO_DTYPE_F32)
+    // bf16 operands exist for the fused matrix families alone (kernels_fused_matrix_bf16.hip): PPO_KERNEL_FUSED_MATRIX beside the policy's own family flag, which
+    // the flag's block above has held to env_kind = PPO_ENV_HOST and to exactly one family flag; every other bf16 request is answered as before
+    const bool fused_bf16 = fused_matrix && cfg->compute_dtype == PPO_DTYPE_BF16;
+    if (gauss && cfg->compute_dtype != PPO_DTYPE_F32 && !(fused_bf16 && (cfg->kernel_flags & PPO_KERNEL_GAUSS_FUSED)))
         return fail(nullptr, PPO_ERR_UNSUPPORTED, "dist_kind = PPO_DIST_GAUSSIAN is built for compute_dtype = PPO_DTYPE_F32; bf16 storage is not");
     if (gauss && cfg->n_heads != 1)
         return fail(nullptr, PPO_ERR_UNSUPPORTED, "dist_kind = PPO_DIST_GAUSSIAN takes n_heads = 1 with head_dims[0] = the action dimension D; got n_heads = %d", cfg->n_heads);
@@ -808,11 +811,12 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
         if (fused_matrix && !fused_matrix_serves_hidden(cfg->hidden))
             return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED beside PPO_KERNEL_FUSED_MATRIX is built for hidden = 64 and hidden = %d; got hidden = %d "
                         "(hidden = 256 needs two [256][68] f32 images and two X chunk buffers, 174080 bytes against %d bytes of LDS per workgroup, before "
-                        "any weight: it is not built)", FUSED_MATRIX_WIDE_HIDDEN, cfg->hidden, 160 * 1024);
+                        "any weight: it is not built%s)", FUSED_MATRIX_WIDE_HIDDEN, cfg->hidden, 160 * 1024,
+                        fused_bf16 ? "; at compute_dtype = PPO_DTYPE_BF16 the kernel set is instantiated for 64 and 128 only" : "");
         if (!fused_matrix && cfg->hidden != 64)
             return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED is built for hidden = 64; got hidden = %d", cfg->hidden);
         if (cfg->n_hidden != 2) return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED is built for n_hidden = 2; got n_hidden = %d", cfg->n_hidden);
-        if (cfg->compute_dtype != PPO_DTYPE_F32)
+        if (cfg->compute_dtype != PPO_DTYPE_F32 && !fused_bf16)
             return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED is built for compute_dtype = PPO_DTYPE_F32; bf16 storage is not");
         if (cfg->obs_size < 1 || cfg->obs_size > fused_max_obs)
             return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_CAT_FUSED is built for 1 <= obs_size <= %d; got obs_size = %d", fused_max_obs, cfg->obs_size);
@@ -843,7 +847,8 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
         if (fused_matrix && !fused_matrix_serves_hidden(cfg->hidden))
             return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_GAUSS_FUSED beside PPO_KERNEL_FUSED_MATRIX is built for hidden = 64 and hidden = %d; got hidden = %d "
                         "(hidden = 256 needs two [256][68] f32 images and two X chunk buffers, 174080 bytes against %d bytes of LDS per workgroup, before "
-                        "any weight: it is not built)", FUSED_MATRIX_WIDE_HIDDEN, cfg->hidden, 160 * 1024);
+                        "any weight: it is not built%s)", FUSED_MATRIX_WIDE_HIDDEN, cfg->hidden, 160 * 1024,
+                        fused_bf16 ? "; at compute_dtype = PPO_DTYPE_BF16 the kernel set is instantiated for 64 and 128 only" : "");
         if (!fused_matrix && cfg->hidden != 64)
             return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_GAUSS_FUSED is built for hidden = 64; got hidden = %d", cfg->hidden);
         if (cfg->n_hidden != 2) return fail(nullptr, PPO_ERR_UNSUPPORTED, "PPO_KERNEL_GAUSS_FUSED is built for n_hidden = 2; got n_hidden = %d", cfg->n_hidden);
@@ -877,6 +882,7 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
         c->gen->L = make_gen_layout(cfg->obs_size, cfg->hidden, cfg->n_hidden, cfg->n_heads, cfg->head_dims, gauss);
         c->gen->L.fused_matrix = fused_matrix || env_matrix;   // a flagged device env's act, critic and update launches are kernels_fused_matrix.hip's
         c->gen->L.env_matrix = env_matrix;
+        c->gen->L.fused_bf16 = fused_bf16;   // the fused launchers pick kernels_fused_matrix_bf16.hip; the generic engine's bf16 storage is not built for it
         // the shared code sizes the flat parameter / gradient / moment buffers from L.P; the 2 x 64 offsets in L are not used
         c->L.P = c->gen->L.P;
         c->L.n_tensors = c->gen->L.n_tensors;
@@ -991,7 +997,7 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
         const GenLayout& GL = g.L;
         g.rows_max = (std::max<int64_t>(c->MB, c->N) + 127) / 128 * 128;
         const size_t R = (size_t)g.rows_max;
-        g.bf16 = cfg->compute_dtype == PPO_DTYPE_BF16;
+        g.bf16 = cfg->compute_dtype == PPO_DTYPE_BF16 && !fused_bf16;
         if (g.bf16) {
             // every bf16 buffer: 128 extra rows (the unguarded staging prefetches up to three chunks past the last one it uses), pitches padded
             // to 128 columns, zero-filled once -- nothing ever writes the padding
@@ -1063,7 +1069,7 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
                     off += 3ll * g.wp_npad[net][l] * g.wp_kpad[l];
                 }
             CK(dalloc(c, &g.wplanes, (size_t)off + 128 * 256));   // + slack for the staging's prefetch past the last chunk
-            if (cfg->compute_dtype == PPO_DTYPE_BF16) CK(dalloc(c, &g.wfrags, (size_t)off + 128 * 256));
+            if (g.bf16) CK(dalloc(c, &g.wfrags, (size_t)off + 128 * 256));
             g.planes_dirty = true;
         }
         CK(dalloc(c, &g.act64, N * GL.n_heads));
@@ -1089,7 +1095,7 @@ extern "C" ppo_status ppo_ctx_create(const ppo_config* cfg, ppo_ctx** out) {
         CK(hipDeviceSynchronize());
         CK(gen_fill(g.row_f[4] + 2, (int64_t)R, 1.0f, c->stream));   // the ones vector of the bias-gradient gemv
         // arithmetic of the layer products (kernels_gemm.hip): fp32 carried as three bf16 terms, or plain bf16 operands (configs[4])
-        g.gemm_prec = cfg->compute_dtype == PPO_DTYPE_BF16 ? PPO_MM_BF16 : PPO_MM_F32X3;
+        g.gemm_prec = g.bf16 ? PPO_MM_BF16 : PPO_MM_F32X3;
     }
 #undef CK
     // every env can reset at most once per step: steps per env over the whole run bounds the shared reset stream

@@ -86,6 +86,19 @@ hipError_t fused_matrix_h128_values(const GenLayout& L, const float* params, con
 hipError_t fused_matrix_h128_dev_fold(const GenLayout& L, const float* params, const DevFoldArgs& a, hipStream_t s);
 hipError_t fused_matrix_h128_fwd_bwd(const GenLayout& L, const GfUpdArgs& a, float* grads, hipStream_t s);   // the policy's kind is a.hp.dist_kind
 
+// ---- PPO_KERNEL_FUSED_MATRIX at compute_dtype = PPO_DTYPE_BF16 (kernels_fused_matrix_bf16.hip): the same five launches at hidden = 64 and 128 with bf16
+// operands on v_mfma_f32_16x16x32_bf16 (f32 accumulation, f32 parameters and gradients; weights converted in registers at every fetch).  The six launchers
+// above hand a layout with L.fused_matrix and L.fused_bf16 set to these, in front of the width test and argument for argument; nobody else calls them.
+// ppo_ctx_create sets L.fused_bf16 only for env_kind = PPO_ENV_HOST under the flag beside one family flag. ----
+hipError_t fused_matrix_bf16_gauss_act(const GenLayout& L, const float* params, const float* obs, const float* forced, int64_t n, int64_t seed, int64_t row_offset,
+                                       int64_t step_index, bool greedy, float* action, float* logprob, float* entropy, const GaussStepStores* st, hipStream_t s);
+hipError_t fused_matrix_bf16_cat_act(const GenLayout& L, int dist_kind, const float* params, const float* obs, const uint8_t* mask, const int64_t* forced, int64_t n,
+                                     int64_t seed, int64_t row_offset, int64_t step_index, bool greedy, int64_t* action, float* logprob, float* entropy,
+                                     const CatStepStores* st, hipStream_t s);
+hipError_t fused_matrix_bf16_values(const GenLayout& L, const float* params, const float* obs, int64_t n, float* value, hipStream_t s);
+hipError_t fused_matrix_bf16_dev_fold(const GenLayout& L, const float* params, const DevFoldArgs& a, hipStream_t s);
+hipError_t fused_matrix_bf16_fwd_bwd(const GenLayout& L, const GfUpdArgs& a, float* grads, hipStream_t s);   // the policy's kind is a.hp.dist_kind
+
 // ---- The device envs of the two fused families.  An env is a trait in ppo_internal.hpp (GaussEnv*: one real-valued action; CatEnv*: one head of integer
 // actions), one line of its family's dispatcher and one row of the table in kernels_gauss_fused.hip; everything the C-ABI layer knows about an env it reads
 // from the row.  The numbers of a row come from the trait. ----

@@ -29,6 +29,7 @@ struct GenLayout {
     int logstd_off;                        // ... and the offset of log_std [D], the last tensor (behind the actor's layers)
     int fused_matrix;                      // PPO_KERNEL_FUSED_MATRIX (set by ppo_ctx_create behind make_gen_layout): the fused launchers pick kernels_fused_matrix.hip
     int env_matrix;                        // PPO_KERNEL_ENV_MATRIX (likewise; fused_matrix is set with it): the device env's rollout and evaluation pick kernels_env_matrix.hip
+    int fused_bf16;                        // PPO_KERNEL_FUSED_MATRIX at compute_dtype = PPO_DTYPE_BF16 on PPO_ENV_HOST (likewise): the fused launchers pick kernels_fused_matrix_bf16.hip
 };
 
 inline GenLayout make_gen_layout(int obs, int hidden, int n_hidden, int n_heads, const int* head_dims, bool gauss = false) {

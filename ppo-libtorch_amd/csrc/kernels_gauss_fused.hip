@@ -1056,6 +1056,7 @@ hipError_t gauss_fused_slab_reduce(const GenLayout& L, const float* slab, int sl
 hipError_t gauss_fused_act(const GenLayout& L, const float* params, const float* obs, const float* forced, int64_t n, int64_t seed, int64_t row_offset,
                            int64_t step_index, bool greedy, float* action, float* logprob, float* entropy, const GaussStepStores* st, hipStream_t s) {
     if (n <= 0) return hipSuccess;
+    if (L.fused_matrix && L.fused_bf16) return fused_matrix_bf16_gauss_act(L, params, obs, forced, n, seed, row_offset, step_index, greedy, action, logprob, entropy, st, s);
     if (L.fused_matrix && L.hidden == FUSED_MATRIX_WIDE_HIDDEN) return fused_matrix_h128_gauss_act(L, params, obs, forced, n, seed, row_offset, step_index, greedy, action, logprob, entropy, st, s);
     if (L.fused_matrix) return fused_matrix_gauss_act(L, params, obs, forced, n, seed, row_offset, step_index, greedy, action, logprob, entropy, st, s);
     if (L.obs > GAUSS_FUSED_MAX_OBS) return fused_wide_gauss_act(L, params, obs, forced, n, seed, row_offset, step_index, greedy, action, logprob, entropy, st, s);
@@ -1080,6 +1081,7 @@ hipError_t gauss_fused_act(const GenLayout& L, const float* params, const float*
 
 hipError_t gauss_fused_values(const GenLayout& L, const float* params, const float* obs, int64_t n, float* value, hipStream_t s) {
     if (n <= 0) return hipSuccess;
+    if (L.fused_matrix && L.fused_bf16) return fused_matrix_bf16_values(L, params, obs, n, value, s);
     if (L.fused_matrix && L.hidden == FUSED_MATRIX_WIDE_HIDDEN) return fused_matrix_h128_values(L, params, obs, n, value, s);
     if (L.fused_matrix) return fused_matrix_values(L, params, obs, n, value, s);
     if (L.obs > GAUSS_FUSED_MAX_OBS) return fused_wide_values(L, params, obs, n, value, s);
@@ -1095,6 +1097,7 @@ hipError_t gauss_fused_values(const GenLayout& L, const float* params, const flo
 
 hipError_t gauss_fused_dev_fold(const GenLayout& L, const float* params, const DevFoldArgs& a, hipStream_t s) {
     if (a.N <= 0) return hipSuccess;
+    if (L.fused_matrix && L.fused_bf16) return fused_matrix_bf16_dev_fold(L, params, a, s);
     if (L.fused_matrix && L.hidden == FUSED_MATRIX_WIDE_HIDDEN) return fused_matrix_h128_dev_fold(L, params, a, s);
     if (L.fused_matrix) return fused_matrix_dev_fold(L, params, a, s);
     if (L.obs > GAUSS_FUSED_MAX_OBS) return fused_wide_dev_fold(L, params, a, s);
@@ -1114,6 +1117,7 @@ hipError_t gauss_fused_fwd_bwd(const GenLayout& L, const LossParams& hp, const f
                                const AdvStat* adv_stat, float* slab, double* loss_part, float* grads, hipStream_t s) {
     if (M < 1 || M >= (1ll << 31) - 64 || !slab || !loss_part) return hipErrorInvalidValue;
     const GfUpdArgs a = gf_upd_args(L, hp, params, obs, actions, nullptr, oldlp, adv, ret, oldv, idx, M, inv_global_M, global_M, adv_stat, slab, loss_part);
+    if (L.fused_matrix && L.fused_bf16) return fused_matrix_bf16_fwd_bwd(L, a, grads, s);
     if (L.fused_matrix && L.hidden == FUSED_MATRIX_WIDE_HIDDEN) return fused_matrix_h128_fwd_bwd(L, a, grads, s);
     if (L.fused_matrix) return fused_matrix_fwd_bwd(L, a, grads, s);
     if (L.obs > GAUSS_FUSED_MAX_OBS) return fused_wide_fwd_bwd(L, a, grads, s);
@@ -1144,6 +1148,7 @@ hipError_t cat_fused_act(const GenLayout& L, int dist_kind, const float* params,
                          int64_t row_offset, int64_t step_index, bool greedy, int64_t* action, float* logprob, float* entropy, const CatStepStores* st, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     if (L.gauss || (dist_kind != PPO_DIST_CATEGORICAL && dist_kind != PPO_DIST_MASKED)) return hipErrorInvalidValue;
+    if (L.fused_matrix && L.fused_bf16) return fused_matrix_bf16_cat_act(L, dist_kind, params, obs, mask, forced, n, seed, row_offset, step_index, greedy, action, logprob, entropy, st, s);
     if (L.fused_matrix && L.hidden == FUSED_MATRIX_WIDE_HIDDEN) return fused_matrix_h128_cat_act(L, dist_kind, params, obs, mask, forced, n, seed, row_offset, step_index, greedy, action, logprob, entropy, st, s);
     if (L.fused_matrix) return fused_matrix_cat_act(L, dist_kind, params, obs, mask, forced, n, seed, row_offset, step_index, greedy, action, logprob, entropy, st, s);
     if (L.obs > GAUSS_FUSED_MAX_OBS)
@@ -1168,6 +1173,7 @@ hipError_t cat_fused_fwd_bwd(const GenLayout& L, const LossParams& hp, const flo
     if (hp.dist_kind != PPO_DIST_CATEGORICAL && hp.dist_kind != PPO_DIST_MASKED) return hipErrorInvalidValue;
     const GfUpdArgs a = gf_upd_args(L, hp, params, obs, reinterpret_cast<const float*>(actions), hp.dist_kind == PPO_DIST_MASKED ? masks : nullptr, oldlp, adv, ret, oldv,
                                     idx, M, inv_global_M, global_M, adv_stat, slab, loss_part);
+    if (L.fused_matrix && L.fused_bf16) return fused_matrix_bf16_fwd_bwd(L, a, grads, s);
     if (L.fused_matrix && L.hidden == FUSED_MATRIX_WIDE_HIDDEN) return fused_matrix_h128_fwd_bwd(L, a, grads, s);
     if (L.fused_matrix) return fused_matrix_fwd_bwd(L, a, grads, s);
     if (L.obs > GAUSS_FUSED_MAX_OBS) return fused_wide_fwd_bwd(L, a, grads, s);

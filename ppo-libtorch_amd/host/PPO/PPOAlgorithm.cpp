@@ -87,6 +87,9 @@ void PPOAlgorithm::getArgs() {
             I("network", "hidden_size", m_hidden_size);
             m_hidden_size_given = cfg.integer("network", "hidden_size").has_value();
         }
+        // extension key (PPO_HostEnv, PPO_HostEnvBox beside matrix_cores and the family key: bf16 operands on the fused matrix kernels, compute_dtype =
+        // PPO_DTYPE_BF16; the parameters, checkpoints and the optimizer stay f32); a context the library does not build for that dtype is its refusal
+        B("network", "bf16", m_bf16);
         I("general", "seed", m_seed);
         I("general", "total_timesteps", m_total_timesteps);
         B("general", "use_cuda", m_use_cuda);
@@ -169,6 +172,7 @@ void PPOAlgorithm::construct() {
     if (m_keep_cut_states) c.kernel_flags |= PPO_KERNEL_ENV_CUT_STATE;   // a class whose env is no fused device env: the library's refusal is thrown below, with its message
     if (m_env_norm_reward) c.kernel_flags |= PPO_KERNEL_ENV_REWARD_NORM;   // set by the fused device-env classes alone (normRewardOnDeviceEnv): ppo_reward_norm_* on the one-launch rollout
     if (m_hidden_size_given && m_env_kind != PPO_ENV_HOST) c.kernel_flags |= PPO_KERNEL_ENV_GENERIC;   // CartPole / MountainCar on the generic engine, also at hidden_size = 64; a width out of range is the library's refusal
+    if (m_bf16) c.compute_dtype = PPO_DTYPE_BF16;   // served beside PPO_KERNEL_FUSED_MATRIX and a family flag on a caller-stepped context; elsewhere the library's refusal is thrown below
     ppo::check(ppo_ctx_create(&c, &m_ctx), nullptr, "PPO");    // obs-size mismatch surfaces here with the reference's message (:370-375)
     ppo::check(ppo_params_init_orthogonal(m_ctx, m_seed), m_ctx, "agent init");
     // update + apply, clip 10, eps 1e-8, as PPO_HostEnv::setNormReward; in front of the resume, which sets a checkpoint's statistics

@@ -125,6 +125,10 @@ class PPOAlgorithm {
     // thrown at construction.  Absent: 64, no flag, the reference-shape kernels, nothing printed.  Depth other than 2 and bf16 storage stay with the C-ABI and
     // the Python binding: the reference's archive has names for two hidden layers only (TorchArchive.h), so a checkpoint of another depth could not be written
     int64_t m_hidden_size = 64;
+    // extension ([network] bf16 = true; PPO_HostEnv with fused_categorical, PPO_HostEnvBox with fused_policy, beside matrix_cores, at hidden_size 64 or 128):
+    // compute_dtype = PPO_DTYPE_BF16, the fused matrix kernels with bf16 operands and f32 accumulation; parameters, checkpoints and the optimizer stay f32.
+    // On any other class, or without matrix_cores beside a family key, the library refuses the context
+    bool m_bf16 = false;
     bool m_hidden_size_given = false;
     float m_target_kl = 0.0f;            // extension ([ppo] target_kl): stop an update's optimizer steps once an epoch's last approx_kl exceeds it (ppo_target_kl_set); absent or 0: off
 

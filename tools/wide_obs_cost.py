@@ -25,11 +25,11 @@ N, T = 4096, 8
 SHAPES = (("obs 105, D 8 Gaussian", 105, (8,), "gauss"), ("obs 376, D 17 Gaussian", 376, (17,), "gauss"), ("obs 100, heads (5, 3, 4) masked", 100, (5, 3, 4), "masked"))
 
 
-def make(P, obs, heads, kind, flags, nmb, hidden=64):
+def make(P, obs, heads, kind, flags, nmb, hidden=64, compute_dtype=0):
     gauss = kind == "gauss"
     ctx = P.Context(P.make_config(env_kind=P.ENV_HOST, dist_kind=P.DIST_GAUSSIAN if gauss else P.DIST_MASKED, obs_size=obs, head_dims=heads, hidden=hidden, n_hidden=2,
                                   num_envs=N, num_steps=T, num_minibatches=nmb, update_epochs=1, seed=3, total_timesteps=1 << 40, learning_rate=1e-4,
-                                  anneal_lr=False, max_episode_steps=1000, kernel_flags=flags))
+                                  anneal_lr=False, max_episode_steps=1000, kernel_flags=flags, compute_dtype=compute_dtype))
     ctx.init_orthogonal(3)
     rng = np.random.default_rng(obs)
     dev = dict(act=ctx.empty((N, heads[0]), np.float32) if gauss else ctx.empty((N, len(heads)), np.int64),
